@@ -8,6 +8,7 @@ synthesis).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--model default|little]
                   [--nn mfma|vector] [--repeats R] [--host-io] [--s16] [--frames-per-call F]
+                  [--dump-outputs DIR]
 
 Workload at N=1: BASELINE.json configs[2] -- 65,536 concurrent streams on one MI355X (the largest
 single-GPU configuration), default architecture, int8 model, network recast as batched MFMA
@@ -19,10 +20,18 @@ collectives are the barriers and the max-over-ranks of the elapsed times.
 `python bench.py --gpus N` may be started directly (it re-executes itself under
 torch.distributed.run, one rank per GPU) or under a launcher that already set RANK / WORLD_SIZE.
 
-Timing: W untimed warm-up steps, then R repetitions (default 25) of EXACTLY K steps, each
-bracketed by barrier + synchronize on both sides; every repetition's time is the MAX over
-ranks; `value` is the median repetition (min / max are reported beside it) and
-`ms_per_step x steps` is that repetition.
+Timing: W untimed warm-up steps, then EXACTLY K timed steps, split into R consecutive
+repetitions (default 1; sizes differ by at most one step), each bracketed by barrier +
+synchronize on both sides; every repetition's time is the MAX over ranks; `ms_per_step` is
+the median over repetitions of a repetition's time per step, `value` is the frames of one
+step over it (min / max are reported beside it).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to
+its caller as float32 .npy files -- pcm_out (S, 480), vad (S,), gains (S, 32) (not on the
+host-fed path, which returns none) -- and the global ids of those S streams as stream_id
+(S,) float64.  S is every stream of the rank, or a fixed, seeded sample of them when all
+would exceed DUMP_MAX_BYTES.  The inputs depend only on the arguments, so two builds run
+with the same arguments can be compared file for file.
 
 The model is the synthetic default-architecture blob produced by the reference's own
 exporter (the trained weights are a separate download upstream; tests/golden/make_golden.py).
@@ -203,6 +212,39 @@ def synth_pcm_torch(torch, n_streams: int, n_frames: int, device, seed_base: int
         x = torch.clamp(torch.round(6000.0 * h + 1500.0 * nz), -32768, 32767)
         out[:, s0:s0 + chunk] = x.reshape(ids.shape[0], n_frames, FRAME).permute(1, 0, 2)
     return out
+
+
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 20250223
+
+
+def dump_sample(n_streams: int, bytes_per_stream: int, n_files: int):
+    """Stream indices (sorted numpy int64) whose outputs --dump-outputs writes: all of them when they fit in DUMP_MAX_BYTES,
+    otherwise a fixed, seeded sample of as many as fit (the same for the same n_streams in every run and every build)."""
+    import numpy as np
+    keep = (DUMP_MAX_BYTES - 256 * n_files) // bytes_per_stream
+    if n_streams <= keep:
+        return np.arange(n_streams, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_streams, keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(directory: str, arrays: dict, first_stream: int, torch) -> dict:
+    """Write {name: (N, ...) tensor of one step} as DIR/<name>.npy (float32) for the streams of dump_sample, plus their
+    global ids as DIR/stream_id.npy (float64).  Returns what was written, for the JSON line."""
+    import numpy as np
+    n = next(iter(arrays.values())).shape[0]
+    per_stream = 8 + sum(4 * int(math.prod(t.shape[1:])) for t in arrays.values())
+    idx = dump_sample(n, per_stream, len(arrays) + 1)
+    os.makedirs(directory, exist_ok=True)
+    files = {}
+    for name, t in arrays.items():
+        sel = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        files[name] = sel.to(torch.float32).cpu().numpy()
+    files["stream_id"] = (idx + first_stream).astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+    return {"dir": directory, "files": {name: list(a.shape) for name, a in files.items()}, "streams": int(len(idx)),
+            "sampled": bool(len(idx) < n), "seed": DUMP_SEED if len(idx) < n else None}
 
 
 def pmc_record(kernel: str, n_streams: int, model: str = "default"):
@@ -557,33 +599,46 @@ def bench_rank(a) -> dict | None:
     run(0, Wm)
     barrier()
     batch.enable_timing(True)
+    # exactly K timed steps, in R consecutive repetitions whose sizes differ by at most one step
+    sizes = [K // R + (1 if r < K % R else 0) for r in range(R)]
     times = []
-    for r in range(R):
+    f = Wm
+    for n in sizes:
         barrier()
         t0 = time.perf_counter()
-        run(Wm + r * K, K)
+        run(f, n)
         barrier()
         times.append(time.perf_counter() - t0)
+        f += n
     if os.environ.get("BENCH_TRACE"):
         print("[bench] timed region done", file=sys.stderr, flush=True)
     kms = batch.kernel_ms()
     if os.environ.get("BENCH_TRACE"):
         print("[bench] kernel_ms read", file=sys.stderr, flush=True)
+    dumped = None
+    if a.dump_outputs and rank == 0 and not stub:
+        k = (f - 1) % cap  # the input slot, and so the output slot, of the last timed step
+        outs = {"pcm_out": (h_out if a.host_io else d_out)[k], "vad": (h_vad if a.host_io else d_vad)[k]}
+        if not a.host_io:
+            outs["gains"] = d_gains[k]
+        dumped = dump_outputs(a.dump_outputs, outs, mine.start, torch)
+        dumped["frame"] = f - 1
     # the same K steps once more with every kernel on ONE stream: stand-alone kernel durations (in the pipelined schedule
     # the kernels of neighbouring frames share the machine, which stretches each one's own duration)
     kms_alone = None
     if not stub and not a.host_io:
         old = batch.set_schedule(9)
-        run(Wm + R * K, K)
+        run(f, K)
         sync()
         batch.kernel_ms()
-        run(Wm + (R + 1) * K, K)
+        run(f + K, K)
         sync()
         kms_alone = batch.kernel_ms()
         batch.set_schedule(old)
     batch.enable_timing(False)
-    own_median = statistics.median(times)
+    own_median = statistics.median(t / n for t, n in zip(times, sizes))
     times = aggregate_times(times, dist, red_dev, group=data_group)  # element-wise MAX over ranks: the one data-path collective
+    times = [t / n for t, n in zip(times, sizes)]                   # seconds per step of each repetition
     shards, rank_medians = [[mine.start, mine.stop]], [own_median]
     if dist:  # (object gathers ride on the gloo control group)
         shards, rank_medians = [None] * world, [None] * world
@@ -596,8 +651,8 @@ def bench_rank(a) -> dict | None:
     if dist:
         devices = [None] * world
         dist.all_gather_object(devices, report)
-    frames_per_rep = float(N * K * world)
-    med = statistics.median(times)
+    frames_per_step = float(N * world)
+    med = statistics.median(times)  # seconds per step
     line = None
     if rank == 0:
         sane = True
@@ -619,14 +674,14 @@ def bench_rank(a) -> dict | None:
         traffic = int(pmc["hbm_bytes_per_frame"] * N) if "hbm_bytes_per_frame" in pmc else None
         line = {
             "metric": METRIC if not stub else "LAUNCHER SELF-TEST (stub batch, no GPU work)",
-            "value": round(frames_per_rep / med, 1), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
-            "ms_per_step": round(1e3 * med / K, 4), "higher_is_better": True, "scaling": "weak",
+            "value": round(frames_per_step / med, 1), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
+            "ms_per_step": round(1e3 * med, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "int8 weights x u8 activations (i32 accumulate) + f32/f64 DSP",
             "data": "synthetic" + (", fed from and returned to pinned host memory over PCIe inside the timed region" if a.host_io else ""),
-            "value_min": round(frames_per_rep / max(times), 1), "value_max": round(frames_per_rep / min(times), 1),
-            "repeats": R,
-            # each rank's own rate (its frames / the median of ITS repetition times): the aggregate is paced by the slowest
-            "value_by_rank": [round(N * K / t, 1) for t in rank_medians],
+            "value_min": round(frames_per_step / max(times), 1), "value_max": round(frames_per_step / min(times), 1),
+            "repeats": R, "steps_by_repeat": sizes,
+            # each rank's own rate (its frames per step / the median of ITS repetitions' times per step): the aggregate is paced by the slowest
+            "value_by_rank": [round(N / t, 1) for t in rank_medians],
             "config": {"workload": workload_name(a, N), "streams_per_gpu": N, "frames_per_step": N * world,
                        "nn_path": a.nn, "model": a.model, "outputs_sane": sane,
                        "stream_ids_rank0": [mine.start, mine.stop], "stream_ids_by_rank": shards},
@@ -639,10 +694,10 @@ def bench_rank(a) -> dict | None:
                                  "the launches of a kind; overlapping kernels of neighbouring frames stretch each other's durations); "
                                  "it is LDS/issue-bound, not HBM-bound: see roofline_lds and roofline_valu"},
             # whole step against HBM: mandatory bytes of all four kernels / step time
-            "roofline_step": {"bound": "hbm", "achieved": round(sum(per_launch.values()) / (med / K) / 1e9, 2),
-                              "unit": "GB/s", "frac": round(sum(per_launch.values()) / (med / K) / HBM_PEAK, 5),
+            "roofline_step": {"bound": "hbm", "achieved": round(sum(per_launch.values()) / med / 1e9, 2),
+                              "unit": "GB/s", "frac": round(sum(per_launch.values()) / med / HBM_PEAK, 5),
                               "algorithmic_bytes_per_step": sum(per_launch.values())},
-            "weight_roofline": {"W_bytes_per_frame": W, "frac": round(frames_per_rep / med * W / (world * HBM_PEAK), 5),
+            "weight_roofline": {"W_bytes_per_frame": W, "frac": round(frames_per_step / med * W / (world * HBM_PEAK), 5),
                                 "definition": "frames/s x W / (n_gpus x 8.0e12 B/s), north_star / SURVEY 8d; weights are "
                                               "L2-served, so this normalised figure may exceed 1"},
         }
@@ -701,7 +756,7 @@ def bench_rank(a) -> dict | None:
             vi = step_valu_issue_ms(N, a.model, a.nn)
             if vi and med > 0:
                 line["roofline_step_valu"] = {"bound": "valu-issue", "issue_bound_ms": round(vi, 4),
-                                              "frac": round(vi / (1e3 * med / K), 4),
+                                              "frac": round(vi / (1e3 * med), 4),
                                               "definition": "sum over the step's kernels of waves x VALU instructions per wave (PMC passes under "
                                                             "profiles/) x that kernel's mix-priced clocks per instruction (profiles/valu_mix.json, "
                                                             "profiles/r4_valu_issue.txt), over 1024 SIMDs at each kernel's measured clock, divided by ms_per_step"}
@@ -718,6 +773,8 @@ def bench_rank(a) -> dict | None:
             if mf:
                 line["mfma_utilisation"] = {"definition": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs) per launch, one-stream schedule",
                                             "kernels": mf}
+        if dumped:
+            line["dump_outputs"] = dumped
         line["devices_by_rank"] = devices
         buses = [d.get("pci_bus") for d in devices if d.get("pci_bus")]
         if len(buses) != len(set(buses)):
@@ -748,9 +805,10 @@ def bench_rank(a) -> dict | None:
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps: the timed region runs exactly this many")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=25, help="repetitions of the K-step timed region (median reported)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="consecutive repetitions the timed steps are split into (median time per step reported)")
     ap.add_argument("--streams", type=int, default=65536, help="concurrent streams PER GPU (configs[2]: 65536)")
     ap.add_argument("--model", choices=["default", "little"], default="default")
     ap.add_argument("--nn", choices=["vector", "mfma"], default=os.environ.get("RNNOISE_AMD_NN", "mfma"),
@@ -763,10 +821,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--smoke", action="store_true",
                     help="a two-step, one-repetition run of the same path (launcher, collectives, sharding, parity leg): what to run first on a new node")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (PCM, VAD, gains) as DIR/<name>.npy, at most 64 MB")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # launcher self-test on CPU (gloo)
     a = ap.parse_args(argv)
     if a.smoke:
         a.steps, a.warmup, a.repeats, a.no_cpu_baseline = 2, 1, 1, True
+    if a.steps < 1 or a.warmup < 0 or not 1 <= a.repeats <= a.steps:
+        ap.error("need --steps >= 1, --warmup >= 0 and 1 <= --repeats <= --steps")
     return a
 
 

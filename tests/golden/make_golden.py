@@ -14,6 +14,9 @@ running it.
   tests/golden/digest_default.npz-- 4 streams x 400 frames: vad, pitch, raw gains, CRC32 of PCM out
   tests/golden/edge_default.npz  -- loud noise / DC / impulses / gaps, 60 frames each
   tests/golden/digest_little.npz -- 2 streams x 200 frames on the sparser model
+  tests/golden/reference_pins.npz-- what tests/test_oracle.py's and tests/test_train_features.py's reference comparisons
+                                    read where oracle/_ref is not built: tables, FFT / pitch search, a free-running and a
+                                    teacher-forced stream, training features (`make_golden.py --pins [OUTDIR]` writes only it)
 
 The reference's tanh / sigmoid execute the generating CPU's `rcpps` (src/vec_avx.h:413,442), so a fixture belongs to one
 CPU family and says which ("rcp_profile", "host_cpu" entries).  The Intel build host writes tests/golden/*.npz; run on the
@@ -32,7 +35,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from oracle import binding  # noqa: E402
-from oracle.binding import RefHarness  # noqa: E402
+from oracle.binding import RefHarness, RefTrainHarness  # noqa: E402
 from rnnoise_amd import synth  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -65,15 +68,67 @@ def host_profile():
     return dict(rcp_profile=np.array(name), host_cpu=np.array(cpu))
 
 
+def train_case(stream, T, rng):
+    """tests/test_train_features.py: make_case"""
+    clean = synth.stream_pcm(stream, T).astype(np.float32).reshape(T, 480) * 0.5
+    noise = (rng.standard_normal((T, 480)) * (300 + 200 * stream)).astype(np.float32)
+    noisy = clean + noise
+    clean[10:14] = 0
+    noisy[10:14] = noise[10:14] * 1e-4
+    vad = (np.arange(T) % 3 != 0).astype(np.float32)
+    return clean, noisy, vad
+
+
+def reference_pins(gold, tag, blob):
+    """The inputs are those of the tests that read the file; they regenerate them, so only outputs are stored."""
+    d = {}
+    for k, v in zip(("window", "dct", "twiddles", "bitrev"), RefHarness.tables()):
+        d[f"tables_{k}"] = v
+    rng = np.random.default_rng(3)
+    for i in range(4):
+        x = (rng.standard_normal(1920) * 3000).astype(np.float32)
+        d[f"fft{i}"] = RefHarness.fft(x)
+        buf = (rng.standard_normal(1728) * 2000).astype(np.float32)
+        T, g, lp = RefHarness.pitch(buf, 200, 0.4)
+        d[f"pitch{i}_period"], d[f"pitch{i}_gain"], d[f"pitch{i}_x_lp"] = np.int32(T), np.float32(g), lp
+    pcm = synth.stream_pcm(11, 250, lead_silence=7).astype(np.float32).reshape(250, 480)
+    r = RefHarness(blob)
+    assert r.L.refh_arch(r.h) == 2
+    for k, v in r.run(pcm).items():
+        if k == "out":
+            d["free_out_crc"] = crc_rows(v)
+        else:
+            d[f"free_{k}"] = v
+    d["free_state"] = r.get_state()
+    pcm = synth.stream_pcm(21, 60).astype(np.float32).reshape(60, 480)
+    r = RefHarness(blob)
+    r.run(pcm[:40])
+    d["forced_state"] = r.get_state()
+    for k, v in r.run(pcm[40:]).items():
+        d[f"forced_{k}"] = v
+    rng = np.random.default_rng(5)
+    for stream, (lp, blp, nf) in enumerate([(481, 32, 0), (200, 24, 0), (481, 32, 1), (90, 16, 1)]):
+        clean, noisy, vad = train_case(stream, 40, rng)
+        rt = RefTrainHarness()
+        d[f"train{stream}"] = np.stack([rt.frame(clean[t], noisy[t], lp, blp, vad[t], nf) for t in range(40)])
+    np.savez_compressed(os.path.join(gold, "reference_pins.npz"), **d, **tag)
+
+
 def main():
     global GOLD
     tag = host_profile()
+    pins_only = "--pins" in sys.argv
+    if pins_only:
+        sys.argv.remove("--pins")
     blob_dir = GOLD
     if str(tag["rcp_profile"]) != "intel":
         GOLD = os.path.join(GOLD, str(tag["rcp_profile"]).replace("-", "_"))
     if len(sys.argv) > 1:
         GOLD = sys.argv[1]
     os.makedirs(GOLD, exist_ok=True)
+    if pins_only:
+        reference_pins(GOLD, tag, open(os.path.join(ROOT, "oracle", "_ref", "default.blob"), "rb").read())
+        return
     for name in ("default", "little"):
         blob = open(os.path.join(ROOT, "oracle", "_ref", f"{name}.blob"), "rb").read()
         path = os.path.join(blob_dir, f"{name}.blob.xz")
@@ -140,6 +195,7 @@ def main():
         d[f"s{s}_out_crc"] = crc_rows(res["out"])
         d[f"s{s}_state_crc"] = np.uint32(synth.crc32(r.get_state()))
     np.savez_compressed(os.path.join(GOLD, "digest_little.npz"), **d, **tag)
+    reference_pins(GOLD, tag, blob)
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)))
 

@@ -48,7 +48,9 @@ def test_step_valu_issue_bound_from_the_pmc_tables():
 
 def test_defaults_are_the_largest_single_gpu_config():
     a = bench.parse_args([])
-    assert a.streams == 65536 and a.gpus == 1 and a.repeats >= 25 and a.nn == "mfma" and a.model == "default"
+    assert a.streams == 65536 and a.gpus == 1 and a.nn == "mfma" and a.model == "default"
+    # the timed region is exactly --steps steps: one repetition unless --repeats splits them
+    assert a.steps == 100 and a.repeats == 1 and a.dump_outputs is None
     assert "configs[2]" in bench.workload_name(a, a.streams)
     a = bench.parse_args(["--model", "little", "--streams", "32768"])
     assert "configs[3]" in bench.workload_name(a, a.streams)
@@ -164,3 +166,25 @@ def test_round4_rooflines_are_measurements():
     assert v["clocks_per_inst_kind"] == "dynamic" and "GRBM_GUI_ACTIVE" in v["clock_source"] and 1.5 <= v["clock_ghz"] <= 2.4
     assert d["roofline_lds"]["clock_ghz"] == v["clock_ghz"]
     assert d["cpu_baseline"]["kind"] == "reference" and d["cpu_baseline"]["cores"] >= 1
+
+
+def test_dump_outputs_sample_is_fixed_and_fits_the_budget(tmp_path):
+    """--dump-outputs: every stream while they fit, otherwise the same seeded sample in every run; the files of the largest
+    default-size step (65,536 streams: PCM, VAD, gains, stream ids) stay within 64 MB"""
+    import numpy as np
+    import torch
+    assert (bench.dump_sample(96, 2060, 4) == np.arange(96)).all()
+    s = bench.dump_sample(65536, 2060, 4)
+    assert (s == bench.dump_sample(65536, 2060, 4)).all() and (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < 65536
+    assert len(s) * 2060 <= bench.DUMP_MAX_BYTES < (len(s) + 1) * 2060 + 4 * 256
+    N = 65536
+    arrays = {"pcm_out": torch.arange(N * 480, dtype=torch.float32).reshape(N, 480), "vad": torch.arange(N, dtype=torch.float32),
+              "gains": torch.zeros((N, 32))}
+    info = bench.dump_outputs(str(tmp_path), arrays, 1000, torch)
+    assert info["sampled"] is True and info["streams"] == len(s)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 * 10**6
+    ids = np.load(tmp_path / "stream_id.npy")
+    pcm = np.load(tmp_path / "pcm_out.npy")
+    assert ids.dtype == np.float64 and (ids == s + 1000).all()
+    assert pcm.dtype == np.float32 and pcm.shape == (len(s), 480) and (pcm[:, 0] == s * 480).all()
+    assert np.load(tmp_path / "vad.npy").shape == (len(s),) and np.load(tmp_path / "gains.npy").shape == (len(s), 32)

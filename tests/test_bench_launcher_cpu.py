@@ -20,13 +20,14 @@ def _run(args, env_extra=None, timeout=300):
 
 
 def test_direct_invocation_with_gpus_2_self_launches_and_prints_one_line():
-    r = _run(["--gpus", "2", "--stub", "--streams", "96", "--steps", "3", "--warmup", "1", "--repeats", "5"])
+    r = _run(["--gpus", "2", "--stub", "--streams", "96", "--steps", "7", "--warmup", "1", "--repeats", "5"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout  # rank 0 only
     d = json.loads(lines[0])
     assert d["stub"] is True and "SELF-TEST" in d["metric"]
-    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["repeats"] == 5
+    assert d["n_gpus"] == 2 and d["steps"] == 7 and d["warmup"] == 1 and d["repeats"] == 5
+    assert d["steps_by_repeat"] == [2, 2, 1, 1, 1]           # --steps is the number of timed steps, whatever --repeats
     assert d["config"]["streams_per_gpu"] == 96 and d["config"]["frames_per_step"] == 192
     assert d["config"]["stream_ids_rank0"] == [0, 96]       # rnnoise_amd.dist.shard_streams
     assert d["scaling"] == "weak" and d["value_min"] <= d["value"] <= d["value_max"]
@@ -36,7 +37,7 @@ def test_direct_invocation_with_gpus_2_self_launches_and_prints_one_line():
 
 
 def test_single_rank_stub_line():
-    r = _run(["--stub", "--streams", "64", "--steps", "2", "--warmup", "1", "--repeats", "5", "--no-cpu-baseline"])
+    r = _run(["--stub", "--streams", "64", "--steps", "5", "--warmup", "1", "--repeats", "5", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["frames_per_step"] == 64

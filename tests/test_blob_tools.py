@@ -25,6 +25,7 @@ def test_malformed_streams_raise():
 
 
 @pytest.mark.parametrize("density", [0.1, 1 / 3, 1.0])
+@pytest.mark.rcp("host")  # the compiled reference executes this CPU's rcpps: the oracle must carry this CPU's table
 def test_synthetic_models_are_accepted_and_behave(density):
     b = rb.synth_model(seed=7, density=density)
     rec = rb.read_blob(b)

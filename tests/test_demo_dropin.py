@@ -3,8 +3,8 @@ unmodified against OUR include/rnnoise.h and linked to librnnoise_amd.so, must p
 same bytes as the demo semantics applied to the oracle (first frame dropped, truncating
 (short) cast, partial tail frame dropped; examples/rnnoise_demo.c:52-61).
 
-The binary is built where /root/reference is mounted (__graft_entry__.build()) into
-tests/_build/ and travels to the GPU box with the snapshot.
+The binary is built where the reference's sources are mounted (__graft_entry__.build(): make -C oracle ref) into
+oracle/_ref/, and travels with the rest of oracle/_ref/.
 """
 import os
 import subprocess
@@ -15,19 +15,19 @@ import pytest
 from conftest import ROOT, load_blob
 from rnnoise_amd import capi, synth
 
-DEMO_SRC = os.path.join(os.environ.get("RNNOISE_REFERENCE", "/root/reference"), "examples", "rnnoise_demo.c")
-DEMO_BIN = os.path.join(ROOT, "tests", "_build", "rnnoise_demo_dropin")
+REF_SRC = os.environ.get("RNNOISE_REFERENCE", "/root/reference")
+DEMO_SRC = os.path.join(REF_SRC, "examples", "rnnoise_demo.c")
+DEMO_BIN = os.path.join(ROOT, "oracle", "_ref", "rnnoise_demo_dropin")
 
 
 def build_demo():
-    os.makedirs(os.path.dirname(DEMO_BIN), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-w", "-DUSE_WEIGHTS_FILE", f"-I{ROOT}/include", DEMO_SRC, "-o", DEMO_BIN,
-                           f"-L{ROOT}/rnnoise_amd", "-l:librnnoise_amd.so", f"-Wl,-rpath,{ROOT}/rnnoise_amd", "-lm"])
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), f"R={REF_SRC}", "_ref/rnnoise_demo_dropin"])
 
 
-@pytest.mark.skipif(not os.path.exists(DEMO_SRC), reason="reference sources not mounted")
+@pytest.mark.skipif(not (os.path.exists(DEMO_SRC) or os.path.exists(DEMO_BIN)), reason="reference sources not mounted at build time")
 def test_reference_demo_compiles_and_links_against_our_header_and_library():
-    build_demo()
+    if os.path.exists(DEMO_SRC):
+        build_demo()
     assert os.path.exists(DEMO_BIN)
     nm = subprocess.run(["nm", "-D", "--undefined-only", DEMO_BIN], capture_output=True, text=True).stdout
     for sym in ("rnnoise_create", "rnnoise_process_frame", "rnnoise_destroy", "rnnoise_model_from_filename",
@@ -39,7 +39,7 @@ def test_reference_demo_compiles_and_links_against_our_header_and_library():
 @pytest.mark.rcp("host")  # what a deployed process gets by default: the rcpps of the CPU it runs on, in the demo and in the oracle
 def test_demo_output_is_byte_identical(tmp_path):
     if not os.path.exists(DEMO_BIN):
-        pytest.skip("tests/_build/rnnoise_demo_dropin not built (needs the reference sources at build time)")
+        pytest.skip("oracle/_ref/rnnoise_demo_dropin not built (needs the reference sources at build time)")
     from oracle.binding import Oracle
     blob = load_blob("default")
     (tmp_path / "weights_blob.bin").write_bytes(blob)

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bits_equal
+from conftest import ROOT, assert_bits_equal, load_blob
 from oracle.binding import Oracle
 from rnnoise_amd import capi, synth
 from test_gpu_parity import oracle_run
@@ -346,3 +346,42 @@ def test_bench_falls_back_to_gloo_when_rccl_refuses():
     assert d["n_gpus"] == 2 and len(d["value_by_rank"]) == 2
     assert abs(d["value"] * d["ms_per_step"] * 1e-3 / 8192 - 1) < 0.01
     assert d["parity"]["bit_identical"] is True and d["config"]["outputs_sane"] is True
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs: what the last of the --steps timed steps returned to its caller (PCM, VAD, raw gains of every
+    stream of a small batch) is written as float32 .npy; it is bit-identical to the oracle on the same input frames, and a
+    second run with the same arguments writes the same bytes (the inputs depend on the arguments alone)"""
+    import json
+
+    import torch
+
+    import bench
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    N, K, W = 40, 5, 2
+    args = ["--streams", str(N), "--steps", str(K), "--warmup", str(W), "--repeats", "2", "--no-cpu-baseline", "--no-parity"]
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == K and d["steps_by_repeat"] == [3, 2]
+        assert d["dump_outputs"]["frame"] == W + K - 1 and d["dump_outputs"]["streams"] == N and not d["dump_outputs"]["sampled"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["gains.npy", "pcm_out.npy", "stream_id.npy", "vad.npy"]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.tobytes() == b.tobytes(), f
+    out, vad, gains = (np.load(tmp_path / "a" / f) for f in ("pcm_out.npy", "vad.npy", "gains.npy"))
+    assert out.shape == (N, 480) and vad.shape == (N,) and gains.shape == (N, 32)
+    assert (np.load(tmp_path / "a" / "stream_id.npy") == np.arange(N)).all()
+    # the bench's own input (W + K frames fit in its smallest input ring: no wrap), through the oracle up to the last timed step
+    pcm = bench.synth_pcm_torch(torch, N, 8, torch.device("cuda", 0), 0)[:W + K].cpu().numpy()
+    blob = load_blob("default")
+    for s in (0, 17, N - 1):
+        want = Oracle(blob).run(pcm[:, s])
+        assert_bits_equal(out[s], want["out"][-1], f"stream {s} pcm")
+        assert_bits_equal(vad[s], want["vad"][-1], f"stream {s} vad")
+        assert_bits_equal(gains[s], want["gains"][-1], f"stream {s} gains")

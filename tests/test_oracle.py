@@ -3,7 +3,8 @@
 The reference ships no golden vectors; the pins are
   (a) tests/golden/*.npz -- outputs of the reference's own sources, compiled unmodified by
       oracle/Makefile and recorded through oracle/ref_harness.c (tests/golden/make_golden.py);
-  (b) where oracle/_ref exists (build container), the live reference itself.
+  (b) where oracle/_ref exists (build container), the live reference itself; elsewhere the same comparisons read
+      its recorded outputs (tests/golden/reference_pins.npz).
 Bar: bit-exact on every float and integer, because the int8 quantisers amplify 1-ULP
 differences to >1e-4 gain differences.
 """
@@ -13,7 +14,7 @@ import zlib
 import numpy as np
 import pytest
 
-from conftest import both_profiles, ROOT, assert_bits_equal, golden, load_blob
+from conftest import both_profiles, ROOT, assert_bits_equal, golden, load_blob, use_rcp_profile
 from oracle.binding import Oracle, RefHarness
 from rnnoise_amd import synth
 
@@ -223,53 +224,99 @@ def test_profiles_move_the_gains_by_less_than_the_activation_error(blob_default)
           f"max |dvad| {np.abs(a['vad'] - b['vad']).max():.2e}; max |dpcm| {np.abs(a['out'] - b['out']).max():.3f}")
 
 
-# ---- live reference (build container only) ---------------------------------------------------
-needs_ref = pytest.mark.skipif(not RefHarness.available(), reason="oracle/_ref not built (needs /root/reference)")
+# ---- the reference itself: live where oracle/_ref is built, otherwise its recorded outputs -------------------------------
+def reference_pins():
+    """tests/golden/reference_pins.npz (tests/golden/make_golden.py): the reference's outputs for the tests below, recorded on
+    the host named in the file.  The oracle is switched to that host's rcpps profile, which the stored outputs belong to."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_pins.npz"))
+    use_rcp_profile(str(g["rcp_profile"]))
+    return g
 
 
-@needs_ref
 def test_tables_match_reference_bit_for_bit():
-    for a, b, name in zip(Oracle.tables(), RefHarness.tables(), ("window", "dct", "twiddles", "bitrev")):
+    if RefHarness.available():
+        want = RefHarness.tables()
+    else:
+        g = reference_pins()
+        want = [g[f"tables_{k}"] for k in ("window", "dct", "twiddles", "bitrev")]
+    for a, b, name in zip(Oracle.tables(), want, ("window", "dct", "twiddles", "bitrev")):
         assert_bits_equal(a, b, name)
 
 
-@needs_ref
 @pytest.mark.rcp("host")  # the compiled reference executes this CPU's rcpps: the oracle must carry this CPU's table
 def test_live_reference_free_running(blob_default):
     pcm = synth.stream_pcm(11, 250, lead_silence=7).astype(np.float32).reshape(250, 480)
-    o, r = Oracle(blob_default), RefHarness(blob_default)
-    assert r.L.refh_arch(r.h) == 2, "host must select the AVX2 code path (src/x86/x86cpu.c)"
-    a, b = o.run(pcm), r.run(pcm)
-    for k in a:
-        assert_bits_equal(a[k], b[k], k)
-    assert_bits_equal(o.get_state(), r.get_state(), "state")
+    if RefHarness.available():
+        r = RefHarness(blob_default)
+        assert r.L.refh_arch(r.h) == 2, "host must select the AVX2 code path (src/x86/x86cpu.c)"
+        want = r.run(pcm)
+        want_state = r.get_state()
+    else:
+        g = reference_pins()
+        want = {k[5:]: g[k] for k in g.files if k.startswith("free_") and k != "free_state"}
+        want_state = g["free_state"]
+    o = Oracle(blob_default)
+    a = o.run(pcm)
+    a["out_crc"] = crc_rows(a["out"])
+    assert set(want) - set(a) == set()
+    for k in want:
+        assert_bits_equal(a[k], want[k], k)
+    assert_bits_equal(o.get_state(), want_state, "state")
 
 
-@needs_ref
 def test_live_reference_fft_and_pitch():
+    g = None if RefHarness.available() else reference_pins()
     rng = np.random.default_rng(3)
-    for _ in range(4):
+    for i in range(4):
         x = (rng.standard_normal(1920) * 3000).astype(np.float32)
-        assert_bits_equal(Oracle.fft(x), RefHarness.fft(x), "fft")
+        assert_bits_equal(Oracle.fft(x), RefHarness.fft(x) if g is None else g[f"fft{i}"], "fft")
         buf = (rng.standard_normal(1728) * 2000).astype(np.float32)
-        a, b = Oracle.pitch(buf, 200, 0.4), RefHarness.pitch(buf, 200, 0.4)
+        a = Oracle.pitch(buf, 200, 0.4)
+        b = RefHarness.pitch(buf, 200, 0.4) if g is None else (g[f"pitch{i}_period"], g[f"pitch{i}_gain"], g[f"pitch{i}_x_lp"])
         assert a[0] == b[0]
         assert_bits_equal(np.float32(a[1]), np.float32(b[1]), "pitch gain")
         assert_bits_equal(a[2], b[2], "x_lp")
 
 
-@needs_ref
 @pytest.mark.rcp("host")
 def test_live_reference_teacher_forced_state_import(blob_default):
     """state exported from the reference mid-stream drives the oracle to the same next frame"""
     pcm = synth.stream_pcm(21, 60).astype(np.float32).reshape(60, 480)
-    r = RefHarness(blob_default)
-    r.run(pcm[:40])
+    if RefHarness.available():
+        r = RefHarness(blob_default)
+        r.run(pcm[:40])
+        state = r.get_state()
+        want = r.run(pcm[40:])
+    else:
+        g = reference_pins()
+        state = g["forced_state"]
+        want = {k[7:]: g[k] for k in g.files if k.startswith("forced_") and k != "forced_state"}
     o = Oracle(blob_default)
-    o.set_state(r.get_state())
-    a, b = o.run(pcm[40:]), r.run(pcm[40:])
+    o.set_state(state)
+    a = o.run(pcm[40:])
+    assert set(a) == set(want)
     for k in a:
-        assert_bits_equal(a[k], b[k], k)
+        assert_bits_equal(a[k], want[k], k)
+
+
+@pytest.mark.skipif(not RefHarness.available(), reason="oracle/_ref not built (needs the reference sources at build time)")
+def test_reference_pins_are_the_reference():
+    """the recorded outputs above are what the compiled reference computes, where it runs on a host of the recording's
+    rcpps profile (tests/golden/make_golden.py --pins)"""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_pins.npz"))
+    from oracle import binding
+    binding.set_rcp_profile("host")
+    if binding.rcp_profile() != str(g["rcp_profile"]):
+        pytest.skip(f"pins recorded on the {g['rcp_profile']} profile, this host is {binding.rcp_profile()}")
+    for k, v in zip(("window", "dct", "twiddles", "bitrev"), RefHarness.tables()):
+        assert_bits_equal(v, g[f"tables_{k}"], k)
+    blob = load_blob("default")
+    r = RefHarness(blob)
+    res = r.run(synth.stream_pcm(11, 250, lead_silence=7).astype(np.float32).reshape(250, 480))
+    assert np.array_equal(crc_rows(res["out"]), g["free_out_crc"])
+    for k in ("vad", "gains", "features", "pitch", "pitch_gain", "silence"):
+        assert_bits_equal(res[k], g[f"free_{k}"], k)
+    assert_bits_equal(r.get_state(), g["free_state"], "state")
 
 
 def test_x86_float_to_short_model_matches_the_compiler(tmp_path):
