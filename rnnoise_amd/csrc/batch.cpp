@@ -285,18 +285,14 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   const int pipe_force = b->schedule ? b->schedule : pipe_env;
   const bool pipelined = n_frames > 1 && pipe_force != 9;
   const bool side_k1 = pipelined && pipe_force != 1;
-  // $RNNOISE_AMD_SIDE_PRIO = <k1>,<hp> (A/B runs): queue priorities of the two side streams, -1 high / 0 normal / 1 low (the caller's
-  // stream, which carries network + synthesis, is whatever the caller made it: normal for torch's)
-  static const int side_prio[2] = {[] { const char *e = RN_LAB_ENV("SIDE_PRIO"); return e ? atoi(e) : 0; }(),
-                                   [] { const char *e = RN_LAB_ENV("SIDE_PRIO"); const char *c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 0; }()};
-  if (side_k1 && !b->side) HIP_OK(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, side_prio[0]));
+  // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
+  // made it: normal for torch's)
+  if (side_k1 && !b->side) HIP_OK(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, 0));
   if (pipelined && !b->side_hp) {
-    HIP_OK(hipStreamCreateWithPriority(&b->side_hp, hipStreamNonBlocking, side_prio[1]));
+    HIP_OK(hipStreamCreateWithPriority(&b->side_hp, hipStreamNonBlocking, 0));
     // ordering between streams of ONE device: no system-scope fence (it writes back and invalidates the caches at
     // every record, which the next kernels then pay for)
-    // ($RNNOISE_AMD_EVENT_FENCE=1, A/B runs only: ordering events with the system-scope fence back on)
-    static const bool sys_fence = [] { const char *e = RN_LAB_ENV("EVENT_FENCE"); return e && atoi(e) == 1; }();
-    const unsigned evf = hipEventDisableTiming | (sys_fence ? 0u : (unsigned)hipEventDisableSystemFence);
+    const unsigned evf = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
     HIP_OK(hipEventCreateWithFlags(&b->ev_begin, evf));
     for (int k = 0; k < 8; k++) {
       HIP_OK(hipEventCreateWithFlags(&b->own_hp[k], evf));
@@ -329,13 +325,12 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     // SIMD for 0.18 ms, and a GRU workgroup (2 waves x 240 VGPRs per SIMD) does not fit beside even one of them: the first
     // layer kernel of every frame waited that long (rocprofv3 timeline: 283 us instead of 115).  Beside the analysis kernel
     // (4 waves x 56 VGPRs per SIMD) it costs nothing.
-    static const bool hp_early = RN_LAB_ENV("HP_EARLY") != nullptr;  // A/B runs only: the ring-bound start
-    if (side_k1 && f >= 4 && !hp_early) HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[(f - 4) & 7], 0));
+    if (side_k1 && f >= 4) HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[(f - 4) & 7], 0));
     // ... and the same concern when only the high-pass runs aside (schedule 1: the host-fed path): there analysis(f-2) follows
     // synthesis(f-3) on the main stream, so that is the event to start behind -- the high-pass of frame f is launched after it (see the
     // frame loop).  Started at the ring's earliest moment it ran beside the layer kernels of frame f-3: network 0.73 ms instead of 0.57
     // (profiles/r5_hostio_sdma.txt).
-    if (pipelined && !side_k1 && f >= 3 && !hp_early) HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[(f - 3) & 7], 0));
+    if (pipelined && !side_k1 && f >= 3) HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[(f - 3) & 7], 0));
     if (hk && hk->before_hp(f, sc)) return -1;
     {
       TimedLaunch t(b, 3);
@@ -360,60 +355,6 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     }
     return 0;
   };
-#if RN_INSTRUMENT
-  // LAB ($RNNOISE_AMD_FUSE_K3K1=1, instrumented library; profiles/r6_fused_k3k1.txt): synthesis(f - 1) as the prologue of analysis(f) in ONE
-  // kernel on the main stream -- [K3(f-1) . K1(f)] -> K2(f) -> [K3(f) . K1(f+1)] -> ... -- the high-pass ahead on its side stream, started
-  // behind the network of frame f - 3, and one trailing stand-alone synthesis at the end of the call
-  static const bool fuse_env = [] { const char *e = RN_LAB_ENV("FUSE_K3K1"); return e && atoi(e) == 1; }();
-  if (fuse_env && n_frames > 1 && !hk && pipe_force != 9 && b->n >= 6144) {
-    const bool whole = b->g.n_streams == b->g.n_stride && (size_t)b->g.n_streams * RN_GRU * 4 < (1ull << 32);
-    if (!(whole && (b->nn_path == 2 || (b->nn_path == 1 && b->n >= nn_layers_min_streams())))) return -1;  // (layer-wise network only)
-    for (int f = 0; f < 3 && f < n_frames; f++)
-      if (highpass(f)) return -1;
-    for (int f = 0; f < n_frames; f++) {
-      RnGroupDev g = frame_group(f), gs = frame_group(f > 0 ? f - 1 : 0);
-      const int cur = (b->parity + f) % RN_SPEC_SLOTS, prev = (cur + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, pprev = (prev + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
-      HIP_OK(hipStreamWaitEvent(st, b->cur_hp[f & 7], 0));
-      {
-        TimedLaunch t(b, 0);
-        b->cur_k1[f & 7] = t.on ? t.stop() : b->own_k1[f & 7];
-        HIP_OK(rn_launch_analysis_synth(&g, &gs, &b->tb, (b->ring_slot + f) % RN_RING_SLOTS, cur, d_out + buf(f > 0 ? f - 1 : 0) * N * RN_FRAME_SIZE * esz, s16,
-                                        f > 0 ? prev : -1, pprev, st, t.start(), b->cur_k1[f & 7]));
-      }
-      {
-        if (!b->img_valid) HIP_OK(rn_launch_nn_requant(&g, st));
-        b->img_valid = true;
-        std::unique_ptr<TimedLaunch> tl[5];
-        hipEvent_t ev[5][2] = {};
-        const int nl = rn_nn_layers_launches();
-        for (int i = 0; i < nl; i++) {
-          tl[i].reset(new TimedLaunch(b, 1));
-          ev[i][0] = tl[i]->start();
-          ev[i][1] = tl[i]->stop();
-        }
-        if (!ev[nl - 1][1]) ev[nl - 1][1] = b->own_k3[f & 7];
-        b->cur_k3[f & 7] = ev[nl - 1][1];  // (here: "the network of frame f is done" -- what the high-pass three frames ahead starts behind)
-        HIP_OK(rn_launch_nn_layers(&g, &b->m, &b->tb, st, ev));
-      }
-      if (f + 3 < n_frames) {
-        HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[f & 7], 0));  // (beside the fused kernel of frame f + 1, not beside this frame's layer kernels)
-        if (highpass(f + 3)) return -1;
-      }
-      b->launches += b->timing ? 1 : 0;
-    }
-    {
-      const int f = n_frames - 1;
-      RnGroupDev g = frame_group(f);
-      const int cur = (b->parity + f) % RN_SPEC_SLOTS, prev = (cur + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
-      TimedLaunch t(b, 2);
-      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * N * RN_FRAME_SIZE * esz, s16, cur, prev, st, t.start(), t.stop()));
-    }
-    b->parity = (b->parity + n_frames) % RN_SPEC_SLOTS;
-    b->ring_slot = (b->ring_slot + n_frames) % RN_RING_SLOTS;
-    b->frame_no += n_frames;
-    return 0;
-  }
-#endif
   if (pipelined) {
     for (int f = 0; f < 3 && f < n_frames; f++)
       if (highpass(f)) return -1;
@@ -436,10 +377,10 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
       if (whole && (b->nn_path == 2 || (b->nn_path == 1 && b->n >= nn_layers_min_streams()))) {
         if (!b->img_valid) HIP_OK(rn_launch_nn_requant(&g, st));
         b->img_valid = true;
-        // four or five launches, each timed on its own (kind 1: the durations add up to the network's)
+        // five launches, each timed on its own (kind 1: the durations add up to the network's)
         std::unique_ptr<TimedLaunch> tl[5];
         hipEvent_t ev[5][2] = {};
-        for (int i = 0, nl = rn_nn_layers_launches(); i < nl; i++) {
+        for (int i = 0; i < 5; i++) {
           tl[i].reset(new TimedLaunch(b, 1));
           ev[i][0] = tl[i]->start();
           ev[i][1] = tl[i]->stop();
@@ -647,15 +588,6 @@ extern "C" int rnnoise_amd_debug_log_energy_range(int device, float *out, const 
 extern "C" int rnnoise_amd_debug_log_energy(int device, float *out, const float *ex, int n) {
   if (!ex || n <= 0) return -1;
   return rnnoise_amd_debug_log_energy_range(device, out, ex, 0, (unsigned)n, 0);
-}
-
-// the GRU layer kernel's row-buffer check (nn_layers.hip: CHK instantiations): copies the log out and clears it
-extern "C" hipError_t rn_gru_race_log_read(unsigned *out, int words);
-extern "C" int rnnoise_amd_debug_gru_race(int device, unsigned *log, int words) {
-  if (!log) return -1;
-  ON_DEVICE(device);
-  HIP_OK(rn_gru_race_log_read(log, words));
-  return 0;
 }
 
 #endif  // RN_INSTRUMENT

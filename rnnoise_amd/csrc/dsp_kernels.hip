@@ -876,13 +876,6 @@ __device__ __forceinline__ void analysis_body(const RnGroupDev &g, const RnTable
   // every workgroup, and the two running-energy sweeps of phase 3 advance side by side.  Clear: everything on wave 0 (round 3).
   const bool spread = SPW > 1;                            // (round 4 measured it against everything-on-wave-0 in one kernel: 4 %; that
                                                           //  form now lives only in the one-stream workgroups, where wave 0 is the stream)
-  // (A/B switches of the instrumented build, rn_launch_analysis: compile-time constants in the product)
-  const bool xrow = !(RN_INSTRUMENT && (slot_arg & 1024));              // bit 10: the doubling dots read x per lane from LDS (chain_dot8_y2)
-  const int narrow_prio = (RN_INSTRUMENT && (slot_arg & 4096)) ? 1 : 3; // bit 12: the narrow-phase waves keep the kernel's priority
-  const bool fine_deep = !(RN_INSTRUMENT && (slot_arg & 16384));        // bit 14: the fine-search chains fetch one block ahead, not two
-  // bit 13: TIMING ONLY, WRONG RESULTS -- the 31 candidate chains of remove_doubling read at offsets 2 l (one bank pair per lane: no bank
-  // conflict is possible): what the kernel would take if the conflicts of that pass were gone (profiles/r6_k1_dots_conflicts.txt)
-  const bool dots_noconf = RN_INSTRUMENT && (slot_arg & 8192);
   const int nw0 = spread ? (int)((blockIdx.x * 0x9E3779B1u) >> 30) : 0;
   const int nw1 = nw0, nw2 = spread ? (nw0 + 1) & 3 : 0, nw3a = spread ? (nw0 + 2) & 3 : 0, nw3b = spread ? (nw0 + 3) & 3 : 0;
   const int ring0 = RN_RING0(slot);
@@ -1200,7 +1193,7 @@ __device__ __forceinline__ void analysis_body(const RnGroupDev &g, const RnTable
     // of the fine find_best_pitch of every stream, one lane each, and from it the running energy Syy of the fine search,
     // one row per stream (sweep_syy_fine_row_x: its increments are formed on the way, nothing of it waits for nw2's chains).
     if (wave == nw2) {
-      if (narrow_prio == 3) __builtin_amdgcn_s_setprio(3);
+      __builtin_amdgcn_s_setprio(3);
       const int gq = lane >> 4, r = lane & 15;  // (SPW == 4 rows)
       float *ag = ARENA(gq < SPW ? gq : 0).a;
       const int b0 = __float_as_int(ag[SCR_MAIL + MAIL_BP0]), b1 = __float_as_int(ag[SCR_MAIL + MAIL_BP1]);
@@ -1208,12 +1201,12 @@ __device__ __forceinline__ void analysis_body(const RnGroupDev &g, const RnTable
       const bool lag = r < 10 && c >= 0 && c < 294;
       const int a = lag ? c : 384;
       ldsf xg = to_lds(ag + SCR_XLP + 384), yg = to_lds(ag + ((a & 1) ? SCR_XS + (a - 1) : SCR_XLP + a));
-      const float sum = fine_deep ? chain_dot16_xrow<true>(xg, yg, 480, lane) : chain_dot16_xrow<false>(xg, yg, 480, lane);
+      const float sum = chain_dot16_xrow<true>(xg, yg, 480, lane);
       if (lag) ag[SCR_XC + c] = (-1 > sum) ? -1 : sum;
       if (r == 10) ag[SCR_MAIL + MAIL_XX] = sum;
       __builtin_amdgcn_s_setprio(1);
     } else if (wave == nw3a) {
-      if (narrow_prio == 3) __builtin_amdgcn_s_setprio(3);
+      __builtin_amdgcn_s_setprio(3);
       {  // (every lane takes part: the rows' DPP operands come from the other lanes' registers)
         float *a = ARENA((lane >> 4) < SPW ? (lane >> 4) : 0).a;
         const float syy0 = chain_sq_row(to_lds(a + SCR_XLP), 480, 1.f, lane & 15);
@@ -1360,23 +1353,22 @@ __device__ __forceinline__ void analysis_body(const RnGroupDev &g, const RnTable
         off = T0g + ((l & 1) ? 1 : -1);
         if (off < 0) off = 0;
       }
-      if (dots_noconf && off >= 0) off = 2 * l;
       // every lane runs a chain (chain_dot16_xrow takes x from the registers of the other lanes of its row); the lanes without
       // an offset of their own run <x, x>, all of them on the same addresses (a broadcast, not a bank conflict), and drop it
       const int a = maxperiod - (off >= 0 ? off : 0);  // y = x_lp + a
       ldsf xg = to_lds(ag + SCR_XLP + maxperiod), ya = to_lds(ag + ((a & 1) ? SCR_XS + (a - 1) : SCR_XLP + a));
-      const float d = xrow ? chain_dot16_xrow<false>(xg, ya, N, lane) : (off >= 0 ? chain_dot8_y2(xg, ya, N) : 0.f);
+      const float d = chain_dot16_xrow<false>(xg, ya, N, lane);
       if (off >= 0) ag[SCR_DOTS + l] = d;
     };
     if (spread) {
       if (wave == nw1 || wave == nw3b) {
-        if (narrow_prio == 3) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         float *ag = ARENA((wave == nw1 ? 0 : 2) + (lane >> 5)).a;
         const int T0g = __float_as_int(ag[SCR_MAIL + MAIL_T0]);
         candidate_dots(ag, T0g, lane & 31);
         __builtin_amdgcn_s_setprio(1);
       } else if (wave == nw2) {  // yy_lookup of every stream, one row each (every lane takes part: DPP operands)
-        if (narrow_prio == 3) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         float *a = ARENA((lane >> 4) < SPW ? (lane >> 4) : 0).a;
         sweep_yy_lookup_row_x(a + SCR_XLP, a + SCR_YYL, a[SCR_MAIL + MAIL_XX], lane & 15);
         __builtin_amdgcn_s_setprio(1);
@@ -1622,7 +1614,7 @@ extern "C" __global__ void __launch_bounds__(WAVE * K1_SPW) __attribute__((amdgp
 rn_analysis_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity) {
   // Above the high-pass kernel's waves (priority 0), which run beside this kernel two frames ahead and are in no hurry:
   // one of them per SIMD, always ready with an old instruction, otherwise takes issue slots from four analysis waves
-  // (29.14 -> 29.41 M frames/s at 65,536 streams; RNNOISE_AMD_K1_PRIO=0 switches it off for A/B runs).
+  // (29.14 -> 29.41 M frames/s at 65,536 streams; bit 8 of `slot`, which rn_launch_analysis always sets).
   if (slot & 256) __builtin_amdgcn_s_setprio(1);
   analysis_body<false, K1_SPW>(g, tb, slot & ~256, parity, RnTrainArgs{});
 }
@@ -1682,12 +1674,6 @@ static_assert(sizeof(SynthLds) <= 5120 && RN_WINDOW_SIZE <= 1052 && RN_BAND_QSTR
 #endif
 // LATE: the overlap-add operands behind the transform (the throughput form); !LATE: with everything else at the top (a handful of
 // waves on an empty machine have nobody to cover the extra round trip: rn_synthesis_few_kernel)
-// where a synthesis wave works: its stream, its lane number, its 4.9 KB of LDS (a one-wave workgroup of its own -- or, lab build, a wave
-// of a fused analysis workgroup: rn_analysis_synth_kernel)
-struct SynthPlace {
-  int s, lane;
-  char *lds;
-};
 // Where transform output b of a lane goes (src/denoise.c:213-216, 400-407).  The lane holds y[p], p = 64 b + pos, pos = fft_pos(lane) in
 // 0..63; time sample n = (960 - p) % 960.  lo = "p == 0 or p > 480" = n < 480: an output sample, out[n] = 960 y w[n] + synthesis_mem[n];
 // otherwise synthesis_mem[n - 480] = 960 y w[959 - n] = 960 y w[p - 1], n - 480 = 480 - p.  Returns the window index (n or p - 1) and sets
@@ -1719,7 +1705,7 @@ __device__ __forceinline__ unsigned synth_index(int b, unsigned pos, bool &lo, u
 }
 template <bool LATE>
 __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTablesDev &tb, float *__restrict__ out, int parity_arg, int prev_arg,
-                                               const RnRows &rows, const SynthPlace *place = nullptr) {
+                                               const RnRows &rows) {
   // bit 8 of parity_arg: `out` holds int16 samples, written with the truncating conversion of the reference's only caller
   // (examples/rnnoise_demo.c:58: tmp[i] = x[i], float -> short as x86 compiles it: cvttss2si to 32 bits -- "integer
   // indefinite" 0x80000000 when out of range or NaN -- then the low 16 bits)
@@ -1729,8 +1715,8 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
   const int prev = listed ? (parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS : prev_arg;
   const bool out_s16 = !listed && (parity_arg & 256);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  SynthLds &L = *reinterpret_cast<SynthLds *>(place ? place->lds : smem_raw);
-  const int s = place ? place->s : (listed ? RN_ROW_OF(re) : (int)blockIdx.x), lane = place ? place->lane : (int)threadIdx.x, pos = fft_pos(lane);
+  SynthLds &L = *reinterpret_cast<SynthLds *>(smem_raw);
+  const int s = listed ? RN_ROW_OF(re) : (int)blockIdx.x, lane = (int)threadIdx.x, pos = fft_pos(lane);
   const float2 *dX = reinterpret_cast<const float2 *>(g.spec_X[prev] + (size_t)s * RN_SPEC_STRIDE);
   const float2 *dP = reinterpret_cast<const float2 *>(g.spec_P[prev] + (size_t)s * RN_SPEC_STRIDE);
   const float *dE = g.spec_E[prev] + (size_t)s * 96;
@@ -1913,58 +1899,23 @@ rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, i
   synthesis_body<false>(g, tb, out, parity_arg, prev_arg, rows);
 }
 
-#if RN_INSTRUMENT
-// ---- LAB (instrumented build only; VERDICT r5 Next #2, profiles/r6_fused_k3k1.txt) ----
-// Synthesis of frame t-1 as the PROLOGUE of the analysis of frame t: same wave = same stream, in the wave's own arena (4.9 of its 9.3 KB),
-// at the analysis kernel's occupancy.  The question: does the stage with the most HBM traffic per instruction hide under the
-// issue-bound one when they are phases of ONE kernel (waves of a CU drift apart between the six barriers of a workgroup), where as
-// separate kernels they cannot co-reside (profiles/r5_overlap.txt)?  gs: the group as frame t-1 sees it (its features / silence /
-// gains buffers); synth_cur < 0: no synthesis (first frame of a call).
-extern "C" __global__ void __launch_bounds__(WAVE * K1_SPW) __attribute__((amdgpu_waves_per_eu(4, 4)))
-rn_analysis_synth_kernel(RnGroupDev g, RnGroupDev gs, RnTablesDev tb, int slot, int parity, float *__restrict__ out, int synth_cur, int synth_prev) {
-  if (slot & 256) __builtin_amdgcn_s_setprio(1);
-  {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), s = (int)blockIdx.x * K1_SPW + wave;
-    if (synth_cur >= 0 && s < gs.n_streams) {
-      const SynthPlace pl{s, (int)(threadIdx.x & (WAVE - 1)), smem_raw + wave * sizeof(AnalysisLds)};
-      synthesis_body<true>(gs, tb, out, synth_cur, synth_prev, RnRows{}, &pl);
-      RN_WSYNC();
-    }
-  }
-  analysis_body<false, K1_SPW>(g, tb, slot & ~256, parity, RnTrainArgs{});
-}
-extern "C" hipError_t rn_launch_analysis_synth(const RnGroupDev *g, const RnGroupDev *gs, const RnTablesDev *tb, int slot, int parity, void *out,
-                                               int out_s16, int synth_cur, int synth_prev, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  const dim3 grid((g->n_streams + K1_SPW - 1) / K1_SPW), block(WAVE * K1_SPW);
-  RN_LAUNCH(rn_analysis_synth_kernel, grid, block, K1_SPW * sizeof(AnalysisLds), st, e0, e1, *g, *gs, *tb, slot | 256, parity,
-            static_cast<float *>(out), synth_cur < 0 ? -1 : (synth_cur | (out_s16 ? 256 : 0)), synth_prev);
-  return hipGetLastError();
-}
-#endif
 
 // host-visible launch helpers -----------------------------------------------------------------
 // (K0 lives in hp_kernel.hip; K0 and K1 are launched separately so that the host may put K0 of the next frame on a side stream)
 extern "C" hipError_t rn_launch_hp_passthrough(const RnGroupDev *g, const float *in, int slot, hipStream_t st);  // hp_kernel.hip
 extern "C" hipError_t rn_launch_analysis(const RnGroupDev *g, const RnTablesDev *tb, int slot, int parity, hipStream_t st,
                                          hipEvent_t e0, hipEvent_t e1) {
-  // A/B runs only: RNNOISE_AMD_K1_SPW=1 / 4 forces one / K1_SPW streams per workgroup; RNNOISE_AMD_K1_LDS -> a larger
-  // LDS request per wave lowers the waves per CU (occupancy experiments)
+  // A/B runs only: RNNOISE_AMD_K1_SPW=1 / 4 forces one / K1_SPW streams per workgroup
   static const int spw_force = [] { const char *e = getenv("RNNOISE_AMD_K1_SPW"); return e ? atoi(e) : 0; }();
-  static const size_t lds1 = [] { const char *e = RN_LAB_ENV("K1_LDS"); return e ? (size_t)atoi(e) : sizeof(AnalysisLds); }();
   const int n = g->n_streams;
   const bool single = spw_force == 1 || (spw_force == 0 && n < RN_K1_MULTI_MIN_STREAMS);
   if (single) {
-    RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), lds1, st, e0, e1, *g, *tb, slot, parity, RnRows{});
+    RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity, RnRows{});
   } else {
     const dim3 grid((n + K1_SPW - 1) / K1_SPW), block(WAVE * K1_SPW);
-    static const int prio = [] { const char *e = RN_LAB_ENV("K1_PRIO"); return (e && atoi(e) == 0) ? 0 : 256; }();
+    // bit 8: issue priority (rn_analysis_kernel); bits 16-20: K1_STOP (instrumented build, tools/k1_prefix.sh)
     static const int stop = [] { const char *e = RN_LAB_ENV("K1_STOP"); return (RN_INSTRUMENT && e) ? atoi(e) << 16 : 0; }();
-    static const int noxrow = [] {
-      const char *e = RN_LAB_ENV("K1_XROW"), *x = RN_LAB_ENV("K1_EXPERIMENT");  // (A/B bits 12, 14: see analysis_body)
-      return ((e && atoi(e) == 0) ? 1024 : 0) | (x ? (atoi(x) & (4096 | 8192 | 16384)) : 0);
-    }();
-    RN_LAUNCH(rn_analysis_kernel, grid, block, K1_SPW * lds1, st, e0, e1, *g, *tb, slot | prio | stop | noxrow, parity);
+    RN_LAUNCH(rn_analysis_kernel, grid, block, K1_SPW * sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot | 256 | stop, parity);
   }
   return hipGetLastError();
 }
@@ -1988,10 +1939,7 @@ extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev
 }
 // K1 / K3 of a launch group of the one-frame API (rn_dev.h: RnRows): one one-wave workgroup per listed row
 extern "C" hipError_t rn_launch_analysis_rows(const RnGroupDev *g, const RnTablesDev *tb, const RnRows *rows, hipStream_t st) {
-  // RNNOISE_AMD_ROWS_K1=1 (A/B runs): one wave per row (rn_analysis_single_kernel) instead of a workgroup of four
-  static const bool one_wave = [] { const char *e = RN_LAB_ENV("ROWS_K1"); return e && atoi(e) == 1; }();
-  if (one_wave) hipLaunchKernelGGL(rn_analysis_single_kernel, dim3(rows->n), dim3(WAVE), sizeof(AnalysisLds), st, *g, *tb, 0, 0, *rows);
-  else hipLaunchKernelGGL(rn_analysis_rows_kernel, dim3(rows->n), dim3(WAVE * K1_SPW), K1_SPW * sizeof(AnalysisLds), st, *g, *tb, *rows);
+  hipLaunchKernelGGL(rn_analysis_rows_kernel, dim3(rows->n), dim3(WAVE * K1_SPW), K1_SPW * sizeof(AnalysisLds), st, *g, *tb, *rows);
   return hipGetLastError();
 }
 extern "C" hipError_t rn_launch_synthesis_rows(const RnGroupDev *g, const RnTablesDev *tb, const RnRows *rows, hipStream_t st) {

@@ -1,6 +1,9 @@
 // fft_probe.hip -- test / measurement kernels: the register-resident FFT (fft_reg.h) in isolation, the LDS work-area FFT it
 // replaced, the exchange-primitive map, the device log10 sweep.  Compiled into the INSTRUMENTED library only
 // (librnnoise_amd_instr.so, include/rnnoise_amd_debug.h); the product library does not contain this file.
+#if !RN_INSTRUMENT
+#error "fft_probe.hip is an INSTRUMENTED BUILD ONLY source (-DRN_INSTRUMENT=1)"
+#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fft_reg.h"

@@ -7,7 +7,7 @@
 // number); the radix-3 (m = 64) and radix-5 (m = 192) stages combine blk = 3u+{0,1,2} and blk = t+{0,3,6,9,12}, i.e.
 // they are entirely inside a lane.  Every output is the reference's exact expression tree (kiss_fft.c:101-306,
 // _kiss_fft_guts.h:101-103; unfused multiplies and adds, -ffp-contract=off), so the bits are the oracle's:
-// tools/proto/regfft_emul.py is the lane-level numpy model of this file, checked against oracle/rn_oracle.c:fft960.
+// tools/regfft_emul.py is the lane-level numpy model of this file, checked against oracle/rn_oracle.c:fft960.
 //
 // A cross-lane radix-4 butterfly on inputs v0..v3 (v1..v3 already multiplied by their twiddles by the lanes that own
 // them), role k = the lane's digit:

@@ -348,24 +348,6 @@ static int batch_process_pinned(RNNoiseBatch *b, char *out, const char *in, floa
     if (f >= RING) HIP_OK(hipStreamWaitEvent(st, io.r_down[f % RING], 0));
     return 0;
   };
-  // Downloads are hipMemcpyAsync (DMA).  $RNNOISE_AMD_D2H=kernel:<workgroups> (A/B runs) replaces them by a small copy kernel
-  // writing the caller's pinned memory through its device address (state_kernels.hip: rn_copy_to_host_kernel): measured
-  // slower than the serialised DMA copies (18 M against 23-28 M frames/s), kept for the record.
-  static const int d2h_blocks = [] {
-    const char *e = RN_LAB_ENV("D2H");
-    if (e && !strncmp(e, "kernel:", 7)) return std::max(1, atoi(e + 7));
-    return 0;
-  }();
-  auto dev_view = [](void *host) -> void * {  // device address of pinned host memory, or nullptr (then: hipMemcpyAsync)
-    void *d = nullptr;
-    if (!host || hipHostGetDevicePointer(&d, host, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    return d;
-  };
-  char *out_dev = d2h_blocks ? static_cast<char *>(dev_view(out)) : nullptr;
-  float *vad_dev = d2h_blocks && vad ? static_cast<float *>(dev_view(vad)) : nullptr;
-  float *gains_dev = d2h_blocks && gains ? static_cast<float *>(dev_view(gains)) : nullptr;
-  const bool by_kernel = out_dev && (!vad || vad_dev) && (!gains || gains_dev) && !(reinterpret_cast<uintptr_t>(out_dev) & 15) &&
-                         !(reinterpret_cast<uintptr_t>(vad_dev) & 15) && !(reinterpret_cast<uintptr_t>(gains_dev) & 15) && N % 4 == 0;
   hk.after_k3 = [&](int f, hipStream_t st) -> int {
     const int k = f % RING;
     if (sd) {
@@ -386,17 +368,10 @@ static int batch_process_pinned(RNNoiseBatch *b, char *out, const char *in, floa
     }
     HIP_OK(hipEventRecord(io.r_k3[k], st));
     HIP_OK(hipStreamWaitEvent(io.down, io.r_k3[k], 0));
-    if (by_kernel) {
-      HIP_OK(rn_launch_copy_to_host(out_dev + (size_t)f * fsz, r_out + (size_t)k * fsz, fsz, d2h_blocks, io.down));
-      if (vad) HIP_OK(rn_launch_copy_to_host(vad_dev + (size_t)f * N, r_vad + (size_t)k * N, N * sizeof(float), 1, io.down));
-      if (gains) HIP_OK(rn_launch_copy_to_host(gains_dev + (size_t)f * N * RN_NB_BANDS, r_g + (size_t)k * N * RN_NB_BANDS,
-                                               N * RN_NB_BANDS * sizeof(float), std::max(1, d2h_blocks / 4), io.down));
-    } else {
-      HIP_OK(hipMemcpyAsync(out + (size_t)f * fsz, r_out + (size_t)k * fsz, fsz, hipMemcpyDeviceToHost, io.down));
-      if (vad) HIP_OK(hipMemcpyAsync(vad + (size_t)f * N, r_vad + (size_t)k * N, N * sizeof(float), hipMemcpyDeviceToHost, io.down));
-      if (gains) HIP_OK(hipMemcpyAsync(gains + (size_t)f * N * RN_NB_BANDS, r_g + (size_t)k * N * RN_NB_BANDS, N * RN_NB_BANDS * sizeof(float),
-                                       hipMemcpyDeviceToHost, io.down));
-    }
+    HIP_OK(hipMemcpyAsync(out + (size_t)f * fsz, r_out + (size_t)k * fsz, fsz, hipMemcpyDeviceToHost, io.down));
+    if (vad) HIP_OK(hipMemcpyAsync(vad + (size_t)f * N, r_vad + (size_t)k * N, N * sizeof(float), hipMemcpyDeviceToHost, io.down));
+    if (gains) HIP_OK(hipMemcpyAsync(gains + (size_t)f * N * RN_NB_BANDS, r_g + (size_t)k * N * RN_NB_BANDS, N * RN_NB_BANDS * sizeof(float),
+                                     hipMemcpyDeviceToHost, io.down));
     HIP_OK(hipEventRecord(io.r_down[k], io.down));
     return 0;
   };
@@ -405,9 +380,8 @@ static int batch_process_pinned(RNNoiseBatch *b, char *out, const char *in, floa
   // streams then share a queue: what the high-pass stream carries queues up behind analysis kernels and the whole step
   // serialises (rocprofv3 trace: 3.5 ms per 65,536-stream s16 step).  Analysis therefore stays on the main stream here
   // (schedule 1: only the high-pass runs ahead on a side stream), which costs the 2-3 % the analysis overlap is worth.
-  static const int sched_env = [] { const char *e = RN_LAB_ENV("HOSTIO_SCHEDULE"); return e ? atoi(e) : 1; }();  // (A/B runs)
   const int keep = b->schedule;
-  if (b->schedule == 0) b->schedule = sched_env;
+  if (b->schedule == 0) b->schedule = 1;
   const int rc = batch_process_device_impl(b, r_out, r_in, r_vad, r_g, n_frames, io.run, s16, &hk);
   b->schedule = keep;
   if (sd && !rc && n_frames > 0) {

@@ -2,7 +2,7 @@
 // Levinson), transposed to lane = stream.  Compiled WITHOUT the SLP vectoriser since round 5: with it (~9 % fewer
 // instructions) the autocorrelation chains became v_pk_mul_f32 / v_pk_add_f32 with op_sel operand selects, and those take the
 // wrong operand half in lanes 48..63 whenever a wave issuing v_mfma_i32_16x16x64_i8 shares the SIMD (profiles/r5_gru_race.txt;
-// tests/test_kernel_budgets_cpu.py keeps every such instruction out of the library).  hp_slp.hip is the old build, for A/B runs.
+// tests/test_kernel_budgets_cpu.py keeps every such instruction out of the library).
 // Numerics contract as in dsp_kernels.hip: -ffp-contract=off, reference order of every float sum.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,15 +19,7 @@
 // a0*yi and a1*yi are products of two 24-bit significands, exact in double, so
 // fma(-a, yi, b*xi) rounds once exactly like the reference's (b*xi - a*yi).
 // ---------------------------------------------------------------------------------------------
-#ifndef RN_HP_KERNEL_NAME
-#define RN_HP_KERNEL_NAME rn_hp_kernel
-#endif
-#ifndef RN_HP_BLK
 #define RN_HP_BLK 8   // float4 per block and stream: 8 = one 128-byte line
-#endif
-#ifndef RN_HP_ATTR
-#define RN_HP_ATTR
-#endif
 // The body is compiled once per (high-pass applied, int16 input): as run-time flags the two were tested inside the block loop, per
 // float4, and behind those joins the compiler could no longer count the loads in flight -- it waited with vmcnt(0) in front of every
 // block's arithmetic, i.e. for the NEXT block's loads it had just issued: the one-block prefetch hid nothing (round 6, last day).
@@ -36,15 +28,11 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
   // mode: bit 0 = apply the high-pass (inference); bit 1 = `in` holds int16 samples, converted as the reference's only caller
   // does (examples/rnnoise_demo.c:56: x[i] = tmp[i], short -> float, exact)
   constexpr bool apply_hp = HP_ON, in_s16 = IN_S16;
-  // bits 12-13: streams per wave = 64 >> k.  The kernel is bound by how many loads its waves keep in flight (one wave per SIMD at 64 streams
-  // per wave and 65,536 streams: each lane's HBM round trips are its own), not by issue: half-empty waves are twice as many waves
+  // bits 12-13: streams per wave = 64 >> k (rn_launch_hp passes 0: 64 streams per wave)
   const int spw = WAVE >> ((mode >> 12) & 3);
-  // (one wave per workgroup; or, A/B, four whole waves: blockDim.x = 256, one wave per SIMD of the CU that gets the workgroup)
+  // (one wave per workgroup, which is what rn_launch_hp launches; or four whole waves: blockDim.x = 256)
   const int s = blockDim.x > WAVE ? blockIdx.x * blockDim.x + threadIdx.x : blockIdx.x * spw + threadIdx.x;
   if ((blockDim.x == WAVE && (int)threadIdx.x >= spw) || s >= g.n_streams) return;
-  // (race hunt, $RNNOISE_AMD_HP_AB: 512 = raised issue priority, 1024 = drain the tap stores before the wave ends; 256 drained the
-  //  wave's stores before the pitch ring was read back -- nothing is read back any more)
-  if (RN_INSTRUMENT && (mode & 512)) __builtin_amdgcn_s_setprio(3);
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
   const double na0 = -(double)a0, na1 = -(double)a1, b0d = (double)b0;
   float m0 = g.mem_hp[2 * s], m1 = g.mem_hp[2 * s + 1];
@@ -196,17 +184,12 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
 #pragma unroll
       for (int k = 0; k < 5; k++) g.debug[(size_t)s * RN_DBG_FLOATS + RN_DBG_AC + k] = ac[k];
     }
-    if (RN_INSTRUMENT && (mode & 1024)) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-    }
   }
 }
 // ONE kernel for the four forms.  (Tried: a kernel of its own for int16 input, so that the float forms keep their 101 registers
 // instead of the 128 of the hungriest form -- slower, 0.147 against 0.135 ms at 65,536 streams: inside the common kernel the scheduler
 // works the float forms to the looser budget too, and that is the faster code.  profiles/r6_hp_specialised.txt)
-extern "C" __global__ void __launch_bounds__(4 * WAVE) RN_HP_ATTR
-RN_HP_KERNEL_NAME(RnGroupDev g, const float *__restrict__ in, int slot, int mode) {
+extern "C" __global__ void __launch_bounds__(4 * WAVE) rn_hp_kernel(RnGroupDev g, const float *__restrict__ in, int slot, int mode) {
   if (mode & 2) {
     if (mode & 1) hp_body<true, true>(g, in, slot, mode);
     else hp_body<false, true>(g, in, slot, mode);
@@ -215,7 +198,6 @@ RN_HP_KERNEL_NAME(RnGroupDev g, const float *__restrict__ in, int slot, int mode
     else hp_body<false, false>(g, in, slot, mode);
   }
 }
-#ifndef RN_HP_VARIANT_ONLY
 // ---------------------------------------------------------------------------------------------
 // K0 for a handful of streams (the one-stream states behind rnnoise_process_frame, and batches of up to 64 streams): the
 // same arithmetic with ONE WAVE PER STREAM instead of one lane, arranged for latency.  What is serial stays serial -- the
@@ -345,7 +327,7 @@ __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, co
     }
     // a listed row whose analysis runs as a four-wave workgroup gets its 5 FIR taps there, on a spare wave, beside the
     // transform of X (rn_analysis_rows_kernel): the lags, a third of this kernel's time, are not formed here (bit 8 of
-    // slot_arg set by the launcher: they ARE wanted -- the one-wave analysis of $RNNOISE_AMD_ROWS_K1=1)
+    // slot_arg set by the launcher: they ARE wanted -- rn_launch_hp_rows leaves it clear)
     if (listed && !(slot_arg & 256)) return;
     if (lane == 0) xlp[0] = .5f * (.5f * pb01.y + pb01.x);
     if (lane < 8) xlp[864 + lane] = 0;
@@ -400,11 +382,6 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
 #define RN_HP_ONE_MAX 2048
 #define RN_HP_ONE_MAX_PIPELINED 2048
 #define RN_HP_SPW 64  // streams per wave of the lane = stream kernel
-#if RN_INSTRUMENT
-extern "C" __global__ void rn_hp_slp_kernel(RnGroupDev g, const float *__restrict__ in, int slot, int mode);  // hp_slp.hip
-#else
-#define rn_hp_slp_kernel rn_hp_kernel
-#endif
 extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s16, int slot, hipStream_t st, hipEvent_t e0, hipEvent_t done) {
   // bit 9 of `slot` (batch.cpp): the call is one frame of a PIPELINED multi-frame call -- this kernel then runs on a side stream beside the
   // analysis and network kernels of other frames (the two switches are kept apart because they were different ones until round 6's
@@ -417,27 +394,13 @@ extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s
     RN_LAUNCH(rn_hp_one_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot, in_s16, RnRows{});
     return hipGetLastError();
   }
-  static const int ab = [] { const char *e = RN_LAB_ENV("HP_AB"); return e ? atoi(e) & (256 | 512 | 1024) : 0; }();  // (A/B runs)
-#if RN_INSTRUMENT
-  static const bool slp = [] { const char *e = RN_LAB_ENV("HP_AB"); return e && (atoi(e) & 2048); }();  // (A/B: hp_slp.hip)
-#else
-  const bool slp = false;
-#endif
-  // $RNNOISE_AMD_HP_SPW = 64 | 32 | 16 streams per wave (A/B; default below)
-  static const int spw_shift = [] {
-    const char *e = RN_LAB_ENV("HP_SPW");
-    const int v = e ? atoi(e) : RN_HP_SPW;
-    return v == 16 ? 2 : (v == 32 ? 1 : 0);
-  }();
-  const int spw = WAVE >> spw_shift;
   // (rounds 5-6 had a second build of this kernel with 16-sample blocks at 64 VGPRs -- rn_hp_lean_kernel, a wave of which fits a SIMD
   // beside four analysis waves: +0.5 % at 65,536 streams while the autocorrelation pass re-read the whole pitch ring.  Over the decimated
   // ring the 32-sample form is the faster one inside the pipeline too (profiles/r6_xlp_ring.txt), and with the chains fed from the
   // biquad's registers the 64-register budget spills: gone.)
-  static const int wpb = [] { const char *e = RN_LAB_ENV("HP_WPB"); return e && atoi(e) == 4 ? 4 : 1; }();  // (A/B: waves per workgroup)
-  const int per_block = wpb > 1 ? wpb * WAVE : spw;
-  RN_LAUNCH(slp ? rn_hp_slp_kernel : rn_hp_kernel, dim3((g->n_streams + per_block - 1) / per_block), dim3(wpb * WAVE),
-            0, st, e0, done, *g, static_cast<const float *>(in), slot, 1 | (in_s16 ? 2 : 0) | ab | (spw_shift << 12));
+  // one wave of RN_HP_SPW streams per workgroup
+  RN_LAUNCH(rn_hp_kernel, dim3((g->n_streams + RN_HP_SPW - 1) / RN_HP_SPW), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot,
+            1 | (in_s16 ? 2 : 0));
   return hipGetLastError();
 }
 extern "C" hipError_t rn_launch_hp_passthrough(const RnGroupDev *g, const float *in, int slot, hipStream_t st) {
@@ -446,8 +409,6 @@ extern "C" hipError_t rn_launch_hp_passthrough(const RnGroupDev *g, const float 
 }
 // K0 of a launch group of the one-frame API (rn_dev.h: RnRows): one wave per listed row, float frames from the pool's pinned blocks
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *g, const RnRows *rows, hipStream_t st) {
-  static const int taps_here = [] { const char *e = RN_LAB_ENV("ROWS_K1"); return (e && atoi(e) == 1) ? 256 : 0; }();  // (dsp_kernels.hip: rn_launch_analysis_rows)
-  hipLaunchKernelGGL(rn_hp_one_kernel, dim3(rows->n), dim3(WAVE), 0, st, *g, static_cast<const float *>(nullptr), taps_here, 0, *rows);
+  hipLaunchKernelGGL(rn_hp_one_kernel, dim3(rows->n), dim3(WAVE), 0, st, *g, static_cast<const float *>(nullptr), 0, 0, *rows);
   return hipGetLastError();
 }
-#endif  // RN_HP_VARIANT_ONLY

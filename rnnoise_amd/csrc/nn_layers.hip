@@ -17,19 +17,15 @@
 // and profiles/r5_gru_race.txt why this one could not ship before round 5)
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 rn_nn_gru_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb, int layer) {
-  gru_body<2, 4, 1, false>(g, m, tb, layer);
+  gru_body<2, 4, 1>(g, m, tb, layer);
 }
 // eight waves, a row buffer per unit tile, 152 KB: a workgroup owns its CU
 extern "C" __global__ void __launch_bounds__(512) rn_nn_gru_w8_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb, int layer) {
-  gru_body<2, 8, 3, false>(g, m, tb, layer);
+  gru_body<2, 8, 3>(g, m, tb, layer);
 }
 
-#if RN_INSTRUMENT
-extern "C" const RnGruVariant *rn_gru_lab_variant(const char *name);  // lab/nn_gru_lab.hip: the A/B forms of the instrumented build
-#endif
-
-static const RnGruVariant gru_product[2] = {{"w4", rn_nn_gru_kernel, 256, sizeof(GruLdsT<4, 1>), false, false},
-                                             {"w8", rn_nn_gru_w8_kernel, 512, sizeof(GruLdsT<8, 3>), false, false}};
+static const RnGruVariant gru_product[2] = {{"w4", rn_nn_gru_kernel, 256, sizeof(GruLdsT<4, 1>)},
+                                             {"w8", rn_nn_gru_w8_kernel, 512, sizeof(GruLdsT<8, 3>)}};
 static const RnGruVariant *gru_forced_variant() {
   static const RnGruVariant *const forced = []() -> const RnGruVariant * {
 
@@ -37,19 +33,11 @@ static const RnGruVariant *gru_forced_variant() {
     if (!e || !*e) return nullptr;
     for (const RnGruVariant &v : gru_product)
       if (!strcmp(e, v.name)) return &v;
-#if RN_INSTRUMENT
-    if (const RnGruVariant *v = rn_gru_lab_variant(e)) return v;
-#endif
     fprintf(stderr, "[rnnoise_amd] RNNOISE_AMD_GRU_VARIANT=%s: no such form of the layer kernel in this build (w4 | w8)\n", e);
-    static const RnGruVariant none = {nullptr, nullptr, 0, 0, false, false};
+    static const RnGruVariant none = {nullptr, nullptr, 0, 0};
     return &none;
   }();
   return forced;
-}
-// does the layer-wise network of this process fold the output chains into its layer launches?  (nn_mfma.hip: rn_launch_nn_layers)
-extern "C" int rn_nn_layers_fold(void) {
-  const RnGruVariant *f = gru_forced_variant();
-  return f && f->k && f->fold;
 }
 
 extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, int layer, hipStream_t st,
@@ -59,7 +47,7 @@ extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelD
   // under the eight-wave one stand-alone in every A/B of profiles/r5_gru_bound.txt) once there are more groups than CUs; the eight-wave
   // form while every group has a CU to itself (a four-wave workgroup would then leave each SIMD with ONE wave: 16,384 streams 0.200
   // against 0.174 ms for the three layers + front + dense).  $RNNOISE_AMD_GRU_VARIANT = w4 | w8 forces one (tests run both at every
-  // size); any other name is an error, not a silent default -- the instrumented build knows more names (lab/nn_gru_lab.hip).
+  // size); any other name is an error, not a silent default.
   static const RnGruVariant *const forced = gru_forced_variant();
   if (forced && !forced->k) return hipErrorInvalidValue;
   int dev = 0;
@@ -74,19 +62,7 @@ extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelD
   const RnGruVariant &v = forced ? *forced : gru_product[n_groups > ncu ? 0 : 1];
   // more than 64 KB of LDS is an opt-in, per kernel and device (a process may hold batches on several GPUs)
   if (hipError_t e = rn_gru_opt_in(v, dev)) return e;
-  int grid = n_groups, flags = 0;
-#if RN_INSTRUMENT
-  // persistent lab forms: one workgroup per CU, each walking over groups b, b + grid, ... -- $RNNOISE_AMD_GRU_GRID overrides the count
-  static const int grid_env = [] { const char *e = RN_LAB_ENV("GRU_GRID"); return e ? atoi(e) : 0; }();
-  if (v.persist) grid = grid_env > 0 ? (grid_env < n_groups ? grid_env : n_groups) : (ncu < n_groups ? ncu : n_groups);
-  // gru_body: bit 2 $RNNOISE_AMD_GRU_ACT=0; bits 3-4 $RNNOISE_AMD_GRU_SETTLE; bit 5 $RNNOISE_AMD_GRU_PRIO=0; bit 6 _GRU_TIMELINE (lab forms)
-  static const int flags_env = [] {
-    const char *e = RN_LAB_ENV("GRU_ACT"), *s = RN_LAB_ENV("GRU_SETTLE"), *p = RN_LAB_ENV("GRU_PRIO"), *t = RN_LAB_ENV("GRU_TIMELINE");
-    return ((e && atoi(e) == 0) ? 4 : 0) | ((s ? atoi(s) & 3 : 0) << 3) | ((p && atoi(p) == 0) ? 32 : 0) | ((t && atoi(t)) ? 64 : 0);
-  }();
-  flags = flags_env;
-#endif
-  RN_LAUNCH(v.k, dim3(grid), dim3(v.threads), v.lds, st, e0, e1, *g, *m, *tb, layer | flags);
+  RN_LAUNCH(v.k, dim3(n_groups), dim3(v.threads), v.lds, st, e0, e1, *g, *m, *tb, layer);
   return hipGetLastError();
 }
 

@@ -1,12 +1,9 @@
 // nn_tile_body.inc -- body of the 16-stream tile kernels of nn_mfma.hip, included once per RN_NN_MODE (a template or a
 // shared __device__ function costs the fused kernel 30-80 VGPRs with this compiler: measured 118 -> 150 / 201).
-//   RN_NN_MODE 0: the whole network;  1: front of the layer-wise schedule (conv1, conv2, image to act_q[0], f32 copy to nn_act);
-//   2: the front with the output chains (nn_gru.h: gru_body FOLD) taken through the conv2 segment: partial sums to g.gains / g.vad
+//   RN_NN_MODE 0: the whole network;  1: front of the layer-wise schedule (conv1, conv2, image to act_q[0], f32 copy to nn_act)
 // NWAVES (8 | 16) is whatever the including file has it at: every loop over row / unit tiles strides by it, the one-per-wave roles
 // (conv1's eight row tiles, the 512 producer threads of the dense phase, the three chain waves) stay on the first eight waves.
-#if RN_NN_MODE == 2
-  __shared__ __attribute__((aligned(16))) FrontFoldLds L;
-#elif RN_NN_MODE == 1
+#if RN_NN_MODE == 1
   __shared__ __attribute__((aligned(16))) FrontLds L;
 #else
   __shared__ __attribute__((aligned(16))) MfmaLds L;
@@ -147,12 +144,7 @@
       v4f o = int8_finish(m.conv2, row0, int8_tile(m.conv2.wmf, rt, lane, L.xq[0]));
 #pragma unroll
       for (int r = 0; r < 4; r++) o[r] = tanh_x86(o[r], lut);
-#if RN_NN_MODE == 2
-      // f32 for the output chains, in their order [input / 4][stream][input % 4] (over the conv1 input, dead behind conv1's barrier)
-      *reinterpret_cast<v4f *>(&L.stage[4 * rt + gq][n][0]) = o;
-#else
       if (s0 + n < N) *reinterpret_cast<v4f *>(g.nn_act + (size_t)sn * RN_GRU + row0) = o;  // f32 copy for dense_out
-#endif
       *reinterpret_cast<int *>(L.xq[1] + frag_off(n, row0)) = pack4(o[0], o[1], o[2], o[3]);
     }
   }
@@ -162,42 +154,6 @@
   {
     v4i *dst = reinterpret_cast<v4i *>(g.act_q[0] + (size_t)blockIdx.x * (KT * 64 * 16));
     for (int i = tid; i < KT * 64; i += NTHREADS) dst[i] = reinterpret_cast<const v4i *>(L.xq[1])[i];
-  }
-#endif
-#if RN_NN_MODE == 2
-  // The image goes to the layer kernels (waves 3..7) while waves 0 and 1 take dense_out's two chains (row tile = wave) and wave 2, lane
-  // = stream, vad_dense through the 384 conv2 outputs -- the first segment of cat (src/rnn.c:53-58); the 33 partial sums of a stream go
-  // to g.gains / g.vad, where the first layer kernel picks them up (nn_gru.h: "the output chains").
-  __syncthreads();
-  if (wave >= 3) {
-    v4i *dst = reinterpret_cast<v4i *>(g.act_q[0] + (size_t)blockIdx.x * (KT * 64 * 16));
-    for (int i = tid - 3 * 64; i < KT * 64; i += NTHREADS - 3 * 64) dst[i] = reinterpret_cast<const v4i *>(L.xq[1])[i];
-  } else if (wave < 2) {
-    constexpr int NG = RN_GRU / 16, AD2 = 4;  // 24 groups of four chain steps; weight groups in flight
-    const v4f *wq = reinterpret_cast<const v4f *>(m.dense_out.fwm) + (size_t)wave * (RN_CAT / 16) * 64 + lane;
-    v4f wb[AD2];
-#pragma unroll
-    for (int q = 0; q < AD2; q++) wb[q] = wq[q * 64];
-    v4f dacc = {0, 0, 0, 0};
-    const float *bx = &L.stage[0][n][gq];
-#pragma unroll
-    for (int G = 0; G < NG; G++) {
-      const v4f a = wb[G % AD2];
-      if (G + AD2 < NG) wb[G % AD2] = wq[(G + AD2) * 64];
-#pragma unroll
-      for (int e = 0; e < 4; e++) dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], bx[(4 * G + e) * (TS * 4)], dacc, 0, 0, 0);
-    }
-    if (s0 + n < N) *reinterpret_cast<v4f *>(g.gains + (size_t)sn * RN_NB_BANDS + 16 * wave + 4 * gq) = dacc;
-  } else if (lane < TS) {  // unfused mul-then-add, src/vec_avx.h:732-736
-    float vacc = 0;
-    const float *vw = m.vad_dense.fw;
-#pragma unroll 8
-    for (int e = 0; e < RN_GRU / 4; e++) {
-      const v4f x = *reinterpret_cast<const v4f *>(&L.stage[e][lane][0]);
-#pragma unroll
-      for (int i = 0; i < 4; i++) vacc = vacc + vw[4 * e + i] * x[i];
-    }
-    if (s0 + lane < N) g.vad[s0 + lane] = vacc;
   }
 #endif
 #if RN_NN_MODE == 0

@@ -24,9 +24,9 @@
 //   getenv("RNNOISE_AMD_...")   product knobs: configuration, and dispatch thresholds that select between kernels with the
 //                               same bits.  Every one of them is listed in INTEGRATION.md ("Environment variables");
 //                               tests/test_product_surface_cpu.py compares the names found in the product .so with that list.
-//   RN_LAB_ENV("...")           A/B switches, timing experiments and fault injection: read by the INSTRUMENTED build only.  In the
-//                               product the macro is a null constant -- the name is not even in the binary, and no environment
-//                               can steer a drop-in librnnoise.so.0 onto an experiment.
+//   RN_LAB_ENV("...")           read by the INSTRUMENTED build only: TEST_FAIL_GROUP (fault injection, dropin.cpp) and K1_STOP
+//                               (section prefix runs, dsp_kernels.hip).  In the product the macro is a null constant -- the name is
+//                               not even in the binary, and no environment can steer a drop-in librnnoise.so.0 onto them.
 #if RN_INSTRUMENT
 #define RN_LAB_ENV(name) getenv("RNNOISE_AMD_" name)
 #else

@@ -45,20 +45,16 @@ extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *, const RnModelDev *, c
 extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
                                         hipEvent_t, int alone);  // alone: no other kernel of the call runs beside it
 extern "C" hipError_t rn_launch_nn_layers(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t[5][2]);
-extern "C" int rn_nn_layers_launches(void);
 extern "C" hipError_t rn_launch_nn_requant(const RnGroupDev *, hipStream_t);
 extern "C" int rn_nn_mfma_available(void);
 extern "C" hipError_t rn_launch_release_store(void *, long long, hipStream_t);
 #if RN_INSTRUMENT
-extern "C" hipError_t rn_launch_analysis_synth(const RnGroupDev *, const RnGroupDev *, const RnTablesDev *, int, int, void *, int, int, int, hipStream_t,
-                                               hipEvent_t, hipEvent_t);
 extern "C" hipError_t rn_launch_log_energy(const float *, unsigned, float *, unsigned, const double *, hipStream_t);
 extern "C" hipError_t rn_launch_fft_probe(int, const float *, float *, unsigned long long *, int, int, const RnTablesDev *, hipStream_t);
 extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 #endif
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, float *, int, int, hipStream_t);
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, const float *, int, int, hipStream_t);
-extern "C" hipError_t rn_launch_copy_to_host(void *, const void *, size_t, int, hipStream_t);
 
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);

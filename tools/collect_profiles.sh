@@ -31,11 +31,8 @@ bash "$R/tools/configs0_scope.sh" 2>&1 | grep -v amdgpu.ids > "$O/configs0_cthre
 # the host-fed path's copy modes (round 5) and what its step is made of (round 6)
 bash "$R/tools/hostio_sdma.sh" 2>&1 | grep -v amdgpu.ids > "$O/hostio_sdma.txt"
 bash "$R/tools/hostio_breakdown.sh" 2>&1 | grep -v amdgpu.ids > "$O/hostio_breakdown.txt"
-# round 6: what rn_analysis_kernel would take without the bank conflicts of its candidate dots (instrumented library, timing only)
-bash "$R/tools/k1_dots_conflicts.sh" 2>&1 | grep -v amdgpu.ids > "$O/k1_dots_conflicts.txt"
-# round 5's investigations (the layer kernel's lab forms, what the frame pipeline hides): COLLECT_R5=1 repeats them on the instrumented library
+# round 5's investigation (what the frame pipeline hides): COLLECT_R5=1 repeats it
 if [ "${COLLECT_R5:-0}" = 1 ]; then
-  python "$R/tools/gru_variants.py" w4 w8 p v3 2>&1 | grep -v amdgpu.ids > "$O/gru_variants.txt"
   python "$R/tools/overlap_table.py" 2>&1 | grep -v amdgpu.ids > "$O/overlap.txt"
 fi
 python "$R/tools/fft_bench.py" 2>&1 | grep -v amdgpu.ids > "$O/fft_bench.txt"

@@ -20,18 +20,13 @@ CONFIGS = [
     ("default (K1 4 workgroups / CU, GRU w4)", {}),
     ("one stream (no overlap at all)", {"RNNOISE_AMD_PIPE": "9"}),
     ("only the high-pass aside", {"RNNOISE_AMD_PIPE": "1"}),
-    ("K1 at 3 workgroups / CU (52 KB each: 46 KB of LDS and 176 VGPRs per SIMD left for K0 / K3 / front waves)", {"RNNOISE_AMD_K1_LDS": "13000"}),
-    ("K1 at 2 workgroups / CU", {"RNNOISE_AMD_K1_LDS": "20000"}),
     ("GRU w8 (152 KB: a layer workgroup owns its CU)", {"RNNOISE_AMD_GRU_VARIANT": "w8"}),
-    ("GRU v3 (12 waves, 145 VGPRs, persistent)", {"RNNOISE_AMD_GRU_VARIANT": "v3"}),
-    ("K1 at 3 workgroups / CU + GRU w8", {"RNNOISE_AMD_K1_LDS": "13000", "RNNOISE_AMD_GRU_VARIANT": "w8"}),
 ]
 
 
 def bench(env):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-parity", "--steps", "40", "--warmup", "8", "--repeats", "9"],
-                       # (RNNOISE_AMD_K1_LDS and the lab forms of the layer kernel exist in the instrumented library only: every row is measured on it)
-                       env=dict(os.environ, RNNOISE_AMD_LIB=os.path.join(ROOT, "rnnoise_amd", "librnnoise_amd_instr.so"), **env), capture_output=True, text=True, timeout=600)
+                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     return json.loads(lines[-1]) if lines else None
 
@@ -56,7 +51,7 @@ def main():
         rows = []
         facts = [("dsp_kernels", "rn_analysis_kernel", 4, 38.0), ("hp_kernel", "rn_hp_kernel", 1, 0.0), ("dsp_kernels", "rn_synthesis_kernel", 1, 4.9),
                  ("nn_mfma", "rn_nn_front_kernel", 8, 33.0), ("nn_layers", "rn_nn_gru_kernel", 4, 72.0), ("nn_layers", "rn_nn_gru_w8_kernel", 8, 152.0),
-                 ("nn_layers", "rn_nn_gru3_kernel", 12, 152.0), ("nn_layers", "rn_nn_dense_kernel", 8, 78.0)]
+                 ("nn_layers", "rn_nn_dense_kernel", 8, 78.0)]
         for obj, k, w, lds in facts:
             meta, _ = t._kernels(os.path.join(t.BUILD, obj + ".o"))
             v = meta[k]["vgpr_count"]
