@@ -85,6 +85,34 @@ RNNOISE_EXPORT int rnnoise_batch_process_s16(RNNoiseBatch *b, short *out, const 
 RNNOISE_EXPORT int rnnoise_batch_process_device_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad,
                                                     float *d_gains, int n_frames, void *hip_stream);
 
+/* Masked calls: streams that skip frames.  active : [n_frames][n_streams] unsigned char, nonzero = the stream has this frame.
+ * For every stream the result is that of rnnoise_process_frame() on its PRESENT frames only, in order: a present frame gives
+ * out / vad / gains and state bit for bit as the unmasked call; on an absent frame the stream's state is not touched, its row of
+ * `out` is not written (the caller's bytes stay), vad reads 0 and its gains row 32 zeros, as on a silent frame, and the rows of
+ * `in` are not read.  active == NULL: every stream present -- exactly rnnoise_batch_process*.  Buffer shapes as in the unmasked
+ * calls.  The first masked call switches the batch to per-stream frame phase (each stream's pitch ring and spectra slots follow
+ * its own frame count); it stays there until rnnoise_batch_reset, and every call keeps working in it, but the analysis then runs
+ * one stream per workgroup at every batch size (the cost) and rnnoise_batch_train_features* returns -1.
+ * rnnoise_batch_debug_last reports silence = 2 for a stream that was absent from the last frame.
+ * Device forms: device buffers as rnnoise_batch_process_device, asynchronous on hip_stream.  Host forms: the convenience path --
+ * synchronous, staged through device memory with plain copies (no pinned ring or copy engines).  0 / -1. */
+RNNOISE_EXPORT int rnnoise_batch_process_device_masked(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad,
+                                                       float *d_gains, const unsigned char *d_active, int n_frames,
+                                                       void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad,
+                                                           float *d_gains, const unsigned char *d_active, int n_frames,
+                                                           void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_masked(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains,
+                                                const unsigned char *active, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
+                                                    const unsigned char *active, int n_frames);
+
+/* Back to rnnoise_init()'s state for the listed streams only; every other stream is untouched.  Host list: synchronous, -1 if an
+ * index is out of range (nothing is reset then).  Device list (int32 in the batch's device memory): asynchronous on hip_stream,
+ * out-of-range entries ignored.  Duplicates are harmless; n == 0 does nothing.  0 / -1. */
+RNNOISE_EXPORT int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n);
+RNNOISE_EXPORT int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int *d_streams, int n, void *hip_stream);
+
 /* Portable per-stream state: RN_STATE_FLOATS 32-bit words laid out as in rn_layout.h
  * (the 25,128 live bytes of the reference's DenoiseState).  Import requires
  * analysis_mem == the last 480 samples of pitch_buf, which every state produced by the

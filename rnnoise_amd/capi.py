@@ -39,6 +39,8 @@ EXPORTS = [
     "rnnoise_batch_kernel_ms",
     "rnnoise_batch_train_features", "rnnoise_batch_train_features_device", "rnnoise_amd_model_pack", "rnnoise_batch_set_schedule",
     "rnnoise_amd_set_rcp_profile", "rnnoise_amd_rcp_profile", "rnnoise_amd_log10_model",
+    "rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_masked_s16", "rnnoise_batch_process_masked",
+    "rnnoise_batch_process_masked_s16", "rnnoise_batch_reset_streams", "rnnoise_batch_reset_streams_device",
 ]
 
 
@@ -123,6 +125,13 @@ def _load(path, debug):
         L.rnnoise_batch_process_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
         L.rnnoise_batch_process_s16.argtypes = [vp, C.POINTER(C.c_short), C.POINTER(C.c_short), fp, fp, C.c_int]
         L.rnnoise_batch_process_device_s16.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
+        sp, up = C.POINTER(C.c_short), C.POINTER(C.c_ubyte)
+        L.rnnoise_batch_process_device_masked.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
+        L.rnnoise_batch_process_device_masked_s16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
+        L.rnnoise_batch_process_masked.argtypes = [vp, fp, fp, fp, fp, up, C.c_int]
+        L.rnnoise_batch_process_masked_s16.argtypes = [vp, sp, sp, fp, fp, up, C.c_int]
+        L.rnnoise_batch_reset_streams.argtypes = [vp, ip, C.c_int]
+        L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
@@ -296,6 +305,58 @@ class Batch:
         fn = self._L.rnnoise_batch_process_device_s16 if s16 else self._L.rnnoise_batch_process_device
         if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_process_device failed")
+
+    def _masked_args(self, pcm, active, out, dtype):
+        pcm = np.ascontiguousarray(pcm, dtype)
+        T, N, F = pcm.shape
+        assert N == self.n and F == FRAME
+        active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        assert active is None or active.shape == (T, N)
+        if out is None:
+            out = np.zeros_like(pcm)
+        assert out.dtype == dtype and out.shape == pcm.shape and out.flags.c_contiguous
+        return pcm, active, out, T
+
+    def process_masked(self, pcm: np.ndarray, active, want_gains: bool = True, out: np.ndarray | None = None):
+        """pcm: (T, N, 480) float32, active: (T, N) (nonzero = the stream has this frame; None = all) -> (out, vad[T,N],
+        gains[T,N,32]): rnnoise_batch_process_masked.  Absent rows of `out` are not written: they keep what `out` held (zeros
+        when it is not given)."""
+        pcm, active, out, T = self._masked_args(pcm, active, out, np.float32)
+        vad = np.empty((T, self.n), np.float32)
+        gains = np.empty((T, self.n, NB_BANDS), np.float32) if want_gains else None
+        ap = active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None
+        if self._L.rnnoise_batch_process_masked(self.h, _fp(out), _fp(pcm), _fp(vad), _fp(gains), ap, T):
+            raise RuntimeError("rnnoise_batch_process_masked failed")
+        return out, vad, gains
+
+    def process_masked_s16(self, pcm: np.ndarray, active, want_gains: bool = True, out: np.ndarray | None = None):
+        """process_masked on int16 PCM (rnnoise_batch_process_masked_s16)"""
+        pcm, active, out, T = self._masked_args(pcm, active, out, np.int16)
+        vad = np.empty((T, self.n), np.float32)
+        gains = np.empty((T, self.n, NB_BANDS), np.float32) if want_gains else None
+        sp = C.POINTER(C.c_short)
+        ap = active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None
+        if self._L.rnnoise_batch_process_masked_s16(self.h, out.ctypes.data_as(sp), pcm.ctypes.data_as(sp), _fp(vad), _fp(gains), ap, T):
+            raise RuntimeError("rnnoise_batch_process_masked_s16 failed")
+        return out, vad, gains
+
+    def process_masked_device(self, d_out: int, d_in: int, d_vad: int, d_gains: int, d_active: int, n_frames: int, stream: int = 0,
+                              s16: bool = False):
+        """Raw device pointers (ints), asynchronous on `stream`; d_active: [n_frames][N] bytes, 0 = every stream present."""
+        fn = self._L.rnnoise_batch_process_device_masked_s16 if s16 else self._L.rnnoise_batch_process_device_masked
+        if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_active or None, n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_process_device_masked failed")
+
+    def reset_streams(self, indices):
+        """the listed streams back to rnnoise_init()'s state (synchronous; ValueError on an index out of range)"""
+        idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.int32)
+        if self._L.rnnoise_batch_reset_streams(self.h, idx.ctypes.data_as(C.POINTER(C.c_int)), int(idx.size)):
+            raise ValueError("rnnoise_batch_reset_streams failed (stream index out of range?)")
+
+    def reset_streams_device(self, d_streams: int, n: int, stream: int = 0):
+        """the same from an int32 device list, asynchronous on `stream` (out-of-range entries ignored)"""
+        if self._L.rnnoise_batch_reset_streams_device(self.h, d_streams or None, n, stream or None):
+            raise RuntimeError("rnnoise_batch_reset_streams_device failed")
 
     def export_state(self, stream: int) -> np.ndarray:
         s = np.empty(STATE_FLOATS, np.float32)

@@ -67,6 +67,7 @@ size_t batch_layout(RnGroupDev &g, uint8_t *base, int n) {
   for (int k = 0; k < 4; k++) g.act_q[k] = carve<int8_t>(p, (N + 15) / 16 * 6144);
   g.lpc2 = carve<float>(p, 8 * N * RN_RING_SLOTS);
   g.train_clean_mem = carve<float>(p, RN_FRAME_SIZE * N);
+  g.phase = carve<int>(p, N);  // (moved to RNNoiseBatch::phase_buf: the group carries it only in per-stream mode)
   return (size_t)(p - base);
 }
 
@@ -104,6 +105,8 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
   v.lpc2 += 8 * f;
   v.train_clean_mem += RN_FRAME_SIZE * f;
   if (v.debug) v.debug += RN_DBG_FLOATS * f;
+  if (v.phase) v.phase += f;
+  if (v.active) v.active += f;  // (rows of the mask keep the stride n_stride)
   return v;
 }
 
@@ -193,6 +196,8 @@ extern "C" RNNoiseBatch *rnnoise_batch_create(RNNModel *model, int n_streams, in
     return nullptr;
   }
   batch_layout(b->g, static_cast<uint8_t *>(b->arena), n_streams);
+  b->phase_buf = b->g.phase;
+  b->g.phase = nullptr;
   b->scratch_gains = b->g.gains;
   b->scratch_vad = b->g.vad;
   b->features2[0] = b->g.features;
@@ -241,6 +246,7 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   b->parity = 0;
   b->ring_slot = 0;
   b->frame_no = 0;
+  b->per_stream = false;  // (the only way back to lock-step frame phase)
   return 0;
 }
 
@@ -261,11 +267,26 @@ extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
 
 // PCM frames are float (the reference API's sample type) or, with s16 set, int16 converted at the two ends of the step as the
 // reference's only caller does (examples/rnnoise_demo.c:56,58): half the bytes over HBM and, in the host-fed path, PCIe.
+// d_active: the presence mask of a masked call ([n_frames][N] bytes, include/rnnoise_amd.h), or null.
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v, float *d_vad, float *d_gains, int n_frames,
-                              void *hip_stream, bool s16, const FrameIoHooks *hk) {
+                              void *hip_stream, bool s16, const FrameIoHooks *hk, const uint8_t *d_active) {
   if (!b || !d_out_v || !d_in_v || n_frames < 0) return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
+  if (d_active && !b->per_stream && n_frames > 0) {
+    // the first masked call puts the batch into per-stream frame phase: every stream starts at the batch's phase.  ring_slot, not
+    // frame_no: the training-feature calls advance the slots without counting frames (ring_slot % 3 == parity always)
+    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->phase_buf), b->ring_slot, b->n, st));
+    b->per_stream = true;
+  }
+  // the phase fields of the group a kernel of frame f gets (all null / 0 in lock-step mode: today's launches)
+  auto phased = [&](RnGroupDev &g, int f) {
+    if (!b->per_stream) return;
+    g.phase = b->phase_buf;
+    g.active = d_active;
+    g.call_frame = f;
+    g.call_frames = n_frames;
+  };
   const size_t N = b->n, esz = s16 ? sizeof(short) : sizeof(float);
   const char *d_in = static_cast<const char *>(d_in_v);
   char *d_out = static_cast<char *>(d_out_v);
@@ -314,6 +335,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     g.pitch = b->pitch2[c];
     g.vad = d_vad ? d_vad + buf(f) * N : b->scratch_vad;
     g.gains = d_gains ? d_gains + buf(f) * N * RN_NB_BANDS : b->scratch_gains;
+    phased(g, f);
     return g;
   };
   auto highpass = [&](int f) -> int {  // K0 of frame f on stream sc
@@ -335,7 +357,9 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     {
       TimedLaunch t(b, 3);
       b->cur_hp[f & 7] = t.on ? t.stop() : (pipelined ? b->own_hp[f & 7] : nullptr);
-      HIP_OK(rn_launch_hp(&b->g, d_in + buf(f) * N * RN_FRAME_SIZE * esz, s16, ((b->ring_slot + f) % RN_RING_SLOTS) | (pipelined ? 512 : 0), sc, t.start(),
+      RnGroupDev gh = b->g;
+      phased(gh, f);
+      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * N * RN_FRAME_SIZE * esz, s16, ((b->ring_slot + f) % RN_RING_SLOTS) | (pipelined ? 512 : 0), sc, t.start(),
                           b->cur_hp[f & 7]));
     }
     if (hk && hk->after_hp(f, sc)) return -1;
@@ -420,6 +444,90 @@ extern "C" int rnnoise_batch_process_device_s16(RNNoiseBatch *b, short *d_out, c
   return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true);
 }
 
+// ---- masked calls and per-stream reset (include/rnnoise_amd.h) ----
+extern "C" int rnnoise_batch_process_device_masked(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad, float *d_gains,
+                                                   const unsigned char *d_active, int n_frames, void *hip_stream) {
+  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, false, nullptr, d_active);
+}
+
+extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad,
+                                                       float *d_gains, const unsigned char *d_active, int n_frames, void *hip_stream) {
+  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true, nullptr, d_active);
+}
+
+namespace {
+// The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
+// ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
+// the caller left them.
+int batch_process_masked_host(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
+                              int n_frames, bool s16) {
+  if (!b || !out || !in || n_frames < 0) return -1;
+  if (!active) return s16 ? rnnoise_batch_process_s16(b, (short *)out, (const short *)in, vad, gains, n_frames)
+                          : rnnoise_batch_process(b, (float *)out, (const float *)in, vad, gains, n_frames);
+  if (n_frames == 0) return 0;
+  ON_DEVICE(b->device);
+  const size_t fs = (size_t)n_frames * b->n, pcm = fs * RN_FRAME_SIZE * (s16 ? 2 : 4);
+  const size_t o_in = 0, o_out = pcm, o_vad = 2 * pcm, o_gains = o_vad + fs * 4, o_act = o_gains + fs * RN_NB_BANDS * 4,
+               total = o_act + fs;
+  char *d = nullptr;
+  HIP_OK(hipMalloc((void **)&d, total));
+  int rc = -1;
+  if (hipMemcpy(d + o_in, in, pcm, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess &&
+      batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,
+                                n_frames, nullptr, s16, nullptr, (const uint8_t *)(d + o_act)) == 0 &&
+      hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d + o_out, pcm, hipMemcpyDeviceToHost) == hipSuccess &&
+      (!vad || hipMemcpy(vad, d + o_vad, fs * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+      (!gains || hipMemcpy(gains, d + o_gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost) == hipSuccess))
+    rc = 0;
+  hipFree(d);
+  return rc;
+}
+
+// zero state for the n streams of the device list d_list, on st; the layer-wise network's state images of their tiles follow
+// (rn_dev.h: act_q) while they are in use, so that a reset costs no re-quantisation of the whole batch at the next step
+int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) {
+  HIP_OK(rn_launch_state_scatter(&b->g, nullptr, 0, 0, st, d_list, n));
+  if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n));
+  return 0;
+}
+}  // namespace
+
+extern "C" int rnnoise_batch_process_masked(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains,
+                                            const unsigned char *active, int n_frames) {
+  return batch_process_masked_host(b, out, in, vad, gains, active, n_frames, false);
+}
+
+extern "C" int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
+                                                const unsigned char *active, int n_frames) {
+  return batch_process_masked_host(b, out, in, vad, gains, active, n_frames, true);
+}
+
+extern "C" int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n) {
+  if (!b || n < 0 || (n > 0 && !streams)) return -1;
+  for (int i = 0; i < n; i++)
+    if (streams[i] < 0 || streams[i] >= b->n) return -1;
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset and import_state)
+  int *d = nullptr;
+  HIP_OK(hipMalloc((void **)&d, (size_t)n * sizeof(int)));
+  int rc = -1;
+  if (hipMemcpy(d, streams, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess && reset_streams_on(b, d, n, nullptr) == 0 &&
+      hipDeviceSynchronize() == hipSuccess)
+    rc = 0;
+  hipFree(d);
+  return rc;
+}
+
+extern "C" int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int *d_streams, int n, void *hip_stream) {
+  if (!b || n < 0 || (n > 0 && !d_streams)) return -1;
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  return reset_streams_on(b, d_streams, n, static_cast<hipStream_t>(hip_stream));
+}
+
 // ---- training-feature extraction (reference loop src/dump_features.c:466-491) ----
 extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_records, const float *d_clean,
                                                    const float *d_noisy, const float *d_vad, const int *d_lowpass,
@@ -427,6 +535,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
                                                    void *hip_stream) {
   if (!b || !d_records || !d_clean || !d_noisy || !d_vad || !d_lowpass || !d_band_lp || !d_noise_free || n_frames < 0)
     return -1;
+  if (b->per_stream) return -1;  // (extraction runs in lock-step frame phase only)
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
   const size_t N = b->n;
@@ -449,7 +558,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
 extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, const float *clean, const float *noisy,
                                             const float *vad, const int *lowpass, const int *band_lp,
                                             const int *noise_free, int n_frames) {
-  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0) return -1;
+  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream) return -1;
   ON_DEVICE(b->device);
   const size_t N = b->n, fb = (size_t)n_frames * N * RN_FRAME_SIZE * 4;
   char *dev = nullptr;
@@ -477,6 +586,15 @@ extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, con
 #define D2H(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyDeviceToHost))
 #define H2D(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyHostToDevice))
 
+namespace {
+// frame phase of stream s (the slots its next frame writes: ring slot p % RN_RING_SLOTS, spectra slot p % RN_SPEC_SLOTS), after a drain
+int stream_phase(RNNoiseBatch *b, int s, int &p) {
+  p = b->ring_slot;
+  if (b->per_stream) HIP_OK(hipMemcpy(&p, b->phase_buf + s, sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+
 // State migration: one gather / scatter kernel (state_kernels.hip) and one copy per call.  Synchronous with everything
 // the batch has in flight (the caller's streams are not known here, so the device is drained first).
 extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
@@ -484,9 +602,11 @@ extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
   if (!b->state_stage) HIP_OK(hipMalloc((void **)&b->state_stage, RN_STATE_FLOATS * sizeof(float)));
+  int p;
+  if (stream_phase(b, s, p)) return -1;
   const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_gather(&v, b->state_stage, (b->ring_slot + RN_RING_SLOTS - 1) % RN_RING_SLOTS,
-                                (b->parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, nullptr));
+  HIP_OK(rn_launch_state_gather(&v, b->state_stage, (p + RN_RING_SLOTS - 1) % RN_RING_SLOTS,
+                                (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, nullptr));
   D2H(f, b->state_stage, RN_STATE_FLOATS);  // (a blocking copy on the null stream: ordered after the kernel)
   return 0;
 }
@@ -502,9 +622,11 @@ extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f
   if (!b->state_stage) HIP_OK(hipMalloc((void **)&b->state_stage, RN_STATE_FLOATS * sizeof(float)));
   H2D(b->state_stage, f, RN_STATE_FLOATS);
   b->img_valid = false;
+  int p;
+  if (stream_phase(b, s, p)) return -1;
   const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_scatter(&v, b->state_stage, (b->ring_slot + RN_RING_SLOTS - 1) % RN_RING_SLOTS,
-                                 (b->parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, nullptr));
+  HIP_OK(rn_launch_state_scatter(&v, b->state_stage, (p + RN_RING_SLOTS - 1) % RN_RING_SLOTS,
+                                 (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, nullptr));
   HIP_OK(hipStreamSynchronize(nullptr));
   return 0;
 }

@@ -1628,8 +1628,18 @@ rn_analysis_single_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity, Rn
   //  kernel 80 KB of code, more than the instruction cache two CUs share)
   const bool listed = rows.n > 0;
   const uint32_t re = listed ? rows.e[blockIdx.x] : 0u;
-  analysis_body<false, 1>(g, tb, listed ? RN_ROW_RING(re) : slot, listed ? RN_ROW_SPEC(re) : parity, RnTrainArgs{},
-                          listed ? RN_ROW_OF(re) : -1);
+  int ring = listed ? RN_ROW_RING(re) : slot, spec = listed ? RN_ROW_SPEC(re) : parity;
+  if (!listed && g.phase) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
+    bool present;
+    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, blockIdx.x, present));  // (the workgroup's one stream: uniform)
+    if (!present) {  // an absent stream: the sentinel silence = 2 keeps the network off its state, and nothing else is written
+      if (threadIdx.x == 0) g.silence[blockIdx.x] = 2;
+      return;
+    }
+    ring = p % RN_RING_SLOTS;
+    spec = p % RN_SPEC_SLOTS;
+  }
+  analysis_body<false, 1>(g, tb, ring, spec, RnTrainArgs{}, listed ? RN_ROW_OF(re) : -1);
 }
 
 // A launch group of the one-frame API, for LATENCY: one workgroup of K1_SPW waves per listed row, every wave working on that
@@ -1711,8 +1721,17 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
   // indefinite" 0x80000000 when out of range or NaN -- then the low 16 bits)
   const bool listed = rows.n > 0;  // a launch group of the one-frame API (rn_dev.h: RnRows)
   const uint32_t re = listed ? rows.e[blockIdx.x] : 0u;
-  const int parity = listed ? RN_ROW_SPEC(re) : (parity_arg & 255);
-  const int prev = listed ? (parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS : prev_arg;
+  int parity = listed ? RN_ROW_SPEC(re) : (parity_arg & 255);
+  int prev = listed ? (parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS : prev_arg;
+  if (!listed && g.phase) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
+    bool present;
+    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, blockIdx.x, present));  // (the wave's one stream: uniform)
+    // the call's last frame advances the stream's phase (every kernel of the call that reads it has finished: batch.cpp)
+    if (g.call_frame == g.call_frames - 1 && threadIdx.x == 0) g.phase[blockIdx.x] = (p + (present ? 1 : 0)) % RN_RING_SLOTS;
+    if (!present) return;  // an absent stream: neither `out` nor any state is written
+    parity = p % RN_SPEC_SLOTS;
+    prev = (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
+  }
   const bool out_s16 = !listed && (parity_arg & 256);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   SynthLds &L = *reinterpret_cast<SynthLds *>(smem_raw);
@@ -1908,7 +1927,8 @@ extern "C" hipError_t rn_launch_analysis(const RnGroupDev *g, const RnTablesDev 
   // A/B runs only: RNNOISE_AMD_K1_SPW=1 / 4 forces one / K1_SPW streams per workgroup
   static const int spw_force = [] { const char *e = getenv("RNNOISE_AMD_K1_SPW"); return e ? atoi(e) : 0; }();
   const int n = g->n_streams;
-  const bool single = spw_force == 1 || (spw_force == 0 && n < RN_K1_MULTI_MIN_STREAMS);
+  // (per-stream frame phase: the one-stream form at every size -- rn_analysis_kernel's four streams share their narrow phases)
+  const bool single = g->phase || spw_force == 1 || (spw_force == 0 && n < RN_K1_MULTI_MIN_STREAMS);
   if (single) {
     RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity, RnRows{});
   } else {

@@ -23,7 +23,7 @@
 // The body is compiled once per (high-pass applied, int16 input): as run-time flags the two were tested inside the block loop, per
 // float4, and behind those joins the compiler could no longer count the loads in flight -- it waited with vmcnt(0) in front of every
 // block's arithmetic, i.e. for the NEXT block's loads it had just issued: the one-block prefetch hid nothing (round 6, last day).
-template <bool HP_ON, bool IN_S16>
+template <bool HP_ON, bool IN_S16, bool PHASED = false>
 __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__restrict__ in, int slot, int mode) {
   // mode: bit 0 = apply the high-pass (inference); bit 1 = `in` holds int16 samples, converted as the reference's only caller
   // does (examples/rnnoise_demo.c:56: x[i] = tmp[i], short -> float, exact)
@@ -33,6 +33,11 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
   // (one wave per workgroup, which is what rn_launch_hp launches; or four whole waves: blockDim.x = 256)
   const int s = blockDim.x > WAVE ? blockIdx.x * blockDim.x + threadIdx.x : blockIdx.x * spw + threadIdx.x;
   if ((blockDim.x == WAVE && (int)threadIdx.x >= spw) || s >= g.n_streams) return;
+  if (PHASED) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase): the lane's own ring slot; an absent stream writes nothing
+    bool present;
+    slot = rn_stream_phase(g, s, present) % RN_RING_SLOTS;
+    if (!present) return;
+  }
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
   const double na0 = -(double)a0, na1 = -(double)a1, b0d = (double)b0;
   float m0 = g.mem_hp[2 * s], m1 = g.mem_hp[2 * s + 1];
@@ -50,7 +55,9 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
   const float xlp0 = .5f * (.5f * (pb01.y) + pb01.x);
   // BLK float4 (32 samples = one 128-byte line per stream at BLK = 8) per block, the next block's loads in flight while this one is
   // consumed: with one wave per SIMD nothing else hides the HBM round trip
-  constexpr int BLK = RN_HP_BLK;  // float4 per block
+  // (per-stream phase: half the blocks in flight.  Its slot-dependent addresses are per lane there, and at eight float4 per block the
+  //  kernel's register budget -- four waves per SIMD, which the lock-step forms need -- spilled over)
+  constexpr int BLK = PHASED ? RN_HP_BLK / 2 : RN_HP_BLK;  // float4 per block
   float4 cur[BLK], nxt[BLK];
   const short4 *x16 = reinterpret_cast<const short4 *>(reinterpret_cast<const short *>(in) + (size_t)s * RN_FRAME_SIZE);
   auto load4 = [&](int idx) -> float4 {
@@ -189,8 +196,12 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
 // ONE kernel for the four forms.  (Tried: a kernel of its own for int16 input, so that the float forms keep their 101 registers
 // instead of the 128 of the hungriest form -- slower, 0.147 against 0.135 ms at 65,536 streams: inside the common kernel the scheduler
 // works the float forms to the looser budget too, and that is the faster code.  profiles/r6_hp_specialised.txt)
+// (bit 4 of mode: per-stream frame phase, the slot of each lane from RnGroupDev::phase -- it enters only the lane's addresses)
 extern "C" __global__ void __launch_bounds__(4 * WAVE) rn_hp_kernel(RnGroupDev g, const float *__restrict__ in, int slot, int mode) {
-  if (mode & 2) {
+  if (mode & 16) {
+    if (mode & 2) hp_body<true, true, true>(g, in, slot, mode);
+    else hp_body<true, false, true>(g, in, slot, mode);
+  } else if (mode & 2) {
     if (mode & 1) hp_body<true, true>(g, in, slot, mode);
     else hp_body<false, true>(g, in, slot, mode);
   } else {
@@ -367,7 +378,13 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
   // (rows: the launch groups of the one-frame API, rn_dev.h -- the block's stream, ring slot and frame buffer come from the list)
   const bool listed = rows.n > 0;
   const uint32_t re = listed ? rows.e[blockIdx.x] : 0u;
-  const int s = listed ? RN_ROW_OF(re) : (int)blockIdx.x, slot = listed ? RN_ROW_RING(re) : slot_arg;
+  const int s = listed ? RN_ROW_OF(re) : (int)blockIdx.x;
+  int slot = listed ? RN_ROW_RING(re) : slot_arg;
+  if (!listed && g.phase) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase); an absent stream writes nothing
+    bool present;
+    slot = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, s, present)) % RN_RING_SLOTS;  // (the wave's one stream: uniform)
+    if (!present) return;
+  }
   const float *in_row = listed ? rows.io + (size_t)s * RN_ROW_IO : in + (size_t)s * RN_FRAME_SIZE;
   if (in_s16) hp_one_body<true>(L, g, in, in_row, listed, s, slot, slot_arg);
   else hp_one_body<false>(L, g, in, in_row, listed, s, slot, slot_arg);
@@ -400,7 +417,7 @@ extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s
   // biquad's registers the 64-register budget spills: gone.)
   // one wave of RN_HP_SPW streams per workgroup
   RN_LAUNCH(rn_hp_kernel, dim3((g->n_streams + RN_HP_SPW - 1) / RN_HP_SPW), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot,
-            1 | (in_s16 ? 2 : 0));
+            1 | (in_s16 ? 2 : 0) | (g->phase ? 16 : 0));
   return hipGetLastError();
 }
 extern "C" hipError_t rn_launch_hp_passthrough(const RnGroupDev *g, const float *in, int slot, hipStream_t st) {

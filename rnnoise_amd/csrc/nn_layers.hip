@@ -211,8 +211,11 @@ extern "C" hipError_t rn_launch_nn_dense(const RnGroupDev *g, const RnModelDev *
 
 // Rebuilds the state images act_q[1..3] from the f32 GRU state (after a reset, an import, or steps taken by the other
 // network kernels): one workgroup per (tile, layer).
-extern "C" __global__ void __launch_bounds__(256) rn_nn_requant_kernel(RnGroupDev g) {
-  const int tile = blockIdx.x, layer = blockIdx.y, N = g.n_streams;
+// (list: block x re-quantises the tile of stream list[x] -- the streams a reset just zeroed; entries outside the batch are ignored)
+extern "C" __global__ void __launch_bounds__(256) rn_nn_requant_kernel(RnGroupDev g, const int *__restrict__ list) {
+  const int N = g.n_streams, ls = list ? list[blockIdx.x] : 0;
+  if (list && (ls < 0 || ls >= N)) return;
+  const int tile = list ? ls / TS : (int)blockIdx.x, layer = blockIdx.y;
   const float *st = g.gru_state + (size_t)layer * g.n_stride * RN_GRU;
   int8_t *img = g.act_q[layer + 1] + (size_t)tile * (KT * 64 * 16);
   for (int e = threadIdx.x; e < TS * 96; e += 256) {
@@ -221,8 +224,9 @@ extern "C" __global__ void __launch_bounds__(256) rn_nn_requant_kernel(RnGroupDe
     *reinterpret_cast<int *>(img + frag_off(q, c4)) = pack4(h[0], h[1], h[2], h[3]);
   }
 }
-extern "C" hipError_t rn_launch_nn_requant(const RnGroupDev *g, hipStream_t st) {
-  hipLaunchKernelGGL(rn_nn_requant_kernel, dim3((g->n_streams + TS - 1) / TS, 3), dim3(256), 0, st, *g);
+extern "C" hipError_t rn_launch_nn_requant(const RnGroupDev *g, hipStream_t st, const int *list, int n) {
+  if (list && n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rn_nn_requant_kernel, dim3(list ? n : (g->n_streams + TS - 1) / TS, 3), dim3(256), 0, st, *g, list);
   return hipGetLastError();
 }
 

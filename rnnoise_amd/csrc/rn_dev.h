@@ -145,6 +145,13 @@ struct RnGroupDev {
                        //   (RNNoiseBatch::img_valid; rn_launch_nn_requant rebuilds them).  Whole batches only, never offset by views.
   float *train_clean_mem;  // [N][480] analysis memory of the clean stream (training-feature extraction only)
   float *debug;        // [N][RN_DBG_FLOATS] pitch stage taps, or null (tests only)
+  // per-stream frame phase (include/rnnoise_amd.h: masked calls).  Null `phase` on every lock-step launch: the kernels then take the
+  // ring and spectra slots from their launch arguments.  Set, stream s is at frame phase p = phase[s] + (frames of s present in
+  // 0 .. call_frame - 1) of the call: ring slot p % RN_RING_SLOTS, spectra slot p % RN_SPEC_SLOTS (rn_stream_phase).  The K0 / K1 / K3
+  // forms that own one stream per workgroup or lane honour it; the synthesis kernel of the call's last frame advances phase[s].
+  int *phase;                  // [N] frame phase of each stream at the start of the call, mod RN_RING_SLOTS
+  const uint8_t *active;       // [call_frames][n_stride] nonzero = the stream has this frame; null = every stream present
+  int call_frame, call_frames; // frame of the call this launch works on; frames in the call
 };
 
 // Row list of the one-frame API (dropin.cpp: the combiner behind rnnoise_process_frame).  Concurrent rnnoise_process_frame calls on
@@ -234,6 +241,21 @@ __device__ __forceinline__ void rn_fir_taps_from_ac(float (&ac)[5], float (&o)[5
   o[2] = lpc[2] + c1 * lpc[1];
   o[3] = lpc[3] + c1 * lpc[2];
   o[4] = c1 * lpc[3];
+}
+// Frame phase of stream s at frame g.call_frame of a call in per-stream mode (g.phase set; rn_dev.h: RnGroupDev) and whether the stream
+// has that frame.  At most call_frame + 1 byte loads, down the stream's column of the mask.
+__device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, bool &present) {
+  typedef __attribute__((address_space(1))) const uint8_t gu8;
+  int p = *(__attribute__((address_space(1))) const int *)(g.phase + s);
+  present = true;
+  if (g.active) {
+    gu8 *a = (gu8 *)(g.active + s);
+    for (int f = 0; f < g.call_frame; f++) p += a[(size_t)f * g.n_stride] != 0;
+    present = a[(size_t)g.call_frame * g.n_stride] != 0;
+  } else {
+    p += g.call_frame;
+  }
+  return p;
 }
 #include <hip/hip_ext.h>
 // Launch with optional start / stop events: they are bound to the dispatch packet itself (hipExtLaunchKernel), so

@@ -45,7 +45,7 @@ extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *, const RnModelDev *, c
 extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
                                         hipEvent_t, int alone);  // alone: no other kernel of the call runs beside it
 extern "C" hipError_t rn_launch_nn_layers(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t[5][2]);
-extern "C" hipError_t rn_launch_nn_requant(const RnGroupDev *, hipStream_t);
+extern "C" hipError_t rn_launch_nn_requant(const RnGroupDev *, hipStream_t, const int *list = nullptr, int n = 0);
 extern "C" int rn_nn_mfma_available(void);
 extern "C" hipError_t rn_launch_release_store(void *, long long, hipStream_t);
 #if RN_INSTRUMENT
@@ -54,7 +54,8 @@ extern "C" hipError_t rn_launch_fft_probe(int, const float *, float *, unsigned 
 extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 #endif
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, float *, int, int, hipStream_t);
-extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, const float *, int, int, hipStream_t);
+extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, const float *, int, int, hipStream_t, const int *list = nullptr,
+                                              int n = 0);
 
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);
@@ -158,6 +159,10 @@ struct RNNoiseBatch {
   float *features2[2] = {nullptr, nullptr};
   int *silence2[2] = {nullptr, nullptr}, *pitch2[2] = {nullptr, nullptr};
   int ring_slot = 0;  // pitch-ring slot the next frame is written to
+  // per-stream frame phase (include/rnnoise_amd.h: masked calls): from the first masked call until rnnoise_batch_reset the kernels
+  // take each stream's ring and spectra slots from phase_buf (rn_dev.h: RnGroupDev::phase) instead of ring_slot / parity
+  bool per_stream = false;
+  int *phase_buf = nullptr;  // [N] in the arena
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
   hipStream_t side = nullptr, side_hp = nullptr;
@@ -293,5 +298,6 @@ void pools_free(RNNModel *model);                                    // dropin.c
 RnGroupDev group_view(const RnGroupDev &g, int first, int count);    // batch.cpp
 int nn_one_max_streams();                                            // batch.cpp
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out, const void *d_in, float *d_vad, float *d_gains, int n_frames,
-                              void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr);  // batch.cpp
+                              void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr,
+                              const uint8_t *d_active = nullptr);  // batch.cpp
 void host_io_release(RNNoiseBatch *b);                               // host_io.cpp

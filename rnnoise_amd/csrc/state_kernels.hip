@@ -35,10 +35,35 @@ rn_state_gather_kernel(RnGroupDev g, float *__restrict__ flat, int newest_slot, 
   }
 }
 
-// stream s of the view <- flat[s][RN_STATE_FLOATS] (analysis_mem is implied by pitch_buf and not stored)
+// stream s of the view <- flat[s][RN_STATE_FLOATS] (analysis_mem is implied by pitch_buf and not stored).
+// list (optional): block b works on stream list[b] instead of stream b; entries outside the view are ignored.  flat == null: the zero
+// state of rnnoise_init() -- every slot of the two rings and of the spectra, whatever the stream's frame phase.
 extern "C" __global__ void __launch_bounds__(1024)
-rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ flat, int newest_slot, int last) {
-  const size_t s = blockIdx.x, N = g.n_stride;
+rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ flat, int newest_slot, int last, const int *__restrict__ list) {
+  const int sl = list ? list[blockIdx.x] : (int)blockIdx.x;
+  if (sl < 0 || sl >= g.n_streams) return;
+  const size_t s = sl, N = g.n_stride;
+  if (!flat) {
+    auto zero = [](float *p, int n) {
+      for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0.f;
+    };
+    zero(g.pitch_ring + s * RN_RING_SIZE, RN_RING_SIZE);
+    zero(g.xlp_ring + s * RN_XRING_SIZE, RN_XRING_SIZE);
+    zero(g.synth_mem + s * RN_FRAME_SIZE, RN_FRAME_SIZE);
+    zero(g.mem_hp + 2 * s, 2);
+    zero(g.lastg + s * RN_NB_BANDS, RN_NB_BANDS);
+    zero(g.last_gain + s, 1);
+    zero(g.conv1_state + s * 130, 130);
+    zero(g.conv2_state + s * 256, 256);
+    for (int k = 0; k < 3; k++) zero(g.gru_state + (k * N + s) * RN_GRU, RN_GRU);
+    for (int k = 0; k < RN_SPEC_SLOTS; k++) {
+      zero(g.spec_X[k] + s * RN_SPEC_STRIDE, RN_SPEC_STRIDE);
+      zero(g.spec_P[k] + s * RN_SPEC_STRIDE, RN_SPEC_STRIDE);
+      zero(g.spec_E[k] + s * 96, 96);
+    }
+    if (threadIdx.x == 0) g.last_period[s] = 0;
+    return;
+  }
   const float *f = flat + s * RN_STATE_FLOATS;
   const int ring0 = RN_RING0(newest_slot);
   float *ring = g.pitch_ring + s * RN_RING_SIZE;
@@ -77,8 +102,11 @@ extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *g, float *flat, i
   hipLaunchKernelGGL(rn_state_gather_kernel, dim3(g->n_streams), dim3(1024), 0, st, *g, flat, newest_slot, last);
   return hipGetLastError();
 }
-extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *g, const float *flat, int newest_slot, int last, hipStream_t st) {
-  hipLaunchKernelGGL(rn_state_scatter_kernel, dim3(g->n_streams), dim3(1024), 0, st, *g, flat, newest_slot, last);
+extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *g, const float *flat, int newest_slot, int last, hipStream_t st,
+                                              const int *list, int n) {
+  // (list: n stream indices of the view, one block each; otherwise one block per stream of the view)
+  if (list && n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rn_state_scatter_kernel, dim3(list ? n : g->n_streams), dim3(1024), 0, st, *g, flat, newest_slot, last, list);
   return hipGetLastError();
 }
 

@@ -46,6 +46,20 @@ def register_torch_op():
         T, N = pcm.shape[0], pcm.shape[1]
         return torch.empty_like(pcm), pcm.new_empty((T, N)), pcm.new_empty((T, N, capi.NB_BANDS))
 
+    # the masked form (include/rnnoise_amd.h: rnnoise_batch_process_device_masked): active (T, N) bool / uint8, nonzero = the stream
+    # has this frame.  Absent rows of the returned PCM are zeros, their vad 0 and gains zeros; absent frames leave a stream's state alone.
+    @torch.library.custom_op("rnnoise_amd::process_masked", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)")
+    def process_masked(pcm, active, state, handle):
+        res = _OPS[handle]._run(pcm, active)
+        state.add_(pcm.shape[0])
+        return res
+
+    @process_masked.register_fake
+    def _(pcm, active, state, handle):
+        T, N = pcm.shape[0], pcm.shape[1]
+        return torch.empty_like(pcm), pcm.new_empty((T, N)), pcm.new_empty((T, N, capi.NB_BANDS))
+
     _registered = True
 
 
@@ -83,16 +97,35 @@ class RNNoiseOp:
     def __call__(self, pcm):
         return self.torch.ops.rnnoise_amd.process(pcm, self.state, self.handle)
 
-    def _run(self, pcm):
+    def process_masked(self, pcm, active):
+        """pcm (T, N, 480) float32 CUDA tensor, active (T, N) bool / uint8 CUDA tensor: streams whose frame has not arrived skip it
+        (torch.ops.rnnoise_amd.process_masked)"""
+        return self.torch.ops.rnnoise_amd.process_masked(pcm, active, self.state, self.handle)
+
+    def reset_streams(self, idx):
+        """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
+        a host synchronisation (rnnoise_batch_reset_streams_device: entries out of range are ignored)"""
+        torch = self.torch
+        idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        # (freeing idx afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        self.batch.reset_streams_device(idx.data_ptr(), int(idx.numel()), torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _run(self, pcm, active=None):
         torch = self.torch
         assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[1:] == (self.n, capi.FRAME)
         pcm = pcm.contiguous()
         T = pcm.shape[0]
-        out = torch.empty_like(pcm)
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
         vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
         gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
-        self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T,
-                                  torch.cuda.current_stream(pcm.device).cuda_stream)
+        if active is None:
+            out = torch.empty_like(pcm)
+            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream)
+        else:
+            assert active.is_cuda and active.shape == (T, self.n)
+            act = (active != 0).to(torch.uint8).contiguous()
+            out = torch.zeros_like(pcm)
+            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream)
         return out, vad, gains
 
     def reset(self):
