@@ -113,10 +113,28 @@ RNNOISE_EXPORT int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out,
 RNNOISE_EXPORT int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n);
 RNNOISE_EXPORT int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int *d_streams, int n, void *hip_stream);
 
+/* PCM rate of the batch's calls: 48000 (default), 24000, 16000 or 8000.  Returns the previous rate, or -1 for any other
+ * value (nothing changes then).  Synchronous.  Changing the rate zeroes every stream's resampler history; the
+ * DenoiseState of every stream is untouched.
+ * At rate R, L = 48000 / R (2, 3 or 6), the in / out buffers of every rnnoise_batch_process* call are
+ * [n_frames][n_streams][480 / L] (240, 160 or 80 samples), float or int16 as before; vad and gains stay per 10 ms frame.  Each
+ * stream is upsampled to 48 kHz, run through rnnoise_process_frame() frame by frame, and downsampled back to R (int16: the input
+ * converted exactly, the downsampled float output with the truncating cast of the 48 kHz calls).  The filters are one
+ * Kaiser-windowed sinc per L of 48 L taps (rnnoise_amd/resample.py defines them and their arithmetic bit for bit); up followed
+ * by down is a pure delay of RNNOISE_AMD_RESAMPLE_DELAY = 47 low-rate samples.  Device-buffer calls stay asynchronous and
+ * pipelined; host-buffer calls at R != 48000 are synchronous and staged through device memory (the convenience path of the masked
+ * host calls).  An absent frame of a masked call leaves the stream's resampler history untouched; rnnoise_batch_reset,
+ * rnnoise_batch_reset_streams[_device] and rnnoise_batch_import_state zero it.  rnnoise_batch_train_features* returns -1 at
+ * R != 48000.  The per-frame API of rnnoise.h stays 48 kHz only. */
+#define RNNOISE_AMD_RESAMPLE_DELAY 47
+RNNOISE_EXPORT int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz);
+RNNOISE_EXPORT int rnnoise_batch_pcm_rate(const RNNoiseBatch *b);
+
 /* Portable per-stream state: RN_STATE_FLOATS 32-bit words laid out as in rn_layout.h
  * (the 25,128 live bytes of the reference's DenoiseState).  Import requires
  * analysis_mem == the last 480 samples of pitch_buf, which every state produced by the
- * reference or by export satisfies; -1 otherwise. */
+ * reference or by export satisfies; -1 otherwise.  Import zeroes the stream's resampler history
+ * (rnnoise_batch_set_pcm_rate): the portable state carries none. */
 RNNOISE_EXPORT int rnnoise_batch_export_state(RNNoiseBatch *b, int stream, float *state);
 RNNOISE_EXPORT int rnnoise_batch_import_state(RNNoiseBatch *b, int stream, const float *state);
 

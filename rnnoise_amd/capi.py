@@ -41,7 +41,9 @@ EXPORTS = [
     "rnnoise_amd_set_rcp_profile", "rnnoise_amd_rcp_profile", "rnnoise_amd_log10_model",
     "rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_masked_s16", "rnnoise_batch_process_masked",
     "rnnoise_batch_process_masked_s16", "rnnoise_batch_reset_streams", "rnnoise_batch_reset_streams_device",
+    "rnnoise_batch_set_pcm_rate", "rnnoise_batch_pcm_rate",
 ]
+PCM_RATES = (48000, 24000, 16000, 8000)
 
 
 def _share_hip_runtime_with_torch():
@@ -132,6 +134,8 @@ def _load(path, debug):
         L.rnnoise_batch_process_masked_s16.argtypes = [vp, sp, sp, fp, fp, up, C.c_int]
         L.rnnoise_batch_reset_streams.argtypes = [vp, ip, C.c_int]
         L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
+        L.rnnoise_batch_set_pcm_rate.argtypes = [vp, C.c_int]
+        L.rnnoise_batch_pcm_rate.argtypes = [vp]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
@@ -265,11 +269,28 @@ class Batch:
             raise RuntimeError(f"schedule {schedule} unsupported")
         return r
 
+    def set_pcm_rate(self, hz: int) -> int:
+        """PCM rate of the batch's calls (rnnoise_batch_set_pcm_rate): 48000, 24000, 16000 or 8000; returns the previous one.
+        At rate R the PCM arrays of every call are (T, N, 480 * R // 48000)."""
+        r = self._L.rnnoise_batch_set_pcm_rate(self.h, int(hz))
+        if r < 0:
+            raise ValueError(f"PCM rate {hz} unsupported (one of {PCM_RATES})")
+        return r
+
+    @property
+    def pcm_rate(self) -> int:
+        return self._L.rnnoise_batch_pcm_rate(self.h)
+
+    @property
+    def frame(self) -> int:
+        """samples per stream and frame at the batch's PCM rate (480 at 48 kHz)"""
+        return FRAME * self.pcm_rate // 48000
+
     def process(self, pcm: np.ndarray, want_gains: bool = True):
-        """pcm: (T, N, 480) float32 host array -> (out, vad[T,N], gains[T,N,32])."""
+        """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32])."""
         pcm = np.ascontiguousarray(pcm, np.float32)
         T, N, F = pcm.shape
-        assert N == self.n and F == FRAME
+        assert N == self.n and F == self.frame
         out = np.empty_like(pcm)
         vad = np.empty((T, N), np.float32)
         gains = np.empty((T, N, NB_BANDS), np.float32) if want_gains else None
@@ -282,7 +303,7 @@ class Batch:
         conversions of examples/rnnoise_demo.c:56,58 done on the device."""
         pcm = np.ascontiguousarray(pcm, np.int16)
         T, N, F = pcm.shape
-        assert N == self.n and F == FRAME
+        assert N == self.n and F == self.frame
         out = np.empty_like(pcm)
         vad = np.empty((T, N), np.float32)
         gains = np.empty((T, N, NB_BANDS), np.float32) if want_gains else None
@@ -309,7 +330,7 @@ class Batch:
     def _masked_args(self, pcm, active, out, dtype):
         pcm = np.ascontiguousarray(pcm, dtype)
         T, N, F = pcm.shape
-        assert N == self.n and F == FRAME
+        assert N == self.n and F == self.frame
         active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
         assert active is None or active.shape == (T, N)
         if out is None:

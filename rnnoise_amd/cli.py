@@ -23,14 +23,18 @@ FRAME = capi.FRAME
 
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
-                  vad_csv: bool = False):
+                  vad_csv: bool = False, rate: int = 48000):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
-    at a time (two staging buffers, reused), whatever the file lengths."""
+    at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 24000, 16000 or
+    8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device)."""
     os.makedirs(out_dir, exist_ok=True)
+    FRAME = capi.FRAME * rate // 48000
     n_frames = [os.path.getsize(p) // 2 // FRAME for p in inputs]  # partial tail dropped (rnnoise_demo.c:55)
     N, T = len(inputs), max(n_frames + [0])
     model = capi.Model(model_blob)
     batch = capi.Batch(model, N, device=device)
+    if rate != 48000:
+        batch.set_pcm_rate(rate)
     ins = [open(p, "rb") for p in inputs]
     outs = [open(os.path.join(out_dir, os.path.basename(p) + ".denoised.raw"), "wb") for p in inputs]
     vfs = [open(os.path.join(out_dir, os.path.basename(p) + ".vad.csv"), "w") for p in inputs] if vad_csv else None
@@ -68,9 +72,10 @@ def main(argv=None):
     p.add_argument("--chunk-frames", type=int, default=100)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--vad-csv", action="store_true")
+    p.add_argument("--rate", type=int, default=48000, choices=capi.PCM_RATES, help="sample rate of the RAW files")
     p.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
-    n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv)
+    n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

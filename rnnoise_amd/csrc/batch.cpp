@@ -107,6 +107,11 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
   if (v.debug) v.debug += RN_DBG_FLOATS * f;
   if (v.phase) v.phase += f;
   if (v.active) v.active += f;  // (rows of the mask keep the stride n_stride)
+  if (v.rs_hist) {
+    v.rs_hist += RN_RS_HIST * f;
+    v.rs_up += RN_FRAME_SIZE * f;
+    v.rs_dn += RN_FRAME_SIZE * f;
+  }
   return v;
 }
 
@@ -222,6 +227,7 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   host_io_release(b);
   if (b->state_stage) hipFree(b->state_stage);
   if (b->arena) hipFree(b->arena);
+  if (b->rs_buf) hipFree(b->rs_buf);
   if (b->debug_buf) hipFree(b->debug_buf);
   if (b->side) hipStreamDestroy(b->side);
   if (b->side_hp) {
@@ -241,6 +247,7 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   // this device is drained first, and the cleared state is in place when the call returns
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemset(b->arena, 0, b->arena_bytes));
+  if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float)));  // (the histories; rs_up / rs_dn are scratch)
   HIP_OK(hipDeviceSynchronize());
   b->img_valid = false;
   b->parity = 0;
@@ -249,6 +256,29 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   b->per_stream = false;  // (the only way back to lock-step frame phase)
   return 0;
 }
+
+// PCM rate: K0 upsamples the caller's rows from 48000 / L, K3 downsamples its output back (rn_dev.h: RnGroupDev::rs_L).  48 kHz
+// leaves g.rs_hist / g.rs_L null: every launch is then the one of a batch that never saw this call.
+extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
+  if (!b || (hz != 48000 && hz != 24000 && hz != 16000 && hz != 8000)) return -1;
+  const int old = b->pcm_rate;
+  if (hz == old) return old;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset: nothing of the old rate is in flight)
+  // [N][RN_RS_HIST] histories, then the [N][480] planes rs_up and rs_dn (the 48 kHz frames between the filters and the bodies of K0 / K3)
+  const size_t N = b->n, bytes = N * RN_RS_HIST * sizeof(float);
+  if (hz != 48000 && !b->rs_buf) HIP_OK(hipMalloc((void **)&b->rs_buf, bytes + 2 * N * RN_FRAME_SIZE * sizeof(float)));
+  if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, bytes));
+  HIP_OK(hipDeviceSynchronize());
+  b->pcm_rate = hz;
+  b->g.rs_L = hz == 48000 ? 0 : 48000 / hz;
+  b->g.rs_hist = hz == 48000 ? nullptr : b->rs_buf;
+  b->g.rs_up = hz == 48000 ? nullptr : b->rs_buf + N * RN_RS_HIST;
+  b->g.rs_dn = hz == 48000 ? nullptr : b->rs_buf + N * (RN_RS_HIST + RN_FRAME_SIZE);
+  return old;
+}
+
+extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
 
 extern "C" int rnnoise_batch_set_schedule(RNNoiseBatch *b, int schedule) {
   if (!b || (schedule != 0 && schedule != 1 && schedule != 9)) return -1;
@@ -288,6 +318,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     g.call_frames = n_frames;
   };
   const size_t N = b->n, esz = s16 ? sizeof(short) : sizeof(float);
+  const size_t fl = RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1);  // samples per stream and frame at the batch's PCM rate
   const char *d_in = static_cast<const char *>(d_in_v);
   char *d_out = static_cast<char *>(d_out_v);
   auto buf = [&](int f) -> size_t { return hk ? (size_t)(f % hk->ring) : (size_t)f; };  // frame f's place in the caller's buffers
@@ -359,7 +390,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
       b->cur_hp[f & 7] = t.on ? t.stop() : (pipelined ? b->own_hp[f & 7] : nullptr);
       RnGroupDev gh = b->g;
       phased(gh, f);
-      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * N * RN_FRAME_SIZE * esz, s16, ((b->ring_slot + f) % RN_RING_SLOTS) | (pipelined ? 512 : 0), sc, t.start(),
+      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * N * fl * esz, s16, ((b->ring_slot + f) % RN_RING_SLOTS) | (pipelined ? 512 : 0), sc, t.start(),
                           b->cur_hp[f & 7]));
     }
     if (hk && hk->after_hp(f, sc)) return -1;
@@ -421,7 +452,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     {
       TimedLaunch t(b, 2);
       b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
-      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * N * RN_FRAME_SIZE * esz, s16, cur, prev, st, t.start(), b->cur_k3[f & 7]));
+      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * N * fl * esz, s16, cur, prev, st, t.start(), b->cur_k3[f & 7]));
     }
     if (hk && hk->after_k3(f, st)) return -1;
     // (schedule 1: the high-pass three frames ahead goes out HERE, behind the synthesis launch whose end it starts at)
@@ -455,34 +486,40 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
   return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true, nullptr, d_active);
 }
 
-namespace {
 // The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
 // ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
-// the caller left them.
-int batch_process_masked_host(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
-                              int n_frames, bool s16) {
+// the caller left them.  The masked host calls, and every host call at a PCM rate other than 48 kHz, come here.
+int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
+                         int n_frames, bool s16) {
   if (!b || !out || !in || n_frames < 0) return -1;
-  if (!active) return s16 ? rnnoise_batch_process_s16(b, (short *)out, (const short *)in, vad, gains, n_frames)
-                          : rnnoise_batch_process(b, (float *)out, (const float *)in, vad, gains, n_frames);
   if (n_frames == 0) return 0;
   ON_DEVICE(b->device);
-  const size_t fs = (size_t)n_frames * b->n, pcm = fs * RN_FRAME_SIZE * (s16 ? 2 : 4);
+  const size_t fs = (size_t)n_frames * b->n, pcm = fs * (RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1)) * (s16 ? 2 : 4);
   const size_t o_in = 0, o_out = pcm, o_vad = 2 * pcm, o_gains = o_vad + fs * 4, o_act = o_gains + fs * RN_NB_BANDS * 4,
                total = o_act + fs;
   char *d = nullptr;
   HIP_OK(hipMalloc((void **)&d, total));
   int rc = -1;
   if (hipMemcpy(d + o_in, in, pcm, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess &&
+      (!active || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&  // (absent rows keep the caller's values)
+      (!active || hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess) &&
       batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,
-                                n_frames, nullptr, s16, nullptr, (const uint8_t *)(d + o_act)) == 0 &&
+                                n_frames, nullptr, s16, nullptr, active ? (const uint8_t *)(d + o_act) : nullptr) == 0 &&
       hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d + o_out, pcm, hipMemcpyDeviceToHost) == hipSuccess &&
       (!vad || hipMemcpy(vad, d + o_vad, fs * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
       (!gains || hipMemcpy(gains, d + o_gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost) == hipSuccess))
     rc = 0;
   hipFree(d);
   return rc;
+}
+
+namespace {
+int batch_process_masked_host(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
+                              int n_frames, bool s16) {
+  if (!b || !out || !in || n_frames < 0) return -1;
+  if (!active) return s16 ? rnnoise_batch_process_s16(b, (short *)out, (const short *)in, vad, gains, n_frames)
+                          : rnnoise_batch_process(b, (float *)out, (const float *)in, vad, gains, n_frames);
+  return batch_process_staged(b, out, in, vad, gains, active, n_frames, s16);
 }
 
 // zero state for the n streams of the device list d_list, on st; the layer-wise network's state images of their tiles follow
@@ -535,7 +572,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
                                                    void *hip_stream) {
   if (!b || !d_records || !d_clean || !d_noisy || !d_vad || !d_lowpass || !d_band_lp || !d_noise_free || n_frames < 0)
     return -1;
-  if (b->per_stream) return -1;  // (extraction runs in lock-step frame phase only)
+  if (b->per_stream || b->g.rs_L) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz, only)
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
   const size_t N = b->n;
@@ -558,7 +595,8 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
 extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, const float *clean, const float *noisy,
                                             const float *vad, const int *lowpass, const int *band_lp,
                                             const int *noise_free, int n_frames) {
-  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream) return -1;
+  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L)
+    return -1;
   ON_DEVICE(b->device);
   const size_t N = b->n, fb = (size_t)n_frames * N * RN_FRAME_SIZE * 4;
   char *dev = nullptr;

@@ -26,6 +26,8 @@
 // else.  (In a one-wave workgroup __syncthreads() compiles to exactly this; the analysis kernel runs several waves per
 // workgroup and must not make them march in lock-step through every stage.)  Workgroup barriers are spelled
 // __syncthreads() and appear only where one wave works on data of the others (analysis_body: "narrow phases").
+#define RN_RS_CONST static __constant__
+#include "rs_coeffs.h"
 #define RN_WSYNC()                                             \
   do {                                                         \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     \
@@ -1668,6 +1670,7 @@ struct SynthLds {
 // 4,976 B: two of these waves fit into the LDS that four analysis workgroups (4 x 38,016 B) leave free on a CU -- with the
 // complex spectrum staged in one piece (8,448 B) it was one, and synthesis mostly waited for analysis workgroups to drain
 static_assert(sizeof(SynthLds) <= 5120 && RN_WINDOW_SIZE <= 1052 && RN_BAND_QSTRIDE <= 1052, "synthesis LDS");
+static_assert(RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE + RN_RS_TAPS * 6 <= 1052, "down history, frame and taps fit L.S");
 
 // ---------------------------------------------------------------------------------------------
 // K3: rnn_pitch_filter + gain smoothing/interpolation + frame_synthesis
@@ -1907,15 +1910,82 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
                                       __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+// Downsampling to the batch's PCM rate 48000 / L (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate; rs_coeffs.h,
+// rnnoise_amd/resample.py): y[m] = sum_{k < 48 L} h[k] v[L m + L - 1 - k], four chains over k mod 4 combined as (a0 + a1) + (a2 + a3).
+// An epilogue of both synthesis kernels (bit 9 of parity_arg; bit 10: int16 output): the launcher hands their 48 kHz float body
+// RnGroupDev::rs_dn as `out` and the caller's buffer as RnGroupDev::rs_out, and after the body the wave stages, in L.S (free once the body is done), the stream's down history
+// v[-47 L .. -1], the frame's 480 samples and the taps, and forms the 480 / L outputs, lane l those of m = l, l + 64, ...  The body is not
+// compiled a second time and L is a run-time value, so that the epilogue stays inside the registers of the body.
+__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s) {
+  void *out = g.rs_out;
+  if (g.phase && g.active && !g.active[(size_t)g.call_frame * g.n_stride + s]) return;  // (absent: the body wrote nothing either)
+  const int lane = threadIdx.x, L = g.rs_L, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
+  float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
+  const float *row = g.rs_dn + (size_t)s * RN_FRAME_SIZE;
+  const float *ht = rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
+  float *h = vs + RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE;
+  __syncthreads();  // (the body's stores to rs_dn, by other lanes)
+  // (clamped indices, without a branch: a lane past the end rewrites the last element with its own value)
+#pragma unroll
+  for (int i = 0; i < (RN_RS_DOWN_HIST(6) + WAVE - 1) / WAVE; i++) {
+    const int k = min(lane + WAVE * i, D - 1);
+    vs[k] = hist[k];
+  }
+#pragma unroll
+  for (int i = 0; i < RN_FRAME_SIZE / WAVE + 1; i++) {
+    const int k = min(lane + WAVE * i, RN_FRAME_SIZE - 1);
+    vs[D + k] = row[k];
+  }
+#pragma unroll
+  for (int i = 0; i < (RN_RS_TAPS * 6 + WAVE - 1) / WAVE; i++) {
+    const int k = min(lane + WAVE * i, N - 1);
+    h[k] = ht[k];
+  }
+  RN_WSYNC();
+  for (int m = lane; m < M; m += WAVE) {
+    const float *vm = vs + D + L * m + L - 1;
+    float a0 = h[0] * vm[0], a1 = h[1] * vm[-1], a2 = h[2] * vm[-2], a3 = h[3] * vm[-3];
+#pragma unroll 2
+    for (int k = 4; k < N; k += 4) {
+      a0 = a0 + h[k] * vm[-k];
+      a1 = a1 + h[k + 1] * vm[-(k + 1)];
+      a2 = a2 + h[k + 2] * vm[-(k + 2)];
+      a3 = a3 + h[k + 3] * vm[-(k + 3)];
+    }
+    const float r = (a0 + a1) + (a2 + a3);
+    if (out_s16) {  // (the truncating conversion of the 48 kHz calls: synthesis_body)
+      const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
+      static_cast<short *>(out)[(size_t)s * M + m] = (short)q;
+    } else {
+      static_cast<float *>(out)[(size_t)s * M + m] = r;
+    }
+  }
+  // the new history: the frame's last 47 L samples
+#pragma unroll
+  for (int i = 0; i < (RN_RS_DOWN_HIST(6) + WAVE - 1) / WAVE; i++) {
+    const int k = min(lane + WAVE * i, D - 1);
+    hist[k] = vs[RN_FRAME_SIZE + k];
+  }
+}
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(RN_K3_WAVES, RN_K3_WAVES)))
 rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg, RnRows rows) {
+  const bool rs = parity_arg & 512;
   synthesis_body<true>(g, tb, out, parity_arg, prev_arg, rows);
+  if (rs) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, blockIdx.x);
+  }
 }
 // the launch groups of the one-frame API and batches of up to RN_K3_FEW_MAX streams (one frame: 10.4 -> 9.6 us)
 #define RN_K3_FEW_MAX 256
 extern "C" __global__ void __launch_bounds__(WAVE)
 rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg, RnRows rows) {
+  const bool rs = parity_arg & 512;  // (never set for a row list)
   synthesis_body<false>(g, tb, out, parity_arg, prev_arg, rows);
+  if (rs) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, blockIdx.x);
+  }
 }
 
 
@@ -1949,12 +2019,21 @@ extern "C" hipError_t rn_launch_train_features(const RnGroupDev *g, const RnTabl
 }
 extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev *tb, void *out, int out_s16, int cur, int prev,
                                           hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  // bit 9: low-rate output (rn_dev.h: RnGroupDev::rs_L; rs_down_stream): the body writes rs_dn, the epilogue `out` (bit 10: int16)
+  RnGroupDev gr;
+  if (g->rs_L) {
+    gr = *g;
+    gr.rs_out = out;
+    out = g->rs_dn;
+    g = &gr;
+  }
+  const int arg = g->rs_L ? cur | 512 | (out_s16 ? 1024 : 0) : cur | (out_s16 ? 256 : 0);
   if (g->n_streams <= RN_K3_FEW_MAX)
     RN_LAUNCH(rn_synthesis_few_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
-              cur | (out_s16 ? 256 : 0), prev, RnRows{});
+              arg, prev, RnRows{});
   else
     RN_LAUNCH(rn_synthesis_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
-              cur | (out_s16 ? 256 : 0), prev, RnRows{});
+              arg, prev, RnRows{});
   return hipGetLastError();
 }
 // K1 / K3 of a launch group of the one-frame API (rn_dev.h: RnRows): one one-wave workgroup per listed row

@@ -8,8 +8,72 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "rn_dev.h"
+#define RN_RS_CONST static __constant__
+#include "rs_coeffs.h"
 
 #define WAVE 64
+
+// ---------------------------------------------------------------------------------------------
+// Upsampling of a low-rate stream (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate; rs_coeffs.h, rnnoise_amd/resample.py):
+// u[L q + p] = sum_{k<48} hup[p][k] x[q - k], four chains over k mod 4 combined as (a0 + a1) + (a2 + a3).  A prologue of both K0
+// kernels: one wave forms one stream's 480 samples at 48 kHz into the stream's row of RnGroupDev::rs_up, from its row staged in LDS
+// -- xs[0 .. 46] the history x[-47 .. -1], xs[47 ..] the frame's 480 / L samples -- and the taps staged beside it (hu: [L][48]);
+// lane l forms outputs l, l + 64, ...  (rn_hp_one_kernel only: rn_launch_hp.)  The kernel's 48 kHz float body then reads rs_up as its input: the body is not compiled a
+// second time (a second copy of it, even with nothing else changed, took 6 SGPRs more than the kernel's budget), and L is a run-time
+// value with four accumulators per lane, so that the prologue fits inside the registers of the body.
+// ---------------------------------------------------------------------------------------------
+#define RN_RS_LDS (RN_RS_XS + RN_RS_TAPS * 6)  // LDS floats of the prologue: the staged row, then the taps
+__device__ __forceinline__ const float *rs_up_taps(int L) {
+  return L == 2 ? &rn_rs_up2[0][0] : L == 3 ? &rn_rs_up3[0][0] : &rn_rs_up6[0][0];
+}
+// the wave's LDS hand-offs (one wave per workgroup: no s_barrier needed)
+__device__ __forceinline__ void rs_wsync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <bool IN_S16>
+__device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, float *xs, int L) {
+  const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
+  float *hu = xs + RN_RS_XS;
+  float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
+  // (loads and LDS stores at clamped indices, without a branch: a lane past the end rewrites the last element with its own value)
+  constexpr int NX = RN_FRAME_SIZE / 2 / WAVE + 1, NT = (RN_RS_TAPS * 6 + WAVE - 1) / WAVE;
+  const float rh = hist[min(lane, RN_RS_UP_HIST - 1)];
+  float rx[NX], rt[NT];
+#pragma unroll
+  for (int i = 0; i < NX; i++) {
+    const size_t q = (size_t)s * M + min(lane + WAVE * i, M - 1);
+    rx[i] = IN_S16 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
+  }
+  const float *ht = rs_up_taps(L);
+#pragma unroll
+  for (int i = 0; i < NT; i++) rt[i] = ht[min(lane + WAVE * i, RN_RS_TAPS * L - 1)];
+  rs_wsync();  // (the previous stream's reads of xs are behind us)
+  xs[min(lane, RN_RS_UP_HIST - 1)] = rh;
+#pragma unroll
+  for (int i = 0; i < NX; i++) xs[RN_RS_UP_HIST + min(lane + WAVE * i, M - 1)] = rx[i];
+#pragma unroll
+  for (int i = 0; i < NT; i++) hu[min(lane + WAVE * i, RN_RS_TAPS * L - 1)] = rt[i];
+  rs_wsync();
+  float *dst = g.rs_up + (size_t)s * RN_FRAME_SIZE;
+  const unsigned inv = (65536u + L - 1) / L;  // n / L = (n * inv) >> 16, exact for n < 480
+  for (int n = lane; n < RN_FRAME_SIZE; n += WAVE) {
+    const int q = (int)(((unsigned)n * inv) >> 16), p = n - q * L;
+    const float *xq = xs + RN_RS_UP_HIST + q, *hp = hu + p * RN_RS_TAPS;
+    float a0 = hp[0] * xq[0], a1 = hp[1] * xq[-1], a2 = hp[2] * xq[-2], a3 = hp[3] * xq[-3];
+#pragma unroll 2
+    for (int k = 4; k < RN_RS_TAPS; k += 4) {
+      a0 = a0 + hp[k] * xq[-k];
+      a1 = a1 + hp[k + 1] * xq[-(k + 1)];
+      a2 = a2 + hp[k + 2] * xq[-(k + 2)];
+      a3 = a3 + hp[k + 3] * xq[-(k + 3)];
+    }
+    dst[n] = (a0 + a1) + (a2 + a3);
+  }
+  // the new up history: the row's last 47 samples (all of the frame's own, 480 / L >= 80)
+  if (lane < RN_RS_UP_HIST) hist[lane] = xs[M + lane];
+}
 
 // ---------------------------------------------------------------------------------------------
 // K0: rnn_biquad (src/denoise.c:409-419, coefficients :469-470), transposed: lane = stream.
@@ -228,6 +292,7 @@ struct HpOneLds {
   float pb[RN_PITCH_BUF_SIZE];
 };
 static_assert(864 + 64 + 8 <= RN_PITCH_BUF_SIZE - RN_FRAME_SIZE, "the decimated signal and its pad stay below the new frame");
+static_assert(RN_RS_LDS <= RN_PITCH_BUF_SIZE, "the upsampling prologue's LDS fits the body's");
 
 // (the body once per input type, like hp_body above: behind the run-time test per load the frame's two loads and the three loads of
 //  old samples were each followed by its own s_waitcnt vmcnt(0) -- five serial round trips, two of them to pinned host memory in the
@@ -385,6 +450,13 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
     slot = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, s, present)) % RN_RING_SLOTS;  // (the wave's one stream: uniform)
     if (!present) return;
   }
+  if (in_s16 & 2) {  // low-rate rows (never a row list): upsampled into RnGroupDev::rs_up, staged in the body's LDS before the body uses it
+    if (in_s16 & 1) rs_up_stream<true>(g, in, s, L.pb, g.rs_L);
+    else rs_up_stream<false>(g, in, s, L.pb, g.rs_L);
+    __syncthreads();
+    in = g.rs_up;
+    in_s16 = 0;
+  }
   const float *in_row = listed ? rows.io + (size_t)s * RN_ROW_IO : in + (size_t)s * RN_FRAME_SIZE;
   if (in_s16) hp_one_body<true>(L, g, in, in_row, listed, s, slot, slot_arg);
   else hp_one_body<false>(L, g, in, in_row, listed, s, slot, slot_arg);
@@ -407,8 +479,13 @@ extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s
   const bool beside_others = slot & 512;
   slot &= 511;
   const int one_max = one_max_env >= 0 ? one_max_env : (beside_others ? RN_HP_ONE_MAX_PIPELINED : RN_HP_ONE_MAX);
-  if (g->n_streams <= one_max) {
-    RN_LAUNCH(rn_hp_one_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot, in_s16, RnRows{});
+  // low-rate rows (rn_dev.h: RnGroupDev::rs_L) take the wave-per-stream form at every batch size.  (An upsampling prologue in the lane
+  // = stream kernel, one stream after the other per wave, took that kernel from 50 to 61-64 SGPRs in every arrangement tried; the 48 kHz
+  // kernels keep their registers instead.  The cost at large batches: DESIGN.md 4.10, profiles/resample_rate_bench.txt)
+  const int rs = g->rs_L ? 1 : 0;
+  if (rs || g->n_streams <= one_max) {
+    RN_LAUNCH(rn_hp_one_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot,
+              in_s16 | (rs ? 2 : 0), RnRows{});
     return hipGetLastError();
   }
   // (rounds 5-6 had a second build of this kernel with 16-sample blocks at 64 VGPRs -- rn_hp_lean_kernel, a wave of which fits a SIMD

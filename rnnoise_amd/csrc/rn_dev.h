@@ -152,7 +152,21 @@ struct RnGroupDev {
   int *phase;                  // [N] frame phase of each stream at the start of the call, mod RN_RING_SLOTS
   const uint8_t *active;       // [call_frames][n_stride] nonzero = the stream has this frame; null = every stream present
   int call_frame, call_frames; // frame of the call this launch works on; frames in the call
+  // PCM rate R = 48000 / rs_L of the batch's calls (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate).  0 / null at 48 kHz: every
+  // launch is today's.  Otherwise K0 upsamples the caller's rows and K3 downsamples its output (rs_coeffs.h: the filters), and
+  // rs_hist[s] holds stream s's filter histories: [0, RN_RS_UP_HIST) the last low-rate input samples, [RN_RS_DOWN0, RN_RS_DOWN0 +
+  // RN_RS_DOWN_HIST(L)) the last 48 kHz output samples, oldest first.  Zeroed by reset, reset_streams, import and a rate change.
+  float *rs_hist;              // [N][RN_RS_HIST]
+  float *rs_up, *rs_dn;        // [N][480] each: the frame at 48 kHz as K0 formed it from the low-rate row / as K3's body formed it
+  void *rs_out;                // K3 only: the caller's low-rate output (float or int16)
+  int rs_L;
 };
+#define RN_RS_TAPS 48                           // taps per phase of the up filter; the down filter has RN_RS_TAPS * L
+#define RN_RS_UP_HIST (RN_RS_TAPS - 1)          // 47 low-rate samples
+#define RN_RS_DOWN_HIST(L) ((RN_RS_TAPS - 1) * (L))  // N - L 48 kHz samples
+#define RN_RS_DOWN0 48
+#define RN_RS_HIST (RN_RS_DOWN0 + RN_RS_DOWN_HIST(6) + 6)  // 336 floats (1,344 B) per stream
+#define RN_RS_XS (RN_RS_UP_HIST + RN_FRAME_SIZE / 2 + 1)    // LDS floats of one staged low-rate row: history + frame, at most 288
 
 // Row list of the one-frame API (dropin.cpp: the combiner behind rnnoise_process_frame).  Concurrent rnnoise_process_frame calls on
 // states of one pool are gathered into ONE launch group: block b of the latency kernels (rn_hp_one_kernel,

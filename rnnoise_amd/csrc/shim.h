@@ -163,6 +163,10 @@ struct RNNoiseBatch {
   // take each stream's ring and spectra slots from phase_buf (rn_dev.h: RnGroupDev::phase) instead of ring_slot / parity
   bool per_stream = false;
   int *phase_buf = nullptr;  // [N] in the arena
+  // PCM rate of the calls (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate).  rs_buf: the resampler histories (rn_dev.h:
+  // RnGroupDev::rs_hist), allocated the first time the rate leaves 48 kHz; g.rs_hist / g.rs_L are set only while it is away
+  int pcm_rate = 48000;
+  float *rs_buf = nullptr;
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
   hipStream_t side = nullptr, side_hp = nullptr;
@@ -301,3 +305,5 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out, const void *d_in, fl
                               void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr,
                               const uint8_t *d_active = nullptr);  // batch.cpp
 void host_io_release(RNNoiseBatch *b);                               // host_io.cpp
+int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
+                         int n_frames, bool s16);                    // batch.cpp: host buffers through one device allocation

@@ -64,10 +64,11 @@ def register_torch_op():
 
 
 class RNNoiseOp:
-    """N concurrent streams; call with a (T, N, 480) float32 CUDA tensor of int16-scaled PCM.  The same object is
-    reachable as the registered op: torch.ops.rnnoise_amd.process(pcm, op.state, op.handle)."""
+    """N concurrent streams; call with a (T, N, 480 // L) float32 CUDA tensor of int16-scaled PCM at `rate` = 48000 / L (48000,
+    24000, 16000 or 8000: include/rnnoise_amd.h, rnnoise_batch_set_pcm_rate).  The same object is reachable as the registered op:
+    torch.ops.rnnoise_amd.process(pcm, op.state, op.handle)."""
 
-    def __init__(self, model_blob: bytes, n_streams: int, device: int = 0, nn_path: str = "mfma"):
+    def __init__(self, model_blob: bytes, n_streams: int, device: int = 0, nn_path: str = "mfma", rate: int = 48000):
         import torch
         self.torch = torch
         self.device = torch.device("cuda", device)
@@ -75,6 +76,8 @@ class RNNoiseOp:
         self.batch = capi.Batch(self.model, n_streams, device=device)
         if nn_path == "mfma":
             self.batch.set_nn_path(1)
+        if rate != 48000:
+            self.batch.set_pcm_rate(rate)
         self.n = n_streams
         register_torch_op()
         self.handle = id(self)
@@ -98,7 +101,7 @@ class RNNoiseOp:
         return self.torch.ops.rnnoise_amd.process(pcm, self.state, self.handle)
 
     def process_masked(self, pcm, active):
-        """pcm (T, N, 480) float32 CUDA tensor, active (T, N) bool / uint8 CUDA tensor: streams whose frame has not arrived skip it
+        """pcm (T, N, 480 // L) float32 CUDA tensor, active (T, N) bool / uint8 CUDA tensor: streams whose frame has not arrived skip it
         (torch.ops.rnnoise_amd.process_masked)"""
         return self.torch.ops.rnnoise_amd.process_masked(pcm, active, self.state, self.handle)
 
@@ -112,7 +115,7 @@ class RNNoiseOp:
 
     def _run(self, pcm, active=None):
         torch = self.torch
-        assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[1:] == (self.n, capi.FRAME)
+        assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[1:] == (self.n, self.batch.frame)
         pcm = pcm.contiguous()
         T = pcm.shape[0]
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
