@@ -44,6 +44,50 @@ const BlobRecord *blob_find(const std::vector<BlobRecord> &recs, const std::stri
   return nullptr;
 }
 
+// The two places where the loader accepts less than the reference's parser.  No exporter writes either.
+//  * A same-sign input pair (c0, c1) or (c2, c3) of a block with |w0 + w1| >= 130: the reference's maddubs
+//    (src/vec_avx.h:629-634) saturates u8 * s8 pair sums to int16, and with activations up to 254 that happens from 130 on
+//    (254 * 129 = 32,766).  The oracle and every kernel sum exactly, so such a blob has no bit-exact answer here.
+//  * A block listed twice or more in one 8-row group (the reference sums the copies) whose merged weight falls outside
+//    [-128, 127]: the MFMA paths read the merged matrix as one int8 image (stage_linear) and cannot hold it.
+bool int8_blocks_exact(const HostLinear &l, const std::string &layer) {
+  const int ng = l.nout / 8, nb_dense = l.nin / 4;
+  const int8_t *w = l.w;
+  const int32_t *idx = l.idx;
+  std::vector<int> merged(8 * l.nin);
+  std::vector<uint8_t> seen(nb_dense);
+  for (int g = 0; g < ng; g++) {
+    const int nb = idx ? *idx++ : nb_dense;
+    bool dup = false;
+    std::fill(seen.begin(), seen.end(), 0);
+    std::fill(merged.begin(), merged.end(), 0);
+    for (int b = 0; b < nb; b++, w += 32) {
+      const int col = idx ? *idx++ : 4 * b;
+      dup |= seen[col / 4]++ != 0;
+      for (int r = 0; r < 8; r++) {
+        for (int c = 0; c < 4; c++) merged[r * l.nin + col + c] += w[r * 4 + c];
+        for (int c = 0; c < 4; c += 2) {
+          const int w0 = w[r * 4 + c], w1 = w[r * 4 + c + 1];
+          if ((w0 > 0 && w1 > 0 && w0 + w1 >= 130) || (w0 < 0 && w1 < 0 && w0 + w1 <= -130)) {
+            fprintf(stderr, "[rnnoise_amd] weight blob rejected: %s, row %d, inputs %d and %d: the pair sum %d saturates the "
+                            "reference's int16 pair products (|sum| must stay below 130)\n",
+                    layer.c_str(), 8 * g + r, col + c, col + c + 1, w0 + w1);
+            return false;
+          }
+        }
+      }
+    }
+    if (!dup) continue;
+    for (int k = 0; k < 8 * l.nin; k++)
+      if (merged[k] < -128 || merged[k] > 127) {
+        fprintf(stderr, "[rnnoise_amd] weight blob rejected: %s, row %d, input %d: repeated blocks sum to %d, outside int8\n",
+                layer.c_str(), 8 * g + k / l.nin, k % l.nin, merged[k]);
+        return false;
+      }
+  }
+  return true;
+}
+
 // kind: 0 float dense, 1 int8 dense, 2 int8 block-sparse, 3 int8 block-sparse + diagonal
 bool linear_from_blob(HostLinear &l, const std::vector<BlobRecord> &recs, const std::string &layer, int nin, int nout,
                       int kind) {
@@ -66,7 +110,7 @@ bool linear_from_blob(HostLinear &l, const std::vector<BlobRecord> &recs, const 
     if (!(r = blob_find(recs, layer + "_weights_int8", nin * nout))) return false;
     l.w = reinterpret_cast<const int8_t *>(r->data);
     l.nblocks = (nin / 4) * (nout / 8);
-    return true;
+    return int8_blocks_exact(l, layer);
   }
   if (!(r = blob_find(recs, layer + "_weights_idx", -1))) return false;
   l.idx = reinterpret_cast<const int32_t *>(r->data);
@@ -94,7 +138,7 @@ bool linear_from_blob(HostLinear &l, const std::vector<BlobRecord> &recs, const 
     if (!(r = blob_find(recs, layer + "_weights_diag", nout * 4))) return false;
     l.diag = reinterpret_cast<const float *>(r->data);
   }
-  return true;
+  return int8_blocks_exact(l, layer);
 }
 
 // the ten layers of the default architecture and their byte-exact shapes
@@ -164,13 +208,17 @@ DevLinearOffsets stage_linear(Staging &st, const HostLinear &l) {
   }
   for (auto &v : rowsum) v *= 128;
   o.rowsum = st.add(rowsum.data(), 4 * rowsum.size());
-  {  // MFMA copy: zero-fill to dense [nout][nin], then A-fragment order (nn_mfma.hip)
+  {  // MFMA copy: zero-fill to dense [nout][nin], then A-fragment order (nn_mfma.hip).  A block listed more than once in a
+     // group adds to the copies before it, as the reference's block loop does (the loader has checked that the sums fit)
     std::vector<int8_t> dense((size_t)l.nout * l.nin, 0), frag((size_t)l.nout * l.nin, 0);
     const int8_t *wb = l.w;
     for (int g = 0, b = 0; g < l.nout / 8; g++)
       for (; b < grp[g + 1]; b++, wb += 32)
         for (int r = 0; r < 8; r++)
-          for (int c = 0; c < 4; c++) dense[(size_t)(8 * g + r) * l.nin + cols[b] + c] = wb[r * 4 + c];
+          for (int c = 0; c < 4; c++) {
+            int8_t &d = dense[(size_t)(8 * g + r) * l.nin + cols[b] + c];
+            d = (int8_t)(d + wb[r * 4 + c]);
+          }
     const int KTn = l.nin / 64;
     for (int rt = 0; rt < l.nout / 16; rt++)
       for (int kt = 0; kt < KTn; kt++)
@@ -280,7 +328,8 @@ bool unpack_model(const void *p, int len, StagedModel &sm, long &weight_bytes) {
     const bool k_int8 = i >= 1 && i <= 7, k_diag = i == 3 || i == 5 || i == 7, k_cols = i >= 2 && i <= 7;
     if ((l.is_int8 != 0) != k_int8 || (l.has_fw != 0) != !k_int8 || (l.has_diag != 0) != k_diag || (l.has_cols != 0) != k_cols)
       return false;
-    if (l.nin != want[i][0] || l.nout != want[i][1] || l.nblocks < 0 || l.nblocks > (l.nin / 4) * (l.nout / 8)) return false;
+    // (no bound on nblocks from the shape: a blob may list a block more than once in a group; fits() bounds it by the payload)
+    if (l.nin != want[i][0] || l.nout != want[i][1] || l.nblocks < 0) return false;
     if (k_int8 && !k_cols && l.nblocks != (l.nin / 4) * (l.nout / 8)) return false;  // a dense int8 layer has every block
     auto fits = [&](uint64_t off, uint64_t bytes) { return off <= n && bytes <= n - off && !(off & 15); };
     const uint64_t no = l.nout, ni = l.nin;

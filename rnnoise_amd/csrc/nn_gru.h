@@ -39,8 +39,10 @@ __device__ __forceinline__ void stg(void *base, unsigned byte_off, T v) {
   *reinterpret_cast<T *>(reinterpret_cast<char *>(base) + byte_off) = v;
 }
 // ---- the activations and the quantiser of nn_common.h with fewer VALU operations (this kernel's main loop is VALU-bound) ----
-// Same bits for every finite argument -- which is all a GRU layer can see: its pre-activations are int32 sums times
-// finite scales plus diag * h, and h stays in [-1, 1] from a zero or any finite start.  What differs from nn_common.h:
+// Same bits for every finite argument below ~1.8e19 in magnitude.  Above it x * x overflows, rcp(inf) = 0 and the x86 form's
+// inf * 0 is a NaN, which the x86 clamps pass on and v_med3_f32 does not: finite weights can reach that (DESIGN.md §2,
+// "Residuals"; not fixed).  Below it a GRU layer sees only finite arguments: its pre-activations are int32 sums times finite
+// scales plus diag * h, and h stays in [-1, 1] from a zero or any finite start.  What differs from nn_common.h:
 //   * the two clamps are one v_med3_f32 (differs from the x86 min/max pair only for a NaN argument);
 //   * the u8 quantiser is v_rndne + v_cvt_pk_u8_f32 (saturating both ways like packs/packus; differs only for
 //     |127 x + 127| >= 2^31, where cvtps2dq's "integer indefinite" turns a huge positive value into 0).

@@ -656,8 +656,10 @@ def test_throughput_kernels_at_small_sizes():
     # streams take it; the multi-frame calls of these cases run the eight-wave form in the default run of the suite)
     env = dict(os.environ, RNNOISE_AMD_NN_ONE_MAX="0", RNNOISE_AMD_HP_ONE_MAX="0", RNNOISE_AMD_K1_SPW="4", RNNOISE_AMD_TILE_WAVES="16")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_blob_tools.py"), "-k",
-                        "test_mfma_path_bit_exact or test_synthetic_models_on_gpu or test_s16_entry_points or test_drop_in_single_stream_api"],
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_blob_tools.py"),
+                        os.path.join(root, "tests", "test_weight_layouts_gpu.py"), "-k",
+                        "test_mfma_path_bit_exact or test_synthetic_models_on_gpu or test_s16_entry_points or test_drop_in_single_stream_api"
+                        " or test_weight_layout_on_every_network_path"],
                        env=env, capture_output=True, text=True, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
@@ -678,8 +680,10 @@ def test_at_size_kernels_on_small_ragged_batches():
     env = dict(os.environ, RNNOISE_AMD_NN_ONE_MAX="0", RNNOISE_AMD_HP_ONE_MAX="0", RNNOISE_AMD_K1_SPW="4", RNNOISE_AMD_NN_LAYERS_MIN="0",
                RNNOISE_AMD_GRU_VARIANT="w4")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_blob_tools.py"), "-k",
-                        "test_mfma_path_bit_exact or test_sparser_blob_on_ragged_batches or test_synthetic_models_on_gpu or test_s16_entry_points"],
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_blob_tools.py"),
+                        os.path.join(root, "tests", "test_weight_layouts_gpu.py"), "-k",
+                        "test_mfma_path_bit_exact or test_sparser_blob_on_ragged_batches or test_synthetic_models_on_gpu or test_s16_entry_points"
+                        " or test_weight_layout_on_every_network_path"],
                        env=env, capture_output=True, text=True, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
