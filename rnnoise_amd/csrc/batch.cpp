@@ -12,27 +12,10 @@ T *carve(uint8_t *&p, size_t count) {
 
 }  // namespace
 
-// Batches from this size up run the network layer by layer (nn_layers.hip: 64 streams per GRU workgroup); below it the five launches
-// and the smaller grids cost more than the weight reuse gains.  The tile kernel holds out while a CU has at most two tiles (8,192
-// streams on 256 CUs: 25.9 against 24.2 M frames/s); with a third its K2 jumps (0.139 -> 0.193 ms at 10,240 streams) and the layer-wise
-// network is ahead -- 27.5 against 25.8 M frames/s at 10,240, 29.5 against 26.2 at 12,288, one frame per call 24.8 against 23.0 M at
-// 10,240 (profiles/r6_late_ab.txt; rounds 3-6 had the switch at 16,384).  $RNNOISE_AMD_NN_LAYERS_MIN overrides (A/B runs).
-int nn_layers_min_streams() {
-  static const int v = [] {
-    const char *e = getenv("RNNOISE_AMD_NN_LAYERS_MIN");
-    return e ? atoi(e) : 10240;
-  }();
-  return v;
-}
-
-// Up to this many streams the vector-path network runs as the latency-oriented kernel (nn_kernels.hip: rn_nn_one_kernel, one
-// 14-wave workgroup with 125 KB of LDS per stream -- one per CU, two rounds at 512 streams); $RNNOISE_AMD_NN_ONE_MAX overrides (A/B runs, 0 = never).
-int nn_one_max_streams() {
-  static const int v = [] {
-    const char *e = getenv("RNNOISE_AMD_NN_ONE_MAX");
-    return e ? atoi(e) : 512;
-  }();
-  return v;
+// the dispatch switches (dispatch.h), read once per process
+const RnKnobs &rn_knobs() {
+  static const RnKnobs k = rn_knobs_from_env();
+  return k;
 }
 namespace {
 size_t batch_layout(RnGroupDev &g, uint8_t *base, int n) {
@@ -184,10 +167,7 @@ extern "C" RNNoiseBatch *rnnoise_batch_create(RNNModel *model, int n_streams, in
   b->model = model;
   b->device = device;
   b->n = n_streams;
-  // same bits either way.  Up to 512 streams the latency-oriented vector kernel (one 14-wave workgroup per stream, one per CU)
-  // finishes first -- measured K2 at 64 / 256 / 512 / 768 streams: 36 / 42 / 83 / 120 us against 82 / 101 / 105 / 105 us for MFMA
-  // tiles of 16 streams; beyond that the MFMA paths do
-  b->nn_path = (n_streams > nn_one_max_streams() && n_streams >= 16 && rn_nn_mfma_available()) ? 1 : 0;
+  b->nn_path = rn_default_nn_path(rn_knobs(), n_streams);
   if (model_on_device(model, device, b->m) || tables_for_device(device, b->tb)) {
     delete b;
     return nullptr;
@@ -200,6 +180,11 @@ extern "C" RNNoiseBatch *rnnoise_batch_create(RNNModel *model, int n_streams, in
     delete b;
     return nullptr;
   }
+  // the device's facts the plans need: its compute units, and the large-LDS opt-ins (kept, not fatal: only launches of a refused
+  // form fail)
+  if (hipDeviceGetAttribute(&b->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || b->cus <= 0) b->cus = 256;
+  b->lds_one = rn_nn_one_opt_in();
+  rn_nn_gru_opt_in(b->lds_gru);
   batch_layout(b->g, static_cast<uint8_t *>(b->arena), n_streams);
   b->phase_buf = b->g.phase;
   b->g.phase = nullptr;
@@ -288,8 +273,7 @@ extern "C" int rnnoise_batch_set_schedule(RNNoiseBatch *b, int schedule) {
 }
 
 extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
-  if (!b || path < 0 || path > 2) return -1;  // 0 vector, 1 MFMA (layer-wise from nn_layers_min_streams() up), 2 layer-wise
-  if (path >= 1 && !rn_nn_mfma_available()) return -1;
+  if (!b || path < 0 || path > 2) return -1;  // 0 vector, 1 MFMA (layer-wise from $RNNOISE_AMD_NN_LAYERS_MIN streams up), 2 layer-wise
   int old = b->nn_path;
   b->nn_path = path;
   return old;
@@ -330,13 +314,12 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   //   * the spectra rotate through 3 slots and the per-step scratch (features, silence, pitch) is
   //     double-buffered, so analysis(f) only has to wait for synthesis(f-2);
   //   * every other piece of state is touched by one kernel only, in frame order on its own stream.
-  // RNNOISE_AMD_PIPE (A/B runs only): 9 = no side streams, 1 = K0 on a side stream, 2 = K0 and K1 on side streams.
-  // Measured after the fence-free events: the 3-stream schedule is the best or within noise of the best from 1 K to
-  // 64 K streams (65,536: 20.2 M frames/s vs 20.0 M on one stream, 19.6 M with only K0 aside), so it is the only default.
-  static const int pipe_env = [] { const char *e = getenv("RNNOISE_AMD_PIPE"); return e ? atoi(e) : 0; }();
-  const int pipe_force = b->schedule ? b->schedule : pipe_env;
-  const bool pipelined = n_frames > 1 && pipe_force != 9;
-  const bool side_k1 = pipelined && pipe_force != 1;
+  // (dispatch.h: rn_schedule has the other schedules and rn_plan every kernel's form; one plan serves every frame of the call.  The
+  // layer images are indexed by tile of the whole batch; the layer kernels use 32-bit byte offsets into a state plane)
+  const RnSchedule sched = rn_schedule(rn_knobs(), n_frames, b->schedule);
+  const bool pipelined = sched.pipelined, side_k1 = sched.side_k1;
+  const bool whole = b->g.n_streams == b->g.n_stride && (size_t)b->g.n_streams * RN_GRU * 4 < (1ull << 32);
+  const RnPlan plan = rn_plan(rn_knobs(), {b->n, whole, b->cus, b->nn_path, pipelined, b->per_stream, b->g.rs_L != 0});
   // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
   // made it: normal for torch's)
   if (side_k1 && !b->side) HIP_OK(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, 0));
@@ -390,7 +373,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
       b->cur_hp[f & 7] = t.on ? t.stop() : (pipelined ? b->own_hp[f & 7] : nullptr);
       RnGroupDev gh = b->g;
       phased(gh, f);
-      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * N * fl * esz, s16, ((b->ring_slot + f) % RN_RING_SLOTS) | (pipelined ? 512 : 0), sc, t.start(),
+      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * N * fl * esz, s16, (b->ring_slot + f) % RN_RING_SLOTS, plan.hp, sc, t.start(),
                           b->cur_hp[f & 7]));
     }
     if (hk && hk->after_hp(f, sc)) return -1;
@@ -405,7 +388,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     {
       TimedLaunch t(b, 0);
       b->cur_k1[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k1[f & 7] : nullptr);
-      HIP_OK(rn_launch_analysis(&g, &b->tb, (b->ring_slot + f) % RN_RING_SLOTS, (b->parity + f) % RN_SPEC_SLOTS, sb, t.start(),
+      HIP_OK(rn_launch_analysis(&g, &b->tb, (b->ring_slot + f) % RN_RING_SLOTS, (b->parity + f) % RN_SPEC_SLOTS, plan.k1, sb, t.start(),
                                 b->cur_k1[f & 7]));
     }
     return 0;
@@ -427,9 +410,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     }
     if (hk && hk->before_nn(f, st)) return -1;
     {
-      // (the layer images are indexed by tile of the whole batch; the layer kernels use 32-bit byte offsets into a state plane)
-      const bool whole = g.n_streams == g.n_stride && (size_t)g.n_streams * RN_GRU * 4 < (1ull << 32);
-      if (whole && (b->nn_path == 2 || (b->nn_path == 1 && b->n >= nn_layers_min_streams()))) {
+      if (plan.nn == RN_NN_LAYERS) {
         if (!b->img_valid) HIP_OK(rn_launch_nn_requant(&g, st));
         b->img_valid = true;
         // five launches, each timed on its own (kind 1: the durations add up to the network's)
@@ -440,19 +421,19 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
           ev[i][0] = tl[i]->start();
           ev[i][1] = tl[i]->stop();
         }
-        HIP_OK(rn_launch_nn_layers(&g, &b->m, &b->tb, st, ev));
+        HIP_OK(rn_launch_nn_layers(&g, &b->m, &b->tb, plan.gru, b->lds_gru, st, ev));
       } else {
         TimedLaunch t(b, 1);
         b->img_valid = false;
-        if (b->nn_path >= 1) HIP_OK(rn_launch_nn_mfma(&g, &b->m, &b->tb, st, t.start(), t.stop(), !pipelined));
-        else if (g.n_streams <= nn_one_max_streams()) HIP_OK(rn_launch_nn_one(&g, &b->m, &b->tb, st, t.start(), t.stop()));
-        else HIP_OK(rn_launch_nn_vector(&g, &b->m, &b->tb, st, t.start(), t.stop()));
+        if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, &b->m, &b->tb, b->lds_one, st, t.start(), t.stop()));
+        else if (plan.nn == RN_NN_VECTOR) HIP_OK(rn_launch_nn_vector(&g, &b->m, &b->tb, st, t.start(), t.stop()));
+        else HIP_OK(rn_launch_nn_mfma(&g, &b->m, &b->tb, plan.nn, st, t.start(), t.stop()));
       }
     }
     {
       TimedLaunch t(b, 2);
       b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
-      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * N * fl * esz, s16, cur, prev, st, t.start(), b->cur_k3[f & 7]));
+      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * N * fl * esz, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
     }
     if (hk && hk->after_k3(f, st)) return -1;
     // (schedule 1: the high-pass three frames ahead goes out HERE, behind the synthesis launch whose end it starts at)

@@ -24,6 +24,10 @@ int pool_rows() {
   return n;
 }
 
+// The plan of one frame of one pooled state (pool_step): a one-stream view of the pool's batch, at 48 kHz in lock-step phase, on
+// the vector path's kernels whatever the batch's own path (a one-stream view is never the whole batch)
+RnPlan pool_plan(const RNNoiseBatch *b) { return rn_plan(rn_knobs(), {1, false, b->cus, 0, false, false, false}); }
+
 StatePool *pool_new(RNNModel *model, int device) {
   StatePool *p = new StatePool();
   p->rows = pool_rows();
@@ -54,9 +58,9 @@ StatePool *pool_new(RNNModel *model, int device) {
     delete p;
     return nullptr;
   }
-  // launch groups run the latency network kernel (rn_nn_one_kernel, 125 KB of LDS by opt-in): where it cannot run, pooled frames go
-  // through pool_step one state at a time, which has the vector kernel to fall back on
-  p->comb.no_nn_one = nn_one_max_streams() < 1;
+  // launch groups run the latency network kernel (rn_nn_one_kernel): where the one-stream plan does not take it, pooled frames go
+  // through pool_step one state at a time, which follows that plan
+  p->comb.no_nn_one = pool_plan(p->batch).nn != RN_NN_ONE;
   return p;
 }
 
@@ -144,11 +148,12 @@ int pool_step(StatePool *p, int slot, int parity, int ring_slot, long frame_no, 
   }
   g.vad = d_vad;
   const int prev = (parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
-  HIP_OK(rn_launch_hp(&g, d_in, 0, ring_slot, st, nullptr, nullptr));
-  HIP_OK(rn_launch_analysis(&g, &b->tb, ring_slot, parity, st, nullptr, nullptr));
-  if (nn_one_max_streams() >= 1) HIP_OK(rn_launch_nn_one(&g, &b->m, &b->tb, st, nullptr, nullptr));
+  const RnPlan plan = pool_plan(b);
+  HIP_OK(rn_launch_hp(&g, d_in, 0, ring_slot, plan.hp, st, nullptr, nullptr));
+  HIP_OK(rn_launch_analysis(&g, &b->tb, ring_slot, parity, plan.k1, st, nullptr, nullptr));
+  if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, &b->m, &b->tb, b->lds_one, st, nullptr, nullptr));
   else HIP_OK(rn_launch_nn_vector(&g, &b->m, &b->tb, st, nullptr, nullptr));
-  HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out, 0, parity, prev, st, nullptr, nullptr));
+  HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out, 0, parity, prev, plan.k3, st, nullptr, nullptr));
   return 0;
 }
 
@@ -304,7 +309,7 @@ int comb_launch(StatePool *p, int k, const std::vector<CombMember> &grp) {
     if (f == this_group) return -1;
 #endif
   HIP_OK(rn_launch_analysis_rows(&b->g, &b->tb, &rows, st));
-  HIP_OK(rn_launch_nn_rows(&b->g, &b->m, &b->tb, &rows, st));
+  HIP_OK(rn_launch_nn_rows(&b->g, &b->m, &b->tb, &rows, b->lds_one, st));
   HIP_OK(rn_launch_synthesis_rows(&b->g, &b->tb, &rows, st));
   return 0;
 }

@@ -11,15 +11,11 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "rn_dev.h"
+#include "dispatch.h"
 #include "fft_reg.h"
 #include "log10_glibc.h"
 
 #define WAVE 64
-// from here on K1_SPW streams share a workgroup (see rn_analysis_single_kernel).  6,144 until round 6's last day; since the narrow
-// phases and the follower are shared by the four streams of a workgroup (round 6) that form is ahead from 3,072 streams -- 23.3
-// against 20.8 M frames/s there, 26.4 against 24.5 at 4,096 (one frame per call 0.201 against 0.231 ms), 27.8 against 26.0 at
-// 5,120 -- and level at 2,048 (profiles/r6_late_ab.txt)
-#define RN_K1_MULTI_MIN_STREAMS 2560
 
 // Every LDS arena below belongs to ONE wavefront, and a wavefront's LDS instructions execute in issue order, so the
 // hand-offs between lanes of a wave need no s_barrier: a wavefront-scope fence pins the compiler's ordering and nothing
@@ -1976,8 +1972,7 @@ rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int p
     rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, blockIdx.x);
   }
 }
-// the launch groups of the one-frame API and batches of up to RN_K3_FEW_MAX streams (one frame: 10.4 -> 9.6 us)
-#define RN_K3_FEW_MAX 256
+// the launch groups of the one-frame API and small batches (dispatch.h: RN_K3_FEW)
 extern "C" __global__ void __launch_bounds__(WAVE)
 rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg, RnRows rows) {
   const bool rs = parity_arg & 512;  // (never set for a row list)
@@ -1992,14 +1987,10 @@ rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, i
 // host-visible launch helpers -----------------------------------------------------------------
 // (K0 lives in hp_kernel.hip; K0 and K1 are launched separately so that the host may put K0 of the next frame on a side stream)
 extern "C" hipError_t rn_launch_hp_passthrough(const RnGroupDev *g, const float *in, int slot, hipStream_t st);  // hp_kernel.hip
-extern "C" hipError_t rn_launch_analysis(const RnGroupDev *g, const RnTablesDev *tb, int slot, int parity, hipStream_t st,
+extern "C" hipError_t rn_launch_analysis(const RnGroupDev *g, const RnTablesDev *tb, int slot, int parity, RnK1Form form, hipStream_t st,
                                          hipEvent_t e0, hipEvent_t e1) {
-  // A/B runs only: RNNOISE_AMD_K1_SPW=1 / 4 forces one / K1_SPW streams per workgroup
-  static const int spw_force = [] { const char *e = getenv("RNNOISE_AMD_K1_SPW"); return e ? atoi(e) : 0; }();
   const int n = g->n_streams;
-  // (per-stream frame phase: the one-stream form at every size -- rn_analysis_kernel's four streams share their narrow phases)
-  const bool single = g->phase || spw_force == 1 || (spw_force == 0 && n < RN_K1_MULTI_MIN_STREAMS);
-  if (single) {
+  if (form == RN_K1_SINGLE) {
     RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity, RnRows{});
   } else {
     const dim3 grid((n + K1_SPW - 1) / K1_SPW), block(WAVE * K1_SPW);
@@ -2018,7 +2009,7 @@ extern "C" hipError_t rn_launch_train_features(const RnGroupDev *g, const RnTabl
   return hipGetLastError();
 }
 extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev *tb, void *out, int out_s16, int cur, int prev,
-                                          hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+                                          RnK3Form form, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   // bit 9: low-rate output (rn_dev.h: RnGroupDev::rs_L; rs_down_stream): the body writes rs_dn, the epilogue `out` (bit 10: int16)
   RnGroupDev gr;
   if (g->rs_L) {
@@ -2028,7 +2019,7 @@ extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev
     g = &gr;
   }
   const int arg = g->rs_L ? cur | 512 | (out_s16 ? 1024 : 0) : cur | (out_s16 ? 256 : 0);
-  if (g->n_streams <= RN_K3_FEW_MAX)
+  if (form == RN_K3_FEW)
     RN_LAUNCH(rn_synthesis_few_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
               arg, prev, RnRows{});
   else

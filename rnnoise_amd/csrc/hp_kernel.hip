@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "rn_dev.h"
+#include "dispatch.h"
 #define RN_RS_CONST static __constant__
 #include "rs_coeffs.h"
 
@@ -463,29 +464,13 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
 }
 
 
-// (up to RN_HP_ONE_MAX streams one wave per stream is the faster form.  With the lane = stream kernel's block loop waiting properly
-// (profiles/r6_hp_specialised.txt) that kernel is one wave's latency chain of ~36 us whatever the batch, from 1,024 to 5,120 streams, and the
-// one-wave form 25 / 35 / 45 / 55 / 65 us at 1,024 / 2,048 / 3,072 / 4,096 / 5,120: the switch sits at 2,048 -- alone on the machine
-// (one frame per call: 0.258 -> 0.239 ms per step at 4,096 streams) and inside pipelined calls (3,072 streams: 20.8 -> 21.1 M frames/s;
-// at 2,048 the one-wave form is the better one by 6 %).  Rounds 5-6 until then: 5,120 / 3,072.)
-#define RN_HP_ONE_MAX 2048
-#define RN_HP_ONE_MAX_PIPELINED 2048
 #define RN_HP_SPW 64  // streams per wave of the lane = stream kernel
-extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s16, int slot, hipStream_t st, hipEvent_t e0, hipEvent_t done) {
-  // bit 9 of `slot` (batch.cpp): the call is one frame of a PIPELINED multi-frame call -- this kernel then runs on a side stream beside the
-  // analysis and network kernels of other frames (the two switches are kept apart because they were different ones until round 6's
-  // last day, and may be again)
-  static const int one_max_env = [] { const char *e = getenv("RNNOISE_AMD_HP_ONE_MAX"); return e ? atoi(e) : -1; }();  // (A/B runs)
-  const bool beside_others = slot & 512;
-  slot &= 511;
-  const int one_max = one_max_env >= 0 ? one_max_env : (beside_others ? RN_HP_ONE_MAX_PIPELINED : RN_HP_ONE_MAX);
-  // low-rate rows (rn_dev.h: RnGroupDev::rs_L) take the wave-per-stream form at every batch size.  (An upsampling prologue in the lane
-  // = stream kernel, one stream after the other per wave, took that kernel from 50 to 61-64 SGPRs in every arrangement tried; the 48 kHz
-  // kernels keep their registers instead.  The cost at large batches: DESIGN.md 4.10, profiles/resample_rate_bench.txt)
-  const int rs = g->rs_L ? 1 : 0;
-  if (rs || g->n_streams <= one_max) {
+// K0 in the form the step's plan chose (dispatch.h: rn_plan)
+extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s16, int slot, RnHpForm form, hipStream_t st, hipEvent_t e0,
+                                   hipEvent_t done) {
+  if (form == RN_HP_ONE_WAVE) {  // (low-rate rows: always this form, dispatch.h)
     RN_LAUNCH(rn_hp_one_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot,
-              in_s16 | (rs ? 2 : 0), RnRows{});
+              in_s16 | (g->rs_L ? 2 : 0), RnRows{});
     return hipGetLastError();
   }
   // (rounds 5-6 had a second build of this kernel with 16-sample blocks at 64 VGPRs -- rn_hp_lean_kernel, a wave of which fits a SIMD

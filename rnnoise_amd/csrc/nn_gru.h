@@ -390,31 +390,3 @@ __device__ __forceinline__ void gru_body(const RnGroupDev &g, const RnModelDev &
   }
 }
 
-
-// ---- host side: a form of the layer kernel, and its LDS opt-in ----
-#include <atomic>
-typedef void (*RnGruKernel)(RnGroupDev, RnModelDev, RnTablesDev, int);
-struct RnGruVariant {
-  const char *name;
-  RnGruKernel k;
-  int threads;
-  size_t lds;
-};
-// more than 64 KB of dynamic LDS is an opt-in per kernel and device; remembered per (kernel, device) -- at most 64 kernels x 64 devices
-// (the product has two kernels).  Concurrent first launches may both set the attribute: idempotent.
-static inline hipError_t rn_gru_opt_in(const RnGruVariant &v, int dev) {
-  static std::atomic<const void *> seen[64][64];
-  const void *key = reinterpret_cast<const void *>(v.k);
-  for (int i = 0; i < 64; i++) {
-    const void *have = seen[dev][i].load(std::memory_order_acquire);
-    if (have == key) return hipSuccess;
-    if (!have) {
-      const hipError_t e = hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
-      if (e != hipSuccess) return e;
-      const void *expect = nullptr;
-      if (seen[dev][i].compare_exchange_strong(expect, key, std::memory_order_acq_rel) || expect == key) return hipSuccess;
-      // (another thread took the slot for another kernel: keep looking)
-    }
-  }
-  return hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);  // table full: set it every time
-}

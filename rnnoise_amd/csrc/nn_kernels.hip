@@ -4,7 +4,6 @@
 // x86 s8 x u8 accumulator exactly), float layers as one FMA chain per output in the
 // reference's AVX2 order.  Follows oracle/rn_oracle.c (lin_float / lin_int8 / gru_step).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <stdint.h>
 #include "rn_dev.h"
 
@@ -538,32 +537,21 @@ rn_nn_one_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb, RnRows rows) {
 #undef ONE_TAP
 }
 
-// the 125 KB of dynamic LDS are an opt-in per DEVICE (a process may hold pools and batches on several GPUs): once per device,
-// on the device the launch goes to
-static hipError_t nn_one_opt_in() {
-  static std::atomic<int> opted[64];
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !opted[dev].load(std::memory_order_acquire)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(rn_nn_one_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(OneLds));
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) opted[dev].store(1, std::memory_order_release);
-  }
-  return hipSuccess;
+// the 125 KB of dynamic LDS are an opt-in per kernel and device: rnnoise_batch_create asks for it on the batch's device (the current one)
+// and keeps the answer, which the launches below return
+extern "C" hipError_t rn_nn_one_opt_in(void) {
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(rn_nn_one_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(OneLds));
 }
-extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, hipStream_t st, hipEvent_t e0,
-                                       hipEvent_t e1) {
-  const hipError_t attr = nn_one_opt_in();
-  if (attr != hipSuccess) return attr;
+extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, hipError_t lds_opt_in, hipStream_t st,
+                                       hipEvent_t e0, hipEvent_t e1) {
+  if (lds_opt_in != hipSuccess) return lds_opt_in;
   RN_LAUNCH(rn_nn_one_kernel, dim3(g->n_streams), dim3(ONE_THREADS), sizeof(OneLds), st, e0, e1, *g, *m, *tb, RnRows{});
   return hipGetLastError();
 }
 // K2 of a launch group of the one-frame API (rn_dev.h: RnRows): one workgroup per listed row
-extern "C" hipError_t rn_launch_nn_rows(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, const RnRows *rows, hipStream_t st) {
-  const hipError_t attr = nn_one_opt_in();
-  if (attr != hipSuccess) return attr;
+extern "C" hipError_t rn_launch_nn_rows(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, const RnRows *rows,
+                                        hipError_t lds_opt_in, hipStream_t st) {
+  if (lds_opt_in != hipSuccess) return lds_opt_in;
   hipLaunchKernelGGL(rn_nn_one_kernel, dim3(rows->n), dim3(ONE_THREADS), sizeof(OneLds), st, *g, *m, *tb, *rows);
   return hipGetLastError();
 }

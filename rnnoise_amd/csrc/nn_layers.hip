@@ -1,4 +1,4 @@
-// nn_layers.hip -- K2 for large batches (from 10,240 streams up, batch.cpp: nn_layers_min_streams): the network layer by layer.
+// nn_layers.hip -- K2 for large batches (from 10,240 streams up, dispatch.h: RN_NN_LAYERS): the network layer by layer.
 //
 //   rn_nn_front_kernel (nn_mfma.hip)  conv1, conv2 per 16-stream tile; leaves the u8 image of the conv2 output in act_q[0]
 //   rn_nn_gru_kernel    x 3           one GRU layer (src/nnet.c:65-94) for 64 streams per workgroup
@@ -12,6 +12,7 @@
 // once the next layer's input and this layer's recurrent operand of the next frame -- leaves the same way.
 // Arithmetic per element is the fused kernel's, so the bits are too (tests/test_gpu_parity.py runs both; tools/ab_layers.py).
 #include "nn_gru.h"
+#include "dispatch.h"
 
 // four waves, one row buffer per wave, 72 KB: two workgroups per CU (profiles/r5_gru_bound.txt has the A/B against the eight-wave form
 // and profiles/r5_gru_race.txt why this one could not ship before round 5)
@@ -24,45 +25,27 @@ extern "C" __global__ void __launch_bounds__(512) rn_nn_gru_w8_kernel(RnGroupDev
   gru_body<2, 8, 3>(g, m, tb, layer);
 }
 
-static const RnGruVariant gru_product[2] = {{"w4", rn_nn_gru_kernel, 256, sizeof(GruLdsT<4, 1>)},
-                                             {"w8", rn_nn_gru_w8_kernel, 512, sizeof(GruLdsT<8, 3>)}};
-static const RnGruVariant *gru_forced_variant() {
-  static const RnGruVariant *const forced = []() -> const RnGruVariant * {
+// the two forms of the layer kernel, indexed by RnGruForm (dispatch.h: the rule between them)
+static const struct {
+  void (*k)(RnGroupDev, RnModelDev, RnTablesDev, int);
+  int threads;
+  size_t lds;
+} gru_forms[2] = {{rn_nn_gru_kernel, 256, sizeof(GruLdsT<4, 1>)}, {rn_nn_gru_w8_kernel, 512, sizeof(GruLdsT<8, 3>)}};
 
-    const char *e = getenv("RNNOISE_AMD_GRU_VARIANT");
-    if (!e || !*e) return nullptr;
-    for (const RnGruVariant &v : gru_product)
-      if (!strcmp(e, v.name)) return &v;
-    fprintf(stderr, "[rnnoise_amd] RNNOISE_AMD_GRU_VARIANT=%s: no such form of the layer kernel in this build (w4 | w8)\n", e);
-    static const RnGruVariant none = {nullptr, nullptr, 0, 0};
-    return &none;
-  }();
-  return forced;
+// more than 64 KB of dynamic LDS is an opt-in per kernel and device: rnnoise_batch_create asks for both forms on the batch's device
+// (the current one) and keeps the answers, which the launches of each form return
+extern "C" void rn_nn_gru_opt_in(hipError_t out[2]) {
+  for (int f = 0; f < 2; f++)
+    out[f] = hipFuncSetAttribute(reinterpret_cast<const void *>(gru_forms[f].k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)gru_forms[f].lds);
 }
 
-extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, int layer, hipStream_t st,
-                                             hipEvent_t e0, hipEvent_t e1) {
-  const int n_tiles = (g->n_streams + TS - 1) / TS, n_groups = (n_tiles + GM - 1) / GM;
-  // The product has exactly these two forms, with the same bits.  By batch size: the four-wave form (two workgroups per CU: 1-3 %
-  // under the eight-wave one stand-alone in every A/B of profiles/r5_gru_bound.txt) once there are more groups than CUs; the eight-wave
-  // form while every group has a CU to itself (a four-wave workgroup would then leave each SIMD with ONE wave: 16,384 streams 0.200
-  // against 0.174 ms for the three layers + front + dense).  $RNNOISE_AMD_GRU_VARIANT = w4 | w8 forces one (tests run both at every
-  // size); any other name is an error, not a silent default.
-  static const RnGruVariant *const forced = gru_forced_variant();
-  if (forced && !forced->k) return hipErrorInvalidValue;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  // (per-device caches written from whichever thread launches first: relaxed atomics, every writer stores the same value)
-  static std::atomic<int> cus[64];
-  int ncu = cus[dev].load(std::memory_order_relaxed);
-  if (!ncu) {
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    cus[dev].store(ncu, std::memory_order_relaxed);
-  }
-  const RnGruVariant &v = forced ? *forced : gru_product[n_groups > ncu ? 0 : 1];
-  // more than 64 KB of LDS is an opt-in, per kernel and device (a process may hold batches on several GPUs)
-  if (hipError_t e = rn_gru_opt_in(v, dev)) return e;
-  RN_LAUNCH(v.k, dim3(n_groups), dim3(v.threads), v.lds, st, e0, e1, *g, *m, *tb, layer);
+extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, int layer, RnGruForm form,
+                                             const hipError_t lds_opt_in[2], hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (form == RN_GRU_UNKNOWN) return hipErrorInvalidValue;  // ($RNNOISE_AMD_GRU_VARIANT names no form: an error, not a silent default)
+  if (lds_opt_in[form] != hipSuccess) return lds_opt_in[form];
+  const int n_groups = ((g->n_streams + TS - 1) / TS + GM - 1) / GM;
+  RN_LAUNCH(gru_forms[form].k, dim3(n_groups), dim3(gru_forms[form].threads), gru_forms[form].lds, st, e0, e1, *g, *m, *tb, layer);
   return hipGetLastError();
 }
 

@@ -15,8 +15,8 @@
 // B lane l -> column (stream) l&15, k-group l>>4; C/D lane l, reg r -> row 4*(l>>4)+r, col l&15.
 // Results are bit-identical to the vector path and to the oracle.
 #include "nn_common.h"
+#include "dispatch.h"
 #include <stdlib.h>
-#include <atomic>
 
 #define CHUNK 256      // inputs per staged chunk of the dense_out / vad chains
 #define CH_STRIDE 260  // floats per stream and chunk in LDS (16-byte aligned rows, 2-way bank conflicts at most)
@@ -87,43 +87,33 @@ extern "C" __global__ void __launch_bounds__(NTHREADS) rn_nn_front_kernel(RnGrou
 #include "nn_tile_body.inc"
 #undef RN_NN_MODE
 }
-extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, hipStream_t st,
-                                        hipEvent_t e0, hipEvent_t e1, int alone) {
+// the tile kernel in the form the step's plan chose (dispatch.h: RN_NN_TILE8 | RN_NN_TILE16)
+extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, RnNnForm form, hipStream_t st,
+                                        hipEvent_t e0, hipEvent_t e1) {
   if (!m->conv2.wmf || !g->nn_act || !m->dense_out.fwm || !m->conv1.fwm) return hipErrorNotSupported;
   const int n_tiles = (g->n_streams + TS - 1) / TS;
-  // sixteen waves per tile in a call that runs nothing beside the network while every tile has a CU to itself, eight otherwise;
-  // $RNNOISE_AMD_TILE_WAVES = 8 | 16 forces one (same bits: tests run both)
-  static const int forced = [] { const char *e = getenv("RNNOISE_AMD_TILE_WAVES"); return e ? atoi(e) : 0; }();
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  static std::atomic<int> cus[64];  // (per-device cache, relaxed: every writer stores the same value)
-  int ncu = cus[dev].load(std::memory_order_relaxed);
-  if (!ncu) {
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    cus[dev].store(ncu, std::memory_order_relaxed);
-  }
-  if (forced == 16 || (forced != 8 && alone && n_tiles <= ncu))
+  if (form == RN_NN_TILE16)
     RN_LAUNCH(rn_nn_mfma16_kernel, dim3(n_tiles), dim3(1024), 0, st, e0, e1, *g, *m, *tb);
   else
     RN_LAUNCH(rn_nn_mfma_kernel, dim3(n_tiles), dim3(NTHREADS), 0, st, e0, e1, *g, *m, *tb);
   return hipGetLastError();
 }
-extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, int layer, hipStream_t st,
-                                             hipEvent_t e0, hipEvent_t e1);
+extern "C" hipError_t rn_launch_nn_gru_layer(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, int layer, RnGruForm form,
+                                             const hipError_t lds_opt_in[2], hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 extern "C" hipError_t rn_launch_nn_dense(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, hipStream_t st, hipEvent_t e0,
                                          hipEvent_t e1);
-// the network layer by layer (front, three GRU layers at 64 streams per workgroup, dense); ev[i] = the optional (start, stop) events
-// of launch i: each kernel is timed on its own, the durations add up to the network's
-extern "C" hipError_t rn_launch_nn_layers(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, hipStream_t st,
-                                          hipEvent_t ev[5][2]) {
+// the network layer by layer (front, three GRU layers at 64 streams per workgroup in the form `gru`, dense); lds_opt_in: the batch's
+// opt-ins of the two GRU forms (rnnoise_batch_create); ev[i] = the optional (start, stop) events of launch i: each kernel is timed on its
+// own, the durations add up to the network's
+extern "C" hipError_t rn_launch_nn_layers(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, RnGruForm gru,
+                                          const hipError_t lds_opt_in[2], hipStream_t st, hipEvent_t ev[5][2]) {
   if (!m->conv2.wmf || !g->nn_act || !m->dense_out.fwm || !m->conv1.fwm || !g->act_q[0] || g->n_streams != g->n_stride) return hipErrorNotSupported;
   if ((size_t)g->n_streams * RN_GRU * 4 >= (1ull << 32)) return hipErrorNotSupported;  // 32-bit offsets in nn_layers.hip
   const dim3 grid((g->n_streams + TS - 1) / TS);
   RN_LAUNCH(rn_nn_front_kernel, grid, dim3(NTHREADS), 0, st, ev[0][0], ev[0][1], *g, *m, *tb);
   for (int k = 0; k < 3; k++) {
-    hipError_t e = rn_launch_nn_gru_layer(g, m, tb, k, st, ev[1 + k][0], ev[1 + k][1]);
+    hipError_t e = rn_launch_nn_gru_layer(g, m, tb, k, gru, lds_opt_in, st, ev[1 + k][0], ev[1 + k][1]);
     if (e != hipSuccess) return e;
   }
   return rn_launch_nn_dense(g, m, tb, st, ev[4][0], ev[4][1]);
 }
-extern "C" int rn_nn_mfma_available(void) { return 1; }

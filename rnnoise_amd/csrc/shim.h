@@ -32,21 +32,27 @@
 #include "../../include/rnnoise_amd_debug.h"
 #endif
 #include "rcp_profiles.h"
+#include "dispatch.h"
 
-extern "C" hipError_t rn_launch_hp(const RnGroupDev *, const void *, int in_s16, int, hipStream_t, hipEvent_t, hipEvent_t);
-extern "C" hipError_t rn_launch_analysis(const RnGroupDev *, const RnTablesDev *, int, int, hipStream_t, hipEvent_t, hipEvent_t);
-extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *, const RnTablesDev *, void *, int out_s16, int, int, hipStream_t,
+// the launchers of a frame step take the form the step's plan chose (dispatch.h: rn_plan)
+extern "C" hipError_t rn_launch_hp(const RnGroupDev *, const void *, int in_s16, int, RnHpForm, hipStream_t, hipEvent_t, hipEvent_t);
+extern "C" hipError_t rn_launch_analysis(const RnGroupDev *, const RnTablesDev *, int, int, RnK1Form, hipStream_t, hipEvent_t, hipEvent_t);
+extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *, const RnTablesDev *, void *, int out_s16, int, int, RnK3Form, hipStream_t,
                                           hipEvent_t, hipEvent_t);
 extern "C" hipError_t rn_launch_train_features(const RnGroupDev *, const RnTablesDev *, const float *, int, int,
                                                const RnTrainArgs *, hipStream_t);
 extern "C" hipError_t rn_launch_nn_vector(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
                                           hipEvent_t);
-extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t, hipEvent_t);
-extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
-                                        hipEvent_t, int alone);  // alone: no other kernel of the call runs beside it
-extern "C" hipError_t rn_launch_nn_layers(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t[5][2]);
+// (lds_opt_in: the batch's answer to the kernel's large-LDS opt-in, RNNoiseBatch::lds_one / lds_gru, returned instead of a launch)
+extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipError_t lds_opt_in, hipStream_t,
+                                       hipEvent_t, hipEvent_t);
+extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, RnNnForm, hipStream_t, hipEvent_t,
+                                        hipEvent_t);
+extern "C" hipError_t rn_launch_nn_layers(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, RnGruForm,
+                                          const hipError_t lds_opt_in[2], hipStream_t, hipEvent_t[5][2]);
 extern "C" hipError_t rn_launch_nn_requant(const RnGroupDev *, hipStream_t, const int *list = nullptr, int n = 0);
-extern "C" int rn_nn_mfma_available(void);
+extern "C" hipError_t rn_nn_one_opt_in(void);             // nn_kernels.hip, on the current device
+extern "C" void rn_nn_gru_opt_in(hipError_t out[2]);      // nn_layers.hip, both forms (RnGruForm order), on the current device
 extern "C" hipError_t rn_launch_release_store(void *, long long, hipStream_t);
 #if RN_INSTRUMENT
 extern "C" hipError_t rn_launch_log_energy(const float *, unsigned, float *, unsigned, const double *, hipStream_t);
@@ -60,7 +66,8 @@ extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, const float *,
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);
 extern "C" hipError_t rn_launch_analysis_rows(const RnGroupDev *, const RnTablesDev *, const RnRows *, hipStream_t);
-extern "C" hipError_t rn_launch_nn_rows(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, const RnRows *, hipStream_t);
+extern "C" hipError_t rn_launch_nn_rows(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, const RnRows *, hipError_t lds_opt_in,
+                                        hipStream_t);
 extern "C" hipError_t rn_launch_synthesis_rows(const RnGroupDev *, const RnTablesDev *, const RnRows *, hipStream_t);
 
 // Every entry point works on the batch's device and leaves the calling thread's current device as it found it
@@ -152,6 +159,10 @@ struct RNNModel {
 struct RNNoiseBatch {
   RNNModel *model = nullptr;
   int device = 0, n = 0, nn_path = 0;
+  // facts about the device, resolved once by rnnoise_batch_create: its compute units (dispatch.h: RnStepShape::cus) and the
+  // large-LDS opt-ins of rn_nn_one_kernel and the two GRU forms (RnGruForm order) -- a launch of a form whose opt-in failed returns it
+  int cus = 256;
+  hipError_t lds_one = hipSuccess, lds_gru[2] = {hipSuccess, hipSuccess};
   bool img_valid = false;  // g.act_q[1..3] mirror gru_state (rn_dev.h); cleared by whatever else writes the state
   int schedule = 0;  // 0: default (3-stream frame pipeline in multi-frame calls); 9: one stream; 1: only the high-pass aside
   int parity = 0;  // spectra slot (mod RN_SPEC_SLOTS) the next frame writes; the previous one holds the delayed spectra
@@ -228,7 +239,7 @@ struct Combiner {
   std::atomic<uint64_t> t_complete_ns{0};  // ... when the last of them left
   std::atomic<int> active{0};              // threads inside rnnoise_process_frame on this pool right now (spin or sleep?)
   std::atomic<uint64_t> group_ns{0};       // running estimate of a group's launch -> frames-out time (followers sleep through most of it)
-  bool no_nn_one = false;                  // the latency network kernel cannot run here (LDS opt-in refused, $RNNOISE_AMD_NN_ONE_MAX=0):
+  bool no_nn_one = false;                  // a one-stream step does not take the latency network kernel ($RNNOISE_AMD_NN_ONE_MAX=0):
                                            // frames go one state at a time through pool_step instead of through launch groups
 };
 
@@ -300,7 +311,7 @@ int model_on_device(RNNModel *m, int device, RnModelDev &out);       // model.cp
 RNNModel *default_model();                                           // model.cpp: the blob behind model == NULL
 void pools_free(RNNModel *model);                                    // dropin.cpp: the state pools of a model (rnnoise_model_free)
 RnGroupDev group_view(const RnGroupDev &g, int first, int count);    // batch.cpp
-int nn_one_max_streams();                                            // batch.cpp
+const RnKnobs &rn_knobs();                                           // batch.cpp: the dispatch switches, read once per process
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out, const void *d_in, float *d_vad, float *d_gains, int n_frames,
                               void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr,
                               const uint8_t *d_active = nullptr);  // batch.cpp

@@ -134,7 +134,7 @@ def test_ragged_40037_streams(blob_default, blob_little, which):
 
 @pytest.mark.rcp("host")
 def test_ragged_10277_streams_just_above_the_network_switch(blob_default):
-    """The layer-wise network starts at 10,240 streams (batch.cpp: nn_layers_min_streams; 16,384 until round 6's last day): a
+    """The layer-wise network starts at 10,240 streams (rnnoise_amd/csrc/dispatch.h: RN_NN_LAYERS; 16,384 until round 6's last day): a
     ragged batch just above the switch -- 10,277 = 16 x 642 + 5 = 64 x 160 + 37, the eight-wave layer kernel (fewer 64-stream groups
     than CUs) with a partial tile and a partial group -- and, below, the largest batches of the tile kernel on both sides of 8,192
     streams (two tiles per CU, then three).  Arithmetic under test: src/nnet.c:65-94, src/rnn.c:44-60."""
