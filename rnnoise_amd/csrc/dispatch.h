@@ -1,7 +1,7 @@
 // dispatch.h -- which form of each kernel a frame step runs, as pure functions of the step's shape and the dispatch switches
 // (no HIP in here, so that tests/test_dispatch_cpu.py can run the rules at every boundary without a GPU).  All forms of a stage give
-// the same bits; the rules only pick the fastest.  batch.cpp builds one plan per call (batch_process_device_impl) and dropin.cpp one
-// for its one-stream view (pool_step); the launchers take the chosen form and make no size decision of their own.
+// the same bits; the rules only pick the fastest.  batch.cpp builds one plan per call (batch_process_device_impl); the launchers take
+// the chosen form and make no size decision of their own.  (Drop-in frames take no plan: they run the row-list kernels, dropin.cpp.)
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>

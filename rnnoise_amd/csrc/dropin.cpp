@@ -24,10 +24,6 @@ int pool_rows() {
   return n;
 }
 
-// The plan of one frame of one pooled state (pool_step): a one-stream view of the pool's batch, at 48 kHz in lock-step phase, on
-// the vector path's kernels whatever the batch's own path (a one-stream view is never the whole batch)
-RnPlan pool_plan(const RNNoiseBatch *b) { return rn_plan(rn_knobs(), {1, false, b->cus, 0, false, false, false}); }
-
 StatePool *pool_new(RNNModel *model, int device) {
   StatePool *p = new StatePool();
   p->rows = pool_rows();
@@ -39,7 +35,7 @@ StatePool *pool_new(RNNModel *model, int device) {
   DeviceGuard guard(device);
   if (!guard.ok ||
       hipHostMalloc((void **)&p->h_io, (size_t)p->rows * RN_ROW_IO * sizeof(float), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-      hipMalloc((void **)&p->d_flat, (size_t)StatePool::FLAT_ROWS * StatePool::FLAT_BLK * sizeof(float)) != hipSuccess) {
+      hipMalloc((void **)&p->d_flat, (size_t)StatePool::FLAT_ROWS * RN_STATE_FLOATS * sizeof(float)) != hipSuccess) {
     if (p->h_io) hipHostFree(p->h_io);
     rnnoise_batch_destroy(p->batch);
     delete p;
@@ -58,9 +54,6 @@ StatePool *pool_new(RNNModel *model, int device) {
     delete p;
     return nullptr;
   }
-  // launch groups run the latency network kernel (rn_nn_one_kernel): where the one-stream plan does not take it, pooled frames go
-  // through pool_step one state at a time, which follows that plan
-  p->comb.no_nn_one = pool_plan(p->batch).nn != RN_NN_ONE;
   return p;
 }
 
@@ -135,25 +128,47 @@ int pool_zero_row(StatePool *p, int slot, hipStream_t st) {
   return 0;
 }
 
-// one frame of one row: the four kernels of a step on a one-stream view, on `st` (no side streams: a single frame has
-// nothing to overlap with).  The row's frame bookkeeping (parity, ring slot, scratch copy) is the caller's.
-int pool_step(StatePool *p, int slot, int parity, int ring_slot, long frame_no, float *d_out, const float *d_in, float *d_vad,
-              hipStream_t st) {
+#if RN_INSTRUMENT
+// $RNNOISE_AMD_TEST_FAIL_GROUP=<n>[,<m>...] (fault injection, instrumented library only): the n-th (m-th ...) launch group of the process
+// "fails" -- AFTER its high-pass has been queued, which is the case that leaves a row's pitch ring one frame ahead of the host-side slot
+// counters
+bool test_fail_group() {
+  static const std::vector<long> fail_at = [] {
+    std::vector<long> v;
+    if (const char *e = RN_LAB_ENV("TEST_FAIL_GROUP"))
+      for (const char *q = e; *q;) {
+        char *end = nullptr;
+        v.push_back(strtol(q, &end, 10));
+        if (end == q) break;
+        q = *end ? end + 1 : end;
+      }
+    return v;
+  }();
+  static std::atomic<long> n_groups{0};
+  const long this_group = n_groups.fetch_add(1);
+  for (long f : fail_at)
+    if (f == this_group) return true;
+  return false;
+}
+#endif
+
+// The four kernels of one frame step over the pool rows of `rows` (entries and count filled in; each row's frame in and out, and its
+// VAD, in the row's block of the pinned memory), on `st`.  group: a launch group of the combiner (the fault injection counts those).
+int rows_launch(StatePool *p, RnRows &rows, hipStream_t st, bool group) {
   RNNoiseBatch *b = p->batch;
-  RnGroupDev g = group_view(b->g, slot, 1);
-  if (frame_no & 1) {
-    g.features = g.features_b;
-    g.silence = g.silence_b;
-    g.pitch = g.pitch_b;
-  }
-  g.vad = d_vad;
-  const int prev = (parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
-  const RnPlan plan = pool_plan(b);
-  HIP_OK(rn_launch_hp(&g, d_in, 0, ring_slot, plan.hp, st, nullptr, nullptr));
-  HIP_OK(rn_launch_analysis(&g, &b->tb, ring_slot, parity, plan.k1, st, nullptr, nullptr));
-  if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, &b->m, &b->tb, b->lds_one, st, nullptr, nullptr));
-  else HIP_OK(rn_launch_nn_vector(&g, &b->m, &b->tb, st, nullptr, nullptr));
-  HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out, 0, parity, prev, plan.k3, st, nullptr, nullptr));
+  // (mapped, coherent pinned memory: the device's alias of the block -- the same address under unified addressing, asked for all the same)
+  void *d_io = nullptr;
+  HIP_OK(hipHostGetDevicePointer(&d_io, p->h_io, 0));
+  rows.io = static_cast<float *>(d_io);
+  HIP_OK(rn_launch_hp_rows(&b->g, &rows, st));
+#if RN_INSTRUMENT
+  if (group && test_fail_group()) return -1;
+#else
+  (void)group;
+#endif
+  HIP_OK(rn_launch_analysis_rows(&b->g, &b->tb, &rows, st));
+  HIP_OK(rn_launch_nn_rows(&b->g, &b->m, &b->tb, &rows, b->lds_one, st));
+  HIP_OK(rn_launch_synthesis_rows(&b->g, &b->tb, &rows, st));
   return 0;
 }
 
@@ -216,7 +231,7 @@ int effective_cpus() {
   return n;
 }
 long futex(int *addr, int op, int val) { return syscall(SYS_futex, addr, op, val, nullptr, nullptr, 0); }
-inline volatile uint32_t *done_word(StatePool *p, int slot) { return reinterpret_cast<volatile uint32_t *>(p->h_io + (size_t)slot * RN_ROW_IO + RN_ROW_IO - 1); }
+inline volatile uint32_t *done_word(StatePool *p, int slot) { return reinterpret_cast<volatile uint32_t *>(p->h_io + (size_t)slot * RN_ROW_IO + RN_ROW_DONE); }
 
 // Retire the entries of a group (combiner lock held): an entry's request goes INFLIGHT / SYNCER -> `state` unless its
 // caller has already seen its frame come out and left (it may be back with a new request under a new sequence number:
@@ -274,44 +289,13 @@ void comb_take_queue(StatePool *p, int k, std::vector<CombMember> &grp) {
 
 // the four kernels of one frame step over the rows of `grp`, on stream k of the pool's combiner
 int comb_launch(StatePool *p, int k, const std::vector<CombMember> &grp) {
-  RNNoiseBatch *b = p->batch;
-  RnRows rows;
-  // (mapped, coherent pinned memory: the device's alias of the block -- the same address under unified addressing, asked for all the same)
-  void *d_io = nullptr;
-  HIP_OK(hipHostGetDevicePointer(&d_io, p->h_io, 0));
-  rows.io = static_cast<float *>(d_io);
+  RnRows rows{};
   rows.n = (int)grp.size();
   for (int i = 0; i < rows.n; i++) {
     const PooledRef *m = grp[i].ref;
     rows.e[i] = RN_ROW_ENTRY(m->slot, m->ring_slot, m->parity, grp[i].seq);
   }
-  for (int i = rows.n; i < RN_ROWS_MAX; i++) rows.e[i] = 0;
-  hipStream_t st = p->comb.stream[k];
-  HIP_OK(rn_launch_hp_rows(&b->g, &rows, st));
-#if RN_INSTRUMENT
-  // $RNNOISE_AMD_TEST_FAIL_GROUP=<n>[,<m>...] (fault injection, instrumented library only): the n-th (m-th ...) launch group of the process
-  // "fails" here -- AFTER its high-pass has been queued, which is the case that leaves a row's pitch ring one frame ahead of the
-  // host-side slot counters
-  static const std::vector<long> fail_at = [] {
-    std::vector<long> v;
-    if (const char *e = RN_LAB_ENV("TEST_FAIL_GROUP"))
-      for (const char *q = e; *q;) {
-        char *end = nullptr;
-        v.push_back(strtol(q, &end, 10));
-        if (end == q) break;
-        q = *end ? end + 1 : end;
-      }
-    return v;
-  }();
-  static std::atomic<long> n_groups{0};
-  const long this_group = n_groups.fetch_add(1);
-  for (long f : fail_at)
-    if (f == this_group) return -1;
-#endif
-  HIP_OK(rn_launch_analysis_rows(&b->g, &b->tb, &rows, st));
-  HIP_OK(rn_launch_nn_rows(&b->g, &b->m, &b->tb, &rows, b->lds_one, st));
-  HIP_OK(rn_launch_synthesis_rows(&b->g, &b->tb, &rows, st));
-  return 0;
+  return rows_launch(p, rows, p->comb.stream[k], true);
 }
 
 bool comb_complete(StatePool *p, int k, PooledRef *self);
@@ -678,11 +662,6 @@ extern "C" void rnnoise_destroy(DenoiseState *st) {
   if (st->magic == kPooledMagic) {
     PooledRef &r = st->ref;
     comb_forget(r.pool, &r);
-    if (r.stream) {
-      DeviceGuard guard(r.pool->batch->device);
-      hipStreamSynchronize(r.stream);
-      hipStreamDestroy(r.stream);
-    }
     delete r.mu;
     pool_release(r.pool, r.slot);
   }
@@ -704,45 +683,32 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
     // device-resident state.  The frame travels through the row's block of the pool's pinned memory, which the kernels address
     // directly (host memory mapped into the device's address space: the first kernel reads its 1,920 bytes over PCIe, the
     // last ones write frame and VAD back): no copy commands.  The launches are shared with whoever else is calling on this
-    // pool right now (the combiner above); $RNNOISE_AMD_COMBINE=0: four launches on a stream of the state's own, as in
-    // round 3 (A/B runs).
+    // pool right now (the combiner above).
     PooledRef &r = st->ref;
     std::lock_guard<std::mutex> lk(*r.mu);
     DeviceGuard guard(r.pool->batch->device);
     if (!guard.ok) return frame_failed(out, "cannot select the HIP device");
-    static const bool combine = [] { const char *e = getenv("RNNOISE_AMD_COMBINE"); return !e || atoi(e) != 0; }();
-    float *h_in = r.h_io, *h_out = r.h_io + RN_FRAME_SIZE + 4;
     if (__atomic_load_n(&r.poisoned, __ATOMIC_SEQ_CST)) {
       // a launch group this state was part of failed after its high-pass may have run: the row's pitch ring and the host-side slot
       // counters no longer agree.  Restart the stream from zero (what rnnoise_init leaves) rather than run it one ring slot off.
       fprintf(stderr, "[rnnoise_amd] rnnoise_process_frame: the previous frame of this state failed on the GPU; its state restarts from zero\n");
       if (pool_zero_row(r.pool, r.slot, nullptr) || hipStreamSynchronize(nullptr) != hipSuccess) return frame_failed(out, "cannot reset the state's row");
       r.parity = r.ring_slot = 0;
-      r.frame_no = 0;
       __atomic_store_n(&r.poisoned, 0, __ATOMIC_SEQ_CST);
     }
-    memcpy(h_in, in, RN_FRAME_SIZE * sizeof(float));
-    bool ok;
-    if (combine && !r.pool->comb.no_nn_one) {
-      ok = comb_submit(r.pool, &r);
-    } else {
-      ok = (r.stream || hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking) == hipSuccess) &&
-           pool_step(r.pool, r.slot, r.parity, r.ring_slot, r.frame_no, h_out, h_in, h_out + RN_FRAME_SIZE, r.stream) == 0 &&
-           hipStreamSynchronize(r.stream) == hipSuccess;
-    }
-    if (!ok) {
-      __atomic_store_n(&r.poisoned, 1, __ATOMIC_SEQ_CST);  // (whichever path failed: the frame may be half in the row's state)
+    memcpy(r.h_io + RN_ROW_IN, in, RN_FRAME_SIZE * sizeof(float));
+    if (!comb_submit(r.pool, &r)) {
+      __atomic_store_n(&r.poisoned, 1, __ATOMIC_SEQ_CST);  // (the frame may be half in the row's state)
       return frame_failed(out, "GPU step failed");
     }
     r.parity = (r.parity + 1) % RN_SPEC_SLOTS;
     r.ring_slot = (r.ring_slot + 1) % RN_RING_SLOTS;
-    r.frame_no++;
-    memcpy(out, h_out, RN_FRAME_SIZE * sizeof(float));
-    return h_out[RN_FRAME_SIZE];
+    memcpy(out, r.h_io + RN_ROW_OUT, RN_FRAME_SIZE * sizeof(float));
+    return r.h_io[RN_ROW_VAD];
   }
-  // self-contained state: borrow a pool row for the duration of the call -- state + frame up in one copy, scatter,
-  // the four kernels, gather, state + frame + VAD down in one copy.  Rows are per call, so states on different threads
-  // proceed concurrently.
+  // self-contained state: borrow a pool row for the duration of the call -- state up, scatter into the row, the row kernels of a
+  // launch group of one (the frame in and out through the row's block of pinned memory, as a pooled state's), gather, state down.
+  // Rows are per call, so states on different threads proceed concurrently.
   RNNModel *m = st->model;
   StatePool *pool = nullptr;
   int slot = -1;
@@ -755,7 +721,7 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
       if (stream && h && device == dev) return true;
       release();
       if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { stream = nullptr; return false; }
-      if (hipHostMalloc((void **)&h, 2 * StatePool::FLAT_BLK * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+      if (hipHostMalloc((void **)&h, 2 * RN_STATE_FLOATS * sizeof(float), hipHostMallocDefault) != hipSuccess) {
         h = nullptr;
         release();
         return false;
@@ -780,25 +746,28 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
   bool ok = false;
   {
     DeviceGuard guard(pool->batch->device);
-    constexpr size_t IO = StatePool::FLAT_IO, UP = IO + RN_FRAME_SIZE, DOWN = UP + 1;
     if (guard.ok && sc.ready(pool->batch->device)) {
-      float *d_blk = pool->d_flat + (size_t)slot * StatePool::FLAT_BLK, *d_io = d_blk + IO;  // frame processed in place
+      float *d_state = pool->d_flat + (size_t)slot * RN_STATE_FLOATS, *h_row = pool->h_io + (size_t)slot * RN_ROW_IO;
       const RnGroupDev v = group_view(pool->batch->g, slot, 1);
       // conventions of a freshly scattered row: its newest frame sits in ring slot 5 and spectra slot 2, so the next frame
-      // goes to ring slot 0 / spectra slot 0 and leaves its own "delayed" spectra in slot 0
-      float *hu = sc.h, *hd = sc.h + StatePool::FLAT_BLK;
+      // goes to ring slot 0 / spectra slot 0 and leaves its own "delayed" spectra in slot 0.  (Sequence number 0: nobody polls a
+      // borrowed row's `done` word -- this thread synchronises its stream.)
+      RnRows rows{};
+      rows.n = 1;
+      rows.e[0] = RN_ROW_ENTRY(slot, 0, 0, 0);
+      float *hu = sc.h, *hd = sc.h + RN_STATE_FLOATS;
       memcpy(hu, st->state, RN_STATE_FLOATS * sizeof(float));
-      memcpy(hu + IO, in, RN_FRAME_SIZE * sizeof(float));
-      ok = hipMemcpyAsync(d_blk, hu, UP * sizeof(float), hipMemcpyHostToDevice, sc.stream) == hipSuccess &&
-           rn_launch_state_scatter(&v, d_blk, RN_RING_SLOTS - 1, RN_SPEC_SLOTS - 1, sc.stream) == hipSuccess &&
-           pool_step(pool, slot, 0, 0, 0, d_io, d_io, d_io + RN_FRAME_SIZE, sc.stream) == 0 &&
-           rn_launch_state_gather(&v, d_blk, 0, 0, sc.stream) == hipSuccess &&
-           hipMemcpyAsync(hd, d_blk, DOWN * sizeof(float), hipMemcpyDeviceToHost, sc.stream) == hipSuccess &&
+      memcpy(h_row + RN_ROW_IN, in, RN_FRAME_SIZE * sizeof(float));
+      ok = hipMemcpyAsync(d_state, hu, RN_STATE_FLOATS * sizeof(float), hipMemcpyHostToDevice, sc.stream) == hipSuccess &&
+           rn_launch_state_scatter(&v, d_state, RN_RING_SLOTS - 1, RN_SPEC_SLOTS - 1, sc.stream) == hipSuccess &&
+           rows_launch(pool, rows, sc.stream, false) == 0 &&
+           rn_launch_state_gather(&v, d_state, 0, 0, sc.stream) == hipSuccess &&
+           hipMemcpyAsync(hd, d_state, RN_STATE_FLOATS * sizeof(float), hipMemcpyDeviceToHost, sc.stream) == hipSuccess &&
            hipStreamSynchronize(sc.stream) == hipSuccess;
       if (ok) {
         memcpy(st->state, hd, RN_STATE_FLOATS * sizeof(float));
-        memcpy(out, hd + IO, RN_FRAME_SIZE * sizeof(float));
-        vad = hd[IO + RN_FRAME_SIZE];
+        memcpy(out, h_row + RN_ROW_OUT, RN_FRAME_SIZE * sizeof(float));
+        vad = h_row[RN_ROW_VAD];
       }
     }
   }
@@ -806,4 +775,3 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
   if (!ok) return frame_failed(out, "GPU step failed");
   return vad;
 }
-

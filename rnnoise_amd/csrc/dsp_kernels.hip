@@ -1621,23 +1621,13 @@ rn_analysis_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity) {
 // (pipelined bench, M frames/s, 1 vs K1_SPW streams per workgroup): 2048 streams 13.9 / 14.0, 4096: 20.0 / 18.3,
 // 8192: 17.7 / 19.6, 16,384: 19.0 / 22.1.  (Round 1's 80-VGPR "lean" build no longer pays at any size and is gone.)
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
-rn_analysis_single_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity, RnRows rows) {
-  // (a launch group of the one-frame API: the block's row at that row's own frame phase.  ONE instance of the body: two made the
-  //  kernel 80 KB of code, more than the instruction cache two CUs share)
-  const bool listed = rows.n > 0;
-  const uint32_t re = listed ? rows.e[blockIdx.x] : 0u;
-  int ring = listed ? RN_ROW_RING(re) : slot, spec = listed ? RN_ROW_SPEC(re) : parity;
-  if (!listed && g.phase) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
-    bool present;
-    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, blockIdx.x, present));  // (the workgroup's one stream: uniform)
-    if (!present) {  // an absent stream: the sentinel silence = 2 keeps the network off its state, and nothing else is written
-      if (threadIdx.x == 0) g.silence[blockIdx.x] = 2;
-      return;
-    }
-    ring = p % RN_RING_SLOTS;
-    spec = p % RN_SPEC_SLOTS;
+rn_analysis_single_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity) {
+  const RnStreamAt at = rn_stream_at(g, nullptr, slot, parity, 0);
+  if (!at.present) {  // an absent stream: the sentinel silence = 2 keeps the network off its state, and nothing else is written
+    g.silence[at.s] = 2;  // (every lane stores the same word)
+    return;
   }
-  analysis_body<false, 1>(g, tb, ring, spec, RnTrainArgs{}, listed ? RN_ROW_OF(re) : -1);
+  analysis_body<false, 1>(g, tb, at.ring, at.spec, RnTrainArgs{});
 }
 
 // A launch group of the one-frame API, for LATENCY: one workgroup of K1_SPW waves per listed row, every wave working on that
@@ -1647,8 +1637,9 @@ rn_analysis_single_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity, Rn
 // after the other on the stream's only wave.  Only wave 0 stores.
 extern "C" __global__ void __launch_bounds__(WAVE * K1_SPW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 rn_analysis_rows_kernel(RnGroupDev g, RnTablesDev tb, RnRows rows) {
-  const uint32_t re = rows.e[blockIdx.x];
-  analysis_body<false, K1_SPW>(g, tb, RN_ROW_RING(re), RN_ROW_SPEC(re), RnTrainArgs{}, RN_ROW_OF(re));
+  __builtin_assume(rows.n > 0);  // (launched for launch groups only)
+  const RnStreamAt at = rn_stream_at(g, &rows, 0, 0, 0);
+  analysis_body<false, K1_SPW>(g, tb, at.ring, at.spec, RnTrainArgs{}, at.s);
 }
 
 // TRAINING-mode variant: the inner loop of src/dump_features.c:466-491
@@ -1713,28 +1704,22 @@ __device__ __forceinline__ unsigned synth_index(int b, unsigned pos, bool &lo, u
   return mem;
 }
 template <bool LATE>
-__device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTablesDev &tb, float *__restrict__ out, int parity_arg, int prev_arg,
-                                               const RnRows &rows) {
+__device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTablesDev &tb, float *__restrict__ out, int parity_arg,
+                                               const RnStreamAt &at) {
   // bit 8 of parity_arg: `out` holds int16 samples, written with the truncating conversion of the reference's only caller
   // (examples/rnnoise_demo.c:58: tmp[i] = x[i], float -> short as x86 compiles it: cvttss2si to 32 bits -- "integer
   // indefinite" 0x80000000 when out of range or NaN -- then the low 16 bits)
-  const bool listed = rows.n > 0;  // a launch group of the one-frame API (rn_dev.h: RnRows)
-  const uint32_t re = listed ? rows.e[blockIdx.x] : 0u;
-  int parity = listed ? RN_ROW_SPEC(re) : (parity_arg & 255);
-  int prev = listed ? (parity + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS : prev_arg;
-  if (!listed && g.phase) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
-    bool present;
-    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, blockIdx.x, present));  // (the wave's one stream: uniform)
-    // the call's last frame advances the stream's phase (every kernel of the call that reads it has finished: batch.cpp)
-    if (g.call_frame == g.call_frames - 1 && threadIdx.x == 0) g.phase[blockIdx.x] = (p + (present ? 1 : 0)) % RN_RING_SLOTS;
-    if (!present) return;  // an absent stream: neither `out` nor any state is written
-    parity = p % RN_SPEC_SLOTS;
-    prev = (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
-  }
+  const bool listed = at.listed;  // a launch group of the one-frame API (rn_dev.h: RnRows)
+  const int parity = at.spec, prev = at.prev;
+  // per-stream frame phase (rn_dev.h: RnGroupDev::phase): the call's last frame advances the stream's phase (every kernel of the call
+  // that reads it has finished: batch.cpp)
+  if (!listed && g.phase && g.call_frame == g.call_frames - 1 && threadIdx.x == 0)
+    g.phase[at.s] = (at.ring + (at.present ? 1 : 0)) % RN_RING_SLOTS;
+  if (!at.present) return;  // an absent stream: neither `out` nor any state is written
   const bool out_s16 = !listed && (parity_arg & 256);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   SynthLds &L = *reinterpret_cast<SynthLds *>(smem_raw);
-  const int s = listed ? RN_ROW_OF(re) : (int)blockIdx.x, lane = (int)threadIdx.x, pos = fft_pos(lane);
+  const int s = at.s, lane = (int)threadIdx.x, pos = fft_pos(lane);
   const float2 *dX = reinterpret_cast<const float2 *>(g.spec_X[prev] + (size_t)s * RN_SPEC_STRIDE);
   const float2 *dP = reinterpret_cast<const float2 *>(g.spec_P[prev] + (size_t)s * RN_SPEC_STRIDE);
   const float *dE = g.spec_E[prev] + (size_t)s * 96;
@@ -1878,7 +1863,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     }
   }
   // window + overlap-add (src/denoise.c:400-407), straight from the registers
-  float *o = listed ? rows.io + (size_t)s * RN_ROW_IO + RN_FRAME_SIZE + 4 : out + (size_t)s * RN_FRAME_SIZE;
+  float *o = listed ? at.io + RN_ROW_OUT : out + (size_t)s * RN_FRAME_SIZE;
 #pragma unroll
   for (int b = 0; b < 15; b++) {
     bool lo;
@@ -1902,7 +1887,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     // completion word of the row's request (the last word of its pinned block): the caller waiting for this frame polls it
     // instead of waiting for the whole stream to drain.  System-scope release: the frame and the VAD are visible before it.
     __threadfence_system();
-    if (lane == 0) __hip_atomic_store(reinterpret_cast<uint32_t *>(rows.io + (size_t)s * RN_ROW_IO + RN_ROW_IO - 1), RN_ROW_SEQ(re),
+    if (lane == 0) __hip_atomic_store(reinterpret_cast<uint32_t *>(at.io + RN_ROW_DONE), RN_ROW_SEQ(at.e),
                                       __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -1912,9 +1897,9 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
 // RnGroupDev::rs_dn as `out` and the caller's buffer as RnGroupDev::rs_out, and after the body the wave stages, in L.S (free once the body is done), the stream's down history
 // v[-47 L .. -1], the frame's 480 samples and the taps, and forms the 480 / L outputs, lane l those of m = l, l + 64, ...  The body is not
 // compiled a second time and L is a run-time value, so that the epilogue stays inside the registers of the body.
+// Called only for a stream that has this frame (rn_stream_at: RnStreamAt::present).
 __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s) {
   void *out = g.rs_out;
-  if (g.phase && g.active && !g.active[(size_t)g.call_frame * g.n_stride + s]) return;  // (absent: the body wrote nothing either)
   const int lane = threadIdx.x, L = g.rs_L, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
   const float *row = g.rs_dn + (size_t)s * RN_FRAME_SIZE;
@@ -1964,22 +1949,24 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
   }
 }
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(RN_K3_WAVES, RN_K3_WAVES)))
-rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg, RnRows rows) {
+rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg) {
   const bool rs = parity_arg & 512;
-  synthesis_body<true>(g, tb, out, parity_arg, prev_arg, rows);
-  if (rs) {
+  const RnStreamAt at = rn_stream_at(g, nullptr, 0, parity_arg & 255, prev_arg);
+  synthesis_body<true>(g, tb, out, parity_arg, at);
+  if (rs && at.present) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, blockIdx.x);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s);
   }
 }
 // the launch groups of the one-frame API and small batches (dispatch.h: RN_K3_FEW)
 extern "C" __global__ void __launch_bounds__(WAVE)
 rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg, RnRows rows) {
   const bool rs = parity_arg & 512;  // (never set for a row list)
-  synthesis_body<false>(g, tb, out, parity_arg, prev_arg, rows);
-  if (rs) {
+  const RnStreamAt at = rn_stream_at(g, &rows, 0, parity_arg & 255, prev_arg);
+  synthesis_body<false>(g, tb, out, parity_arg, at);
+  if (rs && at.present) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, blockIdx.x);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s);
   }
 }
 
@@ -1991,7 +1978,7 @@ extern "C" hipError_t rn_launch_analysis(const RnGroupDev *g, const RnTablesDev 
                                          hipEvent_t e0, hipEvent_t e1) {
   const int n = g->n_streams;
   if (form == RN_K1_SINGLE) {
-    RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity, RnRows{});
+    RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity);
   } else {
     const dim3 grid((n + K1_SPW - 1) / K1_SPW), block(WAVE * K1_SPW);
     // bit 8: issue priority (rn_analysis_kernel); bits 16-20: K1_STOP (instrumented build, tools/k1_prefix.sh)
@@ -2024,7 +2011,7 @@ extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev
               arg, prev, RnRows{});
   else
     RN_LAUNCH(rn_synthesis_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
-              arg, prev, RnRows{});
+              arg, prev);
   return hipGetLastError();
 }
 // K1 / K3 of a launch group of the one-frame API (rn_dev.h: RnRows): one one-wave workgroup per listed row

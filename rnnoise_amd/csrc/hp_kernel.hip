@@ -300,7 +300,7 @@ static_assert(RN_RS_LDS <= RN_PITCH_BUF_SIZE, "the upsampling prologue's LDS fit
 //  one-frame API, in front of a kernel of ~20 us)
 template <bool IN_S16>
 __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, const float *__restrict__ in, const float *__restrict__ in_row,
-                                            bool listed, int s, int slot, int slot_arg) {
+                                            bool listed, int s, int slot) {
   constexpr bool in_s16 = IN_S16;
   const int lane = threadIdx.x;
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
@@ -403,9 +403,8 @@ __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, co
       }
     }
     // a listed row whose analysis runs as a four-wave workgroup gets its 5 FIR taps there, on a spare wave, beside the
-    // transform of X (rn_analysis_rows_kernel): the lags, a third of this kernel's time, are not formed here (bit 8 of
-    // slot_arg set by the launcher: they ARE wanted -- rn_launch_hp_rows leaves it clear)
-    if (listed && !(slot_arg & 256)) return;
+    // transform of X (rn_analysis_rows_kernel): the lags, a third of this kernel's time, are not formed here
+    if (listed) return;
     if (lane == 0) xlp[0] = .5f * (.5f * pb01.y + pb01.x);
     if (lane < 8) xlp[864 + lane] = 0;
     xlp[872 + lane] = 0;
@@ -442,15 +441,9 @@ extern "C" __global__ void __launch_bounds__(WAVE)
 rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int in_s16, RnRows rows) {
   __shared__ __attribute__((aligned(16))) HpOneLds L;
   // (rows: the launch groups of the one-frame API, rn_dev.h -- the block's stream, ring slot and frame buffer come from the list)
-  const bool listed = rows.n > 0;
-  const uint32_t re = listed ? rows.e[blockIdx.x] : 0u;
-  const int s = listed ? RN_ROW_OF(re) : (int)blockIdx.x;
-  int slot = listed ? RN_ROW_RING(re) : slot_arg;
-  if (!listed && g.phase) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase); an absent stream writes nothing
-    bool present;
-    slot = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, s, present)) % RN_RING_SLOTS;  // (the wave's one stream: uniform)
-    if (!present) return;
-  }
+  const RnStreamAt at = rn_stream_at(g, &rows, slot_arg, 0, 0);
+  const int s = at.s;
+  if (!at.present) return;  // an absent stream writes nothing
   if (in_s16 & 2) {  // low-rate rows (never a row list): upsampled into RnGroupDev::rs_up, staged in the body's LDS before the body uses it
     if (in_s16 & 1) rs_up_stream<true>(g, in, s, L.pb, g.rs_L);
     else rs_up_stream<false>(g, in, s, L.pb, g.rs_L);
@@ -458,9 +451,9 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
     in = g.rs_up;
     in_s16 = 0;
   }
-  const float *in_row = listed ? rows.io + (size_t)s * RN_ROW_IO : in + (size_t)s * RN_FRAME_SIZE;
-  if (in_s16) hp_one_body<true>(L, g, in, in_row, listed, s, slot, slot_arg);
-  else hp_one_body<false>(L, g, in, in_row, listed, s, slot, slot_arg);
+  const float *in_row = at.listed ? at.io + RN_ROW_IN : in + (size_t)s * RN_FRAME_SIZE;
+  if (in_s16) hp_one_body<true>(L, g, in, in_row, at.listed, s, at.ring);
+  else hp_one_body<false>(L, g, in, in_row, at.listed, s, at.ring);
 }
 
 

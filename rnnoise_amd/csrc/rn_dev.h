@@ -172,9 +172,9 @@ struct RnGroupDev {
 // states of one pool are gathered into ONE launch group: block b of the latency kernels (rn_hp_one_kernel,
 // rn_analysis_rows_kernel, rn_nn_one_kernel, rn_synthesis_few_kernel) then works on pool row RN_ROW_OF(e[b]) at that row's own
 // frame phase -- ring slot RN_ROW_RING(e[b]), spectra slot RN_ROW_SPEC(e[b]) -- and exchanges the frame through the row's block
-// of the pool's pinned host memory: io + row * RN_ROW_IO = in[480] | pad[4] | out[480] | vad | pad[2] | done, where the last
-// kernel of the group stores the request's sequence number RN_ROW_SEQ(e[b]) into `done` once frame and VAD are out.  n == 0: no
-// list -- block b is stream b of the group and the launch's own arguments apply (every batched call).  Passed by value: the list
+// of the pool's pinned host memory: io + row * RN_ROW_IO = in[480] | pad[4] | out[480] | vad | pad[2] | done (RN_ROW_IN ...), where
+// the last kernel of the group stores the request's sequence number RN_ROW_SEQ(e[b]) into `done` once frame and VAD are out.  n == 0:
+// no list -- block b is stream b of the group and the launch's own arguments apply (every batched call).  Passed by value: the list
 // rides in the kernel arguments, so a group costs no copy and no extra memory round trip.
 // A list has at most RN_ROWS_MAX entries; a pool has up to RN_POOL_ROWS_MAX rows (round 5: 1024 instead of 64, so that a thousand
 // states share ONE combiner and its three streams instead of opening a pool -- and three streams -- per 64).
@@ -185,7 +185,11 @@ struct RnGroupDev {
 #define RN_ROW_RING(e) ((int)(((e) >> 10) & 7u))
 #define RN_ROW_SPEC(e) ((int)(((e) >> 13) & 3u))
 #define RN_ROW_SEQ(e) ((e) >> 16)
-#define RN_ROW_IO 968
+#define RN_ROW_IO 968                          // floats of a row's block
+#define RN_ROW_IN 0                            // the frame in
+#define RN_ROW_OUT (RN_FRAME_SIZE + 4)         // the frame out (16-byte aligned)
+#define RN_ROW_VAD (2 * RN_FRAME_SIZE + 4)     // its VAD probability
+#define RN_ROW_DONE (RN_ROW_IO - 1)            // the sequence number of the last request whose frame and VAD are out
 struct RnRows {
   float *io;
   int n;
@@ -270,6 +274,46 @@ __device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, bool 
     p += g.call_frame;
   }
   return p;
+}
+// Which stream a workgroup-per-stream kernel works on, and at which frame phase -- resolved once at its top (rn_stream_at):
+// from its row list entry (listed), from the stream's own phase (g.phase set), or from the launch's arguments (lock-step).
+// Every field is wave-uniform.
+struct RnStreamAt {
+  int s;           // the stream's row in the group's arrays
+  int ring;        // pitch-ring slot of this frame
+  int spec, prev;  // spectra slot of this frame, and the one before it (the reference's delayed_*)
+  bool present;    // the stream has this frame (false only for a masked-out stream of a per-stream call)
+  bool listed;     // block b works on row list entry e ...
+  uint32_t e;
+  float *io;       // ... and exchanges the frame through this block of pinned memory (rn_dev.h: RnRows)
+};
+// rows: the kernel's row list, or null for the kernels that have none; ring / spec / prev: the launch's lock-step arguments
+__device__ __forceinline__ RnStreamAt rn_stream_at(const RnGroupDev &g, const RnRows *rows, int ring, int spec, int prev) {
+  RnStreamAt a;
+  a.listed = rows && rows->n > 0;
+  a.present = true;
+  if (a.listed) {
+    a.e = rows->e[blockIdx.x];
+    a.s = RN_ROW_OF(a.e);
+    a.ring = RN_ROW_RING(a.e);
+    a.spec = RN_ROW_SPEC(a.e);
+    a.prev = (a.spec + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
+    a.io = rows->io + (size_t)a.s * RN_ROW_IO;
+    return a;
+  }
+  a.e = 0;
+  a.io = nullptr;
+  a.s = (int)blockIdx.x;
+  a.ring = ring;
+  a.spec = spec;
+  a.prev = prev;
+  if (g.phase) {
+    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, a.s, a.present));  // (the workgroup's one stream: uniform)
+    a.ring = p % RN_RING_SLOTS;
+    a.spec = p % RN_SPEC_SLOTS;
+    a.prev = (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
+  }
+  return a;
 }
 #include <hip/hip_ext.h>
 // Launch with optional start / stop events: they are bound to the dispatch packet itself (hipExtLaunchKernel), so

@@ -239,8 +239,6 @@ struct Combiner {
   std::atomic<uint64_t> t_complete_ns{0};  // ... when the last of them left
   std::atomic<int> active{0};              // threads inside rnnoise_process_frame on this pool right now (spin or sleep?)
   std::atomic<uint64_t> group_ns{0};       // running estimate of a group's launch -> frames-out time (followers sleep through most of it)
-  bool no_nn_one = false;                  // a one-stream step does not take the latency network kernel ($RNNOISE_AMD_NN_ONE_MAX=0):
-                                           // frames go one state at a time through pool_step instead of through launch groups
 };
 
 // A pool of device-resident one-stream states of one model on one device: the arrays of a POOL_SLOTS-stream batch, of
@@ -252,11 +250,9 @@ struct StatePool {
   // and three streams of its own -- 64 threads over 256 / 1,024 states: 152 k / 30 k frames/s against 304 k / 132 k with 256 rows.
   int rows = 0;
   RNNoiseBatch *batch = nullptr;   // owns the arena; never processed as a whole
-  static constexpr int FLAT_IO = RN_STATE_FLOATS + 2;           // frame offset inside a staging block (16-byte aligned)
-  static constexpr int FLAT_BLK = FLAT_IO + RN_FRAME_SIZE + 4;  // state | pad | frame (in, then out in place) | vad | pad
-  static constexpr int FLAT_ROWS = 64;                          // staging blocks (rnnoise_init states borrow rows 0 .. 63 only)
-  float *h_io = nullptr;           // pinned [rows][RN_ROW_IO]: in[480] | pad[4] | out[480] | vad | pad[2] | done (rn_dev.h: RnRows)
-  float *d_flat = nullptr;         // [FLAT_ROWS][FLAT_BLK] staging for self-contained states (rnnoise_init path)
+  static constexpr int FLAT_ROWS = 64;  // staged states (rnnoise_init states borrow rows 0 .. 63 only)
+  float *h_io = nullptr;                // pinned [rows][RN_ROW_IO]: in[480] | pad[4] | out[480] | vad | pad[2] | done (rn_dev.h: RnRows)
+  float *d_flat = nullptr;              // [FLAT_ROWS][RN_STATE_FLOATS] staging of self-contained states (rnnoise_init path)
   std::mutex mu;
   std::vector<unsigned long long> used;  // bit per row
   // combiner words of the rows' requests.  They live HERE, not in the state (PooledRef), because a group's owner touches a
@@ -272,10 +268,8 @@ struct PooledRef {
   StatePool *pool;
   int slot;
   int parity, ring_slot;
-  long frame_no;
   float *h_io;        // the row's block of the pool's pinned frame memory
   std::mutex *mu;     // one frame at a time per state (the reference's states are not re-entrant either)
-  hipStream_t stream; // only when the combiner is switched off ($RNNOISE_AMD_COMBINE=0): the state's own stream
   int grp;            // combiner: stream slot of the group the request went into
   uint32_t seq;       // combiner: sequence number of the request (never 0); the last kernel stores it into the row's `done` word
   uint32_t req_no;    // combiner: requests made so far, failed ones included (the sequence numbers come from here, so that a retried

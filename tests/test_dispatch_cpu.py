@@ -71,7 +71,7 @@ def test_k2_path0_latency_kernel_up_to_nn_one_max(prog):
     assert k2(prog, 513) == "rn_nn_vector_kernel"
     assert k2(prog, 1, NN_ONE_MAX=0) == "rn_nn_vector_kernel"
     assert k2(prog, 65536, whole=True) == "rn_nn_vector_kernel"                  # path 0 never runs the layers
-    # a pooled state's frame (dropin.cpp: pool_plan, one stream, never whole): the combiner is skipped iff this is not rn_nn_one_kernel
+    # a one-stream view that is not the whole batch (drop-in frames do not take a plan: they run the row-list kernels, dropin.cpp)
     assert plan(prog, 1, whole=False) == ("rn_hp_one_kernel", "rn_analysis_single_kernel", "rn_nn_one_kernel", "rn_nn_gru_w8_kernel",
                                           "rn_synthesis_few_kernel")
     assert k2(prog, 1, whole=False, NN_ONE_MAX=0) == "rn_nn_vector_kernel"
@@ -173,7 +173,7 @@ def _src(name):
     return open(os.path.join(CSRC, name)).read()
 
 
-def test_the_launchers_take_the_plan_and_read_no_switch():
+def test_the_launchers_take_the_plan_and_drop_in_frames_the_row_kernels():
     for f in ("hp_kernel.hip", "dsp_kernels.hip", "nn_kernels.hip", "nn_mfma.hip", "nn_layers.hip", "nn_gru.h"):
         text = _src(f)
         assert "getenv" not in text and "hipGetDevice(" not in text, f
@@ -183,8 +183,13 @@ def test_the_launchers_take_the_plan_and_read_no_switch():
     batch = _src("batch.cpp")
     assert "rn_plan(rn_knobs()" in batch and "rn_schedule(rn_knobs()" in batch and "rn_default_nn_path(rn_knobs()" in batch
     assert "hipDeviceAttributeMultiprocessorCount" in batch and "rn_nn_one_opt_in()" in batch and "rn_nn_gru_opt_in(" in batch
+    # drop-in frames take no plan: every one of them is a launch group of the row-list kernels
     dropin = _src("dropin.cpp")
-    assert "rn_plan(rn_knobs()" in dropin and "pool_plan(p->batch).nn != RN_NN_ONE" in dropin
+    assert "rn_plan(" not in dropin
+    for launcher in ("rn_launch_hp_rows(", "rn_launch_analysis_rows(", "rn_launch_nn_rows(", "rn_launch_synthesis_rows("):
+        assert dropin.count(launcher) == 1, launcher
+    for launcher in ("rn_launch_hp(", "rn_launch_analysis(", "rn_launch_nn_one(", "rn_launch_nn_vector(", "rn_launch_synthesis("):
+        assert launcher not in dropin, launcher
     for f in ("batch.cpp", "dropin.cpp", "host_io.cpp"):
         for knob in KNOBS:
             assert f'"RNNOISE_AMD_{knob}"' not in _src(f), (f, knob)

@@ -24,19 +24,37 @@ def model(blob_default):
     return capi.Model(blob_default)
 
 
+class _CallerMemoryState:
+    """rnnoise_get_size() + rnnoise_init() on caller memory: a self-contained state, staged to a borrowed pool row per frame"""
+
+    def __init__(self, model):
+        self._L = capi.lib()
+        self.buf = (C.c_char * self._L.rnnoise_get_size())()
+        assert self._L.rnnoise_init(C.cast(self.buf, C.c_void_p), model.h) == 0
+
+    def process_frame(self, frame):
+        x = np.ascontiguousarray(frame, np.float32).copy()
+        v = self._L.rnnoise_process_frame(C.cast(self.buf, C.c_void_p), capi._fp(x), capi._fp(x))
+        return x, v
+
+    def close(self):
+        pass
+
+
 @pytest.mark.parametrize("n_threads", [4, 32])
 def test_pooled_states_on_four_threads(model, blob_default, n_threads):
     """70 rnnoise_create()d states (more than a launch group's 64 entries), driven from 4 and from 32 threads at once: every stream gets the
     oracle's bits -- states are independent, no global lock serialises them into one another's data, and the combiner that
     gathers concurrent calls into shared launches (dropin.cpp) keeps every row at its own frame phase: state s starts s % 4
-    frames late, so the rows of one launch group sit at different ring and spectra slots"""
+    frames late, so the rows of one launch group sit at different ring and spectra slots.  Every fifth state lives in caller
+    memory (rnnoise_init): its frames borrow rows of the same pool, beside the combiner's launch groups."""
     T, n = 12, 70
     pcm = [synth.stream_pcm(s % 9, T, lead_silence=s % 3).astype(np.float32).reshape(T, 480) for s in range(n)]
     want = {}
     for s in range(n):
         if (s % 9, s % 3) not in want:
             want[(s % 9, s % 3)] = Oracle(blob_default).run(pcm[s])
-    states = [capi.DenoiseState(model) for _ in range(n)]
+    states = [_CallerMemoryState(model) if s % 5 == 4 else capi.DenoiseState(model) for s in range(n)]
     got_out = [np.zeros((T, 480), np.float32) for _ in range(n)]
     got_vad = [np.zeros(T, np.float32) for _ in range(n)]
     errs = []

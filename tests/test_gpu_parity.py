@@ -643,7 +643,9 @@ def test_throughput_kernels_at_small_sizes():
     """Small batches run the latency-oriented kernels by default (rn_hp_one_kernel up to 2048 streams, rn_nn_one_kernel up to
     512 on the vector path); with both switched off ($RNNOISE_AMD_HP_ONE_MAX / $RNNOISE_AMD_NN_ONE_MAX = 0, read once per
     process) the same cases go through rn_hp_kernel and rn_nn_vector_kernel -- the kernels of larger batches -- and must give
-    the same bits; $RNNOISE_AMD_K1_SPW=4 adds the four-stream analysis workgroups of large batches, tails included"""
+    the same bits; $RNNOISE_AMD_K1_SPW=4 adds the four-stream analysis workgroups of large batches, tails included.  Drop-in
+    frames run the row-list kernels whatever the switches: test_drop_in_single_stream_api checks that they do not notice, and
+    test_s16_entry_points has the one-stream batch"""
     import os
     import subprocess
     import sys
@@ -712,7 +714,7 @@ def x86_float_to_short(x):
     return (i & 0xFFFF).astype(np.uint16).view(np.int16)
 
 
-@pytest.mark.parametrize("n", [5, 70])
+@pytest.mark.parametrize("n", [1, 5, 70])  # (1: the forced runs' one-stream batch -- test_throughput_kernels_at_small_sizes)
 def test_s16_entry_points(model, blob_default, n):
     """rnnoise_batch_process_s16 / _device_s16: int16 PCM in and out, converted inside the first and the last kernel of the step
     as the reference's only caller converts around its call (examples/rnnoise_demo.c:56,58).  Bits = the float path's,

@@ -20,5 +20,3 @@ echo "# ... with pools of 64 rows (round 4's size: 2, 4 and 16 pools with three 
 for s in 128 256 1024; do RNNOISE_AMD_POOL_ROWS=64 timeout 200 /tmp/configs0_mt /tmp/default.blob 64 $((60000 / s)) $s 2>&1; done
 echo "# 128 threads over 256 states (a queue longer than a row list)"
 timeout 200 /tmp/configs0_mt /tmp/default.blob 128 300 256 2>&1
-echo "# a stream per state (RNNOISE_AMD_COMBINE=0: round 3)"
-for t in 4 16; do RNNOISE_AMD_COMBINE=0 timeout 200 /tmp/configs0_mt /tmp/default.blob $t 2000 2>&1; done
