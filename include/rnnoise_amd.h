@@ -130,6 +130,28 @@ RNNOISE_EXPORT int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int
 RNNOISE_EXPORT int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz);
 RNNOISE_EXPORT int rnnoise_batch_pcm_rate(const RNNoiseBatch *b);
 
+/* Several models in one batch: every stream runs with the model of its SLOT.  Slot 0 is the model the batch was created with;
+ * rnnoise_batch_add_model puts another one into the next free slot (1 .. RNNOISE_AMD_MAX_MODELS - 1) and returns that slot: -1 on a
+ * NULL batch or model, a full table, or a model that cannot be put on the batch's device.  Synchronous.  The model must outlive the
+ * batch.  Every stream stays on slot 0 until told otherwise.
+ * models[n_streams] is the slot of every stream.  rnnoise_batch_set_stream_models (host array): synchronous, like
+ * rnnoise_batch_reset_streams; -1 and no change if any entry names no slot.  rnnoise_batch_set_stream_models_device (n_streams bytes
+ * in the batch's device memory): a stream-ordered copy on hip_stream (no kernel, no host synchronisation); an entry >= the number of
+ * slots reads as slot 0.  rnnoise_batch_stream_models reads the map back (synchronous).  0 / -1.
+ * A stream's frame runs with the weights of its slot at the time of that frame.  Changing a stream's slot keeps its whole state --
+ * DenoiseState, resampler history, frame phase --: its next frame gives what the reference gives when the stream's state is carried
+ * into a state initialised with the new model.  rnnoise_batch_reset, reset_streams[_device], import_state, set_pcm_rate, set_nn_path
+ * and masked calls leave the map alone; masked calls, every PCM rate, int16 and the host-fed calls work as on a one-model batch.
+ * The network runs once per slot in every step (the launch of a slot works on its own streams only): a map that puts whole
+ * 64-stream groups on one slot costs little more than one model, an interleaved map about one network per extra slot (DESIGN.md
+ * section 4.11).  rnnoise_batch_train_features* runs no network and ignores the map.  The per-frame API of rnnoise.h has one model
+ * per state, as before. */
+#define RNNOISE_AMD_MAX_MODELS 8
+RNNOISE_EXPORT int rnnoise_batch_add_model(RNNoiseBatch *b, RNNModel *model);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_models(RNNoiseBatch *b, const unsigned char *models);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_models_device(RNNoiseBatch *b, const unsigned char *d_models, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_stream_models(RNNoiseBatch *b, unsigned char *models);
+
 /* Portable per-stream state: RN_STATE_FLOATS 32-bit words laid out as in rn_layout.h
  * (the 25,128 live bytes of the reference's DenoiseState).  Import requires
  * analysis_mem == the last 480 samples of pitch_buf, which every state produced by the

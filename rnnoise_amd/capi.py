@@ -42,7 +42,9 @@ EXPORTS = [
     "rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_masked_s16", "rnnoise_batch_process_masked",
     "rnnoise_batch_process_masked_s16", "rnnoise_batch_reset_streams", "rnnoise_batch_reset_streams_device",
     "rnnoise_batch_set_pcm_rate", "rnnoise_batch_pcm_rate",
+    "rnnoise_batch_add_model", "rnnoise_batch_set_stream_models", "rnnoise_batch_set_stream_models_device", "rnnoise_batch_stream_models",
 ]
+MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
 
 
@@ -136,6 +138,10 @@ def _load(path, debug):
         L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
         L.rnnoise_batch_set_pcm_rate.argtypes = [vp, C.c_int]
         L.rnnoise_batch_pcm_rate.argtypes = [vp]
+        L.rnnoise_batch_add_model.argtypes = [vp, vp]
+        L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
+        L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
+        L.rnnoise_batch_stream_models.argtypes = [vp, up]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
@@ -237,6 +243,7 @@ class Batch:
     def __init__(self, model: Model, n_streams: int, device: int = 0):
         self._L = lib()  # the library image that owns this handle (capi.instrumented() swaps the global one)
         self.model = model
+        self.extra_models = []  # the models of slots 1.. (add_model): held so that they outlive the batch
         self.n = n_streams
         self.h = self._L.rnnoise_batch_create(model.h, n_streams, device)
         if not self.h:
@@ -378,6 +385,37 @@ class Batch:
         """the same from an int32 device list, asynchronous on `stream` (out-of-range entries ignored)"""
         if self._L.rnnoise_batch_reset_streams_device(self.h, d_streams or None, n, stream or None):
             raise RuntimeError("rnnoise_batch_reset_streams_device failed")
+
+    def add_model(self, model: Model) -> int:
+        """puts `model` into the batch's next model slot (rnnoise_batch_add_model) and returns the slot (1 .. MAX_MODELS - 1); every
+        stream stays where it is.  The batch keeps a reference: the model outlives it."""
+        k = self._L.rnnoise_batch_add_model(self.h, model.h if model is not None else None)
+        if k < 0:
+            raise RuntimeError("rnnoise_batch_add_model failed (table full, or the model cannot go on this device)")
+        self.extra_models.append(model)
+        return k
+
+    def set_stream_models(self, models):
+        """the model slot of every stream: (N,) integers (synchronous; ValueError if an entry names no slot -- nothing changes then)"""
+        m = np.asarray(models).reshape(-1)
+        assert m.size == self.n
+        if m.min(initial=0) < 0 or m.max(initial=0) > 255:
+            raise ValueError("model slot out of range")
+        m = np.ascontiguousarray(m, np.uint8)
+        if self._L.rnnoise_batch_set_stream_models(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise ValueError("rnnoise_batch_set_stream_models failed (an entry names no slot)")
+
+    def set_stream_models_device(self, d_models: int, stream: int = 0):
+        """the same from N bytes of device memory, a copy ordered on `stream` (entries naming no slot read as slot 0)"""
+        if self._L.rnnoise_batch_set_stream_models_device(self.h, d_models or None, stream or None):
+            raise RuntimeError("rnnoise_batch_set_stream_models_device failed")
+
+    def stream_models(self) -> np.ndarray:
+        """the model slot of every stream, (N,) uint8 (synchronous)"""
+        m = np.empty(self.n, np.uint8)
+        if self._L.rnnoise_batch_stream_models(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise RuntimeError("rnnoise_batch_stream_models failed")
+        return m
 
     def export_state(self, stream: int) -> np.ndarray:
         s = np.empty(STATE_FLOATS, np.float32)

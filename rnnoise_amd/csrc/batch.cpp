@@ -90,6 +90,7 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
   if (v.debug) v.debug += RN_DBG_FLOATS * f;
   if (v.phase) v.phase += f;
   if (v.active) v.active += f;  // (rows of the mask keep the stride n_stride)
+  if (v.model_of) v.model_of += f;
   if (v.rs_hist) {
     v.rs_hist += RN_RS_HIST * f;
     v.rs_up += RN_FRAME_SIZE * f;
@@ -165,6 +166,7 @@ extern "C" RNNoiseBatch *rnnoise_batch_create(RNNModel *model, int n_streams, in
   }
   RNNoiseBatch *b = new RNNoiseBatch();
   b->model = model;
+  b->models[0] = model;
   b->device = device;
   b->n = n_streams;
   b->nn_path = rn_default_nn_path(rn_knobs(), n_streams);
@@ -213,6 +215,7 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->state_stage) hipFree(b->state_stage);
   if (b->arena) hipFree(b->arena);
   if (b->rs_buf) hipFree(b->rs_buf);
+  if (b->model_map) hipFree(b->model_map);
   if (b->debug_buf) hipFree(b->debug_buf);
   if (b->side) hipStreamDestroy(b->side);
   if (b->side_hp) {
@@ -264,6 +267,61 @@ extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
 }
 
 extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
+
+// ---- per-stream models (include/rnnoise_amd.h) ----
+// The network of every step is launched once per slot (batch_process_device_impl); the launch of slot k owns the streams the map puts
+// on k (rn_dev.h: rn_owns).  The map exists from the first add_model on; before that every stream is on slot 0 and nothing is read.
+extern "C" int rnnoise_batch_add_model(RNNoiseBatch *b, RNNModel *model) {
+  if (!b || !model || b->n_models >= RNNOISE_AMD_MAX_MODELS) return -1;
+  ON_DEVICE(b->device);
+  RnModelDev md;
+  if (model_on_device(model, b->device, md)) return -1;
+  HIP_OK(hipDeviceSynchronize());  // (synchronous: a call in flight keeps the slots it was launched with)
+  if (!b->model_map) {
+    HIP_OK(hipMalloc((void **)&b->model_map, (size_t)b->n));
+    HIP_OK(hipMemset(b->model_map, 0, (size_t)b->n));
+    HIP_OK(hipDeviceSynchronize());
+  }
+  const int k = b->n_models++;
+  b->models[k] = model;
+  b->slot_m[k] = md;
+  b->g.model_of = b->model_map;
+  b->g.n_models = b->n_models;
+  return k;
+}
+
+extern "C" int rnnoise_batch_set_stream_models(RNNoiseBatch *b, const unsigned char *models) {
+  if (!b || !models) return -1;
+  for (int s = 0; s < b->n; s++)
+    if (models[s] >= b->n_models) return -1;
+  if (!b->model_map) return 0;  // (one slot: every entry is 0, which is what the batch runs)
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset_streams)
+  HIP_OK(hipMemcpy(b->model_map, models, (size_t)b->n, hipMemcpyHostToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" int rnnoise_batch_set_stream_models_device(RNNoiseBatch *b, const unsigned char *d_models, void *hip_stream) {
+  if (!b || !d_models) return -1;
+  if (!b->model_map) return 0;  // (one slot: any entry reads as slot 0)
+  ON_DEVICE(b->device);
+  // a copy, not a kernel: ordered on the caller's stream between its calls; entries naming no slot are read as slot 0 by the kernels
+  HIP_OK(hipMemcpyAsync(b->model_map, d_models, (size_t)b->n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
+  return 0;
+}
+
+extern "C" int rnnoise_batch_stream_models(RNNoiseBatch *b, unsigned char *models) {
+  if (!b || !models) return -1;
+  if (!b->model_map) {
+    memset(models, 0, (size_t)b->n);
+    return 0;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(models, b->model_map, (size_t)b->n, hipMemcpyDeviceToHost));
+  return 0;
+}
 
 extern "C" int rnnoise_batch_set_schedule(RNNoiseBatch *b, int schedule) {
   if (!b || (schedule != 0 && schedule != 1 && schedule != 9)) return -1;
@@ -409,7 +467,12 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
       if (side_k1) HIP_OK(hipStreamWaitEvent(st, b->cur_k1[f & 7], 0));
     }
     if (hk && hk->before_nn(f, st)) return -1;
-    {
+    // the network once per model slot (one slot without a map: exactly the launches of a one-model batch).  Slot k's launch owns the
+    // streams the map puts on k (rn_dev.h: rn_owns).  Layer-wise, a slot's whole network runs before the next slot's front: act_q[0]
+    // and nn_act are the tile's scratch, which the next front overwrites for every column.
+    for (int k = 0; k < b->n_models; k++) {
+      g.model_sel = k;
+      const RnModelDev *mk = k ? &b->slot_m[k] : &b->m;
       if (plan.nn == RN_NN_LAYERS) {
         if (!b->img_valid) HIP_OK(rn_launch_nn_requant(&g, st));
         b->img_valid = true;
@@ -421,13 +484,13 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
           ev[i][0] = tl[i]->start();
           ev[i][1] = tl[i]->stop();
         }
-        HIP_OK(rn_launch_nn_layers(&g, &b->m, &b->tb, plan.gru, b->lds_gru, st, ev));
+        HIP_OK(rn_launch_nn_layers(&g, mk, &b->tb, plan.gru, b->lds_gru, st, ev));
       } else {
         TimedLaunch t(b, 1);
         b->img_valid = false;
-        if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, &b->m, &b->tb, b->lds_one, st, t.start(), t.stop()));
-        else if (plan.nn == RN_NN_VECTOR) HIP_OK(rn_launch_nn_vector(&g, &b->m, &b->tb, st, t.start(), t.stop()));
-        else HIP_OK(rn_launch_nn_mfma(&g, &b->m, &b->tb, plan.nn, st, t.start(), t.stop()));
+        if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, mk, &b->tb, b->lds_one, st, t.start(), t.stop()));
+        else if (plan.nn == RN_NN_VECTOR) HIP_OK(rn_launch_nn_vector(&g, mk, &b->tb, st, t.start(), t.stop()));
+        else HIP_OK(rn_launch_nn_mfma(&g, mk, &b->tb, plan.nn, st, t.start(), t.stop()));
       }
     }
     {

@@ -211,6 +211,17 @@ __device__ __forceinline__ void gru_body(const RnGroupDev &g, const RnModelDev &
     const int s = (tile0 + t) * TS + n;
     sil[t] = g.silence[(unsigned)(s < N ? s : N - 1)];
   }
+  if (g.model_of) {  // model slots (rn_dev.h: RnGroupDev::model_of): a stream of another slot is, to this launch, a silent one
+    bool any = false;
+#pragma unroll
+    for (int t = 0; t < GM; t++) {
+      const int s = (tile0 + t) * TS + n;
+      const bool own = s < N && rn_owns(g, s);
+      sil[t] |= !own;
+      any |= own;
+    }
+    if (!__ballot(any)) return;  // (no owned row in the workgroup's 64 streams: every wave sees the same lanes, the exit is uniform)
+  }
   // Prologue: the two images of the workgroup's GM tiles and the rcpps table go straight from HBM to LDS (1 KB per wave
   // instruction, no staging registers, no ds_write pass: the images are stored in exactly the order LDS wants), then
   // this wave's f32 rows for its first unit tile.

@@ -179,6 +179,7 @@ rn_nn_vector_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb) {
   __shared__ NnLds L;
   const int s = blockIdx.x, t = threadIdx.x;
   const uint16_t *lut = tb.rcp16;
+  if (!rn_owns(g, s)) return;  // (a stream of another model slot: that slot's launch writes its outputs)
   if (g.silence[s]) {  // src/denoise.c:474: the network and its state are untouched on silent frames
     if (t < RN_NB_BANDS) g.gains[(size_t)s * RN_NB_BANDS + t] = 0;
     if (t == 0) g.vad[s] = 0;
@@ -315,6 +316,7 @@ rn_nn_one_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb, RnRows rows) {
   // consecutive rows of one 8-row group (int8_rows shares their activation reads)
   const int half = t >= RN_GRU && t < ONE_ROW_THREADS, u = t - (t >= RN_GRU ? RN_GRU : 0);
   const uint16_t *lut = O.lut;  // the rcpps table in LDS: three dependent lookups per unit and layer must not be L2 trips
+  if (!rn_owns(g, s)) return;  // (a stream of another model slot: that slot's launch writes its outputs)
   if (g.silence[s]) {  // src/denoise.c:474
     if (t < RN_NB_BANDS) g.gains[(size_t)s * RN_NB_BANDS + t] = 0;
     if (t == 0) *vad_dst = 0;

@@ -135,6 +135,15 @@ extern "C" __global__ void __launch_bounds__(GTHREADS) rn_nn_dense_kernel(RnGrou
   constexpr int NW4 = RN_CAT / 16;
   static_assert((XP + WP) % GW == 0 && XP % GW == 0 && GW == 2 * GM && RN_GRU % DKC == 0 && DKC == 64, "dense staging");
 
+  if (g.model_of) {  // model slots (rn_dev.h: RnGroupDev::model_of): a workgroup without a stream of this launch's slot leaves at once
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < GM; q++) {
+      const int s = (tile0 + q) * TS + n;
+      any |= s < N && rn_owns(g, s);
+    }
+    if (!__ballot(any)) return;
+  }
   auto stage_fetch = [&](int c) {
     const int seg = (c * DKC) / RN_GRU, k0 = c * DKC - seg * RN_GRU, bi = c % DNB;
     const float *src = seg == 0 ? g.nn_act : g.gru_state + (size_t)(seg - 1) * g.n_stride * RN_GRU;
@@ -171,17 +180,18 @@ extern "C" __global__ void __launch_bounds__(GTHREADS) rn_nn_dense_kernel(RnGrou
   // (five activations per lane: the rcpps table straight from memory)
   {
     const int s = (tile0 + t) * TS + n, sc = s < N ? s : N - 1;
-    const bool live = s < N && !g.silence[sc];
+    const bool own = s < N && rn_owns(g, s);  // (another slot's stream: its own slot's launch writes its gains and vad)
+    const bool live = own && !g.silence[sc];
     const int row0 = 16 * rt + 4 * gq;
     const v4f bs = *reinterpret_cast<const v4f *>(m.dense_out.bias + row0);
     v4f o;
 #pragma unroll
     for (int r = 0; r < 4; r++) o[r] = live ? sigmoid_x86(dacc[r] + bs[r], tb.rcp16) : 0.f;
-    if (s < N) *reinterpret_cast<v4f *>(g.gains + (size_t)sc * RN_NB_BANDS + row0) = o;
+    if (own) *reinterpret_cast<v4f *>(g.gains + (size_t)sc * RN_NB_BANDS + row0) = o;
   }
   if (vad_wave) {
     const int vs = tile0 * TS + lane;
-    if (vs < N) g.vad[vs] = g.silence[vs] ? 0.f : sigmoid_x86(vacc + m.vad_dense.bias[0], tb.rcp16);
+    if (vs < N && rn_owns(g, vs)) g.vad[vs] = g.silence[vs] ? 0.f : sigmoid_x86(vacc + m.vad_dense.bias[0], tb.rcp16);
   }
 }
 

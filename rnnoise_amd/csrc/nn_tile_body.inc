@@ -16,7 +16,16 @@
   const int N = g.n_streams, s0 = blockIdx.x * TS;
   const int sn = (s0 + n < N) ? s0 + n : N - 1;              // this lane's stream (clamped for loads)
   const int sil_n = g.silence[sn];                           // (sn is clamped: loaded unconditionally, not behind the range test's branch)
-  const bool live = (s0 + n < N) && !sil_n;                  // silent streams keep state (src/denoise.c:474)
+  // model slots (rn_dev.h: RnGroupDev::model_of): bit q of ownm = this launch owns stream s0 + q.  Rows of another slot get no store
+  // at all -- their slot's launch writes them -- and a tile without an owned row is left before any LDS or barrier (uniform: every
+  // wave forms the same mask).
+  uint32_t ownm = 0xffffu;
+  if (g.model_of) {
+    ownm = (uint32_t)__ballot(lane < TS && s0 + lane < N && rn_owns(g, s0 + lane));
+    if (!ownm) return;
+  }
+#define OWN(q) ((ownm >> (q)) & 1u)
+  const bool live = (s0 + n < N) && !sil_n && OWN(n);        // silent streams keep state (src/denoise.c:474)
   const uint16_t *lut = L.lut;
 #if RN_INSTRUMENT
   float *dbg = (g.debug && tid == 0) ? g.debug + (size_t)s0 * RN_DBG_FLOATS + RN_DBG_CLK2 : nullptr;
@@ -101,11 +110,11 @@
 #pragma unroll
   for (int j = 0; j < NE2; j++) {
     const int e = tid + j * NTHREADS, q = e / 130, k = e - q * 130;
-    if (e < TS * 130 && s0 + q < N && !sil2[j]) g.conv1_state[(size_t)(s0 + q) * 130 + k] = L.tmp1[q][65 + k];
+    if (e < TS * 130 && s0 + q < N && !sil2[j] && OWN(q)) g.conv1_state[(size_t)(s0 + q) * 130 + k] = L.tmp1[q][65 + k];
   }
 #pragma unroll
   for (int c = 0; c < HC; c++)
-    if (hk_[c] >= 128 && s0 + hq_[c] < N && !g.silence[s0 + hq_[c]])
+    if (hk_[c] >= 128 && s0 + hq_[c] < N && !g.silence[s0 + hq_[c]] && OWN(hq_[c]))
       *reinterpret_cast<v4f *>(g.conv2_state + (size_t)(s0 + hq_[c]) * 256 + hk_[c] - 128) = hist[c];
 
   CLK_TAP(0);  // loads, history quantisation, state shifts
@@ -283,13 +292,14 @@
       v4f o;
 #pragma unroll
       for (int r = 0; r < 4; r++) o[r] = live ? sigmoid_x86(dacc[r] + bs[r], lut) : 0.f;
-      if (s0 + n < N) *reinterpret_cast<v4f *>(g.gains + (size_t)sn * RN_NB_BANDS + row0) = o;
+      if (s0 + n < N && OWN(n)) *reinterpret_cast<v4f *>(g.gains + (size_t)sn * RN_NB_BANDS + row0) = o;
     } else if (wave == 2 && lane < TS) {
       const int q = s0 + lane, sq = q < N ? q : N - 1;
       const bool lv = q < N && !g.silence[sq];
-      if (q < N) g.vad[sq] = lv ? sigmoid_x86(vacc + m.vad_dense.bias[0], lut) : 0.f;
+      if (q < N && OWN(lane)) g.vad[sq] = lv ? sigmoid_x86(vacc + m.vad_dense.bias[0], lut) : 0.f;
     }
   }
   CLK_TAP(6);  // dense_out / vad (wave 0's view)
 #endif  // RN_NN_MODE == 0 (dense phase)
 #undef CLK_TAP
+#undef OWN

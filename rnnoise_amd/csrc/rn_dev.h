@@ -160,6 +160,11 @@ struct RnGroupDev {
   float *rs_up, *rs_dn;        // [N][480] each: the frame at 48 kHz as K0 formed it from the low-rate row / as K3's body formed it
   void *rs_out;                // K3 only: the caller's low-rate output (float or int16)
   int rs_L;
+  // Per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model).  Null model_of: every row belongs to the launch (a batch with
+  // one model).  Set, the network launch of slot model_sel owns row s when (model_of[s] < n_models ? model_of[s] : 0) == model_sel
+  // (rn_owns): only owned rows get stores -- state, state images, gains, vad -- and a workgroup with no owned row returns at once.
+  const uint8_t *model_of;     // [N] slot of every stream, or null
+  int model_sel, n_models;
 };
 #define RN_RS_TAPS 48                           // taps per phase of the up filter; the down filter has RN_RS_TAPS * L
 #define RN_RS_UP_HIST (RN_RS_TAPS - 1)          // 47 low-rate samples
@@ -274,6 +279,12 @@ __device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, bool 
     p += g.call_frame;
   }
   return p;
+}
+// Whether the network launch of g.model_sel owns stream s (rn_dev.h: RnGroupDev::model_of); an entry naming no slot reads as slot 0
+__device__ __forceinline__ bool rn_owns(const RnGroupDev &g, int s) {
+  if (!g.model_of) return true;
+  const int k = *(__attribute__((address_space(1))) const uint8_t *)(g.model_of + s);
+  return (k < g.n_models ? k : 0) == g.model_sel;
 }
 // Which stream a workgroup-per-stream kernel works on, and at which frame phase -- resolved once at its top (rn_stream_at):
 // from its row list entry (listed), from the stream's own phase (g.phase set), or from the launch's arguments (lock-step).

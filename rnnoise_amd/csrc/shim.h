@@ -178,6 +178,13 @@ struct RNNoiseBatch {
   // RnGroupDev::rs_hist), allocated the first time the rate leaves 48 kHz; g.rs_hist / g.rs_L are set only while it is away
   int pcm_rate = 48000;
   float *rs_buf = nullptr;
+  // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
+  // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of) -- allocated by the first
+  // add_model, like rs_buf by the first rate change; g.model_of / g.n_models are set from then on
+  int n_models = 1;
+  RNNModel *models[RNNOISE_AMD_MAX_MODELS] = {};
+  RnModelDev slot_m[RNNOISE_AMD_MAX_MODELS] = {};
+  uint8_t *model_map = nullptr;
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
   hipStream_t side = nullptr, side_hp = nullptr;

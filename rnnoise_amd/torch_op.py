@@ -66,9 +66,12 @@ def register_torch_op():
 class RNNoiseOp:
     """N concurrent streams; call with a (T, N, 480 // L) float32 CUDA tensor of int16-scaled PCM at `rate` = 48000 / L (48000,
     24000, 16000 or 8000: include/rnnoise_amd.h, rnnoise_batch_set_pcm_rate).  The same object is reachable as the registered op:
-    torch.ops.rnnoise_amd.process(pcm, op.state, op.handle)."""
+    torch.ops.rnnoise_amd.process(pcm, op.state, op.handle).
+    extra_models: more model blobs, put into model slots 1, 2, ... of the batch (rnnoise_batch_add_model); every stream starts on
+    slot 0 (model_blob) and set_stream_models moves streams between slots."""
 
-    def __init__(self, model_blob: bytes, n_streams: int, device: int = 0, nn_path: str = "mfma", rate: int = 48000):
+    def __init__(self, model_blob: bytes, n_streams: int, device: int = 0, nn_path: str = "mfma", rate: int = 48000,
+                 extra_models=()):
         import torch
         self.torch = torch
         self.device = torch.device("cuda", device)
@@ -78,6 +81,8 @@ class RNNoiseOp:
             self.batch.set_nn_path(1)
         if rate != 48000:
             self.batch.set_pcm_rate(rate)
+        for blob in extra_models:
+            self.batch.add_model(capi.Model(blob))
         self.n = n_streams
         register_torch_op()
         self.handle = id(self)
@@ -87,8 +92,11 @@ class RNNoiseOp:
     def close(self):
         _OPS.pop(getattr(self, "handle", None), None)
         if getattr(self, "batch", None) is not None:
+            extra = self.batch.extra_models
             self.batch.close()
             self.model.close()
+            for m in extra:
+                m.close()
             self.batch = None
 
     def __del__(self):
@@ -112,6 +120,15 @@ class RNNoiseOp:
         idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
         # (freeing idx afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.reset_streams_device(idx.data_ptr(), int(idx.numel()), torch.cuda.current_stream(self.device).cuda_stream)
+
+    def set_stream_models(self, slots):
+        """the model slot of every stream: an (N,) uint8 CUDA tensor, copied on torch's current stream without a host synchronisation
+        (rnnoise_batch_set_stream_models_device: entries naming no slot read as slot 0).  The frames of later calls run with it."""
+        torch = self.torch
+        assert slots.is_cuda and slots.dtype == torch.uint8 and slots.numel() == self.n
+        slots = slots.to(self.device).contiguous()
+        # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        self.batch.set_stream_models_device(slots.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
 
     def _run(self, pcm, active=None):
         torch = self.torch
