@@ -123,6 +123,41 @@ def test_three_hundred_states_from_ninety_six_threads(model, blob_default):
         st.close()
 
 
+def test_mixed_streams_through_row_lists_from_24_threads(model, blob_default):
+    """the first 97 streams of tests/stream_mix.py's block -- pitch over the whole range, silence that flips frame by frame, extreme
+    and edge signals, zeros -- through 97 rnnoise_create()d states from 24 threads at staggered frame phases: the row-list kernels
+    (dropin.cpp) take launch groups whose rows differ in every data-dependent length, and every stream gets the oracle's bits"""
+    import stream_mix
+    n, n_threads = 97, 24
+    pcm, _ = stream_mix.block()
+    pcm = pcm[:, :n]
+    T = pcm.shape[0]
+    want = stream_mix.oracle_block(blob_default, pcm, collect_state=False)
+    states = [capi.DenoiseState(model) for _ in range(n)]
+    got_out = np.zeros((T, n, 480), np.float32)
+    got_vad = np.zeros((T, n), np.float32)
+    errs = []
+
+    def work(tid):
+        try:
+            for t in range(T + 4):
+                for s in range(tid, n, n_threads):
+                    f = t - s % 5
+                    if 0 <= f < T:
+                        got_out[f, s], got_vad[f, s] = states[s].process_frame(pcm[f, s])
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+
+    th = [threading.Thread(target=work, args=(i,)) for i in range(n_threads)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    assert not errs, errs
+    assert_bits_equal(got_out, want["out"], "pcm")
+    assert_bits_equal(got_vad, want["vad"], "vad")
+    for st in states:
+        st.close()
+
+
 def test_batch_and_pooled_state_on_the_last_device(blob_default):
     """a node with several GPUs: a batch created on the LAST device, and a process whose rnnoise_create() states are sent there
     ($RNNOISE_AMD_DEVICE), give the oracle's bits -- device 0 is not special.  (One GPU: skipped; the 8-GPU run is the driver's.)"""

@@ -2,8 +2,9 @@
 build of the analysis kernel and 4096 MFMA tiles) and configs[3] (sparser blob, 32,768 streams).  An oracle run of
 65,536 streams would take hours, so the checks are the size-independent ones: tiled replicas of a 32-stream block must
 stay bit-identical to each other (no cross-talk, no dependence on the tile / CU / XCD a stream lands on), and the block
-itself is checked bit for bit against the oracle, including a stream that starts silent inside a live MFMA tile.
-Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
+itself is checked bit for bit against the oracle, including a stream that starts silent inside a live MFMA tile.  The mixed
+block of tests/stream_mix.py (389 streams of every kind, compared stream by stream) runs at batch sizes that reach every kernel
+form, and with NaN / Inf in copies of one of its streams.  Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
 import os
 import subprocess
 import sys
@@ -13,6 +14,7 @@ import pytest
 
 from conftest import ROOT, assert_bits_equal, load_blob
 from oracle.binding import Oracle
+import stream_mix
 from rnnoise_amd import capi, synth
 from test_gpu_parity import oracle_run
 
@@ -77,47 +79,80 @@ def test_sparser_model_32768(blob_little, rcp_profile):
     _tiled_check(blob_little, 32768, (5, 1, 8), silent_stream=9)
 
 
-def _ragged_check(blob, N, calls, silent_stream):
-    """_tiled_check for a batch size that is NOT a multiple of anything: N = 32 q + r streams = q replicas of a 32-stream block and
-    the first r streams of one more.  Every kernel of the default schedule then has a partial unit at the end of its grid -- the
-    lane = stream high-pass a partial wave, the four-stream analysis workgroups a partial workgroup, the front kernel a partial
-    16-stream tile, the four-wave GRU layer kernel and the dense kernel a partial 64-stream group -- whose surplus lanes work on
-    clamped addresses and must store nothing.  Whole replicas are compared among themselves, the ragged tail with the head of
-    block 0, block 0 with the oracle; states are exported from the tail."""
-    import torch
-    T, q, r = sum(calls), N // 32, N % 32
-    assert r and N % 64 and N % 16 and N % 4
+def _synth_block(T, silent_stream):
+    """the 32-stream block of the synth recipe, with a stream silent for its first 3 frames and one silent across the last call boundary"""
     base = synth.batch_pcm(range(32), T)
     base[:3, silent_stream] = 0
     base[T - 5:T - 3, (silent_stream + 3) % 32] = 0
+    return base
+
+
+def _ragged_check(blob, N, calls, block, want=None, silent_stream=None, nn_path=1, state_streams=None, every_call=False, poisoned=(), ragged=True):
+    """_tiled_check for a batch size that is NOT a multiple of anything: N = B q + r streams = q copies of a B-stream `block` and the
+    first r streams of one more (stream i takes block stream i mod B).  Every kernel of the default schedule then has a partial unit at
+    the end of its grid -- the lane = stream high-pass a partial wave, the four-stream analysis workgroups a partial workgroup, the front
+    kernel a partial 16-stream tile, the four-wave GRU layer kernel and the dense kernel a partial 64-stream group -- whose surplus lanes
+    work on clamped addresses and must store nothing.  Whole copies are compared among themselves, the ragged tail with the head of
+    copy 0, and every stream's pcm / gains / vad with the oracle's run of its block stream (`want`), on the device; states are exported
+    from `state_streams` (default: the tail and the middle).  every_call: after every call the features, silence flag and pitch of
+    the call's last frame (debug_last) of all N streams against the oracle's frame.  poisoned: (frame, stream, sample, value) writes
+    into the input -- those streams' own output is not checked, nor the copy comparisons.  ragged: N is a multiple of neither B nor
+    4, 16, 64."""
+    import torch
+    T, B = sum(calls), block.shape[1]
+    q, r = N // B, N % B
+    assert not ragged or (r and N % 64 and N % 16 and N % 4)
+    if want is None:
+        want = oracle_run(blob, block)
+    if silent_stream is not None:
+        assert want["silence"][:, silent_stream].any() and not want["silence"][:, 0].any()
     dev = torch.device("cuda", 0)
-    d_in = torch.from_numpy(base).to(dev).repeat(1, q + 1, 1)[:, :N].contiguous()
+    idx = torch.arange(N, device=dev) % B
+    d_in = torch.from_numpy(np.ascontiguousarray(block, np.float32)).to(dev)[:, idx].contiguous()
+    bad = sorted({s for _, s, _, _ in poisoned})
+    for t, s, k, v in poisoned:
+        d_in[t, s, k] = float(v)
+    live = np.ones(N, bool)
+    live[bad] = False
     d_out = torch.empty_like(d_in)
     d_vad = torch.empty((T, N), device=dev)
     d_gains = torch.empty((T, N, 32), device=dev)
     m = capi.Model(blob)
     b = capi.Batch(m, N)
-    assert b.set_nn_path(1) == 1
+    if nn_path is not None:
+        old = b.set_nn_path(nn_path)
+        assert old in (0, 1) and (N <= 512 or old == 1)   # the MFMA path is the default above 512 streams
     st = torch.cuda.current_stream().cuda_stream
     f = 0
     for n in calls:
         b.process_device(d_out[f].data_ptr(), d_in[f].data_ptr(), d_vad[f].data_ptr(), d_gains[f].data_ptr(), n, st)
         f += n
+        if every_call:
+            torch.cuda.synchronize()
+            feats, sil, pitch = b.debug_last()
+            at = idx.cpu().numpy()
+            for name, got in (("features", feats), ("silence", sil), ("pitch", pitch)):
+                assert_bits_equal(got[live], want[name][f - 1][at][live], f"{name} of frame {f - 1} (the last of a {n}-frame call)")
     torch.cuda.synchronize()
-    for name, t, w in (("pcm", d_out, 480), ("gains", d_gains, 32), ("vad", d_vad, 1)):
+    d_live = torch.from_numpy(live).to(dev)
+    for name, t, w in (("out", d_out, 480), ("gains", d_gains, 32), ("vad", d_vad, 1)):
         t = t.reshape(T, N, w).view(torch.int32)
-        whole = t[:, :32 * q].reshape(T, q, 32 * w)
-        assert bool((whole == whole[:, :1]).all().item()), f"replicated streams diverged ({name})"
-        assert bool((t[:, 32 * q:] == t[:, :r]).all().item()), f"the ragged tail differs from the head of block 0 ({name})"
-    out, gains, vad = d_out[:, :32].cpu().numpy(), d_gains[:, :32].cpu().numpy(), d_vad[:, :32].cpu().numpy()
+        if not poisoned:
+            whole = t[:, :B * q].reshape(T, q, B * w)
+            assert bool((whole == whole[:, :1]).all().item()), f"replicated streams diverged ({name})"
+            assert bool((t[:, B * q:] == t[:, :r]).all().item()), f"the ragged tail differs from the head of block 0 ({name})"
+        ref = torch.from_numpy(np.ascontiguousarray(want[name], np.float32)).to(dev).reshape(T, B, w).view(torch.int32)[:, idx]
+        ne = (t != ref).any(-1) & d_live
+        if bool(ne.any().item()):
+            where = ne.nonzero()[:5].tolist()
+            raise AssertionError(f"{name}: {int(ne.sum().item())} of {T * int(d_live.sum().item())} stream-frames differ from the oracle, "
+                                 f"first (frame, stream) {where}, block streams {[s_ % B for _, s_ in where]}")
+        del ref, ne
     del d_in, d_out, d_gains, d_vad
-    want = oracle_run(blob, base)
-    assert want["silence"][:, silent_stream].any() and not want["silence"][:, 0].any()
-    assert_bits_equal(out, want["out"], "pcm")
-    assert_bits_equal(gains, want["gains"], "gains")
-    assert_bits_equal(vad, want["vad"], "vad")
-    for s_ in (N - 1, N - r, N - r - 1, (N // 2 // 32) * 32 + silent_stream):   # the last stream, the tail's first, the last whole block's last
-        assert_bits_equal(b.export_state(s_), want["state"][s_ % 32], f"state of stream {s_}")
+    if state_streams is None:
+        state_streams = (N - 1, N - r, N - r - 1, (N // 2 // B) * B + silent_stream)   # the last, the tail's first, the last whole copy's last
+    for s_ in state_streams:
+        assert_bits_equal(b.export_state(s_), want["state"][s_ % B], f"state of stream {s_} (block stream {s_ % B})")
     b.close()
     m.close()
 
@@ -129,7 +164,7 @@ def test_ragged_40037_streams(blob_default, blob_little, which):
     > 16,384 streams) and the lane-per-stream high-pass inside pipelined calls -- on a batch with a partial tile (40,037 = 16 x
     2,502 + 5), a partial group (64 x 625 + 37), a partial analysis workgroup and a partial high-pass wave; default and sparser blob,
     default schedule, 14 frames as calls of 5 + 1 + 8.  Arithmetic under test: src/nnet.c:65-94, src/denoise.c:409-419."""
-    _ragged_check(blob_default if which == "default" else blob_little, 40037, (5, 1, 8), silent_stream=3)
+    _ragged_check(blob_default if which == "default" else blob_little, 40037, (5, 1, 8), _synth_block(14, 3), silent_stream=3)
 
 
 @pytest.mark.rcp("host")
@@ -138,7 +173,76 @@ def test_ragged_10277_streams_just_above_the_network_switch(blob_default):
     ragged batch just above the switch -- 10,277 = 16 x 642 + 5 = 64 x 160 + 37, the eight-wave layer kernel (fewer 64-stream groups
     than CUs) with a partial tile and a partial group -- and, below, the largest batches of the tile kernel on both sides of 8,192
     streams (two tiles per CU, then three).  Arithmetic under test: src/nnet.c:65-94, src/rnn.c:44-60."""
-    _ragged_check(blob_default, 10277, (4, 1, 3), silent_stream=3)
+    _ragged_check(blob_default, 10277, (4, 1, 3), _synth_block(8, 3), silent_stream=3)
+
+
+_MIX = {}
+
+
+def _mix(blob, profile):
+    """tests/stream_mix.py's block and the oracle's run of it, once per module and rcpps profile"""
+    if profile not in _MIX:
+        pcm, _ = stream_mix.block()
+        _MIX[profile] = pcm, stream_mix.oracle_block(blob, pcm)
+    return _MIX[profile]
+
+
+def _need_256_cus():
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if cus != 256:
+        pytest.skip(f"{cus} CUs: the forms stream_mix.CASES reach are chosen for 256")
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path,calls", stream_mix.CASES, ids=[f"n{n}-path{p}" for n, p, _ in stream_mix.CASES])
+def test_stream_mix_at_every_form(blob_default, rcp_profile, n, path, calls):
+    """The mixed block of tests/stream_mix.py -- pitch from 60 to 767, silence that flips frame by frame and at call boundaries,
+    extreme and edge signals, a stream of zeros, a permutation that puts different kinds of stream side by side -- copied over n
+    streams and fed through the batch's default schedule in stream_mix.CALLS: with the network paths of CASES every form of every
+    stage runs (tests/test_stream_mix_cpu.py: the forms on 256 CUs), among them the rows of one wave of rn_analysis_kernel's narrow
+    phases, of one tile and of one layer-kernel group at different pitch, remove_doubling lengths and silence.  Every stream's pcm,
+    gains and vad, and after every call the last frame's features, silence and pitch of every stream, against the oracle; then the
+    state of every block position, each from a different copy."""
+    _need_256_cus()
+    pcm, want = _mix(blob_default, rcp_profile)
+    B = pcm.shape[1]
+    # block position p from copy (7 p) mod (the copies holding p)
+    states = [p + (7 * p) % ((n - p + B - 1) // B) * B for p in range(min(B, n))]
+    _ragged_check(blob_default, n, calls, pcm[:sum(calls)], want=want, nn_path=path, state_streams=states, every_call=True,
+                  ragged=False)
+
+
+def _poison_places(n, B):
+    """a block stream p and three of its copies: the first lane of an analysis quad, the last lane of a 64-stream wave (high-pass lanes,
+    GRU group) and the middle of a 16-stream tile"""
+    for p in range(B):
+        copies = [p + c * B for c in range((n - p + B - 1) // B)]
+        quad = [s for s in copies if s % 4 == 0]
+        wave = [s for s in copies if s % 64 == 63 and s + 1 <= n - n % 64]
+        tile = [s for s in copies if s % 16 in (7, 8) and s not in wave]
+        if quad and wave and tile and len({quad[0], wave[0], tile[0]}) == 3:
+            return p, (quad[0], wave[0], tile[0])
+    raise AssertionError(f"no block stream has copies at all three places in {n} streams")
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n", [3001, 40037])
+def test_poisoned_stream_in_every_at_size_unit(blob_default, rcp_profile, n):
+    """NaN, +Inf and -Inf samples in three copies of one stream of the mixed block, placed at the first lane of a four-stream analysis
+    workgroup, the last lane of a lane-per-stream high-pass wave and of a 64-stream GRU group, and the middle of a tile (rn_hp_kernel,
+    rn_analysis_kernel, the tile kernels at 3,001 streams; the layer-wise network with rn_nn_gru_kernel at 40,037): every other stream
+    still gets the oracle's bits"""
+    _need_256_cus()
+    pcm, want = _mix(blob_default, rcp_profile)
+    B, calls = pcm.shape[1], stream_mix.CALLS
+    p, places = _poison_places(n, B)
+    poisoned = []
+    for s in places:
+        poisoned += [(2, s, 100, np.nan), (9, s, 7, np.inf), (16, s, 300, -np.inf), (23, s, 479, np.nan)]
+    others = [s for s in range(n - 1, n - 1 - 3 * B, -7) if s not in places] + [places[0] + 1, places[1] - 1, places[2] + 1]
+    _ragged_check(blob_default, n, calls, pcm, want=want, nn_path=None, state_streams=others, every_call=True,
+                  poisoned=poisoned, ragged=False)
 
 
 @pytest.mark.rcp("host")

@@ -334,25 +334,33 @@ def test_reset_restores_initial_state(model):
     assert not a[0][0].any()  # first output frame is all zeros
 
 
-@pytest.mark.parametrize("path", [0, 2])
-def test_extreme_but_finite_inputs(model, blob_default, path):
-    """the corners of the input domain the reference's own callers can reach: full-scale square waves, samples far outside
-    the int16 range, a large DC offset, isolated impulses, amplitudes down in the denormal range (nothing flushes to zero:
-    the x86 build runs without FTZ/DAZ), exact digital silence between bursts"""
-    T = 30
+def extreme_signals(T):
+    """the corners of the input domain the reference's own callers can reach, T frames each (float64, not rounded to int16):
+    full-scale square waves, samples far outside the int16 range, a large DC offset, isolated impulses, amplitudes down in the
+    denormal range (nothing flushes to zero: the x86 build runs without FTZ/DAZ), exact digital silence between bursts, and
+    white noise below and on the silence threshold (E < 0.04, src/denoise.c:389: sigma 1e-3 is silent in every frame, sigma
+    0.5 in some frames and live in the others)"""
     n = T * 480
     t = np.arange(n)
     rng = np.random.default_rng(5)
-    sig = [
+    return [
         32767.0 * np.sign(np.sin(2 * np.pi * 440 * t / 48000) + 1e-9),                 # full-scale square
         3.0e6 * np.sin(2 * np.pi * 233 * t / 48000),                                    # 100x beyond int16
         30000.0 + 2000.0 * rng.standard_normal(n),                                      # DC offset + noise
         np.where(t % 997 == 0, 32768.0, 0.0) - np.where(t % 1499 == 0, 32768.0, 0.0),   # impulses in silence
         1e-38 * rng.standard_normal(n),                                                 # denormal products all along the path
         np.where((t // 4800) % 2 == 0, 8000.0 * np.sin(2 * np.pi * 150 * t / 48000), 0.0),  # bursts / exact zeros
-        1e-3 * rng.standard_normal(n),                                                  # just above the silence threshold
+        1e-3 * rng.standard_normal(n),                                                  # far below the silence threshold
+        0.5 * rng.standard_normal(n),                                                   # on the threshold: flips frame by frame
     ]
-    ids = list(range(len(sig))) * 3                                                      # 21 streams: a full tile and a ragged one
+
+
+@pytest.mark.parametrize("path", [0, 2])
+def test_extreme_but_finite_inputs(model, blob_default, path):
+    """extreme_signals(30), each in three streams of one batch, against the oracle"""
+    T = 30
+    sig = extreme_signals(T)
+    ids = list(range(len(sig))) * 3                                                      # 24 streams: a full tile and a ragged one
     pcm = np.stack([sig[i].astype(np.float32).reshape(T, 480) for i in ids], axis=1)
     b = capi.Batch(model, len(ids))
     b.set_nn_path(path)
@@ -622,6 +630,10 @@ def test_pipeline_chunking_is_invisible(model, blob_default):
             assert_bits_equal(b.export_state(i), want["state"][i], f"state {i}")
 
 
+# the mixed block of tests/stream_mix.py on its small batches (251 and 389 streams, every network path) in the forced runs below
+_SMALL_MIX = " or (test_stream_mix_at_every_form and (n251 or n389))"
+
+
 @pytest.mark.parametrize("mode", ["1", "9"])
 def test_other_stream_schedules_forced(mode):
     """RNNOISE_AMD_PIPE (read once per process) selects the A/B schedules -- 1: only K0 on a side stream, 9: no side
@@ -632,8 +644,9 @@ def test_other_stream_schedules_forced(mode):
     if os.environ.get("RNNOISE_AMD_PIPE"):
         pytest.skip("already inside a forced run")
     env = dict(os.environ, RNNOISE_AMD_PIPE=mode)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, "-k",
-                        "test_pipeline_chunking or test_device_call_in_place or test_mfma_path_bit_exact"],
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_gpu_at_size.py"), "-k",
+                        "test_pipeline_chunking or test_device_call_in_place or test_mfma_path_bit_exact" + _SMALL_MIX],
                        env=env, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
@@ -659,9 +672,9 @@ def test_throughput_kernels_at_small_sizes():
     env = dict(os.environ, RNNOISE_AMD_NN_ONE_MAX="0", RNNOISE_AMD_HP_ONE_MAX="0", RNNOISE_AMD_K1_SPW="4", RNNOISE_AMD_TILE_WAVES="16")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_blob_tools.py"),
-                        os.path.join(root, "tests", "test_weight_layouts_gpu.py"), "-k",
+                        os.path.join(root, "tests", "test_weight_layouts_gpu.py"), os.path.join(root, "tests", "test_gpu_at_size.py"), "-k",
                         "test_mfma_path_bit_exact or test_synthetic_models_on_gpu or test_s16_entry_points or test_drop_in_single_stream_api"
-                        " or test_weight_layout_on_every_network_path"],
+                        " or test_weight_layout_on_every_network_path" + _SMALL_MIX],
                        env=env, capture_output=True, text=True, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
@@ -683,9 +696,9 @@ def test_at_size_kernels_on_small_ragged_batches():
                RNNOISE_AMD_GRU_VARIANT="w4")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, os.path.join(root, "tests", "test_blob_tools.py"),
-                        os.path.join(root, "tests", "test_weight_layouts_gpu.py"), "-k",
+                        os.path.join(root, "tests", "test_weight_layouts_gpu.py"), os.path.join(root, "tests", "test_gpu_at_size.py"), "-k",
                         "test_mfma_path_bit_exact or test_sparser_blob_on_ragged_batches or test_synthetic_models_on_gpu or test_s16_entry_points"
-                        " or test_weight_layout_on_every_network_path"],
+                        " or test_weight_layout_on_every_network_path" + _SMALL_MIX],
                        env=env, capture_output=True, text=True, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
