@@ -152,6 +152,36 @@ RNNOISE_EXPORT int rnnoise_batch_set_stream_models(RNNoiseBatch *b, const unsign
 RNNOISE_EXPORT int rnnoise_batch_set_stream_models_device(RNNoiseBatch *b, const unsigned char *d_models, void *hip_stream);
 RNNOISE_EXPORT int rnnoise_batch_stream_models(RNNoiseBatch *b, unsigned char *models);
 
+/* Per-stream suppression controls: how hard each stream is suppressed.  ctl[n_streams][RNNOISE_AMD_CTL_FLOATS] = {floor, thr, hold}:
+ *   floor  a floor on the band gains, linear in [0, 1] (0: none) -- an attenuation limit of L dB is floor = 10^(-L/20);
+ *   thr    a VAD gate threshold in [0, 1] (0: no gate);
+ *   hold   frames the gate stays open after the last voice frame, a whole number in [0, 65535].
+ * Each stream counts c, the frames since its last voice frame.  On every frame the stream has (an absent frame of a masked call
+ * touches nothing), with vad the value the call returns for it (0 on a silent frame): c = (thr == 0 || vad >= thr) ? 0 :
+ * min(c + 1, 65536) -- a NaN vad is no voice.  That vad belongs to the frame after the one being synthesised: one frame of look-ahead.
+ * Non-silent frames: after the decay cap of the band gains and its memory update (src/denoise.c:479-487, on the raw gains), every
+ * band gain below floor is raised to floor (a NaN gain stays NaN); the per-bin gains are interpolated from the result.  When thr > 0
+ * and c > hold, the gate is closed: the spectrum to be synthesised is zero (silent frames too), so the frame's output is the previous
+ * frame's synthesis tail and the new synthesis tail is zero.  The returned vad and gains stay the raw network values, and of the
+ * exported state only synthesis_mem can differ from that of a stream without controls.  All zeros: the reference's bits exactly.
+ * A new stream starts with c = 65536 ("no voice yet": a gated stream stays muted until its first voice frame); rnnoise_batch_reset,
+ * reset_streams[_device], import_state and a host-fed call that fails (it resets the batch) put it back there.  set_pcm_rate,
+ * set_nn_path, set_schedule, the model map and a new table leave it alone.  rnnoise_batch_train_features* ignores the controls.
+ * rnnoise_batch_set_stream_controls (host array): synchronous; -1 and no change if any entry is non-finite, out of range, or has a
+ * fractional hold.  ctl == NULL drops the table and the counters: the batch then launches exactly what a batch that never had one
+ * launches, and the next table set restarts every counter at 65536.
+ * rnnoise_batch_set_stream_controls_device (n_streams records in the batch's device memory): a copy ordered on hip_stream (no kernel,
+ * no host synchronisation; the first table of a batch allocates its memory).  Entries are not checked: the kernel that reads one maps
+ * NaN to 0, clamps each value into its range and truncates hold.
+ * rnnoise_batch_stream_controls reads the table back (synchronous; zeros when there is none).  0 / -1.
+ * Cost: with a table the synthesis kernel reads 20 more bytes per stream and frame (record, counter, VAD) and writes 4; without
+ * one, nothing.
+ * The per-frame API of rnnoise.h has no controls. */
+#define RNNOISE_AMD_CTL_FLOATS 3
+RNNOISE_EXPORT int rnnoise_batch_set_stream_controls(RNNoiseBatch *b, const float *ctl);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_controls_device(RNNoiseBatch *b, const float *d_ctl, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_stream_controls(RNNoiseBatch *b, float *ctl);
+
 /* Portable per-stream state: RN_STATE_FLOATS 32-bit words laid out as in rn_layout.h
  * (the 25,128 live bytes of the reference's DenoiseState).  Import requires
  * analysis_mem == the last 480 samples of pitch_buf, which every state produced by the

@@ -43,9 +43,34 @@ EXPORTS = [
     "rnnoise_batch_process_masked_s16", "rnnoise_batch_reset_streams", "rnnoise_batch_reset_streams_device",
     "rnnoise_batch_set_pcm_rate", "rnnoise_batch_pcm_rate",
     "rnnoise_batch_add_model", "rnnoise_batch_set_stream_models", "rnnoise_batch_set_stream_models_device", "rnnoise_batch_stream_models",
+    "rnnoise_batch_set_stream_controls", "rnnoise_batch_set_stream_controls_device", "rnnoise_batch_stream_controls",
 ]
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
+CTL_FLOATS = 3  # RNNOISE_AMD_CTL_FLOATS: {floor, thr, hold} per stream (rnnoise_batch_set_stream_controls)
+CTL_HOLD_MAX = 65535
+
+
+def floor_of_limit_db(limit_db):
+    """the linear gain floor of an attenuation limit of `limit_db` dB (scalar or array; 0 dB = floor 1, +inf = no floor):
+    float32(10 ** (-limit_db / 20)).  The C API takes the linear floor only."""
+    return np.float32(10.0 ** (-np.asarray(limit_db, np.float64) / 20.0))
+
+
+def controls_table(n_streams, limit_db=None, vad_threshold=0.0, hold_frames=0):
+    """the (N, 3) float32 table of rnnoise_batch_set_stream_controls from an attenuation limit in dB (None / inf: no floor), a VAD gate
+    threshold (0: no gate) and a hold in frames -- each a scalar or an (N,) array"""
+    t = np.zeros((n_streams, CTL_FLOATS), np.float32)
+    t[:, 0] = 0.0 if limit_db is None else floor_of_limit_db(limit_db)
+    t[:, 1] = vad_threshold
+    t[:, 2] = hold_frames
+    return t
+
+
+def limit_db_of_floor(floor):
+    """the inverse: the attenuation limit in dB of a linear floor (0 = no limit: +inf)"""
+    with np.errstate(divide="ignore"):
+        return -20.0 * np.log10(np.asarray(floor, np.float64))
 
 
 def _share_hip_runtime_with_torch():
@@ -142,6 +167,9 @@ def _load(path, debug):
         L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
         L.rnnoise_batch_stream_models.argtypes = [vp, up]
+        L.rnnoise_batch_set_stream_controls.argtypes = [vp, fp]
+        L.rnnoise_batch_set_stream_controls_device.argtypes = [vp, vp, vp]
+        L.rnnoise_batch_stream_controls.argtypes = [vp, fp]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
@@ -416,6 +444,31 @@ class Batch:
         if self._L.rnnoise_batch_stream_models(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte))):
             raise RuntimeError("rnnoise_batch_stream_models failed")
         return m
+
+    def set_stream_controls(self, ctl):
+        """per-stream suppression controls (rnnoise_batch_set_stream_controls): (N, 3) float32 rows {floor, thr, hold} -- floor a
+        linear gain floor in [0, 1], thr a VAD gate threshold in [0, 1] (0: no gate), hold whole frames in [0, 65535] -- or None to
+        drop the table.  Synchronous; ValueError (and nothing changes) on a non-finite, out-of-range or fractional entry."""
+        if ctl is None:
+            if self._L.rnnoise_batch_set_stream_controls(self.h, None):
+                raise RuntimeError("rnnoise_batch_set_stream_controls failed")
+            return
+        c = np.ascontiguousarray(ctl, np.float32)
+        assert c.shape == (self.n, CTL_FLOATS), c.shape
+        if self._L.rnnoise_batch_set_stream_controls(self.h, _fp(c)):
+            raise ValueError("rnnoise_batch_set_stream_controls failed (an entry is non-finite, out of range or has a fractional hold)")
+
+    def set_stream_controls_device(self, d_ctl: int, stream: int = 0):
+        """the same from N x 3 floats of device memory, a copy ordered on `stream` (the kernel maps NaN to 0, clamps, truncates hold)"""
+        if self._L.rnnoise_batch_set_stream_controls_device(self.h, d_ctl or None, stream or None):
+            raise RuntimeError("rnnoise_batch_set_stream_controls_device failed")
+
+    def stream_controls(self) -> np.ndarray:
+        """the control table, (N, 3) float32 (zeros when there is none; synchronous)"""
+        c = np.empty((self.n, CTL_FLOATS), np.float32)
+        if self._L.rnnoise_batch_stream_controls(self.h, _fp(c)):
+            raise RuntimeError("rnnoise_batch_stream_controls failed")
+        return c
 
     def export_state(self, stream: int) -> np.ndarray:
         s = np.empty(STATE_FLOATS, np.float32)

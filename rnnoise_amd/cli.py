@@ -8,6 +8,9 @@ ways (rnnoise_batch_process_s16: the two conversions of rnnoise_demo.c:56,58 run
 batch; a stream whose file has ended is fed zeros and produces no more output.
 
   python -m rnnoise_amd.cli denoise --model weights_blob.bin --out-dir out  a.raw b.raw ...
+
+--atten-limit-db, --vad-gate and --vad-hold apply the per-stream suppression controls of include/rnnoise_amd.h
+(rnnoise_batch_set_stream_controls) to every file: a floor on the band gains, and a VAD gate with a hold time.
 """
 from __future__ import annotations
 
@@ -23,10 +26,11 @@ FRAME = capi.FRAME
 
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
-                  vad_csv: bool = False, rate: int = 48000):
+                  vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 24000, 16000 or
-    8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device)."""
+    8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
+    controls of every file (capi.controls_table); all unset, the batch has no control table."""
     os.makedirs(out_dir, exist_ok=True)
     FRAME = capi.FRAME * rate // 48000
     n_frames = [os.path.getsize(p) // 2 // FRAME for p in inputs]  # partial tail dropped (rnnoise_demo.c:55)
@@ -35,6 +39,8 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     batch = capi.Batch(model, N, device=device)
     if rate != 48000:
         batch.set_pcm_rate(rate)
+    if atten_limit_db is not None or vad_gate or vad_hold:
+        batch.set_stream_controls(capi.controls_table(N, atten_limit_db, vad_gate, vad_hold))
     ins = [open(p, "rb") for p in inputs]
     outs = [open(os.path.join(out_dir, os.path.basename(p) + ".denoised.raw"), "wb") for p in inputs]
     vfs = [open(os.path.join(out_dir, os.path.basename(p) + ".vad.csv"), "w") for p in inputs] if vad_csv else None
@@ -73,9 +79,14 @@ def main(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--vad-csv", action="store_true")
     p.add_argument("--rate", type=int, default=48000, choices=capi.PCM_RATES, help="sample rate of the RAW files")
+    p.add_argument("--atten-limit-db", type=float, default=None,
+                   help="attenuation limit in dB: no band is suppressed by more (a floor on the band gains); default none")
+    p.add_argument("--vad-gate", type=float, default=0.0, help="VAD threshold in [0, 1] below which output is muted (0: no gate)")
+    p.add_argument("--vad-hold", type=int, default=0, help="frames the VAD gate stays open after the last voice frame")
     p.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
-    n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate)
+    n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
+                      a.atten_limit_db, a.vad_gate, a.vad_hold)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

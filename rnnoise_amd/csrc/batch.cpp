@@ -91,6 +91,10 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
   if (v.phase) v.phase += f;
   if (v.active) v.active += f;  // (rows of the mask keep the stride n_stride)
   if (v.model_of) v.model_of += f;
+  if (v.ctl) {
+    v.ctl += RN_CTL_FLOATS * f;
+    v.gate_c += f;
+  }
   if (v.rs_hist) {
     v.rs_hist += RN_RS_HIST * f;
     v.rs_up += RN_FRAME_SIZE * f;
@@ -216,6 +220,7 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->arena) hipFree(b->arena);
   if (b->rs_buf) hipFree(b->rs_buf);
   if (b->model_map) hipFree(b->model_map);
+  if (b->ctl_buf) hipFree(b->ctl_buf);
   if (b->debug_buf) hipFree(b->debug_buf);
   if (b->side) hipStreamDestroy(b->side);
   if (b->side_hp) {
@@ -236,6 +241,7 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemset(b->arena, 0, b->arena_bytes));
   if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float)));  // (the histories; rs_up / rs_dn are scratch)
+  if (b->g.gate_c) HIP_OK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b->g.gate_c), RN_CTL_NONE, b->n));  // (the table stays)
   HIP_OK(hipDeviceSynchronize());
   b->img_valid = false;
   b->parity = 0;
@@ -320,6 +326,71 @@ extern "C" int rnnoise_batch_stream_models(RNNoiseBatch *b, unsigned char *model
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemcpy(models, b->model_map, (size_t)b->n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- per-stream suppression controls (include/rnnoise_amd.h) ----
+// The table and the counters live in ctl_buf from the first set on; g.ctl / g.gate_c point into it while a table is set, and K3 reads
+// them (rn_dev.h: RnGroupDev::ctl).  Without a table both are null and every launch is the one of a batch that never saw these calls.
+static_assert(RN_CTL_FLOATS == RNNOISE_AMD_CTL_FLOATS, "one record size for the kernels and the API");
+namespace {
+bool ctl_entry_ok(const float *e) {
+  const float floor_gain = e[0], thr = e[1], hold = e[2];
+  return std::isfinite(floor_gain) && std::isfinite(thr) && std::isfinite(hold) && floor_gain >= 0.f && floor_gain <= 1.f &&
+         thr >= 0.f && thr <= 1.f && hold >= 0.f && hold <= 65535.f && hold == std::floor(hold);
+}
+// memory on first use; a table set after none (or after a NULL set) starts every counter at RN_CTL_NONE, ordered on st
+int ctl_arm(RNNoiseBatch *b, hipStream_t st) {
+  const size_t N = b->n;
+  if (!b->ctl_buf) HIP_OK(hipMalloc((void **)&b->ctl_buf, N * RN_CTL_FLOATS * sizeof(float) + N * sizeof(int)));
+  if (!b->g.ctl) {
+    int *c = reinterpret_cast<int *>(b->ctl_buf + N * RN_CTL_FLOATS);
+    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c), RN_CTL_NONE, N, st));
+    b->g.ctl = b->ctl_buf;
+    b->g.gate_c = c;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int rnnoise_batch_set_stream_controls(RNNoiseBatch *b, const float *ctl) {
+  if (!b) return -1;
+  if (ctl)
+    for (int s = 0; s < b->n; s++)
+      if (!ctl_entry_ok(ctl + (size_t)s * RN_CTL_FLOATS)) return -1;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_stream_models: a call in flight keeps what it was launched with)
+  if (!ctl) {  // no table: the launches of a batch without one; the counters go with it
+    b->g.ctl = nullptr;
+    b->g.gate_c = nullptr;
+    return 0;
+  }
+  if (ctl_arm(b, nullptr)) return -1;
+  HIP_OK(hipMemcpy(b->ctl_buf, ctl, (size_t)b->n * RN_CTL_FLOATS * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" int rnnoise_batch_set_stream_controls_device(RNNoiseBatch *b, const float *d_ctl, void *hip_stream) {
+  if (!b || !d_ctl) return -1;
+  ON_DEVICE(b->device);
+  // a copy, not a kernel: ordered on the caller's stream between its calls; K3 sanitises what it reads (NaN as 0, clamped, truncated)
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (ctl_arm(b, st)) return -1;
+  HIP_OK(hipMemcpyAsync(b->ctl_buf, d_ctl, (size_t)b->n * RN_CTL_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+extern "C" int rnnoise_batch_stream_controls(RNNoiseBatch *b, float *ctl) {
+  if (!b || !ctl) return -1;
+  const size_t bytes = (size_t)b->n * RN_CTL_FLOATS * sizeof(float);
+  if (!b->g.ctl) {
+    memset(ctl, 0, bytes);
+    return 0;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(ctl, b->ctl_buf, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 

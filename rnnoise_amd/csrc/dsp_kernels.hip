@@ -1728,7 +1728,19 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
   float *Q = L.S;
   const int silence = g.silence[s];
   constexpr int NBIN = 8;  // bins pos + 64*j
-
+  // per-stream suppression controls (rn_dev.h: RnGroupDev::ctl): one uniform branch on the pointer.  The record, the counter and the
+  // frame's VAD (what the network wrote for this frame: g.vad is the frame's own row, batch.cpp) are requested here, with the other
+  // operands, and used only after them (below); all are wave-uniform, in SGPRs
+  float ctl_floor = 0.f, ctl_thr = 0.f, ctl_hold = 0.f, ctl_vad = 0.f;
+  int ctl_c = 0;
+  if (g.ctl) {
+    const float *cr = g.ctl + (size_t)s * RN_CTL_FLOATS;
+    ctl_floor = cr[0];
+    ctl_thr = cr[1];
+    ctl_hold = cr[2];
+    ctl_vad = g.vad[s];
+    ctl_c = g.gate_c[s];
+  }
   // ---- every HBM operand up front ----
   float2 X[NBIN], P[NBIN];
   float frac[NBIN];
@@ -1763,6 +1775,19 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       wv[b] = tb.half_window[wi];
       smv[b] = lo ? sm[mi] : 0.f;
     }
+  }
+
+  bool gate = false;
+  if (g.ctl) {  // counter, gate and floor (include/rnnoise_amd.h): NaN as 0, each value clamped into its range, hold truncated
+    auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    auto clamp = [](float v, float hi) { return v > 0.f ? (v < hi ? v : hi) : 0.f; };
+    ctl_floor = clamp(uni(ctl_floor), 1.f);
+    const float thr = clamp(uni(ctl_thr), 1.f), vad = silence ? 0.f : uni(ctl_vad);
+    const int hold = (int)clamp(uni(ctl_hold), 65535.f);
+    int c = __builtin_amdgcn_readfirstlane(ctl_c);
+    c = (thr > 0.f && !(vad >= thr)) ? min(c + 1, RN_CTL_NONE) : 0;  // (a NaN vad is no voice)
+    if (lane == 0) g.gate_c[s] = c;
+    gate = thr > 0.f && c > hold;
   }
 
 // src/denoise.c:140-154 per bin (bins >= 400 -> 0), from a 32-entry band vector in LDS
@@ -1806,7 +1831,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       gi = (gi > alpha * lastg) ? gi : alpha * lastg;
       double q = (double)gi * ((double)e_ex + 1e-3) / ((double)c_ex + 1e-3);
       g.lastg[(size_t)s * RN_NB_BANDS + lane] = (float)((1.f < q) ? 1.f : q);
-      gsm[lane] = gi;
+      gsm[lane] = (ctl_floor > 0.f && gi < ctl_floor) ? ctl_floor : gi;  // (the floor of the controls: 0 = none)
     }
     RN_WSYNC();
 #pragma unroll
@@ -1871,6 +1896,9 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     (void)synth_index(b, (unsigned)pos & 63u, lo, n);
     float v = (float)RN_WINDOW_SIZE * yr[b];
     v *= wv[b];
+    // a closed gate: the spectrum is zero, so its transform is +0 at every sample -- written as such, not left to the signs of zero
+    // a transform of zeros produces in this transform's order of operations
+    if (gate) v = 0.f;
     if (lo) {
       const float r = v + smv[b];
       if (out_s16) {

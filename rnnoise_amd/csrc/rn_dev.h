@@ -165,7 +165,18 @@ struct RnGroupDev {
   // (rn_owns): only owned rows get stores -- state, state images, gains, vad -- and a workgroup with no owned row returns at once.
   const uint8_t *model_of;     // [N] slot of every stream, or null
   int model_sel, n_models;
+  // Per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls).  Null ctl / gate_c: every launch is
+  // today's (every drop-in pool, and a batch without a table).  Set, K3 (synthesis_body) reads stream s's record ctl[s] = {floor, thr,
+  // hold} -- NaN as 0, each value clamped into its range, hold truncated -- and its counter gate_c[s], the frames since its last voice
+  // frame (RN_CTL_NONE: none yet).  On every frame the stream has: c = (thr == 0 || vad >= thr) ? 0 : min(c + 1, RN_CTL_NONE); the
+  // band gains that shape the spectrum are floored at `floor` (after the decay cap and the lastg update, which see the raw gain); the
+  // spectrum is zero when thr > 0 && c > hold.  gate_c[s] = RN_CTL_NONE after reset, reset_streams and import (the scatter kernel)
+  // and when a table is set after none.
+  const float *ctl;            // [N][RN_CTL_FLOATS] or null
+  int *gate_c;                 // [N] or null
 };
+#define RN_CTL_FLOATS 3      // = RNNOISE_AMD_CTL_FLOATS: floor, thr, hold
+#define RN_CTL_NONE 65536    // counter of a stream with no voice frame yet
 #define RN_RS_TAPS 48                           // taps per phase of the up filter; the down filter has RN_RS_TAPS * L
 #define RN_RS_UP_HIST (RN_RS_TAPS - 1)          // 47 low-rate samples
 #define RN_RS_DOWN_HIST(L) ((RN_RS_TAPS - 1) * (L))  // N - L 48 kHz samples

@@ -185,6 +185,9 @@ struct RNNoiseBatch {
   RNNModel *models[RNNOISE_AMD_MAX_MODELS] = {};
   RnModelDev slot_m[RNNOISE_AMD_MAX_MODELS] = {};
   uint8_t *model_map = nullptr;
+  // per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): [N][RN_CTL_FLOATS] table, then the [N]
+  // counters -- allocated by the first set, like model_map by the first add_model; g.ctl / g.gate_c point into it while a table is set
+  float *ctl_buf = nullptr;
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
   hipStream_t side = nullptr, side_hp = nullptr;

@@ -36,7 +36,7 @@ rn_state_gather_kernel(RnGroupDev g, float *__restrict__ flat, int newest_slot, 
 }
 
 // stream s of the view <- flat[s][RN_STATE_FLOATS] (analysis_mem is implied by pitch_buf and not stored).
-// g.rs_hist set: the stream's resampler histories are zeroed too.
+// g.rs_hist set: the stream's resampler histories are zeroed too; g.gate_c set: the stream's counter restarts at RN_CTL_NONE.
 // list (optional): block b works on stream list[b] instead of stream b; entries outside the view are ignored.  flat == null: the zero
 // state of rnnoise_init() -- every slot of the two rings and of the spectra, whatever the stream's frame phase.
 extern "C" __global__ void __launch_bounds__(1024)
@@ -47,6 +47,8 @@ rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ flat, int newest
   // the resampler histories (rn_dev.h: rs_hist) restart from zero on a reset and on an import: the portable state carries none
   if (g.rs_hist)
     for (int i = threadIdx.x; i < RN_RS_HIST; i += blockDim.x) g.rs_hist[s * RN_RS_HIST + i] = 0.f;
+  // ... and so does the counter of the suppression controls (rn_dev.h: gate_c): no voice frame yet
+  if (g.gate_c && threadIdx.x == 0) g.gate_c[s] = RN_CTL_NONE;
   if (!flat) {
     auto zero = [](float *p, int n) {
       for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0.f;

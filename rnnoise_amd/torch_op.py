@@ -130,6 +130,17 @@ class RNNoiseOp:
         # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.set_stream_models_device(slots.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
 
+    def set_stream_controls(self, limit_db=None, vad_threshold=0.0, hold_frames=0):
+        """per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): an attenuation limit in dB (a
+        floor on the band gains; None / inf: none), a VAD gate threshold in [0, 1] (0: no gate) and the frames the gate stays open
+        after the last voice frame -- each a scalar or a per-stream sequence / array of N.  Synchronous; ValueError on a value out of
+        range.  clear_stream_controls() drops the table."""
+        self.batch.set_stream_controls(capi.controls_table(self.n, limit_db, vad_threshold, hold_frames))
+
+    def clear_stream_controls(self):
+        """no controls: every stream back to the reference's suppression (the table and the gate counters are dropped)"""
+        self.batch.set_stream_controls(None)
+
     def _run(self, pcm, active=None):
         torch = self.torch
         assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[1:] == (self.n, self.batch.frame)
