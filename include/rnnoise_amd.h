@@ -107,6 +107,33 @@ RNNOISE_EXPORT int rnnoise_batch_process_masked(RNNoiseBatch *b, float *out, con
 RNNOISE_EXPORT int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                                     const unsigned char *active, int n_frames);
 
+/* Stream-list calls: advance ONLY the listed streams, with compact buffers.  Their cost follows n_rows, not the batch size.
+ * Buffers are indexed by list position i, not by stream: in / out [n_frames][n_rows][480 / L] (float or int16, at the batch's PCM
+ * rate 48000 / L), vad [n_frames][n_rows], gains [n_frames][n_rows][32] or NULL.  streams[i] is the batch stream of row i, in any
+ * order.  active: optional [n_frames][n_rows] unsigned char, nonzero = row i has this frame; NULL = every listed stream has every frame.
+ * A listed stream gets exactly what the masked call would give it with the same frames present in full-size buffers: out, vad,
+ * gains and state, bit for bit.  An unlisted stream is not touched -- not its state, resampler history, gate counter or phase.  An
+ * absent frame's vad reads 0 and its gains row 32 zeros; its out row is not written.  The first list call switches the batch to
+ * per-stream frame phase, as the first masked call does (rnnoise_batch_train_features* then returns -1 until rnnoise_batch_reset).
+ * List calls work together with lock-step, masked and list calls on the same batch, every PCM rate and int16, model slots (the
+ * network runs once per slot, over the listed rows only), suppression controls and rnnoise_batch_reset_streams[_device].
+ * Device forms: asynchronous on hip_stream, device buffers as the masked device calls; d_streams is int32 in the batch's device
+ * memory.  An entry outside [0, n_streams) makes its row absent.  Duplicate entries are the caller's error: the affected streams'
+ * results are unspecified, and no other stream changes.  Host forms: the masked calls' convenience path (synchronous, staged
+ * through device memory with plain copies); the list is checked first, and an out-of-range or duplicate entry returns -1 with
+ * nothing changed.  n_rows == 0 is a successful no-op; n_rows < 0, n_rows > n_streams, or a NULL list with n_rows > 0 return -1.
+ * After a list call rnnoise_batch_debug_last defines only the entries of the streams listed in the last frame.  0 / -1. */
+RNNOISE_EXPORT int rnnoise_batch_process_device_list(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad,
+                                                     float *d_gains, const int *d_streams, int n_rows,
+                                                     const unsigned char *d_active, int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_device_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad,
+                                                         float *d_gains, const int *d_streams, int n_rows,
+                                                         const unsigned char *d_active, int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_list(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains,
+                                              const int *streams, int n_rows, const unsigned char *active, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_process_list_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
+                                                  const int *streams, int n_rows, const unsigned char *active, int n_frames);
+
 /* Back to rnnoise_init()'s state for the listed streams only; every other stream is untouched.  Host list: synchronous, -1 if an
  * index is out of range (nothing is reset then).  Device list (int32 in the batch's device memory): asynchronous on hip_stream,
  * out-of-range entries ignored.  Duplicates are harmless; n == 0 does nothing.  0 / -1. */

@@ -41,6 +41,8 @@ EXPORTS = [
     "rnnoise_amd_set_rcp_profile", "rnnoise_amd_rcp_profile", "rnnoise_amd_log10_model",
     "rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_masked_s16", "rnnoise_batch_process_masked",
     "rnnoise_batch_process_masked_s16", "rnnoise_batch_reset_streams", "rnnoise_batch_reset_streams_device",
+    "rnnoise_batch_process_device_list", "rnnoise_batch_process_device_list_s16", "rnnoise_batch_process_list",
+    "rnnoise_batch_process_list_s16",
     "rnnoise_batch_set_pcm_rate", "rnnoise_batch_pcm_rate",
     "rnnoise_batch_add_model", "rnnoise_batch_set_stream_models", "rnnoise_batch_set_stream_models_device", "rnnoise_batch_stream_models",
     "rnnoise_batch_set_stream_controls", "rnnoise_batch_set_stream_controls_device", "rnnoise_batch_stream_controls",
@@ -159,6 +161,10 @@ def _load(path, debug):
         L.rnnoise_batch_process_device_masked_s16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
         L.rnnoise_batch_process_masked.argtypes = [vp, fp, fp, fp, fp, up, C.c_int]
         L.rnnoise_batch_process_masked_s16.argtypes = [vp, sp, sp, fp, fp, up, C.c_int]
+        L.rnnoise_batch_process_device_list.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
+        L.rnnoise_batch_process_device_list_s16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
+        L.rnnoise_batch_process_list.argtypes = [vp, fp, fp, fp, fp, ip, C.c_int, up, C.c_int]
+        L.rnnoise_batch_process_list_s16.argtypes = [vp, sp, sp, fp, fp, ip, C.c_int, up, C.c_int]
         L.rnnoise_batch_reset_streams.argtypes = [vp, ip, C.c_int]
         L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
         L.rnnoise_batch_set_pcm_rate.argtypes = [vp, C.c_int]
@@ -402,6 +408,48 @@ class Batch:
         fn = self._L.rnnoise_batch_process_device_masked_s16 if s16 else self._L.rnnoise_batch_process_device_masked
         if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_active or None, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_process_device_masked failed")
+
+    def _list_args(self, pcm, streams, active, out, dtype):
+        pcm = np.ascontiguousarray(pcm, dtype)
+        T, R, F = pcm.shape
+        streams = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+        assert streams.size == R and F == self.frame
+        active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        assert active is None or active.shape == (T, R)
+        if out is None:
+            out = np.zeros_like(pcm)
+        assert out.dtype == dtype and out.shape == pcm.shape and out.flags.c_contiguous
+        return pcm, streams, active, out, T, R
+
+    def _process_list(self, fn, name, pcm, streams, active, want_gains, out, dtype, ptr):
+        pcm, streams, active, out, T, R = self._list_args(pcm, streams, active, out, dtype)
+        vad = np.empty((T, R), np.float32)
+        gains = np.empty((T, R, NB_BANDS), np.float32) if want_gains else None
+        ap = active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None
+        if fn(self.h, out.ctypes.data_as(ptr), pcm.ctypes.data_as(ptr), _fp(vad), _fp(gains), streams.ctypes.data_as(C.POINTER(C.c_int)),
+              R, ap, T):
+            raise ValueError(f"{name} failed (a stream out of range or listed twice?)")
+        return out, vad, gains
+
+    def process_list(self, pcm: np.ndarray, streams, active=None, want_gains: bool = True, out: np.ndarray | None = None):
+        """Advance only the listed streams: pcm (T, R, 480 / L) float32, row i of every frame belongs to stream streams[i]; active:
+        (T, R) or None -> (out, vad[T,R], gains[T,R,32]): rnnoise_batch_process_list.  Absent rows of `out` keep what `out` held
+        (zeros when it is not given).  ValueError on an out-of-range or repeated stream (nothing changes then)."""
+        return self._process_list(self._L.rnnoise_batch_process_list, "rnnoise_batch_process_list", pcm, streams, active, want_gains,
+                                  out, np.float32, C.POINTER(C.c_float))
+
+    def process_list_s16(self, pcm: np.ndarray, streams, active=None, want_gains: bool = True, out: np.ndarray | None = None):
+        """process_list on int16 PCM (rnnoise_batch_process_list_s16)"""
+        return self._process_list(self._L.rnnoise_batch_process_list_s16, "rnnoise_batch_process_list_s16", pcm, streams, active,
+                                  want_gains, out, np.int16, C.POINTER(C.c_short))
+
+    def process_list_device(self, d_out: int, d_in: int, d_vad: int, d_gains: int, d_streams: int, n_rows: int, d_active: int,
+                            n_frames: int, stream: int = 0, s16: bool = False):
+        """Raw device pointers (ints), asynchronous on `stream`: d_streams [n_rows] int32; buffers of n_rows rows per frame;
+        d_active [n_frames][n_rows] bytes, 0 = every listed stream present.  Out-of-range entries are absent rows."""
+        fn = self._L.rnnoise_batch_process_device_list_s16 if s16 else self._L.rnnoise_batch_process_device_list
+        if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_streams or None, n_rows, d_active or None, n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_process_device_list failed")
 
     def reset_streams(self, indices):
         """the listed streams back to rnnoise_init()'s state (synchronous; ValueError on an index out of range)"""

@@ -411,13 +411,22 @@ extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
 // PCM frames are float (the reference API's sample type) or, with s16 set, int16 converted at the two ends of the step as the
 // reference's only caller does (examples/rnnoise_demo.c:56,58): half the bytes over HBM and, in the host-fed path, PCIe.
 // d_active: the presence mask of a masked call ([n_frames][N] bytes, include/rnnoise_amd.h), or null.
+// d_list: the streams of a stream-list call (n_rows int32 on the device, include/rnnoise_amd.h), or null; the caller's buffers and
+// d_active then have n_rows rows per frame (rn_dev.h: RnGroupDev::list).
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v, float *d_vad, float *d_gains, int n_frames,
-                              void *hip_stream, bool s16, const FrameIoHooks *hk, const uint8_t *d_active) {
-  if (!b || !d_out_v || !d_in_v || n_frames < 0) return -1;
+                              void *hip_stream, bool s16, const FrameIoHooks *hk, const uint8_t *d_active, const int *d_list,
+                              int n_rows) {
+  if (!b || n_frames < 0) return -1;
+  const bool listed = d_list || n_rows;
+  if (listed) {
+    if (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !d_list)) return -1;
+    if (n_rows == 0) return 0;
+  }
+  if (!d_out_v || !d_in_v) return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
-  if (d_active && !b->per_stream && n_frames > 0) {
-    // the first masked call puts the batch into per-stream frame phase: every stream starts at the batch's phase.  ring_slot, not
+  if ((d_active || listed) && !b->per_stream && n_frames > 0) {
+    // the first masked or list call puts the batch into per-stream frame phase: every stream starts at the batch's phase.  ring_slot, not
     // frame_no: the training-feature calls advance the slots without counting frames (ring_slot % 3 == parity always)
     HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->phase_buf), b->ring_slot, b->n, st));
     b->per_stream = true;
@@ -429,8 +438,12 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     g.active = d_active;
     g.call_frame = f;
     g.call_frames = n_frames;
+    if (listed) {
+      g.list = d_list;
+      g.list_n = n_rows;
+    }
   };
-  const size_t N = b->n, esz = s16 ? sizeof(short) : sizeof(float);
+  const size_t N = listed ? n_rows : b->n, esz = s16 ? sizeof(short) : sizeof(float);  // (N: rows of the caller's buffers)
   const size_t fl = RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1);  // samples per stream and frame at the batch's PCM rate
   const char *d_in = static_cast<const char *>(d_in_v);
   char *d_out = static_cast<char *>(d_out_v);
@@ -448,7 +461,9 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   const RnSchedule sched = rn_schedule(rn_knobs(), n_frames, b->schedule);
   const bool pipelined = sched.pipelined, side_k1 = sched.side_k1;
   const bool whole = b->g.n_streams == b->g.n_stride && (size_t)b->g.n_streams * RN_GRU * 4 < (1ull << 32);
-  const RnPlan plan = rn_plan(rn_knobs(), {b->n, whole, b->cus, b->nn_path, pipelined, b->per_stream, b->g.rs_L != 0});
+  RnStepShape shape{(int)N, whole && !listed, b->cus, b->nn_path, pipelined, b->per_stream, b->g.rs_L != 0};
+  shape.listed = listed;
+  const RnPlan plan = rn_plan(rn_knobs(), shape);
   // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
   // made it: normal for torch's)
   if (side_k1 && !b->side) HIP_OK(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, 0));
@@ -479,6 +494,12 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     g.vad = d_vad ? d_vad + buf(f) * N : b->scratch_vad;
     g.gains = d_gains ? d_gains + buf(f) * N * RN_NB_BANDS : b->scratch_gains;
     phased(g, f);
+    if (listed) {  // the network writes the per-stream scratch, K3 copies the listed rows out (rn_dev.h: RnGroupDev::list)
+      g.list_vad = d_vad ? g.vad : nullptr;
+      g.list_gains = d_gains ? g.gains : nullptr;
+      g.vad = b->scratch_vad;
+      g.gains = b->scratch_gains;
+    }
     return g;
   };
   auto highpass = [&](int f) -> int {  // K0 of frame f on stream sc
@@ -558,7 +579,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
         HIP_OK(rn_launch_nn_layers(&g, mk, &b->tb, plan.gru, b->lds_gru, st, ev));
       } else {
         TimedLaunch t(b, 1);
-        b->img_valid = false;
+        b->img_valid = b->img_valid && listed;  // (a list call re-quantises its rows' tiles behind its last frame, below)
         if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, mk, &b->tb, b->lds_one, st, t.start(), t.stop()));
         else if (plan.nn == RN_NN_VECTOR) HIP_OK(rn_launch_nn_vector(&g, mk, &b->tb, st, t.start(), t.stop()));
         else HIP_OK(rn_launch_nn_mfma(&g, mk, &b->tb, plan.nn, st, t.start(), t.stop()));
@@ -574,6 +595,9 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     if (pipelined && !side_k1 && f + 3 < n_frames && highpass(f + 3)) return -1;
     b->launches += b->timing ? 1 : 0;
   }
+  // a list call keeps the layer-wise network's state images: only its rows' tiles are rebuilt (rn_dev.h: act_q), as after
+  // rnnoise_batch_reset_streams -- not the whole batch at the next lock-step step
+  if (listed && b->img_valid && n_frames > 0) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n_rows));
   b->parity = (b->parity + n_frames) % RN_SPEC_SLOTS;
   b->ring_slot = (b->ring_slot + n_frames) % RN_RING_SLOTS;
   b->frame_no += n_frames;
@@ -604,22 +628,26 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
 // The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
 // ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
 // the caller left them.  The masked host calls, and every host call at a PCM rate other than 48 kHz, come here.
+// A list call (list set: n_rows host int32 entries, checked by the caller) stages the list too, and its buffers have n_rows rows.
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
-                         int n_frames, bool s16) {
+                         int n_frames, bool s16, const int *list, int n_rows) {
   if (!b || !out || !in || n_frames < 0) return -1;
   if (n_frames == 0) return 0;
   ON_DEVICE(b->device);
-  const size_t fs = (size_t)n_frames * b->n, pcm = fs * (RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1)) * (s16 ? 2 : 4);
+  const size_t rows = list ? n_rows : b->n;
+  const size_t fs = (size_t)n_frames * rows, pcm = fs * (RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1)) * (s16 ? 2 : 4);
   const size_t o_in = 0, o_out = pcm, o_vad = 2 * pcm, o_gains = o_vad + fs * 4, o_act = o_gains + fs * RN_NB_BANDS * 4,
-               total = o_act + fs;
+               o_list = (o_act + fs + 255) & ~size_t(255), total = o_list + (list ? rows * sizeof(int) : 0);
   char *d = nullptr;
   HIP_OK(hipMalloc((void **)&d, total));
   int rc = -1;
   if (hipMemcpy(d + o_in, in, pcm, hipMemcpyHostToDevice) == hipSuccess &&
-      (!active || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&  // (absent rows keep the caller's values)
+      ((!active && !list) || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&  // (absent rows keep the caller's values)
       (!active || hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess) &&
+      (!list || hipMemcpy(d + o_list, list, rows * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
       batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,
-                                n_frames, nullptr, s16, nullptr, active ? (const uint8_t *)(d + o_act) : nullptr) == 0 &&
+                                n_frames, nullptr, s16, nullptr, active ? (const uint8_t *)(d + o_act) : nullptr,
+                                list ? (const int *)(d + o_list) : nullptr, list ? n_rows : 0) == 0 &&
       hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d + o_out, pcm, hipMemcpyDeviceToHost) == hipSuccess &&
       (!vad || hipMemcpy(vad, d + o_vad, fs * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
       (!gains || hipMemcpy(gains, d + o_gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost) == hipSuccess))
@@ -654,6 +682,47 @@ extern "C" int rnnoise_batch_process_masked(RNNoiseBatch *b, float *out, const f
 extern "C" int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                                 const unsigned char *active, int n_frames) {
   return batch_process_masked_host(b, out, in, vad, gains, active, n_frames, true);
+}
+
+// ---- stream-list calls (include/rnnoise_amd.h) ----
+extern "C" int rnnoise_batch_process_device_list(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad, float *d_gains,
+                                                 const int *d_streams, int n_rows, const unsigned char *d_active, int n_frames,
+                                                 void *hip_stream) {
+  if (!d_streams && n_rows == 0) return b ? 0 : -1;
+  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, false, nullptr, d_active, d_streams, n_rows);
+}
+
+extern "C" int rnnoise_batch_process_device_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad, float *d_gains,
+                                                     const int *d_streams, int n_rows, const unsigned char *d_active, int n_frames,
+                                                     void *hip_stream) {
+  if (!d_streams && n_rows == 0) return b ? 0 : -1;
+  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true, nullptr, d_active, d_streams, n_rows);
+}
+
+namespace {
+// the host list is checked before anything moves: an entry outside the batch or a stream listed twice refuses the call
+int batch_process_list_host(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const int *streams, int n_rows,
+                            const unsigned char *active, int n_frames, bool s16) {
+  if (!b || n_rows < 0 || n_rows > b->n || (n_rows > 0 && !streams) || n_frames < 0) return -1;
+  if (n_rows == 0) return 0;
+  std::vector<uint8_t> seen((size_t)b->n, 0);
+  for (int i = 0; i < n_rows; i++) {
+    const int s = streams[i];
+    if (s < 0 || s >= b->n || seen[s]) return -1;
+    seen[s] = 1;
+  }
+  return batch_process_staged(b, out, in, vad, gains, active, n_frames, s16, streams, n_rows);
+}
+}  // namespace
+
+extern "C" int rnnoise_batch_process_list(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains, const int *streams,
+                                          int n_rows, const unsigned char *active, int n_frames) {
+  return batch_process_list_host(b, out, in, vad, gains, streams, n_rows, active, n_frames, false);
+}
+
+extern "C" int rnnoise_batch_process_list_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
+                                              const int *streams, int n_rows, const unsigned char *active, int n_frames) {
+  return batch_process_list_host(b, out, in, vad, gains, streams, n_rows, active, n_frames, true);
 }
 
 extern "C" int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n) {

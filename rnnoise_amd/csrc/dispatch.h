@@ -60,6 +60,7 @@ struct RnStepShape {
   bool pipelined;  // the step is a frame of a pipelined multi-frame call (rn_schedule): other frames' kernels run beside it
   bool per_stream; // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
   bool low_rate;   // PCM below 48 kHz (rn_dev.h: RnGroupDev::rs_L)
+  bool listed = false;  // a stream-list call (rn_dev.h: RnGroupDev::list): n counts its listed rows, never the batch
 };
 
 struct RnPlan {
@@ -80,13 +81,14 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   // Low-rate rows take the wave-per-stream form at every batch size.  (An upsampling prologue in the lane = stream kernel, one stream
   // after the other per wave, took that kernel from 50 to 61-64 SGPRs in every arrangement tried; the 48 kHz kernels keep their
   // registers instead.  The cost at large batches: DESIGN.md 4.10, profiles/resample_rate_bench.txt)
-  p.hp = s.low_rate || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
+  // A list call: the one-wave form at every size (the lane = stream kernel has no list path).
+  p.hp = s.listed || s.low_rate || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
   // K1.  From 2,560 streams four streams share a workgroup (rn_analysis_kernel).  6,144 until round 6's last day; since the narrow
   // phases and the follower are shared by the four streams of a workgroup (round 6) that form is ahead from 3,072 streams -- 23.3
   // against 20.8 M frames/s there, 26.4 against 24.5 at 4,096 (one frame per call 0.201 against 0.231 ms), 27.8 against 26.0 at
   // 5,120 -- and level at 2,048 (profiles/r6_late_ab.txt).  Per-stream frame phase: the one-stream form at every size (the four
   // streams of rn_analysis_kernel share their narrow phases).
-  p.k1 = s.per_stream || k.k1_spw == 1 || (k.k1_spw == 0 && s.n < 2560) ? RN_K1_SINGLE : RN_K1_FOUR;
+  p.k1 = s.listed || s.per_stream || k.k1_spw == 1 || (k.k1_spw == 0 && s.n < 2560) ? RN_K1_SINGLE : RN_K1_FOUR;
   // K2.  Path 1 runs the network layer by layer (nn_layers.hip: 64 streams per GRU workgroup) from 10,240 streams; below it the five
   // launches and the smaller grids cost more than the weight reuse gains.  The tile kernel holds out while a CU has at most two tiles
   // (8,192 streams on 256 CUs: 25.9 against 24.2 M frames/s); with a third its K2 jumps (0.139 -> 0.193 ms at 10,240 streams) and the
@@ -98,10 +100,13 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   // Path 0: up to 512 streams the latency-oriented kernel (nn_kernels.hip: rn_nn_one_kernel, one 14-wave workgroup with 125 KB of LDS
   // per stream, one per CU) finishes first -- measured K2 at 64 / 256 / 512 / 768 streams: 36 / 42 / 83 / 120 us against 82 / 101 /
   // 105 / 105 us for MFMA tiles of 16 streams; the vector kernel above.
+  // A list call: never layer by layer (its tiles are tiles of listed rows, the layer images tiles of the batch) -- the tile kernel on
+  // paths 1 and 2, the one-stream kernel on path 0 whatever the number of rows.
   const int tiles = (s.n + 15) / 16;
-  if (s.whole && (s.nn_path == 2 || (s.nn_path == 1 && s.n >= k.nn_layers_min))) p.nn = RN_NN_LAYERS;
-  else if (s.nn_path >= 1)
-    p.nn = k.tile_waves == 16 || (k.tile_waves != 8 && !s.pipelined && tiles <= s.cus) ? RN_NN_TILE16 : RN_NN_TILE8;
+  const RnNnForm tile = k.tile_waves == 16 || (k.tile_waves != 8 && !s.pipelined && tiles <= s.cus) ? RN_NN_TILE16 : RN_NN_TILE8;
+  if (s.listed) p.nn = s.nn_path == 0 ? RN_NN_ONE : tile;
+  else if (s.whole && (s.nn_path == 2 || (s.nn_path == 1 && s.n >= k.nn_layers_min))) p.nn = RN_NN_LAYERS;
+  else if (s.nn_path >= 1) p.nn = tile;
   else p.nn = s.n <= k.nn_one_max ? RN_NN_ONE : RN_NN_VECTOR;
   // The GRU layer kernel: the four-wave form (two workgroups per CU: 1-3 % under the eight-wave one stand-alone in every A/B of
   // profiles/r5_gru_bound.txt) once there are more 64-stream groups than CUs; the eight-wave form while every group has a CU to itself

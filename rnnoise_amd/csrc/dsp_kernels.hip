@@ -1624,10 +1624,10 @@ extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_p
 rn_analysis_single_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity) {
   const RnStreamAt at = rn_stream_at(g, nullptr, slot, parity, 0);
   if (!at.present) {  // an absent stream: the sentinel silence = 2 keeps the network off its state, and nothing else is written
-    g.silence[at.s] = 2;  // (every lane stores the same word)
+    if (at.s >= 0) g.silence[at.s] = 2;  // (every lane stores the same word; a list entry naming no stream: nothing at all)
     return;
   }
-  analysis_body<false, 1>(g, tb, at.ring, at.spec, RnTrainArgs{});
+  analysis_body<false, 1>(g, tb, at.ring, at.spec, RnTrainArgs{}, at.s);
 }
 
 // A launch group of the one-frame API, for LATENCY: one workgroup of K1_SPW waves per listed row, every wave working on that
@@ -1703,6 +1703,14 @@ __device__ __forceinline__ unsigned synth_index(int b, unsigned pos, bool &lo, u
   mem = (897u - 64u * b) + q;
   return mem;
 }
+// A list call (rn_dev.h: RnGroupDev::list): the frame's VAD and gains of row i, from the per-stream scratch the network wrote, out to the
+// caller's rows -- zeros for an absent row, as the network writes them for an absent stream
+__device__ __forceinline__ void rn_list_outputs(const RnGroupDev &g, const RnStreamAt &at) {
+  const int lane = (int)threadIdx.x;
+  if (g.list_gains && lane < RN_NB_BANDS)
+    g.list_gains[(size_t)at.i * RN_NB_BANDS + lane] = at.present ? g.gains[(size_t)at.s * RN_NB_BANDS + lane] : 0.f;
+  if (g.list_vad && lane == 0) g.list_vad[at.i] = at.present ? g.vad[at.s] : 0.f;
+}
 template <bool LATE>
 __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTablesDev &tb, float *__restrict__ out, int parity_arg,
                                                const RnStreamAt &at) {
@@ -1713,9 +1721,12 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
   const int parity = at.spec, prev = at.prev;
   // per-stream frame phase (rn_dev.h: RnGroupDev::phase): the call's last frame advances the stream's phase (every kernel of the call
   // that reads it has finished: batch.cpp)
-  if (!listed && g.phase && g.call_frame == g.call_frames - 1 && threadIdx.x == 0)
+  if (!listed && g.phase && g.call_frame == g.call_frames - 1 && threadIdx.x == 0 && at.s >= 0)
     g.phase[at.s] = (at.ring + (at.present ? 1 : 0)) % RN_RING_SLOTS;
-  if (!at.present) return;  // an absent stream: neither `out` nor any state is written
+  if (!at.present) {  // an absent stream: neither `out` nor any state is written
+    if (g.list) rn_list_outputs(g, at);
+    return;
+  }
   const bool out_s16 = !listed && (parity_arg & 256);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   SynthLds &L = *reinterpret_cast<SynthLds *>(smem_raw);
@@ -1888,7 +1899,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     }
   }
   // window + overlap-add (src/denoise.c:400-407), straight from the registers
-  float *o = listed ? at.io + RN_ROW_OUT : out + (size_t)s * RN_FRAME_SIZE;
+  float *o = listed ? at.io + RN_ROW_OUT : out + (size_t)at.i * RN_FRAME_SIZE;  // (the caller's row: rn_dev.h RnStreamAt::i)
 #pragma unroll
   for (int b = 0; b < 15; b++) {
     bool lo;
@@ -1903,7 +1914,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       const float r = v + smv[b];
       if (out_s16) {
         const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-        reinterpret_cast<short *>(out)[(size_t)s * RN_FRAME_SIZE + n] = (short)q;
+        reinterpret_cast<short *>(out)[(size_t)at.i * RN_FRAME_SIZE + n] = (short)q;
       } else {
         o[n] = r;
       }
@@ -1911,6 +1922,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       sm[n] = v;
     }
   }
+  if (g.list) rn_list_outputs(g, at);
   if (listed) {
     // completion word of the row's request (the last word of its pinned block): the caller waiting for this frame polls it
     // instead of waiting for the whole stream to drain.  System-scope release: the frame and the VAD are visible before it.
@@ -1926,11 +1938,11 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
 // v[-47 L .. -1], the frame's 480 samples and the taps, and forms the 480 / L outputs, lane l those of m = l, l + 64, ...  The body is not
 // compiled a second time and L is a run-time value, so that the epilogue stays inside the registers of the body.
 // Called only for a stream that has this frame (rn_stream_at: RnStreamAt::present).
-__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s) {
+__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row) {
   void *out = g.rs_out;
   const int lane = threadIdx.x, L = g.rs_L, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
-  const float *row = g.rs_dn + (size_t)s * RN_FRAME_SIZE;
+  const float *body = g.rs_dn + (size_t)row * RN_FRAME_SIZE;  // (the body wrote its output row: the caller's row, RnStreamAt::i)
   const float *ht = rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
   float *h = vs + RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE;
   __syncthreads();  // (the body's stores to rs_dn, by other lanes)
@@ -1943,7 +1955,7 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
 #pragma unroll
   for (int i = 0; i < RN_FRAME_SIZE / WAVE + 1; i++) {
     const int k = min(lane + WAVE * i, RN_FRAME_SIZE - 1);
-    vs[D + k] = row[k];
+    vs[D + k] = body[k];
   }
 #pragma unroll
   for (int i = 0; i < (RN_RS_TAPS * 6 + WAVE - 1) / WAVE; i++) {
@@ -1964,9 +1976,9 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
     const float r = (a0 + a1) + (a2 + a3);
     if (out_s16) {  // (the truncating conversion of the 48 kHz calls: synthesis_body)
       const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-      static_cast<short *>(out)[(size_t)s * M + m] = (short)q;
+      static_cast<short *>(out)[(size_t)row * M + m] = (short)q;
     } else {
-      static_cast<float *>(out)[(size_t)s * M + m] = r;
+      static_cast<float *>(out)[(size_t)row * M + m] = r;
     }
   }
   // the new history: the frame's last 47 L samples
@@ -1983,7 +1995,7 @@ rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int p
   synthesis_body<true>(g, tb, out, parity_arg, at);
   if (rs && at.present) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i);
   }
 }
 // the launch groups of the one-frame API and small batches (dispatch.h: RN_K3_FEW)
@@ -1994,7 +2006,7 @@ rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, i
   synthesis_body<false>(g, tb, out, parity_arg, at);
   if (rs && at.present) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i);
   }
 }
 
@@ -2006,7 +2018,7 @@ extern "C" hipError_t rn_launch_analysis(const RnGroupDev *g, const RnTablesDev 
                                          hipEvent_t e0, hipEvent_t e1) {
   const int n = g->n_streams;
   if (form == RN_K1_SINGLE) {
-    RN_LAUNCH(rn_analysis_single_kernel, dim3(n), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity);
+    RN_LAUNCH(rn_analysis_single_kernel, dim3(rn_launch_rows(g)), dim3(WAVE), sizeof(AnalysisLds), st, e0, e1, *g, *tb, slot, parity);
   } else {
     const dim3 grid((n + K1_SPW - 1) / K1_SPW), block(WAVE * K1_SPW);
     // bit 8: issue priority (rn_analysis_kernel); bits 16-20: K1_STOP (instrumented build, tools/k1_prefix.sh)
@@ -2035,10 +2047,10 @@ extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev
   }
   const int arg = g->rs_L ? cur | 512 | (out_s16 ? 1024 : 0) : cur | (out_s16 ? 256 : 0);
   if (form == RN_K3_FEW)
-    RN_LAUNCH(rn_synthesis_few_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
+    RN_LAUNCH(rn_synthesis_few_kernel, dim3(rn_launch_rows(g)), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
               arg, prev, RnRows{});
   else
-    RN_LAUNCH(rn_synthesis_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
+    RN_LAUNCH(rn_synthesis_kernel, dim3(rn_launch_rows(g)), dim3(WAVE), sizeof(SynthLds), st, e0, e1, *g, *tb, static_cast<float *>(out),
               arg, prev);
   return hipGetLastError();
 }

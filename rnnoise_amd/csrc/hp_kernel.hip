@@ -34,7 +34,7 @@ __device__ __forceinline__ void rs_wsync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 template <bool IN_S16>
-__device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, float *xs, int L) {
+__device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, int row, float *xs, int L) {
   const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
   float *hu = xs + RN_RS_XS;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
@@ -44,7 +44,7 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
   float rx[NX], rt[NT];
 #pragma unroll
   for (int i = 0; i < NX; i++) {
-    const size_t q = (size_t)s * M + min(lane + WAVE * i, M - 1);
+    const size_t q = (size_t)row * M + min(lane + WAVE * i, M - 1);  // (row: the caller's row of stream s, RnStreamAt::i)
     rx[i] = IN_S16 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
   }
   const float *ht = rs_up_taps(L);
@@ -100,7 +100,7 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
   if ((blockDim.x == WAVE && (int)threadIdx.x >= spw) || s >= g.n_streams) return;
   if (PHASED) {  // per-stream frame phase (rn_dev.h: RnGroupDev::phase): the lane's own ring slot; an absent stream writes nothing
     bool present;
-    slot = rn_stream_phase(g, s, present) % RN_RING_SLOTS;
+    slot = rn_stream_phase(g, s, s, present) % RN_RING_SLOTS;
     if (!present) return;
   }
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
@@ -299,7 +299,7 @@ static_assert(RN_RS_LDS <= RN_PITCH_BUF_SIZE, "the upsampling prologue's LDS fit
 //  old samples were each followed by its own s_waitcnt vmcnt(0) -- five serial round trips, two of them to pinned host memory in the
 //  one-frame API, in front of a kernel of ~20 us)
 template <bool IN_S16>
-__device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, const float *__restrict__ in, const float *__restrict__ in_row,
+__device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, const void *__restrict__ in_row,
                                             bool listed, int s, int slot) {
   constexpr bool in_s16 = IN_S16;
   const int lane = threadIdx.x;
@@ -316,7 +316,7 @@ __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, co
   {  // frame -> pb[1248..] (120 float4); the 624 decimated samples older frames left in the decimated ring -> pb[0..623] (156 float4 from
      // ring0 / 2, a multiple of 16; the decimated ring's size is a multiple of 4, so a float4 never straddles the wrap)
     const float4 *x = reinterpret_cast<const float4 *>(in_row);
-    const short4 *x16 = reinterpret_cast<const short4 *>(reinterpret_cast<const short *>(in) + (size_t)s * RN_FRAME_SIZE);
+    const short4 *x16 = reinterpret_cast<const short4 *>(in_row);
     constexpr int OLD4 = (RN_PITCH_BUF_SIZE - RN_FRAME_SIZE) / 2 / 4;
     float4 f[2], o[3];
 #pragma unroll
@@ -444,16 +444,21 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
   const RnStreamAt at = rn_stream_at(g, &rows, slot_arg, 0, 0);
   const int s = at.s;
   if (!at.present) return;  // an absent stream writes nothing
+  const float *rs_row = nullptr;
   if (in_s16 & 2) {  // low-rate rows (never a row list): upsampled into RnGroupDev::rs_up, staged in the body's LDS before the body uses it
-    if (in_s16 & 1) rs_up_stream<true>(g, in, s, L.pb, g.rs_L);
-    else rs_up_stream<false>(g, in, s, L.pb, g.rs_L);
+    if (in_s16 & 1) rs_up_stream<true>(g, in, s, at.i, L.pb, g.rs_L);
+    else rs_up_stream<false>(g, in, s, at.i, L.pb, g.rs_L);
     __syncthreads();
-    in = g.rs_up;
+    rs_row = g.rs_up + (size_t)s * RN_FRAME_SIZE;
     in_s16 = 0;
   }
-  const float *in_row = at.listed ? at.io + RN_ROW_IN : in + (size_t)s * RN_FRAME_SIZE;
-  if (in_s16) hp_one_body<true>(L, g, in, in_row, at.listed, s, at.ring);
-  else hp_one_body<false>(L, g, in, in_row, at.listed, s, at.ring);
+  // the caller's row i (rn_dev.h: RnStreamAt::i -- stream s's own row except in a list call)
+  const void *in_row = at.listed ? static_cast<const void *>(at.io + RN_ROW_IN)
+                       : rs_row ? static_cast<const void *>(rs_row)
+                       : (in_s16 & 1) ? static_cast<const void *>(reinterpret_cast<const short *>(in) + (size_t)at.i * RN_FRAME_SIZE)
+                                      : static_cast<const void *>(in + (size_t)at.i * RN_FRAME_SIZE);
+  if (in_s16) hp_one_body<true>(L, g, in_row, at.listed, s, at.ring);
+  else hp_one_body<false>(L, g, in_row, at.listed, s, at.ring);
 }
 
 
@@ -462,7 +467,7 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
 extern "C" hipError_t rn_launch_hp(const RnGroupDev *g, const void *in, int in_s16, int slot, RnHpForm form, hipStream_t st, hipEvent_t e0,
                                    hipEvent_t done) {
   if (form == RN_HP_ONE_WAVE) {  // (low-rate rows: always this form, dispatch.h)
-    RN_LAUNCH(rn_hp_one_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot,
+    RN_LAUNCH(rn_hp_one_kernel, dim3(rn_launch_rows(g)), dim3(WAVE), 0, st, e0, done, *g, static_cast<const float *>(in), slot,
               in_s16 | (g->rs_L ? 2 : 0), RnRows{});
     return hipGetLastError();
   }

@@ -316,6 +316,7 @@ rn_nn_one_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb, RnRows rows) {
   // consecutive rows of one 8-row group (int8_rows shares their activation reads)
   const int half = t >= RN_GRU && t < ONE_ROW_THREADS, u = t - (t >= RN_GRU ? RN_GRU : 0);
   const uint16_t *lut = O.lut;  // the rcpps table in LDS: three dependent lookups per unit and layer must not be L2 trips
+  if (s < 0) return;  // (a list entry naming no stream: rn_dev.h RnStreamAt)
   if (!rn_owns(g, s)) return;  // (a stream of another model slot: that slot's launch writes its outputs)
   if (g.silence[s]) {  // src/denoise.c:474
     if (t < RN_NB_BANDS) g.gains[(size_t)s * RN_NB_BANDS + t] = 0;
@@ -547,7 +548,7 @@ extern "C" hipError_t rn_nn_one_opt_in(void) {
 extern "C" hipError_t rn_launch_nn_one(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, hipError_t lds_opt_in, hipStream_t st,
                                        hipEvent_t e0, hipEvent_t e1) {
   if (lds_opt_in != hipSuccess) return lds_opt_in;
-  RN_LAUNCH(rn_nn_one_kernel, dim3(g->n_streams), dim3(ONE_THREADS), sizeof(OneLds), st, e0, e1, *g, *m, *tb, RnRows{});
+  RN_LAUNCH(rn_nn_one_kernel, dim3(rn_launch_rows(g)), dim3(ONE_THREADS), sizeof(OneLds), st, e0, e1, *g, *m, *tb, RnRows{});
   return hipGetLastError();
 }
 // K2 of a launch group of the one-frame API (rn_dev.h: RnRows): one workgroup per listed row

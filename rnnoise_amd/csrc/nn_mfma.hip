@@ -61,8 +61,11 @@ __device__ __forceinline__ v4i int8_tile(const int8_t *__restrict__ wmf, int rt,
 // "At least 4" costs 8 spilled registers, "exactly 4" 36.  (Forcing <= 64 VGPRs for 4 workgroups per CU is slower: measured.)
 extern "C" __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(4)))
 rn_nn_mfma_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb) {
+  __shared__ __attribute__((aligned(16))) MfmaLds L;
 #define RN_NN_MODE 0
+#define RN_NN_LIST 1  // (rows through g.list when it is set: nn_tile_body.inc)
 #include "nn_tile_body.inc"
+#undef RN_NN_LIST
 #undef RN_NN_MODE
 }
 // The same with SIXTEEN waves per tile, for one-frame calls on batches in which every tile has a CU to itself (n_tiles <= CUs: up to
@@ -76,22 +79,28 @@ rn_nn_mfma_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb) {
 #undef NWAVES
 #define NWAVES 16
 extern "C" __global__ void __launch_bounds__(NTHREADS) rn_nn_mfma16_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb) {
+  __shared__ __attribute__((aligned(16))) MfmaLds L;
 #define RN_NN_MODE 0
+#define RN_NN_LIST 1  // (rows through g.list when it is set: nn_tile_body.inc)
 #include "nn_tile_body.inc"
+#undef RN_NN_LIST
 #undef RN_NN_MODE
 }
 #undef NWAVES
 #define NWAVES 8
 extern "C" __global__ void __launch_bounds__(NTHREADS) rn_nn_front_kernel(RnGroupDev g, RnModelDev m, RnTablesDev tb) {
+  __shared__ __attribute__((aligned(16))) FrontLds L;
 #define RN_NN_MODE 1
+#define RN_NN_LIST 0  // (the layer-wise schedule never runs a list call: dispatch.h)
 #include "nn_tile_body.inc"
+#undef RN_NN_LIST
 #undef RN_NN_MODE
 }
 // the tile kernel in the form the step's plan chose (dispatch.h: RN_NN_TILE8 | RN_NN_TILE16)
 extern "C" hipError_t rn_launch_nn_mfma(const RnGroupDev *g, const RnModelDev *m, const RnTablesDev *tb, RnNnForm form, hipStream_t st,
                                         hipEvent_t e0, hipEvent_t e1) {
   if (!m->conv2.wmf || !g->nn_act || !m->dense_out.fwm || !m->conv1.fwm) return hipErrorNotSupported;
-  const int n_tiles = (g->n_streams + TS - 1) / TS;
+  const int n_tiles = (rn_launch_rows(g) + TS - 1) / TS;  // (a list call: tiles of listed rows)
   if (form == RN_NN_TILE16)
     RN_LAUNCH(rn_nn_mfma16_kernel, dim3(n_tiles), dim3(1024), 0, st, e0, e1, *g, *m, *tb);
   else

@@ -1,31 +1,40 @@
 // nn_tile_body.inc -- body of the 16-stream tile kernels of nn_mfma.hip, included once per RN_NN_MODE (a template or a
 // shared __device__ function costs the fused kernel 30-80 VGPRs with this compiler: measured 118 -> 150 / 201).
 //   RN_NN_MODE 0: the whole network;  1: front of the layer-wise schedule (conv1, conv2, image to act_q[0], f32 copy to nn_act)
+//   RN_NN_LIST 0: tile row r is stream r;  1: tile row r is stream g.list[r] when a list is set (rn_dev.h: RnGroupDev::list), stream r
+//   otherwise.  (Compiled once per value behind a uniform branch on g.list, the two bodies in one kernel spilled 29-49 registers.)
+// The including kernel declares the LDS arena L (MfmaLds, or FrontLds for RN_NN_MODE 1).
 // NWAVES (8 | 16) is whatever the including file has it at: every loop over row / unit tiles strides by it, the one-per-wave roles
 // (conv1's eight row tiles, the 512 producer threads of the dense phase, the three chain waves) stay on the first eight waves.
-#if RN_NN_MODE == 1
-  __shared__ __attribute__((aligned(16))) FrontLds L;
-#else
-  __shared__ __attribute__((aligned(16))) MfmaLds L;
-#endif
   // The tile is one long dependency chain and the analysis kernel of the next frame queues behind the LDS it
   // holds: let its waves win instruction arbitration against the co-resident analysis waves (4096 streams:
   // +2.4 % mean over 4 alternating A/B runs, run-to-run noise +-3 %; no effect at 65,536).
   __builtin_amdgcn_s_setprio(3);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, gq = lane >> 4;
+  // Tile rows r = s0 .. s0 + 15: without a list row r is stream r; in a list call it is stream list[r] (rn_dev.h: RnGroupDev::list).
+  // ROW_OK(r): row r has a stream -- only such rows get stores.  ROW_S(r): the stream to load from for row min(r, N - 1) (stream 0 for
+  // a list entry naming none).
+#if RN_NN_LIST
+  const int N = g.list ? g.list_n : g.n_streams, s0 = blockIdx.x * TS;
+#define ROW_OK(r) ((r) < N && (!g.list || (unsigned)g.list[(r)] < (unsigned)g.n_stride))
+#define ROW_S(r) (g.list ? rn_list_stream_or0(g, min((r), N - 1)) : min((r), N - 1))
+#else
   const int N = g.n_streams, s0 = blockIdx.x * TS;
-  const int sn = (s0 + n < N) ? s0 + n : N - 1;              // this lane's stream (clamped for loads)
+#define ROW_OK(r) ((r) < N)
+#define ROW_S(r) ((r) < N ? (r) : N - 1)
+#endif
+  const int sn = ROW_S(s0 + n);                              // this lane's stream (clamped for loads)
   const int sil_n = g.silence[sn];                           // (sn is clamped: loaded unconditionally, not behind the range test's branch)
   // model slots (rn_dev.h: RnGroupDev::model_of): bit q of ownm = this launch owns stream s0 + q.  Rows of another slot get no store
   // at all -- their slot's launch writes them -- and a tile without an owned row is left before any LDS or barrier (uniform: every
   // wave forms the same mask).
   uint32_t ownm = 0xffffu;
   if (g.model_of) {
-    ownm = (uint32_t)__ballot(lane < TS && s0 + lane < N && rn_owns(g, s0 + lane));
+    ownm = (uint32_t)__ballot(lane < TS && ROW_OK(s0 + lane) && rn_owns(g, ROW_S(s0 + lane)));
     if (!ownm) return;
   }
 #define OWN(q) ((ownm >> (q)) & 1u)
-  const bool live = (s0 + n < N) && !sil_n && OWN(n);        // silent streams keep state (src/denoise.c:474)
+  const bool live = ROW_OK(s0 + n) && !sil_n && OWN(n);        // silent streams keep state (src/denoise.c:474)
   const uint16_t *lut = L.lut;
 #if RN_INSTRUMENT
   float *dbg = (g.debug && tid == 0) ? g.debug + (size_t)s0 * RN_DBG_FLOATS + RN_DBG_CLK2 : nullptr;
@@ -69,7 +78,7 @@
   float t1v[NE1];
 #pragma unroll
   for (int j = 0; j < NE1; j++) {
-    const int e = tid + j * NTHREADS, q = e / 196, k = e - q * 196, s = (s0 + q < N) ? s0 + q : N - 1;
+    const int e = tid + j * NTHREADS, q = e / 196, k = e - q * 196, s = ROW_S(s0 + q);
     float v = 0;
     if (e < TS * 196 && k < 130) v = g.conv1_state[(size_t)s * 130 + k];
     else if (e < TS * 196 && k < 195) v = g.features[(size_t)s * 68 + (k - 130)];
@@ -87,7 +96,7 @@
 #pragma unroll
   for (int c = 0; c < HC; c++) {
     const int chunk = tid + c * NTHREADS, q = chunk >> 6, k = (chunk & 63) << 2;  // 16 streams x 64 chunks of 4
-    const int s = (s0 + q < N) ? s0 + q : N - 1;
+    const int s = ROW_S(s0 + q);
     hist[c] = *reinterpret_cast<const v4f *>(g.conv2_state + (size_t)s * 256 + k);
     hq_[c] = q;
     hk_[c] = k;
@@ -105,17 +114,17 @@
 #pragma unroll
   for (int j = 0; j < NE2; j++) {
     const int q = (tid + j * NTHREADS) / 130;
-    sil2[j] = g.silence[(s0 + q < N) ? s0 + q : N - 1];
+    sil2[j] = g.silence[ROW_S(s0 + q)];
   }
 #pragma unroll
   for (int j = 0; j < NE2; j++) {
     const int e = tid + j * NTHREADS, q = e / 130, k = e - q * 130;
-    if (e < TS * 130 && s0 + q < N && !sil2[j] && OWN(q)) g.conv1_state[(size_t)(s0 + q) * 130 + k] = L.tmp1[q][65 + k];
+    if (e < TS * 130 && ROW_OK(s0 + q) && !sil2[j] && OWN(q)) g.conv1_state[(size_t)ROW_S(s0 + q) * 130 + k] = L.tmp1[q][65 + k];
   }
 #pragma unroll
   for (int c = 0; c < HC; c++)
-    if (hk_[c] >= 128 && s0 + hq_[c] < N && !g.silence[s0 + hq_[c]] && OWN(hq_[c]))
-      *reinterpret_cast<v4f *>(g.conv2_state + (size_t)(s0 + hq_[c]) * 256 + hk_[c] - 128) = hist[c];
+    if (hk_[c] >= 128 && ROW_OK(s0 + hq_[c]) && !g.silence[ROW_S(s0 + hq_[c])] && OWN(hq_[c]))
+      *reinterpret_cast<v4f *>(g.conv2_state + (size_t)ROW_S(s0 + hq_[c]) * 256 + hk_[c] - 128) = hist[c];
 
   CLK_TAP(0);  // loads, history quantisation, state shifts
   // ---- conv1: f32 MFMA, 195(+1) -> 128 = 8 row tiles, one per wave ----
@@ -153,7 +162,7 @@
       v4f o = int8_finish(m.conv2, row0, int8_tile(m.conv2.wmf, rt, lane, L.xq[0]));
 #pragma unroll
       for (int r = 0; r < 4; r++) o[r] = tanh_x86(o[r], lut);
-      if (s0 + n < N) *reinterpret_cast<v4f *>(g.nn_act + (size_t)sn * RN_GRU + row0) = o;  // f32 copy for dense_out
+      if (ROW_OK(s0 + n)) *reinterpret_cast<v4f *>(g.nn_act + (size_t)sn * RN_GRU + row0) = o;  // f32 copy for dense_out
       *reinterpret_cast<int *>(L.xq[1] + frag_off(n, row0)) = pack4(o[0], o[1], o[2], o[3]);
     }
   }
@@ -172,7 +181,7 @@
   for (int k = 0; k < 3; k++) {
     float *st = g.gru_state + (size_t)k * g.n_stride * RN_GRU;
     for (int e = tid; e < TS * 96; e += NTHREADS) {  // quantise the old state into hq
-      const int q = e / 96, c4 = (e - q * 96) << 2, s = (s0 + q < N) ? s0 + q : N - 1;
+      const int q = e / 96, c4 = (e - q * 96) << 2, s = ROW_S(s0 + q);
       const v4f h = *reinterpret_cast<const v4f *>(st + (size_t)s * RN_GRU + c4);
       *reinterpret_cast<int *>(L.hq + frag_off(q, c4)) = pack4(h[0], h[1], h[2], h[3]);
     }
@@ -221,7 +230,7 @@
   // 128 VGPRs: K2 1.00 -> 1.14-1.28 ms); one 384-input chunk per barrier (172 VGPRs or spills: 1.13 ms).
   {
     const int pq = tid >> 5, pc = (tid & 31) << 2;              // producer role: stream pq, floats pc + 128 j .. +3 of a chunk, j = 0, 1
-    const int ps = (s0 + pq < N) ? s0 + pq : N - 1;
+    const int ps = ROW_S(s0 + pq);
     auto chunk_src = [&](int c) {                                // chunk c = inputs 128c .. 128c+127 of cat
       // half-chunk h = 2c + j covers inputs 128 h .. 128 h + 127 of cat: segment h / 3, offset 128 (h % 3)
       return [=](int j) {
@@ -292,14 +301,16 @@
       v4f o;
 #pragma unroll
       for (int r = 0; r < 4; r++) o[r] = live ? sigmoid_x86(dacc[r] + bs[r], lut) : 0.f;
-      if (s0 + n < N && OWN(n)) *reinterpret_cast<v4f *>(g.gains + (size_t)sn * RN_NB_BANDS + row0) = o;
+      if (ROW_OK(s0 + n) && OWN(n)) *reinterpret_cast<v4f *>(g.gains + (size_t)sn * RN_NB_BANDS + row0) = o;
     } else if (wave == 2 && lane < TS) {
-      const int q = s0 + lane, sq = q < N ? q : N - 1;
-      const bool lv = q < N && !g.silence[sq];
-      if (q < N && OWN(lane)) g.vad[sq] = lv ? sigmoid_x86(vacc + m.vad_dense.bias[0], lut) : 0.f;
+      const int q = s0 + lane, sq = ROW_S(q);
+      const bool ok = ROW_OK(q), lv = ok && !g.silence[sq];
+      if (ok && OWN(lane)) g.vad[sq] = lv ? sigmoid_x86(vacc + m.vad_dense.bias[0], lut) : 0.f;
     }
   }
   CLK_TAP(6);  // dense_out / vad (wave 0's view)
 #endif  // RN_NN_MODE == 0 (dense phase)
 #undef CLK_TAP
 #undef OWN
+#undef ROW_OK
+#undef ROW_S

@@ -151,7 +151,18 @@ struct RnGroupDev {
   // forms that own one stream per workgroup or lane honour it; the synthesis kernel of the call's last frame advances phase[s].
   int *phase;                  // [N] frame phase of each stream at the start of the call, mod RN_RING_SLOTS
   const uint8_t *active;       // [call_frames][n_stride] nonzero = the stream has this frame; null = every stream present
+                               //   ([call_frames][list_n], by row, in a list call)
   int call_frame, call_frames; // frame of the call this launch works on; frames in the call
+  // Stream-list calls (include/rnnoise_amd.h: rnnoise_batch_process_device_list).  Null `list` on every other launch.  Set, the launch
+  // works on list_n ROWS: workgroup (or tile row) i is stream list[i] (rn_stream_at: RnStreamAt::i, ::s).  The caller's buffers -- the
+  // PCM rows the launchers hand K0 and K3, the mask `active`, list_vad, list_gains -- are indexed by row, every per-stream array by
+  // stream; an entry outside [0, n_stride) is an absent row that touches nothing.  `vad` / `gains` then point at the per-stream
+  // scratch (the network writes them by stream as in every call) and K3 copies row i out to list_vad / list_gains, zeros for an absent
+  // row.  Grids are sized by list_n (rn_launch_rows).
+  const int *list;             // [list_n] int32, or null
+  int list_n;
+  float *list_vad;             // [list_n] or null
+  float *list_gains;           // [list_n][32] or null
   // PCM rate R = 48000 / rs_L of the batch's calls (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate).  0 / null at 48 kHz: every
   // launch is today's.  Otherwise K0 upsamples the caller's rows and K3 downsamples its output (rs_coeffs.h: the filters), and
   // rs_hist[s] holds stream s's filter histories: [0, RN_RS_UP_HIST) the last low-rate input samples, [RN_RS_DOWN0, RN_RS_DOWN0 +
@@ -276,16 +287,17 @@ __device__ __forceinline__ void rn_fir_taps_from_ac(float (&ac)[5], float (&o)[5
   o[3] = lpc[3] + c1 * lpc[2];
   o[4] = c1 * lpc[3];
 }
-// Frame phase of stream s at frame g.call_frame of a call in per-stream mode (g.phase set; rn_dev.h: RnGroupDev) and whether the stream
-// has that frame.  At most call_frame + 1 byte loads, down the stream's column of the mask.
-__device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, bool &present) {
+// Frame phase of stream s (caller row i: column i of the mask) at frame g.call_frame of a call in per-stream mode (g.phase set;
+// rn_dev.h: RnGroupDev) and whether the stream has that frame.  At most call_frame + 1 byte loads, down the row's column of the mask.
+__device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, int i, bool &present) {
   typedef __attribute__((address_space(1))) const uint8_t gu8;
   int p = *(__attribute__((address_space(1))) const int *)(g.phase + s);
   present = true;
   if (g.active) {
-    gu8 *a = (gu8 *)(g.active + s);
-    for (int f = 0; f < g.call_frame; f++) p += a[(size_t)f * g.n_stride] != 0;
-    present = a[(size_t)g.call_frame * g.n_stride] != 0;
+    gu8 *a = (gu8 *)(g.active + i);
+    const size_t stride = g.list ? g.list_n : g.n_stride;
+    for (int f = 0; f < g.call_frame; f++) p += a[(size_t)f * stride] != 0;
+    present = a[(size_t)g.call_frame * stride] != 0;
   } else {
     p += g.call_frame;
   }
@@ -297,11 +309,18 @@ __device__ __forceinline__ bool rn_owns(const RnGroupDev &g, int s) {
   const int k = *(__attribute__((address_space(1))) const uint8_t *)(g.model_of + s);
   return (k < g.n_models ? k : 0) == g.model_sel;
 }
+// Stream of list row r of a list call (rn_dev.h: RnGroupDev::list), or stream 0 for an entry naming none: an address to load from,
+// never to store to (the 16-stream tile kernels)
+__device__ __forceinline__ int rn_list_stream_or0(const RnGroupDev &g, int r) {
+  const int e = *(__attribute__((address_space(1))) const int *)(g.list + r);
+  return (unsigned)e < (unsigned)g.n_stride ? e : 0;
+}
 // Which stream a workgroup-per-stream kernel works on, and at which frame phase -- resolved once at its top (rn_stream_at):
 // from its row list entry (listed), from the stream's own phase (g.phase set), or from the launch's arguments (lock-step).
 // Every field is wave-uniform.
 struct RnStreamAt {
-  int s;           // the stream's row in the group's arrays
+  int s;           // the stream's row in the group's arrays (-1: a list entry naming no stream -- present is false)
+  int i;           // the caller's row: the row of its in / out / vad / gains / mask (= s except in a list call)
   int ring;        // pitch-ring slot of this frame
   int spec, prev;  // spectra slot of this frame, and the one before it (the reference's delayed_*)
   bool present;    // the stream has this frame (false only for a masked-out stream of a per-stream call)
@@ -321,22 +340,36 @@ __device__ __forceinline__ RnStreamAt rn_stream_at(const RnGroupDev &g, const Rn
     a.spec = RN_ROW_SPEC(a.e);
     a.prev = (a.spec + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
     a.io = rows->io + (size_t)a.s * RN_ROW_IO;
+    a.i = a.s;
     return a;
   }
   a.e = 0;
   a.io = nullptr;
-  a.s = (int)blockIdx.x;
+  a.i = (int)blockIdx.x;
+  a.s = a.i;
   a.ring = ring;
   a.spec = spec;
   a.prev = prev;
+  if (g.list) {  // a list call (rn_dev.h: RnGroupDev::list): row i is stream list[i]
+    a.s = __builtin_amdgcn_readfirstlane(*(__attribute__((address_space(1))) const int *)(g.list + a.i));
+    if ((unsigned)a.s >= (unsigned)g.n_stride) {
+      a.s = -1;
+      a.present = false;
+      return a;
+    }
+  }
   if (g.phase) {
-    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, a.s, a.present));  // (the workgroup's one stream: uniform)
+    const int p = __builtin_amdgcn_readfirstlane(rn_stream_phase(g, a.s, a.i, a.present));  // (the workgroup's one stream: uniform)
     a.ring = p % RN_RING_SLOTS;
     a.spec = p % RN_SPEC_SLOTS;
     a.prev = (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
   }
   return a;
 }
+#endif
+// rows a launch of g works on: one workgroup (or tile row) per stream, or per list entry in a list call
+static inline int rn_launch_rows(const RnGroupDev *g) { return g->list ? g->list_n : g->n_streams; }
+#ifdef __HIPCC__
 #include <hip/hip_ext.h>
 // Launch with optional start / stop events: they are bound to the dispatch packet itself (hipExtLaunchKernel), so
 // timing a kernel or publishing its completion to another stream adds no packets to the queue.

@@ -318,7 +318,8 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count);    // batch.cp
 const RnKnobs &rn_knobs();                                           // batch.cpp: the dispatch switches, read once per process
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out, const void *d_in, float *d_vad, float *d_gains, int n_frames,
                               void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr,
-                              const uint8_t *d_active = nullptr);  // batch.cpp
+                              const uint8_t *d_active = nullptr, const int *d_list = nullptr, int n_rows = 0);  // batch.cpp
 void host_io_release(RNNoiseBatch *b);                               // host_io.cpp
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
-                         int n_frames, bool s16);                    // batch.cpp: host buffers through one device allocation
+                         int n_frames, bool s16, const int *list = nullptr,
+                         int n_rows = 0);                            // batch.cpp: host buffers through one device allocation

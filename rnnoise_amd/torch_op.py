@@ -60,6 +60,21 @@ def register_torch_op():
         T, N = pcm.shape[0], pcm.shape[1]
         return torch.empty_like(pcm), pcm.new_empty((T, N)), pcm.new_empty((T, N, capi.NB_BANDS))
 
+    # the stream-list form (include/rnnoise_amd.h: rnnoise_batch_process_device_list): pcm (T, R, 480 // L), row i of every frame
+    # belongs to stream idx[i] (int32 CUDA tensor); active (T, R) or None.  Only the listed streams advance; absent rows of the returned
+    # PCM are zeros, their vad 0 and gains zeros.
+    @torch.library.custom_op("rnnoise_amd::process_list", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor idx, Tensor? active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)")
+    def process_list(pcm, idx, active, state, handle):
+        res = _OPS[handle]._run_list(pcm, idx, active)
+        state.add_(pcm.shape[0])
+        return res
+
+    @process_list.register_fake
+    def _(pcm, idx, active, state, handle):
+        T, R = pcm.shape[0], pcm.shape[1]
+        return torch.empty_like(pcm), pcm.new_empty((T, R)), pcm.new_empty((T, R, capi.NB_BANDS))
+
     _registered = True
 
 
@@ -113,6 +128,11 @@ class RNNoiseOp:
         (torch.ops.rnnoise_amd.process_masked)"""
         return self.torch.ops.rnnoise_amd.process_masked(pcm, active, self.state, self.handle)
 
+    def process_list(self, pcm, idx, active=None):
+        """pcm (T, R, 480 // L) float32 CUDA tensor whose row i is stream idx[i] (an (R,) int32 CUDA tensor), active (T, R) bool / uint8
+        CUDA tensor or None: only the listed streams advance, with compact buffers (torch.ops.rnnoise_amd.process_list)"""
+        return self.torch.ops.rnnoise_amd.process_list(pcm, idx, active, self.state, self.handle)
+
     def reset_streams(self, idx):
         """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
         a host synchronisation (rnnoise_batch_reset_streams_device: entries out of range are ignored)"""
@@ -157,6 +177,24 @@ class RNNoiseOp:
             act = (active != 0).to(torch.uint8).contiguous()
             out = torch.zeros_like(pcm)
             self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream)
+        return out, vad, gains
+
+    def _run_list(self, pcm, idx, active=None):
+        torch = self.torch
+        assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.dim() == 3 and pcm.shape[2] == self.batch.frame
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.numel() == pcm.shape[1]
+        pcm, idx = pcm.contiguous(), idx.contiguous()
+        T, R = pcm.shape[0], pcm.shape[1]
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        vad = torch.empty((T, R), device=pcm.device, dtype=torch.float32)
+        gains = torch.empty((T, R, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        out = torch.zeros_like(pcm)
+        act = None
+        if active is not None:
+            assert active.is_cuda and active.shape == (T, R)
+            act = (active != 0).to(torch.uint8).contiguous()
+        self.batch.process_list_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), idx.data_ptr(), R,
+                                       act.data_ptr() if act is not None else 0, T, stream)
         return out, vad, gains
 
     def reset(self):
