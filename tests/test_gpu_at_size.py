@@ -4,7 +4,8 @@ build of the analysis kernel and 4096 MFMA tiles) and configs[3] (sparser blob, 
 stay bit-identical to each other (no cross-talk, no dependence on the tile / CU / XCD a stream lands on), and the block
 itself is checked bit for bit against the oracle, including a stream that starts silent inside a live MFMA tile.  The mixed
 block of tests/stream_mix.py (389 streams of every kind, compared stream by stream) runs at batch sizes that reach every kernel
-form, and with NaN / Inf in copies of one of its streams.  Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
+form, with NaN / Inf in copies of one of its streams, and through masked, stream-list and per-stream-phase lock-step calls with
+NaN in every absent row.  Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
 import os
 import subprocess
 import sys
@@ -211,6 +212,110 @@ def test_stream_mix_at_every_form(blob_default, rcp_profile, n, path, calls):
     states = [p + (7 * p) % ((n - p + B - 1) // B) * B for p in range(min(B, n))]
     _ragged_check(blob_default, n, calls, pcm[:sum(calls)], want=want, nn_path=path, state_streams=states, every_call=True,
                   ragged=False)
+
+
+_MASKED_MIX = {}
+SENTINEL_OUT = 0x7FA0BEEF                 # (int32 bit patterns: signalling NaNs that no arithmetic produces)
+SENTINEL_AUX = 0x7FB0CAFE
+
+
+def _masked_mix(blob, profile):
+    """the block and the oracle's run of it under stream_mix's presence schedule and resets, once per module and rcpps profile"""
+    if profile not in _MASKED_MIX:
+        pcm, _ = stream_mix.block()
+        _MASKED_MIX[profile] = pcm, stream_mix.oracle_block(blob, pcm, presence=stream_mix.presence(), resets=stream_mix.RESET)
+    return _MASKED_MIX[profile]
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path,calls", stream_mix.CASES, ids=[f"n{n}-path{p}" for n, p, _ in stream_mix.CASES])
+def test_stream_mix_masked_and_listed_at_every_form(blob_default, rcp_profile, n, path, calls):
+    """The mixed block through the serving API (include/rnnoise_amd.h): stream_mix.KINDS -- masked calls, stream-list calls with
+    out-of-range entries and lock-step calls on a batch in per-stream frame phase, one-frame and pipelined -- with the presence
+    schedule of stream_mix.presence() and a reset of stream_mix.RESET's copies before call RESET_BEFORE, on n copies of the block and
+    the network paths of CASES: every form rn_plan chooses in per-stream phase and in list calls runs (tests/test_stream_mix_cpu.py),
+    among them the lane-per-stream high-pass with the lanes of one wave at different ring slots.  Every absent input row is NaN (absent
+    rows are not read), out is pre-filled with one sentinel and vad / gains with another: every present stream-frame matches the oracle
+    run on that position's present frames bit for bit in pcm, vad and gains, every absent row keeps out's sentinel and reads vad 0 and
+    32 zero gains.  After every call debug_last's defined entries against the oracle's frame; at the end the state of every block
+    position (each from a different copy), of the reset copies, and of the position absent from every masked and list frame."""
+    import torch
+    _need_256_cus()
+    assert calls == stream_mix.CALLS
+    pcm, want = _masked_mix(blob_default, rcp_profile)
+    B = pcm.shape[1]
+    idx = np.arange(n) % B
+    dev = torch.device("cuda", 0)
+    blk = torch.from_numpy(pcm).to(dev)
+    ref = {k: torch.from_numpy(np.ascontiguousarray(want[k], np.float32)).to(dev).view(torch.int32) for k in ("out", "vad", "gains")}
+    m = capi.Model(blob_default)
+    b = capi.Batch(m, n)
+    if path is not None:
+        b.set_nn_path(path)
+    st = torch.cuda.current_stream().cuda_stream
+    never = [s for s in range(n) if idx[s] == stream_mix.SPECIAL["never"]]
+    never_state = {}
+    for c, kind in enumerate(stream_mix.KINDS):
+        plan = stream_mix.call_plan(n, c)
+        fr = plan["frames"]
+        k, R = len(fr), len(plan["src"])
+        src = torch.from_numpy(plan["src"]).to(dev)
+        present = torch.from_numpy(plan["present"]).to(dev)
+        x = stream_mix.call_input(blk, fr, src, present).contiguous()
+        out = torch.empty_like(x)
+        out.view(torch.int32).fill_(SENTINEL_OUT)
+        vad = torch.empty((k, R), device=dev)
+        gains = torch.empty((k, R, 32), device=dev)
+        vad.view(torch.int32).fill_(SENTINEL_AUX)
+        gains.view(torch.int32).fill_(SENTINEL_AUX)
+        ptrs = (out.data_ptr(), x.data_ptr(), vad.data_ptr(), gains.data_ptr())
+        if kind == "lock":
+            b.process_device(*ptrs, k, st)
+        else:
+            act = torch.from_numpy(plan["active"]).to(dev).contiguous()
+            if kind == "masked":
+                b.process_masked_device(*ptrs, act.data_ptr(), k, st)
+            else:
+                rows = torch.from_numpy(plan["rows"]).to(dev)
+                b.process_list_device(*ptrs, rows.data_ptr(), R, act.data_ptr(), k, st)
+        torch.cuda.synchronize()
+        what = f"call {c} ({kind}, frames {fr.start}..{fr.stop - 1})"
+        for name, got, w in (("out", out, 480), ("vad", vad, 1), ("gains", gains, 32)):
+            r = ref[name][fr.start:fr.stop][:, src].reshape(k, R, w)
+            r = torch.where(present[..., None], r, SENTINEL_OUT if name == "out" else 0)
+            ne = (got.view(torch.int32).reshape(k, R, w) != r).any(-1)
+            if bool(ne.any().item()):
+                where = ne.nonzero()[:5].tolist()
+                raise AssertionError(f"{what}: {name} of {int(ne.sum().item())} of {k * R} row-frames differs, first (frame, row) "
+                                     f"{where}: present {[bool(plan['present'][f, i]) for f, i in where]}, list entry "
+                                     f"{[None if plan['rows'] is None else int(plan['rows'][i]) for _, i in where]}, block position "
+                                     f"{[int(plan['src'][i]) for _, i in where]}")
+            del r, ne
+        del x, out, vad, gains
+        # debug_last: every stream after a masked or lock-step call (silence 2 where absent), the listed streams after a list call
+        feats, sil, pitch = b.debug_last()
+        last = fr.stop - 1
+        streams = np.arange(n) if plan["rows"] is None else plan["rows"][(plan["rows"] >= 0) & (plan["rows"] < n)]
+        here = stream_mix.presence()[last, streams % B] != 0
+        assert (sil[streams[~here]] == 2).all(), f"{what}: silence of streams absent from frame {last}"
+        on = streams[here]
+        for name, got in (("features", feats), ("silence", sil), ("pitch", pitch)):
+            assert_bits_equal(got[on], want[name][last][on % B], f"{what}: {name} of frame {last}")
+        if c + 1 == stream_mix.RESET_BEFORE:
+            b.reset_streams([s for s in range(n) if idx[s] in stream_mix.RESET])
+        if kind == "lock":
+            never_state = {s: b.export_state(s) for s in (never[0], never[-1])}
+    torch.cuda.synchronize()
+    # every block position from a different copy, as the lock-step test; the last copy of every reset position; the position that
+    # missed every masked and list frame as it was after the last lock-step call
+    states = [p + (7 * p) % ((n - p + B - 1) // B) * B for p in range(min(B, n))]
+    states += [p + (n - 1 - p) // B * B for p in stream_mix.RESET if p < n]
+    for s_ in states:
+        assert_bits_equal(b.export_state(s_), want["state"][s_ % B], f"state of stream {s_} (block stream {s_ % B})")
+    for s_, st_ in never_state.items():
+        assert_bits_equal(b.export_state(s_), st_, f"state of stream {s_}, absent from every frame since the last lock-step call")
+    b.close()
+    m.close()
 
 
 def _poison_places(n, B):

@@ -630,8 +630,10 @@ def test_pipeline_chunking_is_invisible(model, blob_default):
             assert_bits_equal(b.export_state(i), want["state"][i], f"state {i}")
 
 
-# the mixed block of tests/stream_mix.py on its small batches (251 and 389 streams, every network path) in the forced runs below
-_SMALL_MIX = " or (test_stream_mix_at_every_form and (n251 or n389))"
+# the mixed block of tests/stream_mix.py on its small batches (251 and 389 streams, every network path) in the forced runs below, in
+# lock-step calls and under its presence schedule (masked and list calls: there the forced runs put the lane-per-stream high-pass with
+# the lanes of a wave at different ring slots, and the four-wave GRU layer kernel under masks, on small batches)
+_SMALL_MIX = " or ((test_stream_mix_at_every_form or test_stream_mix_masked_and_listed_at_every_form) and (n251 or n389))"
 
 
 @pytest.mark.parametrize("mode", ["1", "9"])
