@@ -53,6 +53,21 @@
 #define RN_OFF_DELAYED_EXP (RN_OFF_DELAYED_EP + 32)
 #define RN_STATE_FLOATS (RN_OFF_DELAYED_EXP + 32)           /* 6282 words = 25,128 B */
 
+/* Stream snapshot (include/rnnoise_amd.h: rnnoise_batch_save_streams): the portable state, then what it leaves out of a
+ * stream of a batch -- the history of the PCM-rate converters and the counter of the VAD gate.  Words [0, RN_STATE_FLOATS)
+ * are the portable state unchanged; the header words hold int32 bit patterns; the history starts on a 16-byte boundary and
+ * RN_SNAP_FLOATS is a multiple of 4, so the rows of a snapshot array are 16-byte aligned.  State only: no model slot, no
+ * controls record, no rate, no frame phase. */
+#define RN_SNAP_OFF_MAGIC RN_STATE_FLOATS                   /* RN_SNAP_MAGIC; 0: an empty record   */
+#define RN_SNAP_OFF_L (RN_SNAP_OFF_MAGIC + 1)               /* PCM-rate divisor of the history: 1, 2, 3 or 6 (48000 / rate) */
+#define RN_SNAP_OFF_GATE (RN_SNAP_OFF_MAGIC + 2)            /* gate counter, 0..65536 (65536: no voice frame yet, or no control table) */
+#define RN_SNAP_OFF_RESERVED (RN_SNAP_OFF_MAGIC + 3)        /* 3 words: written as 0, ignored on load */
+#define RN_SNAP_OFF_HIST (RN_SNAP_OFF_MAGIC + 6)            /* 6288: resampler history, zeros at 48 kHz */
+#define RN_SNAP_HIST_FLOATS 336
+#define RN_SNAP_FLOATS (RN_SNAP_OFF_HIST + RN_SNAP_HIST_FLOATS)  /* 6624 words = 26,496 B */
+#define RN_SNAP_MAGIC 0x534E5201                            /* "\1RNS": record version 1 */
+#define RN_SNAP_GATE_NONE 65536
+
 /* Stage-tap record of the pitch analysis (tests only; rnnoise_batch_debug_pitch) */
 #define RN_DBG_XLP 0          /* [864] decimated + whitened signal (src/pitch.c:146-214)  */
 #define RN_DBG_AC 864         /* [5]   lag-windowed autocorrelation                       */

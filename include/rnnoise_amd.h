@@ -213,9 +213,44 @@ RNNOISE_EXPORT int rnnoise_batch_stream_controls(RNNoiseBatch *b, float *ctl);
  * (the 25,128 live bytes of the reference's DenoiseState).  Import requires
  * analysis_mem == the last 480 samples of pitch_buf, which every state produced by the
  * reference or by export satisfies; -1 otherwise.  Import zeroes the stream's resampler history
- * (rnnoise_batch_set_pcm_rate): the portable state carries none. */
+ * (rnnoise_batch_set_pcm_rate): the portable state carries none.  One stream per call, each call a device drain: to move
+ * streams with their history and gate counter, many at a time and ordered on a stream, see rnnoise_batch_save_streams below. */
 RNNOISE_EXPORT int rnnoise_batch_export_state(RNNoiseBatch *b, int stream, float *state);
 RNNOISE_EXPORT int rnnoise_batch_import_state(RNNoiseBatch *b, int stream, const float *state);
+
+/* Stream snapshots: save and load the COMPLETE state of many streams at once -- to move a call leg to another batch or GPU, to
+ * compact or grow a batch, to checkpoint.  A snapshot is RNNOISE_AMD_SNAP_FLOATS 32-bit words (rn_layout.h: RN_SNAP_*): the
+ * portable state exactly as rnnoise_batch_export_state writes it (a snapshot's first RN_STATE_FLOATS words can be handed to
+ * import_state or the reference unchanged), a header of int32 words -- magic / version, the PCM-rate divisor L = 48000 / rate the
+ * history belongs to, the VAD-gate counter (65536 without a control table), three reserved zeros -- and the 336 floats of
+ * resampler history (zeros at 48 kHz).  It holds state, not configuration: the stream's model slot, its controls record, the
+ * batch's rate and network path have their own setters and are set on the destination by the caller; frame phase never appears.
+ * snap is [n][RNNOISE_AMD_SNAP_FLOATS], indexed by list position; streams[i] is the batch stream of row i, in any order.
+ * streams == NULL with n == n_streams: stream i = row i (the whole batch); a NULL list with any other n > 0 returns -1.
+ * save leaves the batch untouched.  load writes every field of the listed streams: what import_state writes, placed at the
+ * DESTINATION stream's own frame phase, then the history -- copied when the record's L is the batch's current one, zeroed otherwise
+ * (what import_state does) -- and the counter, clamped to [0, 65536], when the batch has a control table.  analysis_mem is implied
+ * by pitch_buf and ignored.  A moved stream continues bit for bit as if it had stayed.  Neither call changes the batch's mode: a
+ * lock-step batch stays lock-step, one in per-stream frame phase stays there; model slots, controls, rate, network path and
+ * schedule are left alone.
+ * Device forms: asynchronous on hip_stream, no host synchronisation and no copy to the host; ordered after every earlier call of the
+ * batch on that stream and before every later one, like rnnoise_batch_reset_streams_device.  d_snap (16-byte aligned; -1 otherwise)
+ * and d_streams (int32) are in the batch's device memory.  save: an entry outside [0, n_streams) gets an empty record (magic word 0,
+ * the row's other words are not written).  load: a row whose magic word is not RN_SNAP_MAGIC or whose entry is out of range touches
+ * nothing.  Duplicate entries in a load are the caller's error: those streams are unspecified and no other stream changes; in a save
+ * they are harmless.
+ * Host forms: synchronous, staged through device memory in bounded chunks.  The list is checked first: an out-of-range entry, and
+ * in a load a duplicate entry, a bad magic word or analysis_mem != the last 480 samples of pitch_buf in any record, return -1 with
+ * nothing changed.
+ * n == 0 is a successful no-op.  A NULL batch, a NULL buffer with n > 0, n < 0 or n > n_streams return -1 without touching the
+ * device.  Cost: one launch per call (two for a load while the layer-wise network is in use), moving about 60 KB per stream at a
+ * large fraction of the device's copy rate.  0 / -1. */
+#define RNNOISE_AMD_SNAP_FLOATS RN_SNAP_FLOATS
+RNNOISE_EXPORT int rnnoise_batch_save_streams_device(RNNoiseBatch *b, float *d_snap, const int *d_streams, int n, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_load_streams_device(RNNoiseBatch *b, const float *d_snap, const int *d_streams, int n,
+                                                     void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_save_streams(RNNoiseBatch *b, float *snap, const int *streams, int n);
+RNNOISE_EXPORT int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap, const int *streams, int n);
 
 /* Network implementation: 0 = vector path (v_dot4 / FMA chains), 1 = batched MFMA path -- one kernel per 16-stream tile
  * below 10,240 streams, layer by layer (64 streams per GRU workgroup, five launches) from there up --, 2 = the layer-wise

@@ -21,6 +21,17 @@ FRAME = 480
 NB_BANDS = 32
 NB_FEATURES = 65
 STATE_FLOATS = 6282
+# the stream snapshot of rnnoise_batch_save_streams (include/rn_layout.h: RN_SNAP_*): the portable state, a header of int32 words, the
+# resampler history
+SNAP_OFF_MAGIC = STATE_FLOATS
+SNAP_OFF_L = SNAP_OFF_MAGIC + 1
+SNAP_OFF_GATE = SNAP_OFF_MAGIC + 2
+SNAP_OFF_RESERVED = SNAP_OFF_MAGIC + 3
+SNAP_OFF_HIST = SNAP_OFF_MAGIC + 6
+SNAP_HIST_FLOATS = 336
+SNAP_FLOATS = SNAP_OFF_HIST + SNAP_HIST_FLOATS  # 6624
+SNAP_MAGIC = 0x534E5201
+SNAP_GATE_NONE = 65536
 
 _lib = None
 _product = None
@@ -46,6 +57,7 @@ EXPORTS = [
     "rnnoise_batch_set_pcm_rate", "rnnoise_batch_pcm_rate",
     "rnnoise_batch_add_model", "rnnoise_batch_set_stream_models", "rnnoise_batch_set_stream_models_device", "rnnoise_batch_stream_models",
     "rnnoise_batch_set_stream_controls", "rnnoise_batch_set_stream_controls_device", "rnnoise_batch_stream_controls",
+    "rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device", "rnnoise_batch_save_streams", "rnnoise_batch_load_streams",
 ]
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
@@ -178,6 +190,10 @@ def _load(path, debug):
         L.rnnoise_batch_stream_controls.argtypes = [vp, fp]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
+        L.rnnoise_batch_save_streams_device.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.rnnoise_batch_load_streams_device.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.rnnoise_batch_save_streams.argtypes = [vp, fp, ip, C.c_int]
+        L.rnnoise_batch_load_streams.argtypes = [vp, fp, ip, C.c_int]
         L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
         L.rnnoise_batch_set_schedule.argtypes = [vp, C.c_int]
         L.rnnoise_amd_model_pack.restype = C.c_long
@@ -528,6 +544,43 @@ class Batch:
         state = np.ascontiguousarray(state, np.float32)
         if self._L.rnnoise_batch_import_state(self.h, stream, _fp(state)):
             raise RuntimeError("import_state failed")
+
+    def _snap_list(self, streams):
+        if streams is None:
+            return None, self.n
+        idx = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+        return idx, int(idx.size)
+
+    def save_streams(self, streams=None) -> np.ndarray:
+        """complete snapshots of the listed streams (None: the whole batch, row i = stream i), (n, SNAP_FLOATS) float32:
+        rnnoise_batch_save_streams.  Row i's first STATE_FLOATS words are export_state(streams[i]); then the header (view as int32)
+        and the resampler history.  Synchronous; the batch is unchanged.  ValueError on an index out of range."""
+        idx, n = self._snap_list(streams)
+        snap = np.empty((n, SNAP_FLOATS), np.float32)
+        if self._L.rnnoise_batch_save_streams(self.h, _fp(snap), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
+            raise ValueError("rnnoise_batch_save_streams failed (a stream out of range, or too many rows?)")
+        return snap
+
+    def load_streams(self, snap: np.ndarray, streams=None):
+        """row i of snap (n, SNAP_FLOATS) becomes the state of stream streams[i] (None: the whole batch): rnnoise_batch_load_streams.
+        Synchronous.  ValueError, and nothing changes, on an out-of-range or repeated stream, a record without the magic word or one
+        whose analysis_mem is not the tail of its pitch_buf."""
+        idx, n = self._snap_list(streams)
+        snap = np.ascontiguousarray(snap, np.float32)
+        assert snap.shape == (n, SNAP_FLOATS), snap.shape
+        if self._L.rnnoise_batch_load_streams(self.h, _fp(snap), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
+            raise ValueError("rnnoise_batch_load_streams failed (a stream out of range or listed twice, or a bad record?)")
+
+    def save_streams_device(self, d_snap: int, d_streams: int, n: int, stream: int = 0):
+        """Raw device pointers (ints), asynchronous on `stream`: d_snap [n][SNAP_FLOATS] float32 (16-byte aligned), d_streams [n] int32 or
+        0 with n == N for the whole batch.  A row whose entry is out of range gets an empty record (magic word 0)."""
+        if self._L.rnnoise_batch_save_streams_device(self.h, d_snap or None, d_streams or None, n, stream or None):
+            raise RuntimeError("rnnoise_batch_save_streams_device failed")
+
+    def load_streams_device(self, d_snap: int, d_streams: int, n: int, stream: int = 0):
+        """the inverse, asynchronous on `stream`: rows without the magic word and out-of-range entries touch nothing"""
+        if self._L.rnnoise_batch_load_streams_device(self.h, d_snap or None, d_streams or None, n, stream or None):
+            raise RuntimeError("rnnoise_batch_load_streams_device failed")
 
     def debug_last(self):
         f = np.empty((self.n, NB_FEATURES), np.float32)

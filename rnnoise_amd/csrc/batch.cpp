@@ -853,6 +853,105 @@ extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f
   return 0;
 }
 
+// ---- stream snapshots (include/rnnoise_amd.h: rnnoise_batch_save_streams) ----
+// The device forms are two launches at the most, ordered on the caller's stream like rnnoise_batch_reset_streams_device.  Nothing
+// has to be joined here: a pipelined call ends with the synthesis of its last frame on the caller's stream, which waited for that
+// frame's analysis (cur_k1) on the side stream, which waited for its high-pass (cur_hp) on the other one -- both side streams run
+// in frame order, so everything the call queued anywhere is complete before a kernel that follows it on the caller's stream; and the
+// next pipelined call records ev_begin on the caller's stream behind these launches and makes both side streams wait for it.
+static_assert(RNNOISE_AMD_SNAP_FLOATS == RN_SNAP_FLOATS && RN_SNAP_FLOATS % 4 == 0, "one record size for the kernels and the API");
+namespace {
+bool snap_args_ok(const RNNoiseBatch *b, const void *snap, const int *streams, int n) {
+  if (!b || n < 0 || n > b->n || (n > 0 && !snap)) return false;
+  if (n > 0 && !streams && n != b->n) return false;  // (no list: the whole batch, stream i = row i)
+  return true;
+}
+int save_on(RNNoiseBatch *b, float *d_snap, const int *d_list, int n, hipStream_t st) {
+  HIP_OK(rn_launch_state_save(&b->g, d_snap, d_list, n, b->ring_slot, b->per_stream ? b->phase_buf : nullptr, st));
+  return 0;
+}
+// the listed rows' tiles of the layer-wise network's state images follow the load while they are live (rn_dev.h: act_q), as after
+// a per-stream reset; without a list that is every tile
+int load_on(RNNoiseBatch *b, const float *d_snap, const int *d_list, int n, hipStream_t st) {
+  HIP_OK(rn_launch_state_load(&b->g, d_snap, d_list, n, b->ring_slot, b->per_stream ? b->phase_buf : nullptr, st));
+  if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, d_list ? n : 0));
+  return 0;
+}
+constexpr int SNAP_CHUNK = 1024;  // rows of the host forms' staging buffer (27 MB)
+
+// the host forms: the list is checked, the device drained (the caller's streams are not known here), then chunks of SNAP_CHUNK rows
+// go through one staging allocation with blocking copies
+int snap_host(RNNoiseBatch *b, float *snap, const int *streams, int n, bool load) {
+  if (!snap_args_ok(b, snap, streams, n)) return -1;
+  if (n == 0) return 0;
+  std::vector<int> list((size_t)n);
+  std::vector<uint8_t> seen(load ? (size_t)b->n : 0, 0);
+  for (int i = 0; i < n; i++) {
+    const int s = streams ? streams[i] : i;
+    if (s < 0 || s >= b->n) return -1;
+    if (load) {
+      if (seen[s]) return -1;
+      seen[s] = 1;
+      const float *f = snap + (size_t)i * RN_SNAP_FLOATS;
+      int magic;
+      memcpy(&magic, f + RN_SNAP_OFF_MAGIC, sizeof magic);
+      if (magic != RN_SNAP_MAGIC) return -1;
+      if (memcmp(f + RN_OFF_ANALYSIS, f + RN_OFF_PITCH_BUF + RN_PITCH_BUF_SIZE - RN_FRAME_SIZE, RN_FRAME_SIZE * 4)) {
+        fprintf(stderr, "[rnnoise_amd] load_streams: row %d: analysis_mem differs from the tail of pitch_buf\n", i);
+        return -1;
+      }
+    }
+    list[i] = s;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  const size_t chunk = n < SNAP_CHUNK ? n : SNAP_CHUNK, row_bytes = RN_SNAP_FLOATS * sizeof(float);
+  char *d = nullptr;
+  HIP_OK(hipMalloc((void **)&d, chunk * row_bytes + chunk * sizeof(int)));
+  float *d_snap = reinterpret_cast<float *>(d);
+  int *d_list = reinterpret_cast<int *>(d + chunk * row_bytes);
+  int rc = 0;
+  for (size_t r0 = 0; r0 < (size_t)n && rc == 0; r0 += chunk) {
+    const int rows = (int)std::min(chunk, (size_t)n - r0);
+    float *h = snap + r0 * RN_SNAP_FLOATS;
+    rc = -1;
+    if (hipMemcpy(d_list, list.data() + r0, rows * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) break;
+    if (load) {
+      if (hipMemcpy(d_snap, h, rows * row_bytes, hipMemcpyHostToDevice) == hipSuccess && load_on(b, d_snap, d_list, rows, nullptr) == 0 &&
+          hipStreamSynchronize(nullptr) == hipSuccess)
+        rc = 0;
+    } else if (save_on(b, d_snap, d_list, rows, nullptr) == 0 && hipStreamSynchronize(nullptr) == hipSuccess &&
+               hipMemcpy(h, d_snap, rows * row_bytes, hipMemcpyDeviceToHost) == hipSuccess) {
+      rc = 0;
+    }
+  }
+  hipFree(d);
+  return rc;
+}
+}  // namespace
+
+extern "C" int rnnoise_batch_save_streams_device(RNNoiseBatch *b, float *d_snap, const int *d_streams, int n, void *hip_stream) {
+  if (!snap_args_ok(b, d_snap, d_streams, n) || (reinterpret_cast<uintptr_t>(d_snap) & 15)) return -1;
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  return save_on(b, d_snap, d_streams, n, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int rnnoise_batch_load_streams_device(RNNoiseBatch *b, const float *d_snap, const int *d_streams, int n, void *hip_stream) {
+  if (!snap_args_ok(b, d_snap, d_streams, n) || (reinterpret_cast<uintptr_t>(d_snap) & 15)) return -1;
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  return load_on(b, d_snap, d_streams, n, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int rnnoise_batch_save_streams(RNNoiseBatch *b, float *snap, const int *streams, int n) {
+  return snap_host(b, snap, streams, n, false);
+}
+
+extern "C" int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap, const int *streams, int n) {
+  return snap_host(b, const_cast<float *>(snap), streams, n, true);
+}
+
 extern "C" int rnnoise_batch_debug_last(RNNoiseBatch *b, float *features, int *silence, int *pitch) {
   if (!b) return -1;
   ON_DEVICE(b->device);

@@ -62,6 +62,10 @@ extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, float *, int, int, hipStream_t);
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, const float *, int, int, hipStream_t, const int *list = nullptr,
                                               int n = 0);
+// (snapshot records of `rows` streams, by device list, at frame phase p or at the per-stream phases `phase`: state_kernels.hip)
+extern "C" hipError_t rn_launch_state_save(const RnGroupDev *, float *snap, const int *list, int rows, int p, const int *phase, hipStream_t);
+extern "C" hipError_t rn_launch_state_load(const RnGroupDev *, const float *snap, const int *list, int rows, int p, const int *phase,
+                                           hipStream_t);
 
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);

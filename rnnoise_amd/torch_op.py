@@ -141,6 +141,33 @@ class RNNoiseOp:
         # (freeing idx afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.reset_streams_device(idx.data_ptr(), int(idx.numel()), torch.cuda.current_stream(self.device).cuda_stream)
 
+    def save_streams(self, idx=None):
+        """complete snapshots of the listed streams (a sequence or a tensor of indices; None: the whole batch) as an (n, SNAP_FLOATS)
+        float32 CUDA tensor, on torch's current stream without a host synchronisation (rnnoise_batch_save_streams_device: a row whose
+        entry is out of range gets an empty record).  The batch is unchanged."""
+        torch = self.torch
+        if idx is not None:
+            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = self.n if idx is None else int(idx.numel())
+        snap = torch.empty((n, capi.SNAP_FLOATS), device=self.device, dtype=torch.float32)
+        self.batch.save_streams_device(snap.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
+                                       torch.cuda.current_stream(self.device).cuda_stream)
+        return snap
+
+    def load_streams(self, snap, idx=None):
+        """row i of snap ((n, SNAP_FLOATS) float32 CUDA tensor) becomes the complete state of stream idx[i] (None: the whole batch), on
+        torch's current stream without a host synchronisation (rnnoise_batch_load_streams_device: empty records and entries out of
+        range touch nothing).  Model slots and controls are the caller's to set."""
+        torch = self.torch
+        if idx is not None:
+            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = self.n if idx is None else int(idx.numel())
+        assert snap.is_cuda and snap.dtype == torch.float32 and tuple(snap.shape) == (n, capi.SNAP_FLOATS)
+        snap = snap.to(self.device).contiguous()
+        # (freeing idx or a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        self.batch.load_streams_device(snap.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
+                                       torch.cuda.current_stream(self.device).cuda_stream)
+
     def set_stream_models(self, slots):
         """the model slot of every stream: an (N,) uint8 CUDA tensor, copied on torch's current stream without a host synchronisation
         (rnnoise_batch_set_stream_models_device: entries naming no slot read as slot 0).  The frames of later calls run with it."""
