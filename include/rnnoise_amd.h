@@ -157,6 +157,37 @@ RNNOISE_EXPORT int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int
 RNNOISE_EXPORT int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz);
 RNNOISE_EXPORT int rnnoise_batch_pcm_rate(const RNNoiseBatch *b);
 
+/* Mixed-rate batches: a PCM rate per stream.  rates[n_streams] is the divisor L_s = 48000 / rate of every stream: 1, 2, 3 or 6
+ * (48, 24, 16, 8 kHz).  The batch's own rate (rnnoise_batch_set_pcm_rate, divisor Lb) keeps defining the ROW PITCH of every PCM buffer:
+ * in / out rows stay 480 / Lb samples apart in every call form (lock-step, masked, list; float and int16; host and device).  A stream
+ * runs at the batch's rate or below it, L_s >= Lb, so that its frame fits its row: a batch at 48 kHz takes all four rates, one at
+ * 16 kHz takes 16 and 8 kHz.  Stream s uses the FIRST 480 / L_s samples of its row; the rest of its `in` row is not read and the rest
+ * of its `out` row is not written (the caller's bytes stay).  vad and gains stay per 10 ms frame.  Every stream gives, bit for bit in
+ * out, vad, gains and exported state, what it gives in a uniform batch at its own rate -- for L_s = 1 the plain 48 kHz path: no
+ * filter, no added delay -- whatever the rates of its neighbours.  Without a table a batch launches exactly what it launched before
+ * these calls existed.
+ * rnnoise_batch_set_stream_rates (host array): synchronous, like rnnoise_batch_set_stream_models; -1 and no change if any entry is
+ * not one of 1, 2, 3, 6 or is below Lb.  The resampler history of every stream whose divisor CHANGES is zeroed; a stream whose divisor
+ * stays keeps its history and continues bit for bit.  No stream's DenoiseState, gate counter, model slot, controls or frame phase is
+ * touched.  rates == NULL drops the table: every stream is at the batch's rate again (history zeroed for the streams that were not)
+ * and the batch is back to the launches of one that never had a table.
+ * rnnoise_batch_set_stream_rates_device (n_streams bytes in the batch's device memory): a copy ordered on hip_stream (no kernel, no
+ * host synchronisation; the first table of a batch allocates its memory).  Entries are not checked: the kernel that reads one maps
+ * anything that is not 1, 2, 3 or 6, or that is below Lb, to Lb.  It does NOT touch histories: a stream whose divisor it changes must
+ * be reset (rnnoise_batch_reset_streams_device) or loaded from a snapshot on the same stream before its next frame -- which is what
+ * recycling a slot for a new call does anyway; otherwise that stream's first frames start from the old rate's history (finite
+ * samples, confined to that stream, gone after 47 of its input samples and 47 L_s of its 48 kHz output samples).
+ * rnnoise_batch_stream_rates reads the divisors back as the kernels read them (synchronous; Lb everywhere when there is no table).
+ * rnnoise_batch_set_pcm_rate drops the table.  rnnoise_batch_reset, reset_streams[_device] and import_state zero histories as before
+ * and leave the table alone.  rnnoise_batch_train_features* returns -1 while a table is set.  Snapshots: save writes the stream's own
+ * divisor into the record, load copies the history when the record's divisor equals the DESTINATION stream's current one and zeroes
+ * it otherwise.  Host-buffer process calls on a batch with a table take the staged convenience path of the low-rate batches, also at
+ * Lb = 1.  With a table K0 runs one wave per stream at every batch size, as in a low-rate batch (the cost).
+ * 0 / -1; a NULL batch or buffer returns -1 without touching the device. */
+RNNOISE_EXPORT int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned char *rates);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates);
+
 /* Several models in one batch: every stream runs with the model of its SLOT.  Slot 0 is the model the batch was created with;
  * rnnoise_batch_add_model puts another one into the next free slot (1 .. RNNOISE_AMD_MAX_MODELS - 1) and returns that slot: -1 on a
  * NULL batch or model, a full table, or a model that cannot be put on the batch's device.  Synchronous.  The model must outlive the
@@ -228,7 +259,7 @@ RNNOISE_EXPORT int rnnoise_batch_import_state(RNNoiseBatch *b, int stream, const
  * snap is [n][RNNOISE_AMD_SNAP_FLOATS], indexed by list position; streams[i] is the batch stream of row i, in any order.
  * streams == NULL with n == n_streams: stream i = row i (the whole batch); a NULL list with any other n > 0 returns -1.
  * save leaves the batch untouched.  load writes every field of the listed streams: what import_state writes, placed at the
- * DESTINATION stream's own frame phase, then the history -- copied when the record's L is the batch's current one, zeroed otherwise
+ * DESTINATION stream's own frame phase, then the history -- copied when the record's L is the destination stream's current one (the batch's, or the stream's own under a rate table), zeroed otherwise
  * (what import_state does) -- and the counter, clamped to [0, 65536], when the batch has a control table.  analysis_mem is implied
  * by pitch_buf and ignored.  A moved stream continues bit for bit as if it had stayed.  Neither call changes the batch's mode: a
  * lock-step batch stays lock-step, one in per-stream frame phase stays there; model slots, controls, rate, network path and

@@ -58,6 +58,7 @@ EXPORTS = [
     "rnnoise_batch_add_model", "rnnoise_batch_set_stream_models", "rnnoise_batch_set_stream_models_device", "rnnoise_batch_stream_models",
     "rnnoise_batch_set_stream_controls", "rnnoise_batch_set_stream_controls_device", "rnnoise_batch_stream_controls",
     "rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device", "rnnoise_batch_save_streams", "rnnoise_batch_load_streams",
+    "rnnoise_batch_set_stream_rates", "rnnoise_batch_set_stream_rates_device", "rnnoise_batch_stream_rates",
 ]
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
@@ -181,6 +182,9 @@ def _load(path, debug):
         L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
         L.rnnoise_batch_set_pcm_rate.argtypes = [vp, C.c_int]
         L.rnnoise_batch_pcm_rate.argtypes = [vp]
+        L.rnnoise_batch_set_stream_rates.argtypes = [vp, up]
+        L.rnnoise_batch_set_stream_rates_device.argtypes = [vp, vp, vp]
+        L.rnnoise_batch_stream_rates.argtypes = [vp, up]
         L.rnnoise_batch_add_model.argtypes = [vp, vp]
         L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
@@ -340,8 +344,41 @@ class Batch:
 
     @property
     def frame(self) -> int:
-        """samples per stream and frame at the batch's PCM rate (480 at 48 kHz)"""
+        """samples per stream and frame at the batch's PCM rate (480 at 48 kHz): the row length of every PCM array, also with a
+        rate table (set_stream_rates), under which a stream fills only the first 480 * rate // 48000 samples of its row"""
         return FRAME * self.pcm_rate // 48000
+
+    def set_stream_rates(self, hz):
+        """the PCM rate of every stream in Hz (rnnoise_batch_set_stream_rates): (N,) values out of PCM_RATES, none above the batch's
+        own rate, or None to drop the table.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose
+        rate changes restart their resampling filters from zero; every stream keeps its DenoiseState."""
+        if hz is None:
+            if self._L.rnnoise_batch_set_stream_rates(self.h, None):
+                raise RuntimeError("rnnoise_batch_set_stream_rates failed")
+            return
+        hz = np.asarray(hz).reshape(-1)
+        assert hz.size == self.n
+        if not np.isin(hz, PCM_RATES).all():
+            raise ValueError(f"stream rate unsupported (each one of {PCM_RATES})")
+        if hz.max(initial=0) > self.pcm_rate:
+            raise ValueError(f"a stream rate above the batch's PCM rate {self.pcm_rate}: its frame would not fit its row")
+        L = np.ascontiguousarray(48000 // hz.astype(np.int64), np.uint8)
+        if self._L.rnnoise_batch_set_stream_rates(self.h, L.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise ValueError("rnnoise_batch_set_stream_rates failed")
+
+    def set_stream_rates_device(self, d_rates: int, stream: int = 0):
+        """the same from N bytes of device memory holding the DIVISORS 48000 / rate (1, 2, 3, 6), a copy ordered on `stream`; any other
+        byte, or a divisor below the batch's, reads as the batch's rate.  Histories are not touched: reset or load the streams whose
+        rate changed (reset_streams_device / load_streams_device) on the same stream before their next frame."""
+        if self._L.rnnoise_batch_set_stream_rates_device(self.h, d_rates or None, stream or None):
+            raise RuntimeError("rnnoise_batch_set_stream_rates_device failed")
+
+    def stream_rates(self) -> np.ndarray:
+        """the PCM rate of every stream in Hz, (N,) int32 (synchronous; the batch's rate everywhere without a table)"""
+        L = np.empty(self.n, np.uint8)
+        if self._L.rnnoise_batch_stream_rates(self.h, L.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise RuntimeError("rnnoise_batch_stream_rates failed")
+        return (48000 // L.astype(np.int32)).astype(np.int32)
 
     def process(self, pcm: np.ndarray, want_gains: bool = True):
         """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32])."""

@@ -11,6 +11,8 @@ batch; a stream whose file has ended is fed zeros and produces no more output.
 
 --atten-limit-db, --vad-gate and --vad-hold apply the per-stream suppression controls of include/rnnoise_amd.h
 (rnnoise_batch_set_stream_controls) to every file: a floor on the band gains, and a VAD gate with a hold time.
+--rates 8000,48000,16000 gives every file its own sample rate (one per input, each at most --rate): one mixed-rate batch
+(rnnoise_batch_set_stream_rates), every file read and written at its own rate.
 """
 from __future__ import annotations
 
@@ -26,19 +28,25 @@ FRAME = capi.FRAME
 
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
-                  vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0):
+                  vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
-    controls of every file (capi.controls_table); all unset, the batch has no control table."""
+    controls of every file (capi.controls_table); all unset, the batch has no control table.  rates: one sample rate per file, none
+    above `rate` (a mixed-rate batch: capi.Batch.set_stream_rates); a file's frames fill the front of its rows."""
     os.makedirs(out_dir, exist_ok=True)
     FRAME = capi.FRAME * rate // 48000
-    n_frames = [os.path.getsize(p) // 2 // FRAME for p in inputs]  # partial tail dropped (rnnoise_demo.c:55)
+    if rates is not None and len(rates) != len(inputs):
+        raise ValueError(f"{len(rates)} rates for {len(inputs)} files")
+    frame_of = [capi.FRAME * r // 48000 for r in rates] if rates is not None else [FRAME] * len(inputs)  # samples per 10 ms of each file
+    n_frames = [os.path.getsize(p) // 2 // fl for p, fl in zip(inputs, frame_of)]  # partial tail dropped (rnnoise_demo.c:55)
     N, T = len(inputs), max(n_frames + [0])
     model = capi.Model(model_blob)
     batch = capi.Batch(model, N, device=device)
     if rate != 48000:
         batch.set_pcm_rate(rate)
+    if rates is not None:
+        batch.set_stream_rates(rates)
     if atten_limit_db is not None or vad_gate or vad_hold:
         batch.set_stream_controls(capi.controls_table(N, atten_limit_db, vad_gate, vad_hold))
     ins = [open(p, "rb") for p in inputs]
@@ -52,14 +60,14 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
         for s, f in enumerate(ins):
             k = max(0, min(tn, n_frames[s] - t0))
             if k:
-                x = np.frombuffer(f.read(k * FRAME * 2), dtype=np.int16)
-                chunk[:k, s] = x.reshape(k, FRAME)
+                x = np.frombuffer(f.read(k * frame_of[s] * 2), dtype=np.int16)
+                chunk[:k, s, :frame_of[s]] = x.reshape(k, frame_of[s])
         out, vad, _ = batch.process_s16(chunk, want_gains=False)
         for s in range(N):
             k = max(0, min(tn, n_frames[s] - t0))
             first = 1 if t0 == 0 else 0  # the demo drops the first output frame (rnnoise_demo.c:59-60)
             if k > first:
-                outs[s].write(out[first:k, s].tobytes())  # (the demo's truncating (short) cast was done on the device)
+                outs[s].write(out[first:k, s, :frame_of[s]].tobytes())  # (the demo's truncating (short) cast was done on the device)
             if vfs and k:
                 vfs[s].write("".join(f"{v:.6f}\n" for v in vad[:k, s]))
     for f in ins + outs + (vfs or []):
@@ -79,6 +87,8 @@ def main(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--vad-csv", action="store_true")
     p.add_argument("--rate", type=int, default=48000, choices=capi.PCM_RATES, help="sample rate of the RAW files")
+    p.add_argument("--rates", type=lambda v: [int(x) for x in v.split(",")], default=None,
+                   help="comma list, one sample rate per input file, each at most --rate: a mixed-rate batch")
     p.add_argument("--atten-limit-db", type=float, default=None,
                    help="attenuation limit in dB: no band is suppressed by more (a floor on the band gains); default none")
     p.add_argument("--vad-gate", type=float, default=0.0, help="VAD threshold in [0, 1] below which output is muted (0: no gate)")
@@ -86,7 +96,7 @@ def main(argv=None):
     p.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
-                      a.atten_limit_db, a.vad_gate, a.vad_hold)
+                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

@@ -95,6 +95,7 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
     v.ctl += RN_CTL_FLOATS * f;
     v.gate_c += f;
   }
+  if (v.rs_Ls) v.rs_Ls += f;
   if (v.rs_hist) {
     v.rs_hist += RN_RS_HIST * f;
     v.rs_up += RN_FRAME_SIZE * f;
@@ -219,6 +220,7 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->state_stage) hipFree(b->state_stage);
   if (b->arena) hipFree(b->arena);
   if (b->rs_buf) hipFree(b->rs_buf);
+  if (b->rate_map) hipFree(b->rate_map);
   if (b->model_map) hipFree(b->model_map);
   if (b->ctl_buf) hipFree(b->ctl_buf);
   if (b->debug_buf) hipFree(b->debug_buf);
@@ -252,24 +254,109 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
 }
 
 // PCM rate: K0 upsamples the caller's rows from 48000 / L, K3 downsamples its output back (rn_dev.h: RnGroupDev::rs_L).  48 kHz
-// leaves g.rs_hist / g.rs_L null: every launch is then the one of a batch that never saw this call.
+// without a rate table leaves g.rs_hist / g.rs_L null: every launch is then the one of a batch that never saw these calls.
+namespace {
+// the group's resampler fields from the batch's rate and whether it has a rate table (rn_dev.h: RnGroupDev::rs_Ls)
+void rs_point(RNNoiseBatch *b, bool table) {
+  const size_t N = b->n;
+  const bool on = table || b->pcm_rate != 48000;
+  b->g.rs_L = on ? 48000 / b->pcm_rate : 0;
+  b->g.rs_pitch = on ? RN_FRAME_SIZE / b->g.rs_L : 0;
+  b->g.rs_hist = on ? b->rs_buf : nullptr;
+  b->g.rs_up = on ? b->rs_buf + N * RN_RS_HIST : nullptr;
+  b->g.rs_dn = on ? b->rs_buf + N * (RN_RS_HIST + RN_FRAME_SIZE) : nullptr;
+  b->g.rs_Ls = table ? b->rate_map : nullptr;
+}
+// [N][RN_RS_HIST] histories (zero), then the [N][480] planes rs_up and rs_dn (the 48 kHz frames between the filters and the bodies of
+// K0 / K3), on first use; the zeroing is ordered on st
+int rs_alloc(RNNoiseBatch *b, hipStream_t st) {
+  if (b->rs_buf) return 0;
+  const size_t N = b->n, bytes = N * RN_RS_HIST * sizeof(float);
+  HIP_OK(hipMalloc((void **)&b->rs_buf, bytes + 2 * N * RN_FRAME_SIZE * sizeof(float)));
+  HIP_OK(hipMemsetAsync(b->rs_buf, 0, bytes, st));
+  return 0;
+}
+bool rate_divisor_ok(int v, int Lb) { return (v == 1 || v == 2 || v == 3 || v == 6) && v >= Lb; }
+}  // namespace
+
 extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
   if (!b || (hz != 48000 && hz != 24000 && hz != 16000 && hz != 8000)) return -1;
   const int old = b->pcm_rate;
-  if (hz == old) return old;
+  if (hz == old && !b->g.rs_Ls) return old;  // (a rate table is dropped by every call: the rows are redefined)
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset: nothing of the old rate is in flight)
-  // [N][RN_RS_HIST] histories, then the [N][480] planes rs_up and rs_dn (the 48 kHz frames between the filters and the bodies of K0 / K3)
-  const size_t N = b->n, bytes = N * RN_RS_HIST * sizeof(float);
-  if (hz != 48000 && !b->rs_buf) HIP_OK(hipMalloc((void **)&b->rs_buf, bytes + 2 * N * RN_FRAME_SIZE * sizeof(float)));
-  if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, bytes));
+  if (hz != 48000 && rs_alloc(b, nullptr)) return -1;
+  if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float)));
   HIP_OK(hipDeviceSynchronize());
   b->pcm_rate = hz;
-  b->g.rs_L = hz == 48000 ? 0 : 48000 / hz;
-  b->g.rs_hist = hz == 48000 ? nullptr : b->rs_buf;
-  b->g.rs_up = hz == 48000 ? nullptr : b->rs_buf + N * RN_RS_HIST;
-  b->g.rs_dn = hz == 48000 ? nullptr : b->rs_buf + N * (RN_RS_HIST + RN_FRAME_SIZE);
+  rs_point(b, false);
   return old;
+}
+
+// ---- per-stream rates (include/rnnoise_amd.h) ----
+// The table lives in rate_map from the first set on; while one is set the batch runs its resampling launches at 48 kHz too (rs_L = 1),
+// and K0 / K3 and the snapshot kernels take each stream's divisor from it (rn_dev.h: rn_stream_L).
+extern "C" int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned char *rates) {
+  if (!b) return -1;
+  const int Lb = 48000 / b->pcm_rate;
+  if (rates)
+    for (int s = 0; s < b->n; s++)
+      if (!rate_divisor_ok(rates[s], Lb)) return -1;
+  if (!rates && !b->g.rs_Ls) return 0;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_stream_models: a call in flight keeps what it was launched with)
+  const size_t N = b->n;
+  std::vector<uint8_t> cur(N, (uint8_t)Lb);
+  if (b->g.rs_Ls) {
+    HIP_OK(hipMemcpy(cur.data(), b->rate_map, N, hipMemcpyDeviceToHost));
+    for (auto &v : cur)
+      if (!rate_divisor_ok(v, Lb)) v = (uint8_t)Lb;  // (what the kernels read an unchecked entry of the device setter as)
+  }
+  if (rs_alloc(b, nullptr)) return -1;
+  if (rates && !b->rate_map) HIP_OK(hipMalloc((void **)&b->rate_map, N));
+  // the history of every stream whose divisor changes restarts from zero: one memset per run of such streams
+  for (size_t s = 0; s < N;) {
+    if (cur[s] == (rates ? rates[s] : Lb)) {
+      s++;
+      continue;
+    }
+    size_t e = s + 1;
+    while (e < N && cur[e] != (rates ? rates[e] : Lb)) e++;
+    HIP_OK(hipMemsetAsync(b->rs_buf + s * RN_RS_HIST, 0, (e - s) * RN_RS_HIST * sizeof(float), nullptr));
+    s = e;
+  }
+  if (rates) HIP_OK(hipMemcpy(b->rate_map, rates, N, hipMemcpyHostToDevice));
+  HIP_OK(hipDeviceSynchronize());
+  rs_point(b, rates != nullptr);
+  return 0;
+}
+
+extern "C" int rnnoise_batch_set_stream_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream) {
+  if (!b || !d_rates) return -1;
+  ON_DEVICE(b->device);
+  // a copy, not a kernel: ordered on the caller's stream between its calls; the kernels read an entry that names no rate of this
+  // batch as the batch's own.  Histories are the caller's to reset (include/rnnoise_amd.h).
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (rs_alloc(b, st)) return -1;
+  if (!b->rate_map) HIP_OK(hipMalloc((void **)&b->rate_map, (size_t)b->n));
+  if (!b->g.rs_Ls) rs_point(b, true);
+  HIP_OK(hipMemcpyAsync(b->rate_map, d_rates, (size_t)b->n, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates) {
+  if (!b || !rates) return -1;
+  const int Lb = 48000 / b->pcm_rate;
+  if (!b->g.rs_Ls) {
+    memset(rates, Lb, (size_t)b->n);
+    return 0;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(rates, b->rate_map, (size_t)b->n, hipMemcpyDeviceToHost));
+  for (int s = 0; s < b->n; s++)
+    if (!rate_divisor_ok(rates[s], Lb)) rates[s] = (unsigned char)Lb;  // (as the kernels read it)
+  return 0;
 }
 
 extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
@@ -461,7 +548,8 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   const RnSchedule sched = rn_schedule(rn_knobs(), n_frames, b->schedule);
   const bool pipelined = sched.pipelined, side_k1 = sched.side_k1;
   const bool whole = b->g.n_streams == b->g.n_stride && (size_t)b->g.n_streams * RN_GRU * 4 < (1ull << 32);
-  RnStepShape shape{(int)N, whole && !listed, b->cus, b->nn_path, pipelined, b->per_stream, b->g.rs_L != 0};
+  RnStepShape shape{(int)N, whole && !listed, b->cus, b->nn_path, pipelined, b->per_stream,
+                    rn_shape_low_rate(b->pcm_rate, b->g.rs_Ls != nullptr)};
   shape.listed = listed;
   const RnPlan plan = rn_plan(rn_knobs(), shape);
   // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
@@ -627,7 +715,7 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
 
 // The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
 // ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
-// the caller left them.  The masked host calls, and every host call at a PCM rate other than 48 kHz, come here.
+// the caller left them.  The masked host calls, and every host call at a PCM rate other than 48 kHz or with a rate table, come here.
 // A list call (list set: n_rows host int32 entries, checked by the caller) stages the list too, and its buffers have n_rows rows.
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
                          int n_frames, bool s16, const int *list, int n_rows) {
@@ -642,7 +730,8 @@ int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad,
   HIP_OK(hipMalloc((void **)&d, total));
   int rc = -1;
   if (hipMemcpy(d + o_in, in, pcm, hipMemcpyHostToDevice) == hipSuccess &&
-      ((!active && !list) || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&  // (absent rows keep the caller's values)
+      // (absent rows, and the part of a row behind the frame of a stream of a rate table, keep the caller's values)
+      ((!active && !list && !b->g.rs_Ls) || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&
       (!active || hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess) &&
       (!list || hipMemcpy(d + o_list, list, rows * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
       batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,

@@ -59,9 +59,13 @@ struct RnStepShape {
   int nn_path;     // the batch's network path (rnnoise_batch_set_nn_path): 0 vector, 1 MFMA, 2 layer-wise
   bool pipelined;  // the step is a frame of a pipelined multi-frame call (rn_schedule): other frames' kernels run beside it
   bool per_stream; // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
-  bool low_rate;   // PCM below 48 kHz (rn_dev.h: RnGroupDev::rs_L)
+  bool low_rate;   // PCM below 48 kHz, or a per-stream rate table (rn_shape_low_rate; rn_dev.h: RnGroupDev::rs_L, ::rs_Ls)
   bool listed = false;  // a stream-list call (rn_dev.h: RnGroupDev::list): n counts its listed rows, never the batch
 };
+
+// RnStepShape::low_rate of a batch: its calls run the resampling prologue / epilogue -- at a PCM rate below 48 kHz, and at any rate
+// once the batch carries a rate table (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates), whose streams may be at any of them
+static inline bool rn_shape_low_rate(int pcm_rate, bool rate_table) { return pcm_rate != 48000 || rate_table; }
 
 struct RnPlan {
   RnHpForm hp;
@@ -80,7 +84,8 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   // frames/s; at 2,048 the one-wave form is the better one by 6 %).  Rounds 5-6 until then: 5,120 / 3,072.
   // Low-rate rows take the wave-per-stream form at every batch size.  (An upsampling prologue in the lane = stream kernel, one stream
   // after the other per wave, took that kernel from 50 to 61-64 SGPRs in every arrangement tried; the 48 kHz kernels keep their
-  // registers instead.  The cost at large batches: DESIGN.md 4.10, profiles/resample_rate_bench.txt)
+  // registers instead.  The cost at large batches: DESIGN.md 4.10, profiles/resample_rate_bench.txt)  A batch with a rate table
+  // plans the same way: its low-rate streams need the prologue, and one wave serves one stream, so each takes its own L.
   // A list call: the one-wave form at every size (the lane = stream kernel has no list path).
   p.hp = s.listed || s.low_rate || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
   // K1.  From 2,560 streams four streams share a workgroup (rn_analysis_kernel).  6,144 until round 6's last day; since the narrow

@@ -1938,9 +1938,11 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
 // v[-47 L .. -1], the frame's 480 samples and the taps, and forms the 480 / L outputs, lane l those of m = l, l + 64, ...  The body is not
 // compiled a second time and L is a run-time value, so that the epilogue stays inside the registers of the body.
 // Called only for a stream that has this frame (rn_stream_at: RnStreamAt::present).
-__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row) {
+// L: the batch's divisor or, with a rate table, the stream's own (rn_dev.h: rn_stream_L; never 1 here); the caller's rows are
+// g.rs_pitch samples apart and the stream's 480 / L outputs fill the front of its row.
+__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row, int L) {
   void *out = g.rs_out;
-  const int lane = threadIdx.x, L = g.rs_L, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
+  const int lane = threadIdx.x, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
   const float *body = g.rs_dn + (size_t)row * RN_FRAME_SIZE;  // (the body wrote its output row: the caller's row, RnStreamAt::i)
   const float *ht = rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
@@ -1976,9 +1978,9 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
     const float r = (a0 + a1) + (a2 + a3);
     if (out_s16) {  // (the truncating conversion of the 48 kHz calls: synthesis_body)
       const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-      static_cast<short *>(out)[(size_t)row * M + m] = (short)q;
+      static_cast<short *>(out)[(size_t)row * g.rs_pitch + m] = (short)q;
     } else {
-      static_cast<float *>(out)[(size_t)row * M + m] = r;
+      static_cast<float *>(out)[(size_t)row * g.rs_pitch + m] = r;
     }
   }
   // the new history: the frame's last 47 L samples
@@ -1988,25 +1990,38 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
     hist[k] = vs[RN_FRAME_SIZE + k];
   }
 }
+// The divisor the epilogue of this workgroup's stream runs at: 0 = no epilogue (a 48 kHz launch, or an absent stream).  A 48 kHz
+// stream of a rate table (rn_dev.h: RnGroupDev::rs_Ls -- only in a batch whose rows are whole frames) has none either: the body's
+// `out` becomes the caller's buffer again and bit 10 (int16) of parity_arg moves to the body's bit 8.
+__device__ __forceinline__ int rs_divert(const RnGroupDev &g, const RnStreamAt &at, float *&out, int &parity_arg) {
+  if (!(parity_arg & 512) || !at.present) return 0;
+  const int L = rn_stream_L(g, at.s);
+  if (L > 1) return L;
+  out = static_cast<float *>(g.rs_out);
+  parity_arg = (parity_arg & 255) | ((parity_arg & 1024) ? 256 : 0);
+  return 0;
+}
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(RN_K3_WAVES, RN_K3_WAVES)))
 rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg) {
-  const bool rs = parity_arg & 512;
   const RnStreamAt at = rn_stream_at(g, nullptr, 0, parity_arg & 255, prev_arg);
-  synthesis_body<true>(g, tb, out, parity_arg, at);
-  if (rs && at.present) {
+  float *body_out = out;
+  const int rs_L = rs_divert(g, at, body_out, parity_arg);
+  synthesis_body<true>(g, tb, body_out, parity_arg, at);
+  if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L);
   }
 }
 // the launch groups of the one-frame API and small batches (dispatch.h: RN_K3_FEW)
 extern "C" __global__ void __launch_bounds__(WAVE)
 rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg, RnRows rows) {
-  const bool rs = parity_arg & 512;  // (never set for a row list)
   const RnStreamAt at = rn_stream_at(g, &rows, 0, parity_arg & 255, prev_arg);
-  synthesis_body<false>(g, tb, out, parity_arg, at);
-  if (rs && at.present) {
+  float *body_out = out;
+  const int rs_L = rs_divert(g, at, body_out, parity_arg);  // (bit 9 is never set for a row list)
+  synthesis_body<false>(g, tb, body_out, parity_arg, at);
+  if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L);
   }
 }
 

@@ -19,7 +19,8 @@
 // u[L q + p] = sum_{k<48} hup[p][k] x[q - k], four chains over k mod 4 combined as (a0 + a1) + (a2 + a3).  A prologue of both K0
 // kernels: one wave forms one stream's 480 samples at 48 kHz into the stream's row of RnGroupDev::rs_up, from its row staged in LDS
 // -- xs[0 .. 46] the history x[-47 .. -1], xs[47 ..] the frame's 480 / L samples -- and the taps staged beside it (hu: [L][48]);
-// lane l forms outputs l, l + 64, ...  (rn_hp_one_kernel only: rn_launch_hp.)  The kernel's 48 kHz float body then reads rs_up as its input: the body is not compiled a
+// lane l forms outputs l, l + 64, ...  (rn_hp_one_kernel only: rn_launch_hp.)  L is the batch's, or the stream's own where the batch
+// has a rate table (rn_dev.h: rn_stream_L) -- one wave serves one stream, so it stays wave-uniform.  The kernel's 48 kHz float body then reads rs_up as its input: the body is not compiled a
 // second time (a second copy of it, even with nothing else changed, took 6 SGPRs more than the kernel's budget), and L is a run-time
 // value with four accumulators per lane, so that the prologue fits inside the registers of the body.
 // ---------------------------------------------------------------------------------------------
@@ -35,6 +36,8 @@ __device__ __forceinline__ void rs_wsync() {
 }
 template <bool IN_S16>
 __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, int row, float *xs, int L) {
+  // (M: the stream's samples per frame; its row starts at row * rs_pitch -- M of the batch's rate, which a stream of a rate table may
+  //  fill only in part: rn_dev.h RnGroupDev::rs_Ls)
   const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
   float *hu = xs + RN_RS_XS;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
@@ -44,7 +47,7 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
   float rx[NX], rt[NT];
 #pragma unroll
   for (int i = 0; i < NX; i++) {
-    const size_t q = (size_t)row * M + min(lane + WAVE * i, M - 1);  // (row: the caller's row of stream s, RnStreamAt::i)
+    const size_t q = (size_t)row * g.rs_pitch + min(lane + WAVE * i, M - 1);  // (row: the caller's row of stream s, RnStreamAt::i)
     rx[i] = IN_S16 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
   }
   const float *ht = rs_up_taps(L);
@@ -446,11 +449,16 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
   if (!at.present) return;  // an absent stream writes nothing
   const float *rs_row = nullptr;
   if (in_s16 & 2) {  // low-rate rows (never a row list): upsampled into RnGroupDev::rs_up, staged in the body's LDS before the body uses it
-    if (in_s16 & 1) rs_up_stream<true>(g, in, s, at.i, L.pb, g.rs_L);
-    else rs_up_stream<false>(g, in, s, at.i, L.pb, g.rs_L);
-    __syncthreads();
-    rs_row = g.rs_up + (size_t)s * RN_FRAME_SIZE;
-    in_s16 = 0;
+    const int rs_L = rn_stream_L(g, s);  // (the batch's divisor, or the stream's own from the rate table)
+    if (rs_L > 1) {
+      if (in_s16 & 1) rs_up_stream<true>(g, in, s, at.i, L.pb, rs_L);
+      else rs_up_stream<false>(g, in, s, at.i, L.pb, rs_L);
+      __syncthreads();
+      rs_row = g.rs_up + (size_t)s * RN_FRAME_SIZE;
+      in_s16 = 0;
+    } else {
+      in_s16 &= 1;  // a 48 kHz stream of a rate table: its row is a whole frame (rows are 480 apart), read in place below
+    }
   }
   // the caller's row i (rn_dev.h: RnStreamAt::i -- stream s's own row except in a list call)
   const void *in_row = at.listed ? static_cast<const void *>(at.io + RN_ROW_IN)

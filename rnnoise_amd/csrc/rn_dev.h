@@ -171,6 +171,14 @@ struct RnGroupDev {
   float *rs_up, *rs_dn;        // [N][480] each: the frame at 48 kHz as K0 formed it from the low-rate row / as K3's body formed it
   void *rs_out;                // K3 only: the caller's low-rate output (float or int16)
   int rs_L;
+  // Per-stream PCM rates (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates).  Null rs_Ls: every stream runs at the batch's rate
+  // (every launch is today's).  Set, rs_L is the BATCH's divisor Lb (1 at 48 kHz: the batch then has rs_hist / rs_up / rs_dn too) and
+  // stream s runs at divisor rs_Ls[s] -- anything that is not 1, 2, 3 or 6, or that is below Lb, reads as Lb (rn_stream_L).  Indexed by
+  // batch stream, also in a list call.  rs_pitch: samples between the caller's PCM rows, 480 / Lb, set whenever rs_L is; a stream uses
+  // the first 480 / L_s samples of its row.  L_s = 1 (only where Lb = 1, so its row is a whole 48 kHz frame): K0's body reads the row
+  // and K3's body writes it in place, no filter runs and the stream's history is not touched.
+  const uint8_t *rs_Ls;        // [N] or null
+  int rs_pitch;
   // Per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model).  Null model_of: every row belongs to the launch (a batch with
   // one model).  Set, the network launch of slot model_sel owns row s when (model_of[s] < n_models ? model_of[s] : 0) == model_sel
   // (rn_owns): only owned rows get stores -- state, state images, gains, vad -- and a workgroup with no owned row returns at once.
@@ -302,6 +310,13 @@ __device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, int i
     p += g.call_frame;
   }
   return p;
+}
+// PCM-rate divisor of stream s in a launch with resampling on (g.rs_L != 0; rn_dev.h: RnGroupDev::rs_Ls).  s is the workgroup's one
+// stream: the result is wave-uniform
+__device__ __forceinline__ int rn_stream_L(const RnGroupDev &g, int s) {
+  if (!g.rs_Ls) return g.rs_L;
+  const int v = __builtin_amdgcn_readfirstlane((int)*(__attribute__((address_space(1))) const uint8_t *)(g.rs_Ls + s));
+  return ((v == 1 || v == 2 || v == 3 || v == 6) && v >= g.rs_L) ? v : g.rs_L;
 }
 // Whether the network launch of g.model_sel owns stream s (rn_dev.h: RnGroupDev::model_of); an entry naming no slot reads as slot 0
 __device__ __forceinline__ bool rn_owns(const RnGroupDev &g, int s) {

@@ -182,6 +182,10 @@ struct RNNoiseBatch {
   // RnGroupDev::rs_hist), allocated the first time the rate leaves 48 kHz; g.rs_hist / g.rs_L are set only while it is away
   int pcm_rate = 48000;
   float *rs_buf = nullptr;
+  // per-stream rates (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates): rate_map, the [N] divisor bytes K0 / K3 and the snapshot
+  // kernels read (rn_dev.h: RnGroupDev::rs_Ls) -- allocated by the first table; g.rs_Ls points at it while a table is set, and g.rs_L /
+  // g.rs_hist are then set at 48 kHz too (batch.cpp: rs_point)
+  uint8_t *rate_map = nullptr;
   // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
   // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of) -- allocated by the first
   // add_model, like rs_buf by the first rate change; g.model_of / g.n_models are set from then on

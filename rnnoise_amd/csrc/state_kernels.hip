@@ -58,6 +58,10 @@ __device__ __forceinline__ void latest_slots(const int *__restrict__ phase, int 
   last = (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
 }
 
+// the divisor stream s's resampler history belongs to: the batch's (1 at 48 kHz), or the stream's own where the batch has a rate table
+// (rn_dev.h: RnGroupDev::rs_Ls)
+__device__ __forceinline__ int stream_L(const RnGroupDev &g, int s) { return g.rs_L ? rn_stream_L(g, s) : 1; }
+
 // snap[row][RN_SNAP_FLOATS] <- stream list[row] (row, without a list); an entry outside the view leaves an empty record (magic 0)
 __device__ __forceinline__ void gather_rows(const RnGroupDev &g, float *__restrict__ snap, int newest_arg, int last_arg,
                                             const int *__restrict__ list, const int *__restrict__ phase, int rows) {
@@ -91,7 +95,7 @@ __device__ __forceinline__ void gather_rows(const RnGroupDev &g, float *__restri
     move_run(f + RN_OFF_DELAYED_EX, slot3(g.spec_E, last) + s * 96, 96);
     if (t >= 64 && t < 70) {  // the header: magic, L, counter, three reserved zeros
       const int w = t - 64;
-      const int v = w == 0 ? RN_SNAP_MAGIC : w == 1 ? (g.rs_L ? g.rs_L : 1) : w == 2 ? (g.gate_c ? g.gate_c[s] : RN_CTL_NONE) : 0;
+      const int v = w == 0 ? RN_SNAP_MAGIC : w == 1 ? stream_L(g, sl) : w == 2 ? (g.gate_c ? g.gate_c[s] : RN_CTL_NONE) : 0;
       f[RN_SNAP_OFF_MAGIC + w] = __int_as_float(v);
     }
     if (g.rs_hist) move_run(f + RN_SNAP_OFF_HIST, g.rs_hist + s * RN_RS_HIST, RN_RS_HIST);
@@ -100,7 +104,7 @@ __device__ __forceinline__ void gather_rows(const RnGroupDev &g, float *__restri
 }
 
 // stream list[row] <- snap[row][RN_SNAP_FLOATS]: what the one-state form below writes, at the stream's own phase, then the
-// resampler history (when the record's L is the view's; zeros otherwise) and the gate counter (when the view has one).  A row with
+// resampler history (when the record's L is the stream's current one; zeros otherwise) and the gate counter (when the view has one).  A row with
 // another magic word, or an entry outside the view, touches nothing.
 __device__ __forceinline__ void scatter_rows(const RnGroupDev &g, const float *__restrict__ snap, int newest_arg, int last_arg,
                                              const int *__restrict__ list, const int *__restrict__ phase, int rows) {
@@ -150,7 +154,7 @@ __device__ __forceinline__ void scatter_rows(const RnGroupDev &g, const float *_
     move_run(slot3(g.spec_P, last) + s * RN_SPEC_STRIDE, f + RN_OFF_DELAYED_P, RN_OFF_DELAYED_EX - RN_OFF_DELAYED_P);
     move_run(slot3(g.spec_E, last) + s * 96, f + RN_OFF_DELAYED_EX, 96);
     if (g.rs_hist) {
-      if (__float_as_int(f[RN_SNAP_OFF_L]) == (g.rs_L ? g.rs_L : 1)) move_run(g.rs_hist + s * RN_RS_HIST, f + RN_SNAP_OFF_HIST, RN_RS_HIST);
+      if (__float_as_int(f[RN_SNAP_OFF_L]) == stream_L(g, sl)) move_run(g.rs_hist + s * RN_RS_HIST, f + RN_SNAP_OFF_HIST, RN_RS_HIST);
       else zero_run(g.rs_hist + s * RN_RS_HIST, RN_RS_HIST);
     }
     if (g.gate_c && t == 64) g.gate_c[s] = min(max(__float_as_int(f[RN_SNAP_OFF_GATE]), 0), RN_CTL_NONE);

@@ -177,6 +177,13 @@ class RNNoiseOp:
         # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.set_stream_models_device(slots.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
 
+    def set_stream_rates(self, hz):
+        """the PCM rate of every stream in Hz (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates): a sequence / array of N values
+        out of 48000, 24000, 16000, 8000, none above the op's `rate`, or None to drop the table.  Rows of the PCM tensors keep the
+        op's frame length; stream s reads and writes the first 480 * hz[s] // 48000 samples of its row and leaves the rest alone.
+        Synchronous; ValueError on any other value."""
+        self.batch.set_stream_rates(hz)
+
     def set_stream_controls(self, limit_db=None, vad_threshold=0.0, hold_frames=0):
         """per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): an attenuation limit in dB (a
         floor on the band gains; None / inf: none), a VAD gate threshold in [0, 1] (0: no gate) and the frames the gate stays open
