@@ -188,6 +188,49 @@ RNNOISE_EXPORT int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigne
 RNNOISE_EXPORT int rnnoise_batch_set_stream_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream);
 RNNOISE_EXPORT int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates);
 
+/* Per-stream G.711: a PCM format per stream.  formats[n_streams] says what the rows of every `_s16` call hold for each stream:
+ * RNNOISE_AMD_PCM_LINEAR int16 samples (the meaning of those calls without a table), RNNOISE_AMD_PCM_ULAW or RNNOISE_AMD_PCM_ALAW one
+ * G.711 byte per sample.  The table describes every _s16 call form -- lock-step, masked and list; device and host --; the float calls
+ * ignore it.  The ROW PITCH does not change: rows stay 480 / Lb int16 (960 / Lb bytes) apart, Lb the batch's divisor.  A companded
+ * stream with M = 480 / L_s samples per frame (L_s from the rate table, else Lb) uses the FIRST M bytes of its row; the rest of its `in`
+ * row is not read and the rest of its `out` row is not written (the caller's bytes stay) -- the rate table's rule applied to bytes, so
+ * that an 8 kHz G.711 leg (80 bytes) sits beside a 48 kHz linear leg (960 bytes) in one buffer.  Any format goes with any rate.
+ * The codec is the 14-bit mu-law / 13-bit A-law form that rnnoise_amd/g711.py states, equal for every input to CPython's audioop at
+ * width 2.  >> is an arithmetic shift, x the int16 sample, b the byte:
+ *   mu-law  encode  p = x >> 2; neg = p < 0; p = min((neg ? -p : p) + 33, 8191); seg = floor(log2(p)) - 5;
+ *                   b = ((seg << 4) | ((p >> (seg + 1)) & 15)) ^ (neg ? 0x7F : 0xFF)
+ *           decode  u = ~b & 0xFF; t = (((u & 15) << 3) + 132) << ((u >> 4) & 7); x = (u & 0x80) ? 132 - t : t - 132
+ *   A-law   encode  i = x >> 3; neg = i < 0; if (neg) i = ~i; seg = i < 32 ? 0 : floor(log2(i)) - 4;
+ *                   m = seg < 2 ? (i >> 1) & 15 : (i >> seg) & 15; b = ((seg << 4) | m) ^ (neg ? 0x55 : 0xD5)
+ *           decode  a = b ^ 0x55; t = (a & 15) << 4; seg = (a >> 4) & 7; t = seg == 0 ? t + 8 : (t + 0x108) << (seg - 1);
+ *                   x = (a & 0x80) ? t : -t
+ * Result, bit for bit: a companded stream's vad, gains and complete state (snapshot) are those of the same stream fed decode(bytes)
+ * through the same _s16 call on a batch without a format table, and its output bytes are encode() of that call's int16 output (the
+ * truncating conversion of the _s16 calls, then the code).  Every other stream of the batch is unchanged in every bit.  This holds in
+ * every call form, at every rate, with masks, lists, model slots and controls, and across rnnoise_batch_reset_streams[_device] and
+ * snapshot save / load.
+ * rnnoise_batch_set_stream_formats (host array): synchronous, like rnnoise_batch_set_stream_models; -1 and no change if any entry is
+ * above 2.  formats == NULL drops the table: the batch then launches exactly what a batch that never had one launches.
+ * rnnoise_batch_set_stream_formats_device (n_streams bytes in the batch's device memory): a copy ordered on hip_stream (no kernel, no
+ * host synchronisation; the first table of a batch allocates its n_streams bytes).  Entries are not checked: the kernel that reads one
+ * takes anything that is not 1 or 2 as linear.
+ * rnnoise_batch_stream_formats reads the table back as the kernels read it (synchronous; zeros when there is none).
+ * A format is configuration, not state: it has no history, nothing is zeroed when it changes, and it does not appear in snapshots.
+ * rnnoise_batch_reset, reset_streams[_device], import_state, load_streams, set_pcm_rate, set_stream_rates, set_nn_path and
+ * set_schedule leave the table alone (set_pcm_rate too: no entry can become invalid at another rate).  A slot recycled for a leg of
+ * another codec: set_stream_rates_device + set_stream_formats_device + reset_streams_device on one stream.
+ * Host-buffer _s16 calls on a batch with a table take the staged convenience path, as with a rate table.
+ * rnnoise_batch_train_features* is a float call and ignores the table.  While a table is set the _s16 calls run K0 one wave per
+ * stream at every batch size, as with a rate table -- at 48 kHz without a rate table that replaces the lane-per-stream K0 of batches
+ * above 2,048 streams, whose cost has not been measured yet; float calls launch what they launched before.
+ * 0 / -1; a NULL batch or buffer returns -1 without touching the device.  The per-frame API of rnnoise.h stays linear float. */
+#define RNNOISE_AMD_PCM_LINEAR 0   /* int16: the _s16 calls without a table */
+#define RNNOISE_AMD_PCM_ULAW   1
+#define RNNOISE_AMD_PCM_ALAW   2
+RNNOISE_EXPORT int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsigned char *formats);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *formats);
+
 /* Several models in one batch: every stream runs with the model of its SLOT.  Slot 0 is the model the batch was created with;
  * rnnoise_batch_add_model puts another one into the next free slot (1 .. RNNOISE_AMD_MAX_MODELS - 1) and returns that slot: -1 on a
  * NULL batch or model, a full table, or a model that cannot be put on the batch's device.  Synchronous.  The model must outlive the

@@ -59,6 +59,7 @@ EXPORTS = [
     "rnnoise_batch_set_stream_controls", "rnnoise_batch_set_stream_controls_device", "rnnoise_batch_stream_controls",
     "rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device", "rnnoise_batch_save_streams", "rnnoise_batch_load_streams",
     "rnnoise_batch_set_stream_rates", "rnnoise_batch_set_stream_rates_device", "rnnoise_batch_stream_rates",
+    "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
 ]
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
@@ -185,6 +186,9 @@ def _load(path, debug):
         L.rnnoise_batch_set_stream_rates.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_rates_device.argtypes = [vp, vp, vp]
         L.rnnoise_batch_stream_rates.argtypes = [vp, up]
+        L.rnnoise_batch_set_stream_formats.argtypes = [vp, up]
+        L.rnnoise_batch_set_stream_formats_device.argtypes = [vp, vp, vp]
+        L.rnnoise_batch_stream_formats.argtypes = [vp, up]
         L.rnnoise_batch_add_model.argtypes = [vp, vp]
         L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
@@ -379,6 +383,35 @@ class Batch:
         if self._L.rnnoise_batch_stream_rates(self.h, L.ctypes.data_as(C.POINTER(C.c_ubyte))):
             raise RuntimeError("rnnoise_batch_stream_rates failed")
         return (48000 // L.astype(np.int32)).astype(np.int32)
+
+    def set_stream_formats(self, formats):
+        """the PCM format of every stream's rows in the int16 calls (rnnoise_batch_set_stream_formats): (N,) names out of "s16",
+        "ulaw", "alaw" or codes 0, 1, 2 (rnnoise_amd.g711), or None to drop the table.  A companded stream's G.711 bytes fill the
+        first 480 * rate // 48000 BYTES of its int16 row.  Synchronous; ValueError (and nothing changes) on anything else."""
+        if formats is None:
+            if self._L.rnnoise_batch_set_stream_formats(self.h, None):
+                raise RuntimeError("rnnoise_batch_set_stream_formats failed")
+            return
+        from . import g711
+        if isinstance(formats, np.ndarray) and formats.dtype.kind in "iu":
+            formats = formats.reshape(-1).tolist()
+        codes = np.array([g711.code(f) for f in formats], np.uint8)
+        assert codes.size == self.n
+        if self._L.rnnoise_batch_set_stream_formats(self.h, codes.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise ValueError("rnnoise_batch_set_stream_formats failed")
+
+    def set_stream_formats_device(self, d_formats: int, stream: int = 0):
+        """the same from N bytes of device memory holding the CODES (0 s16, 1 ulaw, 2 alaw), a copy ordered on `stream`; any other
+        byte reads as s16.  Nothing else changes: a stream that changes codec mid-run is the caller's to reset."""
+        if self._L.rnnoise_batch_set_stream_formats_device(self.h, d_formats or None, stream or None):
+            raise RuntimeError("rnnoise_batch_set_stream_formats_device failed")
+
+    def stream_formats(self) -> np.ndarray:
+        """the format code of every stream as the kernels read it, (N,) uint8 (synchronous; zeros without a table)"""
+        f = np.empty(self.n, np.uint8)
+        if self._L.rnnoise_batch_stream_formats(self.h, f.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise RuntimeError("rnnoise_batch_stream_formats failed")
+        return f
 
     def process(self, pcm: np.ndarray, want_gains: bool = True):
         """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32])."""

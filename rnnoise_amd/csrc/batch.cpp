@@ -96,6 +96,7 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
     v.gate_c += f;
   }
   if (v.rs_Ls) v.rs_Ls += f;
+  if (v.pcm_fmt) v.pcm_fmt += f;
   if (v.rs_hist) {
     v.rs_hist += RN_RS_HIST * f;
     v.rs_up += RN_FRAME_SIZE * f;
@@ -221,6 +222,7 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->arena) hipFree(b->arena);
   if (b->rs_buf) hipFree(b->rs_buf);
   if (b->rate_map) hipFree(b->rate_map);
+  if (b->fmt_map) hipFree(b->fmt_map);
   if (b->model_map) hipFree(b->model_map);
   if (b->ctl_buf) hipFree(b->ctl_buf);
   if (b->debug_buf) hipFree(b->debug_buf);
@@ -360,6 +362,50 @@ extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates)
 }
 
 extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
+
+// ---- per-stream PCM formats (include/rnnoise_amd.h) ----
+// The table lives in fmt_map from the first set on; while one is set (g.pcm_fmt) K0 expands and K3 compresses the rows of the
+// companded streams in every int16 call (rn_dev.h: rn_stream_fmt), and those calls plan K0 one wave per stream (dispatch.h).  It is
+// configuration: nothing is zeroed when it changes, and nothing but these two setters and the batch's end touches it.
+extern "C" int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsigned char *formats) {
+  if (!b) return -1;
+  if (formats)
+    for (int s = 0; s < b->n; s++)
+      if (formats[s] > RNNOISE_AMD_PCM_ALAW) return -1;
+  if (!formats && !b->g.pcm_fmt) return 0;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_stream_models: a call in flight keeps what it was launched with)
+  if (formats) {
+    if (!b->fmt_map) HIP_OK(hipMalloc((void **)&b->fmt_map, (size_t)b->n));
+    HIP_OK(hipMemcpy(b->fmt_map, formats, (size_t)b->n, hipMemcpyHostToDevice));
+  }
+  b->g.pcm_fmt = formats ? b->fmt_map : nullptr;
+  return 0;
+}
+
+extern "C" int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream) {
+  if (!b || !d_formats) return -1;
+  ON_DEVICE(b->device);
+  // a copy, not a kernel: ordered on the caller's stream between its calls; the kernels read a byte that names no law as int16 rows
+  if (!b->fmt_map) HIP_OK(hipMalloc((void **)&b->fmt_map, (size_t)b->n));
+  b->g.pcm_fmt = b->fmt_map;
+  HIP_OK(hipMemcpyAsync(b->fmt_map, d_formats, (size_t)b->n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
+  return 0;
+}
+
+extern "C" int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *formats) {
+  if (!b || !formats) return -1;
+  if (!b->g.pcm_fmt) {
+    memset(formats, 0, (size_t)b->n);
+    return 0;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(formats, b->fmt_map, (size_t)b->n, hipMemcpyDeviceToHost));
+  for (int s = 0; s < b->n; s++)
+    if (formats[s] > RNNOISE_AMD_PCM_ALAW) formats[s] = RNNOISE_AMD_PCM_LINEAR;  // (as the kernels read it)
+  return 0;
+}
 
 // ---- per-stream models (include/rnnoise_amd.h) ----
 // The network of every step is launched once per slot (batch_process_device_impl); the launch of slot k owns the streams the map puts
@@ -551,6 +597,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   RnStepShape shape{(int)N, whole && !listed, b->cus, b->nn_path, pipelined, b->per_stream,
                     rn_shape_low_rate(b->pcm_rate, b->g.rs_Ls != nullptr)};
   shape.listed = listed;
+  shape.companded = s16 && b->g.pcm_fmt != nullptr;  // (float calls never look at the format table)
   const RnPlan plan = rn_plan(rn_knobs(), shape);
   // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
   // made it: normal for torch's)
@@ -715,7 +762,8 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
 
 // The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
 // ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
-// the caller left them.  The masked host calls, and every host call at a PCM rate other than 48 kHz or with a rate table, come here.
+// the caller left them.  The masked host calls, every host call at a PCM rate other than 48 kHz or with a rate table, and the int16
+// host calls of a batch with a format table come here.
 // A list call (list set: n_rows host int32 entries, checked by the caller) stages the list too, and its buffers have n_rows rows.
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
                          int n_frames, bool s16, const int *list, int n_rows) {
@@ -730,8 +778,9 @@ int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad,
   HIP_OK(hipMalloc((void **)&d, total));
   int rc = -1;
   if (hipMemcpy(d + o_in, in, pcm, hipMemcpyHostToDevice) == hipSuccess &&
-      // (absent rows, and the part of a row behind the frame of a stream of a rate table, keep the caller's values)
-      ((!active && !list && !b->g.rs_Ls) || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&
+      // (absent rows, and the part of a row behind the frame of a stream of a rate table or behind a companded stream's bytes, keep
+      //  the caller's values)
+      ((!active && !list && !b->g.rs_Ls && !(s16 && b->g.pcm_fmt)) || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&
       (!active || hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess) &&
       (!list || hipMemcpy(d + o_list, list, rows * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
       batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,

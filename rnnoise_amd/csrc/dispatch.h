@@ -61,6 +61,7 @@ struct RnStepShape {
   bool per_stream; // per-stream frame phase (rn_dev.h: RnGroupDev::phase)
   bool low_rate;   // PCM below 48 kHz, or a per-stream rate table (rn_shape_low_rate; rn_dev.h: RnGroupDev::rs_L, ::rs_Ls)
   bool listed = false;  // a stream-list call (rn_dev.h: RnGroupDev::list): n counts its listed rows, never the batch
+  bool companded = false;  // an int16 call of a batch with a per-stream format table (rn_dev.h: RnGroupDev::pcm_fmt)
 };
 
 // RnStepShape::low_rate of a batch: its calls run the resampling prologue / epilogue -- at a PCM rate below 48 kHz, and at any rate
@@ -87,7 +88,10 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   // registers instead.  The cost at large batches: DESIGN.md 4.10, profiles/resample_rate_bench.txt)  A batch with a rate table
   // plans the same way: its low-rate streams need the prologue, and one wave serves one stream, so each takes its own L.
   // A list call: the one-wave form at every size (the lane = stream kernel has no list path).
-  p.hp = s.listed || s.low_rate || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
+  // An int16 call of a batch with a format table (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats): the one-wave form at every
+  // size too -- one wave serves one stream, so the row's format is wave-uniform and a wave reads either bytes or int16, and the lane =
+  // stream kernel, where 64 neighbours of different formats would share a wave, keeps its registers.
+  p.hp = s.listed || s.low_rate || s.companded || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
   // K1.  From 2,560 streams four streams share a workgroup (rn_analysis_kernel).  6,144 until round 6's last day; since the narrow
   // phases and the follower are shared by the four streams of a workgroup (round 6) that form is ahead from 3,072 streams -- 23.3
   // against 20.8 M frames/s there, 26.4 against 24.5 at 4,096 (one frame per call 0.201 against 0.231 ms), 27.8 against 26.0 at

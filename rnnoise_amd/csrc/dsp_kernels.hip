@@ -1716,7 +1716,8 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
                                                const RnStreamAt &at) {
   // bit 8 of parity_arg: `out` holds int16 samples, written with the truncating conversion of the reference's only caller
   // (examples/rnnoise_demo.c:58: tmp[i] = x[i], float -> short as x86 compiles it: cvttss2si to 32 bits -- "integer
-  // indefinite" 0x80000000 when out of range or NaN -- then the low 16 bits)
+  // indefinite" 0x80000000 when out of range or NaN -- then the low 16 bits).  Bits 11-12 (rn_fmt_arg, only beside bit 8): the row
+  // is a companded stream's -- that int16 value goes out as one G.711 byte of that law, at byte n of the row (g711.h)
   const bool listed = at.listed;  // a launch group of the one-frame API (rn_dev.h: RnRows)
   const int parity = at.spec, prev = at.prev;
   // per-stream frame phase (rn_dev.h: RnGroupDev::phase): the call's last frame advances the stream's phase (every kernel of the call
@@ -1728,6 +1729,7 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     return;
   }
   const bool out_s16 = !listed && (parity_arg & 256);
+  const int out_fmt = (parity_arg >> 11) & 3;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   SynthLds &L = *reinterpret_cast<SynthLds *>(smem_raw);
   const int s = at.s, lane = (int)threadIdx.x, pos = fft_pos(lane);
@@ -1914,7 +1916,8 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       const float r = v + smv[b];
       if (out_s16) {
         const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-        reinterpret_cast<short *>(out)[(size_t)at.i * RN_FRAME_SIZE + n] = (short)q;
+        if (out_fmt) reinterpret_cast<uint8_t *>(out)[(size_t)at.i * RN_FRAME_SIZE * sizeof(short) + n] = (uint8_t)rn_g711_encode(out_fmt, (short)q);
+        else reinterpret_cast<short *>(out)[(size_t)at.i * RN_FRAME_SIZE + n] = (short)q;
       } else {
         o[n] = r;
       }
@@ -1940,7 +1943,8 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
 // Called only for a stream that has this frame (rn_stream_at: RnStreamAt::present).
 // L: the batch's divisor or, with a rate table, the stream's own (rn_dev.h: rn_stream_L; never 1 here); the caller's rows are
 // g.rs_pitch samples apart and the stream's 480 / L outputs fill the front of its row.
-__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row, int L) {
+// fmt: a companded stream's law (bits 11-12 of parity_arg: rn_fmt_arg), its int16 values going out as the first 480 / L bytes of the row.
+__device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row, int L, int fmt) {
   void *out = g.rs_out;
   const int lane = threadIdx.x, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
@@ -1978,7 +1982,8 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
     const float r = (a0 + a1) + (a2 + a3);
     if (out_s16) {  // (the truncating conversion of the 48 kHz calls: synthesis_body)
       const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-      static_cast<short *>(out)[(size_t)row * g.rs_pitch + m] = (short)q;
+      if (fmt) static_cast<uint8_t *>(out)[(size_t)row * g.rs_pitch * sizeof(short) + m] = (uint8_t)rn_g711_encode(fmt, (short)q);
+      else static_cast<short *>(out)[(size_t)row * g.rs_pitch + m] = (short)q;
     } else {
       static_cast<float *>(out)[(size_t)row * g.rs_pitch + m] = r;
     }
@@ -2001,15 +2006,22 @@ __device__ __forceinline__ int rs_divert(const RnGroupDev &g, const RnStreamAt &
   parity_arg = (parity_arg & 255) | ((parity_arg & 1024) ? 256 : 0);
   return 0;
 }
+// The PCM format of this workgroup's stream as bits 11-12 of parity_arg (rn_dev.h: RnGroupDev::pcm_fmt; after rs_divert): set only
+// where the launch writes int16 rows (bit 8, or bit 10 beside bit 9) for a stream that has this frame.  Without a table: nothing.
+__device__ __forceinline__ int rn_fmt_arg(const RnGroupDev &g, const RnStreamAt &at, int parity_arg) {
+  if (!g.pcm_fmt || !at.present || !(parity_arg & (256 | 1024))) return parity_arg;
+  return parity_arg | rn_stream_fmt(g, at.s) << 11;
+}
 extern "C" __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(RN_K3_WAVES, RN_K3_WAVES)))
 rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int parity_arg, int prev_arg) {
   const RnStreamAt at = rn_stream_at(g, nullptr, 0, parity_arg & 255, prev_arg);
   float *body_out = out;
   const int rs_L = rs_divert(g, at, body_out, parity_arg);
+  parity_arg = rn_fmt_arg(g, at, parity_arg);
   synthesis_body<true>(g, tb, body_out, parity_arg, at);
   if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L, (parity_arg >> 11) & 3);
   }
 }
 // the launch groups of the one-frame API and small batches (dispatch.h: RN_K3_FEW)
@@ -2018,10 +2030,11 @@ rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, i
   const RnStreamAt at = rn_stream_at(g, &rows, 0, parity_arg & 255, prev_arg);
   float *body_out = out;
   const int rs_L = rs_divert(g, at, body_out, parity_arg);  // (bit 9 is never set for a row list)
+  parity_arg = rn_fmt_arg(g, at, parity_arg);
   synthesis_body<false>(g, tb, body_out, parity_arg, at);
   if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L);
+    rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L, (parity_arg >> 11) & 3);
   }
 }
 

@@ -518,7 +518,7 @@ extern "C" int rnnoise_batch_process(RNNoiseBatch *b, float *out, const float *i
 
 extern "C" int rnnoise_batch_process_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                          int n_frames) {
-  if (b && b->g.rs_L) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, true);
+  if (b && (b->g.rs_L || b->g.pcm_fmt)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, true);  // (or a format table)
   return batch_process_host_impl(b, out, in, vad, gains, n_frames, true);
 }
 

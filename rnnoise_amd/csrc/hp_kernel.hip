@@ -34,8 +34,10 @@ __device__ __forceinline__ void rs_wsync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-template <bool IN_S16>
-__device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, int row, float *xs, int L) {
+// IN: 0 float rows, 1 int16 rows, 2 companded rows (rn_dev.h: RnGroupDev::pcm_fmt) -- G.711 bytes of law `fmt` in the first M bytes
+// of the row, which keeps its int16 pitch; each is expanded to the int16 value the linear path would have read (g711.h)
+template <int IN>
+__device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, int row, float *xs, int L, int fmt = 0) {
   // (M: the stream's samples per frame; its row starts at row * rs_pitch -- M of the batch's rate, which a stream of a rate table may
   //  fill only in part: rn_dev.h RnGroupDev::rs_Ls)
   const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
@@ -47,8 +49,10 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
   float rx[NX], rt[NT];
 #pragma unroll
   for (int i = 0; i < NX; i++) {
-    const size_t q = (size_t)row * g.rs_pitch + min(lane + WAVE * i, M - 1);  // (row: the caller's row of stream s, RnStreamAt::i)
-    rx[i] = IN_S16 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
+    const int m = min(lane + WAVE * i, M - 1);
+    const size_t q = (size_t)row * g.rs_pitch + m;  // (row: the caller's row of stream s, RnStreamAt::i)
+    if (IN == 2) rx[i] = (float)rn_g711_decode(fmt, static_cast<const uint8_t *>(in)[(size_t)row * g.rs_pitch * sizeof(short) + m]);
+    else rx[i] = IN == 1 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
   }
   const float *ht = rs_up_taps(L);
 #pragma unroll
@@ -301,10 +305,12 @@ static_assert(RN_RS_LDS <= RN_PITCH_BUF_SIZE, "the upsampling prologue's LDS fit
 // (the body once per input type, like hp_body above: behind the run-time test per load the frame's two loads and the three loads of
 //  old samples were each followed by its own s_waitcnt vmcnt(0) -- five serial round trips, two of them to pinned host memory in the
 //  one-frame API, in front of a kernel of ~20 us)
-template <bool IN_S16>
+// IN: 0 a float row, 1 an int16 row, 2 a companded row -- 480 G.711 bytes of law `fmt` at the front of the int16 row (rn_dev.h:
+// RnGroupDev::pcm_fmt), four codes per lane and load where the int16 row gives four samples, expanded in registers (g711.h)
+template <int IN>
 __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, const void *__restrict__ in_row,
-                                            bool listed, int s, int slot) {
-  constexpr bool in_s16 = IN_S16;
+                                            bool listed, int s, int slot, int fmt = 0) {
+  constexpr bool in_s16 = IN == 1;
   const int lane = threadIdx.x;
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
   const double na0 = -(double)a0, na1 = -(double)a1, b0d = (double)b0;
@@ -320,12 +326,17 @@ __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, co
      // ring0 / 2, a multiple of 16; the decimated ring's size is a multiple of 4, so a float4 never straddles the wrap)
     const float4 *x = reinterpret_cast<const float4 *>(in_row);
     const short4 *x16 = reinterpret_cast<const short4 *>(in_row);
+    const uint32_t *x8 = reinterpret_cast<const uint32_t *>(in_row);
     constexpr int OLD4 = (RN_PITCH_BUF_SIZE - RN_FRAME_SIZE) / 2 / 4;
     float4 f[2], o[3];
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       const int q = min(lane + 64 * i, RN_FRAME_SIZE / 4 - 1);  // (lanes past the end re-read the last 16 bytes and drop them)
-      if (in_s16) {
+      if (IN == 2) {
+        const uint32_t v = x8[q];
+        f[i] = make_float4((float)rn_g711_decode(fmt, v & 255), (float)rn_g711_decode(fmt, (v >> 8) & 255),
+                           (float)rn_g711_decode(fmt, (v >> 16) & 255), (float)rn_g711_decode(fmt, v >> 24));
+      } else if (in_s16) {
         const short4 v = x16[q];
         f[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
       } else {
@@ -448,11 +459,14 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
   const int s = at.s;
   if (!at.present) return;  // an absent stream writes nothing
   const float *rs_row = nullptr;
+  // a companded stream of an int16 call (rn_dev.h: RnGroupDev::pcm_fmt; never a row list): its row holds bytes
+  const int fmt = (in_s16 & 1) ? rn_stream_fmt(g, s) : 0;
   if (in_s16 & 2) {  // low-rate rows (never a row list): upsampled into RnGroupDev::rs_up, staged in the body's LDS before the body uses it
     const int rs_L = rn_stream_L(g, s);  // (the batch's divisor, or the stream's own from the rate table)
     if (rs_L > 1) {
-      if (in_s16 & 1) rs_up_stream<true>(g, in, s, at.i, L.pb, rs_L);
-      else rs_up_stream<false>(g, in, s, at.i, L.pb, rs_L);
+      if (fmt) rs_up_stream<2>(g, in, s, at.i, L.pb, rs_L, fmt);
+      else if (in_s16 & 1) rs_up_stream<1>(g, in, s, at.i, L.pb, rs_L);
+      else rs_up_stream<0>(g, in, s, at.i, L.pb, rs_L);
       __syncthreads();
       rs_row = g.rs_up + (size_t)s * RN_FRAME_SIZE;
       in_s16 = 0;
@@ -465,8 +479,9 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
                        : rs_row ? static_cast<const void *>(rs_row)
                        : (in_s16 & 1) ? static_cast<const void *>(reinterpret_cast<const short *>(in) + (size_t)at.i * RN_FRAME_SIZE)
                                       : static_cast<const void *>(in + (size_t)at.i * RN_FRAME_SIZE);
-  if (in_s16) hp_one_body<true>(L, g, in_row, at.listed, s, at.ring);
-  else hp_one_body<false>(L, g, in_row, at.listed, s, at.ring);
+  if (in_s16 && fmt) hp_one_body<2>(L, g, in_row, at.listed, s, at.ring, fmt);
+  else if (in_s16) hp_one_body<1>(L, g, in_row, at.listed, s, at.ring);
+  else hp_one_body<0>(L, g, in_row, at.listed, s, at.ring);
 }
 
 

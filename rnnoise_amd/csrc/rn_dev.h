@@ -19,6 +19,7 @@
 #define RN_INSTRUMENT 0
 #endif
 #include "../../include/rn_layout.h"
+#include "g711.h"
 #include <stdlib.h>
 // The environment variables this library reads come in two classes:
 //   getenv("RNNOISE_AMD_...")   product knobs: configuration, and dispatch thresholds that select between kernels with the
@@ -179,6 +180,12 @@ struct RnGroupDev {
   // and K3's body writes it in place, no filter runs and the stream's history is not touched.
   const uint8_t *rs_Ls;        // [N] or null
   int rs_pitch;
+  // Per-stream PCM formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats).  Null pcm_fmt: every row of an int16 call holds
+  // int16 samples (every launch is today's).  Set, stream s's rows of the int16 calls hold pcm_fmt[s]: RN_PCM_ULAW / RN_PCM_ALAW
+  // (g711.h) one byte per sample in the FIRST 480 / L_s bytes of the row -- K0 expands them where it reads the row (hp_one_body,
+  // rs_up_stream), K3 compresses its truncated int16 value where it stores it (synthesis_body, rs_down_stream) --, anything else
+  // int16 (rn_stream_fmt).  Rows keep their pitch.  Indexed by batch stream, also in a list call.  Float calls never look at it.
+  const uint8_t *pcm_fmt;      // [N] or null
   // Per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model).  Null model_of: every row belongs to the launch (a batch with
   // one model).  Set, the network launch of slot model_sel owns row s when (model_of[s] < n_models ? model_of[s] : 0) == model_sel
   // (rn_owns): only owned rows get stores -- state, state images, gains, vad -- and a workgroup with no owned row returns at once.
@@ -317,6 +324,13 @@ __device__ __forceinline__ int rn_stream_L(const RnGroupDev &g, int s) {
   if (!g.rs_Ls) return g.rs_L;
   const int v = __builtin_amdgcn_readfirstlane((int)*(__attribute__((address_space(1))) const uint8_t *)(g.rs_Ls + s));
   return ((v == 1 || v == 2 || v == 3 || v == 6) && v >= g.rs_L) ? v : g.rs_L;
+}
+// PCM format of stream s's rows in an int16 call (rn_dev.h: RnGroupDev::pcm_fmt): RN_PCM_ULAW, RN_PCM_ALAW, or 0 for int16 rows -- no
+// table, or a byte that names neither law.  s is the workgroup's one stream: the result is wave-uniform
+__device__ __forceinline__ int rn_stream_fmt(const RnGroupDev &g, int s) {
+  if (!g.pcm_fmt) return 0;
+  const int v = __builtin_amdgcn_readfirstlane((int)*(__attribute__((address_space(1))) const uint8_t *)(g.pcm_fmt + s));
+  return (v == RN_PCM_ULAW || v == RN_PCM_ALAW) ? v : 0;
 }
 // Whether the network launch of g.model_sel owns stream s (rn_dev.h: RnGroupDev::model_of); an entry naming no slot reads as slot 0
 __device__ __forceinline__ bool rn_owns(const RnGroupDev &g, int s) {

@@ -186,6 +186,10 @@ struct RNNoiseBatch {
   // kernels read (rn_dev.h: RnGroupDev::rs_Ls) -- allocated by the first table; g.rs_Ls points at it while a table is set, and g.rs_L /
   // g.rs_hist are then set at 48 kHz too (batch.cpp: rs_point)
   uint8_t *rate_map = nullptr;
+  // per-stream PCM formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats): fmt_map, the [N] format bytes K0 / K3 read in
+  // the int16 calls (rn_dev.h: RnGroupDev::pcm_fmt) -- allocated by the first table, like model_map; g.pcm_fmt points at it while a
+  // table is set.  Configuration, not state: no reset, import, load or rate change touches it
+  uint8_t *fmt_map = nullptr;
   // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
   // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of) -- allocated by the first
   // add_model, like rs_buf by the first rate change; g.model_of / g.n_models are set from then on

@@ -184,6 +184,17 @@ class RNNoiseOp:
         Synchronous; ValueError on any other value."""
         self.batch.set_stream_rates(hz)
 
+    def set_stream_formats(self, formats):
+        """the PCM format of every stream's rows in the batch's int16 calls: an (N,) uint8 CUDA tensor of codes (0 s16, 1 ulaw, 2 alaw:
+        rnnoise_amd.g711), copied on torch's current stream without a host synchronisation (rnnoise_batch_set_stream_formats_device: any
+        other byte reads as s16).  The op's own calls are float calls and ignore the table; it serves the int16 device calls made on
+        `self.batch` with tensors of this process (capi.Batch.process_device_s16 and its masked and list forms)."""
+        torch = self.torch
+        assert formats.is_cuda and formats.dtype == torch.uint8 and formats.numel() == self.n
+        formats = formats.to(self.device).contiguous()
+        # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        self.batch.set_stream_formats_device(formats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+
     def set_stream_controls(self, limit_db=None, vad_threshold=0.0, hold_frames=0):
         """per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): an attenuation limit in dB (a
         floor on the band gains; None / inf: none), a VAD gate threshold in [0, 1] (0: no gate) and the frames the gate stays open
