@@ -18,39 +18,21 @@ const RnKnobs &rn_knobs() {
   return k;
 }
 namespace {
-size_t batch_layout(RnGroupDev &g, uint8_t *base, int n) {
+// the arrays of rn_dev.h: RN_GROUP_ARRAYS for n streams from `base` on, then the [n] frame phases of per-stream mode (the group
+// carries a pointer to them only while a call runs in that mode); returns the bytes used (a null base: the arena's size)
+size_t batch_layout(RnGroupDev &g, int *&phase_buf, uint8_t *base, int n) {
   uint8_t *p = base;
-  size_t N = n;
+  const size_t N = n;
   g.n_streams = n;
   g.n_stride = n;
-  g.mem_hp = carve<float>(p, 2 * N);
-  g.pitch_ring = carve<float>(p, RN_RING_SIZE * N);
-  g.xlp_ring = carve<float>(p, RN_XRING_SIZE * N);
-  g.synth_mem = carve<float>(p, RN_FRAME_SIZE * N);
-  g.last_gain = carve<float>(p, N);
-  g.last_period = carve<int>(p, N);
-  g.lastg = carve<float>(p, RN_NB_BANDS * N);
-  g.conv1_state = carve<float>(p, 130 * N);
-  g.conv2_state = carve<float>(p, 256 * N);
-  g.gru_state = carve<float>(p, 3 * RN_GRU * N);
-  for (int k = 0; k < RN_SPEC_SLOTS; k++) {
-    g.spec_X[k] = carve<float>(p, RN_SPEC_STRIDE * N);
-    g.spec_P[k] = carve<float>(p, RN_SPEC_STRIDE * N);
-    g.spec_E[k] = carve<float>(p, 96 * N);
-  }
-  g.features = carve<float>(p, 68 * N);
-  g.silence = carve<int>(p, N);
-  g.pitch = carve<int>(p, N);
-  g.features_b = carve<float>(p, 68 * N);
-  g.silence_b = carve<int>(p, N);
-  g.pitch_b = carve<int>(p, N);
-  g.gains = carve<float>(p, RN_NB_BANDS * N);
-  g.vad = carve<float>(p, N);
-  g.nn_act = carve<float>(p, RN_GRU * N);
-  for (int k = 0; k < 4; k++) g.act_q[k] = carve<int8_t>(p, (N + 15) / 16 * 6144);
-  g.lpc2 = carve<float>(p, 8 * N * RN_RING_SLOTS);
-  g.train_clean_mem = carve<float>(p, RN_FRAME_SIZE * N);
-  g.phase = carve<int>(p, N);  // (moved to RNNoiseBatch::phase_buf: the group carries it only in per-stream mode)
+#define CARVE(m, T, row, planes) g.m = carve<T>(p, (size_t)(planes) * (row) * N);
+#define CARVE_TILES(m, T, tile) g.m = carve<T>(p, (N + 15) / 16 * (tile));
+#define NOT_CARVED(m, row)
+  RN_GROUP_ARRAYS(CARVE, CARVE_TILES, NOT_CARVED)
+#undef CARVE
+#undef CARVE_TILES
+#undef NOT_CARVED
+  phase_buf = carve<int>(p, N);
   return (size_t)(p - base);
 }
 
@@ -61,47 +43,14 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count) {
   RnGroupDev v = g;
   const size_t f = first;
   v.n_streams = count;
-  v.mem_hp += 2 * f;
-  v.pitch_ring += RN_RING_SIZE * f;
-  v.xlp_ring += RN_XRING_SIZE * f;
-  v.synth_mem += RN_FRAME_SIZE * f;
-  v.last_gain += f;
-  v.last_period += f;
-  v.lastg += RN_NB_BANDS * f;
-  v.conv1_state += 130 * f;
-  v.conv2_state += 256 * f;
-  v.gru_state += RN_GRU * f;
-  for (int k = 0; k < RN_SPEC_SLOTS; k++) {
-    v.spec_X[k] += RN_SPEC_STRIDE * f;
-    v.spec_P[k] += RN_SPEC_STRIDE * f;
-    v.spec_E[k] += 96 * f;
-  }
-  v.features += 68 * f;
-  v.silence += f;
-  v.pitch += f;
-  v.features_b += 68 * f;
-  v.silence_b += f;
-  v.pitch_b += f;
-  v.gains += RN_NB_BANDS * f;
-  v.vad += f;
-  v.nn_act += RN_GRU * f;
-  v.lpc2 += 8 * f;
-  v.train_clean_mem += RN_FRAME_SIZE * f;
-  if (v.debug) v.debug += RN_DBG_FLOATS * f;
-  if (v.phase) v.phase += f;
-  if (v.active) v.active += f;  // (rows of the mask keep the stride n_stride)
-  if (v.model_of) v.model_of += f;
-  if (v.ctl) {
-    v.ctl += RN_CTL_FLOATS * f;
-    v.gate_c += f;
-  }
-  if (v.rs_Ls) v.rs_Ls += f;
-  if (v.pcm_fmt) v.pcm_fmt += f;
-  if (v.rs_hist) {
-    v.rs_hist += RN_RS_HIST * f;
-    v.rs_up += RN_FRAME_SIZE * f;
-    v.rs_dn += RN_FRAME_SIZE * f;
-  }
+#define ADVANCE(m, T, row, planes) v.m += (row) * f;
+#define WHOLE(m, T, tile)
+#define ADVANCE_IF_SET(m, row) \
+  if (v.m) v.m += (row) * f;
+  RN_GROUP_ARRAYS(ADVANCE, WHOLE, ADVANCE_IF_SET)
+#undef ADVANCE
+#undef WHOLE
+#undef ADVANCE_IF_SET
   return v;
 }
 
@@ -181,7 +130,8 @@ extern "C" RNNoiseBatch *rnnoise_batch_create(RNNModel *model, int n_streams, in
     return nullptr;
   }
   RnGroupDev probe{};
-  b->arena_bytes = batch_layout(probe, nullptr, n_streams);
+  int *no_phases = nullptr;
+  b->arena_bytes = batch_layout(probe, no_phases, nullptr, n_streams);
   DeviceGuard guard(device);
   if (!guard.ok || hipMalloc(&b->arena, b->arena_bytes) != hipSuccess) {
     fprintf(stderr, "[rnnoise_amd] cannot allocate %zu bytes of HBM for %d streams\n", b->arena_bytes, n_streams);
@@ -193,9 +143,7 @@ extern "C" RNNoiseBatch *rnnoise_batch_create(RNNModel *model, int n_streams, in
   if (hipDeviceGetAttribute(&b->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || b->cus <= 0) b->cus = 256;
   b->lds_one = rn_nn_one_opt_in();
   rn_nn_gru_opt_in(b->lds_gru);
-  batch_layout(b->g, static_cast<uint8_t *>(b->arena), n_streams);
-  b->phase_buf = b->g.phase;
-  b->g.phase = nullptr;
+  batch_layout(b->g, b->phase_buf, static_cast<uint8_t *>(b->arena), n_streams);
   b->scratch_gains = b->g.gains;
   b->scratch_vad = b->g.vad;
   b->features2[0] = b->g.features;
@@ -806,7 +754,7 @@ int batch_process_masked_host(RNNoiseBatch *b, void *out, const void *in, float 
 // zero state for the n streams of the device list d_list, on st; the layer-wise network's state images of their tiles follow
 // (rn_dev.h: act_q) while they are in use, so that a reset costs no re-quantisation of the whole batch at the next step
 int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_scatter(&b->g, nullptr, 0, 0, st, d_list, n));
+  HIP_OK(rn_launch_state_zero(&b->g, d_list, n, st));
   if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n));
   return 0;
 }
@@ -947,12 +895,19 @@ extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, con
 #define H2D(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyHostToDevice))
 
 namespace {
-// frame phase of stream s (the slots its next frame writes: ring slot p % RN_RING_SLOTS, spectra slot p % RN_SPEC_SLOTS), after a drain
-int stream_phase(RNNoiseBatch *b, int s, int &p) {
-  p = b->ring_slot;
-  if (b->per_stream) HIP_OK(hipMemcpy(&p, b->phase_buf + s, sizeof(int), hipMemcpyDeviceToHost));
+// what every state produced by the reference or by export_state satisfies, and what lets the batch not store analysis_mem (rn_dev.h)
+bool analysis_is_pitch_tail(const float *f) {
+  return !memcmp(f + RN_OFF_ANALYSIS, f + RN_OFF_PITCH_BUF + RN_PITCH_BUF_SIZE - RN_FRAME_SIZE, RN_FRAME_SIZE * sizeof(float));
+}
+// the one-state staging row of export / import (16-byte aligned, as the scatter kernel wants its records)
+int stage_ready(RNNoiseBatch *b) {
+  if (!b->state_stage) HIP_OK(hipMalloc((void **)&b->state_stage, RN_STATE_FLOATS * sizeof(float)));
   return 0;
 }
+// where the state kernels find the frame phases of streams s, s + 1, ... in per-stream mode (they read them on the device; null in
+// lock-step mode, where the launch carries b->ring_slot: the slots its next frame writes, ring slot p % RN_RING_SLOTS, spectra slot
+// p % RN_SPEC_SLOTS)
+const int *phase_of(const RNNoiseBatch *b, int s) { return b->per_stream ? b->phase_buf + s : nullptr; }
 }  // namespace
 
 // State migration: one gather / scatter kernel (state_kernels.hip) and one copy per call.  Synchronous with everything
@@ -961,32 +916,26 @@ extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
   if (!b || !f || s < 0 || s >= b->n) return -1;
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
-  if (!b->state_stage) HIP_OK(hipMalloc((void **)&b->state_stage, RN_STATE_FLOATS * sizeof(float)));
-  int p;
-  if (stream_phase(b, s, p)) return -1;
+  if (stage_ready(b)) return -1;
   const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_gather(&v, b->state_stage, (p + RN_RING_SLOTS - 1) % RN_RING_SLOTS,
-                                (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, nullptr));
+  HIP_OK(rn_launch_state_gather(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr));
   D2H(f, b->state_stage, RN_STATE_FLOATS);  // (a blocking copy on the null stream: ordered after the kernel)
   return 0;
 }
 
 extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f) {
   if (!b || !f || s < 0 || s >= b->n) return -1;
-  if (memcmp(f + RN_OFF_ANALYSIS, f + RN_OFF_PITCH_BUF + RN_PITCH_BUF_SIZE - RN_FRAME_SIZE, RN_FRAME_SIZE * 4)) {
+  if (!analysis_is_pitch_tail(f)) {
     fprintf(stderr, "[rnnoise_amd] import_state: analysis_mem differs from the tail of pitch_buf\n");
     return -1;
   }
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
-  if (!b->state_stage) HIP_OK(hipMalloc((void **)&b->state_stage, RN_STATE_FLOATS * sizeof(float)));
+  if (stage_ready(b)) return -1;
   H2D(b->state_stage, f, RN_STATE_FLOATS);
   b->img_valid = false;
-  int p;
-  if (stream_phase(b, s, p)) return -1;
   const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_scatter(&v, b->state_stage, (p + RN_RING_SLOTS - 1) % RN_RING_SLOTS,
-                                 (p + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS, nullptr));
+  HIP_OK(rn_launch_state_scatter(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr));
   HIP_OK(hipStreamSynchronize(nullptr));
   return 0;
 }
@@ -1005,13 +954,13 @@ bool snap_args_ok(const RNNoiseBatch *b, const void *snap, const int *streams, i
   return true;
 }
 int save_on(RNNoiseBatch *b, float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_save(&b->g, d_snap, d_list, n, b->ring_slot, b->per_stream ? b->phase_buf : nullptr, st));
+  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), st));
   return 0;
 }
 // the listed rows' tiles of the layer-wise network's state images follow the load while they are live (rn_dev.h: act_q), as after
 // a per-stream reset; without a list that is every tile
 int load_on(RNNoiseBatch *b, const float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_load(&b->g, d_snap, d_list, n, b->ring_slot, b->per_stream ? b->phase_buf : nullptr, st));
+  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), st));
   if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, d_list ? n : 0));
   return 0;
 }
@@ -1034,7 +983,7 @@ int snap_host(RNNoiseBatch *b, float *snap, const int *streams, int n, bool load
       int magic;
       memcpy(&magic, f + RN_SNAP_OFF_MAGIC, sizeof magic);
       if (magic != RN_SNAP_MAGIC) return -1;
-      if (memcmp(f + RN_OFF_ANALYSIS, f + RN_OFF_PITCH_BUF + RN_PITCH_BUF_SIZE - RN_FRAME_SIZE, RN_FRAME_SIZE * 4)) {
+      if (!analysis_is_pitch_tail(f)) {
         fprintf(stderr, "[rnnoise_amd] load_streams: row %d: analysis_mem differs from the tail of pitch_buf\n", i);
         return -1;
       }

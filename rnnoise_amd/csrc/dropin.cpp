@@ -35,7 +35,7 @@ StatePool *pool_new(RNNModel *model, int device) {
   DeviceGuard guard(device);
   if (!guard.ok ||
       hipHostMalloc((void **)&p->h_io, (size_t)p->rows * RN_ROW_IO * sizeof(float), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-      hipMalloc((void **)&p->d_flat, (size_t)StatePool::FLAT_ROWS * RN_STATE_FLOATS * sizeof(float)) != hipSuccess) {
+      hipMalloc((void **)&p->d_flat, (size_t)StatePool::FLAT_ROWS * RN_STATE_PITCH * sizeof(float)) != hipSuccess) {
     if (p->h_io) hipHostFree(p->h_io);
     rnnoise_batch_destroy(p->batch);
     delete p;
@@ -106,25 +106,10 @@ void pool_release(StatePool *p, int slot) {
   p->used[slot >> 6] &= ~(1ull << (slot & 63));
 }
 
-// the stateful arrays of one row back to all-zero (what rnnoise_init does to a DenoiseState, src/denoise.c:286)
+// the stateful arrays of one row back to all-zero (what rnnoise_init does to a DenoiseState, src/denoise.c:286): one launch on st
 int pool_zero_row(StatePool *p, int slot, hipStream_t st) {
   const RnGroupDev v = group_view(p->batch->g, slot, 1);
-  const size_t N = p->batch->n;
-  HIP_OK(hipMemsetAsync(v.mem_hp, 0, 2 * 4, st));
-  HIP_OK(hipMemsetAsync(v.pitch_ring, 0, RN_RING_SIZE * 4, st));
-  HIP_OK(hipMemsetAsync(v.xlp_ring, 0, RN_XRING_SIZE * 4, st));
-  HIP_OK(hipMemsetAsync(v.synth_mem, 0, RN_FRAME_SIZE * 4, st));
-  HIP_OK(hipMemsetAsync(v.last_gain, 0, 4, st));
-  HIP_OK(hipMemsetAsync(v.last_period, 0, 4, st));
-  HIP_OK(hipMemsetAsync(v.lastg, 0, RN_NB_BANDS * 4, st));
-  HIP_OK(hipMemsetAsync(v.conv1_state, 0, 130 * 4, st));
-  HIP_OK(hipMemsetAsync(v.conv2_state, 0, 256 * 4, st));
-  for (int k = 0; k < 3; k++) HIP_OK(hipMemsetAsync(v.gru_state + k * N * RN_GRU, 0, RN_GRU * 4, st));
-  for (int k = 0; k < RN_SPEC_SLOTS; k++) {
-    HIP_OK(hipMemsetAsync(v.spec_X[k], 0, RN_SPEC_STRIDE * 4, st));
-    HIP_OK(hipMemsetAsync(v.spec_P[k], 0, RN_SPEC_STRIDE * 4, st));
-    HIP_OK(hipMemsetAsync(v.spec_E[k], 0, 96 * 4, st));
-  }
+  HIP_OK(rn_launch_state_zero(&v, nullptr, 0, st));
   return 0;
 }
 
@@ -747,10 +732,10 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
   {
     DeviceGuard guard(pool->batch->device);
     if (guard.ok && sc.ready(pool->batch->device)) {
-      float *d_state = pool->d_flat + (size_t)slot * RN_STATE_FLOATS, *h_row = pool->h_io + (size_t)slot * RN_ROW_IO;
+      float *d_state = pool->d_flat + (size_t)slot * RN_STATE_PITCH, *h_row = pool->h_io + (size_t)slot * RN_ROW_IO;
       const RnGroupDev v = group_view(pool->batch->g, slot, 1);
-      // conventions of a freshly scattered row: its newest frame sits in ring slot 5 and spectra slot 2, so the next frame
-      // goes to ring slot 0 / spectra slot 0 and leaves its own "delayed" spectra in slot 0.  (Sequence number 0: nobody polls a
+      // conventions of a freshly scattered row: it is at frame phase 0 -- its newest frame sits in ring slot 5 and spectra slot 2, so
+      // the next frame goes to ring slot 0 / spectra slot 0 -- and at phase 1 when the frame has run.  (Sequence number 0: nobody polls a
       // borrowed row's `done` word -- this thread synchronises its stream.)
       RnRows rows{};
       rows.n = 1;
@@ -759,9 +744,9 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
       memcpy(hu, st->state, RN_STATE_FLOATS * sizeof(float));
       memcpy(h_row + RN_ROW_IN, in, RN_FRAME_SIZE * sizeof(float));
       ok = hipMemcpyAsync(d_state, hu, RN_STATE_FLOATS * sizeof(float), hipMemcpyHostToDevice, sc.stream) == hipSuccess &&
-           rn_launch_state_scatter(&v, d_state, RN_RING_SLOTS - 1, RN_SPEC_SLOTS - 1, sc.stream) == hipSuccess &&
+           rn_launch_state_scatter(&v, RN_REC_STATE, d_state, nullptr, 1, 0, nullptr, sc.stream) == hipSuccess &&
            rows_launch(pool, rows, sc.stream, false) == 0 &&
-           rn_launch_state_gather(&v, d_state, 0, 0, sc.stream) == hipSuccess &&
+           rn_launch_state_gather(&v, RN_REC_STATE, d_state, nullptr, 1, 1, nullptr, sc.stream) == hipSuccess &&
            hipMemcpyAsync(hd, d_state, RN_STATE_FLOATS * sizeof(float), hipMemcpyDeviceToHost, sc.stream) == hipSuccess &&
            hipStreamSynchronize(sc.stream) == hipSuccess;
       if (ok) {

@@ -38,6 +38,15 @@
 // kernel forms two band vectors at once from two arrays this far apart
 #define RN_BAND_QSTRIDE 1044
 #define RN_SPEC_STRIDE 964  // 481 complex = 962 floats, padded to a 16-byte multiple
+// the other row lengths of the per-stream arrays (RN_GROUP_ARRAYS below) that no constant of rn_layout.h names
+#define RN_SPEC_E_ROW 96    // Ex | Ep | Exp, RN_NB_BANDS each
+#define RN_CONV1_ROW 130    // conv1_state: two frames of RN_CONV1_IN inputs
+#define RN_CONV2_ROW 256    // conv2_state: two frames of RN_CONV2_IN inputs
+#define RN_FEAT_ROW 68      // RN_NB_FEATURES = 65 used
+#define RN_LPC2_ROW 8       // 5 used
+// floats between the portable states of an array of them on the device (state_kernels.hip): rows stay 16-byte aligned, which
+// RN_STATE_FLOATS * 4 = 25,128 bytes would not give every other row
+#define RN_STATE_PITCH ((RN_STATE_FLOATS + 3) & ~3)
 // spectra slots: frame t writes slot t%3, synthesis of frame t reads slots t%3 (Ex) and (t-1)%3 (the
 // reference's delayed_*); the third slot lets the analysis of frame t+1 run beside synthesis of frame t
 #define RN_SPEC_SLOTS 3
@@ -122,14 +131,14 @@ struct RnGroupDev {
   float *last_gain;    // [N]
   int *last_period;    // [N]
   float *lastg;        // [N][32]
-  float *conv1_state;  // [N][130]
-  float *conv2_state;  // [N][256]
+  float *conv1_state;  // [N][RN_CONV1_ROW = 130]
+  float *conv2_state;  // [N][RN_CONV2_ROW = 256]
   float *gru_state;    // [3][N][384]
   float *spec_X[RN_SPEC_SLOTS];  // [N][RN_SPEC_STRIDE]  rotating: current, delayed, (free for the next frame)
   float *spec_P[RN_SPEC_SLOTS];  // [N][RN_SPEC_STRIDE]
-  float *spec_E[RN_SPEC_SLOTS];  // [N][96] = Ex | Ep | Exp
+  float *spec_E[RN_SPEC_SLOTS];  // [N][RN_SPEC_E_ROW = 96] = Ex | Ep | Exp
   // per-step scratch
-  float *features;     // [N][68] (65 used)
+  float *features;     // [N][RN_FEAT_ROW = 68] (65 used)
   int *silence;        // [N]
   int *pitch;          // [N]   final period (debug/tests)
   float *features_b;   // second copy of the three per-step arrays above (the host alternates them per frame
@@ -137,7 +146,7 @@ struct RnGroupDev {
   int *pitch_b;
   float *gains;        // [N][32] raw network gains of the current step
   float *vad;          // [N]
-  float *lpc2;         // [RN_RING_SLOTS][N][8] (5 used) FIR taps of rnn_pitch_downsample, produced by K0, consumed by K1
+  float *lpc2;         // [RN_RING_SLOTS][N][RN_LPC2_ROW = 8] (5 used) FIR taps of rnn_pitch_downsample, produced by K0, consumed by K1
   float *nn_act;       // [N][384] conv2 output in f32 (MFMA path: input of dense_out)
   int8_t *act_q[4];    // [ceil(N/16)][6144] layer-wise network: u8-quantised activations per 16-stream tile, B-fragment order:
                        //   [0] conv2 output (scratch of the step), [1 + k] GRU state k -- at once the input of layer k + 1 and
@@ -201,6 +210,57 @@ struct RnGroupDev {
   const float *ctl;            // [N][RN_CTL_FLOATS] or null
   int *gate_c;                 // [N] or null
 };
+// The per-stream arrays of RnGroupDev, once, in the order the arena holds them: batch_layout carves them and group_view advances
+// them from this list (batch.cpp).
+//   ROWS(member, type, row, planes)   [planes][N][row]: carved whole, a view advances it by `row` per stream; the planes of gru_state
+//                                     and lpc2 stay n_stride rows apart
+//   TILES(member, type, tile)         `tile` elements per 16 streams: whole batches only, never offset by a view
+//   OPT(member, row)                  [N][row], not in the arena: null until its feature sets it, advanced only when set (ctl and
+//                                     gate_c are set together, and so are rs_hist, rs_up and rs_dn)
+// Slot k of the three spectra sets lies together, and so the four images of act_q.
+#define RN_EACH(k, n, ...) \
+  for (int k = 0; k < (n); k++) { __VA_ARGS__ }
+#define RN_GROUP_ARRAYS(ROWS, TILES, OPT)                        \
+  ROWS(mem_hp, float, 2, 1)                                      \
+  ROWS(pitch_ring, float, RN_RING_SIZE, 1)                       \
+  ROWS(xlp_ring, float, RN_XRING_SIZE, 1)                        \
+  ROWS(synth_mem, float, RN_FRAME_SIZE, 1)                       \
+  ROWS(last_gain, float, 1, 1)                                   \
+  ROWS(last_period, int, 1, 1)                                   \
+  ROWS(lastg, float, RN_NB_BANDS, 1)                             \
+  ROWS(conv1_state, float, RN_CONV1_ROW, 1)                      \
+  ROWS(conv2_state, float, RN_CONV2_ROW, 1)                      \
+  ROWS(gru_state, float, RN_GRU, 3)                              \
+  RN_EACH(k, RN_SPEC_SLOTS,                                      \
+          ROWS(spec_X[k], float, RN_SPEC_STRIDE, 1)              \
+          ROWS(spec_P[k], float, RN_SPEC_STRIDE, 1)              \
+          ROWS(spec_E[k], float, RN_SPEC_E_ROW, 1))              \
+  ROWS(features, float, RN_FEAT_ROW, 1)                          \
+  ROWS(silence, int, 1, 1)                                       \
+  ROWS(pitch, int, 1, 1)                                         \
+  ROWS(features_b, float, RN_FEAT_ROW, 1)                        \
+  ROWS(silence_b, int, 1, 1)                                     \
+  ROWS(pitch_b, int, 1, 1)                                       \
+  ROWS(gains, float, RN_NB_BANDS, 1)                             \
+  ROWS(vad, float, 1, 1)                                         \
+  ROWS(nn_act, float, RN_GRU, 1)                                 \
+  RN_EACH(k, 4, TILES(act_q[k], int8_t, 6144))                   \
+  ROWS(lpc2, float, RN_LPC2_ROW, RN_RING_SLOTS)                  \
+  ROWS(train_clean_mem, float, RN_FRAME_SIZE, 1)                 \
+  OPT(debug, RN_DBG_FLOATS)                                      \
+  OPT(phase, 1)                                                  \
+  OPT(active, 1) /* (rows of the mask keep the stride n_stride) */ \
+  OPT(model_of, 1)                                               \
+  OPT(ctl, RN_CTL_FLOATS)                                        \
+  OPT(gate_c, 1)                                                 \
+  OPT(rs_Ls, 1)                                                  \
+  OPT(pcm_fmt, 1)                                                \
+  OPT(rs_hist, RN_RS_HIST)                                       \
+  OPT(rs_up, RN_FRAME_SIZE)                                      \
+  OPT(rs_dn, RN_FRAME_SIZE)
+// what the records of a state gather / scatter launch are (state_kernels.hip): portable states, RN_STATE_PITCH floats apart, or
+// snapshot records (include/rn_layout.h: RN_SNAP_*)
+enum RnRecKind { RN_REC_STATE, RN_REC_SNAP };
 #define RN_CTL_FLOATS 3      // = RNNOISE_AMD_CTL_FLOATS: floor, thr, hold
 #define RN_CTL_NONE 65536    // counter of a stream with no voice frame yet
 #define RN_RS_TAPS 48                           // taps per phase of the up filter; the down filter has RN_RS_TAPS * L

@@ -59,14 +59,13 @@ extern "C" hipError_t rn_launch_log_energy(const float *, unsigned, float *, uns
 extern "C" hipError_t rn_launch_fft_probe(int, const float *, float *, unsigned long long *, int, int, const RnTablesDev *, hipStream_t);
 extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 #endif
-extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, float *, int, int, hipStream_t);
-extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, const float *, int, int, hipStream_t, const int *list = nullptr,
-                                              int n = 0);
-// (snapshot records of `rows` streams, by device list, at frame phase p or at the per-stream phases `phase`: state_kernels.hip)
-extern "C" hipError_t rn_launch_state_save(const RnGroupDev *, float *snap, const int *list, int rows, int p, const int *phase, hipStream_t);
-extern "C" hipError_t rn_launch_state_load(const RnGroupDev *, const float *snap, const int *list, int rows, int p, const int *phase,
-                                           hipStream_t);
-
+// (state_kernels.hip: `rows` records of `kind`, record i <-> stream list[i] of the view, at frame phase p or at the per-stream
+//  phases `phase`; and the zero state for the listed streams of the view, or for all of them)
+extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, RnRecKind kind, float *rec, const int *list, int rows, int p,
+                                             const int *phase, hipStream_t);
+extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, RnRecKind kind, const float *rec, const int *list, int rows, int p,
+                                              const int *phase, hipStream_t);
+extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *, const int *list, int n, hipStream_t);
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);
 extern "C" hipError_t rn_launch_analysis_rows(const RnGroupDev *, const RnTablesDev *, const RnRows *, hipStream_t);
@@ -274,7 +273,7 @@ struct StatePool {
   RNNoiseBatch *batch = nullptr;   // owns the arena; never processed as a whole
   static constexpr int FLAT_ROWS = 64;  // staged states (rnnoise_init states borrow rows 0 .. 63 only)
   float *h_io = nullptr;                // pinned [rows][RN_ROW_IO]: in[480] | pad[4] | out[480] | vad | pad[2] | done (rn_dev.h: RnRows)
-  float *d_flat = nullptr;              // [FLAT_ROWS][RN_STATE_FLOATS] staging of self-contained states (rnnoise_init path)
+  float *d_flat = nullptr;              // [FLAT_ROWS][RN_STATE_PITCH] staging of self-contained states (rnnoise_init path)
   std::mutex mu;
   std::vector<unsigned long long> used;  // bit per row
   // combiner words of the rows' requests.  They live HERE, not in the state (PooledRef), because a group's owner touches a

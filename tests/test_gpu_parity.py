@@ -323,6 +323,92 @@ def test_state_export_import_round_trip_and_teacher_forcing(model, blob_default)
         b2.import_state(0, bad)
 
 
+@pytest.fixture(scope="module")
+def phase_ref(blob_default):
+    """Three streams, ten frames, the oracle frame by frame: its outputs, and state[j][s] = its state of stream s after j frames
+    (j = 0: what rnnoise_init leaves).  Shared by the cases below and never written to."""
+    T, N = 10, 3
+    pcm = synth.batch_pcm([31, 32, 33], T, lead_silence=1)
+    out, vad = np.zeros_like(pcm), np.zeros((T, N), np.float32)
+    state = np.zeros((T + 1, N, capi.STATE_FLOATS), np.float32)
+    for s in range(N):
+        o = Oracle(blob_default)
+        state[0, s] = o.get_state()
+        for t in range(T):
+            r = o.run(pcm[t:t + 1, s])
+            out[t, s], vad[t, s] = r["out"][0], r["vad"][0]
+            state[t + 1, s] = o.get_state()
+    for a in (pcm, out, vad, state):
+        a.setflags(write=False)
+    return dict(pcm=pcm, out=out, vad=vad, state=state)
+
+
+@pytest.mark.parametrize("k,per_stream", [(k, False) for k in range(8)] + [(4, True)])
+def test_export_and_import_at_every_frame_phase(model, phase_ref, k, per_stream):
+    """export_state / import_state of every stream of a 3-stream batch (streams 1 and 2: planes n_stride apart, odd conv1_state
+    rows) after k = 0 .. 7 frames: every one of the six pitch-ring phases, both wrap positions of pitch_buf, all three spectra
+    slots.  The exported states are the oracle's; imported into other positions of a second batch that stands at another frame
+    phase -- in one case at per-stream phases, which the kernels read on the device -- they drive two more frames to the oracle's
+    outputs and states, on both batches."""
+    pcm, N = phase_ref["pcm"], 3
+    a = capi.Batch(model, N)
+    if k:
+        a.process(pcm[:k])
+    states = [a.export_state(s) for s in range(N)]
+    for s in range(N):
+        assert_bits_equal(states[s], phase_ref["state"][k, s], f"stream {s} after {k} frames")
+    b = capi.Batch(model, N)
+    m = (k + 3) % 8  # frames the second batch has run: never k
+    if per_stream:   # ... and a different number on each stream: 3, 2, 1
+        b.process_masked(pcm[:3], np.array([[1, 1, 1], [1, 1, 0], [1, 0, 0]], np.uint8))
+    elif m:
+        b.process(pcm[:m])
+    to = [(s + 1) % N for s in range(N)]  # stream s of the first batch goes on as stream to[s] of the second
+    for s in range(N):
+        b.import_state(to[s], states[s])
+    nxt = pcm[k:k + 2]
+    moved = np.empty_like(nxt)
+    moved[:, to] = nxt
+    oa, va, _ = a.process(nxt)
+    ob, vb, _ = b.process(moved)
+    assert_bits_equal(oa, phase_ref["out"][k:k + 2], "pcm of the exporting batch")
+    assert_bits_equal(va, phase_ref["vad"][k:k + 2], "vad of the exporting batch")
+    assert_bits_equal(ob[:, to], phase_ref["out"][k:k + 2], "pcm after import")
+    assert_bits_equal(vb[:, to], phase_ref["vad"][k:k + 2], "vad after import")
+    for s in range(N):
+        assert_bits_equal(a.export_state(s), phase_ref["state"][k + 2, s], f"stream {s}, two frames on")
+        assert_bits_equal(b.export_state(to[s]), phase_ref["state"][k + 2, s], f"stream {s} as {to[s]} of the second batch, two frames on")
+
+
+def test_two_caller_memory_states_in_flight_at_once(model, phase_ref):
+    """Two rnnoise_init() states called from two threads at the same moment: each call borrows a pool row of its own, so one of the
+    two stages its state through an odd row of the pool's staging block."""
+    import ctypes as C
+    import threading
+    L = capi.lib()
+    L.rnnoise_process_frame.restype = C.c_float
+    FP = C.POINTER(C.c_float)
+    T = 6
+    bufs = [(C.c_char * L.rnnoise_get_size())() for _ in range(2)]
+    for buf in bufs:
+        assert L.rnnoise_init(C.cast(buf, C.c_void_p), model.h) == 0
+    got, vad = np.zeros((T, 2, 480), np.float32), np.zeros((T, 2), np.float32)
+    together = threading.Barrier(2, timeout=60)
+
+    def work(i):
+        for t in range(T):
+            x = phase_ref["pcm"][t, i].copy()
+            together.wait()
+            vad[t, i] = L.rnnoise_process_frame(C.cast(bufs[i], C.c_void_p), x.ctypes.data_as(FP), x.ctypes.data_as(FP))
+            got[t, i] = x
+
+    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    assert_bits_equal(got, phase_ref["out"][:T, :2], "pcm")
+    assert_bits_equal(vad, phase_ref["vad"][:T, :2], "vad")
+
+
 def test_reset_restores_initial_state(model):
     pcm = synth.batch_pcm([1, 2, 3], 10)
     b = capi.Batch(model, 3)
