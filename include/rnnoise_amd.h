@@ -231,6 +231,36 @@ RNNOISE_EXPORT int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsig
 RNNOISE_EXPORT int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream);
 RNNOISE_EXPORT int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *formats);
 
+/* Caller-defined PCM strides: where the frames of `in` and `out` lie.  By default every rnnoise_batch_process* call takes PCM as
+ * [n_frames][n_rows][M], M = 480 / Lb samples (Lb the batch's divisor; n_rows = n_streams, or the list length of a list call): frame f
+ * of row r starts at sample (f * n_rows + r) * M.  With a layout set it starts at
+ *     f * frame_stride + r * row_stride
+ * in `in` and in `out`, both strides in SAMPLES of the call's own type (float, or int16 in the _s16 calls -- a companded row keeps
+ * its int16 stride and holds its bytes at the front of its slot).  So a [B][T] tensor or one contiguous jitter buffer per call leg is
+ * passed where it lies: frame_stride = M, row_stride = samples between the buffers.
+ * rnnoise_batch_set_pcm_layout: (0, 0) is the default and drops the layout -- the batch then launches exactly what a batch that never
+ * saw the call launches.  Any other pair must have both strides > 0 and multiples of 4 samples (80, 160, 240 and 480 all are: the 16-byte
+ * alignment of the float kernels and the 8-byte alignment of the int16 ones stay; the buffers themselves must be aligned as before);
+ * otherwise -1 and nothing changes.  Synchronous, like rnnoise_batch_set_pcm_rate.
+ * Every process call of a batch with a layout: the frames must not overlap --
+ *     row-major:          row_stride >= M  and  frame_stride >= n_rows * row_stride,   or
+ *     stream-contiguous:  frame_stride >= M  and  row_stride >= n_frames * frame_stride
+ * (rnnoise_amd_pcm_layout_fits: 1 / 0) -- else the call returns -1 with nothing launched and nothing changed.  A stream reads and writes
+ * the first 480 / L_s samples (a companded one: bytes) of its frame slot and nothing else: not the rest of the slot, not the padding
+ * between rows or frames.  vad, gains and active keep their [n_frames][n_rows] shapes; `in` may alias `out`.  Everything else -- out,
+ * vad, gains, complete state, histories, gate counters -- is bit for bit what the same frames give in the default layout.
+ * The layout applies to every call form: lock-step, masked and list; float and int16; device and host.  Host-buffer calls with a layout
+ * take the staged convenience path (strided copies of the frame slots into the default layout in device memory and back); the
+ * pinned-ring path of rnnoise_batch_process[_s16] serves the default layout only.
+ * A layout is configuration, not state: rnnoise_batch_reset, reset_streams[_device], import_state, load_streams and the model, control,
+ * rate and format tables leave it alone, and it does not appear in snapshots.  rnnoise_batch_set_pcm_rate drops it (its strides are in
+ * samples of the old M).  rnnoise_batch_train_features* returns -1 while a layout is set.
+ * rnnoise_batch_pcm_layout writes the strides in force, the default as (0, 0).  0 / -1; a NULL batch returns -1 without touching the
+ * device. */
+RNNOISE_EXPORT int rnnoise_batch_set_pcm_layout(RNNoiseBatch *b, long frame_stride, long row_stride);
+RNNOISE_EXPORT int rnnoise_batch_pcm_layout(const RNNoiseBatch *b, long *frame_stride, long *row_stride);
+RNNOISE_EXPORT int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_stride, int frame_samples, int n_rows, int n_frames);
+
 /* Several models in one batch: every stream runs with the model of its SLOT.  Slot 0 is the model the batch was created with;
  * rnnoise_batch_add_model puts another one into the next free slot (1 .. RNNOISE_AMD_MAX_MODELS - 1) and returns that slot: -1 on a
  * NULL batch or model, a full table, or a model that cannot be put on the batch's device.  Synchronous.  The model must outlive the

@@ -60,6 +60,7 @@ EXPORTS = [
     "rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device", "rnnoise_batch_save_streams", "rnnoise_batch_load_streams",
     "rnnoise_batch_set_stream_rates", "rnnoise_batch_set_stream_rates_device", "rnnoise_batch_stream_rates",
     "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
+    "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
 ]
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
@@ -189,6 +190,9 @@ def _load(path, debug):
         L.rnnoise_batch_set_stream_formats.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_formats_device.argtypes = [vp, vp, vp]
         L.rnnoise_batch_stream_formats.argtypes = [vp, up]
+        L.rnnoise_batch_set_pcm_layout.argtypes = [vp, C.c_long, C.c_long]
+        L.rnnoise_batch_pcm_layout.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        L.rnnoise_amd_pcm_layout_fits.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int]
         L.rnnoise_batch_add_model.argtypes = [vp, vp]
         L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
@@ -352,6 +356,59 @@ class Batch:
         rate table (set_stream_rates), under which a stream fills only the first 480 * rate // 48000 samples of its row"""
         return FRAME * self.pcm_rate // 48000
 
+    def set_pcm_layout(self, frame_stride: int = 0, row_stride: int = 0):
+        """where the frames of the PCM buffers of every call lie (rnnoise_batch_set_pcm_layout): frame f of row r starts at sample
+        f * frame_stride + r * row_stride of `in` and of `out` -- (frame, T * frame) for (N, T * frame) stream-contiguous buffers.
+        (0, 0): the default (T, N, frame) layout.  Both strides positive multiples of 4 samples, else ValueError and nothing changes.
+        With a layout the host calls (process, process_s16, process_masked*, process_list*) take (T, rows, frame) arrays whose
+        strides ARE the layout's -- views of the caller's buffers, pcm_array() makes one -- and read and write them in place."""
+        if self._L.rnnoise_batch_set_pcm_layout(self.h, int(frame_stride), int(row_stride)):
+            raise ValueError(f"PCM layout ({frame_stride}, {row_stride}) unsupported (both 0, or both positive multiples of 4 samples)")
+
+    @property
+    def pcm_layout(self):
+        """(frame_stride, row_stride) in samples; (0, 0): the default layout"""
+        f, r = C.c_long(0), C.c_long(0)
+        if self._L.rnnoise_batch_pcm_layout(self.h, C.byref(f), C.byref(r)):
+            raise RuntimeError("rnnoise_batch_pcm_layout failed")
+        return int(f.value), int(r.value)
+
+    def pcm_array(self, n_frames: int, dtype=np.float32, rows: int | None = None, fill=0):
+        """a (n_frames, rows, frame) view, in the batch's PCM layout, of a fresh buffer that spans its frame slots and is filled with
+        `fill` (rows: the batch's streams, or the rows of a list call); with a layout set `.base` is the flat buffer"""
+        rows = self.n if rows is None else rows
+        fs, rs = self.pcm_layout
+        if not rs:
+            return np.full((n_frames, rows, self.frame), fill, dtype)
+        flat = np.full(max(n_frames - 1, 0) * fs + max(rows - 1, 0) * rs + self.frame, fill, dtype)
+        it = flat.itemsize
+        return np.ndarray((n_frames, rows, self.frame), flat.dtype, flat, 0, (fs * it, rs * it, it))
+
+    def _pcm_in(self, pcm, dtype):
+        """the PCM argument of a host call: a C-contiguous (T, rows, frame) array in the default layout (copied if need be); with a
+        layout set, the caller's array as it lies -- its strides must be the layout's"""
+        fs, rs = self.pcm_layout
+        if not rs:
+            return np.ascontiguousarray(pcm, dtype)
+        it = np.dtype(dtype).itemsize
+        if not (isinstance(pcm, np.ndarray) and pcm.dtype == dtype and pcm.ndim == 3):
+            raise ValueError(f"with a PCM layout set the call takes a 3-D {np.dtype(dtype).name} array in that layout")
+        want = (fs * it, rs * it, it)
+        if any(n > 1 and st != w for n, st, w in zip(pcm.shape, pcm.strides, want)):
+            raise ValueError(f"array strides {pcm.strides} are not the batch's PCM layout {want} (bytes)")
+        return pcm
+
+    def _pcm_out(self, out, pcm, dtype, zero=False):
+        """the output array of a host call: given (checked like the input), or fresh -- in the batch's layout"""
+        if out is not None:
+            if self.pcm_layout[1]:
+                out = self._pcm_in(out, dtype)
+            assert out.dtype == dtype and out.shape == pcm.shape and (self.pcm_layout[1] or out.flags.c_contiguous)
+            return out
+        if self.pcm_layout[1]:
+            return self.pcm_array(pcm.shape[0], dtype, pcm.shape[1])
+        return np.zeros_like(pcm) if zero else np.empty_like(pcm)
+
     def set_stream_rates(self, hz):
         """the PCM rate of every stream in Hz (rnnoise_batch_set_stream_rates): (N,) values out of PCM_RATES, none above the batch's
         own rate, or None to drop the table.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose
@@ -413,25 +470,26 @@ class Batch:
             raise RuntimeError("rnnoise_batch_stream_formats failed")
         return f
 
-    def process(self, pcm: np.ndarray, want_gains: bool = True):
-        """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32])."""
-        pcm = np.ascontiguousarray(pcm, np.float32)
+    def process(self, pcm: np.ndarray, want_gains: bool = True, out: np.ndarray | None = None):
+        """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32]).  With a PCM layout set (set_pcm_layout) pcm and
+        out are arrays with the layout's strides, used in place; out may be pcm itself."""
+        pcm = self._pcm_in(pcm, np.float32)
         T, N, F = pcm.shape
         assert N == self.n and F == self.frame
-        out = np.empty_like(pcm)
+        out = self._pcm_out(out, pcm, np.float32)
         vad = np.empty((T, N), np.float32)
         gains = np.empty((T, N, NB_BANDS), np.float32) if want_gains else None
         if self._L.rnnoise_batch_process(self.h, _fp(out), _fp(pcm), _fp(vad), _fp(gains), T):
             raise RuntimeError("rnnoise_batch_process failed")
         return out, vad, gains
 
-    def process_s16(self, pcm: np.ndarray, want_gains: bool = True):
+    def process_s16(self, pcm: np.ndarray, want_gains: bool = True, out: np.ndarray | None = None):
         """pcm: (T, N, 480) int16 host array -> (out int16, vad[T,N], gains[T,N,32]): rnnoise_batch_process_s16, the
         conversions of examples/rnnoise_demo.c:56,58 done on the device."""
-        pcm = np.ascontiguousarray(pcm, np.int16)
+        pcm = self._pcm_in(pcm, np.int16)
         T, N, F = pcm.shape
         assert N == self.n and F == self.frame
-        out = np.empty_like(pcm)
+        out = self._pcm_out(out, pcm, np.int16)
         vad = np.empty((T, N), np.float32)
         gains = np.empty((T, N, NB_BANDS), np.float32) if want_gains else None
         sp = C.POINTER(C.c_short)
@@ -455,14 +513,12 @@ class Batch:
             raise RuntimeError("rnnoise_batch_process_device failed")
 
     def _masked_args(self, pcm, active, out, dtype):
-        pcm = np.ascontiguousarray(pcm, dtype)
+        pcm = self._pcm_in(pcm, dtype)
         T, N, F = pcm.shape
         assert N == self.n and F == self.frame
         active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
         assert active is None or active.shape == (T, N)
-        if out is None:
-            out = np.zeros_like(pcm)
-        assert out.dtype == dtype and out.shape == pcm.shape and out.flags.c_contiguous
+        out = self._pcm_out(out, pcm, dtype, zero=True)
         return pcm, active, out, T
 
     def process_masked(self, pcm: np.ndarray, active, want_gains: bool = True, out: np.ndarray | None = None):
@@ -496,15 +552,13 @@ class Batch:
             raise RuntimeError("rnnoise_batch_process_device_masked failed")
 
     def _list_args(self, pcm, streams, active, out, dtype):
-        pcm = np.ascontiguousarray(pcm, dtype)
+        pcm = self._pcm_in(pcm, dtype)
         T, R, F = pcm.shape
         streams = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
         assert streams.size == R and F == self.frame
         active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
         assert active is None or active.shape == (T, R)
-        if out is None:
-            out = np.zeros_like(pcm)
-        assert out.dtype == dtype and out.shape == pcm.shape and out.flags.c_contiguous
+        out = self._pcm_out(out, pcm, dtype, zero=True)
         return pcm, streams, active, out, T, R
 
     def _process_list(self, fn, name, pcm, streams, active, want_gains, out, dtype, ptr):

@@ -63,8 +63,13 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     ins = [open(p, "rb") for p in inputs]
     outs = [open(os.path.join(out_dir, os.path.basename(p) + ".denoised.raw"), "wb") for p in inputs]
     vfs = [open(os.path.join(out_dir, os.path.basename(p) + ".vad.csv"), "w") for p in inputs] if vad_csv else None
-    buf = np.zeros((min(chunk_frames, max(T, 1)), N, FRAME), np.int16)
-    rows8 = lambda a: a.view(np.uint8).reshape(a.shape[0], N, 2 * FRAME)  # the same rows as bytes (a companded file's view)
+    # every file's chunk is ONE contiguous run of the staging buffer, [N][chunk frames * FRAME], which the batch reads and writes where
+    # it lies (capi.Batch.set_pcm_layout: frames FRAME apart, files a whole chunk apart) -- no interleaving into frame-major rows here.
+    # `chunk` / `out` below are (frames, N, FRAME) VIEWS of those runs
+    cf = min(chunk_frames, max(T, 1))
+    batch.set_pcm_layout(FRAME, cf * FRAME)
+    buf, obuf = batch.pcm_array(cf, np.int16), batch.pcm_array(cf, np.int16)
+    rows8 = lambda a: a.view(np.uint8)  # the same rows as bytes (a companded file's view): (frames, N, 2 * FRAME)
     for t0 in range(0, T, chunk_frames):
         tn = min(chunk_frames, T - t0)
         chunk = buf[:tn]
@@ -80,7 +85,7 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
                     continue
                 x = np.frombuffer(f.read(k * frame_of[s] * 2), dtype=np.int16)
                 chunk[:k, s, :frame_of[s]] = x.reshape(k, frame_of[s])
-        out, vad, _ = batch.process_s16(chunk, want_gains=False)
+        out, vad, _ = batch.process_s16(chunk, want_gains=False, out=obuf[:tn])
         for s in range(N):
             k = max(0, min(tn, n_frames[s] - t0))
             first = 1 if t0 == 0 else 0  # the demo drops the first output frame (rnnoise_demo.c:59-60)

@@ -232,6 +232,7 @@ bool rate_divisor_ok(int v, int Lb) { return (v == 1 || v == 2 || v == 3 || v ==
 extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
   if (!b || (hz != 48000 && hz != 24000 && hz != 16000 && hz != 8000)) return -1;
   const int old = b->pcm_rate;
+  b->frame_stride = b->row_stride = 0;  // (a PCM layout is in samples of the old rate's frame: dropped by every call)
   if (hz == old && !b->g.rs_Ls) return old;  // (a rate table is dropped by every call: the rows are redefined)
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset: nothing of the old rate is in flight)
@@ -310,6 +311,33 @@ extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates)
 }
 
 extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
+
+// ---- caller-defined PCM strides (include/rnnoise_amd.h) ----
+// Two numbers of the batch.  A process call hands the row stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and steps its frame
+// pointers by the frame stride (batch_process_device_impl); without a layout both keep their defaults and every launch is the one of
+// a batch that never saw these calls.
+extern "C" int rnnoise_batch_set_pcm_layout(RNNoiseBatch *b, long frame_stride, long row_stride) {
+  if (!b || !rn_pcm_layout_ok(frame_stride, row_stride)) return -1;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_pcm_rate: a call in flight keeps what it was launched with)
+  b->frame_stride = frame_stride;
+  b->row_stride = row_stride;
+  return 0;
+}
+
+extern "C" int rnnoise_batch_pcm_layout(const RNNoiseBatch *b, long *frame_stride, long *row_stride) {
+  if (!b) return -1;
+  if (frame_stride) *frame_stride = b->frame_stride;
+  if (row_stride) *row_stride = b->row_stride;
+  return 0;
+}
+
+extern "C" int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_stride, int frame_samples, int n_rows, int n_frames) {
+  return rn_pcm_layout_ok(frame_stride, row_stride) && (frame_stride || row_stride) &&
+                 rn_pcm_layout_fits(frame_stride, row_stride, frame_samples, n_rows, n_frames)
+             ? 1
+             : 0;
+}
 
 // ---- per-stream PCM formats (include/rnnoise_amd.h) ----
 // The table lives in fmt_map from the first set on; while one is set (g.pcm_fmt) K0 expands and K3 compresses the rows of the
@@ -496,7 +524,7 @@ extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
 // d_active then have n_rows rows per frame (rn_dev.h: RnGroupDev::list).
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v, float *d_vad, float *d_gains, int n_frames,
                               void *hip_stream, bool s16, const FrameIoHooks *hk, const uint8_t *d_active, const int *d_list,
-                              int n_rows) {
+                              int n_rows, bool packed) {
   if (!b || n_frames < 0) return -1;
   const bool listed = d_list || n_rows;
   if (listed) {
@@ -504,6 +532,12 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     if (n_rows == 0) return 0;
   }
   if (!d_out_v || !d_in_v) return -1;
+  // the caller's PCM layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), unless the buffers are the library's own (packed:
+  // the staged host path; hk: the pinned ring).  Its frame slots must be disjoint, checked before anything is launched or changed
+  const bool laid = b->row_stride && !packed && !hk;
+  if (laid && !rn_pcm_layout_fits(b->frame_stride, b->row_stride, RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1), listed ? n_rows : b->n,
+                                  n_frames))
+    return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
   if ((d_active || listed) && !b->per_stream && n_frames > 0) {
@@ -529,6 +563,9 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   const char *d_in = static_cast<const char *>(d_in_v);
   char *d_out = static_cast<char *>(d_out_v);
   auto buf = [&](int f) -> size_t { return hk ? (size_t)(f % hk->ring) : (size_t)f; };  // frame f's place in the caller's buffers
+  // bytes between the frames of the PCM buffers, and the row pitch K0 / K3 get (0: the form's own constant -- today's arguments)
+  const size_t fstep = (laid ? (size_t)b->frame_stride : N * fl) * esz;
+  const int pcm_pitch = laid ? (int)b->row_stride : 0;
   // Multi-frame calls are software-pipelined over three streams: C runs the high-pass of frames up to
   // f+2, B the analysis of frame f+1, A (the caller's stream) network + synthesis of frame f.
   // What makes that legal:
@@ -570,6 +607,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   }
   auto frame_group = [&](int f) {
     RnGroupDev g = b->g;
+    g.pcm_pitch = pcm_pitch;
     const int c = (int)((b->frame_no + f) & 1);
     g.features = b->features2[c];
     g.silence = b->silence2[c];
@@ -605,8 +643,9 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
       TimedLaunch t(b, 3);
       b->cur_hp[f & 7] = t.on ? t.stop() : (pipelined ? b->own_hp[f & 7] : nullptr);
       RnGroupDev gh = b->g;
+      gh.pcm_pitch = pcm_pitch;
       phased(gh, f);
-      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * N * fl * esz, s16, (b->ring_slot + f) % RN_RING_SLOTS, plan.hp, sc, t.start(),
+      HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * fstep, s16, (b->ring_slot + f) % RN_RING_SLOTS, plan.hp, sc, t.start(),
                           b->cur_hp[f & 7]));
     }
     if (hk && hk->after_hp(f, sc)) return -1;
@@ -671,7 +710,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     {
       TimedLaunch t(b, 2);
       b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
-      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * N * fl * esz, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
+      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * fstep, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
     }
     if (hk && hk->after_k3(f, st)) return -1;
     // (schedule 1: the high-pass three frames ahead goes out HERE, behind the synthesis launch whose end it starts at)
@@ -710,31 +749,49 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
 
 // The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
 // ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
-// the caller left them.  The masked host calls, every host call at a PCM rate other than 48 kHz or with a rate table, and the int16
-// host calls of a batch with a format table come here.
+// the caller left them.  The masked host calls, every host call at a PCM rate other than 48 kHz or with a rate table, the int16
+// host calls of a batch with a format table, and every host call of a batch with a PCM layout come here.
 // A list call (list set: n_rows host int32 entries, checked by the caller) stages the list too, and its buffers have n_rows rows.
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
                          int n_frames, bool s16, const int *list, int n_rows) {
   if (!b || !out || !in || n_frames < 0) return -1;
   if (n_frames == 0) return 0;
-  ON_DEVICE(b->device);
   const size_t rows = list ? n_rows : b->n;
-  const size_t fs = (size_t)n_frames * rows, pcm = fs * (RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1)) * (s16 ? 2 : 4);
+  const size_t M = RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1), esz = s16 ? 2 : 4;
+  // a caller-defined layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): the frame slots travel by strided copies between
+  // the caller's buffers and the default layout in device memory -- one 2-D copy per frame, its rows row_stride apart --, so the
+  // device runs the launches of the default layout and nothing but the slots themselves is read or written on the host
+  const bool laid = b->row_stride != 0;
+  if (laid && !rn_pcm_layout_fits(b->frame_stride, b->row_stride, (int)M, (int)rows, n_frames)) return -1;
+  ON_DEVICE(b->device);
+  auto pcm_copy = [&](void *dst, const void *src, bool up) -> bool {
+    if (!laid) return hipMemcpy(dst, src, (size_t)n_frames * rows * M * esz, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) == hipSuccess;
+    const size_t hp = (size_t)b->row_stride * esz, hf = (size_t)b->frame_stride * esz, dp = M * esz, df = rows * dp;
+    for (int f = 0; f < n_frames; f++) {
+      const hipError_t e = up ? hipMemcpy2D(static_cast<char *>(dst) + f * df, dp, static_cast<const char *>(src) + f * hf, hp, dp, rows,
+                                            hipMemcpyHostToDevice)
+                              : hipMemcpy2D(static_cast<char *>(dst) + f * hf, hp, static_cast<const char *>(src) + f * df, dp, dp, rows,
+                                            hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return false;
+    }
+    return true;
+  };
+  const size_t fs = (size_t)n_frames * rows, pcm = fs * M * esz;
   const size_t o_in = 0, o_out = pcm, o_vad = 2 * pcm, o_gains = o_vad + fs * 4, o_act = o_gains + fs * RN_NB_BANDS * 4,
                o_list = (o_act + fs + 255) & ~size_t(255), total = o_list + (list ? rows * sizeof(int) : 0);
   char *d = nullptr;
   HIP_OK(hipMalloc((void **)&d, total));
   int rc = -1;
-  if (hipMemcpy(d + o_in, in, pcm, hipMemcpyHostToDevice) == hipSuccess &&
+  if (pcm_copy(d + o_in, in, true) &&
       // (absent rows, and the part of a row behind the frame of a stream of a rate table or behind a companded stream's bytes, keep
       //  the caller's values)
-      ((!active && !list && !b->g.rs_Ls && !(s16 && b->g.pcm_fmt)) || hipMemcpy(d + o_out, out, pcm, hipMemcpyHostToDevice) == hipSuccess) &&
+      ((!active && !list && !b->g.rs_Ls && !(s16 && b->g.pcm_fmt)) || pcm_copy(d + o_out, out, true)) &&
       (!active || hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess) &&
       (!list || hipMemcpy(d + o_list, list, rows * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
       batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,
                                 n_frames, nullptr, s16, nullptr, active ? (const uint8_t *)(d + o_act) : nullptr,
-                                list ? (const int *)(d + o_list) : nullptr, list ? n_rows : 0) == 0 &&
-      hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d + o_out, pcm, hipMemcpyDeviceToHost) == hipSuccess &&
+                                list ? (const int *)(d + o_list) : nullptr, list ? n_rows : 0, true) == 0 &&
+      hipDeviceSynchronize() == hipSuccess && pcm_copy(out, d + o_out, false) &&
       (!vad || hipMemcpy(vad, d + o_vad, fs * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
       (!gains || hipMemcpy(gains, d + o_gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost) == hipSuccess))
     rc = 0;
@@ -842,7 +899,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
                                                    void *hip_stream) {
   if (!b || !d_records || !d_clean || !d_noisy || !d_vad || !d_lowpass || !d_band_lp || !d_noise_free || n_frames < 0)
     return -1;
-  if (b->per_stream || b->g.rs_L) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz, only)
+  if (b->per_stream || b->g.rs_L || b->row_stride) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz, in the default PCM layout, only)
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
   const size_t N = b->n;
@@ -865,7 +922,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
 extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, const float *clean, const float *noisy,
                                             const float *vad, const int *lowpass, const int *band_lp,
                                             const int *noise_free, int n_frames) {
-  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L)
+  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->row_stride)
     return -1;
   ON_DEVICE(b->device);
   const size_t N = b->n, fb = (size_t)n_frames * N * RN_FRAME_SIZE * 4;

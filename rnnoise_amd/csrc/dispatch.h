@@ -145,3 +145,20 @@ static inline RnSchedule rn_schedule(const RnKnobs &k, int n_frames, int batch_s
 
 // The network path of a new batch: the MFMA tiles above rn_nn_one_kernel's range (and from one whole tile up), the vector path below.
 static inline int rn_default_nn_path(const RnKnobs &k, int n) { return n > k.nn_one_max && n >= 16 ? 1 : 0; }
+
+// ---- caller-defined PCM strides (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout) ----
+// what the setter accepts: the default (0, 0), or two positive multiples of 4 samples (the row stride an int: the kernels' row pitch)
+static inline bool rn_pcm_layout_ok(long frame_stride, long row_stride) {
+  if (frame_stride == 0 && row_stride == 0) return true;
+  return frame_stride > 0 && row_stride > 0 && frame_stride % 4 == 0 && row_stride % 4 == 0 && row_stride <= 2147483647L;
+}
+// whether the frame slots of a call -- n_frames x n_rows slots of M samples, slot (f, r) at f * frame_stride + r * row_stride -- are
+// disjoint: rows inside a frame (row-major) or frames inside a row (stream-contiguous).  A call with no slot fits.
+static inline bool rn_pcm_layout_fits(long frame_stride, long row_stride, int M, int n_rows, int n_frames) {
+  if (M <= 0 || n_rows < 0 || n_frames < 0 || frame_stride <= 0 || row_stride <= 0) return false;
+  if (n_rows == 0 || n_frames == 0) return true;
+  typedef long long ll;
+  const bool row_major = row_stride >= M && (ll)frame_stride >= (ll)n_rows * row_stride;
+  const bool stream_contiguous = frame_stride >= M && (ll)row_stride >= (ll)n_frames * frame_stride;
+  return row_major || stream_contiguous;
+}

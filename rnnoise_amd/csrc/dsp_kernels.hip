@@ -1711,9 +1711,11 @@ __device__ __forceinline__ void rn_list_outputs(const RnGroupDev &g, const RnStr
     g.list_gains[(size_t)at.i * RN_NB_BANDS + lane] = at.present ? g.gains[(size_t)at.s * RN_NB_BANDS + lane] : 0.f;
   if (g.list_vad && lane == 0) g.list_vad[at.i] = at.present ? g.vad[at.s] : 0.f;
 }
+// out_pitch: samples (of the output's type) between rows of `out` -- RN_FRAME_SIZE, or the caller's layout where `out` is the caller's
+// buffer (rn_dev.h: RnGroupDev::pcm_pitch; the kernels below)
 template <bool LATE>
 __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTablesDev &tb, float *__restrict__ out, int parity_arg,
-                                               const RnStreamAt &at) {
+                                               const RnStreamAt &at, size_t out_pitch) {
   // bit 8 of parity_arg: `out` holds int16 samples, written with the truncating conversion of the reference's only caller
   // (examples/rnnoise_demo.c:58: tmp[i] = x[i], float -> short as x86 compiles it: cvttss2si to 32 bits -- "integer
   // indefinite" 0x80000000 when out of range or NaN -- then the low 16 bits).  Bits 11-12 (rn_fmt_arg, only beside bit 8): the row
@@ -1901,7 +1903,8 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     }
   }
   // window + overlap-add (src/denoise.c:400-407), straight from the registers
-  float *o = listed ? at.io + RN_ROW_OUT : out + (size_t)at.i * RN_FRAME_SIZE;  // (the caller's row: rn_dev.h RnStreamAt::i)
+  const size_t row0 = (size_t)at.i * out_pitch;  // (the caller's row: rn_dev.h RnStreamAt::i)
+  float *o = listed ? at.io + RN_ROW_OUT : out + row0;
 #pragma unroll
   for (int b = 0; b < 15; b++) {
     bool lo;
@@ -1916,8 +1919,8 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       const float r = v + smv[b];
       if (out_s16) {
         const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-        if (out_fmt) reinterpret_cast<uint8_t *>(out)[(size_t)at.i * RN_FRAME_SIZE * sizeof(short) + n] = (uint8_t)rn_g711_encode(out_fmt, (short)q);
-        else reinterpret_cast<short *>(out)[(size_t)at.i * RN_FRAME_SIZE + n] = (short)q;
+        if (out_fmt) reinterpret_cast<uint8_t *>(out)[row0 * sizeof(short) + n] = (uint8_t)rn_g711_encode(out_fmt, (short)q);
+        else reinterpret_cast<short *>(out)[row0 + n] = (short)q;
       } else {
         o[n] = r;
       }
@@ -1942,13 +1945,14 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
 // compiled a second time and L is a run-time value, so that the epilogue stays inside the registers of the body.
 // Called only for a stream that has this frame (rn_stream_at: RnStreamAt::present).
 // L: the batch's divisor or, with a rate table, the stream's own (rn_dev.h: rn_stream_L; never 1 here); the caller's rows are
-// g.rs_pitch samples apart and the stream's 480 / L outputs fill the front of its row.
+// g.rs_pitch samples apart (g.pcm_pitch in a caller-defined layout) and the stream's 480 / L outputs fill the front of its row.
 // fmt: a companded stream's law (bits 11-12 of parity_arg: rn_fmt_arg), its int16 values going out as the first 480 / L bytes of the row.
 __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row, int L, int fmt) {
   void *out = g.rs_out;
   const int lane = threadIdx.x, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
   const float *body = g.rs_dn + (size_t)row * RN_FRAME_SIZE;  // (the body wrote its output row: the caller's row, RnStreamAt::i)
+  const size_t row0 = (size_t)row * rn_pcm_pitch(g, g.rs_pitch);
   const float *ht = rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
   float *h = vs + RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE;
   __syncthreads();  // (the body's stores to rs_dn, by other lanes)
@@ -1982,10 +1986,10 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
     const float r = (a0 + a1) + (a2 + a3);
     if (out_s16) {  // (the truncating conversion of the 48 kHz calls: synthesis_body)
       const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-      if (fmt) static_cast<uint8_t *>(out)[(size_t)row * g.rs_pitch * sizeof(short) + m] = (uint8_t)rn_g711_encode(fmt, (short)q);
-      else static_cast<short *>(out)[(size_t)row * g.rs_pitch + m] = (short)q;
+      if (fmt) static_cast<uint8_t *>(out)[row0 * sizeof(short) + m] = (uint8_t)rn_g711_encode(fmt, (short)q);
+      else static_cast<short *>(out)[row0 + m] = (short)q;
     } else {
-      static_cast<float *>(out)[(size_t)row * g.rs_pitch + m] = r;
+      static_cast<float *>(out)[row0 + m] = r;
     }
   }
   // the new history: the frame's last 47 L samples
@@ -2018,7 +2022,8 @@ rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int p
   float *body_out = out;
   const int rs_L = rs_divert(g, at, body_out, parity_arg);
   parity_arg = rn_fmt_arg(g, at, parity_arg);
-  synthesis_body<true>(g, tb, body_out, parity_arg, at);
+  // (the body writes the caller's buffer -- in the caller's layout -- except in front of the epilogue, where it writes rs_dn)
+  synthesis_body<true>(g, tb, body_out, parity_arg, at, rs_L > 1 ? (size_t)RN_FRAME_SIZE : rn_pcm_pitch(g, RN_FRAME_SIZE));
   if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L, (parity_arg >> 11) & 3);
@@ -2031,7 +2036,7 @@ rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, i
   float *body_out = out;
   const int rs_L = rs_divert(g, at, body_out, parity_arg);  // (bit 9 is never set for a row list)
   parity_arg = rn_fmt_arg(g, at, parity_arg);
-  synthesis_body<false>(g, tb, body_out, parity_arg, at);
+  synthesis_body<false>(g, tb, body_out, parity_arg, at, rs_L > 1 ? (size_t)RN_FRAME_SIZE : rn_pcm_pitch(g, RN_FRAME_SIZE));
   if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L, (parity_arg >> 11) & 3);

@@ -39,8 +39,9 @@ __device__ __forceinline__ void rs_wsync() {
 template <int IN>
 __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, int row, float *xs, int L, int fmt = 0) {
   // (M: the stream's samples per frame; its row starts at row * rs_pitch -- M of the batch's rate, which a stream of a rate table may
-  //  fill only in part: rn_dev.h RnGroupDev::rs_Ls)
+  //  fill only in part: rn_dev.h RnGroupDev::rs_Ls -- or at row * pcm_pitch in a caller-defined layout)
   const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
+  const size_t row0 = (size_t)row * rn_pcm_pitch(g, g.rs_pitch);
   float *hu = xs + RN_RS_XS;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
   // (loads and LDS stores at clamped indices, without a branch: a lane past the end rewrites the last element with its own value)
@@ -50,8 +51,8 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
 #pragma unroll
   for (int i = 0; i < NX; i++) {
     const int m = min(lane + WAVE * i, M - 1);
-    const size_t q = (size_t)row * g.rs_pitch + m;  // (row: the caller's row of stream s, RnStreamAt::i)
-    if (IN == 2) rx[i] = (float)rn_g711_decode(fmt, static_cast<const uint8_t *>(in)[(size_t)row * g.rs_pitch * sizeof(short) + m]);
+    const size_t q = row0 + m;  // (row: the caller's row of stream s, RnStreamAt::i)
+    if (IN == 2) rx[i] = (float)rn_g711_decode(fmt, static_cast<const uint8_t *>(in)[row0 * sizeof(short) + m]);
     else rx[i] = IN == 1 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
   }
   const float *ht = rs_up_taps(L);
@@ -113,7 +114,10 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
   const double na0 = -(double)a0, na1 = -(double)a1, b0d = (double)b0;
   float m0 = g.mem_hp[2 * s], m1 = g.mem_hp[2 * s + 1];
-  const float4 *x = reinterpret_cast<const float4 *>(in + (size_t)s * RN_FRAME_SIZE);
+  // (the lane's row of the caller's buffer: one 64-bit product per lane, here, outside the block loop; the pitch is wave-uniform and a
+  //  multiple of 4 samples, so the float4 / short4 loads keep their alignment -- rn_dev.h: RnGroupDev::pcm_pitch)
+  const size_t row0 = (size_t)s * rn_pcm_pitch(g, RN_FRAME_SIZE);
+  const float4 *x = reinterpret_cast<const float4 *>(in + row0);
   float4 *y = reinterpret_cast<float4 *>(g.pitch_ring + (size_t)s * RN_RING_SIZE + slot * RN_FRAME_SIZE);
   // the slot's 240 decimated samples (rn_dev.h: RN_XRING_SLOT) are formed from the filtered frame as it leaves the registers; the
   // first one needs the last sample of the previous slot
@@ -131,7 +135,7 @@ __device__ __forceinline__ void hp_body(const RnGroupDev &g, const float *__rest
   //  kernel's register budget -- four waves per SIMD, which the lock-step forms need -- spilled over)
   constexpr int BLK = PHASED ? RN_HP_BLK / 2 : RN_HP_BLK;  // float4 per block
   float4 cur[BLK], nxt[BLK];
-  const short4 *x16 = reinterpret_cast<const short4 *>(reinterpret_cast<const short *>(in) + (size_t)s * RN_FRAME_SIZE);
+  const short4 *x16 = reinterpret_cast<const short4 *>(reinterpret_cast<const short *>(in) + row0);
   auto load4 = [&](int idx) -> float4 {
     if (in_s16) {
       const short4 q = x16[idx];
@@ -474,11 +478,13 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
       in_s16 &= 1;  // a 48 kHz stream of a rate table: its row is a whole frame (rows are 480 apart), read in place below
     }
   }
-  // the caller's row i (rn_dev.h: RnStreamAt::i -- stream s's own row except in a list call)
+  // the caller's row i (rn_dev.h: RnStreamAt::i -- stream s's own row except in a list call), RnGroupDev::pcm_pitch samples of the
+  // call's type from row i - 1 (a companded row keeps its int16 pitch: its byte base is row * pitch * sizeof(short))
+  const size_t row0 = (size_t)at.i * rn_pcm_pitch(g, RN_FRAME_SIZE);
   const void *in_row = at.listed ? static_cast<const void *>(at.io + RN_ROW_IN)
                        : rs_row ? static_cast<const void *>(rs_row)
-                       : (in_s16 & 1) ? static_cast<const void *>(reinterpret_cast<const short *>(in) + (size_t)at.i * RN_FRAME_SIZE)
-                                      : static_cast<const void *>(in + (size_t)at.i * RN_FRAME_SIZE);
+                       : (in_s16 & 1) ? static_cast<const void *>(reinterpret_cast<const short *>(in) + row0)
+                                      : static_cast<const void *>(in + row0);
   if (in_s16 && fmt) hp_one_body<2>(L, g, in_row, at.listed, s, at.ring, fmt);
   else if (in_s16) hp_one_body<1>(L, g, in_row, at.listed, s, at.ring);
   else hp_one_body<0>(L, g, in_row, at.listed, s, at.ring);

@@ -189,6 +189,12 @@ struct RnGroupDev {
   // and K3's body writes it in place, no filter runs and the stream's history is not touched.
   const uint8_t *rs_Ls;        // [N] or null
   int rs_pitch;
+  // Caller-defined PCM layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout).  0: the caller's rows are the form's own constant
+  // apart -- RN_FRAME_SIZE samples, or rs_pitch on a resampling launch (every launch is today's).  Otherwise the samples (of the call's
+  // type: float or int16; a companded row keeps its int16 pitch) between the caller's rows i and i + 1 of `in` and `out`, a multiple
+  // of 4 (rn_pcm_pitch).  Only K0 and K3 look at it, and only where they address the caller's buffers: the scratch rows rs_up / rs_dn
+  // stay RN_FRAME_SIZE apart.  The frame pitch is the host's: the launchers get each frame's base pointer (batch.cpp).
+  int pcm_pitch;
   // Per-stream PCM formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats).  Null pcm_fmt: every row of an int16 call holds
   // int16 samples (every launch is today's).  Set, stream s's rows of the int16 calls hold pcm_fmt[s]: RN_PCM_ULAW / RN_PCM_ALAW
   // (g711.h) one byte per sample in the FIRST 480 / L_s bytes of the row -- K0 expands them where it reads the row (hp_one_body,
@@ -385,6 +391,8 @@ __device__ __forceinline__ int rn_stream_L(const RnGroupDev &g, int s) {
   const int v = __builtin_amdgcn_readfirstlane((int)*(__attribute__((address_space(1))) const uint8_t *)(g.rs_Ls + s));
   return ((v == 1 || v == 2 || v == 3 || v == 6) && v >= g.rs_L) ? v : g.rs_L;
 }
+// Samples between the caller's PCM rows (rn_dev.h: RnGroupDev::pcm_pitch): the layout's, or `own` -- the form's constant -- without one
+__device__ __forceinline__ size_t rn_pcm_pitch(const RnGroupDev &g, int own) { return (size_t)(g.pcm_pitch ? g.pcm_pitch : own); }
 // PCM format of stream s's rows in an int16 call (rn_dev.h: RnGroupDev::pcm_fmt): RN_PCM_ULAW, RN_PCM_ALAW, or 0 for int16 rows -- no
 // table, or a byte that names neither law.  s is the workgroup's one stream: the result is wave-uniform
 __device__ __forceinline__ int rn_stream_fmt(const RnGroupDev &g, int s) {

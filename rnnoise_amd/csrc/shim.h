@@ -189,6 +189,10 @@ struct RNNoiseBatch {
   // the int16 calls (rn_dev.h: RnGroupDev::pcm_fmt) -- allocated by the first table, like model_map; g.pcm_fmt points at it while a
   // table is set.  Configuration, not state: no reset, import, load or rate change touches it
   uint8_t *fmt_map = nullptr;
+  // caller-defined PCM strides (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), in samples; both 0: the default layout.  The
+  // process calls hand row_stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and step their frame pointers by frame_stride; b->g
+  // itself never carries a pitch.  Configuration, not state
+  long frame_stride = 0, row_stride = 0;
   // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
   // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of) -- allocated by the first
   // add_model, like rs_buf by the first rate change; g.model_of / g.n_models are set from then on
@@ -329,7 +333,8 @@ RnGroupDev group_view(const RnGroupDev &g, int first, int count);    // batch.cp
 const RnKnobs &rn_knobs();                                           // batch.cpp: the dispatch switches, read once per process
 int batch_process_device_impl(RNNoiseBatch *b, void *d_out, const void *d_in, float *d_vad, float *d_gains, int n_frames,
                               void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr,
-                              const uint8_t *d_active = nullptr, const int *d_list = nullptr, int n_rows = 0);  // batch.cpp
+                              const uint8_t *d_active = nullptr, const int *d_list = nullptr, int n_rows = 0,
+                              bool packed = false);  // batch.cpp (packed: the buffers are in the default layout whatever the batch's)
 void host_io_release(RNNoiseBatch *b);                               // host_io.cpp
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
                          int n_frames, bool s16, const int *list = nullptr,

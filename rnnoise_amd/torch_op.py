@@ -75,6 +75,22 @@ def register_torch_op():
         T, R = pcm.shape[0], pcm.shape[1]
         return torch.empty_like(pcm), pcm.new_empty((T, R)), pcm.new_empty((T, R, capi.NB_BANDS))
 
+    # the stream-contiguous form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): pcm (N, T * (480 // L)) float32 or int16, one
+    # contiguous run of samples per stream -- the [B, T] tensor a torch user holds, read and written where it lies, no transpose.
+    # active (T, N) or None, as in process_masked.  Returns out (same shape and dtype as pcm), vad (T, N), gains (T, N, 32).
+    @torch.library.custom_op("rnnoise_amd::process_streams", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor? active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)")
+    def process_streams(pcm, active, state, handle):
+        op = _OPS[handle]
+        res = op._run_streams(pcm, active)
+        state.add_(pcm.shape[1] // op.batch.frame)
+        return res
+
+    @process_streams.register_fake
+    def _(pcm, active, state, handle):
+        N, T = pcm.shape[0], pcm.shape[1] // _OPS[handle].batch.frame
+        return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
+
     _registered = True
 
 
@@ -132,6 +148,14 @@ class RNNoiseOp:
         """pcm (T, R, 480 // L) float32 CUDA tensor whose row i is stream idx[i] (an (R,) int32 CUDA tensor), active (T, R) bool / uint8
         CUDA tensor or None: only the listed streams advance, with compact buffers (torch.ops.rnnoise_amd.process_list)"""
         return self.torch.ops.rnnoise_amd.process_list(pcm, idx, active, self.state, self.handle)
+
+    def process_streams(self, pcm, active=None):
+        """pcm (N, T * (480 // L)) float32 or int16 CUDA tensor, stream-contiguous: row s is T consecutive frames of stream s.  The
+        batch reads it and writes the result of the same shape where they lie (rnnoise_batch_set_pcm_layout: no transpose to frame-
+        major and back); active (T, N) bool / uint8 or None as in process_masked.  -> out (N, T * (480 // L)), vad (T, N), gains
+        (T, N, 32) (torch.ops.rnnoise_amd.process_streams).  The layout is set when it changes -- a synchronous call, so keep T and
+        the entry point the same from call to call."""
+        return self.torch.ops.rnnoise_amd.process_streams(pcm, active, self.state, self.handle)
 
     def reset_streams(self, idx):
         """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
@@ -206,9 +230,38 @@ class RNNoiseOp:
         """no controls: every stream back to the reference's suppression (the table and the gate counters are dropped)"""
         self.batch.set_stream_controls(None)
 
+    def _layout(self, frame_stride, row_stride):
+        # (the setter drains the device: called only when the layout changes)
+        if self.batch.pcm_layout != (frame_stride, row_stride):
+            self.batch.set_pcm_layout(frame_stride, row_stride)
+
+    def _run_streams(self, pcm, active=None):
+        torch = self.torch
+        M = self.batch.frame
+        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2
+        assert pcm.shape[0] == self.n and pcm.shape[1] % M == 0 and pcm.shape[1] > 0
+        pcm = pcm.contiguous()  # (a [B, T] tensor as torch makes it is: no copy)
+        T = pcm.shape[1] // M
+        s16 = pcm.dtype == torch.int16
+        self._layout(M, T * M)
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
+        gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        if active is None:
+            out = torch.empty_like(pcm)
+            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream, s16=s16)
+        else:
+            assert active.is_cuda and active.shape == (T, self.n)
+            act = (active != 0).to(torch.uint8).contiguous()
+            out = torch.zeros_like(pcm)
+            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream,
+                                             s16=s16)
+        return out, vad, gains
+
     def _run(self, pcm, active=None):
         torch = self.torch
         assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[1:] == (self.n, self.batch.frame)
+        self._layout(0, 0)
         pcm = pcm.contiguous()
         T = pcm.shape[0]
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
@@ -228,6 +281,7 @@ class RNNoiseOp:
         torch = self.torch
         assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.dim() == 3 and pcm.shape[2] == self.batch.frame
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.numel() == pcm.shape[1]
+        self._layout(0, 0)
         pcm, idx = pcm.contiguous(), idx.contiguous()
         T, R = pcm.shape[0], pcm.shape[1]
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
