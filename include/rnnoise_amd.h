@@ -261,6 +261,43 @@ RNNOISE_EXPORT int rnnoise_batch_set_pcm_layout(RNNoiseBatch *b, long frame_stri
 RNNOISE_EXPORT int rnnoise_batch_pcm_layout(const RNNoiseBatch *b, long *frame_stride, long *row_stride);
 RNNOISE_EXPORT int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_stride, int frame_samples, int n_rows, int n_frames);
 
+/* Interleaved multichannel PCM: a channel count for the rows.  With C = channels > 1 the rows of every rnnoise_batch_process* call
+ * are taken C at a time: row r = C * g + c is channel c of group g (r: the list position in a list call, the stream index in every
+ * other call), and sample i of frame f of row r lies at
+ *     f * frame_stride + g * row_stride + i * C + c
+ * in `in` and in `out`, in SAMPLES of the call's own type, M = 480 / Lb samples per row and frame (Lb the batch's divisor).  Each
+ * channel is a stream of its own -- state, model slot, controls, rate, format, mask bit and list entry are per row as before; only
+ * where its samples lie changes.  So stereo LRLR... from a WAV file or a capture device, or a [B][T][C] tensor, is passed where it
+ * lies, with no de-interleaving pass before the call and no re-interleaving pass after it.
+ * Without a layout row_stride = M * C and frame_stride = (n_rows / C) * M * C: each frame is [n_rows / C][M][C].  With a layout
+ * (rnnoise_batch_set_pcm_layout, in either order with this call) the caller's two strides apply and row_stride is the distance between
+ * GROUPS: a [G][T][C] tensor is frame_stride = M * C, row_stride = n_frames * M * C.  Stride validity is unchanged (positive multiples
+ * of 4 samples: every group slot stays 16 / 8-byte aligned), and the no-overlap rule is rnnoise_amd_pcm_layout_fits with the slot
+ * size M * C and n_rows / C groups (rnnoise_amd_pcm_channels_fit: 1 / 0, host only; for channels == 1 it equals
+ * rnnoise_amd_pcm_layout_fits; 0 when n_rows % channels != 0) -- a call whose slots overlap returns -1 with nothing launched.
+ * A stream below the batch's rate uses the positions i * C + c for i < 480 / L_s only; a companded stream holds one BYTE at byte
+ * offset i * C + c of its group slot -- so the channels of one group must all be linear or all be companded (either law, any rates):
+ * next to a linear channel's int16 samples those bytes would share positions, and what such a group gives is undefined.
+ * Every other position of the slot, and all padding, is neither read nor written: a masked or
+ * list call in which a channel of a group is absent leaves that channel's samples in `out` as they were and writes its siblings'.
+ * vad, gains and active keep their [n_frames][n_rows] shapes, one entry per row; `in` may alias `out`.  Every stream gives bit for
+ * bit -- out, vad, gains, complete state -- what it gives when the same samples are passed planar, in every call form: lock-step,
+ * masked and list; float and int16; device and host; with a rate table, a format table, model slots, controls, resets, snapshots.
+ * rnnoise_batch_set_pcm_channels returns the previous count; -1 with nothing changed for a NULL batch, channels < 1, channels >
+ * RNNOISE_AMD_MAX_CHANNELS or n_streams % channels != 0.  Synchronous, like rnnoise_batch_set_pcm_layout.  channels == 1 drops the
+ * feature: the batch then launches exactly what a batch that never saw the call launches.  A list call whose n_rows % C != 0
+ * returns -1 with nothing launched.  Host-buffer calls with C > 1 take the staged convenience path (whole group slots copied to
+ * device memory and back); the pinned-ring path of rnnoise_batch_process[_s16] serves C == 1 only.
+ * A channel count is configuration, not state: rnnoise_batch_reset, reset_streams[_device], import_state, load_streams and every table
+ * setter leave it alone, and it is in no snapshot.  rnnoise_batch_set_pcm_rate leaves it alone too (a count does not depend on M;
+ * that call still drops the layout).  rnnoise_batch_train_features* returns -1 while C > 1.
+ * rnnoise_batch_pcm_channels: the count in force, 1 by default; -1 for a NULL batch, without touching the device. */
+#define RNNOISE_AMD_MAX_CHANNELS 8
+RNNOISE_EXPORT int rnnoise_batch_set_pcm_channels(RNNoiseBatch *b, int channels);
+RNNOISE_EXPORT int rnnoise_batch_pcm_channels(const RNNoiseBatch *b);
+RNNOISE_EXPORT int rnnoise_amd_pcm_channels_fit(long frame_stride, long row_stride, int frame_samples, int channels, int n_rows,
+                                                int n_frames);
+
 /* Several models in one batch: every stream runs with the model of its SLOT.  Slot 0 is the model the batch was created with;
  * rnnoise_batch_add_model puts another one into the next free slot (1 .. RNNOISE_AMD_MAX_MODELS - 1) and returns that slot: -1 on a
  * NULL batch or model, a full table, or a model that cannot be put on the batch's device.  Synchronous.  The model must outlive the

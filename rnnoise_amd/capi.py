@@ -61,7 +61,9 @@ EXPORTS = [
     "rnnoise_batch_set_stream_rates", "rnnoise_batch_set_stream_rates_device", "rnnoise_batch_stream_rates",
     "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
     "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
+    "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
 ]
+MAX_CHANNELS = 8  # RNNOISE_AMD_MAX_CHANNELS: interleaved channels of a batch's PCM rows
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)
 CTL_FLOATS = 3  # RNNOISE_AMD_CTL_FLOATS: {floor, thr, hold} per stream (rnnoise_batch_set_stream_controls)
@@ -193,6 +195,9 @@ def _load(path, debug):
         L.rnnoise_batch_set_pcm_layout.argtypes = [vp, C.c_long, C.c_long]
         L.rnnoise_batch_pcm_layout.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
         L.rnnoise_amd_pcm_layout_fits.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int]
+        L.rnnoise_batch_set_pcm_channels.argtypes = [vp, C.c_int]
+        L.rnnoise_batch_pcm_channels.argtypes = [vp]
+        L.rnnoise_amd_pcm_channels_fit.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int]
         L.rnnoise_batch_add_model.argtypes = [vp, vp]
         L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
         L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
@@ -242,6 +247,13 @@ def log10_model() -> str:
     """which log10 the feature stage evaluates: "host=glibc-fma" (the host libm's algorithm restated on the device) | "glibc-fma" |
     "ocml" | "host=unknown:ocml" (include/rnnoise_amd.h; $RNNOISE_AMD_LOG10)"""
     return lib().rnnoise_amd_log10_model().decode()
+
+
+def pcm_channels_fit(frame_stride: int, row_stride: int, frame_samples: int, channels: int, n_rows: int, n_frames: int) -> bool:
+    """whether the group slots of a call with `channels` interleaved channels are disjoint under a PCM layout
+    (rnnoise_amd_pcm_channels_fit: n_frames x n_rows // channels slots of frame_samples * channels samples; host only)"""
+    return bool(lib().rnnoise_amd_pcm_channels_fit(int(frame_stride), int(row_stride), int(frame_samples), int(channels), int(n_rows),
+                                                   int(n_frames)))
 
 
 def _fp(a):
@@ -373,27 +385,60 @@ class Batch:
             raise RuntimeError("rnnoise_batch_pcm_layout failed")
         return int(f.value), int(r.value)
 
+    def set_pcm_channels(self, channels: int = 1) -> int:
+        """interleaved channels (rnnoise_batch_set_pcm_channels): with C = channels > 1 the rows of every call are taken C at a time,
+        row C * g + c being channel c of group g, its sample i at i * C + c of the group's slot -- stereo LRLR... is C = 2.  Returns the
+        previous count; ValueError (nothing changes) unless 1 <= channels <= MAX_CHANNELS and channels divides the batch's streams.
+        With C > 1 the host calls take and return (T, rows // C, frame, C) arrays; vad / gains / active stay (T, rows[, 32])."""
+        r = self._L.rnnoise_batch_set_pcm_channels(self.h, int(channels))
+        if r < 0:
+            raise ValueError(f"{channels} PCM channels unsupported (1 .. {MAX_CHANNELS}, a divisor of the batch's {self.n} streams)")
+        return r
+
+    @property
+    def pcm_channels(self) -> int:
+        return self._L.rnnoise_batch_pcm_channels(self.h)
+
     def pcm_array(self, n_frames: int, dtype=np.float32, rows: int | None = None, fill=0):
         """a (n_frames, rows, frame) view, in the batch's PCM layout, of a fresh buffer that spans its frame slots and is filled with
-        `fill` (rows: the batch's streams, or the rows of a list call); with a layout set `.base` is the flat buffer"""
+        `fill` (rows: the batch's streams, or the rows of a list call); with a layout set `.base` is the flat buffer.  With C > 1
+        interleaved channels (set_pcm_channels): a (n_frames, rows // C, frame, C) view"""
         rows = self.n if rows is None else rows
         fs, rs = self.pcm_layout
+        ch = self.pcm_channels
+        if ch > 1:
+            assert rows % ch == 0
+            g, it = rows // ch, np.dtype(dtype).itemsize
+            if not rs:
+                return np.full((n_frames, g, self.frame, ch), fill, dtype)
+            flat = np.full(max(n_frames - 1, 0) * fs + max(g - 1, 0) * rs + self.frame * ch, fill, dtype)
+            return np.ndarray((n_frames, g, self.frame, ch), flat.dtype, flat, 0, (fs * it, rs * it, ch * it, it))
         if not rs:
             return np.full((n_frames, rows, self.frame), fill, dtype)
         flat = np.full(max(n_frames - 1, 0) * fs + max(rows - 1, 0) * rs + self.frame, fill, dtype)
         it = flat.itemsize
         return np.ndarray((n_frames, rows, self.frame), flat.dtype, flat, 0, (fs * it, rs * it, it))
 
+    @staticmethod
+    def _pcm_dims(pcm):
+        """(T, rows, frame) of a PCM array: (T, rows, frame), or (T, groups, frame, C) with interleaved channels"""
+        if pcm.ndim == 4:
+            return pcm.shape[0], pcm.shape[1] * pcm.shape[3], pcm.shape[2]
+        return pcm.shape
+
     def _pcm_in(self, pcm, dtype):
         """the PCM argument of a host call: a C-contiguous (T, rows, frame) array in the default layout (copied if need be); with a
         layout set, the caller's array as it lies -- its strides must be the layout's"""
         fs, rs = self.pcm_layout
+        ch = self.pcm_channels
+        if ch > 1 and not (np.ndim(pcm) == 4 and np.shape(pcm)[3] == ch):
+            raise ValueError(f"with {ch} interleaved channels the call takes a (T, rows // {ch}, frame, {ch}) array")
         if not rs:
             return np.ascontiguousarray(pcm, dtype)
         it = np.dtype(dtype).itemsize
-        if not (isinstance(pcm, np.ndarray) and pcm.dtype == dtype and pcm.ndim == 3):
-            raise ValueError(f"with a PCM layout set the call takes a 3-D {np.dtype(dtype).name} array in that layout")
-        want = (fs * it, rs * it, it)
+        if not (isinstance(pcm, np.ndarray) and pcm.dtype == dtype and pcm.ndim == (4 if ch > 1 else 3)):
+            raise ValueError(f"with a PCM layout set the call takes a {np.dtype(dtype).name} array in that layout")
+        want = (fs * it, rs * it, ch * it, it) if ch > 1 else (fs * it, rs * it, it)
         if any(n > 1 and st != w for n, st, w in zip(pcm.shape, pcm.strides, want)):
             raise ValueError(f"array strides {pcm.strides} are not the batch's PCM layout {want} (bytes)")
         return pcm
@@ -474,7 +519,7 @@ class Batch:
         """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32]).  With a PCM layout set (set_pcm_layout) pcm and
         out are arrays with the layout's strides, used in place; out may be pcm itself."""
         pcm = self._pcm_in(pcm, np.float32)
-        T, N, F = pcm.shape
+        T, N, F = self._pcm_dims(pcm)
         assert N == self.n and F == self.frame
         out = self._pcm_out(out, pcm, np.float32)
         vad = np.empty((T, N), np.float32)
@@ -487,7 +532,7 @@ class Batch:
         """pcm: (T, N, 480) int16 host array -> (out int16, vad[T,N], gains[T,N,32]): rnnoise_batch_process_s16, the
         conversions of examples/rnnoise_demo.c:56,58 done on the device."""
         pcm = self._pcm_in(pcm, np.int16)
-        T, N, F = pcm.shape
+        T, N, F = self._pcm_dims(pcm)
         assert N == self.n and F == self.frame
         out = self._pcm_out(out, pcm, np.int16)
         vad = np.empty((T, N), np.float32)
@@ -514,7 +559,7 @@ class Batch:
 
     def _masked_args(self, pcm, active, out, dtype):
         pcm = self._pcm_in(pcm, dtype)
-        T, N, F = pcm.shape
+        T, N, F = self._pcm_dims(pcm)
         assert N == self.n and F == self.frame
         active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
         assert active is None or active.shape == (T, N)
@@ -553,7 +598,7 @@ class Batch:
 
     def _list_args(self, pcm, streams, active, out, dtype):
         pcm = self._pcm_in(pcm, dtype)
-        T, R, F = pcm.shape
+        T, R, F = self._pcm_dims(pcm)
         streams = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
         assert streams.size == R and F == self.frame
         active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)

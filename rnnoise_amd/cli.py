@@ -15,6 +15,9 @@ batch; a stream whose file has ended is fed zeros and produces no more output.
 (rnnoise_batch_set_stream_rates), every file read and written at its own rate.
 --formats s16,ulaw,alaw gives every file its own sample format (one per input): a G.711 file is raw companded bytes, one per sample
 (the .ul / .al convention), expanded and compressed on the device (rnnoise_batch_set_stream_formats); its output is written the same way.
+An input that starts with RIFF....WAVE is read as a WAV file (rnnoise_amd/wav.py: PCM16, A-law or mu-law, 1 to 8 channels, 8 to 48 kHz):
+its rate, format and channel count come from its header, each channel is one stream, its samples cross the batch interleaved as they lie
+in the file (rnnoise_batch_set_pcm_channels), and the output is <name>.denoised.wav with the input's header fields.
 """
 from __future__ import annotations
 
@@ -24,10 +27,24 @@ import sys
 
 import numpy as np
 
-from . import capi, g711
+from . import capi, g711, wav
 
 FRAME = capi.FRAME
 SILENCE = {g711.ULAW: 0xFF, g711.ALAW: 0xD5}  # the code of sample 0 (A-law: of +8, its smallest magnitude)
+
+
+def _describe(path, rate, fmt):
+    """what the batch needs to know of one input: a WAV file's header gives rate, format and channel count; a RAW file is mono at
+    the rate and in the format the caller names"""
+    if wav.is_wav(path):
+        info = wav.read_info(path)
+        if fmt is not None and fmt != info.codec:
+            raise ValueError(f"{path}: the header says {info.codec}, --formats says {fmt}")
+        return dict(path=path, wav=info, channels=info.channels, rate=info.rate, codec=info.codec, width=info.width,
+                    offset=info.data_offset, size=info.data_bytes)
+    codec = fmt if fmt is not None else "s16"
+    return dict(path=path, wav=None, channels=1, rate=rate, codec=codec, width=1 if g711.code(codec) else 2, offset=0,
+                size=os.path.getsize(path))
 
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
@@ -39,67 +56,108 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     controls of every file (capi.controls_table); all unset, the batch has no control table.  rates: one sample rate per file, none
     above `rate` (a mixed-rate batch: capi.Batch.set_stream_rates); a file's frames fill the front of its rows.  formats: one of
     "s16", "ulaw", "alaw" per file (capi.Batch.set_stream_formats): a companded file holds one byte per sample, which fill the front of
-    its int16 rows as bytes, and is written back the same way."""
+    its int16 rows as bytes, and is written back the same way.
+    An input that starts with RIFF....WAVE is a WAV file (rnnoise_amd/wav.py): its header gives its rate, its format and its channel
+    count, every channel is one stream, and its samples go through the batch interleaved as they lie in the file
+    (capi.Batch.set_pcm_channels) into <name>.denoised.wav under the input's header fields.  The inputs are grouped by channel count,
+    one batch per distinct count (a RAW file is mono).  Returns the frames of every input."""
     os.makedirs(out_dir, exist_ok=True)
-    FRAME = capi.FRAME * rate // 48000
     if rates is not None and len(rates) != len(inputs):
         raise ValueError(f"{len(rates)} rates for {len(inputs)} files")
-    frame_of = [capi.FRAME * r // 48000 for r in rates] if rates is not None else [FRAME] * len(inputs)  # samples per 10 ms of each file
     if formats is not None and len(formats) != len(inputs):
         raise ValueError(f"{len(formats)} formats for {len(inputs)} files")
-    width = [1 if g711.code(f) else 2 for f in formats] if formats is not None else [2] * len(inputs)  # bytes per sample of each file
-    n_frames = [os.path.getsize(p) // w // fl for p, fl, w in zip(inputs, frame_of, width)]  # partial tail dropped (rnnoise_demo.c:55)
-    N, T = len(inputs), max(n_frames + [0])
+    files = [_describe(p, rates[i] if rates is not None else rate, formats[i] if formats is not None else None)
+             for i, p in enumerate(inputs)]
+    for d in files:
+        if d["rate"] > rate:
+            raise ValueError(f"{d['path']}: {d['rate']} Hz is above the batch's rate {rate} (--rate)")
+        d["frame"] = capi.FRAME * d["rate"] // 48000  # samples per 10 ms and channel
+        d["n_frames"] = d["size"] // (d["width"] * d["channels"]) // d["frame"]  # partial tail dropped (rnnoise_demo.c:55)
+    groups = {}
+    for d in files:
+        groups.setdefault(d["channels"], []).append(d)
     model = capi.Model(model_blob)
+    for channels, group in groups.items():
+        _denoise_group(model, group, channels, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold,
+                       rate_table=rates is not None, format_table=formats is not None)
+    model.close()
+    return [d["n_frames"] for d in files]
+
+
+def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold, rate_table,
+                   format_table):
+    """the files of one channel count C through one batch of len(files) * C streams: file g's channel c is stream g * C + c"""
+    FRAME = capi.FRAME * rate // 48000
+    G, N = len(files), len(files) * C
+    frame_of = [d["frame"] for d in files]
+    width = [d["width"] for d in files]  # bytes per sample of each file
+    n_frames = [d["n_frames"] for d in files]
+    T = max(n_frames + [0])
     batch = capi.Batch(model, N, device=device)
     if rate != 48000:
         batch.set_pcm_rate(rate)
-    if rates is not None:
-        batch.set_stream_rates(rates)
-    if formats is not None:
-        batch.set_stream_formats(formats)
+    if rate_table or any(d["rate"] != rate for d in files):
+        batch.set_stream_rates([d["rate"] for d in files for _ in range(C)])
+    if format_table or any(w == 1 for w in width):
+        batch.set_stream_formats([d["codec"] for d in files for _ in range(C)])
     if atten_limit_db is not None or vad_gate or vad_hold:
         batch.set_stream_controls(capi.controls_table(N, atten_limit_db, vad_gate, vad_hold))
-    ins = [open(p, "rb") for p in inputs]
-    outs = [open(os.path.join(out_dir, os.path.basename(p) + ".denoised.raw"), "wb") for p in inputs]
-    vfs = [open(os.path.join(out_dir, os.path.basename(p) + ".vad.csv"), "w") for p in inputs] if vad_csv else None
-    # every file's chunk is ONE contiguous run of the staging buffer, [N][chunk frames * FRAME], which the batch reads and writes where
-    # it lies (capi.Batch.set_pcm_layout: frames FRAME apart, files a whole chunk apart) -- no interleaving into frame-major rows here.
-    # `chunk` / `out` below are (frames, N, FRAME) VIEWS of those runs
+    if C > 1:
+        batch.set_pcm_channels(C)
+    ins = [open(d["path"], "rb") for d in files]
+    outs = [open(os.path.join(out_dir, os.path.basename(d["path"]) + (".denoised.wav" if d["wav"] else ".denoised.raw")), "wb")
+            for d in files]
+    for d, f, o in zip(files, ins, outs):
+        f.seek(d["offset"])
+        if d["wav"]:  # (the first output frame is dropped, as for a RAW file: the length is known up front)
+            d["out_bytes"] = max(d["n_frames"] - 1, 0) * d["frame"] * d["wav"].block
+            o.write(wav.header(d["wav"], d["out_bytes"]))
+    vfs = [open(os.path.join(out_dir, os.path.basename(d["path"]) + ".vad.csv"), "w") for d in files] if vad_csv else None
+    # every file's chunk is ONE contiguous run of the staging buffer, [G][chunk frames * FRAME * C], which the batch reads and writes
+    # where it lies (capi.Batch.set_pcm_layout: frames FRAME * C apart, files a whole chunk apart) -- no interleaving into frame-major
+    # rows here, and no de-interleaving of a file's channels: a frame's slot holds FRAME * C samples as they lie in the file
+    # (capi.Batch.set_pcm_channels).  `chunk` / `out` below are (frames, G, FRAME * C) VIEWS of those runs
     cf = min(chunk_frames, max(T, 1))
-    batch.set_pcm_layout(FRAME, cf * FRAME)
+    batch.set_pcm_layout(FRAME * C, cf * FRAME * C)
     buf, obuf = batch.pcm_array(cf, np.int16), batch.pcm_array(cf, np.int16)
-    rows8 = lambda a: a.view(np.uint8)  # the same rows as bytes (a companded file's view): (frames, N, 2 * FRAME)
+
+    def slots(a):  # (frames, G, FRAME * C): a file's frame as one run, whatever the channel count
+        v = a.reshape(a.shape[0], G, FRAME * C)
+        assert np.shares_memory(v, a)
+        return v
+    rows8 = lambda a: a.view(np.uint8)  # the same rows as bytes (a companded file's view): (frames, G, 2 * FRAME * C)
     for t0 in range(0, T, chunk_frames):
         tn = min(chunk_frames, T - t0)
-        chunk = buf[:tn]
+        chunk = slots(buf)[:tn]
         chunk[:] = 0  # a stream whose file has ended is fed silence and produces no more output
-        for s in range(N):  # (silence of a companded stream is its law's zero code, not a zero byte: 0x00 is a full-scale sample)
+        for s in range(G):  # (silence of a companded stream is its law's zero code, not a zero byte: 0x00 is a full-scale sample)
             if width[s] == 1:
-                rows8(chunk)[:, s, :frame_of[s]] = SILENCE[g711.code(formats[s])]
+                rows8(chunk)[:, s, :frame_of[s] * C] = SILENCE[g711.code(files[s]["codec"])]
         for s, f in enumerate(ins):
             k = max(0, min(tn, n_frames[s] - t0))
             if k:
                 if width[s] == 1:
-                    rows8(chunk)[:k, s, :frame_of[s]] = np.frombuffer(f.read(k * frame_of[s]), dtype=np.uint8).reshape(k, frame_of[s])
+                    rows8(chunk)[:k, s, :frame_of[s] * C] = np.frombuffer(f.read(k * frame_of[s] * C), dtype=np.uint8).reshape(k, frame_of[s] * C)
                     continue
-                x = np.frombuffer(f.read(k * frame_of[s] * 2), dtype=np.int16)
-                chunk[:k, s, :frame_of[s]] = x.reshape(k, frame_of[s])
-        out, vad, _ = batch.process_s16(chunk, want_gains=False, out=obuf[:tn])
-        for s in range(N):
+                x = np.frombuffer(f.read(k * frame_of[s] * C * 2), dtype=np.int16)
+                chunk[:k, s, :frame_of[s] * C] = x.reshape(k, frame_of[s] * C)
+        out, vad, _ = batch.process_s16(buf[:tn], want_gains=False, out=obuf[:tn])
+        out = slots(obuf)[:tn]
+        for s in range(G):
             k = max(0, min(tn, n_frames[s] - t0))
             first = 1 if t0 == 0 else 0  # the demo drops the first output frame (rnnoise_demo.c:59-60)
             if k > first and width[s] == 1:
-                outs[s].write(rows8(out)[first:k, s, :frame_of[s]].tobytes())
+                outs[s].write(rows8(out)[first:k, s, :frame_of[s] * C].tobytes())
             elif k > first:
-                outs[s].write(out[first:k, s, :frame_of[s]].tobytes())  # (the demo's truncating (short) cast was done on the device)
-            if vfs and k:
-                vfs[s].write("".join(f"{v:.6f}\n" for v in vad[:k, s]))
+                outs[s].write(out[first:k, s, :frame_of[s] * C].tobytes())  # (the demo's truncating (short) cast was done on the device)
+            if vfs and k:  # (one column per channel)
+                vfs[s].write("".join(",".join(f"{v:.6f}" for v in row) + "\n" for row in vad[:k, s * C:(s + 1) * C]))
+    for d, o in zip(files, outs):
+        if d["wav"] and d["out_bytes"] & 1:
+            o.write(b"\0")  # (the pad byte of an odd data chunk)
     for f in ins + outs + (vfs or []):
         f.close()
     batch.close()
-    model.close()
-    return n_frames
 
 
 def main(argv=None):

@@ -339,6 +339,28 @@ extern "C" int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_stride, i
              : 0;
 }
 
+// ---- interleaved channels (include/rnnoise_amd.h) ----
+// One number of the batch.  A process call hands it to K0 / K3 (rn_dev.h: RnGroupDev::pcm_chan) and to the step's plan (dispatch.h:
+// RnStepShape::channels); at 1 nothing is handed on and every launch is the one of a batch that never saw these calls.
+extern "C" int rnnoise_batch_set_pcm_channels(RNNoiseBatch *b, int channels) {
+  if (!b || !rn_pcm_channels_ok(channels, b->n)) return -1;
+  const int old = b->channels;
+  if (channels == old) return old;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_pcm_layout: a call in flight keeps what it was launched with)
+  b->channels = channels;
+  return old;
+}
+
+extern "C" int rnnoise_batch_pcm_channels(const RNNoiseBatch *b) { return b ? b->channels : -1; }
+
+extern "C" int rnnoise_amd_pcm_channels_fit(long frame_stride, long row_stride, int frame_samples, int channels, int n_rows, int n_frames) {
+  return rn_pcm_layout_ok(frame_stride, row_stride) && (frame_stride || row_stride) &&
+                 rn_pcm_channels_fit(frame_stride, row_stride, frame_samples, channels, n_rows, n_frames)
+             ? 1
+             : 0;
+}
+
 // ---- per-stream PCM formats (include/rnnoise_amd.h) ----
 // The table lives in fmt_map from the first set on; while one is set (g.pcm_fmt) K0 expands and K3 compresses the rows of the
 // companded streams in every int16 call (rn_dev.h: rn_stream_fmt), and those calls plan K0 one wave per stream (dispatch.h).  It is
@@ -534,9 +556,13 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   if (!d_out_v || !d_in_v) return -1;
   // the caller's PCM layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), unless the buffers are the library's own (packed:
   // the staged host path; hk: the pinned ring).  Its frame slots must be disjoint, checked before anything is launched or changed
+  // Interleaved channels (rnnoise_batch_set_pcm_channels): the rows are taken `chan` at a time, in the library's staging buffer
+  // (packed) as in the caller's; the strides then place group slots of chan rows.  The pinned ring (hk) never sees channels
+  const int chan = hk ? 1 : b->channels;
+  if (listed && n_rows % chan) return -1;
   const bool laid = b->row_stride && !packed && !hk;
-  if (laid && !rn_pcm_layout_fits(b->frame_stride, b->row_stride, RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1), listed ? n_rows : b->n,
-                                  n_frames))
+  if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1), chan,
+                                   listed ? n_rows : b->n, n_frames))
     return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
@@ -566,6 +592,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   // bytes between the frames of the PCM buffers, and the row pitch K0 / K3 get (0: the form's own constant -- today's arguments)
   const size_t fstep = (laid ? (size_t)b->frame_stride : N * fl) * esz;
   const int pcm_pitch = laid ? (int)b->row_stride : 0;
+  const int pcm_chan = chan > 1 ? chan : 0;  // (rn_dev.h: RnGroupDev::pcm_chan -- 0: today's addressing)
   // Multi-frame calls are software-pipelined over three streams: C runs the high-pass of frames up to
   // f+2, B the analysis of frame f+1, A (the caller's stream) network + synthesis of frame f.
   // What makes that legal:
@@ -583,6 +610,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
                     rn_shape_low_rate(b->pcm_rate, b->g.rs_Ls != nullptr)};
   shape.listed = listed;
   shape.companded = s16 && b->g.pcm_fmt != nullptr;  // (float calls never look at the format table)
+  shape.channels = chan;
   const RnPlan plan = rn_plan(rn_knobs(), shape);
   // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
   // made it: normal for torch's)
@@ -608,6 +636,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   auto frame_group = [&](int f) {
     RnGroupDev g = b->g;
     g.pcm_pitch = pcm_pitch;
+    g.pcm_chan = pcm_chan;
     const int c = (int)((b->frame_no + f) & 1);
     g.features = b->features2[c];
     g.silence = b->silence2[c];
@@ -644,6 +673,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
       b->cur_hp[f & 7] = t.on ? t.stop() : (pipelined ? b->own_hp[f & 7] : nullptr);
       RnGroupDev gh = b->g;
       gh.pcm_pitch = pcm_pitch;
+      gh.pcm_chan = pcm_chan;
       phased(gh, f);
       HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * fstep, s16, (b->ring_slot + f) % RN_RING_SLOTS, plan.hp, sc, t.start(),
                           b->cur_hp[f & 7]));
@@ -750,7 +780,7 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
 // The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
 // ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
 // the caller left them.  The masked host calls, every host call at a PCM rate other than 48 kHz or with a rate table, the int16
-// host calls of a batch with a format table, and every host call of a batch with a PCM layout come here.
+// host calls of a batch with a format table, and every host call of a batch with a PCM layout or with interleaved channels come here.
 // A list call (list set: n_rows host int32 entries, checked by the caller) stages the list too, and its buffers have n_rows rows.
 int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
                          int n_frames, bool s16, const int *list, int n_rows) {
@@ -761,16 +791,20 @@ int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad,
   // a caller-defined layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): the frame slots travel by strided copies between
   // the caller's buffers and the default layout in device memory -- one 2-D copy per frame, its rows row_stride apart --, so the
   // device runs the launches of the default layout and nothing but the slots themselves is read or written on the host
+  // Interleaved channels (rnnoise_batch_set_pcm_channels): what travels is the group slot, C rows of M samples interleaved, and the
+  // device works on the staging buffer with the same channel count (batch_process_device_impl: packed) -- no de-interleave here
+  const size_t C = b->channels;
+  if (rows % C) return -1;
   const bool laid = b->row_stride != 0;
-  if (laid && !rn_pcm_layout_fits(b->frame_stride, b->row_stride, (int)M, (int)rows, n_frames)) return -1;
+  if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, (int)M, (int)C, (int)rows, n_frames)) return -1;
   ON_DEVICE(b->device);
   auto pcm_copy = [&](void *dst, const void *src, bool up) -> bool {
     if (!laid) return hipMemcpy(dst, src, (size_t)n_frames * rows * M * esz, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) == hipSuccess;
-    const size_t hp = (size_t)b->row_stride * esz, hf = (size_t)b->frame_stride * esz, dp = M * esz, df = rows * dp;
+    const size_t hp = (size_t)b->row_stride * esz, hf = (size_t)b->frame_stride * esz, dp = M * C * esz, df = rows * M * esz;
     for (int f = 0; f < n_frames; f++) {
-      const hipError_t e = up ? hipMemcpy2D(static_cast<char *>(dst) + f * df, dp, static_cast<const char *>(src) + f * hf, hp, dp, rows,
+      const hipError_t e = up ? hipMemcpy2D(static_cast<char *>(dst) + f * df, dp, static_cast<const char *>(src) + f * hf, hp, dp, rows / C,
                                             hipMemcpyHostToDevice)
-                              : hipMemcpy2D(static_cast<char *>(dst) + f * hf, hp, static_cast<const char *>(src) + f * df, dp, dp, rows,
+                              : hipMemcpy2D(static_cast<char *>(dst) + f * hf, hp, static_cast<const char *>(src) + f * df, dp, dp, rows / C,
                                             hipMemcpyDeviceToHost);
       if (e != hipSuccess) return false;
     }
@@ -899,7 +933,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
                                                    void *hip_stream) {
   if (!b || !d_records || !d_clean || !d_noisy || !d_vad || !d_lowpass || !d_band_lp || !d_noise_free || n_frames < 0)
     return -1;
-  if (b->per_stream || b->g.rs_L || b->row_stride) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz, in the default PCM layout, only)
+  if (b->per_stream || b->g.rs_L || b->row_stride || b->channels > 1) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz, in the default PCM layout, one row per slot, only)
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
   const size_t N = b->n;
@@ -922,7 +956,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
 extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, const float *clean, const float *noisy,
                                             const float *vad, const int *lowpass, const int *band_lp,
                                             const int *noise_free, int n_frames) {
-  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->row_stride)
+  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->row_stride || b->channels > 1)
     return -1;
   ON_DEVICE(b->device);
   const size_t N = b->n, fb = (size_t)n_frames * N * RN_FRAME_SIZE * 4;

@@ -62,6 +62,7 @@ struct RnStepShape {
   bool low_rate;   // PCM below 48 kHz, or a per-stream rate table (rn_shape_low_rate; rn_dev.h: RnGroupDev::rs_L, ::rs_Ls)
   bool listed = false;  // a stream-list call (rn_dev.h: RnGroupDev::list): n counts its listed rows, never the batch
   bool companded = false;  // an int16 call of a batch with a per-stream format table (rn_dev.h: RnGroupDev::pcm_fmt)
+  int channels = 1;        // interleaved channels of the call's PCM rows (rn_dev.h: RnGroupDev::pcm_chan); 1: none
 };
 
 // RnStepShape::low_rate of a batch: its calls run the resampling prologue / epilogue -- at a PCM rate below 48 kHz, and at any rate
@@ -91,7 +92,11 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   // An int16 call of a batch with a format table (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats): the one-wave form at every
   // size too -- one wave serves one stream, so the row's format is wave-uniform and a wave reads either bytes or int16, and the lane =
   // stream kernel, where 64 neighbours of different formats would share a wave, keeps its registers.
-  p.hp = s.listed || s.low_rate || s.companded || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
+  // Interleaved channels (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels): the one-wave form at every size as well.  A wave
+  // of it reads its row with lane-consecutive samples, each cache line of the group slot once; a lane of the lane = stream kernel
+  // would walk its row 4 C samples at a time beside 63 lanes of other slots, and its block loop has no registers to spare for the
+  // addressing.  No other stage looks at the caller's PCM: K1, the network and K3's form do not depend on it.
+  p.hp = s.listed || s.low_rate || s.companded || s.channels > 1 || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
   // K1.  From 2,560 streams four streams share a workgroup (rn_analysis_kernel).  6,144 until round 6's last day; since the narrow
   // phases and the follower are shared by the four streams of a workgroup (round 6) that form is ahead from 3,072 streams -- 23.3
   // against 20.8 M frames/s there, 26.4 against 24.5 at 4,096 (one frame per call 0.201 against 0.231 ms), 27.8 against 26.0 at
@@ -161,4 +166,17 @@ static inline bool rn_pcm_layout_fits(long frame_stride, long row_stride, int M,
   const bool row_major = row_stride >= M && (ll)frame_stride >= (ll)n_rows * row_stride;
   const bool stream_contiguous = frame_stride >= M && (ll)row_stride >= (ll)n_frames * frame_stride;
   return row_major || stream_contiguous;
+}
+
+// ---- interleaved channels (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels) ----
+#define RN_MAX_CHANNELS 8  // = RNNOISE_AMD_MAX_CHANNELS
+// what the setter accepts for a batch of n streams
+static inline bool rn_pcm_channels_ok(int channels, int n_streams) {
+  return channels >= 1 && channels <= RN_MAX_CHANNELS && n_streams % channels == 0;
+}
+// whether a call's group slots -- n_frames x n_rows / channels slots of M * channels samples, slot (f, g) at f * frame_stride +
+// g * row_stride -- are disjoint: rn_pcm_layout_fits with the slot as the row.  Rows that do not fill whole groups never fit.
+static inline bool rn_pcm_channels_fit(long frame_stride, long row_stride, int M, int channels, int n_rows, int n_frames) {
+  if (channels < 1 || channels > RN_MAX_CHANNELS || M <= 0 || n_rows < 0 || n_rows % channels) return false;
+  return rn_pcm_layout_fits(frame_stride, row_stride, M * channels, n_rows / channels, n_frames);
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "rn_dev.h"
 #include "dispatch.h"
 #include "fft_reg.h"
@@ -1712,7 +1713,8 @@ __device__ __forceinline__ void rn_list_outputs(const RnGroupDev &g, const RnStr
   if (g.list_vad && lane == 0) g.list_vad[at.i] = at.present ? g.vad[at.s] : 0.f;
 }
 // out_pitch: samples (of the output's type) between rows of `out` -- RN_FRAME_SIZE, or the caller's layout where `out` is the caller's
-// buffer (rn_dev.h: RnGroupDev::pcm_pitch; the kernels below)
+// buffer (rn_dev.h: RnGroupDev::pcm_pitch; the kernels below).  0: `out` is the caller's buffer with interleaved channels (rn_dev.h:
+// RnGroupDev::pcm_chan) -- the row's place and sample step come from rn_pcm_row
 template <bool LATE>
 __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTablesDev &tb, float *__restrict__ out, int parity_arg,
                                                const RnStreamAt &at, size_t out_pitch) {
@@ -1902,32 +1904,42 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
       smv[b] = lo ? sm[mi] : 0.f;
     }
   }
-  // window + overlap-add (src/denoise.c:400-407), straight from the registers
-  const size_t row0 = (size_t)at.i * out_pitch;  // (the caller's row: rn_dev.h RnStreamAt::i)
-  float *o = listed ? at.io + RN_ROW_OUT : out + row0;
+  // window + overlap-add (src/denoise.c:400-407), straight from the registers.  Every store is one element of this row -- 4, 2 or 1
+  // bytes -- in both forms: with interleaved channels (ch) the elements between this row's belong to the sibling channels, which other
+  // workgroups write, maybe in other launches, or which are absent from the call.  The loop once per form, chosen by one uniform
+  // branch, so that C = 1 keeps its code: o[n], not o[n * 1]
+  auto overlap_add = [&](auto ch) {
+    constexpr bool CH = decltype(ch)::value;
+    const RnPcmRow pr = CH ? rn_pcm_row(g, at.i, RN_FRAME_SIZE) : RnPcmRow{(size_t)at.i * out_pitch, 0, 1};  // (the caller's row: RnStreamAt::i)
+    const size_t row0 = pr.slot + pr.c;
+    float *o = listed ? at.io + RN_ROW_OUT : out + row0;
 #pragma unroll
-  for (int b = 0; b < 15; b++) {
-    bool lo;
-    unsigned n;  // (lo: the output sample's index; otherwise where the sample goes in synthesis_mem)
-    (void)synth_index(b, (unsigned)pos & 63u, lo, n);
-    float v = (float)RN_WINDOW_SIZE * yr[b];
-    v *= wv[b];
-    // a closed gate: the spectrum is zero, so its transform is +0 at every sample -- written as such, not left to the signs of zero
-    // a transform of zeros produces in this transform's order of operations
-    if (gate) v = 0.f;
-    if (lo) {
-      const float r = v + smv[b];
-      if (out_s16) {
-        const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-        if (out_fmt) reinterpret_cast<uint8_t *>(out)[row0 * sizeof(short) + n] = (uint8_t)rn_g711_encode(out_fmt, (short)q);
-        else reinterpret_cast<short *>(out)[row0 + n] = (short)q;
+    for (int b = 0; b < 15; b++) {
+      bool lo;
+      unsigned n;  // (lo: the output sample's index; otherwise where the sample goes in synthesis_mem)
+      (void)synth_index(b, (unsigned)pos & 63u, lo, n);
+      float v = (float)RN_WINDOW_SIZE * yr[b];
+      v *= wv[b];
+      // a closed gate: the spectrum is zero, so its transform is +0 at every sample -- written as such, not left to the signs of zero
+      // a transform of zeros produces in this transform's order of operations
+      if (gate) v = 0.f;
+      if (lo) {
+        const float r = v + smv[b];
+        const size_t at_n = CH ? (size_t)(n * (unsigned)pr.step) : (size_t)n;
+        if (out_s16) {
+          const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
+          if (out_fmt) reinterpret_cast<uint8_t *>(out)[pr.slot * sizeof(short) + pr.c + at_n] = (uint8_t)rn_g711_encode(out_fmt, (short)q);
+          else reinterpret_cast<short *>(out)[row0 + at_n] = (short)q;
+        } else {
+          o[at_n] = r;
+        }
       } else {
-        o[n] = r;
+        sm[n] = v;
       }
-    } else {
-      sm[n] = v;
     }
-  }
+  };
+  if (out_pitch) overlap_add(std::false_type{});
+  else overlap_add(std::true_type{});
   if (g.list) rn_list_outputs(g, at);
   if (listed) {
     // completion word of the row's request (the last word of its pinned block): the caller waiting for this frame polls it
@@ -1952,7 +1964,9 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
   const int lane = threadIdx.x, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
   const float *body = g.rs_dn + (size_t)row * RN_FRAME_SIZE;  // (the body wrote its output row: the caller's row, RnStreamAt::i)
-  const size_t row0 = (size_t)row * rn_pcm_pitch(g, g.rs_pitch);
+  // (with interleaved channels the outputs go pr.step apart from pr.slot + pr.c on, one element per store: rn_dev.h rn_pcm_row)
+  const RnPcmRow pr = rn_pcm_row(g, row, g.rs_pitch);
+  const size_t row0 = pr.slot + pr.c;
   const float *ht = rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
   float *h = vs + RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE;
   __syncthreads();  // (the body's stores to rs_dn, by other lanes)
@@ -1986,10 +2000,10 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
     const float r = (a0 + a1) + (a2 + a3);
     if (out_s16) {  // (the truncating conversion of the 48 kHz calls: synthesis_body)
       const int q = (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-      if (fmt) static_cast<uint8_t *>(out)[row0 * sizeof(short) + m] = (uint8_t)rn_g711_encode(fmt, (short)q);
-      else static_cast<short *>(out)[row0 + m] = (short)q;
+      if (fmt) static_cast<uint8_t *>(out)[pr.slot * sizeof(short) + pr.c + (size_t)(m * pr.step)] = (uint8_t)rn_g711_encode(fmt, (short)q);
+      else static_cast<short *>(out)[row0 + (size_t)(m * pr.step)] = (short)q;
     } else {
-      static_cast<float *>(out)[row0 + m] = r;
+      static_cast<float *>(out)[row0 + (size_t)(m * pr.step)] = r;
     }
   }
   // the new history: the frame's last 47 L samples
@@ -2023,7 +2037,7 @@ rn_synthesis_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, int p
   const int rs_L = rs_divert(g, at, body_out, parity_arg);
   parity_arg = rn_fmt_arg(g, at, parity_arg);
   // (the body writes the caller's buffer -- in the caller's layout -- except in front of the epilogue, where it writes rs_dn)
-  synthesis_body<true>(g, tb, body_out, parity_arg, at, rs_L > 1 ? (size_t)RN_FRAME_SIZE : rn_pcm_pitch(g, RN_FRAME_SIZE));
+  synthesis_body<true>(g, tb, body_out, parity_arg, at, rs_L > 1 ? (size_t)RN_FRAME_SIZE : g.pcm_chan ? 0 : rn_pcm_pitch(g, RN_FRAME_SIZE));
   if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L, (parity_arg >> 11) & 3);
@@ -2036,7 +2050,7 @@ rn_synthesis_few_kernel(RnGroupDev g, RnTablesDev tb, float *__restrict__ out, i
   float *body_out = out;
   const int rs_L = rs_divert(g, at, body_out, parity_arg);  // (bit 9 is never set for a row list)
   parity_arg = rn_fmt_arg(g, at, parity_arg);
-  synthesis_body<false>(g, tb, body_out, parity_arg, at, rs_L > 1 ? (size_t)RN_FRAME_SIZE : rn_pcm_pitch(g, RN_FRAME_SIZE));
+  synthesis_body<false>(g, tb, body_out, parity_arg, at, rs_L > 1 ? (size_t)RN_FRAME_SIZE : g.pcm_chan ? 0 : rn_pcm_pitch(g, RN_FRAME_SIZE));
   if (rs_L > 1) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     rs_down_stream(g, reinterpret_cast<SynthLds *>(smem_raw)->S, parity_arg & 1024, at.s, at.i, rs_L, (parity_arg >> 11) & 3);

@@ -509,17 +509,17 @@ static int batch_process_host_impl(RNNoiseBatch *b, void *out_v, const void *in_
   return 0;
 }
 
-// (at a PCM rate other than 48 kHz, and with a caller-defined PCM layout, the host forms take the staged convenience path of the
-//  masked calls: batch.cpp)
+// (at a PCM rate other than 48 kHz, with a caller-defined PCM layout and with interleaved channels the host forms take the staged
+//  convenience path of the masked calls: batch.cpp)
 extern "C" int rnnoise_batch_process(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains,
                                      int n_frames) {
-  if (b && (b->g.rs_L || b->row_stride)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, false);  // (or a PCM layout)
+  if (b && (b->g.rs_L || b->row_stride || b->channels > 1)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, false);  // (or a PCM layout, or channels)
   return batch_process_host_impl(b, out, in, vad, gains, n_frames, false);
 }
 
 extern "C" int rnnoise_batch_process_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                          int n_frames) {
-  if (b && (b->g.rs_L || b->g.pcm_fmt || b->row_stride)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, true);  // (or a format table, or a PCM layout)
+  if (b && (b->g.rs_L || b->g.pcm_fmt || b->row_stride || b->channels > 1)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, true);  // (or a format table, a PCM layout, channels)
   return batch_process_host_impl(b, out, in, vad, gains, n_frames, true);
 }
 

@@ -39,9 +39,12 @@ __device__ __forceinline__ void rs_wsync() {
 template <int IN>
 __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in, int s, int row, float *xs, int L, int fmt = 0) {
   // (M: the stream's samples per frame; its row starts at row * rs_pitch -- M of the batch's rate, which a stream of a rate table may
-  //  fill only in part: rn_dev.h RnGroupDev::rs_Ls -- or at row * pcm_pitch in a caller-defined layout)
+  //  fill only in part: rn_dev.h RnGroupDev::rs_Ls -- or at row * pcm_pitch in a caller-defined layout; with interleaved channels its
+  //  samples are pr.step apart from pr.slot + pr.c on: rn_dev.h rn_pcm_row.  Lane l reads samples l, l + 64, ...: one load of the
+  //  wave covers 64 * step consecutive elements, every cache line of the group slot once)
   const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
-  const size_t row0 = (size_t)row * rn_pcm_pitch(g, g.rs_pitch);
+  const RnPcmRow pr = rn_pcm_row(g, row, g.rs_pitch);
+  const size_t row0 = pr.slot + pr.c;
   float *hu = xs + RN_RS_XS;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
   // (loads and LDS stores at clamped indices, without a branch: a lane past the end rewrites the last element with its own value)
@@ -51,8 +54,8 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
 #pragma unroll
   for (int i = 0; i < NX; i++) {
     const int m = min(lane + WAVE * i, M - 1);
-    const size_t q = row0 + m;  // (row: the caller's row of stream s, RnStreamAt::i)
-    if (IN == 2) rx[i] = (float)rn_g711_decode(fmt, static_cast<const uint8_t *>(in)[row0 * sizeof(short) + m]);
+    const size_t q = row0 + (size_t)(m * pr.step);  // (row: the caller's row of stream s, RnStreamAt::i)
+    if (IN == 2) rx[i] = (float)rn_g711_decode(fmt, static_cast<const uint8_t *>(in)[pr.slot * sizeof(short) + pr.c + (size_t)(m * pr.step)]);
     else rx[i] = IN == 1 ? (float)static_cast<const short *>(in)[q] : static_cast<const float *>(in)[q];
   }
   const float *ht = rs_up_taps(L);
@@ -311,9 +314,14 @@ static_assert(RN_RS_LDS <= RN_PITCH_BUF_SIZE, "the upsampling prologue's LDS fit
 //  one-frame API, in front of a kernel of ~20 us)
 // IN: 0 a float row, 1 an int16 row, 2 a companded row -- 480 G.711 bytes of law `fmt` at the front of the int16 row (rn_dev.h:
 // RnGroupDev::pcm_fmt), four codes per lane and load where the int16 row gives four samples, expanded in registers (g711.h)
-template <int IN>
+// CH: interleaved channels (rn_dev.h: RnGroupDev::pcm_chan) -- in_row points at the row's first sample (a companded row's first byte)
+// and its samples are `step` elements apart.  Lane l then takes samples l, l + 64, ... one element per load, so that one load of the
+// wave covers 64 * step consecutive elements: every cache line of the group slot is requested once by this wave (its other elements are
+// the sibling channels', whose waves find the line in L2), where four-sample runs per lane would request each line four times.  A
+// body of its own, not a run-time stride in the body above: C = 1 keeps its float4 / short4 loads and its code
+template <int IN, bool CH = false>
 __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, const void *__restrict__ in_row,
-                                            bool listed, int s, int slot, int fmt = 0) {
+                                            bool listed, int s, int slot, int fmt = 0, int step = 1) {
   constexpr bool in_s16 = IN == 1;
   const int lane = threadIdx.x;
   const float a0 = -1.99599f, a1 = 0.99600f, b0 = -2.f;
@@ -332,9 +340,18 @@ __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, co
     const short4 *x16 = reinterpret_cast<const short4 *>(in_row);
     const uint32_t *x8 = reinterpret_cast<const uint32_t *>(in_row);
     constexpr int OLD4 = (RN_PITCH_BUF_SIZE - RN_FRAME_SIZE) / 2 / 4;
+    constexpr int NE = (RN_FRAME_SIZE + 63) / 64;
     float4 f[2], o[3];
+    float e[NE];
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; CH && i < NE; i++) {
+      const size_t q = (size_t)(min(lane + 64 * i, RN_FRAME_SIZE - 1) * step);  // (lanes past the end re-read the last sample)
+      if (IN == 2) e[i] = (float)rn_g711_decode(fmt, static_cast<const uint8_t *>(in_row)[q]);
+      else if (in_s16) e[i] = (float)static_cast<const short *>(in_row)[q];
+      else e[i] = static_cast<const float *>(in_row)[q];
+    }
+#pragma unroll
+    for (int i = 0; !CH && i < 2; i++) {
       const int q = min(lane + 64 * i, RN_FRAME_SIZE / 4 - 1);  // (lanes past the end re-read the last 16 bytes and drop them)
       if (IN == 2) {
         const uint32_t v = x8[q];
@@ -357,7 +374,9 @@ __device__ __forceinline__ void hp_one_body(HpOneLds &L, const RnGroupDev &g, co
     // (stores at the clamped index too, without a branch: a lane past the end holds the last float4 and rewrites it with its own value.
     //  Behind a branch per store the compiler sank every load to its store and waited for it there: five round trips one after the other)
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+    for (int i = 0; CH && i < NE; i++) L.pb[RN_PITCH_BUF_SIZE - RN_FRAME_SIZE + min(lane + 64 * i, RN_FRAME_SIZE - 1)] = e[i];
+#pragma unroll
+    for (int i = 0; !CH && i < 2; i++)
       reinterpret_cast<float4 *>(L.pb + (RN_PITCH_BUF_SIZE - RN_FRAME_SIZE))[min(lane + 64 * i, RN_FRAME_SIZE / 4 - 1)] = f[i];
 #pragma unroll
     for (int i = 0; i < 3; i++) reinterpret_cast<float4 *>(L.pb)[min(lane + 64 * i, OLD4 - 1)] = o[i];
@@ -480,6 +499,15 @@ rn_hp_one_kernel(RnGroupDev g, const float *__restrict__ in, int slot_arg, int i
   }
   // the caller's row i (rn_dev.h: RnStreamAt::i -- stream s's own row except in a list call), RnGroupDev::pcm_pitch samples of the
   // call's type from row i - 1 (a companded row keeps its int16 pitch: its byte base is row * pitch * sizeof(short))
+  if (g.pcm_chan && !at.listed && !rs_row) {
+    // interleaved channels (rn_dev.h: RnGroupDev::pcm_chan): row i is channel pr.c of its group's slot, its samples pr.step apart
+    const RnPcmRow pr = rn_pcm_row(g, at.i, RN_FRAME_SIZE);
+    if (in_s16 && fmt)
+      hp_one_body<2, true>(L, g, reinterpret_cast<const uint8_t *>(in) + pr.slot * sizeof(short) + pr.c, false, s, at.ring, fmt, pr.step);
+    else if (in_s16) hp_one_body<1, true>(L, g, reinterpret_cast<const short *>(in) + pr.slot + pr.c, false, s, at.ring, 0, pr.step);
+    else hp_one_body<0, true>(L, g, in + pr.slot + pr.c, false, s, at.ring, 0, pr.step);
+    return;
+  }
   const size_t row0 = (size_t)at.i * rn_pcm_pitch(g, RN_FRAME_SIZE);
   const void *in_row = at.listed ? static_cast<const void *>(at.io + RN_ROW_IN)
                        : rs_row ? static_cast<const void *>(rs_row)

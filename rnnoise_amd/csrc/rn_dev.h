@@ -195,6 +195,13 @@ struct RnGroupDev {
   // of 4 (rn_pcm_pitch).  Only K0 and K3 look at it, and only where they address the caller's buffers: the scratch rows rs_up / rs_dn
   // stay RN_FRAME_SIZE apart.  The frame pitch is the host's: the launchers get each frame's base pointer (batch.cpp).
   int pcm_pitch;
+  // Interleaved channels (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels).  0: one row per slot (every launch is today's).
+  // C = 2 .. 8: the caller's rows are taken C at a time -- row r = C g + c is channel c of group g, its sample i at
+  //     g * pitch + c + i * C      (pitch: pcm_pitch, or C times the form's own constant without a layout)
+  // of `in` and `out`, a companded row's BYTE i at byte g * pitch * sizeof(short) + c + i * C (rn_pcm_row).  K0 and K3 only, and only
+  // in their one-wave-per-stream forms (dispatch.h: the lane = stream K0 is never planned for such a call); r is the list position in
+  // a list call.  K3 stores single elements: the siblings' samples in between belong to other workgroups, maybe of other launches.
+  int pcm_chan;
   // Per-stream PCM formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats).  Null pcm_fmt: every row of an int16 call holds
   // int16 samples (every launch is today's).  Set, stream s's rows of the int16 calls hold pcm_fmt[s]: RN_PCM_ULAW / RN_PCM_ALAW
   // (g711.h) one byte per sample in the FIRST 480 / L_s bytes of the row -- K0 expands them where it reads the row (hp_one_body,
@@ -393,6 +400,18 @@ __device__ __forceinline__ int rn_stream_L(const RnGroupDev &g, int s) {
 }
 // Samples between the caller's PCM rows (rn_dev.h: RnGroupDev::pcm_pitch): the layout's, or `own` -- the form's constant -- without one
 __device__ __forceinline__ size_t rn_pcm_pitch(const RnGroupDev &g, int own) { return (size_t)(g.pcm_pitch ? g.pcm_pitch : own); }
+// The caller's PCM row `row` (rn_dev.h: RnGroupDev::pcm_pitch, ::pcm_chan): its sample i lies at  slot + c + i * step  samples of the
+// call's type, a companded row's byte i at byte  slot * sizeof(short) + c + i * step.  Without channels: c = 0, step = 1, slot =
+// row * pitch -- what the kernels computed before there were channels.  row is wave-uniform (RnStreamAt::i), and so is the result
+struct RnPcmRow {
+  size_t slot;
+  int c, step;
+};
+__device__ __forceinline__ RnPcmRow rn_pcm_row(const RnGroupDev &g, int row, int own) {
+  if (!g.pcm_chan) return {(size_t)row * rn_pcm_pitch(g, own), 0, 1};
+  const unsigned grp = (unsigned)row / (unsigned)g.pcm_chan;
+  return {(size_t)grp * rn_pcm_pitch(g, own * g.pcm_chan), (int)((unsigned)row - grp * (unsigned)g.pcm_chan), g.pcm_chan};
+}
 // PCM format of stream s's rows in an int16 call (rn_dev.h: RnGroupDev::pcm_fmt): RN_PCM_ULAW, RN_PCM_ALAW, or 0 for int16 rows -- no
 // table, or a byte that names neither law.  s is the workgroup's one stream: the result is wave-uniform
 __device__ __forceinline__ int rn_stream_fmt(const RnGroupDev &g, int s) {

@@ -193,6 +193,10 @@ struct RNNoiseBatch {
   // process calls hand row_stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and step their frame pointers by frame_stride; b->g
   // itself never carries a pitch.  Configuration, not state
   long frame_stride = 0, row_stride = 0;
+  // interleaved channels (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels): the PCM rows of every process call are taken
+  // `channels` at a time; 1: none.  The process calls hand it to K0 / K3 (rn_dev.h: RnGroupDev::pcm_chan, 0 for 1); b->g itself
+  // never carries it.  Configuration, not state
+  int channels = 1;
   // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
   // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of) -- allocated by the first
   // add_model, like rs_buf by the first rate change; g.model_of / g.n_models are set from then on

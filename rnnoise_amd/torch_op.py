@@ -91,6 +91,22 @@ def register_torch_op():
         N, T = pcm.shape[0], pcm.shape[1] // _OPS[handle].batch.frame
         return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
 
+    # the interleaved form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels): pcm (G, T * (480 // L), C) float32 or int16 with
+    # G * C the batch's streams -- channel c of group g is stream g * C + c --, read and written where it lies, no de-interleave.
+    # active (T, G * C) or None.  Returns out (same shape and dtype as pcm), vad (T, G * C), gains (T, G * C, 32).
+    @torch.library.custom_op("rnnoise_amd::process_channels", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor? active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)")
+    def process_channels(pcm, active, state, handle):
+        op = _OPS[handle]
+        res = op._run_channels(pcm, active)
+        state.add_(pcm.shape[1] // op.batch.frame)
+        return res
+
+    @process_channels.register_fake
+    def _(pcm, active, state, handle):
+        N, T = pcm.shape[0] * pcm.shape[2], pcm.shape[1] // _OPS[handle].batch.frame
+        return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
+
     _registered = True
 
 
@@ -156,6 +172,15 @@ class RNNoiseOp:
         (T, N, 32) (torch.ops.rnnoise_amd.process_streams).  The layout is set when it changes -- a synchronous call, so keep T and
         the entry point the same from call to call."""
         return self.torch.ops.rnnoise_amd.process_streams(pcm, active, self.state, self.handle)
+
+    def process_channels(self, pcm, active=None):
+        """pcm (G, T * (480 // L), C) float32 or int16 CUDA tensor with G * C == n_streams: interleaved channels, channel c of group g
+        being stream g * C + c.  The batch reads it and writes the result of the same shape where they lie
+        (rnnoise_batch_set_pcm_channels + rnnoise_batch_set_pcm_layout: no de-interleave and no transpose); active (T, G * C) bool /
+        uint8 or None as in process_masked.  -> out (G, T * (480 // L), C), vad (T, G * C), gains (T, G * C, 32)
+        (torch.ops.rnnoise_amd.process_channels).  Channel count and layout are set when they change -- synchronous calls, so keep
+        T, C and the entry point the same from call to call."""
+        return self.torch.ops.rnnoise_amd.process_channels(pcm, active, self.state, self.handle)
 
     def reset_streams(self, idx):
         """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
@@ -230,10 +255,36 @@ class RNNoiseOp:
         """no controls: every stream back to the reference's suppression (the table and the gate counters are dropped)"""
         self.batch.set_stream_controls(None)
 
-    def _layout(self, frame_stride, row_stride):
-        # (the setter drains the device: called only when the layout changes)
+    def _layout(self, frame_stride, row_stride, channels=1):
+        # (the setters drain the device: called only when the layout or the channel count changes)
+        if self.batch.pcm_channels != channels:
+            self.batch.set_pcm_channels(channels)
         if self.batch.pcm_layout != (frame_stride, row_stride):
             self.batch.set_pcm_layout(frame_stride, row_stride)
+
+    def _run_channels(self, pcm, active=None):
+        torch = self.torch
+        M = self.batch.frame
+        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 3
+        G, C = pcm.shape[0], pcm.shape[2]
+        assert G * C == self.n and 1 <= C <= capi.MAX_CHANNELS and pcm.shape[1] % M == 0 and pcm.shape[1] > 0
+        pcm = pcm.contiguous()  # (a [B, T, C] tensor as torch makes it is: no copy)
+        T = pcm.shape[1] // M
+        s16 = pcm.dtype == torch.int16
+        self._layout(M * C, T * M * C, C)
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
+        gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        if active is None:
+            out = torch.empty_like(pcm)
+            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream, s16=s16)
+        else:
+            assert active.is_cuda and active.shape == (T, self.n)
+            act = (active != 0).to(torch.uint8).contiguous()
+            out = torch.zeros_like(pcm)
+            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream,
+                                             s16=s16)
+        return out, vad, gains
 
     def _run_streams(self, pcm, active=None):
         torch = self.torch
