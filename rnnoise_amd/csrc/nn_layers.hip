@@ -1,6 +1,6 @@
 // nn_layers.hip -- K2 for large batches (from 10,240 streams up, dispatch.h: RN_NN_LAYERS): the network layer by layer.
 //
-//   rn_nn_front_kernel (nn_mfma.hip)  conv1, conv2 per 16-stream tile; leaves the u8 image of the conv2 output in act_q[0]
+//   rn_nn_front_kernel (nn_mfma.hip)  conv1, conv2 for 64 streams per workgroup; leaves the u8 images of the conv2 output in act_q[0]
 //   rn_nn_gru_kernel    x 3           one GRU layer (src/nnet.c:65-94) for 64 streams per workgroup
 //   rn_nn_dense_kernel                dense_out + vad_dense (src/rnn.c:53-58) for 64 streams per workgroup
 //   rn_nn_requant_kernel              rebuilds the state images after anything else wrote the GRU state

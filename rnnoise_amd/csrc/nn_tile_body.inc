@@ -1,9 +1,8 @@
-// nn_tile_body.inc -- body of the 16-stream tile kernels of nn_mfma.hip, included once per RN_NN_MODE (a template or a
-// shared __device__ function costs the fused kernel 30-80 VGPRs with this compiler: measured 118 -> 150 / 201).
-//   RN_NN_MODE 0: the whole network;  1: front of the layer-wise schedule (conv1, conv2, image to act_q[0], f32 copy to nn_act)
+// nn_tile_body.inc -- body of the 16-stream tile kernels of nn_mfma.hip (the whole network for one tile), included once per kernel
+// (a template or a shared __device__ function costs the fused kernel 30-80 VGPRs with this compiler: measured 118 -> 150 / 201).
 //   RN_NN_LIST 0: tile row r is stream r;  1: tile row r is stream g.list[r] when a list is set (rn_dev.h: RnGroupDev::list), stream r
 //   otherwise.  (Compiled once per value behind a uniform branch on g.list, the two bodies in one kernel spilled 29-49 registers.)
-// The including kernel declares the LDS arena L (MfmaLds, or FrontLds for RN_NN_MODE 1).
+// The including kernel declares the LDS arena L (MfmaLds).
 // NWAVES (8 | 16) is whatever the including file has it at: every loop over row / unit tiles strides by it, the one-per-wave roles
 // (conv1's eight row tiles, the 512 producer threads of the dense phase, the three chain waves) stay on the first eight waves.
   // The tile is one long dependency chain and the analysis kernel of the next frame queues behind the LDS it
@@ -59,7 +58,6 @@
 #pragma unroll
     for (int j = 0; j < 2048 / NTHREADS; j++) reinterpret_cast<uint32_t *>(L.lut)[tid + j * NTHREADS] = lw[j];
   }
-#if RN_NN_MODE == 0
   {
     static_assert(RN_CAT % 512 == 0, "whole trips of the first eight waves");
     float vw_[RN_CAT / 512];
@@ -70,7 +68,6 @@
       for (int j = 0; j < RN_CAT / 512; j++) L.vadw[tid + j * 512] = vw_[j];
     }
   }
-#endif
   // ---- conv1 input: [conv1_state(130) | features(65) | 0] per stream ----
   // (constant trip count, fully unrolled, loads before stores: all of a thread's loads are in flight together -- as a
   //  run-time loop each iteration waited out its own HBM trip: 21k of the front kernel's 66k cycles per tile)
@@ -167,14 +164,6 @@
     }
   }
 
-#if RN_NN_MODE == 1  // hand the image to the layer kernels
-  __syncthreads();
-  {
-    v4i *dst = reinterpret_cast<v4i *>(g.act_q[0] + (size_t)blockIdx.x * (KT * 64 * 16));
-    for (int i = tid; i < KT * 64; i += NTHREADS) dst[i] = reinterpret_cast<const v4i *>(L.xq[1])[i];
-  }
-#endif
-#if RN_NN_MODE == 0
   // ---- three GRUs (src/nnet.c:65-94); wave w owns hidden-unit tiles w, w+4, ... ----
   int cur = 1;
   CLK_TAP(2);  // conv2
@@ -214,8 +203,6 @@
     __syncthreads();
     CLK_TAP(3 + k);  // GRU k
   }
-#endif  // RN_NN_MODE == 0
-#if RN_NN_MODE == 0
 
   // ---- dense_out (1536 -> 32, f32 MFMA chains, waves 0-1) and vad_dense (wave 2, lane = stream) ----
   // cat = [conv2 out | gru1 | gru2 | gru3] (src/rnn.c:53-55); silent streams are computed on
@@ -309,7 +296,6 @@
     }
   }
   CLK_TAP(6);  // dense_out / vad (wave 0's view)
-#endif  // RN_NN_MODE == 0 (dense phase)
 #undef CLK_TAP
 #undef OWN
 #undef ROW_OK
