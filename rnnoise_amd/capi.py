@@ -169,29 +169,25 @@ def _load(path, debug):
         L.rnnoise_batch_destroy.argtypes = [vp]
         L.rnnoise_batch_size.argtypes = [vp]
         L.rnnoise_batch_reset.argtypes = [vp]
-        L.rnnoise_batch_process.argtypes = [vp, fp, fp, fp, fp, C.c_int]
-        L.rnnoise_batch_process_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_process_s16.argtypes = [vp, C.POINTER(C.c_short), C.POINTER(C.c_short), fp, fp, C.c_int]
-        L.rnnoise_batch_process_device_s16.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
         sp, up = C.POINTER(C.c_short), C.POINTER(C.c_ubyte)
-        L.rnnoise_batch_process_device_masked.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_process_device_masked_s16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_process_masked.argtypes = [vp, fp, fp, fp, fp, up, C.c_int]
-        L.rnnoise_batch_process_masked_s16.argtypes = [vp, sp, sp, fp, fp, up, C.c_int]
-        L.rnnoise_batch_process_device_list.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
-        L.rnnoise_batch_process_device_list_s16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
-        L.rnnoise_batch_process_list.argtypes = [vp, fp, fp, fp, fp, ip, C.c_int, up, C.c_int]
-        L.rnnoise_batch_process_list_s16.argtypes = [vp, sp, sp, fp, fp, ip, C.c_int, up, C.c_int]
+        # the process calls, each as float and as int16 ("_s16"): host PCM pointers typed, device pointers plain addresses
+        for sfx, pp in (("", fp), ("_s16", sp)):
+            for name, args in (("process", [vp, pp, pp, fp, fp, C.c_int]),
+                               ("process_device", [vp] * 5 + [C.c_int, vp]),
+                               ("process_masked", [vp, pp, pp, fp, fp, up, C.c_int]),
+                               ("process_device_masked", [vp] * 6 + [C.c_int, vp]),
+                               ("process_list", [vp, pp, pp, fp, fp, ip, C.c_int, up, C.c_int]),
+                               ("process_device_list", [vp] * 6 + [C.c_int, vp, C.c_int, vp])):
+                getattr(L, f"rnnoise_batch_{name}{sfx}").argtypes = args
+        # the per-stream tables: host setter, device setter (table, stream), getter
+        for name, tp in (("rates", up), ("formats", up), ("models", up), ("controls", fp)):
+            getattr(L, f"rnnoise_batch_set_stream_{name}").argtypes = [vp, tp]
+            getattr(L, f"rnnoise_batch_set_stream_{name}_device").argtypes = [vp, vp, vp]
+            getattr(L, f"rnnoise_batch_stream_{name}").argtypes = [vp, tp]
         L.rnnoise_batch_reset_streams.argtypes = [vp, ip, C.c_int]
         L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
         L.rnnoise_batch_set_pcm_rate.argtypes = [vp, C.c_int]
         L.rnnoise_batch_pcm_rate.argtypes = [vp]
-        L.rnnoise_batch_set_stream_rates.argtypes = [vp, up]
-        L.rnnoise_batch_set_stream_rates_device.argtypes = [vp, vp, vp]
-        L.rnnoise_batch_stream_rates.argtypes = [vp, up]
-        L.rnnoise_batch_set_stream_formats.argtypes = [vp, up]
-        L.rnnoise_batch_set_stream_formats_device.argtypes = [vp, vp, vp]
-        L.rnnoise_batch_stream_formats.argtypes = [vp, up]
         L.rnnoise_batch_set_pcm_layout.argtypes = [vp, C.c_long, C.c_long]
         L.rnnoise_batch_pcm_layout.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
         L.rnnoise_amd_pcm_layout_fits.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int]
@@ -199,12 +195,6 @@ def _load(path, debug):
         L.rnnoise_batch_pcm_channels.argtypes = [vp]
         L.rnnoise_amd_pcm_channels_fit.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int]
         L.rnnoise_batch_add_model.argtypes = [vp, vp]
-        L.rnnoise_batch_set_stream_models.argtypes = [vp, up]
-        L.rnnoise_batch_set_stream_models_device.argtypes = [vp, vp, vp]
-        L.rnnoise_batch_stream_models.argtypes = [vp, up]
-        L.rnnoise_batch_set_stream_controls.argtypes = [vp, fp]
-        L.rnnoise_batch_set_stream_controls_device.argtypes = [vp, vp, vp]
-        L.rnnoise_batch_stream_controls.argtypes = [vp, fp]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
         L.rnnoise_batch_save_streams_device.argtypes = [vp, vp, vp, C.c_int, vp]
@@ -454,14 +444,17 @@ class Batch:
             return self.pcm_array(pcm.shape[0], dtype, pcm.shape[1])
         return np.zeros_like(pcm) if zero else np.empty_like(pcm)
 
+    def _call(self, fn, *args, exc=RuntimeError, why=""):
+        """one call of the library on this batch that answers 0, or `exc`"""
+        if getattr(self._L, fn)(self.h, *args):
+            raise exc(f"{fn} failed{why}")
+
     def set_stream_rates(self, hz):
         """the PCM rate of every stream in Hz (rnnoise_batch_set_stream_rates): (N,) values out of PCM_RATES, none above the batch's
         own rate, or None to drop the table.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose
         rate changes restart their resampling filters from zero; every stream keeps its DenoiseState."""
         if hz is None:
-            if self._L.rnnoise_batch_set_stream_rates(self.h, None):
-                raise RuntimeError("rnnoise_batch_set_stream_rates failed")
-            return
+            return self._call("rnnoise_batch_set_stream_rates", None)
         hz = np.asarray(hz).reshape(-1)
         assert hz.size == self.n
         if not np.isin(hz, PCM_RATES).all():
@@ -469,21 +462,18 @@ class Batch:
         if hz.max(initial=0) > self.pcm_rate:
             raise ValueError(f"a stream rate above the batch's PCM rate {self.pcm_rate}: its frame would not fit its row")
         L = np.ascontiguousarray(48000 // hz.astype(np.int64), np.uint8)
-        if self._L.rnnoise_batch_set_stream_rates(self.h, L.ctypes.data_as(C.POINTER(C.c_ubyte))):
-            raise ValueError("rnnoise_batch_set_stream_rates failed")
+        self._call("rnnoise_batch_set_stream_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
 
     def set_stream_rates_device(self, d_rates: int, stream: int = 0):
         """the same from N bytes of device memory holding the DIVISORS 48000 / rate (1, 2, 3, 6), a copy ordered on `stream`; any other
         byte, or a divisor below the batch's, reads as the batch's rate.  Histories are not touched: reset or load the streams whose
         rate changed (reset_streams_device / load_streams_device) on the same stream before their next frame."""
-        if self._L.rnnoise_batch_set_stream_rates_device(self.h, d_rates or None, stream or None):
-            raise RuntimeError("rnnoise_batch_set_stream_rates_device failed")
+        self._call("rnnoise_batch_set_stream_rates_device", d_rates or None, stream or None)
 
     def stream_rates(self) -> np.ndarray:
         """the PCM rate of every stream in Hz, (N,) int32 (synchronous; the batch's rate everywhere without a table)"""
         L = np.empty(self.n, np.uint8)
-        if self._L.rnnoise_batch_stream_rates(self.h, L.ctypes.data_as(C.POINTER(C.c_ubyte))):
-            raise RuntimeError("rnnoise_batch_stream_rates failed")
+        self._call("rnnoise_batch_stream_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)))
         return (48000 // L.astype(np.int32)).astype(np.int32)
 
     def set_stream_formats(self, formats):
@@ -491,56 +481,34 @@ class Batch:
         "ulaw", "alaw" or codes 0, 1, 2 (rnnoise_amd.g711), or None to drop the table.  A companded stream's G.711 bytes fill the
         first 480 * rate // 48000 BYTES of its int16 row.  Synchronous; ValueError (and nothing changes) on anything else."""
         if formats is None:
-            if self._L.rnnoise_batch_set_stream_formats(self.h, None):
-                raise RuntimeError("rnnoise_batch_set_stream_formats failed")
-            return
+            return self._call("rnnoise_batch_set_stream_formats", None)
         from . import g711
         if isinstance(formats, np.ndarray) and formats.dtype.kind in "iu":
             formats = formats.reshape(-1).tolist()
         codes = np.array([g711.code(f) for f in formats], np.uint8)
         assert codes.size == self.n
-        if self._L.rnnoise_batch_set_stream_formats(self.h, codes.ctypes.data_as(C.POINTER(C.c_ubyte))):
-            raise ValueError("rnnoise_batch_set_stream_formats failed")
+        self._call("rnnoise_batch_set_stream_formats", codes.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
 
     def set_stream_formats_device(self, d_formats: int, stream: int = 0):
         """the same from N bytes of device memory holding the CODES (0 s16, 1 ulaw, 2 alaw), a copy ordered on `stream`; any other
         byte reads as s16.  Nothing else changes: a stream that changes codec mid-run is the caller's to reset."""
-        if self._L.rnnoise_batch_set_stream_formats_device(self.h, d_formats or None, stream or None):
-            raise RuntimeError("rnnoise_batch_set_stream_formats_device failed")
+        self._call("rnnoise_batch_set_stream_formats_device", d_formats or None, stream or None)
 
     def stream_formats(self) -> np.ndarray:
         """the format code of every stream as the kernels read it, (N,) uint8 (synchronous; zeros without a table)"""
         f = np.empty(self.n, np.uint8)
-        if self._L.rnnoise_batch_stream_formats(self.h, f.ctypes.data_as(C.POINTER(C.c_ubyte))):
-            raise RuntimeError("rnnoise_batch_stream_formats failed")
+        self._call("rnnoise_batch_stream_formats", f.ctypes.data_as(C.POINTER(C.c_ubyte)))
         return f
 
     def process(self, pcm: np.ndarray, want_gains: bool = True, out: np.ndarray | None = None):
         """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32]).  With a PCM layout set (set_pcm_layout) pcm and
         out are arrays with the layout's strides, used in place; out may be pcm itself."""
-        pcm = self._pcm_in(pcm, np.float32)
-        T, N, F = self._pcm_dims(pcm)
-        assert N == self.n and F == self.frame
-        out = self._pcm_out(out, pcm, np.float32)
-        vad = np.empty((T, N), np.float32)
-        gains = np.empty((T, N, NB_BANDS), np.float32) if want_gains else None
-        if self._L.rnnoise_batch_process(self.h, _fp(out), _fp(pcm), _fp(vad), _fp(gains), T):
-            raise RuntimeError("rnnoise_batch_process failed")
-        return out, vad, gains
+        return self._process("process", np.float32, pcm, want_gains, out)
 
     def process_s16(self, pcm: np.ndarray, want_gains: bool = True, out: np.ndarray | None = None):
         """pcm: (T, N, 480) int16 host array -> (out int16, vad[T,N], gains[T,N,32]): rnnoise_batch_process_s16, the
         conversions of examples/rnnoise_demo.c:56,58 done on the device."""
-        pcm = self._pcm_in(pcm, np.int16)
-        T, N, F = self._pcm_dims(pcm)
-        assert N == self.n and F == self.frame
-        out = self._pcm_out(out, pcm, np.int16)
-        vad = np.empty((T, N), np.float32)
-        gains = np.empty((T, N, NB_BANDS), np.float32) if want_gains else None
-        sp = C.POINTER(C.c_short)
-        if self._L.rnnoise_batch_process_s16(self.h, out.ctypes.data_as(sp), pcm.ctypes.data_as(sp), _fp(vad), _fp(gains), T):
-            raise RuntimeError("rnnoise_batch_process_s16 failed")
-        return out, vad, gains
+        return self._process("process_s16", np.int16, pcm, want_gains, out)
 
     def process_into(self, out_ptr: int, in_ptr: int, vad_ptr: int, gains_ptr: int, n_frames: int, s16: bool = False):
         """rnnoise_batch_process[_s16] on raw HOST pointers (ints).  Pinned memory (hipHostMalloc / torch pin_memory) is read
@@ -557,37 +525,38 @@ class Batch:
         if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_process_device failed")
 
-    def _masked_args(self, pcm, active, out, dtype):
+    def _process(self, name, dtype, pcm, want_gains, out, masked=False, active=None, streams=None):
+        """the host process calls: rnnoise_batch_<name> on PCM of `dtype`.  masked: the call takes `active` and leaves absent rows of
+        `out` alone; streams: a list call, whose arrays have one row per listed stream"""
         pcm = self._pcm_in(pcm, dtype)
-        T, N, F = self._pcm_dims(pcm)
-        assert N == self.n and F == self.frame
+        T, R, F = self._pcm_dims(pcm)
+        if streams is None:
+            assert R == self.n and F == self.frame
+            rows, exc, why = [], RuntimeError, ""
+        else:
+            streams = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+            assert streams.size == R and F == self.frame
+            rows, exc, why = [streams.ctypes.data_as(C.POINTER(C.c_int)), R], ValueError, " (a stream out of range or listed twice?)"
         active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        assert active is None or active.shape == (T, N)
-        out = self._pcm_out(out, pcm, dtype, zero=True)
-        return pcm, active, out, T
+        assert active is None or active.shape == (T, R)
+        out = self._pcm_out(out, pcm, dtype, zero=masked)
+        vad = np.empty((T, R), np.float32)
+        gains = np.empty((T, R, NB_BANDS), np.float32) if want_gains else None
+        ptr = C.POINTER(C.c_short if dtype == np.int16 else C.c_float)
+        mask = [active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None] if masked else []
+        self._call("rnnoise_batch_" + name, out.ctypes.data_as(ptr), pcm.ctypes.data_as(ptr), _fp(vad), _fp(gains), *rows, *mask, T,
+                   exc=exc, why=why)
+        return out, vad, gains
 
     def process_masked(self, pcm: np.ndarray, active, want_gains: bool = True, out: np.ndarray | None = None):
         """pcm: (T, N, 480) float32, active: (T, N) (nonzero = the stream has this frame; None = all) -> (out, vad[T,N],
         gains[T,N,32]): rnnoise_batch_process_masked.  Absent rows of `out` are not written: they keep what `out` held (zeros
         when it is not given)."""
-        pcm, active, out, T = self._masked_args(pcm, active, out, np.float32)
-        vad = np.empty((T, self.n), np.float32)
-        gains = np.empty((T, self.n, NB_BANDS), np.float32) if want_gains else None
-        ap = active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None
-        if self._L.rnnoise_batch_process_masked(self.h, _fp(out), _fp(pcm), _fp(vad), _fp(gains), ap, T):
-            raise RuntimeError("rnnoise_batch_process_masked failed")
-        return out, vad, gains
+        return self._process("process_masked", np.float32, pcm, want_gains, out, masked=True, active=active)
 
     def process_masked_s16(self, pcm: np.ndarray, active, want_gains: bool = True, out: np.ndarray | None = None):
         """process_masked on int16 PCM (rnnoise_batch_process_masked_s16)"""
-        pcm, active, out, T = self._masked_args(pcm, active, out, np.int16)
-        vad = np.empty((T, self.n), np.float32)
-        gains = np.empty((T, self.n, NB_BANDS), np.float32) if want_gains else None
-        sp = C.POINTER(C.c_short)
-        ap = active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None
-        if self._L.rnnoise_batch_process_masked_s16(self.h, out.ctypes.data_as(sp), pcm.ctypes.data_as(sp), _fp(vad), _fp(gains), ap, T):
-            raise RuntimeError("rnnoise_batch_process_masked_s16 failed")
-        return out, vad, gains
+        return self._process("process_masked_s16", np.int16, pcm, want_gains, out, masked=True, active=active)
 
     def process_masked_device(self, d_out: int, d_in: int, d_vad: int, d_gains: int, d_active: int, n_frames: int, stream: int = 0,
                               s16: bool = False):
@@ -596,37 +565,15 @@ class Batch:
         if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_active or None, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_process_device_masked failed")
 
-    def _list_args(self, pcm, streams, active, out, dtype):
-        pcm = self._pcm_in(pcm, dtype)
-        T, R, F = self._pcm_dims(pcm)
-        streams = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
-        assert streams.size == R and F == self.frame
-        active = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        assert active is None or active.shape == (T, R)
-        out = self._pcm_out(out, pcm, dtype, zero=True)
-        return pcm, streams, active, out, T, R
-
-    def _process_list(self, fn, name, pcm, streams, active, want_gains, out, dtype, ptr):
-        pcm, streams, active, out, T, R = self._list_args(pcm, streams, active, out, dtype)
-        vad = np.empty((T, R), np.float32)
-        gains = np.empty((T, R, NB_BANDS), np.float32) if want_gains else None
-        ap = active.ctypes.data_as(C.POINTER(C.c_ubyte)) if active is not None else None
-        if fn(self.h, out.ctypes.data_as(ptr), pcm.ctypes.data_as(ptr), _fp(vad), _fp(gains), streams.ctypes.data_as(C.POINTER(C.c_int)),
-              R, ap, T):
-            raise ValueError(f"{name} failed (a stream out of range or listed twice?)")
-        return out, vad, gains
-
     def process_list(self, pcm: np.ndarray, streams, active=None, want_gains: bool = True, out: np.ndarray | None = None):
         """Advance only the listed streams: pcm (T, R, 480 / L) float32, row i of every frame belongs to stream streams[i]; active:
         (T, R) or None -> (out, vad[T,R], gains[T,R,32]): rnnoise_batch_process_list.  Absent rows of `out` keep what `out` held
         (zeros when it is not given).  ValueError on an out-of-range or repeated stream (nothing changes then)."""
-        return self._process_list(self._L.rnnoise_batch_process_list, "rnnoise_batch_process_list", pcm, streams, active, want_gains,
-                                  out, np.float32, C.POINTER(C.c_float))
+        return self._process("process_list", np.float32, pcm, want_gains, out, masked=True, active=active, streams=streams)
 
     def process_list_s16(self, pcm: np.ndarray, streams, active=None, want_gains: bool = True, out: np.ndarray | None = None):
         """process_list on int16 PCM (rnnoise_batch_process_list_s16)"""
-        return self._process_list(self._L.rnnoise_batch_process_list_s16, "rnnoise_batch_process_list_s16", pcm, streams, active,
-                                  want_gains, out, np.int16, C.POINTER(C.c_short))
+        return self._process("process_list_s16", np.int16, pcm, want_gains, out, masked=True, active=active, streams=streams)
 
     def process_list_device(self, d_out: int, d_in: int, d_vad: int, d_gains: int, d_streams: int, n_rows: int, d_active: int,
                             n_frames: int, stream: int = 0, s16: bool = False):
@@ -663,19 +610,16 @@ class Batch:
         if m.min(initial=0) < 0 or m.max(initial=0) > 255:
             raise ValueError("model slot out of range")
         m = np.ascontiguousarray(m, np.uint8)
-        if self._L.rnnoise_batch_set_stream_models(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte))):
-            raise ValueError("rnnoise_batch_set_stream_models failed (an entry names no slot)")
+        self._call("rnnoise_batch_set_stream_models", m.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError, why=" (an entry names no slot)")
 
     def set_stream_models_device(self, d_models: int, stream: int = 0):
         """the same from N bytes of device memory, a copy ordered on `stream` (entries naming no slot read as slot 0)"""
-        if self._L.rnnoise_batch_set_stream_models_device(self.h, d_models or None, stream or None):
-            raise RuntimeError("rnnoise_batch_set_stream_models_device failed")
+        self._call("rnnoise_batch_set_stream_models_device", d_models or None, stream or None)
 
     def stream_models(self) -> np.ndarray:
         """the model slot of every stream, (N,) uint8 (synchronous)"""
         m = np.empty(self.n, np.uint8)
-        if self._L.rnnoise_batch_stream_models(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte))):
-            raise RuntimeError("rnnoise_batch_stream_models failed")
+        self._call("rnnoise_batch_stream_models", m.ctypes.data_as(C.POINTER(C.c_ubyte)))
         return m
 
     def set_stream_controls(self, ctl):
@@ -683,24 +627,20 @@ class Batch:
         linear gain floor in [0, 1], thr a VAD gate threshold in [0, 1] (0: no gate), hold whole frames in [0, 65535] -- or None to
         drop the table.  Synchronous; ValueError (and nothing changes) on a non-finite, out-of-range or fractional entry."""
         if ctl is None:
-            if self._L.rnnoise_batch_set_stream_controls(self.h, None):
-                raise RuntimeError("rnnoise_batch_set_stream_controls failed")
-            return
+            return self._call("rnnoise_batch_set_stream_controls", None)
         c = np.ascontiguousarray(ctl, np.float32)
         assert c.shape == (self.n, CTL_FLOATS), c.shape
-        if self._L.rnnoise_batch_set_stream_controls(self.h, _fp(c)):
-            raise ValueError("rnnoise_batch_set_stream_controls failed (an entry is non-finite, out of range or has a fractional hold)")
+        self._call("rnnoise_batch_set_stream_controls", _fp(c), exc=ValueError,
+                   why=" (an entry is non-finite, out of range or has a fractional hold)")
 
     def set_stream_controls_device(self, d_ctl: int, stream: int = 0):
         """the same from N x 3 floats of device memory, a copy ordered on `stream` (the kernel maps NaN to 0, clamps, truncates hold)"""
-        if self._L.rnnoise_batch_set_stream_controls_device(self.h, d_ctl or None, stream or None):
-            raise RuntimeError("rnnoise_batch_set_stream_controls_device failed")
+        self._call("rnnoise_batch_set_stream_controls_device", d_ctl or None, stream or None)
 
     def stream_controls(self) -> np.ndarray:
         """the control table, (N, 3) float32 (zeros when there is none; synchronous)"""
         c = np.empty((self.n, CTL_FLOATS), np.float32)
-        if self._L.rnnoise_batch_stream_controls(self.h, _fp(c)):
-            raise RuntimeError("rnnoise_batch_stream_controls failed")
+        self._call("rnnoise_batch_stream_controls", _fp(c))
         return c
 
     def export_state(self, stream: int) -> np.ndarray:

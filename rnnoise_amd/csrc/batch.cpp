@@ -2,22 +2,18 @@
 #include "shim.h"
 #include "device_choice.h"
 
-namespace {
-template <typename T>
-T *carve(uint8_t *&p, size_t count) {
-  T *r = reinterpret_cast<T *>(p);
-  p += (count * sizeof(T) + 255) & ~size_t(255);
-  return r;
-}
-
-}  // namespace
-
 // the dispatch switches (dispatch.h), read once per process
 const RnKnobs &rn_knobs() {
   static const RnKnobs k = rn_knobs_from_env();
   return k;
 }
 namespace {
+template <typename T>
+T *carve(uint8_t *&p, size_t count) {
+  T *r = reinterpret_cast<T *>(p);
+  p += rn_align256(count * sizeof(T));
+  return r;
+}
 // the arrays of rn_dev.h: RN_GROUP_ARRAYS for n streams from `base` on, then the [n] frame phases of per-stream mode (the group
 // carries a pointer to them only while a call runs in that mode); returns the bytes used (a null base: the arena's size)
 size_t batch_layout(RnGroupDev &g, int *&phase_buf, uint8_t *base, int n) {
@@ -203,328 +199,6 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   return 0;
 }
 
-// PCM rate: K0 upsamples the caller's rows from 48000 / L, K3 downsamples its output back (rn_dev.h: RnGroupDev::rs_L).  48 kHz
-// without a rate table leaves g.rs_hist / g.rs_L null: every launch is then the one of a batch that never saw these calls.
-namespace {
-// the group's resampler fields from the batch's rate and whether it has a rate table (rn_dev.h: RnGroupDev::rs_Ls)
-void rs_point(RNNoiseBatch *b, bool table) {
-  const size_t N = b->n;
-  const bool on = table || b->pcm_rate != 48000;
-  b->g.rs_L = on ? 48000 / b->pcm_rate : 0;
-  b->g.rs_pitch = on ? RN_FRAME_SIZE / b->g.rs_L : 0;
-  b->g.rs_hist = on ? b->rs_buf : nullptr;
-  b->g.rs_up = on ? b->rs_buf + N * RN_RS_HIST : nullptr;
-  b->g.rs_dn = on ? b->rs_buf + N * (RN_RS_HIST + RN_FRAME_SIZE) : nullptr;
-  b->g.rs_Ls = table ? b->rate_map : nullptr;
-}
-// [N][RN_RS_HIST] histories (zero), then the [N][480] planes rs_up and rs_dn (the 48 kHz frames between the filters and the bodies of
-// K0 / K3), on first use; the zeroing is ordered on st
-int rs_alloc(RNNoiseBatch *b, hipStream_t st) {
-  if (b->rs_buf) return 0;
-  const size_t N = b->n, bytes = N * RN_RS_HIST * sizeof(float);
-  HIP_OK(hipMalloc((void **)&b->rs_buf, bytes + 2 * N * RN_FRAME_SIZE * sizeof(float)));
-  HIP_OK(hipMemsetAsync(b->rs_buf, 0, bytes, st));
-  return 0;
-}
-bool rate_divisor_ok(int v, int Lb) { return (v == 1 || v == 2 || v == 3 || v == 6) && v >= Lb; }
-}  // namespace
-
-extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
-  if (!b || (hz != 48000 && hz != 24000 && hz != 16000 && hz != 8000)) return -1;
-  const int old = b->pcm_rate;
-  b->frame_stride = b->row_stride = 0;  // (a PCM layout is in samples of the old rate's frame: dropped by every call)
-  if (hz == old && !b->g.rs_Ls) return old;  // (a rate table is dropped by every call: the rows are redefined)
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset: nothing of the old rate is in flight)
-  if (hz != 48000 && rs_alloc(b, nullptr)) return -1;
-  if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float)));
-  HIP_OK(hipDeviceSynchronize());
-  b->pcm_rate = hz;
-  rs_point(b, false);
-  return old;
-}
-
-// ---- per-stream rates (include/rnnoise_amd.h) ----
-// The table lives in rate_map from the first set on; while one is set the batch runs its resampling launches at 48 kHz too (rs_L = 1),
-// and K0 / K3 and the snapshot kernels take each stream's divisor from it (rn_dev.h: rn_stream_L).
-extern "C" int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned char *rates) {
-  if (!b) return -1;
-  const int Lb = 48000 / b->pcm_rate;
-  if (rates)
-    for (int s = 0; s < b->n; s++)
-      if (!rate_divisor_ok(rates[s], Lb)) return -1;
-  if (!rates && !b->g.rs_Ls) return 0;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_stream_models: a call in flight keeps what it was launched with)
-  const size_t N = b->n;
-  std::vector<uint8_t> cur(N, (uint8_t)Lb);
-  if (b->g.rs_Ls) {
-    HIP_OK(hipMemcpy(cur.data(), b->rate_map, N, hipMemcpyDeviceToHost));
-    for (auto &v : cur)
-      if (!rate_divisor_ok(v, Lb)) v = (uint8_t)Lb;  // (what the kernels read an unchecked entry of the device setter as)
-  }
-  if (rs_alloc(b, nullptr)) return -1;
-  if (rates && !b->rate_map) HIP_OK(hipMalloc((void **)&b->rate_map, N));
-  // the history of every stream whose divisor changes restarts from zero: one memset per run of such streams
-  for (size_t s = 0; s < N;) {
-    if (cur[s] == (rates ? rates[s] : Lb)) {
-      s++;
-      continue;
-    }
-    size_t e = s + 1;
-    while (e < N && cur[e] != (rates ? rates[e] : Lb)) e++;
-    HIP_OK(hipMemsetAsync(b->rs_buf + s * RN_RS_HIST, 0, (e - s) * RN_RS_HIST * sizeof(float), nullptr));
-    s = e;
-  }
-  if (rates) HIP_OK(hipMemcpy(b->rate_map, rates, N, hipMemcpyHostToDevice));
-  HIP_OK(hipDeviceSynchronize());
-  rs_point(b, rates != nullptr);
-  return 0;
-}
-
-extern "C" int rnnoise_batch_set_stream_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream) {
-  if (!b || !d_rates) return -1;
-  ON_DEVICE(b->device);
-  // a copy, not a kernel: ordered on the caller's stream between its calls; the kernels read an entry that names no rate of this
-  // batch as the batch's own.  Histories are the caller's to reset (include/rnnoise_amd.h).
-  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (rs_alloc(b, st)) return -1;
-  if (!b->rate_map) HIP_OK(hipMalloc((void **)&b->rate_map, (size_t)b->n));
-  if (!b->g.rs_Ls) rs_point(b, true);
-  HIP_OK(hipMemcpyAsync(b->rate_map, d_rates, (size_t)b->n, hipMemcpyDeviceToDevice, st));
-  return 0;
-}
-
-extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates) {
-  if (!b || !rates) return -1;
-  const int Lb = 48000 / b->pcm_rate;
-  if (!b->g.rs_Ls) {
-    memset(rates, Lb, (size_t)b->n);
-    return 0;
-  }
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(rates, b->rate_map, (size_t)b->n, hipMemcpyDeviceToHost));
-  for (int s = 0; s < b->n; s++)
-    if (!rate_divisor_ok(rates[s], Lb)) rates[s] = (unsigned char)Lb;  // (as the kernels read it)
-  return 0;
-}
-
-extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
-
-// ---- caller-defined PCM strides (include/rnnoise_amd.h) ----
-// Two numbers of the batch.  A process call hands the row stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and steps its frame
-// pointers by the frame stride (batch_process_device_impl); without a layout both keep their defaults and every launch is the one of
-// a batch that never saw these calls.
-extern "C" int rnnoise_batch_set_pcm_layout(RNNoiseBatch *b, long frame_stride, long row_stride) {
-  if (!b || !rn_pcm_layout_ok(frame_stride, row_stride)) return -1;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_pcm_rate: a call in flight keeps what it was launched with)
-  b->frame_stride = frame_stride;
-  b->row_stride = row_stride;
-  return 0;
-}
-
-extern "C" int rnnoise_batch_pcm_layout(const RNNoiseBatch *b, long *frame_stride, long *row_stride) {
-  if (!b) return -1;
-  if (frame_stride) *frame_stride = b->frame_stride;
-  if (row_stride) *row_stride = b->row_stride;
-  return 0;
-}
-
-extern "C" int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_stride, int frame_samples, int n_rows, int n_frames) {
-  return rn_pcm_layout_ok(frame_stride, row_stride) && (frame_stride || row_stride) &&
-                 rn_pcm_layout_fits(frame_stride, row_stride, frame_samples, n_rows, n_frames)
-             ? 1
-             : 0;
-}
-
-// ---- interleaved channels (include/rnnoise_amd.h) ----
-// One number of the batch.  A process call hands it to K0 / K3 (rn_dev.h: RnGroupDev::pcm_chan) and to the step's plan (dispatch.h:
-// RnStepShape::channels); at 1 nothing is handed on and every launch is the one of a batch that never saw these calls.
-extern "C" int rnnoise_batch_set_pcm_channels(RNNoiseBatch *b, int channels) {
-  if (!b || !rn_pcm_channels_ok(channels, b->n)) return -1;
-  const int old = b->channels;
-  if (channels == old) return old;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_pcm_layout: a call in flight keeps what it was launched with)
-  b->channels = channels;
-  return old;
-}
-
-extern "C" int rnnoise_batch_pcm_channels(const RNNoiseBatch *b) { return b ? b->channels : -1; }
-
-extern "C" int rnnoise_amd_pcm_channels_fit(long frame_stride, long row_stride, int frame_samples, int channels, int n_rows, int n_frames) {
-  return rn_pcm_layout_ok(frame_stride, row_stride) && (frame_stride || row_stride) &&
-                 rn_pcm_channels_fit(frame_stride, row_stride, frame_samples, channels, n_rows, n_frames)
-             ? 1
-             : 0;
-}
-
-// ---- per-stream PCM formats (include/rnnoise_amd.h) ----
-// The table lives in fmt_map from the first set on; while one is set (g.pcm_fmt) K0 expands and K3 compresses the rows of the
-// companded streams in every int16 call (rn_dev.h: rn_stream_fmt), and those calls plan K0 one wave per stream (dispatch.h).  It is
-// configuration: nothing is zeroed when it changes, and nothing but these two setters and the batch's end touches it.
-extern "C" int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsigned char *formats) {
-  if (!b) return -1;
-  if (formats)
-    for (int s = 0; s < b->n; s++)
-      if (formats[s] > RNNOISE_AMD_PCM_ALAW) return -1;
-  if (!formats && !b->g.pcm_fmt) return 0;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_stream_models: a call in flight keeps what it was launched with)
-  if (formats) {
-    if (!b->fmt_map) HIP_OK(hipMalloc((void **)&b->fmt_map, (size_t)b->n));
-    HIP_OK(hipMemcpy(b->fmt_map, formats, (size_t)b->n, hipMemcpyHostToDevice));
-  }
-  b->g.pcm_fmt = formats ? b->fmt_map : nullptr;
-  return 0;
-}
-
-extern "C" int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream) {
-  if (!b || !d_formats) return -1;
-  ON_DEVICE(b->device);
-  // a copy, not a kernel: ordered on the caller's stream between its calls; the kernels read a byte that names no law as int16 rows
-  if (!b->fmt_map) HIP_OK(hipMalloc((void **)&b->fmt_map, (size_t)b->n));
-  b->g.pcm_fmt = b->fmt_map;
-  HIP_OK(hipMemcpyAsync(b->fmt_map, d_formats, (size_t)b->n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
-  return 0;
-}
-
-extern "C" int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *formats) {
-  if (!b || !formats) return -1;
-  if (!b->g.pcm_fmt) {
-    memset(formats, 0, (size_t)b->n);
-    return 0;
-  }
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(formats, b->fmt_map, (size_t)b->n, hipMemcpyDeviceToHost));
-  for (int s = 0; s < b->n; s++)
-    if (formats[s] > RNNOISE_AMD_PCM_ALAW) formats[s] = RNNOISE_AMD_PCM_LINEAR;  // (as the kernels read it)
-  return 0;
-}
-
-// ---- per-stream models (include/rnnoise_amd.h) ----
-// The network of every step is launched once per slot (batch_process_device_impl); the launch of slot k owns the streams the map puts
-// on k (rn_dev.h: rn_owns).  The map exists from the first add_model on; before that every stream is on slot 0 and nothing is read.
-extern "C" int rnnoise_batch_add_model(RNNoiseBatch *b, RNNModel *model) {
-  if (!b || !model || b->n_models >= RNNOISE_AMD_MAX_MODELS) return -1;
-  ON_DEVICE(b->device);
-  RnModelDev md;
-  if (model_on_device(model, b->device, md)) return -1;
-  HIP_OK(hipDeviceSynchronize());  // (synchronous: a call in flight keeps the slots it was launched with)
-  if (!b->model_map) {
-    HIP_OK(hipMalloc((void **)&b->model_map, (size_t)b->n));
-    HIP_OK(hipMemset(b->model_map, 0, (size_t)b->n));
-    HIP_OK(hipDeviceSynchronize());
-  }
-  const int k = b->n_models++;
-  b->models[k] = model;
-  b->slot_m[k] = md;
-  b->g.model_of = b->model_map;
-  b->g.n_models = b->n_models;
-  return k;
-}
-
-extern "C" int rnnoise_batch_set_stream_models(RNNoiseBatch *b, const unsigned char *models) {
-  if (!b || !models) return -1;
-  for (int s = 0; s < b->n; s++)
-    if (models[s] >= b->n_models) return -1;
-  if (!b->model_map) return 0;  // (one slot: every entry is 0, which is what the batch runs)
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset_streams)
-  HIP_OK(hipMemcpy(b->model_map, models, (size_t)b->n, hipMemcpyHostToDevice));
-  HIP_OK(hipDeviceSynchronize());
-  return 0;
-}
-
-extern "C" int rnnoise_batch_set_stream_models_device(RNNoiseBatch *b, const unsigned char *d_models, void *hip_stream) {
-  if (!b || !d_models) return -1;
-  if (!b->model_map) return 0;  // (one slot: any entry reads as slot 0)
-  ON_DEVICE(b->device);
-  // a copy, not a kernel: ordered on the caller's stream between its calls; entries naming no slot are read as slot 0 by the kernels
-  HIP_OK(hipMemcpyAsync(b->model_map, d_models, (size_t)b->n, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
-  return 0;
-}
-
-extern "C" int rnnoise_batch_stream_models(RNNoiseBatch *b, unsigned char *models) {
-  if (!b || !models) return -1;
-  if (!b->model_map) {
-    memset(models, 0, (size_t)b->n);
-    return 0;
-  }
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(models, b->model_map, (size_t)b->n, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// ---- per-stream suppression controls (include/rnnoise_amd.h) ----
-// The table and the counters live in ctl_buf from the first set on; g.ctl / g.gate_c point into it while a table is set, and K3 reads
-// them (rn_dev.h: RnGroupDev::ctl).  Without a table both are null and every launch is the one of a batch that never saw these calls.
-static_assert(RN_CTL_FLOATS == RNNOISE_AMD_CTL_FLOATS, "one record size for the kernels and the API");
-namespace {
-bool ctl_entry_ok(const float *e) {
-  const float floor_gain = e[0], thr = e[1], hold = e[2];
-  return std::isfinite(floor_gain) && std::isfinite(thr) && std::isfinite(hold) && floor_gain >= 0.f && floor_gain <= 1.f &&
-         thr >= 0.f && thr <= 1.f && hold >= 0.f && hold <= 65535.f && hold == std::floor(hold);
-}
-// memory on first use; a table set after none (or after a NULL set) starts every counter at RN_CTL_NONE, ordered on st
-int ctl_arm(RNNoiseBatch *b, hipStream_t st) {
-  const size_t N = b->n;
-  if (!b->ctl_buf) HIP_OK(hipMalloc((void **)&b->ctl_buf, N * RN_CTL_FLOATS * sizeof(float) + N * sizeof(int)));
-  if (!b->g.ctl) {
-    int *c = reinterpret_cast<int *>(b->ctl_buf + N * RN_CTL_FLOATS);
-    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c), RN_CTL_NONE, N, st));
-    b->g.ctl = b->ctl_buf;
-    b->g.gate_c = c;
-  }
-  return 0;
-}
-}  // namespace
-
-extern "C" int rnnoise_batch_set_stream_controls(RNNoiseBatch *b, const float *ctl) {
-  if (!b) return -1;
-  if (ctl)
-    for (int s = 0; s < b->n; s++)
-      if (!ctl_entry_ok(ctl + (size_t)s * RN_CTL_FLOATS)) return -1;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_set_stream_models: a call in flight keeps what it was launched with)
-  if (!ctl) {  // no table: the launches of a batch without one; the counters go with it
-    b->g.ctl = nullptr;
-    b->g.gate_c = nullptr;
-    return 0;
-  }
-  if (ctl_arm(b, nullptr)) return -1;
-  HIP_OK(hipMemcpy(b->ctl_buf, ctl, (size_t)b->n * RN_CTL_FLOATS * sizeof(float), hipMemcpyHostToDevice));
-  HIP_OK(hipDeviceSynchronize());
-  return 0;
-}
-
-extern "C" int rnnoise_batch_set_stream_controls_device(RNNoiseBatch *b, const float *d_ctl, void *hip_stream) {
-  if (!b || !d_ctl) return -1;
-  ON_DEVICE(b->device);
-  // a copy, not a kernel: ordered on the caller's stream between its calls; K3 sanitises what it reads (NaN as 0, clamped, truncated)
-  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (ctl_arm(b, st)) return -1;
-  HIP_OK(hipMemcpyAsync(b->ctl_buf, d_ctl, (size_t)b->n * RN_CTL_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
-  return 0;
-}
-
-extern "C" int rnnoise_batch_stream_controls(RNNoiseBatch *b, float *ctl) {
-  if (!b || !ctl) return -1;
-  const size_t bytes = (size_t)b->n * RN_CTL_FLOATS * sizeof(float);
-  if (!b->g.ctl) {
-    memset(ctl, 0, bytes);
-    return 0;
-  }
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(ctl, b->ctl_buf, bytes, hipMemcpyDeviceToHost));
-  return 0;
-}
-
 extern "C" int rnnoise_batch_set_schedule(RNNoiseBatch *b, int schedule) {
   if (!b || (schedule != 0 && schedule != 1 && schedule != 9)) return -1;
   const int old = b->schedule;
@@ -539,60 +213,64 @@ extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
   return old;
 }
 
-// PCM frames are float (the reference API's sample type) or, with s16 set, int16 converted at the two ends of the step as the
-// reference's only caller does (examples/rnnoise_demo.c:56,58): half the bytes over HBM and, in the host-fed path, PCIe.
-// d_active: the presence mask of a masked call ([n_frames][N] bytes, include/rnnoise_amd.h), or null.
-// d_list: the streams of a stream-list call (n_rows int32 on the device, include/rnnoise_amd.h), or null; the caller's buffers and
-// d_active then have n_rows rows per frame (rn_dev.h: RnGroupDev::list).
-int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v, float *d_vad, float *d_gains, int n_frames,
-                              void *hip_stream, bool s16, const FrameIoHooks *hk, const uint8_t *d_active, const int *d_list,
-                              int n_rows, bool packed) {
+// The step: the frames of one process call (shim.h: ProcessCall), every pointer of it device memory.  PCM frames are float (the
+// reference API's sample type) or, with s16 set, int16 converted at the two ends of the step as the reference's only caller does
+// (examples/rnnoise_demo.c:56,58): half the bytes over HBM and, in the host-fed path, PCIe.
+int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
+  const int n_frames = c.n_frames, n_rows = c.n_rows;
+  const bool s16 = c.s16;
+  const FrameIoHooks *hk = c.hooks;
   if (!b || n_frames < 0) return -1;
-  const bool listed = d_list || n_rows;
+  const bool listed = c.list || n_rows;
   if (listed) {
-    if (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !d_list)) return -1;
+    if (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !c.list)) return -1;
     if (n_rows == 0) return 0;
   }
-  if (!d_out_v || !d_in_v) return -1;
+  if (!c.out || !c.in) return -1;
   // the caller's PCM layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), unless the buffers are the library's own (packed:
   // the staged host path; hk: the pinned ring).  Its frame slots must be disjoint, checked before anything is launched or changed
   // Interleaved channels (rnnoise_batch_set_pcm_channels): the rows are taken `chan` at a time, in the library's staging buffer
   // (packed) as in the caller's; the strides then place group slots of chan rows.  The pinned ring (hk) never sees channels
   const int chan = hk ? 1 : b->channels;
   if (listed && n_rows % chan) return -1;
-  const bool laid = b->row_stride && !packed && !hk;
-  if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1), chan,
-                                   listed ? n_rows : b->n, n_frames))
+  const bool laid = b->row_stride && !c.packed && !hk;
+  if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, batch_frame_samples(b), chan, listed ? n_rows : b->n, n_frames))
     return -1;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const hipStream_t st = static_cast<hipStream_t>(c.stream);
   ON_DEVICE(b->device);
-  if ((d_active || listed) && !b->per_stream && n_frames > 0) {
+  if ((c.active || listed) && !b->per_stream && n_frames > 0) {
     // the first masked or list call puts the batch into per-stream frame phase: every stream starts at the batch's phase.  ring_slot, not
     // frame_no: the training-feature calls advance the slots without counting frames (ring_slot % 3 == parity always)
     HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->phase_buf), b->ring_slot, b->n, st));
     b->per_stream = true;
   }
-  // the phase fields of the group a kernel of frame f gets (all null / 0 in lock-step mode: today's launches)
-  auto phased = [&](RnGroupDev &g, int f) {
-    if (!b->per_stream) return;
-    g.phase = b->phase_buf;
-    g.active = d_active;
-    g.call_frame = f;
-    g.call_frames = n_frames;
-    if (listed) {
-      g.list = d_list;
-      g.list_n = n_rows;
-    }
-  };
   const size_t N = listed ? n_rows : b->n, esz = s16 ? sizeof(short) : sizeof(float);  // (N: rows of the caller's buffers)
-  const size_t fl = RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1);  // samples per stream and frame at the batch's PCM rate
-  const char *d_in = static_cast<const char *>(d_in_v);
-  char *d_out = static_cast<char *>(d_out_v);
+  const size_t fl = batch_frame_samples(b);
+  const char *d_in = static_cast<const char *>(c.in);
+  char *d_out = static_cast<char *>(c.out);
   auto buf = [&](int f) -> size_t { return hk ? (size_t)(f % hk->ring) : (size_t)f; };  // frame f's place in the caller's buffers
   // bytes between the frames of the PCM buffers, and the row pitch K0 / K3 get (0: the form's own constant -- today's arguments)
   const size_t fstep = (laid ? (size_t)b->frame_stride : N * fl) * esz;
   const int pcm_pitch = laid ? (int)b->row_stride : 0;
   const int pcm_chan = chan > 1 ? chan : 0;  // (rn_dev.h: RnGroupDev::pcm_chan -- 0: today's addressing)
+  // the batch's group with what every launch of frame f gets from the call: the PCM addressing, and in per-stream mode the phase and
+  // list fields (all null / 0 in lock-step mode).  The high-pass takes it as it is, the other kernels through frame_group
+  auto call_group = [&](int f) {
+    RnGroupDev g = b->g;
+    g.pcm_pitch = pcm_pitch;
+    g.pcm_chan = pcm_chan;
+    if (b->per_stream) {
+      g.phase = b->phase_buf;
+      g.active = c.active;
+      g.call_frame = f;
+      g.call_frames = n_frames;
+      if (listed) {
+        g.list = c.list;
+        g.list_n = n_rows;
+      }
+    }
+    return g;
+  };
   // Multi-frame calls are software-pipelined over three streams: C runs the high-pass of frames up to
   // f+2, B the analysis of frame f+1, A (the caller's stream) network + synthesis of frame f.
   // What makes that legal:
@@ -634,19 +312,16 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     HIP_OK(hipStreamWaitEvent(b->side_hp, b->ev_begin, 0));
   }
   auto frame_group = [&](int f) {
-    RnGroupDev g = b->g;
-    g.pcm_pitch = pcm_pitch;
-    g.pcm_chan = pcm_chan;
-    const int c = (int)((b->frame_no + f) & 1);
-    g.features = b->features2[c];
-    g.silence = b->silence2[c];
-    g.pitch = b->pitch2[c];
-    g.vad = d_vad ? d_vad + buf(f) * N : b->scratch_vad;
-    g.gains = d_gains ? d_gains + buf(f) * N * RN_NB_BANDS : b->scratch_gains;
-    phased(g, f);
+    RnGroupDev g = call_group(f);
+    const int k = (int)((b->frame_no + f) & 1);
+    g.features = b->features2[k];
+    g.silence = b->silence2[k];
+    g.pitch = b->pitch2[k];
+    g.vad = c.vad ? c.vad + buf(f) * N : b->scratch_vad;
+    g.gains = c.gains ? c.gains + buf(f) * N * RN_NB_BANDS : b->scratch_gains;
     if (listed) {  // the network writes the per-stream scratch, K3 copies the listed rows out (rn_dev.h: RnGroupDev::list)
-      g.list_vad = d_vad ? g.vad : nullptr;
-      g.list_gains = d_gains ? g.gains : nullptr;
+      g.list_vad = c.vad ? g.vad : nullptr;
+      g.list_gains = c.gains ? g.gains : nullptr;
       g.vad = b->scratch_vad;
       g.gains = b->scratch_gains;
     }
@@ -671,10 +346,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
     {
       TimedLaunch t(b, 3);
       b->cur_hp[f & 7] = t.on ? t.stop() : (pipelined ? b->own_hp[f & 7] : nullptr);
-      RnGroupDev gh = b->g;
-      gh.pcm_pitch = pcm_pitch;
-      gh.pcm_chan = pcm_chan;
-      phased(gh, f);
+      const RnGroupDev gh = call_group(f);
       HIP_OK(rn_launch_hp(&gh, d_in + buf(f) * fstep, s16, (b->ring_slot + f) % RN_RING_SLOTS, plan.hp, sc, t.start(),
                           b->cur_hp[f & 7]));
     }
@@ -749,7 +421,7 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
   }
   // a list call keeps the layer-wise network's state images: only its rows' tiles are rebuilt (rn_dev.h: act_q), as after
   // rnnoise_batch_reset_streams -- not the whole batch at the next lock-step step
-  if (listed && b->img_valid && n_frames > 0) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n_rows));
+  if (listed && b->img_valid && n_frames > 0) HIP_OK(rn_launch_nn_requant(&b->g, st, c.list, n_rows));
   b->parity = (b->parity + n_frames) % RN_SPEC_SLOTS;
   b->ring_slot = (b->ring_slot + n_frames) % RN_RING_SLOTS;
   b->frame_no += n_frames;
@@ -758,36 +430,39 @@ int batch_process_device_impl(RNNoiseBatch *b, void *d_out_v, const void *d_in_v
 
 extern "C" int rnnoise_batch_process_device(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad,
                                             float *d_gains, int n_frames, void *hip_stream) {
-  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, false);
+  return batch_process_device_impl(
+      b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames, .stream = hip_stream});
 }
 
 extern "C" int rnnoise_batch_process_device_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad,
                                                 float *d_gains, int n_frames, void *hip_stream) {
-  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true);
+  return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
+                                       .stream = hip_stream, .s16 = true});
 }
 
-// ---- masked calls and per-stream reset (include/rnnoise_amd.h) ----
+// ---- masked calls (include/rnnoise_amd.h) ----
 extern "C" int rnnoise_batch_process_device_masked(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad, float *d_gains,
                                                    const unsigned char *d_active, int n_frames, void *hip_stream) {
-  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, false, nullptr, d_active);
+  return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
+                                       .stream = hip_stream, .active = d_active});
 }
 
 extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad,
                                                        float *d_gains, const unsigned char *d_active, int n_frames, void *hip_stream) {
-  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true, nullptr, d_active);
+  return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
+                                       .stream = hip_stream, .s16 = true, .active = d_active});
 }
 
-// The convenience form on host buffers: everything staged through one device allocation with plain synchronous copies (no pinned
-// ring, no copy engines -- rnnoise_batch_process is the fast host path).  `out` goes up too, so that its absent rows come back as
-// the caller left them.  The masked host calls, every host call at a PCM rate other than 48 kHz or with a rate table, the int16
-// host calls of a batch with a format table, and every host call of a batch with a PCM layout or with interleaved channels come here.
-// A list call (list set: n_rows host int32 entries, checked by the caller) stages the list too, and its buffers have n_rows rows.
-int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
-                         int n_frames, bool s16, const int *list, int n_rows) {
-  if (!b || !out || !in || n_frames < 0) return -1;
+// The convenience form on host buffers: every pointer of the call is host memory, staged through one device allocation with plain
+// synchronous copies (no pinned ring, no copy engines -- rnnoise_batch_process is the fast host path).  The masked and the list host
+// calls come here, and the plain ones that batch_host_call_staged (shim.h) names.  A list call (its n_rows entries checked by the
+// caller) stages the list too, and its buffers have n_rows rows.
+int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c) {
+  const int n_frames = c.n_frames;
+  if (!b || !c.out || !c.in || n_frames < 0) return -1;
   if (n_frames == 0) return 0;
-  const size_t rows = list ? n_rows : b->n;
-  const size_t M = RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1), esz = s16 ? 2 : 4;
+  const size_t rows = c.list ? c.n_rows : b->n;
+  const size_t M = batch_frame_samples(b), esz = c.s16 ? 2 : 4;
   // a caller-defined layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): the frame slots travel by strided copies between
   // the caller's buffers and the default layout in device memory -- one 2-D copy per frame, its rows row_stride apart --, so the
   // device runs the launches of the default layout and nothing but the slots themselves is read or written on the host
@@ -798,67 +473,54 @@ int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad,
   const bool laid = b->row_stride != 0;
   if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, (int)M, (int)C, (int)rows, n_frames)) return -1;
   ON_DEVICE(b->device);
-  auto pcm_copy = [&](void *dst, const void *src, bool up) -> bool {
-    if (!laid) return hipMemcpy(dst, src, (size_t)n_frames * rows * M * esz, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) == hipSuccess;
+  auto pcm_copy = [&](void *dst, const void *src, bool up) -> int {
+    if (!laid) {
+      HIP_OK(hipMemcpy(dst, src, (size_t)n_frames * rows * M * esz, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+      return 0;
+    }
     const size_t hp = (size_t)b->row_stride * esz, hf = (size_t)b->frame_stride * esz, dp = M * C * esz, df = rows * M * esz;
     for (int f = 0; f < n_frames; f++) {
-      const hipError_t e = up ? hipMemcpy2D(static_cast<char *>(dst) + f * df, dp, static_cast<const char *>(src) + f * hf, hp, dp, rows / C,
-                                            hipMemcpyHostToDevice)
-                              : hipMemcpy2D(static_cast<char *>(dst) + f * hf, hp, static_cast<const char *>(src) + f * df, dp, dp, rows / C,
-                                            hipMemcpyDeviceToHost);
-      if (e != hipSuccess) return false;
+      if (up) HIP_OK(hipMemcpy2D(static_cast<char *>(dst) + f * df, dp, static_cast<const char *>(src) + f * hf, hp, dp, rows / C,
+                                 hipMemcpyHostToDevice));
+      else HIP_OK(hipMemcpy2D(static_cast<char *>(dst) + f * hf, hp, static_cast<const char *>(src) + f * df, dp, dp, rows / C,
+                              hipMemcpyDeviceToHost));
     }
-    return true;
+    return 0;
   };
   const size_t fs = (size_t)n_frames * rows, pcm = fs * M * esz;
-  const size_t o_in = 0, o_out = pcm, o_vad = 2 * pcm, o_gains = o_vad + fs * 4, o_act = o_gains + fs * RN_NB_BANDS * 4,
-               o_list = (o_act + fs + 255) & ~size_t(255), total = o_list + (list ? rows * sizeof(int) : 0);
-  char *d = nullptr;
-  HIP_OK(hipMalloc((void **)&d, total));
-  int rc = -1;
-  if (pcm_copy(d + o_in, in, true) &&
-      // (absent rows, and the part of a row behind the frame of a stream of a rate table or behind a companded stream's bytes, keep
-      //  the caller's values)
-      ((!active && !list && !b->g.rs_Ls && !(s16 && b->g.pcm_fmt)) || pcm_copy(d + o_out, out, true)) &&
-      (!active || hipMemcpy(d + o_act, active, fs, hipMemcpyHostToDevice) == hipSuccess) &&
-      (!list || hipMemcpy(d + o_list, list, rows * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
-      batch_process_device_impl(b, d + o_out, d + o_in, vad ? (float *)(d + o_vad) : nullptr, gains ? (float *)(d + o_gains) : nullptr,
-                                n_frames, nullptr, s16, nullptr, active ? (const uint8_t *)(d + o_act) : nullptr,
-                                list ? (const int *)(d + o_list) : nullptr, list ? n_rows : 0, true) == 0 &&
-      hipDeviceSynchronize() == hipSuccess && pcm_copy(out, d + o_out, false) &&
-      (!vad || hipMemcpy(vad, d + o_vad, fs * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
-      (!gains || hipMemcpy(gains, d + o_gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost) == hipSuccess))
-    rc = 0;
-  hipFree(d);
-  return rc;
-}
-
-namespace {
-int batch_process_masked_host(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
-                              int n_frames, bool s16) {
-  if (!b || !out || !in || n_frames < 0) return -1;
-  if (!active) return s16 ? rnnoise_batch_process_s16(b, (short *)out, (const short *)in, vad, gains, n_frames)
-                          : rnnoise_batch_process(b, (float *)out, (const float *)in, vad, gains, n_frames);
-  return batch_process_staged(b, out, in, vad, gains, active, n_frames, s16);
-}
-
-// zero state for the n streams of the device list d_list, on st; the layer-wise network's state images of their tiles follow
-// (rn_dev.h: act_q) while they are in use, so that a reset costs no re-quantisation of the whole batch at the next step
-int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_zero(&b->g, d_list, n, st));
-  if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n));
+  DevScratch d;
+  const size_t o_in = d.carve(pcm), o_out = d.carve(pcm), o_vad = d.carve(fs * 4), o_gains = d.carve(fs * RN_NB_BANDS * 4),
+               o_act = d.carve(fs), o_list = d.carve(c.list ? rows * sizeof(int) : 0);
+  if (d.alloc()) return -1;
+  const ProcessCall dc{.out = d.at<char>(o_out), .in = d.at<char>(o_in), .vad = c.vad ? d.at<float>(o_vad) : nullptr,
+                       .gains = c.gains ? d.at<float>(o_gains) : nullptr, .n_frames = n_frames, .s16 = c.s16,
+                       .active = c.active ? d.at<uint8_t>(o_act) : nullptr, .list = c.list ? d.at<int>(o_list) : nullptr,
+                       .n_rows = c.list ? c.n_rows : 0, .packed = true};  // the same call on the staged copies, on the null stream
+  if (pcm_copy(d.at<char>(o_in), c.in, true)) return -1;
+  // `out` goes up too where the device leaves parts of it alone: absent rows, the part of a row behind the frame of a stream of a
+  // rate table or behind a companded stream's bytes keep the caller's values
+  if ((c.active || c.list || b->g.rs_Ls || (c.s16 && b->g.pcm_fmt)) && pcm_copy(dc.out, c.out, true)) return -1;
+  if (c.active) HIP_OK(hipMemcpy(d.at<uint8_t>(o_act), c.active, fs, hipMemcpyHostToDevice));
+  if (c.list) HIP_OK(hipMemcpy(d.at<int>(o_list), c.list, rows * sizeof(int), hipMemcpyHostToDevice));
+  if (batch_process_device_impl(b, dc)) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  if (pcm_copy(c.out, dc.out, false)) return -1;
+  if (c.vad) HIP_OK(hipMemcpy(c.vad, dc.vad, fs * 4, hipMemcpyDeviceToHost));
+  if (c.gains) HIP_OK(hipMemcpy(c.gains, dc.gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost));
   return 0;
 }
-}  // namespace
 
 extern "C" int rnnoise_batch_process_masked(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains,
                                             const unsigned char *active, int n_frames) {
-  return batch_process_masked_host(b, out, in, vad, gains, active, n_frames, false);
+  if (!active) return rnnoise_batch_process(b, out, in, vad, gains, n_frames);
+  return batch_process_staged(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames, .active = active});
 }
 
 extern "C" int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                                 const unsigned char *active, int n_frames) {
-  return batch_process_masked_host(b, out, in, vad, gains, active, n_frames, true);
+  if (!active) return rnnoise_batch_process_s16(b, out, in, vad, gains, n_frames);
+  return batch_process_staged(
+      b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames, .s16 = true, .active = active});
 }
 
 // ---- stream-list calls (include/rnnoise_amd.h) ----
@@ -866,64 +528,43 @@ extern "C" int rnnoise_batch_process_device_list(RNNoiseBatch *b, float *d_out, 
                                                  const int *d_streams, int n_rows, const unsigned char *d_active, int n_frames,
                                                  void *hip_stream) {
   if (!d_streams && n_rows == 0) return b ? 0 : -1;
-  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, false, nullptr, d_active, d_streams, n_rows);
+  return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
+                                       .stream = hip_stream, .active = d_active, .list = d_streams, .n_rows = n_rows});
 }
 
 extern "C" int rnnoise_batch_process_device_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad, float *d_gains,
                                                      const int *d_streams, int n_rows, const unsigned char *d_active, int n_frames,
                                                      void *hip_stream) {
   if (!d_streams && n_rows == 0) return b ? 0 : -1;
-  return batch_process_device_impl(b, d_out, d_in, d_vad, d_gains, n_frames, hip_stream, true, nullptr, d_active, d_streams, n_rows);
+  return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
+                                       .stream = hip_stream, .s16 = true, .active = d_active, .list = d_streams, .n_rows = n_rows});
 }
 
 namespace {
 // the host list is checked before anything moves: an entry outside the batch or a stream listed twice refuses the call
-int batch_process_list_host(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const int *streams, int n_rows,
-                            const unsigned char *active, int n_frames, bool s16) {
-  if (!b || n_rows < 0 || n_rows > b->n || (n_rows > 0 && !streams) || n_frames < 0) return -1;
-  if (n_rows == 0) return 0;
+int batch_process_list_host(RNNoiseBatch *b, const ProcessCall &c) {
+  if (!b || c.n_rows < 0 || c.n_rows > b->n || (c.n_rows > 0 && !c.list) || c.n_frames < 0) return -1;
+  if (c.n_rows == 0) return 0;
   std::vector<uint8_t> seen((size_t)b->n, 0);
-  for (int i = 0; i < n_rows; i++) {
-    const int s = streams[i];
+  for (int i = 0; i < c.n_rows; i++) {
+    const int s = c.list[i];
     if (s < 0 || s >= b->n || seen[s]) return -1;
     seen[s] = 1;
   }
-  return batch_process_staged(b, out, in, vad, gains, active, n_frames, s16, streams, n_rows);
+  return batch_process_staged(b, c);
 }
 }  // namespace
 
 extern "C" int rnnoise_batch_process_list(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains, const int *streams,
                                           int n_rows, const unsigned char *active, int n_frames) {
-  return batch_process_list_host(b, out, in, vad, gains, streams, n_rows, active, n_frames, false);
+  return batch_process_list_host(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames, .active = active,
+                                     .list = streams, .n_rows = n_rows});
 }
 
 extern "C" int rnnoise_batch_process_list_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                               const int *streams, int n_rows, const unsigned char *active, int n_frames) {
-  return batch_process_list_host(b, out, in, vad, gains, streams, n_rows, active, n_frames, true);
-}
-
-extern "C" int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n) {
-  if (!b || n < 0 || (n > 0 && !streams)) return -1;
-  for (int i = 0; i < n; i++)
-    if (streams[i] < 0 || streams[i] >= b->n) return -1;
-  if (n == 0) return 0;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());  // (synchronous, like rnnoise_batch_reset and import_state)
-  int *d = nullptr;
-  HIP_OK(hipMalloc((void **)&d, (size_t)n * sizeof(int)));
-  int rc = -1;
-  if (hipMemcpy(d, streams, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess && reset_streams_on(b, d, n, nullptr) == 0 &&
-      hipDeviceSynchronize() == hipSuccess)
-    rc = 0;
-  hipFree(d);
-  return rc;
-}
-
-extern "C" int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int *d_streams, int n, void *hip_stream) {
-  if (!b || n < 0 || (n > 0 && !d_streams)) return -1;
-  if (n == 0) return 0;
-  ON_DEVICE(b->device);
-  return reset_streams_on(b, d_streams, n, static_cast<hipStream_t>(hip_stream));
+  return batch_process_list_host(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames, .s16 = true,
+                                     .active = active, .list = streams, .n_rows = n_rows});
 }
 
 // ---- training-feature extraction (reference loop src/dump_features.c:466-491) ----
@@ -953,181 +594,32 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
   return 0;
 }
 
+#define D2H(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyDeviceToHost))
+#define H2D(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyHostToDevice))
+
 extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, const float *clean, const float *noisy,
                                             const float *vad, const int *lowpass, const int *band_lp,
                                             const int *noise_free, int n_frames) {
   if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->row_stride || b->channels > 1)
     return -1;
   ON_DEVICE(b->device);
-  const size_t N = b->n, fb = (size_t)n_frames * N * RN_FRAME_SIZE * 4;
-  char *dev = nullptr;
-  const size_t o_clean = 0, o_noisy = fb, o_vad = 2 * fb, o_rec = o_vad + (size_t)n_frames * N * 4,
-               o_lp = o_rec + (size_t)n_frames * N * 98 * 4, o_bl = o_lp + N * 4, o_nf = o_bl + N * 4, total = o_nf + N * 4;
-  HIP_OK(hipMalloc((void **)&dev, total));
-  int rc = -1;
-  if (hipMemcpy(dev + o_clean, clean, fb, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(dev + o_noisy, noisy, fb, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(dev + o_vad, vad, (size_t)n_frames * N * 4, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(dev + o_lp, lowpass, N * 4, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(dev + o_bl, band_lp, N * 4, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(dev + o_nf, noise_free, N * 4, hipMemcpyHostToDevice) == hipSuccess &&
-      rnnoise_batch_train_features_device(b, (float *)(dev + o_rec), (const float *)(dev + o_clean),
-                                          (const float *)(dev + o_noisy), (const float *)(dev + o_vad),
-                                          (const int *)(dev + o_lp), (const int *)(dev + o_bl), (const int *)(dev + o_nf),
-                                          n_frames, nullptr) == 0 &&
-      hipDeviceSynchronize() == hipSuccess &&
-      hipMemcpy(records, dev + o_rec, (size_t)n_frames * N * 98 * 4, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = 0;
-  hipFree(dev);
-  return rc;
-}
-
-#define D2H(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyDeviceToHost))
-#define H2D(dst, src, count) HIP_OK(hipMemcpy(dst, src, (count) * 4, hipMemcpyHostToDevice))
-
-namespace {
-// what every state produced by the reference or by export_state satisfies, and what lets the batch not store analysis_mem (rn_dev.h)
-bool analysis_is_pitch_tail(const float *f) {
-  return !memcmp(f + RN_OFF_ANALYSIS, f + RN_OFF_PITCH_BUF + RN_PITCH_BUF_SIZE - RN_FRAME_SIZE, RN_FRAME_SIZE * sizeof(float));
-}
-// the one-state staging row of export / import (16-byte aligned, as the scatter kernel wants its records)
-int stage_ready(RNNoiseBatch *b) {
-  if (!b->state_stage) HIP_OK(hipMalloc((void **)&b->state_stage, RN_STATE_FLOATS * sizeof(float)));
-  return 0;
-}
-// where the state kernels find the frame phases of streams s, s + 1, ... in per-stream mode (they read them on the device; null in
-// lock-step mode, where the launch carries b->ring_slot: the slots its next frame writes, ring slot p % RN_RING_SLOTS, spectra slot
-// p % RN_SPEC_SLOTS)
-const int *phase_of(const RNNoiseBatch *b, int s) { return b->per_stream ? b->phase_buf + s : nullptr; }
-}  // namespace
-
-// State migration: one gather / scatter kernel (state_kernels.hip) and one copy per call.  Synchronous with everything
-// the batch has in flight (the caller's streams are not known here, so the device is drained first).
-extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
-  if (!b || !f || s < 0 || s >= b->n) return -1;
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());
-  if (stage_ready(b)) return -1;
-  const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_gather(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr));
-  D2H(f, b->state_stage, RN_STATE_FLOATS);  // (a blocking copy on the null stream: ordered after the kernel)
-  return 0;
-}
-
-extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f) {
-  if (!b || !f || s < 0 || s >= b->n) return -1;
-  if (!analysis_is_pitch_tail(f)) {
-    fprintf(stderr, "[rnnoise_amd] import_state: analysis_mem differs from the tail of pitch_buf\n");
+  const size_t N = b->n, fN = (size_t)n_frames * N, fb = fN * RN_FRAME_SIZE * 4;
+  DevScratch d;
+  const size_t o_clean = d.carve(fb), o_noisy = d.carve(fb), o_vad = d.carve(fN * 4), o_rec = d.carve(fN * 98 * 4), o_lp = d.carve(N * 4),
+               o_bl = d.carve(N * 4), o_nf = d.carve(N * 4);
+  if (d.alloc()) return -1;
+  HIP_OK(hipMemcpy(d.at<char>(o_clean), clean, fb, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d.at<char>(o_noisy), noisy, fb, hipMemcpyHostToDevice));
+  H2D(d.at<char>(o_vad), vad, fN);
+  H2D(d.at<char>(o_lp), lowpass, N);
+  H2D(d.at<char>(o_bl), band_lp, N);
+  H2D(d.at<char>(o_nf), noise_free, N);
+  if (rnnoise_batch_train_features_device(b, d.at<float>(o_rec), d.at<float>(o_clean), d.at<float>(o_noisy), d.at<float>(o_vad),
+                                          d.at<int>(o_lp), d.at<int>(o_bl), d.at<int>(o_nf), n_frames, nullptr))
     return -1;
-  }
-  ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
-  if (stage_ready(b)) return -1;
-  H2D(b->state_stage, f, RN_STATE_FLOATS);
-  b->img_valid = false;
-  const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_scatter(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr));
-  HIP_OK(hipStreamSynchronize(nullptr));
+  D2H(records, d.at<char>(o_rec), fN * 98);
   return 0;
-}
-
-// ---- stream snapshots (include/rnnoise_amd.h: rnnoise_batch_save_streams) ----
-// The device forms are two launches at the most, ordered on the caller's stream like rnnoise_batch_reset_streams_device.  Nothing
-// has to be joined here: a pipelined call ends with the synthesis of its last frame on the caller's stream, which waited for that
-// frame's analysis (cur_k1) on the side stream, which waited for its high-pass (cur_hp) on the other one -- both side streams run
-// in frame order, so everything the call queued anywhere is complete before a kernel that follows it on the caller's stream; and the
-// next pipelined call records ev_begin on the caller's stream behind these launches and makes both side streams wait for it.
-static_assert(RNNOISE_AMD_SNAP_FLOATS == RN_SNAP_FLOATS && RN_SNAP_FLOATS % 4 == 0, "one record size for the kernels and the API");
-namespace {
-bool snap_args_ok(const RNNoiseBatch *b, const void *snap, const int *streams, int n) {
-  if (!b || n < 0 || n > b->n || (n > 0 && !snap)) return false;
-  if (n > 0 && !streams && n != b->n) return false;  // (no list: the whole batch, stream i = row i)
-  return true;
-}
-int save_on(RNNoiseBatch *b, float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), st));
-  return 0;
-}
-// the listed rows' tiles of the layer-wise network's state images follow the load while they are live (rn_dev.h: act_q), as after
-// a per-stream reset; without a list that is every tile
-int load_on(RNNoiseBatch *b, const float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), st));
-  if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, d_list ? n : 0));
-  return 0;
-}
-constexpr int SNAP_CHUNK = 1024;  // rows of the host forms' staging buffer (27 MB)
-
-// the host forms: the list is checked, the device drained (the caller's streams are not known here), then chunks of SNAP_CHUNK rows
-// go through one staging allocation with blocking copies
-int snap_host(RNNoiseBatch *b, float *snap, const int *streams, int n, bool load) {
-  if (!snap_args_ok(b, snap, streams, n)) return -1;
-  if (n == 0) return 0;
-  std::vector<int> list((size_t)n);
-  std::vector<uint8_t> seen(load ? (size_t)b->n : 0, 0);
-  for (int i = 0; i < n; i++) {
-    const int s = streams ? streams[i] : i;
-    if (s < 0 || s >= b->n) return -1;
-    if (load) {
-      if (seen[s]) return -1;
-      seen[s] = 1;
-      const float *f = snap + (size_t)i * RN_SNAP_FLOATS;
-      int magic;
-      memcpy(&magic, f + RN_SNAP_OFF_MAGIC, sizeof magic);
-      if (magic != RN_SNAP_MAGIC) return -1;
-      if (!analysis_is_pitch_tail(f)) {
-        fprintf(stderr, "[rnnoise_amd] load_streams: row %d: analysis_mem differs from the tail of pitch_buf\n", i);
-        return -1;
-      }
-    }
-    list[i] = s;
-  }
-  ON_DEVICE(b->device);
-  HIP_OK(hipDeviceSynchronize());
-  const size_t chunk = n < SNAP_CHUNK ? n : SNAP_CHUNK, row_bytes = RN_SNAP_FLOATS * sizeof(float);
-  char *d = nullptr;
-  HIP_OK(hipMalloc((void **)&d, chunk * row_bytes + chunk * sizeof(int)));
-  float *d_snap = reinterpret_cast<float *>(d);
-  int *d_list = reinterpret_cast<int *>(d + chunk * row_bytes);
-  int rc = 0;
-  for (size_t r0 = 0; r0 < (size_t)n && rc == 0; r0 += chunk) {
-    const int rows = (int)std::min(chunk, (size_t)n - r0);
-    float *h = snap + r0 * RN_SNAP_FLOATS;
-    rc = -1;
-    if (hipMemcpy(d_list, list.data() + r0, rows * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (load) {
-      if (hipMemcpy(d_snap, h, rows * row_bytes, hipMemcpyHostToDevice) == hipSuccess && load_on(b, d_snap, d_list, rows, nullptr) == 0 &&
-          hipStreamSynchronize(nullptr) == hipSuccess)
-        rc = 0;
-    } else if (save_on(b, d_snap, d_list, rows, nullptr) == 0 && hipStreamSynchronize(nullptr) == hipSuccess &&
-               hipMemcpy(h, d_snap, rows * row_bytes, hipMemcpyDeviceToHost) == hipSuccess) {
-      rc = 0;
-    }
-  }
-  hipFree(d);
-  return rc;
-}
-}  // namespace
-
-extern "C" int rnnoise_batch_save_streams_device(RNNoiseBatch *b, float *d_snap, const int *d_streams, int n, void *hip_stream) {
-  if (!snap_args_ok(b, d_snap, d_streams, n) || (reinterpret_cast<uintptr_t>(d_snap) & 15)) return -1;
-  if (n == 0) return 0;
-  ON_DEVICE(b->device);
-  return save_on(b, d_snap, d_streams, n, static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" int rnnoise_batch_load_streams_device(RNNoiseBatch *b, const float *d_snap, const int *d_streams, int n, void *hip_stream) {
-  if (!snap_args_ok(b, d_snap, d_streams, n) || (reinterpret_cast<uintptr_t>(d_snap) & 15)) return -1;
-  if (n == 0) return 0;
-  ON_DEVICE(b->device);
-  return load_on(b, d_snap, d_streams, n, static_cast<hipStream_t>(hip_stream));
-}
-
-extern "C" int rnnoise_batch_save_streams(RNNoiseBatch *b, float *snap, const int *streams, int n) {
-  return snap_host(b, snap, streams, n, false);
-}
-
-extern "C" int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap, const int *streams, int n) {
-  return snap_host(b, const_cast<float *>(snap), streams, n, true);
 }
 
 extern "C" int rnnoise_batch_debug_last(RNNoiseBatch *b, float *features, int *silence, int *pitch) {
@@ -1171,21 +663,17 @@ extern "C" int rnnoise_amd_debug_fft(int device, int variant, float *out, const 
   RnTablesDev tb;
   if (tables_for_device(device, tb)) return -1;
   const size_t fb = (size_t)n * 960 * 2 * 4;
-  char *d = nullptr;
-  HIP_OK(hipMalloc((void **)&d, 2 * fb + (size_t)n * 8 + 2 * 6 * 64 * 4));
-  float *d_in = (float *)d, *d_out = (float *)(d + fb);
-  unsigned long long *d_clk = (unsigned long long *)(d + 2 * fb);
-  int *d_x = (int *)(d + 2 * fb + (size_t)n * 8);
-  int rc = -1;
-  if (hipMemcpy(d_in, in, fb, hipMemcpyHostToDevice) == hipSuccess &&
-      rn_launch_fft_probe(variant, d_in, d_out, d_clk, n, reps, &tb, nullptr) == hipSuccess &&
-      rn_launch_xlane_probe(d_x, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
-      hipMemcpy(out, d_out, fb, hipMemcpyDeviceToHost) == hipSuccess &&
-      (!clocks || hipMemcpy(clocks, d_clk, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess) &&
-      (!xlane || hipMemcpy(xlane, d_x, 2 * 6 * 64 * 4, hipMemcpyDeviceToHost) == hipSuccess))
-    rc = 0;
-  hipFree(d);
-  return rc;
+  DevScratch d;
+  const size_t o_in = d.carve(fb), o_out = d.carve(fb), o_clk = d.carve((size_t)n * 8), o_x = d.carve(2 * 6 * 64 * 4);
+  if (d.alloc()) return -1;
+  HIP_OK(hipMemcpy(d.at<char>(o_in), in, fb, hipMemcpyHostToDevice));
+  HIP_OK(rn_launch_fft_probe(variant, d.at<float>(o_in), d.at<float>(o_out), d.at<unsigned long long>(o_clk), n, reps, &tb, nullptr));
+  HIP_OK(rn_launch_xlane_probe(d.at<int>(o_x), nullptr));
+  HIP_OK(hipStreamSynchronize(nullptr));
+  HIP_OK(hipMemcpy(out, d.at<char>(o_out), fb, hipMemcpyDeviceToHost));
+  if (clocks) HIP_OK(hipMemcpy(clocks, d.at<char>(o_clk), (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (xlane) D2H(xlane, d.at<char>(o_x), 2 * 6 * 64);
+  return 0;
 }
 
 // out[i] = (float)log10(1e-2 + (double)ex[i]) evaluated on the device by the feature stage's function (host buffers; tests only).
@@ -1196,15 +684,14 @@ extern "C" int rnnoise_amd_debug_log_energy_range(int device, float *out, const 
   ON_DEVICE(device);
   RnTablesDev tb;
   if (tables_for_device(device, tb)) return -1;
-  float *d = nullptr;
-  HIP_OK(hipMalloc((void **)&d, (size_t)n * (ex ? 8 : 4)));
-  int rc = -1;
-  if ((!ex || hipMemcpy(d + n, ex, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-      rn_launch_log_energy(ex ? d + n : nullptr, first_bits, d, n, model == 1 ? nullptr : tb.log_tab, nullptr) == hipSuccess &&
-      hipStreamSynchronize(nullptr) == hipSuccess && hipMemcpy(out, d, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = 0;
-  hipFree(d);
-  return rc;
+  DevScratch d;
+  const size_t o_out = d.carve((size_t)n * 4), o_ex = d.carve(ex ? (size_t)n * 4 : 0);
+  if (d.alloc()) return -1;
+  if (ex) H2D(d.at<char>(o_ex), ex, (size_t)n);
+  HIP_OK(rn_launch_log_energy(ex ? d.at<float>(o_ex) : nullptr, first_bits, d.at<float>(o_out), n, model == 1 ? nullptr : tb.log_tab, nullptr));
+  HIP_OK(hipStreamSynchronize(nullptr));
+  D2H(out, d.at<char>(o_out), (size_t)n);
+  return 0;
 }
 extern "C" int rnnoise_amd_debug_log_energy(int device, float *out, const float *ex, int n) {
   if (!ex || n <= 0) return -1;

@@ -382,7 +382,8 @@ static int batch_process_pinned(RNNoiseBatch *b, char *out, const char *in, floa
   // (schedule 1: only the high-pass runs ahead on a side stream), which costs the 2-3 % the analysis overlap is worth.
   const int keep = b->schedule;
   if (b->schedule == 0) b->schedule = 1;
-  const int rc = batch_process_device_impl(b, r_out, r_in, r_vad, r_g, n_frames, io.run, s16, &hk);
+  const int rc = batch_process_device_impl(
+      b, {.out = r_out, .in = r_in, .vad = r_vad, .gains = r_g, .n_frames = n_frames, .stream = io.run, .s16 = s16, .hooks = &hk});
   b->schedule = keep;
   if (sd && !rc && n_frames > 0) {
     // every copy of the call is complete once the last frame's download count has landed (the engines work in order)
@@ -480,7 +481,9 @@ static int batch_process_host_impl(RNNoiseBatch *b, void *out_v, const void *in_
       if (c + 1 < n_chunks && upload(c + 1)) return -1;
       HIP_OK(hipStreamWaitEvent(io.run, io.up_done[k], 0));
       if (c >= 2) HIP_OK(hipStreamWaitEvent(io.run, io.down_done[k], 0));  // d_out[k] of chunk c-2 has left
-      if (batch_process_device_impl(b, io.d_out[k], io.d_in[k], io.d_vad[k], io.d_gains[k], f, io.run, s16)) return -1;
+      if (batch_process_device_impl(b, {.out = io.d_out[k], .in = io.d_in[k], .vad = io.d_vad[k], .gains = io.d_gains[k], .n_frames = f,
+                                        .stream = io.run, .s16 = s16}))
+        return -1;
       HIP_OK(hipEventRecord(io.run_done[k], io.run));
       if (!direct && c >= 2 && collect(c - 2)) return -1;  // frees h_out[k] for the download queued below
       HIP_OK(hipStreamWaitEvent(io.down, io.run_done[k], 0));
@@ -509,17 +512,17 @@ static int batch_process_host_impl(RNNoiseBatch *b, void *out_v, const void *in_
   return 0;
 }
 
-// (at a PCM rate other than 48 kHz, with a caller-defined PCM layout and with interleaved channels the host forms take the staged
-//  convenience path of the masked calls: batch.cpp)
+// (the calls that batch_host_call_staged names take the staged convenience path of the masked calls: batch.cpp)
 extern "C" int rnnoise_batch_process(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains,
                                      int n_frames) {
-  if (b && (b->g.rs_L || b->row_stride || b->channels > 1)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, false);  // (or a PCM layout, or channels)
+  if (b && batch_host_call_staged(b, false))
+    return batch_process_staged(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames});
   return batch_process_host_impl(b, out, in, vad, gains, n_frames, false);
 }
 
 extern "C" int rnnoise_batch_process_s16(RNNoiseBatch *b, short *out, const short *in, float *vad, float *gains,
                                          int n_frames) {
-  if (b && (b->g.rs_L || b->g.pcm_fmt || b->row_stride || b->channels > 1)) return batch_process_staged(b, out, in, vad, gains, nullptr, n_frames, true);  // (or a format table, a PCM layout, channels)
+  if (b && batch_host_call_staged(b, true))
+    return batch_process_staged(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames, .s16 = true});
   return batch_process_host_impl(b, out, in, vad, gains, n_frames, true);
 }
-

@@ -4,7 +4,10 @@
 //
 //   model.cpp    "DNNw" blob reader, "RNPK" pack, GPU re-layout of the model, rnnoise_model_* entry points
 //   tables.cpp   static tables by formula, the rcpps profile
-//   batch.cpp    rnnoise_batch_*: N streams on one GPU, the frame pipeline over HIP streams, state export / import, timing
+//   batch.cpp         rnnoise_batch_*: N streams on one GPU, the frame step as a pipeline over HIP streams and its host-buffer forms,
+//                     training features, timing, debug taps
+//   batch_tables.cpp  a batch's configuration: PCM rate, strides, channels, the per-stream tables (rates, formats, models, controls)
+//   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
 //   host_io.cpp  host-fed calls: the pinned frame ring, the bounce chunks of pageable callers
 //   dropin.cpp   the reference's own API (include/rnnoise.h): state pools, the combiner of concurrent one-frame calls
 #pragma once
@@ -103,6 +106,20 @@ struct DeviceGuard {
     }                                                                                                  \
   } while (0)
 
+inline size_t rn_align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+// The staging buffer of a host-buffer convenience call: its pieces are carved first (offsets), then allocated as one, and freed when
+// the call's scope ends -- whichever way it ends.
+struct DevScratch {
+  uint8_t *dev = nullptr;
+  size_t bytes = 0;
+  DevScratch() = default;
+  DevScratch(const DevScratch &) = delete;
+  ~DevScratch() { if (dev) hipFree(dev); }
+  size_t carve(size_t n) { const size_t off = bytes; bytes += rn_align256(n); return off; }
+  int alloc() { HIP_OK(hipMalloc((void **)&dev, bytes)); return 0; }
+  template <typename T> T *at(size_t off) const { return reinterpret_cast<T *>(dev + off); }
+};
+
 // Host view of one layer (pointers alias the blob, like the reference's LinearLayer)
 struct HostLinear {
   const float *bias = nullptr, *subias = nullptr, *fw = nullptr, *diag = nullptr, *scale = nullptr;
@@ -178,16 +195,17 @@ struct RNNoiseBatch {
   bool per_stream = false;
   int *phase_buf = nullptr;  // [N] in the arena
   // PCM rate of the calls (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate).  rs_buf: the resampler histories (rn_dev.h:
-  // RnGroupDev::rs_hist), allocated the first time the rate leaves 48 kHz; g.rs_hist / g.rs_L are set only while it is away
+  // RnGroupDev::rs_hist); g.rs_hist / g.rs_L are set only while the rate is away from 48 kHz or a rate table is set.  This buffer and
+  // the four tables below are allocated on first use (batch_tables.cpp: table_alloc) and live until the batch ends
   int pcm_rate = 48000;
   float *rs_buf = nullptr;
   // per-stream rates (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates): rate_map, the [N] divisor bytes K0 / K3 and the snapshot
-  // kernels read (rn_dev.h: RnGroupDev::rs_Ls) -- allocated by the first table; g.rs_Ls points at it while a table is set, and g.rs_L /
-  // g.rs_hist are then set at 48 kHz too (batch.cpp: rs_point)
+  // kernels read (rn_dev.h: RnGroupDev::rs_Ls); g.rs_Ls points at it while a table is set, and g.rs_L / g.rs_hist are then set at
+  // 48 kHz too (batch_tables.cpp: rs_point)
   uint8_t *rate_map = nullptr;
   // per-stream PCM formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats): fmt_map, the [N] format bytes K0 / K3 read in
-  // the int16 calls (rn_dev.h: RnGroupDev::pcm_fmt) -- allocated by the first table, like model_map; g.pcm_fmt points at it while a
-  // table is set.  Configuration, not state: no reset, import, load or rate change touches it
+  // the int16 calls (rn_dev.h: RnGroupDev::pcm_fmt); g.pcm_fmt points at it while a table is set.  Configuration, not state: no reset,
+  // import, load or rate change touches it
   uint8_t *fmt_map = nullptr;
   // caller-defined PCM strides (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), in samples; both 0: the default layout.  The
   // process calls hand row_stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and step their frame pointers by frame_stride; b->g
@@ -198,14 +216,14 @@ struct RNNoiseBatch {
   // never carries it.  Configuration, not state
   int channels = 1;
   // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
-  // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of) -- allocated by the first
-  // add_model, like rs_buf by the first rate change; g.model_of / g.n_models are set from then on
+  // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of), there from the first add_model on;
+  // g.model_of / g.n_models are set from then on
   int n_models = 1;
   RNNModel *models[RNNOISE_AMD_MAX_MODELS] = {};
   RnModelDev slot_m[RNNOISE_AMD_MAX_MODELS] = {};
   uint8_t *model_map = nullptr;
   // per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): [N][RN_CTL_FLOATS] table, then the [N]
-  // counters -- allocated by the first set, like model_map by the first add_model; g.ctl / g.gate_c point into it while a table is set
+  // counters; g.ctl / g.gate_c point into it while a table is set
   float *ctl_buf = nullptr;
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
@@ -335,11 +353,31 @@ RNNModel *default_model();                                           // model.cp
 void pools_free(RNNModel *model);                                    // dropin.cpp: the state pools of a model (rnnoise_model_free)
 RnGroupDev group_view(const RnGroupDev &g, int first, int count);    // batch.cpp
 const RnKnobs &rn_knobs();                                           // batch.cpp: the dispatch switches, read once per process
-int batch_process_device_impl(RNNoiseBatch *b, void *d_out, const void *d_in, float *d_vad, float *d_gains, int n_frames,
-                              void *hip_stream, bool s16, const FrameIoHooks *hk = nullptr,
-                              const uint8_t *d_active = nullptr, const int *d_list = nullptr, int n_rows = 0,
-                              bool packed = false);  // batch.cpp (packed: the buffers are in the default layout whatever the batch's)
 void host_io_release(RNNoiseBatch *b);                               // host_io.cpp
-int batch_process_staged(RNNoiseBatch *b, void *out, const void *in, float *vad, float *gains, const unsigned char *active,
-                         int n_frames, bool s16, const int *list = nullptr,
-                         int n_rows = 0);                            // batch.cpp: host buffers through one device allocation
+// One process call of a batch: what the entry points of include/rnnoise_amd.h hand to the step (batch_process_device_impl: device
+// memory, asynchronous on `stream`) or to its host-buffer form (batch_process_staged: host memory through one device allocation,
+// synchronous; stream, hooks and packed are not read).
+struct ProcessCall {
+  void *out = nullptr;  // PCM frames: float, or int16 with s16 set
+  const void *in = nullptr;
+  float *vad = nullptr, *gains = nullptr;  // optional
+  int n_frames = 0;
+  void *stream = nullptr;  // a hipStream_t, as the API hands it over
+  bool s16 = false;
+  const uint8_t *active = nullptr;  // the presence mask of a masked call ([n_frames][rows] bytes, include/rnnoise_amd.h), or null
+  // the streams of a stream-list call (n_rows int32, include/rnnoise_amd.h), or null; the buffers and `active` then have n_rows rows
+  // per frame (rn_dev.h: RnGroupDev::list)
+  const int *list = nullptr;
+  int n_rows = 0;
+  const FrameIoHooks *hooks = nullptr;  // the pinned ring of the host-fed path (host_io.cpp)
+  bool packed = false;  // the buffers are the library's own, in the default layout whatever the batch's (batch_process_staged)
+};
+int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
+int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
+// samples per row and frame at the batch's PCM rate
+inline int batch_frame_samples(const RNNoiseBatch *b) { return RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1); }
+// whether a host call takes the staged path instead of the pinned ring / bounce chunks of host_io.cpp: at a PCM rate other than 48 kHz
+// or with a rate table, with a PCM layout, with interleaved channels, and the int16 calls of a batch with a format table
+inline bool batch_host_call_staged(const RNNoiseBatch *b, bool s16) {
+  return b->g.rs_L || b->row_stride || b->channels > 1 || (s16 && b->g.pcm_fmt);
+}

@@ -189,8 +189,14 @@ def test_plan_with_channels_under_a_moved_switch(prog):
 
 
 def test_channel_count_sits_beside_the_row_pitch():
-    """RnGroupDev::pcm_chan follows pcm_pitch, and the process calls are the only writers of either (b->g never carries them)"""
-    src = open(os.path.join(ROOT, "rnnoise_amd", "csrc", "rn_dev.h")).read()
+    """RnGroupDev::pcm_chan follows pcm_pitch, and the step is the only writer of either, in one place (b->g never carries them)"""
+    csrc = os.path.join(ROOT, "rnnoise_amd", "csrc")
+    src = open(os.path.join(csrc, "rn_dev.h")).read()
     assert re.search(r"int pcm_pitch;\n(\s*//[^\n]*\n)+\s*int pcm_chan;", src)
-    batch = open(os.path.join(ROOT, "rnnoise_amd", "csrc", "batch.cpp")).read()
-    assert len(re.findall(r"\bg[h]?\.pcm_chan = pcm_chan;", batch)) == 2 and "b->g.pcm_chan" not in batch
+    host = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".cpp")}
+    writers = [f for f, text in host.items() for _ in re.findall(r"[.>]pcm_chan\s*=[^=]", text)]
+    assert len(writers) == 1, writers
+    step = host[writers[0]]  # the one writer is the step itself, handing on the call's count
+    assert re.search(r"^int batch_process_device_impl\(", step, re.M) and "g.pcm_chan = pcm_chan;" in step
+    for f, text in host.items():
+        assert "b->g.pcm_chan" not in text, f
