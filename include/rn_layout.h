@@ -59,10 +59,10 @@
  * RN_SNAP_FLOATS is a multiple of 4, so the rows of a snapshot array are 16-byte aligned.  State only: no model slot, no
  * controls record, no rate, no frame phase. */
 #define RN_SNAP_OFF_MAGIC RN_STATE_FLOATS                   /* RN_SNAP_MAGIC; 0: an empty record   */
-#define RN_SNAP_OFF_L (RN_SNAP_OFF_MAGIC + 1)               /* PCM-rate divisor of the history: 1, 2, 3 or 6 (48000 / rate) */
+#define RN_SNAP_OFF_L (RN_SNAP_OFF_MAGIC + 1)               /* PCM-rate code of the history: 1, 2, 3 or 6 (48000 / rate), 32 at 32 kHz */
 #define RN_SNAP_OFF_GATE (RN_SNAP_OFF_MAGIC + 2)            /* gate counter, 0..65536 (65536: no voice frame yet, or no control table) */
 #define RN_SNAP_OFF_RESERVED (RN_SNAP_OFF_MAGIC + 3)        /* 3 words: written as 0, ignored on load */
-#define RN_SNAP_OFF_HIST (RN_SNAP_OFF_MAGIC + 6)            /* 6288: resampler history, zeros at 48 kHz */
+#define RN_SNAP_OFF_HIST (RN_SNAP_OFF_MAGIC + 6)            /* 6288: resampler history, zeros at 48 kHz; at 32 kHz 47 floats at [0, 47), 70 at [48, 118) */
 #define RN_SNAP_HIST_FLOATS 336
 #define RN_SNAP_FLOATS (RN_SNAP_OFF_HIST + RN_SNAP_HIST_FLOATS)  /* 6624 words = 26,496 B */
 #define RN_SNAP_MAGIC 0x534E5201                            /* "\1RNS": record version 1 */

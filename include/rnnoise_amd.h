@@ -140,40 +140,48 @@ RNNOISE_EXPORT int rnnoise_batch_process_list_s16(RNNoiseBatch *b, short *out, c
 RNNOISE_EXPORT int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n);
 RNNOISE_EXPORT int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int *d_streams, int n, void *hip_stream);
 
-/* PCM rate of the batch's calls: 48000 (default), 24000, 16000 or 8000.  Returns the previous rate, or -1 for any other
+/* PCM rate of the batch's calls: 48000 (default), 32000, 24000, 16000 or 8000.  Returns the previous rate, or -1 for any other
  * value (nothing changes then).  Synchronous.  Changing the rate zeroes every stream's resampler history; the
  * DenoiseState of every stream is untouched.
- * At rate R, L = 48000 / R (2, 3 or 6), the in / out buffers of every rnnoise_batch_process* call are
- * [n_frames][n_streams][480 / L] (240, 160 or 80 samples), float or int16 as before; vad and gains stay per 10 ms frame.  Each
+ * At rate R the in / out buffers of every rnnoise_batch_process* call are [n_frames][n_streams][M], M = 480 R / 48000 samples per
+ * 10 ms frame (320, 240, 160 or 80), float or int16 as before; vad and gains stay per 10 ms frame.  Each
  * stream is upsampled to 48 kHz, run through rnnoise_process_frame() frame by frame, and downsampled back to R (int16: the input
- * converted exactly, the downsampled float output with the truncating cast of the 48 kHz calls).  The filters are one
- * Kaiser-windowed sinc per L of 48 L taps (rnnoise_amd/resample.py defines them and their arithmetic bit for bit); up followed
- * by down is a pure delay of RNNOISE_AMD_RESAMPLE_DELAY = 47 low-rate samples.  Device-buffer calls stay asynchronous and
+ * converted exactly, the downsampled float output with the truncating cast of the 48 kHz calls).  For the divisors L = 48000 / R
+ * (2, 3 or 6) the filters are one Kaiser-windowed sinc per L of 48 L taps (rnnoise_amd/resample.py defines them and their arithmetic
+ * bit for bit); up followed by down is a pure delay of RNNOISE_AMD_RESAMPLE_DELAY = 47 low-rate samples.  32 kHz divides nothing: it
+ * is 2:3 through a common 96 kHz grid, over the filter of L = 3 read at that grid (again 48 taps per 48 kHz sample on the way up, 72
+ * per 32 kHz sample on the way down; frames map to frames, no phase is carried between them).  Up followed by down is a delay of the
+ * same 47 samples at 32 kHz, but not an exact one: the 2:1 step in the middle aliases at the filter's stop-band level (70 dB down).
+ * Device-buffer calls stay asynchronous and
  * pipelined; host-buffer calls at R != 48000 are synchronous and staged through device memory (the convenience path of the masked
  * host calls).  An absent frame of a masked call leaves the stream's resampler history untouched; rnnoise_batch_reset,
  * rnnoise_batch_reset_streams[_device] and rnnoise_batch_import_state zero it.  rnnoise_batch_train_features* returns -1 at
  * R != 48000.  The per-frame API of rnnoise.h stays 48 kHz only. */
 #define RNNOISE_AMD_RESAMPLE_DELAY 47
+#define RNNOISE_AMD_RATE_32K 32 /* the code of a 32 kHz stream where the other rates have their divisor: rate tables, snapshot records */
 RNNOISE_EXPORT int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz);
 RNNOISE_EXPORT int rnnoise_batch_pcm_rate(const RNNoiseBatch *b);
 
-/* Mixed-rate batches: a PCM rate per stream.  rates[n_streams] is the divisor L_s = 48000 / rate of every stream: 1, 2, 3 or 6
- * (48, 24, 16, 8 kHz).  The batch's own rate (rnnoise_batch_set_pcm_rate, divisor Lb) keeps defining the ROW PITCH of every PCM buffer:
- * in / out rows stay 480 / Lb samples apart in every call form (lock-step, masked, list; float and int16; host and device).  A stream
- * runs at the batch's rate or below it, L_s >= Lb, so that its frame fits its row: a batch at 48 kHz takes all four rates, one at
- * 16 kHz takes 16 and 8 kHz.  Stream s uses the FIRST 480 / L_s samples of its row; the rest of its `in` row is not read and the rest
+/* Mixed-rate batches: a PCM rate per stream.  rates[n_streams] is the rate CODE L_s of every stream: the divisor 48000 / rate -- 1, 2,
+ * 3 or 6 (48, 24, 16, 8 kHz) -- or RNNOISE_AMD_RATE_32K for 32 kHz, which divides nothing.  M_s is the stream's samples per frame: 480
+ * / L_s, 320 at 32 kHz.  The batch's own rate (rnnoise_batch_set_pcm_rate, code Lb, frame M_b) keeps defining the ROW PITCH of every
+ * PCM buffer: in / out rows stay M_b samples apart in every call form (lock-step, masked, list; float and int16; host and device).  A
+ * stream runs at the batch's rate or below it, M_s <= M_b, so that its frame fits its row: a batch at 48 kHz takes all five rates, one
+ * at 32 kHz takes 32, 24, 16 and 8 kHz, one at 16 kHz takes 16 and 8 kHz.  Stream s uses the FIRST M_s samples of its row; the rest of
+ * its `in` row is not read and the rest
  * of its `out` row is not written (the caller's bytes stay).  vad and gains stay per 10 ms frame.  Every stream gives, bit for bit in
  * out, vad, gains and exported state, what it gives in a uniform batch at its own rate -- for L_s = 1 the plain 48 kHz path: no
  * filter, no added delay -- whatever the rates of its neighbours.  Without a table a batch launches exactly what it launched before
  * these calls existed.
  * rnnoise_batch_set_stream_rates (host array): synchronous, like rnnoise_batch_set_stream_models; -1 and no change if any entry is
- * not one of 1, 2, 3, 6 or is below Lb.  The resampler history of every stream whose divisor CHANGES is zeroed; a stream whose divisor
+ * no code or has M_s > M_b (code 32 in a batch at 24 kHz or below, a divisor below Lb).  The resampler history of every stream whose divisor CHANGES is zeroed; a stream whose divisor
  * stays keeps its history and continues bit for bit.  No stream's DenoiseState, gate counter, model slot, controls or frame phase is
  * touched.  rates == NULL drops the table: every stream is at the batch's rate again (history zeroed for the streams that were not)
  * and the batch is back to the launches of one that never had a table.
  * rnnoise_batch_set_stream_rates_device (n_streams bytes in the batch's device memory): a copy ordered on hip_stream (no kernel, no
  * host synchronisation; the first table of a batch allocates its memory).  Entries are not checked: the kernel that reads one maps
- * anything that is not 1, 2, 3 or 6, or that is below Lb, to Lb.  It does NOT touch histories: a stream whose divisor it changes must
+ * anything that is no code, or that has M_s > M_b, to Lb (so byte 32 reads as 32 kHz in a batch at 48 or 32 kHz, and as the batch's
+ * rate in one at 24 kHz or below).  It does NOT touch histories: a stream whose divisor it changes must
  * be reset (rnnoise_batch_reset_streams_device) or loaded from a snapshot on the same stream before its next frame -- which is what
  * recycling a slot for a new call does anyway; otherwise that stream's first frames start from the old rate's history (finite
  * samples, confined to that stream, gone after 47 of its input samples and 47 L_s of its 48 kHz output samples).

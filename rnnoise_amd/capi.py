@@ -65,7 +65,21 @@ EXPORTS = [
 ]
 MAX_CHANNELS = 8  # RNNOISE_AMD_MAX_CHANNELS: interleaved channels of a batch's PCM rows
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
-PCM_RATES = (48000, 24000, 16000, 8000)
+PCM_RATES = (48000, 24000, 16000, 8000)  # the rates that divide 48 kHz: code = divisor
+PCM_RATES_ALL = (48000, 32000, 24000, 16000, 8000)  # every rate a batch takes
+RATE_32K = 32  # RNNOISE_AMD_RATE_32K: the code of 32 kHz in rate tables and snapshot records
+
+
+def rate_code(hz):
+    """the rate code of include/rnnoise_amd.h for rates in Hz out of PCM_RATES_ALL (scalar or array): 48000 / hz, RATE_32K at 32 kHz"""
+    hz = np.asarray(hz, np.int64)
+    return np.where(hz == 32000, RATE_32K, 48000 // np.maximum(hz, 1))
+
+
+def code_rate(code):
+    """... and back: Hz of rate codes"""
+    code = np.asarray(code, np.int64)
+    return np.where(code == RATE_32K, 32000, 48000 // np.maximum(code, 1))
 CTL_FLOATS = 3  # RNNOISE_AMD_CTL_FLOATS: {floor, thr, hold} per stream (rnnoise_batch_set_stream_controls)
 CTL_HOLD_MAX = 65535
 
@@ -341,11 +355,11 @@ class Batch:
         return r
 
     def set_pcm_rate(self, hz: int) -> int:
-        """PCM rate of the batch's calls (rnnoise_batch_set_pcm_rate): 48000, 24000, 16000 or 8000; returns the previous one.
+        """PCM rate of the batch's calls (rnnoise_batch_set_pcm_rate): one of PCM_RATES_ALL; returns the previous one.
         At rate R the PCM arrays of every call are (T, N, 480 * R // 48000)."""
         r = self._L.rnnoise_batch_set_pcm_rate(self.h, int(hz))
         if r < 0:
-            raise ValueError(f"PCM rate {hz} unsupported (one of {PCM_RATES})")
+            raise ValueError(f"PCM rate {hz} unsupported (one of {PCM_RATES_ALL})")
         return r
 
     @property
@@ -450,23 +464,23 @@ class Batch:
             raise exc(f"{fn} failed{why}")
 
     def set_stream_rates(self, hz):
-        """the PCM rate of every stream in Hz (rnnoise_batch_set_stream_rates): (N,) values out of PCM_RATES, none above the batch's
+        """the PCM rate of every stream in Hz (rnnoise_batch_set_stream_rates): (N,) values out of PCM_RATES_ALL, none above the batch's
         own rate, or None to drop the table.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose
         rate changes restart their resampling filters from zero; every stream keeps its DenoiseState."""
         if hz is None:
             return self._call("rnnoise_batch_set_stream_rates", None)
         hz = np.asarray(hz).reshape(-1)
         assert hz.size == self.n
-        if not np.isin(hz, PCM_RATES).all():
-            raise ValueError(f"stream rate unsupported (each one of {PCM_RATES})")
+        if not np.isin(hz, PCM_RATES_ALL).all():
+            raise ValueError(f"stream rate unsupported (each one of {PCM_RATES_ALL})")
         if hz.max(initial=0) > self.pcm_rate:
             raise ValueError(f"a stream rate above the batch's PCM rate {self.pcm_rate}: its frame would not fit its row")
-        L = np.ascontiguousarray(48000 // hz.astype(np.int64), np.uint8)
+        L = np.ascontiguousarray(rate_code(hz), np.uint8)
         self._call("rnnoise_batch_set_stream_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
 
     def set_stream_rates_device(self, d_rates: int, stream: int = 0):
-        """the same from N bytes of device memory holding the DIVISORS 48000 / rate (1, 2, 3, 6), a copy ordered on `stream`; any other
-        byte, or a divisor below the batch's, reads as the batch's rate.  Histories are not touched: reset or load the streams whose
+        """the same from N bytes of device memory holding the rate CODES (rate_code: the divisors 1, 2, 3, 6, and RATE_32K), a copy ordered on
+        `stream`; any other byte, or a rate above the batch's, reads as the batch's rate.  Histories are not touched: reset or load the streams whose
         rate changed (reset_streams_device / load_streams_device) on the same stream before their next frame."""
         self._call("rnnoise_batch_set_stream_rates_device", d_rates or None, stream or None)
 
@@ -474,7 +488,7 @@ class Batch:
         """the PCM rate of every stream in Hz, (N,) int32 (synchronous; the batch's rate everywhere without a table)"""
         L = np.empty(self.n, np.uint8)
         self._call("rnnoise_batch_stream_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        return (48000 // L.astype(np.int32)).astype(np.int32)
+        return code_rate(L).astype(np.int32)
 
     def set_stream_formats(self, formats):
         """the PCM format of every stream's rows in the int16 calls (rnnoise_batch_set_stream_formats): (N,) names out of "s16",

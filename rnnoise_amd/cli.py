@@ -51,7 +51,7 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
                   vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None,
                   formats=None):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
-    at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 24000, 16000 or
+    at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 32000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
     controls of every file (capi.controls_table); all unset, the batch has no control table.  rates: one sample rate per file, none
     above `rate` (a mixed-rate batch: capi.Batch.set_stream_rates); a file's frames fill the front of its rows.  formats: one of
@@ -169,7 +169,7 @@ def main(argv=None):
     p.add_argument("--chunk-frames", type=int, default=100)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--vad-csv", action="store_true")
-    p.add_argument("--rate", type=int, default=48000, choices=capi.PCM_RATES, help="sample rate of the RAW files")
+    p.add_argument("--rate", type=int, default=48000, choices=capi.PCM_RATES_ALL, help="sample rate of the RAW files")
     p.add_argument("--rates", type=lambda v: [int(x) for x in v.split(",")], default=None,
                    help="comma list, one sample rate per input file, each at most --rate: a mixed-rate batch")
     p.add_argument("--formats", type=lambda v: v.split(","), default=None,

@@ -49,14 +49,16 @@ int table_get(RNNoiseBatch *b, const void *live, size_t row_bytes, void *rows, i
   return 0;
 }
 
-// PCM rate: K0 upsamples the caller's rows from 48000 / L, K3 downsamples its output back (rn_dev.h: RnGroupDev::rs_L).  48 kHz
+// PCM rate: K0 upsamples the caller's rows from the rate of code L, K3 downsamples its output back (rn_dev.h: RnGroupDev::rs_L).  48 kHz
 // without a rate table leaves g.rs_hist / g.rs_L null: every launch is then the one of a batch that never saw these calls.
+// the code of a rate the batch API takes (rn_dev.h: rn_rate_samples), 0 for any other
+int rate_code(int hz) { return hz == 32000 ? RN_RATE_32K : (hz == 48000 || hz == 24000 || hz == 16000 || hz == 8000) ? 48000 / hz : 0; }
 // the group's resampler fields from the batch's rate and whether it has a rate table (rn_dev.h: RnGroupDev::rs_Ls)
 void rs_point(RNNoiseBatch *b, bool table) {
   const size_t N = b->n;
   const bool on = table || b->pcm_rate != 48000;
-  b->g.rs_L = on ? 48000 / b->pcm_rate : 0;
-  b->g.rs_pitch = on ? RN_FRAME_SIZE / b->g.rs_L : 0;
+  b->g.rs_L = on ? rate_code(b->pcm_rate) : 0;
+  b->g.rs_pitch = on ? rn_rate_samples(b->g.rs_L) : 0;
   b->g.rs_hist = on ? b->rs_buf : nullptr;
   b->g.rs_up = on ? b->rs_buf + N * RN_RS_HIST : nullptr;
   b->g.rs_dn = on ? b->rs_buf + N * (RN_RS_HIST + RN_FRAME_SIZE) : nullptr;
@@ -70,16 +72,19 @@ int rs_alloc(RNNoiseBatch *b, hipStream_t st) {
   HIP_OK(hipMemsetAsync(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float), st));
   return 0;
 }
-bool rate_divisor_ok(int v, int Lb) { return (v == 1 || v == 2 || v == 3 || v == 6) && v >= Lb; }
-// a table as the kernels read it: an entry that names no rate of this batch is the batch's own divisor
+// whether a byte of a rate table names a rate of a batch at code Lb: a code whose frame fits the batch's row, M_s <= M_b
+bool rate_code_ok(int v, int Lb) {
+  return (v == 1 || v == 2 || v == 3 || v == 6 || v == RN_RATE_32K) && rn_rate_samples(v) <= rn_rate_samples(Lb);
+}
+// a table as the kernels read it: an entry that names no rate of this batch is the batch's own code
 void rates_as_read(unsigned char *rates, int n, int Lb) {
   for (int s = 0; s < n; s++)
-    if (!rate_divisor_ok(rates[s], Lb)) rates[s] = (unsigned char)Lb;
+    if (!rate_code_ok(rates[s], Lb)) rates[s] = (unsigned char)Lb;
 }
 }  // namespace
 
 extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
-  if (!b || (hz != 48000 && hz != 24000 && hz != 16000 && hz != 8000)) return -1;
+  if (!b || !rate_code(hz)) return -1;
   const int old = b->pcm_rate;
   b->frame_stride = b->row_stride = 0;  // (a PCM layout is in samples of the old rate's frame: dropped by every call)
   if (hz == old && !b->g.rs_Ls) return old;  // (a rate table is dropped by every call: the rows are redefined)
@@ -96,7 +101,7 @@ extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
 extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm_rate : -1; }
 
 // ---- per-stream rates (include/rnnoise_amd.h) ----
-// The [N] divisor bytes live in rate_map; while a table is set (g.rs_Ls) the batch runs its resampling launches at 48 kHz too
+// The [N] code bytes (a divisor, or RN_RATE_32K) live in rate_map; while a table is set (g.rs_Ls) the batch runs its resampling launches at 48 kHz too
 // (rs_L = 1), and K0 / K3 and the snapshot kernels take each stream's divisor from it (rn_dev.h: rn_stream_L).
 // This table alone: NULL drops the table (nothing to do without one).  A host set also allocates rs_buf, restarts from zero the
 // history of exactly the streams whose divisor changes, and re-points the resampler fields (rs_point); rnnoise_batch_set_pcm_rate
@@ -105,10 +110,10 @@ extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm
 // reads as the batch's own divisor -- the getter's default too.
 extern "C" int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned char *rates) {
   if (!b) return -1;
-  const int Lb = 48000 / b->pcm_rate;
+  const int Lb = rate_code(b->pcm_rate);
   if (rates)
     for (int s = 0; s < b->n; s++)
-      if (!rate_divisor_ok(rates[s], Lb)) return -1;
+      if (!rate_code_ok(rates[s], Lb)) return -1;
   if (!rates && !b->g.rs_Ls) return 0;
   ON_DEVICE(b->device);
   const size_t N = b->n;
@@ -148,7 +153,7 @@ extern "C" int rnnoise_batch_set_stream_rates_device(RNNoiseBatch *b, const unsi
 
 extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates) {
   if (!b || !rates) return -1;
-  const int Lb = 48000 / b->pcm_rate;
+  const int Lb = rate_code(b->pcm_rate);
   if (table_get(b, b->g.rs_Ls, 1, rates, Lb)) return -1;
   rates_as_read(rates, b->n, Lb);
   return 0;

@@ -1659,6 +1659,7 @@ struct SynthLds {
 // complex spectrum staged in one piece (8,448 B) it was one, and synthesis mostly waited for analysis workgroups to drain
 static_assert(sizeof(SynthLds) <= 5120 && RN_WINDOW_SIZE <= 1052 && RN_BAND_QSTRIDE <= 1052, "synthesis LDS");
 static_assert(RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE + RN_RS_TAPS * 6 <= 1052, "down history, frame and taps fit L.S");
+static_assert(RN_RS_DOWN_HIST_32K <= RN_RS_DOWN_HIST(6) && 2 * RN_RS_DOWN_TAPS_32K <= RN_RS_TAPS * 6, "and so do those of 32 kHz");
 
 // ---------------------------------------------------------------------------------------------
 // K3: rnn_pitch_filter + gain smoothing/interpolation + frame_synthesis
@@ -1955,19 +1956,24 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
 // RnGroupDev::rs_dn as `out` and the caller's buffer as RnGroupDev::rs_out, and after the body the wave stages, in L.S (free once the body is done), the stream's down history
 // v[-47 L .. -1], the frame's 480 samples and the taps, and forms the 480 / L outputs, lane l those of m = l, l + 64, ...  The body is not
 // compiled a second time and L is a run-time value, so that the epilogue stays inside the registers of the body.
+// 32 kHz (L = RN_RATE_32K) is 3:2 over twice the taps of L = 3, y[m] = sum_{k < 72} hd[e][k] v[n0 - k] with e = m & 1 and
+// n0 = (3 m + 2) >> 1 (rs_coeffs.h: rn_rs_hd32): the same loop from another base and another tap row, 72 taps long, over a history
+// of 70 samples.  Not an exact delay like the integer ratios: the 2:1 step in the middle aliases at the stop-band level.
 // Called only for a stream that has this frame (rn_stream_at: RnStreamAt::present).
 // L: the batch's divisor or, with a rate table, the stream's own (rn_dev.h: rn_stream_L; never 1 here); the caller's rows are
 // g.rs_pitch samples apart (g.pcm_pitch in a caller-defined layout) and the stream's 480 / L outputs fill the front of its row.
 // fmt: a companded stream's law (bits 11-12 of parity_arg: rn_fmt_arg), its int16 values going out as the first 480 / L bytes of the row.
 __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, bool out_s16, int s, int row, int L, int fmt) {
   void *out = g.rs_out;
-  const int lane = threadIdx.x, M = RN_FRAME_SIZE / L, D = RN_RS_DOWN_HIST(L), N = RN_RS_TAPS * L;
+  const bool r32 = L == RN_RATE_32K;
+  const int lane = threadIdx.x, M = rn_rate_samples(L), D = r32 ? RN_RS_DOWN_HIST_32K : RN_RS_DOWN_HIST(L);
+  const int N = r32 ? RN_RS_DOWN_TAPS_32K : RN_RS_TAPS * L, NH = r32 ? 2 * RN_RS_DOWN_TAPS_32K : N;  // taps per output; taps staged
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST + RN_RS_DOWN0;
   const float *body = g.rs_dn + (size_t)row * RN_FRAME_SIZE;  // (the body wrote its output row: the caller's row, RnStreamAt::i)
   // (with interleaved channels the outputs go pr.step apart from pr.slot + pr.c on, one element per store: rn_dev.h rn_pcm_row)
   const RnPcmRow pr = rn_pcm_row(g, row, g.rs_pitch);
   const size_t row0 = pr.slot + pr.c;
-  const float *ht = rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
+  const float *ht = r32 ? &rn_rs_hd32[0][0] : rn_rs_h_all + (L == 2 ? 0 : L == 3 ? 96 : 240);
   float *h = vs + RN_RS_DOWN_HIST(6) + RN_FRAME_SIZE;
   __syncthreads();  // (the body's stores to rs_dn, by other lanes)
   // (clamped indices, without a branch: a lane past the end rewrites the last element with its own value)
@@ -1983,12 +1989,14 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
   }
 #pragma unroll
   for (int i = 0; i < (RN_RS_TAPS * 6 + WAVE - 1) / WAVE; i++) {
-    const int k = min(lane + WAVE * i, N - 1);
+    const int k = min(lane + WAVE * i, NH - 1);
     h[k] = ht[k];
   }
   RN_WSYNC();
+  // (m and lane have the same parity: a lane keeps its tap row)
+  h += r32 ? (lane & 1) * RN_RS_DOWN_TAPS_32K : 0;
   for (int m = lane; m < M; m += WAVE) {
-    const float *vm = vs + D + L * m + L - 1;
+    const float *vm = vs + D + (r32 ? (3 * m + 2) >> 1 : L * m + L - 1);
     float a0 = h[0] * vm[0], a1 = h[1] * vm[-1], a2 = h[2] * vm[-2], a3 = h[3] * vm[-3];
 #pragma unroll 2
     for (int k = 4; k < N; k += 4) {
@@ -2006,7 +2014,7 @@ __device__ __forceinline__ void rs_down_stream(const RnGroupDev &g, float *vs, b
       static_cast<float *>(out)[row0 + (size_t)(m * pr.step)] = r;
     }
   }
-  // the new history: the frame's last 47 L samples
+  // the new history: the frame's last D samples
 #pragma unroll
   for (int i = 0; i < (RN_RS_DOWN_HIST(6) + WAVE - 1) / WAVE; i++) {
     const int k = min(lane + WAVE * i, D - 1);

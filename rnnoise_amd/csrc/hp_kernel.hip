@@ -23,10 +23,12 @@
 // has a rate table (rn_dev.h: rn_stream_L) -- one wave serves one stream, so it stays wave-uniform.  The kernel's 48 kHz float body then reads rs_up as its input: the body is not compiled a
 // second time (a second copy of it, even with nothing else changed, took 6 SGPRs more than the kernel's budget), and L is a run-time
 // value with four accumulators per lane, so that the prologue fits inside the registers of the body.
+// 32 kHz (L = RN_RATE_32K) is 2:3 over the taps of L = 3: u[J] = sum_{k<48} hup3[p][k] x[q - k] with q = floor(2 J / 3), p = 2 J mod 3 --
+// the same loop with the index pair formed from 2 n and 3 instead of n and L; frames are 320 samples, the history the same 47.
 // ---------------------------------------------------------------------------------------------
 #define RN_RS_LDS (RN_RS_XS + RN_RS_TAPS * 6)  // LDS floats of the prologue: the staged row, then the taps
 __device__ __forceinline__ const float *rs_up_taps(int L) {
-  return L == 2 ? &rn_rs_up2[0][0] : L == 3 ? &rn_rs_up3[0][0] : &rn_rs_up6[0][0];
+  return L == 2 ? &rn_rs_up2[0][0] : L == 6 ? &rn_rs_up6[0][0] : &rn_rs_up3[0][0];  // (L = 3, and 32 kHz)
 }
 // the wave's LDS hand-offs (one wave per workgroup: no s_barrier needed)
 __device__ __forceinline__ void rs_wsync() {
@@ -42,13 +44,14 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
   //  fill only in part: rn_dev.h RnGroupDev::rs_Ls -- or at row * pcm_pitch in a caller-defined layout; with interleaved channels its
   //  samples are pr.step apart from pr.slot + pr.c on: rn_dev.h rn_pcm_row.  Lane l reads samples l, l + 64, ...: one load of the
   //  wave covers 64 * step consecutive elements, every cache line of the group slot once)
-  const int lane = threadIdx.x & (WAVE - 1), M = RN_FRAME_SIZE / L;
+  // (P: phases of the up filter, the divisor of the index pair below; n * mul its dividend)
+  const int lane = threadIdx.x & (WAVE - 1), M = rn_rate_samples(L), P = L == RN_RATE_32K ? 3 : L, mul = L == RN_RATE_32K ? 2 : 1;
   const RnPcmRow pr = rn_pcm_row(g, row, g.rs_pitch);
   const size_t row0 = pr.slot + pr.c;
   float *hu = xs + RN_RS_XS;
   float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
   // (loads and LDS stores at clamped indices, without a branch: a lane past the end rewrites the last element with its own value)
-  constexpr int NX = RN_FRAME_SIZE / 2 / WAVE + 1, NT = (RN_RS_TAPS * 6 + WAVE - 1) / WAVE;
+  constexpr int NX = (RN_RATE_32K_SAMPLES + WAVE - 1) / WAVE, NT = (RN_RS_TAPS * 6 + WAVE - 1) / WAVE;
   const float rh = hist[min(lane, RN_RS_UP_HIST - 1)];
   float rx[NX], rt[NT];
 #pragma unroll
@@ -60,18 +63,18 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
   }
   const float *ht = rs_up_taps(L);
 #pragma unroll
-  for (int i = 0; i < NT; i++) rt[i] = ht[min(lane + WAVE * i, RN_RS_TAPS * L - 1)];
+  for (int i = 0; i < NT; i++) rt[i] = ht[min(lane + WAVE * i, RN_RS_TAPS * P - 1)];
   rs_wsync();  // (the previous stream's reads of xs are behind us)
   xs[min(lane, RN_RS_UP_HIST - 1)] = rh;
 #pragma unroll
   for (int i = 0; i < NX; i++) xs[RN_RS_UP_HIST + min(lane + WAVE * i, M - 1)] = rx[i];
 #pragma unroll
-  for (int i = 0; i < NT; i++) hu[min(lane + WAVE * i, RN_RS_TAPS * L - 1)] = rt[i];
+  for (int i = 0; i < NT; i++) hu[min(lane + WAVE * i, RN_RS_TAPS * P - 1)] = rt[i];
   rs_wsync();
   float *dst = g.rs_up + (size_t)s * RN_FRAME_SIZE;
-  const unsigned inv = (65536u + L - 1) / L;  // n / L = (n * inv) >> 16, exact for n < 480
+  const unsigned inv = (65536u + P - 1) / P;  // j / P = (j * inv) >> 16, exact for j < 960
   for (int n = lane; n < RN_FRAME_SIZE; n += WAVE) {
-    const int q = (int)(((unsigned)n * inv) >> 16), p = n - q * L;
+    const int j = n * mul, q = (int)(((unsigned)j * inv) >> 16), p = j - q * P;
     const float *xq = xs + RN_RS_UP_HIST + q, *hp = hu + p * RN_RS_TAPS;
     float a0 = hp[0] * xq[0], a1 = hp[1] * xq[-1], a2 = hp[2] * xq[-2], a3 = hp[3] * xq[-3];
 #pragma unroll 2
@@ -83,7 +86,7 @@ __device__ __forceinline__ void rs_up_stream(const RnGroupDev &g, const void *in
     }
     dst[n] = (a0 + a1) + (a2 + a3);
   }
-  // the new up history: the row's last 47 samples (all of the frame's own, 480 / L >= 80)
+  // the new up history: the row's last 47 samples (all of the frame's own, M >= 80)
   if (lane < RN_RS_UP_HIST) hist[lane] = xs[M + lane];
 }
 

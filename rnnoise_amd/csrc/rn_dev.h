@@ -173,20 +173,22 @@ struct RnGroupDev {
   int list_n;
   float *list_vad;             // [list_n] or null
   float *list_gains;           // [list_n][32] or null
-  // PCM rate R = 48000 / rs_L of the batch's calls (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate).  0 / null at 48 kHz: every
+  // PCM rate of the batch's calls as its code rs_L (include/rnnoise_amd.h: rnnoise_batch_set_pcm_rate): the divisor 48000 / R, or
+  // RN_RATE_32K for 32 kHz, which divides nothing (2:3; rn_rate_samples: the frame of a code).  0 / null at 48 kHz: every
   // launch is today's.  Otherwise K0 upsamples the caller's rows and K3 downsamples its output (rs_coeffs.h: the filters), and
   // rs_hist[s] holds stream s's filter histories: [0, RN_RS_UP_HIST) the last low-rate input samples, [RN_RS_DOWN0, RN_RS_DOWN0 +
-  // RN_RS_DOWN_HIST(L)) the last 48 kHz output samples, oldest first.  Zeroed by reset, reset_streams, import and a rate change.
+  // RN_RS_DOWN_HIST(L)) the last 48 kHz output samples (RN_RS_DOWN_HIST_32K at 32 kHz), oldest first.  Zeroed by reset, reset_streams,
+  // import and a rate change.
   float *rs_hist;              // [N][RN_RS_HIST]
   float *rs_up, *rs_dn;        // [N][480] each: the frame at 48 kHz as K0 formed it from the low-rate row / as K3's body formed it
   void *rs_out;                // K3 only: the caller's low-rate output (float or int16)
   int rs_L;
   // Per-stream PCM rates (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates).  Null rs_Ls: every stream runs at the batch's rate
-  // (every launch is today's).  Set, rs_L is the BATCH's divisor Lb (1 at 48 kHz: the batch then has rs_hist / rs_up / rs_dn too) and
-  // stream s runs at divisor rs_Ls[s] -- anything that is not 1, 2, 3 or 6, or that is below Lb, reads as Lb (rn_stream_L).  Indexed by
-  // batch stream, also in a list call.  rs_pitch: samples between the caller's PCM rows, 480 / Lb, set whenever rs_L is; a stream uses
-  // the first 480 / L_s samples of its row.  L_s = 1 (only where Lb = 1, so its row is a whole 48 kHz frame): K0's body reads the row
-  // and K3's body writes it in place, no filter runs and the stream's history is not touched.
+  // (every launch is today's).  Set, rs_L is the BATCH's rate code Lb (1 at 48 kHz: the batch then has rs_hist / rs_up / rs_dn too) and
+  // stream s runs at code rs_Ls[s] -- anything that is no code, or whose frame is longer than the batch's, reads as Lb (rn_stream_L).
+  // Indexed by batch stream, also in a list call.  rs_pitch: samples between the caller's PCM rows, the M of Lb (rn_rate_samples), set
+  // whenever rs_L is; a stream uses the first M_s samples of its row.  L_s = 1 (only where Lb = 1, so its row is a whole 48 kHz frame):
+  // K0's body reads the row and K3's body writes it in place, no filter runs and the stream's history is not touched.
   const uint8_t *rs_Ls;        // [N] or null
   int rs_pitch;
   // Caller-defined PCM layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout).  0: the caller's rows are the form's own constant
@@ -281,7 +283,20 @@ enum RnRecKind { RN_REC_STATE, RN_REC_SNAP };
 #define RN_RS_DOWN_HIST(L) ((RN_RS_TAPS - 1) * (L))  // N - L 48 kHz samples
 #define RN_RS_DOWN0 48
 #define RN_RS_HIST (RN_RS_DOWN0 + RN_RS_DOWN_HIST(6) + 6)  // 336 floats (1,344 B) per stream
-#define RN_RS_XS (RN_RS_UP_HIST + RN_FRAME_SIZE / 2 + 1)    // LDS floats of one staged low-rate row: history + frame, at most 288
+#define RN_RATE_32K 32                          // = RNNOISE_AMD_RATE_32K: the code of 32 kHz where the other rates have their divisor
+#define RN_RATE_32K_SAMPLES 320                 // its frame: the longest below 48 kHz
+#define RN_RS_DOWN_TAPS_32K 72                  // taps per phase of its down filter (rs_coeffs.h: rn_rs_hd32), and what they reach back
+#define RN_RS_DOWN_HIST_32K (RN_RS_DOWN_TAPS_32K - 2)
+#define RN_RS_XS (RN_RS_UP_HIST + RN_RATE_32K_SAMPLES)      // LDS floats of one staged low-rate row: history + frame, at most 367
+// samples per frame at the rate of code L (1, 2, 3, 6 or RN_RATE_32K): the one place that knows 320 is no 480 / L.  Selects, no
+// division: the kernels call it with a run-time L
+static inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+int rn_rate_samples(int L) {
+  return L == RN_RATE_32K ? RN_RATE_32K_SAMPLES : L == 2 ? RN_FRAME_SIZE / 2 : L == 3 ? RN_FRAME_SIZE / 3 : L == 6 ? RN_FRAME_SIZE / 6 : RN_FRAME_SIZE;
+}
 
 // Row list of the one-frame API (dropin.cpp: the combiner behind rnnoise_process_frame).  Concurrent rnnoise_process_frame calls on
 // states of one pool are gathered into ONE launch group: block b of the latency kernels (rn_hp_one_kernel,
@@ -391,12 +406,12 @@ __device__ __forceinline__ int rn_stream_phase(const RnGroupDev &g, int s, int i
   }
   return p;
 }
-// PCM-rate divisor of stream s in a launch with resampling on (g.rs_L != 0; rn_dev.h: RnGroupDev::rs_Ls).  s is the workgroup's one
-// stream: the result is wave-uniform
+// PCM-rate code of stream s in a launch with resampling on (g.rs_L != 0; rn_dev.h: RnGroupDev::rs_Ls): a byte of the table that is a
+// code and whose frame fits the batch's row (g.rs_pitch), else the batch's.  s is the workgroup's one stream: the result is wave-uniform
 __device__ __forceinline__ int rn_stream_L(const RnGroupDev &g, int s) {
   if (!g.rs_Ls) return g.rs_L;
   const int v = __builtin_amdgcn_readfirstlane((int)*(__attribute__((address_space(1))) const uint8_t *)(g.rs_Ls + s));
-  return ((v == 1 || v == 2 || v == 3 || v == 6) && v >= g.rs_L) ? v : g.rs_L;
+  return ((v == 1 || v == 2 || v == 3 || v == 6 || v == RN_RATE_32K) && rn_rate_samples(v) <= g.rs_pitch) ? v : g.rs_L;
 }
 // Samples between the caller's PCM rows (rn_dev.h: RnGroupDev::pcm_pitch): the layout's, or `own` -- the form's constant -- without one
 __device__ __forceinline__ size_t rn_pcm_pitch(const RnGroupDev &g, int own) { return (size_t)(g.pcm_pitch ? g.pcm_pitch : own); }

@@ -375,7 +375,7 @@ struct ProcessCall {
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
 int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
 // samples per row and frame at the batch's PCM rate
-inline int batch_frame_samples(const RNNoiseBatch *b) { return RN_FRAME_SIZE / (b->g.rs_L ? b->g.rs_L : 1); }
+inline int batch_frame_samples(const RNNoiseBatch *b) { return b->g.rs_L ? b->g.rs_pitch : RN_FRAME_SIZE; }
 // whether a host call takes the staged path instead of the pinned ring / bounce chunks of host_io.cpp: at a PCM rate other than 48 kHz
 // or with a rate table, with a PCM layout, with interleaved channels, and the int16 calls of a batch with a format table
 inline bool batch_host_call_staged(const RNNoiseBatch *b, bool s16) {

@@ -12,6 +12,13 @@ rnnoise_amd/csrc/rs_coeffs.h, and restates the two filters as a streaming CPU re
              starting from its first product, combined as (a0 + a1) + (a2 + a3).
   delay      up followed by down is a pure delay of DELAY = 47 low-rate samples.
 
+32 kHz is the one rate that is no divisor of 48 kHz: 2:3 through a common 96 kHz grid, where the prototype (144 taps, cutoff 0.45 * 32 kHz
+= 0.15 cycles per sample) is h of L = 3 as it stands.  Its code where an L is expected is RATE_32K = 32; frames are 320 samples.
+  up         u[J] = sum_{k=0..47} hup3[p][k] x[q - k],  q = floor(2 J / 3), p = 2 J mod 3      (history: 47 samples at 32 kHz)
+  down       y[m] = sum_{k=0..71} hd[e][k] v[n0 - k],  e = m & 1, n0 = (3 m + 2) >> 1, hd[e][k] = 2 h3[2 k + e]   (history: 70 at 48 kHz)
+  delay      up followed by down is again a delay of 47 samples at 32 kHz, but not an exact one: the 2:1 step in the middle aliases at the
+             stop-band level.
+
 The table below is the committed one: `design()` recomputes it with this machine's libm, which may move a last bit, so nothing
 regenerates it at build time.  `python -m rnnoise_amd.resample --header` prints the C header from the table.
 """
@@ -21,15 +28,22 @@ import sys
 
 import numpy as np
 
-RATES = {48000: 1, 24000: 2, 16000: 3, 8000: 6}
+RATE_32K = 32  # the code of 32 kHz wherever a divisor L is expected (include/rnnoise_amd.h: RNNOISE_AMD_RATE_32K)
+RATES = {48000: 1, 32000: RATE_32K, 24000: 2, 16000: 3, 8000: 6}
 TAPS_PER_PHASE = 48
+DOWN32_TAPS = 72  # taps per phase of the 32 kHz down filter
 DELAY = 47  # low-rate samples
 UP_HIST = TAPS_PER_PHASE - 1  # low-rate samples of history per stream
 
 
+def frame_samples(L: int) -> int:
+    """samples per 10 ms frame at the rate of code L"""
+    return 320 if L == RATE_32K else 480 // L
+
+
 def down_hist(L: int) -> int:
-    """48 kHz samples of down-filter history per stream (N - L)."""
-    return TAPS_PER_PHASE * L - L
+    """48 kHz samples of down-filter history per stream (N - L; 70 at 32 kHz: y[0] reaches v[1 - 71])."""
+    return DOWN32_TAPS - 2 if L == RATE_32K else TAPS_PER_PHASE * L - L
 
 
 def design(L: int) -> np.ndarray:
@@ -202,6 +216,11 @@ def hup(L: int) -> np.ndarray:
     return np.array([[np.float32(L * hh[L * k + p]) for k in range(TAPS_PER_PHASE)] for p in range(L)], dtype=np.float32)
 
 
+def hd32() -> np.ndarray:
+    """Down filter of 32 kHz: [2][72] float32, hd[e][k] = 2 h3[2 k + e] (an exact doubling)."""
+    return np.ascontiguousarray((np.float32(2) * _H[3]).reshape(DOWN32_TAPS, 2).T)
+
+
 def _fir4(taps: np.ndarray, window) -> np.ndarray:
     """sum_k taps[k] * window(k) in the library's order: four float32 chains over k mod 4, then (a0 + a1) + (a2 + a3).
     window(k) returns the float32 operand vector of tap k (one entry per output)."""
@@ -214,17 +233,26 @@ def _fir4(taps: np.ndarray, window) -> np.ndarray:
 
 
 class Up:
-    """Streaming upsampler of one or more streams: frames of shape [..., M] at R in, [..., M * L] at 48 kHz out."""
+    """Streaming upsampler of one or more streams: frames of shape [..., M] at R in, [..., M * L] at 48 kHz out (L = RATE_32K: M a
+    multiple of 2, [..., M * 3 / 2] out)."""
 
     def __init__(self, L: int, shape=()):
         self.L = L
         self.hist = np.zeros(tuple(shape) + (UP_HIST,), np.float32)
-        self.taps = hup(L)
+        self.taps = hup(3 if L == RATE_32K else L)
 
     def __call__(self, x: np.ndarray) -> np.ndarray:
         x = np.asarray(x, np.float32)
         M, L = x.shape[-1], self.L
         xs = np.concatenate([self.hist, x], axis=-1)  # xs[..., UP_HIST + q] = x[q]
+        if L == RATE_32K:  # three outputs per two inputs: J = 3 i + r reads from q = 2 i + floor(2 r / 3) on, phase 2 r mod 3
+            assert M % 2 == 0
+            i = np.arange(M // 2)
+            u = np.empty(x.shape[:-1] + (M // 2, 3), np.float32)
+            for r in range(3):
+                u[..., r] = _fir4(self.taps[2 * r % 3], lambda k: xs[..., UP_HIST + 2 * i + 2 * r // 3 - k])
+            self.hist = xs[..., -UP_HIST:].copy()
+            return u.reshape(x.shape[:-1] + (M // 2 * 3,))
         q = np.arange(M)
         u = np.empty(x.shape[:-1] + (M, L), np.float32)
         for p in range(L):
@@ -234,19 +262,27 @@ class Up:
 
 
 class Down:
-    """Streaming downsampler: frames [..., M * L] at 48 kHz in, [..., M] at R out."""
+    """Streaming downsampler: frames [..., M * L] at 48 kHz in, [..., M] at R out (L = RATE_32K: a multiple of 3 in, two thirds out)."""
 
     def __init__(self, L: int, shape=()):
         self.L = L
         self.D = down_hist(L)
         self.hist = np.zeros(tuple(shape) + (self.D,), np.float32)
-        self.taps = h(L)
+        self.taps = hd32() if L == RATE_32K else h(L)
 
     def __call__(self, v: np.ndarray) -> np.ndarray:
         v = np.asarray(v, np.float32)
         L, D = self.L, self.D
-        M = v.shape[-1] // L
         vs = np.concatenate([self.hist, v], axis=-1)  # vs[..., D + n] = v[n]
+        if L == RATE_32K:  # outputs m = 2 i + e: phase e from n0 = 3 i + 1 + e on
+            assert v.shape[-1] % 3 == 0
+            i = np.arange(v.shape[-1] // 3)
+            y = np.empty(v.shape[:-1] + (len(i), 2), np.float32)
+            for e in range(2):
+                y[..., e] = _fir4(self.taps[e], lambda k: vs[..., D + 3 * i + 1 + e - k])
+            self.hist = vs[..., -D:].copy()
+            return y.reshape(v.shape[:-1] + (2 * len(i),))
+        M = v.shape[-1] // L
         m = np.arange(M)
         y = _fir4(self.taps, lambda k: vs[..., D + L * m + L - 1 - k])
         self.hist = vs[..., -D:].copy()
@@ -261,6 +297,16 @@ def up(x: np.ndarray, L: int) -> np.ndarray:
 def down(v: np.ndarray, L: int) -> np.ndarray:
     """Whole signal(s) [..., T * L] from a zero history -> [..., T]."""
     return Down(L, np.shape(v)[:-1])(v)
+
+
+def up32(x: np.ndarray) -> np.ndarray:
+    """Whole signal(s) [..., T] at 32 kHz from a zero history -> [..., T * 3 / 2] at 48 kHz."""
+    return up(x, RATE_32K)
+
+
+def down32(v: np.ndarray) -> np.ndarray:
+    """Whole signal(s) [..., T] at 48 kHz from a zero history -> [..., T * 2 / 3] at 32 kHz."""
+    return down(v, RATE_32K)
 
 
 def to_s16(y: np.ndarray) -> np.ndarray:
@@ -282,6 +328,7 @@ def header_text() -> str:
            "//   rn_rs_h<L>[48 L]     down filter h[k]",
            "//   rn_rs_up<L>[L][48]   up filter, phase p: (float)(L * (double)h[L k + p])",
            "//   rn_rs_h_all[528]     rn_rs_h2, rn_rs_h3, rn_rs_h6 back to back",
+           "//   rn_rs_hd32[2][72]    down filter of 32 kHz (2:3 over rn_rs_h3; its up filter is rn_rs_up3), phase e: 2 * h3[2 k + e]",
            "// RN_RS_CONST is defined by the includer (__constant__ in device code).",
            "#pragma once",
            "#ifndef RN_RS_CONST",
@@ -303,6 +350,10 @@ def header_text() -> str:
     hx = _hex(np.concatenate([_H[2], _H[3], _H[6]]))
     for i in range(0, len(hx), 6):
         out.append("    " + ", ".join(x + "f" for x in hx[i:i + 6]) + ",")
+    out.append("};")
+    out.append(f"RN_RS_CONST float rn_rs_hd32[2][{DOWN32_TAPS}] = {{")
+    for row in hd32():
+        out.append("    {" + ", ".join(x + "f" for x in _hex(row)) + "},")
     out.append("};")
     return "\n".join(out) + "\n"
 

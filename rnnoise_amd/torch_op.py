@@ -60,7 +60,7 @@ def register_torch_op():
         T, N = pcm.shape[0], pcm.shape[1]
         return torch.empty_like(pcm), pcm.new_empty((T, N)), pcm.new_empty((T, N, capi.NB_BANDS))
 
-    # the stream-list form (include/rnnoise_amd.h: rnnoise_batch_process_device_list): pcm (T, R, 480 // L), row i of every frame
+    # the stream-list form (include/rnnoise_amd.h: rnnoise_batch_process_device_list): pcm (T, R, M), row i of every frame
     # belongs to stream idx[i] (int32 CUDA tensor); active (T, R) or None.  Only the listed streams advance; absent rows of the returned
     # PCM are zeros, their vad 0 and gains zeros.
     @torch.library.custom_op("rnnoise_amd::process_list", mutates_args=("state",),
@@ -75,7 +75,7 @@ def register_torch_op():
         T, R = pcm.shape[0], pcm.shape[1]
         return torch.empty_like(pcm), pcm.new_empty((T, R)), pcm.new_empty((T, R, capi.NB_BANDS))
 
-    # the stream-contiguous form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): pcm (N, T * (480 // L)) float32 or int16, one
+    # the stream-contiguous form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): pcm (N, T * (M)) float32 or int16, one
     # contiguous run of samples per stream -- the [B, T] tensor a torch user holds, read and written where it lies, no transpose.
     # active (T, N) or None, as in process_masked.  Returns out (same shape and dtype as pcm), vad (T, N), gains (T, N, 32).
     @torch.library.custom_op("rnnoise_amd::process_streams", mutates_args=("state",),
@@ -91,7 +91,7 @@ def register_torch_op():
         N, T = pcm.shape[0], pcm.shape[1] // _OPS[handle].batch.frame
         return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
 
-    # the interleaved form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels): pcm (G, T * (480 // L), C) float32 or int16 with
+    # the interleaved form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels): pcm (G, T * (M), C) float32 or int16 with
     # G * C the batch's streams -- channel c of group g is stream g * C + c --, read and written where it lies, no de-interleave.
     # active (T, G * C) or None.  Returns out (same shape and dtype as pcm), vad (T, G * C), gains (T, G * C, 32).
     @torch.library.custom_op("rnnoise_amd::process_channels", mutates_args=("state",),
@@ -111,8 +111,8 @@ def register_torch_op():
 
 
 class RNNoiseOp:
-    """N concurrent streams; call with a (T, N, 480 // L) float32 CUDA tensor of int16-scaled PCM at `rate` = 48000 / L (48000,
-    24000, 16000 or 8000: include/rnnoise_amd.h, rnnoise_batch_set_pcm_rate).  The same object is reachable as the registered op:
+    """N concurrent streams; call with a (T, N, M) float32 CUDA tensor of int16-scaled PCM at `rate` (48000, 32000, 24000, 16000 or 8000:
+    include/rnnoise_amd.h, rnnoise_batch_set_pcm_rate), M = 480 * rate // 48000 samples per frame (capi.Batch.frame).  The same object is reachable as the registered op:
     torch.ops.rnnoise_amd.process(pcm, op.state, op.handle).
     extra_models: more model blobs, put into model slots 1, 2, ... of the batch (rnnoise_batch_add_model); every stream starts on
     slot 0 (model_blob) and set_stream_models moves streams between slots."""
@@ -156,28 +156,28 @@ class RNNoiseOp:
         return self.torch.ops.rnnoise_amd.process(pcm, self.state, self.handle)
 
     def process_masked(self, pcm, active):
-        """pcm (T, N, 480 // L) float32 CUDA tensor, active (T, N) bool / uint8 CUDA tensor: streams whose frame has not arrived skip it
+        """pcm (T, N, M) float32 CUDA tensor, active (T, N) bool / uint8 CUDA tensor: streams whose frame has not arrived skip it
         (torch.ops.rnnoise_amd.process_masked)"""
         return self.torch.ops.rnnoise_amd.process_masked(pcm, active, self.state, self.handle)
 
     def process_list(self, pcm, idx, active=None):
-        """pcm (T, R, 480 // L) float32 CUDA tensor whose row i is stream idx[i] (an (R,) int32 CUDA tensor), active (T, R) bool / uint8
+        """pcm (T, R, M) float32 CUDA tensor whose row i is stream idx[i] (an (R,) int32 CUDA tensor), active (T, R) bool / uint8
         CUDA tensor or None: only the listed streams advance, with compact buffers (torch.ops.rnnoise_amd.process_list)"""
         return self.torch.ops.rnnoise_amd.process_list(pcm, idx, active, self.state, self.handle)
 
     def process_streams(self, pcm, active=None):
-        """pcm (N, T * (480 // L)) float32 or int16 CUDA tensor, stream-contiguous: row s is T consecutive frames of stream s.  The
+        """pcm (N, T * (M)) float32 or int16 CUDA tensor, stream-contiguous: row s is T consecutive frames of stream s.  The
         batch reads it and writes the result of the same shape where they lie (rnnoise_batch_set_pcm_layout: no transpose to frame-
-        major and back); active (T, N) bool / uint8 or None as in process_masked.  -> out (N, T * (480 // L)), vad (T, N), gains
+        major and back); active (T, N) bool / uint8 or None as in process_masked.  -> out (N, T * (M)), vad (T, N), gains
         (T, N, 32) (torch.ops.rnnoise_amd.process_streams).  The layout is set when it changes -- a synchronous call, so keep T and
         the entry point the same from call to call."""
         return self.torch.ops.rnnoise_amd.process_streams(pcm, active, self.state, self.handle)
 
     def process_channels(self, pcm, active=None):
-        """pcm (G, T * (480 // L), C) float32 or int16 CUDA tensor with G * C == n_streams: interleaved channels, channel c of group g
+        """pcm (G, T * (M), C) float32 or int16 CUDA tensor with G * C == n_streams: interleaved channels, channel c of group g
         being stream g * C + c.  The batch reads it and writes the result of the same shape where they lie
         (rnnoise_batch_set_pcm_channels + rnnoise_batch_set_pcm_layout: no de-interleave and no transpose); active (T, G * C) bool /
-        uint8 or None as in process_masked.  -> out (G, T * (480 // L), C), vad (T, G * C), gains (T, G * C, 32)
+        uint8 or None as in process_masked.  -> out (G, T * (M), C), vad (T, G * C), gains (T, G * C, 32)
         (torch.ops.rnnoise_amd.process_channels).  Channel count and layout are set when they change -- synchronous calls, so keep
         T, C and the entry point the same from call to call."""
         return self.torch.ops.rnnoise_amd.process_channels(pcm, active, self.state, self.handle)
@@ -228,7 +228,7 @@ class RNNoiseOp:
 
     def set_stream_rates(self, hz):
         """the PCM rate of every stream in Hz (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates): a sequence / array of N values
-        out of 48000, 24000, 16000, 8000, none above the op's `rate`, or None to drop the table.  Rows of the PCM tensors keep the
+        out of 48000, 32000, 24000, 16000, 8000, none above the op's `rate`, or None to drop the table.  Rows of the PCM tensors keep the
         op's frame length; stream s reads and writes the first 480 * hz[s] // 48000 samples of its row and leaves the rest alone.
         Synchronous; ValueError on any other value."""
         self.batch.set_stream_rates(hz)

@@ -6,7 +6,7 @@ channel count):
 
     format 1 (PCM) with 16-bit samples, format 6 (A-law) and format 7 (mu-law) with 8-bit samples,
     WAVE_FORMAT_EXTENSIBLE (0xFFFE) whose sub-format is one of those three,
-    1 to 8 channels, interleaved,  at 8000, 16000, 24000 or 48000 Hz.
+    1 to 8 channels, interleaved,  at 8000, 16000, 24000, 32000 or 48000 Hz.
 
 Chunks other than `fmt ` and `data` are skipped (with the pad byte of an odd length); the `data` length is the header's, but never
 beyond the end of the file (a recording cut short, or a writer that left 0 / 0xFFFFFFFF there: the rest of the file).  Anything else
@@ -20,7 +20,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-RATES = (8000, 16000, 24000, 48000)
+RATES = (8000, 16000, 24000, 32000, 48000)
 MAX_CHANNELS = 8
 CODECS = {1: "s16", 6: "alaw", 7: "ulaw"}            # wFormatTag -> sample format (rnnoise_amd/g711.py names)
 TAGS = {v: k for k, v in CODECS.items()}
