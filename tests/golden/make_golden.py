@@ -17,6 +17,9 @@ running it.
   tests/golden/reference_pins.npz-- what tests/test_oracle.py's and tests/test_train_features.py's reference comparisons
                                     read where oracle/_ref is not built: tables, FFT / pitch search, a free-running and a
                                     teacher-forced stream, training features (`make_golden.py --pins [OUTDIR]` writes only it)
+                                    "trainedge<i>": (16, 98) records of stream i of tests/train_cases.py: edge_subset(), the band
+                                    limits at and beyond the ends of their ranges.  Keys the file already holds must come out
+                                    bit-identical, or nothing is written
 
 The reference's tanh / sigmoid execute the generating CPU's `rcpps` (src/vec_avx.h:413,442), so a fixture belongs to one
 CPU family and says which ("rcp_profile", "host_cpu" entries).  The Intel build host writes tests/golden/*.npz; run on the
@@ -111,7 +114,22 @@ def reference_pins(gold, tag, blob):
         clean, noisy, vad = train_case(stream, 40, rng)
         rt = RefTrainHarness()
         d[f"train{stream}"] = np.stack([rt.frame(clean[t], noisy[t], lp, blp, vad[t], nf) for t in range(40)])
-    np.savez_compressed(os.path.join(gold, "reference_pins.npz"), **d, **tag)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import train_cases  # noqa: E402  (tests/train_cases.py: test_oracle_train_step_matches_reference_on_the_band_limit_edges)
+    e = train_cases.edge_subset()
+    for s in range(e.n):
+        rt = RefTrainHarness()
+        d[f"trainedge{s}"] = np.stack([rt.frame(e.clean[t, s], e.noisy[t, s], int(e.lowpass[s]), int(e.band_lp[s]), e.vad[t, s],
+                                                int(e.noise_free[s])) for t in range(train_cases.T)])
+    path = os.path.join(gold, "reference_pins.npz")
+    if os.path.exists(path):  # what the file pins already stays pinned ("host_cpu" names the machine, not a result)
+        old = np.load(path)
+        for k in old.files:
+            if k != "host_cpu":
+                assert k in d or k in tag, f"{k} would be dropped"
+                new = np.asarray(d[k] if k in d else tag[k])
+                assert new.dtype == old[k].dtype and new.shape == old[k].shape and new.tobytes() == old[k].tobytes(), f"{k} changed"
+    np.savez_compressed(path, **d, **tag)
 
 
 def main():
