@@ -431,7 +431,8 @@ RNNOISE_EXPORT long rnnoise_amd_model_pack(RNNModel *model, void *out, long cap)
  * TRAINING=1 build of denoise.c): per frame and stream, Ey from the CLEAN frame, the 65 features
  * from the NOISY frame (no silence short-cut), the 32 band-gain targets and the VAD target passed
  * through: records[n_frames][n_streams][98] = features | gains | vad.  Mixing, filtering and
- * augmentation of the signals stay with the caller, as in dump_features.  lowpass[n_streams] is the
+ * augmentation of the signals are the calls below (RNNoiseTrainMix), whose outputs have the layouts
+ * this call takes; a caller with a mixer of their own passes its frames here.  lowpass[n_streams] is the
  * first zeroed FFT bin (481 = none, src/denoise.c:340-343), band_lp[n_streams] the last band with a
  * valid target (32 = all), noise_free[n_streams] = (noise_gain==0 && fgnoise_gain==0).
  * The batch's per-stream analysis state tracks the noisy signal; a batch used for extraction
@@ -443,6 +444,54 @@ RNNOISE_EXPORT int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d
                                                        const float *d_noisy, const float *d_vad, const int *d_lowpass,
                                                        const int *d_band_lp, const int *d_noise_free, int n_frames,
                                                        void *hip_stream);
+
+/* Training sequences (the caller-side half of the reference's feature dumper, src/dump_features.c:408-465): from three int16
+ * corpora on the device -- speech, noise, foreground noise -- to the clean / noisy frames rnnoise_batch_train_features_device
+ * takes, one sequence of n_frames frames per stream of the batch (n_seq = the batch size), bit for bit what the reference
+ * computes from the same draws in its pinned build (-O2 -ffp-contract=off).  RNNoiseTrainMix holds one sequence's draws
+ * (:367-399, :454, :460): the first sample of the sequence in each corpus (in samples; odd values too), the three gains as they
+ * stand after :395-396 (before the level normalisation), the six filter coefficient pairs of rand_resp (:397-399) and the two
+ * augmentation flags.  Four calls, in this order:
+ *   rnnoise_amd_train_mix_check        host only: 1 when every position lies in [0, len - 480 * n_frames], every gain and
+ *                                      coefficient is finite and the flags are 0 or 1 (n_seq, n_frames >= 1); 0 otherwise.
+ *   rnnoise_batch_train_levels_device  d_energy[n_seq][n_frames]: the speech energy per frame (:409-412);
+ *                                      d_rms[n_seq][3]: weighted_rms (:283-293) of each signal after its two biquads (:420-431).
+ *   rnnoise_amd_train_vad              host only, on the energies copied back: viterbi_vad (:199-254) per row with n_frames for
+ *                                      its 2000 frames, then the first start_pos[s] / 480 frames cleared (:437; start_pos NULL:
+ *                                      none) -> vad[n_seq][n_frames] bytes.  It stays on the host on purpose: its log, pow and
+ *                                      sqrt in double are the host libm's, as in the reference.  0 / -1.
+ *   rnnoise_batch_train_mix_device     the biquads again, clear_vad (:256-281) on the speech with d_vad[n_seq][n_frames] bytes,
+ *                                      the level normalisation with d_rms (:440-442), the mix (:443-448), clipping (:457) and
+ *                                      quantisation (:463) where the flags say so ->
+ *                                      d_clean, d_noisy [n_frames][n_seq][480] (16-byte aligned), d_vad_target [n_frames][n_seq],
+ *                                      d_noise_free [n_seq] (noise_gain == 0 && fgnoise_gain == 0 as :477 sees them).
+ * RIR filtering (-rir_list, :449-453) is not part of it: a caller puts a RIR of their own between mix and clip by passing
+ * clip = quantize = 0 and clipping / quantising afterwards.
+ * The two device calls enqueue on hip_stream; `mix` is a host array of n_seq entries, copied into a buffer the batch owns
+ * (allocated on first use) by a copy ordered on hip_stream.  `mix` is read before the call returns and may be freed then: for
+ * pageable memory that means the call waits until the stream has reached the copy; the kernel runs asynchronously after it.  A
+ * batch has one such buffer: issue its training-mix calls on one stream, or order them yourself.  They run the check first; a failed check, a NULL argument or n_frames < 1 returns -1 with
+ * nothing launched.  They read and write no per-stream state, ignore the rate, format, layout, channel, model and control
+ * tables, work in lock-step and in per-stream frame phase, and write nothing but the named outputs.  *_len: corpus lengths in
+ * samples.  Cost: DESIGN.md section 4.20. */
+typedef struct RNNoiseTrainMix {
+  long long speech_pos, noise_pos, fgnoise_pos;
+  float speech_gain, noise_gain, fgnoise_gain;
+  float a_sig[2], b_sig[2], a_noise[2], b_noise[2], a_fgnoise[2], b_fgnoise[2];
+  int clip, quantize;
+} RNNoiseTrainMix;
+RNNOISE_EXPORT int rnnoise_amd_train_mix_check(const RNNoiseTrainMix *mix, int n_seq, long long speech_len, long long noise_len,
+                                               long long fgnoise_len, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_train_levels_device(RNNoiseBatch *b, float *d_energy, float *d_rms, const short *d_speech,
+                                                     const short *d_noise, const short *d_fgnoise, long long speech_len,
+                                                     long long noise_len, long long fgnoise_len, const RNNoiseTrainMix *mix,
+                                                     int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_amd_train_vad(const float *energy, int n_seq, int n_frames, const int *start_pos, unsigned char *vad);
+RNNOISE_EXPORT int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clean, float *d_noisy, float *d_vad_target,
+                                                  int *d_noise_free, const short *d_speech, const short *d_noise,
+                                                  const short *d_fgnoise, long long speech_len, long long noise_len,
+                                                  long long fgnoise_len, const RNNoiseTrainMix *mix, const float *d_rms,
+                                                  const unsigned char *d_vad, int n_frames, void *hip_stream);
 
 /* Test taps for the last processed frame step: per-stream feature vectors [N][65],
  * silence flags [N] and final pitch periods [N] (host buffers, any may be NULL). */

@@ -62,7 +62,19 @@ EXPORTS = [
     "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
     "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
     "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
+    "rnnoise_amd_train_mix_check", "rnnoise_batch_train_levels_device", "rnnoise_amd_train_vad", "rnnoise_batch_train_mix_device",
 ]
+
+
+class TrainMix(C.Structure):
+    """RNNoiseTrainMix (include/rnnoise_amd.h): one training sequence's draws.  np.dtype(TrainMix) is the record type of a table."""
+    _fields_ = [("speech_pos", C.c_longlong), ("noise_pos", C.c_longlong), ("fgnoise_pos", C.c_longlong),
+                ("speech_gain", C.c_float), ("noise_gain", C.c_float), ("fgnoise_gain", C.c_float),
+                ("a_sig", C.c_float * 2), ("b_sig", C.c_float * 2), ("a_noise", C.c_float * 2), ("b_noise", C.c_float * 2),
+                ("a_fgnoise", C.c_float * 2), ("b_fgnoise", C.c_float * 2), ("clip", C.c_int), ("quantize", C.c_int)]
+
+
+MIX_DTYPE = np.dtype(TrainMix)
 MAX_CHANNELS = 8  # RNNOISE_AMD_MAX_CHANNELS: interleaved channels of a batch's PCM rows
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)  # the rates that divide 48 kHz: code = divisor
@@ -224,6 +236,11 @@ def _load(path, debug):
         L.rnnoise_batch_debug_last.argtypes = [vp, fp, ip, ip]
         L.rnnoise_batch_train_features.argtypes = [vp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
         L.rnnoise_batch_train_features_device.argtypes = [vp] * 8 + [C.c_int, vp]
+        ll = C.c_longlong
+        L.rnnoise_amd_train_mix_check.argtypes = [vp, C.c_int, ll, ll, ll, C.c_int]
+        L.rnnoise_batch_train_levels_device.argtypes = [vp] * 6 + [ll, ll, ll, vp, C.c_int, vp]
+        L.rnnoise_amd_train_vad.argtypes = [fp, C.c_int, C.c_int, ip, up]
+        L.rnnoise_batch_train_mix_device.argtypes = [vp] * 8 + [ll, ll, ll, vp, vp, vp, C.c_int, vp]
         if debug:
             L.rnnoise_batch_debug_pitch.argtypes = [vp, fp]
             L.rnnoise_amd_debug_log_energy.argtypes = [C.c_int, fp, fp, C.c_int]
@@ -262,6 +279,34 @@ def pcm_channels_fit(frame_stride: int, row_stride: int, frame_samples: int, cha
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
+
+
+def _mix_table(mix):
+    """a table of RNNoiseTrainMix records as one contiguous array of MIX_DTYPE"""
+    mix = np.ascontiguousarray(mix, MIX_DTYPE)
+    assert mix.ndim == 1, mix.shape
+    return mix
+
+
+def train_mix_check(mix, lens, n_frames: int) -> bool:
+    """rnnoise_amd_train_mix_check: whether every sequence of the table lies inside its corpora (lens: the three corpus lengths in
+    samples), every gain and coefficient is finite and the flags are 0 or 1.  Host only."""
+    mix = _mix_table(mix)
+    return bool(lib().rnnoise_amd_train_mix_check(mix.ctypes.data, len(mix), int(lens[0]), int(lens[1]), int(lens[2]), int(n_frames)))
+
+
+def train_vad(energy, start_pos=None):
+    """rnnoise_amd_train_vad: energy (n_seq, n_frames) float32 -> vad (n_seq, n_frames) uint8, the reference's Viterbi VAD per row with
+    the first start_pos[s] // 480 frames cleared.  Host only."""
+    energy = np.ascontiguousarray(energy, np.float32)
+    n_seq, n_frames = energy.shape
+    sp = None if start_pos is None else np.ascontiguousarray(start_pos, np.int32)
+    assert sp is None or sp.shape == (n_seq,), sp.shape
+    vad = np.empty((n_seq, n_frames), np.uint8)
+    if lib().rnnoise_amd_train_vad(_fp(energy), n_seq, n_frames, sp.ctypes.data_as(C.POINTER(C.c_int)) if sp is not None else None,
+                                   vad.ctypes.data_as(C.POINTER(C.c_ubyte))):
+        raise ValueError("rnnoise_amd_train_vad failed")
+    return vad
 
 
 def _close_quietly(obj):
@@ -727,6 +772,35 @@ class Batch:
                                               *[a.ctypes.data_as(ip) for a in ia], T):
             raise RuntimeError("rnnoise_batch_train_features failed")
         return rec
+
+    def train_levels_device(self, d_energy: int, d_rms: int, d_corpora, lens, mix, n_frames: int, stream: int = 0):
+        """Raw device pointers (ints), asynchronous on `stream`: d_energy [N][n_frames] and d_rms [N][3] float32 out; d_corpora: the
+        speech, noise and foreground-noise corpora (int16), lens their lengths in samples; mix: a host table of N MIX_DTYPE records."""
+        mix = _mix_table(mix)
+        assert len(mix) == self.n, (len(mix), self.n)
+        if self._L.rnnoise_batch_train_levels_device(self.h, d_energy or None, d_rms or None, *[p or None for p in d_corpora],
+                                                     *[int(v) for v in lens], mix.ctypes.data, n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_train_levels_device failed (a sequence outside its corpus, a non-finite gain?)")
+
+    def train_mix_device(self, d_clean: int, d_noisy: int, d_vad_target: int, d_noise_free: int, d_corpora, lens, mix, d_rms: int,
+                         d_vad: int, n_frames: int, stream: int = 0):
+        """Raw device pointers (ints), asynchronous on `stream`: d_clean, d_noisy [n_frames][N][480] float32, d_vad_target
+        [n_frames][N] float32 and d_noise_free [N] int32 out -- the layouts rnnoise_batch_train_features_device takes; d_rms [N][3]
+        from train_levels_device, d_vad [N][n_frames] uint8 from train_vad."""
+        mix = _mix_table(mix)
+        assert len(mix) == self.n, (len(mix), self.n)
+        if self._L.rnnoise_batch_train_mix_device(self.h, d_clean or None, d_noisy or None, d_vad_target or None, d_noise_free or None,
+                                                  *[p or None for p in d_corpora], *[int(v) for v in lens], mix.ctypes.data,
+                                                  d_rms or None, d_vad or None, n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_train_mix_device failed (a sequence outside its corpus, a non-finite gain?)")
+
+    def train_features_device(self, d_records: int, d_clean: int, d_noisy: int, d_vad: int, d_lowpass: int, d_band_lp: int,
+                              d_noise_free: int, n_frames: int, stream: int = 0):
+        """rnnoise_batch_train_features_device on raw device pointers (ints), asynchronous on `stream`"""
+        if self._L.rnnoise_batch_train_features_device(self.h, d_records or None, d_clean or None, d_noisy or None, d_vad or None,
+                                                       d_lowpass or None, d_band_lp or None, d_noise_free or None, n_frames,
+                                                       stream or None):
+            raise RuntimeError("rnnoise_batch_train_features_device failed")
 
     def debug_pitch(self, arm_only: bool = False):
         if arm_only:

@@ -18,6 +18,11 @@ batch; a stream whose file has ended is fed zeros and produces no more output.
 An input that starts with RIFF....WAVE is read as a WAV file (rnnoise_amd/wav.py: PCM16, A-law or mu-law, 1 to 8 channels, 8 to 48 kHz):
 its rate, format and channel count come from its header, each channel is one stream, its samples cross the batch interleaved as they lie
 in the file (rnnoise_batch_set_pcm_channels), and the output is <name>.denoised.wav with the input's header fields.
+
+Training data (the reference's src/dump_features.c without its RIR option; rnnoise_amd/train_data.py): COUNT sequences of 98-float
+records from three RAW s16 48 kHz mono corpora, each uploaded once, everything else on the device:
+
+  python -m rnnoise_amd.cli dump-features --model weights_blob.bin speech.pcm noise.pcm fgnoise.pcm out.f32 COUNT
 """
 from __future__ import annotations
 
@@ -160,6 +165,27 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
     batch.close()
 
 
+def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out: str, count: int, seed=None, seq_frames: int = 2000,
+                  streams: int = 64, device: int = 0):
+    """COUNT training sequences of seq_frames frames into `out` (float32 records, sequence after sequence: the reference's file
+    format): sequence i runs on stream i % streams of one batch in round i // streams.  Each corpus is read and uploaded once.  The
+    draws come from numpy's default generator seeded with `seed` (train_data.draw)."""
+    import torch
+
+    from . import train_data
+    dev = torch.device("cuda", device)
+    corpora = [torch.from_numpy(np.fromfile(p, dtype=np.int16)).to(dev) for p in (speech, noise, fgnoise)]
+    draws = train_data.draw(np.random.default_rng(seed), count, [c.numel() for c in corpora], seq_frames)
+    model = capi.Model(model_blob)
+    batch = capi.Batch(model, max(1, min(streams, count)), device=device)
+    with torch.cuda.device(dev), open(out, "wb") as f:
+        for rec in train_data.generate_rounds(batch, *corpora, draws, seq_frames):
+            f.write(rec.tobytes())
+    batch.close()
+    model.close()
+    return count * seq_frames
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -179,7 +205,23 @@ def main(argv=None):
     p.add_argument("--vad-gate", type=float, default=0.0, help="VAD threshold in [0, 1] below which output is muted (0: no gate)")
     p.add_argument("--vad-hold", type=int, default=0, help="frames the VAD gate stays open after the last voice frame")
     p.add_argument("inputs", nargs="+")
+    p = sub.add_parser("dump-features")
+    p.add_argument("--model", required=True, help='"DNNw" weight blob: a batch needs one (the extraction runs no network)')
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--seq-frames", type=int, default=2000, help="frames per sequence (the reference: 2000)")
+    p.add_argument("--streams", type=int, default=64, help="sequences per round: the batch size")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("speech")
+    p.add_argument("noise")
+    p.add_argument("fgnoise")
+    p.add_argument("out")
+    p.add_argument("count", type=int)
     a = ap.parse_args(argv)
+    if a.cmd == "dump-features":
+        n = dump_features(open(a.model, "rb").read(), a.speech, a.noise, a.fgnoise, a.out, a.count, a.seed, a.seq_frames, a.streams,
+                          a.device)
+        print(f"wrote {a.count} sequences, {n} records")
+        return
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
                       a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")

@@ -8,6 +8,7 @@
 //                     training features, timing, debug taps
 //   batch_tables.cpp  a batch's configuration: PCM rate, strides, channels, the per-stream tables (rates, formats, models, controls)
 //   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
+//   train_mix.hip     training sequences: levels, Viterbi VAD and mix of src/dump_features.c:408-465, host code and kernels
 //   host_io.cpp  host-fed calls: the pinned frame ring, the bounce chunks of pageable callers
 //   dropin.cpp   the reference's own API (include/rnnoise.h): state pools, the combiner of concurrent one-frame calls
 #pragma once
@@ -225,6 +226,8 @@ struct RNNoiseBatch {
   // per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): [N][RN_CTL_FLOATS] table, then the [N]
   // counters; g.ctl / g.gate_c point into it while a table is set
   float *ctl_buf = nullptr;
+  // the [N] RNNoiseTrainMix table of the last training-mix call (train_mix.hip), allocated on first use
+  void *train_mix_buf = nullptr;
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
   hipStream_t side = nullptr, side_hp = nullptr;

@@ -1,0 +1,152 @@
+"""Training data on the GPU: what the reference's src/dump_features.c does per sequence, in batches (include/rnnoise_amd.h:
+RNNoiseTrainMix).  draw() makes the random choices of dump_features.c:367-406 and :454 / :460 on the host; generate() runs everything
+from the int16 corpora to the 98-float records on the device, one sequence per stream of a batch and round:
+
+    levels (rnnoise_batch_train_levels_device) -> energies to the host -> Viterbi VAD (rnnoise_amd_train_vad) ->
+    mix (rnnoise_batch_train_mix_device) -> features (rnnoise_batch_train_features_device)
+
+For the same draws the records are bit for bit the reference's (without its optional RIR filtering).  draw() follows the reference's
+distributions, not glibc's rand() stream.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+
+from . import capi
+
+FRAME = capi.FRAME
+FREQ_SIZE = 481
+NB_BANDS = capi.NB_BANDS
+REC = capi.NB_FEATURES + NB_BANDS + 1  # features | gain targets | vad
+# the band edges in bins (src/denoise.c:63-65), as far as dump_features.c:401-406 looks
+EBAND = (0, 2, 4, 6, 8, 10, 12, 15, 18, 21, 24, 28, 32, 36, 41, 47, 53, 60, 68, 77, 87, 98, 110, 124, 140, 157, 176, 198, 223, 251, 282, 317)
+
+# draw() takes all its uniform numbers of a sequence from one row of rng.random((n, N_UNIFORM)); the columns:
+U_POS = 0          # 3: the positions in the three corpora
+U_START = 3        # 2: start_pos -- whether, and how far
+U_GAIN = 5         # 6: speech, noise, foreground noise, two each
+U_NO_NOISE = 11    # noise_gain = 0 with probability 1/8
+U_FG = 12          # fgnoise_gain stays with probability 1/8
+U_QUIET = 13       # both noise gains * 0.03 with probability 1/12
+U_FILT = 14        # 6 filters (a_noise, b_noise, a_fgnoise, b_fgnoise, a_sig, b_sig), 4 each: branch, kind, two values
+U_LOWPASS = 38
+U_CLIP = 39
+U_QUANT = 40
+N_UNIFORM = 41
+
+
+class Draws(NamedTuple):
+    mix: np.ndarray        # (n,) capi.MIX_DTYPE
+    start_pos: np.ndarray  # (n,) int32, samples: the VAD is cleared before it (dump_features.c:382-384, :437)
+    lowpass: np.ndarray    # (n,) int32, first zeroed FFT bin (dump_features.c:400)
+    band_lp: np.ndarray    # (n,) int32, last band with a valid gain target (dump_features.c:401-406)
+
+
+def band_lp_of(lowpass: int, previous: int) -> int:
+    """dump_features.c:401-406: the first band whose edge lies above `lowpass` -- and, as in the reference, the PREVIOUS sequence's
+    value when no band does (band_lp is a global there, 32 before the first sequence)"""
+    for i in range(NB_BANDS):
+        if EBAND[i] > lowpass:
+            return i
+    return previous
+
+
+def _rand_filt(u):
+    """rand_filt (dump_features.c:159-178) from four uniform numbers per filter: u (n, 4) -> (n, 2) float32"""
+    f32 = np.float32
+    r = (f32(.7) * u[:, 2] * u[:, 2]).astype(f32)
+    theta = (np.pi * u[:, 3] * u[:, 3]).astype(f32)
+    pair = np.stack([-2 * r * np.cos(theta.astype(np.float64)), r.astype(np.float64) * r], 1)
+    r0 = (1.4 * (u[:, 2] - .5)).astype(f32).astype(np.float64)
+    r1 = (1.4 * (u[:, 3] - .5)).astype(f32).astype(np.float64)
+    real = np.stack([-r0 - r1, r0 * r1], 1)
+    out = np.where((u[:, 1] > .5)[:, None], pair, real)
+    out[u[:, 0] >= 1 / 3] = 0  # rand() % 3 != 0
+    return out.astype(f32)
+
+
+def draw(rng: np.random.Generator, n: int, lens, n_frames: int, band_lp: int = NB_BANDS) -> Draws:
+    """The draws of n sequences of n_frames frames from corpora of lens = (speech, noise, foreground noise) samples, in sequence
+    order.  band_lp: the value carried in from the sequence before the first one (32 at the start of a run)."""
+    f32 = np.float32
+    span = FRAME * n_frames
+    if min(lens) < span:
+        raise ValueError(f"a corpus of {min(lens)} samples is shorter than a sequence of {span}")
+    u = np.asarray(rng.random((n, N_UNIFORM)), np.float64)
+    assert u.shape == (n, N_UNIFORM)
+    mix = np.zeros(n, capi.MIX_DTYPE)
+    for k, name in enumerate(("speech_pos", "noise_pos", "fgnoise_pos")):
+        mix[name] = np.minimum((u[:, U_POS + k] * lens[k]).astype(np.int64), lens[k] - span)
+    # start_pos = 0 three times out of four, else -(int)(1000 * log(uniform)), at most the sequence (:382-384)
+    far = (-1000.0 * np.log(1.0 - u[:, U_START + 1])).astype(np.int64)
+    start_pos = np.where(u[:, U_START] < .75, 0, np.minimum(far, span)).astype(np.int32)
+    g = u[:, U_GAIN:U_GAIN + 6]
+    speech = (10.0 ** ((-45 + 45 * g[:, 0] + 10 * g[:, 1]) / 20)).astype(f32)
+    noise = (10.0 ** ((-30 + 40 * g[:, 2] + 15 * g[:, 3]) / 20)).astype(f32)
+    fg = (10.0 ** ((-30 + 40 * g[:, 4] + 15 * g[:, 5]) / 20)).astype(f32)
+    noise[u[:, U_NO_NOISE] < 1 / 8] = 0
+    fg[u[:, U_FG] >= 1 / 8] = 0
+    quiet = u[:, U_QUIET] < 1 / 12
+    noise[quiet] = (noise[quiet] * 0.03).astype(f32)
+    fg[quiet] = (fg[quiet] * 0.03).astype(f32)
+    mix["speech_gain"], mix["noise_gain"], mix["fgnoise_gain"] = speech, noise * speech, fg * speech
+    for k, name in enumerate(("a_noise", "b_noise", "a_fgnoise", "b_fgnoise", "a_sig", "b_sig")):
+        mix[name] = _rand_filt(u[:, U_FILT + 4 * k:U_FILT + 4 * k + 4])
+    lowpass = (FREQ_SIZE * 3000. / 24000. * 50.0 ** u[:, U_LOWPASS]).astype(np.int32)
+    bands = np.empty(n, np.int32)
+    for i in range(n):  # (in sequence order: the carry-over)
+        band_lp = bands[i] = band_lp_of(int(lowpass[i]), band_lp)
+    mix["clip"] = u[:, U_CLIP] < 1 / 4
+    mix["quantize"] = u[:, U_QUANT] < 1 / 2
+    return Draws(mix, start_pos, lowpass, bands)
+
+
+def _pad(a, n):
+    """a round's table for a batch of n streams: the streams behind the last sequence repeat it (their records are dropped)"""
+    return a if len(a) == n else np.concatenate([a, np.repeat(a[-1:], n - len(a), 0)])
+
+
+def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int):
+    """Yields the records of sequences [r * N, (r + 1) * N) of `draws`, r = 0, 1, ..., each a (sequences, n_frames, 98) float32 array:
+    sequence i runs on stream i % N of `batch` (N streams) in round i // N, and the batch's per-stream analysis state carries from one
+    sequence of a stream to the next, as the reference's two DenoiseStates carry across its loop.  speech, noise, fgnoise: the corpora
+    as 1-D int16 torch tensors on the batch's device.  Everything is enqueued on torch's current stream; the only host work of a
+    round is the Viterbi VAD on the frame energies.  When the last round is partial, the streams behind the last sequence run that
+    sequence again (records dropped), so their analysis state advances too: a later call on the same batch starts those streams from
+    a state that no sequence of the file order left.  Reset the batch, or use a sequence count that is a multiple of N, where that
+    matters; one run of the command line is not affected."""
+    import torch
+    N = batch.n
+    corpora = (speech, noise, fgnoise)
+    for c in corpora:
+        assert c.dtype == torch.int16 and c.dim() == 1 and c.is_cuda and c.is_contiguous(), (c.dtype, c.shape, c.device)
+    dev = speech.device
+    ptrs, lens = [c.data_ptr() for c in corpora], [c.numel() for c in corpora]
+    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+    energy, rms = new((N, n_frames)), new((N, 3))
+    clean, noisy = new((n_frames, N, FRAME)), new((n_frames, N, FRAME))
+    vad_target, noise_free = new((n_frames, N)), new((N,), torch.int32)
+    rec = new((n_frames, N, REC))
+    count = len(draws.mix)
+    for first in range(0, count, N):
+        k = min(N, count - first)
+        rows = slice(first, first + k)
+        mix = _pad(draws.mix[rows], N)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        batch.train_levels_device(energy.data_ptr(), rms.data_ptr(), ptrs, lens, mix, n_frames, st)
+        vad = capi.train_vad(energy.cpu().numpy(), _pad(draws.start_pos[rows], N))
+        d_vad = torch.from_numpy(vad).to(dev)
+        d_lowpass = torch.from_numpy(_pad(draws.lowpass[rows], N).astype(np.int32)).to(dev)
+        d_band_lp = torch.from_numpy(_pad(draws.band_lp[rows], N).astype(np.int32)).to(dev)
+        batch.train_mix_device(clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), noise_free.data_ptr(), ptrs, lens, mix,
+                               rms.data_ptr(), d_vad.data_ptr(), n_frames, st)
+        batch.train_features_device(rec.data_ptr(), clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), d_lowpass.data_ptr(),
+                                    d_band_lp.data_ptr(), noise_free.data_ptr(), n_frames, st)
+        yield rec.permute(1, 0, 2)[:k].contiguous().cpu().numpy()  # sequence-major: the reference's file order
+
+
+def generate(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int) -> np.ndarray:
+    """all records of `draws`, (sequences, n_frames, 98) float32 in sequence order (generate_rounds)"""
+    return np.concatenate(list(generate_rounds(batch, speech, noise, fgnoise, draws, n_frames)))
