@@ -465,8 +465,9 @@ RNNOISE_EXPORT int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d
  *                                      quantisation (:463) where the flags say so ->
  *                                      d_clean, d_noisy [n_frames][n_seq][480] (16-byte aligned), d_vad_target [n_frames][n_seq],
  *                                      d_noise_free [n_seq] (noise_gain == 0 && fgnoise_gain == 0 as :477 sees them).
- * RIR filtering (-rir_list, :449-453) is not part of it: a caller puts a RIR of their own between mix and clip by passing
- * clip = quantize = 0 and clipping / quantising afterwards.
+ * RIR filtering (-rir_list, :449-453) is not part of it: it sits between mix and clip, so a caller who wants it passes
+ * clip = quantize = 0 here and hands the real flags to rnnoise_batch_train_rir_device (RNNoiseTrainRir, below) -- or filters with a
+ * convolution of their own and clips / quantises afterwards.
  * The two device calls enqueue on hip_stream; `mix` is a host array of n_seq entries, copied into a buffer the batch owns
  * (allocated on first use) by a copy ordered on hip_stream.  `mix` is read before the call returns and may be freed then: for
  * pageable memory that means the call waits until the stream has reached the copy; the kernel runs asynchronously after it.  A
@@ -492,6 +493,41 @@ RNNOISE_EXPORT int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clea
                                                   const short *d_fgnoise, long long speech_len, long long noise_len,
                                                   long long fgnoise_len, const RNNoiseTrainMix *mix, const float *d_rms,
                                                   const unsigned char *d_vad, int n_frames, void *hip_stream);
+
+/* Room impulse responses for training sequences (the reference's -rir_list option, src/dump_features.c:51-144 and :449-465), between
+ * rnnoise_batch_train_mix_device (called with clip = quantize = 0) and rnnoise_batch_train_features_device, bit for bit what the
+ * reference computes in its pinned build: overlap-save in blocks of 32,768 samples with its 65,536-point kiss_fft, whose output is
+ * HALF the convolution (signal and response are both scaled by 1/65536 going forward, the product by 32768) -- kept.
+ *   rnnoise_batch_train_rir_load_device  load_rir (:63-88) for n_rirs responses: d_rir[n_rirs][32768] floats on the device, of
+ *                                      which the first lens[r] count (host array, 1 <= len <= 32768) ->
+ *                                      d_spectra[n_rirs][2][65536][2] floats: [r][0] the whole response, [r][1] the early one
+ *                                      (samples 480..719 faded out, nothing from 720 on).
+ *   rnnoise_batch_train_rir_device     per sequence s of the batch (n_seq = the batch size) with rir[s].rir_id >= 0:
+ *                                      rir_filter_sequence (:119-144) for any n_frames, on d_clean with the early spectrum and on
+ *                                      d_noisy with the whole one, in place, in the [n_frames][n_seq][480] layout; then, for every
+ *                                      sequence (rir_id = -1: not filtered), clipping (:457) and quantisation (:463) of d_noisy
+ *                                      where rir[s] says so.
+ *   rnnoise_amd_train_rir_work_bytes   host only: the bytes of d_work for n_units transform pairs in flight (one unit = one
+ *                                      block of one signal of one sequence; 1 MiB each).  The filter call works through its
+ *                                      2 * ceil(480 * n_frames / 32768) * (filtered sequences) units in slabs of as many as
+ *                                      work_bytes holds; the result does not depend on that number.
+ *   rnnoise_amd_train_rir_check        host only: 1 when every rir_id lies in [-1, n_rirs) and the flags are 0 or 1; else 0.
+ * `rir` and `lens` are host arrays, read before the call returns (for pageable memory the call waits until hip_stream has reached
+ * its table copy, as the training-mix calls do); a batch has one table buffer and one loader scratch, so issue these calls of one
+ * batch on one stream.  The twiddles are the host libm's cos and sin, built on the first call and owned by the batch.  -1 with
+ * nothing enqueued: a NULL argument, n_frames < 1, n_rirs < 1 or a length outside [1, 32768] (load), a failed check, work_bytes
+ * below one unit, a buffer that is not 16-byte aligned.  The calls read and write no per-stream state and ignore every table of the
+ * batch.  Cost: DESIGN.md section 4.21. */
+typedef struct RNNoiseTrainRir {
+  int rir_id, clip, quantize;
+} RNNoiseTrainRir;
+RNNOISE_EXPORT int rnnoise_amd_train_rir_check(const RNNoiseTrainRir *rir, int n_seq, int n_rirs);
+RNNOISE_EXPORT long long rnnoise_amd_train_rir_work_bytes(long long n_units);
+RNNOISE_EXPORT int rnnoise_batch_train_rir_load_device(RNNoiseBatch *b, float *d_spectra, const float *d_rir, const int *lens,
+                                                       int n_rirs, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_train_rir_device(RNNoiseBatch *b, float *d_clean, float *d_noisy, const float *d_spectra,
+                                                  int n_rirs, const RNNoiseTrainRir *rir, void *d_work, long long work_bytes,
+                                                  int n_frames, void *hip_stream);
 
 /* Test taps for the last processed frame step: per-stream feature vectors [N][65],
  * silence flags [N] and final pitch periods [N] (host buffers, any may be NULL). */

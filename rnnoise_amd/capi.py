@@ -63,6 +63,8 @@ EXPORTS = [
     "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
     "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
     "rnnoise_amd_train_mix_check", "rnnoise_batch_train_levels_device", "rnnoise_amd_train_vad", "rnnoise_batch_train_mix_device",
+    "rnnoise_amd_train_rir_check", "rnnoise_amd_train_rir_work_bytes", "rnnoise_batch_train_rir_load_device",
+    "rnnoise_batch_train_rir_device",
 ]
 
 
@@ -75,6 +77,16 @@ class TrainMix(C.Structure):
 
 
 MIX_DTYPE = np.dtype(TrainMix)
+
+
+class TrainRir(C.Structure):
+    """RNNoiseTrainRir (include/rnnoise_amd.h): one sequence's room impulse response (-1: none) and its augmentation flags"""
+    _fields_ = [("rir_id", C.c_int), ("clip", C.c_int), ("quantize", C.c_int)]
+
+
+RIR_DTYPE = np.dtype(TrainRir)
+RIR_MAX = 32768  # the samples of a room impulse response that count (RIR_MAX_DURATION); a row of d_rir
+RIR_FFT = 65536  # complex points of a spectrum
 MAX_CHANNELS = 8  # RNNOISE_AMD_MAX_CHANNELS: interleaved channels of a batch's PCM rows
 MAX_MODELS = 8  # RNNOISE_AMD_MAX_MODELS: model slots of a batch
 PCM_RATES = (48000, 24000, 16000, 8000)  # the rates that divide 48 kHz: code = divisor
@@ -241,6 +253,11 @@ def _load(path, debug):
         L.rnnoise_batch_train_levels_device.argtypes = [vp] * 6 + [ll, ll, ll, vp, C.c_int, vp]
         L.rnnoise_amd_train_vad.argtypes = [fp, C.c_int, C.c_int, ip, up]
         L.rnnoise_batch_train_mix_device.argtypes = [vp] * 8 + [ll, ll, ll, vp, vp, vp, C.c_int, vp]
+        L.rnnoise_amd_train_rir_check.argtypes = [vp, C.c_int, C.c_int]
+        L.rnnoise_amd_train_rir_work_bytes.restype = ll
+        L.rnnoise_amd_train_rir_work_bytes.argtypes = [ll]
+        L.rnnoise_batch_train_rir_load_device.argtypes = [vp, vp, vp, ip, C.c_int, vp]
+        L.rnnoise_batch_train_rir_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, ll, C.c_int, vp]
         if debug:
             L.rnnoise_batch_debug_pitch.argtypes = [vp, fp]
             L.rnnoise_amd_debug_log_energy.argtypes = [C.c_int, fp, fp, C.c_int]
@@ -307,6 +324,24 @@ def train_vad(energy, start_pos=None):
                                    vad.ctypes.data_as(C.POINTER(C.c_ubyte))):
         raise ValueError("rnnoise_amd_train_vad failed")
     return vad
+
+
+def _rir_table(rir):
+    """a table of RNNoiseTrainRir records as one contiguous array of RIR_DTYPE"""
+    rir = np.ascontiguousarray(rir, RIR_DTYPE)
+    assert rir.ndim == 1, rir.shape
+    return rir
+
+
+def train_rir_check(rir, n_rirs: int) -> bool:
+    """rnnoise_amd_train_rir_check: whether every rir_id of the table lies in [-1, n_rirs) and the flags are 0 or 1.  Host only."""
+    rir = _rir_table(rir)
+    return bool(lib().rnnoise_amd_train_rir_check(rir.ctypes.data, len(rir), int(n_rirs)))
+
+
+def train_rir_work_bytes(n_units: int) -> int:
+    """rnnoise_amd_train_rir_work_bytes: the workspace of train_rir_device for n_units transform pairs in flight.  Host only."""
+    return int(lib().rnnoise_amd_train_rir_work_bytes(int(n_units)))
 
 
 def _close_quietly(obj):
@@ -793,6 +828,26 @@ class Batch:
                                                   *[p or None for p in d_corpora], *[int(v) for v in lens], mix.ctypes.data,
                                                   d_rms or None, d_vad or None, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_train_mix_device failed (a sequence outside its corpus, a non-finite gain?)")
+
+    def train_rir_load_device(self, d_spectra: int, d_rir: int, lens, stream: int = 0):
+        """Raw device pointers (ints), asynchronous on `stream`: d_rir [len(lens)][RIR_MAX] float32, of which the first lens[r] samples
+        count -> d_spectra [len(lens)][2][RIR_FFT][2] float32, the whole and the early response of each (load_rir)."""
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert lens.ndim == 1, lens.shape
+        if self._L.rnnoise_batch_train_rir_load_device(self.h, d_spectra or None, d_rir or None, lens.ctypes.data_as(C.POINTER(C.c_int)),
+                                                       len(lens), stream or None):
+            raise RuntimeError("rnnoise_batch_train_rir_load_device failed (a length outside [1, 32768]?)")
+
+    def train_rir_device(self, d_clean: int, d_noisy: int, d_spectra: int, n_rirs: int, rir, d_work: int, work_bytes: int,
+                         n_frames: int, stream: int = 0):
+        """Raw device pointers (ints), asynchronous on `stream`: filters d_clean and d_noisy [n_frames][N][480] float32 in place with
+        the spectra train_rir_load_device made, then clips and quantises d_noisy; rir: a host table of N RIR_DTYPE records; d_work:
+        work_bytes of scratch (train_rir_work_bytes)."""
+        rir = _rir_table(rir)
+        assert len(rir) == self.n, (len(rir), self.n)
+        if self._L.rnnoise_batch_train_rir_device(self.h, d_clean or None, d_noisy or None, d_spectra or None, int(n_rirs),
+                                                  rir.ctypes.data, d_work or None, int(work_bytes), n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_train_rir_device failed (a rir_id outside the list, a workspace below one unit?)")
 
     def train_features_device(self, d_records: int, d_clean: int, d_noisy: int, d_vad: int, d_lowpass: int, d_band_lp: int,
                               d_noise_free: int, n_frames: int, stream: int = 0):

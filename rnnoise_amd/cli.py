@@ -19,10 +19,12 @@ An input that starts with RIFF....WAVE is read as a WAV file (rnnoise_amd/wav.py
 its rate, format and channel count come from its header, each channel is one stream, its samples cross the batch interleaved as they lie
 in the file (rnnoise_batch_set_pcm_channels), and the output is <name>.denoised.wav with the input's header fields.
 
-Training data (the reference's src/dump_features.c without its RIR option; rnnoise_amd/train_data.py): COUNT sequences of 98-float
-records from three RAW s16 48 kHz mono corpora, each uploaded once, everything else on the device:
+Training data (the reference's src/dump_features.c; rnnoise_amd/train_data.py): COUNT sequences of 98-float records from three RAW
+s16 48 kHz mono corpora, each uploaded once, everything else on the device:
 
   python -m rnnoise_amd.cli dump-features --model weights_blob.bin speech.pcm noise.pcm fgnoise.pcm out.f32 COUNT
+--rir-list FILE is the reference's -rir_list: FILE names one room impulse response per line (raw float32 at 48 kHz, of which the first
+32768 samples count); half of the sequences are filtered with one of them before clipping and quantisation.
 """
 from __future__ import annotations
 
@@ -166,20 +168,29 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
 
 
 def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out: str, count: int, seed=None, seq_frames: int = 2000,
-                  streams: int = 64, device: int = 0):
+                  streams: int = 64, device: int = 0, rir_list=None, rir_work_mb: int = 256):
     """COUNT training sequences of seq_frames frames into `out` (float32 records, sequence after sequence: the reference's file
     format): sequence i runs on stream i % streams of one batch in round i // streams.  Each corpus is read and uploaded once.  The
-    draws come from numpy's default generator seeded with `seed` (train_data.draw)."""
+    draws come from numpy's default generator seeded with `seed` (train_data.draw, then train_data.draw_rir from the same generator
+    when rir_list names a file of RIR file names)."""
     import torch
 
     from . import train_data
     dev = torch.device("cuda", device)
     corpora = [torch.from_numpy(np.fromfile(p, dtype=np.int16)).to(dev) for p in (speech, noise, fgnoise)]
-    draws = train_data.draw(np.random.default_rng(seed), count, [c.numel() for c in corpora], seq_frames)
+    rng = np.random.default_rng(seed)
+    draws = train_data.draw(rng, count, [c.numel() for c in corpora], seq_frames)
     model = capi.Model(model_blob)
     batch = capi.Batch(model, max(1, min(streams, count)), device=device)
+    rirs = None
+    if rir_list:
+        with open(rir_list) as f:
+            names = [line.rstrip("\n") for line in f if line.rstrip("\n")]
+        responses = [np.fromfile(name, dtype=np.float32, count=capi.RIR_MAX) for name in names]
+        with torch.cuda.device(dev):
+            rirs = (train_data.rir_spectra(batch, responses, dev), train_data.draw_rir(rng, count, len(responses)))
     with torch.cuda.device(dev), open(out, "wb") as f:
-        for rec in train_data.generate_rounds(batch, *corpora, draws, seq_frames):
+        for rec in train_data.generate_rounds(batch, *corpora, draws, seq_frames, rirs, rir_work_mb << 20):
             f.write(rec.tobytes())
     batch.close()
     model.close()
@@ -211,6 +222,8 @@ def main(argv=None):
     p.add_argument("--seq-frames", type=int, default=2000, help="frames per sequence (the reference: 2000)")
     p.add_argument("--streams", type=int, default=64, help="sequences per round: the batch size")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--rir-list", default=None, help="file of RIR file names, one per line (raw float32): the reference's -rir_list")
+    p.add_argument("--rir-work-mb", type=int, default=256, help="workspace of the RIR filter in MiB, at least 1")
     p.add_argument("speech")
     p.add_argument("noise")
     p.add_argument("fgnoise")
@@ -219,7 +232,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.cmd == "dump-features":
         n = dump_features(open(a.model, "rb").read(), a.speech, a.noise, a.fgnoise, a.out, a.count, a.seed, a.seq_frames, a.streams,
-                          a.device)
+                          a.device, a.rir_list, a.rir_work_mb)
         print(f"wrote {a.count} sequences, {n} records")
         return
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,

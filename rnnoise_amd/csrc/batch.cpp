@@ -170,6 +170,8 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->model_map) hipFree(b->model_map);
   if (b->ctl_buf) hipFree(b->ctl_buf);
   if (b->train_mix_buf) hipFree(b->train_mix_buf);
+  if (b->train_rir_tw) hipFree(b->train_rir_tw);
+  if (b->train_rir_buf) hipFree(b->train_rir_buf);
   if (b->debug_buf) hipFree(b->debug_buf);
   if (b->side) hipStreamDestroy(b->side);
   if (b->side_hp) {

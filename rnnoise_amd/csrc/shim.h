@@ -9,6 +9,7 @@
 //   batch_tables.cpp  a batch's configuration: PCM rate, strides, channels, the per-stream tables (rates, formats, models, controls)
 //   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
 //   train_mix.hip     training sequences: levels, Viterbi VAD and mix of src/dump_features.c:408-465, host code and kernels
+//   train_rir.hip     training sequences: the RIR filtering of src/dump_features.c:51-144, :449-465, host code and kernels
 //   host_io.cpp  host-fed calls: the pinned frame ring, the bounce chunks of pageable callers
 //   dropin.cpp   the reference's own API (include/rnnoise.h): state pools, the combiner of concurrent one-frame calls
 #pragma once
@@ -228,6 +229,9 @@ struct RNNoiseBatch {
   float *ctl_buf = nullptr;
   // the [N] RNNoiseTrainMix table of the last training-mix call (train_mix.hip), allocated on first use
   void *train_mix_buf = nullptr;
+  // train_rir.hip, both allocated on first use: the 65,536 twiddles followed by one transform of scratch for the RIR loader; the [N]
+  // RNNoiseTrainRir records of the last filter call followed by its list of filtered sequences
+  void *train_rir_tw = nullptr, *train_rir_buf = nullptr;
   // side stream + events: in multi-frame calls the (latency-bound, 1 lane per stream) high-pass of frame
   // f+1 runs beside analysis/network/synthesis of frame f
   hipStream_t side = nullptr, side_hp = nullptr;

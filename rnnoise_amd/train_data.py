@@ -3,10 +3,12 @@ RNNoiseTrainMix).  draw() makes the random choices of dump_features.c:367-406 an
 from the int16 corpora to the 98-float records on the device, one sequence per stream of a batch and round:
 
     levels (rnnoise_batch_train_levels_device) -> energies to the host -> Viterbi VAD (rnnoise_amd_train_vad) ->
-    mix (rnnoise_batch_train_mix_device) -> features (rnnoise_batch_train_features_device)
+    mix (rnnoise_batch_train_mix_device) [-> RIR (rnnoise_batch_train_rir_device)] -> features (rnnoise_batch_train_features_device)
 
-For the same draws the records are bit for bit the reference's (without its optional RIR filtering).  draw() follows the reference's
-distributions, not glibc's rand() stream.
+For the same draws the records are bit for bit the reference's.  Its optional RIR filtering (-rir_list) is the bracketed step:
+rir_spectra() transforms a list of room impulse responses once, draw_rir() makes the choices of dump_features.c:449-450, and
+generate(..., rirs=(spectra, records)) filters between mix and clip.  draw() and draw_rir() follow the reference's distributions, not
+glibc's rand() stream.
 """
 from __future__ import annotations
 
@@ -103,12 +105,46 @@ def draw(rng: np.random.Generator, n: int, lens, n_frames: int, band_lp: int = N
     return Draws(mix, start_pos, lowpass, bands)
 
 
+def draw_rir(rng: np.random.Generator, n: int, n_rirs: int) -> np.ndarray:
+    """dump_features.c:449-450 for n sequences: a room impulse response is applied with probability 1/2, and then it is one of the
+    n_rirs of the list, each as likely -> (n,) capi.RIR_DTYPE with rir_id = -1 where none is applied.  The uniform numbers are this
+    function's own rng.random((n, 2)); draw() takes none of them.  clip and quantize stay 0 here: generate() fills them in from
+    the mix table of draw()."""
+    if n_rirs < 1:
+        raise ValueError("an empty RIR list")
+    u = np.asarray(rng.random((n, 2)), np.float64)
+    assert u.shape == (n, 2)
+    rec = np.zeros(n, capi.RIR_DTYPE)
+    rec["rir_id"] = np.where(u[:, 0] < .5, np.minimum((u[:, 1] * n_rirs).astype(np.int64), n_rirs - 1), -1)
+    return rec
+
+
+def rir_spectra(batch: capi.Batch, responses, device):
+    """load_rir (dump_features.c:63-88) for a list of room impulse responses, 1-D float arrays of which the first 32768 samples count
+    -> the (len(responses), 2, 65536, 2) float32 torch tensor on `device` that generate(rirs=...) takes: per response the spectrum of
+    the whole one (for the noisy signal) and of its early part (for the clean signal)."""
+    import torch
+    rows = np.zeros((len(responses), capi.RIR_MAX), np.float32)
+    lens = np.empty(len(responses), np.int32)
+    for i, h in enumerate(responses):
+        h = np.asarray(h, np.float32).ravel()[:capi.RIR_MAX]
+        if len(h) < 1:
+            raise ValueError(f"room impulse response {i} is empty")
+        rows[i, :len(h)], lens[i] = h, len(h)
+    d_rows = torch.from_numpy(rows).to(device)
+    spectra = torch.empty((len(responses), 2, capi.RIR_FFT, 2), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        batch.train_rir_load_device(spectra.data_ptr(), d_rows.data_ptr(), lens, torch.cuda.current_stream(device).cuda_stream)
+        torch.cuda.current_stream(device).synchronize()  # (d_rows dies here)
+    return spectra
+
+
 def _pad(a, n):
     """a round's table for a batch of n streams: the streams behind the last sequence repeat it (their records are dropped)"""
     return a if len(a) == n else np.concatenate([a, np.repeat(a[-1:], n - len(a), 0)])
 
 
-def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int):
+def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20):
     """Yields the records of sequences [r * N, (r + 1) * N) of `draws`, r = 0, 1, ..., each a (sequences, n_frames, 98) float32 array:
     sequence i runs on stream i % N of `batch` (N streams) in round i // N, and the batch's per-stream analysis state carries from one
     sequence of a stream to the next, as the reference's two DenoiseStates carry across its loop.  speech, noise, fgnoise: the corpora
@@ -116,7 +152,11 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
     round is the Viterbi VAD on the frame energies.  When the last round is partial, the streams behind the last sequence run that
     sequence again (records dropped), so their analysis state advances too: a later call on the same batch starts those streams from
     a state that no sequence of the file order left.  Reset the batch, or use a sequence count that is a multiple of N, where that
-    matters; one run of the command line is not affected."""
+    matters; one run of the command line is not affected.
+    rirs = (spectra, records): the tensor of rir_spectra() and draw_rir()'s records, one per sequence of `draws`.  The mix then runs
+    without clipping and quantisation, and the RIR call filters the sequences the records name and applies the flags of `draws` to
+    all (dump_features.c:449-465), in a workspace of rir_work_bytes (at least capi.train_rir_work_bytes(1)).  Without rirs nothing
+    changes."""
     import torch
     N = batch.n
     corpora = (speech, noise, fgnoise)
@@ -130,10 +170,20 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
     vad_target, noise_free = new((n_frames, N)), new((N,), torch.int32)
     rec = new((n_frames, N, REC))
     count = len(draws.mix)
+    if rirs is not None:
+        spectra, rir_rec = rirs
+        assert spectra.dtype == torch.float32 and spectra.is_cuda and spectra.is_contiguous() and spectra.shape[1:] == (2, capi.RIR_FFT, 2)
+        assert len(rir_rec) == count, (len(rir_rec), count)
+        rir_rec = np.array(rir_rec, capi.RIR_DTYPE)
+        rir_rec["clip"], rir_rec["quantize"] = draws.mix["clip"], draws.mix["quantize"]
+        work = new((rir_work_bytes,), torch.uint8)
     for first in range(0, count, N):
         k = min(N, count - first)
         rows = slice(first, first + k)
         mix = _pad(draws.mix[rows], N)
+        if rirs is not None:
+            mix = mix.copy()
+            mix["clip"] = mix["quantize"] = 0
         st = torch.cuda.current_stream(dev).cuda_stream
         batch.train_levels_device(energy.data_ptr(), rms.data_ptr(), ptrs, lens, mix, n_frames, st)
         vad = capi.train_vad(energy.cpu().numpy(), _pad(draws.start_pos[rows], N))
@@ -142,11 +192,14 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
         d_band_lp = torch.from_numpy(_pad(draws.band_lp[rows], N).astype(np.int32)).to(dev)
         batch.train_mix_device(clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), noise_free.data_ptr(), ptrs, lens, mix,
                                rms.data_ptr(), d_vad.data_ptr(), n_frames, st)
+        if rirs is not None:
+            batch.train_rir_device(clean.data_ptr(), noisy.data_ptr(), spectra.data_ptr(), len(spectra), _pad(rir_rec[rows], N),
+                                   work.data_ptr(), rir_work_bytes, n_frames, st)
         batch.train_features_device(rec.data_ptr(), clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), d_lowpass.data_ptr(),
                                     d_band_lp.data_ptr(), noise_free.data_ptr(), n_frames, st)
         yield rec.permute(1, 0, 2)[:k].contiguous().cpu().numpy()  # sequence-major: the reference's file order
 
 
-def generate(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int) -> np.ndarray:
+def generate(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20) -> np.ndarray:
     """all records of `draws`, (sequences, n_frames, 98) float32 in sequence order (generate_rounds)"""
-    return np.concatenate(list(generate_rounds(batch, speech, noise, fgnoise, draws, n_frames)))
+    return np.concatenate(list(generate_rounds(batch, speech, noise, fgnoise, draws, n_frames, rirs, rir_work_bytes)))
