@@ -10,6 +10,7 @@
 //   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
 //   train_mix.hip     training sequences: levels, Viterbi VAD and mix of src/dump_features.c:408-465, host code and kernels
 //   train_rir.hip     training sequences: the RIR filtering of src/dump_features.c:51-144, :449-465, host code and kernels
+//   train_common.h    what those two share: the upload into a batch-owned buffer, argument tests, the device clip-and-quantise
 //   host_io.cpp  host-fed calls: the pinned frame ring, the bounce chunks of pageable callers
 //   dropin.cpp   the reference's own API (include/rnnoise.h): state pools, the combiner of concurrent one-frame calls
 #pragma once

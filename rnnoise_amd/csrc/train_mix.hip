@@ -10,9 +10,9 @@
 // row's end).  The mix kernel hands each chunk through LDS to all 192 threads, which add the three signals and store runs of 32
 // floats per sequence as float4.
 //
-// tests/csrc/train_mix_emul compiles THIS FILE as host C++ against a stand-in for shim.h (tests/test_train_mix_cpu.py, under the
-// address sanitizer): a HIP call, a builtin or a member of RNNoiseBatch that this file starts to use needs its counterpart there.
-#include "shim.h"
+// tests/csrc/hip_emul compiles THIS FILE as host C++ against a stand-in for shim.h (tests/test_train_mix_cpu.py, under the address
+// sanitizer): a HIP call, a builtin or a member of RNNoiseBatch that this file starts to use needs its counterpart there.
+#include "train_common.h"
 
 #include <limits.h>
 
@@ -181,13 +181,7 @@ __device__ __forceinline__ void train_mix_body(const TrainMixArgs &a, MixLds *ld
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           cl[k] = xs[k];
-          float t = (xs[k] + ns[k]) + fs[k];                                // (:447)
-          if (fl & 1) {                                                     // MIN16(32767.f, MAX16(-32767.f, xn)) (:457)
-            t = -32767.f > t ? -32767.f : t;
-            t = 32767.f < t ? 32767.f : t;
-          }
-          if (fl & 2) t = floorf(.5f + t);                                  // (:463)
-          xn[k] = t;
+          xn[k] = clip_quantize((xs[k] + ns[k]) + fs[k], fl & 1, fl & 2);   // (:447, :457, :463)
         }
         const size_t at = (frame_base + s) * RN_FRAME_SIZE + fc * CH + j4;
         *reinterpret_cast<float4 *>(a.clean + at) = make_float4(cl[0], cl[1], cl[2], cl[3]);
@@ -219,7 +213,7 @@ __device__ __forceinline__ void train_mix_body(const TrainMixArgs &a, MixLds *ld
 
 }  // namespace
 
-// (the names of these two end in no "_kernel": tests/test_train_mix_cpu.py pins the kernels of this file by name)
+// (tests/test_product_surface_cpu.py and tests/test_kernel_budgets_cpu.py pin the kernels of this file by name)
 extern "C" __global__ __launch_bounds__(THREADS) void rn_train_levels(TrainMixArgs a) { train_mix_body<false>(a, nullptr); }
 
 extern "C" __global__ __launch_bounds__(THREADS) void rn_train_mix(TrainMixArgs a) {
@@ -241,7 +235,7 @@ extern "C" int rnnoise_amd_train_mix_check(const RNNoiseTrainMix *mix, int n_seq
                        p.a_noise[1], p.b_noise[0], p.b_noise[1], p.a_fgnoise[0], p.a_fgnoise[1], p.b_fgnoise[0], p.b_fgnoise[1]};
     for (float v : f)
       if (!isfinite(v)) return 0;
-    if ((p.clip != 0 && p.clip != 1) || (p.quantize != 0 && p.quantize != 1)) return 0;
+    if (!train_flag01(p.clip) || !train_flag01(p.quantize)) return 0;
   }
   return 1;
 }
@@ -320,15 +314,24 @@ extern "C" int rnnoise_amd_train_vad(const float *energy, int n_seq, int n_frame
 }
 
 namespace {
-// The table of a call on the device: into the batch's own buffer (allocated on first use), a copy ordered on the call's stream.
-// `mix` is the caller's pageable memory, which may die as soon as the call returns (capi.py hands in temporaries): the HIP runtime
-// makes a pageable host-to-device copy host-synchronous -- it returns when the copy has run, that is, when the stream has reached
-// it -- and the calls rely on that and say so in the header.  The kernels that follow stay asynchronous.  One buffer per batch: two
-// training-mix calls of one batch on different streams race on it (include/rnnoise_amd.h).
-int mix_table_upload(RNNoiseBatch *b, const RNNoiseTrainMix *mix, hipStream_t st) {
+// What both device calls do once their pointers are checked and their outputs are in `a`: the table checked and in the batch's
+// buffer (train_common.h), the arguments both kernels read, the launch.
+int mix_launch(void (*kernel)(TrainMixArgs), TrainMixArgs a, RNNoiseBatch *b, const short *d_speech, const short *d_noise,
+               const short *d_fgnoise, long long speech_len, long long noise_len, long long fgnoise_len, const RNNoiseTrainMix *mix,
+               int n_frames, void *hip_stream) {
+  if (!rnnoise_amd_train_mix_check(mix, b->n, speech_len, noise_len, fgnoise_len, n_frames)) return -1;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  ON_DEVICE(b->device);
   const size_t bytes = (size_t)b->n * sizeof(RNNoiseTrainMix);
-  if (!b->train_mix_buf) HIP_OK(hipMalloc((void **)&b->train_mix_buf, bytes));
-  HIP_OK(hipMemcpyAsync(b->train_mix_buf, mix, bytes, hipMemcpyHostToDevice, st));
+  if (train_upload(&b->train_mix_buf, bytes, mix, bytes, st)) return -1;
+  a.mix = static_cast<const RNNoiseTrainMix *>(b->train_mix_buf);
+  a.corpus[0] = d_speech;
+  a.corpus[1] = d_noise;
+  a.corpus[2] = d_fgnoise;
+  a.n_seq = b->n;
+  a.n_frames = n_frames;
+  hipLaunchKernelGGL(kernel, dim3((b->n + SEQS - 1) / SEQS), dim3(THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 }  // namespace
@@ -337,22 +340,10 @@ extern "C" int rnnoise_batch_train_levels_device(RNNoiseBatch *b, float *d_energ
                                                  const short *d_noise, const short *d_fgnoise, long long speech_len, long long noise_len,
                                                  long long fgnoise_len, const RNNoiseTrainMix *mix, int n_frames, void *hip_stream) {
   if (!b || !d_energy || !d_rms || !d_speech || !d_noise || !d_fgnoise || !mix || n_frames < 1) return -1;
-  if (!rnnoise_amd_train_mix_check(mix, b->n, speech_len, noise_len, fgnoise_len, n_frames)) return -1;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  ON_DEVICE(b->device);
-  if (mix_table_upload(b, mix, st)) return -1;
   TrainMixArgs a{};
-  a.mix = static_cast<const RNNoiseTrainMix *>(b->train_mix_buf);
-  a.corpus[0] = d_speech;
-  a.corpus[1] = d_noise;
-  a.corpus[2] = d_fgnoise;
-  a.n_seq = b->n;
-  a.n_frames = n_frames;
   a.energy = d_energy;
   a.rms_out = d_rms;
-  hipLaunchKernelGGL(rn_train_levels, dim3((b->n + SEQS - 1) / SEQS), dim3(THREADS), 0, st, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return mix_launch(rn_train_levels, a, b, d_speech, d_noise, d_fgnoise, speech_len, noise_len, fgnoise_len, mix, n_frames, hip_stream);
 }
 
 extern "C" int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clean, float *d_noisy, float *d_vad_target, int *d_noise_free,
@@ -362,25 +353,13 @@ extern "C" int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clean, f
   if (!b || !d_clean || !d_noisy || !d_vad_target || !d_noise_free || !d_speech || !d_noise || !d_fgnoise || !mix || !d_rms || !d_vad ||
       n_frames < 1)
     return -1;
-  if ((reinterpret_cast<uintptr_t>(d_clean) | reinterpret_cast<uintptr_t>(d_noisy)) & 15) return -1;  // (stored as float4)
-  if (!rnnoise_amd_train_mix_check(mix, b->n, speech_len, noise_len, fgnoise_len, n_frames)) return -1;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  ON_DEVICE(b->device);
-  if (mix_table_upload(b, mix, st)) return -1;
+  if (!aligned16(d_clean) || !aligned16(d_noisy)) return -1;  // (stored as float4)
   TrainMixArgs a{};
-  a.mix = static_cast<const RNNoiseTrainMix *>(b->train_mix_buf);
-  a.corpus[0] = d_speech;
-  a.corpus[1] = d_noise;
-  a.corpus[2] = d_fgnoise;
-  a.n_seq = b->n;
-  a.n_frames = n_frames;
   a.clean = d_clean;
   a.noisy = d_noisy;
   a.vad_target = d_vad_target;
   a.noise_free = d_noise_free;
   a.rms = d_rms;
   a.vad = d_vad;
-  hipLaunchKernelGGL(rn_train_mix, dim3((b->n + SEQS - 1) / SEQS), dim3(THREADS), 0, st, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return mix_launch(rn_train_mix, a, b, d_speech, d_noise, d_fgnoise, speech_len, noise_len, fgnoise_len, mix, n_frames, hip_stream);
 }

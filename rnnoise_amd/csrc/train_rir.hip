@@ -20,9 +20,9 @@
 //   rn_rir_inv2  pass 2, real part of the second half, clip, quantise            -> the frame layout
 // rn_rir_spec is the pass 2 that ends load_rir (natural order out), rn_rir_finish clips and quantises the unfiltered sequences.
 //
-// tests/csrc/train_rir_emul compiles THIS FILE as host C++ against a stand-in for shim.h (tests/test_train_rir_cpu.py, under the
-// address sanitizer): a HIP call, a builtin or a member of RNNoiseBatch that this file starts to use needs its counterpart there.
-#include "shim.h"
+// tests/csrc/hip_emul compiles THIS FILE as host C++ against a stand-in for shim.h (tests/test_train_rir_cpu.py, under the address
+// sanitizer): a HIP call, a builtin or a member of RNNoiseBatch that this file starts to use needs its counterpart there.
+#include "train_common.h"
 
 #include <limits.h>
 
@@ -154,19 +154,9 @@ __device__ __forceinline__ size_t frame_at(const RirArgs &a, int seq, unsigned s
   const unsigned f = s / RN_FRAME_SIZE;
   return ((size_t)f * a.n_seq + seq) * RN_FRAME_SIZE + (s - f * RN_FRAME_SIZE);
 }
-
-// MIN16(32767.f, MAX16(-32767.f, xn)) (src/dump_features.c:457), floor(.5f + xn) (:463)
-__device__ __forceinline__ float clip_quantize(float t, int clip, int quantize) {
-  if (clip) {
-    t = -32767.f > t ? -32767.f : t;
-    t = 32767.f < t ? 32767.f : t;
-  }
-  if (quantize) t = floorf(.5f + t);
-  return t;
-}
 }  // namespace
 
-// (no name here ends in "_kernel" or starts with "rn_train_": tests pin those sets)
+// (tests/test_product_surface_cpu.py and tests/test_kernel_budgets_cpu.py pin the kernels of this file by name)
 // grid: units * 16; LOAD: one RIR in one form (load_rir, :63-88), else a unit's [previous block | block]
 extern "C" __global__ __launch_bounds__(THREADS) void rn_rir_fwd1(RirArgs a) {
   __shared__ RirLds s;
@@ -277,7 +267,7 @@ extern "C" int rnnoise_amd_train_rir_check(const RNNoiseTrainRir *rir, int n_seq
   for (int s = 0; s < n_seq; s++) {
     const RNNoiseTrainRir &p = rir[s];
     if (p.rir_id < -1 || p.rir_id >= n_rirs) return 0;
-    if ((p.clip != 0 && p.clip != 1) || (p.quantize != 0 && p.quantize != 1)) return 0;
+    if (!train_flag01(p.clip) || !train_flag01(p.quantize)) return 0;
   }
   return 1;
 }
@@ -287,7 +277,6 @@ extern "C" long long rnnoise_amd_train_rir_work_bytes(long long n_units) { retur
 namespace {
 // The batch's twiddle table, followed by one transform of scratch for rnnoise_batch_train_rir_load_device: built on first use.
 // compute_twiddles (src/kiss_fft.c:406-421): the phase in double with the reference's literal of pi, cos and sin of the host's libm.
-// The table is pageable memory that dies here: a pageable host-to-device copy returns when it has run (train_mix.hip: mix_table_upload).
 int twiddles(RNNoiseBatch *b, hipStream_t st) {
   if (b->train_rir_tw) return 0;
   std::vector<float> tw(2 * (size_t)NFFT);
@@ -297,17 +286,21 @@ int twiddles(RNNoiseBatch *b, hipStream_t st) {
     tw[2 * i] = (float)cos(phase);
     tw[2 * i + 1] = (float)sin(phase);
   }
-  void *d = nullptr;
-  HIP_OK(hipMalloc(&d, 2 * (size_t)NFFT * sizeof(float2)));
-  if (hipMemcpyAsync(d, tw.data(), (size_t)NFFT * sizeof(float2), hipMemcpyHostToDevice, st) != 0) {
-    hipFree(d);
-    return -1;
-  }
-  b->train_rir_tw = d;
-  return 0;
+  return train_upload(&b->train_rir_tw, 2 * (size_t)NFFT * sizeof(float2), tw.data(), (size_t)NFFT * sizeof(float2), st);
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// What both device calls do around their launches: on the batch's device and the caller's stream, the twiddles in place and in `a`.
+template <typename Launches>
+int rir_call(RNNoiseBatch *b, void *hip_stream, Launches launches) {
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  ON_DEVICE(b->device);
+  if (twiddles(b, st)) return -1;
+  RirArgs a{};
+  a.tw = static_cast<const float2 *>(b->train_rir_tw);
+  if (launches(a, st)) return -1;
+  HIP_OK(hipGetLastError());
+  return 0;
+}
 }  // namespace
 
 extern "C" int rnnoise_batch_train_rir_load_device(RNNoiseBatch *b, float *d_spectra, const float *d_rir, const int *lens, int n_rirs,
@@ -316,23 +309,19 @@ extern "C" int rnnoise_batch_train_rir_load_device(RNNoiseBatch *b, float *d_spe
   if (!aligned16(d_spectra) || !aligned16(d_rir)) return -1;
   for (int r = 0; r < n_rirs; r++)
     if (lens[r] < 1 || lens[r] > RIR_MAX) return -1;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  ON_DEVICE(b->device);
-  if (twiddles(b, st)) return -1;
-  RirArgs a{};
-  a.tw = static_cast<const float2 *>(b->train_rir_tw);
-  a.work = static_cast<float2 *>(b->train_rir_tw) + NFFT;  // (one transform at a time: the launches of a stream run in order)
-  for (int r = 0; r < n_rirs; r++)
-    for (int early = 0; early < 2; early++) {
-      a.rir = d_rir + (size_t)r * RIR_MAX;
-      a.len = lens[r];
-      a.early = early;
-      a.spec_out = reinterpret_cast<float2 *>(d_spectra) + ((size_t)r * 2 + early) * NFFT;
-      hipLaunchKernelGGL(rn_rir_fwd1, dim3(TILES), dim3(THREADS), 0, st, a);
-      hipLaunchKernelGGL(rn_rir_spec, dim3(TILES), dim3(THREADS), 0, st, a);
-    }
-  HIP_OK(hipGetLastError());
-  return 0;
+  return rir_call(b, hip_stream, [&](RirArgs &a, hipStream_t st) {
+    a.work = static_cast<float2 *>(b->train_rir_tw) + NFFT;  // (one transform at a time: the launches of a stream run in order)
+    for (int r = 0; r < n_rirs; r++)
+      for (int early = 0; early < 2; early++) {
+        a.rir = d_rir + (size_t)r * RIR_MAX;
+        a.len = lens[r];
+        a.early = early;
+        a.spec_out = reinterpret_cast<float2 *>(d_spectra) + ((size_t)r * 2 + early) * NFFT;
+        hipLaunchKernelGGL(rn_rir_fwd1, dim3(TILES), dim3(THREADS), 0, st, a);
+        hipLaunchKernelGGL(rn_rir_spec, dim3(TILES), dim3(THREADS), 0, st, a);
+      }
+    return 0;
+  });
 }
 
 extern "C" int rnnoise_batch_train_rir_device(RNNoiseBatch *b, float *d_clean, float *d_noisy, const float *d_spectra, int n_rirs,
@@ -342,7 +331,7 @@ extern "C" int rnnoise_batch_train_rir_device(RNNoiseBatch *b, float *d_clean, f
   if (n_frames < 1 || n_frames > (INT_MAX - NFFT) / RN_FRAME_SIZE || work_bytes < (long long)UNIT_BYTES) return -1;
   if (!aligned16(d_clean) || !aligned16(d_noisy) || !aligned16(d_spectra) || !aligned16(d_work)) return -1;
   if (!rnnoise_amd_train_rir_check(rir, b->n, n_rirs)) return -1;
-  // the records and the list of filtered sequences, in one buffer of the batch and one copy (train_mix.hip: mix_table_upload)
+  // the records and the list of filtered sequences, in one buffer of the batch and one copy
   const int n = b->n;
   std::vector<int> table(4 * (size_t)n);
   memcpy(table.data(), rir, sizeof(RNNoiseTrainRir) * n);
@@ -354,34 +343,30 @@ extern "C" int rnnoise_batch_train_rir_device(RNNoiseBatch *b, float *d_clean, f
   const int n_blocks = (int)(((long long)n_frames * RN_FRAME_SIZE + HALF - 1) / HALF);
   const long long units = (long long)n_blocks * 2 * n_filtered;
   if (units > INT_MAX || (long long)n_frames * n > INT_MAX) return -1;  // (a unit index and the grid of rn_rir_finish are ints)
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  ON_DEVICE(b->device);
-  if (twiddles(b, st)) return -1;
-  if (!b->train_rir_buf) HIP_OK(hipMalloc((void **)&b->train_rir_buf, table.size() * sizeof(int)));
-  HIP_OK(hipMemcpyAsync(b->train_rir_buf, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  RirArgs a{};
-  a.tw = static_cast<const float2 *>(b->train_rir_tw);
-  a.work = static_cast<float2 *>(d_work);
-  a.rec = static_cast<const RNNoiseTrainRir *>(b->train_rir_buf);
-  a.fseq = static_cast<const int *>(b->train_rir_buf) + 3 * (size_t)n;
-  a.spectra = reinterpret_cast<const float2 *>(d_spectra);
-  a.clean = d_clean;
-  a.noisy = d_noisy;
-  a.n_seq = n;
-  a.n_frames = n_frames;
-  a.n_filtered = n_filtered;
-  a.n_blocks = n_blocks;
-  if (finish) hipLaunchKernelGGL(rn_rir_finish, dim3((unsigned)n_frames * n), dim3(128), 0, st, a);
-  // Slabs of as many units as the workspace holds, blocks descending: a slab's loads (fwd1) all precede its stores (inv2), and a
-  // later slab reads only blocks that no earlier one wrote for the same signal.
-  const long long slab = std::min<long long>(work_bytes / (long long)UNIT_BYTES, INT_MAX / TILES);
-  for (long long u0 = 0; u0 < units; u0 += slab) {
-    const unsigned grid = (unsigned)(std::min(slab, units - u0) * TILES);
-    a.unit0 = (int)u0;
-    hipLaunchKernelGGL(rn_rir_fwd1, dim3(grid), dim3(THREADS), 0, st, a);
-    hipLaunchKernelGGL(rn_rir_mid, dim3(grid), dim3(THREADS), 0, st, a);
-    hipLaunchKernelGGL(rn_rir_inv2, dim3(grid), dim3(THREADS), 0, st, a);
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
+  return rir_call(b, hip_stream, [&](RirArgs &a, hipStream_t st) {
+    const size_t bytes = table.size() * sizeof(int);
+    if (train_upload(&b->train_rir_buf, bytes, table.data(), bytes, st)) return -1;
+    a.work = static_cast<float2 *>(d_work);
+    a.rec = static_cast<const RNNoiseTrainRir *>(b->train_rir_buf);
+    a.fseq = static_cast<const int *>(b->train_rir_buf) + 3 * (size_t)n;
+    a.spectra = reinterpret_cast<const float2 *>(d_spectra);
+    a.clean = d_clean;
+    a.noisy = d_noisy;
+    a.n_seq = n;
+    a.n_frames = n_frames;
+    a.n_filtered = n_filtered;
+    a.n_blocks = n_blocks;
+    if (finish) hipLaunchKernelGGL(rn_rir_finish, dim3((unsigned)n_frames * n), dim3(128), 0, st, a);
+    // Slabs of as many units as the workspace holds, blocks descending: a slab's loads (fwd1) all precede its stores (inv2), and a
+    // later slab reads only blocks that no earlier one wrote for the same signal.
+    const long long slab = std::min<long long>(work_bytes / (long long)UNIT_BYTES, INT_MAX / TILES);
+    for (long long u0 = 0; u0 < units; u0 += slab) {
+      const unsigned grid = (unsigned)(std::min(slab, units - u0) * TILES);
+      a.unit0 = (int)u0;
+      hipLaunchKernelGGL(rn_rir_fwd1, dim3(grid), dim3(THREADS), 0, st, a);
+      hipLaunchKernelGGL(rn_rir_mid, dim3(grid), dim3(THREADS), 0, st, a);
+      hipLaunchKernelGGL(rn_rir_inv2, dim3(grid), dim3(THREADS), 0, st, a);
+    }
+    return 0;
+  });
 }

@@ -1,4 +1,4 @@
-// main.cpp -- the loops of rnnoise_amd/csrc/train_mix.hip on the host (shim.h beside this file), against tests/csrc/mix_oracle.c.  TEST
+// mix_main.cpp -- the loops of rnnoise_amd/csrc/train_mix.hip on the host (shim.h beside this file), against tests/csrc/mix_oracle.c.  TEST
 // INFRASTRUCTURE, a stand-alone program built with the address and undefined-behaviour sanitizers: every buffer is a heap block of its
 // exact size (the corpora at even and at odd addresses), so any access outside a corpus or an output is reported, and every output is
 // compared bit for bit.  Exit status 0: all equal.

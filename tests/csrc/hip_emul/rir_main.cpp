@@ -1,4 +1,4 @@
-// main.cpp -- the kernels of rnnoise_amd/csrc/train_rir.hip on the host (shim.h beside this file), against tests/csrc/rir_oracle.c.  TEST
+// rir_main.cpp -- the kernels of rnnoise_amd/csrc/train_rir.hip on the host (shim.h beside this file), against tests/csrc/rir_oracle.c.  TEST
 // INFRASTRUCTURE, a stand-alone program built with the address and undefined-behaviour sanitizers: every buffer is a heap block of its
 // exact size, so any access outside the frames, the spectra, the responses or the workspace is reported, and every output is compared
 // bit for bit.  The workspace holds one unit: every slab is one transform pair.  Exit status 0: all equal.

@@ -1,7 +1,8 @@
-// shim.h -- a host stand-in for rnnoise_amd/csrc/shim.h.  TEST INFRASTRUCTURE: tests/test_train_rir_cpu.py copies rnnoise_amd/csrc/train_rir.hip
-// next to this file and main.cpp and compiles the three as plain C++, so that the kernels' own source runs on the host: a workgroup is
-// as many host threads as the launch asks for around a std::barrier, which run the workgroups of a grid one after the other; device
-// memory is the heap.
+// shim.h -- a host stand-in for rnnoise_amd/csrc/shim.h and the HIP runtime.  TEST INFRASTRUCTURE: tests/train_support.py
+// (run_kernel_emul) copies a training unit -- rnnoise_amd/csrc/train_mix.hip or train_rir.hip -- and train_common.h next to this file
+// and the unit's main (mix_main.cpp, rir_main.cpp) and compiles them as plain C++, so that the kernels' own source runs on the host:
+// a workgroup is as many host threads as the launch asks for around a std::barrier, which run the workgroups of a grid one after the
+// other; device memory is the heap.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -23,13 +24,16 @@ struct Dim { unsigned x; };
 static thread_local Dim threadIdx, blockIdx;
 static std::barrier<> *g_bar;
 static inline void __syncthreads() { g_bar->arrive_and_wait(); }
+static inline uint32_t __builtin_amdgcn_alignbit(uint32_t hi, uint32_t lo, unsigned sh) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31)); }
+static inline unsigned __builtin_amdgcn_readfirstlane(unsigned v) { return v; }
+using std::min;
 struct float2 { float x, y; };
 static inline float2 make_float2(float a, float b) { return {a, b}; }
 struct alignas(16) float4 { float x, y, z, w; };
 static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
 typedef void *hipStream_t;
 struct dim3 { unsigned x; dim3(unsigned v) : x(v) {} };
-struct RNNoiseBatch { int n, device; void *train_rir_tw = nullptr, *train_rir_buf = nullptr; };
+struct RNNoiseBatch { int n, device; void *train_mix_buf = nullptr, *train_rir_tw = nullptr, *train_rir_buf = nullptr; };
 #define ON_DEVICE(d)
 #define HIP_OK(e) do { if (e) return -1; } while (0)
 static inline int hipMalloc(void **p, size_t n) { *p = malloc(n); return 0; }

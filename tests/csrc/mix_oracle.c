@@ -1,6 +1,6 @@
 /* mix_oracle.c -- the mixing stage of training-data generation (include/rnnoise_amd.h: RNNoiseTrainMix) restated in plain C for
  * explicit parameters and any number of frames.  TEST INFRASTRUCTURE: compiled by tests/mix_oracle.py (gcc -O2 -ffp-contract=off)
- * into a library of its own; tests/test_train_mix_cpu.py holds it to the reference's own functions (tests/csrc/ref_mix_harness.c).
+ * into a library of its own; tests/test_train_mix_cpu.py holds it to the reference's own functions (tests/csrc/ref_dump_harness.c).
  *
  * What it restates, with the types of every intermediate as C gives them to the reference's expressions:
  *   mixo_biquad        rnn_biquad, src/denoise.c:409-419

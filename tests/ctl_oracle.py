@@ -1,14 +1,13 @@
 """The oracle of the per-stream suppression controls (tests/csrc/ctl_oracle.c: rno_process_frame_ctl): built once per process with the
-flags of oracle/Makefile's liboracle.so, bound by ctypes.  TEST INFRASTRUCTURE."""
+flags of oracle/Makefile's liboracle.so (train_support.c_library), bound by ctypes.  TEST INFRASTRUCTURE."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import binding
 from oracle.binding import FRAME, NB_BANDS, STATE_FLOATS, Record
+from train_support import c_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "csrc", "ctl_oracle.c")
@@ -23,10 +22,7 @@ def _fp(a):
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="ctl_oracle"), "libctl_oracle.so")
-        subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-I", os.path.join(ROOT, "oracle"),
-                        "-I", os.path.join(ROOT, "rnnoise_amd", "csrc"), "-o", so, SRC, "-lm"], check=True)
-        L = C.CDLL(so)
+        L = c_library(SRC, [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "rnnoise_amd", "csrc")], ["-mfma"])
         fp = C.POINTER(C.c_float)
         L.rno_model_from_blob.restype = C.c_void_p
         L.rno_model_from_blob.argtypes = [C.c_char_p, C.c_int]

@@ -1,14 +1,13 @@
-"""The oracle of the training-mix calls (tests/csrc/mix_oracle.c): built once per process with gcc -O2 -ffp-contract=off, bound by
+"""The oracle of the training-mix calls (tests/csrc/mix_oracle.c): built once per process (train_support.c_library), bound by
 ctypes.  TEST INFRASTRUCTURE.  sequence() runs one sequence through levels, VAD and mix; batch() lays the sequences of a table out as
 the device calls do."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from rnnoise_amd import capi
+from train_support import c_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "csrc", "mix_oracle.c")
@@ -23,10 +22,7 @@ def _p(a, t):
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="mix_oracle"), "libmix_oracle.so")
-        subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", so, SRC,
-                        "-lm"], check=True)
-        L = C.CDLL(so)
+        L = c_library(SRC, [os.path.join(ROOT, "include")], ["-Wall"])
         fp, ip, sp, up, vp = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_short), C.POINTER(C.c_ubyte), C.c_void_p
         L.mixo_biquad.argtypes = [fp, fp, fp, fp, fp, C.c_int]
         L.mixo_weighted_rms.argtypes = [fp, C.c_int]

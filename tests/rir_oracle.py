@@ -1,13 +1,13 @@
-"""The oracle of the RIR calls (tests/csrc/rir_oracle.c): built once per process with gcc -O2 -ffp-contract=off, bound by ctypes.  TEST
+"""The oracle of the RIR calls (tests/csrc/rir_oracle.c): built once per process (train_support.c_library), bound by ctypes.  TEST
 INFRASTRUCTURE.  load() is load_rir from memory, filter() rir_filter_sequence for any number of frames; batch() applies a table of
 capi.RIR_DTYPE records to frames in the layout of the device calls.  signal() and responses() are the seeded inputs the CPU and the
 GPU tests share."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+from train_support import c_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "csrc", "rir_oracle.c")
@@ -25,9 +25,7 @@ def _fp(a):
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="rir_oracle"), "librir_oracle.so")
-        subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-o", so, SRC, "-lm"], check=True)
-        L = C.CDLL(so)
+        L = c_library(SRC, flags=["-Wall"])
         fp = C.POINTER(C.c_float)
         L.riro_twiddles.argtypes = [fp]
         L.riro_bitrev.argtypes = [C.POINTER(C.c_int)]

@@ -12,6 +12,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 BUILD = os.path.join(ROOT, "rnnoise_amd", "csrc", "build")
+# the training units: every kernel of each object, by name.  train_rir.hip: 40 KiB of LDS per workgroup of four waves -- four
+# workgroups per CU, four waves per SIMD, 512 / 4 registers each; train_mix.hip: three waves per workgroup under the same cap
+TRAIN_KERNELS = {"train_mix": {"rn_train_levels", "rn_train_mix"},
+                 "train_rir": {"rn_rir_fwd1", "rn_rir_spec", "rn_rir_mid", "rn_rir_inv2", "rn_rir_finish"}}
+TRAIN_VGPR_CAP = 128
 
 
 def _code_object(obj, td):
@@ -44,7 +49,7 @@ def _kernels(obj):
 
 @pytest.fixture(scope="module")
 def built():
-    objs = {n: os.path.join(BUILD, n + ".o") for n in ("dsp_kernels", "hp_kernel", "nn_layers", "nn_kernels", "nn_mfma")}
+    objs = {n: os.path.join(BUILD, n + ".o") for n in ("dsp_kernels", "hp_kernel", "nn_layers", "nn_kernels", "nn_mfma", *TRAIN_KERNELS)}
     if not all(os.path.exists(p) for p in objs.values()):
         pytest.skip("kernels not built (python -c 'import __graft_entry__ as g; g.build()')")
     return {n: _kernels(p) for n, p in objs.items()}
@@ -67,6 +72,11 @@ def test_register_budgets(built):
     one, _ = built["nn_kernels"]
     # (its 14-wave workgroup caps it at 128 VGPRs; round 5: 5 -> 1 spilled dword, a quad's LDS address that is reloaded once per layer)
     assert one["rn_nn_one_kernel"]["vgpr_spill_count"] <= 1
+    for obj, names in TRAIN_KERNELS.items():
+        meta, _ = built[obj]
+        assert set(meta) == names, (obj, sorted(meta))
+        for k, m in meta.items():
+            assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["vgpr_count"] <= TRAIN_VGPR_CAP, (k, m)
 
 
 def test_no_flat_or_scratch_memory_instructions_in_the_hot_kernels(built):
@@ -82,6 +92,10 @@ def test_no_flat_or_scratch_memory_instructions_in_the_hot_kernels(built):
             assert len(ins) > 200, (k, len(ins))
             bad = [i for i in ins if i.startswith(("flat_load", "flat_store", "scratch_"))]
             assert not bad, (k, bad[:5])
+    for obj, names in TRAIN_KERNELS.items():   # (rn_rir_finish is short: no length asked of these)
+        _, code = built[obj]
+        for k in names:
+            assert code[k] and not [i for i in code[k] if i.startswith(("scratch_", "flat_"))], k
     _, code = built["dsp_kernels"]
     assert sum(i.startswith("s_barrier") for i in code["rn_analysis_kernel"]) == 6  # the workgroup barriers of the narrow phases
 

@@ -1,16 +1,14 @@
 """The training-mix calls without a GPU (include/rnnoise_amd.h: RNNoiseTrainMix; the reference's src/dump_features.c:408-465).
 
   a  tests/csrc/mix_oracle.c -- what the GPU tests compare against -- equals the reference's own rnn_biquad, weighted_rms, clear_vad
-     and viterbi_vad (tests/csrc/ref_mix_harness.c, compiled where the reference's sources are) on 2000-frame sequences
+     and viterbi_vad (tests/csrc/ref_dump_harness.c, compiled where the reference's sources are) on 2000-frame sequences
   b  rnnoise_amd_train_vad: the reference at 2000 frames, the oracle at other lengths, the start_pos rule
   c  rnnoise_amd_train_mix_check, the struct's layout, NULL arguments
   d  train_data.draw: ranges, branch frequencies, the band_lp carry-over
-  e  the kernels of train_mix.hip by name, without scratch or spills
-  f  the kernels' own source run on the host under the address sanitizer (tests/csrc/train_mix_emul), against the oracle"""
+  e  the kernels' own source run on the host under the address sanitizer (tests/csrc/hip_emul), against the oracle
+(the kernels of train_mix.hip by name, without scratch or spills: tests/test_product_surface_cpu.py, tests/test_kernel_budgets_cpu.py)"""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,10 +17,8 @@ import pytest
 import mix_oracle as mo
 from conftest import ROOT, assert_bits_equal
 from rnnoise_amd import capi, train_data
+from train_support import T_REF, reference_dump_features, run_kernel_emul
 
-REF = os.environ.get("RNNOISE_REFERENCE", "/root/reference")
-GEN = os.path.join(ROOT, "oracle", "_ref", "gen_default")
-T_REF = 2000
 N_REF = T_REF * 480
 B_HP, A_HP = (-2, 1), (-1.99599, 0.99600)
 # one coefficient pair per branch of rand_filt (dump_features.c:159-178): none, a complex pair, two real roots
@@ -31,25 +27,10 @@ FILTERS = {"zero": (0.0, 0.0), "complex": (-2 * .55 * np.cos(.9), .55 * .55), "r
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    """the reference's functions (tests/csrc/ref_mix_harness.c), with the flags of its pinned build (oracle/Makefile: REF_CFLAGS)"""
-    if not os.path.isdir(os.path.join(REF, "src")):
-        pytest.skip("the reference's sources are not here")
-    if not os.path.exists(os.path.join(GEN, "rnnoise_data.h")):
-        pytest.skip("oracle/_ref/gen_default not built (python -c 'import __graft_entry__ as g; g.build()')")
-    so = str(tmp_path_factory.mktemp("ref_mix") / "libref_mix_harness.so")
-    src = [os.path.join(ROOT, "tests", "csrc", "ref_mix_harness.c")] + [os.path.join(REF, "src", f) for f in
-                                                                         ("denoise.c", "kiss_fft.c", "pitch.c", "celt_lpc.c", "rnnoise_tables.c")]
-    subprocess.run(["gcc", "-O2", "-fPIC", "-ffp-contract=off", "-DDISABLE_DEBUG_FLOAT", "-DRNN_ENABLE_X86_RTCD", "-DCPU_INFO_BY_ASM",
-                    "-DRNNOISE_BUILD", "-DTRAINING=1", f"-DREF_DUMP_FEATURES_C=\"{REF}/src/dump_features.c\"", f"-I{GEN}", f"-I{REF}/include",
-                    f"-I{REF}/src", f"-I{REF}", "-w", "-shared", "-o", so] + src + ["-lm"], check=True)
-    L = C.CDLL(so)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
-    L.refm_biquad.argtypes = [fp, fp, fp, fp, fp, C.c_int]
-    L.refm_weighted_rms.argtypes = [fp]
-    L.refm_weighted_rms.restype = C.c_float
-    L.refm_viterbi_vad.argtypes = [fp, ip]
-    L.refm_clear_vad.argtypes = [fp, ip]
-    assert L.refm_sequence_frames() == T_REF
+    """the reference's functions (tests/csrc/ref_dump_harness.c: train_support.reference_dump_features)"""
+    L = reference_dump_features(tmp_path_factory.mktemp("ref_dump"))
+    if isinstance(L, str):
+        pytest.skip(L)
     return L
 
 
@@ -316,36 +297,10 @@ def test_draw_band_lp_keeps_the_previous_sequences_value_when_no_band_is_above_l
     assert list(d2.band_lp) == [7, 18, 18, 28]
 
 
-# ---- e. the kernels ----
-def test_the_kernels_of_train_mix_by_name_without_scratch():
-    from test_kernel_budgets_cpu import BUILD, _kernels
-    obj = os.path.join(BUILD, "train_mix.o")
-    if not os.path.exists(obj):
-        pytest.skip("kernels not built (python -c 'import __graft_entry__ as g; g.build()')")
-    meta, code = _kernels(obj)
-    assert set(meta) == {"rn_train_levels", "rn_train_mix"}, sorted(meta)
-    for k, m in meta.items():
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["vgpr_count"] <= 128, (k, m)
-        assert not [i for i in code[k] if i.startswith(("scratch_", "flat_"))], k
-    for name in ("librnnoise_amd.so", "librnnoise.so.0"):
-        text = subprocess.run(["strings", "-a", os.path.join(ROOT, "rnnoise_amd", name)], capture_output=True, text=True, check=True).stdout
-        assert set(re.findall(r"\b(rn_train_\w+)\.kd\b", text)) == {"rn_train_features_kernel", "rn_train_levels", "rn_train_mix"}, name
-
-
-# ---- f. the kernels' loops on the host ----
+# ---- e. the kernels' loops on the host ----
 def test_kernel_source_on_the_host_stays_inside_its_buffers_and_gives_the_oracles_bits(tmp_path):
     """train_mix.hip compiled as plain C++ against a stand-in for shim.h (192 host threads per workgroup), a stand-alone program under
     the address and undefined-behaviour sanitizers: corpora and outputs of exact size, rows at even and odd addresses, a row that
     ends with its corpus, 1 / 65 / 70 sequences, 1 to 40 frames"""
-    emul = os.path.join(ROOT, "tests", "csrc", "train_mix_emul")
-    for f in ("shim.h", "main.cpp"):
-        shutil.copy(os.path.join(emul, f), tmp_path / f)
-    shutil.copy(os.path.join(ROOT, "rnnoise_amd", "csrc", "train_mix.hip"), tmp_path / "train_mix.cpp")
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-I", inc, "-c", os.path.join(ROOT, "tests", "csrc", "mix_oracle.c"), "-o",
-                    str(tmp_path / "mix_oracle.o")], check=True)
-    subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-w", "-I", str(tmp_path), "-I", inc, str(tmp_path / "train_mix.cpp"), str(tmp_path / "main.cpp"),
-                    str(tmp_path / "mix_oracle.o"), "-o", str(tmp_path / "emul"), "-lpthread", "-lm"], check=True)
-    r = subprocess.run([str(tmp_path / "emul")], capture_output=True, text=True)
+    r = run_kernel_emul(tmp_path, "train_mix", "mix_main.cpp", "mix_oracle.c", [os.path.join(ROOT, "include")])
     assert r.returncode == 0 and r.stdout.strip().endswith("all equal"), r.stdout[-2000:] + r.stderr[-4000:]

@@ -19,10 +19,10 @@ import pytest
 import mix_oracle as mo
 from conftest import ROOT, assert_bits_equal, load_blob
 from rnnoise_amd import capi, train_data
+from train_support import GUARD, guarded, guards_intact
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-GUARD = 64
 FILTERS = [(0.0, 0.0), (-2 * .55 * np.cos(.9), .55 * .55), (-.62 + .31, -.62 * .31), (-2 * .69 * np.cos(.1), .69 * .69)]
 SPECIAL = (32767, -32767, -32768, 12345, -12345, 32767, -32768, 777)   # noise samples planted for (a): see special_rows
 
@@ -110,7 +110,7 @@ def special_rows(t, rows, corpora, T):
 
 
 class Device:
-    """the corpora on the device, and output buffers with guard words on both sides"""
+    """the corpora on the device, and output buffers with guard words on both sides (train_support.guarded)"""
 
     def __init__(self, corpora):
         self.dev = torch.device("cuda", 0)
@@ -122,20 +122,12 @@ class Device:
         self.lens = [len(c) for c in corpora]
 
     def out(self, shape, dtype=torch.float32):
-        n = int(np.prod(shape))
-        fill = {torch.float32: -7.5e33, torch.int32: -77777777, torch.uint8: 0xA5}[dtype]
-        buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=self.dev)
-        return buf, buf[GUARD:GUARD + n].view(*shape), fill
+        return guarded(shape, dtype)
 
     def corpora_unchanged(self):
         for p, c in zip(self.padded, self.host):
             h = p.cpu().numpy()
             assert (h[GUARD:-GUARD] == c).all() and (h[:GUARD] == 0x5A5A).all() and (h[-GUARD:] == 0x5A5A).all()
-
-
-def guards_intact(buf, fill):
-    h = buf.cpu().numpy()
-    assert (h[:GUARD] == h.dtype.type(fill)).all() and (h[-GUARD:] == h.dtype.type(fill)).all(), "a guard word was written"
 
 
 def run_gpu(b, d, table, T, start_pos=None, vad_tracks=None, stream=0, sync=torch.cuda.synchronize):
@@ -157,8 +149,8 @@ def run_gpu(b, d, table, T, start_pos=None, vad_tracks=None, stream=0, sync=torc
                        stream)
     sync()
     for k, (buf, _, fill) in bufs.items():
-        guards_intact(buf, fill)
-    guards_intact(vbuf, vfill)
+        guards_intact(buf, fill, k)
+    guards_intact(vbuf, vfill, "vad")
     assert (vview.cpu().numpy() == vad).all()
     r = {k: v[1].cpu().numpy() for k, v in bufs.items()}
     r["vad"] = vad

@@ -1,16 +1,15 @@
 """The RIR calls without a GPU (include/rnnoise_amd.h: RNNoiseTrainRir; the reference's src/dump_features.c:51-144, :449-465).
 
   a  tests/csrc/rir_oracle.c -- what the GPU tests compare against -- equals the reference's own kiss_fft tables, load_rir and
-     rir_filter_sequence (tests/csrc/ref_rir_harness.c, compiled where the reference's sources are), bit for bit
+     rir_filter_sequence (tests/csrc/ref_dump_harness.c, compiled where the reference's sources are), bit for bit
   b  the oracle itself: half a double-precision convolution within the fp32 error of its transforms; blocks independent of later input
   c  rnnoise_amd_train_rir_check, the -1 returns that need no device, the struct's layout, train_data.draw_rir
-  d  the kernels of train_rir.hip by name, their registers, no scratch, no flat accesses
-  e  the kernels' own source run on the host under the address sanitizer (tests/csrc/train_rir_emul), against the oracle"""
+  d  the kernels' own source run on the host under the address sanitizer (tests/csrc/hip_emul), against the oracle
+(the kernels of train_rir.hip by name, their registers, no scratch, no flat accesses: tests/test_product_surface_cpu.py,
+tests/test_kernel_budgets_cpu.py)"""
 import ctypes as C
 import hashlib
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,44 +18,19 @@ import pytest
 import rir_oracle as ro
 from conftest import GOLD, ROOT, assert_bits_equal
 from rnnoise_amd import capi, train_data
+from train_support import NFFT_REF, T_REF, reference_dump_features, run_kernel_emul
 
-REF = os.environ.get("RNNOISE_REFERENCE", "/root/reference")
-GEN = os.path.join(ROOT, "oracle", "_ref", "gen_default")
-T_REF = 2000
-KERNELS = {"rn_rir_fwd1", "rn_rir_spec", "rn_rir_mid", "rn_rir_inv2", "rn_rir_finish"}
-# 40 KiB of LDS per workgroup of four waves: four workgroups per CU, four waves per SIMD, 512 / 4 registers each
-VGPR_CAP = 128
+assert ro.NFFT == NFFT_REF
 
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def build_ref(where):
-    """the reference's functions (tests/csrc/ref_rir_harness.c), with the flags of its pinned build (oracle/Makefile: REF_CFLAGS),
-    compiled into the directory `where`; a string saying why not where that cannot be done"""
-    if not os.path.isdir(os.path.join(REF, "src")):
-        return "the reference's sources are not here"
-    if not os.path.exists(os.path.join(GEN, "rnnoise_data.h")):
-        return "oracle/_ref/gen_default not built (python -c 'import __graft_entry__ as g; g.build()')"
-    so = os.path.join(str(where), "libref_rir_harness.so")
-    src = [os.path.join(ROOT, "tests", "csrc", "ref_rir_harness.c")] + [os.path.join(REF, "src", f) for f in
-                                                                         ("denoise.c", "kiss_fft.c", "pitch.c", "celt_lpc.c", "rnnoise_tables.c")]
-    subprocess.run(["gcc", "-O2", "-fPIC", "-ffp-contract=off", "-DDISABLE_DEBUG_FLOAT", "-DRNN_ENABLE_X86_RTCD", "-DCPU_INFO_BY_ASM",
-                    "-DRNNOISE_BUILD", "-DTRAINING=1", f"-DREF_DUMP_FEATURES_C=\"{REF}/src/dump_features.c\"", f"-I{GEN}", f"-I{REF}/include",
-                    f"-I{REF}/src", f"-I{REF}", "-w", "-shared", "-o", so] + src + ["-lm"], check=True)
-    L = C.CDLL(so)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
-    L.refr_tables.argtypes = [fp, ip, ip]
-    L.refr_load_rir.argtypes = [C.c_char_p, C.c_int, fp]
-    L.refr_filter.argtypes = [fp, fp]
-    assert L.refr_fft_size() == ro.NFFT and L.refr_sequence_frames() == T_REF
-    return L
-
-
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    L = build_ref(tmp_path_factory.mktemp("ref_rir"))
+    """the reference's functions (tests/csrc/ref_dump_harness.c: train_support.reference_dump_features)"""
+    L = reference_dump_features(tmp_path_factory.mktemp("ref_dump"))
     if isinstance(L, str):
         pytest.skip(L)
     return L
@@ -321,36 +295,10 @@ def test_draw_is_unchanged_by_draw_rir():
     assert ((train_data.draw_rir(rng, 300, 4)["rir_id"] >= 0) == (u[:, 0] < .5)).all()
 
 
-# ---- d. the kernels ----
-def test_the_kernels_of_train_rir_by_name_without_scratch():
-    from test_kernel_budgets_cpu import BUILD, _kernels
-    obj = os.path.join(BUILD, "train_rir.o")
-    if not os.path.exists(obj):
-        pytest.skip("kernels not built (python -c 'import __graft_entry__ as g; g.build()')")
-    meta, code = _kernels(obj)
-    assert set(meta) == KERNELS, sorted(meta)
-    for k, m in meta.items():
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["vgpr_count"] <= VGPR_CAP, (k, m)
-        assert not [i for i in code[k] if i.startswith(("scratch_", "flat_"))], k
-    for name in ("librnnoise_amd.so", "librnnoise.so.0"):
-        text = subprocess.run(["strings", "-a", os.path.join(ROOT, "rnnoise_amd", name)], capture_output=True, text=True, check=True).stdout
-        assert set(re.findall(r"\b(rn_rir_\w+)\.kd\b", text)) == KERNELS, name
-
-
-# ---- e. the kernels' own source on the host ----
+# ---- d. the kernels' own source on the host ----
 def test_kernel_source_on_the_host_stays_inside_its_buffers_and_gives_the_oracles_bits(tmp_path):
     """train_rir.hip compiled as plain C++ against a stand-in for shim.h (256 host threads per workgroup), a stand-alone program under
     the address and undefined-behaviour sanitizers: frames, responses, spectra and a one-unit workspace of exact size; two responses
     through the loader, then 3 sequences (two filtered, one only clipped and quantised) of 7 and of 69 frames"""
-    emul = os.path.join(ROOT, "tests", "csrc", "train_rir_emul")
-    for f in ("shim.h", "main.cpp"):
-        shutil.copy(os.path.join(emul, f), tmp_path / f)
-    shutil.copy(os.path.join(ROOT, "rnnoise_amd", "csrc", "train_rir.hip"), tmp_path / "train_rir.cpp")
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-c", os.path.join(ROOT, "tests", "csrc", "rir_oracle.c"), "-o",
-                    str(tmp_path / "rir_oracle.o")], check=True)
-    subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-w", "-I", str(tmp_path), "-I", inc, str(tmp_path / "train_rir.cpp"), str(tmp_path / "main.cpp"),
-                    str(tmp_path / "rir_oracle.o"), "-o", str(tmp_path / "emul"), "-lpthread", "-lm"], check=True)
-    r = subprocess.run([str(tmp_path / "emul")], capture_output=True, text=True)
+    r = run_kernel_emul(tmp_path, "train_rir", "rir_main.cpp", "rir_oracle.c")
     assert r.returncode == 0 and r.stdout.strip().endswith("all equal"), r.stdout[-2000:] + r.stderr[-4000:]

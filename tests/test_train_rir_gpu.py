@@ -21,10 +21,10 @@ import mix_oracle as mo
 import rir_oracle as ro
 from conftest import GOLD, ROOT, assert_bits_equal, load_blob
 from rnnoise_amd import capi, train_data
+from train_support import guarded, guards_intact
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-GUARD = 64
 PLANTED = (32767.0, -32767.0, 32768.0, -32769.0, 6172.5, -6172.5, 32767.5, -.5)
 UNIT = 2 * ro.NFFT * 8
 
@@ -41,18 +41,6 @@ def rirs():
     spec = ro.spectra(h)
     spec.setflags(write=False)
     return h, spec
-
-
-def guarded(shape, dtype=torch.float32, fill=-7.5e33):
-    """a buffer of `shape` between guard words: (whole, view, fill)"""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda:0")
-    return buf, buf[GUARD:GUARD + n].view(*shape), fill
-
-
-def guards_intact(buf, fill, what):
-    h = buf.cpu().numpy()
-    assert (h[:GUARD] == h.dtype.type(fill)).all() and (h[-GUARD:] == h.dtype.type(fill)).all(), f"{what}: a guard word was written"
 
 
 def upload(a):
