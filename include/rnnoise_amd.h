@@ -451,15 +451,25 @@ RNNOISE_EXPORT int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d
  * computes from the same draws in its pinned build (-O2 -ffp-contract=off).  RNNoiseTrainMix holds one sequence's draws
  * (:367-399, :454, :460): the first sample of the sequence in each corpus (in samples; odd values too), the three gains as they
  * stand after :395-396 (before the level normalisation), the six filter coefficient pairs of rand_resp (:397-399) and the two
- * augmentation flags.  Four calls, in this order:
+ * augmentation flags.  Four calls, in this order (or three: the levels call with the VAD in it, then the mix):
  *   rnnoise_amd_train_mix_check        host only: 1 when every position lies in [0, len - 480 * n_frames], every gain and
  *                                      coefficient is finite and the flags are 0 or 1 (n_seq, n_frames >= 1); 0 otherwise.
  *   rnnoise_batch_train_levels_device  d_energy[n_seq][n_frames]: the speech energy per frame (:409-412);
  *                                      d_rms[n_seq][3]: weighted_rms (:283-293) of each signal after its two biquads (:420-431).
  *   rnnoise_amd_train_vad              host only, on the energies copied back: viterbi_vad (:199-254) per row with n_frames for
  *                                      its 2000 frames, then the first start_pos[s] / 480 frames cleared (:437; start_pos NULL:
- *                                      none) -> vad[n_seq][n_frames] bytes.  It stays on the host on purpose: its log, pow and
- *                                      sqrt in double are the host libm's, as in the reference.  0 / -1.
+ *                                      none) -> vad[n_seq][n_frames] bytes.  Its log, pow and sqrt in double are the host libm's,
+ *                                      as in the reference.  0 / -1.
+ *   rnnoise_batch_train_levels_vad_device  the levels call and, in the same launch, d_vad[n_seq][n_frames] = what
+ *                                      rnnoise_amd_train_vad(energy, n_seq, n_frames, start_pos, vad) gives on those energies, byte
+ *                                      for byte: no copy to the host, no host work between levels and mix.  start_pos: a host
+ *                                      array of n_seq ints, or NULL; it goes up with `mix`, in the same copy.  The device
+ *                                      evaluates the host libm's log and pow, restated operation for operation for GNU libc >=
+ *                                      2.28 on an x86-64 with FMA, so the call exists only on such a host:
+ *   rnnoise_amd_train_vad_device_available  1 when this process's log and pow equal the restated ones on a short sweep (run on
+ *                                      first use, cached), 0 when they do not (said once on stderr).  At 0 the device call
+ *                                      returns -1 with nothing enqueued, as it does for a NULL d_vad and for everything the
+ *                                      levels call refuses; use the levels call and rnnoise_amd_train_vad there.
  *   rnnoise_batch_train_mix_device     the biquads again, clear_vad (:256-281) on the speech with d_vad[n_seq][n_frames] bytes,
  *                                      the level normalisation with d_rms (:440-442), the mix (:443-448), clipping (:457) and
  *                                      quantisation (:463) where the flags say so ->
@@ -468,8 +478,8 @@ RNNOISE_EXPORT int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d
  * RIR filtering (-rir_list, :449-453) is not part of it: it sits between mix and clip, so a caller who wants it passes
  * clip = quantize = 0 here and hands the real flags to rnnoise_batch_train_rir_device (RNNoiseTrainRir, below) -- or filters with a
  * convolution of their own and clips / quantises afterwards.
- * The two device calls enqueue on hip_stream; `mix` is a host array of n_seq entries, copied into a buffer the batch owns
- * (allocated on first use) by a copy ordered on hip_stream.  `mix` is read before the call returns and may be freed then: for
+ * The device calls enqueue on hip_stream; `mix` is a host array of n_seq entries, copied into a buffer the batch owns
+ * (allocated on first use) by a copy ordered on hip_stream.  `mix` (and `start_pos`) is read before the call returns and may be freed then: for
  * pageable memory that means the call waits until the stream has reached the copy; the kernel runs asynchronously after it.  A
  * batch has one such buffer: issue its training-mix calls on one stream, or order them yourself.  They run the check first; a failed check, a NULL argument or n_frames < 1 returns -1 with
  * nothing launched.  They read and write no per-stream state, ignore the rate, format, layout, channel, model and control
@@ -488,6 +498,12 @@ RNNOISE_EXPORT int rnnoise_batch_train_levels_device(RNNoiseBatch *b, float *d_e
                                                      long long noise_len, long long fgnoise_len, const RNNoiseTrainMix *mix,
                                                      int n_frames, void *hip_stream);
 RNNOISE_EXPORT int rnnoise_amd_train_vad(const float *energy, int n_seq, int n_frames, const int *start_pos, unsigned char *vad);
+RNNOISE_EXPORT int rnnoise_amd_train_vad_device_available(void);
+RNNOISE_EXPORT int rnnoise_batch_train_levels_vad_device(RNNoiseBatch *b, float *d_energy, float *d_rms, unsigned char *d_vad,
+                                                         const short *d_speech, const short *d_noise, const short *d_fgnoise,
+                                                         long long speech_len, long long noise_len, long long fgnoise_len,
+                                                         const RNNoiseTrainMix *mix, const int *start_pos, int n_frames,
+                                                         void *hip_stream);
 RNNOISE_EXPORT int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clean, float *d_noisy, float *d_vad_target,
                                                   int *d_noise_free, const short *d_speech, const short *d_noise,
                                                   const short *d_fgnoise, long long speech_len, long long noise_len,

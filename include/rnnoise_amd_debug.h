@@ -29,6 +29,17 @@ RNNOISE_EXPORT int rnnoise_amd_debug_fft(int device, int variant, float *out, co
 RNNOISE_EXPORT int rnnoise_amd_debug_log_energy(int device, float *out, const float *ex, int n);
 RNNOISE_EXPORT int rnnoise_amd_debug_log_energy_range(int device, float *out, const float *ex, unsigned first_bits, unsigned n, int model);
 
+/* The Viterbi VAD of training-data generation on the device (rnnoise_batch_train_levels_vad_device) evaluates the host libm's log()
+ * and pow() (rnnoise_amd/csrc/pow_glibc.h).
+ * _libm: those device functions against THIS host's libm, for the n floats f with bit patterns first_bits, first_bits + stride, ...:
+ *   mode 1 pow((double)((1.f - f) / f), .5), 2 log(1e-15 + (double)f), 3 log((double)f); *mismatches = how many doubles differ in a
+ *   bit (two NaNs count as equal), *first_bad = the bits of the first such f.  0 / -1.
+ * _selfcheck: forced = 0 or 1 replaces the answer of rnnoise_amd_train_vad_device_available() (0: the device call refuses as on a
+ *   host with a foreign libm), -1 gives it back to the self-check.  Host only. */
+RNNOISE_EXPORT int rnnoise_amd_debug_train_vad_libm(int device, int mode, unsigned first_bits, unsigned stride, unsigned n,
+                                                    unsigned long long *mismatches, unsigned *first_bad);
+RNNOISE_EXPORT void rnnoise_amd_debug_train_vad_selfcheck(int forced);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,7 @@ EXPORTS = [
     "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
     "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
     "rnnoise_amd_train_mix_check", "rnnoise_batch_train_levels_device", "rnnoise_amd_train_vad", "rnnoise_batch_train_mix_device",
+    "rnnoise_amd_train_vad_device_available", "rnnoise_batch_train_levels_vad_device",
     "rnnoise_amd_train_rir_check", "rnnoise_amd_train_rir_work_bytes", "rnnoise_batch_train_rir_load_device",
     "rnnoise_batch_train_rir_device",
 ]
@@ -145,7 +146,8 @@ def _share_hip_runtime_with_torch():
 
 
 # entry points of include/rnnoise_amd_debug.h: present in the instrumented library only
-DEBUG_EXPORTS = ["rnnoise_batch_debug_pitch", "rnnoise_amd_debug_fft", "rnnoise_amd_debug_log_energy", "rnnoise_amd_debug_log_energy_range"]
+DEBUG_EXPORTS = ["rnnoise_batch_debug_pitch", "rnnoise_amd_debug_fft", "rnnoise_amd_debug_log_energy", "rnnoise_amd_debug_log_energy_range",
+                 "rnnoise_amd_debug_train_vad_libm", "rnnoise_amd_debug_train_vad_selfcheck"]
 
 
 def lib():
@@ -252,6 +254,8 @@ def _load(path, debug):
         L.rnnoise_amd_train_mix_check.argtypes = [vp, C.c_int, ll, ll, ll, C.c_int]
         L.rnnoise_batch_train_levels_device.argtypes = [vp] * 6 + [ll, ll, ll, vp, C.c_int, vp]
         L.rnnoise_amd_train_vad.argtypes = [fp, C.c_int, C.c_int, ip, up]
+        L.rnnoise_amd_train_vad_device_available.argtypes = []
+        L.rnnoise_batch_train_levels_vad_device.argtypes = [vp] * 7 + [ll, ll, ll, vp, ip, C.c_int, vp]
         L.rnnoise_batch_train_mix_device.argtypes = [vp] * 8 + [ll, ll, ll, vp, vp, vp, C.c_int, vp]
         L.rnnoise_amd_train_rir_check.argtypes = [vp, C.c_int, C.c_int]
         L.rnnoise_amd_train_rir_work_bytes.restype = ll
@@ -260,6 +264,10 @@ def _load(path, debug):
         L.rnnoise_batch_train_rir_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, ll, C.c_int, vp]
         if debug:
             L.rnnoise_batch_debug_pitch.argtypes = [vp, fp]
+            L.rnnoise_amd_debug_train_vad_libm.argtypes = [C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong),
+                                                           C.POINTER(C.c_uint)]
+            L.rnnoise_amd_debug_train_vad_selfcheck.argtypes = [C.c_int]
+            L.rnnoise_amd_debug_train_vad_selfcheck.restype = None
             L.rnnoise_amd_debug_log_energy.argtypes = [C.c_int, fp, fp, C.c_int]
             L.rnnoise_amd_debug_log_energy_range.argtypes = [C.c_int, fp, fp, C.c_uint, C.c_uint, C.c_int]
             L.rnnoise_amd_debug_fft.argtypes = [C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), ip]
@@ -310,6 +318,12 @@ def train_mix_check(mix, lens, n_frames: int) -> bool:
     samples), every gain and coefficient is finite and the flags are 0 or 1.  Host only."""
     mix = _mix_table(mix)
     return bool(lib().rnnoise_amd_train_mix_check(mix.ctypes.data, len(mix), int(lens[0]), int(lens[1]), int(lens[2]), int(n_frames)))
+
+
+def train_vad_device_available() -> bool:
+    """rnnoise_amd_train_vad_device_available: whether Batch.train_levels_vad_device exists on this host -- its log and pow are the
+    ones the device restates"""
+    return bool(lib().rnnoise_amd_train_vad_device_available())
 
 
 def train_vad(energy, start_pos=None):
@@ -816,6 +830,24 @@ class Batch:
         if self._L.rnnoise_batch_train_levels_device(self.h, d_energy or None, d_rms or None, *[p or None for p in d_corpora],
                                                      *[int(v) for v in lens], mix.ctypes.data, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_train_levels_device failed (a sequence outside its corpus, a non-finite gain?)")
+
+    def train_levels_vad_device(self, d_energy: int, d_rms: int, d_vad: int, d_corpora, lens, mix, start_pos, n_frames: int,
+                                stream: int = 0):
+        """train_levels_device and, in the same launch, d_vad [N][n_frames] uint8 out: what train_vad(energy, start_pos) gives on
+        those energies, byte for byte (rnnoise_batch_train_levels_vad_device).  start_pos: N ints on the host, or None.  Only where
+        train_vad_device_available() says so."""
+        mix = _mix_table(mix)
+        assert len(mix) == self.n, (len(mix), self.n)
+        sp = None
+        if start_pos is not None:
+            sp = np.ascontiguousarray(start_pos, np.int32)
+            assert sp.shape == (self.n,), (sp.shape, self.n)
+        if self._L.rnnoise_batch_train_levels_vad_device(self.h, d_energy or None, d_rms or None, d_vad or None,
+                                                         *[p or None for p in d_corpora], *[int(v) for v in lens], mix.ctypes.data,
+                                                         sp.ctypes.data_as(C.POINTER(C.c_int)) if sp is not None else None, n_frames,
+                                                         stream or None):
+            raise RuntimeError("rnnoise_batch_train_levels_vad_device failed (a sequence outside its corpus, a non-finite gain, a host "
+                               "whose libm is not the restated one: train_vad_device_available()?)")
 
     def train_mix_device(self, d_clean: int, d_noisy: int, d_vad_target: int, d_noise_free: int, d_corpora, lens, mix, d_rms: int,
                          d_vad: int, n_frames: int, stream: int = 0):

@@ -168,11 +168,12 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
 
 
 def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out: str, count: int, seed=None, seq_frames: int = 2000,
-                  streams: int = 64, device: int = 0, rir_list=None, rir_work_mb: int = 256):
+                  streams: int = 64, device: int = 0, rir_list=None, rir_work_mb: int = 256, vad: str = "auto"):
     """COUNT training sequences of seq_frames frames into `out` (float32 records, sequence after sequence: the reference's file
     format): sequence i runs on stream i % streams of one batch in round i // streams.  Each corpus is read and uploaded once.  The
     draws come from numpy's default generator seeded with `seed` (train_data.draw, then train_data.draw_rir from the same generator
-    when rir_list names a file of RIR file names)."""
+    when rir_list names a file of RIR file names).  vad: where the Viterbi VAD runs, "auto" | "device" | "host" (train_data.generate_rounds);
+    the file is the same either way."""
     import torch
 
     from . import train_data
@@ -190,7 +191,7 @@ def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out:
         with torch.cuda.device(dev):
             rirs = (train_data.rir_spectra(batch, responses, dev), train_data.draw_rir(rng, count, len(responses)))
     with torch.cuda.device(dev), open(out, "wb") as f:
-        for rec in train_data.generate_rounds(batch, *corpora, draws, seq_frames, rirs, rir_work_mb << 20):
+        for rec in train_data.generate_rounds(batch, *corpora, draws, seq_frames, rirs, rir_work_mb << 20, vad):
             f.write(rec.tobytes())
     batch.close()
     model.close()
@@ -224,6 +225,9 @@ def main(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--rir-list", default=None, help="file of RIR file names, one per line (raw float32): the reference's -rir_list")
     p.add_argument("--rir-work-mb", type=int, default=256, help="workspace of the RIR filter in MiB, at least 1")
+    p.add_argument("--vad", default="auto", choices=("host", "device", "auto"),
+                   help="where the Viterbi VAD runs: in the levels kernel, on the host, or on the device where this host's libm allows "
+                        "(the default); the records are the same")
     p.add_argument("speech")
     p.add_argument("noise")
     p.add_argument("fgnoise")
@@ -232,7 +236,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.cmd == "dump-features":
         n = dump_features(open(a.model, "rb").read(), a.speech, a.noise, a.fgnoise, a.out, a.count, a.seed, a.seq_frames, a.streams,
-                          a.device, a.rir_list, a.rir_work_mb)
+                          a.device, a.rir_list, a.rir_work_mb, a.vad)
         print(f"wrote {a.count} sequences, {n} records")
         return
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,

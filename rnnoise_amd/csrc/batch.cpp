@@ -701,6 +701,39 @@ extern "C" int rnnoise_amd_debug_log_energy(int device, float *out, const float 
   return rnnoise_amd_debug_log_energy_range(device, out, ex, 0, (unsigned)n, 0);
 }
 
+// The functions of the Viterbi VAD's epilogue (include/rn_train_vad.h) on the device against this host's libm, for the n floats with
+// bit patterns first_bits, first_bits + stride, ...: mode 1 pow((double)((1.f - f) / f), .5), 2 log(1e-15 + (double)f),
+// 3 log((double)f).  *mismatches: how many doubles differ in a bit (two NaNs are equal); *first_bad: the first such float's bits.
+extern "C" int rnnoise_amd_debug_train_vad_libm(int device, int mode, unsigned first_bits, unsigned stride, unsigned n,
+                                                unsigned long long *mismatches, unsigned *first_bad) {
+  if (mode < 1 || mode > 3 || !mismatches || !first_bad || n == 0 || stride == 0) return -1;
+  if ((unsigned long long)first_bits + (unsigned long long)(n - 1) * stride > 0xffffffffull) return -1;
+  ON_DEVICE(device);
+  const unsigned chunk = 1u << 22;
+  DevScratch d;
+  const size_t o_out = d.carve((size_t)std::min(n, chunk) * 8);
+  if (d.alloc()) return -1;
+  std::vector<double> got(std::min(n, chunk));
+  volatile double half = 0.5;  // (volatile: pow() stays the libm call)
+  *mismatches = 0;
+  *first_bad = 0;
+  for (unsigned at = 0; at < n; at += chunk) {
+    const unsigned m = std::min(chunk, n - at);
+    HIP_OK(rn_launch_vad_libm(mode, first_bits + at * stride, stride, d.at<double>(o_out), m, nullptr));
+    HIP_OK(hipStreamSynchronize(nullptr));
+    HIP_OK(hipMemcpy(got.data(), d.at<char>(o_out), (size_t)m * 8, hipMemcpyDeviceToHost));
+    for (unsigned i = 0; i < m; i++) {
+      const unsigned u = first_bits + (at + i) * stride;
+      float f;
+      memcpy(&f, &u, 4);
+      const volatile double x = mode == 1 ? (double)((1.f - f) / f) : mode == 2 ? 1e-15 + (double)f : (double)f;
+      const double want = mode == 1 ? pow(x, half) : log(x);
+      if (memcmp(&want, &got[i], 8) && !(want != want && got[i] != got[i]) && !(*mismatches)++) *first_bad = u;
+    }
+  }
+  return 0;
+}
+
 #endif  // RN_INSTRUMENT
 
 extern "C" int rnnoise_batch_enable_timing(RNNoiseBatch *b, int on) {

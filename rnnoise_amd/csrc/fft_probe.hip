@@ -9,6 +9,7 @@
 #include "fft_reg.h"
 #include "rn_dev.h"
 #include "log10_glibc.h"
+#include "../../include/rn_train_vad.h"
 
 #define WAVE 64
 struct cpx { float r, i; };
@@ -166,13 +167,26 @@ extern "C" hipError_t rn_launch_fft_probe_lds(const float *in, float *out, unsig
 // test tap: the log-energy expression of the feature stage (src/denoise.c:383) on arbitrary inputs -- ex[i], or, with ex == null,
 // the float whose bit pattern is first_bits + i (exhaustive sweeps without an input array) -- through the feature stage's own
 // function: tab = RnTablesDev::log_tab (the host libm's algorithm, log10_glibc.h) or null (the device library's log10)
+// vad_mode != 0: the same sweep through the functions of the Viterbi VAD's epilogue (include/rn_train_vad.h), doubles to vad_out,
+// for the float f with bit pattern first_bits + i * stride: 1 = pow((double)((1.f - f) / f), .5), 2 = log(1e-15 + (double)f),
+// 3 = log((double)f)
 extern "C" __global__ void rn_log_energy_kernel(const float *__restrict__ ex, unsigned first_bits, float *__restrict__ out, unsigned n,
-                                                const double *tab) {
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    out[i] = rn_log_energy(ex ? ex[i] : __uint_as_float(first_bits + i), tab);
+                                                const double *tab, int vad_mode, unsigned stride, double *__restrict__ vad_out) {
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (vad_mode == 0) {
+      out[i] = rn_log_energy(ex ? ex[i] : __uint_as_float(first_bits + i), tab);
+    } else {
+      const float f = __uint_as_float(first_bits + i * stride);
+      vad_out[i] = vad_mode == 1 ? rn_vad_pow_half((double)((1.f - f) / f)) : rn_vad_log(vad_mode == 2 ? 1e-15 + (double)f : (double)f);
+    }
+  }
 }
 extern "C" hipError_t rn_launch_log_energy(const float *ex, unsigned first_bits, float *out, unsigned n, const double *tab, hipStream_t st) {
-  hipLaunchKernelGGL(rn_log_energy_kernel, dim3(4096), dim3(256), 0, st, ex, first_bits, out, n, tab);
+  hipLaunchKernelGGL(rn_log_energy_kernel, dim3(4096), dim3(256), 0, st, ex, first_bits, out, n, tab, 0, 1u, nullptr);
+  return hipGetLastError();
+}
+extern "C" hipError_t rn_launch_vad_libm(int vad_mode, unsigned first_bits, unsigned stride, double *out, unsigned n, hipStream_t st) {
+  hipLaunchKernelGGL(rn_log_energy_kernel, dim3(4096), dim3(256), 0, st, nullptr, first_bits, nullptr, n, nullptr, vad_mode, stride, out);
   return hipGetLastError();
 }
 

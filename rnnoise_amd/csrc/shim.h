@@ -62,6 +62,7 @@ extern "C" void rn_nn_gru_opt_in(hipError_t out[2]);      // nn_layers.hip, both
 extern "C" hipError_t rn_launch_release_store(void *, long long, hipStream_t);
 #if RN_INSTRUMENT
 extern "C" hipError_t rn_launch_log_energy(const float *, unsigned, float *, unsigned, const double *, hipStream_t);
+extern "C" hipError_t rn_launch_vad_libm(int, unsigned, unsigned, double *, unsigned, hipStream_t);
 extern "C" hipError_t rn_launch_fft_probe(int, const float *, float *, unsigned long long *, int, int, const RnTablesDev *, hipStream_t);
 extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 #endif

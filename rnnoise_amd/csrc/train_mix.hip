@@ -1,6 +1,7 @@
 // train_mix.hip -- the mixing stage of training-data generation (include/rnnoise_amd.h: RNNoiseTrainMix; the reference's
 // src/dump_features.c:408-465 without the RIR): rnnoise_amd_train_mix_check, rnnoise_batch_train_levels_device,
-// rnnoise_amd_train_vad, rnnoise_batch_train_mix_device and their two kernels.  DESIGN.md section 4.20.
+// rnnoise_amd_train_vad, rnnoise_batch_train_levels_vad_device, rnnoise_batch_train_mix_device and their two kernels.  DESIGN.md
+// sections 4.20 and 4.22.
 //
 // Every signal of a sequence is a strictly serial recurrence over 480 * n_frames samples (two biquads with double intermediates,
 // src/denoise.c:409-419; a third one in the levels pass), so a lane owns one (sequence, signal) chain: a workgroup is three waves,
@@ -13,8 +14,10 @@
 // tests/csrc/hip_emul compiles THIS FILE as host C++ against a stand-in for shim.h (tests/test_train_mix_cpu.py, under the address
 // sanitizer): a HIP call, a builtin or a member of RNNoiseBatch that this file starts to use needs its counterpart there.
 #include "train_common.h"
+#include "rn_train_vad.h"  // (include/: the Viterbi VAD as device code, the epilogue of rn_train_levels)
 
 #include <limits.h>
+#include <atomic>
 
 namespace {
 constexpr int CH = 32;                              // samples per chunk: 480 = 15 * 32, a chunk never straddles a frame
@@ -30,6 +33,8 @@ struct TrainMixArgs {
   int n_seq, n_frames;
   // levels
   float *energy, *rms_out;
+  uint8_t *vad_out;      // [n_seq][n_frames], or null: no VAD epilogue
+  const int *start_pos;  // [n_seq] behind the table in the batch's buffer (with vad_out)
   // mix
   float *clean, *noisy, *vad_target;
   int *noise_free;
@@ -208,6 +213,13 @@ __device__ __forceinline__ void train_mix_body(const TrainMixArgs &a, MixLds *ld
   if constexpr (!MIX) {
     // weighted_rms (:291-292): the mean in float, the root and the product with 0.9506 in double, rounded once
     if (live) a.rms_out[(size_t)seq * 3 + sig] = (float)(0.9506 * sqrt((double)(mse / (float)(RN_FRAME_SIZE * a.n_frames))));
+    // The Viterbi VAD of the row of energies this lane has just written (include/rn_train_vad.h): the speech wave only, and
+    // only for the call that asks for it -- both tests are uniform in the wave.
+    if (a.vad_out && sig == 0 && live) {
+      const int sp = a.start_pos[seq];
+      const int lead = sp > 0 ? min(sp / RN_FRAME_SIZE, a.n_frames) : 0;
+      rn_vad_row(a.energy + (size_t)seq * a.n_frames, a.n_frames, a.vad_out + (size_t)seq * a.n_frames, lead);
+    }
   }
 }
 
@@ -313,17 +325,86 @@ extern "C" int rnnoise_amd_train_vad(const float *energy, int n_seq, int n_frame
   return 0;
 }
 
+// ---- the device form of the VAD: rn_train_levels' epilogue evaluates the host libm's log() and pow() (pow_glibc.h) ----
+// It is offered only where that is true of THIS process's libm: a short sweep of the restated functions against the running ones
+// over the VAD's arguments, on first use, cached -- like the log10 model of the feature stage (tables.cpp), except that there is no
+// second-best form to fall back to: a VAD with other arithmetic would make a record file depend on where it was written.
+namespace {
+std::atomic<int> g_vad_selfcheck{-1};  // -1: not run yet; 0: differs; 1: equal
+#if RN_INSTRUMENT
+std::atomic<int> g_vad_selfcheck_forced{-1};  // (rnnoise_amd_debug_train_vad_selfcheck: tests)
+#endif
+
+bool host_libm_is_the_restated_one() {
+  uint64_t s = 0x9e3779b97f4a7c15ull;
+  auto rnd = [&s] {  // splitmix64
+    uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+  };
+  volatile double half = 0.5;  // (volatile: the libm calls are made, not folded)
+  uint32_t w_lo, w_hi;
+  const float lo = .1f, hi = .9f;
+  memcpy(&w_lo, &lo, 4);
+  memcpy(&w_hi, &hi, 4);
+  for (int it = 0; it < 100000; it++) {
+    const uint64_t r = rnd();
+    uint32_t u = w_lo + (uint32_t)(r % (w_hi - w_lo + 1)), e = (uint32_t)((r >> 32) % 0x7f800000u);  // w of [.1f, .9f]; any energy
+    float w, en;
+    memcpy(&w, &u, 4);
+    memcpy(&en, &e, 4);
+    const volatile double x = (double)((1.f - w) / w), l = 1e-15 + (double)en;
+    const double want_p = pow(x, half), got_p = rn_vad_pow_half(x), want_l = log(l), got_l = rn_vad_log(l);
+    if (memcmp(&want_p, &got_p, 8) || memcmp(&want_l, &got_l, 8)) return false;
+  }
+  const volatile double zero = 0.0, one = 1.0;
+  return log(zero) == rn_vad_log(zero) && pow(one, half) == rn_vad_pow_half(one);
+}
+}  // namespace
+
+extern "C" int rnnoise_amd_train_vad_device_available(void) {
+#if RN_INSTRUMENT
+  if (g_vad_selfcheck_forced.load() >= 0) return g_vad_selfcheck_forced.load();
+#endif
+  int v = g_vad_selfcheck.load();
+  if (v < 0) {
+    v = host_libm_is_the_restated_one() ? 1 : 0;
+    int expected = -1;
+    if (g_vad_selfcheck.compare_exchange_strong(expected, v) && !v)  // (said once)
+      fprintf(stderr, "[rnnoise_amd] this host's log and pow are not GNU libc >= 2.28 with FMA; the Viterbi VAD of training-data "
+                      "generation stays on the host (rnnoise_amd_train_vad), rnnoise_batch_train_levels_vad_device refuses\n");
+  }
+  return v;
+}
+#if RN_INSTRUMENT
+// include/rnnoise_amd_debug.h: 0 or 1 makes the self-check's answer, -1 gives it back to the sweep
+extern "C" void rnnoise_amd_debug_train_vad_selfcheck(int forced) {
+  g_vad_selfcheck_forced.store(forced < 0 ? -1 : forced != 0);
+}
+#endif
+
 namespace {
 // What both device calls do once their pointers are checked and their outputs are in `a`: the table checked and in the batch's
 // buffer (train_common.h), the arguments both kernels read, the launch.
+// The batch's buffer holds the table and, behind it, room for one int per sequence: the start positions of the call with the VAD
+// (`with_start`: start_pos or, for null, zeros), which go up with the table in one copy.
 int mix_launch(void (*kernel)(TrainMixArgs), TrainMixArgs a, RNNoiseBatch *b, const short *d_speech, const short *d_noise,
                const short *d_fgnoise, long long speech_len, long long noise_len, long long fgnoise_len, const RNNoiseTrainMix *mix,
-               int n_frames, void *hip_stream) {
+               int n_frames, void *hip_stream, bool with_start = false, const int *start_pos = nullptr) {
   if (!rnnoise_amd_train_mix_check(mix, b->n, speech_len, noise_len, fgnoise_len, n_frames)) return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
-  const size_t bytes = (size_t)b->n * sizeof(RNNoiseTrainMix);
-  if (train_upload(&b->train_mix_buf, bytes, mix, bytes, st)) return -1;
+  const size_t bytes = (size_t)b->n * sizeof(RNNoiseTrainMix), capacity = bytes + (size_t)b->n * sizeof(int);
+  if (with_start) {
+    std::vector<unsigned char> both(capacity, 0);
+    memcpy(both.data(), mix, bytes);
+    if (start_pos) memcpy(both.data() + bytes, start_pos, capacity - bytes);
+    if (train_upload(&b->train_mix_buf, capacity, both.data(), capacity, st)) return -1;
+    a.start_pos = reinterpret_cast<const int *>(static_cast<const unsigned char *>(b->train_mix_buf) + bytes);
+  } else if (train_upload(&b->train_mix_buf, capacity, mix, bytes, st)) {
+    return -1;
+  }
   a.mix = static_cast<const RNNoiseTrainMix *>(b->train_mix_buf);
   a.corpus[0] = d_speech;
   a.corpus[1] = d_noise;
@@ -344,6 +425,20 @@ extern "C" int rnnoise_batch_train_levels_device(RNNoiseBatch *b, float *d_energ
   a.energy = d_energy;
   a.rms_out = d_rms;
   return mix_launch(rn_train_levels, a, b, d_speech, d_noise, d_fgnoise, speech_len, noise_len, fgnoise_len, mix, n_frames, hip_stream);
+}
+
+extern "C" int rnnoise_batch_train_levels_vad_device(RNNoiseBatch *b, float *d_energy, float *d_rms, unsigned char *d_vad,
+                                                     const short *d_speech, const short *d_noise, const short *d_fgnoise,
+                                                     long long speech_len, long long noise_len, long long fgnoise_len,
+                                                     const RNNoiseTrainMix *mix, const int *start_pos, int n_frames, void *hip_stream) {
+  if (!b || !d_energy || !d_rms || !d_vad || !d_speech || !d_noise || !d_fgnoise || !mix || n_frames < 1) return -1;
+  if (!rnnoise_amd_train_vad_device_available()) return -1;
+  TrainMixArgs a{};
+  a.energy = d_energy;
+  a.rms_out = d_rms;
+  a.vad_out = d_vad;
+  return mix_launch(rn_train_levels, a, b, d_speech, d_noise, d_fgnoise, speech_len, noise_len, fgnoise_len, mix, n_frames, hip_stream,
+                    true, start_pos);
 }
 
 extern "C" int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clean, float *d_noisy, float *d_vad_target, int *d_noise_free,

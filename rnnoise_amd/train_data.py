@@ -2,8 +2,12 @@
 RNNoiseTrainMix).  draw() makes the random choices of dump_features.c:367-406 and :454 / :460 on the host; generate() runs everything
 from the int16 corpora to the 98-float records on the device, one sequence per stream of a batch and round:
 
-    levels (rnnoise_batch_train_levels_device) -> energies to the host -> Viterbi VAD (rnnoise_amd_train_vad) ->
+    levels with the Viterbi VAD in the same launch (rnnoise_batch_train_levels_vad_device) ->
     mix (rnnoise_batch_train_mix_device) [-> RIR (rnnoise_batch_train_rir_device)] -> features (rnnoise_batch_train_features_device)
+
+with nothing copied back and no synchronisation between the kernels -- or, on a host whose libm the device does not restate (vad="host"):
+
+    levels (rnnoise_batch_train_levels_device) -> energies to the host -> Viterbi VAD (rnnoise_amd_train_vad) -> mix -> ...
 
 For the same draws the records are bit for bit the reference's.  Its optional RIR filtering (-rir_list) is the bracketed step:
 rir_spectra() transforms a list of room impulse responses once, draw_rir() makes the choices of dump_features.c:449-450, and
@@ -144,12 +148,16 @@ def _pad(a, n):
     return a if len(a) == n else np.concatenate([a, np.repeat(a[-1:], n - len(a), 0)])
 
 
-def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20):
+def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20,
+                    vad: str = "auto"):
     """Yields the records of sequences [r * N, (r + 1) * N) of `draws`, r = 0, 1, ..., each a (sequences, n_frames, 98) float32 array:
     sequence i runs on stream i % N of `batch` (N streams) in round i // N, and the batch's per-stream analysis state carries from one
     sequence of a stream to the next, as the reference's two DenoiseStates carry across its loop.  speech, noise, fgnoise: the corpora
-    as 1-D int16 torch tensors on the batch's device.  Everything is enqueued on torch's current stream; the only host work of a
-    round is the Viterbi VAD on the frame energies.  When the last round is partial, the streams behind the last sequence run that
+    as 1-D int16 torch tensors on the batch's device.  Everything is enqueued on torch's current stream.  vad: where the Viterbi VAD of the
+    frame energies runs -- "device": in the levels launch, a round then copies nothing back and does not synchronise between its
+    kernels (RuntimeError on a host whose libm the device does not restate, capi.train_vad_device_available()); "host": the energies
+    go to the host, rnnoise_amd_train_vad decodes them on one thread, the bytes go back; "auto" (the default): "device" where
+    available, else "host".  The records are the same to the byte.  When the last round is partial, the streams behind the last sequence run that
     sequence again (records dropped), so their analysis state advances too: a later call on the same batch starts those streams from
     a state that no sequence of the file order left.  Reset the batch, or use a sequence count that is a multiple of N, where that
     matters; one run of the command line is not affected.
@@ -158,6 +166,9 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
     all (dump_features.c:449-465), in a workspace of rir_work_bytes (at least capi.train_rir_work_bytes(1)).  Without rirs nothing
     changes."""
     import torch
+    if vad not in ("auto", "device", "host"):
+        raise ValueError(f"vad={vad!r}: auto | device | host")
+    on_device = vad == "device" or (vad == "auto" and capi.train_vad_device_available())
     N = batch.n
     corpora = (speech, noise, fgnoise)
     for c in corpora:
@@ -169,6 +180,7 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
     clean, noisy = new((n_frames, N, FRAME)), new((n_frames, N, FRAME))
     vad_target, noise_free = new((n_frames, N)), new((N,), torch.int32)
     rec = new((n_frames, N, REC))
+    d_vad = new((N, n_frames), torch.uint8) if on_device else None
     count = len(draws.mix)
     if rirs is not None:
         spectra, rir_rec = rirs
@@ -185,9 +197,12 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
             mix = mix.copy()
             mix["clip"] = mix["quantize"] = 0
         st = torch.cuda.current_stream(dev).cuda_stream
-        batch.train_levels_device(energy.data_ptr(), rms.data_ptr(), ptrs, lens, mix, n_frames, st)
-        vad = capi.train_vad(energy.cpu().numpy(), _pad(draws.start_pos[rows], N))
-        d_vad = torch.from_numpy(vad).to(dev)
+        if on_device:
+            batch.train_levels_vad_device(energy.data_ptr(), rms.data_ptr(), d_vad.data_ptr(), ptrs, lens, mix,
+                                          _pad(draws.start_pos[rows], N), n_frames, st)
+        else:
+            batch.train_levels_device(energy.data_ptr(), rms.data_ptr(), ptrs, lens, mix, n_frames, st)
+            d_vad = torch.from_numpy(capi.train_vad(energy.cpu().numpy(), _pad(draws.start_pos[rows], N))).to(dev)
         d_lowpass = torch.from_numpy(_pad(draws.lowpass[rows], N).astype(np.int32)).to(dev)
         d_band_lp = torch.from_numpy(_pad(draws.band_lp[rows], N).astype(np.int32)).to(dev)
         batch.train_mix_device(clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), noise_free.data_ptr(), ptrs, lens, mix,
@@ -200,6 +215,7 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
         yield rec.permute(1, 0, 2)[:k].contiguous().cpu().numpy()  # sequence-major: the reference's file order
 
 
-def generate(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20) -> np.ndarray:
+def generate(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20,
+             vad: str = "auto") -> np.ndarray:
     """all records of `draws`, (sequences, n_frames, 98) float32 in sequence order (generate_rounds)"""
-    return np.concatenate(list(generate_rounds(batch, speech, noise, fgnoise, draws, n_frames, rirs, rir_work_bytes)))
+    return np.concatenate(list(generate_rounds(batch, speech, noise, fgnoise, draws, n_frames, rirs, rir_work_bytes, vad)))

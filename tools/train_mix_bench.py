@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Cost of generating training sequences (include/rnnoise_amd.h: RNNoiseTrainMix), one JSON line on stdout.
 
-  python tools/train_mix_bench.py [--seqs N ...] [--frames T] [--reps K] [--warmup W] [--cpu-seqs C] [--corpus-samples S]
+  python tools/train_mix_bench.py [--seqs N ...] [--frames T] [--reps K] [--warmup W] [--cpu-seqs C] [--corpus-samples S] [--vad-device]
 
 For every batch size: rnnoise_batch_train_levels_device, rnnoise_batch_train_mix_device and rnnoise_batch_train_features_device over one
 sequence of --frames frames per stream, each timed on its own with HIP events on the call's stream (median of --reps after --warmup),
 on draws of train_data.draw from three random corpora.  Beside them the same work on this host's CPU: tests/csrc/mix_oracle.c, one
 thread, --cpu-seqs sequences (levels, Viterbi VAD and mix timed apart), and rnnoise_amd_train_vad, the host step of the GPU path.
+--vad-device: also rnnoise_batch_train_levels_vad_device, the levels launch with the Viterbi VAD in it, beside
+what it replaces -- the levels call, the energies to the host, rnnoise_amd_train_vad, the bytes back -- between the same two events.
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-seqs", type=int, default=4)
     ap.add_argument("--corpus-samples", type=int, default=1 << 26)
+    ap.add_argument("--vad-device", action="store_true", help="also time the levels call with the VAD and the host path it replaces")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -96,6 +99,21 @@ def main():
                                                         dr.mix, rms.data_ptr(), d_vad.data_ptr(), T, h))
         t_tf, all_tf = timed(lambda: b.train_features_device(rec.data_ptr(), clean.data_ptr(), noisy.data_ptr(), target.data_ptr(),
                                                              d_lp.data_ptr(), d_bl.data_ptr(), nf.data_ptr(), T, h))
+        extra = {}
+        if a.vad_device:
+            d_v = new((N, T), torch.uint8)
+            t_lvv, all_lvv = timed(lambda: b.train_levels_vad_device(energy.data_ptr(), rms.data_ptr(), d_v.data_ptr(), ptrs, lens, dr.mix,
+                                                                     dr.start_pos, T, h))
+            assert (d_v.cpu().numpy() == vad).all()
+
+            def host_path():
+                b.train_levels_device(energy.data_ptr(), rms.data_ptr(), ptrs, lens, dr.mix, T, h)
+                return torch.from_numpy(capi.train_vad(energy.cpu().numpy(), dr.start_pos)).to(dev)
+            t_hp, all_hp = timed(host_path)
+            extra = {"levels_vad_ms": round(t_lvv, 3), "levels_vad_runs": [round(v, 3) for v in all_lvv],
+                     "levels_copy_host_vad_copy_ms": round(t_hp, 3), "levels_copy_host_vad_copy_runs": [round(v, 3) for v in all_hp],
+                     "vad_epilogue_ms": round(t_lvv - t_lv, 3)}
+            del d_v
         cpu_ms = (cpu["levels"] + cpu["mix"]) * N
         res[f"seqs_{N}"] = {
             "levels_ms": round(t_lv, 3), "mix_ms": round(t_mx, 3), "train_features_ms": round(t_tf, 3),
@@ -106,7 +124,7 @@ def main():
             "sequences_per_s_levels_plus_mix": round(N / (t_lv + t_mx) * 1e3, 1),
             "sequences_per_s_all_three": round(N / (t_lv + t_mx + t_tf) * 1e3, 1),
             "cpu_one_thread_levels_plus_mix_ms": round(cpu_ms, 1),
-            "cpu_over_gpu_levels_plus_mix": round(cpu_ms / (t_lv + t_mx), 1)}
+            "cpu_over_gpu_levels_plus_mix": round(cpu_ms / (t_lv + t_mx), 1), **extra}
         b.close()
         del energy, rms, clean, noisy, target, nf, rec, d_vad
         torch.cuda.empty_cache()
