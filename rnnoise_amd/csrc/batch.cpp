@@ -222,7 +222,7 @@ extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
   const int n_frames = c.n_frames, n_rows = c.n_rows;
   const bool s16 = c.s16;
-  const FrameIoHooks *hk = c.hooks;
+  FrameIo *hk = c.hooks;
   if (!b || n_frames < 0) return -1;
   const bool listed = c.list || n_rows;
   if (listed) {
@@ -274,8 +274,8 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
     }
     return g;
   };
-  // Multi-frame calls are software-pipelined over three streams: C runs the high-pass of frames up to
-  // f+2, B the analysis of frame f+1, A (the caller's stream) network + synthesis of frame f.
+  // Multi-frame calls are software-pipelined over three streams: C runs the high-pass up to three frames ahead (f+3), B the analysis
+  // of frame f+1, A (the caller's stream) network + synthesis of frame f; under schedule 1 (the host-fed path) analysis stays on A.
   // What makes that legal:
   //   * the pitch ring has 6 slots and analysis(g) reads slots g-3..g, so high-pass(f) only has to wait
   //     for analysis(f-3);

@@ -26,7 +26,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -249,16 +248,17 @@ struct RNNoiseBatch {
   float *scratch_gains = nullptr, *scratch_vad = nullptr;
   float *debug_buf = nullptr;
   float *state_stage = nullptr;  // one flat state in HBM: export / import go through the gather / scatter kernels
-  // host-fed path (rnnoise_batch_process): two chunks in flight -- H2D of chunk i+1 and D2H of chunk i-1 overlap the
-  // kernels of chunk i; pinned bounce buffers are used only when the caller's memory is pageable
+  // host-fed path (rnnoise_batch_process, host_io.cpp).  `run` carries the kernels and `down` the downloads of both kinds of caller
   struct HostIo {
     hipStream_t up = nullptr, run = nullptr, down = nullptr;
+    // pageable callers, the chunk loop: two chunks in flight -- H2D of chunk i+1 (on `up`) and D2H of chunk i-1 overlap the kernels of
+    // chunk i -- between device staging d_* and pinned bounce buffers h_*
     hipEvent_t up_done[2] = {}, run_done[2] = {}, down_done[2] = {};
     float *d_in[2] = {}, *d_out[2] = {}, *d_vad[2] = {}, *d_gains[2] = {};
     float *h_in[2] = {}, *h_out[2] = {}, *h_vad[2] = {}, *h_gains[2] = {};
     int chunk_frames = 0;
-    size_t pcm_floats = 0;  // capacity of d_in / d_out (and h_in / h_out) of one chunk
-    // pinned callers: a ring of RING frame slots, filled and drained frame by frame beside the kernels
+    size_t pcm_floats = 0;  // capacity of d_in / d_out and h_in / h_out of one chunk
+    // pinned callers: a ring of RING frame slots, filled and drained frame by frame beside the kernels of one device call
     static constexpr int RING = 6;
     char *ring_mem = nullptr;
     hipEvent_t r_k3[RING] = {}, r_down[RING] = {}, r_up[RING] = {}, r_hp[RING] = {};
@@ -346,12 +346,17 @@ struct DenoiseState {
 static const uint32_t kStateMagic = 0x524e4e41u;   // "RNNA": self-contained state
 static const uint32_t kPooledMagic = 0x524e4e50u;  // "RNNP": row of a StatePool
 
-// Hooks of the host-fed path: the frame buffers of a call are then a ring of `ring` frame slots in HBM (frame f lives in
-// slot f % ring) that uploads fill and downloads drain while the kernels run; each hook is called on the host right where
-// the named kernel of frame f is enqueued, with the stream it goes to.
-struct FrameIoHooks {
+// The copy back end of a host-fed call (host_io.cpp): the frame buffers of the call are then a ring of `ring` frame slots in HBM
+// (frame f lives in slot f % ring) that uploads fill and downloads drain while the kernels run; each hook is called on the host
+// right where the named kernel of frame f is enqueued, with the stream it goes to.
+struct FrameIo {
   int ring = 0;
-  std::function<int(int, hipStream_t)> before_hp, after_hp, before_nn, after_k3;
+  virtual int before_hp(int f, hipStream_t sc) = 0;
+  virtual int after_hp(int f, hipStream_t sc) = 0;
+  virtual int before_nn(int f, hipStream_t st) = 0;
+  virtual int after_k3(int f, hipStream_t st) = 0;
+ protected:
+  ~FrameIo() = default;
 };
 
 // ---- functions that cross file boundaries ----
@@ -378,7 +383,7 @@ struct ProcessCall {
   // per frame (rn_dev.h: RnGroupDev::list)
   const int *list = nullptr;
   int n_rows = 0;
-  const FrameIoHooks *hooks = nullptr;  // the pinned ring of the host-fed path (host_io.cpp)
+  FrameIo *hooks = nullptr;  // the pinned ring of the host-fed path (host_io.cpp)
   bool packed = false;  // the buffers are the library's own, in the default layout whatever the batch's (batch_process_staged)
 };
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
