@@ -276,7 +276,8 @@ RNNOISE_EXPORT int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_strid
  * in `in` and in `out`, in SAMPLES of the call's own type, M = 480 / Lb samples per row and frame (Lb the batch's divisor).  Each
  * channel is a stream of its own -- state, model slot, controls, rate, format, mask bit and list entry are per row as before; only
  * where its samples lie changes.  So stereo LRLR... from a WAV file or a capture device, or a [B][T][C] tensor, is passed where it
- * lies, with no de-interleaving pass before the call and no re-interleaving pass after it.
+ * lies, with no de-interleaving pass before the call and no re-interleaving pass after it.  (One
+ * suppression for the channels of a group: rnnoise_batch_set_gain_link, below.)
  * Without a layout row_stride = M * C and frame_stride = (n_rows / C) * M * C: each frame is [n_rows / C][M][C].  With a layout
  * (rnnoise_batch_set_pcm_layout, in either order with this call) the caller's two strides apply and row_stride is the distance between
  * GROUPS: a [G][T][C] tensor is frame_stride = M * C, row_stride = n_frames * M * C.  Stride validity is unchanged (positive multiples
@@ -305,6 +306,37 @@ RNNOISE_EXPORT int rnnoise_batch_set_pcm_channels(RNNoiseBatch *b, int channels)
 RNNOISE_EXPORT int rnnoise_batch_pcm_channels(const RNNoiseBatch *b);
 RNNOISE_EXPORT int rnnoise_amd_pcm_channels_fit(long frame_stride, long row_stride, int frame_samples, int channels, int n_rows,
                                                 int n_frames);
+
+/* Linked gains: one suppression per group of rows (the "link channels" switch of a stereo denoiser).  Each channel is a stream of its
+ * own, so by default it gets its own band gains and its own VAD gate: the noise floor of a stereo pair then moves by different
+ * amounts left and right and the image wanders.  With a link count K > 1 the rows of every rnnoise_batch_process* call are taken K at a
+ * time -- rows K * j .. K * j + K - 1 are a link group; a row is the stream index, or the list position in a list call, as for
+ * channels -- and per frame and group:
+ *   participants   the rows of the group whose stream has this frame and whose frame is not silent (the reference's E < 0.04
+ *                  short-cut).  A masked-out row, a list entry naming no stream and a silent row do not participate.
+ *   linked gain    per band b = 0 .. 31 a fold over the participants in ascending row order: m = the first participant's raw network
+ *                  gain g[b]; for each further participant's x: m = (x < m) ? x : m.  A NaN never replaces m; a NaN first value stays.
+ *   linked VAD     the same fold with (x > m) ? x : m over the participants' VADs; 0 without a participant.
+ * A participant uses the linked gain wherever the reference uses the network's gain after its network call: the pitch filter's r[],
+ * the decay cap and the lastg update (both stay per row, on the row's own lastg and energies), the floor of the controls and the
+ * per-bin interpolation.  What is linked is the network's decision; the release smoothing is not.  Every present row of the group,
+ * silent ones included, uses the linked VAD in place of its own in the `voice` decision of the controls (above), with its own thr
+ * and hold: rows that share thr and hold open and close together.  A silent row is otherwise processed as ever, an absent row is not
+ * touched at all.  The returned vad and gains stay each row's own raw values.
+ * K is independent of the channel count of rnnoise_batch_set_pcm_channels (planar callers link too; a stereo file sets both to 2), of
+ * rate, format, model slot, controls, layout, masks, lists and per-stream frame phase.  The drop-in API (rnnoise.h) and
+ * rnnoise_batch_train_features* ignore it.
+ * rnnoise_batch_set_gain_link returns the previous count; -1 with nothing changed for a NULL batch, k < 1, k > RNNOISE_AMD_MAX_CHANNELS
+ * or n_streams % k != 0.  Synchronous, like rnnoise_batch_set_pcm_channels.  k == 1 (the default) drops the feature: the batch then
+ * launches exactly what a batch that never saw the call launches.  A list call whose n_rows % K != 0 returns -1 with nothing
+ * launched.  Host-buffer calls with K > 1 take the staged convenience path; the pinned-ring path of rnnoise_batch_process[_s16] serves
+ * K == 1 only.
+ * A link count is configuration, not state: no state word is added and nothing goes into snapshots; rnnoise_batch_reset,
+ * reset_streams[_device], import_state, load_streams, every table setter, rnnoise_batch_set_pcm_rate and
+ * rnnoise_batch_set_pcm_channels leave it alone.
+ * rnnoise_batch_gain_link: the count in force, 1 by default; -1 for a NULL batch, without touching the device. */
+RNNOISE_EXPORT int rnnoise_batch_set_gain_link(RNNoiseBatch *b, int k);
+RNNOISE_EXPORT int rnnoise_batch_gain_link(const RNNoiseBatch *b);
 
 /* Several models in one batch: every stream runs with the model of its SLOT.  Slot 0 is the model the batch was created with;
  * rnnoise_batch_add_model puts another one into the next free slot (1 .. RNNOISE_AMD_MAX_MODELS - 1) and returns that slot: -1 on a

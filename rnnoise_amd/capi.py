@@ -62,6 +62,7 @@ EXPORTS = [
     "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
     "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
     "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
+    "rnnoise_batch_set_gain_link", "rnnoise_batch_gain_link",
     "rnnoise_amd_train_mix_check", "rnnoise_batch_train_levels_device", "rnnoise_amd_train_vad", "rnnoise_batch_train_mix_device",
     "rnnoise_amd_train_vad_device_available", "rnnoise_batch_train_levels_vad_device",
     "rnnoise_amd_train_rir_check", "rnnoise_amd_train_rir_work_bytes", "rnnoise_batch_train_rir_load_device",
@@ -233,6 +234,8 @@ def _load(path, debug):
         L.rnnoise_amd_pcm_layout_fits.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int]
         L.rnnoise_batch_set_pcm_channels.argtypes = [vp, C.c_int]
         L.rnnoise_batch_pcm_channels.argtypes = [vp]
+        L.rnnoise_batch_set_gain_link.argtypes = [vp, C.c_int]
+        L.rnnoise_batch_gain_link.argtypes = [vp]
         L.rnnoise_amd_pcm_channels_fit.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int]
         L.rnnoise_batch_add_model.argtypes = [vp, vp]
         L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
@@ -496,6 +499,20 @@ class Batch:
     @property
     def pcm_channels(self) -> int:
         return self._L.rnnoise_batch_pcm_channels(self.h)
+
+    def set_gain_link(self, k: int = 1) -> int:
+        """linked gains (rnnoise_batch_set_gain_link): with k > 1 the rows of every call are taken k at a time and each group gets one
+        suppression per frame -- per band the smallest raw gain of its non-silent present rows, and their largest VAD for the gate of
+        the controls.  vad / gains returned stay each row's own.  Returns the previous count; ValueError (nothing changes) unless
+        1 <= k <= MAX_CHANNELS and k divides the batch's streams.  Independent of set_pcm_channels: a stereo file sets both to 2."""
+        r = self._L.rnnoise_batch_set_gain_link(self.h, int(k))
+        if r < 0:
+            raise ValueError(f"link count {k} unsupported (1 .. {MAX_CHANNELS}, a divisor of the batch's {self.n} streams)")
+        return r
+
+    @property
+    def gain_link(self) -> int:
+        return self._L.rnnoise_batch_gain_link(self.h)
 
     def pcm_array(self, n_frames: int, dtype=np.float32, rows: int | None = None, fill=0):
         """a (n_frames, rows, frame) view, in the batch's PCM layout, of a fresh buffer that spans its frame slots and is filled with

@@ -18,6 +18,9 @@ batch; a stream whose file has ended is fed zeros and produces no more output.
 An input that starts with RIFF....WAVE is read as a WAV file (rnnoise_amd/wav.py: PCM16, A-law or mu-law, 1 to 8 channels, 8 to 48 kHz):
 its rate, format and channel count come from its header, each channel is one stream, its samples cross the batch interleaved as they lie
 in the file (rnnoise_batch_set_pcm_channels), and the output is <name>.denoised.wav with the input's header fields.
+--link-channels gives the channels of every multichannel WAV file one suppression (rnnoise_batch_set_gain_link): per frame and band
+the smallest gain of the file's non-silent channels, and one VAD for the gate, so that the stereo image stays put.  Mono inputs are
+unaffected.
 
 Training data (the reference's src/dump_features.c; rnnoise_amd/train_data.py): COUNT sequences of 98-float records from three RAW
 s16 48 kHz mono corpora, each uploaded once, everything else on the device:
@@ -56,7 +59,7 @@ def _describe(path, rate, fmt):
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
                   vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None,
-                  formats=None):
+                  formats=None, link_channels: bool = False):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 32000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
@@ -67,7 +70,8 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     An input that starts with RIFF....WAVE is a WAV file (rnnoise_amd/wav.py): its header gives its rate, its format and its channel
     count, every channel is one stream, and its samples go through the batch interleaved as they lie in the file
     (capi.Batch.set_pcm_channels) into <name>.denoised.wav under the input's header fields.  The inputs are grouped by channel count,
-    one batch per distinct count (a RAW file is mono).  Returns the frames of every input."""
+    one batch per distinct count (a RAW file is mono).  link_channels: the channels of each multichannel file form one link group
+    (capi.Batch.set_gain_link with the file's channel count).  Returns the frames of every input."""
     os.makedirs(out_dir, exist_ok=True)
     if rates is not None and len(rates) != len(inputs):
         raise ValueError(f"{len(rates)} rates for {len(inputs)} files")
@@ -86,13 +90,13 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     model = capi.Model(model_blob)
     for channels, group in groups.items():
         _denoise_group(model, group, channels, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold,
-                       rate_table=rates is not None, format_table=formats is not None)
+                       rate_table=rates is not None, format_table=formats is not None, link=link_channels)
     model.close()
     return [d["n_frames"] for d in files]
 
 
 def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold, rate_table,
-                   format_table):
+                   format_table, link=False):
     """the files of one channel count C through one batch of len(files) * C streams: file g's channel c is stream g * C + c"""
     FRAME = capi.FRAME * rate // 48000
     G, N = len(files), len(files) * C
@@ -111,6 +115,8 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
         batch.set_stream_controls(capi.controls_table(N, atten_limit_db, vad_gate, vad_hold))
     if C > 1:
         batch.set_pcm_channels(C)
+        if link:
+            batch.set_gain_link(C)
     ins = [open(d["path"], "rb") for d in files]
     outs = [open(os.path.join(out_dir, os.path.basename(d["path"]) + (".denoised.wav" if d["wav"] else ".denoised.raw")), "wb")
             for d in files]
@@ -216,6 +222,8 @@ def main(argv=None):
                    help="attenuation limit in dB: no band is suppressed by more (a floor on the band gains); default none")
     p.add_argument("--vad-gate", type=float, default=0.0, help="VAD threshold in [0, 1] below which output is muted (0: no gate)")
     p.add_argument("--vad-hold", type=int, default=0, help="frames the VAD gate stays open after the last voice frame")
+    p.add_argument("--link-channels", action="store_true",
+                   help="one suppression for the channels of each multichannel WAV file: linked band gains and VAD gate")
     p.add_argument("inputs", nargs="+")
     p = sub.add_parser("dump-features")
     p.add_argument("--model", required=True, help='"DNNw" weight blob: a batch needs one (the extraction runs no network)')
@@ -240,7 +248,7 @@ def main(argv=None):
         print(f"wrote {a.count} sequences, {n} records")
         return
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
-                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats)
+                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

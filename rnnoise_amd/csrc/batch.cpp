@@ -236,6 +236,10 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
   // (packed) as in the caller's; the strides then place group slots of chan rows.  The pinned ring (hk) never sees channels
   const int chan = hk ? 1 : b->channels;
   if (listed && n_rows % chan) return -1;
+  // Linked gains (rnnoise_batch_set_gain_link): the rows are taken `link` at a time too, whatever the channel count; the pinned ring
+  // (hk) never sees a link either (shim.h: batch_host_call_staged)
+  const int link = hk ? 1 : b->link;
+  if (listed && n_rows % link) return -1;
   const bool laid = b->row_stride && !c.packed && !hk;
   if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, batch_frame_samples(b), chan, listed ? n_rows : b->n, n_frames))
     return -1;
@@ -415,6 +419,7 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
     {
       TimedLaunch t(b, 2);
       b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
+      g.link = link > 1 ? link : 0;  // (rn_dev.h: RnGroupDev::link -- K3's copy alone; 0: today's launch)
       HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * fstep, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
     }
     if (hk && hk->after_k3(f, st)) return -1;
@@ -472,7 +477,7 @@ int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c) {
   // Interleaved channels (rnnoise_batch_set_pcm_channels): what travels is the group slot, C rows of M samples interleaved, and the
   // device works on the staging buffer with the same channel count (batch_process_device_impl: packed) -- no de-interleave here
   const size_t C = b->channels;
-  if (rows % C) return -1;
+  if (rows % C || rows % (size_t)b->link) return -1;
   const bool laid = b->row_stride != 0;
   if (laid && !rn_pcm_channels_fit(b->frame_stride, b->row_stride, (int)M, (int)C, (int)rows, n_frames)) return -1;
   ON_DEVICE(b->device);

@@ -208,6 +208,21 @@ extern "C" int rnnoise_amd_pcm_channels_fit(long frame_stride, long row_stride, 
              : 0;
 }
 
+// ---- linked gains (include/rnnoise_amd.h) ----
+// One number of the batch, with the rule of the channel count.  A process call hands it to K3 alone (rn_dev.h: RnGroupDev::link); at 1
+// nothing is handed on and every launch is the one of a batch that never saw these calls.
+extern "C" int rnnoise_batch_set_gain_link(RNNoiseBatch *b, int k) {
+  if (!b || !rn_pcm_channels_ok(k, b->n)) return -1;
+  const int old = b->link;
+  if (k == old) return old;
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());  // (synchronous: a call in flight keeps what it was launched with)
+  b->link = k;
+  return old;
+}
+
+extern "C" int rnnoise_batch_gain_link(const RNNoiseBatch *b) { return b ? b->link : -1; }
+
 // ---- per-stream PCM formats (include/rnnoise_amd.h) ----
 // The [N] format bytes live in fmt_map; while a table is set (g.pcm_fmt) K0 expands and K3 compresses the rows of the companded
 // streams in every int16 call (rn_dev.h: rn_stream_fmt), and those calls plan K0 one wave per stream (dispatch.h).

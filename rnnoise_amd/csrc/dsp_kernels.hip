@@ -1795,12 +1795,54 @@ __device__ __forceinline__ void synthesis_body(const RnGroupDev &g, const RnTabl
     }
   }
 
+  // linked gains (rn_dev.h: RnGroupDev::link): one uniform branch on the count, behind the requests above and in front of their first
+  // use.  The two folds run over the group's participants -- the rows whose silence word of this frame (K1) is 0: present and not
+  // silent -- in ascending row order: per band the smallest raw gain of the network (lanes 0..31), and the largest VAD; `x < m ? x : m`
+  // and `x > m ? x : m` from the first participant's value on, so a NaN never replaces a value and a NaN first value stays.  A
+  // participant goes on with the folded gains in place of its own (the pitch filter's r[], the decay cap and the lastg update on its
+  // OWN lastg, the floor, the per-bin gains); the folded VAD, 0 without a participant, decides the gate of every present row of the
+  // group, silent ones too.  A rolled loop with running values over FOUR members per trip, their twelve words requested together
+  // (member j's stream, silence word and VAD are wave-uniform): one memory round trip up to K = 4, two up to 8.  Unrolled eight times
+  // with every load up front the branch fits the registers too, but its 400 instructions cost the launches that skip it; one member
+  // per trip is the smallest code and the slowest link
+  bool own_vad = true;  // the gate below sees the row's own VAD (0 on a silent frame)
+  if (g.link > 1) {
+    float m = 0.f, link_vad = 0.f;
+    bool none = true;
+    const int k = g.link;
+#pragma unroll 1
+    for (int j0 = 0; j0 < k; j0 += 4) {  // four members per trip: their twelve words are requested together
+      float x[4], vj[4];
+      int sil[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int sj = j0 + u < k ? __builtin_amdgcn_readfirstlane(rn_link_stream(g, at.i, k, j0 + u)) : -1;
+        const int q = sj >= 0 ? sj : s;  // (a member past the group, or a list entry naming no stream: this row's words, not used)
+        sil[u] = g.silence[q];
+        vj[u] = g.vad[q];
+        x[u] = g.gains[(size_t)q * RN_NB_BANDS + (lane & (RN_NB_BANDS - 1))];
+        if (sj < 0) sil[u] = 2;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (__builtin_amdgcn_readfirstlane(sil[u]) != 0) continue;
+        const float v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(vj[u])));
+        m = none ? x[u] : (x[u] < m ? x[u] : m);
+        link_vad = none ? v : (v > link_vad ? v : link_vad);
+        none = false;
+      }
+    }
+    if (lane < RN_NB_BANDS && !silence) gi = m;
+    ctl_vad = link_vad;
+    own_vad = false;
+  }
+
   bool gate = false;
   if (g.ctl) {  // counter, gate and floor (include/rnnoise_amd.h): NaN as 0, each value clamped into its range, hold truncated
     auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
     auto clamp = [](float v, float hi) { return v > 0.f ? (v < hi ? v : hi) : 0.f; };
     ctl_floor = clamp(uni(ctl_floor), 1.f);
-    const float thr = clamp(uni(ctl_thr), 1.f), vad = silence ? 0.f : uni(ctl_vad);
+    const float thr = clamp(uni(ctl_thr), 1.f), vad = (own_vad && silence) ? 0.f : uni(ctl_vad);
     const int hold = (int)clamp(uni(ctl_hold), 65535.f);
     int c = __builtin_amdgcn_readfirstlane(ctl_c);
     c = (thr > 0.f && !(vad >= thr)) ? min(c + 1, RN_CTL_NONE) : 0;  // (a NaN vad is no voice)

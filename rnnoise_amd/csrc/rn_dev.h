@@ -204,6 +204,15 @@ struct RnGroupDev {
   // in their one-wave-per-stream forms (dispatch.h: the lane = stream K0 is never planned for such a call); r is the list position in
   // a list call.  K3 stores single elements: the siblings' samples in between belong to other workgroups, maybe of other launches.
   int pcm_chan;
+  // Linked gains (include/rnnoise_amd.h: rnnoise_batch_set_gain_link).  0: every row keeps its own gains and VAD (every launch is
+  // today's).  K = 2 .. 8: the rows of the launch are taken K at a time -- rows K j .. K j + K - 1 are a link group, a row being the
+  // stream index or the list position -- and K3 (synthesis_body) folds the raw gains and the VADs of the group's PARTICIPANTS, the rows
+  // whose silence word of this frame is 0, in ascending row order: per band the smallest gain, and the largest VAD.  A participant
+  // shapes its spectrum with the folded gains; every present row decides its gate with the folded VAD.  Set only on the copies the
+  // step hands K3 (batch.cpp); b->g never carries it.  K3 reads what the network and K1 of this frame wrote for the siblings --
+  // gains, vad, silence -- and nothing a sibling's K3 workgroup writes.  (The int fills the padding in front of pcm_fmt: no
+  // kernel's arguments move.)
+  int link;
   // Per-stream PCM formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_formats).  Null pcm_fmt: every row of an int16 call holds
   // int16 samples (every launch is today's).  Set, stream s's rows of the int16 calls hold pcm_fmt[s]: RN_PCM_ULAW / RN_PCM_ALAW
   // (g711.h) one byte per sample in the FIRST 480 / L_s bytes of the row -- K0 expands them where it reads the row (hp_one_body,
@@ -498,6 +507,18 @@ __device__ __forceinline__ RnStreamAt rn_stream_at(const RnGroupDev &g, const Rn
   return a;
 }
 #endif
+// Stream of member j of the link group that row `row` belongs to (rn_dev.h: RnGroupDev::link = k): row k * (row / k) + j of the launch
+// -- the stream of that index, or that list entry's in a list call, range-checked as rn_stream_at checks its own.  -1: a list entry
+// naming no stream.  row is wave-uniform (RnStreamAt::i) and so is the result.  Host code compiles it too (tests/csrc)
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int rn_link_stream(const RnGroupDev &g, int row, int k, int j) {
+  const int r = (int)((unsigned)row / (unsigned)k * (unsigned)k) + j;
+  if (!g.list) return r;
+  const int e = g.list[r];
+  return (unsigned)e < (unsigned)g.n_stride ? e : -1;
+}
 // rows a launch of g works on: one workgroup (or tile row) per stream, or per list entry in a list call
 static inline int rn_launch_rows(const RnGroupDev *g) { return g->list ? g->list_n : g->n_streams; }
 #ifdef __HIPCC__

@@ -218,6 +218,10 @@ struct RNNoiseBatch {
   // `channels` at a time; 1: none.  The process calls hand it to K0 / K3 (rn_dev.h: RnGroupDev::pcm_chan, 0 for 1); b->g itself
   // never carries it.  Configuration, not state
   int channels = 1;
+  // linked gains (include/rnnoise_amd.h: rnnoise_batch_set_gain_link): the rows of every process call are taken `link` at a time and
+  // K3 gives each group one set of band gains and one VAD for the gate; 1: none.  The step hands it to K3 alone (rn_dev.h:
+  // RnGroupDev::link, 0 for 1); b->g itself never carries it.  Configuration, not state
+  int link = 1;
   // per-stream models (include/rnnoise_amd.h: rnnoise_batch_add_model): slot k's model and its device copy (slot 0's: model / m),
   // and model_map, the [N] slot bytes the network launches read (rn_dev.h: RnGroupDev::model_of), there from the first add_model on;
   // g.model_of / g.n_models are set from then on
@@ -393,5 +397,5 @@ inline int batch_frame_samples(const RNNoiseBatch *b) { return b->g.rs_L ? b->g.
 // whether a host call takes the staged path instead of the pinned ring / bounce chunks of host_io.cpp: at a PCM rate other than 48 kHz
 // or with a rate table, with a PCM layout, with interleaved channels, and the int16 calls of a batch with a format table
 inline bool batch_host_call_staged(const RNNoiseBatch *b, bool s16) {
-  return b->g.rs_L || b->row_stride || b->channels > 1 || (s16 && b->g.pcm_fmt);
+  return b->g.rs_L || b->row_stride || b->channels > 1 || b->link > 1 || (s16 && b->g.pcm_fmt);
 }

@@ -173,13 +173,17 @@ class RNNoiseOp:
         the entry point the same from call to call."""
         return self.torch.ops.rnnoise_amd.process_streams(pcm, active, self.state, self.handle)
 
-    def process_channels(self, pcm, active=None):
+    def process_channels(self, pcm, active=None, link=None):
         """pcm (G, T * (M), C) float32 or int16 CUDA tensor with G * C == n_streams: interleaved channels, channel c of group g
         being stream g * C + c.  The batch reads it and writes the result of the same shape where they lie
         (rnnoise_batch_set_pcm_channels + rnnoise_batch_set_pcm_layout: no de-interleave and no transpose); active (T, G * C) bool /
         uint8 or None as in process_masked.  -> out (G, T * (M), C), vad (T, G * C), gains (T, G * C, 32)
         (torch.ops.rnnoise_amd.process_channels).  Channel count and layout are set when they change -- synchronous calls, so keep
-        T, C and the entry point the same from call to call."""
+        T, C and the entry point the same from call to call.
+        link: True gives the C channels of every group one suppression (set_gain_link(C): rnnoise_batch_set_gain_link), False
+        none (set_gain_link(1)), None leaves the link count as it is.  vad and gains returned stay each channel's own."""
+        if link is not None:
+            self.set_gain_link(int(pcm.shape[2]) if link else 1)
         return self.torch.ops.rnnoise_amd.process_channels(pcm, active, self.state, self.handle)
 
     def reset_streams(self, idx):
@@ -250,6 +254,13 @@ class RNNoiseOp:
         after the last voice frame -- each a scalar or a per-stream sequence / array of N.  Synchronous; ValueError on a value out of
         range.  clear_stream_controls() drops the table."""
         self.batch.set_stream_controls(capi.controls_table(self.n, limit_db, vad_threshold, hold_frames))
+
+    def set_gain_link(self, k=1):
+        """linked gains (include/rnnoise_amd.h: rnnoise_batch_set_gain_link): the rows of every call taken k at a time, each group with
+        one set of band gains and one VAD for the gate per frame; 1: none.  Synchronous, and only when the count changes; ValueError
+        unless 1 <= k <= 8 and k divides the op's streams.  Returns the previous count."""
+        old = self.batch.gain_link
+        return self.batch.set_gain_link(k) if old != k else old
 
     def clear_stream_controls(self):
         """no controls: every stream back to the reference's suppression (the table and the gate counters are dropped)"""
