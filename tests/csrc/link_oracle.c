@@ -35,8 +35,9 @@ void rno_link_fold(int n, const float *x, const float *v, float *g_link, float *
  * without a participant).  Returns the number of participants, -1 for a K outside 1 .. 8 */
 int rno_link_group_frame(int K, const RnoModel *const *m, float *st_all, int *c, const float *ctl, const int *present, float *out_all,
                          const float *in_all, RnoRecord *rec, float *vad, float *g_link_out, float *vad_link_out) {
-  static cpx X[LINK_MAX][NFREQ], P[LINK_MAX][NFREQ];
-  static float Ex[LINK_MAX][NB], Ep[LINK_MAX][NB], Exp[LINK_MAX][NB], g[LINK_MAX][NB];
+  /* (per thread: tests/stream_mix.py runs one group per thread, and the ctypes call releases the GIL) */
+  static _Thread_local cpx X[LINK_MAX][NFREQ], P[LINK_MAX][NFREQ];
+  static _Thread_local float Ex[LINK_MAX][NB], Ep[LINK_MAX][NB], Exp[LINK_MAX][NB], g[LINK_MAX][NB];
   float x[NFRAME], xw[NWIN], features[RN_NB_FEATURES], gf[NFREQ], g_link[NB], part_g[LINK_MAX * NB], part_v[LINK_MAX];
   float vad_link = 0, gain;
   int silence[LINK_MAX];

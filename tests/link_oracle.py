@@ -85,7 +85,17 @@ class LinkGroup:
         assert n >= 0
         gains = np.stack([np.frombuffer(rec[k].gains, np.float32).copy() for k in range(K)])
         silence = np.array([rec[k].silence if pres[k] else 2 for k in range(K)])
-        return dict(out=out, vad=vad, gains=gains, silence=silence, n=n, g_link=g_link, vad_link=vad_link[0], present=pres)
+        features = np.stack([np.frombuffer(rec[k].features, np.float32).copy() for k in range(K)])
+        pitch = np.array([rec[k].pitch for k in range(K)], np.int32)
+        return dict(out=out, vad=vad, gains=gains, silence=silence, n=n, g_link=g_link, vad_link=vad_link[0], present=pres,
+                    features=features, pitch=pitch)
+
+    def reset_row(self, k, counter=True):
+        """row k back to a new stream's state and gate counter (include/rnnoise_amd.h: rnnoise_batch_reset_streams); counter=False
+        leaves the counter, which no reset of the product does"""
+        self.state[k] = 0
+        if counter:
+            self.c[k] = C_NONE
 
     def run(self, pcm, active=None):
         """pcm (T, K, 480), active (T, K) or None -> dict of (T, ...) arrays of process()'s entries"""

@@ -1,5 +1,6 @@
 """One mixed block of streams for the at-size parity tests (plain helper module: tests/test_stream_mix_cpu.py checks what the block
-covers, tests/test_gpu_at_size.py, tests/test_dropin_gpu.py run it).
+and its dressings cover; tests/test_gpu_at_size.py runs it in lock-step calls, through masked and list calls, with poisoned streams
+and under linked gains; tests/test_dropin_gpu.py runs it through the drop-in API).
 
 `block()` is B = 389 streams x 30 frames of float PCM.  The at-size tests lay a batch out as copies of it (stream i takes block
 stream i mod B); B is prime, so the copies land at shifting offsets modulo the 4 streams of an analysis workgroup, the 16 of a tile
@@ -19,6 +20,11 @@ The presence schedule (`KINDS`, `presence()`, `LISTED`, `RESET`) runs the same b
 stream-list calls and lock-step calls on a batch in per-stream frame phase, and a per-stream reset between two calls.  It is defined
 on block positions, so every copy of a position gets the same frames and one oracle run per position (`oracle_block` with
 `presence` and `resets`) covers the whole batch.
+
+The link dressing (`LINK_CASES`, `controls()`, `slots()`, `link_presence()`, `link_list_rows()`, `oracle_groups`) runs the block
+under a link count K (include/rnnoise_amd.h: rnnoise_batch_set_gain_link) with a control record and a model slot on every position:
+group j of a batch is streams K j .. K j + K - 1, at positions g0 .. g0 + K - 1 with g0 = (K j) mod B.  Rows are dressed by position,
+groups by g0 -- a list call lists whole groups --, so one run of the link oracle per g0 covers every copy.
 """
 from __future__ import annotations
 
@@ -100,7 +106,8 @@ def labels():
 
 
 @functools.lru_cache(None)
-def _presence():
+def _presence_mask():
+    """(T, B) bool: the schedule before a list call's choice of positions -- the mask of the masked calls, all ones in lock-step calls"""
     rng = _rng(6)
     lab, nth = labels()
     a = rng.random((T, B)) < rng.uniform(0.45, 0.95, B)
@@ -128,13 +135,19 @@ def _presence():
             a[fr, p] = True
             a[fr[0] if name.startswith("first") else fr[-1], p] = False
     for c, kind in enumerate(KINDS):
-        fr = list(call_frames(c))
         if kind == "lock":
-            a[fr] = True
-        elif kind == "list":
+            a[list(call_frames(c))] = True
+    return a
+
+
+@functools.lru_cache(None)
+def _presence():
+    a = _presence_mask().copy()
+    for c, kind in enumerate(KINDS):
+        if kind == "list":
             off = np.ones(B, bool)
             off[list(LISTED[c])] = False
-            a[np.ix_(fr, np.flatnonzero(off))] = False
+            a[np.ix_(list(call_frames(c)), np.flatnonzero(off))] = False
     return a.astype(np.uint8)
 
 
@@ -287,4 +300,290 @@ def oracle_block(blob, pcm, streams=None, collect_state=True, presence=None, res
         out["state"] = np.stack([r["state"] for r in runs])
     if present is not None:
         out["present"] = present[:, streams]
+    return out
+
+
+# ---- the link dressing: the block under rnnoise_batch_set_gain_link, with controls, model slots and group-wise list calls ----
+# With link count K, group j of a batch is streams K j .. K j + K - 1; its member k sits at block position (g0 + k) mod B with
+# g0 = (K j) mod B.  B is prime, so a batch of more than B streams has groups at every g0 that K j reaches, the ones that wrap from
+# position 388 to 0 among them, and one position is member 0 of one group and member 1 of another.  Whatever dresses a row is a function
+# of its position, whatever dresses a group a function of its g0: one LinkGroup run per g0 (oracle_groups) covers every copy.
+#
+# LINK_CASES: (streams, network path or None for the batch's default, K), n % K == 0 and n % B != 0.  On 256 CUs with the default
+# switches (test_stream_mix_cpu.py holds them to it):
+LINK_CASES = [
+    (252, 0, 2),        # rn_nn_one_kernel, rn_synthesis_few_kernel (list calls too: ~70 % of the rows), one-wave high-pass
+    (390, 0, 3),        # rn_nn_one_kernel, rn_synthesis_kernel
+    (390, 1, 2),        # tile 16 in one-frame calls, tile 8 in pipelined ones
+    (390, 2, 3),        # layer-wise network, rn_nn_gru_w8_kernel; the tile kernels in its list calls
+    (1032, 0, 8),       # rn_nn_vector_kernel (rn_nn_one_kernel in its list calls)
+    (2568, None, 8),    # rn_hp_kernel, tile 16 / tile 8, rn_analysis_kernel in lock-step calls
+    (16416, None, 2),   # layer-wise network, rn_nn_gru_kernel (w4): 257 groups of 64 on 256 CUs, the last one half full
+]
+LINK_KS = tuple(sorted({K for _, _, K in LINK_CASES}))
+
+
+def link_g0(n, K):
+    """g0 of every link group of a batch of n copies of the block, (n // K,) int"""
+    assert n % K == 0
+    return (K * np.arange(n // K)) % B
+
+
+def link_groups(K, common=False):
+    """the g0 that occur for link count K in some case of LINK_CASES (common: in every one of them), ascending"""
+    sets = [{int(g) for g in link_g0(n, k)} for n, _, k in LINK_CASES if k == K]
+    return sorted(set.intersection(*sets) if common else set.union(*sets))
+
+
+def link_index(n, K):
+    """(n,) int: where stream i of a batch of n copies finds its row in arrays indexed [g0, member] flattened to [g0 * K + member]"""
+    i = np.arange(n)
+    return (i // K * K) % B * K + i % K
+
+
+# thr of controls(): the oracle's VAD on the block (default blob, no link) is below 0.05 in 2 % of the live row-frames, below 0.3 in
+# 26 %, below 0.5 in 53 %, below 0.7 in 81 % and below 0.9 in 96 %, so every value below has rows on both sides of it in one group;
+# 0.05 is a gate that nearly any live sibling opens for a silent row (the silent row's own VAD is 0)
+_CTL_FLOOR = (0.0, 0.05, 0.1, 0.25, 0.5)
+_CTL_THR = (0.0, 0.05, 0.3, 0.5, 0.7, 0.9)
+_CTL_HOLD = (0, 0, 1, 2, 5)
+RESET_HOLD = 20
+
+
+@functools.lru_cache(None)
+def _controls():
+    rng = _rng(7)
+    lab, _ = labels()
+    on = rng.random(B) < 0.47
+    quiet = [p for p in range(B) if lab[p] in ("zero_runs", "threshold", "all_zero")]
+    on[quiet[::2]] = True                                  # silent rows with a gate of their own, and silent rows without one
+    ctl = np.zeros((B, 3), np.float32)
+    for p in np.flatnonzero(on):
+        f, t, h = rng.choice(_CTL_FLOOR), rng.choice(_CTL_THR), rng.choice(_CTL_HOLD)
+        if lab[p] in ("zero_runs", "threshold", "all_zero") and t == 0:
+            t = _CTL_THR[1 + p % 3]
+        if f == 0 and t == 0:
+            f = _CTL_FLOOR[1 + p % 4]
+        ctl[p] = f, t, h if t else 0
+    for p in range(0, B - 1, 5):                           # neighbours that share thr and hold: they open and close together
+        if ctl[p, 1] > 0 and on[p + 1]:
+            ctl[p + 1, 1:] = ctl[p, 1:]
+    # every other RESET position: a high threshold and a long hold.  Such a gate opens at the group's first loud frame and would stay
+    # open for the rest of the run; the restart puts the counter back to 65536 ("no voice yet"), so the gate is closed again until the
+    # next frame at thr -- a reset that forgot the counter shows in `out`
+    for i, p in enumerate(RESET[::2]):
+        ctl[p, 1:] = (0.7, 0.9)[i % 2], RESET_HOLD
+    return ctl
+
+
+def controls():
+    """(B, 3) float32: the control record {floor, thr, hold} of every block position; about half keep the all-zero record"""
+    return _controls().copy()
+
+
+@functools.lru_cache(None)
+def _slots():
+    s = (_rng(8).random(B) < 1 / 3).astype(np.uint8)
+    for p in range(2 * B):                                 # never a whole run of 8 (cyclic: groups wrap from 388 to 0)
+        if all(s[(p + k) % B] for k in range(8)):
+            s[(p + 7) % B] = 0
+    return s
+
+
+def slots():
+    """(B,) uint8: the model slot of every block position -- slot 1 (tests/golden/little.blob.xz) on about a third, never on 8 in a row"""
+    return _slots().copy()
+
+
+def _members(K):
+    return tuple(sorted({0, K // 2, K - 1})) if K > 2 else (0, 1, 1)
+
+
+@functools.lru_cache(None)
+def link_listed(K, c):
+    """the g0 of the groups list call c lists under link count K: about 70 % of all g0, the groups of the hand-made rows that must
+    show in a list call always.  A function of g0 (and K) alone"""
+    must = {(SPECIAL[k] - m) % B for k in ("once", "alternating", "first1", "last1") for m in range(K)}
+    return tuple(sorted(set(_pick(_rng(300 + c), 0.7)) | must))
+
+
+@functools.lru_cache(None)
+def link_replaced(K, c):
+    """the three (g0, member, list entry) of list call c whose list entry names no stream: the first member of one group, a middle one
+    of another and the last of a third (K = 8: members 0, 4, 7; K = 2: 0, 1, 1), groups that every case of K has and the call lists,
+    away from the hand-made rows.  The stream is absent for that call in EVERY copy of the group -- its history must not depend on
+    the copy --: one copy's entry is replaced (link_list_rows), the others are listed and masked out for the call (link_presence)"""
+    near = {(p - m) % B for p in SPECIAL.values() for m in range(K)}
+    fr = list(call_frames(c))
+    there = _presence_mask()[fr]
+    out, rng = [], _rng(400 + 10 * K + c)
+    for m, e in zip(_members(K), OUT_OF_RANGE):            # a sibling is there in every frame of the call
+        ok = [g for g in link_groups(K, common=True) if g in set(link_listed(K, c)) and g not in near and g not in {x[0] for x in out}
+              and there[:, [(g + k) % B for k in range(K) if k != m]].any(1).all()]
+        out.append((int(rng.choice(ok)), m, e))
+    return tuple(out)
+
+
+LONE_CALL = 6                                              # the masked call in which the hand-made groups have one row: a silent one, a voice
+
+
+@functools.lru_cache(None)
+def link_lone(K):
+    """(g0, member) of a hand-made group that every case of K has and that holds the all-zero stream, or None without one (K = 2): from
+    the second frame of the masked call LONE_CALL on every sibling is absent and the all-zero row present -- a present row and no
+    participant, for K = 8 with the row in the second half of the group"""
+    z = labels()[0].index("all_zero")
+    at = [((z - m) % B, m) for m in range(K) if (z - m) % B in link_groups(K, common=True)]
+    return at[-1] if at else None
+
+
+@functools.lru_cache(None)
+def link_solo(K):
+    """(g0, member) of a second hand-made group that every case of K has, all of its rows fuzz_pcm voices (never silent): from the
+    second frame of the masked call LONE_CALL on the member is present and every sibling absent -- exactly one participant, for
+    K = 8 the sixth row (the second trip of the fold's loop, not its first word)"""
+    lab = labels()[0]
+    m = 2 * K // 3
+    taken = {(p - k) % B for p in SPECIAL.values() for k in range(K)}
+    if link_lone(K):
+        taken |= {(link_lone(K)[0] + d) % B for d in range(-K + 1, K)}
+    ok = [g for g in link_groups(K, common=True) if g not in taken and all(lab[(g + k) % B].startswith("fuzz") for k in range(K))]
+    return ok[len(ok) // 2], m
+
+
+@functools.lru_cache(None)
+def _link_presence(K):
+    base = _presence_mask()
+    g0 = np.arange(B)
+    a = np.stack([base[:, (g0 + k) % B] for k in range(K)], axis=-1)          # (T, B, K)
+    for c, kind in enumerate(KINDS):
+        if kind == "list":
+            fr = list(call_frames(c))
+            off = np.ones(B, bool)
+            off[list(link_listed(K, c))] = False
+            a[np.ix_(fr, np.flatnonzero(off))] = False
+            for g, m, _ in link_replaced(K, c):
+                a[fr, g, m] = False
+    if link_lone(K):                                       # the hand-made group: the all-zero row there, every sibling absent
+        g, m = link_lone(K)
+        fr = list(call_frames(LONE_CALL))[1:]
+        a[np.ix_(fr, [g], [k for k in range(K) if k != m])] = False
+        a[fr, g, m] = True
+    g, m = link_solo(K)                                    # the second one: one voice there, every sibling absent
+    fr = list(call_frames(LONE_CALL))[1:]
+    a[np.ix_(fr, [g], [k for k in range(K) if k != m])] = False
+    a[fr, g, m] = True
+    return a
+
+
+def link_presence(K):
+    """(T, B, K) bool, indexed [frame, g0, member]: the schedule of KINDS for linked runs.  Masked and lock-step calls: presence()'s
+    mask of the member's position.  A list call lists whole groups (link_listed), so a group keeps its members in every call and a
+    row's history is a function of (g0, member); the member whose entry link_replaced() takes is absent for that call.  Two
+    hand-made groups (link_lone, link_solo) have one row on its own from the second frame of the masked call LONE_CALL on"""
+    return _link_presence(K).copy()
+
+
+def link_list_rows(n, K, c):
+    """the stream list of list call c on a batch of n copies under link count K: every copy of the groups link_listed(K, c) in a fixed
+    pseudo-random group order, members ascending, and OUT_OF_RANGE's three entries in place of one member each: of the first, a middle
+    and the last copy of link_replaced()'s groups.  (rows int32, g0 of every row, member of every row)"""
+    g0 = link_g0(n, K)
+    keep = np.zeros(B, bool)
+    keep[list(link_listed(K, c))] = True
+    order = _rng(200 + c).permutation(np.flatnonzero(keep[g0]))
+    rows = (K * order[:, None] + np.arange(K)).astype(np.int64)
+    for x, (g, m, e) in enumerate(link_replaced(K, c)):
+        copies = np.flatnonzero(g0[order] == g)
+        at = copies[np.argsort(order[copies])][(0, len(copies) // 2, -1)[x]]
+        rows[at, m] = n if e is None else e
+    return rows.reshape(-1).astype(np.int32), np.repeat(g0[order], K), np.tile(np.arange(K), len(order))
+
+
+def link_call_plan(n, K, c):
+    """call_plan() for a linked run: what call c of KINDS hands a batch of n copies under link count K.  "kind", "frames", "rows" (a
+    list call's int32 stream list, else None), "src" (the block position of every row), "gm" (its g0 * K + member: where
+    oracle_groups' arrays, flattened over [g0, member], hold it), "present" and "active" as call_plan() has them"""
+    frames = call_frames(c)
+    pres = _link_presence(K)[frames.start:frames.stop].reshape(len(frames), B * K)
+    rows = active = None
+    if KINDS[c] == "list":
+        rows, g0, mem = link_list_rows(n, K, c)
+        named = (rows >= 0) & (rows < n)
+        gm = g0 * K + mem
+        present = pres[:, gm] & named
+        active = np.where(named, present, True).astype(np.uint8)
+    else:
+        gm = link_index(n, K)
+        g0, mem = gm // K, gm % K
+        present = pres[:, gm]
+        if KINDS[c] == "masked":
+            active = present.astype(np.uint8)
+    present = np.ascontiguousarray(present)
+    active = None if active is None else np.ascontiguousarray(active)
+    return dict(kind=KINDS[c], frames=frames, rows=rows, src=(g0 + mem) % B, gm=gm, present=present, active=active)
+
+
+def link_state_streams(n, K):
+    """one stream per (g0, member) of a batch of n copies under link count K, each pair from a different copy of its group:
+    (streams, their g0 * K + member)"""
+    g0 = link_g0(n, K)
+    streams, gm = [], []
+    for x, g in enumerate(sorted(set(g0.tolist()))):
+        copies = np.flatnonzero(g0 == g)
+        for k in range(K):
+            streams.append(int(K * copies[(7 * (K * x + k)) % len(copies)] + k))
+            gm.append(g * K + k)
+    return np.array(streams), np.array(gm)
+
+
+def oracle_groups(blobs, pcm, K, ctl, slots, presence=None, resets=None, groups=None, restart_counter=True):
+    """the link oracle (tests/link_oracle.py: LinkGroup) over the groups of the block under link count K, one run per g0 (all of them,
+    or `groups`), several at a time.  blobs: the model blob of every slot; ctl (B, 3) and slots (B,) by block position; presence
+    (T, B, K) as link_presence() gives it, None: every row has every frame; resets: positions that restart as new streams -- state
+    and gate counter (65536: include/rnnoise_amd.h, rnnoise_batch_reset_streams) -- at the first frame of call RESET_BEFORE
+    (restart_counter=False: the state alone, what a reset that forgot the counter would do -- for the tests of the tests).
+    Arrays indexed [frame, g0, member]: out, vad, gains, features, pitch, silence (each row's own raw values; an absent frame holds
+    what the header promises: out 0 for untouched, vad 0, 32 zero gains, silence 2), present; [frame, g0]: n (participants), g_link,
+    vad_link; [g0, member]: state, gate (the counter after the last frame); [g0]: ran.  Groups that were not run hold zeros"""
+    import link_oracle
+    Tn = pcm.shape[0]
+    groups = list(range(B)) if groups is None else [int(g) for g in groups]
+    pres = None if presence is None else np.asarray(presence)[:Tn] != 0
+    resets = set(resets or ())
+    cut = call_frames(RESET_BEFORE)[0]
+    link_oracle.lib()
+
+    def one(g0):
+        pos = [(g0 + k) % B for k in range(K)]
+        grp = link_oracle.LinkGroup([blobs[slots[p]] for p in pos], K, ctl[pos])
+        frames = []
+        for t in range(Tn):
+            if t == cut:
+                for k, p in enumerate(pos):
+                    if p in resets:
+                        grp.reset_row(k, counter=restart_counter)
+            frames.append(grp.process(pcm[t, pos], None if pres is None else pres[t, g0]))
+        r = {k: np.stack([np.asarray(f[k]) for f in frames]) for k in frames[0]}
+        r["state"], r["gate"] = grp.state.copy(), grp.c.copy()
+        return r
+
+    workers = max(1, min(16, len(os.sched_getaffinity(0))))
+    first = one(groups[0])                                                     # (the library's tables are built by its first call)
+    with ThreadPoolExecutor(workers) as pool:
+        runs = [first] + list(pool.map(one, groups[1:]))
+    out = {}
+    for k, v in first.items():
+        lead = (B,) if k in ("state", "gate") else (Tn, B)
+        out[k] = np.zeros(lead + v.shape[len(lead) - 1:], v.dtype)
+    out["silence"][:] = 2
+    out["ran"] = np.zeros(B, bool)
+    for g0, r in zip(groups, runs):
+        out["ran"][g0] = True
+        for k, v in r.items():
+            if k in ("state", "gate"):
+                out[k][g0] = v
+            else:
+                out[k][:, g0] = v
+    out["present"] = out["present"] != 0
     return out

@@ -4,7 +4,10 @@ counters -- over 12 frames in calls of 5 + 1 + 6, so the pipelined and the one-f
 up to 256 rows; wide: 264), K = 2, 3 and 8; masks with an absent sibling and silent frames; a list call over non-adjacent streams;
 controls with a gate; mixed rates and G.711 formats, two model slots, interleaved int16 under a layout and the staged host forms inside
 one group; K = 1 after K = 2 and groups of identical rows against the unlinked batch; the setter on a live batch; the torch op; the CLI.
-The rows of a group carry different signals, and every oracle run first shows on its own numbers that the link bites."""
+The rows of a group carry different signals, and every oracle run first shows on its own numbers that the link bites.
+At these sizes the dispatch plan picks rn_nn_one_kernel, the one-wave high-pass and the one-stream analysis kernel throughout; every
+other form of every stage under a link -- with controls, two model slots, masks and group-wise list calls on the mixed stream block --
+runs in tests/test_gpu_at_size.py (test_stream_mix_linked_at_every_form, test_stream_mix_linked_masked_and_listed_at_every_form)."""
 import functools
 
 import numpy as np

@@ -5,7 +5,8 @@ stay bit-identical to each other (no cross-talk, no dependence on the tile / CU 
 itself is checked bit for bit against the oracle, including a stream that starts silent inside a live MFMA tile.  The mixed
 block of tests/stream_mix.py (389 streams of every kind, compared stream by stream) runs at batch sizes that reach every kernel
 form, with NaN / Inf in copies of one of its streams, and through masked, stream-list and per-stream-phase lock-step calls with
-NaN in every absent row.  Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
+NaN in every absent row; and under linked gains with controls and two model slots (stream_mix.LINK_CASES), the same two ways.
+Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
 import os
 import subprocess
 import sys
@@ -316,6 +317,193 @@ def test_stream_mix_masked_and_listed_at_every_form(blob_default, rcp_profile, n
         assert_bits_equal(b.export_state(s_), st_, f"state of stream {s_}, absent from every frame since the last lock-step call")
     b.close()
     m.close()
+
+
+# ---- the block under linked gains (stream_mix.LINK_CASES): controls, two model slots, group-wise list calls ----
+_LINK_MIX = {}
+_LINK_IDS = [f"n{n}-path{p}-k{K}" for n, p, K in stream_mix.LINK_CASES]
+
+
+def _link_mix(blobs, K, profile, scheduled):
+    """the block and the link oracle's run of the groups that occur for K -- lock-step, or under stream_mix's linked presence schedule
+    and resets --, once per module, K and rcpps profile"""
+    key = (K, profile, scheduled)
+    if key not in _LINK_MIX:
+        pcm, _ = stream_mix.block()
+        kw = dict(presence=stream_mix.link_presence(K), resets=stream_mix.RESET) if scheduled else {}
+        _LINK_MIX[key] = pcm, stream_mix.oracle_groups(blobs, pcm, K, stream_mix.controls(), stream_mix.slots(),
+                                                       groups=stream_mix.link_groups(K), **kw)
+    return _LINK_MIX[key]
+
+
+def _linked_batch(blobs, n, path, K):
+    """a batch of n copies of the block with the link dressing set before its first call: network path, slot 1 = the sparser model and
+    the slot map, the control table, link count K"""
+    idx = np.arange(n) % stream_mix.B
+    models = [capi.Model(blob) for blob in blobs]
+    b = capi.Batch(models[0], n)
+    if path is not None:
+        b.set_nn_path(path)
+    assert b.add_model(models[1]) == 1
+    b.set_stream_models(stream_mix.slots()[idx])
+    b.set_stream_controls(stream_mix.controls()[idx])
+    assert b.set_gain_link(K) == 1 and b.gain_link == K
+    return b, models
+
+
+def _device_refs(torch, want, dev):
+    """out, vad and gains of oracle_groups as int32 bit patterns on the device, (T, B * K, width): row g0 * K + member"""
+    T = want["vad"].shape[0]
+    return {k: torch.from_numpy(np.ascontiguousarray(want[k], np.float32)).to(dev).reshape(T, -1, w).view(torch.int32)
+            for k, w in (("out", 480), ("vad", 1), ("gains", 32))}
+
+
+def _check_last_frame(b, want, frame, streams, gm, what):
+    """debug_last's features, silence and pitch of `streams` against frame `frame` of oracle_groups' rows gm"""
+    for name, got in zip(("features", "silence", "pitch"), b.debug_last()):
+        ref = want[name][frame]
+        assert_bits_equal(got[streams], ref.reshape((-1,) + ref.shape[2:])[gm].astype(got.dtype), f"{what}: {name} of frame {frame}")
+
+
+def _check_linked_states(b, want, n, K):
+    """save_streams of one copy per (g0, member), each from a different copy: the complete state, and the gate counter"""
+    streams, gm = stream_mix.link_state_streams(n, K)
+    snap = b.save_streams(streams)
+    where = [(int(s_), int(x) // K, int(x) % K) for s_, x in zip(streams, gm)]
+    state = want["state"].reshape(-1, capi.STATE_FLOATS)[gm]
+    bad = np.flatnonzero((snap[:, :capi.STATE_FLOATS].view(np.uint32) != state.view(np.uint32)).any(1))
+    assert not len(bad), f"state of {len(bad)} of {len(streams)} streams differs, first (stream, g0, member) {[where[i] for i in bad[:5]]}"
+    gate = np.ascontiguousarray(snap[:, capi.SNAP_OFF_GATE]).view(np.int32)
+    bad = np.flatnonzero(gate != want["gate"].reshape(-1)[gm])
+    assert not len(bad), (f"gate counter of {len(bad)} of {len(streams)} streams differs, first (stream, g0, member) "
+                          f"{[where[i] for i in bad[:5]]}: {gate[bad[:5]].tolist()} for {want['gate'].reshape(-1)[gm][bad[:5]].tolist()}")
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path,K", stream_mix.LINK_CASES, ids=_LINK_IDS)
+def test_stream_mix_linked_at_every_form(blob_default, blob_little, rcp_profile, n, path, K):
+    """Linked gains (include/rnnoise_amd.h: rnnoise_batch_set_gain_link) at every kernel form: n copies of the mixed block with link
+    count K, stream_mix.controls() and slots() on its positions, in lock-step calls of stream_mix.CALLS on the default schedule.  The
+    linked branch of the synthesis kernel reads its siblings' silence word, VAD and gains, which K1 and the network launch(es) of the
+    same frame wrote: with the network paths of LINK_CASES every form of every stage writes them (tests/test_stream_mix_cpu.py), one
+    launch per model slot, under the three-stream pipeline.  Every stream's pcm, vad and gains against the link oracle's run of its
+    group (one per g0, stream_mix.oracle_groups) bit for bit, on the device; after every call debug_last; at the end the complete
+    state and the gate counter of one copy per (g0, member)."""
+    import torch
+    _need_256_cus()
+    blobs = (blob_default, blob_little)
+    pcm, want = _link_mix(blobs, K, rcp_profile, False)
+    T, B = sum(stream_mix.CALLS), stream_mix.B
+    dev = torch.device("cuda", 0)
+    gm_h = stream_mix.link_index(n, K)
+    gm = torch.from_numpy(gm_h).to(dev)
+    d_in = torch.from_numpy(pcm[:T]).to(dev)[:, torch.arange(n, device=dev) % B].contiguous()
+    d_out = torch.empty_like(d_in)
+    d_vad = torch.empty((T, n), device=dev)
+    d_gains = torch.empty((T, n, 32), device=dev)
+    b, models = _linked_batch(blobs, n, path, K)
+    st = torch.cuda.current_stream().cuda_stream
+    f = 0
+    for c in stream_mix.CALLS:
+        b.process_device(d_out[f].data_ptr(), d_in[f].data_ptr(), d_vad[f].data_ptr(), d_gains[f].data_ptr(), c, st)
+        f += c
+        torch.cuda.synchronize()
+        _check_last_frame(b, want, f - 1, np.arange(n), gm_h, f"the {c}-frame call")
+    ref = _device_refs(torch, want, dev)
+    for name, t, w in (("out", d_out, 480), ("vad", d_vad, 1), ("gains", d_gains, 32)):
+        ne = (t.reshape(T, n, w).view(torch.int32) != ref[name][:T][:, gm]).any(-1)
+        if bool(ne.any().item()):
+            where = ne.nonzero()[:5].tolist()
+            raise AssertionError(f"{name}: {int(ne.sum().item())} of {T * n} stream-frames differ from the link oracle, first (frame, "
+                                 f"stream) {where}, (g0, member) {[(int(gm_h[s_]) // K, s_ % K) for _, s_ in where]}")
+        del ne
+    del d_in, d_out, d_vad, d_gains, ref
+    _check_linked_states(b, want, n, K)
+    b.close()
+    for m in models:
+        m.close()
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path,K", stream_mix.LINK_CASES, ids=_LINK_IDS)
+def test_stream_mix_linked_masked_and_listed_at_every_form(blob_default, blob_little, rcp_profile, n, path, K):
+    """The same batches through the serving API: stream_mix.KINDS with the linked presence schedule (link_presence: masks by position,
+    list calls that list whole groups by g0 in a pseudo-random group order, three entries that name no stream in place of a first, a
+    middle and a last member, a hand-made group whose only present row is silent) and a reset of RESET's copies before call
+    RESET_BEFORE.  In per-stream frame phase an absent sibling's words of an earlier frame must not be folded, in a list call the
+    siblings are found through the list, and every slot's network launch stores only its own rows of the scratch planes.  NaN in
+    every absent input row, the sentinels of test_stream_mix_masked_and_listed_at_every_form: every present row-frame matches the
+    link oracle bit for bit in pcm, vad and gains, every absent row -- the replaced entries' among them -- keeps out's sentinel and
+    reads vad 0 and 32 zero gains.  After every call debug_last's defined entries; at the end the complete state and the gate counter
+    of one copy per (g0, member), and the copies of the position absent from every masked and list frame as the last lock-step call
+    left them."""
+    import torch
+    _need_256_cus()
+    blobs = (blob_default, blob_little)
+    pcm, want = _link_mix(blobs, K, rcp_profile, True)
+    B = stream_mix.B
+    idx = np.arange(n) % B
+    dev = torch.device("cuda", 0)
+    blk = torch.from_numpy(pcm).to(dev)
+    ref = _device_refs(torch, want, dev)
+    b, models = _linked_batch(blobs, n, path, K)
+    st = torch.cuda.current_stream().cuda_stream
+    never = np.flatnonzero(idx == stream_mix.SPECIAL["never"])
+    never_snap = None
+    for c, kind in enumerate(stream_mix.KINDS):
+        plan = stream_mix.link_call_plan(n, K, c)
+        fr = plan["frames"]
+        k, R = len(fr), len(plan["src"])
+        src = torch.from_numpy(plan["src"]).to(dev)
+        gm = torch.from_numpy(plan["gm"]).to(dev)
+        present = torch.from_numpy(plan["present"]).to(dev)
+        x = stream_mix.call_input(blk, fr, src, present).contiguous()
+        out = torch.empty_like(x)
+        out.view(torch.int32).fill_(SENTINEL_OUT)
+        vad = torch.empty((k, R), device=dev)
+        gains = torch.empty((k, R, 32), device=dev)
+        vad.view(torch.int32).fill_(SENTINEL_AUX)
+        gains.view(torch.int32).fill_(SENTINEL_AUX)
+        ptrs = (out.data_ptr(), x.data_ptr(), vad.data_ptr(), gains.data_ptr())
+        if kind == "lock":
+            b.process_device(*ptrs, k, st)
+        else:
+            act = torch.from_numpy(plan["active"]).to(dev).contiguous()
+            if kind == "masked":
+                b.process_masked_device(*ptrs, act.data_ptr(), k, st)
+            else:
+                rows = torch.from_numpy(plan["rows"]).to(dev)
+                b.process_list_device(*ptrs, rows.data_ptr(), R, act.data_ptr(), k, st)
+        torch.cuda.synchronize()
+        what = f"call {c} ({kind}, frames {fr.start}..{fr.stop - 1})"
+        for name, got, w in (("out", out, 480), ("vad", vad, 1), ("gains", gains, 32)):
+            r = torch.where(present[..., None], ref[name][fr.start:fr.stop][:, gm], SENTINEL_OUT if name == "out" else 0)
+            ne = (got.view(torch.int32).reshape(k, R, w) != r).any(-1)
+            if bool(ne.any().item()):
+                where = ne.nonzero()[:5].tolist()
+                raise AssertionError(f"{what}: {name} of {int(ne.sum().item())} of {k * R} row-frames differs, first (frame, row) "
+                                     f"{where}: present {[bool(plan['present'][f, i]) for f, i in where]}, list entry "
+                                     f"{[None if plan['rows'] is None else int(plan['rows'][i]) for _, i in where]}, (g0, member) "
+                                     f"{[(int(plan['gm'][i]) // K, int(plan['gm'][i]) % K) for _, i in where]}")
+            del r, ne
+        del x, out, vad, gains
+        # debug_last: every stream after a masked or lock-step call (silence 2 where absent), the listed streams after a list call
+        named = np.ones(R, bool) if plan["rows"] is None else (plan["rows"] >= 0) & (plan["rows"] < n)
+        streams = np.arange(n) if plan["rows"] is None else plan["rows"][named]
+        here = plan["present"][-1][named]
+        assert (b.debug_last()[1][streams[~here]] == 2).all(), f"{what}: silence of streams absent from frame {fr.stop - 1}"
+        _check_last_frame(b, want, fr.stop - 1, streams[here], plan["gm"][named][here], what)
+        if c + 1 == stream_mix.RESET_BEFORE:
+            b.reset_streams(np.flatnonzero(np.isin(idx, stream_mix.RESET)))
+        if kind == "lock":
+            never_snap = b.save_streams(never)
+    torch.cuda.synchronize()
+    del blk, ref
+    _check_linked_states(b, want, n, K)
+    assert_bits_equal(b.save_streams(never), never_snap, "the streams absent from every frame since the last lock-step call")
+    b.close()
+    for m in models:
+        m.close()
 
 
 def _poison_places(n, B):
