@@ -21,6 +21,13 @@ running it.
                                     limits at and beyond the ends of their ranges.  Keys the file already holds must come out
                                     bit-identical, or nothing is written
 
+  tests/golden/block_pins.npz    -- the mixed block of tests/stream_mix.py through the reference (`make_golden.py --block-pins
+                                    [OUTDIR]` writes only it): per run of stream_mix.block_pin_runs() -- every position on the
+                                    default model, 40 on the sparser one, in lock step and under the presence schedule with its
+                                    restarts -- CRC32 per (frame, position) of out, gains and features, vad, pitch, silence and one
+                                    CRC32 of the final state per position.  Keys the file already holds must come out bit-identical,
+                                    or nothing is written
+
 The reference's tanh / sigmoid execute the generating CPU's `rcpps` (src/vec_avx.h:413,442), so a fixture belongs to one
 CPU family and says which ("rcp_profile", "host_cpu" entries).  The Intel build host writes tests/golden/*.npz; run on the
 GPU boxes' AMD EPYC host (the compiled reference under oracle/_ref travels there) the same script writes the same streams
@@ -132,18 +139,47 @@ def reference_pins(gold, tag, blob):
     np.savez_compressed(path, **d, **tag)
 
 
+def block_pins(gold, tag):
+    """The inputs are stream_mix.block(), which the test that reads the file regenerates; only digests of outputs are stored."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stream_mix  # noqa: E402  (tests/stream_mix.py: test_oracle.py's block tests)
+    d = {}
+    for run, name, positions, scheduled in stream_mix.block_pin_runs():
+        blob = open(os.path.join(ROOT, "oracle", "_ref", f"{name}.blob"), "rb").read()
+        r = stream_mix.block_run(blob, positions, scheduled, engine=RefHarness)
+        d[f"{run}_positions"] = np.array(positions, np.int16)
+        for k, v in stream_mix.block_digest(r).items():
+            d[f"{run}_{k}"] = v
+    path = os.path.join(gold, "block_pins.npz")
+    if os.path.exists(path):  # what the file pins already stays pinned
+        old = np.load(path)
+        for k in old.files:
+            if k != "host_cpu":
+                assert k in d or k in tag, f"{k} would be dropped"
+                new = np.asarray(d[k] if k in d else tag[k])
+                assert new.dtype == old[k].dtype and new.shape == old[k].shape and new.tobytes() == old[k].tobytes(), f"{k} changed"
+    np.savez_compressed(path, **d, **tag)
+    print(path, os.path.getsize(path))
+
+
 def main():
     global GOLD
     tag = host_profile()
     pins_only = "--pins" in sys.argv
     if pins_only:
         sys.argv.remove("--pins")
+    block_only = "--block-pins" in sys.argv
+    if block_only:
+        sys.argv.remove("--block-pins")
     blob_dir = GOLD
     if str(tag["rcp_profile"]) != "intel":
         GOLD = os.path.join(GOLD, str(tag["rcp_profile"]).replace("-", "_"))
     if len(sys.argv) > 1:
         GOLD = sys.argv[1]
     os.makedirs(GOLD, exist_ok=True)
+    if block_only:
+        block_pins(GOLD, tag)
+        return
     if pins_only:
         reference_pins(GOLD, tag, open(os.path.join(ROOT, "oracle", "_ref", "default.blob"), "rb").read())
         return
@@ -214,6 +250,7 @@ def main():
         d[f"s{s}_state_crc"] = np.uint32(synth.crc32(r.get_state()))
     np.savez_compressed(os.path.join(GOLD, "digest_little.npz"), **d, **tag)
     reference_pins(GOLD, tag, blob)
+    block_pins(GOLD, tag)
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)))
 

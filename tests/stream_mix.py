@@ -1,6 +1,6 @@
 """One mixed block of streams for the at-size parity tests (plain helper module: tests/test_stream_mix_cpu.py checks what the block
 and its dressings cover; tests/test_gpu_at_size.py runs it in lock-step calls, through masked and list calls, with poisoned streams
-and under linked gains; tests/test_dropin_gpu.py runs it through the drop-in API).
+under linked gains and through the PCM front ends; tests/test_dropin_gpu.py runs it through the drop-in API).
 
 `block()` is B = 389 streams x 30 frames of float PCM.  The at-size tests lay a batch out as copies of it (stream i takes block
 stream i mod B); B is prime, so the copies land at shifting offsets modulo the 4 streams of an analysis workgroup, the 16 of a tile
@@ -25,6 +25,13 @@ The link dressing (`LINK_CASES`, `controls()`, `slots()`, `link_presence()`, `li
 under a link count K (include/rnnoise_amd.h: rnnoise_batch_set_gain_link) with a control record and a model slot on every position:
 group j of a batch is streams K j .. K j + K - 1, at positions g0 .. g0 + K - 1 with g0 = (K j) mod B.  Rows are dressed by position,
 groups by g0 -- a list call lists whole groups --, so one run of the link oracle per g0 covers every copy.
+
+The PCM dressing (`DRESS_CASES`, `rate_codes()`, `formats()`, `laws()`, `dress_input()`, `dress_call_plan()`, `dress_expectation()`)
+runs the block through the PCM front ends: a rate code (8 to 48 kHz) and a format (linear, mu-law, A-law) on every position, int16
+and float calls, interleaved channels and caller strides.  Its expectation is a chain on the CPU alone, one run per position.
+
+`block_pin_runs()`, `block_run()` and `block_digest()` are the runs of the block that tests/test_oracle.py compares between the oracle
+and the compiled reference, and what tests/golden/block_pins.npz records of them.
 """
 from __future__ import annotations
 
@@ -35,7 +42,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from conftest import GOLD
-from rnnoise_amd import synth
+from rnnoise_amd import g711, resample, synth
 from test_gpu_parity import extreme_signals, fuzz_pcm
 
 B = 389                                   # streams of the block: prime
@@ -257,13 +264,16 @@ def block():
     return np.ascontiguousarray(pcm[:, src]), [labels[s] for s in src]
 
 
-def oracle_block(blob, pcm, streams=None, collect_state=True, presence=None, resets=None):
+def oracle_block(blob, pcm, streams=None, collect_state=True, presence=None, resets=None, engine=None):
     """the oracle over the streams of a (T, n, 480) block (all of them, or the listed ones), several streams at a time: every stream
     has an Oracle of its own, and the oracle's C calls release the GIL.  Same keys as test_gpu_parity.oracle_run.
     presence: (T, n) -- each stream's oracle runs on its present frames only; the absent frames hold what include/rnnoise_amd.h
     promises for them: out 0 (untouched), vad 0, 32 zero gains, silence 2, features and pitch 0 (undefined), and "present" (T, n)
-    bool comes back too.  resets: streams that restart from a fresh Oracle at the first frame of call RESET_BEFORE of CALLS."""
-    from oracle.binding import Oracle
+    bool comes back too.  resets: streams that restart from a fresh Oracle at the first frame of call RESET_BEFORE of CALLS.
+    engine: the class that runs a stream, oracle.binding.Oracle by default; RefHarness (the compiled reference, where oracle/_ref is
+    built) runs one stream after the other."""
+    from oracle import binding
+    Oracle = engine or binding.Oracle
     streams = list(range(pcm.shape[1])) if streams is None else list(streams)
     Tn = pcm.shape[0]
     present = None if presence is None else np.asarray(presence)[:Tn] != 0
@@ -291,7 +301,7 @@ def oracle_block(blob, pcm, streams=None, collect_state=True, presence=None, res
             r["state"] = o.get_state()
         return r
 
-    workers = max(1, min(16, len(os.sched_getaffinity(0))))
+    workers = max(1, min(16, len(os.sched_getaffinity(0)))) if Oracle is binding.Oracle else 1
     with ThreadPoolExecutor(workers) as pool:
         runs = list(pool.map(one, streams))
     keys = ("out", "vad", "gains", "features", "pitch", "silence") + (("state",) if collect_state else ())
@@ -587,3 +597,270 @@ def oracle_groups(blobs, pcm, K, ctl, slots, presence=None, resets=None, groups=
                 out[k][:, g0] = v
     out["present"] = out["present"] != 0
     return out
+
+
+# ---- the PCM dressing: the block through the rate table, the format table, caller strides, interleaved channels, the int16 calls ----
+# A rate code and a format on every block position; the batch stays at 48 kHz, so every row is 480 samples wide and a position at code
+# L uses the first M = frame_samples(L) of them.  A position's low-rate input is resample.down of its 48 kHz block signal from zero
+# history; the expectation is a chain on the CPU alone -- decode -> resample.up -> Oracle -> resample.down -> to_s16 -> encode --, one
+# run per position and variant.  The variants: "float" (float calls: no cast, no codec; the format table is set and ignored), "s16"
+# (int16 calls, linear rows) and "law" (int16 calls, the position's own law).  With C > 1 interleaved channels the rows of a group
+# must all be linear or all companded (include/rnnoise_amd.h), so whether a row of an int16 call is companded is a property of its
+# group -- of the position of the group's first row -- and the law a property of its own position: one position is a linear row in one
+# copy and a companded one in another, which is why both variants are run for every position.
+#
+# DRESS_CASES: (streams, network path or None for the batch's default, "int16" | "float", channels C, layout), n % C == 0 and
+# n % B != 0.  Layouts: "default"; "streams" (stream-contiguous [groups][frames of the call][M][C]); "padded" (row-major, 8 samples
+# behind every group slot and 16 behind every frame).  On 256 CUs with the default switches (test_stream_mix_cpu.py holds them to it;
+# K0 is rn_hp_one_kernel in every call: a rate table forces it):
+DRESS_CASES = [
+    (252, 0, "int16", 2, "default"),        # rn_nn_one_kernel, rn_synthesis_few_kernel, one-stream analysis
+    (390, 0, "float", 1, "streams"),        # rn_synthesis_kernel
+    (390, 1, "int16", 3, "padded"),         # tile 16 in one-frame calls, tile 8 in pipelined ones
+    (390, 2, "int16", 1, "default"),        # layer-wise network, rn_nn_gru_w8_kernel
+    (1032, 0, "float", 8, "default"),       # rn_nn_vector_kernel
+    (2568, None, "int16", 2, "streams"),    # above K0's lane switch (the plain batch runs rn_hp_kernel there); rn_analysis_kernel in lock-step calls
+    (10278, None, "int16", 1, "default"),   # layer-wise network at size, rn_nn_gru_w8_kernel
+    (16416, None, "int16", 2, "default"),   # rn_nn_gru_kernel (w4): 257 groups of 64 on 256 CUs
+]
+DRESS_IDS = [f"n{n}-path{p}-{t}-c{C}-{lay}" for n, p, t, C, lay in DRESS_CASES]
+RATE_CODES = (1, resample.RATE_32K, 2, 3, 6)
+VARIANTS = ("float", "s16", "law")
+JUNK_S16 = 7777                           # what the unused int16 samples of an input buffer hold (the float ones: NaN)
+
+
+def rate_codes():
+    """(B,) int: the rate code of every block position.  With p = 15 c + 5 a + j: RATE_CODES[(j + 2 c) mod 5] -- every five positions
+    5 b .. 5 b + 4 hold all five rates, in an order that moves on with every fifteen"""
+    p = np.arange(B)
+    return np.array(RATE_CODES)[(p % 5 + 2 * (p // 15)) % 5]
+
+
+def formats():
+    """(B,) uint8: the format of every block position (g711.LINEAR, ULAW, ALAW).  With p = 15 c + 5 a + j: (j + a) mod 3 -- any three
+    neighbours within five hold all three, and a rate meets each format once in its fifteen: every fifteen positions 15 c .. 15 c + 14
+    hold all fifteen (rate, format) pairs, a third of the block each format.  (No formula in p mod 3 alone: the groups of a batch with
+    three channels start at the multiples of 3.)"""
+    p = np.arange(B)
+    return ((p % 5 + p % 15 // 5) % 3).astype(np.uint8)
+
+
+def laws():
+    """(B,) uint8: the law a position's rows take where they are companded -- its own format, and for a linear position (whose row is
+    companded where its group is) mu-law and A-law in turn"""
+    f = formats()
+    return np.where(f != 0, f, 1 + np.arange(B) % 2).astype(np.uint8)
+
+
+def frame_lengths():
+    """(B,) int: M of every block position, the samples (bytes, where companded) of its row it uses"""
+    return np.array([resample.frame_samples(int(L)) for L in rate_codes()])
+
+
+def dress_companded(n, C, s16=True):
+    """(n,) bool: whether stream i of an int16 batch of n copies with C channels holds G.711 bytes: its group's first row sits on a
+    position whose format is a law (C = 1: its own position).  Float calls: never"""
+    lead = (np.arange(n) // C * C) % B
+    return (formats()[lead] != 0) & bool(s16)
+
+
+def dress_formats(n, C, s16=True):
+    """(n,) uint8: the format table of a dressed batch.  Int16: the row's law where its group is companded, else linear.  Float: the
+    position's format, which the float calls ignore"""
+    p = np.arange(n) % B
+    return np.where(dress_companded(n, C), laws()[p], 0).astype(np.uint8) if s16 else formats()[p]
+
+
+def dress_strides(layout, C, k, R, M=480):
+    """(frame_stride, row_stride) in samples of a call of k frames and R rows under `layout`, None for the default layout"""
+    if layout == "default":
+        return None
+    if layout == "streams":
+        return M * C, k * M * C
+    assert layout == "padded"
+    rs = M * C + 8
+    return R // C * rs + 16, rs
+
+
+@functools.lru_cache(None)
+def _dress_list(n, C, c):
+    if C == 1:
+        rows = list_rows(n, c)
+        return rows, np.where((rows >= 0) & (rows < n), rows, 0).astype(np.int64)
+    keep = np.zeros(B, bool)
+    keep[list(LISTED[c])] = True
+    on = keep[np.arange(n) % B].reshape(-1, C)
+    order = _rng(500 + c).permutation(np.flatnonzero(on.any(1)))
+    streams = (C * order[:, None] + np.arange(C)).astype(np.int64)
+    rows = streams.copy()
+    # the entries that name no stream stand for rows that LISTED[c] leaves out: those streams miss the call in every copy anyway
+    free = np.argwhere(~on[order])
+    taken = set()
+    for m, at, e in zip((0, C // 2, C - 1), (0, len(free) // 2, len(free) - 1), OUT_OF_RANGE):   # a first, a middle, a last member
+        cand = np.array([i for i in np.flatnonzero(free[:, 1] == m) if int(free[i, 0]) not in taken])
+        g = int(free[cand[np.argmin(np.abs(cand - at))], 0])
+        taken.add(g)
+        rows[g, m] = n if e is None else e
+    return rows.reshape(-1).astype(np.int32), streams.reshape(-1)
+
+
+def dress_list_rows(n, C, c):
+    """the stream list of list call c on a dressed batch of n copies with C channels, and the stream every row stands for.  C = 1:
+    list_rows().  C > 1: whole groups -- every group with a row on a position of LISTED[c], in a fixed pseudo-random group order,
+    members ascending; the rows on other positions are listed and masked out (dress_call_plan), so presence() stays a function of the
+    position -- and OUT_OF_RANGE's three entries in place of a first, a middle and a last member that is masked out anyway"""
+    rows, streams = _dress_list(n, C, c)
+    return rows.copy(), streams.copy()
+
+
+def dress_call_plan(n, C, c, scheduled=True):
+    """call_plan() for a dressed batch of n copies with C channels; scheduled=False: call c of the lock-step run (every row present).
+    Also "stream": the stream of every row (for a list entry that names no stream: the one it stands for)"""
+    frames = call_frames(c)
+    if not scheduled:
+        return dict(kind="lock", frames=frames, rows=None, src=np.arange(n) % B, stream=np.arange(n),
+                    present=np.ones((len(frames), n), bool), active=None)
+    if KINDS[c] != "list":
+        return dict(call_plan(n, c), stream=np.arange(n))
+    rows, streams = dress_list_rows(n, C, c)
+    named = (rows >= 0) & (rows < n)
+    src = streams % B
+    present = (presence()[frames.start:frames.stop] != 0)[:, src] & named
+    active = np.ascontiguousarray(np.where(named, present, True).astype(np.uint8))
+    return dict(kind="list", frames=frames, rows=rows, src=src, stream=streams, present=np.ascontiguousarray(present), active=active)
+
+
+@functools.lru_cache(None)
+def _low_input():
+    pcm, _ = block()
+    sig = pcm.transpose(1, 0, 2).reshape(B, T * 480)
+    x = np.zeros((T, B, 480), np.float32)
+    codes = rate_codes()
+    for L in RATE_CODES:
+        pos = np.flatnonzero(codes == L)
+        M = resample.frame_samples(L)
+        y = sig[pos] if L == 1 else resample.down(sig[pos], L)
+        x[:, pos, :M] = y.reshape(len(pos), T, M).transpose(1, 0, 2)
+    return x
+
+
+def _encode(x16, law):
+    """g711.encode of (..., B, 480) int16 with the law of every position"""
+    return np.where((law == g711.ULAW)[:, None], g711.ulaw_encode(x16), g711.alaw_encode(x16)).astype(np.uint8)
+
+
+def _decode(b, law):
+    return np.where((law == g711.ULAW)[:, None], g711.ulaw_decode(b), g711.alaw_decode(b)).astype(np.int16)
+
+
+@functools.lru_cache(None)
+def _dress_input(variant):
+    x = _low_input()
+    if variant == "float":
+        return x
+    x16 = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+    return x16 if variant == "s16" else _encode(x16, laws())
+
+
+def dress_input(variant):
+    """(T, B, 480): what the rows of every block position hold under `variant` -- "float": resample.down / down32 of the position's
+    48 kHz block signal from zero history as float32 (the position's own signal at code 1); "s16": that rounded and clipped to int16;
+    "law": g711.encode of the int16 samples with the position's law (laws()), uint8.  The first frame_lengths()[p] entries of a row
+    count, the rest are zero"""
+    return _dress_input(variant).copy()
+
+
+def _resampled(x, codes, segments, up):
+    """x (T, B, 480) through resample.up (rows of M samples -> 480) or resample.down (480 -> M) by position, whole signal by whole
+    signal: `segments` are (T, B) masks, and the frames of a position that a segment marks are, concatenated, one signal from zero
+    history (tests/test_resample_cpu.py: streaming equals the whole signal).  Frames in no segment come back zero; code 1 passes"""
+    y = np.zeros((T, B, 480), np.float32)
+    for L in RATE_CODES:
+        pos = np.flatnonzero(codes == L)
+        M = resample.frame_samples(L)
+        w_in, w_out = (M, 480) if up else (480, M)
+        for seg in segments:
+            sel = seg[:, pos]
+            if L == 1:
+                y[:, pos] = np.where(sel[..., None], x[:, pos], y[:, pos])
+                continue
+            order = np.argsort(~sel, axis=0, kind="stable")                     # every position's marked frames first, in order
+            packed = np.take_along_axis(x[:, pos, :w_in], order[..., None], axis=0)
+            packed[np.arange(T)[:, None] >= sel.sum(0)[None]] = 0
+            sig = packed.transpose(1, 0, 2).reshape(len(pos), T * w_in)
+            res = (resample.up if up else resample.down)(sig, L).reshape(len(pos), T, w_out).transpose(1, 0, 2)
+            back = np.zeros((T, len(pos), w_out), np.float32)
+            np.put_along_axis(back, order[..., None], res, axis=0)
+            y[:, pos, :w_out] = np.where(sel[..., None], back, y[:, pos, :w_out])
+    return y
+
+
+DRESS_MUTANTS = ("absent_advances", "reset_keeps_history", "encode_before_cast")
+
+
+def dress_expectation(blob, variant, scheduled, mutant=None):
+    """the CPU chain over every block position under `variant` (VARIANTS), lock-step or (scheduled) under presence() with RESET's
+    restarts before call RESET_BEFORE: an absent frame advances neither the denoiser nor the resampler histories, a reset zeroes both.
+    Keys as oracle_block, "out" (T, B, 480) in the variant's type (float32 | int16 | uint8 codes): the first frame_lengths()[p] entries
+    of a present row, zeros elsewhere.  mutant (DRESS_MUTANTS) -- for the tests of the tests: a chain whose resampler histories advance
+    over absent frames, one whose reset leaves them, one that encodes the rounded float output instead of the truncated int16"""
+    assert variant in VARIANTS and mutant in (None,) + DRESS_MUTANTS
+    codes, law = rate_codes(), laws()
+    x = _dress_input(variant)
+    x = (_decode(x, law) if variant == "law" else x).astype(np.float32)
+    pres = presence() != 0 if scheduled else np.ones((T, B), bool)
+    restart = np.zeros(B, bool)
+    if scheduled and mutant != "reset_keeps_history":
+        restart[list(RESET)] = True
+    after = (np.arange(T) >= call_frames(RESET_BEFORE)[0])[:, None] & restart[None]
+    run = np.ones((T, B), bool) if mutant == "absent_advances" else pres
+    segments = (run & ~after, run & after)
+    v = _resampled(x, codes, segments, up=True)
+    r = oracle_block(blob, v, presence=pres, resets=RESET) if scheduled else oracle_block(blob, v)
+    y = _resampled(r["out"], codes, segments, up=False)
+    y[~pres] = 0
+    if variant != "float":
+        y16 = resample.to_s16(y)
+        if variant == "law":
+            y = _encode(np.clip(np.rint(y), -32768, 32767).astype(np.int16) if mutant == "encode_before_cast" else y16, law)
+            y[~(pres[..., None] & (np.arange(480) < frame_lengths()[:, None])[None])] = 0
+        else:
+            y = y16
+    r["out"], r["present"] = y, pres
+    return r
+
+
+# ---- the block through the compiled reference (tests/test_oracle.py; tests/golden/make_golden.py --block-pins) ----
+PIN_KEYS = ("out_crc", "gains_crc", "features_crc", "vad", "pitch", "silence", "state_crc")
+
+
+def block_pin_runs():
+    """the runs of the block that tie the oracle to the reference, as (tag, blob name, block positions, scheduled): every position on
+    the default model, and on the sparser one the first 40 of the positions that carry model slot 1 under the link dressing (slots());
+    each in lock step and under presence() with RESET's restarts"""
+    little = [int(p) for p in np.flatnonzero(slots() == 1)[:40]]
+    return [(f"{name}_{'sched' if scheduled else 'lock'}", name, pos, scheduled)
+            for name, pos in (("default", list(range(B))), ("little", little)) for scheduled in (False, True)]
+
+
+def block_run(blob, positions, scheduled, engine=None):
+    """oracle_block over `positions` of the block on `engine` (the oracle, or oracle.binding.RefHarness): lock-step, or each position's
+    present frames with a fresh state at RESET's restart"""
+    pcm, _ = block()
+    if not scheduled:
+        return oracle_block(blob, pcm, streams=positions, engine=engine)
+    return oracle_block(blob, pcm, streams=positions, presence=presence(), resets=RESET, engine=engine)
+
+
+def block_digest(r):
+    """what tests/golden/block_pins.npz holds of a block_run(): CRC32 per (frame, position) of out, gains and features, vad as float32,
+    pitch as int16, silence as int8, one CRC32 of the final state per position (PIN_KEYS)"""
+    import zlib
+
+    def crc(a):
+        a = np.ascontiguousarray(a)
+        flat = a.reshape(-1, a.shape[-1])
+        return np.array([zlib.crc32(row.tobytes()) for row in flat], np.uint32).reshape(a.shape[:-1])
+
+    return dict(out_crc=crc(r["out"]), gains_crc=crc(r["gains"]), features_crc=crc(r["features"]), vad=r["vad"].astype(np.float32),
+                pitch=r["pitch"].astype(np.int16), silence=r["silence"].astype(np.int8), state_crc=crc(r["state"]))

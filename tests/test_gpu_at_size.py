@@ -5,7 +5,9 @@ stay bit-identical to each other (no cross-talk, no dependence on the tile / CU 
 itself is checked bit for bit against the oracle, including a stream that starts silent inside a live MFMA tile.  The mixed
 block of tests/stream_mix.py (389 streams of every kind, compared stream by stream) runs at batch sizes that reach every kernel
 form, with NaN / Inf in copies of one of its streams, and through masked, stream-list and per-stream-phase lock-step calls with
-NaN in every absent row; and under linked gains with controls and two model slots (stream_mix.LINK_CASES), the same two ways.
+NaN in every absent row; under linked gains with controls and two model slots (stream_mix.LINK_CASES), the same two ways; and
+through the PCM front ends -- rate table, format table, strides, channels, int16 calls (stream_mix.DRESS_CASES) --, the same two ways,
+against a chain on the CPU alone.
 Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
 import os
 import subprocess
@@ -317,6 +319,196 @@ def test_stream_mix_masked_and_listed_at_every_form(blob_default, rcp_profile, n
         assert_bits_equal(b.export_state(s_), st_, f"state of stream {s_}, absent from every frame since the last lock-step call")
     b.close()
     m.close()
+
+
+# ---- the block through the PCM front ends (stream_mix.DRESS_CASES): rate table, format table, strides, channels, int16 calls ----
+_DRESSED = {}
+SENTINEL_S16 = 0x5AA5                     # what `out` of an int16 call holds before it (bytes A5 5A)
+PAD = 32                                  # samples behind the last slot of every PCM buffer: nothing may land there either
+
+
+def _dressed(blob, profile, scheduled):
+    """the CPU chain's run of the block (stream_mix.dress_expectation) under every variant, lock-step or under the presence schedule,
+    once per module and rcpps profile.  No GPU takes part in it"""
+    key = (profile, scheduled)
+    if key not in _DRESSED:
+        _DRESSED[key] = {v: stream_mix.dress_expectation(blob, v, scheduled) for v in stream_mix.VARIANTS}
+    return _DRESSED[key]
+
+
+def _dressed_run(blob, profile, case, scheduled):
+    """One DRESS_CASES batch through lock-step CALLS or (scheduled) through KINDS with presence(), NaN / junk in everything of `in`
+    that no present row owns and the reset before RESET_BEFORE.  After every call the whole allocation of `out` -- every present
+    row's first M samples or bytes from the CPU chain, the sentinel everywhere else: the rest of the slot, the padding between rows
+    and frames, absent rows, the channels of absent siblings --, vad and gains of every row (0 where absent), and `in` untouched; at
+    the end the state of every block position from a different copy, the snapshots of 16 positions across all of their copies, and
+    the tables."""
+    import torch
+    n, path, typ, C, layout = case
+    s16 = typ == "int16"
+    B, M = stream_mix.B, 480
+    want = _dressed(blob, profile, scheduled)
+    dev = torch.device("cuda", 0)
+    kinds = ("float",) if not s16 else ("s16", "law")                         # the variants of this batch's rows: index = companded
+    codes, Ms = stream_mix.rate_codes(), stream_mix.frame_lengths()
+    comp_h = stream_mix.dress_companded(n, C, s16)
+    table_h = stream_mix.dress_formats(n, C, s16)
+    idx = np.arange(n) % B
+
+    def bits(a):
+        a = np.ascontiguousarray(a)
+        return torch.from_numpy(a.view(np.int32) if a.dtype == np.float32 else a).to(dev)
+
+    x_in = {v: bits(stream_mix.dress_input(v)) for v in kinds}                # (T, B, 480) int32 bits | int16 | uint8
+    ref_out = {v: bits(want[v]["out"]) for v in kinds}
+    ref_vad = torch.cat([bits(want[v]["vad"]) for v in kinds], 1)             # (T, variants * B): row companded * B + position
+    ref_gains = torch.cat([bits(want[v]["gains"]) for v in kinds], 1)
+    comp = torch.from_numpy(comp_h).to(dev)
+    Ms_d = torch.from_numpy(Ms).to(dev)
+    lane = torch.arange(M, device=dev)
+    el = torch.int16 if s16 else torch.int32
+    junk, sentinel = (stream_mix.JUNK_S16, SENTINEL_S16) if s16 else (0x7FC00000, SENTINEL_OUT)
+
+    m = capi.Model(blob)
+    b = capi.Batch(m, n)
+    if path is not None:
+        b.set_nn_path(path)
+    b.set_stream_rates(capi.code_rate(codes[idx]))
+    b.set_stream_formats(table_h)
+    if C > 1:
+        assert b.set_pcm_channels(C) == 1
+    st = torch.cuda.current_stream().cuda_stream
+    for c in range(len(stream_mix.CALLS)):
+        plan = stream_mix.dress_call_plan(n, C, c, scheduled)
+        kind, fr = plan["kind"], plan["frames"]
+        k, R = len(fr), len(plan["src"])
+        G = R // C
+        strides = stream_mix.dress_strides(layout, C, k, R)
+        fs, rs = strides or (G * M * C, M * C)
+        if strides:
+            b.set_pcm_layout(fs, rs)
+        size = (k - 1) * fs + (G - 1) * rs + M * C + PAD
+        src = torch.from_numpy(plan["src"]).to(dev)
+        present = torch.from_numpy(plan["present"]).to(dev)
+        rcomp = comp[torch.from_numpy(plan["stream"]).to(dev)]                # (R,) the row holds bytes
+        own = present[:, :, None] & (lane[None, None, :] < Ms_d[src][None, :, None])   # (k, R, 480): what a present row owns
+
+        def slots(flat, as_bytes=False):
+            """(k, G, M, C) view of the samples (bytes of companded groups) of a flat buffer: [f, g, i, ch] at f fs + g rs + i C + ch"""
+            w = 2 if as_bytes else 1
+            return (flat.view(torch.uint8) if as_bytes else flat).as_strided((k, G, M, C), (w * fs, w * rs, C, 1))
+
+        def rows(a):
+            return a.reshape(k, G, C, M).permute(0, 1, 3, 2)
+
+        def put(flat, values, where, as_bytes=False):
+            v = slots(flat, as_bytes)
+            v.copy_(torch.where(rows(where), rows(values), v))
+
+        def gather(t):
+            return t[fr.start:fr.stop][:, src]
+
+        d_in = torch.full((size,), junk, dtype=el, device=dev)
+        d_exp = torch.full((size,), sentinel, dtype=el, device=dev)
+        if s16:
+            lin, law = own & ~rcomp[None, :, None], own & rcomp[None, :, None]
+            put(d_in, gather(x_in["s16"]), lin)
+            put(d_in, gather(x_in["law"]), law, as_bytes=True)
+            put(d_exp, gather(ref_out["s16"]), lin)
+            put(d_exp, gather(ref_out["law"]), law, as_bytes=True)
+        else:
+            put(d_in, gather(x_in["float"]), own)
+            put(d_exp, gather(ref_out["float"]), own)
+        d_in0 = d_in.clone()
+        d_out = torch.full((size,), sentinel, dtype=el, device=dev)
+        vad = torch.full((k, R), SENTINEL_AUX, dtype=torch.int32, device=dev)
+        gains = torch.full((k, R, 32), SENTINEL_AUX, dtype=torch.int32, device=dev)
+        ptrs = (d_out.data_ptr(), d_in.data_ptr(), vad.data_ptr(), gains.data_ptr())
+        if kind == "lock":
+            b.process_device(*ptrs, k, st, s16=s16)
+        else:
+            act = torch.from_numpy(plan["active"]).to(dev).contiguous()
+            if kind == "masked":
+                b.process_masked_device(*ptrs, act.data_ptr(), k, st, s16=s16)
+            else:
+                lst = torch.from_numpy(plan["rows"]).to(dev)
+                b.process_list_device(*ptrs, lst.data_ptr(), R, act.data_ptr(), k, st, s16=s16)
+        torch.cuda.synchronize()
+        what = f"call {c} ({kind}, frames {fr.start}..{fr.stop - 1})"
+
+        def where_rows(ne):
+            w = ne.nonzero()[:5].tolist()
+            return (f"first (frame, row) {w}: present {[bool(plan['present'][f, i]) for f, i in w]}, stream {[int(plan['stream'][i]) for _, i in w]}, "
+                    f"block position {[int(plan['src'][i]) for _, i in w]}, rate code {[int(codes[plan['src'][i]]) for _, i in w]}, "
+                    f"companded {[bool(comp_h[plan['stream'][i]]) for _, i in w]}")
+
+        if not torch.equal(d_out, d_exp):
+            # which rows: the samples (and, in an int16 call, the bytes) of every row's positions, present or not
+            ne = (slots(d_out) != slots(d_exp)).permute(0, 1, 3, 2).reshape(k, R, M).any(-1)
+            if s16:
+                ne |= (slots(d_out, True) != slots(d_exp, True)).permute(0, 1, 3, 2).reshape(k, R, M).any(-1)
+            at = int((d_out != d_exp).nonzero()[0])
+            raise AssertionError(f"{what}: out differs in {int((d_out != d_exp).sum())} of {size} samples, the first at sample {at} "
+                                 f"(frame stride {fs}, group stride {rs}, {C} channels); {int(ne.sum())} of {k * R} row-frames, " + where_rows(ne))
+        assert torch.equal(d_in, d_in0), f"{what}: `in` was written"
+        vidx = rcomp.long() * B + src
+        for name, got, ref in (("vad", vad, ref_vad), ("gains", gains, ref_gains)):
+            r = ref[fr.start:fr.stop][:, vidx].reshape(k, R, -1)
+            r = torch.where(present[..., None], r, 0)
+            ne = (got.reshape(k, R, -1) != r).any(-1)
+            if bool(ne.any().item()):
+                raise AssertionError(f"{what}: {name} of {int(ne.sum())} of {k * R} row-frames differs, " + where_rows(ne))
+        del d_in, d_in0, d_out, d_exp, vad, gains
+        if scheduled and c + 1 == stream_mix.RESET_BEFORE:
+            b.reset_streams(np.flatnonzero(np.isin(idx, stream_mix.RESET)))
+    del x_in, ref_out, ref_vad, ref_gains
+    # every block position from a different copy
+    streams = np.array([p + (7 * p) % ((n - p + B - 1) // B) * B for p in range(min(B, n))])
+    if scheduled:
+        streams = np.unique(np.concatenate([streams, [p + (n - 1 - p) // B * B for p in stream_mix.RESET if p < n]]))   # (a list names a stream once)
+    snap = b.save_streams(streams)
+    state = np.stack([want[kinds[int(comp_h[s_])]]["state"][s_ % B] for s_ in streams])
+    bad = np.flatnonzero((snap[:, :capi.STATE_FLOATS].view(np.uint32) != state.view(np.uint32)).any(1))
+    assert not len(bad), (f"state of {len(bad)} of {len(streams)} streams differs, first (stream, block position, companded) "
+                          f"{[(int(streams[i]), int(streams[i]) % B, bool(comp_h[streams[i]])) for i in bad[:5]]}")
+    # 16 positions, every copy: one record per variant (a resampler history that drifts between copies shows here)
+    for p in range(3, min(B, n), 24)[:16]:
+        copies = np.arange(p, n, B)
+        snap = b.save_streams(copies).view(np.uint32)
+        for v in (False, True):
+            recs = snap[comp_h[copies] == v]
+            assert (recs == recs[:1]).all(), f"snapshots of block position {p} differ between its {len(recs)} copies (companded: {v})"
+    assert_bits_equal(b.stream_rates(), capi.code_rate(codes[idx]).astype(np.int32), "the rate table")
+    assert_bits_equal(b.stream_formats(), table_h, "the format table")
+    assert b.pcm_channels == C
+    b.close()
+    m.close()
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("case", stream_mix.DRESS_CASES, ids=stream_mix.DRESS_IDS)
+def test_stream_mix_dressed_at_every_form(blob_default, rcp_profile, case):
+    """The mixed block through the PCM front ends (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates, _set_stream_formats,
+    _set_pcm_layout, _set_pcm_channels, the _s16 calls) at every kernel form: n copies of the block with stream_mix.rate_codes() and
+    formats() on its positions -- 8 to 48 kHz, linear, mu-law and A-law side by side in every tile --, in lock-step calls of
+    stream_mix.CALLS under the sample type, channel count and layout of DRESS_CASES.  The expectation is a chain on the CPU alone
+    (stream_mix.dress_expectation: decode, resample.up, the oracle, resample.down, the truncating cast, encode), one run per block
+    position and variant; every row of every copy is compared with it on the device, bit for bit, with everything a row does not own
+    held to its sentinel (_dressed_run)."""
+    _need_256_cus()
+    _dressed_run(blob_default, rcp_profile, case, scheduled=False)
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("case", stream_mix.DRESS_CASES, ids=stream_mix.DRESS_IDS)
+def test_stream_mix_dressed_masked_and_listed_at_every_form(blob_default, rcp_profile, case):
+    """The same batches through the serving API: stream_mix.KINDS with presence() -- masked calls, list calls that list whole channel
+    groups in a pseudo-random order with three entries that name no stream, lock-step calls in per-stream frame phase -- and a reset
+    of RESET's copies before call RESET_BEFORE.  An absent frame advances neither a row's state nor its resampler histories, a reset
+    zeroes both; absent float rows hold NaN, absent int16 rows junk; an absent channel's samples of a group slot keep the sentinel
+    beside its siblings' output."""
+    _need_256_cus()
+    _dressed_run(blob_default, rcp_profile, case, scheduled=True)
 
 
 # ---- the block under linked gains (stream_mix.LINK_CASES): controls, two model slots, group-wise list calls ----

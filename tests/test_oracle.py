@@ -319,6 +319,72 @@ def test_reference_pins_are_the_reference():
     assert_bits_equal(r.get_state(), g["free_state"], "state")
 
 
+# ---- the mixed block of tests/stream_mix.py: what every at-size GPU test trusts the oracle on ----
+_REF_BLOCK = {}
+
+
+def _reference_block(run):
+    """one run of stream_mix.block_pin_runs() through the compiled reference, once per module"""
+    import stream_mix
+    tag, name, positions, scheduled = run
+    if tag not in _REF_BLOCK:
+        _REF_BLOCK[tag] = stream_mix.block_run(load_blob(name), positions, scheduled, engine=RefHarness)
+    return _REF_BLOCK[tag]
+
+
+@pytest.mark.rcp("host")  # the compiled reference executes this CPU's rcpps; the pins belong to the profile of the host that wrote them
+@pytest.mark.parametrize("which", range(4), ids=["default_lock", "default_sched", "little_lock", "little_sched"])
+def test_the_mixed_block_is_the_reference(which):
+    """The block that the at-size tests compare the GPU with -- 389 positions x 30 frames: pitch from 60 to 767, silence that flips at
+    call boundaries, zero runs, threshold noise, denormals, +-3e6 sines -- through the reference and through the oracle, position by
+    position: in lock step and on each position's present frames under stream_mix.presence() with a fresh state at RESET's restart; on
+    the default model, and on the sparser one for 40 of the positions that take it under the link dressing.  Bit identity in out, vad,
+    gains, features, pitch, silence and final state: live where oracle/_ref is built, else against the recorded digests
+    (tests/golden/block_pins.npz, make_golden.py --block-pins)."""
+    import stream_mix
+    run = stream_mix.block_pin_runs()[which]
+    tag, name, positions, scheduled = run
+    assert tag == ["default_lock", "default_sched", "little_lock", "little_sched"][which]
+    if RefHarness.available():
+        want = _reference_block(run)
+        got = stream_mix.block_run(load_blob(name), positions, scheduled)
+        assert set(got) == set(want)
+        for k in ("out", "vad", "gains", "features", "pitch", "silence", "state"):
+            assert_bits_equal(got[k], want[k], f"{tag}: {k}")
+        return
+    g = golden("block_pins.npz")
+    assert g[f"{tag}_positions"].tolist() == positions
+    got = stream_mix.block_digest(stream_mix.block_run(load_blob(name), positions, scheduled))
+    assert set(got) == set(stream_mix.PIN_KEYS)
+    for k, v in got.items():
+        pin = g[f"{tag}_{k}"]
+        assert v.dtype == pin.dtype
+        assert_bits_equal(v, pin, f"{tag}: {k}")
+
+
+@pytest.mark.skipif(not RefHarness.available(), reason="oracle/_ref not built (needs the reference sources at build time)")
+def test_block_pins_are_the_reference():
+    """the recorded digests of the block are what the compiled reference computes, where it runs on a host of the recording's rcpps
+    profile (tests/golden/make_golden.py --block-pins)"""
+    import stream_mix
+    from oracle import binding
+    binding.set_rcp_profile("host")
+    prof = binding.rcp_profile()
+    path = os.path.join(ROOT, "tests", "golden", *(() if prof == "intel" else (prof.replace("-", "_"),)), "block_pins.npz")
+    if not os.path.exists(path):
+        pytest.skip(f"no block_pins.npz fixture for the {prof} profile")
+    g = np.load(path)
+    assert str(g["rcp_profile"]) == prof
+    runs = stream_mix.block_pin_runs()
+    assert {k for k in g.files if k not in ("rcp_profile", "host_cpu")} == {f"{t}_{k}" for t, *_ in runs for k in stream_mix.PIN_KEYS + ("positions",)}
+    for run in runs:
+        tag, _, positions, _ = run
+        assert g[f"{tag}_positions"].tolist() == positions
+        for k, v in stream_mix.block_digest(_reference_block(run)).items():
+            assert v.dtype == g[f"{tag}_{k}"].dtype
+            assert_bits_equal(v, g[f"{tag}_{k}"], f"{tag}: {k}")
+
+
 def test_x86_float_to_short_model_matches_the_compiler(tmp_path):
     """The int16 entry points (include/rnnoise_amd.h: rnnoise_batch_process_s16) convert on the device "as the reference's only
     caller does" (examples/rnnoise_demo.c:58: tmp[i] = x[i], float -> short).  Out of range that cast is undefined in C; what

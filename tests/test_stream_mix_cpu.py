@@ -10,7 +10,12 @@ that the linked gain differs from a participant's own almost everywhere, that th
 participates (no participant beside a present row, one, a silent or an absent row beside one, only the second half of a group of
 eight -- each for every K), and that a kernel that skips the fold, folds an absent row or gates on a row's own VAD, or a reset that
 forgets the gate counter, has something to fail on
-(test_stream_mix_linked_at_every_form, test_stream_mix_linked_masked_and_listed_at_every_form)."""
+(test_stream_mix_linked_at_every_form, test_stream_mix_linked_masked_and_listed_at_every_form).  And for the PCM dressing
+(stream_mix.DRESS_CASES and what follows it) on the CPU chain alone: that rates and formats mix in every neighbourhood, that groups
+of channels stay pure and lists whole, that every call's strides fit, that the cases reach the kernel forms they are for with the
+one-wave K0 everywhere, that the expectation reaches every G.711 segment, the zero codes and the denormals, and that a chain whose
+histories advance on an absent frame, whose reset keeps them or which encodes before the truncating cast changes expected rows
+(test_stream_mix_dressed_at_every_form, test_stream_mix_dressed_masked_and_listed_at_every_form)."""
 import os
 import subprocess
 
@@ -565,6 +570,231 @@ def test_the_linked_expectation_has_teeth(mix):
         msg[K]["absent_sibling_changes_out"] = found
         assert found >= 1, msg
     print("teeth", msg)
+
+
+# ---- the PCM dressing (stream_mix.DRESS_CASES, rate_codes(), formats(), dress_call_plan(), dress_expectation): what
+# test_stream_mix_dressed_at_every_form and test_stream_mix_dressed_masked_and_listed_at_every_form run ----
+_DRESSED = {}
+
+
+def _dressed(variant, scheduled, mutant=None):
+    """the CPU chain's run of the block under `variant`, lock-step or under the presence schedule, on the goldens' profile"""
+    from conftest import use_rcp_profile
+    use_rcp_profile("intel")
+    if (variant, scheduled, mutant) not in _DRESSED:
+        _DRESSED[variant, scheduled, mutant] = sm.dress_expectation(load_blob("default"), variant, scheduled, mutant)
+    return _DRESSED[variant, scheduled, mutant]
+
+
+def _valid(r):
+    """(T, B, 480) bool: the entries of the expectation's `out` that a present row owns"""
+    return r["present"][..., None] & (np.arange(480) < sm.frame_lengths()[:, None])[None]
+
+
+def test_the_pcm_dressing_keeps_its_rules(tmp_path):
+    from rnnoise_amd import g711, resample
+    codes, fmt, law = sm.rate_codes(), sm.formats(), sm.laws()
+    assert codes.shape == fmt.shape == law.shape == (sm.B,) and set(codes.tolist()) == {1, resample.RATE_32K, 2, 3, 6}
+    assert set(fmt.tolist()) == {g711.LINEAR, g711.ULAW, g711.ALAW} and set(law.tolist()) == {g711.ULAW, g711.ALAW}
+    assert (law[fmt != 0] == fmt[fmt != 0]).all() and len(set(law[fmt == 0].tolist())) == 2
+    pair = [(int(c), int(f)) for c, f in zip(codes, fmt)]
+    for p in range(sm.B):                                                     # cyclic: the copies of a batch wrap from 388 to 0
+        near = [pair[(p + d) % sm.B] for d in range(64)]
+        assert len({c for c, _ in near[:16]}) == 5 and len({f for _, f in near[:16]}) == 3, p
+        assert len(set(near)) == 15, p
+    lab, nth = sm.labels()
+    for cat in ("zero_runs", "threshold", "extreme"):
+        assert {int(codes[p]) for p in range(sm.B) if lab[p] == cat} == set(sm.RATE_CODES), cat
+    exe = _build(tmp_path, "channels_dispatch_test")
+    fit, side_by_side = [], 0
+    for n, path, typ, C, lay in sm.DRESS_CASES:
+        s16 = typ == "int16"
+        assert n % C == 0 and n % sm.B != 0 and typ in ("int16", "float") and 1 <= C <= 8, (n, C)
+        pos = np.arange(n) % sm.B
+        comp, table = sm.dress_companded(n, C, s16), sm.dress_formats(n, C, s16)
+        groups = comp.reshape(-1, C)
+        assert (groups == groups[:, :1]).all(), "a group with linear and companded rows"
+        if s16:
+            assert (table == np.where(comp, law[pos], 0)).all() and (groups[:, 0] == (fmt[pos[::C]] != 0)).all()
+            assert {int(x) for x in table} == {0, 1, 2}
+            if C > 1:
+                side_by_side += int((groups[:-1, 0] != groups[1:, 0]).sum())
+                both = (table.reshape(-1, C) == g711.ULAW).any(1) & (table.reshape(-1, C) == g711.ALAW).any(1)
+                assert both.sum() >= 10, "no group holds both laws"
+                # one position as a linear row in one copy and as a companded one in another
+                assert n < 2 * sm.B or any(len(set(comp[p::sm.B].tolist())) == 2 for p in range(sm.B))
+        else:
+            assert not comp.any() and (table == fmt[pos]).all() and table.any()     # a table that the float calls must ignore
+        for scheduled in (False, True):
+            for c in range(len(sm.CALLS)):
+                plan = sm.dress_call_plan(n, C, c, scheduled)
+                k, R = len(plan["frames"]), len(plan["src"])
+                assert R % C == 0 and plan["present"].shape == (k, R) and len(plan["stream"]) == R
+                assert (plan["stream"] % sm.B == plan["src"]).all()
+                st = sm.dress_strides(lay, C, k, R)
+                if st is not None:
+                    assert st[0] % 4 == 0 and st[1] % 4 == 0 and min(st) > 0
+                    fit.append(f"fit:{st[0]},{st[1]},480,{C},{R},{k}")
+                if scheduled and plan["kind"] == "list" and s16:              # a list's groups are groups of the batch: still pure
+                    rows_comp = comp[plan["stream"]].reshape(-1, C)
+                    assert (rows_comp == rows_comp[:, :1]).all()
+    assert side_by_side >= 100
+    got = subprocess.run([exe] + fit, capture_output=True, text=True, check=True).stdout.split()
+    laid = sum(lay != "default" for *_, lay in sm.DRESS_CASES)
+    assert laid >= 3 and len(fit) == laid * 2 * len(sm.CALLS) and got == ["1"] * len(fit)
+
+
+@pytest.mark.parametrize("n,path,typ,C,lay", sm.DRESS_CASES, ids=sm.DRESS_IDS)
+def test_every_dressed_case_lists_whole_groups(n, path, typ, C, lay):
+    pres = sm.presence() != 0
+    for c, kind in enumerate(sm.KINDS):
+        plan = sm.dress_call_plan(n, C, c)
+        fr = plan["frames"]
+        if kind != "list":
+            assert (plan["stream"] == np.arange(n)).all() and (plan["present"] == pres[fr.start:fr.stop][:, np.arange(n) % sm.B]).all()
+            continue
+        rows, streams = sm.dress_list_rows(n, C, c)
+        assert rows.dtype == np.int32 and len(rows) % C == 0 and len(rows) <= n + 3 and (plan["rows"] == rows).all()
+        bad = (rows < 0) | (rows >= n)
+        assert bad.sum() == 3 and sorted(rows[bad].tolist()) == [-1, n, 2 ** 31 - 1]
+        assert (rows[~bad] == streams[~bad]).all() and len(set(streams[~bad].tolist())) == (~bad).sum()
+        listed = np.isin(np.arange(n) % sm.B, sm.LISTED[c])
+        # every copy of every listed position is in the list, so that a position's frames do not depend on the copy
+        assert set(np.flatnonzero(listed).tolist()) <= set(rows[~bad].tolist())
+        assert (plan["present"] == (pres[fr.start:fr.stop][:, streams % sm.B] & ~bad)).all()
+        assert not plan["present"][:, bad].any() and plan["active"][:, bad].all() and (plan["active"][:, ~bad] == plan["present"][:, ~bad]).all()
+        assert (np.diff(streams[::C]) < 0).any()                              # not in stream order
+        if C > 1:
+            assert (streams.reshape(-1, C) == streams[::C, None] + np.arange(C)).all() and (streams[::C] % C == 0).all()
+            assert set((streams[::C] // C).tolist()) == set(np.flatnonzero(listed.reshape(-1, C).any(1)).tolist())
+            assert not listed[streams[bad]].any()                             # the replaced entries: rows that miss the call in every copy
+            assert sorted((np.flatnonzero(bad) % C).tolist()) == sorted([0, C // 2, C - 1])
+            assert plan["present"].reshape(len(fr), -1, C)[:, bad.reshape(-1, C).any(1)].any(), "no replaced entry beside a present sibling"
+            masked = ~bad & ~listed[streams]
+            assert masked.sum() >= 10 and not plan["active"][:, masked].any()  # listed with their group, masked out
+
+
+def test_the_dressed_cases_reach_every_kernel_form(tmp_path):
+    """every DRESS_CASES entry through the library's dispatch rules on 256 CUs with the default switches, shaped as a call of a batch
+    with a rate table (and, in the int16 calls, a format table): K0 is the one-wave form in every call, the other stages take the
+    forms the comments of DRESS_CASES name, and together every form that CASES reaches"""
+    exe = _build(tmp_path, "formats_dispatch_test")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RNNOISE_AMD_")}
+
+    def run(cases):
+        out = subprocess.run([exe] + cases, capture_output=True, text=True, check=True, env=env).stdout.split("\n")[:len(cases)]
+        return [tuple(l.split()) for l in out]
+
+    plan_exe = _build(tmp_path, "dispatch_test")
+    lock, stream, lists = {}, {}, {}
+    for case in sm.DRESS_CASES:
+        n, path, typ, C, _ = case
+        comp = int(typ == "int16")
+        if path is None:
+            path = int(subprocess.run([plan_exe, f"path:{n}"], capture_output=True, text=True, check=True, env=env).stdout)
+            assert path == 1
+        for c, kind in enumerate(sm.KINDS):
+            pipe = int(sm.CALLS[c] > 1)
+            lock.setdefault(case, []).append((pipe,) + run([f"fmt:{n},1,256,{path},{pipe},0,1,0,{comp}"])[0])
+            if kind == "list":
+                R = len(sm.dress_list_rows(n, C, c)[0])
+                lists.setdefault(case, []).append((pipe,) + run([f"fmt:{R},0,256,{path},{pipe},1,1,1,{comp}"])[0])
+            else:
+                stream.setdefault(case, []).append((pipe,) + run([f"fmt:{n},1,256,{path},{pipe},1,1,0,{comp}"])[0])
+    every = [f for d in (lock, stream, lists) for v in d.values() for f in v]
+    assert {f[1] for f in every} == {"rn_hp_one_kernel"}
+    by_n = {(c[0], c[1]): c for c in sm.DRESS_CASES}
+    for f in lock[by_n[252, 0]]:
+        assert (f[2], f[3], f[5]) == ("rn_analysis_single_kernel", "rn_nn_one_kernel", "rn_synthesis_few_kernel"), f
+    assert {(f[3], f[5]) for f in lock[by_n[390, 0]]} == {("rn_nn_one_kernel", "rn_synthesis_kernel")}
+    assert {(f[0], f[3]) for f in lock[by_n[390, 1]]} == {(0, "rn_nn_mfma16_kernel"), (1, "rn_nn_mfma_kernel")}
+    assert {f[3:5] for f in lock[by_n[390, 2]]} == {("layers", "rn_nn_gru_w8_kernel")}
+    assert {f[3] for f in lock[by_n[1032, 0]]} == {"rn_nn_vector_kernel"}
+    assert {f[2] for f in lock[by_n[2568, None]]} == {"rn_analysis_kernel"}
+    assert {f[2] for f in stream[by_n[2568, None]]} == {"rn_analysis_single_kernel"}
+    assert run(["fmt:2568,1,256,1,0,0,0,0,0"])[0][0] == "rn_hp_kernel"       # what the plain batch runs there
+    for d in (lock, stream):
+        assert {f[3:5] for f in d[by_n[10278, None]]} == {("layers", "rn_nn_gru_w8_kernel")}
+        assert {f[3:5] for f in d[by_n[16416, None]]} == {("layers", "rn_nn_gru_kernel")}
+    assert (16416 + 63) // 64 == 257
+    forms = _forms()
+    seen = {"kK1": {f[2] for f in every}, "kNn": {f[3] for f in every}, "kGru": {f[4] for f in every if f[3] == "layers"},
+            "kK3": {f[5] for f in every}}
+    for kind, names in seen.items():
+        assert names == forms[kind], (kind, forms[kind] - names)
+
+
+def test_the_dressed_expectation_has_teeth():
+    """on the CPU chain alone: both laws reach every segment with both signs in the expected output, zero frames come out as the laws'
+    zero codes, the denormal stream is still denormal at its low rate, the float and the int16 chain differ, and the schedule shows"""
+    from rnnoise_amd import g711
+    lab, nth = sm.labels()
+    law, codes, M = sm.laws(), sm.rate_codes(), sm.frame_lengths()
+    msg = {}
+    for scheduled in (False, True):
+        r = _dressed("law", scheduled)
+        ok = _valid(r)
+        assert r["out"].dtype == np.uint8 and not r["out"][~ok].any()
+        for name, code, zero in (("ulaw", g711.ULAW, 0xFF), ("alaw", g711.ALAW, 0xD5)):
+            at = ok & (law == code)[None, :, None]
+            seg, neg = g711.segment(r["out"][at], code)
+            msg[name, scheduled] = len(set(zip(seg.tolist(), neg.tolist())))
+            assert msg[name, scheduled] == 16, msg
+            # frames whose output is exact zero: all of the row's bytes are the law's code of zero
+            quiet = [(t, p) for p in np.flatnonzero(law == code) for t in range(sm.T)
+                     if r["present"][t, p] and lab[p] in ("all_zero", "zero_runs") and (r["out"][t, p, :M[p]] == zero).all()]
+            msg[name + "_zero_frames", scheduled] = len(quiet)
+            assert len(quiet) >= 3, msg
+    zero = sm.labels()[0].index("all_zero")
+    assert (sm.dress_input("law")[:, zero, :M[zero]] == (0xFF if law[zero] == g711.ULAW else 0xD5)).all()
+    assert (_dressed("law", False)["out"][:, zero, :M[zero]] == (0xFF if law[zero] == g711.ULAW else 0xD5)).all()
+    # the denormal stream (extreme_signals' fifth, sigma 1e-38): a low rate; its low-rate input is nonzero nearly everywhere, below the
+    # smallest normal in most samples (a sample beyond one sigma is a normal number) and nowhere above a few sigma; so is what comes out
+    den = next(p for p in range(sm.B) if lab[p] == "extreme" and nth[p] == 4)
+    tiny = np.finfo(np.float32).tiny
+    for what, x in (("in", sm.dress_input("float")[:, den, :M[den]]), ("out", _dressed("float", False)["out"][:, den, :M[den]])):
+        msg["denormal " + what] = (int(codes[den]), float((x != 0).mean()), float((np.abs(x) < tiny).mean()), float(np.abs(x).max()))
+        assert codes[den] != 1 and (x != 0).mean() >= 0.9 and ((x != 0) & (np.abs(x) < tiny)).mean() >= 0.5 and np.abs(x).max() < 1e-37, msg
+    # +-3e6: the float rows keep it, the int16 rows clip it
+    loud = next(p for p in range(sm.B) if lab[p] == "extreme" and nth[p] == 1)
+    assert np.abs(sm.dress_input("float")[:, loud]).max() > 1e6 and np.abs(sm.dress_input("s16")[:, loud].astype(int)).max() >= 32767
+    # the three variants are three runs: vad differs between them for most positions
+    f, s, c = (_dressed(v, True) for v in sm.VARIANTS)
+    assert ((f["vad"] != s["vad"]).any(0)).mean() >= 0.5 and ((s["vad"] != c["vad"]).any(0)).mean() >= 0.5
+    # a kernel that ignores the mask: the expectation under the schedule differs from the lock-step one on present frames
+    for v in sm.VARIANTS:
+        a, b = _dressed(v, True), _dressed(v, False)
+        differ = [(a["out"][a["present"][:, p], p] != b["out"][a["present"][:, p], p]).any() for p in range(sm.B)]
+        assert np.mean(differ) >= 0.5, (v, np.mean(differ))
+    print("dressed teeth", msg)
+
+
+@pytest.mark.parametrize("mutant", sm.DRESS_MUTANTS)
+def test_the_dressed_expectation_catches_a_wrong_chain(mutant):
+    """a chain whose resampler history advances on an absent frame, one whose reset keeps the history, one that encodes before the
+    truncating cast: each changes expected rows"""
+    variant = "law" if mutant == "encode_before_cast" else "s16"
+    good, bad = _dressed(variant, True), _dressed(variant, True, mutant)
+    rows = (good["out"] != bad["out"]).any(-1)                                # (T, B)
+    codes = sm.rate_codes()
+    assert not rows[~good["present"]].any()
+    if mutant == "encode_before_cast":
+        assert rows.any(0).sum() >= 100, rows.any(0).sum()
+        for k in ("vad", "gains", "state"):
+            assert (good[k].view(np.uint32) == bad[k].view(np.uint32)).all(), k
+        return
+    assert not rows[:, codes == 1].any()                                      # (no resampler, no history)
+    low = np.flatnonzero(codes != 1)
+    if mutant == "reset_keeps_history":
+        cut = sm.call_frames(sm.RESET_BEFORE)[0]
+        hit = [p for p in sm.RESET if codes[p] != 1]
+        assert not rows[:cut].any() and not rows[:, [p for p in low if p not in sm.RESET]].any()
+        assert len(hit) >= 10 and rows[cut:, hit].any(0).sum() >= len(hit) - 3, (len(hit), rows[cut:, hit].any(0).sum())
+        assert {int(codes[p]) for p in hit if rows[:, p].any()} == set(sm.RATE_CODES) - {1}
+    else:
+        gaps = ~good["present"][:, low].all(0)
+        assert rows[:, low][:, gaps].any(0).mean() >= 0.9
+        assert {int(codes[p]) for p in low if rows[:, p].any()} == set(sm.RATE_CODES) - {1}
 
 
 def test_a_reset_that_forgets_the_gate_counter_shows_in_the_expectation():
