@@ -433,6 +433,51 @@ RNNOISE_EXPORT int rnnoise_batch_load_streams_device(RNNoiseBatch *b, const floa
 RNNOISE_EXPORT int rnnoise_batch_save_streams(RNNoiseBatch *b, float *snap, const int *streams, int n);
 RNNOISE_EXPORT int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap, const int *streams, int n);
 
+/* Chunked calls: any number of samples per stream and call.  Audio that does not arrive in 10 ms frames -- AAC blocks of 1024,
+ * capture callbacks of 64 .. 2048 samples, 7.5 ms Bluetooth frames, legs whose packet sizes differ inside one batch -- goes through
+ * two FIFOs per stream that live on the device, so the caller re-blocks nothing.  M = 480 * rate / 48000, the batch's frame.
+ * Every stream s owns an input FIFO of r_s pending samples, 0 <= r_s < M, and an output FIFO of M - r_s samples; after create,
+ * rnnoise_batch_reset and every restart below r_s = 0 and the output FIFO holds M zeros.  A chunk call gives stream s
+ * counts[s] = n_s new samples, 0 <= n_s <= max_count, and returns exactly n_s output samples.  With x the concatenation of all input
+ * ever pushed to the stream and y that of all output ever returned:  y[t] = 0 for t < M, and y[t] = z[t - M] otherwise, where z is what
+ * the lock-step call returns for x cut into frames -- bit for bit, float and int16 (the int16 forms: the float call on the exactly
+ * converted input, then the truncating cast of the int16 calls).  The constant latency is one frame, the smallest that lets every
+ * push return as many samples as it took.  A push completes k_s = (r_s + n_s) / M frames and leaves (r_s + n_s) % M samples pending.
+ * Buffers: in / out are [n_streams][max_count], rows max_count samples apart and aligned as their element only (a row of 441 or 1023
+ * samples is legal); in may be out.  Stream s reads and writes the first counts[s] samples of its row; the rest of the row is neither
+ * read nor written.  vad is [F][n_streams], gains [F][n_streams][32], F = rnnoise_amd_chunk_frames(M, max_count), the most frames a
+ * push can complete: rows j < k_s of a stream hold what the lock-step call gives for those frames, bit for bit, rows k_s <= j < F
+ * vad 0 and 32 zero gains, as absent frames of a masked call.  frames is [n_streams] and receives k_s.  The three may be NULL.
+ * rnnoise_amd_chunk_frames: (frame_samples - 1 + max_count) / frame_samples; 0 for max_count == 0; -1 for frame_samples <= 0 or
+ * max_count < 0.  Host only.
+ * Device forms: asynchronous on hip_stream, three steps on it -- the caller's rows and the pending samples into whole frames in a
+ * staging buffer of the batch, the masked float call on those frames (F frames are launched whatever the counts, which only the
+ * device knows), the frames' output and the output FIFO into the caller's rows.  d_counts is int32 in device memory; a negative
+ * entry reads as 0, an entry above max_count as max_count.  The FIFOs (3.9 KB per stream) and the staging buffer (F frames of the
+ * batch) are allocated at the first chunk call; a later call with a larger F grows the staging buffer, and that one call
+ * synchronises with the device.  Host forms: the convenience path -- synchronous, plain copies; a count out of range returns -1 with
+ * nothing changed.  max_count == 0 is a successful no-op; max_count < 0, a NULL batch or NULL counts / in / out return -1.
+ * Works with every batch rate (rnnoise_batch_set_pcm_rate), float and int16, model slots, stream controls and
+ * rnnoise_batch_reset_streams[_device].  Returns -1 with nothing launched while the batch has a rate table, a format table, a PCM
+ * layout, channels > 1 or a gain link > 1.  The first chunk call switches the batch to per-stream frame phase, as the first masked
+ * call does.  rnnoise_batch_reset, rnnoise_batch_reset_streams[_device], rnnoise_batch_import_state and
+ * rnnoise_batch_load_streams[_device] restart the FIFOs of the streams they touch, rnnoise_batch_set_pcm_rate those of every stream.
+ * Snapshots do not carry FIFO contents (RNNOISE_AMD_SNAP_FLOATS and the record stay): move a stream at a frame boundary --
+ * rnnoise_batch_chunk_fill writes r_s of every stream into fill[n_streams], synchronously; at r_s = 0 only the M output samples
+ * still in the FIFO are lost with the move.  The other call forms on the same batch neither read nor change the
+ * FIFOs.  0 / -1. */
+RNNOISE_EXPORT int rnnoise_amd_chunk_frames(int frame_samples, int max_count);
+RNNOISE_EXPORT int rnnoise_batch_process_device_chunks(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts,
+                                                       int max_count, float *d_vad, float *d_gains, int *d_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_device_chunks_s16(RNNoiseBatch *b, short *d_out, const short *d_in, const int *d_counts,
+                                                           int max_count, float *d_vad, float *d_gains, int *d_frames,
+                                                           void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_chunks(RNNoiseBatch *b, float *out, const float *in, const int *counts, int max_count,
+                                                float *vad, float *gains, int *frames);
+RNNOISE_EXPORT int rnnoise_batch_process_chunks_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts, int max_count,
+                                                    float *vad, float *gains, int *frames);
+RNNOISE_EXPORT int rnnoise_batch_chunk_fill(RNNoiseBatch *b, int *fill);
+
 /* Network implementation: 0 = vector path (v_dot4 / FMA chains), 1 = batched MFMA path -- one kernel per 16-stream tile
  * below 10,240 streams, layer by layer (64 streams per GRU workgroup, five launches) from there up --, 2 = the layer-wise
  * MFMA schedule whatever the batch size (tests, A/B runs).  All produce identical bits and share all state: the path may

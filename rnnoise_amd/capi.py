@@ -67,6 +67,8 @@ EXPORTS = [
     "rnnoise_amd_train_vad_device_available", "rnnoise_batch_train_levels_vad_device",
     "rnnoise_amd_train_rir_check", "rnnoise_amd_train_rir_work_bytes", "rnnoise_batch_train_rir_load_device",
     "rnnoise_batch_train_rir_device",
+    "rnnoise_amd_chunk_frames", "rnnoise_batch_process_device_chunks", "rnnoise_batch_process_device_chunks_s16",
+    "rnnoise_batch_process_chunks", "rnnoise_batch_process_chunks_s16", "rnnoise_batch_chunk_fill",
 ]
 
 
@@ -220,6 +222,10 @@ def _load(path, debug):
                                ("process_list", [vp, pp, pp, fp, fp, ip, C.c_int, up, C.c_int]),
                                ("process_device_list", [vp] * 6 + [C.c_int, vp, C.c_int, vp])):
                 getattr(L, f"rnnoise_batch_{name}{sfx}").argtypes = args
+            getattr(L, f"rnnoise_batch_process_chunks{sfx}").argtypes = [vp, pp, pp, ip, C.c_int, fp, fp, ip]
+            getattr(L, f"rnnoise_batch_process_device_chunks{sfx}").argtypes = [vp] * 4 + [C.c_int] + [vp] * 4
+        L.rnnoise_amd_chunk_frames.argtypes = [C.c_int, C.c_int]
+        L.rnnoise_batch_chunk_fill.argtypes = [vp, ip]
         # the per-stream tables: host setter, device setter (table, stream), getter
         for name, tp in (("rates", up), ("formats", up), ("models", up), ("controls", fp)):
             getattr(L, f"rnnoise_batch_set_stream_{name}").argtypes = [vp, tp]
@@ -296,6 +302,15 @@ def log10_model() -> str:
     """which log10 the feature stage evaluates: "host=glibc-fma" (the host libm's algorithm restated on the device) | "glibc-fma" |
     "ocml" | "host=unknown:ocml" (include/rnnoise_amd.h; $RNNOISE_AMD_LOG10)"""
     return lib().rnnoise_amd_log10_model().decode()
+
+
+def chunk_frames(frame_samples: int, max_count: int) -> int:
+    """F, the frame rows of vad / gains a chunk call of at most max_count samples per stream can complete at a frame of
+    frame_samples (rnnoise_amd_chunk_frames; host only).  ValueError for a bad argument."""
+    f = lib().rnnoise_amd_chunk_frames(int(frame_samples), int(max_count))
+    if f < 0:
+        raise ValueError("rnnoise_amd_chunk_frames: frame_samples > 0 and max_count >= 0")
+    return f
 
 
 def pcm_channels_fit(frame_stride: int, row_stride: int, frame_samples: int, channels: int, n_rows: int, n_frames: int) -> bool:
@@ -689,6 +704,55 @@ class Batch:
         fn = self._L.rnnoise_batch_process_device_masked_s16 if s16 else self._L.rnnoise_batch_process_device_masked
         if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_active or None, n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_process_device_masked failed")
+
+    def _process_chunks(self, name, dtype, pcm, counts, want_gains, out):
+        pcm = np.asarray(pcm)
+        if pcm.ndim != 2 or pcm.shape[0] != self.n:
+            raise ValueError(f"chunk PCM is (n_streams, max_count); got {pcm.shape} for {self.n} streams")
+        pcm = np.ascontiguousarray(pcm, dtype)
+        max_count = pcm.shape[1]
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.int32)
+        if counts.size != self.n:
+            raise ValueError("one count per stream")
+        if out is None:
+            out = np.zeros_like(pcm)
+        elif out.dtype != dtype or out.shape != pcm.shape or not out.flags.c_contiguous:
+            raise ValueError("out: a C-contiguous array of the PCM's shape and type")
+        F = chunk_frames(self.frame, max_count)
+        vad = np.zeros((F, self.n), np.float32)
+        gains = np.zeros((F, self.n, 32), np.float32) if want_gains else None
+        frames = np.zeros(self.n, np.int32)
+        pp = C.POINTER(C.c_short if dtype == np.int16 else C.c_float)
+        ip = C.POINTER(C.c_int)
+        self._call(f"rnnoise_batch_{name}", out.ctypes.data_as(pp), pcm.ctypes.data_as(pp), counts.ctypes.data_as(ip),
+                   int(max_count), _fp(vad), _fp(gains), frames.ctypes.data_as(ip), exc=ValueError,
+                   why=" (a count outside [0, max_count], or a batch with a rate / format table, a PCM layout, channels or a gain link?)")
+        return out, vad, gains, frames
+
+    def process_chunks(self, pcm: np.ndarray, counts, want_gains: bool = True, out: np.ndarray | None = None):
+        """Any number of samples per stream: pcm (N, max_count) float32, stream s pushes its first counts[s] samples -> (out, vad[F,N],
+        gains[F,N,32], frames[N]): rnnoise_batch_process_chunks.  out[s, :counts[s]] is the stream's output, one frame late; the rest of
+        the row keeps what `out` held (zeros when it is not given).  frames[s] rows of vad / gains belong to stream s."""
+        return self._process_chunks("process_chunks", np.float32, pcm, counts, want_gains, out)
+
+    def process_chunks_s16(self, pcm: np.ndarray, counts, want_gains: bool = True, out: np.ndarray | None = None):
+        """process_chunks on int16 PCM (rnnoise_batch_process_chunks_s16)"""
+        return self._process_chunks("process_chunks_s16", np.int16, pcm, counts, want_gains, out)
+
+    def process_chunks_device(self, d_out: int, d_in: int, d_counts: int, max_count: int, d_vad: int = 0, d_gains: int = 0,
+                              d_frames: int = 0, stream: int = 0, s16: bool = False):
+        """Raw device pointers (ints), asynchronous on `stream`: d_in / d_out [N][max_count] float32 (int16 with s16), d_counts [N]
+        int32 (clamped into [0, max_count]), d_vad [F][N], d_gains [F][N][32], d_frames [N] int32 or 0."""
+        fn = self._L.rnnoise_batch_process_device_chunks_s16 if s16 else self._L.rnnoise_batch_process_device_chunks
+        if fn(self.h, d_out or None, d_in or None, d_counts or None, int(max_count), d_vad or None, d_gains or None, d_frames or None,
+              stream or None):
+            raise RuntimeError("rnnoise_batch_process_device_chunks failed")
+
+    def chunk_fill(self) -> np.ndarray:
+        """the pending input samples r_s of every stream, (N,) int32 (rnnoise_batch_chunk_fill; synchronous)"""
+        fill = np.zeros(self.n, np.int32)
+        self._call("rnnoise_batch_chunk_fill", fill.ctypes.data_as(C.POINTER(C.c_int)))
+        return fill
 
     def process_list(self, pcm: np.ndarray, streams, active=None, want_gains: bool = True, out: np.ndarray | None = None):
         """Advance only the listed streams: pcm (T, R, 480 / L) float32, row i of every frame belongs to stream streams[i]; active:

@@ -163,6 +163,8 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   for (auto &e : b->pool) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   host_io_release(b);
   if (b->state_stage) hipFree(b->state_stage);
+  if (b->chunk_fifo) hipFree(b->chunk_fifo);
+  if (b->chunk_stage) hipFree(b->chunk_stage);
   if (b->arena) hipFree(b->arena);
   if (b->rs_buf) hipFree(b->rs_buf);
   if (b->rate_map) hipFree(b->rate_map);
@@ -193,6 +195,7 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   HIP_OK(hipMemset(b->arena, 0, b->arena_bytes));
   if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float)));  // (the histories; rs_up / rs_dn are scratch)
   if (b->g.gate_c) HIP_OK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b->g.gate_c), RN_CTL_NONE, b->n));  // (the table stays)
+  if (batch_chunk_restart_all(b)) return -1;  // (the sample FIFOs of the chunk calls)
   HIP_OK(hipDeviceSynchronize());
   b->img_valid = false;
   b->parity = 0;
@@ -573,6 +576,134 @@ extern "C" int rnnoise_batch_process_list_s16(RNNoiseBatch *b, short *out, const
                                               const int *streams, int n_rows, const unsigned char *active, int n_frames) {
   return batch_process_list_host(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames, .s16 = true,
                                      .active = active, .list = streams, .n_rows = n_rows});
+}
+
+// ---- chunk calls (include/rnnoise_amd.h) ----
+// Any number of samples per stream and call: the streams' sample FIFOs live on the device (chunk_plan.h has the rule), and a call is
+// three steps on the caller's stream -- the scatter kernel's chunk form (pending samples ++ the caller's rows -> whole frames in the
+// batch's own staging buffer, their mask, the new tails), the masked float call on that buffer in place, the gather kernel's chunk form
+// (output FIFO ++ the frames' output -> the caller's rows, the rest kept).  The int16 forms differ in the two staging steps alone.
+extern "C" int rnnoise_amd_chunk_frames(int frame_samples, int max_count) { return rn_chunk_frames(frame_samples, max_count); }
+
+// every stream's FIFOs as after create; the caller has selected the device and drained it, and drains it again
+int batch_chunk_restart_all(RNNoiseBatch *b) {
+  if (!b->chunk_fifo) return 0;
+  HIP_OK(hipMemset(b->chunk_fifo, 0, (size_t)b->n * RN_CHUNK_REC * sizeof(float)));  // (chunk_plan.h: a record of zeros)
+  return 0;
+}
+
+namespace {
+// what a chunk call does not combine with (include/rnnoise_amd.h): per-stream rates and formats, a PCM layout, channels, linked gains
+bool chunk_refused(const RNNoiseBatch *b) { return b->g.rs_Ls || b->g.pcm_fmt || b->row_stride || b->channels > 1 || b->link > 1; }
+// The FIFOs, on the first chunk call (their first state written on st, ahead of the call), and a staging buffer of at least F frames:
+// frames of RN_FRAME_SIZE floats whatever the rate, so that a rate change keeps it.  Growing it drains the device first -- the old
+// buffer may be in use by a call in flight on another stream.
+int chunk_ready(RNNoiseBatch *b, int F, hipStream_t st) {
+  const size_t N = b->n;
+  if (!b->chunk_fifo) {
+    HIP_OK(hipMalloc((void **)&b->chunk_fifo, N * RN_CHUNK_REC * sizeof(float)));
+    HIP_OK(hipMemsetAsync(b->chunk_fifo, 0, N * RN_CHUNK_REC * sizeof(float), st));
+  }
+  if (F > b->chunk_stage_frames) {
+    if (b->chunk_stage) {
+      HIP_OK(hipDeviceSynchronize());
+      HIP_OK(hipFree(b->chunk_stage));
+      b->chunk_stage = nullptr;
+      b->chunk_stage_frames = 0;
+    }
+    HIP_OK(hipMalloc(&b->chunk_stage, (size_t)F * N * (RN_FRAME_SIZE * sizeof(float) + 1)));
+    b->chunk_stage_frames = F;
+  }
+  return 0;
+}
+
+int chunks_device(RNNoiseBatch *b, void *d_out, const void *d_in, const int *d_counts, int max_count, float *d_vad, float *d_gains,
+                  int *d_frames, void *hip_stream, bool s16) {
+  if (!b || !d_out || !d_in || !d_counts || max_count < 0 || chunk_refused(b)) return -1;
+  if (max_count == 0) return 0;
+  const int M = batch_frame_samples(b), F = rn_chunk_frames(M, max_count);
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  ON_DEVICE(b->device);
+  if (chunk_ready(b, F, st)) return -1;
+  RnChunkDev ck = batch_chunk_fifos(b, 0);
+  ck.N = b->n;
+  ck.max_count = max_count;
+  ck.F = F;
+  ck.s16 = s16;
+  ck.counts = d_counts;
+  ck.in = d_in;
+  ck.out = d_out;
+  ck.stage = static_cast<float *>(b->chunk_stage);
+  ck.active = reinterpret_cast<unsigned char *>(ck.stage + (size_t)b->chunk_stage_frames * b->n * RN_FRAME_SIZE);
+  ck.frames = d_frames;
+  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_CHUNK, nullptr, nullptr, b->n, 0, nullptr, &ck, st));
+  // (the masked call reads frame f's rows in K0 and writes them in K3 of the same frame: in place)
+  if (batch_process_device_impl(b, {.out = ck.stage, .in = ck.stage, .vad = d_vad, .gains = d_gains, .n_frames = F, .stream = hip_stream,
+                                    .active = ck.active, .packed = true}))
+    return -1;
+  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_CHUNK, nullptr, nullptr, b->n, 0, nullptr, &ck, st));
+  return 0;
+}
+
+// the convenience form on host buffers: the counts are checked before anything moves; whole rows go up, and only the first counts[s]
+// samples of a row come back into the caller's `out`
+int chunks_host(RNNoiseBatch *b, void *out, const void *in, const int *counts, int max_count, float *vad, float *gains, int *frames,
+                bool s16) {
+  if (!b || !out || !in || !counts || max_count < 0 || chunk_refused(b)) return -1;
+  for (int s = 0; s < b->n; s++)
+    if (counts[s] < 0 || counts[s] > max_count) return -1;
+  if (max_count == 0) return 0;
+  const size_t N = b->n, esz = s16 ? sizeof(short) : sizeof(float), row = (size_t)max_count * esz;
+  const size_t fs = (size_t)rn_chunk_frames(batch_frame_samples(b), max_count) * N;
+  ON_DEVICE(b->device);
+  DevScratch d;
+  const size_t o_in = d.carve(N * row), o_out = d.carve(N * row), o_counts = d.carve(N * sizeof(int)), o_vad = d.carve(fs * 4),
+               o_gains = d.carve(fs * RN_NB_BANDS * 4), o_frames = d.carve(N * sizeof(int));
+  if (d.alloc()) return -1;
+  HIP_OK(hipMemcpy(d.at<char>(o_in), in, N * row, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d.at<char>(o_counts), counts, N * sizeof(int), hipMemcpyHostToDevice));
+  if (chunks_device(b, d.at<char>(o_out), d.at<char>(o_in), d.at<int>(o_counts), max_count, vad ? d.at<float>(o_vad) : nullptr,
+                    gains ? d.at<float>(o_gains) : nullptr, frames ? d.at<int>(o_frames) : nullptr, nullptr, s16))
+    return -1;
+  HIP_OK(hipDeviceSynchronize());
+  std::vector<char> rows(N * row);
+  HIP_OK(hipMemcpy(rows.data(), d.at<char>(o_out), N * row, hipMemcpyDeviceToHost));
+  for (size_t s = 0; s < N; s++) memcpy(static_cast<char *>(out) + s * row, rows.data() + s * row, (size_t)counts[s] * esz);
+  if (vad) HIP_OK(hipMemcpy(vad, d.at<char>(o_vad), fs * 4, hipMemcpyDeviceToHost));
+  if (gains) HIP_OK(hipMemcpy(gains, d.at<char>(o_gains), fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost));
+  if (frames) HIP_OK(hipMemcpy(frames, d.at<char>(o_frames), N * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+
+extern "C" int rnnoise_batch_process_device_chunks(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts, int max_count,
+                                                   float *d_vad, float *d_gains, int *d_frames, void *hip_stream) {
+  return chunks_device(b, d_out, d_in, d_counts, max_count, d_vad, d_gains, d_frames, hip_stream, false);
+}
+extern "C" int rnnoise_batch_process_device_chunks_s16(RNNoiseBatch *b, short *d_out, const short *d_in, const int *d_counts,
+                                                       int max_count, float *d_vad, float *d_gains, int *d_frames, void *hip_stream) {
+  return chunks_device(b, d_out, d_in, d_counts, max_count, d_vad, d_gains, d_frames, hip_stream, true);
+}
+extern "C" int rnnoise_batch_process_chunks(RNNoiseBatch *b, float *out, const float *in, const int *counts, int max_count, float *vad,
+                                            float *gains, int *frames) {
+  return chunks_host(b, out, in, counts, max_count, vad, gains, frames, false);
+}
+extern "C" int rnnoise_batch_process_chunks_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts, int max_count,
+                                                float *vad, float *gains, int *frames) {
+  return chunks_host(b, out, in, counts, max_count, vad, gains, frames, true);
+}
+extern "C" int rnnoise_batch_chunk_fill(RNNoiseBatch *b, int *fill) {
+  if (!b || !fill) return -1;
+  if (!b->chunk_fifo) {  // (no chunk call yet: nothing pending anywhere)
+    memset(fill, 0, (size_t)b->n * sizeof(int));
+    return 0;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  // (one word of every record)
+  HIP_OK(hipMemcpy2D(fill, sizeof(int), b->chunk_fifo + 2 * RN_CHUNK_FIFO_ROW, RN_CHUNK_REC * sizeof(float), sizeof(int), b->n,
+                     hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // ---- training-feature extraction (reference loop src/dump_features.c:466-491) ----

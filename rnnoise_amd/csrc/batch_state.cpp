@@ -5,9 +5,11 @@
 
 namespace {
 // zero state for the n streams of the device list d_list, on st; the layer-wise network's state images of their tiles follow
-// (rn_dev.h: act_q) while they are in use, so that a reset costs no re-quantisation of the whole batch at the next step
+// (rn_dev.h: act_q) while they are in use, so that a reset costs no re-quantisation of the whole batch at the next step.  Every
+// scatter launch of this file gets the streams' sample FIFOs to restart (shim.h: batch_chunk_fifos)
 int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_zero(&b->g, d_list, n, st));
+  const RnChunkDev ck = batch_chunk_fifos(b, 0);
+  HIP_OK(rn_launch_state_zero(&b->g, d_list, n, &ck, st));
   if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n));
   return 0;
 }
@@ -61,7 +63,7 @@ extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
   HIP_OK(hipDeviceSynchronize());
   if (stage_ready(b)) return -1;
   const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_gather(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr));
+  HIP_OK(rn_launch_state_gather(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr, nullptr));
   // (a blocking copy on the null stream: ordered after the kernel)
   HIP_OK(hipMemcpy(f, b->state_stage, RN_STATE_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
@@ -79,7 +81,8 @@ extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f
   HIP_OK(hipMemcpy(b->state_stage, f, RN_STATE_FLOATS * sizeof(float), hipMemcpyHostToDevice));
   b->img_valid = false;
   const RnGroupDev v = group_view(b->g, s, 1);
-  HIP_OK(rn_launch_state_scatter(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), nullptr));
+  const RnChunkDev ck = batch_chunk_fifos(b, s);
+  HIP_OK(rn_launch_state_scatter(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), &ck, nullptr));
   HIP_OK(hipStreamSynchronize(nullptr));
   return 0;
 }
@@ -98,13 +101,14 @@ bool snap_args_ok(const RNNoiseBatch *b, const void *snap, const int *streams, i
   return true;
 }
 int save_on(RNNoiseBatch *b, float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), st));
+  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), nullptr, st));
   return 0;
 }
 // the listed rows' tiles of the layer-wise network's state images follow the load while they are live (rn_dev.h: act_q), as after
 // a per-stream reset; without a list that is every tile
 int load_on(RNNoiseBatch *b, const float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), st));
+  const RnChunkDev ck = batch_chunk_fifos(b, 0);
+  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), &ck, st));
   if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, d_list ? n : 0));
   return 0;
 }

@@ -87,14 +87,20 @@ extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
   if (!b || !rate_code(hz)) return -1;
   const int old = b->pcm_rate;
   b->frame_stride = b->row_stride = 0;  // (a PCM layout is in samples of the old rate's frame: dropped by every call)
-  if (hz == old && !b->g.rs_Ls) return old;  // (a rate table is dropped by every call: the rows are redefined)
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());  // (synchronous: nothing of the old rate is in flight)
+  if (hz == old && !b->g.rs_Ls) {  // (a rate table is dropped by every call: the rows are redefined)
+    if (batch_chunk_restart_all(b)) return -1;  // (... and the sample FIFOs of the chunk calls restart with every call)
+    HIP_OK(hipDeviceSynchronize());
+    return old;
+  }
   if (hz != 48000 && rs_alloc(b, nullptr)) return -1;
   if (b->rs_buf) HIP_OK(hipMemset(b->rs_buf, 0, (size_t)b->n * RN_RS_HIST * sizeof(float)));
   HIP_OK(hipDeviceSynchronize());
   b->pcm_rate = hz;
   rs_point(b, false);
+  if (batch_chunk_restart_all(b)) return -1;  // (at the new frame length)
+  HIP_OK(hipDeviceSynchronize());
   return old;
 }
 

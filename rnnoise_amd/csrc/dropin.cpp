@@ -109,7 +109,7 @@ void pool_release(StatePool *p, int slot) {
 // the stateful arrays of one row back to all-zero (what rnnoise_init does to a DenoiseState, src/denoise.c:286): one launch on st
 int pool_zero_row(StatePool *p, int slot, hipStream_t st) {
   const RnGroupDev v = group_view(p->batch->g, slot, 1);
-  HIP_OK(rn_launch_state_zero(&v, nullptr, 0, st));
+  HIP_OK(rn_launch_state_zero(&v, nullptr, 0, nullptr, st));
   return 0;
 }
 
@@ -744,9 +744,9 @@ extern "C" float rnnoise_process_frame(DenoiseState *st, float *out, const float
       memcpy(hu, st->state, RN_STATE_FLOATS * sizeof(float));
       memcpy(h_row + RN_ROW_IN, in, RN_FRAME_SIZE * sizeof(float));
       ok = hipMemcpyAsync(d_state, hu, RN_STATE_FLOATS * sizeof(float), hipMemcpyHostToDevice, sc.stream) == hipSuccess &&
-           rn_launch_state_scatter(&v, RN_REC_STATE, d_state, nullptr, 1, 0, nullptr, sc.stream) == hipSuccess &&
+           rn_launch_state_scatter(&v, RN_REC_STATE, d_state, nullptr, 1, 0, nullptr, nullptr, sc.stream) == hipSuccess &&
            rows_launch(pool, rows, sc.stream, false) == 0 &&
-           rn_launch_state_gather(&v, RN_REC_STATE, d_state, nullptr, 1, 1, nullptr, sc.stream) == hipSuccess &&
+           rn_launch_state_gather(&v, RN_REC_STATE, d_state, nullptr, 1, 1, nullptr, nullptr, sc.stream) == hipSuccess &&
            hipMemcpyAsync(hd, d_state, RN_STATE_FLOATS * sizeof(float), hipMemcpyDeviceToHost, sc.stream) == hipSuccess &&
            hipStreamSynchronize(sc.stream) == hipSuccess;
       if (ok) {

@@ -283,8 +283,8 @@ struct RnGroupDev {
   OPT(rs_up, RN_FRAME_SIZE)                                      \
   OPT(rs_dn, RN_FRAME_SIZE)
 // what the records of a state gather / scatter launch are (state_kernels.hip): portable states, RN_STATE_PITCH floats apart, or
-// snapshot records (include/rn_layout.h: RN_SNAP_*)
-enum RnRecKind { RN_REC_STATE, RN_REC_SNAP };
+// snapshot records (include/rn_layout.h: RN_SNAP_*), or the caller's PCM rows of a chunk call (chunk_plan.h: RnChunkDev -- no `rec`)
+enum RnRecKind { RN_REC_STATE, RN_REC_SNAP, RN_REC_CHUNK };
 #define RN_CTL_FLOATS 3      // = RNNOISE_AMD_CTL_FLOATS: floor, thr, hold
 #define RN_CTL_NONE 65536    // counter of a stream with no voice frame yet
 #define RN_RS_TAPS 48                           // taps per phase of the up filter; the down filter has RN_RS_TAPS * L

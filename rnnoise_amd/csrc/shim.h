@@ -38,6 +38,7 @@
 #endif
 #include "rcp_profiles.h"
 #include "dispatch.h"
+#include "chunk_plan.h"
 
 // the launchers of a frame step take the form the step's plan chose (dispatch.h: rn_plan)
 extern "C" hipError_t rn_launch_hp(const RnGroupDev *, const void *, int in_s16, int, RnHpForm, hipStream_t, hipEvent_t, hipEvent_t);
@@ -66,12 +67,14 @@ extern "C" hipError_t rn_launch_fft_probe(int, const float *, float *, unsigned 
 extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 #endif
 // (state_kernels.hip: `rows` records of `kind`, record i <-> stream list[i] of the view, at frame phase p or at the per-stream
-//  phases `phase`; and the zero state for the listed streams of the view, or for all of them)
+//  phases `phase`; and the zero state for the listed streams of the view, or for all of them.  ck: the sample FIFOs of the view's
+//  streams (chunk_plan.h; batch_chunk_fifos below), which every scatter restarts -- null where the group has none -- and, with
+//  RN_REC_CHUNK, the chunk call the launch is a staging step of)
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, RnRecKind kind, float *rec, const int *list, int rows, int p,
-                                             const int *phase, hipStream_t);
+                                             const int *phase, const RnChunkDev *ck, hipStream_t);
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, RnRecKind kind, const float *rec, const int *list, int rows, int p,
-                                              const int *phase, hipStream_t);
-extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *, const int *list, int n, hipStream_t);
+                                              const int *phase, const RnChunkDev *ck, hipStream_t);
+extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *, const int *list, int n, const RnChunkDev *ck, hipStream_t);
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);
 extern "C" hipError_t rn_launch_analysis_rows(const RnGroupDev *, const RnTablesDev *, const RnRows *, hipStream_t);
@@ -252,6 +255,12 @@ struct RNNoiseBatch {
   float *scratch_gains = nullptr, *scratch_vad = nullptr;
   float *debug_buf = nullptr;
   float *state_stage = nullptr;  // one flat state in HBM: export / import go through the gather / scatter kernels
+  // chunk calls (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks; batch.cpp).  chunk_fifo: the streams' sample FIFOs, from
+  // the first chunk call to the batch's end -- [N] records of RN_CHUNK_REC floats (chunk_plan.h; batch_chunk_fifos).  chunk_stage: the frames and the mask of the masked call inside a chunk call, [F][N][M] floats then [F][N]
+  // bytes for chunk_stage_frames = F frames; it grows when a call needs more
+  float *chunk_fifo = nullptr;
+  void *chunk_stage = nullptr;
+  int chunk_stage_frames = 0;
   // host-fed path (rnnoise_batch_process, host_io.cpp).  `run` carries the kernels and `down` the downloads of both kinds of caller
   struct HostIo {
     hipStream_t up = nullptr, run = nullptr, down = nullptr;
@@ -392,8 +401,18 @@ struct ProcessCall {
 };
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
 int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
+int batch_chunk_restart_all(RNNoiseBatch *b);                          // batch.cpp: every stream's sample FIFOs as after create
 // samples per row and frame at the batch's PCM rate
 inline int batch_frame_samples(const RNNoiseBatch *b) { return b->g.rs_L ? b->g.rs_pitch : RN_FRAME_SIZE; }
+// the sample FIFOs of streams first, first + 1, ... of a batch as the state kernels take them (chunk_plan.h: RnChunkDev, the call's
+// fields null), at the batch's current frame length; all null before the first chunk call
+inline RnChunkDev batch_chunk_fifos(const RNNoiseBatch *b, int first) {
+  RnChunkDev c{};
+  if (!b->chunk_fifo) return c;
+  c.fifo = b->chunk_fifo + (size_t)first * RN_CHUNK_REC;
+  c.M = batch_frame_samples(b);
+  return c;
+}
 // whether a host call takes the staged path instead of the pinned ring / bounce chunks of host_io.cpp: at a PCM rate other than 48 kHz
 // or with a rate table, with a PCM layout, with interleaved channels, and the int16 calls of a batch with a format table
 inline bool batch_host_call_staged(const RNNoiseBatch *b, bool s16) {

@@ -4,10 +4,13 @@
 //   rows == 0   one portable state per stream of the view (export / import, the caller-memory frames of the drop-in API);
 //   rows > 0    snapshot records (include/rn_layout.h: RN_SNAP_*) of many streams: the same body, then the record's tail;
 //   no record   (scatter only) the zero state of rnnoise_init().
+// A third record kind moves no state: the caller's PCM rows of a chunk call <-> the streams' sample FIFOs (chunk_fifo.h), scatter
+// in front of the call's frames and gather behind them.
 // The host side needs one memcpy per direction instead of one per field.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rn_dev.h"
+#include "chunk_fifo.h"
 
 // rnnoise_batch_save_streams / load_streams move 26.5 KB per stream for up to 65,536 streams, so the body is a copy, not a
 // dispatch: every field is one contiguous run in the record and one in the batch's arrays (the pitch ring: at most two on each side
@@ -32,6 +35,7 @@ static_assert(RN_SNAP_FLOATS % 4 == 0 && RN_STATE_PITCH % 4 == 0 && RN_SNAP_OFF_
 static_assert(RN_RING0(1) % 4 == 0 && RN_FRAME_SIZE % 4 == 0 && RN_PITCH_BUF_SIZE % 4 == 0, "ring runs are 16-byte aligned");
 static_assert(RN_OFF_LAST_PERIOD == RN_OFF_LAST_GAIN + 1 && RN_OFF_MEM_HP == RN_OFF_LAST_GAIN + 2, "the four scalar words are consecutive");
 static_assert(!(RN_SNAP_THREADS & (RN_SNAP_THREADS - 1)) && !(RN_STATE_THREADS & (RN_STATE_THREADS - 1)), "move_run rotates lanes by a mask");
+static_assert(RN_CHUNK_FIFO_ROW == RN_FRAME_SIZE, "a FIFO row holds the longest frame");
 static_assert(RN_RING_SLOTS % RN_SPEC_SLOTS == 0, "one frame phase, mod RN_RING_SLOTS, gives the ring slot and the spectra slot");
 namespace {
 // n floats, src -> dst, by the workgroup (both pointers uniform), lane `lane0` (mod the workgroup, a power of two) taking the first
@@ -163,22 +167,36 @@ __device__ __forceinline__ void zero_state(const RnGroupDev &g, size_t s) {
   }
 }
 // what a stream of a batch has beside its portable state restarts with a state that carries none of it: the resampler histories
-// (rn_dev.h: rs_hist) zeroed, the counter of the suppression controls (gate_c) at "no voice frame yet"
-__device__ __forceinline__ void restart_extras(const RnGroupDev &g, size_t s) {
+// (rn_dev.h: rs_hist) zeroed, the counter of the suppression controls (gate_c) at "no voice frame yet", the sample FIFOs of the chunk
+// calls (chunk_plan.h: RnChunkDev) empty in and M zeros out
+__device__ __forceinline__ void restart_extras(const RnGroupDev &g, size_t s, const RnChunkDev &ck) {
   if (g.rs_hist) zero_run(g.rs_hist + s * RN_RS_HIST, RN_RS_HIST);
   if (g.gate_c && threadIdx.x == 0) g.gate_c[s] = RN_CTL_NONE;
+  rn_chunk_restart(ck, s, threadIdx.x, blockDim.x);
 }
 }  // namespace
 
 // Both kernels: record `row` <-> stream list[row] of the view (stream `row` without a list), at the frame phase phase[stream] (the
 // launch's p without `phase`).  rows > 0: `rows` snapshot records of RN_SNAP_FLOATS, the workgroups striding over them.  rows == 0:
 // one workgroup per record, portable states `pitch` floats apart.  An entry outside the view moves nothing.
+// rows < 0: a chunk launch (RN_REC_CHUNK; ck carries the call), workgroup b = stream b of the group and nothing of the above; the two
+// halves of its body (chunk_fifo.h) on either side of the workgroup's barrier.  (The sign of `rows`, not a field of ck: a state
+// launch decides from the arguments it read before there was a ck, and never waits for ck's end of the argument block.)
 
 // rec[row] <- stream.  A snapshot's tail: the header (magic, L, the gate counter or RN_CTL_NONE, three zeros) and the resampler
 // history or zeros; an entry outside the view leaves an empty record (magic 0).
 extern "C" __global__ void __launch_bounds__(1024)
 rn_state_gather_kernel(RnGroupDev g, float *__restrict__ rec, int p, const int *__restrict__ list, const int *__restrict__ phase, int rows,
-                       int pitch) {
+                       int pitch, RnChunkDev ck) {
+  if (rows < 0) {  // out[s] <- the stream's output FIFO ++ its staged frames; what is left is the FIFO
+    extern __shared__ float kept[];  // (RN_CHUNK_FIFO_ROW floats, on chunk launches only: a state launch keeps its LDS-free dispatch)
+    const size_t s = blockIdx.x;
+    if (s >= (size_t)ck.N) return;
+    const RnChunkHead h = rn_chunk_gather_head(ck, s);
+    rn_chunk_gather_pop(ck, s, h, kept, threadIdx.x, blockDim.x);
+    __syncthreads();
+    return rn_chunk_gather_keep(ck, s, h, kept, threadIdx.x, blockDim.x);
+  }
   const bool snap = rows > 0;
   const int n = snap ? rows : (int)gridDim.x, t = threadIdx.x;
   const size_t stride = snap ? RN_SNAP_FLOATS : pitch;
@@ -204,17 +222,25 @@ rn_state_gather_kernel(RnGroupDev g, float *__restrict__ rec, int p, const int *
 // stream <- rec[row] (16-byte aligned records), then what the portable state does not carry, where the view has it (g.rs_hist,
 // g.gate_c).  A snapshot brings both: the resampler history when its L is the stream's current one (zeros otherwise) and the gate
 // counter, clamped; a record with another magic word touches nothing.  A portable state restarts them (restart_extras).
-// No `rec`: stream <- the zero state, one workgroup per stream, and the extras restart as well.
+// No `rec`: stream <- the zero state, one workgroup per stream, and the extras restart as well (ck: the FIFOs among them).
 extern "C" __global__ void __launch_bounds__(1024)
 rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, const int *__restrict__ list, const int *__restrict__ phase,
-                        int rows, int pitch) {
+                        int rows, int pitch, RnChunkDev ck) {
+  if (rows < 0) {  // the stream's pending samples ++ in[s] -> its frames of the call and their mask; the tail is left pending
+    const size_t s = blockIdx.x;
+    if (s >= (size_t)ck.N) return;
+    const RnChunkHead h = rn_chunk_scatter_head(ck, s);
+    rn_chunk_scatter_frames(ck, s, h, threadIdx.x, blockDim.x);
+    __syncthreads();
+    return rn_chunk_scatter_tail(ck, s, h, threadIdx.x, blockDim.x);
+  }
   const bool snap = rows > 0;
   const int n = snap ? rows : (int)gridDim.x, t = threadIdx.x;
   if (!rec) {
     const int s = list ? list[blockIdx.x] : (int)blockIdx.x;
     if (s < 0 || s >= g.n_streams) return;
     zero_state(g, s);
-    return restart_extras(g, s);
+    return restart_extras(g, s, ck);
   }
   const size_t stride = snap ? RN_SNAP_FLOATS : pitch;
   for (int row = blockIdx.x; row < n; row += gridDim.x) {
@@ -223,7 +249,7 @@ rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, cons
     if (s < 0 || s >= g.n_streams || (snap && __float_as_int(f[RN_SNAP_OFF_MAGIC]) != RN_SNAP_MAGIC)) continue;
     scatter_state(g, s, f, latest_slots(p, phase, s));
     if (!snap) {
-      restart_extras(g, s);
+      restart_extras(g, s, ck);
       continue;
     }
     if (g.rs_hist) {
@@ -231,37 +257,47 @@ rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, cons
       else zero_run(g.rs_hist + (size_t)s * RN_RS_HIST, RN_RS_HIST);
     }
     if (g.gate_c && t == 64) g.gate_c[s] = min(max(__float_as_int(f[RN_SNAP_OFF_GATE]), 0), RN_CTL_NONE);
+    rn_chunk_restart(ck, s, t, blockDim.x);  // (a record carries no FIFO contents)
   }
 }
 
 // The launchers, one per direction: `rows` records of `kind`, record i <-> stream list[i] of the view (stream i when list is null).
 // p: the frame phase of a lock-step batch (the ring slot its next frame writes); phase: the per-stream phases on the device, indexed
 // as the view's rows, which then take p's place.  Scattered records are 16-byte aligned (both pitches are multiples of 4 floats).
+// ck: the FIFOs of the view's streams, which a scatter restarts (null: the group has none), and with kind RN_REC_CHUNK the chunk
+// call -- `rows` streams, one workgroup of RN_SNAP_THREADS lanes each, no record and no list.
 namespace {
 template <typename Kernel, typename Rec>
 hipError_t launch_state(Kernel kernel, const RnGroupDev *g, RnRecKind kind, Rec rec, const int *list, int rows, int p, const int *phase,
-                        hipStream_t st) {
+                        const RnChunkDev *ck, hipStream_t st) {
   if (rows <= 0) return hipSuccess;
   const bool snap = kind == RN_REC_SNAP;
+  RnChunkDev c = ck ? *ck : RnChunkDev{};
+  if (kind == RN_REC_CHUNK) {
+    if (!ck || !ck->counts || rows != ck->N || rec) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(rows), dim3(RN_SNAP_THREADS), RN_CHUNK_FIFO_ROW * sizeof(float), st, *g, rec, 0, nullptr, nullptr, -1,
+                       RN_STATE_PITCH, c);
+    return hipGetLastError();
+  }
   // (RN_STATE_THREADS where one record's latency is the call's: a single state moved between two copies; RN_SNAP_THREADS where
   //  many records share the device, the zero state of a stream list included)
   hipLaunchKernelGGL(kernel, dim3(rows < RN_SNAP_GRID_CAP || !snap ? rows : RN_SNAP_GRID_CAP), dim3(snap || !rec ? RN_SNAP_THREADS : RN_STATE_THREADS),
-                     0, st, *g, rec, p, list, phase, snap ? rows : 0, RN_STATE_PITCH);
+                     0, st, *g, rec, p, list, phase, snap ? rows : 0, RN_STATE_PITCH, c);
   return hipGetLastError();
 }
 }  // namespace
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *g, RnRecKind kind, float *rec, const int *list, int rows, int p,
-                                             const int *phase, hipStream_t st) {
-  return launch_state(rn_state_gather_kernel, g, kind, rec, list, rows, p, phase, st);
+                                             const int *phase, const RnChunkDev *ck, hipStream_t st) {
+  return launch_state(rn_state_gather_kernel, g, kind, rec, list, rows, p, phase, ck, st);
 }
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *g, RnRecKind kind, const float *rec, const int *list, int rows, int p,
-                                              const int *phase, hipStream_t st) {
-  return launch_state(rn_state_scatter_kernel, g, kind, rec, list, rows, p, phase, st);
+                                              const int *phase, const RnChunkDev *ck, hipStream_t st) {
+  return launch_state(rn_state_scatter_kernel, g, kind, rec, list, rows, p, phase, ck, st);
 }
 // the zero state for the n streams list[i] of the view (one workgroup each), or for every stream of the view without a list
-extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *g, const int *list, int n, hipStream_t st) {
+extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *g, const int *list, int n, const RnChunkDev *ck, hipStream_t st) {
   return launch_state(rn_state_scatter_kernel, g, RN_REC_STATE, static_cast<const float *>(nullptr), list, list ? n : g->n_streams, 0,
-                      nullptr, st);
+                      nullptr, ck, st);
 }
 
 // One 64-bit store with system-scope release: how a HIP stream releases an explicit SDMA-engine copy that lists an HSA signal as its

@@ -107,6 +107,24 @@ def register_torch_op():
         N, T = pcm.shape[0] * pcm.shape[2], pcm.shape[1] // _OPS[handle].batch.frame
         return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
 
+    # the chunk form (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks): pcm (N, max_count) float32 or int16, stream s pushes
+    # its first counts[s] samples (counts: (N,) int32 CUDA tensor, clamped into [0, max_count]) and gets as many back, one frame late.
+    # Returns out (same shape and dtype as pcm, zeros beyond counts), vad (F, N), gains (F, N, 32) with F = capi.chunk_frames(M,
+    # max_count), and frames (N,) int32: the rows of vad / gains each stream filled.  The frame counter advances by F.
+    @torch.library.custom_op("rnnoise_amd::process_chunks", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor counts, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor, Tensor)")
+    def process_chunks(pcm, counts, state, handle):
+        op = _OPS[handle]
+        res = op._run_chunks(pcm, counts)
+        state.add_(capi.chunk_frames(op.batch.frame, pcm.shape[1]))
+        return res
+
+    @process_chunks.register_fake
+    def _(pcm, counts, state, handle):
+        N, F = pcm.shape[0], capi.chunk_frames(_OPS[handle].batch.frame, pcm.shape[1])
+        return (torch.empty_like(pcm), pcm.new_empty((F, N), dtype=torch.float32),
+                pcm.new_empty((F, N, capi.NB_BANDS), dtype=torch.float32), pcm.new_empty((N,), dtype=torch.int32))
+
     _registered = True
 
 
@@ -185,6 +203,12 @@ class RNNoiseOp:
         if link is not None:
             self.set_gain_link(int(pcm.shape[2]) if link else 1)
         return self.torch.ops.rnnoise_amd.process_channels(pcm, active, self.state, self.handle)
+
+    def process_chunks(self, pcm, counts):
+        """pcm (N, max_count) float32 or int16 CUDA tensor, counts (N,) int32 CUDA tensor: stream s pushes the first counts[s] samples
+        of its row, any number of them, through the batch's sample FIFOs on the device and gets as many output samples back, one
+        frame late.  -> out (N, max_count), vad (F, N), gains (F, N, 32), frames (N,) int32 (torch.ops.rnnoise_amd.process_chunks)"""
+        return self.torch.ops.rnnoise_amd.process_chunks(pcm, counts, self.state, self.handle)
 
     def reset_streams(self, idx):
         """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
@@ -338,6 +362,24 @@ class RNNoiseOp:
             out = torch.zeros_like(pcm)
             self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream)
         return out, vad, gains
+
+    def _run_chunks(self, pcm, counts):
+        torch = self.torch
+        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2 and pcm.shape[0] == self.n
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == self.n
+        self._layout(0, 0)
+        pcm, counts = pcm.contiguous(), counts.contiguous()
+        F = capi.chunk_frames(self.batch.frame, pcm.shape[1])
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        vad = torch.empty((F, self.n), device=pcm.device, dtype=torch.float32)
+        gains = torch.empty((F, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        frames = torch.zeros((self.n,), device=pcm.device, dtype=torch.int32)
+        out = torch.zeros_like(pcm)
+        if pcm.shape[1] == 0:  # (nothing to push: the library's no-op, and an empty tensor has no address to hand it)
+            return out, vad, gains, frames
+        self.batch.process_chunks_device(out.data_ptr(), pcm.data_ptr(), counts.data_ptr(), pcm.shape[1], vad.data_ptr(), gains.data_ptr(),
+                                         frames.data_ptr(), stream, s16=pcm.dtype == torch.int16)
+        return out, vad, gains, frames
 
     def _run_list(self, pcm, idx, active=None):
         torch = self.torch
