@@ -464,7 +464,8 @@ RNNOISE_EXPORT int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap
  * rnnoise_batch_load_streams[_device] restart the FIFOs of the streams they touch, rnnoise_batch_set_pcm_rate those of every stream.
  * Snapshots do not carry FIFO contents (RNNOISE_AMD_SNAP_FLOATS and the record stay): move a stream at a frame boundary --
  * rnnoise_batch_chunk_fill writes r_s of every stream into fill[n_streams], synchronously; at r_s = 0 only the M output samples
- * still in the FIFO are lost with the move.  The other call forms on the same batch neither read nor change the
+ * still in the FIFO are lost with the move --, or take its FIFO record along (rnnoise_batch_save_chunk_fifos below), which moves
+ * it anywhere in a frame with nothing lost.  The other call forms on the same batch neither read nor change the
  * FIFOs.  0 / -1. */
 RNNOISE_EXPORT int rnnoise_amd_chunk_frames(int frame_samples, int max_count);
 RNNOISE_EXPORT int rnnoise_batch_process_device_chunks(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts,
@@ -477,6 +478,67 @@ RNNOISE_EXPORT int rnnoise_batch_process_chunks(RNNoiseBatch *b, float *out, con
 RNNOISE_EXPORT int rnnoise_batch_process_chunks_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts, int max_count,
                                                     float *vad, float *gains, int *frames);
 RNNOISE_EXPORT int rnnoise_batch_chunk_fill(RNNoiseBatch *b, int *fill);
+
+/* Chunk calls on a stream list: the chunk call for the n_rows streams streams[i] only, at a cost that follows n_rows -- packets of
+ * different legs do not arrive on one clock, and a tick usually carries pushes for a small part of the batch.  Every buffer is
+ * indexed by list position i, not by stream: in / out are [n_rows][max_count] (rows max_count samples apart, aligned as their
+ * element only; in may be out), counts [n_rows], vad [F][n_rows], gains [F][n_rows][32], frames [n_rows] (the three may be NULL),
+ * F = rnnoise_amd_chunk_frames(M, max_count); streams[i] is the batch stream of row i, in any order.
+ * A listed stream gets, bit for bit in output samples, vad, gains, frames, state and FIFOs, what the full-size chunk call gives it
+ * with the same count and a count of 0 for every unlisted stream.  An unlisted stream is not touched: state, both FIFOs and their
+ * fill, resampler history, gate counter and frame phase stay.  The two forms work on the same FIFOs: a stream may be pushed through
+ * either form from one call to the next.
+ * Device forms: three steps on hip_stream, all sized by n_rows -- the listed rows and their pending samples into a compact staging
+ * buffer [F][n_rows][M], the stream-list call (rnnoise_batch_process_device_list) on it with the mask the first step wrote, the
+ * frames' output and the output FIFOs into the listed rows.  The staging buffer is the full-size form's; a call that fits what is
+ * allocated neither frees nor grows it, one that does not synchronises with the device once.  An entry outside [0, n_streams)
+ * makes its row absent: its mask column is zero, frames[i] = 0, its out row is not written and no FIFO is touched.  A negative count
+ * reads as 0, one above max_count as max_count.  Duplicate entries are the caller's error: those streams are unspecified, no other
+ * stream changes and no access leaves its row or record.
+ * Host forms: the list and the counts are checked first; an out-of-range or duplicate entry or a count out of range returns -1 with
+ * nothing changed.
+ * n_rows == 0 or max_count == 0 is a successful no-op.  n_rows < 0, n_rows > n_streams, a NULL list with n_rows > 0, a NULL batch,
+ * in, out or counts, max_count < 0, and every configuration the chunk calls refuse (rate table, format table, PCM layout,
+ * channels > 1, gain link > 1) return -1 with nothing launched.  The first call allocates the FIFOs and switches the batch to
+ * per-stream frame phase, exactly as the first chunk call does.  0 / -1. */
+RNNOISE_EXPORT int rnnoise_batch_process_device_chunks_list(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts,
+                                                            int max_count, const int *d_streams, int n_rows, float *d_vad,
+                                                            float *d_gains, int *d_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_device_chunks_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, const int *d_counts,
+                                                                int max_count, const int *d_streams, int n_rows, float *d_vad,
+                                                                float *d_gains, int *d_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_chunks_list(RNNoiseBatch *b, float *out, const float *in, const int *counts, int max_count,
+                                                     const int *streams, int n_rows, float *vad, float *gains, int *frames);
+RNNOISE_EXPORT int rnnoise_batch_process_chunks_list_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts,
+                                                         int max_count, const int *streams, int n_rows, float *vad, float *gains,
+                                                         int *frames);
+
+/* FIFO records: the two sample FIFOs of a stream that is fed in chunks, to move a leg that is not at a frame boundary -- a leg fed by
+ * 1024-sample AAC blocks almost never is.  A snapshot (rnnoise_batch_save_streams) carries no FIFO contents; a FIFO record carries
+ * nothing else.  rec is [n][RNNOISE_AMD_CHUNK_REC_FLOATS] 32-bit words, by list position: words [0, r) the pending input samples
+ * and zeros up to 480; words [480, 480 + M - r) the output FIFO and zeros up to 960; word 960 r, word 961 M (the frame length the
+ * record belongs to), word 962 RNNOISE_AMD_CHUNK_MAGIC, word 963 zero, as int32.  Samples move as bits (a NaN payload survives),
+ * and saving the same stream twice gives identical bytes.  The list, streams == NULL with n == n_streams, and the NULL / n rules
+ * are those of rnnoise_batch_save_streams; no alignment is asked of rec.
+ * save leaves the batch untouched; on a batch that has made no chunk call it allocates nothing and writes restarted records (r = 0,
+ * M zeros to give out).  load takes a row whose magic word matches, whose word 961 is the batch's current M and whose r is in
+ * [0, M), and writes the stream's two FIFOs and their fill -- nothing else: no state, no history, no counter, no frame phase, no
+ * mode; on a batch without FIFOs it allocates them as the first chunk call does.
+ * Device forms: asynchronous on hip_stream, one launch.  save: an entry outside [0, n_streams) gets magic word 0 and the rest of its
+ * row is not written.  load: a row that is not taken and an entry out of range touch nothing; duplicate entries are the caller's
+ * error.  Host forms: synchronous; a load checks every row first, and one bad row or a duplicate or out-of-range entry returns -1
+ * with nothing changed.
+ * ORDER OF A MOVE.  rnnoise_batch_load_streams[_device] restarts the FIFOs of the streams it touches, so the FIFO records go in
+ * behind the snapshots: (1) save_streams and save_chunk_fifos on the source, (2) load_streams on the destination,
+ * (3) load_chunk_fifos on the destination.  A leg moved that way continues bit for bit as if it had stayed, output samples
+ * included.  0 / -1. */
+#define RNNOISE_AMD_CHUNK_REC_FLOATS 964
+#define RNNOISE_AMD_CHUNK_MAGIC 0x464b4301 /* "\1CKF": record version 1 */
+RNNOISE_EXPORT int rnnoise_batch_save_chunk_fifos_device(RNNoiseBatch *b, float *d_rec, const int *d_streams, int n, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_load_chunk_fifos_device(RNNoiseBatch *b, const float *d_rec, const int *d_streams, int n,
+                                                         void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_save_chunk_fifos(RNNoiseBatch *b, float *rec, const int *streams, int n);
+RNNOISE_EXPORT int rnnoise_batch_load_chunk_fifos(RNNoiseBatch *b, const float *rec, const int *streams, int n);
 
 /* Network implementation: 0 = vector path (v_dot4 / FMA chains), 1 = batched MFMA path -- one kernel per 16-stream tile
  * below 10,240 streams, layer by layer (64 streams per GRU workgroup, five launches) from there up --, 2 = the layer-wise

@@ -32,6 +32,13 @@ SNAP_HIST_FLOATS = 336
 SNAP_FLOATS = SNAP_OFF_HIST + SNAP_HIST_FLOATS  # 6624
 SNAP_MAGIC = 0x534E5201
 SNAP_GATE_NONE = 65536
+# the FIFO record of rnnoise_batch_save_chunk_fifos (include/rnnoise_amd.h): pending samples, output FIFO, then int32 r, M, magic, 0
+CHUNK_FIFO_ROW = 480
+CHUNK_OFF_FILL = 2 * CHUNK_FIFO_ROW
+CHUNK_OFF_M = CHUNK_OFF_FILL + 1
+CHUNK_OFF_MAGIC = CHUNK_OFF_FILL + 2
+CHUNK_REC_FLOATS = CHUNK_OFF_FILL + 4  # 964
+CHUNK_MAGIC = 0x464B4301
 
 _lib = None
 _product = None
@@ -69,6 +76,10 @@ EXPORTS = [
     "rnnoise_batch_train_rir_device",
     "rnnoise_amd_chunk_frames", "rnnoise_batch_process_device_chunks", "rnnoise_batch_process_device_chunks_s16",
     "rnnoise_batch_process_chunks", "rnnoise_batch_process_chunks_s16", "rnnoise_batch_chunk_fill",
+    "rnnoise_batch_process_device_chunks_list", "rnnoise_batch_process_device_chunks_list_s16",
+    "rnnoise_batch_process_chunks_list", "rnnoise_batch_process_chunks_list_s16",
+    "rnnoise_batch_save_chunk_fifos_device", "rnnoise_batch_load_chunk_fifos_device", "rnnoise_batch_save_chunk_fifos",
+    "rnnoise_batch_load_chunk_fifos",
 ]
 
 
@@ -224,6 +235,8 @@ def _load(path, debug):
                 getattr(L, f"rnnoise_batch_{name}{sfx}").argtypes = args
             getattr(L, f"rnnoise_batch_process_chunks{sfx}").argtypes = [vp, pp, pp, ip, C.c_int, fp, fp, ip]
             getattr(L, f"rnnoise_batch_process_device_chunks{sfx}").argtypes = [vp] * 4 + [C.c_int] + [vp] * 4
+            getattr(L, f"rnnoise_batch_process_chunks_list{sfx}").argtypes = [vp, pp, pp, ip, C.c_int, ip, C.c_int, fp, fp, ip]
+            getattr(L, f"rnnoise_batch_process_device_chunks_list{sfx}").argtypes = [vp] * 4 + [C.c_int, vp, C.c_int] + [vp] * 4
         L.rnnoise_amd_chunk_frames.argtypes = [C.c_int, C.c_int]
         L.rnnoise_batch_chunk_fill.argtypes = [vp, ip]
         # the per-stream tables: host setter, device setter (table, stream), getter
@@ -250,6 +263,10 @@ def _load(path, debug):
         L.rnnoise_batch_load_streams_device.argtypes = [vp, vp, vp, C.c_int, vp]
         L.rnnoise_batch_save_streams.argtypes = [vp, fp, ip, C.c_int]
         L.rnnoise_batch_load_streams.argtypes = [vp, fp, ip, C.c_int]
+        L.rnnoise_batch_save_chunk_fifos_device.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.rnnoise_batch_load_chunk_fifos_device.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.rnnoise_batch_save_chunk_fifos.argtypes = [vp, fp, ip, C.c_int]
+        L.rnnoise_batch_load_chunk_fifos.argtypes = [vp, fp, ip, C.c_int]
         L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
         L.rnnoise_batch_set_schedule.argtypes = [vp, C.c_int]
         L.rnnoise_amd_model_pack.restype = C.c_long
@@ -747,6 +764,83 @@ class Batch:
         if fn(self.h, d_out or None, d_in or None, d_counts or None, int(max_count), d_vad or None, d_gains or None, d_frames or None,
               stream or None):
             raise RuntimeError("rnnoise_batch_process_device_chunks failed")
+
+    def _process_chunks_list(self, name, dtype, pcm, counts, streams, want_gains, out):
+        idx = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+        R = int(idx.size)
+        pcm = np.asarray(pcm)
+        if pcm.ndim != 2 or pcm.shape[0] != R:
+            raise ValueError(f"list chunk PCM is (n_rows, max_count); got {pcm.shape} for {R} listed streams")
+        pcm = np.ascontiguousarray(pcm, dtype)
+        max_count = pcm.shape[1]
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.int32)
+        if counts.size != R:
+            raise ValueError("one count per listed stream")
+        if out is None:
+            out = np.zeros_like(pcm)
+        elif out.dtype != dtype or out.shape != pcm.shape or not out.flags.c_contiguous:
+            raise ValueError("out: a C-contiguous array of the PCM's shape and type")
+        F = chunk_frames(self.frame, max_count)
+        vad = np.zeros((F, R), np.float32)
+        gains = np.zeros((F, R, 32), np.float32) if want_gains else None
+        frames = np.zeros(R, np.int32)
+        pp = C.POINTER(C.c_short if dtype == np.int16 else C.c_float)
+        ip = C.POINTER(C.c_int)
+        self._call(f"rnnoise_batch_{name}", out.ctypes.data_as(pp), pcm.ctypes.data_as(pp), counts.ctypes.data_as(ip),
+                   int(max_count), idx.ctypes.data_as(ip), R, _fp(vad), _fp(gains), frames.ctypes.data_as(ip), exc=ValueError,
+                   why=" (a stream out of range or listed twice, a count outside [0, max_count], more rows than streams, or a batch"
+                       " with a rate / format table, a PCM layout, channels or a gain link?)")
+        return out, vad, gains, frames
+
+    def process_chunks_list(self, pcm: np.ndarray, counts, streams, want_gains: bool = True, out: np.ndarray | None = None):
+        """process_chunks for the listed streams only: pcm (R, max_count) float32, row i belongs to stream streams[i] and pushes its
+        first counts[i] samples -> (out, vad[F,R], gains[F,R,32], frames[R]): rnnoise_batch_process_chunks_list.  Unlisted streams
+        are not touched.  ValueError, and nothing changes, on a stream out of range or listed twice or a count out of range."""
+        return self._process_chunks_list("process_chunks_list", np.float32, pcm, counts, streams, want_gains, out)
+
+    def process_chunks_list_s16(self, pcm: np.ndarray, counts, streams, want_gains: bool = True, out: np.ndarray | None = None):
+        """process_chunks_list on int16 PCM (rnnoise_batch_process_chunks_list_s16)"""
+        return self._process_chunks_list("process_chunks_list_s16", np.int16, pcm, counts, streams, want_gains, out)
+
+    def process_chunks_list_device(self, d_out: int, d_in: int, d_counts: int, max_count: int, d_streams: int, n_rows: int,
+                                   d_vad: int = 0, d_gains: int = 0, d_frames: int = 0, stream: int = 0, s16: bool = False):
+        """Raw device pointers (ints), asynchronous on `stream`: d_in / d_out [R][max_count] float32 (int16 with s16), d_counts [R]
+        int32 (clamped into [0, max_count]), d_streams [R] int32 (an entry out of range: an absent row), d_vad [F][R],
+        d_gains [F][R][32], d_frames [R] int32 or 0."""
+        fn = self._L.rnnoise_batch_process_device_chunks_list_s16 if s16 else self._L.rnnoise_batch_process_device_chunks_list
+        if fn(self.h, d_out or None, d_in or None, d_counts or None, int(max_count), d_streams or None, int(n_rows), d_vad or None,
+              d_gains or None, d_frames or None, stream or None):
+            raise RuntimeError("rnnoise_batch_process_device_chunks_list failed")
+
+    def save_chunk_fifos(self, streams=None) -> np.ndarray:
+        """the FIFO records of the listed streams (None: the whole batch), (n, CHUNK_REC_FLOATS) float32: pending samples, output FIFO,
+        then r, M and the magic word (view as int32) -- rnnoise_batch_save_chunk_fifos.  Synchronous; the batch is unchanged."""
+        idx, n = self._snap_list(streams)
+        rec = np.empty((n, CHUNK_REC_FLOATS), np.float32)
+        if self._L.rnnoise_batch_save_chunk_fifos(self.h, _fp(rec), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
+            raise ValueError("rnnoise_batch_save_chunk_fifos failed (a stream out of range, or too many rows?)")
+        return rec
+
+    def load_chunk_fifos(self, rec: np.ndarray, streams=None):
+        """row i of rec (n, CHUNK_REC_FLOATS) becomes the FIFOs of stream streams[i]: rnnoise_batch_load_chunk_fifos -- AFTER
+        load_streams, which restarts them.  Synchronous.  ValueError, and nothing changes, on an out-of-range or repeated stream or
+        a record with another magic word, another frame length or a fill outside [0, M)."""
+        idx, n = self._snap_list(streams)
+        rec = np.ascontiguousarray(rec, np.float32)
+        assert rec.shape == (n, CHUNK_REC_FLOATS), rec.shape
+        if self._L.rnnoise_batch_load_chunk_fifos(self.h, _fp(rec), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
+            raise ValueError("rnnoise_batch_load_chunk_fifos failed (a stream out of range or listed twice, or a bad record?)")
+
+    def save_chunk_fifos_device(self, d_rec: int, d_streams: int, n: int, stream: int = 0):
+        """Raw device pointers (ints), asynchronous on `stream`: d_rec [n][CHUNK_REC_FLOATS] float32, d_streams [n] int32 or 0 with
+        n == N.  A row whose entry is out of range gets magic word 0."""
+        if self._L.rnnoise_batch_save_chunk_fifos_device(self.h, d_rec or None, d_streams or None, n, stream or None):
+            raise RuntimeError("rnnoise_batch_save_chunk_fifos_device failed")
+
+    def load_chunk_fifos_device(self, d_rec: int, d_streams: int, n: int, stream: int = 0):
+        """the inverse, asynchronous on `stream`: rows that are not records of this frame length and out-of-range entries touch nothing"""
+        if self._L.rnnoise_batch_load_chunk_fifos_device(self.h, d_rec or None, d_streams or None, n, stream or None):
+            raise RuntimeError("rnnoise_batch_load_chunk_fifos_device failed")
 
     def chunk_fill(self) -> np.ndarray:
         """the pending input samples r_s of every stream, (N,) int32 (rnnoise_batch_chunk_fill; synchronous)"""

@@ -592,41 +592,51 @@ int batch_chunk_restart_all(RNNoiseBatch *b) {
   return 0;
 }
 
+// the FIFOs, where the batch has none yet: every stream's as after create, written on st ahead of what follows there
+int batch_chunk_fifos_ready(RNNoiseBatch *b, hipStream_t st) {
+  if (b->chunk_fifo) return 0;
+  const size_t bytes = (size_t)b->n * RN_CHUNK_REC * sizeof(float);
+  HIP_OK(hipMalloc((void **)&b->chunk_fifo, bytes));
+  HIP_OK(hipMemsetAsync(b->chunk_fifo, 0, bytes, st));
+  return 0;
+}
+
 namespace {
 // what a chunk call does not combine with (include/rnnoise_amd.h): per-stream rates and formats, a PCM layout, channels, linked gains
 bool chunk_refused(const RNNoiseBatch *b) { return b->g.rs_Ls || b->g.pcm_fmt || b->row_stride || b->channels > 1 || b->link > 1; }
-// The FIFOs, on the first chunk call (their first state written on st, ahead of the call), and a staging buffer of at least F frames:
-// frames of RN_FRAME_SIZE floats whatever the rate, so that a rate change keeps it.  Growing it drains the device first -- the old
-// buffer may be in use by a call in flight on another stream.
-int chunk_ready(RNNoiseBatch *b, int F, hipStream_t st) {
-  const size_t N = b->n;
-  if (!b->chunk_fifo) {
-    HIP_OK(hipMalloc((void **)&b->chunk_fifo, N * RN_CHUNK_REC * sizeof(float)));
-    HIP_OK(hipMemsetAsync(b->chunk_fifo, 0, N * RN_CHUNK_REC * sizeof(float), st));
-  }
-  if (F > b->chunk_stage_frames) {
+// The FIFOs, on the first chunk call (their first state written on st, ahead of the call), and a staging buffer for F frames of
+// `rows` rows with their mask behind them: frames of RN_FRAME_SIZE floats whatever the rate, so that a rate change keeps it.  It is
+// sized in bytes and shared by the full-size and the list form: a call that fits leaves it alone.  Growing it drains the device first
+// -- the old buffer may be in use by a call in flight on another stream.
+int chunk_ready(RNNoiseBatch *b, int F, size_t rows, hipStream_t st) {
+  if (batch_chunk_fifos_ready(b, st)) return -1;
+  const size_t need = (size_t)F * rows * (RN_FRAME_SIZE * sizeof(float) + 1);
+  if (need > b->chunk_stage_bytes) {
     if (b->chunk_stage) {
       HIP_OK(hipDeviceSynchronize());
       HIP_OK(hipFree(b->chunk_stage));
       b->chunk_stage = nullptr;
-      b->chunk_stage_frames = 0;
+      b->chunk_stage_bytes = 0;
     }
-    HIP_OK(hipMalloc(&b->chunk_stage, (size_t)F * N * (RN_FRAME_SIZE * sizeof(float) + 1)));
-    b->chunk_stage_frames = F;
+    HIP_OK(hipMalloc(&b->chunk_stage, need));
+    b->chunk_stage_bytes = need;
   }
   return 0;
 }
 
-int chunks_device(RNNoiseBatch *b, void *d_out, const void *d_in, const int *d_counts, int max_count, float *d_vad, float *d_gains,
-                  int *d_frames, void *hip_stream, bool s16) {
+// d_streams: the list form -- every buffer has n_rows rows and row i belongs to stream d_streams[i]; null: the full-size form
+int chunks_device(RNNoiseBatch *b, void *d_out, const void *d_in, const int *d_counts, int max_count, const int *d_streams, int n_rows,
+                  float *d_vad, float *d_gains, int *d_frames, void *hip_stream, bool s16) {
   if (!b || !d_out || !d_in || !d_counts || max_count < 0 || chunk_refused(b)) return -1;
-  if (max_count == 0) return 0;
-  const int M = batch_frame_samples(b), F = rn_chunk_frames(M, max_count);
+  const bool listed = d_streams || n_rows;
+  if (listed && (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !d_streams))) return -1;
+  if (max_count == 0 || (listed && n_rows == 0)) return 0;
+  const int M = batch_frame_samples(b), F = rn_chunk_frames(M, max_count), rows = listed ? n_rows : b->n;
   const hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
-  if (chunk_ready(b, F, st)) return -1;
+  if (chunk_ready(b, F, rows, st)) return -1;
   RnChunkDev ck = batch_chunk_fifos(b, 0);
-  ck.N = b->n;
+  ck.N = rows;
   ck.max_count = max_count;
   ck.F = F;
   ck.s16 = s16;
@@ -634,36 +644,53 @@ int chunks_device(RNNoiseBatch *b, void *d_out, const void *d_in, const int *d_c
   ck.in = d_in;
   ck.out = d_out;
   ck.stage = static_cast<float *>(b->chunk_stage);
-  ck.active = reinterpret_cast<unsigned char *>(ck.stage + (size_t)b->chunk_stage_frames * b->n * RN_FRAME_SIZE);
+  // (the mask behind the frames THIS call can have, at the longest frame: inside the allocation whatever it was sized for)
+  ck.active = reinterpret_cast<unsigned char *>(ck.stage + (size_t)F * rows * RN_FRAME_SIZE);
   ck.frames = d_frames;
-  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_CHUNK, nullptr, nullptr, b->n, 0, nullptr, &ck, st));
-  // (the masked call reads frame f's rows in K0 and writes them in K3 of the same frame: in place)
+  ck.list = d_streams;
+  ck.S = b->n;
+  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_CHUNK, nullptr, nullptr, rows, 0, nullptr, &ck, st));
+  // (the masked call reads frame f's rows in K0 and writes them in K3 of the same frame: in place.  The list form: the list call on
+  //  the compact buffer -- every launch sized by n_rows)
   if (batch_process_device_impl(b, {.out = ck.stage, .in = ck.stage, .vad = d_vad, .gains = d_gains, .n_frames = F, .stream = hip_stream,
-                                    .active = ck.active, .packed = true}))
+                                    .active = ck.active, .list = d_streams, .n_rows = listed ? n_rows : 0, .packed = true}))
     return -1;
-  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_CHUNK, nullptr, nullptr, b->n, 0, nullptr, &ck, st));
+  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_CHUNK, nullptr, nullptr, rows, 0, nullptr, &ck, st));
   return 0;
 }
 
-// the convenience form on host buffers: the counts are checked before anything moves; whole rows go up, and only the first counts[s]
-// samples of a row come back into the caller's `out`
-int chunks_host(RNNoiseBatch *b, void *out, const void *in, const int *counts, int max_count, float *vad, float *gains, int *frames,
-                bool s16) {
+// the convenience form on host buffers: the counts (and the list: an entry outside the batch or listed twice) are checked before
+// anything moves; whole rows go up, and only the first counts[i] samples of a row come back into the caller's `out`
+int chunks_host(RNNoiseBatch *b, void *out, const void *in, const int *counts, int max_count, const int *streams, int n_rows, float *vad,
+                float *gains, int *frames, bool s16) {
   if (!b || !out || !in || !counts || max_count < 0 || chunk_refused(b)) return -1;
-  for (int s = 0; s < b->n; s++)
-    if (counts[s] < 0 || counts[s] > max_count) return -1;
-  if (max_count == 0) return 0;
-  const size_t N = b->n, esz = s16 ? sizeof(short) : sizeof(float), row = (size_t)max_count * esz;
+  const bool listed = streams || n_rows;
+  if (listed && (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !streams))) return -1;
+  const size_t N = listed ? n_rows : b->n;
+  if (listed) {
+    std::vector<uint8_t> seen((size_t)b->n, 0);
+    for (size_t i = 0; i < N; i++) {
+      const int s = streams[i];
+      if (s < 0 || s >= b->n || seen[s]) return -1;
+      seen[s] = 1;
+    }
+  }
+  for (size_t i = 0; i < N; i++)
+    if (counts[i] < 0 || counts[i] > max_count) return -1;
+  if (max_count == 0 || N == 0) return 0;
+  const size_t esz = s16 ? sizeof(short) : sizeof(float), row = (size_t)max_count * esz;
   const size_t fs = (size_t)rn_chunk_frames(batch_frame_samples(b), max_count) * N;
   ON_DEVICE(b->device);
   DevScratch d;
   const size_t o_in = d.carve(N * row), o_out = d.carve(N * row), o_counts = d.carve(N * sizeof(int)), o_vad = d.carve(fs * 4),
-               o_gains = d.carve(fs * RN_NB_BANDS * 4), o_frames = d.carve(N * sizeof(int));
+               o_gains = d.carve(fs * RN_NB_BANDS * 4), o_frames = d.carve(N * sizeof(int)), o_list = d.carve(listed ? N * sizeof(int) : 0);
   if (d.alloc()) return -1;
   HIP_OK(hipMemcpy(d.at<char>(o_in), in, N * row, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(d.at<char>(o_counts), counts, N * sizeof(int), hipMemcpyHostToDevice));
-  if (chunks_device(b, d.at<char>(o_out), d.at<char>(o_in), d.at<int>(o_counts), max_count, vad ? d.at<float>(o_vad) : nullptr,
-                    gains ? d.at<float>(o_gains) : nullptr, frames ? d.at<int>(o_frames) : nullptr, nullptr, s16))
+  if (listed) HIP_OK(hipMemcpy(d.at<char>(o_list), streams, N * sizeof(int), hipMemcpyHostToDevice));
+  if (chunks_device(b, d.at<char>(o_out), d.at<char>(o_in), d.at<int>(o_counts), max_count, listed ? d.at<int>(o_list) : nullptr,
+                    listed ? n_rows : 0, vad ? d.at<float>(o_vad) : nullptr, gains ? d.at<float>(o_gains) : nullptr,
+                    frames ? d.at<int>(o_frames) : nullptr, nullptr, s16))
     return -1;
   HIP_OK(hipDeviceSynchronize());
   std::vector<char> rows(N * row);
@@ -678,19 +705,42 @@ int chunks_host(RNNoiseBatch *b, void *out, const void *in, const int *counts, i
 
 extern "C" int rnnoise_batch_process_device_chunks(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts, int max_count,
                                                    float *d_vad, float *d_gains, int *d_frames, void *hip_stream) {
-  return chunks_device(b, d_out, d_in, d_counts, max_count, d_vad, d_gains, d_frames, hip_stream, false);
+  return chunks_device(b, d_out, d_in, d_counts, max_count, nullptr, 0, d_vad, d_gains, d_frames, hip_stream, false);
 }
 extern "C" int rnnoise_batch_process_device_chunks_s16(RNNoiseBatch *b, short *d_out, const short *d_in, const int *d_counts,
                                                        int max_count, float *d_vad, float *d_gains, int *d_frames, void *hip_stream) {
-  return chunks_device(b, d_out, d_in, d_counts, max_count, d_vad, d_gains, d_frames, hip_stream, true);
+  return chunks_device(b, d_out, d_in, d_counts, max_count, nullptr, 0, d_vad, d_gains, d_frames, hip_stream, true);
 }
 extern "C" int rnnoise_batch_process_chunks(RNNoiseBatch *b, float *out, const float *in, const int *counts, int max_count, float *vad,
                                             float *gains, int *frames) {
-  return chunks_host(b, out, in, counts, max_count, vad, gains, frames, false);
+  return chunks_host(b, out, in, counts, max_count, nullptr, 0, vad, gains, frames, false);
 }
 extern "C" int rnnoise_batch_process_chunks_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts, int max_count,
                                                 float *vad, float *gains, int *frames) {
-  return chunks_host(b, out, in, counts, max_count, vad, gains, frames, true);
+  return chunks_host(b, out, in, counts, max_count, nullptr, 0, vad, gains, frames, true);
+}
+// the same on a stream list (include/rnnoise_amd.h): an empty list is a no-op even without a list pointer
+extern "C" int rnnoise_batch_process_device_chunks_list(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts,
+                                                        int max_count, const int *d_streams, int n_rows, float *d_vad, float *d_gains,
+                                                        int *d_frames, void *hip_stream) {
+  if (!d_streams && n_rows == 0) return b && d_out && d_in && d_counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
+  return chunks_device(b, d_out, d_in, d_counts, max_count, d_streams, n_rows, d_vad, d_gains, d_frames, hip_stream, false);
+}
+extern "C" int rnnoise_batch_process_device_chunks_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, const int *d_counts,
+                                                            int max_count, const int *d_streams, int n_rows, float *d_vad,
+                                                            float *d_gains, int *d_frames, void *hip_stream) {
+  if (!d_streams && n_rows == 0) return b && d_out && d_in && d_counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
+  return chunks_device(b, d_out, d_in, d_counts, max_count, d_streams, n_rows, d_vad, d_gains, d_frames, hip_stream, true);
+}
+extern "C" int rnnoise_batch_process_chunks_list(RNNoiseBatch *b, float *out, const float *in, const int *counts, int max_count,
+                                                 const int *streams, int n_rows, float *vad, float *gains, int *frames) {
+  if (!streams && n_rows == 0) return b && out && in && counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
+  return chunks_host(b, out, in, counts, max_count, streams, n_rows, vad, gains, frames, false);
+}
+extern "C" int rnnoise_batch_process_chunks_list_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts, int max_count,
+                                                     const int *streams, int n_rows, float *vad, float *gains, int *frames) {
+  if (!streams && n_rows == 0) return b && out && in && counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
+  return chunks_host(b, out, in, counts, max_count, streams, n_rows, vad, gains, frames, true);
 }
 extern "C" int rnnoise_batch_chunk_fill(RNNoiseBatch *b, int *fill) {
   if (!b || !fill) return -1;

@@ -185,3 +185,86 @@ extern "C" int rnnoise_batch_save_streams(RNNoiseBatch *b, float *snap, const in
 extern "C" int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap, const int *streams, int n) {
   return snap_host(b, const_cast<float *>(snap), streams, n, true);
 }
+
+// ---- FIFO records of the chunk calls (include/rnnoise_amd.h: rnnoise_batch_save_chunk_fifos) ----
+// What a snapshot leaves behind of a stream that is fed in chunks: its two sample FIFOs and their fill.  One launch of the state
+// kernels' chunk form per call (chunk_fifo.h: rn_chunk_rec_save / rn_chunk_rec_load), n workgroups, list and argument rules as the
+// snapshots above.  A save reads whatever the batch has -- restarted FIFOs where it has none --, a load allocates them first.
+static_assert(RNNOISE_AMD_CHUNK_REC_FLOATS == RN_CHUNK_REC && RNNOISE_AMD_CHUNK_MAGIC == RN_CHUNK_MAGIC && RN_CHUNK_MAGIC != RN_SNAP_MAGIC,
+              "one FIFO record for the kernels and the API");
+namespace {
+int fifo_rec_on(RNNoiseBatch *b, float *d_rec, const int *d_list, int n, bool load, hipStream_t st) {
+  if (load && batch_chunk_fifos_ready(b, st)) return -1;
+  RnChunkDev ck = batch_chunk_fifos(b, 0);
+  ck.M = batch_frame_samples(b);
+  ck.N = n;
+  ck.list = d_list;
+  ck.S = b->n;
+  ck.op = load ? RN_CHUNK_OP_LOAD : RN_CHUNK_OP_SAVE;
+  ck.rec = d_rec;
+  if (load) HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_CHUNK, nullptr, nullptr, n, 0, nullptr, &ck, st));
+  else HIP_OK(rn_launch_state_gather(&b->g, RN_REC_CHUNK, nullptr, nullptr, n, 0, nullptr, &ck, st));
+  return 0;
+}
+constexpr int FIFO_REC_CHUNK = 8192;  // rows of the host forms' staging buffer (32 MB)
+
+int fifo_rec_host(RNNoiseBatch *b, float *rec, const int *streams, int n, bool load) {
+  if (!snap_args_ok(b, rec, streams, n)) return -1;
+  if (n == 0) return 0;
+  const int M = batch_frame_samples(b);
+  std::vector<int> list((size_t)n);
+  std::vector<uint8_t> seen(load ? (size_t)b->n : 0, 0);
+  for (int i = 0; i < n; i++) {
+    const int s = streams ? streams[i] : i;
+    if (s < 0 || s >= b->n) return -1;
+    if (load) {
+      if (seen[s]) return -1;
+      seen[s] = 1;
+      int hdr[3];  // fill, M, magic
+      memcpy(hdr, rec + (size_t)i * RN_CHUNK_REC + RN_CHUNK_OFF_FILL, sizeof hdr);
+      if (!rn_chunk_rec_ok(hdr[2], hdr[1], hdr[0], M)) return -1;
+    }
+    list[i] = s;
+  }
+  ON_DEVICE(b->device);
+  HIP_OK(hipDeviceSynchronize());
+  const size_t chunk = n < FIFO_REC_CHUNK ? n : FIFO_REC_CHUNK, row_bytes = RN_CHUNK_REC * sizeof(float);
+  DevScratch d;
+  const size_t o_rec = d.carve(chunk * row_bytes), o_list = d.carve(chunk * sizeof(int));
+  if (d.alloc()) return -1;
+  float *d_rec = d.at<float>(o_rec);
+  int *d_list = d.at<int>(o_list);
+  for (size_t r0 = 0; r0 < (size_t)n; r0 += chunk) {
+    const int rows = (int)std::min(chunk, (size_t)n - r0);
+    float *h = rec + r0 * RN_CHUNK_REC;
+    HIP_OK(hipMemcpy(d_list, list.data() + r0, rows * sizeof(int), hipMemcpyHostToDevice));
+    if (load) HIP_OK(hipMemcpy(d_rec, h, rows * row_bytes, hipMemcpyHostToDevice));
+    if (fifo_rec_on(b, d_rec, d_list, rows, load, nullptr)) return -1;
+    HIP_OK(hipStreamSynchronize(nullptr));
+    if (!load) HIP_OK(hipMemcpy(h, d_rec, rows * row_bytes, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int rnnoise_batch_save_chunk_fifos_device(RNNoiseBatch *b, float *d_rec, const int *d_streams, int n, void *hip_stream) {
+  if (!snap_args_ok(b, d_rec, d_streams, n)) return -1;
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  return fifo_rec_on(b, d_rec, d_streams, n, false, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int rnnoise_batch_load_chunk_fifos_device(RNNoiseBatch *b, const float *d_rec, const int *d_streams, int n, void *hip_stream) {
+  if (!snap_args_ok(b, d_rec, d_streams, n)) return -1;
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  return fifo_rec_on(b, const_cast<float *>(d_rec), d_streams, n, true, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int rnnoise_batch_save_chunk_fifos(RNNoiseBatch *b, float *rec, const int *streams, int n) {
+  return fifo_rec_host(b, rec, streams, n, false);
+}
+
+extern "C" int rnnoise_batch_load_chunk_fifos(RNNoiseBatch *b, const float *rec, const int *streams, int n) {
+  return fifo_rec_host(b, const_cast<float *>(rec), streams, n, true);
+}

@@ -69,4 +69,26 @@ struct RnChunkDev {
   float *stage;               // [F][N][M] the frames of the masked call in between, in and out
   unsigned char *active;      // [F][N] its mask (scatter writes it)
   int *frames;                // [N] k of every stream, or null (scatter writes it)
+  // a chunk call on a stream list (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks_list): N is the list's length, every
+  // buffer above is indexed by list position (row), and row i's FIFO record is that of stream list[i] -- `fifo` then covers the
+  // whole batch.  Null: row i is stream i, the full-size call
+  const int *list;            // [N] the batch stream of every row
+  int S;                      // streams of the batch: an entry outside [0, S) makes its row absent
+  // FIFO records (rnnoise_batch_save_chunk_fifos_device / load): no call, N rows of `rec` <-> the FIFOs of streams list[i] (stream i
+  // without a list)
+  int op;                     // RN_CHUNK_OP_*
+  float *rec;                 // [N][RN_CHUNK_REC] (load only reads it)
 };
+enum { RN_CHUNK_OP_CALL = 0, RN_CHUNK_OP_SAVE, RN_CHUNK_OP_LOAD };
+// The saved record, RN_CHUNK_REC words like the one on the device: [0, r) the pending samples and zeros up to 480, [480, 480 + M - r)
+// the output FIFO and zeros up to 960, then r, the frame length M the record belongs to, the magic word and a zero, as int32.
+// (A FIFO record on the device is not one: samples behind the fills stay as they were, and the padding is never written.)
+#define RN_CHUNK_OFF_FILL (2 * RN_CHUNK_FIFO_ROW)
+#define RN_CHUNK_OFF_M (RN_CHUNK_OFF_FILL + 1)
+#define RN_CHUNK_OFF_MAGIC (RN_CHUNK_OFF_FILL + 2)
+#define RN_CHUNK_MAGIC 0x464b4301  // "\1CKF"
+// whether load takes a record with this header on a batch whose frame is M
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline bool rn_chunk_rec_ok(int magic, int rec_M, int r, int M) { return magic == RN_CHUNK_MAGIC && rec_M == M && r >= 0 && r < M; }

@@ -69,7 +69,8 @@ extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 // (state_kernels.hip: `rows` records of `kind`, record i <-> stream list[i] of the view, at frame phase p or at the per-stream
 //  phases `phase`; and the zero state for the listed streams of the view, or for all of them.  ck: the sample FIFOs of the view's
 //  streams (chunk_plan.h; batch_chunk_fifos below), which every scatter restarts -- null where the group has none -- and, with
-//  RN_REC_CHUNK, the chunk call the launch is a staging step of)
+//  RN_REC_CHUNK, the chunk call the launch is a staging step of -- full-size or on a stream list -- or the FIFO records it saves /
+//  loads: `rows` is then ck->N, the rows of the call or of the records)
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, RnRecKind kind, float *rec, const int *list, int rows, int p,
                                              const int *phase, const RnChunkDev *ck, hipStream_t);
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, RnRecKind kind, const float *rec, const int *list, int rows, int p,
@@ -256,11 +257,12 @@ struct RNNoiseBatch {
   float *debug_buf = nullptr;
   float *state_stage = nullptr;  // one flat state in HBM: export / import go through the gather / scatter kernels
   // chunk calls (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks; batch.cpp).  chunk_fifo: the streams' sample FIFOs, from
-  // the first chunk call to the batch's end -- [N] records of RN_CHUNK_REC floats (chunk_plan.h; batch_chunk_fifos).  chunk_stage: the frames and the mask of the masked call inside a chunk call, [F][N][M] floats then [F][N]
-  // bytes for chunk_stage_frames = F frames; it grows when a call needs more
+  // the first chunk call to the batch's end -- [N] records of RN_CHUNK_REC floats (chunk_plan.h; batch_chunk_fifos).  chunk_stage: the frames and the mask of the masked call inside a chunk call, [F][rows][M] floats then, F x rows
+  // frames of RN_FRAME_SIZE floats in, [F][rows] bytes -- rows = N, or a list call's n_rows; chunk_stage_bytes of it, which grow when
+  // a call needs more
   float *chunk_fifo = nullptr;
   void *chunk_stage = nullptr;
-  int chunk_stage_frames = 0;
+  size_t chunk_stage_bytes = 0;
   // host-fed path (rnnoise_batch_process, host_io.cpp).  `run` carries the kernels and `down` the downloads of both kinds of caller
   struct HostIo {
     hipStream_t up = nullptr, run = nullptr, down = nullptr;
@@ -402,6 +404,7 @@ struct ProcessCall {
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
 int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
 int batch_chunk_restart_all(RNNoiseBatch *b);                          // batch.cpp: every stream's sample FIFOs as after create
+int batch_chunk_fifos_ready(RNNoiseBatch *b, hipStream_t st);          // batch.cpp: ... allocated where the batch has none yet
 // samples per row and frame at the batch's PCM rate
 inline int batch_frame_samples(const RNNoiseBatch *b) { return b->g.rs_L ? b->g.rs_pitch : RN_FRAME_SIZE; }
 // the sample FIFOs of streams first, first + 1, ... of a batch as the state kernels take them (chunk_plan.h: RnChunkDev, the call's

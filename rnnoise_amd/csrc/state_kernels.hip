@@ -37,6 +37,7 @@ static_assert(RN_OFF_LAST_PERIOD == RN_OFF_LAST_GAIN + 1 && RN_OFF_MEM_HP == RN_
 static_assert(!(RN_SNAP_THREADS & (RN_SNAP_THREADS - 1)) && !(RN_STATE_THREADS & (RN_STATE_THREADS - 1)), "move_run rotates lanes by a mask");
 static_assert(RN_CHUNK_FIFO_ROW == RN_FRAME_SIZE, "a FIFO row holds the longest frame");
 static_assert(RN_RING_SLOTS % RN_SPEC_SLOTS == 0, "one frame phase, mod RN_RING_SLOTS, gives the ring slot and the spectra slot");
+enum { RN_CHUNK_PITCH_MORE = 0 };  // `pitch` of a chunk launch that is not the full-size call's
 namespace {
 // n floats, src -> dst, by the workgroup (both pointers uniform), lane `lane0` (mod the workgroup, a power of two) taking the first
 // access: a record's runs start on the lane their record offset names, so that they spread over the waves and a wave that has
@@ -181,7 +182,12 @@ __device__ __forceinline__ void restart_extras(const RnGroupDev &g, size_t s, co
 // one workgroup per record, portable states `pitch` floats apart.  An entry outside the view moves nothing.
 // rows < 0: a chunk launch (RN_REC_CHUNK; ck carries the call), workgroup b = stream b of the group and nothing of the above; the two
 // halves of its body (chunk_fifo.h) on either side of the workgroup's barrier.  (The sign of `rows`, not a field of ck: a state
-// launch decides from the arguments it read before there was a ck, and never waits for ck's end of the argument block.)
+// launch decides from the arguments it read before there was a ck, and never waits for ck's end of the argument block.)  Further
+// cases of the chunk launch, told apart by ck's last fields: with ck.list, workgroup b = row b of a list call's buffers and stream
+// ck.list[b]; with ck.op, no call at all -- row b of ck.rec <-> that stream's FIFOs (gather saves, scatter loads).  `pitch`,
+// which a chunk launch has no other use for, says whether there is any such field to look at (RN_CHUNK_PITCH_MORE): the full-size
+// call's launch reads what it read before there were any.  (Told by a second value of `rows` instead, the scatter kernel reserved
+// 20 bytes of scratch; told by the fields alone, the full-size call with few streams pushing lost 0.3 to 0.5 %: DESIGN 4.26.)
 
 // rec[row] <- stream.  A snapshot's tail: the header (magic, L, the gate counter or RN_CTL_NONE, three zeros) and the resampler
 // history or zeros; an entry outside the view leaves an empty record (magic 0).
@@ -190,8 +196,17 @@ rn_state_gather_kernel(RnGroupDev g, float *__restrict__ rec, int p, const int *
                        int pitch, RnChunkDev ck) {
   if (rows < 0) {  // out[s] <- the stream's output FIFO ++ its staged frames; what is left is the FIFO
     extern __shared__ float kept[];  // (RN_CHUNK_FIFO_ROW floats, on chunk launches only: a state launch keeps its LDS-free dispatch)
+    if (blockIdx.x >= (unsigned)ck.N) return;
+    if (pitch == RN_CHUNK_PITCH_MORE) {  // (the full-size launch never waits for ck's last fields either)
+      if (ck.op == RN_CHUNK_OP_SAVE) return rn_chunk_rec_save(ck, blockIdx.x, threadIdx.x, blockDim.x);  // rec[row] <- the stream's FIFOs
+      // the same on a stream list: workgroup b = row b of the call, stream list[b]
+      const int row = blockIdx.x, ls = rn_chunk_row_stream(ck, row);
+      const RnChunkHead lh = rn_chunk_list_gather_head(ck, row, ls);
+      rn_chunk_list_gather_pop(ck, row, ls, lh, kept, threadIdx.x, blockDim.x);
+      __syncthreads();
+      return rn_chunk_list_gather_keep(ck, row, ls, lh, kept, threadIdx.x, blockDim.x);
+    }
     const size_t s = blockIdx.x;
-    if (s >= (size_t)ck.N) return;
     const RnChunkHead h = rn_chunk_gather_head(ck, s);
     rn_chunk_gather_pop(ck, s, h, kept, threadIdx.x, blockDim.x);
     __syncthreads();
@@ -227,8 +242,16 @@ extern "C" __global__ void __launch_bounds__(1024)
 rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, const int *__restrict__ list, const int *__restrict__ phase,
                         int rows, int pitch, RnChunkDev ck) {
   if (rows < 0) {  // the stream's pending samples ++ in[s] -> its frames of the call and their mask; the tail is left pending
+    if (blockIdx.x >= (unsigned)ck.N) return;
+    if (pitch == RN_CHUNK_PITCH_MORE) {
+      if (ck.op == RN_CHUNK_OP_LOAD) return rn_chunk_rec_load(ck, blockIdx.x, threadIdx.x, blockDim.x);  // the stream's FIFOs <- rec[row]
+      const int row = blockIdx.x, ls = rn_chunk_row_stream(ck, row);
+      const RnChunkHead lh = rn_chunk_list_scatter_head(ck, row, ls);
+      rn_chunk_list_scatter_frames(ck, row, ls, lh, threadIdx.x, blockDim.x);
+      __syncthreads();
+      return rn_chunk_list_scatter_tail(ck, row, ls, lh, threadIdx.x, blockDim.x);
+    }
     const size_t s = blockIdx.x;
-    if (s >= (size_t)ck.N) return;
     const RnChunkHead h = rn_chunk_scatter_head(ck, s);
     rn_chunk_scatter_frames(ck, s, h, threadIdx.x, blockDim.x);
     __syncthreads();
@@ -265,7 +288,8 @@ rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, cons
 // p: the frame phase of a lock-step batch (the ring slot its next frame writes); phase: the per-stream phases on the device, indexed
 // as the view's rows, which then take p's place.  Scattered records are 16-byte aligned (both pitches are multiples of 4 floats).
 // ck: the FIFOs of the view's streams, which a scatter restarts (null: the group has none), and with kind RN_REC_CHUNK the chunk
-// call -- `rows` streams, one workgroup of RN_SNAP_THREADS lanes each, no record and no list.
+// call -- `rows` streams, one workgroup of RN_SNAP_THREADS lanes each, no record and no list among the arguments: a list call's
+// list and a FIFO record launch's records travel in ck, with as many workgroups as they have rows.
 namespace {
 template <typename Kernel, typename Rec>
 hipError_t launch_state(Kernel kernel, const RnGroupDev *g, RnRecKind kind, Rec rec, const int *list, int rows, int p, const int *phase,
@@ -274,9 +298,11 @@ hipError_t launch_state(Kernel kernel, const RnGroupDev *g, RnRecKind kind, Rec 
   const bool snap = kind == RN_REC_SNAP;
   RnChunkDev c = ck ? *ck : RnChunkDev{};
   if (kind == RN_REC_CHUNK) {
-    if (!ck || !ck->counts || rows != ck->N || rec) return hipErrorInvalidValue;
+    if (!ck || rows != ck->N || rec) return hipErrorInvalidValue;
+    if (ck->op == RN_CHUNK_OP_CALL ? !ck->counts || (ck->list && ck->S != g->n_streams) : !ck->rec || ck->S != g->n_streams)
+      return hipErrorInvalidValue;
     hipLaunchKernelGGL(kernel, dim3(rows), dim3(RN_SNAP_THREADS), RN_CHUNK_FIFO_ROW * sizeof(float), st, *g, rec, 0, nullptr, nullptr, -1,
-                       RN_STATE_PITCH, c);
+                       ck->op || ck->list ? RN_CHUNK_PITCH_MORE : RN_STATE_PITCH, c);
     return hipGetLastError();
   }
   // (RN_STATE_THREADS where one record's latency is the call's: a single state moved between two copies; RN_SNAP_THREADS where

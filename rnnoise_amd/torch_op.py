@@ -125,6 +125,22 @@ def register_torch_op():
         return (torch.empty_like(pcm), pcm.new_empty((F, N), dtype=torch.float32),
                 pcm.new_empty((F, N, capi.NB_BANDS), dtype=torch.float32), pcm.new_empty((N,), dtype=torch.int32))
 
+    # ... and on a stream list (rnnoise_batch_process_device_chunks_list): pcm (R, max_count), counts (R,) int32 and idx (R,) int32 CUDA
+    # tensors, row i belonging to stream idx[i]; every result has R rows in idx's order.  The frame counter advances by F.
+    @torch.library.custom_op("rnnoise_amd::process_chunks_list", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor counts, Tensor idx, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor, Tensor)")
+    def process_chunks_list(pcm, counts, idx, state, handle):
+        op = _OPS[handle]
+        res = op._run_chunks_list(pcm, counts, idx)
+        state.add_(capi.chunk_frames(op.batch.frame, pcm.shape[1]))
+        return res
+
+    @process_chunks_list.register_fake
+    def _(pcm, counts, idx, state, handle):
+        R, F = pcm.shape[0], capi.chunk_frames(_OPS[handle].batch.frame, pcm.shape[1])
+        return (torch.empty_like(pcm), pcm.new_empty((F, R), dtype=torch.float32),
+                pcm.new_empty((F, R, capi.NB_BANDS), dtype=torch.float32), pcm.new_empty((R,), dtype=torch.int32))
+
     _registered = True
 
 
@@ -210,6 +226,12 @@ class RNNoiseOp:
         frame late.  -> out (N, max_count), vad (F, N), gains (F, N, 32), frames (N,) int32 (torch.ops.rnnoise_amd.process_chunks)"""
         return self.torch.ops.rnnoise_amd.process_chunks(pcm, counts, self.state, self.handle)
 
+    def process_chunks_list(self, pcm, counts, idx):
+        """process_chunks for the listed streams only: pcm (R, max_count) float32 or int16, counts (R,) int32 and idx (R,) int32 CUDA
+        tensors, row i belonging to stream idx[i].  Unlisted streams are not touched and the cost follows R.  -> out (R, max_count),
+        vad (F, R), gains (F, R, 32), frames (R,) int32 (torch.ops.rnnoise_amd.process_chunks_list)"""
+        return self.torch.ops.rnnoise_amd.process_chunks_list(pcm, counts, idx, self.state, self.handle)
+
     def reset_streams(self, idx):
         """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
         a host synchronisation (rnnoise_batch_reset_streams_device: entries out of range are ignored)"""
@@ -244,6 +266,33 @@ class RNNoiseOp:
         # (freeing idx or a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.load_streams_device(snap.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
                                        torch.cuda.current_stream(self.device).cuda_stream)
+
+    def save_chunk_fifos(self, idx=None):
+        """the FIFO records of the listed streams (None: the whole batch) as an (n, CHUNK_REC_FLOATS) float32 CUDA tensor, on torch's
+        current stream without a host synchronisation (rnnoise_batch_save_chunk_fifos_device): what save_streams leaves behind of a
+        stream fed through process_chunks.  The batch is unchanged."""
+        torch = self.torch
+        if idx is not None:
+            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = self.n if idx is None else int(idx.numel())
+        rec = torch.empty((n, capi.CHUNK_REC_FLOATS), device=self.device, dtype=torch.float32)
+        self.batch.save_chunk_fifos_device(rec.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
+                                           torch.cuda.current_stream(self.device).cuda_stream)
+        return rec
+
+    def load_chunk_fifos(self, rec, idx=None):
+        """row i of rec ((n, CHUNK_REC_FLOATS) float32 CUDA tensor) becomes the FIFOs of stream idx[i], on torch's current stream
+        (rnnoise_batch_load_chunk_fifos_device: rows that are no records of the batch's frame length and entries out of range touch
+        nothing).  Call it AFTER load_streams, which restarts the FIFOs of the streams it loads."""
+        torch = self.torch
+        if idx is not None:
+            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = self.n if idx is None else int(idx.numel())
+        assert rec.is_cuda and rec.dtype == torch.float32 and tuple(rec.shape) == (n, capi.CHUNK_REC_FLOATS)
+        rec = rec.to(self.device).contiguous()
+        # (freeing idx or a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        self.batch.load_chunk_fifos_device(rec.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
+                                           torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_stream_models(self, slots):
         """the model slot of every stream: an (N,) uint8 CUDA tensor, copied on torch's current stream without a host synchronisation
@@ -379,6 +428,26 @@ class RNNoiseOp:
             return out, vad, gains, frames
         self.batch.process_chunks_device(out.data_ptr(), pcm.data_ptr(), counts.data_ptr(), pcm.shape[1], vad.data_ptr(), gains.data_ptr(),
                                          frames.data_ptr(), stream, s16=pcm.dtype == torch.int16)
+        return out, vad, gains, frames
+
+    def _run_chunks_list(self, pcm, counts, idx):
+        torch = self.torch
+        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2 and pcm.shape[0] <= self.n
+        R = pcm.shape[0]
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == R
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.numel() == R
+        self._layout(0, 0)
+        pcm, counts, idx = pcm.contiguous(), counts.contiguous(), idx.contiguous()
+        F = capi.chunk_frames(self.batch.frame, pcm.shape[1])
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        vad = torch.zeros((F, R), device=pcm.device, dtype=torch.float32)
+        gains = torch.zeros((F, R, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        frames = torch.zeros((R,), device=pcm.device, dtype=torch.int32)
+        out = torch.zeros_like(pcm)
+        if pcm.shape[1] == 0 or R == 0:  # (nothing to push: the library's no-op, and an empty tensor has no address to hand it)
+            return out, vad, gains, frames
+        self.batch.process_chunks_list_device(out.data_ptr(), pcm.data_ptr(), counts.data_ptr(), pcm.shape[1], idx.data_ptr(), R,
+                                              vad.data_ptr(), gains.data_ptr(), frames.data_ptr(), stream, s16=pcm.dtype == torch.int16)
         return out, vad, gains, frames
 
     def _run_list(self, pcm, idx, active=None):
