@@ -25,8 +25,10 @@ running it.
                                     [OUTDIR]` writes only it): per run of stream_mix.block_pin_runs() -- every position on the
                                     default model, 40 on the sparser one, in lock step and under the presence schedule with its
                                     restarts -- CRC32 per (frame, position) of out, gains and features, vad, pitch, silence and one
-                                    CRC32 of the final state per position.  Keys the file already holds must come out bit-identical,
-                                    or nothing is written
+                                    CRC32 of the final state per position; and per run of stream_mix.chunk_pin_runs() -- the oracle inputs
+                                    of the chunk dressing: the block rounded to int16, and brought to 16 and 32 kHz and back up, every
+                                    position in lock step -- one CRC32 per (frame, position) over all of those, and the state's.  Keys the file already
+                                    holds must come out bit-identical, or nothing is written
 
 The reference's tanh / sigmoid execute the generating CPU's `rcpps` (src/vec_avx.h:413,442), so a fixture belongs to one
 CPU family and says which ("rcp_profile", "host_cpu" entries).  The Intel build host writes tests/golden/*.npz; run on the
@@ -149,6 +151,10 @@ def block_pins(gold, tag):
         r = stream_mix.block_run(blob, positions, scheduled, engine=RefHarness)
         d[f"{run}_positions"] = np.array(positions, np.int16)
         for k, v in stream_mix.block_digest(r).items():
+            d[f"{run}_{k}"] = v
+    blob = open(os.path.join(ROOT, "oracle", "_ref", "default.blob"), "rb").read()
+    for run, hz, typ in stream_mix.chunk_pin_runs():  # the chunk dressing's oracle inputs: every position, lock step
+        for k, v in stream_mix.chunk_pin_digest(stream_mix.chunk_pin_run(blob, hz, typ, engine=RefHarness)).items():
             d[f"{run}_{k}"] = v
     path = os.path.join(gold, "block_pins.npz")
     if os.path.exists(path):  # what the file pins already stays pinned

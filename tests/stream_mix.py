@@ -1,6 +1,6 @@
 """One mixed block of streams for the at-size parity tests (plain helper module: tests/test_stream_mix_cpu.py checks what the block
 and its dressings cover; tests/test_gpu_at_size.py runs it in lock-step calls, through masked and list calls, with poisoned streams
-under linked gains and through the PCM front ends; tests/test_dropin_gpu.py runs it through the drop-in API).
+under linked gains, through the PCM front ends and through the chunk calls; tests/test_dropin_gpu.py runs it through the drop-in API).
 
 `block()` is B = 389 streams x 30 frames of float PCM.  The at-size tests lay a batch out as copies of it (stream i takes block
 stream i mod B); B is prime, so the copies land at shifting offsets modulo the 4 streams of an analysis workgroup, the 16 of a tile
@@ -32,6 +32,12 @@ and float calls, interleaved channels and caller strides.  Its expectation is a 
 
 `block_pin_runs()`, `block_run()` and `block_digest()` are the runs of the block that tests/test_oracle.py compares between the oracle
 and the compiled reference, and what tests/golden/block_pins.npz records of them.
+
+The chunk dressing (`CHUNK_CASES`, `CHUNK_PUSHES`, `chunk_schedule()`, `chunk_push_plan()`, `chunk_expectation()`, `chunk_records()`)
+runs the block through the chunk calls: every position's signal as one row at the batch rate (48, 32 or 16 kHz, float or int16),
+handed over in full-size and list pushes of 0 .. max_count samples, with a reset while samples are pending and a move of the whole
+batch with its FIFO records.  Its expectation is the closed form of include/rnnoise_amd.h -- y = 0^M ++ z -- over one CPU chain per
+position; `chunk_pin_runs()` are the oracle inputs it adds, which tests/test_oracle.py compares with the compiled reference.
 """
 from __future__ import annotations
 
@@ -864,3 +870,413 @@ def block_digest(r):
 
     return dict(out_crc=crc(r["out"]), gains_crc=crc(r["gains"]), features_crc=crc(r["features"]), vad=r["vad"].astype(np.float32),
                 pitch=r["pitch"].astype(np.int16), silence=r["silence"].astype(np.int8), state_crc=crc(r["state"]))
+
+
+# ---- the chunk dressing: the block through the chunk calls (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks[_list]) ----
+# Position p's signal is one row of T M samples at the case's rate (M = 480 rate / 48000), handed over in the pushes of CHUNK_PUSHES:
+# counts[q, p] new samples in push q, a function of the position, so one CPU chain per position covers every copy.  The expectation is
+# cumulative sums and slices of the closed form the header promises -- y = 0^M ++ z --; nothing of rnnoise_amd/csrc/chunk_plan.h is
+# ported here.
+#
+# CHUNK_CASES: (streams, network path or None for the batch's default, rate in Hz, "float" | "int16"), n % B != 0.  On 256 CUs with the
+# default switches (test_stream_mix_cpu.py holds them to it; a low batch rate forces rn_hp_one_kernel at every size):
+CHUNK_CASES = [
+    (252, 0, 48000, "float"),       # rn_nn_one_kernel, rn_synthesis_few_kernel, rn_hp_one_kernel
+    (390, 1, 48000, "int16"),       # tile 16 in F = 1 pushes, tile 8 in pipelined ones, rn_synthesis_kernel
+    (390, 2, 16000, "int16"),       # layer-wise network, rn_nn_gru_w8_kernel; M = 160, rows packed 160 apart
+    (1031, 0, 32000, "float"),      # rn_nn_vector_kernel behind the 2:3 resampler, M = 320
+    (3001, None, 48000, "float"),   # rn_hp_kernel (lane = stream) in place, both tile kernels
+    (4099, 0, 48000, "int16"),      # rn_nn_vector_kernel at size behind rn_hp_kernel
+    (10277, None, 48000, "float"),  # layer-wise network, rn_nn_gru_w8_kernel just above the switch: partial tile, partial group
+    (16421, None, 48000, "int16"),  # rn_nn_gru_kernel (w4): 257 groups of 64, ragged in every unit
+]
+CHUNK_IDS = [f"n{n}-path{p}-{hz}-{typ}" for n, p, hz, typ in CHUNK_CASES]
+CHUNK_VARIANTS = tuple(sorted({(hz, typ) for _, _, hz, typ in CHUNK_CASES}))
+
+# A push: max_count (a, b) = a M + b samples, so that one schedule serves every rate; its form; for a list push the share of the
+# positions it lists; and its recipe: the count of position p is recipe[(p + shift) % len(recipe)], with
+#   (a, b)  a M + b samples            "J"  jitter(p, M): a count of the position's own, 12 .. M - 13
+#   "U"     unlisted (list pushes)     "T"  the tail: whatever brings the position to its total (_chunk_tail)
+# The recipes are Latin: with the shifts 0, 1, 2 .. of the pushes that share a recipe every position takes every entry once -- the
+# special counts 0, 1, M - 1, M, M + 1, 2 M and the push's max_count (M in the small pushes, 2 M in the big ones), in a full-size push
+# and while listed -- and any four (five) neighbours hold all of a recipe's entries in every push.
+# Where a rule of the schedule cannot hold as a sentence, it holds as far as it can (test_stream_mix_cpu.py asserts exactly this): a
+# push with F = 1 has two values of k, not three; before the first push every FIFO is empty, so the fills mix from the second on; the
+# position that no list push lists takes its special counts in full-size pushes only, the one in every other list push those of
+# the list pushes it is in.
+_SMALL = ((1, 0), (0, 0), (0, 1), (1, -1))                 # M = max_count (k = 1 = F), 0, 1, M - 1
+_BIG = ((2, 0), (0, 0), (1, 1), (1, 0))                    # 2 M = max_count (k = 2 = F), 0, M + 1, M (k = 1)
+_KINDS = {                                                 # kind: (max_count, form, recipe)
+    "J": ((1, 0), "full", ((1, 0), "J", "J", "J")),        # the first push: a fill of its own on three positions in four
+    "S": ((1, 0), "full", _SMALL),
+    "s": ((1, 0), "list", _SMALL + ("U",)),
+    "B": ((2, 0), "full", _BIG),
+    "b": ((2, 0), "list", _BIG + ("U",)),
+    "T7": ((7, 0), "full", ("T",)),                        # F = 7: the 6-slot pitch ring wraps inside one chunk call
+    "t7": ((7, -1), "full", ("T",)),                       # ... with rows an odd number of samples apart
+    "T4": ((4, 0), "full", ("T",)),
+}
+# full F = 1, list F = 1, full F = 2 and list F = 2 back to back, then alternating in form and schedule, then the tail
+_ORDER = ("J", "S", "S", "s", "s", "B", "B", "b", "b", "S", "b", "S", "b", "s", "B", "s", "B", "s", "b", "T7", "t7", "T7", "T4")
+
+
+def _pushes():
+    seen, out = {}, []
+    for kind in _ORDER:
+        mc, form, recipe = _KINDS[kind]
+        share = None if form == "full" else 1 - recipe.count("U") / len(recipe)
+        out.append(dict(max_count=mc, form=form, share=share, recipe=recipe, shift=seen.get(kind, 0), tail=recipe == ("T",)))
+        seen[kind] = seen.get(kind, 0) + 1
+    return tuple(out)
+
+
+CHUNK_PUSHES = _pushes()
+CHUNK_RESET_BEFORE = 7                    # RESET's positions are reset (every copy) before this push ...
+CHUNK_MOVE_BEFORE = 13                    # ... and the whole batch moves to a fresh one before this one
+CHUNK_MUTANTS = ("no_delay", "reset_keeps_pending", "reset_keeps_history", "frames_late", "cast_before_down", "list_advances_unlisted")
+
+
+def chunk_frame(hz):
+    """M: the samples of a frame at a batch rate of hz"""
+    return 480 * hz // 48000
+
+
+def chunk_jitter(M):
+    """(B,) int: a count of the position's own, 12 .. M - 13 (53 is coprime to M - 24 for M = 480, 320, 160)"""
+    return 12 + (np.arange(B) * 53) % (M - 24)
+
+
+_TAIL_IDLE_TOO = (3, 131, 259)
+
+
+def _chunk_tail(M, cum, total, maxes, max_last):
+    """the counts of the tail's pushes -- max_count maxes[t], and max_last in the last one --, which bring position p to total[p].
+    Three kinds of position.  "Idle" ones -- p mod 4 = 1 without SPECIAL's "never", and _TAIL_IDLE_TOO: three more, one of them in the
+    gap that "never" and the wrap from 388 to 0 leave -- keep max_last samples for the last push (k = F there), and the j-th of them
+    pushes nothing in tail push t where (j + t) mod 3 = 0: k = 0 on one in any three of them.  Those with p mod 4 = 0 are done before
+    the last push (k = 0 there), the others keep M - jitter for it (fill jitter, k = 1); both push max_count (k = F) in tail push t
+    where (p + t) mod 4 = 0.  All of that wherever the rest still fits the other pushes; what is free takes whole frames first, so that
+    the fills stay as mixed as they were"""
+    jit = chunk_jitter(M)
+    idle = [p for p in range(B) if (p % 4 == 1 and p != SPECIAL["never"]) or p in _TAIL_IDLE_TOO]
+    assert len(idle) % 3 == 0                              # (cyclic: the copies wrap from 388 to 0)
+    last = np.select([np.isin(np.arange(B), idle) | (np.arange(B) == SPECIAL["never"]), np.arange(B) % 4 == 0], [max_last, 0], M - jit)
+    last = last + np.maximum(0, total - last - cum - sum(maxes))          # (a position that list pushes left behind: what does not fit)
+    assert (last <= max_last).all()
+    need = total - last - cum
+    n_t = len(maxes)
+    out = np.zeros((n_t + 1, B), np.int64)
+    for p in range(B):
+        if p in idle:
+            want = ["zero" if (idle.index(p) + t) % 3 == 0 else None for t in range(n_t)]
+        else:
+            want = ["max" if (p + t) % 4 == 0 else None for t in range(n_t)]
+        D = int(need[p])
+        assert 0 <= D <= sum(maxes), (p, D)
+        if D < sum(m for w, m in zip(want, maxes) if w == "max"):
+            want = [None if w == "max" else w for w in want]
+        fixed = sum(m for w, m in zip(want, maxes) if w == "max")
+        if D - fixed > sum(m for w, m in zip(want, maxes) if w is None):
+            want = [None if w == "zero" else w for w in want]
+        rest = D - fixed
+        free = [t for t in range(n_t) if want[t] is None]
+        for i, t in enumerate(free):
+            later = sum(maxes[u] for u in free[i + 1:])
+            if i + 1 == len(free):
+                n = rest
+            else:
+                n = min(maxes[t], rest, -(-rest // (len(free) - i) // M) * M)
+                n = max(n, rest - later)
+            assert 0 <= n <= maxes[t], (p, t, n)
+            out[t, p] = n
+            rest -= n
+        for t in range(n_t):
+            if want[t] == "max":
+                out[t, p] = maxes[t]
+    out[n_t] = last
+    assert (out.sum(0) + cum == total).all()
+    return out
+
+
+@functools.lru_cache(None)
+def chunk_schedule(M):
+    """the schedule of CHUNK_PUSHES at frame length M, everything by block position: "counts" (Q, B) int32; "listed" (Q, B) bool (all
+    true in a full-size push); "max_count", "F" (Q,); "cum" (Q + 1, B): samples pushed before push q; "base": the value of cum at the
+    position's last restart before push q (0, or for RESET's positions from CHUNK_RESET_BEFORE on the samples pushed until then);
+    "fill" = (cum - base) % M and "done" (frames completed) before push q, a restart before it included; "fill_after" (Q, B): the
+    fill push q leaves; "k" (Q, B) = done[q + 1] - done[q]; "total" (B,)."""
+    Q = len(CHUNK_PUSHES)
+    jit = chunk_jitter(M)
+    counts, listed = np.zeros((Q, B), np.int64), np.ones((Q, B), bool)
+    maxc = np.array([a * M + b for a, b in (p["max_count"] for p in CHUNK_PUSHES)])
+    reset = np.zeros(B, bool)
+    reset[list(RESET)] = True
+    nth_list = 0
+    first_tail = min(q for q, p in enumerate(CHUNK_PUSHES) if p["tail"])
+    assert all(p["tail"] for p in CHUNK_PUSHES[first_tail:]) and CHUNK_RESET_BEFORE < CHUNK_MOVE_BEFORE < first_tail
+    for q, push in enumerate(CHUNK_PUSHES[:first_tail]):
+        rec = push["recipe"]
+        for p in range(B):
+            e = rec[(p + push["shift"]) % len(rec)]
+            if q == 0 and reset[p]:
+                e = "J"                                    # a fill that no sum of special counts brings back to 0 before the reset
+            if push["form"] == "list":
+                if p == SPECIAL["never"] or (p == SPECIAL["alternating"] and nth_list % 2):
+                    e = "U"
+                elif p == SPECIAL["alternating"] and e == "U":
+                    e = "J"
+            if e == "U":
+                listed[q, p] = False
+            else:
+                counts[q, p] = jit[p] if e == "J" else e[0] * M + e[1]
+        nth_list += push["form"] == "list"
+    cum = np.concatenate([np.zeros((1, B), np.int64), np.cumsum(counts, 0)])
+    c_r = np.where(reset, cum[CHUNK_RESET_BEFORE], 0)
+    total = c_r + (T * M - c_r) // M * M
+    counts[first_tail:] = _chunk_tail(M, cum[first_tail], total, [int(m) for m in maxc[first_tail:-1]], int(maxc[-1]))
+    assert (counts <= maxc[:, None]).all() and (counts >= 0).all() and not counts[~listed].any()
+    cum = np.concatenate([np.zeros((1, B), np.int64), np.cumsum(counts, 0)])
+    base = np.where((np.arange(Q + 1) >= CHUNK_RESET_BEFORE)[:, None], c_r[None], 0)
+    fill = (cum - base) % M
+    done = base // M + (cum - base) // M
+    r = dict(counts=counts.astype(np.int32), listed=listed, max_count=maxc, F=(M - 1 + maxc) // M, cum=cum, base=base, fill=fill,
+             fill_after=(cum[1:] - base[:-1]) % M, done=done, k=np.diff(done, axis=0), total=total)
+    for v in r.values():
+        v.setflags(write=False)
+    return r
+
+
+def chunk_counts(M):
+    """(pushes, B) int32: the samples position p hands over in push q at frame length M"""
+    return chunk_schedule(M)["counts"].copy()
+
+
+def chunk_list_rows(n, q, M=480):
+    """the stream list of list push q on a batch of n copies of the block: every copy of the positions the push lists in a fixed
+    pseudo-random order, and the entries of OUT_OF_RANGE at the front, the middle and the end (as list_rows()).  int32"""
+    assert CHUNK_PUSHES[q]["form"] == "list"
+    keep = chunk_schedule(M)["listed"][q]                  # (the same positions at every M)
+    rows = _rng(600 + q).permutation(np.flatnonzero(keep[np.arange(n) % B]))
+    bad = [n if e is None else e for e in OUT_OF_RANGE]
+    mid = len(rows) // 2
+    return np.concatenate([[bad[0]], rows[:mid], [bad[1]], rows[mid:], [bad[2]]]).astype(np.int32)
+
+
+def chunk_push_plan(n, q, M):
+    """what push q hands a batch of n copies: "rows" (the int32 stream list of a list push, else None: one row per stream), "named"
+    (the row's entry names a stream), "src" (the block position of every row; 0 for an entry that names no stream) and "counts"
+    (int32 per row; the three rows whose entry names no stream carry max_count // 2, 1 and max_count of position 0's samples)"""
+    s = chunk_schedule(M)
+    if CHUNK_PUSHES[q]["form"] == "full":
+        src = np.arange(n) % B
+        return dict(rows=None, named=np.ones(n, bool), src=src, counts=s["counts"][q][src])
+    rows = chunk_list_rows(n, q, M)
+    named = (rows >= 0) & (rows < n)
+    src = np.where(named, rows, 0) % B
+    counts = np.where(named, s["counts"][q][src], 0).astype(np.int32)
+    counts[~named] = int(s["max_count"][q]) // 2, 1, int(s["max_count"][q])
+    return dict(rows=rows, named=named, src=src, counts=counts)
+
+
+@functools.lru_cache(None)
+def _chunk_signal(hz):
+    pcm, _ = block()
+    sig = np.ascontiguousarray(pcm.transpose(1, 0, 2).reshape(B, T * 480))
+    L = resample.RATES[hz]
+    return sig if L == 1 else np.ascontiguousarray(resample.down(sig, L), np.float32)
+
+
+def chunk_signal(hz, typ):
+    """(B, T M): position p's block signal as one row at the batch rate -- block()[:, p] itself at 48 kHz, resample.down of it from
+    zero history below (as dress_input) --, float32, or for "int16" rounded and clipped (as dress_input("s16"))"""
+    x = _chunk_signal(hz)
+    return x.copy() if typ == "float" else np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+
+
+def _by_length(items, fn):
+    """fn over the rows of `items` {key: 1-D array}, batched by length -> {key: result row}"""
+    out = {}
+    for n in sorted({len(v) for v in items.values()}):
+        keys = [k for k, v in items.items() if len(v) == n]
+        if n == 0:
+            out.update({k: np.zeros(0, np.float32) for k in keys})
+            continue
+        res = fn(np.stack([items[k] for k in keys]))
+        out.update({k: np.ascontiguousarray(res[i], np.float32) for i, k in enumerate(keys)})
+    return out
+
+
+def chunk_expectation(blob, hz, typ, lock=None, mutant=None):
+    """The chunk calls' results on the CPU alone, by block position.  One chain per position over its whole frames -- resample.up ->
+    Oracle -> resample.down -> (int16: resample.to_s16) -- gives z; the position's output, all pushes concatenated, is then
+
+        y = 0^M ++ z                                 (a plain position)
+        y = (0^M ++ z1)[:c] ++ 0^M ++ z2             (a position of RESET, restarted with c samples pushed, c = k1 M + f, 0 < f < M)
+
+    A restart drops the f pending samples and the output FIFO.  Until then the position had been handed c samples: the M zeros and
+    the first c - M = (k1 - 1) M + f samples of z1 (nothing of z1 while c < M), so the last M - f samples of z1's frame k1 - 1 were
+    still in the FIFO and are lost.  z1 is the chain over x[0 : k1 M]; z2 a second chain from zero state and zero resampler history
+    over the whole frames of x[c:], and the restarted FIFO's M zeros stand in front of it.
+    Push q returns y[cum[q] : cum[q + 1]], completes k = (cum'[q + 1] // M) - (cum'[q] // M) frames with cum' counted from the
+    restart, and leaves cum'[q + 1] % M pending (chunk_schedule: "cum", "base", "k", "fill"); its vad / gains rows are rows
+    done[q] .. done[q] + k - 1 of "vad" / "gains" below.
+    -> "x" (B, T M) the input in the call's type; "y" (B, (T + 1) M) in the call's type and "yf" the same before the cast (what the
+    output FIFO holds); "vad" (B, T), "gains" (B, T, 32) by completed frame; "state" (B, STATE): the oracle's after the last frame;
+    "move_state": after the frames completed before push CHUNK_MOVE_BEFORE.
+    lock: oracle_block's lock-step run of the block -- at 48 kHz float the plain positions take their frames from it.
+    mutant (CHUNK_MUTANTS) -- for the tests of the tests: a wrong expectation of that kind."""
+    from oracle import binding
+    assert mutant in (None,) + CHUNK_MUTANTS and typ in ("float", "int16")
+    M, L = chunk_frame(hz), resample.RATES[hz]
+    s = chunk_schedule(M)
+    x = chunk_signal(hz, typ)
+    xf = x.astype(np.float32)
+    reset = np.zeros(B, bool)
+    reset[list(RESET)] = True
+    c_r = s["base"][-1]
+    late = int(mutant == "frames_late")
+    segs = {}                                              # (position, segment): the samples of its whole frames
+    for p in range(B):
+        if reset[p]:
+            c = int(c_r[p])
+            segs[p, 0] = xf[p, late:late + (c - late) // M * M]
+            start = c - (c % M if mutant == "reset_keeps_pending" else 0) + late
+            segs[p, 1] = xf[p, start:start + (int(s["total"][p]) - start) // M * M]
+        else:
+            segs[p, 0] = xf[p, late:late + (T * M - late) // M * M]
+    keep_hist = mutant == "reset_keeps_history"
+
+    def resampled(rows, fn):
+        if L == 1:
+            return dict(rows)
+        if not keep_hist:
+            return _by_length(rows, lambda a: fn(a, L))
+        joined = {p: np.concatenate([rows[p, 0]] + ([rows[p, 1]] if reset[p] else [])) for p in range(B)}
+        res = _by_length(joined, lambda a: fn(a, L))
+        out = {}
+        for p in range(B):
+            cut = len(rows[p, 0]) * len(res[p]) // max(1, len(joined[p]))
+            out[p, 0] = res[p][:cut]
+            if reset[p]:
+                out[p, 1] = res[p][cut:]
+        return out
+
+    v = resampled(segs, resample.up)
+    use_lock = lock is not None and L == 1 and typ == "float" and mutant in (None, "no_delay")
+    moved = s["done"][CHUNK_MOVE_BEFORE]                   # frames completed at the move, restarts included
+    # list_advances_unlisted: every list push feeds a frame of zeros to the positions it does not list
+    extra = {p: [int(s["done"][q, p]) for q, push in enumerate(CHUNK_PUSHES) if push["form"] == "list" and not s["listed"][q, p]]
+             for p in range(B)} if mutant == "list_advances_unlisted" else {}
+
+    def one(p):
+        o = binding.Oracle(blob)
+        runs, at, move_state = [], 0, None
+        for seg in range(2 if reset[p] else 1):
+            if seg:
+                o = binding.Oracle(blob)
+            fr = v[p, seg].reshape(-1, 480)
+            if use_lock and not reset[p]:
+                stop = int(moved[p])
+                o.run(fr[:stop]) if stop else None
+                return None, o.get_state()
+            cuts = sorted({0, len(fr)} | ({int(moved[p]) - at} if at <= moved[p] <= at + len(fr) else set())
+                          | {e - at for e in extra.get(p, ()) if at <= e < at + len(fr)})
+            for a, b in zip(cuts[:-1], cuts[1:] if len(cuts) > 1 else []):
+                if at + a == moved[p] and move_state is None:
+                    move_state = o.get_state()
+                for _ in range(extra.get(p, ()).count(at + a)):
+                    o.run(np.zeros((1, 480), np.float32))
+                runs.append(o.run(fr[a:b]))
+            at += len(fr)
+            if at == moved[p] and move_state is None:
+                move_state = o.get_state()
+        r = {k: np.concatenate([x_[k] for x_ in runs]) for k in ("out", "vad", "gains")} if runs else None
+        return (r, o.get_state()), move_state
+
+    workers = max(1, min(16, len(os.sched_getaffinity(0))))
+    with ThreadPoolExecutor(workers) as pool:
+        res = list(pool.map(one, range(B)))
+    vad, gains = np.zeros((B, T), np.float32), np.zeros((B, T, 32), np.float32)
+    state = np.zeros((B, res[0][1].shape[0]), np.float32)
+    move_state = np.zeros_like(state)
+    outs = {}
+    for p, (r, ms) in enumerate(res):
+        move_state[p] = ms
+        if r is None:                                      # a plain position at 48 kHz float: the lock-step run's frames
+            outs[p, 0] = lock["out"][:, p].reshape(-1)
+            vad[p], gains[p], state[p] = lock["vad"][:, p], lock["gains"][:, p], lock["state"][p]
+            continue
+        run, state[p] = r
+        K = 0 if run is None else len(run["vad"])
+        if K:
+            vad[p, :K], gains[p, :K] = run["vad"], run["gains"]
+        k1 = len(v[p, 0]) // 480
+        out = np.zeros((0, 480), np.float32) if run is None else run["out"]
+        outs[p, 0] = out[:k1].reshape(-1)
+        if reset[p]:
+            outs[p, 1] = out[k1:].reshape(-1)
+    if mutant == "cast_before_down":
+        outs = {k: resample.to_s16(a).astype(np.float32) for k, a in outs.items()}
+    z = resampled(outs, resample.down)
+    yf = np.zeros((B, (T + 1) * M), np.float32)
+    lead = 0 if mutant == "no_delay" else M + late
+    for p in range(B):
+        a = np.concatenate([np.zeros(lead, np.float32), z[p, 0]])
+        if reset[p]:
+            c = int(c_r[p])
+            a = np.concatenate([a, np.zeros(c, np.float32)])[:c]
+            a = np.concatenate([a, np.zeros(lead, np.float32), z[p, 1]])
+        n = min(len(a), yf.shape[1])
+        yf[p, :n] = a[:n]
+    y = yf if typ == "float" else resample.to_s16(yf)
+    return dict(x=x, y=y, yf=yf, vad=vad, gains=gains, state=state, move_state=move_state)
+
+
+def chunk_records(exp, M, q):
+    """(B, 964) int32: the FIFO record of every position before push q (include/rnnoise_amd.h: rnnoise_batch_save_chunk_fifos) -- the
+    pending samples x[cum - fill : cum], the output FIFO y[cum : cum + M - fill] before the cast, zeros up to 480 behind either, then
+    fill, M, the magic word and a zero"""
+    s = chunk_schedule(M)
+    rec = np.zeros((B, 964), np.float32)
+    xf = exp["x"].astype(np.float32)
+    for p in range(B):
+        c, f = int(s["cum"][q, p]), int(s["fill"][q, p])
+        rec[p, :f] = xf[p, c - f:c]
+        rec[p, 480:480 + M - f] = exp["yf"][p, c:c + M - f]
+    rec = rec.view(np.int32)
+    rec[:, 960], rec[:, 961], rec[:, 962] = s["fill"][q], M, 0x464B4301
+    return rec
+
+
+# ---- the chunk dressing's oracle inputs through the compiled reference (tests/test_oracle.py; make_golden.py --block-pins) ----
+def chunk_pin_runs():
+    """the signals the chunk expectation feeds the oracle that no run of block_pin_runs() holds, as (tag, rate, type): the block rounded
+    to int16, and the two resampled ones -- resample.up of the 16 kHz int16 and of the 32 kHz float signal.  Every position, default
+    model, lock step (the 48 kHz float signal is the block itself: "default_lock")"""
+    return [(f"chunk_{hz}_{typ}", hz, typ) for hz, typ in CHUNK_VARIANTS if (hz, typ) != (48000, "float")]
+
+
+def chunk_pin_input(hz, typ):
+    """(T, B, 480) float32: the frames chunk_expectation's chain hands the oracle for the plain positions' whole signals"""
+    x = chunk_signal(hz, typ).astype(np.float32)
+    L = resample.RATES[hz]
+    v = x if L == 1 else resample.up(x, L)
+    return np.ascontiguousarray(np.asarray(v, np.float32).reshape(B, T, 480).transpose(1, 0, 2))
+
+
+def chunk_pin_run(blob, hz, typ, engine=None):
+    """oracle_block over chunk_pin_input() on `engine` (the oracle, or oracle.binding.RefHarness)"""
+    return oracle_block(blob, chunk_pin_input(hz, typ), engine=engine)
+
+
+CHUNK_PIN_KEYS = ("frame_crc", "state_crc")
+
+
+def chunk_pin_digest(r):
+    """what tests/golden/block_pins.npz holds of a chunk_pin_run(): one CRC32 per (frame, position) over out, gains, features, vad, pitch
+    and silence together, and one of the final state per position (CHUNK_PIN_KEYS)"""
+    import zlib
+    Tn, n = r["vad"].shape
+    parts = [np.ascontiguousarray(r[k][..., None] if r[k].ndim == 2 else r[k]) for k in ("out", "gains", "features", "vad", "pitch", "silence")]
+    frame = np.array([[zlib.crc32(b"".join(a[t, s].tobytes() for a in parts)) for s in range(n)] for t in range(Tn)], np.uint32)
+    return dict(frame_crc=frame, state_crc=np.array([zlib.crc32(np.ascontiguousarray(x).tobytes()) for x in r["state"]], np.uint32))

@@ -7,7 +7,9 @@ block of tests/stream_mix.py (389 streams of every kind, compared stream by stre
 form, with NaN / Inf in copies of one of its streams, and through masked, stream-list and per-stream-phase lock-step calls with
 NaN in every absent row; under linked gains with controls and two model slots (stream_mix.LINK_CASES), the same two ways; and
 through the PCM front ends -- rate table, format table, strides, channels, int16 calls (stream_mix.DRESS_CASES) --, the same two ways,
-against a chain on the CPU alone.
+against a chain on the CPU alone; and through the chunk calls -- full-size and list pushes of any count, in place on the staging
+buffer, a reset with samples pending, a move with FIFO records (stream_mix.CHUNK_CASES) -- against the header's closed form on the CPU
+alone.
 Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
 import os
 import subprocess
@@ -509,6 +511,179 @@ def test_stream_mix_dressed_masked_and_listed_at_every_form(blob_default, rcp_pr
     beside its siblings' output."""
     _need_256_cus()
     _dressed_run(blob_default, rcp_profile, case, scheduled=True)
+
+
+# ---- the block through the chunk calls (stream_mix.CHUNK_CASES): in place on the staging buffer, a mask the device writes ----
+_CHUNKED = {}
+
+
+def _chunked(blob, profile, hz, typ):
+    """the CPU chain's chunk expectation of the block (stream_mix.chunk_expectation), once per module, rcpps profile, rate and sample
+    type; at 48 kHz float the plain positions take their frames from the lock-step run of _mix.  No GPU takes part in it"""
+    key = (profile, hz, typ)
+    if key not in _CHUNKED:
+        lock = _mix(blob, profile)[1] if (hz, typ) == (48000, "float") else None
+        _CHUNKED[key] = stream_mix.chunk_expectation(blob, hz, typ, lock=lock)
+    return _CHUNKED[key]
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path,hz,typ", stream_mix.CHUNK_CASES, ids=stream_mix.CHUNK_IDS)
+def test_stream_mix_chunked_at_every_form(blob_default, rcp_profile, n, path, hz, typ):
+    """The mixed block through the chunk calls (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks[_list][_s16],
+    rnnoise_batch_save / load_chunk_fifos_device) at every kernel form: n copies of the block, every position's signal as one row at
+    the batch rate, handed over in the pushes of stream_mix.CHUNK_PUSHES -- full-size and list pushes, F = 1 to 7, every count from 0
+    to max_count, so that the rows of one tile, wave and GRU group complete 0 .. F frames in the same call from FIFOs at every fill.
+    The masked call inside runs in place on the batch's staging buffer, with rows M apart and a mask the scatter kernel wrote.  The
+    expectation is the closed form y = 0^M ++ z on the CPU alone (stream_mix.chunk_expectation).  Every push: NaN / 31000 behind every
+    row's count of `in`; the whole allocation of `out` -- the first count samples of every row from the expectation, the sentinel in
+    everything else: the rest of the row, the rows of list entries that name no stream, the padding behind the buffer --, frames, vad
+    and gains of every row (zeros from row k on), `in` untouched, and chunk_fill() of every stream; all as bit patterns, on the
+    device.  Before push CHUNK_RESET_BEFORE RESET's copies are reset with samples pending; before push CHUNK_MOVE_BEFORE the whole
+    batch moves to a fresh one through the device forms of snapshots and FIFO records and a shuffled list: the records of every stream
+    against the CPU's, the portable state of every block position (each from a different copy) against the oracle's after its
+    completed frames, and the destination's records the same bytes.  At the end the states as in the masked test, and empty FIFOs."""
+    import torch
+    _need_256_cus()
+    B, T, s16 = stream_mix.B, stream_mix.T, typ == "int16"
+    M = stream_mix.chunk_frame(hz)
+    exp, s = _chunked(blob_default, rcp_profile, hz, typ), stream_mix.chunk_schedule(M)
+    dev = torch.device("cuda", 0)
+    el = torch.int16 if s16 else torch.int32
+    junk, sentinel = (31000, SENTINEL_S16) if s16 else (0x7FC00000, SENTINEL_OUT)
+    top, Fmax = int(s["max_count"].max()), int(s["F"].max())
+    idx = np.arange(n) % B
+
+    def padded(a, extra):
+        """a (B, W, ...) as bit patterns on the device, with `extra` zero columns behind it: every gather below stays inside"""
+        a = np.ascontiguousarray(a)
+        t = torch.from_numpy(a.view(np.int32) if a.dtype == np.float32 else a).to(dev)
+        return torch.cat([t, torch.zeros((B, extra) + t.shape[2:], dtype=t.dtype, device=dev)], 1)
+
+    x, y = padded(exp["x"], top), padded(exp["y"], top)
+    ref_vad, ref_gains = padded(exp["vad"], Fmax), padded(exp["gains"], Fmax)
+    cum, done, k_all = (torch.from_numpy(s[key].copy()).to(dev) for key in ("cum", "done", "k"))
+    m = capi.Model(blob_default)
+
+    def batch():
+        b_ = capi.Batch(m, n)
+        if path is not None:
+            b_.set_nn_path(path)
+        if hz != 48000:
+            b_.set_pcm_rate(hz)
+        assert b_.frame == M
+        return b_
+
+    b = batch()
+    st = torch.cuda.current_stream().cuda_stream
+    # every block position from a different copy, as the masked test
+    one_each = np.array([p + (7 * p) % ((n - p + B - 1) // B) * B for p in range(min(B, n))])
+    for q, push in enumerate(stream_mix.CHUNK_PUSHES):
+        if q == stream_mix.CHUNK_RESET_BEFORE:
+            hit = np.flatnonzero(np.isin(idx, stream_mix.RESET))
+            assert b.chunk_fill()[hit].all()                                  # (something to drop on every one of them)
+            b.reset_streams(hit)
+            assert not b.chunk_fill()[hit].any()
+        if q == stream_mix.CHUNK_MOVE_BEFORE:
+            order = np.random.default_rng([n, 700]).permutation(n).astype(np.int32)
+            d_list = torch.from_numpy(order).to(dev)
+            d_snap = torch.empty((n, capi.SNAP_FLOATS), device=dev)
+            d_rec = torch.full((n, capi.CHUNK_REC_FLOATS), 7.0, device=dev)
+            b.save_streams_device(d_snap.data_ptr(), d_list.data_ptr(), n, st)
+            b.save_chunk_fifos_device(d_rec.data_ptr(), d_list.data_ptr(), n, st)
+            torch.cuda.synchronize()
+            want_rec = torch.from_numpy(stream_mix.chunk_records(exp, M, q)).to(dev)[torch.from_numpy(order % B).to(dev)]
+            ne = (d_rec.view(torch.int32) != want_rec).any(1)
+            if bool(ne.any().item()):
+                w = ne.nonzero()[:5, 0].tolist()
+                raise AssertionError(f"the move before push {q}: the FIFO records of {int(ne.sum())} of {n} streams differ from the CPU's, first "
+                                     f"(stream, block position, fill) {[(int(order[i]), int(order[i]) % B, int(s['fill'][q, order[i] % B])) for i in w]}")
+            at = np.empty(n, np.int64)
+            at[order] = np.arange(n)                                          # (where the list holds stream i)
+            got = d_snap[torch.from_numpy(at[one_each]).to(dev), :capi.STATE_FLOATS].cpu().numpy()
+            bad = np.flatnonzero((got.view(np.uint32) != exp["move_state"][one_each % B].view(np.uint32)).any(1))
+            assert not len(bad), (f"the move before push {q}: the snapshots of {len(bad)} of {len(one_each)} block positions differ from the "
+                                  f"oracle's state after their completed frames, first (stream, frames) "
+                                  f"{[(int(one_each[i]), int(s['done'][q, one_each[i] % B])) for i in bad[:5]]}")
+            fresh = batch()
+            fresh.load_streams_device(d_snap.data_ptr(), d_list.data_ptr(), n, st)
+            fresh.load_chunk_fifos_device(d_rec.data_ptr(), d_list.data_ptr(), n, st)
+            torch.cuda.synchronize()
+            b.close()
+            b = fresh
+            d_again = torch.full((n, capi.CHUNK_REC_FLOATS), 9.0, device=dev)
+            b.save_chunk_fifos_device(d_again.data_ptr(), d_list.data_ptr(), n, st)
+            torch.cuda.synchronize()
+            assert torch.equal(d_again.view(torch.int32), d_rec.view(torch.int32)), "the destination's FIFO records, saved again, differ"
+            assert_bits_equal(b.chunk_fill(), s["fill"][q][idx].astype(np.int32), "chunk_fill of the destination batch")
+            del d_snap, d_rec, d_again, want_rec
+        plan = stream_mix.chunk_push_plan(n, q, M)
+        mc, F, R = int(s["max_count"][q]), int(s["F"][q]), len(plan["src"])
+        src = torch.from_numpy(plan["src"]).to(dev)
+        named = torch.from_numpy(plan["named"]).to(dev)
+        cnt = torch.from_numpy(np.ascontiguousarray(plan["counts"], np.int32)).to(dev)
+        at = cum[q][src][:, None] + torch.arange(mc, device=dev)[None]        # (R, mc): where the row's samples stand in x and y
+        own = torch.arange(mc, device=dev)[None] < cnt[:, None]
+        size = R * mc + PAD
+        d_in = torch.full((size,), junk, dtype=el, device=dev)
+        d_exp = torch.full((size,), sentinel, dtype=el, device=dev)
+        d_in[:R * mc] = torch.where(own, x[src[:, None], at], junk).reshape(-1)
+        d_exp[:R * mc] = torch.where(own & named[:, None], y[src[:, None], at], sentinel).reshape(-1)
+        del at, own
+        d_in0 = d_in.clone()
+        d_out = torch.full((size,), sentinel, dtype=el, device=dev)
+        vad = torch.full((F, R), SENTINEL_AUX, dtype=torch.int32, device=dev)
+        gains = torch.full((F, R, 32), SENTINEL_AUX, dtype=torch.int32, device=dev)
+        frames = torch.full((R,), SENTINEL_AUX, dtype=torch.int32, device=dev)
+        if plan["rows"] is None:
+            b.process_chunks_device(d_out.data_ptr(), d_in.data_ptr(), cnt.data_ptr(), mc, vad.data_ptr(), gains.data_ptr(),
+                                    frames.data_ptr(), st, s16=s16)
+        else:
+            rows = torch.from_numpy(plan["rows"]).to(dev)
+            b.process_chunks_list_device(d_out.data_ptr(), d_in.data_ptr(), cnt.data_ptr(), mc, rows.data_ptr(), R, vad.data_ptr(),
+                                         gains.data_ptr(), frames.data_ptr(), st, s16=s16)
+        torch.cuda.synchronize()
+        what = f"push {q} ({push['form']}, max_count {mc}, F {F}, {R} rows)"
+        k = torch.where(named, k_all[q][src], 0)
+
+        def where_rows(ne):
+            w = ne.nonzero()[:5, 0].tolist()
+            return (f"first (push, row) {[(q, i) for i in w]}: list entry {[None if plan['rows'] is None else int(plan['rows'][i]) for i in w]}, "
+                    f"block position {[int(plan['src'][i]) for i in w]}, count {[int(plan['counts'][i]) for i in w]}, fill before "
+                    f"{[int(s['fill'][q, plan['src'][i]]) if plan['named'][i] else None for i in w]}, k {[int(k[i]) for i in w]}")
+
+        if not torch.equal(d_out, d_exp):
+            ne = (d_out[:R * mc].reshape(R, mc) != d_exp[:R * mc].reshape(R, mc)).any(1)
+            raise AssertionError(f"{what}: out differs in {int((d_out != d_exp).sum())} of {size} samples, the first at sample "
+                                 f"{int((d_out != d_exp).nonzero()[0])}; {int(ne.sum())} of {R} rows, " + where_rows(ne))
+        assert torch.equal(d_in, d_in0), f"{what}: `in` was written"
+        ne = frames != k
+        if bool(ne.any().item()):
+            raise AssertionError(f"{what}: frames of {int(ne.sum())} of {R} rows differ, " + where_rows(ne))
+        j = torch.arange(F, device=dev)[:, None]
+        live = j < k[None]                                                    # (F, R)
+        fr = done[q][src][None] + j
+        for name, got, ref in (("vad", vad, ref_vad), ("gains", gains, ref_gains)):
+            r = ref[src[None].expand(F, R), fr].reshape(F, R, -1)
+            r = torch.where(live[..., None], r, 0)
+            ne = (got.reshape(F, R, -1) != r).any(-1).any(0)
+            if bool(ne.any().item()):
+                raise AssertionError(f"{what}: {name} of {int(ne.sum())} of {R} rows differs, " + where_rows(ne))
+        del d_in, d_in0, d_out, d_exp, vad, gains, frames
+        fill = b.chunk_fill()
+        bad = np.flatnonzero(fill != s["fill_after"][q][idx])
+        if len(bad):
+            raise AssertionError(f"{what}: chunk_fill of {len(bad)} of {n} streams differs, first (stream, block position, listed, got, expected) "
+                                 f"{[(int(i), int(i) % B, bool(s['listed'][q, i % B]), int(fill[i]), int(s['fill_after'][q, i % B])) for i in bad[:5]]}")
+    del x, y, ref_vad, ref_gains
+    assert not b.chunk_fill().any()
+    # every block position from a different copy, the last copy of every reset position, every copy of the position no list push lists
+    streams = np.unique(np.concatenate([one_each, [p + (n - 1 - p) // B * B for p in stream_mix.RESET if p < n],
+                                        np.arange(stream_mix.SPECIAL["never"], n, B)]))
+    for s_ in streams:
+        assert_bits_equal(b.export_state(int(s_)), exp["state"][s_ % B], f"state of stream {s_} (block stream {s_ % B})")
+    b.close()
+    m.close()
 
 
 # ---- the block under linked gains (stream_mix.LINK_CASES): controls, two model slots, group-wise list calls ----

@@ -362,6 +362,33 @@ def test_the_mixed_block_is_the_reference(which):
         assert_bits_equal(v, pin, f"{tag}: {k}")
 
 
+@pytest.mark.rcp("host")  # (as above)
+@pytest.mark.parametrize("which", range(3), ids=["16000_int16", "32000_float", "48000_int16"])
+def test_the_chunk_dressings_oracle_inputs_are_the_reference(which):
+    """The chunk expectation of the at-size tests (stream_mix.chunk_expectation) rests on the oracle over signals that the runs above do
+    not contain: the block rounded to int16, and resample.up of the block brought down to 16 kHz (rounded to int16) and to 32 kHz.  All
+    389 positions of each in lock step on the default model, through the reference and through the oracle: bit identity in out, vad,
+    gains, features, pitch, silence and final state, live where oracle/_ref is built, else against the recorded digests
+    (tests/golden/block_pins.npz, make_golden.py --block-pins)."""
+    import stream_mix
+    tag, hz, typ = stream_mix.chunk_pin_runs()[which]
+    assert tag == ["chunk_16000_int16", "chunk_32000_float", "chunk_48000_int16"][which]
+    got = stream_mix.chunk_pin_run(load_blob("default"), hz, typ)
+    if RefHarness.available():
+        want = stream_mix.chunk_pin_run(load_blob("default"), hz, typ, engine=RefHarness)
+        assert set(got) == set(want)
+        for k in ("out", "vad", "gains", "features", "pitch", "silence", "state"):
+            assert_bits_equal(got[k], want[k], f"{tag}: {k}")
+        return
+    g = golden("block_pins.npz")
+    digest = stream_mix.chunk_pin_digest(got)
+    assert set(digest) == set(stream_mix.CHUNK_PIN_KEYS)
+    for k, v in digest.items():
+        pin = g[f"{tag}_{k}"]
+        assert v.dtype == pin.dtype
+        assert_bits_equal(v, pin, f"{tag}: {k}")
+
+
 @pytest.mark.skipif(not RefHarness.available(), reason="oracle/_ref not built (needs the reference sources at build time)")
 def test_block_pins_are_the_reference():
     """the recorded digests of the block are what the compiled reference computes, where it runs on a host of the recording's rcpps
@@ -376,7 +403,14 @@ def test_block_pins_are_the_reference():
     g = np.load(path)
     assert str(g["rcp_profile"]) == prof
     runs = stream_mix.block_pin_runs()
-    assert {k for k in g.files if k not in ("rcp_profile", "host_cpu")} == {f"{t}_{k}" for t, *_ in runs for k in stream_mix.PIN_KEYS + ("positions",)}
+    chunk_runs = stream_mix.chunk_pin_runs()
+    assert {k for k in g.files if k not in ("rcp_profile", "host_cpu")} == (
+        {f"{t}_{k}" for t, *_ in runs for k in stream_mix.PIN_KEYS + ("positions",)} | {f"{t}_{k}" for t, *_ in chunk_runs for k in stream_mix.CHUNK_PIN_KEYS})
+    for tag, hz, typ in chunk_runs:
+        ref = stream_mix.chunk_pin_run(load_blob("default"), hz, typ, engine=RefHarness)
+        for k, v in stream_mix.chunk_pin_digest(ref).items():
+            assert v.dtype == g[f"{tag}_{k}"].dtype
+            assert_bits_equal(v, g[f"{tag}_{k}"], f"{tag}: {k}")
     for run in runs:
         tag, _, positions, _ = run
         assert g[f"{tag}_positions"].tolist() == positions

@@ -15,7 +15,12 @@ forgets the gate counter, has something to fail on
 of channels stay pure and lists whole, that every call's strides fit, that the cases reach the kernel forms they are for with the
 one-wave K0 everywhere, that the expectation reaches every G.711 segment, the zero codes and the denormals, and that a chain whose
 histories advance on an absent frame, whose reset keeps them or which encodes before the truncating cast changes expected rows
-(test_stream_mix_dressed_at_every_form, test_stream_mix_dressed_masked_and_listed_at_every_form)."""
+(test_stream_mix_dressed_at_every_form, test_stream_mix_dressed_masked_and_listed_at_every_form).  And for the chunk dressing
+(stream_mix.CHUNK_CASES and what follows it): that the schedule of pushes keeps its rules at every frame length -- both forms in both
+schedules, every special count on every position, frames completed and FIFO fills mixed in every neighbourhood, a reset that drops
+something, a move at every fill class, a tail that ends on whole frames --, that the cases reach every form a masked and a list call
+can take, that six wrong expectations each change the samples some push returns, and that the closed form is the FIFO model of
+tests/test_chunks_gpu.py on the oracle's frames (test_stream_mix_chunked_at_every_form)."""
 import os
 import subprocess
 
@@ -238,12 +243,23 @@ def _build(tmp_path, name):
     return exe
 
 
-def test_the_cases_reach_every_per_stream_and_list_form(tmp_path):
+def _forms_of(lines):
+    """the forms of every stage in the output lines of dispatch_test / list_dispatch_test (the GRU form only where the network is layer-wise)"""
+    seen = {k: set() for k in ("hp", "k1", "nn", "gru", "k3")}
+    for hp, k1, nn, gru, k3 in lines:
+        seen["hp"].add(hp), seen["k1"].add(k1), seen["nn"].add(nn), seen["k3"].add(k3)
+        if nn == "layers":
+            seen["gru"].add(gru)
+    return seen
+
+
+@pytest.fixture(scope="module")
+def form_sweep(tmp_path_factory):
     """The forms the rules can choose in per-stream frame phase (masked calls, lock-step calls after them) and in list calls -- found by
-    sweeping rn_plan over batch sizes, network paths and pipelining on 256 CUs with the default switches -- are all reached by CASES
-    under KINDS on the default schedule: one-frame calls unpipelined, longer ones pipelined, a list call with as many rows as
-    list_rows() gives it (tests/csrc/dispatch_test.cpp, tests/csrc/list_dispatch_test.cpp)"""
-    plan_exe, list_exe = _build(tmp_path, "dispatch_test"), _build(tmp_path, "list_dispatch_test")
+    sweeping rn_plan over batch sizes, network paths and pipelining on 256 CUs with the default switches (tests/csrc/dispatch_test.cpp,
+    tests/csrc/list_dispatch_test.cpp) -- as (run, plan_exe, list_exe, can_stream, can_list); run(exe, cases) gives the output lines"""
+    tmp = tmp_path_factory.mktemp("form_sweep")
+    plan_exe, list_exe = _build(tmp, "dispatch_test"), _build(tmp, "list_dispatch_test")
     env = {k: v for k, v in os.environ.items() if not k.startswith("RNNOISE_AMD_")}
 
     def run(exe, cases):
@@ -253,24 +269,24 @@ def test_the_cases_reach_every_per_stream_and_list_form(tmp_path):
             lines += subprocess.run([exe] + part, capture_output=True, text=True, check=True, env=env).stdout.split("\n")[:len(part)]
         return [tuple(l.split()) for l in lines]
 
-    def forms(lines):
-        seen = {k: set() for k in ("hp", "k1", "nn", "gru", "k3")}
-        for hp, k1, nn, gru, k3 in lines:
-            seen["hp"].add(hp), seen["k1"].add(k1), seen["nn"].add(nn), seen["k3"].add(k3)
-            if nn == "layers":
-                seen["gru"].add(gru)
-        return seen
-
     sizes = sorted(set(range(1, 4200)) | {int(x) + d for x in np.geomspace(4096, 1 << 17, 400) for d in (-1, 0, 1)})
     grid = [(n, path, pipe) for n in sizes for path in (0, 1, 2) for pipe in (0, 1)]
-    can_stream = forms(run(plan_exe, [f"plan:{n},1,256,{path},{pipe},1,0" for n, path, pipe in grid]))
-    can_list = forms(run(list_exe, [f"list:{n},{n},256,{pipe},0,{path}" for n, path, pipe in grid]))
+    can_stream = _forms_of(run(plan_exe, [f"plan:{n},1,256,{path},{pipe},1,0" for n, path, pipe in grid]))
+    can_list = _forms_of(run(list_exe, [f"list:{n},{n},256,{pipe},0,{path}" for n, path, pipe in grid]))
     # what the rules allow today (a new form shows up in the sweep on its own; this only says the sweep sees the regimes)
     assert can_stream["hp"] == {"rn_hp_one_kernel", "rn_hp_kernel"} and can_stream["k1"] == {"rn_analysis_single_kernel"}
     assert can_stream["nn"] == {"rn_nn_one_kernel", "rn_nn_vector_kernel", "rn_nn_mfma_kernel", "rn_nn_mfma16_kernel", "layers"}
     assert can_stream["gru"] == {"rn_nn_gru_kernel", "rn_nn_gru_w8_kernel"}
     assert can_list["hp"] == {"rn_hp_one_kernel"} and can_list["nn"] == {"rn_nn_one_kernel", "rn_nn_mfma_kernel", "rn_nn_mfma16_kernel"}
     assert can_stream["k3"] == can_list["k3"] == {"rn_synthesis_few_kernel", "rn_synthesis_kernel"}
+    return run, plan_exe, list_exe, can_stream, can_list
+
+
+def test_the_cases_reach_every_per_stream_and_list_form(form_sweep):
+    """The forms the rules can choose in per-stream frame phase and in list calls (form_sweep) are all reached by CASES under KINDS on
+    the default schedule: one-frame calls unpipelined, longer ones pipelined, a list call with as many rows as list_rows() gives it"""
+    run, plan_exe, list_exe, can_stream, can_list = form_sweep
+    forms = _forms_of
 
     stream_cases, list_cases = [], []
     for n, path, calls in sm.CASES:
@@ -823,3 +839,281 @@ def test_a_reset_that_forgets_the_gate_counter_shows_in_the_expectation():
                       final_counters=int((r2["gate"][groups] != r["gate"][groups]).sum()))
         assert differ.sum() >= 10 and rows.sum() >= 3 and msg[K]["final_counters"] >= 1, msg
     print("counter restart", msg)
+
+
+# ---- the chunk dressing (stream_mix.CHUNK_CASES, CHUNK_PUSHES, chunk_schedule(), chunk_expectation): what
+# test_stream_mix_chunked_at_every_form runs ----
+_CHUNK_MS = (480, 320, 160)
+_CHUNKED = {}
+
+
+def _chunked(hz, typ, mutant=None):
+    """the CPU chain's chunk expectation of the block, on the goldens' profile"""
+    from conftest import use_rcp_profile
+    use_rcp_profile("intel")
+    if (hz, typ, mutant) not in _CHUNKED:
+        _CHUNKED[hz, typ, mutant] = sm.chunk_expectation(load_blob("default"), hz, typ, mutant=mutant)
+    return _CHUNKED[hz, typ, mutant]
+
+
+def _windows(a, w):
+    """the sets of values that any w neighbouring positions hold (cyclic: the copies of a batch wrap from 388 to 0)"""
+    return [set(a[np.arange(i, i + w) % sm.B].tolist()) for i in range(sm.B)]
+
+
+@pytest.mark.parametrize("M", _CHUNK_MS)
+def test_the_chunk_schedule_keeps_its_rules(M):
+    assert {sm.chunk_frame(hz) for _, _, hz, _ in sm.CHUNK_CASES} == set(_CHUNK_MS)
+    s, P = sm.chunk_schedule(M), sm.CHUNK_PUSHES
+    Q = len(P)
+    counts, listed, F, cum, fill, k = s["counts"], s["listed"], s["F"], s["cum"], s["fill"], s["k"]
+    assert counts.shape == (Q, sm.B) and counts.dtype == np.int32 and (sm.chunk_counts(M) == counts).all()
+    assert (s["max_count"] == [a * M + b for a, b in (p["max_count"] for p in P)]).all() and (F == (M - 1 + s["max_count"]) // M).all()
+    assert (counts >= 0).all() and (counts <= s["max_count"][:, None]).all()
+    # both schedules in both forms, back to back and alternating; one push wraps the 6-slot pitch ring
+    kind = [(p["form"], bool(f > 1)) for p, f in zip(P, F)]
+    for form in ("full", "list"):
+        for piped in (False, True):
+            at = [q for q in range(Q) if kind[q] == (form, piped)]
+            assert any(b - a == 1 for a, b in zip(at, at[1:])), ("back to back", form, piped)
+            assert any(q + 1 < Q and kind[q + 1] == (other, not piped) for q in at for other in ("full", "list") if other != form), (form, piped)
+    assert (s["max_count"][F == 1] <= M).all() and (s["max_count"][F > 1] > M).all() and F.max() >= 7
+    assert any(b % 2 for (_, b), f in zip((p["max_count"] for p in P), F) if f > 1)          # rows an odd number of samples apart
+    # every position is pushed every special count in a full-size push and while listed (the position in no list push and the one in
+    # every other list push: in the full-size pushes)
+    never, alt = sm.SPECIAL["never"], sm.SPECIAL["alternating"]
+    full = np.array([p["form"] == "full" for p in P])
+    for p in range(sm.B):
+        for form_rows, where in ((full, np.ones(Q, bool)), (~full, listed[:, p])):
+            if not form_rows[0] and p in (never, alt):
+                continue
+            got = set(counts[form_rows & where, p].tolist())
+            assert {0, 1, M - 1, M, M + 1, 2 * M} <= got, (p, form_rows[0], sorted(got))
+            assert (counts[form_rows & where, p] == s["max_count"][form_rows & where]).any(), (p, "max_count")
+    # unlisted positions push nothing; the hand-made rows carry over
+    assert listed[full].all() and not counts[~listed].any()
+    lists = np.flatnonzero(~full)
+    assert not listed[lists, never].any() and (listed[lists, alt] == (np.arange(len(lists)) % 2 == 0)).all()
+    for q in lists:
+        assert abs(listed[q].mean() - P[q]["share"]) < 0.01 and P[q]["share"] == 0.8
+        assert (~listed[q]).sum() >= 70                                       # (what "a list push that advances unlisted positions" bites on)
+    # some push completes a frame exactly (on nearly every position), some leaves M - 1 pending
+    moved = counts > 0
+    assert ((s["fill_after"] == 0) & moved & (fill[:-1] != 0)).any(0).mean() >= 0.9 and ((s["fill_after"] == M - 1) & moved).any(0).sum() >= 20
+    # in every push any 16 neighbours hold 3 different k (2 where F = 1: there are no more), k = 0 and k = F among them; before every
+    # push but the first (every FIFO is empty then) any 64 neighbours hold 16 different fills
+    assert (k >= 0).all() and (k <= F[:, None]).all() and (k == (fill[:-1] + counts) // M).all()
+    for q in range(Q):
+        for w in _windows(k[q], 16):
+            assert len(w) >= min(3, F[q] + 1) and 0 in w and F[q] in w, (q, w)
+        if q:
+            assert min(len(w) for w in _windows(fill[q], 64)) >= 16, q
+    assert not fill[0].any()
+    # the reset drops something on every position of RESET; the move finds every fill class
+    pend = cum[sm.CHUNK_RESET_BEFORE, list(sm.RESET)] % M
+    assert (pend != 0).all() and len(set(pend.tolist())) >= 10 and (s["base"][-1, list(sm.RESET)] == cum[sm.CHUNK_RESET_BEFORE, list(sm.RESET)]).all()
+    assert 0 < sm.CHUNK_RESET_BEFORE < sm.CHUNK_MOVE_BEFORE < min(q for q in range(Q) if P[q]["tail"])
+    at = fill[sm.CHUNK_MOVE_BEFORE]
+    assert (at == 0).any() and (at == 1).any() and (at == M - 1).any() and ((at > 1) & (at < M - 1)).sum() >= 100
+    assert s["done"][sm.CHUNK_MOVE_BEFORE].min() >= 1 and len(set(s["done"][sm.CHUNK_MOVE_BEFORE].tolist())) >= 4
+    # the tail tops every position up to whole frames: T M samples for the plain ones
+    plain = np.setdiff1d(np.arange(sm.B), sm.RESET)
+    assert (cum[-1] == s["total"]).all() and (s["total"][plain] == sm.T * M).all() and not fill[-1].any()
+    assert ((s["total"] - s["base"][-1]) % M == 0).all() and (s["total"] > (sm.T - 2) * M).all()
+
+
+@pytest.mark.parametrize("n,path,hz,typ", sm.CHUNK_CASES, ids=sm.CHUNK_IDS)
+def test_every_chunk_case_lists_every_copy_once_and_three_entries_that_name_no_stream(n, path, hz, typ):
+    M = sm.chunk_frame(hz)
+    s = sm.chunk_schedule(M)
+    assert n % sm.B != 0 and n <= 16421 and typ in ("float", "int16")
+    for q, push in enumerate(sm.CHUNK_PUSHES):
+        plan = sm.chunk_push_plan(n, q, M)
+        if push["form"] == "full":
+            assert plan["rows"] is None and (plan["src"] == np.arange(n) % sm.B).all() and (plan["counts"] == s["counts"][q][plan["src"]]).all()
+            continue
+        rows = sm.chunk_list_rows(n, q, M)
+        assert rows.dtype == np.int32 and (rows == plan["rows"]).all() and len(rows) <= n
+        bad = (rows < 0) | (rows >= n)
+        assert bad.sum() == 3 and bad[0] and bad[-1] and bad[len(rows) // 2 - 1:len(rows) // 2 + 2].any()
+        assert sorted(rows[bad].tolist()) == [-1, n, 2 ** 31 - 1] and (plan["named"] == ~bad).all()
+        good = rows[~bad]
+        assert len(set(good.tolist())) == len(good) and set(good.tolist()) == {i for i in range(n) if s["listed"][q][i % sm.B]}
+        assert len(rows) == 3 + sum(int(s["listed"][q][i % sm.B]) for i in range(n))
+        assert (np.diff(good) < 0).any()                                      # not in stream order
+        assert (plan["counts"][~bad] == s["counts"][q][good % sm.B]).all()
+        assert plan["counts"][bad].tolist() == [s["max_count"][q] // 2, 1, s["max_count"][q]]   # samples and a count of their own
+
+
+def test_the_chunk_cases_reach_every_kernel_form(form_sweep):
+    """every full-size push of every CHUNK_CASES entry through dispatch_test as the masked call it makes, every list push through
+    list_dispatch_test with the push's row count: the forms the comments of CHUNK_CASES name, and together every form of form_sweep
+    but rn_analysis_kernel, which per-stream frame phase cannot take"""
+    run, plan_exe, list_exe, can_stream, can_list = form_sweep
+    full, lists = {}, {}
+    for case in sm.CHUNK_CASES:
+        n, path, hz, typ = case
+        M = sm.chunk_frame(hz)
+        F = sm.chunk_schedule(M)["F"]
+        if path is None:
+            path = int(run(plan_exe, [f"path:{n}"])[0][0])
+            assert path == 1, n
+        pipes = [int(x[0]) for x in run(plan_exe, [f"sched:{f},0" for f in F])]
+        assert pipes == [int(f > 1) for f in F]
+        for q, push in enumerate(sm.CHUNK_PUSHES):
+            if push["form"] == "full":
+                full.setdefault(case, []).append((pipes[q],) + run(plan_exe, [f"plan:{n},1,256,{path},{pipes[q]},1,{int(hz != 48000)}"])[0])
+            else:
+                R = len(sm.chunk_list_rows(n, q, M))
+                lists.setdefault(case, []).append((pipes[q],) + run(list_exe, [f"list:{n},{R},256,{pipes[q]},{int(hz != 48000)},{path}"])[0])
+    seen_full = _forms_of([f[1:] for v in full.values() for f in v])
+    seen_list = _forms_of([f[1:] for v in lists.values() for f in v])
+    for kind in can_stream:
+        assert seen_full[kind] == can_stream[kind], ("full-size", kind, can_stream[kind] - seen_full[kind])
+        assert seen_list[kind] == can_list[kind], ("list", kind, can_list[kind] - seen_list[kind])
+    assert "rn_analysis_kernel" not in can_stream["k1"]
+    by = {(c[0], c[1]): c for c in sm.CHUNK_CASES}
+    for f in full[by[252, 0]]:
+        assert (f[1], f[3], f[5]) == ("rn_hp_one_kernel", "rn_nn_one_kernel", "rn_synthesis_few_kernel"), f
+    assert {(f[0], f[3], f[5]) for f in full[by[390, 1]]} == {(0, "rn_nn_mfma16_kernel", "rn_synthesis_kernel"), (1, "rn_nn_mfma_kernel", "rn_synthesis_kernel")}
+    assert {f[3:5] for f in full[by[390, 2]]} == {("layers", "rn_nn_gru_w8_kernel")} and by[390, 2][2] == 16000
+    assert {(f[1], f[3]) for f in full[by[1031, 0]]} == {("rn_hp_one_kernel", "rn_nn_vector_kernel")} and by[1031, 0][2] == 32000
+    assert {(f[0], f[1], f[3]) for f in full[by[3001, None]]} == {(0, "rn_hp_kernel", "rn_nn_mfma16_kernel"), (1, "rn_hp_kernel", "rn_nn_mfma_kernel")}
+    assert {(f[1], f[3]) for f in full[by[4099, 0]]} == {("rn_hp_kernel", "rn_nn_vector_kernel")}
+    assert {(f[1],) + f[3:5] for f in full[by[10277, None]]} == {("rn_hp_kernel", "layers", "rn_nn_gru_w8_kernel")}
+    assert {(f[1],) + f[3:5] for f in full[by[16421, None]]} == {("rn_hp_kernel", "layers", "rn_nn_gru_kernel")}
+    assert (16421 + 63) // 64 == 257 and 16421 % 64 and 16421 % 16 and 10277 % 16 and 10277 % 64
+    # a low batch rate: the one-wave K0 at every size, so the lane = stream form is met at 48 kHz only
+    assert {f[1] for c, v in full.items() if c[2] != 48000 for f in v} == {"rn_hp_one_kernel"}
+    assert {f[3] for v in lists.values() for f in v} == {"rn_nn_one_kernel", "rn_nn_mfma16_kernel", "rn_nn_mfma_kernel"}
+
+
+def _first_difference(good, bad, M):
+    """where two chunk expectations part: (positions whose returned samples differ, the first (push, position) in push order)"""
+    s = sm.chunk_schedule(M)
+    total = s["cum"][-1]
+    ne = (good["y"] != bad["y"]) & (np.arange(good["y"].shape[1])[None] < total[:, None])
+    pos = np.flatnonzero(ne.any(1))
+    if not len(pos):
+        return pos, None
+    first = np.array([np.flatnonzero(ne[p])[0] for p in pos])
+    push = np.array([np.searchsorted(s["cum"][:, p], t, side="right") - 1 for p, t in zip(pos, first)])
+    i = int(np.argmin(push))
+    return pos, (int(push[i]), int(pos[i]))
+
+
+# (variant the mutant is run on, the rule of the schedule that makes it differ)
+_CHUNK_TEETH = {
+    "no_delay": ((48000, "float"), "the tail tops every position up to T M samples, so all of z but its last frame is returned: z and "
+                                   "0^M ++ z differ wherever a live signal is not periodic in M"),
+    "reset_keeps_pending": ((48000, "int16"), "before push CHUNK_RESET_BEFORE every RESET position holds pending samples (fill != 0), so "
+                                              "frames cut with them start `fill` samples early"),
+    "reset_keeps_history": ((16000, "int16"), "RESET's positions are reset after completed frames of live signal, at a batch rate that "
+                                              "has resampler histories to zero"),
+    "frames_late": ((32000, "float"), "every position completes frames in many pushes; frames cut at x[1 + j M] differ from those at x[j M]"),
+    "cast_before_down": ((16000, "int16"), "an int16 case runs at a low batch rate (CHUNK_CASES), where the down-resampler stands between "
+                                           "the denoiser's float output and the cast"),
+    "list_advances_unlisted": ((48000, "float"), "every list push leaves a fifth of the positions unlisted (and SPECIAL's never-listed one "
+                                                 "always): advancing them changes every frame they complete later"),
+}
+
+
+@pytest.mark.parametrize("mutant", sm.CHUNK_MUTANTS)
+def test_the_chunk_expectation_catches_a_wrong_one(mutant):
+    """six wrong expectations, each of which must differ from the true one in the samples some push returns to some position"""
+    (hz, typ), rule = _CHUNK_TEETH[mutant]
+    M = sm.chunk_frame(hz)
+    s = sm.chunk_schedule(M)
+    good, bad = _chunked(hz, typ), _chunked(hz, typ, mutant)
+    pos, first = _first_difference(good, bad, M)
+    assert first is not None, f"{mutant}: the expectation does not change ({rule})"
+    print(f"{mutant} ({hz} Hz {typ}): caught on {len(pos)} of {sm.B} positions, first in push {first[0]} at position {first[1]} -- {rule}")
+    lab = sm.labels()[0]
+    live = np.array([lab[p] not in ("all_zero",) for p in range(sm.B)])
+    if mutant in ("reset_keeps_pending", "reset_keeps_history"):
+        assert set(pos.tolist()) <= set(sm.RESET) and first[0] >= sm.CHUNK_RESET_BEFORE and len(pos) >= len(sm.RESET) - 3, (len(pos), first)
+    elif mutant == "list_advances_unlisted":
+        unlisted = np.flatnonzero((~s["listed"]).any(0))
+        assert set(pos.tolist()) <= set(unlisted.tolist()) and len(pos) >= 0.9 * len(unlisted), (len(pos), len(unlisted))
+        assert sm.SPECIAL["never"] in pos and first[0] <= min(q for q, p in enumerate(sm.CHUNK_PUSHES) if p["form"] == "list") + 3
+    else:
+        assert len(pos) >= 0.9 * live.sum(), len(pos)
+
+
+def test_the_chunk_expectation_is_the_fifo_model_on_the_oracles_frames():
+    """on 7 positions -- the never-listed one, the one in every other list push, two of RESET, the block's first and last -- the closed
+    form equals the numpy deques of tests/test_chunks_gpu.py (Fifos) driven push by push with the oracle's frames: samples returned,
+    frames completed, fills, vad and gains"""
+    from conftest import assert_bits_equal
+    from oracle.binding import Oracle
+    from test_chunks_gpu import Fifos                                         # (lazily: its module carries the gpu mark)
+    hz, typ, M = 48000, "float", 480
+    s, exp = sm.chunk_schedule(M), _chunked(hz, typ)
+    pos = [sm.SPECIAL["never"], sm.SPECIAL["alternating"], sm.RESET[0], sm.RESET[-1], 0, 1, sm.B - 1]
+    blob = load_blob("default")
+    fifos, oracles = Fifos(len(pos), M), [Oracle(blob) for _ in pos]
+    done = np.zeros(len(pos), int)
+    for q in range(len(sm.CHUNK_PUSHES)):
+        if q == sm.CHUNK_RESET_BEFORE:
+            hit = [i for i, p in enumerate(pos) if p in sm.RESET]
+            fifos.restart(hit)
+            for i in hit:
+                oracles[i] = Oracle(blob)
+        counts, mc, F = s["counts"][q][pos], int(s["max_count"][q]), int(s["F"][q])
+        rows = np.full((len(pos), mc), np.nan, np.float32)
+        for i, p in enumerate(pos):
+            rows[i, :counts[i]] = exp["x"][p, s["cum"][q, p]:s["cum"][q + 1, p]]
+        frames, mask, k = fifos.push(rows, counts, F)
+        ref = np.zeros_like(frames)
+        for i, p in enumerate(pos):
+            if k[i]:
+                r = oracles[i].run(frames[:k[i], i])
+                ref[:k[i], i] = r["out"]
+                assert_bits_equal(exp["vad"][p, done[i]:done[i] + k[i]], r["vad"], f"push {q} position {p}: vad")
+                assert_bits_equal(exp["gains"][p, done[i]:done[i] + k[i]], r["gains"], f"push {q} position {p}: gains")
+            assert done[i] == s["done"][q, p]
+            done[i] += k[i]
+        want = fifos.pop(ref, k, counts)
+        assert (k == s["k"][q][pos]).all() and (fifos.fill() == s["fill_after"][q][pos]).all(), q
+        for i, p in enumerate(pos):
+            assert_bits_equal(exp["y"][p, s["cum"][q, p]:s["cum"][q + 1, p]], want[i], f"push {q} position {p}: the samples returned")
+        if q + 1 == sm.CHUNK_MOVE_BEFORE:                                     # the FIFO records at the move are the deques' contents
+            rec = sm.chunk_records(exp, M, q + 1)
+            for i, p in enumerate(pos):
+                f = int(s["fill"][q + 1, p])
+                assert_bits_equal(rec[p, :f].view(np.float32), fifos.inq[i], f"position {p}: pending samples at the move")
+                assert_bits_equal(rec[p, 480:480 + M - f].view(np.float32), fifos.outq[i], f"position {p}: output FIFO at the move")
+                assert not rec[p, f:480].any() and not rec[p, 480 + M - f:960].any() and rec[p, 960:].tolist() == [f, M, 0x464B4301, 0]
+                assert_bits_equal(exp["move_state"][p], oracles[i].get_state(), f"position {p}: state at the move")
+    for i, p in enumerate(pos):
+        assert_bits_equal(exp["state"][p], oracles[i].get_state(), f"position {p}: final state")
+        assert done[i] == s["done"][-1, p]
+
+
+def test_the_int16_and_low_rate_chunk_expectations_are_their_chains():
+    """what the 48 kHz float model above does not reach: the int16 expectation is the float chain on the rounded input followed by the
+    truncating cast, and a low-rate one the same chain between resample.up and resample.down, restarted with the reset"""
+    from rnnoise_amd import resample
+    from oracle.binding import Oracle
+    blob = load_blob("default")
+    for hz, typ in sm.CHUNK_VARIANTS:
+        M, L = sm.chunk_frame(hz), resample.RATES[hz]
+        s, exp = sm.chunk_schedule(M), _chunked(hz, typ)
+        assert exp["x"].dtype == (np.float32 if typ == "float" else np.int16) and exp["y"].dtype == exp["x"].dtype
+        assert (exp["y"] == (exp["yf"] if typ == "float" else resample.to_s16(exp["yf"]))).all()
+        assert not exp["yf"][:, :M].any()
+        for p in (2, sm.RESET[3]):
+            x = exp["x"][p].astype(np.float32)
+            c = int(s["base"][-1, p])
+            parts = []
+            for a, b in (((0, c // M * M), (c, int(s["total"][p]))) if c else ((0, sm.T * M),)):
+                o = Oracle(blob)
+                v = x[a:b] if L == 1 else resample.up(x[a:b], L)
+                out = o.run(v.reshape(-1, 480))["out"].reshape(-1)
+                parts.append(out if L == 1 else resample.down(out, L))
+            want = np.concatenate([np.zeros(M, np.float32), parts[0]])
+            if c:
+                want = np.concatenate([want[:c], np.zeros(M, np.float32), parts[1]])
+            n = int(s["total"][p])
+            assert (exp["yf"][p, :n].view(np.uint32) == want[:n].view(np.uint32)).all(), (hz, typ, p)
+            assert (exp["state"][p].view(np.uint32) == o.get_state().view(np.uint32)).all(), (hz, typ, p)
