@@ -61,7 +61,9 @@
 #define RN_SNAP_OFF_MAGIC RN_STATE_FLOATS                   /* RN_SNAP_MAGIC; 0: an empty record   */
 #define RN_SNAP_OFF_L (RN_SNAP_OFF_MAGIC + 1)               /* PCM-rate code of the history: 1, 2, 3 or 6 (48000 / rate), 32 at 32 kHz */
 #define RN_SNAP_OFF_GATE (RN_SNAP_OFF_MAGIC + 2)            /* gate counter, 0..65536 (65536: no voice frame yet, or no control table) */
-#define RN_SNAP_OFF_RESERVED (RN_SNAP_OFF_MAGIC + 3)        /* 3 words: written as 0, ignored on load */
+#define RN_SNAP_OFF_RESERVED (RN_SNAP_OFF_MAGIC + 3)        /* 3 words; the first is RN_SNAP_OFF_OUT_L, the others written as 0, ignored on load */
+#define RN_SNAP_OFF_OUT_L RN_SNAP_OFF_RESERVED              /* PCM-rate code of the DOWN half of the history where the batch had an out-rate
+                                                             * table (rnnoise_batch_set_stream_out_rates); 0: the code of RN_SNAP_OFF_L */
 #define RN_SNAP_OFF_HIST (RN_SNAP_OFF_MAGIC + 6)            /* 6288: resampler history, zeros at 48 kHz; at 32 kHz 47 floats at [0, 47), 70 at [48, 118) */
 #define RN_SNAP_HIST_FLOATS 336
 #define RN_SNAP_FLOATS (RN_SNAP_OFF_HIST + RN_SNAP_HIST_FLOATS)  /* 6624 words = 26,496 B */

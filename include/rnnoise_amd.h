@@ -239,6 +239,54 @@ RNNOISE_EXPORT int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsig
 RNNOISE_EXPORT int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream);
 RNNOISE_EXPORT int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *formats);
 
+/* Per-stream OUTPUT rates and formats: legs that leave in another shape than they came in -- 48 kHz linear in and 8 kHz mu-law out
+ * towards the PSTN, G.711 in and 16 kHz linear out towards a recogniser.  The two tables above describe a stream's `in` and `out`
+ * rows with one entry; these two describe the `out` rows alone, with the same codes: rates[n_streams] of 1, 2, 3, 6 or
+ * RNNOISE_AMD_RATE_32K, formats[n_streams] of RNNOISE_AMD_PCM_LINEAR / _ULAW / _ALAW.
+ * WITHOUT an out table a stream's output code is its input code -- its entry of the rate table, or the batch's code Lb without one;
+ * the same for formats -- and the batch launches exactly what it launched before these calls existed.  WITH one, stream s's `out`
+ * rows are written at the out table's code L_out (format F_out) whatever its input code L_in (F_in) is.
+ * Rows: the ROW PITCH stays that of the batch's rate, M_b samples, in `in` and in `out`.  Stream s reads the first M_in samples (a
+ * companded stream: bytes) of its `in` row and writes the first M_out samples (bytes) of its `out` row; the rest of either row is
+ * neither read nor written.  So an out code must be a code with M_out <= M_b, the rule of the rate table.
+ * Result, bit for bit: the stream's vad, gains and DenoiseState are those of the same stream in a uniform batch at L_in and F_in; its
+ * output is Down(L_out) of the 48 kHz denoised signal -- the 48 kHz signal itself, written in place, for L_out = 1 --, in the _s16
+ * calls followed by the truncating cast and then F_out's encoder.  rnnoise_amd/resample.py (Up, Down) and rnnoise_amd/g711.py define
+ * every stage.  The delay is the sum of the two stages' delays, Up(L_in)'s in input samples plus Down(L_out)'s in 48 kHz samples; for
+ * L_in != L_out it is in general no whole number of output samples, and there is no call that reports it.  Float calls ignore both
+ * format tables.
+ * Histories: the up half of a stream's resampler history belongs to L_in, the down half to L_out.
+ * rnnoise_batch_set_stream_out_rates (host array): synchronous; -1 and no change if any entry is no code or has M_out > M_b.  The DOWN
+ * half of exactly the streams whose effective output code changes is zeroed; the up half and every DenoiseState stay.  NULL drops the
+ * table (the down half of the streams whose output code thereby changes is zeroed).  While an out-rate table is set,
+ * rnnoise_batch_set_stream_rates zeroes only the UP half of the streams whose input code changes; without one it does what it did.
+ * rnnoise_batch_set_stream_out_rates_device (n_streams bytes in the batch's device memory): a copy ordered on hip_stream, no kernel,
+ * no check, no history touched (the rules of rnnoise_batch_set_stream_rates_device).  K3 reads this table where it would read the
+ * rate table, with that table's rule: a byte that is no code, or has M_out > M_b, reads as the batch's code Lb -- which is the
+ * stream's input code wherever the rate table does not say otherwise.
+ * rnnoise_batch_set_stream_out_formats[_device]: configuration like the format table; nothing is zeroed; -1 for an entry above 2 (host),
+ * anything that is not 1 or 2 reads as linear (device).
+ * rnnoise_batch_stream_out_rates / _out_formats read the codes back as K3 reads them (synchronous): without an out table, what
+ * rnnoise_batch_stream_rates / _formats answer.
+ * rnnoise_batch_set_pcm_rate drops both out tables along with the rate table.  rnnoise_batch_reset, reset_streams[_device] and
+ * import_state zero both halves of the history and leave the tables alone.  A slot recycled for another leg: the device setters of
+ * the tables that change + reset_streams_device, on one stream.
+ * Snapshots: save writes the output code beside the stream's own code while the batch has an out-rate table (0 otherwise: a record
+ * of a batch without one is what it was); load copies the up half when the record's code is the destination stream's input code and
+ * the down half when the record's output code (0: its code) is the destination's effective output code, and zeroes a half otherwise.
+ * Works with every call form (lock-step, masked, list; float and int16; host and device), model slots, controls, linked gains, PCM
+ * layouts and channels; the channel rule holds per side: within a group all outputs are linear or all are companded.  Host-buffer
+ * calls with an out table take the staged convenience path.  Chunk calls return -1 with nothing launched while either out table is
+ * set; rnnoise_batch_train_features* returns -1 while an out-rate table is set and ignores the out-format table.
+ * K0 never reads an out table: a batch whose inputs are all 48 kHz linear keeps the lane-per-stream K0 above 2,048 streams whatever
+ * its outputs are.  0 / -1; a NULL batch or buffer returns -1 without touching the device. */
+RNNOISE_EXPORT int rnnoise_batch_set_stream_out_rates(RNNoiseBatch *b, const unsigned char *rates);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_out_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_stream_out_rates(RNNoiseBatch *b, unsigned char *rates);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_out_formats(RNNoiseBatch *b, const unsigned char *formats);
+RNNOISE_EXPORT int rnnoise_batch_set_stream_out_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_stream_out_formats(RNNoiseBatch *b, unsigned char *formats);
+
 /* Caller-defined PCM strides: where the frames of `in` and `out` lie.  By default every rnnoise_batch_process* call takes PCM as
  * [n_frames][n_rows][M], M = 480 / Lb samples (Lb the batch's divisor; n_rows = n_streams, or the list length of a list call): frame f
  * of row r starts at sample (f * n_rows + r) * M.  With a layout set it starts at
@@ -403,7 +451,8 @@ RNNOISE_EXPORT int rnnoise_batch_import_state(RNNoiseBatch *b, int stream, const
  * compact or grow a batch, to checkpoint.  A snapshot is RNNOISE_AMD_SNAP_FLOATS 32-bit words (rn_layout.h: RN_SNAP_*): the
  * portable state exactly as rnnoise_batch_export_state writes it (a snapshot's first RN_STATE_FLOATS words can be handed to
  * import_state or the reference unchanged), a header of int32 words -- magic / version, the PCM-rate divisor L = 48000 / rate the
- * history belongs to, the VAD-gate counter (65536 without a control table), three reserved zeros -- and the 336 floats of
+ * history belongs to, the VAD-gate counter (65536 without a control table), the code of the history's down half where the batch has an out-rate
+ * table (0 without one: the same L), two reserved zeros -- and the 336 floats of
  * resampler history (zeros at 48 kHz).  It holds state, not configuration: the stream's model slot, its controls record, the
  * batch's rate and network path have their own setters and are set on the destination by the caller; frame phase never appears.
  * snap is [n][RNNOISE_AMD_SNAP_FLOATS], indexed by list position; streams[i] is the batch stream of row i, in any order.
@@ -458,8 +507,8 @@ RNNOISE_EXPORT int rnnoise_batch_load_streams(RNNoiseBatch *b, const float *snap
  * synchronises with the device.  Host forms: the convenience path -- synchronous, plain copies; a count out of range returns -1 with
  * nothing changed.  max_count == 0 is a successful no-op; max_count < 0, a NULL batch or NULL counts / in / out return -1.
  * Works with every batch rate (rnnoise_batch_set_pcm_rate), float and int16, model slots, stream controls and
- * rnnoise_batch_reset_streams[_device].  Returns -1 with nothing launched while the batch has a rate table, a format table, a PCM
- * layout, channels > 1 or a gain link > 1.  The first chunk call switches the batch to per-stream frame phase, as the first masked
+ * rnnoise_batch_reset_streams[_device].  Returns -1 with nothing launched while the batch has a rate table, a format table, an out-rate or
+ * out-format table, a PCM layout, channels > 1 or a gain link > 1.  The first chunk call switches the batch to per-stream frame phase, as the first masked
  * call does.  rnnoise_batch_reset, rnnoise_batch_reset_streams[_device], rnnoise_batch_import_state and
  * rnnoise_batch_load_streams[_device] restart the FIFOs of the streams they touch, rnnoise_batch_set_pcm_rate those of every stream.
  * Snapshots do not carry FIFO contents (RNNOISE_AMD_SNAP_FLOATS and the record stay): move a stream at a frame boundary --

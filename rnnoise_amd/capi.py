@@ -27,6 +27,7 @@ SNAP_OFF_MAGIC = STATE_FLOATS
 SNAP_OFF_L = SNAP_OFF_MAGIC + 1
 SNAP_OFF_GATE = SNAP_OFF_MAGIC + 2
 SNAP_OFF_RESERVED = SNAP_OFF_MAGIC + 3
+SNAP_OFF_OUT_L = SNAP_OFF_RESERVED  # RN_SNAP_OFF_OUT_L: the code of the down history under an out-rate table, 0 without one
 SNAP_OFF_HIST = SNAP_OFF_MAGIC + 6
 SNAP_HIST_FLOATS = 336
 SNAP_FLOATS = SNAP_OFF_HIST + SNAP_HIST_FLOATS  # 6624
@@ -67,6 +68,8 @@ EXPORTS = [
     "rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device", "rnnoise_batch_save_streams", "rnnoise_batch_load_streams",
     "rnnoise_batch_set_stream_rates", "rnnoise_batch_set_stream_rates_device", "rnnoise_batch_stream_rates",
     "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
+    "rnnoise_batch_set_stream_out_rates", "rnnoise_batch_set_stream_out_rates_device", "rnnoise_batch_stream_out_rates",
+    "rnnoise_batch_set_stream_out_formats", "rnnoise_batch_set_stream_out_formats_device", "rnnoise_batch_stream_out_formats",
     "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
     "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
     "rnnoise_batch_set_gain_link", "rnnoise_batch_gain_link",
@@ -240,7 +243,7 @@ def _load(path, debug):
         L.rnnoise_amd_chunk_frames.argtypes = [C.c_int, C.c_int]
         L.rnnoise_batch_chunk_fill.argtypes = [vp, ip]
         # the per-stream tables: host setter, device setter (table, stream), getter
-        for name, tp in (("rates", up), ("formats", up), ("models", up), ("controls", fp)):
+        for name, tp in (("rates", up), ("formats", up), ("out_rates", up), ("out_formats", up), ("models", up), ("controls", fp)):
             getattr(L, f"rnnoise_batch_set_stream_{name}").argtypes = [vp, tp]
             getattr(L, f"rnnoise_batch_set_stream_{name}_device").argtypes = [vp, vp, vp]
             getattr(L, f"rnnoise_batch_stream_{name}").argtypes = [vp, tp]
@@ -655,6 +658,57 @@ class Batch:
         """the format code of every stream as the kernels read it, (N,) uint8 (synchronous; zeros without a table)"""
         f = np.empty(self.n, np.uint8)
         self._call("rnnoise_batch_stream_formats", f.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        return f
+
+    def set_stream_out_rates(self, hz):
+        """the rate every stream's OUTPUT rows are written at, in Hz (rnnoise_batch_set_stream_out_rates): (N,) values out of
+        PCM_RATES_ALL, none above the batch's own rate, or None to drop the table (every stream then leaves at the rate it came in
+        at).  A stream reads the first 480 * rate_in // 48000 samples of its `in` row and writes the first 480 * rate_out // 48000 of
+        its `out` row.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose output rate changes
+        restart their down-resampling filter from zero; every stream keeps its DenoiseState and its up-resampling filter."""
+        if hz is None:
+            return self._call("rnnoise_batch_set_stream_out_rates", None)
+        hz = np.asarray(hz).reshape(-1)
+        assert hz.size == self.n
+        if not np.isin(hz, PCM_RATES_ALL).all():
+            raise ValueError(f"stream rate unsupported (each one of {PCM_RATES_ALL})")
+        if hz.max(initial=0) > self.pcm_rate:
+            raise ValueError(f"a stream rate above the batch's PCM rate {self.pcm_rate}: its frame would not fit its row")
+        L = np.ascontiguousarray(rate_code(hz), np.uint8)
+        self._call("rnnoise_batch_set_stream_out_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
+
+    def set_stream_out_rates_device(self, d_rates: int, stream: int = 0):
+        """the same from N bytes of device memory holding the rate CODES, a copy ordered on `stream`; any other byte, or a rate above
+        the batch's, reads as the batch's rate.  Histories are not touched (set_stream_rates_device)."""
+        self._call("rnnoise_batch_set_stream_out_rates_device", d_rates or None, stream or None)
+
+    def stream_out_rates(self) -> np.ndarray:
+        """the rate every stream's output is written at in Hz, (N,) int32 (synchronous; stream_rates() without an out table)"""
+        L = np.empty(self.n, np.uint8)
+        self._call("rnnoise_batch_stream_out_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        return code_rate(L).astype(np.int32)
+
+    def set_stream_out_formats(self, formats):
+        """the PCM format of every stream's OUTPUT rows in the int16 calls (rnnoise_batch_set_stream_out_formats): as
+        set_stream_formats, which then describes the `in` rows alone; None drops the table (output format = input format)."""
+        if formats is None:
+            return self._call("rnnoise_batch_set_stream_out_formats", None)
+        from . import g711
+        if isinstance(formats, np.ndarray) and formats.dtype.kind in "iu":
+            formats = formats.reshape(-1).tolist()
+        codes = np.array([g711.code(f) for f in formats], np.uint8)
+        assert codes.size == self.n
+        self._call("rnnoise_batch_set_stream_out_formats", codes.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
+
+    def set_stream_out_formats_device(self, d_formats: int, stream: int = 0):
+        """the same from N bytes of device memory holding the CODES (0 s16, 1 ulaw, 2 alaw), a copy ordered on `stream`; any other
+        byte reads as s16"""
+        self._call("rnnoise_batch_set_stream_out_formats_device", d_formats or None, stream or None)
+
+    def stream_out_formats(self) -> np.ndarray:
+        """the format code of every stream's output rows as K3 reads it, (N,) uint8 (synchronous; stream_formats() without an out table)"""
+        f = np.empty(self.n, np.uint8)
+        self._call("rnnoise_batch_stream_out_formats", f.ctypes.data_as(C.POINTER(C.c_ubyte)))
         return f
 
     def process(self, pcm: np.ndarray, want_gains: bool = True, out: np.ndarray | None = None):

@@ -15,6 +15,8 @@ batch; a stream whose file has ended is fed zeros and produces no more output.
 (rnnoise_batch_set_stream_rates), every file read and written at its own rate.
 --formats s16,ulaw,alaw gives every file its own sample format (one per input): a G.711 file is raw companded bytes, one per sample
 (the .ul / .al convention), expanded and compressed on the device (rnnoise_batch_set_stream_formats); its output is written the same way.
+--out-rate HZ and --out-format s16|ulaw|alaw write every file at another rate or in another format than it was read in (at most
+--rate): the legs leave the batch in that shape (rnnoise_batch_set_stream_out_rates, _out_formats), and a WAV output's header says so.
 An input that starts with RIFF....WAVE is read as a WAV file (rnnoise_amd/wav.py: PCM16, A-law or mu-law, 1 to 8 channels, 8 to 48 kHz):
 its rate, format and channel count come from its header, each channel is one stream, its samples cross the batch interleaved as they lie
 in the file (rnnoise_batch_set_pcm_channels), and the output is <name>.denoised.wav with the input's header fields.
@@ -57,9 +59,15 @@ def _describe(path, rate, fmt):
                 size=os.path.getsize(path))
 
 
+def out_info(info: wav.WavInfo, out_rate=None, out_format=None) -> wav.WavInfo:
+    """the header fields of the output of a WAV input under --out-rate / --out-format: the input's, with the rate and the format
+    replaced where one is given"""
+    return info._replace(rate=out_rate or info.rate, codec=out_format or info.codec)
+
+
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
                   vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None,
-                  formats=None, link_channels: bool = False):
+                  formats=None, link_channels: bool = False, out_rate=None, out_format=None):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 32000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
@@ -71,7 +79,9 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     count, every channel is one stream, and its samples go through the batch interleaved as they lie in the file
     (capi.Batch.set_pcm_channels) into <name>.denoised.wav under the input's header fields.  The inputs are grouped by channel count,
     one batch per distinct count (a RAW file is mono).  link_channels: the channels of each multichannel file form one link group
-    (capi.Batch.set_gain_link with the file's channel count).  Returns the frames of every input."""
+    (capi.Batch.set_gain_link with the file's channel count).  out_rate / out_format: the rate (at most `rate`) and the format every
+    output is written in where it is not the input's (capi.Batch.set_stream_out_rates, set_stream_out_formats); a frame then has
+    480 * out_rate // 48000 samples on the way out.  Returns the frames of every input."""
     os.makedirs(out_dir, exist_ok=True)
     if rates is not None and len(rates) != len(inputs):
         raise ValueError(f"{len(rates)} rates for {len(inputs)} files")
@@ -84,19 +94,26 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
             raise ValueError(f"{d['path']}: {d['rate']} Hz is above the batch's rate {rate} (--rate)")
         d["frame"] = capi.FRAME * d["rate"] // 48000  # samples per 10 ms and channel
         d["n_frames"] = d["size"] // (d["width"] * d["channels"]) // d["frame"]  # partial tail dropped (rnnoise_demo.c:55)
+        # the way out: the input's rate and format unless --out-rate / --out-format say otherwise
+        d["out_rate"], d["out_codec"] = out_rate or d["rate"], out_format or d["codec"]
+        if d["out_rate"] > rate:
+            raise ValueError(f"{d['path']}: output at {d['out_rate']} Hz is above the batch's rate {rate} (--rate)")
+        d["out_frame"] = capi.FRAME * d["out_rate"] // 48000
+        d["out_width"] = 1 if g711.code(d["out_codec"]) else 2
     groups = {}
     for d in files:
         groups.setdefault(d["channels"], []).append(d)
     model = capi.Model(model_blob)
     for channels, group in groups.items():
         _denoise_group(model, group, channels, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold,
-                       rate_table=rates is not None, format_table=formats is not None, link=link_channels)
+                       rate_table=rates is not None, format_table=formats is not None, link=link_channels,
+                       out_tables=out_rate is not None or out_format is not None)
     model.close()
     return [d["n_frames"] for d in files]
 
 
 def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold, rate_table,
-                   format_table, link=False):
+                   format_table, link=False, out_tables=False):
     """the files of one channel count C through one batch of len(files) * C streams: file g's channel c is stream g * C + c"""
     FRAME = capi.FRAME * rate // 48000
     G, N = len(files), len(files) * C
@@ -111,6 +128,10 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
         batch.set_stream_rates([d["rate"] for d in files for _ in range(C)])
     if format_table or any(w == 1 for w in width):
         batch.set_stream_formats([d["codec"] for d in files for _ in range(C)])
+    if out_tables:  # (both, so that each side is described by its own pair of tables)
+        batch.set_stream_out_rates([d["out_rate"] for d in files for _ in range(C)])
+        batch.set_stream_out_formats([d["out_codec"] for d in files for _ in range(C)])
+    out_frame_of, out_width = [d["out_frame"] for d in files], [d["out_width"] for d in files]
     if atten_limit_db is not None or vad_gate or vad_hold:
         batch.set_stream_controls(capi.controls_table(N, atten_limit_db, vad_gate, vad_hold))
     if C > 1:
@@ -123,8 +144,9 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
     for d, f, o in zip(files, ins, outs):
         f.seek(d["offset"])
         if d["wav"]:  # (the first output frame is dropped, as for a RAW file: the length is known up front)
-            d["out_bytes"] = max(d["n_frames"] - 1, 0) * d["frame"] * d["wav"].block
-            o.write(wav.header(d["wav"], d["out_bytes"]))
+            oi = out_info(d["wav"], d["out_rate"], d["out_codec"])
+            d["out_bytes"] = max(d["n_frames"] - 1, 0) * d["out_frame"] * oi.block
+            o.write(wav.header(oi, d["out_bytes"]))
     vfs = [open(os.path.join(out_dir, os.path.basename(d["path"]) + ".vad.csv"), "w") for d in files] if vad_csv else None
     # every file's chunk is ONE contiguous run of the staging buffer, [G][chunk frames * FRAME * C], which the batch reads and writes
     # where it lies (capi.Batch.set_pcm_layout: frames FRAME * C apart, files a whole chunk apart) -- no interleaving into frame-major
@@ -159,10 +181,10 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
         for s in range(G):
             k = max(0, min(tn, n_frames[s] - t0))
             first = 1 if t0 == 0 else 0  # the demo drops the first output frame (rnnoise_demo.c:59-60)
-            if k > first and width[s] == 1:
-                outs[s].write(rows8(out)[first:k, s, :frame_of[s] * C].tobytes())
+            if k > first and out_width[s] == 1:
+                outs[s].write(rows8(out)[first:k, s, :out_frame_of[s] * C].tobytes())
             elif k > first:
-                outs[s].write(out[first:k, s, :frame_of[s] * C].tobytes())  # (the demo's truncating (short) cast was done on the device)
+                outs[s].write(out[first:k, s, :out_frame_of[s] * C].tobytes())  # (the demo's truncating (short) cast was done on the device)
             if vfs and k:  # (one column per channel)
                 vfs[s].write("".join(",".join(f"{v:.6f}" for v in row) + "\n" for row in vad[:k, s * C:(s + 1) * C]))
     for d, o in zip(files, outs):
@@ -218,6 +240,10 @@ def main(argv=None):
                    help="comma list, one sample rate per input file, each at most --rate: a mixed-rate batch")
     p.add_argument("--formats", type=lambda v: v.split(","), default=None,
                    help="comma list, one of s16 | ulaw | alaw per input file: G.711 files are raw bytes, one per sample")
+    p.add_argument("--out-rate", type=int, default=None, choices=capi.PCM_RATES_ALL,
+                   help="sample rate every output is written at, at most --rate (default: each input's own)")
+    p.add_argument("--out-format", default=None, choices=("s16", "ulaw", "alaw"),
+                   help="sample format every output is written in (default: each input's own)")
     p.add_argument("--atten-limit-db", type=float, default=None,
                    help="attenuation limit in dB: no band is suppressed by more (a floor on the band gains); default none")
     p.add_argument("--vad-gate", type=float, default=0.0, help="VAD threshold in [0, 1] below which output is muted (0: no gate)")
@@ -248,7 +274,7 @@ def main(argv=None):
         print(f"wrote {a.count} sequences, {n} records")
         return
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
-                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels)
+                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels, a.out_rate, a.out_format)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

@@ -169,6 +169,8 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->rs_buf) hipFree(b->rs_buf);
   if (b->rate_map) hipFree(b->rate_map);
   if (b->fmt_map) hipFree(b->fmt_map);
+  if (b->out_rate_map) hipFree(b->out_rate_map);
+  if (b->out_fmt_map) hipFree(b->out_fmt_map);
   if (b->model_map) hipFree(b->model_map);
   if (b->ctl_buf) hipFree(b->ctl_buf);
   if (b->train_mix_buf) hipFree(b->train_mix_buf);
@@ -299,7 +301,13 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
   shape.listed = listed;
   shape.companded = s16 && b->g.pcm_fmt != nullptr;  // (float calls never look at the format table)
   shape.channels = chan;
+  // output tables (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates): the fields above are then the input side, what K0
+  // reads, and these the output side, what K3 writes through its own copy of the group (shim.h: batch_k3_group)
+  shape.split = b->out_Ls || b->out_fmt;
+  shape.out_low_rate = shape.low_rate || b->out_Ls;
+  shape.out_companded = s16 && (b->out_fmt || b->g.pcm_fmt);
   const RnPlan plan = rn_plan(rn_knobs(), shape);
+  if (plan.k3_rs != (b->g.rs_L != 0 || b->out_Ls != nullptr)) return -1;  // (the launcher tells the epilogue by its group's rs_L: batch_k3_group)
   // the two side streams at normal queue priority (the caller's stream, which carries network + synthesis, is whatever the caller
   // made it: normal for torch's)
   if (side_k1 && !b->side) HIP_OK(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, 0));
@@ -423,7 +431,8 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
       TimedLaunch t(b, 2);
       b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
       g.link = link > 1 ? link : 0;  // (rn_dev.h: RnGroupDev::link -- K3's copy alone; 0: today's launch)
-      HIP_OK(rn_launch_synthesis(&g, &b->tb, d_out + buf(f) * fstep, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
+      const RnGroupDev g3 = batch_k3_group(b, g);  // (... with the effective output tables; without out tables g itself)
+      HIP_OK(rn_launch_synthesis(&g3, &b->tb, d_out + buf(f) * fstep, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
     }
     if (hk && hk->after_k3(f, st)) return -1;
     // (schedule 1: the high-pass three frames ahead goes out HERE, behind the synthesis launch whose end it starts at)
@@ -509,8 +518,8 @@ int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c) {
                        .n_rows = c.list ? c.n_rows : 0, .packed = true};  // the same call on the staged copies, on the null stream
   if (pcm_copy(d.at<char>(o_in), c.in, true)) return -1;
   // `out` goes up too where the device leaves parts of it alone: absent rows, the part of a row behind the frame of a stream of a
-  // rate table or behind a companded stream's bytes keep the caller's values
-  if ((c.active || c.list || b->g.rs_Ls || (c.s16 && b->g.pcm_fmt)) && pcm_copy(dc.out, c.out, true)) return -1;
+  // rate table or an out-rate table, or behind a companded stream's bytes, keep the caller's values
+  if ((c.active || c.list || b->g.rs_Ls || b->out_Ls || (c.s16 && (b->g.pcm_fmt || b->out_fmt))) && pcm_copy(dc.out, c.out, true)) return -1;
   if (c.active) HIP_OK(hipMemcpy(d.at<uint8_t>(o_act), c.active, fs, hipMemcpyHostToDevice));
   if (c.list) HIP_OK(hipMemcpy(d.at<int>(o_list), c.list, rows * sizeof(int), hipMemcpyHostToDevice));
   if (batch_process_device_impl(b, dc)) return -1;
@@ -602,8 +611,11 @@ int batch_chunk_fifos_ready(RNNoiseBatch *b, hipStream_t st) {
 }
 
 namespace {
-// what a chunk call does not combine with (include/rnnoise_amd.h): per-stream rates and formats, a PCM layout, channels, linked gains
-bool chunk_refused(const RNNoiseBatch *b) { return b->g.rs_Ls || b->g.pcm_fmt || b->row_stride || b->channels > 1 || b->link > 1; }
+// what a chunk call does not combine with (include/rnnoise_amd.h): per-stream rates and formats, on the input or on the output side,
+// a PCM layout, channels, linked gains
+bool chunk_refused(const RNNoiseBatch *b) {
+  return b->g.rs_Ls || b->g.pcm_fmt || b->out_Ls || b->out_fmt || b->row_stride || b->channels > 1 || b->link > 1;
+}
 // The FIFOs, on the first chunk call (their first state written on st, ahead of the call), and a staging buffer for F frames of
 // `rows` rows with their mask behind them: frames of RN_FRAME_SIZE floats whatever the rate, so that a rate change keeps it.  It is
 // sized in bytes and shared by the full-size and the list form: a call that fits leaves it alone.  Growing it drains the device first
@@ -763,7 +775,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
                                                    void *hip_stream) {
   if (!b || !d_records || !d_clean || !d_noisy || !d_vad || !d_lowpass || !d_band_lp || !d_noise_free || n_frames < 0)
     return -1;
-  if (b->per_stream || b->g.rs_L || b->row_stride || b->channels > 1) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz, in the default PCM layout, one row per slot, only)
+  if (b->per_stream || b->g.rs_L || b->out_Ls || b->row_stride || b->channels > 1) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz in and out, in the default PCM layout, one row per slot, only)
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
   const size_t N = b->n;
@@ -789,7 +801,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
 extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, const float *clean, const float *noisy,
                                             const float *vad, const int *lowpass, const int *band_lp,
                                             const int *noise_free, int n_frames) {
-  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->row_stride || b->channels > 1)
+  if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->out_Ls || b->row_stride || b->channels > 1)
     return -1;
   ON_DEVICE(b->device);
   const size_t N = b->n, fN = (size_t)n_frames * N, fb = fN * RN_FRAME_SIZE * 4;

@@ -9,7 +9,8 @@ namespace {
 // scatter launch of this file gets the streams' sample FIFOs to restart (shim.h: batch_chunk_fifos)
 int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) {
   const RnChunkDev ck = batch_chunk_fifos(b, 0);
-  HIP_OK(rn_launch_state_zero(&b->g, d_list, n, &ck, st));
+  const RnGroupDev g = batch_state_group(b);  // (both halves of the history restart, a batch with an out-rate table alone included)
+  HIP_OK(rn_launch_state_zero(&g, d_list, n, &ck, st));
   if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, n));
   return 0;
 }
@@ -80,7 +81,7 @@ extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f
   if (stage_ready(b)) return -1;
   HIP_OK(hipMemcpy(b->state_stage, f, RN_STATE_FLOATS * sizeof(float), hipMemcpyHostToDevice));
   b->img_valid = false;
-  const RnGroupDev v = group_view(b->g, s, 1);
+  const RnGroupDev v = group_view(batch_state_group(b), s, 1);
   const RnChunkDev ck = batch_chunk_fifos(b, s);
   HIP_OK(rn_launch_state_scatter(&v, RN_REC_STATE, b->state_stage, nullptr, 1, b->ring_slot, phase_of(b, s), &ck, nullptr));
   HIP_OK(hipStreamSynchronize(nullptr));
@@ -101,14 +102,16 @@ bool snap_args_ok(const RNNoiseBatch *b, const void *snap, const int *streams, i
   return true;
 }
 int save_on(RNNoiseBatch *b, float *d_snap, const int *d_list, int n, hipStream_t st) {
-  HIP_OK(rn_launch_state_gather(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), nullptr, st));
+  const RnGroupDev g = batch_state_group(b);
+  HIP_OK(rn_launch_state_gather(&g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), nullptr, st, b->out_Ls));
   return 0;
 }
 // the listed rows' tiles of the layer-wise network's state images follow the load while they are live (rn_dev.h: act_q), as after
 // a per-stream reset; without a list that is every tile
 int load_on(RNNoiseBatch *b, const float *d_snap, const int *d_list, int n, hipStream_t st) {
   const RnChunkDev ck = batch_chunk_fifos(b, 0);
-  HIP_OK(rn_launch_state_scatter(&b->g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), &ck, st));
+  const RnGroupDev g = batch_state_group(b);
+  HIP_OK(rn_launch_state_scatter(&g, RN_REC_SNAP, d_snap, d_list, n, b->ring_slot, phase_of(b, 0), &ck, st, b->out_Ls));
   if (b->img_valid) HIP_OK(rn_launch_nn_requant(&b->g, st, d_list, d_list ? n : 0));
   return 0;
 }

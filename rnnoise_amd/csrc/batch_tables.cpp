@@ -1,5 +1,6 @@
-// batch_tables.cpp -- the configuration of a batch's calls: PCM rate, strides and channels, and the four per-stream tables (rates,
-// formats, models, controls).  Nothing here launches a kernel: the step (batch.cpp) reads what these calls leave in the batch.
+// batch_tables.cpp -- the configuration of a batch's calls: PCM rate, strides and channels, and the per-stream tables (rates and
+// formats of the input side and of the output side, models, controls).  Nothing here launches a kernel: the step (batch.cpp) reads
+// what these calls leave in the batch.
 #include "shim.h"
 
 // ---- the per-stream tables ----
@@ -81,6 +82,34 @@ void rates_as_read(unsigned char *rates, int n, int Lb) {
   for (int s = 0; s < n; s++)
     if (!rate_code_ok(rates[s], Lb)) rates[s] = (unsigned char)Lb;
 }
+// the [N] codes K0 reads now (input == true: the rate table, or Lb everywhere) or K3 reads now (the out-rate table, else the same);
+// the caller has drained the device
+int codes_now(RNNoiseBatch *b, bool input, std::vector<uint8_t> &cur) {
+  const int Lb = rate_code(b->pcm_rate);
+  const uint8_t *live = !input && b->out_Ls ? b->out_Ls : b->g.rs_Ls;
+  cur.assign((size_t)b->n, (uint8_t)Lb);
+  if (live) {
+    HIP_OK(hipMemcpy(cur.data(), live, (size_t)b->n, hipMemcpyDeviceToHost));
+    rates_as_read(cur.data(), b->n, Lb);
+  }
+  return 0;
+}
+// zero floats [first, first + count) of the history of every stream whose code in cur differs from its code in next: one strided
+// memset per run of such streams, on the null stream
+int restart_changed_halves(RNNoiseBatch *b, const std::vector<uint8_t> &cur, const std::vector<uint8_t> &next, size_t first, size_t count) {
+  const size_t N = b->n;
+  for (size_t s = 0; s < N;) {
+    if (cur[s] == next[s]) {
+      s++;
+      continue;
+    }
+    size_t e = s + 1;
+    while (e < N && cur[e] != next[e]) e++;
+    HIP_OK(hipMemset2DAsync(b->rs_buf + s * RN_RS_HIST + first, RN_RS_HIST * sizeof(float), 0, count * sizeof(float), e - s, nullptr));
+    s = e;
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
@@ -89,7 +118,9 @@ extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
   b->frame_stride = b->row_stride = 0;  // (a PCM layout is in samples of the old rate's frame: dropped by every call)
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());  // (synchronous: nothing of the old rate is in flight)
-  if (hz == old && !b->g.rs_Ls) {  // (a rate table is dropped by every call: the rows are redefined)
+  const bool out_rates = b->out_Ls != nullptr;
+  b->out_Ls = b->out_fmt = nullptr;  // (the out tables go with the rate table: they describe rows of the old rate)
+  if (hz == old && !b->g.rs_Ls && !out_rates) {  // (a rate table is dropped by every call: the rows are redefined)
     if (batch_chunk_restart_all(b)) return -1;  // (... and the sample FIFOs of the chunk calls restart with every call)
     HIP_OK(hipDeviceSynchronize());
     return old;
@@ -130,6 +161,11 @@ extern "C" int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned ch
       rates_as_read(cur.data(), b->n, Lb);
     }
     if (rs_alloc(b, nullptr)) return -1;
+    if (b->out_Ls) {  // (an out-rate table owns the down halves: only the up half follows the input code)
+      std::vector<uint8_t> next(N, (uint8_t)Lb);
+      if (rates) next.assign(rates, rates + N);
+      return restart_changed_halves(b, cur, next, 0, RN_RS_DOWN0);
+    }
     // one memset per run of streams whose divisor changes
     for (size_t s = 0; s < N;) {
       if (cur[s] == (rates ? rates[s] : Lb)) {
@@ -161,6 +197,56 @@ extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates)
   if (!b || !rates) return -1;
   const int Lb = rate_code(b->pcm_rate);
   if (table_get(b, b->g.rs_Ls, 1, rates, Lb)) return -1;
+  rates_as_read(rates, b->n, Lb);
+  return 0;
+}
+
+// ---- per-stream output rates (include/rnnoise_amd.h) ----
+// The [N] code bytes live in out_rate_map; while a table is set (b->out_Ls) the step points K3's copy of the group at it in the place
+// of the rate table (shim.h: batch_k3_group), so that K3 writes every stream at the table's code whatever K0 read it at, and the
+// snapshot kernels get it beside the group (batch_state_group).  b->g is not touched: K0 and the plan's input side stay what they
+// were.  The two halves of a stream's history then belong to two codes: [0, RN_RS_DOWN0) to its input code, the rest to its output
+// code.
+// This table alone: NULL drops the table (nothing to do without one): every stream's output code is its input code again.  A host set
+// allocates rs_buf and restarts from zero the DOWN half of exactly the streams whose effective output code changes.  The device set
+// allocates rs_buf with its zeroing on the caller's stream and leaves the histories to the caller.  An entry that names no rate of
+// this batch reads as the batch's own code, as K3 reads every table -- the getter's answer too; without a table the getter gives the
+// input codes.
+extern "C" int rnnoise_batch_set_stream_out_rates(RNNoiseBatch *b, const unsigned char *rates) {
+  if (!b) return -1;
+  const int Lb = rate_code(b->pcm_rate);
+  if (rates)
+    for (int s = 0; s < b->n; s++)
+      if (!rate_code_ok(rates[s], Lb)) return -1;
+  if (!rates && !b->out_Ls) return 0;
+  ON_DEVICE(b->device);
+  const size_t N = b->n;
+  auto restart_changed = [&]() -> int {
+    std::vector<uint8_t> cur, next;
+    if (codes_now(b, false, cur)) return -1;
+    if (rates) next.assign(rates, rates + N);
+    else if (codes_now(b, true, next)) return -1;
+    if (rs_alloc(b, nullptr)) return -1;
+    return restart_changed_halves(b, cur, next, RN_RS_DOWN0, RN_RS_HIST - RN_RS_DOWN0);
+  };
+  if (table_set_host(b, b->out_rate_map, 1, rates, restart_changed)) return -1;
+  b->out_Ls = rates ? b->out_rate_map : nullptr;
+  return 0;
+}
+
+extern "C" int rnnoise_batch_set_stream_out_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream) {
+  if (!b || !d_rates) return -1;
+  ON_DEVICE(b->device);
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (rs_alloc(b, st) || table_set_device(b, b->out_rate_map, 1, d_rates, st)) return -1;
+  b->out_Ls = b->out_rate_map;
+  return 0;
+}
+
+extern "C" int rnnoise_batch_stream_out_rates(RNNoiseBatch *b, unsigned char *rates) {
+  if (!b || !rates) return -1;
+  const int Lb = rate_code(b->pcm_rate);
+  if (table_get(b, b->out_Ls ? b->out_Ls : b->g.rs_Ls, 1, rates, Lb)) return -1;
   rates_as_read(rates, b->n, Lb);
   return 0;
 }
@@ -258,6 +344,39 @@ extern "C" int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const un
 extern "C" int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *formats) {
   if (!b || !formats) return -1;
   if (table_get(b, b->g.pcm_fmt, 1, formats, RNNOISE_AMD_PCM_LINEAR)) return -1;
+  for (int s = 0; s < b->n; s++)
+    if (formats[s] > RNNOISE_AMD_PCM_ALAW) formats[s] = RNNOISE_AMD_PCM_LINEAR;  // (as the kernels read it)
+  return 0;
+}
+
+// ---- per-stream output formats (include/rnnoise_amd.h) ----
+// The [N] format bytes live in out_fmt_map; while a table is set (b->out_fmt) the step points K3's copy of the group at it in the
+// place of the format table (shim.h: batch_k3_group): K0 expands what the format table says, K3 compresses what this one says.
+// Configuration like the format table: nothing is zeroed, and nothing but these two setters, rnnoise_batch_set_pcm_rate and the
+// batch's end touches it.  A byte that names no law reads as linear; without a table the getter gives the input formats.
+extern "C" int rnnoise_batch_set_stream_out_formats(RNNoiseBatch *b, const unsigned char *formats) {
+  if (!b) return -1;
+  if (formats)
+    for (int s = 0; s < b->n; s++)
+      if (formats[s] > RNNOISE_AMD_PCM_ALAW) return -1;
+  if (!formats && !b->out_fmt) return 0;
+  ON_DEVICE(b->device);
+  if (table_set_host(b, b->out_fmt_map, 1, formats)) return -1;
+  b->out_fmt = formats ? b->out_fmt_map : nullptr;
+  return 0;
+}
+
+extern "C" int rnnoise_batch_set_stream_out_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream) {
+  if (!b || !d_formats) return -1;
+  ON_DEVICE(b->device);
+  if (table_set_device(b, b->out_fmt_map, 1, d_formats, static_cast<hipStream_t>(hip_stream))) return -1;
+  b->out_fmt = b->out_fmt_map;
+  return 0;
+}
+
+extern "C" int rnnoise_batch_stream_out_formats(RNNoiseBatch *b, unsigned char *formats) {
+  if (!b || !formats) return -1;
+  if (table_get(b, b->out_fmt ? b->out_fmt : b->g.pcm_fmt, 1, formats, RNNOISE_AMD_PCM_LINEAR)) return -1;
   for (int s = 0; s < b->n; s++)
     if (formats[s] > RNNOISE_AMD_PCM_ALAW) formats[s] = RNNOISE_AMD_PCM_LINEAR;  // (as the kernels read it)
   return 0;

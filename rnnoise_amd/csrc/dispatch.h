@@ -63,6 +63,12 @@ struct RnStepShape {
   bool listed = false;  // a stream-list call (rn_dev.h: RnGroupDev::list): n counts its listed rows, never the batch
   bool companded = false;  // an int16 call of a batch with a per-stream format table (rn_dev.h: RnGroupDev::pcm_fmt)
   int channels = 1;        // interleaved channels of the call's PCM rows (rn_dev.h: RnGroupDev::pcm_chan); 1: none
+  // The batch has an output table (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates, _out_formats): low_rate and companded
+  // above then describe the INPUT side alone -- what K0 reads --, and the two below the OUTPUT side -- what K3 writes.  false: one
+  // description serves both sides and the two below are not read (every plan is the one of a batch without output tables).
+  bool split = false;
+  bool out_low_rate = false;   // K3 runs its resampling epilogue: PCM below 48 kHz, a rate table, or an out-rate table
+  bool out_companded = false;  // an int16 call whose output rows follow a format table, the input one or the output one
 };
 
 // RnStepShape::low_rate of a batch: its calls run the resampling prologue / epilogue -- at a PCM rate below 48 kHz, and at any rate
@@ -75,6 +81,7 @@ struct RnPlan {
   RnNnForm nn;
   RnGruForm gru;  // (RN_NN_LAYERS only)
   RnK3Form k3;
+  bool k3_rs;  // K3 is launched with its resampling epilogue (dsp_kernels.hip: bit 9 of parity_arg): the output side's low_rate
 };
 
 static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
@@ -96,6 +103,8 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   // of it reads its row with lane-consecutive samples, each cache line of the group slot once; a lane of the lane = stream kernel
   // would walk its row 4 C samples at a time beside 63 lanes of other slots, and its block loop has no registers to spare for the
   // addressing.  No other stage looks at the caller's PCM: K1, the network and K3's form do not depend on it.
+  // Output tables (RnStepShape::split): K0 never reads them, so low_rate and companded are then the input side's alone, and a batch
+  // whose inputs are all 48 kHz linear keeps the lane = stream kernel above hp_one_max whatever its outputs are.
   p.hp = s.listed || s.low_rate || s.companded || s.channels > 1 || s.n <= k.hp_one_max ? RN_HP_ONE_WAVE : RN_HP_LANES;
   // K1.  From 2,560 streams four streams share a workgroup (rn_analysis_kernel).  6,144 until round 6's last day; since the narrow
   // phases and the follower are shared by the four streams of a workgroup (round 6) that form is ahead from 3,072 streams -- 23.3
@@ -130,6 +139,8 @@ static inline RnPlan rn_plan(const RnKnobs &k, const RnStepShape &s) {
   p.gru = k.gru == 4 ? RN_GRU_W4 : k.gru == 8 ? RN_GRU_W8 : k.gru ? RN_GRU_UNKNOWN : groups > s.cus ? RN_GRU_W4 : RN_GRU_W8;
   // K3.  Up to 256 streams the form that requests every operand up front (one frame: 10.4 -> 9.6 us).
   p.k3 = s.n <= 256 ? RN_K3_FEW : RN_K3_WIDE;
+  // ... and its resampling epilogue from the side K3 writes: the output side of a batch with output tables, else the one description
+  p.k3_rs = s.split ? s.out_low_rate : s.low_rate;
   return p;
 }
 

@@ -70,11 +70,12 @@ extern "C" hipError_t rn_launch_xlane_probe(int *, hipStream_t);
 //  phases `phase`; and the zero state for the listed streams of the view, or for all of them.  ck: the sample FIFOs of the view's
 //  streams (chunk_plan.h; batch_chunk_fifos below), which every scatter restarts -- null where the group has none -- and, with
 //  RN_REC_CHUNK, the chunk call the launch is a staging step of -- full-size or on a stream list -- or the FIFO records it saves /
-//  loads: `rows` is then ck->N, the rows of the call or of the records)
+//  loads: `rows` is then ck->N, the rows of the call or of the records.  out_Ls: the batch's out-rate table for the snapshot
+//  launches, RNNoiseBatch::out_Ls -- null: none, and on every other launch)
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *, RnRecKind kind, float *rec, const int *list, int rows, int p,
-                                             const int *phase, const RnChunkDev *ck, hipStream_t);
+                                             const int *phase, const RnChunkDev *ck, hipStream_t, const uint8_t *out_Ls = nullptr);
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *, RnRecKind kind, const float *rec, const int *list, int rows, int p,
-                                              const int *phase, const RnChunkDev *ck, hipStream_t);
+                                              const int *phase, const RnChunkDev *ck, hipStream_t, const uint8_t *out_Ls = nullptr);
 extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *, const int *list, int n, const RnChunkDev *ck, hipStream_t);
 
 extern "C" hipError_t rn_launch_hp_rows(const RnGroupDev *, const RnRows *, hipStream_t);
@@ -214,6 +215,13 @@ struct RNNoiseBatch {
   // the int16 calls (rn_dev.h: RnGroupDev::pcm_fmt); g.pcm_fmt points at it while a table is set.  Configuration, not state: no reset,
   // import, load or rate change touches it
   uint8_t *fmt_map = nullptr;
+  // per-stream OUTPUT rates and formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates, _out_formats): out_rate_map and
+  // out_fmt_map, [N] bytes each; out_Ls / out_fmt point at them while a table is set.  b->g never carries them: K0 and K1 get the
+  // batch's group, with the input tables, and the step points K3's copy at these (batch.cpp: batch_k3_group) -- and gives that copy
+  // the resampler fields where the batch's group has none (48 kHz inputs without a rate table: batch_rs_48k).  The state kernels get
+  // out_Ls beside a group with those fields (batch_state_group).  Dropped with the rate table by rnnoise_batch_set_pcm_rate
+  uint8_t *out_rate_map = nullptr, *out_fmt_map = nullptr;
+  const uint8_t *out_Ls = nullptr, *out_fmt = nullptr;
   // caller-defined PCM strides (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), in samples; both 0: the default layout.  The
   // process calls hand row_stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and step their frame pointers by frame_stride; b->g
   // itself never carries a pitch.  Configuration, not state
@@ -417,7 +425,34 @@ inline RnChunkDev batch_chunk_fifos(const RNNoiseBatch *b, int first) {
   return c;
 }
 // whether a host call takes the staged path instead of the pinned ring / bounce chunks of host_io.cpp: at a PCM rate other than 48 kHz
-// or with a rate table, with a PCM layout, with interleaved channels, and the int16 calls of a batch with a format table
+// or with a rate table or an out-rate table, with a PCM layout, with interleaved channels, and the int16 calls of a batch with a
+// format table, the input one or the output one
 inline bool batch_host_call_staged(const RNNoiseBatch *b, bool s16) {
-  return b->g.rs_L || b->row_stride || b->channels > 1 || b->link > 1 || (s16 && b->g.pcm_fmt);
+  return b->g.rs_L || b->out_Ls || b->row_stride || b->channels > 1 || b->link > 1 || (s16 && (b->g.pcm_fmt || b->out_fmt));
+}
+// the resampler fields of a 48 kHz batch (batch_tables.cpp: rs_point with a table) on a copy of the group of a batch that has an
+// out-rate table and no resampling on its input side; rs_buf is there from the first out-rate table on
+inline void batch_rs_48k(const RNNoiseBatch *b, RnGroupDev &g) {
+  const size_t N = b->n;
+  g.rs_L = 1;
+  g.rs_pitch = RN_FRAME_SIZE;
+  g.rs_hist = b->rs_buf;
+  g.rs_up = b->rs_buf + N * RN_RS_HIST;
+  g.rs_dn = b->rs_buf + N * (RN_RS_HIST + RN_FRAME_SIZE);
+}
+// K3's copy of a step's group: the effective output tables in the place of the input ones (rn_dev.h: RnGroupDev::rs_Ls, ::pcm_fmt).
+// Without output tables: g as it is
+inline RnGroupDev batch_k3_group(const RNNoiseBatch *b, RnGroupDev g) {
+  if (b->out_Ls) {
+    if (!g.rs_L) batch_rs_48k(b, g);
+    g.rs_Ls = b->out_Ls;
+  }
+  if (b->out_fmt) g.pcm_fmt = b->out_fmt;
+  return g;
+}
+// the batch's group as the state kernels take it: with the histories of a batch whose only resampling is on its output side
+inline RnGroupDev batch_state_group(const RNNoiseBatch *b) {
+  RnGroupDev g = b->g;
+  if (b->out_Ls && !g.rs_L) batch_rs_48k(b, g);
+  return g;
 }

@@ -32,6 +32,8 @@
 static_assert(RN_SNAP_HIST_FLOATS == RN_RS_HIST && RN_SNAP_GATE_NONE == RN_CTL_NONE, "the record and the kernels agree");
 static_assert(RN_SNAP_FLOATS % 4 == 0 && RN_STATE_PITCH % 4 == 0 && RN_SNAP_OFF_HIST % 4 == 0 && RN_OFF_PITCH_BUF % 4 == 0,
               "16-byte rows and runs");
+static_assert(RN_RS_DOWN0 % 4 == 0 && RN_RS_HIST % 4 == 0, "both halves of a history are whole float4s");
+static_assert(RN_SNAP_THREADS > 128, "a snapshot's header words are written by lanes 64 .. 69 and 128");
 static_assert(RN_RING0(1) % 4 == 0 && RN_FRAME_SIZE % 4 == 0 && RN_PITCH_BUF_SIZE % 4 == 0, "ring runs are 16-byte aligned");
 static_assert(RN_OFF_LAST_PERIOD == RN_OFF_LAST_GAIN + 1 && RN_OFF_MEM_HP == RN_OFF_LAST_GAIN + 2, "the four scalar words are consecutive");
 static_assert(!(RN_SNAP_THREADS & (RN_SNAP_THREADS - 1)) && !(RN_STATE_THREADS & (RN_STATE_THREADS - 1)), "move_run rotates lanes by a mask");
@@ -79,6 +81,14 @@ __device__ __forceinline__ Latest latest_slots(int p, const int *__restrict__ ph
 // the divisor stream s's resampler history belongs to: the batch's (1 at 48 kHz), or the stream's own where the batch has a rate table
 // (rn_dev.h: RnGroupDev::rs_Ls)
 __device__ __forceinline__ int stream_L(const RnGroupDev &g, int s) { return g.rs_L ? rn_stream_L(g, s) : 1; }
+// ... and the code its DOWN half belongs to: the stream's own code `in_L`, or its byte of the out-rate table where the batch has one
+// (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates; the view then has its resampler fields), read as K3 reads its copy of
+// the table (rn_dev.h: rn_stream_L)
+__device__ __forceinline__ int stream_out_L(const RnGroupDev &g, const uint8_t *out_Ls, int s, int in_L) {
+  if (!out_Ls) return in_L;
+  const int v = __builtin_amdgcn_readfirstlane((int)*(__attribute__((address_space(1))) const uint8_t *)(out_Ls + s));
+  return ((v == 1 || v == 2 || v == 3 || v == 6 || v == RN_RATE_32K) && rn_rate_samples(v) <= g.rs_pitch) ? v : g.rs_L;
+}
 
 // The fields that are one run on either side, once for both directions and for the zero state: (array row, record offset, floats)
 enum Dir { TO_RECORD, TO_STREAM, TO_ZERO };
@@ -189,11 +199,12 @@ __device__ __forceinline__ void restart_extras(const RnGroupDev &g, size_t s, co
 // call's launch reads what it read before there were any.  (Told by a second value of `rows` instead, the scatter kernel reserved
 // 20 bytes of scratch; told by the fields alone, the full-size call with few streams pushing lost 0.3 to 0.5 %: DESIGN 4.26.)
 
-// rec[row] <- stream.  A snapshot's tail: the header (magic, L, the gate counter or RN_CTL_NONE, three zeros) and the resampler
-// history or zeros; an entry outside the view leaves an empty record (magic 0).
+// rec[row] <- stream.  A snapshot's tail: the header (magic, L, the gate counter or RN_CTL_NONE, the code of the down history where
+// the batch has an out-rate table -- out_Ls, read by snapshot launches alone, behind the state's copy -- or zero, two zeros) and the
+// resampler history or zeros; an entry outside the view leaves an empty record (magic 0).
 extern "C" __global__ void __launch_bounds__(1024)
 rn_state_gather_kernel(RnGroupDev g, float *__restrict__ rec, int p, const int *__restrict__ list, const int *__restrict__ phase, int rows,
-                       int pitch, RnChunkDev ck) {
+                       int pitch, RnChunkDev ck, const uint8_t *__restrict__ out_Ls) {
   if (rows < 0) {  // out[s] <- the stream's output FIFO ++ its staged frames; what is left is the FIFO
     extern __shared__ float kept[];  // (RN_CHUNK_FIFO_ROW floats, on chunk launches only: a state launch keeps its LDS-free dispatch)
     if (blockIdx.x >= (unsigned)ck.N) return;
@@ -224,23 +235,27 @@ rn_state_gather_kernel(RnGroupDev g, float *__restrict__ rec, int p, const int *
     }
     gather_state(g, s, f, latest_slots(p, phase, s));
     if (!snap) continue;
-    if (t >= 64 && t < 70) {
+    if (t >= 64 && t < 70 && !(out_Ls && t == 64 + RN_SNAP_OFF_OUT_L - RN_SNAP_OFF_MAGIC)) {
       const int w = t - 64;
       const int v = w == 0 ? RN_SNAP_MAGIC : w == 1 ? stream_L(g, s) : w == 2 ? (g.gate_c ? g.gate_c[s] : RN_CTL_NONE) : 0;
       f[RN_SNAP_OFF_MAGIC + w] = __int_as_float(v);
     }
+    // (the out-rate table's code in the place of its zero, by a lane of another wave, where there is a table)
+    if (out_Ls && t == 128) f[RN_SNAP_OFF_OUT_L] = __int_as_float(stream_out_L(g, out_Ls, s, g.rs_L));
     if (g.rs_hist) move_run(f + RN_SNAP_OFF_HIST, g.rs_hist + (size_t)s * RN_RS_HIST, RN_RS_HIST);
     else zero_run(f + RN_SNAP_OFF_HIST, RN_RS_HIST);
   }
 }
 
 // stream <- rec[row] (16-byte aligned records), then what the portable state does not carry, where the view has it (g.rs_hist,
-// g.gate_c).  A snapshot brings both: the resampler history when its L is the stream's current one (zeros otherwise) and the gate
-// counter, clamped; a record with another magic word touches nothing.  A portable state restarts them (restart_extras).
+// g.gate_c).  A snapshot brings both: the resampler history, each half when the code it was saved under is the stream's current one --
+// the up half under the record's L against the stream's own code, the down half under the record's output code (0: its L) against the
+// stream's output code (stream_out_L) -- and zeros otherwise, and the gate counter, clamped; a record with another magic word touches
+// nothing.  A portable state restarts them (restart_extras).
 // No `rec`: stream <- the zero state, one workgroup per stream, and the extras restart as well (ck: the FIFOs among them).
 extern "C" __global__ void __launch_bounds__(1024)
 rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, const int *__restrict__ list, const int *__restrict__ phase,
-                        int rows, int pitch, RnChunkDev ck) {
+                        int rows, int pitch, RnChunkDev ck, const uint8_t *__restrict__ out_Ls) {
   if (rows < 0) {  // the stream's pending samples ++ in[s] -> its frames of the call and their mask; the tail is left pending
     if (blockIdx.x >= (unsigned)ck.N) return;
     if (pitch == RN_CHUNK_PITCH_MORE) {
@@ -276,8 +291,13 @@ rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, cons
       continue;
     }
     if (g.rs_hist) {
-      if (__float_as_int(f[RN_SNAP_OFF_L]) == stream_L(g, s)) move_run(g.rs_hist + (size_t)s * RN_RS_HIST, f + RN_SNAP_OFF_HIST, RN_RS_HIST);
-      else zero_run(g.rs_hist + (size_t)s * RN_RS_HIST, RN_RS_HIST);
+      float *hist = g.rs_hist + (size_t)s * RN_RS_HIST;
+      const int rec_L = __float_as_int(f[RN_SNAP_OFF_L]), rec_out = __float_as_int(f[RN_SNAP_OFF_OUT_L]), L = stream_L(g, s);
+      const bool up = rec_L == L, down = (rec_out ? rec_out : rec_L) == stream_out_L(g, out_Ls, s, L);
+      // (one pass over the row's float4s, each from the record or zero by its half: RN_RS_DOWN0 is a multiple of 4)
+      for (int i = t; i < RN_RS_HIST / 4; i += blockDim.x)
+        reinterpret_cast<float4 *>(hist)[i] = (i < RN_RS_DOWN0 / 4 ? up : down) ? reinterpret_cast<const float4 *>(f + RN_SNAP_OFF_HIST)[i]
+                                                                                : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (g.gate_c && t == 64) g.gate_c[s] = min(max(__float_as_int(f[RN_SNAP_OFF_GATE]), 0), RN_CTL_NONE);
     rn_chunk_restart(ck, s, t, blockDim.x);  // (a record carries no FIFO contents)
@@ -290,10 +310,11 @@ rn_state_scatter_kernel(RnGroupDev g, const float *__restrict__ rec, int p, cons
 // ck: the FIFOs of the view's streams, which a scatter restarts (null: the group has none), and with kind RN_REC_CHUNK the chunk
 // call -- `rows` streams, one workgroup of RN_SNAP_THREADS lanes each, no record and no list among the arguments: a list call's
 // list and a FIFO record launch's records travel in ck, with as many workgroups as they have rows.
+// out_Ls: the batch's out-rate table (shim.h: RNNoiseBatch::out_Ls), indexed as the view's rows, for the snapshot launches; null: none.
 namespace {
 template <typename Kernel, typename Rec>
 hipError_t launch_state(Kernel kernel, const RnGroupDev *g, RnRecKind kind, Rec rec, const int *list, int rows, int p, const int *phase,
-                        const RnChunkDev *ck, hipStream_t st) {
+                        const RnChunkDev *ck, hipStream_t st, const uint8_t *out_Ls) {
   if (rows <= 0) return hipSuccess;
   const bool snap = kind == RN_REC_SNAP;
   RnChunkDev c = ck ? *ck : RnChunkDev{};
@@ -302,28 +323,28 @@ hipError_t launch_state(Kernel kernel, const RnGroupDev *g, RnRecKind kind, Rec 
     if (ck->op == RN_CHUNK_OP_CALL ? !ck->counts || (ck->list && ck->S != g->n_streams) : !ck->rec || ck->S != g->n_streams)
       return hipErrorInvalidValue;
     hipLaunchKernelGGL(kernel, dim3(rows), dim3(RN_SNAP_THREADS), RN_CHUNK_FIFO_ROW * sizeof(float), st, *g, rec, 0, nullptr, nullptr, -1,
-                       ck->op || ck->list ? RN_CHUNK_PITCH_MORE : RN_STATE_PITCH, c);
+                       ck->op || ck->list ? RN_CHUNK_PITCH_MORE : RN_STATE_PITCH, c, static_cast<const uint8_t *>(nullptr));
     return hipGetLastError();
   }
   // (RN_STATE_THREADS where one record's latency is the call's: a single state moved between two copies; RN_SNAP_THREADS where
   //  many records share the device, the zero state of a stream list included)
   hipLaunchKernelGGL(kernel, dim3(rows < RN_SNAP_GRID_CAP || !snap ? rows : RN_SNAP_GRID_CAP), dim3(snap || !rec ? RN_SNAP_THREADS : RN_STATE_THREADS),
-                     0, st, *g, rec, p, list, phase, snap ? rows : 0, RN_STATE_PITCH, c);
+                     0, st, *g, rec, p, list, phase, snap ? rows : 0, RN_STATE_PITCH, c, snap ? out_Ls : nullptr);
   return hipGetLastError();
 }
 }  // namespace
 extern "C" hipError_t rn_launch_state_gather(const RnGroupDev *g, RnRecKind kind, float *rec, const int *list, int rows, int p,
-                                             const int *phase, const RnChunkDev *ck, hipStream_t st) {
-  return launch_state(rn_state_gather_kernel, g, kind, rec, list, rows, p, phase, ck, st);
+                                             const int *phase, const RnChunkDev *ck, hipStream_t st, const uint8_t *out_Ls) {
+  return launch_state(rn_state_gather_kernel, g, kind, rec, list, rows, p, phase, ck, st, out_Ls);
 }
 extern "C" hipError_t rn_launch_state_scatter(const RnGroupDev *g, RnRecKind kind, const float *rec, const int *list, int rows, int p,
-                                              const int *phase, const RnChunkDev *ck, hipStream_t st) {
-  return launch_state(rn_state_scatter_kernel, g, kind, rec, list, rows, p, phase, ck, st);
+                                              const int *phase, const RnChunkDev *ck, hipStream_t st, const uint8_t *out_Ls) {
+  return launch_state(rn_state_scatter_kernel, g, kind, rec, list, rows, p, phase, ck, st, out_Ls);
 }
 // the zero state for the n streams list[i] of the view (one workgroup each), or for every stream of the view without a list
 extern "C" hipError_t rn_launch_state_zero(const RnGroupDev *g, const int *list, int n, const RnChunkDev *ck, hipStream_t st) {
   return launch_state(rn_state_scatter_kernel, g, RN_REC_STATE, static_cast<const float *>(nullptr), list, list ? n : g->n_streams, 0,
-                      nullptr, ck, st);
+                      nullptr, ck, st, nullptr);
 }
 
 // One 64-bit store with system-scope release: how a HIP stream releases an explicit SDMA-engine copy that lists an HSA signal as its

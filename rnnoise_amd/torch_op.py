@@ -321,6 +321,20 @@ class RNNoiseOp:
         # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.set_stream_formats_device(formats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
 
+    def set_stream_out_rates(self, hz):
+        """the rate every stream's OUTPUT rows are written at in Hz (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates): as
+        set_stream_rates, which then describes the input rows alone; None drops the table.  Stream s writes the first
+        480 * hz[s] // 48000 samples of its output row.  Synchronous; ValueError on any other value."""
+        self.batch.set_stream_out_rates(hz)
+
+    def set_stream_out_formats(self, formats):
+        """the PCM format of every stream's OUTPUT rows in the batch's int16 calls: an (N,) uint8 CUDA tensor of codes, as
+        set_stream_formats (rnnoise_batch_set_stream_out_formats_device), which then describes the input rows alone"""
+        torch = self.torch
+        assert formats.is_cuda and formats.dtype == torch.uint8 and formats.numel() == self.n
+        formats = formats.to(self.device).contiguous()
+        self.batch.set_stream_out_formats_device(formats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+
     def set_stream_controls(self, limit_db=None, vad_threshold=0.0, hold_frames=0):
         """per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): an attenuation limit in dB (a
         floor on the band gains; None / inf: none), a VAD gate threshold in [0, 1] (0: no gate) and the frames the gate stays open
