@@ -733,6 +733,68 @@ RNNOISE_EXPORT int rnnoise_batch_train_rir_device(RNNoiseBatch *b, float *d_clea
                                                   int n_rirs, const RNNoiseTrainRir *rir, void *d_work, long long work_bytes,
                                                   int n_frames, void *hip_stream);
 
+/* Feature calls: the network alone (the reference's compute_rnn, src/rnn.c:44) on features that already exist, and the same walk over
+ * training records scored with the reference trainer's loss -- what a blob costs, quantised and sparsified as it ships, on records
+ * that may still lie in device memory behind rnnoise_batch_train_features_device.
+ *
+ * ROWS.  Frame t of stream s lies at  base + t * frame_stride + s * row_stride  (in floats); 0, 0 is [frame][n_streams][row], and
+ * any two positive strides whose slots are disjoint do: [frame][n_streams][98] reads the features out of records where they lie,
+ * n_streams sequences one after the other -- the file format of dump_features -- are frame_stride = 98, row_stride = T * 98.  No
+ * alignment beyond the float's 4 bytes and no multiple of anything is asked of pointers or strides.
+ *
+ * rnnoise_batch_process_features[_device]: for t = 0 .. n_frames - 1 the 65 features of every stream go through the stream's
+ * network state; gains[t][s][32] and vad[t][s] receive what compute_rnn returns (either may be NULL).  Every frame runs the
+ * network: the call has no silence decision.
+ *
+ * rnnoise_batch_eval_records[_device]: rows are records of 98 floats -- 65 features, 32 gain targets, 1 VAD target -- and
+ * `records` is the base of the sequences (record 0).  The call runs frames t0 .. t0 + n_frames - 1.  The reference network looks one
+ * frame ahead (two `valid` convolutions, torch/rnnoise/rnnoise.py), so the output of step t belongs to the targets of record t - 1:
+ * step t is scored against record t - 1 for every t >= max(first, 1) -- first = 4 is the trainer's own cut (train_rnnoise.py:147-148),
+ * and step 0 has no record.  A call with t0 > 0 therefore reads record t0 - 1, which must lie there; a file walked in segments
+ * gives the sums of one call bit for bit.  sums is [n_streams][RNNOISE_AMD_EVAL_SUMS] doubles, per stream {sum of gain terms, sum of
+ * VAD terms, frames scored, 0}; the call ADDS to it, so zero it first.  Per scored frame, in double, with g the record's gain targets,
+ * v its VAD target, p the network's gains and q its VAD (train_rnnoise.py:149-155):
+ *     tg = max(g, 0);  tg *= tanh(8 tg)^2
+ *     gain terms, one per band   (1 + 5 v) * min(g + 1, 1) * (p^gamma - tg^gamma)^2
+ *     VAD term                   |2 v - 1| * (-v log(.01 + q) - (1 - v) log(1.01 - q))
+ * The trainer's three means over a set of streams are then, with G, V, F the sums of the three columns over the set:
+ *     gain_loss = G / (32 F),   vad_loss = V / F,   loss = gain_loss + .001 vad_loss
+ * A stream's additions happen in an order that depends on (stream, frame, band) alone: the sums are the same doubles whatever the
+ * batch size, the network path and the cut of the frames into calls.  cfg: NULL or a zeroed struct is {gamma .25, first 4}; any
+ * other struct is taken as it stands (so gamma = 0 beside first != 0 is refused, and first = 0 beside a gamma scores from step 1).
+ * gains / vad as in process_features, over the call's n_frames frames.
+ *
+ * rnnoise_amd_eval_records_check (host only): 1 when the calls accept the arguments -- a finite gamma > 0 and first >= 0 (or the
+ * defaults), t0 >= 0, n_frames >= 0, and the n_streams x (t0 + n_frames) slots of row_floats floats (65 or 98 above) disjoint: rows
+ * inside a frame or frames inside a row, as rnnoise_amd_pcm_layout_fits has it with the record as the row.  The calls return -1
+ * where it returns 0, and for a NULL batch, rows or sums, with nothing launched.
+ *
+ * STATE.  The calls advance the network state of every stream -- conv histories, GRU states -- as rnnoise_batch_process does, and
+ * nothing else: the DSP state of such a batch (pitch ring, spectra, synthesis memory, frame phase) is NOT advanced, so a batch
+ * used for them should not be mixed with PCM calls without a reset between.  rnnoise_batch_reset and rnnoise_batch_reset_streams
+ * restart a sequence.  The model map is honoured (one record set under several blobs in one batch: put the same rows on streams of
+ * different slots); masks, lists, chunk FIFOs, controls and the PCM tables are not read.  The network path and its forms are those of
+ * rnnoise_batch_process_device for a whole batch; rnnoise_batch_kernel_ms counts the network launches under ms[1].  Device forms:
+ * asynchronous on hip_stream, n_frames + 1 small launches around the network's.  Host forms: synchronous; everything from the base
+ * to the last slot goes up in one copy.  Cost: DESIGN.md section 4.28. */
+#define RNNOISE_AMD_EVAL_SUMS 4
+typedef struct RNNoiseEvalConfig {
+  float gamma; /* perceptual exponent of the gain term; the trainer's default .25 */
+  int first;   /* first step that is scored; the trainer's 4 */
+} RNNoiseEvalConfig;
+RNNOISE_EXPORT int rnnoise_amd_eval_records_check(const RNNoiseEvalConfig *cfg, long frame_stride, long row_stride, int row_floats,
+                                                  int n_streams, int t0, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_process_features_device(RNNoiseBatch *b, float *d_gains, float *d_vad, const float *d_features,
+                                                         long frame_stride, long row_stride, int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_process_features(RNNoiseBatch *b, float *gains, float *vad, const float *features,
+                                                  long frame_stride, long row_stride, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_eval_records_device(RNNoiseBatch *b, double *d_sums, float *d_gains, float *d_vad,
+                                                     const float *d_records, long frame_stride, long row_stride, int t0,
+                                                     int n_frames, const RNNoiseEvalConfig *cfg, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_eval_records(RNNoiseBatch *b, double *sums, float *gains, float *vad, const float *records,
+                                              long frame_stride, long row_stride, int t0, int n_frames,
+                                              const RNNoiseEvalConfig *cfg);
+
 /* Test taps for the last processed frame step: per-stream feature vectors [N][65],
  * silence flags [N] and final pitch periods [N] (host buffers, any may be NULL). */
 RNNOISE_EXPORT int rnnoise_batch_debug_last(RNNoiseBatch *b, float *features, int *silence, int *pitch);

@@ -83,6 +83,8 @@ EXPORTS = [
     "rnnoise_batch_process_chunks_list", "rnnoise_batch_process_chunks_list_s16",
     "rnnoise_batch_save_chunk_fifos_device", "rnnoise_batch_load_chunk_fifos_device", "rnnoise_batch_save_chunk_fifos",
     "rnnoise_batch_load_chunk_fifos",
+    "rnnoise_amd_eval_records_check", "rnnoise_batch_process_features_device", "rnnoise_batch_process_features",
+    "rnnoise_batch_eval_records_device", "rnnoise_batch_eval_records",
 ]
 
 
@@ -95,6 +97,15 @@ class TrainMix(C.Structure):
 
 
 MIX_DTYPE = np.dtype(TrainMix)
+
+
+class EvalConfig(C.Structure):
+    """RNNoiseEvalConfig (include/rnnoise_amd.h): the perceptual exponent and the first scored step of the eval-records calls"""
+    _fields_ = [("gamma", C.c_float), ("first", C.c_int)]
+
+
+EVAL_SUMS = 4  # RNNOISE_AMD_EVAL_SUMS: doubles per stream {sum of gain terms, sum of vad terms, frames scored, 0}
+REC = 98       # floats of a training record: 65 features, 32 gain targets, 1 VAD target
 
 
 class TrainRir(C.Structure):
@@ -291,6 +302,12 @@ def _load(path, debug):
         L.rnnoise_amd_train_rir_work_bytes.argtypes = [ll]
         L.rnnoise_batch_train_rir_load_device.argtypes = [vp, vp, vp, ip, C.c_int, vp]
         L.rnnoise_batch_train_rir_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, ll, C.c_int, vp]
+        dp, lg = C.POINTER(C.c_double), C.c_long
+        L.rnnoise_amd_eval_records_check.argtypes = [vp, lg, lg, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.rnnoise_batch_process_features_device.argtypes = [vp] * 4 + [lg, lg, C.c_int, vp]
+        L.rnnoise_batch_process_features.argtypes = [vp, fp, fp, fp, lg, lg, C.c_int]
+        L.rnnoise_batch_eval_records_device.argtypes = [vp] * 5 + [lg, lg, C.c_int, C.c_int, vp, vp]
+        L.rnnoise_batch_eval_records.argtypes = [vp, dp, fp, fp, fp, lg, lg, C.c_int, C.c_int, vp]
         if debug:
             L.rnnoise_batch_debug_pitch.argtypes = [vp, fp]
             L.rnnoise_amd_debug_train_vad_libm.argtypes = [C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong),
@@ -356,6 +373,33 @@ def train_mix_check(mix, lens, n_frames: int) -> bool:
     samples), every gain and coefficient is finite and the flags are 0 or 1.  Host only."""
     mix = _mix_table(mix)
     return bool(lib().rnnoise_amd_train_mix_check(mix.ctypes.data, len(mix), int(lens[0]), int(lens[1]), int(lens[2]), int(n_frames)))
+
+
+def _eval_cfg(gamma, first):
+    """the RNNoiseEvalConfig of the eval-records calls, or None (the trainer's defaults) when both are None"""
+    if gamma is None and first is None:
+        return None
+    return EvalConfig(0.25 if gamma is None else float(gamma), 4 if first is None else int(first))
+
+
+def eval_records_check(frame_stride: int, row_stride: int, row_floats: int, n_streams: int, t0: int, n_frames: int, gamma=None,
+                       first=None) -> bool:
+    """rnnoise_amd_eval_records_check: whether the feature calls accept these arguments -- a finite gamma > 0 and first >= 0 (both
+    None: the defaults), t0 and n_frames >= 0, and disjoint slots of row_floats floats under the strides (0, 0: [frame][n][row]).
+    Host only."""
+    cfg = _eval_cfg(gamma, first)
+    return bool(lib().rnnoise_amd_eval_records_check(C.byref(cfg) if cfg is not None else None, int(frame_stride), int(row_stride),
+                                                     int(row_floats), int(n_streams), int(t0), int(n_frames)))
+
+
+def eval_losses(sums):
+    """the trainer's three means from sums (..., EVAL_SUMS) over all leading axes: dict(frames_scored, gain_loss, vad_loss, loss);
+    nan where no frame was scored"""
+    tot = np.asarray(sums, np.float64).reshape(-1, EVAL_SUMS).sum(0)
+    frames = tot[2]
+    gain = tot[0] / (NB_BANDS * frames) if frames else float("nan")
+    vad = tot[1] / frames if frames else float("nan")
+    return dict(frames_scored=int(frames), gain_loss=float(gain), vad_loss=float(vad), loss=float(gain + .001 * vad))
 
 
 def train_vad_device_available() -> bool:
@@ -1117,6 +1161,64 @@ class Batch:
                                                        d_lowpass or None, d_band_lp or None, d_noise_free or None, n_frames,
                                                        stream or None):
             raise RuntimeError("rnnoise_batch_train_features_device failed")
+
+    @staticmethod
+    def _rows_in(rows, row_floats, layout):
+        """a host array of rows for the feature calls -> (array, frame_stride, row_stride, n_frames): layout "frame" is (T, N, >=
+        row_floats) and "stream" (N, T, >= row_floats), read where they lie -- the last axis may be longer than the row (records as
+        features, a padded pitch)"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        assert rows.ndim == 3 and rows.shape[2] >= row_floats and layout in ("frame", "stream"), (rows.shape, layout)
+        a, bb, w = rows.shape
+        return (rows, bb * w, w, a) if layout == "frame" else (rows, w, bb * w, bb)
+
+    def process_features(self, features, want_gains: bool = True, layout: str = "frame"):
+        """rnnoise_batch_process_features: the network alone on features (T, N, >= 65) (layout "stream": (N, T, >= 65)) ->
+        (vad (T, N), gains (T, N, 32) or None)"""
+        x, fs, rs, T = self._rows_in(features, NB_FEATURES, layout)
+        assert x.shape[1 if layout == "frame" else 0] == self.n, (x.shape, self.n)
+        vad = np.empty((T, self.n), np.float32)
+        gains = np.empty((T, self.n, NB_BANDS), np.float32) if want_gains else None
+        if self._L.rnnoise_batch_process_features(self.h, _fp(gains), _fp(vad), _fp(x), fs, rs, T):
+            raise RuntimeError("rnnoise_batch_process_features failed")
+        return vad, gains
+
+    def process_features_device(self, d_gains: int, d_vad: int, d_features: int, n_frames: int, frame_stride: int = 0,
+                                row_stride: int = 0, stream: int = 0):
+        """rnnoise_batch_process_features_device on raw device pointers (ints), asynchronous on `stream`"""
+        if self._L.rnnoise_batch_process_features_device(self.h, d_gains or None, d_vad or None, d_features or None, int(frame_stride),
+                                                         int(row_stride), n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_process_features_device failed (overlapping slots?)")
+
+    def eval_records(self, records, t0: int = 0, n_frames: int | None = None, sums=None, gamma=None, first=None,
+                     want_gains: bool = True, want_vad: bool = True, layout: str = "frame"):
+        """rnnoise_batch_eval_records: records (T, N, >= 98) from record 0 on (layout "stream": (N, T, >= 98)), frames t0 .. t0 +
+        n_frames - 1 (default: to the end) -> (sums (N, EVAL_SUMS) float64, vad (n_frames, N) or None, gains (n_frames, N, 32) or
+        None).  sums: an (N, EVAL_SUMS) float64 array that is added to in place, or None for a zeroed one."""
+        x, fs, rs, T = self._rows_in(records, REC, layout)
+        assert x.shape[1 if layout == "frame" else 0] == self.n, (x.shape, self.n)
+        n_frames = T - t0 if n_frames is None else n_frames
+        assert 0 <= t0 and 0 <= n_frames and t0 + n_frames <= T, (t0, n_frames, T)
+        if sums is None:
+            sums = np.zeros((self.n, EVAL_SUMS), np.float64)
+        assert sums.dtype == np.float64 and sums.shape == (self.n, EVAL_SUMS) and sums.flags.c_contiguous
+        vad = np.empty((n_frames, self.n), np.float32) if want_vad else None
+        gains = np.empty((n_frames, self.n, NB_BANDS), np.float32) if want_gains else None
+        cfg = _eval_cfg(gamma, first)
+        if self._L.rnnoise_batch_eval_records(self.h, sums.ctypes.data_as(C.POINTER(C.c_double)), _fp(gains), _fp(vad), _fp(x), fs, rs,
+                                              t0, n_frames, C.byref(cfg) if cfg is not None else None):
+            raise RuntimeError("rnnoise_batch_eval_records failed (gamma, first, overlapping slots?)")
+        return sums, vad, gains
+
+    def eval_records_device(self, d_sums: int, d_gains: int, d_vad: int, d_records: int, t0: int, n_frames: int,
+                            frame_stride: int = 0, row_stride: int = 0, gamma=None, first=None, stream: int = 0):
+        """rnnoise_batch_eval_records_device on raw device pointers (ints), asynchronous on `stream`; d_sums [N][EVAL_SUMS] float64 is
+        added to"""
+        cfg = _eval_cfg(gamma, first)
+        if self._L.rnnoise_batch_eval_records_device(self.h, d_sums or None, d_gains or None, d_vad or None, d_records or None,
+                                                     int(frame_stride), int(row_stride), t0, n_frames,
+                                                     C.byref(cfg) if cfg is not None else None, stream or None):
+            raise RuntimeError("rnnoise_batch_eval_records_device failed (gamma, first, overlapping slots?)")
 
     def debug_pitch(self, arm_only: bool = False):
         if arm_only:

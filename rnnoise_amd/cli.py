@@ -30,6 +30,11 @@ s16 48 kHz mono corpora, each uploaded once, everything else on the device:
   python -m rnnoise_amd.cli dump-features --model weights_blob.bin speech.pcm noise.pcm fgnoise.pcm out.f32 COUNT
 --rir-list FILE is the reference's -rir_list: FILE names one room impulse response per line (raw float32 at 48 kHz, of which the first
 32768 samples count); half of the sequences are filtered with one of them before clipping and quantisation.
+
+What a blob costs on such a file, in the reference trainer's loss (rnnoise_amd/evaluate.py; rnnoise_batch_eval_records): the network as
+it ships over every whole sequence of the file, one JSON line with the trainer's three means per model:
+
+  python -m rnnoise_amd.cli eval-records validation.f32 --model weights_blob.bin [--model other.bin ...]
 """
 from __future__ import annotations
 
@@ -267,7 +272,25 @@ def main(argv=None):
     p.add_argument("fgnoise")
     p.add_argument("out")
     p.add_argument("count", type=int)
+    p = sub.add_parser("eval-records")
+    p.add_argument("--model", required=True, action="append", help='"DNNw" weight blob; repeat to score several on the same records')
+    p.add_argument("--sequence-length", type=int, default=2000, help="records per sequence (the trainer: 2000)")
+    p.add_argument("--gamma", type=float, default=0.25, help="perceptual exponent of the gain loss (the trainer: 0.25)")
+    p.add_argument("--first", type=int, default=4, help="first step that is scored (the trainer: 4)")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--max-streams", type=int, default=65536, help="sequences per slab: the batch size")
+    p.add_argument("file", help="float32 records of 98 floats, sequence after sequence (dump-features' output)")
     a = ap.parse_args(argv)
+    if a.cmd == "eval-records":
+        import json
+
+        from . import evaluate
+        res = evaluate.evaluate_records(a.file, [open(m, "rb").read() for m in a.model], a.sequence_length, a.gamma, a.first, a.device,
+                                        a.max_streams)
+        print(json.dumps(dict(file=a.file, sequence_length=a.sequence_length, gamma=a.gamma, first=a.first,
+                              models=[dict(model=m, **{k: v for k, v in r.items() if k != "per_sequence"})
+                                      for m, r in zip(a.model, res)])))
+        return
     if a.cmd == "dump-features":
         n = dump_features(open(a.model, "rb").read(), a.speech, a.noise, a.fgnoise, a.out, a.count, a.seed, a.seq_frames, a.streams,
                           a.device, a.rir_list, a.rir_work_mb, a.vad)

@@ -96,6 +96,38 @@ struct TimedLaunch {
 
 }  // namespace
 
+// The network of one frame, once per model slot (one slot without a map: exactly the launches of a one-model batch).  Slot k's launch
+// owns the streams the map puts on k (rn_dev.h: rn_owns).  Layer-wise, a slot's whole network runs before the next slot's front:
+// act_q[0] and nn_act are the tile's scratch, which the next front overwrites for every column.  g: the frame's group (it leaves with
+// model_sel at the last slot); listed: a list call, which keeps the layer images (batch_process_device_impl).  The process step and
+// the feature calls (batch_eval.cpp) both launch the network here, timed as kind 1.
+int batch_network_step(RNNoiseBatch *b, RnGroupDev &g, const RnPlan &plan, bool listed, hipStream_t st) {
+  for (int k = 0; k < b->n_models; k++) {
+    g.model_sel = k;
+    const RnModelDev *mk = k ? &b->slot_m[k] : &b->m;
+    if (plan.nn == RN_NN_LAYERS) {
+      if (!b->img_valid) HIP_OK(rn_launch_nn_requant(&g, st));
+      b->img_valid = true;
+      // five launches, each timed on its own (kind 1: the durations add up to the network's)
+      std::unique_ptr<TimedLaunch> tl[5];
+      hipEvent_t ev[5][2] = {};
+      for (int i = 0; i < 5; i++) {
+        tl[i].reset(new TimedLaunch(b, 1));
+        ev[i][0] = tl[i]->start();
+        ev[i][1] = tl[i]->stop();
+      }
+      HIP_OK(rn_launch_nn_layers(&g, mk, &b->tb, plan.gru, b->lds_gru, st, ev));
+    } else {
+      TimedLaunch t(b, 1);
+      b->img_valid = b->img_valid && listed;  // (a list call re-quantises its rows' tiles behind its last frame)
+      if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, mk, &b->tb, b->lds_one, st, t.start(), t.stop()));
+      else if (plan.nn == RN_NN_VECTOR) HIP_OK(rn_launch_nn_vector(&g, mk, &b->tb, st, t.start(), t.stop()));
+      else HIP_OK(rn_launch_nn_mfma(&g, mk, &b->tb, plan.nn, st, t.start(), t.stop()));
+    }
+  }
+  return 0;
+}
+
 // =============================================================================================
 // batched API
 // =============================================================================================
@@ -401,32 +433,8 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
       if (side_k1) HIP_OK(hipStreamWaitEvent(st, b->cur_k1[f & 7], 0));
     }
     if (hk && hk->before_nn(f, st)) return -1;
-    // the network once per model slot (one slot without a map: exactly the launches of a one-model batch).  Slot k's launch owns the
-    // streams the map puts on k (rn_dev.h: rn_owns).  Layer-wise, a slot's whole network runs before the next slot's front: act_q[0]
-    // and nn_act are the tile's scratch, which the next front overwrites for every column.
-    for (int k = 0; k < b->n_models; k++) {
-      g.model_sel = k;
-      const RnModelDev *mk = k ? &b->slot_m[k] : &b->m;
-      if (plan.nn == RN_NN_LAYERS) {
-        if (!b->img_valid) HIP_OK(rn_launch_nn_requant(&g, st));
-        b->img_valid = true;
-        // five launches, each timed on its own (kind 1: the durations add up to the network's)
-        std::unique_ptr<TimedLaunch> tl[5];
-        hipEvent_t ev[5][2] = {};
-        for (int i = 0; i < 5; i++) {
-          tl[i].reset(new TimedLaunch(b, 1));
-          ev[i][0] = tl[i]->start();
-          ev[i][1] = tl[i]->stop();
-        }
-        HIP_OK(rn_launch_nn_layers(&g, mk, &b->tb, plan.gru, b->lds_gru, st, ev));
-      } else {
-        TimedLaunch t(b, 1);
-        b->img_valid = b->img_valid && listed;  // (a list call re-quantises its rows' tiles behind its last frame, below)
-        if (plan.nn == RN_NN_ONE) HIP_OK(rn_launch_nn_one(&g, mk, &b->tb, b->lds_one, st, t.start(), t.stop()));
-        else if (plan.nn == RN_NN_VECTOR) HIP_OK(rn_launch_nn_vector(&g, mk, &b->tb, st, t.start(), t.stop()));
-        else HIP_OK(rn_launch_nn_mfma(&g, mk, &b->tb, plan.nn, st, t.start(), t.stop()));
-      }
-    }
+    // the network once per model slot (batch_network_step, above)
+    if (batch_network_step(b, g, plan, listed, st)) return -1;
     {
       TimedLaunch t(b, 2);
       b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
@@ -780,7 +788,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
   ON_DEVICE(b->device);
   const size_t N = b->n;
   for (int f = 0; f < n_frames; f++) {
-    RnTrainArgs tr;
+    RnTrainArgs tr{};  // (step.on = 0: the extraction launch)
     tr.clean = d_clean + f * N * RN_FRAME_SIZE;
     tr.clean_mem = b->g.train_clean_mem;
     tr.vad = d_vad + f * N;

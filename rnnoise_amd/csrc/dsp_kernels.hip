@@ -1643,9 +1643,57 @@ rn_analysis_rows_kernel(RnGroupDev g, RnTablesDev tb, RnRows rows) {
   analysis_body<false, K1_SPW>(g, tb, at.ring, at.spec, RnTrainArgs{}, at.s);
 }
 
-// TRAINING-mode variant: the inner loop of src/dump_features.c:466-491
+// The record step of the feature calls (rn_dev.h: RnEvalStep), one wave per stream.  Scoring: lane = band.  The terms are the
+// reference trainer's (torch/rnnoise/train_rnnoise.py:149-155) in double, NaN going where torch's clamp sends it:
+//   tg = max(g, 0) * tanh(8 max(g, 0))^2;  gain term (1 + 5 v) * min(g + 1, 1) * (p^gamma - tg^gamma)^2;
+//   vad term |2 v - 1| * (-v log(.01 + q) - (1 - v) log(1.01 - q))
+// The 32 gain terms are summed by a butterfly of fixed shape (lanes 32 .. 63 carry +0), lane 0 adds the frame's two sums to the
+// stream's doubles: the order of additions depends on (stream, frame, band) alone.  Staging: lane = record element, so a wave reads
+// its row's consecutive floats wherever the rows lie.
+__device__ __forceinline__ void eval_step_body(const RnGroupDev &g, const RnEvalStep &e) {
+  const int s = (int)blockIdx.x, lane = (int)threadIdx.x;
+  if (e.target) {
+    const float *rec = e.target + (long long)s * e.row_stride;
+    const double v = (double)rec[RN_NB_FEATURES + RN_NB_BANDS];
+    // the f64 library calls are what this launch costs, so each runs once per wave: lane b raises band b's prediction
+    // to gamma while lane 32 + b raises its shaped target, and lanes 0 and 1 take the two logs of the VAD term
+    const int band = lane & (RN_NB_BANDS - 1);
+    const double gt = (double)rec[RN_NB_FEATURES + band], p = (double)e.gains[(size_t)s * RN_NB_BANDS + band];
+    double tg = gt < 0.0 ? 0.0 : gt;
+    const double th = tanh(8.0 * tg);
+    tg = tg * (th * th);
+    const double pw = pow(lane < RN_NB_BANDS ? p : tg, e.gamma);
+    const double d = pw - __shfl_xor(pw, RN_NB_BANDS, WAVE);
+    const double m = gt + 1.0 > 1.0 ? 1.0 : gt + 1.0;
+    double term = lane < RN_NB_BANDS ? ((1.0 + 5.0 * v) * m) * (d * d) : 0.0;
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) term += __shfl_xor(term, off, WAVE);
+    const double q = (double)e.vad[s];
+    const double lg = log(lane == 0 ? .01 + q : 1.01 - q), lg1 = __shfl_xor(lg, 1, WAVE);
+    if (lane == 0) {
+      const double vt = fabs(2.0 * v - 1.0) * (-v * lg - (1.0 - v) * lg1);
+      double *sum = e.sums + (size_t)s * RN_EVAL_SUMS;
+      sum[0] += term;
+      sum[1] += vt;
+      sum[2] += 1.0;
+    }
+  }
+  if (e.stage) {
+    const float *row = e.stage + (long long)s * e.row_stride;
+    float *feat = g.features + (size_t)s * RN_FEAT_ROW;
+    for (int i = lane; i < RN_FEAT_ROW; i += WAVE) feat[i] = i < RN_NB_FEATURES ? row[i] : 0.f;
+    if (lane == 0) g.silence[s] = 0;
+  }
+}
+
+// TRAINING-mode variant: the inner loop of src/dump_features.c:466-491 -- or, with tr.step.on (a launch argument:
+// the branch is wave-uniform and taken before anything else is read), the record step of the feature calls
 extern "C" __global__ void __launch_bounds__(WAVE)
 rn_train_features_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity, RnTrainArgs tr) {
+  if (tr.step.on) {
+    eval_step_body(g, tr.step);
+    return;
+  }
   analysis_body<true, 1>(g, tb, slot, parity, tr);
 }
 
@@ -2130,6 +2178,14 @@ extern "C" hipError_t rn_launch_train_features(const RnGroupDev *g, const RnTabl
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(rn_train_features_kernel, dim3(g->n_streams), dim3(WAVE), sizeof(AnalysisLds), st, *g, *tb,
                      slot, parity, *tr);
+  return hipGetLastError();
+}
+// the record step of the feature calls (rn_dev.h: RnEvalStep): the same kernel, one wave per stream, no LDS
+extern "C" hipError_t rn_launch_eval_step(const RnGroupDev *g, const RnTablesDev *tb, const RnEvalStep *step, hipStream_t st) {
+  RnTrainArgs tr{};
+  tr.step = *step;
+  tr.step.on = 1;
+  hipLaunchKernelGGL(rn_train_features_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, *g, *tb, 0, 0, tr);
   return hipGetLastError();
 }
 extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *g, const RnTablesDev *tb, void *out, int out_s16, int cur, int prev,

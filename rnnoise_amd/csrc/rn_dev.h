@@ -335,6 +335,25 @@ struct RnRows {
   uint32_t e[RN_ROWS_MAX];
 };
 
+// The record step of the feature calls (include/rnnoise_amd.h: rnnoise_batch_process_features_device, rnnoise_batch_eval_records_device;
+// batch_eval.cpp), the second mode of rn_train_features_kernel: one launch between the network of step t and the network of step
+// t + 1, one wave per stream s.  It scores what the network of step t wrote -- gains[s][32], vad[s] -- against the record whose row
+// s is target + s * row_stride (record t - 1: the reference network looks one frame ahead) into sums[s], and stages the row
+// stage + s * row_stride (the features of step t + 1) into g.features[s] with its three pad floats zero and g.silence[s] = 0.
+// target null: nothing is scored (and gains, vad, sums are not read); stage null: nothing is staged (the call's last launch).
+// Rows are read float by float: any 4-byte aligned pointer and stride.
+#define RN_EVAL_SUMS 4  // = RNNOISE_AMD_EVAL_SUMS: doubles per stream {sum of gain terms, sum of vad terms, frames scored, 0}
+struct RnEvalStep {
+  int on;                  // 0: the extraction launch -- nothing below is read
+  const float *stage;      // features of the next step, or null
+  const float *target;     // record to score against (features[65] | gain targets[32] | vad target), or null
+  long long row_stride;    // floats between the rows of two streams, in `stage` and in `target`
+  const float *gains;      // [N][32] the network's output of this step
+  const float *vad;        // [N]
+  double *sums;            // [N][RN_EVAL_SUMS], added to
+  double gamma;            // the perceptual exponent of the gain term
+};
+
 // per-step arguments of the training-feature extraction kernel (src/dump_features.c:466-491)
 struct RnTrainArgs {
   const float *clean;      // [N][480] clean target frames (already filtered/scaled by the caller's mixer)
@@ -344,6 +363,7 @@ struct RnTrainArgs {
   const int *band_lp;      // [N] bands above this get target -1 (dump_features.c:475); 32 = none
   const int *noise_free;   // [N] noise_gain==0 && fgnoise_gain==0 (dump_features.c:477)
   float *rec;              // [N][98] out: features[65] | gain targets[32] | vad
+  RnEvalStep step;         // step.on: the launch is a record step of the feature calls instead, and nothing above is read
 };
 
 // bits(rcpps(x)) for a positive normal x with bits b, from the 16-bit table entry v = rcp16[(b >> 11) & 0xfff]:

@@ -6,6 +6,7 @@
 //   tables.cpp   static tables by formula, the rcpps profile
 //   batch.cpp         rnnoise_batch_*: N streams on one GPU, the frame step as a pipeline over HIP streams and its host-buffer forms,
 //                     training features, timing, debug taps
+//   batch_eval.cpp    the feature calls: the network alone on features that exist, training records scored with the trainer's loss
 //   batch_tables.cpp  a batch's configuration: PCM rate, strides, channels, the per-stream tables (rates, formats, models, controls)
 //   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
 //   train_mix.hip     training sequences: levels, Viterbi VAD and mix of src/dump_features.c:408-465, host code and kernels
@@ -47,6 +48,7 @@ extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *, const RnTablesDev 
                                           hipEvent_t, hipEvent_t);
 extern "C" hipError_t rn_launch_train_features(const RnGroupDev *, const RnTablesDev *, const float *, int, int,
                                                const RnTrainArgs *, hipStream_t);
+extern "C" hipError_t rn_launch_eval_step(const RnGroupDev *, const RnTablesDev *, const RnEvalStep *, hipStream_t);
 extern "C" hipError_t rn_launch_nn_vector(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
                                           hipEvent_t);
 // (lds_opt_in: the batch's answer to the kernel's large-LDS opt-in, RNNoiseBatch::lds_one / lds_gru, returned instead of a launch)
@@ -411,6 +413,8 @@ struct ProcessCall {
 };
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
 int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
+// batch.cpp: the network of one frame on group g, once per model slot, timed as kind 1
+int batch_network_step(RNNoiseBatch *b, RnGroupDev &g, const RnPlan &plan, bool listed, hipStream_t st);
 int batch_chunk_restart_all(RNNoiseBatch *b);                          // batch.cpp: every stream's sample FIFOs as after create
 int batch_chunk_fifos_ready(RNNoiseBatch *b, hipStream_t st);          // batch.cpp: ... allocated where the batch has none yet
 // samples per row and frame at the batch's PCM rate
