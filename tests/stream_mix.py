@@ -1,6 +1,7 @@
 """One mixed block of streams for the at-size parity tests (plain helper module: tests/test_stream_mix_cpu.py checks what the block
 and its dressings cover; tests/test_gpu_at_size.py runs it in lock-step calls, through masked and list calls, with poisoned streams
-under linked gains, through the PCM front ends and through the chunk calls; tests/test_dropin_gpu.py runs it through the drop-in API).
+under linked gains, through the PCM front ends, through the chunk calls and through the feature calls; tests/test_dropin_gpu.py runs it
+through the drop-in API).
 
 `block()` is B = 389 streams x 30 frames of float PCM.  The at-size tests lay a batch out as copies of it (stream i takes block
 stream i mod B); B is prime, so the copies land at shifting offsets modulo the 4 streams of an analysis workgroup, the 16 of a tile
@@ -38,6 +39,12 @@ runs the block through the chunk calls: every position's signal as one row at th
 handed over in full-size and list pushes of 0 .. max_count samples, with a reset while samples are pending and a move of the whole
 batch with its FIFO records.  Its expectation is the closed form of include/rnnoise_amd.h -- y = 0^M ++ z -- over one CPU chain per
 position; `chunk_pin_runs()` are the oracle inputs it adds, which tests/test_oracle.py compares with the compiled reference.
+
+The feature dressing (`FEATURE_CASES`, `FEATURE_CALLS`, `feature_records()`, `feature_expectation()`, `feature_slots()`) runs the
+block through the feature calls (include/rnnoise_amd.h: rnnoise_batch_process_features, rnnoise_batch_eval_records): every position's
+65 features of the lock-step oracle run -- all zero on its silent frames, which a feature call must run the network on all the same --
+as 98-float records with targets of every kind the trainer's loss treats differently, walked in the cuts of `CALLS`.  Its expectation
+is the oracle's compute_rnn alone, one walk per position, and the float64 restatement of tests/eval_cases.py over it.
 """
 from __future__ import annotations
 
@@ -1280,3 +1287,123 @@ def chunk_pin_digest(r):
     parts = [np.ascontiguousarray(r[k][..., None] if r[k].ndim == 2 else r[k]) for k in ("out", "gains", "features", "vad", "pitch", "silence")]
     frame = np.array([[zlib.crc32(b"".join(a[t, s].tobytes() for a in parts)) for s in range(n)] for t in range(Tn)], np.uint32)
     return dict(frame_crc=frame, state_crc=np.array([zlib.crc32(np.ascontiguousarray(x).tobytes()) for x in r["state"]], np.uint32))
+
+
+# ---- the feature dressing: the block through the feature calls (include/rnnoise_amd.h: rnnoise_batch_process_features[_device],
+# rnnoise_batch_eval_records[_device]) ----
+# A feature call plans a whole batch that runs nothing beside the network, unpipelined (rnnoise_amd/csrc/batch_eval.cpp), so the forms
+# it can take are those of plan:n,1,cus,path,0,0,0 of tests/csrc/dispatch_test.cpp.  FEATURE_CASES: (streams, network path or None for
+# the batch's default).  On 256 CUs with the default switches (test_stream_mix_cpu.py holds them to it):
+FEATURE_CASES = [
+    (251, 0),          # rn_nn_one_kernel
+    (389, 1),          # tile 16 (rn_nn_mfma16_kernel)
+    (389, 2),          # layer-wise network, rn_nn_gru_w8_kernel on seven groups, ragged tile and group
+    (4096, None),      # tile 16 at its last size (256 tiles on 256 CUs)
+    (4099, 0),         # rn_nn_vector_kernel at size
+    (4099, 1),         # tile 8 (rn_nn_mfma_kernel): 257 tiles on 256 CUs, the only way a feature call reaches it
+    (10277, None),     # layer-wise network by size, rn_nn_gru_w8_kernel; 10277 = 16 * 642 + 5 = 64 * 160 + 37
+    (40037, None),     # layer-wise network, rn_nn_gru_kernel (w4), ragged in every unit
+]
+FEATURE_IDS = [f"n{n}-path{p}" for n, p in FEATURE_CASES]
+FEATURE_CALLS = CALLS                     # eval calls of 1, 8, 1, 1, 5, 1 and 13 frames, each with the cumulative t0
+FEATURE_LAYOUTS = ("frame", "stream", "pitch100")   # [T][n][98]; [n][T][98]; rows 100 floats apart, NaN in the pad: case i takes i mod 3
+FEATURE_MUTANTS = ("silent_frames_skip", "lag0", "lag2")
+# the kinds of target rows: the six of eval_cases.records()' edge streams, and what dump_features writes
+TARGET_KINDS = ("minus_one", "negative", "zero", "tiny", "one", "mix", "ordinary")
+REC = 98                                  # floats of a record: 65 features, 32 gain targets, 1 VAD target
+
+
+def target_kinds():
+    """(B,) int: the index into TARGET_KINDS of every block position -- that of stream (p * STEP) % B of a layout that deals the kinds
+    out in turn, as block() permutes its streams.  STEP and STEP - B are no multiples of 7, so neighbouring positions (cyclic: the
+    copies wrap from 388 to 0) never share a kind"""
+    return (np.arange(B) * STEP) % B % len(TARGET_KINDS)
+
+
+@functools.lru_cache(None)
+def _feature_targets():
+    import eval_cases as ec
+    rng = _rng(11)
+    kind = target_kinds()
+    band, frame = np.arange(32), np.arange(T)
+    g = np.empty((T, B, 32), np.float32)
+    v = np.empty((T, B), np.float32)
+    negative = -rng.uniform(0.05, 0.95, (T, B, 32)).astype(np.float32)
+    ordinary = rng.uniform(0.02, 0.98, (T, B, 32)).astype(np.float32)
+    limit = rng.integers(1, 33, B)                         # band_lp: -1 from this band upward (32: no band)
+    ordinary[:, band[None, :] >= limit[:, None]] = -1.0
+    vad = rng.uniform(0.0, 1.0, (T, B)).astype(np.float32)
+    vad[rng.random((T, B)) < 0.2] = 1.0                    # (dump_features' VAD is a probability that often sits at its ends)
+    vad[rng.random((T, B)) < 0.2] = 0.0
+    mix = np.array([-1.0, -0.5, 0.0, 1e-20, 1.0, 0.3], np.float32)
+    # the edge kinds' VAD targets: 0, 0.5 and 1 in turn, from a start of the position's own.  The weight 1 + 5 v of a record's gain terms
+    # then changes from frame to frame where the targets themselves do not: a wrong lag between step and record shows in those sums too
+    turn = np.array([0.0, 0.5, 1.0], np.float32)[(frame[:, None] + np.arange(B)[None, :]) % 3]
+    rows = {
+        "minus_one": (np.float32(-1.0), turn),
+        "negative": (negative, turn),
+        "zero": (np.float32(0.0), turn),
+        "tiny": (np.where(band % 2, ec.TINY[0], ec.TINY[1]).astype(np.float32)[None, None, :], turn),
+        "one": (np.float32(1.0), turn),
+        "mix": (mix[(band[None, :] + frame[:, None]) % len(mix)][:, None, :], turn),
+        "ordinary": (ordinary, vad),
+    }
+    for k, name in enumerate(TARGET_KINDS):
+        gk, vk = rows[name]
+        on = kind == k
+        g[:, on] = np.broadcast_to(gk, g.shape)[:, on]
+        v[:, on] = np.broadcast_to(vk, v.shape)[:, on]
+    return g, v
+
+
+def feature_records(want):
+    """(T, B, 98) float32: the records of the feature dressing.  want: oracle_block's lock-step run of the block on the profile the test
+    runs on -- its "features" are the records' 65 features, all exactly zero where the oracle found the frame silent.  The 32 gain
+    targets and the VAD target are a function of position and frame alone (a seeded generator): by position (target_kinds()) -1 on
+    every band, values in (-1, 0), exact 0, eval_cases.TINY, exact 1, a mix of them that moves on with the frame -- each under VAD
+    targets 0, 0.5 and 1 in turn --, and ordinary rows: targets in (0, 1) below a band limit of the position's own and -1 from it
+    upward (dump_features' band_lp), VAD targets in [0, 1].  No NaN, no Inf"""
+    g, v = _feature_targets()
+    feats = np.asarray(want["features"], np.float32)
+    assert feats.shape == (T, B, 65)
+    rec = np.ascontiguousarray(np.concatenate([feats, g, v[..., None]], axis=2), np.float32)
+    assert rec.shape == (T, B, REC) and np.isfinite(rec).all()
+    return rec
+
+
+def feature_slots():
+    """(B,) uint8: the model slot of every block position in the two-model run -- slots() of the link dressing"""
+    return slots()
+
+
+def feature_expectation(blob, rec, slot_blobs=None, mutant=None):
+    """The feature calls' results on the CPU alone, by block position: one oracle.binding.Oracle per position walks compute_rnn over
+    rec[t, p, :65] for every t -- every frame, the all-zero rows too: the calls have no silence decision -- several positions at a
+    time.  slot_blobs: the blob of every model slot, position p then runs on slot_blobs[feature_slots()[p]], else every position on
+    `blob`.  -> "gains" (T, B, 32), "vad" (T, B), "state" (B, STATE): the oracle's get_state() after the walk (nothing but the network
+    state has moved), "sums" (B, 4) float64: eval_cases.expected_sums over the whole walk.
+    mutant (FEATURE_MUTANTS) -- for the tests of the tests: "silent_frames_skip": a position's all-zero rows do not run the network
+    and give zero gains and VAD, as rnnoise_batch_process has it for a silent frame; "lag0" / "lag2": step t scored against record t
+    / t - 2."""
+    import eval_cases as ec
+    from oracle import binding
+    assert mutant in (None,) + FEATURE_MUTANTS and rec.shape[1:] == (B, REC)
+    Tn = rec.shape[0]
+    where = feature_slots() if slot_blobs is not None else np.zeros(B, np.uint8)
+    blobs = slot_blobs if slot_blobs is not None else (blob,)
+    skip = mutant == "silent_frames_skip"
+
+    def one(p):
+        o = binding.Oracle(blobs[where[p]])
+        g, v = np.zeros((Tn, 32), np.float32), np.zeros(Tn, np.float32)
+        for t in range(Tn):
+            if skip and not rec[t, p, :65].any():
+                continue
+            g[t], v[t] = o.compute_rnn(rec[t, p, :65])
+        return g, v, o.get_state()
+
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
+        res = list(pool.map(one, range(B)))
+    gains, vad = np.stack([g for g, _, _ in res], 1), np.stack([v for _, v, _ in res], 1)
+    lag = {"lag0": 0, "lag2": 2}.get(mutant, 1)
+    return dict(gains=gains, vad=vad, state=np.stack([s for _, _, s in res]), sums=ec.expected_sums(rec, gains, vad, lag=lag))

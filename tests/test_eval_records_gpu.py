@@ -14,7 +14,12 @@ float64 restatement of the trainer's loss over those outputs.
   i  the device form on a stream of the caller's, on records extracted in place by rnnoise_batch_train_features_device
   j  argument errors return -1 and launch nothing
 
-Batch stream i takes distinct stream i mod D.  The oracle runs once per distinct stream and blob (eval_cases.oracle_outputs)."""
+Batch stream i takes distinct stream i mod D.  The oracle runs once per distinct stream and blob (eval_cases.oracle_outputs).
+
+The forms of a holds stop at 513 streams.  The at-size forms -- the eight-wave tile kernel, the layer-wise network chosen by size, the
+four-wave rn_nn_gru_kernel, the vector kernel at size, ragged last tiles and groups of grids with more units than CUs -- run in
+tests/test_gpu_at_size.py (test_stream_mix_feature_calls_at_every_form and the three tests behind it) on the mixed block of
+tests/stream_mix.py, whose silent frames are rows of 65 exact zeros that a feature call must run the network on all the same."""
 import ctypes as C
 
 import numpy as np

@@ -9,7 +9,8 @@ NaN in every absent row; under linked gains with controls and two model slots (s
 through the PCM front ends -- rate table, format table, strides, channels, int16 calls (stream_mix.DRESS_CASES) --, the same two ways,
 against a chain on the CPU alone; and through the chunk calls -- full-size and list pushes of any count, in place on the staging
 buffer, a reset with samples pending, a move with FIFO records (stream_mix.CHUNK_CASES) -- against the header's closed form on the CPU
-alone.
+alone; and through the feature calls -- the network alone on the block's features as training records, in cuts, layouts, two models,
+with poisoned streams (stream_mix.FEATURE_CASES) -- against the oracle's compute_rnn and the float64 restatement of the trainer's loss.
 Also here: the device-vs-host log10 sweep behind DESIGN.md's "known residuals", and two processes sharing one GPU."""
 import os
 import subprocess
@@ -903,6 +904,263 @@ def test_poisoned_stream_in_every_at_size_unit(blob_default, rcp_profile, n):
     others = [s for s in range(n - 1, n - 1 - 3 * B, -7) if s not in places] + [places[0] + 1, places[1] - 1, places[2] + 1]
     _ragged_check(blob_default, n, calls, pcm, want=want, nn_path=None, state_streams=others, every_call=True,
                   poisoned=poisoned, ragged=False)
+
+
+# ---- the block through the feature calls (stream_mix.FEATURE_CASES): the network alone on records, scored with the trainer's loss ----
+_FEATURES = {}
+
+
+def _feature_mix(blob, profile, little=None):
+    """the records of the feature dressing, their compute_rnn-only expectation on the CPU (with `little`: under the two-model map of
+    stream_mix.feature_slots()) and the canonical sums -- one 30-frame call of a B-stream batch on path 0 --, once per module, rcpps
+    profile and model set; "worst": the largest relative difference of a position's canonical {gain, VAD} sums from the float64
+    restatement (tests/eval_cases.py) over the expectation"""
+    key = (profile, little is not None)
+    if key not in _FEATURES:
+        import eval_cases as ec
+        import torch
+        B, T = stream_mix.B, stream_mix.T
+        rec = stream_mix.feature_records(_mix(blob, profile)[1])
+        exp = stream_mix.feature_expectation(blob, rec, slot_blobs=None if little is None else (blob, little))
+        dev = torch.device("cuda", 0)
+        b, models = _feature_batch(blob, B, 0, little)
+        d_rec = torch.from_numpy(rec).to(dev)
+        d_sums = torch.zeros((B, capi.EVAL_SUMS), dtype=torch.float64, device=dev)
+        st = torch.cuda.Stream(device=dev)
+        torch.cuda.synchronize()
+        b.eval_records_device(d_sums.data_ptr(), 0, 0, d_rec.data_ptr(), 0, T, stream=st.cuda_stream)
+        st.synchronize()
+        canon = d_sums.cpu().numpy()
+        b.close()
+        for m in models:
+            m.close()
+        worst = [max(ec.rel_diff(canon[p, k], exp["sums"][p, k]) for p in range(B)) for k in (0, 1)]
+        print(f"\n[feature calls] largest relative difference of a block position's sums against the float64 restatement: gain {worst[0]:.3e}, "
+              f"vad {worst[1]:.3e} ({B} positions, {ec.frames_scored(0, T)} scored frames, {'two models' if little is not None else 'one model'})")
+        _FEATURES[key] = dict(rec=rec, exp=exp, canon=canon, worst=worst)
+    return _FEATURES[key]
+
+
+def _feature_batch(blob, n, path, little=None):
+    """a batch of n copies of the block for the feature calls: network path, and with `little` slot 1 = the sparser model under the map
+    of stream_mix.feature_slots() by position"""
+    models = [capi.Model(x) for x in ((blob,) if little is None else (blob, little))]
+    b = capi.Batch(models[0], n)
+    if path is not None:
+        b.set_nn_path(path)
+    if little is not None:
+        assert b.add_model(models[1]) == 1
+        b.set_stream_models(stream_mix.feature_slots()[np.arange(n) % stream_mix.B])
+    return b, models
+
+
+def _feature_rows(torch, r, layout):
+    """r (T, n, w) on the device as the rows of a feature call under `layout` (stream_mix.FEATURE_LAYOUTS): (buffer, frame_stride,
+    row_stride).  "frame": [T + 1][n][w] with the default strides; "stream": [n][T + 1][w], one sequence after the other; "pitch100":
+    [T + 1][n][w + 2].  Record T -- behind every sequence's last record -- and the pad floats are NaN: nothing of them may reach a result"""
+    T, n, w = r.shape
+    if layout == "stream":
+        buf = torch.full((n, T + 1, w), float("nan"), dtype=torch.float32, device=r.device)
+        buf[:, :T] = r.transpose(0, 1)
+        return buf, w, (T + 1) * w
+    pitch = w + 2 if layout == "pitch100" else w
+    buf = torch.full((T + 1, n, pitch), float("nan"), dtype=torch.float32, device=r.device)
+    buf[:T, :, :w] = r
+    return (buf, 0, 0) if layout == "frame" else (buf, n * pitch, pitch)
+
+
+def _feature_differs(name, got, ref, idx, live, B, whole=True):
+    """got (T, n, w) against ref (T, B, w) by block position, both int32 bit patterns on the device, on the streams `live` marks;
+    whole: also the copies among themselves and the ragged tail against the head of copy 0"""
+    T, n, w = got.shape
+    q, r = n // B, n % B
+    if whole:
+        copies = got[:, :B * q].reshape(T, q, B * w)
+        assert bool((copies == copies[:, :1]).all().item()), f"replicated streams diverged ({name})"
+        assert bool((got[:, B * q:] == got[:, :r]).all().item()), f"the ragged tail differs from the head of copy 0 ({name})"
+    ne = (got != ref[:, idx]).any(-1) & live
+    if bool(ne.any().item()):
+        where = ne.nonzero()[:5].tolist()
+        raise AssertionError(f"{name}: {int(ne.sum().item())} of {T * int(live.sum().item())} stream-frames differ from the oracle's compute_rnn, "
+                             f"first (frame, stream) {where}, block positions {[s_ % B for _, s_ in where]}")
+
+
+def _poison_feature_rows(r, n, B):
+    """NaN, +Inf and -Inf into the features, and one NaN into a target, of the copies _poison_places names -> those streams"""
+    _, places = _poison_places(n, B)
+    for s in places:
+        r[2, s, 5] = float("nan")
+        r[9, s, 40] = float("inf")
+        r[16:, s, 0:65:7] = float("-inf")
+        r[23, s, 64] = float("nan")
+        r[6, s, 70] = float("nan")                            # a target, too
+    return places
+
+
+def _feature_run(blob, profile, n, path, layout, little=None, poisoned=False):
+    """One batch of n copies of the block through the feature calls, device forms on a stream of the test's own.  eval_records_device
+    in the cuts of stream_mix.FEATURE_CALLS on records under `layout`: gains and VAD of every stream-frame against the expectation bit
+    for bit (the copies among themselves, the ragged tail against the head of copy 0), the frame behind the call's last keeps its
+    sentinel, every stream's sums the same doubles as its position's canonical sums, frames scored exact.  Not poisoned: the exported
+    state of every block position, each from a different copy, against the oracle's after its compute_rnn-only walk; then, after
+    reset(), process_features_device in ONE 30-frame call on rows 65 floats apart gives the same bits again.  Poisoned: the copies
+    _poison_places names carry NaN / Inf and are left out of every comparison"""
+    import eval_cases as ec
+    import torch
+    mix = _feature_mix(blob, profile, little)
+    exp, canon = mix["exp"], mix["canon"]
+    T, B = stream_mix.T, stream_mix.B
+    dev = torch.device("cuda", 0)
+    idx = torch.arange(n, device=dev) % B
+    r = torch.from_numpy(mix["rec"]).to(dev)[:, idx].contiguous()                 # (T, n, 98)
+    live_h = np.ones(n, bool)
+    if poisoned:
+        live_h[list(_poison_feature_rows(r, n, B))] = False
+    live = torch.from_numpy(live_h).to(dev)
+    buf, fs, rs = _feature_rows(torch, r, layout)
+    ref = {k: torch.from_numpy(np.ascontiguousarray(exp[k], np.float32)).to(dev).reshape(T, B, w).view(torch.int32)
+           for k, w in (("gains", 32), ("vad", 1))}
+
+    def outputs():
+        return (torch.full((T + 1, n, 32), SENTINEL_AUX, dtype=torch.int32, device=dev),
+                torch.full((T + 1, n), SENTINEL_AUX, dtype=torch.int32, device=dev))
+
+    def check(gains, vad, what):
+        assert bool((gains[T] == SENTINEL_AUX).all().item()) and bool((vad[T] == SENTINEL_AUX).all().item()), f"{what} wrote behind its last frame"
+        _feature_differs(f"{what}: gains", gains[:T], ref["gains"], idx, live, B, whole=not poisoned)
+        _feature_differs(f"{what}: vad", vad[:T].reshape(T, n, 1), ref["vad"], idx, live, B, whole=not poisoned)
+
+    gains, vad = outputs()
+    d_sums = torch.zeros((n, capi.EVAL_SUMS), dtype=torch.float64, device=dev)
+    b, models = _feature_batch(blob, n, path, little)
+    st = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    t = 0
+    for k in stream_mix.FEATURE_CALLS:
+        b.eval_records_device(d_sums.data_ptr(), gains.data_ptr() + t * n * 32 * 4, vad.data_ptr() + t * n * 4, buf.data_ptr(), t, k,
+                              frame_stride=fs, row_stride=rs, stream=st.cuda_stream)
+        t += k
+    st.synchronize()
+    assert t == T
+    check(gains, vad, f"eval_records_device in calls of {stream_mix.FEATURE_CALLS}, layout {layout}")
+    # the sums: the same doubles as the position's canonical sums
+    d_canon = torch.from_numpy(canon).to(dev).view(torch.int64)[idx]
+    ne = (d_sums.view(torch.int64) != d_canon).any(-1) & live
+    if bool(ne.any().item()):
+        where = ne.nonzero()[:5, 0].tolist()
+        raise AssertionError(f"sums: {int(ne.sum().item())} of {int(live.sum().item())} streams differ from their position's canonical sums, first "
+                             f"streams {where}, block positions {[s_ % B for s_ in where]}: {d_sums[where].tolist()} for {canon[[s_ % B for s_ in where]].tolist()}")
+    assert bool(((d_sums[:, 2] == ec.frames_scored(0, T)) & (d_sums[:, 3] == 0))[live].all().item()), "frames scored"
+    del buf, d_canon
+    if not poisoned:
+        # block position p from copy (7 p) mod (the copies holding p): nothing but the network state has moved
+        for s_ in [p + (7 * p) % ((n - p + B - 1) // B) * B for p in range(min(B, n))]:
+            assert_bits_equal(b.export_state(s_), exp["state"][s_ % B], f"state of stream {s_} (block position {s_ % B})")
+        feats, _, _ = _feature_rows(torch, r[:, :, :65], "frame")
+        gains2, vad2 = outputs()
+        torch.cuda.synchronize()
+        b.reset()
+        b.process_features_device(gains2.data_ptr(), vad2.data_ptr(), feats.data_ptr(), T, stream=st.cuda_stream)
+        st.synchronize()
+        check(gains2, vad2, "process_features_device in one call after a reset")
+        assert torch.equal(gains2, gains) and torch.equal(vad2, vad), "one 30-frame call after a reset against the seven eval calls"
+    b.close()
+    for m in models:
+        m.close()
+    return mix
+
+
+def _assert_canonical_sums(mix):
+    import eval_cases as ec
+    canon, want = mix["canon"], mix["exp"]["sums"]
+    assert (canon[:, 2] == ec.frames_scored(0, stream_mix.T)).all() and (canon[:, 3] == 0).all() and np.isfinite(canon).all()
+    assert (want[:, 0] > 0).sum() > 300 and (want[:, 1] > 0).sum() > 150                    # (the sums are about something)
+    for p in range(stream_mix.B):
+        for k, name in ((0, "gain"), (1, "vad")):
+            assert ec.rel_diff(canon[p, k], want[p, k]) <= 1e-10, (p, name, canon[p, k], want[p, k])
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path", stream_mix.FEATURE_CASES, ids=stream_mix.FEATURE_IDS)
+def test_stream_mix_feature_calls_at_every_form(blob_default, rcp_profile, n, path):
+    """The mixed block through the feature calls (include/rnnoise_amd.h: rnnoise_batch_eval_records_device,
+    rnnoise_batch_process_features_device) at every form a feature call can take (tests/test_stream_mix_cpu.py): n copies of the
+    records of stream_mix.feature_records() -- every position's 65 features of the lock-step oracle run, all exactly zero on its 304
+    silent stream-frames at and across the call boundaries, beside live rows in the same tile and group, with targets of every kind
+    the trainer's loss tells apart -- walked in the cuts of FEATURE_CALLS, the cases cycling through the three layouts.  The
+    expectation is the oracle's compute_rnn alone, every frame, one walk per position (stream_mix.feature_expectation): a call that
+    skipped the network on a zero row, as rnnoise_batch_process does, fails on 20 of the 22 partly silent positions.  See
+    _feature_run for what is compared.  The canonical sums against the float64 restatement of the trainer's loss: relative difference
+    at most 1e-10 -- a float32 step anywhere would show at 1e-8.
+    Measured on MI355X: largest relative difference over the 389 positions 4.5e-16 (gain sums) and 1.5e-16 (VAD sums); with the
+    sparser model on a third of the positions (the two-model test) 4.3e-16 and 1.5e-16.
+    The block's counts behind this, recomputed in tests/test_stream_mix_cpu.py: 304 zero-feature stream-frames on 29 positions, 7 of
+    them silent throughout and 22 partly, 9 to 20 positions in the first and the last frame of every call, 360 positions never
+    silent; in a 4,099-stream batch 241 of the 256 whole tiles hold a zero row beside a live one in some frame."""
+    _need_256_cus()
+    layout = stream_mix.FEATURE_LAYOUTS[stream_mix.FEATURE_CASES.index((n, path)) % len(stream_mix.FEATURE_LAYOUTS)]
+    _assert_canonical_sums(_feature_run(blob_default, rcp_profile, n, path, layout))
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path", [(4099, 1), (40037, None)], ids=["n4099-path1", "n40037-pathNone"])
+def test_stream_mix_feature_calls_with_two_models(blob_default, blob_little, rcp_profile, n, path):
+    """The same walk with the sparser model as slot 1 under the map of stream_mix.feature_slots(): the slots alternate within every
+    tile and group, and one launch (layer-wise: one whole network) per slot owns its rows.  At 40,037 streams a slot's whole
+    layer-wise network runs before the next slot's front inside a feature call with more groups than CUs; at 4,099 on path 1 the
+    eight-wave tile kernel runs once per slot.  Predictions, sums and states against the two-model expectation"""
+    _need_256_cus()
+    layout = "stream" if n == 4099 else "pitch100"
+    mix = _feature_run(blob_default, rcp_profile, n, path, layout, little=blob_little)
+    _assert_canonical_sums(mix)
+    one = _feature_mix(blob_default, rcp_profile)
+    on = stream_mix.feature_slots() == 1
+    assert (mix["canon"][~on] == one["canon"][~on]).all() and (mix["canon"][on, 0] != one["canon"][on, 0]).mean() > 0.8
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path", [(4099, 1), (40037, None)], ids=["n4099-path1", "n40037-pathNone"])
+def test_feature_calls_keep_poisoned_streams_alone_at_size(blob_default, rcp_profile, n, path):
+    """NaN, +Inf and -Inf in features, and a NaN in a target, of three copies of one block position -- the first lane of a quad, the
+    last lane of a 64-stream GRU group and the middle of a tile (_poison_places) --: every other stream's predictions and sums are bit
+    for bit what they are without the poison, on the eight-wave tile kernel and on the layer-wise network with rn_nn_gru_kernel"""
+    _need_256_cus()
+    _feature_run(blob_default, rcp_profile, n, path, "frame", poisoned=True)
+
+
+@pytest.mark.rcp("host")
+@pytest.mark.parametrize("n,path", [(389, 1), (10277, None)], ids=["n389-path1", "n10277-pathNone"])
+def test_feature_calls_report_their_network_time(blob_default, rcp_profile, n, path):
+    """rnnoise_batch_kernel_ms after a 5-frame eval call with timing on: 5 launches and a positive ms[1] -- through the one-launch
+    branch of the network step (the tile kernel) and the five-launch one (the layer-wise network) --, and ms[0], ms[2], ms[3] what a
+    batch that ran no PCM call reports; the timed call's predictions are the expectation's all the same"""
+    import torch
+    _need_256_cus()
+    mix = _feature_mix(blob_default, rcp_profile)
+    B, k = stream_mix.B, 5
+    dev = torch.device("cuda", 0)
+    idx = torch.arange(n, device=dev) % B
+    buf, fs, rs = _feature_rows(torch, torch.from_numpy(mix["rec"][:k]).to(dev)[:, idx].contiguous(), "frame")
+    gains = torch.full((k + 1, n, 32), SENTINEL_AUX, dtype=torch.int32, device=dev)
+    d_sums = torch.zeros((n, capi.EVAL_SUMS), dtype=torch.float64, device=dev)
+    b, models = _feature_batch(blob_default, n, path)
+    b.enable_timing()
+    idle = b.kernel_ms()
+    assert idle["launches"] == 0
+    st = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    b.eval_records_device(d_sums.data_ptr(), gains.data_ptr(), 0, buf.data_ptr(), 0, k, frame_stride=fs, row_stride=rs, stream=st.cuda_stream)
+    st.synchronize()
+    ms = b.kernel_ms()
+    assert ms["launches"] == k and ms["network"] > 0, ms
+    assert all(ms[key] == idle[key] for key in ("analysis", "synthesis", "highpass")), (ms, idle)
+    assert b.kernel_ms()["launches"] == 0
+    ref = torch.from_numpy(mix["exp"]["gains"][:k]).to(dev).view(torch.int32)
+    _feature_differs("gains of the timed call", gains[:k], ref, idx, torch.ones(n, dtype=torch.bool, device=dev), B)
+    assert bool((gains[k] == SENTINEL_AUX).all().item())
+    b.close()
+    for m in models:
+        m.close()
 
 
 @pytest.mark.rcp("host")

@@ -20,7 +20,12 @@ histories advance on an absent frame, whose reset keeps them or which encodes be
 schedules, every special count on every position, frames completed and FIFO fills mixed in every neighbourhood, a reset that drops
 something, a move at every fill class, a tail that ends on whole frames --, that the cases reach every form a masked and a list call
 can take, that six wrong expectations each change the samples some push returns, and that the closed form is the FIFO model of
-tests/test_chunks_gpu.py on the oracle's frames (test_stream_mix_chunked_at_every_form)."""
+tests/test_chunks_gpu.py on the oracle's frames (test_stream_mix_chunked_at_every_form).  And for the feature dressing
+(stream_mix.FEATURE_CASES and what follows it): that the cases reach every form a feature call can take, that the records keep the
+block's all-zero feature rows -- the silent frames -- at every call boundary and beside live rows in nearly every tile, with targets
+of every kind on neighbouring positions, that the compute_rnn-only expectation is the pinned `process` run on every position that is
+never silent, and that a call which skips the network on zero rows, or scores a step against the wrong record, has something to
+fail on (test_stream_mix_feature_calls_at_every_form and the tests behind it)."""
 import os
 import subprocess
 
@@ -253,6 +258,11 @@ def _forms_of(lines):
     return seen
 
 
+def _sweep_sizes():
+    """the batch sizes of form_sweep: every one up to 4,199, and 400 steps from 4,096 to 131,072 with both neighbours of each"""
+    return sorted(set(range(1, 4200)) | {int(x) + d for x in np.geomspace(4096, 1 << 17, 400) for d in (-1, 0, 1)})
+
+
 @pytest.fixture(scope="module")
 def form_sweep(tmp_path_factory):
     """The forms the rules can choose in per-stream frame phase (masked calls, lock-step calls after them) and in list calls -- found by
@@ -269,8 +279,7 @@ def form_sweep(tmp_path_factory):
             lines += subprocess.run([exe] + part, capture_output=True, text=True, check=True, env=env).stdout.split("\n")[:len(part)]
         return [tuple(l.split()) for l in lines]
 
-    sizes = sorted(set(range(1, 4200)) | {int(x) + d for x in np.geomspace(4096, 1 << 17, 400) for d in (-1, 0, 1)})
-    grid = [(n, path, pipe) for n in sizes for path in (0, 1, 2) for pipe in (0, 1)]
+    grid = [(n, path, pipe) for n in _sweep_sizes() for path in (0, 1, 2) for pipe in (0, 1)]
     can_stream = _forms_of(run(plan_exe, [f"plan:{n},1,256,{path},{pipe},1,0" for n, path, pipe in grid]))
     can_list = _forms_of(run(list_exe, [f"list:{n},{n},256,{pipe},0,{path}" for n, path, pipe in grid]))
     # what the rules allow today (a new form shows up in the sweep on its own; this only says the sweep sees the regimes)
@@ -1117,3 +1126,153 @@ def test_the_int16_and_low_rate_chunk_expectations_are_their_chains():
             n = int(s["total"][p])
             assert (exp["yf"][p, :n].view(np.uint32) == want[:n].view(np.uint32)).all(), (hz, typ, p)
             assert (exp["state"][p].view(np.uint32) == o.get_state().view(np.uint32)).all(), (hz, typ, p)
+
+
+# ---- the feature dressing (stream_mix.FEATURE_CASES, feature_records(), feature_expectation()): what
+# test_stream_mix_feature_calls_at_every_form and the two tests behind it run ----
+@pytest.fixture(scope="module")
+def feature_mix(mix):
+    """(records, the compute_rnn-only expectation, the oracle's lock-step run of the block) on the goldens' profile"""
+    _, _, want = mix
+    rec = sm.feature_records(want)
+    return rec, sm.feature_expectation(load_blob("default"), rec), want
+
+
+def _feature_forms(lines):
+    """the (network form, GRU form where the network is layer-wise) of dispatch_test's output lines"""
+    return {(nn, gru if nn == "layers" else None) for _, _, nn, gru, _ in lines}
+
+
+def test_the_feature_cases_reach_every_form_a_feature_call_can_take(form_sweep):
+    """A feature call plans a whole batch, unpipelined, in lock step, at 48 kHz (rnnoise_amd/csrc/batch_eval.cpp: eval_device): the
+    forms of plan:n,1,256,path,0,0,0 over form_sweep's sizes and the three paths are exactly those FEATURE_CASES produce, and every
+    case runs the form its comment names"""
+    run, plan_exe, _, _, _ = form_sweep
+    can = _feature_forms(run(plan_exe, [f"plan:{n},1,256,{path},0,0,0" for n in _sweep_sizes() for path in (0, 1, 2)]))
+    got = {}
+    for n, path in sm.FEATURE_CASES:
+        p = int(run(plan_exe, [f"path:{n}"])[0][0]) if path is None else path
+        assert path is not None or p == 1, n
+        got[n, path], = _feature_forms(run(plan_exe, [f"plan:{n},1,256,{p},0,0,0"]))
+    assert set(got.values()) == can, (can - set(got.values()), set(got.values()) - can)
+    assert got == {(251, 0): ("rn_nn_one_kernel", None), (389, 1): ("rn_nn_mfma16_kernel", None), (389, 2): ("layers", "rn_nn_gru_w8_kernel"),
+                   (4096, None): ("rn_nn_mfma16_kernel", None), (4099, 0): ("rn_nn_vector_kernel", None),
+                   (4099, 1): ("rn_nn_mfma_kernel", None), (10277, None): ("layers", "rn_nn_gru_w8_kernel"),
+                   (40037, None): ("layers", "rn_nn_gru_kernel")}
+    assert len(sm.FEATURE_IDS) == len(set(sm.FEATURE_IDS)) == len(sm.FEATURE_CASES) and sm.FEATURE_CALLS == sm.CALLS
+    # the units the comments speak of: 257 tiles on 256 CUs, seven groups, ragged tiles and groups, more groups than CUs
+    assert (4099 + 15) // 16 == 257 and 4096 // 16 == 256 and (389 + 63) // 64 == 7 and (40037 + 63) // 64 > 256 >= (10277 + 63) // 64
+    assert all(n % 16 and n % 64 for n in (389, 4099, 10277, 40037))
+    # the eight-wave tile kernel is met on path 1 between 4,097 and 10,239 streams only, the layer-wise network by size from 10,240 on
+    edges = [x[2] for x in run(plan_exe, [f"plan:{n},1,256,1,0,0,0" for n in (4096, 4097, 10239, 10240)])]
+    assert edges == ["rn_nn_mfma16_kernel", "rn_nn_mfma_kernel", "rn_nn_mfma_kernel", "layers"], edges
+
+
+def _target_kind(row):
+    """the kind (stream_mix.TARGET_KINDS) of a record's 32 gain targets, told from the values alone"""
+    import eval_cases as ec
+    g = row[65:97]
+    if (g == -1).all():
+        return "minus_one"
+    if ((g > -1) & (g < 0)).all():
+        return "negative"
+    if (g == 0).all():
+        return "zero"
+    if (g == 1).all():
+        return "one"
+    if set(g.tolist()) == {float(np.float32(x)) for x in ec.TINY}:
+        return "tiny"
+    if set(g.tolist()) == {float(np.float32(x)) for x in (-1.0, -0.5, 0.0, 1e-20, 1.0, 0.3)}:
+        return "mix"
+    limit = int((g != -1).sum())
+    assert limit >= 1 and ((g[:limit] > 0) & (g[:limit] < 1)).all() and (g[limit:] == -1).all(), g
+    return "ordinary"
+
+
+def test_the_feature_records_keep_their_coverage(feature_mix):
+    """Recomputed here (goldens' profile; the silence decision does not depend on the profile): 304 stream-frames of 29 positions have
+    65 features that are all exactly zero, 7 positions throughout and 22 partly; every call of FEATURE_CALLS has between 9 and 20 such
+    positions in its first and in its last frame; 241 of the 256 whole tiles of a 4,099-stream batch hold such a row beside a live one"""
+    rec, _, want = feature_mix
+    assert rec.shape == (sm.T, sm.B, sm.REC) and rec.dtype == np.float32 and np.isfinite(rec).all()
+    assert (rec[..., :65].view(np.uint32) == want["features"].view(np.uint32)).all()
+    assert sm.feature_records(want).tobytes() == rec.tobytes()
+    zero = ~rec[..., :65].any(-1)
+    assert (zero == (want["silence"] != 0)).all(), "the zero-feature rows are not the oracle's silent frames"
+    some, always = zero.any(0), zero.all(0)
+    assert (int(zero.sum()), int(some.sum()), int(always.sum()), int((some & ~always).sum())) == (304, 29, 7, 22)
+    for c in range(len(sm.FEATURE_CALLS)):
+        fr = sm.call_frames(c, sm.FEATURE_CALLS)
+        for t in (fr[0], fr[-1]):
+            assert 9 <= zero[t].sum() <= 20, (c, t, int(zero[t].sum()))
+    idx = np.arange(4099) % sm.B
+    z = zero[:, idx[:4096]].reshape(sm.T, 256, 16)
+    mixed = (z.any(-1) & ~z.all(-1)).any(0)
+    assert mixed.sum() >= 200, int(mixed.sum())
+    # the targets: a function of position and frame, every kind there, no two neighbours (cyclic: the copies wrap) alike
+    kinds = [[_target_kind(rec[t, p]) for p in range(sm.B)] for t in range(sm.T)]
+    assert all(k == kinds[0] for k in kinds), "a position changes its kind of targets from frame to frame"
+    kinds = kinds[0]
+    assert kinds == [sm.TARGET_KINDS[k] for k in sm.target_kinds()]
+    assert all(kinds.count(k) >= sm.B // 8 for k in sm.TARGET_KINDS), {k: kinds.count(k) for k in sm.TARGET_KINDS}
+    assert all(kinds[p] != kinds[(p + 1) % sm.B] for p in range(sm.B))
+    vad = {k: rec[:, [p for p in range(sm.B) if kinds[p] == k], 97] for k in sm.TARGET_KINDS}
+    for k in sm.TARGET_KINDS[:-1]:                                            # 0, 0.5 and 1 in turn on every edge position
+        assert all(set(row.tolist()) == {0.0, 0.5, 1.0} and (row[1:] != row[:-1]).all() for row in vad[k].T), k
+    v = vad["ordinary"]
+    assert ((v >= 0) & (v <= 1)).all() and (v == 0).any() and (v == 1).any() and ((v > 0) & (v < 1)).mean() > 0.5
+    limits = {int((rec[0, p, 65:97] != -1).sum()) for p in range(sm.B) if kinds[p] == "ordinary"}
+    assert len(limits) >= 16 and 32 in limits and min(limits) <= 4, sorted(limits)
+    assert (rec[:, [p for p in range(sm.B) if kinds[p] == "mix"], 65:97][:-1] != rec[:, [p for p in range(sm.B) if kinds[p] == "mix"], 65:97][1:]).any()
+    # the zero-feature rows meet most kinds of target
+    assert len({kinds[p] for p in np.flatnonzero(some)}) >= 5, {kinds[p] for p in np.flatnonzero(some)}
+
+
+def test_the_feature_expectation_is_anchored_to_the_pinned_oracle_run(feature_mix):
+    """tests/test_oracle.py compares the block's `process` run with the compiled reference; here compute_rnn alone is held to that run:
+    on every position that is never silent (360 of them) the compute_rnn walk over the run's features gives the run's gains and VAD
+    bit for bit -- and on the others up to their first silent frame"""
+    rec, exp, want = feature_mix
+    zero = ~rec[..., :65].any(-1)
+    never = np.flatnonzero(~zero.any(0))
+    assert len(never) == 360
+    assert (exp["gains"][:, never].view(np.uint32) == want["gains"][:, never].view(np.uint32)).all()
+    assert (exp["vad"][:, never].view(np.uint32) == want["vad"][:, never].view(np.uint32)).all()
+    for p in np.flatnonzero(zero.any(0) & ~zero[0]):
+        t = int(np.flatnonzero(zero[:, p])[0])
+        assert (exp["gains"][:t, p].view(np.uint32) == want["gains"][:t, p].view(np.uint32)).all(), p
+    # the walk ran the network on every all-zero row: a sigmoid's output, where `process` leaves 32 zero gains
+    assert exp["gains"][zero].all() and not want["gains"][zero].any()
+    # the sums, written out once more for one position of every kind: step t against record t - 1, from step 4 on
+    import eval_cases as ec
+    for k in range(len(sm.TARGET_KINDS)):
+        p = int(never[sm.target_kinds()[never] == k][0])
+        terms = [ec.loss_terms(rec[t - 1, p, 65:97], rec[t - 1, p, 97], exp["gains"][t, p], exp["vad"][t, p]) for t in range(4, sm.T)]
+        by_hand = [sum(float(g.sum()) for g, _ in terms), sum(float(v) for _, v in terms), sm.T - 4, 0]
+        assert np.allclose(exp["sums"][p], by_hand, rtol=1e-12, atol=0), (p, exp["sums"][p], by_hand)
+    assert exp["state"].shape[0] == sm.B and exp["sums"].shape == (sm.B, 4) and np.isfinite(exp["sums"]).all()
+    assert (exp["sums"][:, 0] > 0).sum() > 300 and (exp["sums"][:, 1] > 0).sum() > 150       # (the sums are about something)
+
+
+def test_the_feature_expectation_has_teeth(feature_mix):
+    """a feature call that skipped the network on all-zero rows, as rnnoise_batch_process does on a silent frame, would give other
+    gains on the live frames of at least 15 of the 22 partly silent positions (measured: 20; the other two are silent only at their
+    end); a lag of 0 or 2 between a step and its record moves the gain sums of more than half of the positions that have one"""
+    import eval_cases as ec
+    rec, exp, _ = feature_mix
+    blob = load_blob("default")
+    zero = ~rec[..., :65].any(-1)
+    partly = np.flatnonzero(zero.any(0) & ~zero.all(0))
+    skip = sm.feature_expectation(blob, rec, mutant="silent_frames_skip")
+    moved = [p for p in partly if (skip["gains"][~zero[:, p], p] != exp["gains"][~zero[:, p], p]).any()]
+    print(f"silent_frames_skip: caught on {len(moved)} of {len(partly)} partly silent positions")
+    assert len(moved) >= 15, (len(moved), len(partly))
+    never = ~zero.any(0)
+    assert (skip["gains"][:, never] == exp["gains"][:, never]).all() and not skip["gains"][zero].any()
+    scored = np.flatnonzero(exp["sums"][:, 0] > 0)
+    for mutant in ("lag0", "lag2"):
+        off = sm.feature_expectation(blob, rec, mutant=mutant)
+        assert (off["gains"] == exp["gains"]).all() and (off["sums"][:, 2] == exp["sums"][:, 2]).all()
+        moved = [p for p in scored if ec.rel_diff(off["sums"][p, 0], exp["sums"][p, 0]) > 1e-6]
+        print(f"{mutant}: the gain sums of {len(moved)} of {len(scored)} positions move")
+        assert len(moved) > len(scored) / 2, (mutant, len(moved), len(scored))
