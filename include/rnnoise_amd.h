@@ -795,6 +795,69 @@ RNNOISE_EXPORT int rnnoise_batch_eval_records(RNNoiseBatch *b, double *sums, flo
                                               long frame_stride, long row_stride, int t0, int n_frames,
                                               const RNNoiseEvalConfig *cfg);
 
+/* Split calls: the two DSP halves of the frame step as calls of their own, around a network that is the caller's --
+ *     rnnoise_batch_analyze  ->  any network: 65 features in, 32 band gains and a VAD out  ->  rnnoise_batch_synthesize
+ * so that a float checkpoint, a model of other dimensions or another architecture is heard through the DSP this library restates to
+ * the bit: pitch filter, decay cap, interpolation, resampling, the G.711 ends.  With the batch's own network in the middle
+ * (rnnoise_batch_process_features on the exported rows) the chain gives the bits of rnnoise_batch_process, on streams without silent
+ * frames: the full call skips the network on a silent frame, process_features has no silence decision.
+ *
+ * ROWS.  RNNoiseRows places the rows of a buffer as the feature calls place theirs: frame t of stream s at
+ * base + t * frame_stride + s * row_stride, in floats.  NULL or {0, 0} is [frame][n_streams][row] -- what process_features reads, so
+ * analyze's output plugs straight into it; {65, T * 65} is the trainer's batch-first [n_streams][T][65].  Any two positive strides
+ * with disjoint rows do, and no alignment beyond the float's is asked.  rnnoise_amd_split_rows_check (host only): 1 when the calls
+ * accept the strides for rows of row_floats floats (65 features, 32 gains, 1 vad).
+ *
+ * rnnoise_batch_analyze[_s16][_device] runs the high-pass and the analysis of n_frames frames of every stream -- the launches of
+ * rnnoise_batch_process_device with its plan, the high-pass ahead on a side stream -- and writes exactly 65 floats per stream and
+ * frame to `features`, and the frame's silence word (0: not silent) to silence[t][s] (int32, [n_frames][n_streams]; may be NULL).
+ * It advances what the analysis side owns (high-pass memory, pitch rings, pitch state, up-resampler history, frame counters) and
+ * leaves n_frames frames PENDING in the batch: per stream and frame the X and P spectra, the band energies and the silence word,
+ * rnnoise_amd_split_frame_bytes(n_streams) bytes of device memory per frame.  That store is the batch's own:
+ * rnnoise_batch_split_reserve makes room for max_frames frames (synchronous); a call that needs more grows it, synchronising once.
+ *
+ * rnnoise_batch_synthesize[_s16][_device] runs the synthesis of the pending frames -- n_frames must equal
+ * rnnoise_batch_split_pending -- with gains (rows of 32 floats) and vad (one float per row) in place of the network's.  Values are
+ * taken as they are, NaN included.  On a silent frame (silence word != 0) the caller's rows are NOT read: the frame is synthesised
+ * as the full call synthesises a silent frame and its vad reads 0, for the controls' gate and the link fold too.  (Not read by the
+ * device: the host forms copy every row of the call up, silent frames' too, so there the rows must be readable memory.)  Afterwards the
+ * batch is where rnnoise_batch_process would have left it, and the next call of any kind continues bit for bit.
+ *
+ * Float and int16 PCM, every batch rate, rate / format / out tables, PCM layout and channels, controls and gain link apply as in
+ * rnnoise_batch_process_device[_s16].  The network state, the model slots and the model map are not touched.
+ *
+ * PENDING FRAMES.  While frames are pending every PCM call (analyze included), chunk call and training call, state export / import,
+ * save / load, rnnoise_batch_reset_streams[_device] and every setter return -1 with nothing launched and nothing changed;
+ * process_features*, eval_records* and the getters work.  rnnoise_batch_reset drops the pending frames.  Pending frames are in no
+ * snapshot.  Both calls return -1 on a batch in per-stream frame phase (after a masked, list or chunk call), for a NULL batch or
+ * buffer, for rows that overlap, and synthesize for n_frames != pending.  Device forms: asynchronous on hip_stream, one small
+ * launch per frame beside the DSP kernels.  Host forms: synchronous, staged.  Cost: DESIGN.md section 4.29. */
+#define RNNOISE_AMD_FEATURES 65
+typedef struct RNNoiseRows {
+  long frame_stride, row_stride; /* in elements; NULL or {0, 0}: [frame][n_streams][row] */
+} RNNoiseRows;
+RNNOISE_EXPORT long rnnoise_amd_split_frame_bytes(int n_streams);
+RNNOISE_EXPORT int rnnoise_amd_split_rows_check(const RNNoiseRows *r, int row_floats, int n_streams, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_split_reserve(RNNoiseBatch *b, int max_frames);
+RNNOISE_EXPORT int rnnoise_batch_split_pending(const RNNoiseBatch *b);
+RNNOISE_EXPORT int rnnoise_batch_analyze_device(RNNoiseBatch *b, float *d_features, const RNNoiseRows *feat_rows, int *d_silence,
+                                                const float *d_in, int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_analyze_device_s16(RNNoiseBatch *b, float *d_features, const RNNoiseRows *feat_rows, int *d_silence,
+                                                    const short *d_in, int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_analyze(RNNoiseBatch *b, float *features, const RNNoiseRows *feat_rows, int *silence,
+                                         const float *in, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_analyze_s16(RNNoiseBatch *b, float *features, const RNNoiseRows *feat_rows, int *silence,
+                                             const short *in, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_synthesize_device(RNNoiseBatch *b, float *d_out, const float *d_gains, const RNNoiseRows *gain_rows,
+                                                   const float *d_vad, const RNNoiseRows *vad_rows, int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_synthesize_device_s16(RNNoiseBatch *b, short *d_out, const float *d_gains,
+                                                       const RNNoiseRows *gain_rows, const float *d_vad, const RNNoiseRows *vad_rows,
+                                                       int n_frames, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_synthesize(RNNoiseBatch *b, float *out, const float *gains, const RNNoiseRows *gain_rows,
+                                            const float *vad, const RNNoiseRows *vad_rows, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_synthesize_s16(RNNoiseBatch *b, short *out, const float *gains, const RNNoiseRows *gain_rows,
+                                                const float *vad, const RNNoiseRows *vad_rows, int n_frames);
+
 /* Test taps for the last processed frame step: per-stream feature vectors [N][65],
  * silence flags [N] and final pitch periods [N] (host buffers, any may be NULL). */
 RNNOISE_EXPORT int rnnoise_batch_debug_last(RNNoiseBatch *b, float *features, int *silence, int *pitch);

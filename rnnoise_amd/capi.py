@@ -85,6 +85,9 @@ EXPORTS = [
     "rnnoise_batch_load_chunk_fifos",
     "rnnoise_amd_eval_records_check", "rnnoise_batch_process_features_device", "rnnoise_batch_process_features",
     "rnnoise_batch_eval_records_device", "rnnoise_batch_eval_records",
+    "rnnoise_amd_split_frame_bytes", "rnnoise_amd_split_rows_check", "rnnoise_batch_split_reserve", "rnnoise_batch_split_pending",
+    "rnnoise_batch_analyze_device", "rnnoise_batch_analyze_device_s16", "rnnoise_batch_analyze", "rnnoise_batch_analyze_s16",
+    "rnnoise_batch_synthesize_device", "rnnoise_batch_synthesize_device_s16", "rnnoise_batch_synthesize", "rnnoise_batch_synthesize_s16",
 ]
 
 
@@ -104,6 +107,13 @@ class EvalConfig(C.Structure):
     _fields_ = [("gamma", C.c_float), ("first", C.c_int)]
 
 
+class Rows(C.Structure):
+    """RNNoiseRows (include/rnnoise_amd.h): where the rows of a split call's buffer lie, in elements -- frame t of stream s at
+    t * frame_stride + s * row_stride; (0, 0), like None, is [frame][n_streams][row]"""
+    _fields_ = [("frame_stride", C.c_long), ("row_stride", C.c_long)]
+
+
+FEATURES = 65  # RNNOISE_AMD_FEATURES: floats of a feature row
 EVAL_SUMS = 4  # RNNOISE_AMD_EVAL_SUMS: doubles per stream {sum of gain terms, sum of vad terms, frames scored, 0}
 REC = 98       # floats of a training record: 65 features, 32 gain targets, 1 VAD target
 
@@ -308,6 +318,20 @@ def _load(path, debug):
         L.rnnoise_batch_process_features.argtypes = [vp, fp, fp, fp, lg, lg, C.c_int]
         L.rnnoise_batch_eval_records_device.argtypes = [vp] * 5 + [lg, lg, C.c_int, C.c_int, vp, vp]
         L.rnnoise_batch_eval_records.argtypes = [vp, dp, fp, fp, fp, lg, lg, C.c_int, C.c_int, vp]
+        sp = C.POINTER(C.c_short)
+        L.rnnoise_amd_split_frame_bytes.restype = C.c_long
+        L.rnnoise_amd_split_frame_bytes.argtypes = [C.c_int]
+        L.rnnoise_amd_split_rows_check.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        L.rnnoise_batch_split_reserve.argtypes = [vp, C.c_int]
+        L.rnnoise_batch_split_pending.argtypes = [vp]
+        L.rnnoise_batch_analyze_device.argtypes = [vp] * 5 + [C.c_int, vp]
+        L.rnnoise_batch_analyze_device_s16.argtypes = [vp] * 5 + [C.c_int, vp]
+        L.rnnoise_batch_analyze.argtypes = [vp, fp, vp, ip, fp, C.c_int]
+        L.rnnoise_batch_analyze_s16.argtypes = [vp, fp, vp, ip, sp, C.c_int]
+        L.rnnoise_batch_synthesize_device.argtypes = [vp] * 6 + [C.c_int, vp]
+        L.rnnoise_batch_synthesize_device_s16.argtypes = [vp] * 6 + [C.c_int, vp]
+        L.rnnoise_batch_synthesize.argtypes = [vp, fp, fp, vp, fp, vp, C.c_int]
+        L.rnnoise_batch_synthesize_s16.argtypes = [vp, sp, fp, vp, fp, vp, C.c_int]
         if debug:
             L.rnnoise_batch_debug_pitch.argtypes = [vp, fp]
             L.rnnoise_amd_debug_train_vad_libm.argtypes = [C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong),
@@ -390,6 +414,29 @@ def eval_records_check(frame_stride: int, row_stride: int, row_floats: int, n_st
     cfg = _eval_cfg(gamma, first)
     return bool(lib().rnnoise_amd_eval_records_check(C.byref(cfg) if cfg is not None else None, int(frame_stride), int(row_stride),
                                                      int(row_floats), int(n_streams), int(t0), int(n_frames)))
+
+
+def _rows_arg(rows):
+    """the RNNoiseRows argument of a split call: None, a Rows, or a (frame_stride, row_stride) pair -> (keep-alive, pointer)"""
+    if rows is None:
+        return None, None
+    r = rows if isinstance(rows, Rows) else Rows(int(rows[0]), int(rows[1]))
+    return r, C.byref(r)
+
+
+def split_frame_bytes(n_streams: int) -> int:
+    """rnnoise_amd_split_frame_bytes: the device bytes one pending frame of the split calls costs a batch of n_streams (host only)"""
+    v = lib().rnnoise_amd_split_frame_bytes(int(n_streams))
+    if v < 0:
+        raise ValueError("rnnoise_amd_split_frame_bytes: n_streams > 0")
+    return v
+
+
+def split_rows_check(rows, row_floats: int, n_streams: int, n_frames: int) -> bool:
+    """rnnoise_amd_split_rows_check: whether the split calls accept `rows` (None, Rows or a pair of strides) for rows of row_floats
+    floats of n_streams streams over n_frames frames: the default layout, or positive strides with disjoint rows.  Host only."""
+    _keep, ptr = _rows_arg(rows)
+    return bool(lib().rnnoise_amd_split_rows_check(ptr, int(row_floats), int(n_streams), int(n_frames)))
 
 
 def eval_losses(sums):
@@ -645,7 +692,7 @@ class Batch:
             assert out.dtype == dtype and out.shape == pcm.shape and (self.pcm_layout[1] or out.flags.c_contiguous)
             return out
         if self.pcm_layout[1]:
-            return self.pcm_array(pcm.shape[0], dtype, pcm.shape[1])
+            return self.pcm_array(pcm.shape[0], dtype, self._pcm_dims(pcm)[1])  # (rows, not the groups of a channel array)
         return np.zeros_like(pcm) if zero else np.empty_like(pcm)
 
     def _call(self, fn, *args, exc=RuntimeError, why=""):
@@ -1189,6 +1236,71 @@ class Batch:
         if self._L.rnnoise_batch_process_features_device(self.h, d_gains or None, d_vad or None, d_features or None, int(frame_stride),
                                                          int(row_stride), n_frames, stream or None):
             raise RuntimeError("rnnoise_batch_process_features_device failed (overlapping slots?)")
+
+    # ---- split calls (include/rnnoise_amd.h: rnnoise_batch_analyze, rnnoise_batch_synthesize) ----
+    @property
+    def split_pending(self) -> int:
+        """rnnoise_batch_split_pending: frames analysed and not yet synthesised"""
+        return self._L.rnnoise_batch_split_pending(self.h)
+
+    def split_reserve(self, max_frames: int):
+        """rnnoise_batch_split_reserve: room for max_frames pending frames (split_frame_bytes(n) each); synchronous"""
+        self._call("rnnoise_batch_split_reserve", int(max_frames), why=" (frames pending?)")
+
+    def analyze(self, pcm, layout: str = "frame", s16: bool = False):
+        """rnnoise_batch_analyze[_s16]: pcm as Batch.process[_s16] takes it -> (features, silence (T, N) int32); features is
+        (T, N, 65), or with layout "stream" the trainer's batch-first (N, T, 65).  The T frames stay pending until synthesize."""
+        dtype = np.int16 if s16 else np.float32
+        pcm = self._pcm_in(pcm, dtype)
+        T, R, F = self._pcm_dims(pcm)
+        assert R == self.n and F == self.frame and layout in ("frame", "stream"), (pcm.shape, layout)
+        feats = np.empty((T, R, FEATURES) if layout == "frame" else (R, T, FEATURES), np.float32)
+        _keep, rows = _rows_arg(None if layout == "frame" else (FEATURES, T * FEATURES))
+        sil = np.empty((T, R), np.int32)
+        ptr = C.POINTER(C.c_short if s16 else C.c_float)
+        self._call("rnnoise_batch_analyze_s16" if s16 else "rnnoise_batch_analyze", _fp(feats), rows,
+                   sil.ctypes.data_as(C.POINTER(C.c_int)), pcm.ctypes.data_as(ptr), T, why=" (frames pending, or per-stream frame phase?)")
+        return feats, sil
+
+    def synthesize(self, gains, vad, layout: str = "frame", s16: bool = False, out: np.ndarray | None = None):
+        """rnnoise_batch_synthesize[_s16]: gains (T, N, >= 32) and vad (T, N) or (T, N, >= 1) for the pending frames (layout "stream":
+        (N, T, ...)), read where they lie -> out, the PCM as Batch.process[_s16] returns it"""
+        dtype = np.int16 if s16 else np.float32
+        g, gfs, grs, T = self._rows_in(gains, NB_BANDS, layout)
+        v = np.ascontiguousarray(vad, np.float32)
+        v, vfs, vrs, Tv = self._rows_in(v[..., None] if v.ndim == 2 else v, 1, layout)
+        assert T == Tv and g.shape[1 if layout == "frame" else 0] == self.n and v.shape[:2] == g.shape[:2], (g.shape, v.shape)
+        ch = self.pcm_channels
+        shape = (T, self.n // ch, self.frame, ch) if ch > 1 else (T, self.n, self.frame)
+        if out is None:
+            out = self.pcm_array(T, dtype)
+        elif self.pcm_layout[1]:
+            out = self._pcm_in(out, dtype)
+        assert out.dtype == dtype and out.shape == shape and (self.pcm_layout[1] or out.flags.c_contiguous), (out.shape, shape)
+        kg, grows = _rows_arg((gfs, grs))
+        kv, vrows = _rows_arg((vfs, vrs))
+        ptr = C.POINTER(C.c_short if s16 else C.c_float)
+        self._call("rnnoise_batch_synthesize_s16" if s16 else "rnnoise_batch_synthesize", out.ctypes.data_as(ptr), _fp(g), grows, _fp(v),
+                   vrows, T, why=" (n_frames != split_pending, or overlapping rows?)")
+        return out
+
+    def analyze_device(self, d_features: int, d_silence: int, d_in: int, n_frames: int, feat_rows=None, stream: int = 0,
+                       s16: bool = False):
+        """rnnoise_batch_analyze_device[_s16] on raw device pointers (ints), asynchronous on `stream`; feat_rows: None, Rows or a
+        (frame_stride, row_stride) pair"""
+        _keep, rows = _rows_arg(feat_rows)
+        fn = self._L.rnnoise_batch_analyze_device_s16 if s16 else self._L.rnnoise_batch_analyze_device
+        if fn(self.h, d_features or None, rows, d_silence or None, d_in or None, n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_analyze_device failed (frames pending, per-stream frame phase, overlapping rows?)")
+
+    def synthesize_device(self, d_out: int, d_gains: int, d_vad: int, n_frames: int, gain_rows=None, vad_rows=None, stream: int = 0,
+                          s16: bool = False):
+        """rnnoise_batch_synthesize_device[_s16] on raw device pointers (ints), asynchronous on `stream`"""
+        _kg, grows = _rows_arg(gain_rows)
+        _kv, vrows = _rows_arg(vad_rows)
+        fn = self._L.rnnoise_batch_synthesize_device_s16 if s16 else self._L.rnnoise_batch_synthesize_device
+        if fn(self.h, d_out or None, d_gains or None, grows, d_vad or None, vrows, n_frames, stream or None):
+            raise RuntimeError("rnnoise_batch_synthesize_device failed (n_frames != split_pending, overlapping rows?)")
 
     def eval_records(self, records, t0: int = 0, n_frames: int | None = None, sums=None, gamma=None, first=None,
                      want_gains: bool = True, want_vad: bool = True, layout: str = "frame"):

@@ -72,7 +72,7 @@ def out_info(info: wav.WavInfo, out_rate=None, out_format=None) -> wav.WavInfo:
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
                   vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None,
-                  formats=None, link_channels: bool = False, out_rate=None, out_format=None):
+                  formats=None, link_channels: bool = False, out_rate=None, out_format=None, torch_net=None, max_store_gb: float = 4.0):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 32000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
@@ -86,7 +86,12 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     one batch per distinct count (a RAW file is mono).  link_channels: the channels of each multichannel file form one link group
     (capi.Batch.set_gain_link with the file's channel count).  out_rate / out_format: the rate (at most `rate`) and the format every
     output is written in where it is not the input's (capi.Batch.set_stream_out_rates, set_stream_out_formats); a frame then has
-    480 * out_rate // 48000 samples on the way out.  Returns the frames of every input."""
+    480 * out_rate // 48000 samples on the way out.
+    torch_net: a TorchScript file whose module maps features [N, T, 65] to (gains [N, T, 32], vad [N, T, 1]); it takes the place of
+    the blob's network between the split calls (capi.Batch.analyze / synthesize), on the batch's device.  Each group of files then
+    goes through ONE pair, whole -- a module's state need not survive a call -- and the call is refused (ValueError, before anything
+    runs) where the pending frames would need more than max_store_gb GiB of device memory (capi.split_frame_bytes).
+    Returns the frames of every input."""
     os.makedirs(out_dir, exist_ok=True)
     if rates is not None and len(rates) != len(inputs):
         raise ValueError(f"{len(rates)} rates for {len(inputs)} files")
@@ -108,17 +113,27 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     groups = {}
     for d in files:
         groups.setdefault(d["channels"], []).append(d)
+    net = None
+    if torch_net is not None:
+        for channels, group in groups.items():
+            frames, n = max([d["n_frames"] for d in group] + [0]), len(group) * channels
+            need = frames * capi.split_frame_bytes(n)
+            if need > max_store_gb * 2 ** 30:
+                raise ValueError(f"--torch-net: {frames} pending frames of {n} streams need {need / 2 ** 30:.2f} GiB of device memory, "
+                                 f"above --max-store-gb {max_store_gb}")
+        import torch
+        net = torch.jit.load(torch_net, map_location=f"cuda:{device}").eval()
     model = capi.Model(model_blob)
     for channels, group in groups.items():
         _denoise_group(model, group, channels, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold,
                        rate_table=rates is not None, format_table=formats is not None, link=link_channels,
-                       out_tables=out_rate is not None or out_format is not None)
+                       out_tables=out_rate is not None or out_format is not None, net=net)
     model.close()
     return [d["n_frames"] for d in files]
 
 
 def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold, rate_table,
-                   format_table, link=False, out_tables=False):
+                   format_table, link=False, out_tables=False, net=None):
     """the files of one channel count C through one batch of len(files) * C streams: file g's channel c is stream g * C + c"""
     FRAME = capi.FRAME * rate // 48000
     G, N = len(files), len(files) * C
@@ -126,6 +141,8 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
     width = [d["width"] for d in files]  # bytes per sample of each file
     n_frames = [d["n_frames"] for d in files]
     T = max(n_frames + [0])
+    if net is not None:
+        chunk_frames = max(T, 1)  # (the whole group in one analyze / synthesize pair)
     batch = capi.Batch(model, N, device=device)
     if rate != 48000:
         batch.set_pcm_rate(rate)
@@ -181,7 +198,10 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
                     continue
                 x = np.frombuffer(f.read(k * frame_of[s] * C * 2), dtype=np.int16)
                 chunk[:k, s, :frame_of[s] * C] = x.reshape(k, frame_of[s] * C)
-        out, vad, _ = batch.process_s16(buf[:tn], want_gains=False, out=obuf[:tn])
+        if net is None:
+            out, vad, _ = batch.process_s16(buf[:tn], want_gains=False, out=obuf[:tn])
+        else:
+            vad = _split_pair(batch, net, buf[:tn], obuf[:tn], device)
         out = slots(obuf)[:tn]
         for s in range(G):
             k = max(0, min(tn, n_frames[s] - t0))
@@ -198,6 +218,18 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
     for f in ins + outs + (vfs or []):
         f.close()
     batch.close()
+
+
+def _split_pair(batch, net, pcm, out, device):
+    """pcm through analyze -> net -> synthesize into out; returns the vad as (T, N): the net's, and 0 on a silent frame, where the
+    net's rows are not read -- what the gate and a link saw, and what process_s16 reports there"""
+    import torch
+    feats, silence = batch.analyze(pcm, layout="stream", s16=True)
+    with torch.no_grad():
+        gains, vad = net(torch.from_numpy(feats).to(f"cuda:{device}"))
+    gains, vad = gains.float().cpu().numpy(), vad.float().cpu().numpy()
+    batch.synthesize(gains, vad, layout="stream", s16=True, out=out)
+    return np.where(silence != 0, np.float32(0), vad.reshape(vad.shape[0], vad.shape[1]).T)
 
 
 def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out: str, count: int, seed=None, seq_frames: int = 2000,
@@ -255,6 +287,9 @@ def main(argv=None):
     p.add_argument("--vad-hold", type=int, default=0, help="frames the VAD gate stays open after the last voice frame")
     p.add_argument("--link-channels", action="store_true",
                    help="one suppression for the channels of each multichannel WAV file: linked band gains and VAD gate")
+    p.add_argument("--torch-net", default=None,
+                   help="TorchScript module [N,T,65] -> ([N,T,32], [N,T,1]) that replaces the blob's network (split calls; one pair per file group)")
+    p.add_argument("--max-store-gb", type=float, default=4.0, help="--torch-net: device memory the pending frames may take, in GiB")
     p.add_argument("inputs", nargs="+")
     p = sub.add_parser("dump-features")
     p.add_argument("--model", required=True, help='"DNNw" weight blob: a batch needs one (the extraction runs no network)')
@@ -297,7 +332,8 @@ def main(argv=None):
         print(f"wrote {a.count} sequences, {n} records")
         return
     n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
-                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels, a.out_rate, a.out_format)
+                      a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels, a.out_rate, a.out_format,
+                      a.torch_net, a.max_store_gb)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

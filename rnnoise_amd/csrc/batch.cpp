@@ -197,6 +197,7 @@ extern "C" void rnnoise_batch_destroy(RNNoiseBatch *b) {
   if (b->state_stage) hipFree(b->state_stage);
   if (b->chunk_fifo) hipFree(b->chunk_fifo);
   if (b->chunk_stage) hipFree(b->chunk_stage);
+  if (b->split_store) hipFree(b->split_store);
   if (b->arena) hipFree(b->arena);
   if (b->rs_buf) hipFree(b->rs_buf);
   if (b->rate_map) hipFree(b->rate_map);
@@ -236,11 +237,13 @@ extern "C" int rnnoise_batch_reset(RNNoiseBatch *b) {
   b->ring_slot = 0;
   b->frame_no = 0;
   b->per_stream = false;  // (the only way back to lock-step frame phase)
+  b->split_pending = 0;   // (pending frames of the split calls are dropped; their store stays)
   return 0;
 }
 
 extern "C" int rnnoise_batch_set_schedule(RNNoiseBatch *b, int schedule) {
   if (!b || (schedule != 0 && schedule != 1 && schedule != 9)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const int old = b->schedule;
   b->schedule = schedule;
   return old;
@@ -248,6 +251,7 @@ extern "C" int rnnoise_batch_set_schedule(RNNoiseBatch *b, int schedule) {
 
 extern "C" int rnnoise_batch_set_nn_path(RNNoiseBatch *b, int path) {
   if (!b || path < 0 || path > 2) return -1;  // 0 vector, 1 MFMA (layer-wise from $RNNOISE_AMD_NN_LAYERS_MIN streams up), 2 layer-wise
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   int old = b->nn_path;
   b->nn_path = path;
   return old;
@@ -261,12 +265,18 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
   const bool s16 = c.s16;
   FrameIo *hk = c.hooks;
   if (!b || n_frames < 0) return -1;
+  // one half of the step alone (shim.h: SplitCall; batch_split.cpp has checked the call): the analysis half launches K0, K1 and an
+  // export step per frame, the synthesis half an import step and K3 -- with the plan, the groups and the PCM addressing of the whole
+  // step, which launches what it always did.  A whole step is refused while frames are pending
+  const SplitCall *const sp = c.split;
+  const bool ana = sp && sp->analyze, syn = sp && !sp->analyze;
+  if (!sp && batch_split_busy(b)) return -1;
   const bool listed = c.list || n_rows;
   if (listed) {
     if (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !c.list)) return -1;
     if (n_rows == 0) return 0;
   }
-  if (!c.out || !c.in) return -1;
+  if ((!c.out && !ana) || (!c.in && !syn)) return -1;
   // the caller's PCM layout (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout), unless the buffers are the library's own (packed:
   // the staged host path; hk: the pinned ring).  Its frame slots must be disjoint, checked before anything is launched or changed
   // Interleaved channels (rnnoise_batch_set_pcm_channels): the rows are taken `chan` at a time, in the library's staging buffer
@@ -325,8 +335,10 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
   //   * every other piece of state is touched by one kernel only, in frame order on its own stream.
   // (dispatch.h: rn_schedule has the other schedules and rn_plan every kernel's form; one plan serves every frame of the call.  The
   // layer images are indexed by tile of the whole batch; the layer kernels use 32-bit byte offsets into a state plane)
+  // (a split call: the analysis half keeps K1 on the caller's stream, with its export step behind it, and K0 runs ahead on the side
+  //  stream as far as the ring allows; the synthesis half has nothing to overlap)
   const RnSchedule sched = rn_schedule(rn_knobs(), n_frames, b->schedule);
-  const bool pipelined = sched.pipelined, side_k1 = sched.side_k1;
+  const bool pipelined = sched.pipelined && !syn, side_k1 = sched.side_k1 && !sp;
   const bool whole = b->g.n_streams == b->g.n_stride && (size_t)b->g.n_streams * RN_GRU * 4 < (1ull << 32);
   RnStepShape shape{(int)N, whole && !listed, b->cus, b->nn_path, pipelined, b->per_stream,
                     rn_shape_low_rate(b->pcm_rate, b->g.rs_Ls != nullptr)};
@@ -391,7 +403,7 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
     // synthesis(f-3) on the main stream, so that is the event to start behind -- the high-pass of frame f is launched after it (see the
     // frame loop).  Started at the ring's earliest moment it ran beside the layer kernels of frame f-3: network 0.73 ms instead of 0.57
     // (profiles/r5_hostio_sdma.txt).
-    if (pipelined && !side_k1 && f >= 3) HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[(f - 3) & 7], 0));
+    if (pipelined && !side_k1 && !ana && f >= 3) HIP_OK(hipStreamWaitEvent(sc, b->cur_k3[(f - 3) & 7], 0));
     if (hk && hk->before_hp(f, sc)) return -1;
     {
       TimedLaunch t(b, 3);
@@ -405,6 +417,19 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
   };
   auto analysis = [&](int f) -> int {  // K1 of frame f on stream sb
     RnGroupDev g = frame_group(f);
+    const int slot = (b->parity + f) % RN_SPEC_SLOTS;
+    if (ana && f + 1 < n_frames) {  // a pending frame's spectra go to its entry of the store; the call's last to the batch's own slot
+      const SplitEntry e = batch_split_entry(b, f);
+      g.spec_X[slot] = e.X, g.spec_P[slot] = e.P, g.spec_E[slot] = e.E;
+    } else if (ana && b->split_prev_kept) {
+      // ... which, in a call of a multiple of RN_SPEC_SLOTS frames, still holds what synthesis of frame 0 reads as the delayed
+      // spectra: they move to the store's last entry first, on K1's stream
+      const SplitEntry e = batch_split_entry(b, f);
+      const size_t N = b->n;
+      HIP_OK(hipMemcpyAsync(e.X, b->g.spec_X[slot], N * RN_SPEC_STRIDE * 4, hipMemcpyDeviceToDevice, sb));
+      HIP_OK(hipMemcpyAsync(e.P, b->g.spec_P[slot], N * RN_SPEC_STRIDE * 4, hipMemcpyDeviceToDevice, sb));
+      HIP_OK(hipMemcpyAsync(e.E, b->g.spec_E[slot], N * RN_SPEC_E_ROW * 4, hipMemcpyDeviceToDevice, sb));
+    }
     if (pipelined) {
       HIP_OK(hipStreamWaitEvent(sb, b->cur_hp[f & 7], 0));
       if (side_k1 && f >= 2) HIP_OK(hipStreamWaitEvent(sb, b->cur_k3[(f - 2) & 7], 0));
@@ -415,14 +440,62 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
       HIP_OK(rn_launch_analysis(&g, &b->tb, (b->ring_slot + f) % RN_RING_SLOTS, (b->parity + f) % RN_SPEC_SLOTS, plan.k1, sb, t.start(),
                                 b->cur_k1[f & 7]));
     }
+    if (ana) {  // the frame's features and silence words out of the per-step scratch, behind K1 on K1's stream
+      RnSplitStep x{};
+      x.feat = sp->features + (size_t)f * sp->feat_fs;
+      x.feat_stride = sp->feat_rs;
+      x.sil_keep = batch_split_entry(b, f).silence;
+      x.sil_out = sp->silence ? sp->silence + (size_t)f * b->n : nullptr;
+      HIP_OK(rn_launch_split_step(&g, &b->tb, &x, RN_STEP_EXPORT, sb));
+    }
     return 0;
   };
   if (pipelined) {
     for (int f = 0; f < 3 && f < n_frames; f++)
       if (highpass(f)) return -1;
-    if (analysis(0)) return -1;
+    if (!ana && analysis(0)) return -1;
   }
-  for (int f = 0; f < n_frames; f++) {
+  for (int f = 0; ana && f < n_frames; f++) {  // the analysis half: K1 in frame order, K0 three frames ahead where the call is pipelined
+    if (!pipelined && highpass(f)) return -1;
+    if (analysis(f)) return -1;
+    if (pipelined && f + 3 < n_frames && highpass(f + 3)) return -1;  // (a timed pair counts its frames once, in the synthesis half)
+  }
+  auto synthesis = [&](int f, RnGroupDev &g, int cur, int prev) -> int {  // K3 of frame f on the caller's stream
+    TimedLaunch t(b, 2);
+    b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
+    g.link = link > 1 ? link : 0;  // (rn_dev.h: RnGroupDev::link -- K3's copy alone; 0: today's launch)
+    const RnGroupDev g3 = batch_k3_group(b, g);  // (... with the effective output tables; without out tables g itself)
+    HIP_OK(rn_launch_synthesis(&g3, &b->tb, d_out + buf(f) * fstep, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
+    return 0;
+  };
+  // The synthesis half: per pending frame an import step and K3, at the slots the frame was analysed at (the batch's have moved on).
+  // K3's copy of the group gets the frame's spectra and silence words in the place of the batch's slots (shim.h:
+  // RNNoiseBatch::split_store), and the caller's gains and vad -- zeros on a silent frame -- go into the scratch K3 reads, where the
+  // network would have left its own.  The analysis half has moved the frame counters
+  for (int f = 0; syn && f < n_frames; f++) {
+    RnGroupDev g = frame_group(f);
+    const int cur = (b->split_parity + f) % RN_SPEC_SLOTS, prev = (cur + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
+    if (f + 1 < n_frames) {
+      const SplitEntry e = batch_split_entry(b, f);
+      g.spec_X[cur] = e.X, g.spec_P[cur] = e.P, g.spec_E[cur] = e.E;
+    }
+    if (f > 0 || b->split_prev_kept) {
+      const SplitEntry e = batch_split_entry(b, f > 0 ? f - 1 : n_frames - 1);
+      g.spec_X[prev] = e.X, g.spec_P[prev] = e.P, g.spec_E[prev] = e.E;
+    }
+    g.silence = batch_split_entry(b, f).silence;
+    RnSplitStep x{};
+    x.sil = g.silence;
+    x.gains = sp->gains + (size_t)f * sp->gains_fs;
+    x.gains_stride = sp->gains_rs;
+    x.vad = sp->vad + (size_t)f * sp->vad_fs;
+    x.vad_stride = sp->vad_rs;
+    HIP_OK(rn_launch_split_step(&g, &b->tb, &x, RN_STEP_IMPORT, st));
+    if (synthesis(f, g, cur, prev)) return -1;
+    b->launches += b->timing ? 1 : 0;
+  }
+  if (syn) return 0;
+  for (int f = 0; !sp && f < n_frames; f++) {
     RnGroupDev g = frame_group(f);
     const int cur = (b->parity + f) % RN_SPEC_SLOTS, prev = (cur + RN_SPEC_SLOTS - 1) % RN_SPEC_SLOTS;
     if (!pipelined) {
@@ -435,13 +508,7 @@ int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c) {
     if (hk && hk->before_nn(f, st)) return -1;
     // the network once per model slot (batch_network_step, above)
     if (batch_network_step(b, g, plan, listed, st)) return -1;
-    {
-      TimedLaunch t(b, 2);
-      b->cur_k3[f & 7] = t.on ? t.stop() : (pipelined ? b->own_k3[f & 7] : nullptr);
-      g.link = link > 1 ? link : 0;  // (rn_dev.h: RnGroupDev::link -- K3's copy alone; 0: today's launch)
-      const RnGroupDev g3 = batch_k3_group(b, g);  // (... with the effective output tables; without out tables g itself)
-      HIP_OK(rn_launch_synthesis(&g3, &b->tb, d_out + buf(f) * fstep, s16, cur, prev, plan.k3, st, t.start(), b->cur_k3[f & 7]));
-    }
+    if (synthesis(f, g, cur, prev)) return -1;
     if (hk && hk->after_k3(f, st)) return -1;
     // (schedule 1: the high-pass three frames ahead goes out HERE, behind the synthesis launch whose end it starts at)
     if (pipelined && !side_k1 && f + 3 < n_frames && highpass(f + 3)) return -1;
@@ -487,7 +554,10 @@ extern "C" int rnnoise_batch_process_device_masked_s16(RNNoiseBatch *b, short *d
 // caller) stages the list too, and its buffers have n_rows rows.
 int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c) {
   const int n_frames = c.n_frames;
-  if (!b || !c.out || !c.in || n_frames < 0) return -1;
+  // one half of the step (shim.h: SplitCall; batch_split.cpp): its rows are host memory too, under the caller's strides
+  const SplitCall *const sp = c.split;
+  const bool ana = sp && sp->analyze, syn = sp && !sp->analyze;
+  if ((batch_split_busy(b) && !sp) || !b || (!c.out && !ana) || (!c.in && !syn) || n_frames < 0) return -1;
   if (n_frames == 0) return 0;
   const size_t rows = c.list ? c.n_rows : b->n;
   const size_t M = batch_frame_samples(b), esz = c.s16 ? 2 : 4;
@@ -517,21 +587,55 @@ int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c) {
   };
   const size_t fs = (size_t)n_frames * rows, pcm = fs * M * esz;
   DevScratch d;
-  const size_t o_in = d.carve(pcm), o_out = d.carve(pcm), o_vad = d.carve(fs * 4), o_gains = d.carve(fs * RN_NB_BANDS * 4),
-               o_act = d.carve(fs), o_list = d.carve(c.list ? rows * sizeof(int) : 0);
+  // (a half of the step has no use for the other half's PCM buffer, the analysis half none for vad and gains)
+  const size_t o_in = d.carve(syn ? 0 : pcm), o_out = d.carve(ana ? 0 : pcm), o_vad = d.carve(ana ? 0 : fs * 4),
+               o_gains = d.carve(ana ? 0 : fs * RN_NB_BANDS * 4),
+               o_act = d.carve(fs), o_list = d.carve(c.list ? rows * sizeof(int) : 0),
+               o_feat = d.carve(ana ? fs * RN_NB_FEATURES * 4 : 0), o_sil = d.carve(ana ? fs * 4 : 0);
   if (d.alloc()) return -1;
+  // the half's rows in the default layout on the device: [frame][stream][row]
+  SplitCall dsp;
+  std::vector<float> tight;
+  if (sp) {
+    const long N = (long)rows;
+    dsp.analyze = ana;
+    dsp.features = d.at<float>(o_feat), dsp.feat_fs = N * RN_NB_FEATURES, dsp.feat_rs = RN_NB_FEATURES;
+    dsp.silence = d.at<int>(o_sil);
+    dsp.gains = d.at<float>(o_gains), dsp.gains_fs = N * RN_NB_BANDS, dsp.gains_rs = RN_NB_BANDS;
+    dsp.vad = d.at<float>(o_vad), dsp.vad_fs = N, dsp.vad_rs = 1;
+  }
+  if (syn) {  // (rows of a silent frame go up with the others; the device does not read them)
+    tight.resize(fs * RN_NB_BANDS);
+    for (size_t f = 0; f < (size_t)n_frames; f++)
+      for (size_t r = 0; r < rows; r++)
+        memcpy(&tight[(f * rows + r) * RN_NB_BANDS], sp->gains + f * sp->gains_fs + r * sp->gains_rs, RN_NB_BANDS * 4);
+    HIP_OK(hipMemcpy(d.at<char>(o_gains), tight.data(), fs * RN_NB_BANDS * 4, hipMemcpyHostToDevice));
+    for (size_t f = 0; f < (size_t)n_frames; f++)
+      for (size_t r = 0; r < rows; r++) tight[f * rows + r] = sp->vad[f * sp->vad_fs + r * sp->vad_rs];
+    HIP_OK(hipMemcpy(d.at<char>(o_vad), tight.data(), fs * 4, hipMemcpyHostToDevice));
+  }
   const ProcessCall dc{.out = d.at<char>(o_out), .in = d.at<char>(o_in), .vad = c.vad ? d.at<float>(o_vad) : nullptr,
                        .gains = c.gains ? d.at<float>(o_gains) : nullptr, .n_frames = n_frames, .s16 = c.s16,
                        .active = c.active ? d.at<uint8_t>(o_act) : nullptr, .list = c.list ? d.at<int>(o_list) : nullptr,
-                       .n_rows = c.list ? c.n_rows : 0, .packed = true};  // the same call on the staged copies, on the null stream
-  if (pcm_copy(d.at<char>(o_in), c.in, true)) return -1;
+                       .n_rows = c.list ? c.n_rows : 0, .packed = true,
+                       .split = sp ? &dsp : nullptr};  // the same call on the staged copies, on the null stream
+  if (!syn && pcm_copy(d.at<char>(o_in), c.in, true)) return -1;
   // `out` goes up too where the device leaves parts of it alone: absent rows, the part of a row behind the frame of a stream of a
   // rate table or an out-rate table, or behind a companded stream's bytes, keep the caller's values
-  if ((c.active || c.list || b->g.rs_Ls || b->out_Ls || (c.s16 && (b->g.pcm_fmt || b->out_fmt))) && pcm_copy(dc.out, c.out, true)) return -1;
+  if (!ana && (c.active || c.list || b->g.rs_Ls || b->out_Ls || (c.s16 && (b->g.pcm_fmt || b->out_fmt))) && pcm_copy(dc.out, c.out, true)) return -1;
   if (c.active) HIP_OK(hipMemcpy(d.at<uint8_t>(o_act), c.active, fs, hipMemcpyHostToDevice));
   if (c.list) HIP_OK(hipMemcpy(d.at<int>(o_list), c.list, rows * sizeof(int), hipMemcpyHostToDevice));
   if (batch_process_device_impl(b, dc)) return -1;
   HIP_OK(hipDeviceSynchronize());
+  if (ana) {  // the features to the caller's rows, 65 floats each and nothing around them; the silence words as they lie
+    tight.resize(fs * RN_NB_FEATURES);
+    HIP_OK(hipMemcpy(tight.data(), dsp.features, fs * RN_NB_FEATURES * 4, hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < (size_t)n_frames; f++)
+      for (size_t r = 0; r < rows; r++)
+        memcpy(sp->features + f * sp->feat_fs + r * sp->feat_rs, &tight[(f * rows + r) * RN_NB_FEATURES], RN_NB_FEATURES * 4);
+    if (sp->silence) HIP_OK(hipMemcpy(sp->silence, dsp.silence, fs * 4, hipMemcpyDeviceToHost));
+    return 0;
+  }
   if (pcm_copy(c.out, dc.out, false)) return -1;
   if (c.vad) HIP_OK(hipMemcpy(c.vad, dc.vad, fs * 4, hipMemcpyDeviceToHost));
   if (c.gains) HIP_OK(hipMemcpy(c.gains, dc.gains, fs * RN_NB_BANDS * 4, hipMemcpyDeviceToHost));
@@ -555,6 +659,7 @@ extern "C" int rnnoise_batch_process_masked_s16(RNNoiseBatch *b, short *out, con
 extern "C" int rnnoise_batch_process_device_list(RNNoiseBatch *b, float *d_out, const float *d_in, float *d_vad, float *d_gains,
                                                  const int *d_streams, int n_rows, const unsigned char *d_active, int n_frames,
                                                  void *hip_stream) {
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!d_streams && n_rows == 0) return b ? 0 : -1;
   return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
                                        .stream = hip_stream, .active = d_active, .list = d_streams, .n_rows = n_rows});
@@ -563,6 +668,7 @@ extern "C" int rnnoise_batch_process_device_list(RNNoiseBatch *b, float *d_out, 
 extern "C" int rnnoise_batch_process_device_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, float *d_vad, float *d_gains,
                                                      const int *d_streams, int n_rows, const unsigned char *d_active, int n_frames,
                                                      void *hip_stream) {
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!d_streams && n_rows == 0) return b ? 0 : -1;
   return batch_process_device_impl(b, {.out = d_out, .in = d_in, .vad = d_vad, .gains = d_gains, .n_frames = n_frames,
                                        .stream = hip_stream, .s16 = true, .active = d_active, .list = d_streams, .n_rows = n_rows});
@@ -648,6 +754,7 @@ int chunk_ready(RNNoiseBatch *b, int F, size_t rows, hipStream_t st) {
 int chunks_device(RNNoiseBatch *b, void *d_out, const void *d_in, const int *d_counts, int max_count, const int *d_streams, int n_rows,
                   float *d_vad, float *d_gains, int *d_frames, void *hip_stream, bool s16) {
   if (!b || !d_out || !d_in || !d_counts || max_count < 0 || chunk_refused(b)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const bool listed = d_streams || n_rows;
   if (listed && (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !d_streams))) return -1;
   if (max_count == 0 || (listed && n_rows == 0)) return 0;
@@ -684,6 +791,7 @@ int chunks_device(RNNoiseBatch *b, void *d_out, const void *d_in, const int *d_c
 int chunks_host(RNNoiseBatch *b, void *out, const void *in, const int *counts, int max_count, const int *streams, int n_rows, float *vad,
                 float *gains, int *frames, bool s16) {
   if (!b || !out || !in || !counts || max_count < 0 || chunk_refused(b)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const bool listed = streams || n_rows;
   if (listed && (n_rows < 0 || n_rows > b->n || (n_rows > 0 && !streams))) return -1;
   const size_t N = listed ? n_rows : b->n;
@@ -743,22 +851,26 @@ extern "C" int rnnoise_batch_process_chunks_s16(RNNoiseBatch *b, short *out, con
 extern "C" int rnnoise_batch_process_device_chunks_list(RNNoiseBatch *b, float *d_out, const float *d_in, const int *d_counts,
                                                         int max_count, const int *d_streams, int n_rows, float *d_vad, float *d_gains,
                                                         int *d_frames, void *hip_stream) {
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!d_streams && n_rows == 0) return b && d_out && d_in && d_counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
   return chunks_device(b, d_out, d_in, d_counts, max_count, d_streams, n_rows, d_vad, d_gains, d_frames, hip_stream, false);
 }
 extern "C" int rnnoise_batch_process_device_chunks_list_s16(RNNoiseBatch *b, short *d_out, const short *d_in, const int *d_counts,
                                                             int max_count, const int *d_streams, int n_rows, float *d_vad,
                                                             float *d_gains, int *d_frames, void *hip_stream) {
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!d_streams && n_rows == 0) return b && d_out && d_in && d_counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
   return chunks_device(b, d_out, d_in, d_counts, max_count, d_streams, n_rows, d_vad, d_gains, d_frames, hip_stream, true);
 }
 extern "C" int rnnoise_batch_process_chunks_list(RNNoiseBatch *b, float *out, const float *in, const int *counts, int max_count,
                                                  const int *streams, int n_rows, float *vad, float *gains, int *frames) {
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!streams && n_rows == 0) return b && out && in && counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
   return chunks_host(b, out, in, counts, max_count, streams, n_rows, vad, gains, frames, false);
 }
 extern "C" int rnnoise_batch_process_chunks_list_s16(RNNoiseBatch *b, short *out, const short *in, const int *counts, int max_count,
                                                      const int *streams, int n_rows, float *vad, float *gains, int *frames) {
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!streams && n_rows == 0) return b && out && in && counts && max_count >= 0 && !chunk_refused(b) ? 0 : -1;
   return chunks_host(b, out, in, counts, max_count, streams, n_rows, vad, gains, frames, true);
 }
@@ -783,6 +895,7 @@ extern "C" int rnnoise_batch_train_features_device(RNNoiseBatch *b, float *d_rec
                                                    void *hip_stream) {
   if (!b || !d_records || !d_clean || !d_noisy || !d_vad || !d_lowpass || !d_band_lp || !d_noise_free || n_frames < 0)
     return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (b->per_stream || b->g.rs_L || b->out_Ls || b->row_stride || b->channels > 1) return -1;  // (extraction runs in lock-step frame phase, at 48 kHz in and out, in the default PCM layout, one row per slot, only)
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   ON_DEVICE(b->device);
@@ -811,6 +924,7 @@ extern "C" int rnnoise_batch_train_features(RNNoiseBatch *b, float *records, con
                                             const int *noise_free, int n_frames) {
   if (!b || !records || !clean || !noisy || !vad || !lowpass || !band_lp || !noise_free || n_frames <= 0 || b->per_stream || b->g.rs_L || b->out_Ls || b->row_stride || b->channels > 1)
     return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   const size_t N = b->n, fN = (size_t)n_frames * N, fb = fN * RN_FRAME_SIZE * 4;
   DevScratch d;

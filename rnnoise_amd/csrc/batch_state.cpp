@@ -18,6 +18,7 @@ int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) 
 
 extern "C" int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n) {
   if (!b || n < 0 || (n > 0 && !streams)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   for (int i = 0; i < n; i++)
     if (streams[i] < 0 || streams[i] >= b->n) return -1;
   if (n == 0) return 0;
@@ -35,6 +36,7 @@ extern "C" int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, 
 
 extern "C" int rnnoise_batch_reset_streams_device(RNNoiseBatch *b, const int *d_streams, int n, void *hip_stream) {
   if (!b || n < 0 || (n > 0 && !d_streams)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (n == 0) return 0;
   ON_DEVICE(b->device);
   return reset_streams_on(b, d_streams, n, static_cast<hipStream_t>(hip_stream));
@@ -60,6 +62,7 @@ const int *phase_of(const RNNoiseBatch *b, int s) { return b->per_stream ? b->ph
 // the batch has in flight (the caller's streams are not known here, so the device is drained first).
 extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
   if (!b || !f || s < 0 || s >= b->n) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
   if (stage_ready(b)) return -1;
@@ -72,6 +75,7 @@ extern "C" int rnnoise_batch_export_state(RNNoiseBatch *b, int s, float *f) {
 
 extern "C" int rnnoise_batch_import_state(RNNoiseBatch *b, int s, const float *f) {
   if (!b || !f || s < 0 || s >= b->n) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!analysis_is_pitch_tail(f)) {
     fprintf(stderr, "[rnnoise_amd] import_state: analysis_mem differs from the tail of pitch_buf\n");
     return -1;
@@ -98,6 +102,7 @@ static_assert(RNNOISE_AMD_SNAP_FLOATS == RN_SNAP_FLOATS && RN_SNAP_FLOATS % 4 ==
 namespace {
 bool snap_args_ok(const RNNoiseBatch *b, const void *snap, const int *streams, int n) {
   if (!b || n < 0 || n > b->n || (n > 0 && !snap)) return false;
+  if (batch_split_busy(b)) return false;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (n > 0 && !streams && n != b->n) return false;  // (no list: the whole batch, stream i = row i)
   return true;
 }

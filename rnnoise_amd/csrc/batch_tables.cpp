@@ -114,6 +114,7 @@ int restart_changed_halves(RNNoiseBatch *b, const std::vector<uint8_t> &cur, con
 
 extern "C" int rnnoise_batch_set_pcm_rate(RNNoiseBatch *b, int hz) {
   if (!b || !rate_code(hz)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const int old = b->pcm_rate;
   b->frame_stride = b->row_stride = 0;  // (a PCM layout is in samples of the old rate's frame: dropped by every call)
   ON_DEVICE(b->device);
@@ -147,6 +148,7 @@ extern "C" int rnnoise_batch_pcm_rate(const RNNoiseBatch *b) { return b ? b->pcm
 // reads as the batch's own divisor -- the getter's default too.
 extern "C" int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned char *rates) {
   if (!b) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const int Lb = rate_code(b->pcm_rate);
   if (rates)
     for (int s = 0; s < b->n; s++)
@@ -186,6 +188,7 @@ extern "C" int rnnoise_batch_set_stream_rates(RNNoiseBatch *b, const unsigned ch
 
 extern "C" int rnnoise_batch_set_stream_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream) {
   if (!b || !d_rates) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   const hipStream_t st = static_cast<hipStream_t>(hip_stream);
   if (rs_alloc(b, st) || table_set_device(b, b->rate_map, 1, d_rates, st)) return -1;
@@ -214,6 +217,7 @@ extern "C" int rnnoise_batch_stream_rates(RNNoiseBatch *b, unsigned char *rates)
 // input codes.
 extern "C" int rnnoise_batch_set_stream_out_rates(RNNoiseBatch *b, const unsigned char *rates) {
   if (!b) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const int Lb = rate_code(b->pcm_rate);
   if (rates)
     for (int s = 0; s < b->n; s++)
@@ -236,6 +240,7 @@ extern "C" int rnnoise_batch_set_stream_out_rates(RNNoiseBatch *b, const unsigne
 
 extern "C" int rnnoise_batch_set_stream_out_rates_device(RNNoiseBatch *b, const unsigned char *d_rates, void *hip_stream) {
   if (!b || !d_rates) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   const hipStream_t st = static_cast<hipStream_t>(hip_stream);
   if (rs_alloc(b, st) || table_set_device(b, b->out_rate_map, 1, d_rates, st)) return -1;
@@ -257,6 +262,7 @@ extern "C" int rnnoise_batch_stream_out_rates(RNNoiseBatch *b, unsigned char *ra
 // the one of a batch that never saw these calls.
 extern "C" int rnnoise_batch_set_pcm_layout(RNNoiseBatch *b, long frame_stride, long row_stride) {
   if (!b || !rn_pcm_layout_ok(frame_stride, row_stride)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());  // (synchronous: a call in flight keeps what it was launched with)
   b->frame_stride = frame_stride;
@@ -283,6 +289,7 @@ extern "C" int rnnoise_amd_pcm_layout_fits(long frame_stride, long row_stride, i
 // RnStepShape::channels); at 1 nothing is handed on and every launch is the one of a batch that never saw these calls.
 extern "C" int rnnoise_batch_set_pcm_channels(RNNoiseBatch *b, int channels) {
   if (!b || !rn_pcm_channels_ok(channels, b->n)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const int old = b->channels;
   if (channels == old) return old;
   ON_DEVICE(b->device);
@@ -305,6 +312,7 @@ extern "C" int rnnoise_amd_pcm_channels_fit(long frame_stride, long row_stride, 
 // nothing is handed on and every launch is the one of a batch that never saw these calls.
 extern "C" int rnnoise_batch_set_gain_link(RNNoiseBatch *b, int k) {
   if (!b || !rn_pcm_channels_ok(k, b->n)) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   const int old = b->link;
   if (k == old) return old;
   ON_DEVICE(b->device);
@@ -323,6 +331,7 @@ extern "C" int rnnoise_batch_gain_link(const RNNoiseBatch *b) { return b ? b->li
 // reads as linear int16 rows -- the getter's default too.
 extern "C" int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsigned char *formats) {
   if (!b) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (formats)
     for (int s = 0; s < b->n; s++)
       if (formats[s] > RNNOISE_AMD_PCM_ALAW) return -1;
@@ -335,6 +344,7 @@ extern "C" int rnnoise_batch_set_stream_formats(RNNoiseBatch *b, const unsigned 
 
 extern "C" int rnnoise_batch_set_stream_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream) {
   if (!b || !d_formats) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   if (table_set_device(b, b->fmt_map, 1, d_formats, static_cast<hipStream_t>(hip_stream))) return -1;
   b->g.pcm_fmt = b->fmt_map;
@@ -356,6 +366,7 @@ extern "C" int rnnoise_batch_stream_formats(RNNoiseBatch *b, unsigned char *form
 // batch's end touches it.  A byte that names no law reads as linear; without a table the getter gives the input formats.
 extern "C" int rnnoise_batch_set_stream_out_formats(RNNoiseBatch *b, const unsigned char *formats) {
   if (!b) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (formats)
     for (int s = 0; s < b->n; s++)
       if (formats[s] > RNNOISE_AMD_PCM_ALAW) return -1;
@@ -368,6 +379,7 @@ extern "C" int rnnoise_batch_set_stream_out_formats(RNNoiseBatch *b, const unsig
 
 extern "C" int rnnoise_batch_set_stream_out_formats_device(RNNoiseBatch *b, const unsigned char *d_formats, void *hip_stream) {
   if (!b || !d_formats) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   if (table_set_device(b, b->out_fmt_map, 1, d_formats, static_cast<hipStream_t>(hip_stream))) return -1;
   b->out_fmt = b->out_fmt_map;
@@ -390,6 +402,7 @@ extern "C" int rnnoise_batch_stream_out_formats(RNNoiseBatch *b, unsigned char *
 // NULL is refused.  The kernels read an entry that names no slot as slot 0; the getter hands the bytes out as they are.
 extern "C" int rnnoise_batch_add_model(RNNoiseBatch *b, RNNModel *model) {
   if (!b || !model || b->n_models >= RNNOISE_AMD_MAX_MODELS) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   RnModelDev md;
   if (model_on_device(model, b->device, md)) return -1;
@@ -409,6 +422,7 @@ extern "C" int rnnoise_batch_add_model(RNNoiseBatch *b, RNNModel *model) {
 
 extern "C" int rnnoise_batch_set_stream_models(RNNoiseBatch *b, const unsigned char *models) {
   if (!b || !models) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   for (int s = 0; s < b->n; s++)
     if (models[s] >= b->n_models) return -1;
   if (!b->model_map) return 0;
@@ -418,6 +432,7 @@ extern "C" int rnnoise_batch_set_stream_models(RNNoiseBatch *b, const unsigned c
 
 extern "C" int rnnoise_batch_set_stream_models_device(RNNoiseBatch *b, const unsigned char *d_models, void *hip_stream) {
   if (!b || !d_models) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!b->model_map) return 0;
   ON_DEVICE(b->device);
   return table_set_device(b, b->model_map, 1, d_models, static_cast<hipStream_t>(hip_stream));
@@ -458,6 +473,7 @@ int ctl_arm(RNNoiseBatch *b, hipStream_t st) {
 
 extern "C" int rnnoise_batch_set_stream_controls(RNNoiseBatch *b, const float *ctl) {
   if (!b) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (ctl)
     for (int s = 0; s < b->n; s++)
       if (!ctl_entry_ok(ctl + (size_t)s * RN_CTL_FLOATS)) return -1;
@@ -472,6 +488,7 @@ extern "C" int rnnoise_batch_set_stream_controls(RNNoiseBatch *b, const float *c
 
 extern "C" int rnnoise_batch_set_stream_controls_device(RNNoiseBatch *b, const float *d_ctl, void *hip_stream) {
   if (!b || !d_ctl) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   ON_DEVICE(b->device);
   const hipStream_t st = static_cast<hipStream_t>(hip_stream);
   if (ctl_arm(b, st)) return -1;

@@ -1686,12 +1686,42 @@ __device__ __forceinline__ void eval_step_body(const RnGroupDev &g, const RnEval
   }
 }
 
+// The staging steps of the split calls (rn_dev.h: RnSplitStep), one wave per stream, lane = element.  Every access is one float or
+// one int: the caller's rows may lie at any 4-byte aligned place.  A silent frame's gain and vad rows are not read at all.
+__device__ __forceinline__ void split_step_body(const RnGroupDev &g, const RnSplitStep &p, bool exporting) {
+  const int s = (int)blockIdx.x, lane = (int)threadIdx.x;
+  if (exporting) {
+    const float *feat = g.features + (size_t)s * RN_FEAT_ROW;
+    float *row = p.feat + (long long)s * p.feat_stride;
+    for (int i = lane; i < RN_NB_FEATURES; i += WAVE) row[i] = feat[i];
+    if (lane == 0) {
+      const int w = g.silence[s];
+      p.sil_keep[s] = w;
+      if (p.sil_out) p.sil_out[s] = w;
+    }
+    return;
+  }
+  const bool silent = p.sil[s] != 0;  // (wave-uniform)
+  if (lane < RN_NB_BANDS) {
+    float v = 0.f;
+    if (!silent) v = p.gains[(long long)s * p.gains_stride + lane];
+    g.gains[(size_t)s * RN_NB_BANDS + lane] = v;
+  }
+  if (lane == 0) {
+    float v = 0.f;
+    if (!silent) v = p.vad[(long long)s * p.vad_stride];
+    g.vad[s] = v;
+  }
+}
+
 // TRAINING-mode variant: the inner loop of src/dump_features.c:466-491 -- or, with tr.step.on (a launch argument:
-// the branch is wave-uniform and taken before anything else is read), the record step of the feature calls
+// the branch is wave-uniform and taken before anything else is read), the record step of the feature calls or a staging step of the
+// split calls
 extern "C" __global__ void __launch_bounds__(WAVE)
 rn_train_features_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity, RnTrainArgs tr) {
   if (tr.step.on) {
-    eval_step_body(g, tr.step);
+    if (tr.step.on == RN_STEP_EVAL) eval_step_body(g, tr.step);
+    else split_step_body(g, tr.split, tr.step.on == RN_STEP_EXPORT);
     return;
   }
   analysis_body<true, 1>(g, tb, slot, parity, tr);
@@ -2184,7 +2214,15 @@ extern "C" hipError_t rn_launch_train_features(const RnGroupDev *g, const RnTabl
 extern "C" hipError_t rn_launch_eval_step(const RnGroupDev *g, const RnTablesDev *tb, const RnEvalStep *step, hipStream_t st) {
   RnTrainArgs tr{};
   tr.step = *step;
-  tr.step.on = 1;
+  tr.step.on = RN_STEP_EVAL;
+  hipLaunchKernelGGL(rn_train_features_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, *g, *tb, 0, 0, tr);
+  return hipGetLastError();
+}
+// a staging step of the split calls (rn_dev.h: RnSplitStep; mode: RN_STEP_EXPORT | RN_STEP_IMPORT): the same kernel once more
+extern "C" hipError_t rn_launch_split_step(const RnGroupDev *g, const RnTablesDev *tb, const RnSplitStep *step, int mode, hipStream_t st) {
+  RnTrainArgs tr{};
+  tr.split = *step;
+  tr.step.on = mode;
   hipLaunchKernelGGL(rn_train_features_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, *g, *tb, 0, 0, tr);
   return hipGetLastError();
 }

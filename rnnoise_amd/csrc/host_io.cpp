@@ -504,6 +504,7 @@ static int batch_process_pageable(RNNoiseBatch *b, char *out, const char *in, fl
 
 static int batch_process_host_impl(RNNoiseBatch *b, void *out_v, const void *in_v, float *vad, float *gains, int n_frames, bool s16) {
   if (!b || !out_v || !in_v || n_frames < 0) return -1;
+  if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (n_frames == 0) return 0;
   ON_DEVICE(b->device);
   const char *in = static_cast<const char *>(in_v);

@@ -343,8 +343,28 @@ struct RnRows {
 // target null: nothing is scored (and gains, vad, sums are not read); stage null: nothing is staged (the call's last launch).
 // Rows are read float by float: any 4-byte aligned pointer and stride.
 #define RN_EVAL_SUMS 4  // = RNNOISE_AMD_EVAL_SUMS: doubles per stream {sum of gain terms, sum of vad terms, frames scored, 0}
+// Two further modes of the same launch serve the split calls (include/rnnoise_amd.h: rnnoise_batch_analyze_device,
+// rnnoise_batch_synthesize_device; batch_split.cpp), one wave per stream s, lane = element, single-float accesses:
+//   RN_STEP_EXPORT  behind K1 of a frame, on K1's stream: the 65 features K1 left in g.features[s] go to feat + s * feat_stride, its
+//                   silence word g.silence[s] to sil_keep[s] (the pending frame's, which K3 will read) and to sil_out[s] (the
+//                   caller's, or null)
+//   RN_STEP_IMPORT  in front of K3 of a pending frame: gains + s * gains_stride (32 floats) and vad[s * vad_stride] go to g.gains[s]
+//                   and g.vad[s] -- the batch's scratch, where K3 looks for them -- as they are; where sil[s] != 0 the caller's rows
+//                   are not read and zeros go there, which is what the network writes on a silent frame
+enum { RN_STEP_EVAL = 1, RN_STEP_EXPORT = 2, RN_STEP_IMPORT = 3 };
+struct RnSplitStep {
+  float *feat;             // export: the caller's feature rows of this frame
+  long long feat_stride;
+  int *sil_keep, *sil_out; // export: [N] each; sil_out may be null
+  const int *sil;          // import: [N] the pending frame's silence words
+  const float *gains;      // import: the caller's gain rows of this frame
+  long long gains_stride;
+  const float *vad;        // import: the caller's vad row of this frame
+  long long vad_stride;
+};
 struct RnEvalStep {
-  int on;                  // 0: the extraction launch -- nothing below is read
+  int on;                  // 0: the extraction launch -- nothing below is read; RN_STEP_EVAL: the fields below; RN_STEP_EXPORT /
+                           // RN_STEP_IMPORT: RnTrainArgs::split alone
   const float *stage;      // features of the next step, or null
   const float *target;     // record to score against (features[65] | gain targets[32] | vad target), or null
   long long row_stride;    // floats between the rows of two streams, in `stage` and in `target`
@@ -364,6 +384,7 @@ struct RnTrainArgs {
   const int *noise_free;   // [N] noise_gain==0 && fgnoise_gain==0 (dump_features.c:477)
   float *rec;              // [N][98] out: features[65] | gain targets[32] | vad
   RnEvalStep step;         // step.on: the launch is a record step of the feature calls instead, and nothing above is read
+  RnSplitStep split;       // ... or a staging step of the split calls (step.on = RN_STEP_EXPORT / RN_STEP_IMPORT)
 };
 
 // bits(rcpps(x)) for a positive normal x with bits b, from the 16-bit table entry v = rcp16[(b >> 11) & 0xfff]:

@@ -7,6 +7,7 @@
 //   batch.cpp         rnnoise_batch_*: N streams on one GPU, the frame step as a pipeline over HIP streams and its host-buffer forms,
 //                     training features, timing, debug taps
 //   batch_eval.cpp    the feature calls: the network alone on features that exist, training records scored with the trainer's loss
+//   batch_split.cpp   the split calls: analysis and synthesis as calls of their own around a network of the caller's, the pending frames
 //   batch_tables.cpp  a batch's configuration: PCM rate, strides, channels, the per-stream tables (rates, formats, models, controls)
 //   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
 //   train_mix.hip     training sequences: levels, Viterbi VAD and mix of src/dump_features.c:408-465, host code and kernels
@@ -49,6 +50,7 @@ extern "C" hipError_t rn_launch_synthesis(const RnGroupDev *, const RnTablesDev 
 extern "C" hipError_t rn_launch_train_features(const RnGroupDev *, const RnTablesDev *, const float *, int, int,
                                                const RnTrainArgs *, hipStream_t);
 extern "C" hipError_t rn_launch_eval_step(const RnGroupDev *, const RnTablesDev *, const RnEvalStep *, hipStream_t);
+extern "C" hipError_t rn_launch_split_step(const RnGroupDev *, const RnTablesDev *, const RnSplitStep *, int mode, hipStream_t);
 extern "C" hipError_t rn_launch_nn_vector(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
                                           hipEvent_t);
 // (lds_opt_in: the batch's answer to the kernel's large-LDS opt-in, RNNoiseBatch::lds_one / lds_gru, returned instead of a launch)
@@ -273,6 +275,15 @@ struct RNNoiseBatch {
   float *chunk_fifo = nullptr;
   void *chunk_stage = nullptr;
   size_t chunk_stage_bytes = 0;
+  // split calls (include/rnnoise_amd.h: rnnoise_batch_analyze_device; batch_split.cpp).  split_pending: frames analysed and not yet
+  // synthesised; split_parity: the spectra slot the first of them was analysed at.  split_store: split_cap entries of
+  // rnnoise_amd_split_frame_bytes(n) each -- X | P | Ex Ep Exp | silence words (batch_split_entry) --, grown when a call needs more.
+  // Pending frame f of T keeps its silence words in entry f and, unless it is the last, its spectra too; the last frame's spectra lie
+  // in the batch's own slot, and where that slot is the one synthesis of frame 0 reads as "delayed" (T a multiple of RN_SPEC_SLOTS)
+  // entry T - 1 holds a copy of the delayed spectra, made in front of the last K1 (split_prev_kept)
+  int split_pending = 0, split_parity = 0, split_cap = 0;
+  bool split_prev_kept = false;
+  void *split_store = nullptr;
   // host-fed path (rnnoise_batch_process, host_io.cpp).  `run` carries the kernels and `down` the downloads of both kinds of caller
   struct HostIo {
     hipStream_t up = nullptr, run = nullptr, down = nullptr;
@@ -410,7 +421,36 @@ struct ProcessCall {
   int n_rows = 0;
   FrameIo *hooks = nullptr;  // the pinned ring of the host-fed path (host_io.cpp)
   bool packed = false;  // the buffers are the library's own, in the default layout whatever the batch's (batch_process_staged)
+  const struct SplitCall *split = nullptr;  // one half of the step alone (batch_split.cpp); null: the whole step
 };
+// One split call (include/rnnoise_amd.h: rnnoise_batch_analyze_device, rnnoise_batch_synthesize_device): which half of the step runs,
+// and the caller's rows in place of what the other half would have read or written.  Strides in floats, resolved (never 0).
+struct SplitCall {
+  bool analyze = false;  // K0, K1 and the export step of every frame (ProcessCall::out is not read); else the import step and K3 (::in is not)
+  float *features = nullptr;  // analyze: 65 floats per stream and frame
+  long feat_fs = 0, feat_rs = 0;
+  int *silence = nullptr;     // analyze: [n_frames][N] or null
+  const float *gains = nullptr, *vad = nullptr;  // synthesize: 32 floats / 1 float per stream and frame
+  long gains_fs = 0, gains_rs = 0, vad_fs = 0, vad_rs = 0;
+};
+// the arrays of entry k of a batch's pending store, and the bytes of an entry for n streams (= rnnoise_amd_split_frame_bytes)
+struct SplitEntry {
+  float *X, *P, *E;
+  int *silence;
+};
+inline size_t batch_split_spec_bytes(int n) { return rn_align256((size_t)n * RN_SPEC_STRIDE * 4); }
+inline size_t batch_split_entry_bytes(int n) {
+  return 2 * batch_split_spec_bytes(n) + rn_align256((size_t)n * RN_SPEC_E_ROW * 4) + rn_align256((size_t)n * 4);
+}
+inline SplitEntry batch_split_entry(const RNNoiseBatch *b, int k) {
+  const size_t spec = batch_split_spec_bytes(b->n), e = rn_align256((size_t)b->n * RN_SPEC_E_ROW * 4);
+  uint8_t *p = static_cast<uint8_t *>(b->split_store) + (size_t)k * batch_split_entry_bytes(b->n);
+  return {reinterpret_cast<float *>(p), reinterpret_cast<float *>(p + spec), reinterpret_cast<float *>(p + 2 * spec),
+          reinterpret_cast<int *>(p + 2 * spec + e)};
+}
+// Whether a call that is refused while frames are pending (include/rnnoise_amd.h: "Split calls") has to return -1: every PCM, chunk
+// and training call, state export / import / save / load and every setter start with it
+inline bool batch_split_busy(const RNNoiseBatch *b) { return b && b->split_pending > 0; }
 int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
 int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
 // batch.cpp: the network of one frame on group g, once per model slot, timed as kind 1

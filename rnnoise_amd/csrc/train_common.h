@@ -25,6 +25,15 @@ inline int train_upload(void **slot, size_t capacity, const void *host, size_t b
   return 0;
 }
 
+// The training calls are refused while frames of a split call are pending (include/rnnoise_amd.h: "PENDING FRAMES"): the library's
+// own test (shim.h: batch_split_busy).  The host emulation of tests/csrc/hip_emul, which is not compiled by hipcc, has a stand-in
+// batch without split calls: nothing can be pending there.
+#ifdef __HIPCC__
+inline bool train_split_busy(const RNNoiseBatch *b) { return batch_split_busy(b); }
+#else
+inline bool train_split_busy(const RNNoiseBatch *) { return false; }
+#endif
+
 // clip and quantize of a record are flags: 0 or 1
 inline bool train_flag01(int v) { return v == 0 || v == 1; }
 

@@ -421,6 +421,7 @@ extern "C" int rnnoise_batch_train_levels_device(RNNoiseBatch *b, float *d_energ
                                                  const short *d_noise, const short *d_fgnoise, long long speech_len, long long noise_len,
                                                  long long fgnoise_len, const RNNoiseTrainMix *mix, int n_frames, void *hip_stream) {
   if (!b || !d_energy || !d_rms || !d_speech || !d_noise || !d_fgnoise || !mix || n_frames < 1) return -1;
+  if (train_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   TrainMixArgs a{};
   a.energy = d_energy;
   a.rms_out = d_rms;
@@ -432,6 +433,7 @@ extern "C" int rnnoise_batch_train_levels_vad_device(RNNoiseBatch *b, float *d_e
                                                      long long speech_len, long long noise_len, long long fgnoise_len,
                                                      const RNNoiseTrainMix *mix, const int *start_pos, int n_frames, void *hip_stream) {
   if (!b || !d_energy || !d_rms || !d_vad || !d_speech || !d_noise || !d_fgnoise || !mix || n_frames < 1) return -1;
+  if (train_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!rnnoise_amd_train_vad_device_available()) return -1;
   TrainMixArgs a{};
   a.energy = d_energy;
@@ -448,6 +450,7 @@ extern "C" int rnnoise_batch_train_mix_device(RNNoiseBatch *b, float *d_clean, f
   if (!b || !d_clean || !d_noisy || !d_vad_target || !d_noise_free || !d_speech || !d_noise || !d_fgnoise || !mix || !d_rms || !d_vad ||
       n_frames < 1)
     return -1;
+  if (train_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!aligned16(d_clean) || !aligned16(d_noisy)) return -1;  // (stored as float4)
   TrainMixArgs a{};
   a.clean = d_clean;

@@ -306,6 +306,7 @@ int rir_call(RNNoiseBatch *b, void *hip_stream, Launches launches) {
 extern "C" int rnnoise_batch_train_rir_load_device(RNNoiseBatch *b, float *d_spectra, const float *d_rir, const int *lens, int n_rirs,
                                                    void *hip_stream) {
   if (!b || !d_spectra || !d_rir || !lens || n_rirs < 1) return -1;
+  if (train_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (!aligned16(d_spectra) || !aligned16(d_rir)) return -1;
   for (int r = 0; r < n_rirs; r++)
     if (lens[r] < 1 || lens[r] > RIR_MAX) return -1;
@@ -328,6 +329,7 @@ extern "C" int rnnoise_batch_train_rir_device(RNNoiseBatch *b, float *d_clean, f
                                               const RNNoiseTrainRir *rir, void *d_work, long long work_bytes, int n_frames,
                                               void *hip_stream) {
   if (!b || !d_clean || !d_noisy || !d_spectra || !rir || !d_work) return -1;
+  if (train_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
   if (n_frames < 1 || n_frames > (INT_MAX - NFFT) / RN_FRAME_SIZE || work_bytes < (long long)UNIT_BYTES) return -1;
   if (!aligned16(d_clean) || !aligned16(d_noisy) || !aligned16(d_spectra) || !aligned16(d_work)) return -1;
   if (!rnnoise_amd_train_rir_check(rir, b->n, n_rirs)) return -1;

@@ -141,6 +141,35 @@ def register_torch_op():
         return (torch.empty_like(pcm), pcm.new_empty((F, R), dtype=torch.float32),
                 pcm.new_empty((F, R, capi.NB_BANDS), dtype=torch.float32), pcm.new_empty((R,), dtype=torch.int32))
 
+    # the split calls (include/rnnoise_amd.h: rnnoise_batch_analyze_device, rnnoise_batch_synthesize_device): the DSP around a network of
+    # the caller's.  analyze: pcm (T, N, M) float32 or int16 -> features (N, T, 65), the trainer's batch-first tensor, and the silence
+    # words (T, N) int32; the T frames stay pending in the batch.  synthesize: gains (N, T, 32) and vad (N, T, 1) or (N, T) for the
+    # pending frames -> out (T, N, M) of `like`'s dtype (float32 or int16; only its dtype is read).  The frame counter advances in
+    # synthesize, by T.
+    @torch.library.custom_op("rnnoise_amd::analyze", mutates_args=("state",),
+                             schema="(Tensor pcm, Tensor(a!) state, int handle) -> (Tensor, Tensor)")
+    def analyze(pcm, state, handle):
+        res = _OPS[handle]._run_analyze(pcm)
+        state.add_(0)
+        return res
+
+    @analyze.register_fake
+    def _(pcm, state, handle):
+        T, N = pcm.shape[0], pcm.shape[1]
+        return pcm.new_empty((N, T, capi.FEATURES), dtype=torch.float32), pcm.new_empty((T, N), dtype=torch.int32)
+
+    @torch.library.custom_op("rnnoise_amd::synthesize", mutates_args=("state",),
+                             schema="(Tensor gains, Tensor vad, Tensor like, Tensor(a!) state, int handle) -> Tensor")
+    def synthesize(gains, vad, like, state, handle):
+        out = _OPS[handle]._run_synthesize(gains, vad, like.dtype)
+        state.add_(gains.shape[1])
+        return out
+
+    @synthesize.register_fake
+    def _(gains, vad, like, state, handle):
+        N, T = gains.shape[0], gains.shape[1]
+        return gains.new_empty((T, N, _OPS[handle].batch.frame), dtype=like.dtype)
+
     _registered = True
 
 
@@ -231,6 +260,49 @@ class RNNoiseOp:
         tensors, row i belonging to stream idx[i].  Unlisted streams are not touched and the cost follows R.  -> out (R, max_count),
         vad (F, R), gains (F, R, 32), frames (R,) int32 (torch.ops.rnnoise_amd.process_chunks_list)"""
         return self.torch.ops.rnnoise_amd.process_chunks_list(pcm, counts, idx, self.state, self.handle)
+
+    def analyze(self, pcm):
+        """pcm (T, N, M) float32 or int16 CUDA tensor -> features (N, T, 65) float32, silence (T, N) int32; the T frames stay pending
+        until synthesize (torch.ops.rnnoise_amd.analyze)"""
+        return self.torch.ops.rnnoise_amd.analyze(pcm, self.state, self.handle)
+
+    def synthesize(self, gains, vad, like=None):
+        """gains (N, T, 32) and vad (N, T, 1) or (N, T) float32 CUDA tensors for the pending frames -> out (T, N, M), float32 or of
+        `like`'s dtype (torch.ops.rnnoise_amd.synthesize).  On a silent frame the rows are not read."""
+        like = gains if like is None else like
+        return self.torch.ops.rnnoise_amd.synthesize(gains, vad, like, self.state, self.handle)
+
+    def denoise_with(self, net, pcm):
+        """pcm (T, N, M) through analyze -> net -> synthesize in one pair: net maps features (N, T, 65) to (gains (N, T, 32),
+        vad (N, T, 1)) -- any torch module or function; a stateful one keeps its own state from call to call.  -> out (T, N, M)"""
+        with self.torch.no_grad():  # (forward only, like every op of this module)
+            feats, _silence = self.analyze(pcm)
+            gains, vad = net(feats)
+            return self.synthesize(gains.to(self.torch.float32), vad.to(self.torch.float32), like=pcm)
+
+    def _run_analyze(self, pcm):
+        torch = self.torch
+        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.shape[1:] == (self.n, self.batch.frame)
+        self._layout(0, 0)
+        pcm = pcm.contiguous()
+        T = pcm.shape[0]
+        feats = torch.empty((self.n, T, capi.FEATURES), device=pcm.device, dtype=torch.float32)
+        sil = torch.empty((T, self.n), device=pcm.device, dtype=torch.int32)
+        self.batch.analyze_device(feats.data_ptr(), sil.data_ptr(), pcm.data_ptr(), T, feat_rows=(capi.FEATURES, T * capi.FEATURES),
+                                  stream=torch.cuda.current_stream(pcm.device).cuda_stream, s16=pcm.dtype == torch.int16)
+        return feats, sil
+
+    def _run_synthesize(self, gains, vad, dtype):
+        torch = self.torch
+        assert gains.is_cuda and gains.dtype == torch.float32 and gains.dim() == 3 and gains.shape[0] == self.n
+        assert gains.shape[2] == capi.NB_BANDS and dtype in (torch.float32, torch.int16)
+        T = gains.shape[1]
+        assert vad.is_cuda and vad.dtype == torch.float32 and vad.numel() == self.n * T and vad.shape[:2] == (self.n, T)
+        gains, vad = gains.contiguous(), vad.contiguous()
+        out = torch.empty((T, self.n, self.batch.frame), device=gains.device, dtype=dtype)
+        self.batch.synthesize_device(out.data_ptr(), gains.data_ptr(), vad.data_ptr(), T, gain_rows=(capi.NB_BANDS, T * capi.NB_BANDS),
+                                     vad_rows=(1, T), stream=torch.cuda.current_stream(gains.device).cuda_stream, s16=dtype == torch.int16)
+        return out
 
     def reset_streams(self, idx):
         """the listed streams (a sequence or a tensor of indices) back to rnnoise_init()'s state, on torch's current stream without
