@@ -19,8 +19,7 @@ int reset_streams_on(RNNoiseBatch *b, const int *d_list, int n, hipStream_t st) 
 extern "C" int rnnoise_batch_reset_streams(RNNoiseBatch *b, const int *streams, int n) {
   if (!b || n < 0 || (n > 0 && !streams)) return -1;
   if (batch_split_busy(b)) return -1;  // (frames of a split call are pending: include/rnnoise_amd.h)
-  for (int i = 0; i < n; i++)
-    if (streams[i] < 0 || streams[i] >= b->n) return -1;
+  if (n > 0 && !host_list_ok(b, streams, n, false)) return -1;
   if (n == 0) return 0;
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
@@ -127,14 +126,10 @@ constexpr int SNAP_CHUNK = 1024;  // rows of the host forms' staging buffer (27 
 int snap_host(RNNoiseBatch *b, float *snap, const int *streams, int n, bool load) {
   if (!snap_args_ok(b, snap, streams, n)) return -1;
   if (n == 0) return 0;
+  if (!host_list_ok(b, streams, n, load)) return -1;  // (a save may name a stream twice)
   std::vector<int> list((size_t)n);
-  std::vector<uint8_t> seen(load ? (size_t)b->n : 0, 0);
   for (int i = 0; i < n; i++) {
-    const int s = streams ? streams[i] : i;
-    if (s < 0 || s >= b->n) return -1;
     if (load) {
-      if (seen[s]) return -1;
-      seen[s] = 1;
       const float *f = snap + (size_t)i * RN_SNAP_FLOATS;
       int magic;
       memcpy(&magic, f + RN_SNAP_OFF_MAGIC, sizeof magic);
@@ -144,7 +139,7 @@ int snap_host(RNNoiseBatch *b, float *snap, const int *streams, int n, bool load
         return -1;
       }
     }
-    list[i] = s;
+    list[i] = streams ? streams[i] : i;
   }
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());
@@ -220,19 +215,15 @@ int fifo_rec_host(RNNoiseBatch *b, float *rec, const int *streams, int n, bool l
   if (!snap_args_ok(b, rec, streams, n)) return -1;
   if (n == 0) return 0;
   const int M = batch_frame_samples(b);
+  if (!host_list_ok(b, streams, n, load)) return -1;  // (a save may name a stream twice)
   std::vector<int> list((size_t)n);
-  std::vector<uint8_t> seen(load ? (size_t)b->n : 0, 0);
   for (int i = 0; i < n; i++) {
-    const int s = streams ? streams[i] : i;
-    if (s < 0 || s >= b->n) return -1;
     if (load) {
-      if (seen[s]) return -1;
-      seen[s] = 1;
       int hdr[3];  // fill, M, magic
       memcpy(hdr, rec + (size_t)i * RN_CHUNK_REC + RN_CHUNK_OFF_FILL, sizeof hdr);
       if (!rn_chunk_rec_ok(hdr[2], hdr[1], hdr[0], M)) return -1;
     }
-    list[i] = s;
+    list[i] = streams ? streams[i] : i;
   }
   ON_DEVICE(b->device);
   HIP_OK(hipDeviceSynchronize());

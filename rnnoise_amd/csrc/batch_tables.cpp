@@ -1,5 +1,5 @@
 // batch_tables.cpp -- the configuration of a batch's calls: PCM rate, strides and channels, and the per-stream tables (rates and
-// formats of the input side and of the output side, models, controls).  Nothing here launches a kernel: the step (batch.cpp) reads
+// formats of the input side and of the output side, models, controls).  Nothing here launches a kernel: the step (batch_step.cpp) reads
 // what these calls leave in the batch.
 #include "shim.h"
 
@@ -258,7 +258,7 @@ extern "C" int rnnoise_batch_stream_out_rates(RNNoiseBatch *b, unsigned char *ra
 
 // ---- caller-defined PCM strides (include/rnnoise_amd.h) ----
 // Two numbers of the batch.  A process call hands the row stride to K0 / K3 (rn_dev.h: RnGroupDev::pcm_pitch) and steps its frame
-// pointers by the frame stride (batch.cpp: batch_process_device_impl); without a layout both keep their defaults and every launch is
+// pointers by the frame stride (batch_step.cpp: Step::begin); without a layout both keep their defaults and every launch is
 // the one of a batch that never saw these calls.
 extern "C" int rnnoise_batch_set_pcm_layout(RNNoiseBatch *b, long frame_stride, long row_stride) {
   if (!b || !rn_pcm_layout_ok(frame_stride, row_stride)) return -1;
@@ -395,7 +395,7 @@ extern "C" int rnnoise_batch_stream_out_formats(RNNoiseBatch *b, unsigned char *
 }
 
 // ---- per-stream models (include/rnnoise_amd.h) ----
-// The network of every step is launched once per slot (batch.cpp: batch_process_device_impl); the launch of slot k owns the streams
+// The network of every step is launched once per slot (batch_step.cpp: batch_network_step); the launch of slot k owns the streams
 // the [N] slot bytes of model_map put on k (rn_dev.h: rn_owns).
 // This table alone: it exists from the first add_model on, which allocates and zeroes it and points g.model_of / g.n_models from then
 // on; before that every stream is on slot 0, nothing is read, and both setters are no-ops (the host one still checks its entries).

@@ -513,7 +513,7 @@ static int batch_process_host_impl(RNNoiseBatch *b, void *out_v, const void *in_
   return (pinned ? batch_process_pinned : batch_process_pageable)(b, out, in, vad, gains, n_frames, s16);
 }
 
-// (the calls that batch_host_call_staged names take the staged convenience path of the masked calls: batch.cpp)
+// (the calls that batch_host_call_staged names take the staged convenience path of the masked calls: batch_step.cpp)
 extern "C" int rnnoise_batch_process(RNNoiseBatch *b, float *out, const float *in, float *vad, float *gains, int n_frames) {
   if (b && batch_host_call_staged(b, false))
     return batch_process_staged(b, {.out = out, .in = in, .vad = vad, .gains = gains, .n_frames = n_frames});

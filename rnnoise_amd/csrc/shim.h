@@ -4,10 +4,13 @@
 //
 //   model.cpp    "DNNw" blob reader, "RNPK" pack, GPU re-layout of the model, rnnoise_model_* entry points
 //   tables.cpp   static tables by formula, the rcpps profile
-//   batch.cpp         rnnoise_batch_*: N streams on one GPU, the frame step as a pipeline over HIP streams and its host-buffer forms,
-//                     training features, timing, debug taps
+//   batch.cpp         rnnoise_batch_*: N streams on one GPU -- create, destroy, reset, training features, timing, debug taps
+//   batch_step.cpp    the frame step as a pipeline over HIP streams (batch_step.h: its stages), its host-buffer form, the plain, masked
+//                     and list calls
+//   batch_chunks.cpp  the chunk calls: any number of samples per stream through device FIFOs
 //   batch_eval.cpp    the feature calls: the network alone on features that exist, training records scored with the trainer's loss
-//   batch_split.cpp   the split calls: analysis and synthesis as calls of their own around a network of the caller's, the pending frames
+//   batch_split.cpp   the split calls: analysis and synthesis as calls of their own around a network of the caller's -- the two halves
+//                     of the step and their host-buffer forms, the pending frames
 //   batch_tables.cpp  a batch's configuration: PCM rate, strides, channels, the per-stream tables (rates, formats, models, controls)
 //   batch_state.cpp   single streams of a batch: per-stream reset, state export / import, stream snapshots
 //   train_mix.hip     training sequences: levels, Viterbi VAD and mix of src/dump_features.c:408-465, host code and kernels
@@ -221,7 +224,7 @@ struct RNNoiseBatch {
   uint8_t *fmt_map = nullptr;
   // per-stream OUTPUT rates and formats (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates, _out_formats): out_rate_map and
   // out_fmt_map, [N] bytes each; out_Ls / out_fmt point at them while a table is set.  b->g never carries them: K0 and K1 get the
-  // batch's group, with the input tables, and the step points K3's copy at these (batch.cpp: batch_k3_group) -- and gives that copy
+  // batch's group, with the input tables, and the step points K3's copy at these (shim.h: batch_k3_group) -- and gives that copy
   // the resampler fields where the batch's group has none (48 kHz inputs without a rate table: batch_rs_48k).  The state kernels get
   // out_Ls beside a group with those fields (batch_state_group).  Dropped with the rate table by rnnoise_batch_set_pcm_rate
   uint8_t *out_rate_map = nullptr, *out_fmt_map = nullptr;
@@ -268,7 +271,7 @@ struct RNNoiseBatch {
   float *scratch_gains = nullptr, *scratch_vad = nullptr;
   float *debug_buf = nullptr;
   float *state_stage = nullptr;  // one flat state in HBM: export / import go through the gather / scatter kernels
-  // chunk calls (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks; batch.cpp).  chunk_fifo: the streams' sample FIFOs, from
+  // chunk calls (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks; batch_chunks.cpp).  chunk_fifo: the streams' sample FIFOs, from
   // the first chunk call to the batch's end -- [N] records of RN_CHUNK_REC floats (chunk_plan.h; batch_chunk_fifos).  chunk_stage: the frames and the mask of the masked call inside a chunk call, [F][rows][M] floats then, F x rows
   // frames of RN_FRAME_SIZE floats in, [F][rows] bytes -- rows = N, or a list call's n_rows; chunk_stage_bytes of it, which grow when
   // a call needs more
@@ -404,7 +407,7 @@ void pools_free(RNNModel *model);                                    // dropin.c
 RnGroupDev group_view(const RnGroupDev &g, int first, int count);    // batch.cpp
 const RnKnobs &rn_knobs();                                           // batch.cpp: the dispatch switches, read once per process
 void host_io_release(RNNoiseBatch *b);                               // host_io.cpp
-// One process call of a batch: what the entry points of include/rnnoise_amd.h hand to the step (batch_process_device_impl: device
+// One process call of a batch: what the entry points of include/rnnoise_amd.h hand to the step (batch_step.cpp: batch_process_device_impl, device
 // memory, asynchronous on `stream`) or to its host-buffer form (batch_process_staged: host memory through one device allocation,
 // synchronous; stream, hooks and packed are not read).
 struct ProcessCall {
@@ -421,12 +424,10 @@ struct ProcessCall {
   int n_rows = 0;
   FrameIo *hooks = nullptr;  // the pinned ring of the host-fed path (host_io.cpp)
   bool packed = false;  // the buffers are the library's own, in the default layout whatever the batch's (batch_process_staged)
-  const struct SplitCall *split = nullptr;  // one half of the step alone (batch_split.cpp); null: the whole step
 };
-// One split call (include/rnnoise_amd.h: rnnoise_batch_analyze_device, rnnoise_batch_synthesize_device): which half of the step runs,
-// and the caller's rows in place of what the other half would have read or written.  Strides in floats, resolved (never 0).
+// One split call (include/rnnoise_amd.h: rnnoise_batch_analyze_device, rnnoise_batch_synthesize_device; batch_split.cpp): the caller's
+// rows in place of what the other half of the step would have read or written.  Strides in floats, resolved (never 0).
 struct SplitCall {
-  bool analyze = false;  // K0, K1 and the export step of every frame (ProcessCall::out is not read); else the import step and K3 (::in is not)
   float *features = nullptr;  // analyze: 65 floats per stream and frame
   long feat_fs = 0, feat_rs = 0;
   int *silence = nullptr;     // analyze: [n_frames][N] or null
@@ -451,12 +452,15 @@ inline SplitEntry batch_split_entry(const RNNoiseBatch *b, int k) {
 // Whether a call that is refused while frames are pending (include/rnnoise_amd.h: "Split calls") has to return -1: every PCM, chunk
 // and training call, state export / import / save / load and every setter start with it
 inline bool batch_split_busy(const RNNoiseBatch *b) { return b && b->split_pending > 0; }
-int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch.cpp
-int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch.cpp
-// batch.cpp: the network of one frame on group g, once per model slot, timed as kind 1
+int batch_process_device_impl(RNNoiseBatch *b, const ProcessCall &c);  // batch_step.cpp: the whole step
+int batch_process_staged(RNNoiseBatch *b, const ProcessCall &c);       // batch_step.cpp: ... on host buffers
+// batch_step.cpp: the network of one frame on group g, once per model slot, timed as kind 1
 int batch_network_step(RNNoiseBatch *b, RnGroupDev &g, const RnPlan &plan, bool listed, hipStream_t st);
-int batch_chunk_restart_all(RNNoiseBatch *b);                          // batch.cpp: every stream's sample FIFOs as after create
-int batch_chunk_fifos_ready(RNNoiseBatch *b, hipStream_t st);          // batch.cpp: ... allocated where the batch has none yet
+int batch_chunk_restart_all(RNNoiseBatch *b);                          // batch_chunks.cpp: every stream's sample FIFOs as after create
+int batch_chunk_fifos_ready(RNNoiseBatch *b, hipStream_t st);          // batch_chunks.cpp: ... allocated where the batch has none yet
+// batch.cpp: whether the n entries of a HOST stream list all lie inside the batch and, with `unique`, name no stream twice; a null
+// list stands for stream i in row i
+bool host_list_ok(const RNNoiseBatch *b, const int *list, int n, bool unique);
 // samples per row and frame at the batch's PCM rate
 inline int batch_frame_samples(const RNNoiseBatch *b) { return b->g.rs_L ? b->g.rs_pitch : RN_FRAME_SIZE; }
 // the sample FIFOs of streams first, first + 1, ... of a batch as the state kernels take them (chunk_plan.h: RnChunkDev, the call's

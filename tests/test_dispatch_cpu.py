@@ -180,8 +180,8 @@ def test_the_launchers_take_the_plan_and_drop_in_frames_the_row_kernels():
         for knob in KNOBS:
             assert f'"RNNOISE_AMD_{knob}"' not in text, (f, knob)
     # one plan per call, the schedule from the same module, the device's facts resolved once per batch
-    batch = _src("batch.cpp")
-    assert "rn_plan(rn_knobs()" in batch and "rn_schedule(rn_knobs()" in batch and "rn_default_nn_path(rn_knobs()" in batch
+    step, batch = _src("batch_step.cpp"), _src("batch.cpp")  # (the step; create)
+    assert "rn_plan(rn_knobs()" in step and "rn_schedule(rn_knobs()" in step and "rn_default_nn_path(rn_knobs()" in batch
     assert "hipDeviceAttributeMultiprocessorCount" in batch and "rn_nn_one_opt_in()" in batch and "rn_nn_gru_opt_in(" in batch
     # drop-in frames take no plan: every one of them is a launch group of the row-list kernels
     dropin = _src("dropin.cpp")
@@ -190,6 +190,6 @@ def test_the_launchers_take_the_plan_and_drop_in_frames_the_row_kernels():
         assert dropin.count(launcher) == 1, launcher
     for launcher in ("rn_launch_hp(", "rn_launch_analysis(", "rn_launch_nn_one(", "rn_launch_nn_vector(", "rn_launch_synthesis("):
         assert launcher not in dropin, launcher
-    for f in ("batch.cpp", "dropin.cpp", "host_io.cpp"):
+    for f in [f for f in os.listdir(CSRC) if f.startswith("batch")] + ["dropin.cpp", "host_io.cpp"]:
         for knob in KNOBS:
             assert f'"RNNOISE_AMD_{knob}"' not in _src(f), (f, knob)

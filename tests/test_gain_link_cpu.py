@@ -58,8 +58,8 @@ def test_no_new_kernel_and_the_field_is_k3s_alone():
                    for k in re.findall(r"__global__[^(]*?(\w+)\s*\(", open(os.path.join(csrc, f)).read()))
     host = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".cpp")}
     writers = [f for f, text in host.items() for _ in re.findall(r"[.>]link\s*=[^=]", text)]
-    assert sorted(writers) == ["batch.cpp", "batch_tables.cpp"], writers  # (g.link of the step; b->link of the setter)
-    assert "g.link = link > 1 ? link : 0;" in host["batch.cpp"]
+    assert sorted(writers) == ["batch_step.cpp", "batch_tables.cpp"], writers  # (g.link of the step; b->link of the setter)
+    assert "g.link = link > 1 ? link : 0;" in host["batch_step.cpp"]
     for f, text in host.items():
         assert "b->g.link" not in text, f
 
