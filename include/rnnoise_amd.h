@@ -795,6 +795,41 @@ RNNOISE_EXPORT int rnnoise_batch_eval_records(RNNoiseBatch *b, double *sums, flo
                                               long frame_stride, long row_stride, int t0, int n_frames,
                                               const RNNoiseEvalConfig *cfg);
 
+/* Score calls: the scoring of rnnoise_batch_eval_records with the network taken out -- the trainer's loss on predictions of the
+ * caller's, so that a float checkpoint evaluated in torch and the blob exported from it (python -m rnnoise_amd.cli export) are
+ * scored by one piece of code, in double, in one order of additions.
+ *
+ * rnnoise_batch_score_records[_device]: gains / vad hold the predictions of steps t0 .. t0 + n_frames - 1 of n_rows sequences; step t
+ * of row s lies at  base + (t - t0) * frame_stride + s * row_stride  (gains: 32 floats, vad: 1).  records is record 0, record t of
+ * row s at  records + t * rec_frame_stride + s * rec_row_stride  (98 floats), as in eval_records.  Step t is scored against record
+ * t - 1 for every t >= max(first, 1), with the terms of "Feature calls" above; a call with t0 > 0 reads record t0 - 1.  Of a record
+ * only its 33 targets are read.  sums[n_rows][RNNOISE_AMD_EVAL_SUMS] is ADDED to, column for column as eval_records adds: scoring the
+ * gains / vad that eval_records returned gives the doubles eval_records gave, whatever the cut of the frames into calls.
+ * band_sums[n_rows][32], or NULL: band b's gain terms are ADDED to band_sums[s][b] in frame order -- where in the spectrum a blob
+ * loses; the doubles do not depend on the cut either.  A pair of strides 0, 0 is [frame][n_rows][row] for that buffer.
+ *
+ * STATE.  None is read or written: not the network's, not the DSP's, no table, no pending split frame.  The batch only names the
+ * device, n_rows is not tied to its size, and the calls work while split frames are pending.
+ *
+ * rnnoise_amd_score_records_check (host only): 1 when the calls accept the arguments -- cfg as rnnoise_amd_eval_records_check has
+ * it, n_rows >= 1, t0 >= 0, n_frames >= 0, and for each of the three buffers strides that keep its slots disjoint (records: n_rows x
+ * (t0 + n_frames) slots of 98; gains, vad: n_rows x n_frames slots of 32 and of 1); no alignment beyond the float's.  The calls
+ * return -1 where it returns 0, and for a NULL batch, records, gains, vad or sums, with nothing launched.  Device form: asynchronous
+ * on hip_stream, ONE launch whatever n_frames is (one wave per row walks its frames in order).  Host form: synchronous; each buffer
+ * goes up from its base to its last slot read.  Cost: DESIGN.md section 4.30. */
+RNNOISE_EXPORT int rnnoise_amd_score_records_check(const RNNoiseEvalConfig *cfg, long rec_frame_stride, long rec_row_stride,
+                                                   long gain_frame_stride, long gain_row_stride, long vad_frame_stride,
+                                                   long vad_row_stride, int n_rows, int t0, int n_frames);
+RNNOISE_EXPORT int rnnoise_batch_score_records_device(RNNoiseBatch *b, double *d_sums, double *d_band_sums, const float *d_gains,
+                                                      long gain_frame_stride, long gain_row_stride, const float *d_vad,
+                                                      long vad_frame_stride, long vad_row_stride, const float *d_records,
+                                                      long rec_frame_stride, long rec_row_stride, int n_rows, int t0, int n_frames,
+                                                      const RNNoiseEvalConfig *cfg, void *hip_stream);
+RNNOISE_EXPORT int rnnoise_batch_score_records(RNNoiseBatch *b, double *sums, double *band_sums, const float *gains,
+                                               long gain_frame_stride, long gain_row_stride, const float *vad, long vad_frame_stride,
+                                               long vad_row_stride, const float *records, long rec_frame_stride, long rec_row_stride,
+                                               int n_rows, int t0, int n_frames, const RNNoiseEvalConfig *cfg);
+
 /* Split calls: the two DSP halves of the frame step as calls of their own, around a network that is the caller's --
  *     rnnoise_batch_analyze  ->  any network: 65 features in, 32 band gains and a VAD out  ->  rnnoise_batch_synthesize
  * so that a float checkpoint, a model of other dimensions or another architecture is heard through the DSP this library restates to

@@ -83,16 +83,20 @@ def _quantize(w, scale):
     return q
 
 
-def _linear_int8(rec, name, w, bias, sparse=False, diagonal=False):
-    """w: (n_in, n_out) float.  Emits <name>_weights_int8[/_idx/_diag], _subias, _scale, _bias."""
+def _linear_int8(rec, name, w, bias, sparse=False, diagonal=False, scale_with_diagonal=False):
+    """w: (n_in, n_out) float.  Emits <name>_weights_int8[/_idx/_diag], _subias, _scale, _bias.
+    scale_with_diagonal: the scale of a `diagonal` layer is taken on the matrix as it comes, before the diagonal leaves it -- the
+    reference exporter's order (print_linear_layer computes the scale, print_sparse_weight then extracts the diagonal), which
+    rnnoise_amd.export reproduces byte for byte; the default keeps synth_model's bytes what they have always been."""
     n_in, n_out = w.shape
     w = w.copy()
+    scale_full = _compute_scaling(w) if diagonal and scale_with_diagonal else None
     if diagonal:  # GRU recurrent: the three gate diagonals stay in float (common.py extract_diagonal)
         diag = np.concatenate([np.diag(w[:, g * n_in:(g + 1) * n_in]).copy() for g in range(3)])
         for g in range(3):
             w[np.arange(n_in), g * n_in + np.arange(n_in)] = 0
         rec[name + "_weights_diag"] = diag.astype(np.float32)
-    scale = _compute_scaling(w)
+    scale = _compute_scaling(w) if scale_full is None else scale_full
     q = _quantize(w, scale)
     if sparse:
         W, idx = [], []

@@ -85,6 +85,7 @@ EXPORTS = [
     "rnnoise_batch_load_chunk_fifos",
     "rnnoise_amd_eval_records_check", "rnnoise_batch_process_features_device", "rnnoise_batch_process_features",
     "rnnoise_batch_eval_records_device", "rnnoise_batch_eval_records",
+    "rnnoise_amd_score_records_check", "rnnoise_batch_score_records_device", "rnnoise_batch_score_records",
     "rnnoise_amd_split_frame_bytes", "rnnoise_amd_split_rows_check", "rnnoise_batch_split_reserve", "rnnoise_batch_split_pending",
     "rnnoise_batch_analyze_device", "rnnoise_batch_analyze_device_s16", "rnnoise_batch_analyze", "rnnoise_batch_analyze_s16",
     "rnnoise_batch_synthesize_device", "rnnoise_batch_synthesize_device_s16", "rnnoise_batch_synthesize", "rnnoise_batch_synthesize_s16",
@@ -318,6 +319,9 @@ def _load(path, debug):
         L.rnnoise_batch_process_features.argtypes = [vp, fp, fp, fp, lg, lg, C.c_int]
         L.rnnoise_batch_eval_records_device.argtypes = [vp] * 5 + [lg, lg, C.c_int, C.c_int, vp, vp]
         L.rnnoise_batch_eval_records.argtypes = [vp, dp, fp, fp, fp, lg, lg, C.c_int, C.c_int, vp]
+        L.rnnoise_amd_score_records_check.argtypes = [vp] + [lg] * 6 + [C.c_int] * 3
+        L.rnnoise_batch_score_records_device.argtypes = [vp, vp, vp, vp, lg, lg, vp, lg, lg, vp, lg, lg, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.rnnoise_batch_score_records.argtypes = [vp, dp, dp, fp, lg, lg, fp, lg, lg, fp, lg, lg, C.c_int, C.c_int, C.c_int, vp]
         sp = C.POINTER(C.c_short)
         L.rnnoise_amd_split_frame_bytes.restype = C.c_long
         L.rnnoise_amd_split_frame_bytes.argtypes = [C.c_int]
@@ -414,6 +418,17 @@ def eval_records_check(frame_stride: int, row_stride: int, row_floats: int, n_st
     cfg = _eval_cfg(gamma, first)
     return bool(lib().rnnoise_amd_eval_records_check(C.byref(cfg) if cfg is not None else None, int(frame_stride), int(row_stride),
                                                      int(row_floats), int(n_streams), int(t0), int(n_frames)))
+
+
+def score_records_check(n_rows: int, t0: int, n_frames: int, rec_strides=(0, 0), gain_strides=(0, 0), vad_strides=(0, 0), gamma=None,
+                        first=None) -> bool:
+    """rnnoise_amd_score_records_check: whether the score calls accept these arguments -- gamma / first as eval_records_check has
+    them, n_rows >= 1, t0 and n_frames >= 0, and for each buffer a (frame_stride, row_stride) pair that keeps its slots disjoint
+    ((0, 0): [frame][n_rows][row]).  Host only."""
+    cfg = _eval_cfg(gamma, first)
+    return bool(lib().rnnoise_amd_score_records_check(C.byref(cfg) if cfg is not None else None, int(rec_strides[0]), int(rec_strides[1]),
+                                                      int(gain_strides[0]), int(gain_strides[1]), int(vad_strides[0]),
+                                                      int(vad_strides[1]), int(n_rows), int(t0), int(n_frames)))
 
 
 def _rows_arg(rows):
@@ -1331,6 +1346,45 @@ class Batch:
                                                      int(frame_stride), int(row_stride), t0, n_frames,
                                                      C.byref(cfg) if cfg is not None else None, stream or None):
             raise RuntimeError("rnnoise_batch_eval_records_device failed (gamma, first, overlapping slots?)")
+
+    def score_records(self, records, gains, vad, t0: int = 0, sums=None, band_sums=None, gamma=None, first=None,
+                      want_bands: bool = True, layout: str = "frame"):
+        """rnnoise_batch_score_records: the trainer's loss on predictions of the caller's.  records (T, R, >= 98) from record 0 on,
+        gains (n_frames, R, >= 32) and vad (n_frames, R) or (n_frames, R, >= 1) for steps t0 .. t0 + n_frames - 1 (layout "stream":
+        (R, T, ...) each), read where they lie; R is free of the batch's size -> (sums (R, EVAL_SUMS) float64, band_sums (R, 32)
+        float64 or None).  sums / band_sums: arrays that are added to in place, or None for zeroed ones."""
+        x, rfs, rrs, T = self._rows_in(records, REC, layout)
+        g, gfs, grs, n_frames = self._rows_in(gains, NB_BANDS, layout)
+        v = np.ascontiguousarray(vad, np.float32)
+        v, vfs, vrs, Tv = self._rows_in(v[..., None] if v.ndim == 2 else v, 1, layout)
+        R = x.shape[1 if layout == "frame" else 0]
+        assert n_frames == Tv and g.shape[:2] == v.shape[:2] and g.shape[1 if layout == "frame" else 0] == R, (x.shape, g.shape, v.shape)
+        assert 0 <= t0 and t0 + n_frames <= T, (t0, n_frames, T)
+        if sums is None:
+            sums = np.zeros((R, EVAL_SUMS), np.float64)
+        if band_sums is None and want_bands:
+            band_sums = np.zeros((R, NB_BANDS), np.float64)
+        assert sums.dtype == np.float64 and sums.shape == (R, EVAL_SUMS) and sums.flags.c_contiguous
+        assert band_sums is None or (band_sums.dtype == np.float64 and band_sums.shape == (R, NB_BANDS) and band_sums.flags.c_contiguous)
+        cfg = _eval_cfg(gamma, first)
+        dp = C.POINTER(C.c_double)
+        if self._L.rnnoise_batch_score_records(self.h, sums.ctypes.data_as(dp), band_sums.ctypes.data_as(dp) if band_sums is not None else None,
+                                               _fp(g), gfs, grs, _fp(v), vfs, vrs, _fp(x), rfs, rrs, R, t0, n_frames,
+                                               C.byref(cfg) if cfg is not None else None):
+            raise RuntimeError("rnnoise_batch_score_records failed (gamma, first, overlapping slots?)")
+        return sums, band_sums
+
+    def score_records_device(self, d_sums: int, d_band_sums: int, d_gains: int, d_vad: int, d_records: int, n_rows: int, t0: int,
+                             n_frames: int, gain_strides=(0, 0), vad_strides=(0, 0), rec_strides=(0, 0), gamma=None, first=None,
+                             stream: int = 0):
+        """rnnoise_batch_score_records_device on raw device pointers (ints), asynchronous on `stream`, one launch; d_sums
+        [n_rows][EVAL_SUMS] and d_band_sums [n_rows][32] (or 0) float64 are added to; strides are (frame_stride, row_stride) pairs"""
+        cfg = _eval_cfg(gamma, first)
+        if self._L.rnnoise_batch_score_records_device(self.h, d_sums or None, d_band_sums or None, d_gains or None, int(gain_strides[0]),
+                                                      int(gain_strides[1]), d_vad or None, int(vad_strides[0]), int(vad_strides[1]),
+                                                      d_records or None, int(rec_strides[0]), int(rec_strides[1]), int(n_rows), int(t0),
+                                                      int(n_frames), C.byref(cfg) if cfg is not None else None, stream or None):
+            raise RuntimeError("rnnoise_batch_score_records_device failed (gamma, first, overlapping slots?)")
 
     def debug_pitch(self, arm_only: bool = False):
         if arm_only:

@@ -35,6 +35,17 @@ What a blob costs on such a file, in the reference trainer's loss (rnnoise_amd/e
 it ships over every whole sequence of the file, one JSON line with the trainer's three means per model:
 
   python -m rnnoise_amd.cli eval-records validation.f32 --model weights_blob.bin [--model other.bin ...]
+
+From the trainer's checkpoint to the served blob (rnnoise_amd/export.py, float_net.py):
+
+  python -m rnnoise_amd.cli export ckpt.pth out.blob [--densities R,Z,N] [--pack]
+  python -m rnnoise_amd.cli eval-records validation.f32 --model out.blob --checkpoint ckpt.pth
+  python -m rnnoise_amd.cli denoise --checkpoint ckpt.pth --out-dir out a.raw ...
+export writes the "DNNw" blob the reference's exporter and writer make of the checkpoint, byte for byte (--densities: block-sparsified
+first, as the trainer does it; --pack: the GPU-native RNPK form).  eval-records --checkpoint scores the float checkpoint beside the
+blobs with the same scoring code, and prints every blob's difference to it and the 32 per-band means of the gain loss of each.
+denoise --checkpoint runs the float network between the split calls, as --torch-net runs a TorchScript file; without --model the DSP's
+batch is built on the blob exported from that checkpoint.
 """
 from __future__ import annotations
 
@@ -72,7 +83,8 @@ def out_info(info: wav.WavInfo, out_rate=None, out_format=None) -> wav.WavInfo:
 
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
                   vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None,
-                  formats=None, link_channels: bool = False, out_rate=None, out_format=None, torch_net=None, max_store_gb: float = 4.0):
+                  formats=None, link_channels: bool = False, out_rate=None, out_format=None, torch_net=None, max_store_gb: float = 4.0,
+                  checkpoint=None):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 32000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
@@ -91,6 +103,8 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     the blob's network between the split calls (capi.Batch.analyze / synthesize), on the batch's device.  Each group of files then
     goes through ONE pair, whole -- a module's state need not survive a call -- and the call is refused (ValueError, before anything
     runs) where the pending frames would need more than max_store_gb GiB of device memory (capi.split_frame_bytes).
+    checkpoint: a trainer checkpoint instead: rnnoise_amd.float_net's streaming module on the batch's device goes the same way (reset
+    in front of every group of files); max_store_gb applies.
     Returns the frames of every input."""
     os.makedirs(out_dir, exist_ok=True)
     if rates is not None and len(rates) != len(inputs):
@@ -114,15 +128,21 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     for d in files:
         groups.setdefault(d["channels"], []).append(d)
     net = None
-    if torch_net is not None:
+    if torch_net is not None and checkpoint is not None:
+        raise ValueError("--torch-net and --checkpoint both name the network")
+    if torch_net is not None or checkpoint is not None:
         for channels, group in groups.items():
             frames, n = max([d["n_frames"] for d in group] + [0]), len(group) * channels
             need = frames * capi.split_frame_bytes(n)
             if need > max_store_gb * 2 ** 30:
-                raise ValueError(f"--torch-net: {frames} pending frames of {n} streams need {need / 2 ** 30:.2f} GiB of device memory, "
+                raise ValueError(f"--torch-net / --checkpoint: {frames} pending frames of {n} streams need {need / 2 ** 30:.2f} GiB of device memory, "
                                  f"above --max-store-gb {max_store_gb}")
-        import torch
-        net = torch.jit.load(torch_net, map_location=f"cuda:{device}").eval()
+        if checkpoint is not None:
+            from . import float_net
+            net = float_net.load_checkpoint(checkpoint, device=f"cuda:{device}")
+        else:
+            import torch
+            net = torch.jit.load(torch_net, map_location=f"cuda:{device}").eval()
     model = capi.Model(model_blob)
     for channels, group in groups.items():
         _denoise_group(model, group, channels, out_dir, chunk_frames, device, vad_csv, rate, atten_limit_db, vad_gate, vad_hold,
@@ -143,6 +163,8 @@ def _denoise_group(model, files, C, out_dir, chunk_frames, device, vad_csv, rate
     T = max(n_frames + [0])
     if net is not None:
         chunk_frames = max(T, 1)  # (the whole group in one analyze / synthesize pair)
+        if hasattr(net, "reset"):
+            net.reset()  # (a stateful net starts every group as a new sequence)
     batch = capi.Batch(model, N, device=device)
     if rate != 48000:
         batch.set_pcm_rate(rate)
@@ -267,7 +289,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     p = sub.add_parser("denoise")
-    p.add_argument("--model", required=True, help='"DNNw" weight blob (src/write_weights.c format)')
+    p.add_argument("--model", default=None, help='"DNNw" weight blob (src/write_weights.c format); optional beside --checkpoint')
     p.add_argument("--out-dir", required=True)
     p.add_argument("--chunk-frames", type=int, default=100)
     p.add_argument("--device", type=int, default=0)
@@ -289,7 +311,10 @@ def main(argv=None):
                    help="one suppression for the channels of each multichannel WAV file: linked band gains and VAD gate")
     p.add_argument("--torch-net", default=None,
                    help="TorchScript module [N,T,65] -> ([N,T,32], [N,T,1]) that replaces the blob's network (split calls; one pair per file group)")
-    p.add_argument("--max-store-gb", type=float, default=4.0, help="--torch-net: device memory the pending frames may take, in GiB")
+    p.add_argument("--checkpoint", default=None,
+                   help="trainer checkpoint (.pth): its float network replaces the blob's network (split calls; one pair per file group)")
+    p.add_argument("--max-store-gb", type=float, default=4.0,
+                   help="--torch-net / --checkpoint: device memory the pending frames may take, in GiB")
     p.add_argument("inputs", nargs="+")
     p = sub.add_parser("dump-features")
     p.add_argument("--model", required=True, help='"DNNw" weight blob: a batch needs one (the extraction runs no network)')
@@ -307,8 +332,16 @@ def main(argv=None):
     p.add_argument("fgnoise")
     p.add_argument("out")
     p.add_argument("count", type=int)
+    p = sub.add_parser("export")
+    p.add_argument("--densities", type=lambda v: tuple(float(x) for x in v.split(",")), default=None,
+                   help="R,Z,N: block-sparsify the GRU matrices first, to these densities of the reset, update and new gates")
+    p.add_argument("--pack", action="store_true", help="write the GPU-native RNPK pack instead of the DNNw blob")
+    p.add_argument("checkpoint", help="trainer checkpoint (.pth with 'state_dict', or a bare state dict)")
+    p.add_argument("out")
     p = sub.add_parser("eval-records")
-    p.add_argument("--model", required=True, action="append", help='"DNNw" weight blob; repeat to score several on the same records')
+    p.add_argument("--model", default=None, action="append", help='"DNNw" weight blob; repeat to score several on the same records')
+    p.add_argument("--checkpoint", default=None,
+                   help="trainer checkpoint (.pth): scored in float beside the blobs, with their differences to it and per-band means")
     p.add_argument("--sequence-length", type=int, default=2000, help="records per sequence (the trainer: 2000)")
     p.add_argument("--gamma", type=float, default=0.25, help="perceptual exponent of the gain loss (the trainer: 0.25)")
     p.add_argument("--first", type=int, default=4, help="first step that is scored (the trainer: 4)")
@@ -316,6 +349,27 @@ def main(argv=None):
     p.add_argument("--max-streams", type=int, default=65536, help="sequences per slab: the batch size")
     p.add_argument("file", help="float32 records of 98 floats, sequence after sequence (dump-features' output)")
     a = ap.parse_args(argv)
+    if a.cmd == "export":
+        from . import export
+        n = export.export_file(a.checkpoint, a.out, a.densities, a.pack)
+        print(f"wrote {a.out}: {n} bytes ({'RNPK pack' if a.pack else 'DNNw blob'})")
+        return
+    if a.cmd == "eval-records" and (a.checkpoint is not None or not a.model):
+        import json
+
+        from . import evaluate
+        if a.checkpoint is None:
+            ap.error("eval-records: --model or --checkpoint")
+        strip = lambda r: {k: v for k, v in r.items() if k != "per_sequence"}
+        ck = evaluate.evaluate_checkpoint(a.file, a.checkpoint, a.sequence_length, a.gamma, a.first, a.device, a.max_streams)
+        res = evaluate.evaluate_records(a.file, [open(m, "rb").read() for m in a.model or []], a.sequence_length, a.gamma,
+                                        max(a.first, 4), a.device, a.max_streams, bands=True)
+        delta = lambda r: dict(delta_to_checkpoint={k: r[k] - ck[k] for k in ("gain_loss", "vad_loss", "loss")},
+                               band_delta_to_checkpoint=[x - y for x, y in zip(r["band_gain_loss"], ck["band_gain_loss"])])
+        print(json.dumps(dict(file=a.file, sequence_length=a.sequence_length, gamma=a.gamma, first=max(a.first, 4),
+                              checkpoint=dict(checkpoint=a.checkpoint, **strip(ck)),
+                              models=[dict(model=m, **strip(r), **delta(r)) for m, r in zip(a.model or [], res)])))
+        return
     if a.cmd == "eval-records":
         import json
 
@@ -331,9 +385,16 @@ def main(argv=None):
                           a.device, a.rir_list, a.rir_work_mb, a.vad)
         print(f"wrote {a.count} sequences, {n} records")
         return
-    n = denoise_files(open(a.model, "rb").read(), a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
+    if a.model is None and a.checkpoint is None:
+        ap.error("denoise: --model or --checkpoint")
+    if a.model is None:  # (the DSP's batch needs a blob: the one this checkpoint exports to)
+        from . import export
+        model_blob = export.blob_from_state_dict(export.load_state_dict_file(a.checkpoint))
+    else:
+        model_blob = open(a.model, "rb").read()
+    n = denoise_files(model_blob, a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
                       a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels, a.out_rate, a.out_format,
-                      a.torch_net, a.max_store_gb)
+                      a.torch_net, a.max_store_gb, a.checkpoint)
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 

@@ -126,7 +126,127 @@ int eval_host(RNNoiseBatch *b, EvalCall c, double *sums) {
   if (sums) HIP_OK(hipMemcpy(sums, dc.sums, N * RN_EVAL_SUMS * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
+
+// ---- the score calls: the trainer's loss on predictions of the caller's (RN_STEP_SCORE, one launch) ----
+struct ScoreCall {
+  double *sums = nullptr, *band_sums = nullptr;  // [n_rows][RN_EVAL_SUMS], [n_rows][32] or null
+  const float *gains = nullptr, *vad = nullptr;  // step t0 + f, row s at f * frame_stride + s * row_stride
+  long gain_fs = 0, gain_rs = 0, vad_fs = 0, vad_rs = 0;
+  const float *rec = nullptr;                    // record t, row s at t * rec_fs + s * rec_rs
+  long rec_fs = 0, rec_rs = 0;
+  int n_rows = 0, t0 = 0, n_frames = 0;
+  const RNNoiseEvalConfig *cfg = nullptr;
+  void *stream = nullptr;
+};
+bool score_layout_fits(const ScoreCall &c) {
+  return eval_layout_fits(c.rec_fs, c.rec_rs, 98, c.n_rows, c.t0, c.n_frames) &&
+         eval_layout_fits(c.gain_fs, c.gain_rs, RN_NB_BANDS, c.n_rows, 0, c.n_frames) &&
+         eval_layout_fits(c.vad_fs, c.vad_rs, 1, c.n_rows, 0, c.n_frames);
+}
+void score_strides(ScoreCall &c) {
+  eval_strides(c.rec_fs, c.rec_rs, 98, c.n_rows);
+  eval_strides(c.gain_fs, c.gain_rs, RN_NB_BANDS, c.n_rows);
+  eval_strides(c.vad_fs, c.vad_rs, 1, c.n_rows);
+}
+// the first scored step of a call, and how many follow it: step t against record t - 1 for t >= max(first, 1)
+void score_range(const ScoreCall &c, const EvalConfig &cfg, long long &t_first, int &n) {
+  t_first = std::max<long long>(c.t0, std::max(cfg.first, 1));
+  const long long left = (long long)c.t0 + c.n_frames - t_first;
+  n = left > 0 ? (int)left : 0;
+}
+
+int score_device(RNNoiseBatch *b, ScoreCall c) {
+  if (!b || !c.rec || !c.gains || !c.vad || !c.sums) return -1;
+  EvalConfig cfg;
+  if (!eval_config(c.cfg, cfg) || !score_layout_fits(c)) return -1;
+  score_strides(c);
+  long long t_first;
+  int n;
+  score_range(c, cfg, t_first, n);
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  RnScoreStep x{};
+  x.rec = c.rec + (t_first - 1) * c.rec_fs, x.rec_frame_stride = c.rec_fs, x.rec_row_stride = c.rec_rs;
+  x.gains = c.gains + (t_first - c.t0) * c.gain_fs, x.gain_frame_stride = c.gain_fs, x.gain_row_stride = c.gain_rs;
+  x.vad = c.vad + (t_first - c.t0) * c.vad_fs, x.vad_frame_stride = c.vad_fs, x.vad_row_stride = c.vad_rs;
+  x.sums = c.sums, x.band_sums = c.band_sums, x.gamma = cfg.gamma, x.n = n;
+  // (the batch names the device; its group and tables ride along as the kernel's arguments and are not read in this mode)
+  HIP_OK(rn_launch_score_rows(&b->g, &b->tb, &x, c.n_rows, static_cast<hipStream_t>(c.stream)));
+  return 0;
+}
+
+// floats from a base to the end of the last of n_rows x T slots
+size_t score_extent(long fs, long rs, int row_floats, int n_rows, long long T) {
+  return T > 0 ? (size_t)(T - 1) * (size_t)fs + (size_t)(n_rows - 1) * (size_t)rs + row_floats : 0;
+}
+
+int score_host(RNNoiseBatch *b, ScoreCall c) {
+  if (!b || !c.rec || !c.gains || !c.vad || !c.sums) return -1;
+  EvalConfig cfg;
+  if (!eval_config(c.cfg, cfg) || !score_layout_fits(c)) return -1;
+  score_strides(c);
+  long long t_first;
+  int n;
+  score_range(c, cfg, t_first, n);
+  if (n == 0) return 0;
+  ON_DEVICE(b->device);
+  // records 0 .. t0 + n_frames - 2 (the last step's record is the last one read), the predictions of the call's n_frames steps
+  const size_t R = c.n_rows, e_rec = score_extent(c.rec_fs, c.rec_rs, 98, c.n_rows, (long long)c.t0 + c.n_frames - 1),
+               e_g = score_extent(c.gain_fs, c.gain_rs, RN_NB_BANDS, c.n_rows, c.n_frames),
+               e_v = score_extent(c.vad_fs, c.vad_rs, 1, c.n_rows, c.n_frames);
+  DevScratch d;
+  const size_t o_rec = d.carve(e_rec * 4), o_g = d.carve(e_g * 4), o_v = d.carve(e_v * 4),
+               o_sums = d.carve(R * RN_EVAL_SUMS * sizeof(double)), o_band = d.carve(R * RN_NB_BANDS * sizeof(double));
+  if (d.alloc()) return -1;
+  HIP_OK(hipMemcpy(d.at<char>(o_rec), c.rec, e_rec * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d.at<char>(o_g), c.gains, e_g * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d.at<char>(o_v), c.vad, e_v * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d.at<char>(o_sums), c.sums, R * RN_EVAL_SUMS * sizeof(double), hipMemcpyHostToDevice));
+  if (c.band_sums) HIP_OK(hipMemcpy(d.at<char>(o_band), c.band_sums, R * RN_NB_BANDS * sizeof(double), hipMemcpyHostToDevice));
+  ScoreCall dc = c;
+  dc.rec = d.at<float>(o_rec), dc.gains = d.at<float>(o_g), dc.vad = d.at<float>(o_v);
+  dc.sums = d.at<double>(o_sums), dc.band_sums = c.band_sums ? d.at<double>(o_band) : nullptr;
+  dc.stream = nullptr;
+  if (score_device(b, dc)) return -1;
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(c.sums, dc.sums, R * RN_EVAL_SUMS * sizeof(double), hipMemcpyDeviceToHost));
+  if (c.band_sums) HIP_OK(hipMemcpy(c.band_sums, dc.band_sums, R * RN_NB_BANDS * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
 }  // namespace
+
+extern "C" int rnnoise_amd_score_records_check(const RNNoiseEvalConfig *cfg, long rec_frame_stride, long rec_row_stride,
+                                               long gain_frame_stride, long gain_row_stride, long vad_frame_stride,
+                                               long vad_row_stride, int n_rows, int t0, int n_frames) {
+  EvalConfig e;
+  ScoreCall c;
+  c.rec_fs = rec_frame_stride, c.rec_rs = rec_row_stride, c.gain_fs = gain_frame_stride, c.gain_rs = gain_row_stride;
+  c.vad_fs = vad_frame_stride, c.vad_rs = vad_row_stride, c.n_rows = n_rows, c.t0 = t0, c.n_frames = n_frames;
+  return eval_config(cfg, e) && score_layout_fits(c) ? 1 : 0;
+}
+
+extern "C" int rnnoise_batch_score_records_device(RNNoiseBatch *b, double *d_sums, double *d_band_sums, const float *d_gains,
+                                                  long gain_frame_stride, long gain_row_stride, const float *d_vad,
+                                                  long vad_frame_stride, long vad_row_stride, const float *d_records,
+                                                  long rec_frame_stride, long rec_row_stride, int n_rows, int t0, int n_frames,
+                                                  const RNNoiseEvalConfig *cfg, void *hip_stream) {
+  ScoreCall c;
+  c.sums = d_sums, c.band_sums = d_band_sums, c.gains = d_gains, c.gain_fs = gain_frame_stride, c.gain_rs = gain_row_stride;
+  c.vad = d_vad, c.vad_fs = vad_frame_stride, c.vad_rs = vad_row_stride, c.rec = d_records, c.rec_fs = rec_frame_stride;
+  c.rec_rs = rec_row_stride, c.n_rows = n_rows, c.t0 = t0, c.n_frames = n_frames, c.cfg = cfg, c.stream = hip_stream;
+  return score_device(b, c);
+}
+
+extern "C" int rnnoise_batch_score_records(RNNoiseBatch *b, double *sums, double *band_sums, const float *gains,
+                                           long gain_frame_stride, long gain_row_stride, const float *vad, long vad_frame_stride,
+                                           long vad_row_stride, const float *records, long rec_frame_stride, long rec_row_stride,
+                                           int n_rows, int t0, int n_frames, const RNNoiseEvalConfig *cfg) {
+  ScoreCall c;
+  c.sums = sums, c.band_sums = band_sums, c.gains = gains, c.gain_fs = gain_frame_stride, c.gain_rs = gain_row_stride;
+  c.vad = vad, c.vad_fs = vad_frame_stride, c.vad_rs = vad_row_stride, c.rec = records, c.rec_fs = rec_frame_stride;
+  c.rec_rs = rec_row_stride, c.n_rows = n_rows, c.t0 = t0, c.n_frames = n_frames, c.cfg = cfg;
+  return score_host(b, c);
+}
 
 extern "C" int rnnoise_amd_eval_records_check(const RNNoiseEvalConfig *cfg, long frame_stride, long row_stride, int row_floats,
                                               int n_streams, int t0, int n_frames) {

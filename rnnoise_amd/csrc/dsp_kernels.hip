@@ -1650,30 +1650,50 @@ rn_analysis_rows_kernel(RnGroupDev g, RnTablesDev tb, RnRows rows) {
 // The 32 gain terms are summed by a butterfly of fixed shape (lanes 32 .. 63 carry +0), lane 0 adds the frame's two sums to the
 // stream's doubles: the order of additions depends on (stream, frame, band) alone.  Staging: lane = record element, so a wave reads
 // its row's consecutive floats wherever the rows lie.
+// one scored frame's terms from its four kinds of floats -- gt the record's gain target of band lane & 31, v its VAD target, p the
+// predicted gain of that band, q the predicted VAD -- in the lane roles above: the body of the record step and of the score walk
+struct EvalTerms {
+  double band;     // lanes 0 .. 31: the band's gain term; lanes 32 .. 63: +0
+  double term;     // the butterfly's sum of the 32 gain terms
+  double lg, lg1;  // lane 0: log(.01 + q), log(1.01 - q)
+};
+__device__ __forceinline__ EvalTerms eval_frame_terms(float gt_f, float v_f, float p_f, float q_f, double gamma, int lane) {
+  const double v = (double)v_f;
+  // the f64 library calls are what this launch costs, so each runs once per wave: lane b raises band b's prediction
+  // to gamma while lane 32 + b raises its shaped target, and lanes 0 and 1 take the two logs of the VAD term
+  const double gt = (double)gt_f, p = (double)p_f;
+  double tg = gt < 0.0 ? 0.0 : gt;
+  const double th = tanh(8.0 * tg);
+  tg = tg * (th * th);
+  const double pw = pow(lane < RN_NB_BANDS ? p : tg, gamma);
+  const double d = pw - __shfl_xor(pw, RN_NB_BANDS, WAVE);
+  const double m = gt + 1.0 > 1.0 ? 1.0 : gt + 1.0;
+  EvalTerms k;
+  k.band = lane < RN_NB_BANDS ? ((1.0 + 5.0 * v) * m) * (d * d) : 0.0;
+  k.term = k.band;
+#pragma unroll
+  for (int off = 16; off >= 1; off >>= 1) k.term += __shfl_xor(k.term, off, WAVE);
+  const double q = (double)q_f;
+  k.lg = log(lane == 0 ? .01 + q : 1.01 - q), k.lg1 = __shfl_xor(k.lg, 1, WAVE);
+  return k;
+}
+// lane 0's VAD term of the frame
+__device__ __forceinline__ double eval_vad_term(float v_f, const EvalTerms &k) {
+  const double v = (double)v_f;
+  return fabs(2.0 * v - 1.0) * (-v * k.lg - (1.0 - v) * k.lg1);
+}
+
 __device__ __forceinline__ void eval_step_body(const RnGroupDev &g, const RnEvalStep &e) {
   const int s = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (e.target) {
     const float *rec = e.target + (long long)s * e.row_stride;
-    const double v = (double)rec[RN_NB_FEATURES + RN_NB_BANDS];
-    // the f64 library calls are what this launch costs, so each runs once per wave: lane b raises band b's prediction
-    // to gamma while lane 32 + b raises its shaped target, and lanes 0 and 1 take the two logs of the VAD term
     const int band = lane & (RN_NB_BANDS - 1);
-    const double gt = (double)rec[RN_NB_FEATURES + band], p = (double)e.gains[(size_t)s * RN_NB_BANDS + band];
-    double tg = gt < 0.0 ? 0.0 : gt;
-    const double th = tanh(8.0 * tg);
-    tg = tg * (th * th);
-    const double pw = pow(lane < RN_NB_BANDS ? p : tg, e.gamma);
-    const double d = pw - __shfl_xor(pw, RN_NB_BANDS, WAVE);
-    const double m = gt + 1.0 > 1.0 ? 1.0 : gt + 1.0;
-    double term = lane < RN_NB_BANDS ? ((1.0 + 5.0 * v) * m) * (d * d) : 0.0;
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) term += __shfl_xor(term, off, WAVE);
-    const double q = (double)e.vad[s];
-    const double lg = log(lane == 0 ? .01 + q : 1.01 - q), lg1 = __shfl_xor(lg, 1, WAVE);
+    const float v = rec[RN_NB_FEATURES + RN_NB_BANDS];
+    const EvalTerms k = eval_frame_terms(rec[RN_NB_FEATURES + band], v, e.gains[(size_t)s * RN_NB_BANDS + band], e.vad[s], e.gamma, lane);
     if (lane == 0) {
-      const double vt = fabs(2.0 * v - 1.0) * (-v * lg - (1.0 - v) * lg1);
+      const double vt = eval_vad_term(v, k);
       double *sum = e.sums + (size_t)s * RN_EVAL_SUMS;
-      sum[0] += term;
+      sum[0] += k.term;
       sum[1] += vt;
       sum[2] += 1.0;
     }
@@ -1714,6 +1734,39 @@ __device__ __forceinline__ void split_step_body(const RnGroupDev &g, const RnSpl
   }
 }
 
+// The score walk (rn_dev.h: RnScoreStep), one wave per row: the record step's scoring over the n frames of a call in one launch.  The
+// four floats a lane needs of frame f + 1 are requested before frame f's pow / tanh / log run, so a frame's memory round trip hides
+// behind the f64 calls of the frame before.  The row's three sums (lane 0) and its band's sum (lanes 0 .. 31) stay in registers from
+// the first frame to the last: the same additions in the same order as n record steps, one load and one store of each double.
+__device__ __forceinline__ void score_rows_body(const RnScoreStep &c) {
+  const int s = (int)blockIdx.x, lane = (int)threadIdx.x, band = lane & (RN_NB_BANDS - 1);
+  const float *rec = c.rec + (long long)s * c.rec_row_stride + RN_NB_FEATURES;
+  const float *pg = c.gains + (long long)s * c.gain_row_stride, *pq = c.vad + (long long)s * c.vad_row_stride;
+  double *sum = c.sums + (size_t)s * RN_EVAL_SUMS;
+  double *bsum = c.band_sums && lane < RN_NB_BANDS ? c.band_sums + (size_t)s * RN_NB_BANDS + lane : nullptr;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, ab = 0.0;
+  if (lane == 0) a0 = sum[0], a1 = sum[1], a2 = sum[2];
+  if (bsum) ab = *bsum;
+  float gt = rec[band], v = rec[RN_NB_BANDS], p = pg[band], q = pq[0];
+  for (int f = 0; f < c.n; f++) {
+    const float gt0 = gt, v0 = v, p0 = p, q0 = q;
+    if (f + 1 < c.n) {
+      rec += c.rec_frame_stride, pg += c.gain_frame_stride, pq += c.vad_frame_stride;
+      gt = rec[band], v = rec[RN_NB_BANDS], p = pg[band], q = pq[0];
+    }
+    const EvalTerms k = eval_frame_terms(gt0, v0, p0, q0, c.gamma, lane);
+    if (lane == 0) {
+      const double vt = eval_vad_term(v0, k);
+      a0 += k.term;
+      a1 += vt;
+      a2 += 1.0;
+    }
+    ab += k.band;
+  }
+  if (lane == 0) sum[0] = a0, sum[1] = a1, sum[2] = a2;
+  if (bsum) *bsum = ab;
+}
+
 // TRAINING-mode variant: the inner loop of src/dump_features.c:466-491 -- or, with tr.step.on (a launch argument:
 // the branch is wave-uniform and taken before anything else is read), the record step of the feature calls or a staging step of the
 // split calls
@@ -1721,6 +1774,7 @@ extern "C" __global__ void __launch_bounds__(WAVE)
 rn_train_features_kernel(RnGroupDev g, RnTablesDev tb, int slot, int parity, RnTrainArgs tr) {
   if (tr.step.on) {
     if (tr.step.on == RN_STEP_EVAL) eval_step_body(g, tr.step);
+    else if (tr.step.on == RN_STEP_SCORE) score_rows_body(tr.score);
     else split_step_body(g, tr.split, tr.step.on == RN_STEP_EXPORT);
     return;
   }
@@ -2214,8 +2268,15 @@ extern "C" hipError_t rn_launch_train_features(const RnGroupDev *g, const RnTabl
 extern "C" hipError_t rn_launch_eval_step(const RnGroupDev *g, const RnTablesDev *tb, const RnEvalStep *step, hipStream_t st) {
   RnTrainArgs tr{};
   tr.step = *step;
-  tr.step.on = RN_STEP_EVAL;
-  hipLaunchKernelGGL(rn_train_features_kernel, dim3(g->n_streams), dim3(WAVE), 0, st, *g, *tb, 0, 0, tr);
+  int rows = g->n_streams;
+  if (step->on == RN_STEP_SCORE) {  // the score walk (shim.h: rn_launch_score_rows): one wave per row of the caller's
+    tr.score = *step->score;
+    tr.step.score = nullptr;
+    rows = step->score_rows;
+  } else {
+    tr.step.on = RN_STEP_EVAL;
+  }
+  hipLaunchKernelGGL(rn_train_features_kernel, dim3(rows), dim3(WAVE), 0, st, *g, *tb, 0, 0, tr);
   return hipGetLastError();
 }
 // a staging step of the split calls (rn_dev.h: RnSplitStep; mode: RN_STEP_EXPORT | RN_STEP_IMPORT): the same kernel once more

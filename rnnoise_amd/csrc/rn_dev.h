@@ -351,7 +351,25 @@ struct RnRows {
 //   RN_STEP_IMPORT  in front of K3 of a pending frame: gains + s * gains_stride (32 floats) and vad[s * vad_stride] go to g.gains[s]
 //                   and g.vad[s] -- the batch's scratch, where K3 looks for them -- as they are; where sil[s] != 0 the caller's rows
 //                   are not read and zeros go there, which is what the network writes on a silent frame
-enum { RN_STEP_EVAL = 1, RN_STEP_EXPORT = 2, RN_STEP_IMPORT = 3 };
+// A fourth mode scores predictions of the caller's (include/rnnoise_amd.h: rnnoise_batch_score_records_device; batch_eval.cpp):
+//   RN_STEP_SCORE   the scoring of the record step with the network taken out, ONE launch for a whole call: one wave per row s walks
+//                   its n frames in order -- frame f's record at rec + f * rec_frame_stride + s * rec_row_stride, its predictions
+//                   at gains + f * gain_frame_stride + s * gain_row_stride and vad + f * vad_frame_stride + s * vad_row_stride -- with
+//                   the record step's own terms and additions (eval_frame_terms), the three sums and the band's sum in registers
+//                   between frames, the next frame's floats requested before the current frame's f64 calls.  No batch state is read.
+enum { RN_STEP_EVAL = 1, RN_STEP_EXPORT = 2, RN_STEP_IMPORT = 3, RN_STEP_SCORE = 4 };
+struct RnScoreStep {
+  const float *rec;        // the record of the first scored step, row 0 (features[65] | gain targets[32] | vad target)
+  long long rec_frame_stride, rec_row_stride;
+  const float *gains;      // the gains of the first scored step, row 0
+  long long gain_frame_stride, gain_row_stride;
+  const float *vad;        // its vad
+  long long vad_frame_stride, vad_row_stride;
+  double *sums;            // [rows][RN_EVAL_SUMS], added to
+  double *band_sums;       // [rows][32], added to, or null
+  double gamma;            // the perceptual exponent of the gain term
+  int n;                   // scored steps, > 0
+};
 struct RnSplitStep {
   float *feat;             // export: the caller's feature rows of this frame
   long long feat_stride;
@@ -364,7 +382,7 @@ struct RnSplitStep {
 };
 struct RnEvalStep {
   int on;                  // 0: the extraction launch -- nothing below is read; RN_STEP_EVAL: the fields below; RN_STEP_EXPORT /
-                           // RN_STEP_IMPORT: RnTrainArgs::split alone
+                           // RN_STEP_IMPORT: RnTrainArgs::split alone; RN_STEP_SCORE: RnTrainArgs::score alone
   const float *stage;      // features of the next step, or null
   const float *target;     // record to score against (features[65] | gain targets[32] | vad target), or null
   long long row_stride;    // floats between the rows of two streams, in `stage` and in `target`
@@ -372,6 +390,8 @@ struct RnEvalStep {
   const float *vad;        // [N]
   double *sums;            // [N][RN_EVAL_SUMS], added to
   double gamma;            // the perceptual exponent of the gain term
+  const struct RnScoreStep *score;  // HOST side only, on = RN_STEP_SCORE: what rn_launch_eval_step copies into RnTrainArgs::score (the
+  int score_rows;                   // kernel sees null) and the rows it launches -- shim.h: rn_launch_score_rows
 };
 
 // per-step arguments of the training-feature extraction kernel (src/dump_features.c:466-491)
@@ -385,6 +405,7 @@ struct RnTrainArgs {
   float *rec;              // [N][98] out: features[65] | gain targets[32] | vad
   RnEvalStep step;         // step.on: the launch is a record step of the feature calls instead, and nothing above is read
   RnSplitStep split;       // ... or a staging step of the split calls (step.on = RN_STEP_EXPORT / RN_STEP_IMPORT)
+  RnScoreStep score;       // ... or the scoring of a whole call on predictions of the caller's (step.on = RN_STEP_SCORE)
 };
 
 // bits(rcpps(x)) for a positive normal x with bits b, from the 16-bit table entry v = rcp16[(b >> 11) & 0xfff]:

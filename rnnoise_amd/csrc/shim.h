@@ -54,6 +54,15 @@ extern "C" hipError_t rn_launch_train_features(const RnGroupDev *, const RnTable
                                                const RnTrainArgs *, hipStream_t);
 extern "C" hipError_t rn_launch_eval_step(const RnGroupDev *, const RnTablesDev *, const RnEvalStep *, hipStream_t);
 extern "C" hipError_t rn_launch_split_step(const RnGroupDev *, const RnTablesDev *, const RnSplitStep *, int mode, hipStream_t);
+// the score walk (rn_dev.h: RnScoreStep): the record step's launcher in its fourth mode, one wave per row of the caller's, one launch for
+// the call's frames
+inline hipError_t rn_launch_score_rows(const RnGroupDev *g, const RnTablesDev *tb, const RnScoreStep *score, int n_rows, hipStream_t st) {
+  RnEvalStep step{};
+  step.on = RN_STEP_SCORE;
+  step.score = score;
+  step.score_rows = n_rows;
+  return rn_launch_eval_step(g, tb, &step, st);
+}
 extern "C" hipError_t rn_launch_nn_vector(const RnGroupDev *, const RnModelDev *, const RnTablesDev *, hipStream_t, hipEvent_t,
                                           hipEvent_t);
 // (lds_opt_in: the batch's answer to the kernel's large-LDS opt-in, RNNoiseBatch::lds_one / lds_gru, returned instead of a launch)

@@ -3,7 +3,11 @@ DESIGN.md 4.28): the quantised, sparsified network as it ships, run over the 98-
 src/dump_features.c, or `python -m rnnoise_amd.cli dump-features` -- and scored as torch/rnnoise/train_rnnoise.py scores its float
 checkpoint.  Nothing is trained here.
 
-  python -m rnnoise_amd.cli eval-records validation.f32 --model weights_blob.bin [--model other.bin ...]
+  python -m rnnoise_amd.cli eval-records validation.f32 --model weights_blob.bin [--model other.bin ...] [--checkpoint ckpt.pth]
+
+evaluate_checkpoint scores the float checkpoint itself on the same file -- rnnoise_amd.float_net's forward_sequence in torch, its
+outputs scored by rnnoise_batch_score_records_device, the scoring half of the record step -- so that the difference between a blob's
+loss and its checkpoint's is what quantisation and sparsification cost, not what two pieces of loss code differ by.
 """
 from __future__ import annotations
 
@@ -28,14 +32,28 @@ def map_records(path_or_array, sequence_length: int) -> np.ndarray:
     return data[:n * sequence_length * REC].reshape(n, sequence_length, REC)
 
 
+def _means(sums, bands=None):
+    """the result dict of one model from its per-sequence sums (S, EVAL_SUMS) and, where asked for, band sums (S, 32)"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        g = sums[:, 0] / (capi.NB_BANDS * sums[:, 2])
+        v = sums[:, 1] / sums[:, 2]
+        out = dict(sequences=sums.shape[0], **capi.eval_losses(sums), per_sequence=dict(gain_loss=g, vad_loss=v, loss=g + .001 * v))
+        if bands is not None:  # band b's mean gain term over every scored frame: gain_loss is the mean of the 32
+            frames = sums[:, 2].sum()
+            out["band_gain_loss"] = [float(x) for x in (bands.sum(0) / frames if frames else np.full(capi.NB_BANDS, np.nan))]
+    return out
+
+
 def evaluate_records(path_or_array, models, sequence_length: int = 2000, gamma: float = .25, first: int = 4, device: int = 0,
-                     max_streams: int = 65536, slab_bytes: int = 1 << 30):
+                     max_streams: int = 65536, slab_bytes: int = 1 << 30, bands: bool = False, segment_bytes: int = 1 << 28):
     """Scores every model of `models` (blobs as bytes, or capi.Model objects) on the sequences of a record file or array.  The
     sequences go up in slabs of at most max_streams (and at most slab_bytes) as they lie in the file -- [sequence][frame][98] --, and
     each slab is walked with strides, one sequence per stream, by every model in turn; nothing is transposed.  Returns one dict per
     model: sequences, frames_scored, gain_loss, vad_loss, loss -- the trainer's three means over the whole file -- and per_sequence,
     a dict of (sequences,) float64 arrays gain_loss, vad_loss, loss with each sequence's own means (nan for a sequence with no scored
-    frame)."""
+    frame).  bands: also band_gain_loss, the 32 per-band means of the gain term -- the walk then goes in segments of frames (at most
+    segment_bytes of predictions each), eval_records' gains / vad outputs of a segment scored once more by
+    rnnoise_batch_score_records_device for its band sums; the sums are those of one call either way."""
     import torch
 
     data = map_records(path_or_array, sequence_length)
@@ -46,6 +64,7 @@ def evaluate_records(path_or_array, models, sequence_length: int = 2000, gamma: 
     dev = torch.device("cuda", device)
     per_slab = max(1, min(max_streams, slab_bytes // (T * REC * 4), S))
     sums = [np.zeros((S, capi.EVAL_SUMS), np.float64) for _ in handles]
+    band_sums = [np.zeros((S, capi.NB_BANDS), np.float64) for _ in handles] if bands else None
     batches = {}
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev)
@@ -58,18 +77,79 @@ def evaluate_records(path_or_array, models, sequence_length: int = 2000, gamma: 
                 b = batches[k, n]
                 b.reset()  # (synchronous: the upload above, on torch's stream, is done too)
                 d_sums = torch.zeros((n, capi.EVAL_SUMS), dtype=torch.float64, device=dev)
-                b.eval_records_device(d_sums.data_ptr(), 0, 0, d_rec.data_ptr(), 0, T, frame_stride=REC, row_stride=T * REC,
-                                      gamma=gamma, first=first, stream=st.cuda_stream)
+                if not bands:
+                    b.eval_records_device(d_sums.data_ptr(), 0, 0, d_rec.data_ptr(), 0, T, frame_stride=REC, row_stride=T * REC,
+                                          gamma=gamma, first=first, stream=st.cuda_stream)
+                else:
+                    seg = max(1, min(T, segment_bytes // (n * (capi.NB_BANDS + 1) * 4)))
+                    d_g = torch.empty((seg, n, capi.NB_BANDS), dtype=torch.float32, device=dev)
+                    d_v = torch.empty((seg, n), dtype=torch.float32, device=dev)
+                    d_again = torch.zeros((n, capi.EVAL_SUMS), dtype=torch.float64, device=dev)
+                    d_bands = torch.zeros((n, capi.NB_BANDS), dtype=torch.float64, device=dev)
+                    for t0 in range(0, T, seg):
+                        k_frames = min(seg, T - t0)
+                        b.eval_records_device(d_sums.data_ptr(), d_g.data_ptr(), d_v.data_ptr(), d_rec.data_ptr(), t0, k_frames,
+                                              frame_stride=REC, row_stride=T * REC, gamma=gamma, first=first, stream=st.cuda_stream)
+                        b.score_records_device(d_again.data_ptr(), d_bands.data_ptr(), d_g.data_ptr(), d_v.data_ptr(), d_rec.data_ptr(),
+                                               n, t0, k_frames, rec_strides=(REC, T * REC), gamma=gamma, first=first,
+                                               stream=st.cuda_stream)
+                    band_sums[k][s0:s0 + n] = d_bands.cpu().numpy()
                 sums[k][s0:s0 + n] = d_sums.cpu().numpy()  # (waits for the stream)
     for b in batches.values():
         b.close()
-    out = []
-    with np.errstate(invalid="ignore", divide="ignore"):
-        for k in range(len(handles)):
-            g = sums[k][:, 0] / (capi.NB_BANDS * sums[k][:, 2])
-            v = sums[k][:, 1] / sums[k][:, 2]
-            out.append(dict(sequences=S, **capi.eval_losses(sums[k]), per_sequence=dict(gain_loss=g, vad_loss=v, loss=g + .001 * v)))
+    out = [_means(sums[k], band_sums[k] if bands else None) for k in range(len(handles))]
     for m, h in zip(models, handles):
         if not isinstance(m, capi.Model):
             h.close()
     return out
+
+
+def evaluate_checkpoint(path_or_array, checkpoint, sequence_length: int = 2000, gamma: float = .25, first: int = 4, device: int = 0,
+                        max_streams: int = 65536, slab_bytes: int = 1 << 30, group_bytes: int = 1 << 30):
+    """Scores a float checkpoint -- a path (float_net.load_checkpoint) or a module with forward_sequence -- on the sequences of a
+    record file or array, as evaluate_records scores a blob: the slabs go up the same way, forward_sequence runs in torch on the
+    feature columns of groups of sequences (a group's activations stay under group_bytes), and its [n][T - 4] outputs are scored
+    where they lie by rnnoise_batch_score_records_device with t0 = 4 -- output k is step k + 4 -- against the records of the slab.
+    `first` below 4 scores from step 4 all the same: the float network has no earlier output.  Returns evaluate_records' dict for
+    one model, with band_gain_loss."""
+    import torch
+
+    from . import blob as blob_tools
+    from . import float_net
+    data = map_records(path_or_array, sequence_length)
+    S, T = data.shape[0], sequence_length
+    if S == 0:
+        raise ValueError(f"no whole sequence of {sequence_length} records")
+    if T <= float_net.LOOKAHEAD:
+        raise ValueError(f"sequences of {T} records: the float network needs more than {float_net.LOOKAHEAD}")
+    dev = torch.device("cuda", device)
+    net = checkpoint if isinstance(checkpoint, torch.nn.Module) else float_net.load_checkpoint(checkpoint)
+    net = net.to(dev).eval()
+    model = capi.Model(blob_tools.synth_model())  # (a score call reads no model: the batch only names the device)
+    batch = capi.Batch(model, 1, device=device)
+    per_slab = max(1, min(max_streams, slab_bytes // (T * REC * 4), S))
+    width = capi.FEATURES + 2 * net.cond_size + 10 * net.gru_size  # floats a frame of a sequence keeps alive in forward_sequence, roughly
+    per_group = max(1, group_bytes // (T * width * 4))
+    K = T - float_net.LOOKAHEAD
+    sums, bands = np.zeros((S, capi.EVAL_SUMS), np.float64), np.zeros((S, capi.NB_BANDS), np.float64)
+    with torch.cuda.device(dev), torch.no_grad():
+        st = torch.cuda.current_stream(dev)
+        for s0 in range(0, S, per_slab):
+            n = min(per_slab, S - s0)
+            d_rec = torch.from_numpy(np.array(data[s0:s0 + n])).to(dev)
+            d_sums = torch.zeros((n, capi.EVAL_SUMS), dtype=torch.float64, device=dev)
+            d_bands = torch.zeros((n, capi.NB_BANDS), dtype=torch.float64, device=dev)
+            for g0 in range(0, n, per_group):
+                m = min(per_group, n - g0)
+                gains, vad = net.forward_sequence(d_rec[g0:g0 + m, :, :capi.FEATURES])
+                gains, vad = gains.float().contiguous(), vad.float().contiguous()
+                assert gains.shape == (m, K, capi.NB_BANDS) and vad.shape == (m, K, 1)
+                batch.score_records_device(d_sums[g0:].data_ptr(), d_bands[g0:].data_ptr(), gains.data_ptr(), vad.data_ptr(),
+                                           d_rec[g0:].data_ptr(), m, float_net.LOOKAHEAD, K, gain_strides=(capi.NB_BANDS, K * capi.NB_BANDS),
+                                           vad_strides=(1, K), rec_strides=(REC, T * REC), gamma=gamma, first=first,
+                                           stream=st.cuda_stream)
+                st.synchronize()  # (the group's outputs are read by the launch: they stay until it is done)
+            sums[s0:s0 + n], bands[s0:s0 + n] = d_sums.cpu().numpy(), d_bands.cpu().numpy()
+    batch.close()
+    model.close()
+    return _means(sums, bands)

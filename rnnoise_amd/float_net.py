@@ -1,0 +1,100 @@
+"""The float network in this project's own words: a torch module whose parameter names are the reference trainer's
+(conv1, conv2, gru1 .. gru3, dense_out, vad_dense), so that load_state_dict takes a checkpoint of torch/rnnoise/train_rnnoise.py as it
+is.  Two valid convolutions of three taps, tanh each; three GRUs in a chain; both outputs a sigmoid of one linear layer over the
+concatenation [conv2 | gru1 | gru2 | gru3].
+
+  forward_sequence(features [N, T, 65]) -> gains [N, T - 4, 32], vad [N, T - 4, 1]
+      the trainer's view of a sequence: output k has seen features k .. k + 4; zero GRU states, or given ones
+  forward(features [N, T, 65]) -> gains [N, T, 32], vad [N, T, 1]
+      the streaming view, aligned as the C runtime is: the module keeps the last four feature frames and the three GRU states from
+      call to call, frame k + 4 after a reset is output k of forward_sequence on the frames since that reset, and a stream cut into
+      calls of any lengths gives what one call gives.  The first four frames after a reset have no output in the trainer's view: the
+      GRUs do not run on them, and their gains and vad are zeros -- what the blob's network leaves on a silent frame.  reset() starts a
+      new sequence.  This is the stateful net of RNNoiseOp.denoise_with(net, pcm) and of cli denoise --checkpoint.
+
+Forward only: nothing here trains."""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+FEATURES, BANDS, LOOKAHEAD = 65, 32, 4
+
+
+class FloatNet(nn.Module):
+    def __init__(self, cond_size: int = 128, gru_size: int = 384):
+        super().__init__()
+        self.cond_size, self.gru_size = cond_size, gru_size
+        self.conv1 = nn.Conv1d(FEATURES, cond_size, kernel_size=3)
+        self.conv2 = nn.Conv1d(cond_size, gru_size, kernel_size=3)
+        self.gru1 = nn.GRU(gru_size, gru_size, batch_first=True)
+        self.gru2 = nn.GRU(gru_size, gru_size, batch_first=True)
+        self.gru3 = nn.GRU(gru_size, gru_size, batch_first=True)
+        self.dense_out = nn.Linear(4 * gru_size, BANDS)
+        self.vad_dense = nn.Linear(4 * gru_size, 1)
+        self.reset()
+
+    # ---- the layers ----
+    def _front(self, features):
+        """[N, T, 65] -> [N, T - 4, gru_size]: the two convolutions over time"""
+        x = features.transpose(1, 2)
+        x = torch.tanh(self.conv2(torch.tanh(self.conv1(x))))
+        return x.transpose(1, 2)
+
+    def _back(self, c, states):
+        """conv2's frames [N, K, gru_size] and three states [1, N, gru_size] -> gains, vad, the states after frame K - 1"""
+        g1, s1 = self.gru1(c, states[0])
+        g2, s2 = self.gru2(g1, states[1])
+        g3, s3 = self.gru3(g2, states[2])
+        cat = torch.cat([c, g1, g2, g3], dim=-1)
+        return torch.sigmoid(self.dense_out(cat)), torch.sigmoid(self.vad_dense(cat)), [s1, s2, s3]
+
+    def _zero_states(self, n, like):
+        return [torch.zeros((1, n, self.gru_size), device=like.device, dtype=like.dtype) for _ in range(3)]
+
+    # ---- the trainer's view ----
+    def forward_sequence(self, features, states=None, return_states: bool = False):
+        assert features.dim() == 3 and features.shape[2] == FEATURES and features.shape[1] > LOOKAHEAD, tuple(features.shape)
+        c = self._front(features)
+        gains, vad, states = self._back(c, self._zero_states(features.shape[0], c) if states is None else states)
+        return (gains, vad, states) if return_states else (gains, vad)
+
+    # ---- the streaming view ----
+    def reset(self):
+        """a new sequence for every stream: no history, zero states; the next call sets the number of streams"""
+        self._hist, self._states, self._seen = None, None, 0
+
+    def forward(self, features):
+        assert features.dim() == 3 and features.shape[2] == FEATURES, tuple(features.shape)
+        n, t = features.shape[0], features.shape[1]
+        if self._hist is None or self._hist.shape[0] != n or self._hist.device != features.device or self._hist.dtype != features.dtype:
+            self.reset()
+            self._hist = torch.zeros((n, LOOKAHEAD, FEATURES), device=features.device, dtype=features.dtype)
+            self._states = self._zero_states(n, features)
+        gains = torch.zeros((n, t, BANDS), device=features.device, dtype=features.dtype)
+        vad = torch.zeros((n, t, 1), device=features.device, dtype=features.dtype)
+        if t == 0:
+            return gains, vad
+        x = torch.cat([self._hist, features], dim=1)
+        skip = max(0, min(t, LOOKAHEAD - self._seen))  # frames of this call that still lack their four predecessors
+        if skip < t:
+            g, v, self._states = self._back(self._front(x[:, skip:]), self._states)
+            gains[:, skip:], vad[:, skip:] = g, v
+        self._hist = x[:, -LOOKAHEAD:].detach().clone()
+        self._states = [s.detach() for s in self._states]
+        self._seen += t
+        return gains, vad
+
+
+def load_checkpoint(path: str, device=None) -> FloatNet:
+    """a FloatNet in eval mode holding the weights of a trainer checkpoint (rnnoise_amd.export.load_state_dict_file: a .pth with
+    'state_dict', or a bare state dict); the dimensions are read off the tensors"""
+    from .export import load_state_dict_file
+    try:
+        sd = load_state_dict_file(path)
+    except ValueError:  # (dimensions the blob does not hold: the float network runs them all the same)
+        sd = torch.load(path, map_location="cpu")["state_dict"]
+    net = FloatNet(cond_size=sd["conv1.weight"].shape[0], gru_size=sd["conv2.weight"].shape[0])
+    net.load_state_dict(sd)
+    net.eval()
+    return net.to(device) if device is not None else net
