@@ -7,6 +7,7 @@ if the HIP library is missing or no GPU is visible, construction raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -45,51 +46,138 @@ _lib = None
 _product = None
 _instr = None
 
-# every symbol declared in include/rnnoise.h and include/rnnoise_amd.h
-EXPORTS = [
-    "rnnoise_get_size", "rnnoise_get_frame_size", "rnnoise_init", "rnnoise_create", "rnnoise_destroy",
-    "rnnoise_process_frame", "rnnoise_model_from_buffer", "rnnoise_model_from_file",
-    "rnnoise_model_from_filename", "rnnoise_model_free",
-    "rnnoise_amd_device_count", "rnnoise_batch_create", "rnnoise_batch_destroy", "rnnoise_batch_size",
-    "rnnoise_batch_reset", "rnnoise_batch_process", "rnnoise_batch_process_device",
-    "rnnoise_batch_process_s16", "rnnoise_batch_process_device_s16",
-    "rnnoise_batch_export_state", "rnnoise_batch_import_state", "rnnoise_batch_set_nn_path",
-    "rnnoise_model_weight_bytes", "rnnoise_batch_debug_last", "rnnoise_batch_enable_timing",
-    "rnnoise_batch_kernel_ms",
-    "rnnoise_batch_train_features", "rnnoise_batch_train_features_device", "rnnoise_amd_model_pack", "rnnoise_batch_set_schedule",
-    "rnnoise_amd_set_rcp_profile", "rnnoise_amd_rcp_profile", "rnnoise_amd_log10_model",
-    "rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_masked_s16", "rnnoise_batch_process_masked",
-    "rnnoise_batch_process_masked_s16", "rnnoise_batch_reset_streams", "rnnoise_batch_reset_streams_device",
-    "rnnoise_batch_process_device_list", "rnnoise_batch_process_device_list_s16", "rnnoise_batch_process_list",
-    "rnnoise_batch_process_list_s16",
-    "rnnoise_batch_set_pcm_rate", "rnnoise_batch_pcm_rate",
-    "rnnoise_batch_add_model", "rnnoise_batch_set_stream_models", "rnnoise_batch_set_stream_models_device", "rnnoise_batch_stream_models",
-    "rnnoise_batch_set_stream_controls", "rnnoise_batch_set_stream_controls_device", "rnnoise_batch_stream_controls",
-    "rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device", "rnnoise_batch_save_streams", "rnnoise_batch_load_streams",
-    "rnnoise_batch_set_stream_rates", "rnnoise_batch_set_stream_rates_device", "rnnoise_batch_stream_rates",
-    "rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_device", "rnnoise_batch_stream_formats",
-    "rnnoise_batch_set_stream_out_rates", "rnnoise_batch_set_stream_out_rates_device", "rnnoise_batch_stream_out_rates",
-    "rnnoise_batch_set_stream_out_formats", "rnnoise_batch_set_stream_out_formats_device", "rnnoise_batch_stream_out_formats",
-    "rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_pcm_layout_fits",
-    "rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_amd_pcm_channels_fit",
-    "rnnoise_batch_set_gain_link", "rnnoise_batch_gain_link",
-    "rnnoise_amd_train_mix_check", "rnnoise_batch_train_levels_device", "rnnoise_amd_train_vad", "rnnoise_batch_train_mix_device",
-    "rnnoise_amd_train_vad_device_available", "rnnoise_batch_train_levels_vad_device",
-    "rnnoise_amd_train_rir_check", "rnnoise_amd_train_rir_work_bytes", "rnnoise_batch_train_rir_load_device",
-    "rnnoise_batch_train_rir_device",
-    "rnnoise_amd_chunk_frames", "rnnoise_batch_process_device_chunks", "rnnoise_batch_process_device_chunks_s16",
-    "rnnoise_batch_process_chunks", "rnnoise_batch_process_chunks_s16", "rnnoise_batch_chunk_fill",
-    "rnnoise_batch_process_device_chunks_list", "rnnoise_batch_process_device_chunks_list_s16",
-    "rnnoise_batch_process_chunks_list", "rnnoise_batch_process_chunks_list_s16",
-    "rnnoise_batch_save_chunk_fifos_device", "rnnoise_batch_load_chunk_fifos_device", "rnnoise_batch_save_chunk_fifos",
-    "rnnoise_batch_load_chunk_fifos",
-    "rnnoise_amd_eval_records_check", "rnnoise_batch_process_features_device", "rnnoise_batch_process_features",
-    "rnnoise_batch_eval_records_device", "rnnoise_batch_eval_records",
-    "rnnoise_amd_score_records_check", "rnnoise_batch_score_records_device", "rnnoise_batch_score_records",
-    "rnnoise_amd_split_frame_bytes", "rnnoise_amd_split_rows_check", "rnnoise_batch_split_reserve", "rnnoise_batch_split_pending",
-    "rnnoise_batch_analyze_device", "rnnoise_batch_analyze_device_s16", "rnnoise_batch_analyze", "rnnoise_batch_analyze_s16",
-    "rnnoise_batch_synthesize_device", "rnnoise_batch_synthesize_device_s16", "rnnoise_batch_synthesize", "rnnoise_batch_synthesize_s16",
-]
+# The prototypes of the C API: symbol -> (restype, argtypes), in the order of the headers.  _load applies them; tests/test_capi_cpu.py
+# holds every entry to its declaration (parameter count and return class).  A new entry point gets one line here and nowhere else.
+# Batch, model and state handles, device pointers, streams and struct pointers are plain addresses (_vp); host arrays are typed.
+_int, _long, _ll, _uint, _vp, _cp = C.c_int, C.c_long, C.c_longlong, C.c_uint, C.c_void_p, C.c_char_p
+_fp_t, _ip, _sp, _up, _dp, _lp = (C.POINTER(t) for t in (C.c_float, C.c_int, C.c_short, C.c_ubyte, C.c_double, C.c_long))
+_PCM = object()  # stands for the PCM pointer of a host call in _twins: float * in the float call, short * in its "_s16" twin
+
+
+def _twins(name, argtypes):
+    """a call and its int16 twin, declared next to each other in the header"""
+    return {name + sfx: (_int, tuple(pp if a is _PCM else a for a in argtypes)) for sfx, pp in (("", _fp_t), ("_s16", _sp))}
+
+
+def _stream_table(name, tp):
+    """the three calls of a per-stream table: host setter, device setter (table, stream), getter"""
+    return {f"rnnoise_batch_set_stream_{name}": (_int, (_vp, tp)), f"rnnoise_batch_set_stream_{name}_device": (_int, (_vp, _vp, _vp)),
+            f"rnnoise_batch_stream_{name}": (_int, (_vp, tp))}
+
+
+PROTOTYPES = {
+    # include/rnnoise.h
+    "rnnoise_get_size": (_int, ()),
+    "rnnoise_get_frame_size": (_int, ()),
+    "rnnoise_init": (_int, (_vp, _vp)),
+    "rnnoise_create": (_vp, (_vp,)),
+    "rnnoise_destroy": (_int, (_vp,)),
+    "rnnoise_process_frame": (C.c_float, (_vp, _fp_t, _fp_t)),
+    "rnnoise_model_from_buffer": (_vp, (_cp, _int)),
+    "rnnoise_model_from_file": (_vp, (_vp,)),
+    "rnnoise_model_from_filename": (_vp, (_cp,)),
+    "rnnoise_model_free": (_int, (_vp,)),
+    # include/rnnoise_amd.h
+    "rnnoise_amd_device_count": (_int, ()),
+    "rnnoise_amd_set_rcp_profile": (_int, (_cp,)),
+    "rnnoise_amd_rcp_profile": (_cp, ()),
+    "rnnoise_amd_log10_model": (_cp, ()),
+    "rnnoise_batch_create": (_vp, (_vp, _int, _int)),
+    "rnnoise_batch_destroy": (_int, (_vp,)),
+    "rnnoise_batch_size": (_int, (_vp,)),
+    "rnnoise_batch_reset": (_int, (_vp,)),
+    "rnnoise_batch_process": (_int, (_vp, _fp_t, _fp_t, _fp_t, _fp_t, _int)),
+    "rnnoise_batch_process_device": (_int, (_vp,) * 5 + (_int, _vp)),
+    "rnnoise_batch_process_s16": (_int, (_vp, _sp, _sp, _fp_t, _fp_t, _int)),
+    "rnnoise_batch_process_device_s16": (_int, (_vp,) * 5 + (_int, _vp)),
+    **_twins("rnnoise_batch_process_device_masked", (_vp,) * 6 + (_int, _vp)),
+    **_twins("rnnoise_batch_process_masked", (_vp, _PCM, _PCM, _fp_t, _fp_t, _up, _int)),
+    **_twins("rnnoise_batch_process_device_list", (_vp,) * 6 + (_int, _vp, _int, _vp)),
+    **_twins("rnnoise_batch_process_list", (_vp, _PCM, _PCM, _fp_t, _fp_t, _ip, _int, _up, _int)),
+    "rnnoise_batch_reset_streams": (_int, (_vp, _ip, _int)),
+    "rnnoise_batch_reset_streams_device": (_int, (_vp, _vp, _int, _vp)),
+    "rnnoise_batch_set_pcm_rate": (_int, (_vp, _int)),
+    "rnnoise_batch_pcm_rate": (_int, (_vp,)),
+    **_stream_table("rates", _up),
+    **_stream_table("formats", _up),
+    **_stream_table("out_rates", _up),
+    **_stream_table("out_formats", _up),
+    "rnnoise_batch_set_pcm_layout": (_int, (_vp, _long, _long)),
+    "rnnoise_batch_pcm_layout": (_int, (_vp, _lp, _lp)),
+    "rnnoise_amd_pcm_layout_fits": (_int, (_long, _long, _int, _int, _int)),
+    "rnnoise_batch_set_pcm_channels": (_int, (_vp, _int)),
+    "rnnoise_batch_pcm_channels": (_int, (_vp,)),
+    "rnnoise_amd_pcm_channels_fit": (_int, (_long, _long, _int, _int, _int, _int)),
+    "rnnoise_batch_set_gain_link": (_int, (_vp, _int)),
+    "rnnoise_batch_gain_link": (_int, (_vp,)),
+    "rnnoise_batch_add_model": (_int, (_vp, _vp)),
+    **_stream_table("models", _up),
+    **_stream_table("controls", _fp_t),
+    "rnnoise_batch_export_state": (_int, (_vp, _int, _fp_t)),
+    "rnnoise_batch_import_state": (_int, (_vp, _int, _fp_t)),
+    "rnnoise_batch_save_streams_device": (_int, (_vp, _vp, _vp, _int, _vp)),
+    "rnnoise_batch_load_streams_device": (_int, (_vp, _vp, _vp, _int, _vp)),
+    "rnnoise_batch_save_streams": (_int, (_vp, _fp_t, _ip, _int)),
+    "rnnoise_batch_load_streams": (_int, (_vp, _fp_t, _ip, _int)),
+    "rnnoise_amd_chunk_frames": (_int, (_int, _int)),
+    **_twins("rnnoise_batch_process_device_chunks", (_vp,) * 4 + (_int,) + (_vp,) * 4),
+    **_twins("rnnoise_batch_process_chunks", (_vp, _PCM, _PCM, _ip, _int, _fp_t, _fp_t, _ip)),
+    "rnnoise_batch_chunk_fill": (_int, (_vp, _ip)),
+    **_twins("rnnoise_batch_process_device_chunks_list", (_vp,) * 4 + (_int, _vp, _int) + (_vp,) * 4),
+    **_twins("rnnoise_batch_process_chunks_list", (_vp, _PCM, _PCM, _ip, _int, _ip, _int, _fp_t, _fp_t, _ip)),
+    "rnnoise_batch_save_chunk_fifos_device": (_int, (_vp, _vp, _vp, _int, _vp)),
+    "rnnoise_batch_load_chunk_fifos_device": (_int, (_vp, _vp, _vp, _int, _vp)),
+    "rnnoise_batch_save_chunk_fifos": (_int, (_vp, _fp_t, _ip, _int)),
+    "rnnoise_batch_load_chunk_fifos": (_int, (_vp, _fp_t, _ip, _int)),
+    "rnnoise_batch_set_nn_path": (_int, (_vp, _int)),
+    "rnnoise_batch_set_schedule": (_int, (_vp, _int)),
+    "rnnoise_model_weight_bytes": (_long, (_vp,)),
+    "rnnoise_amd_model_pack": (_long, (_vp, _vp, _long)),
+    "rnnoise_batch_train_features": (_int, (_vp, _fp_t, _fp_t, _fp_t, _fp_t, _ip, _ip, _ip, _int)),
+    "rnnoise_batch_train_features_device": (_int, (_vp,) * 8 + (_int, _vp)),
+    "rnnoise_amd_train_mix_check": (_int, (_vp, _int, _ll, _ll, _ll, _int)),
+    "rnnoise_batch_train_levels_device": (_int, (_vp,) * 6 + (_ll, _ll, _ll, _vp, _int, _vp)),
+    "rnnoise_amd_train_vad": (_int, (_fp_t, _int, _int, _ip, _up)),
+    "rnnoise_amd_train_vad_device_available": (_int, ()),
+    "rnnoise_batch_train_levels_vad_device": (_int, (_vp,) * 7 + (_ll, _ll, _ll, _vp, _ip, _int, _vp)),
+    "rnnoise_batch_train_mix_device": (_int, (_vp,) * 8 + (_ll, _ll, _ll, _vp, _vp, _vp, _int, _vp)),
+    "rnnoise_amd_train_rir_check": (_int, (_vp, _int, _int)),
+    "rnnoise_amd_train_rir_work_bytes": (_ll, (_ll,)),
+    "rnnoise_batch_train_rir_load_device": (_int, (_vp, _vp, _vp, _ip, _int, _vp)),
+    "rnnoise_batch_train_rir_device": (_int, (_vp, _vp, _vp, _vp, _int, _vp, _vp, _ll, _int, _vp)),
+    "rnnoise_amd_eval_records_check": (_int, (_vp, _long, _long, _int, _int, _int, _int)),
+    "rnnoise_batch_process_features_device": (_int, (_vp,) * 4 + (_long, _long, _int, _vp)),
+    "rnnoise_batch_process_features": (_int, (_vp, _fp_t, _fp_t, _fp_t, _long, _long, _int)),
+    "rnnoise_batch_eval_records_device": (_int, (_vp,) * 5 + (_long, _long, _int, _int, _vp, _vp)),
+    "rnnoise_batch_eval_records": (_int, (_vp, _dp, _fp_t, _fp_t, _fp_t, _long, _long, _int, _int, _vp)),
+    "rnnoise_amd_score_records_check": (_int, (_vp,) + (_long,) * 6 + (_int,) * 3),
+    "rnnoise_batch_score_records_device": (_int, (_vp, _vp, _vp, _vp, _long, _long, _vp, _long, _long, _vp, _long, _long, _int, _int, _int,
+                                                  _vp, _vp)),
+    "rnnoise_batch_score_records": (_int, (_vp, _dp, _dp, _fp_t, _long, _long, _fp_t, _long, _long, _fp_t, _long, _long, _int, _int, _int,
+                                           _vp)),
+    "rnnoise_amd_split_frame_bytes": (_long, (_int,)),
+    "rnnoise_amd_split_rows_check": (_int, (_vp, _int, _int, _int)),
+    "rnnoise_batch_split_reserve": (_int, (_vp, _int)),
+    "rnnoise_batch_split_pending": (_int, (_vp,)),
+    **_twins("rnnoise_batch_analyze_device", (_vp,) * 5 + (_int, _vp)),
+    **_twins("rnnoise_batch_analyze", (_vp, _fp_t, _vp, _ip, _PCM, _int)),
+    **_twins("rnnoise_batch_synthesize_device", (_vp,) * 6 + (_int, _vp)),
+    **_twins("rnnoise_batch_synthesize", (_vp, _PCM, _fp_t, _vp, _fp_t, _vp, _int)),
+    "rnnoise_batch_debug_last": (_int, (_vp, _fp_t, _ip, _ip)),
+    "rnnoise_batch_enable_timing": (_int, (_vp, _int)),
+    "rnnoise_batch_kernel_ms": (_int, (_vp, _dp, _lp)),
+}
+# include/rnnoise_amd_debug.h: present in the instrumented library only
+DEBUG_PROTOTYPES = {
+    "rnnoise_batch_debug_pitch": (_int, (_vp, _fp_t)),
+    "rnnoise_amd_debug_fft": (_int, (_int, _int, _fp_t, _fp_t, _int, _int, C.POINTER(C.c_ulonglong), _ip)),
+    "rnnoise_amd_debug_log_energy": (_int, (_int, _fp_t, _fp_t, _int)),
+    "rnnoise_amd_debug_log_energy_range": (_int, (_int, _fp_t, _fp_t, _uint, _uint, _int)),
+    "rnnoise_amd_debug_train_vad_libm": (_int, (_int, _int, _uint, _uint, _uint, C.POINTER(C.c_ulonglong), C.POINTER(_uint))),
+    "rnnoise_amd_debug_train_vad_selfcheck": (None, (_int,)),
+}
+EXPORTS = list(PROTOTYPES)  # every symbol declared in include/rnnoise.h and include/rnnoise_amd.h
+DEBUG_EXPORTS = list(DEBUG_PROTOTYPES)
 
 
 class TrainMix(C.Structure):
@@ -184,11 +272,6 @@ def _share_hip_runtime_with_torch():
             C.CDLL(p, mode=C.RTLD_GLOBAL)
 
 
-# entry points of include/rnnoise_amd_debug.h: present in the instrumented library only
-DEBUG_EXPORTS = ["rnnoise_batch_debug_pitch", "rnnoise_amd_debug_fft", "rnnoise_amd_debug_log_energy", "rnnoise_amd_debug_log_energy_range",
-                 "rnnoise_amd_debug_train_vad_libm", "rnnoise_amd_debug_train_vad_selfcheck"]
-
-
 def lib():
     """the library every call of this module goes to: the product, or -- inside `with instrumented():` -- its instrumented twin"""
     global _lib, _product
@@ -221,135 +304,16 @@ class instrumented:
 
 
 def _load(path, debug):
-    if True:
-        _share_hip_runtime_with_torch()
-        if not os.path.exists(path):
-            raise RuntimeError(
-                f"{path} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        L = C.CDLL(path)
-        vp, fp, ip = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)
-        L.rnnoise_get_size.restype = C.c_int
-        L.rnnoise_get_frame_size.restype = C.c_int
-        L.rnnoise_init.argtypes = [vp, vp]
-        L.rnnoise_create.restype = vp
-        L.rnnoise_create.argtypes = [vp]
-        L.rnnoise_destroy.argtypes = [vp]
-        L.rnnoise_process_frame.restype = C.c_float
-        L.rnnoise_process_frame.argtypes = [vp, fp, fp]
-        L.rnnoise_model_from_buffer.restype = vp
-        L.rnnoise_model_from_buffer.argtypes = [C.c_char_p, C.c_int]
-        L.rnnoise_model_from_filename.restype = vp
-        L.rnnoise_model_from_filename.argtypes = [C.c_char_p]
-        L.rnnoise_model_free.argtypes = [vp]
-        L.rnnoise_amd_device_count.restype = C.c_int
-        L.rnnoise_batch_create.restype = vp
-        L.rnnoise_batch_create.argtypes = [vp, C.c_int, C.c_int]
-        L.rnnoise_batch_destroy.argtypes = [vp]
-        L.rnnoise_batch_size.argtypes = [vp]
-        L.rnnoise_batch_reset.argtypes = [vp]
-        sp, up = C.POINTER(C.c_short), C.POINTER(C.c_ubyte)
-        # the process calls, each as float and as int16 ("_s16"): host PCM pointers typed, device pointers plain addresses
-        for sfx, pp in (("", fp), ("_s16", sp)):
-            for name, args in (("process", [vp, pp, pp, fp, fp, C.c_int]),
-                               ("process_device", [vp] * 5 + [C.c_int, vp]),
-                               ("process_masked", [vp, pp, pp, fp, fp, up, C.c_int]),
-                               ("process_device_masked", [vp] * 6 + [C.c_int, vp]),
-                               ("process_list", [vp, pp, pp, fp, fp, ip, C.c_int, up, C.c_int]),
-                               ("process_device_list", [vp] * 6 + [C.c_int, vp, C.c_int, vp])):
-                getattr(L, f"rnnoise_batch_{name}{sfx}").argtypes = args
-            getattr(L, f"rnnoise_batch_process_chunks{sfx}").argtypes = [vp, pp, pp, ip, C.c_int, fp, fp, ip]
-            getattr(L, f"rnnoise_batch_process_device_chunks{sfx}").argtypes = [vp] * 4 + [C.c_int] + [vp] * 4
-            getattr(L, f"rnnoise_batch_process_chunks_list{sfx}").argtypes = [vp, pp, pp, ip, C.c_int, ip, C.c_int, fp, fp, ip]
-            getattr(L, f"rnnoise_batch_process_device_chunks_list{sfx}").argtypes = [vp] * 4 + [C.c_int, vp, C.c_int] + [vp] * 4
-        L.rnnoise_amd_chunk_frames.argtypes = [C.c_int, C.c_int]
-        L.rnnoise_batch_chunk_fill.argtypes = [vp, ip]
-        # the per-stream tables: host setter, device setter (table, stream), getter
-        for name, tp in (("rates", up), ("formats", up), ("out_rates", up), ("out_formats", up), ("models", up), ("controls", fp)):
-            getattr(L, f"rnnoise_batch_set_stream_{name}").argtypes = [vp, tp]
-            getattr(L, f"rnnoise_batch_set_stream_{name}_device").argtypes = [vp, vp, vp]
-            getattr(L, f"rnnoise_batch_stream_{name}").argtypes = [vp, tp]
-        L.rnnoise_batch_reset_streams.argtypes = [vp, ip, C.c_int]
-        L.rnnoise_batch_reset_streams_device.argtypes = [vp, vp, C.c_int, vp]
-        L.rnnoise_batch_set_pcm_rate.argtypes = [vp, C.c_int]
-        L.rnnoise_batch_pcm_rate.argtypes = [vp]
-        L.rnnoise_batch_set_pcm_layout.argtypes = [vp, C.c_long, C.c_long]
-        L.rnnoise_batch_pcm_layout.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-        L.rnnoise_amd_pcm_layout_fits.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int]
-        L.rnnoise_batch_set_pcm_channels.argtypes = [vp, C.c_int]
-        L.rnnoise_batch_pcm_channels.argtypes = [vp]
-        L.rnnoise_batch_set_gain_link.argtypes = [vp, C.c_int]
-        L.rnnoise_batch_gain_link.argtypes = [vp]
-        L.rnnoise_amd_pcm_channels_fit.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.rnnoise_batch_add_model.argtypes = [vp, vp]
-        L.rnnoise_batch_export_state.argtypes = [vp, C.c_int, fp]
-        L.rnnoise_batch_import_state.argtypes = [vp, C.c_int, fp]
-        L.rnnoise_batch_save_streams_device.argtypes = [vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_load_streams_device.argtypes = [vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_save_streams.argtypes = [vp, fp, ip, C.c_int]
-        L.rnnoise_batch_load_streams.argtypes = [vp, fp, ip, C.c_int]
-        L.rnnoise_batch_save_chunk_fifos_device.argtypes = [vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_load_chunk_fifos_device.argtypes = [vp, vp, vp, C.c_int, vp]
-        L.rnnoise_batch_save_chunk_fifos.argtypes = [vp, fp, ip, C.c_int]
-        L.rnnoise_batch_load_chunk_fifos.argtypes = [vp, fp, ip, C.c_int]
-        L.rnnoise_batch_set_nn_path.argtypes = [vp, C.c_int]
-        L.rnnoise_batch_set_schedule.argtypes = [vp, C.c_int]
-        L.rnnoise_amd_model_pack.restype = C.c_long
-        L.rnnoise_amd_model_pack.argtypes = [vp, vp, C.c_long]
-        L.rnnoise_model_weight_bytes.restype = C.c_long
-        L.rnnoise_model_weight_bytes.argtypes = [vp]
-        L.rnnoise_batch_debug_last.argtypes = [vp, fp, ip, ip]
-        L.rnnoise_batch_train_features.argtypes = [vp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
-        L.rnnoise_batch_train_features_device.argtypes = [vp] * 8 + [C.c_int, vp]
-        ll = C.c_longlong
-        L.rnnoise_amd_train_mix_check.argtypes = [vp, C.c_int, ll, ll, ll, C.c_int]
-        L.rnnoise_batch_train_levels_device.argtypes = [vp] * 6 + [ll, ll, ll, vp, C.c_int, vp]
-        L.rnnoise_amd_train_vad.argtypes = [fp, C.c_int, C.c_int, ip, up]
-        L.rnnoise_amd_train_vad_device_available.argtypes = []
-        L.rnnoise_batch_train_levels_vad_device.argtypes = [vp] * 7 + [ll, ll, ll, vp, ip, C.c_int, vp]
-        L.rnnoise_batch_train_mix_device.argtypes = [vp] * 8 + [ll, ll, ll, vp, vp, vp, C.c_int, vp]
-        L.rnnoise_amd_train_rir_check.argtypes = [vp, C.c_int, C.c_int]
-        L.rnnoise_amd_train_rir_work_bytes.restype = ll
-        L.rnnoise_amd_train_rir_work_bytes.argtypes = [ll]
-        L.rnnoise_batch_train_rir_load_device.argtypes = [vp, vp, vp, ip, C.c_int, vp]
-        L.rnnoise_batch_train_rir_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, ll, C.c_int, vp]
-        dp, lg = C.POINTER(C.c_double), C.c_long
-        L.rnnoise_amd_eval_records_check.argtypes = [vp, lg, lg, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.rnnoise_batch_process_features_device.argtypes = [vp] * 4 + [lg, lg, C.c_int, vp]
-        L.rnnoise_batch_process_features.argtypes = [vp, fp, fp, fp, lg, lg, C.c_int]
-        L.rnnoise_batch_eval_records_device.argtypes = [vp] * 5 + [lg, lg, C.c_int, C.c_int, vp, vp]
-        L.rnnoise_batch_eval_records.argtypes = [vp, dp, fp, fp, fp, lg, lg, C.c_int, C.c_int, vp]
-        L.rnnoise_amd_score_records_check.argtypes = [vp] + [lg] * 6 + [C.c_int] * 3
-        L.rnnoise_batch_score_records_device.argtypes = [vp, vp, vp, vp, lg, lg, vp, lg, lg, vp, lg, lg, C.c_int, C.c_int, C.c_int, vp, vp]
-        L.rnnoise_batch_score_records.argtypes = [vp, dp, dp, fp, lg, lg, fp, lg, lg, fp, lg, lg, C.c_int, C.c_int, C.c_int, vp]
-        sp = C.POINTER(C.c_short)
-        L.rnnoise_amd_split_frame_bytes.restype = C.c_long
-        L.rnnoise_amd_split_frame_bytes.argtypes = [C.c_int]
-        L.rnnoise_amd_split_rows_check.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-        L.rnnoise_batch_split_reserve.argtypes = [vp, C.c_int]
-        L.rnnoise_batch_split_pending.argtypes = [vp]
-        L.rnnoise_batch_analyze_device.argtypes = [vp] * 5 + [C.c_int, vp]
-        L.rnnoise_batch_analyze_device_s16.argtypes = [vp] * 5 + [C.c_int, vp]
-        L.rnnoise_batch_analyze.argtypes = [vp, fp, vp, ip, fp, C.c_int]
-        L.rnnoise_batch_analyze_s16.argtypes = [vp, fp, vp, ip, sp, C.c_int]
-        L.rnnoise_batch_synthesize_device.argtypes = [vp] * 6 + [C.c_int, vp]
-        L.rnnoise_batch_synthesize_device_s16.argtypes = [vp] * 6 + [C.c_int, vp]
-        L.rnnoise_batch_synthesize.argtypes = [vp, fp, fp, vp, fp, vp, C.c_int]
-        L.rnnoise_batch_synthesize_s16.argtypes = [vp, sp, fp, vp, fp, vp, C.c_int]
-        if debug:
-            L.rnnoise_batch_debug_pitch.argtypes = [vp, fp]
-            L.rnnoise_amd_debug_train_vad_libm.argtypes = [C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong),
-                                                           C.POINTER(C.c_uint)]
-            L.rnnoise_amd_debug_train_vad_selfcheck.argtypes = [C.c_int]
-            L.rnnoise_amd_debug_train_vad_selfcheck.restype = None
-            L.rnnoise_amd_debug_log_energy.argtypes = [C.c_int, fp, fp, C.c_int]
-            L.rnnoise_amd_debug_log_energy_range.argtypes = [C.c_int, fp, fp, C.c_uint, C.c_uint, C.c_int]
-            L.rnnoise_amd_debug_fft.argtypes = [C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), ip]
-        L.rnnoise_batch_enable_timing.argtypes = [vp, C.c_int]
-        L.rnnoise_batch_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
-        L.rnnoise_amd_set_rcp_profile.argtypes = [C.c_char_p]
-        L.rnnoise_amd_rcp_profile.restype = C.c_char_p
-        L.rnnoise_amd_log10_model.restype = C.c_char_p
+    _share_hip_runtime_with_torch()
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"{path} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
+    L = C.CDLL(path)
+    for table in (PROTOTYPES, DEBUG_PROTOTYPES) if debug else (PROTOTYPES,):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return L
 
 
@@ -553,6 +517,60 @@ class Model:
             pass
 
 
+def _encode_rates(b, hz):
+    hz = np.asarray(hz).reshape(-1)
+    assert hz.size == b.n
+    if not np.isin(hz, PCM_RATES_ALL).all():
+        raise ValueError(f"stream rate unsupported (each one of {PCM_RATES_ALL})")
+    if hz.max(initial=0) > b.pcm_rate:
+        raise ValueError(f"a stream rate above the batch's PCM rate {b.pcm_rate}: its frame would not fit its row")
+    return np.ascontiguousarray(rate_code(hz), np.uint8)
+
+
+def _encode_formats(b, formats):
+    from . import g711
+    if isinstance(formats, np.ndarray) and formats.dtype.kind in "iu":
+        formats = formats.reshape(-1).tolist()
+    codes = np.array([g711.code(f) for f in formats], np.uint8)
+    assert codes.size == b.n
+    return codes
+
+
+def _encode_models(b, models):
+    m = np.asarray(models).reshape(-1)
+    assert m.size == b.n
+    if m.min(initial=0) < 0 or m.max(initial=0) > 255:
+        raise ValueError("model slot out of range")
+    return np.ascontiguousarray(m, np.uint8)
+
+
+def _encode_controls(b, ctl):
+    c = np.ascontiguousarray(ctl, np.float32)
+    assert c.shape == (b.n, CTL_FLOATS), c.shape
+    return c
+
+
+def _same(a):
+    return a
+
+
+def _decode_rates(codes):
+    return code_rate(codes).astype(np.int32)
+
+
+# The per-stream tables of a batch (rnnoise_batch_set_stream_<stem>, ..._device, rnnoise_batch_stream_<stem>): the element type and
+# the trailing shape of a row, whether None drops the table, the caller's values -> the C table (encode(batch, values): validates, or
+# raises) and back, and what a refusal of the host setter may mean
+_StreamTable = collections.namedtuple("_StreamTable", "stem ctype row droppable encode decode why")
+_RATES = _StreamTable("rates", C.c_ubyte, (), True, _encode_rates, _decode_rates, "")
+_FORMATS = _StreamTable("formats", C.c_ubyte, (), True, _encode_formats, _same, "")
+_OUT_RATES = _RATES._replace(stem="out_rates")
+_OUT_FORMATS = _FORMATS._replace(stem="out_formats")
+_MODELS = _StreamTable("models", C.c_ubyte, (), False, _encode_models, _same, " (an entry names no slot)")
+_CONTROLS = _StreamTable("controls", C.c_float, (CTL_FLOATS,), True, _encode_controls, _same,
+                         " (an entry is non-finite, out of range or has a fractional hold)")
+
+
 class Batch:
     """N concurrent streams on one GPU (include/rnnoise_amd.h)."""
 
@@ -715,56 +733,56 @@ class Batch:
         if getattr(self._L, fn)(self.h, *args):
             raise exc(f"{fn} failed{why}")
 
+    def _call_s16(self, fn, s16, *args, why=""):
+        """... of `fn` or, with s16, of its int16 twin; the RuntimeError names `fn` either way"""
+        if getattr(self._L, fn + "_s16" if s16 else fn)(self.h, *args):
+            raise RuntimeError(f"{fn} failed{why}")
+
+    def _table_set(self, t, table):
+        """the host setter of a per-stream table: `table` through t.encode, or None to drop a table that can be dropped"""
+        fn = f"rnnoise_batch_set_stream_{t.stem}"
+        if table is None and t.droppable:
+            return self._call(fn, None)
+        self._call(fn, t.encode(self, table).ctypes.data_as(C.POINTER(t.ctype)), exc=ValueError, why=t.why)
+
+    def _table_set_device(self, t, d_table, stream):
+        self._call(f"rnnoise_batch_set_stream_{t.stem}_device", d_table or None, stream or None)
+
+    def _table_get(self, t):
+        a = np.empty((self.n,) + t.row, t.ctype)
+        self._call(f"rnnoise_batch_stream_{t.stem}", a.ctypes.data_as(C.POINTER(t.ctype)))
+        return t.decode(a)
+
     def set_stream_rates(self, hz):
         """the PCM rate of every stream in Hz (rnnoise_batch_set_stream_rates): (N,) values out of PCM_RATES_ALL, none above the batch's
         own rate, or None to drop the table.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose
         rate changes restart their resampling filters from zero; every stream keeps its DenoiseState."""
-        if hz is None:
-            return self._call("rnnoise_batch_set_stream_rates", None)
-        hz = np.asarray(hz).reshape(-1)
-        assert hz.size == self.n
-        if not np.isin(hz, PCM_RATES_ALL).all():
-            raise ValueError(f"stream rate unsupported (each one of {PCM_RATES_ALL})")
-        if hz.max(initial=0) > self.pcm_rate:
-            raise ValueError(f"a stream rate above the batch's PCM rate {self.pcm_rate}: its frame would not fit its row")
-        L = np.ascontiguousarray(rate_code(hz), np.uint8)
-        self._call("rnnoise_batch_set_stream_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
+        self._table_set(_RATES, hz)
 
     def set_stream_rates_device(self, d_rates: int, stream: int = 0):
         """the same from N bytes of device memory holding the rate CODES (rate_code: the divisors 1, 2, 3, 6, and RATE_32K), a copy ordered on
         `stream`; any other byte, or a rate above the batch's, reads as the batch's rate.  Histories are not touched: reset or load the streams whose
         rate changed (reset_streams_device / load_streams_device) on the same stream before their next frame."""
-        self._call("rnnoise_batch_set_stream_rates_device", d_rates or None, stream or None)
+        self._table_set_device(_RATES, d_rates, stream)
 
     def stream_rates(self) -> np.ndarray:
         """the PCM rate of every stream in Hz, (N,) int32 (synchronous; the batch's rate everywhere without a table)"""
-        L = np.empty(self.n, np.uint8)
-        self._call("rnnoise_batch_stream_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        return code_rate(L).astype(np.int32)
+        return self._table_get(_RATES)
 
     def set_stream_formats(self, formats):
         """the PCM format of every stream's rows in the int16 calls (rnnoise_batch_set_stream_formats): (N,) names out of "s16",
         "ulaw", "alaw" or codes 0, 1, 2 (rnnoise_amd.g711), or None to drop the table.  A companded stream's G.711 bytes fill the
         first 480 * rate // 48000 BYTES of its int16 row.  Synchronous; ValueError (and nothing changes) on anything else."""
-        if formats is None:
-            return self._call("rnnoise_batch_set_stream_formats", None)
-        from . import g711
-        if isinstance(formats, np.ndarray) and formats.dtype.kind in "iu":
-            formats = formats.reshape(-1).tolist()
-        codes = np.array([g711.code(f) for f in formats], np.uint8)
-        assert codes.size == self.n
-        self._call("rnnoise_batch_set_stream_formats", codes.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
+        self._table_set(_FORMATS, formats)
 
     def set_stream_formats_device(self, d_formats: int, stream: int = 0):
         """the same from N bytes of device memory holding the CODES (0 s16, 1 ulaw, 2 alaw), a copy ordered on `stream`; any other
         byte reads as s16.  Nothing else changes: a stream that changes codec mid-run is the caller's to reset."""
-        self._call("rnnoise_batch_set_stream_formats_device", d_formats or None, stream or None)
+        self._table_set_device(_FORMATS, d_formats, stream)
 
     def stream_formats(self) -> np.ndarray:
         """the format code of every stream as the kernels read it, (N,) uint8 (synchronous; zeros without a table)"""
-        f = np.empty(self.n, np.uint8)
-        self._call("rnnoise_batch_stream_formats", f.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        return f
+        return self._table_get(_FORMATS)
 
     def set_stream_out_rates(self, hz):
         """the rate every stream's OUTPUT rows are written at, in Hz (rnnoise_batch_set_stream_out_rates): (N,) values out of
@@ -772,50 +790,30 @@ class Batch:
         at).  A stream reads the first 480 * rate_in // 48000 samples of its `in` row and writes the first 480 * rate_out // 48000 of
         its `out` row.  Synchronous; ValueError (and nothing changes) on any other value.  The streams whose output rate changes
         restart their down-resampling filter from zero; every stream keeps its DenoiseState and its up-resampling filter."""
-        if hz is None:
-            return self._call("rnnoise_batch_set_stream_out_rates", None)
-        hz = np.asarray(hz).reshape(-1)
-        assert hz.size == self.n
-        if not np.isin(hz, PCM_RATES_ALL).all():
-            raise ValueError(f"stream rate unsupported (each one of {PCM_RATES_ALL})")
-        if hz.max(initial=0) > self.pcm_rate:
-            raise ValueError(f"a stream rate above the batch's PCM rate {self.pcm_rate}: its frame would not fit its row")
-        L = np.ascontiguousarray(rate_code(hz), np.uint8)
-        self._call("rnnoise_batch_set_stream_out_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
+        self._table_set(_OUT_RATES, hz)
 
     def set_stream_out_rates_device(self, d_rates: int, stream: int = 0):
         """the same from N bytes of device memory holding the rate CODES, a copy ordered on `stream`; any other byte, or a rate above
         the batch's, reads as the batch's rate.  Histories are not touched (set_stream_rates_device)."""
-        self._call("rnnoise_batch_set_stream_out_rates_device", d_rates or None, stream or None)
+        self._table_set_device(_OUT_RATES, d_rates, stream)
 
     def stream_out_rates(self) -> np.ndarray:
         """the rate every stream's output is written at in Hz, (N,) int32 (synchronous; stream_rates() without an out table)"""
-        L = np.empty(self.n, np.uint8)
-        self._call("rnnoise_batch_stream_out_rates", L.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        return code_rate(L).astype(np.int32)
+        return self._table_get(_OUT_RATES)
 
     def set_stream_out_formats(self, formats):
         """the PCM format of every stream's OUTPUT rows in the int16 calls (rnnoise_batch_set_stream_out_formats): as
         set_stream_formats, which then describes the `in` rows alone; None drops the table (output format = input format)."""
-        if formats is None:
-            return self._call("rnnoise_batch_set_stream_out_formats", None)
-        from . import g711
-        if isinstance(formats, np.ndarray) and formats.dtype.kind in "iu":
-            formats = formats.reshape(-1).tolist()
-        codes = np.array([g711.code(f) for f in formats], np.uint8)
-        assert codes.size == self.n
-        self._call("rnnoise_batch_set_stream_out_formats", codes.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError)
+        self._table_set(_OUT_FORMATS, formats)
 
     def set_stream_out_formats_device(self, d_formats: int, stream: int = 0):
         """the same from N bytes of device memory holding the CODES (0 s16, 1 ulaw, 2 alaw), a copy ordered on `stream`; any other
         byte reads as s16"""
-        self._call("rnnoise_batch_set_stream_out_formats_device", d_formats or None, stream or None)
+        self._table_set_device(_OUT_FORMATS, d_formats, stream)
 
     def stream_out_formats(self) -> np.ndarray:
         """the format code of every stream's output rows as K3 reads it, (N,) uint8 (synchronous; stream_formats() without an out table)"""
-        f = np.empty(self.n, np.uint8)
-        self._call("rnnoise_batch_stream_out_formats", f.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        return f
+        return self._table_get(_OUT_FORMATS)
 
     def process(self, pcm: np.ndarray, want_gains: bool = True, out: np.ndarray | None = None):
         """pcm: (T, N, frame) float32 host array -> (out, vad[T,N], gains[T,N,32]).  With a PCM layout set (set_pcm_layout) pcm and
@@ -832,15 +830,12 @@ class Batch:
         and written by DMA in place; pageable memory goes through the library's pinned bounce buffers."""
         fp = C.POINTER(C.c_float)
         pp = C.POINTER(C.c_short) if s16 else fp
-        fn = self._L.rnnoise_batch_process_s16 if s16 else self._L.rnnoise_batch_process
-        if fn(self.h, C.cast(out_ptr, pp), C.cast(in_ptr, pp), C.cast(vad_ptr or None, fp), C.cast(gains_ptr or None, fp), n_frames):
-            raise RuntimeError("rnnoise_batch_process failed")
+        self._call_s16("rnnoise_batch_process", s16, C.cast(out_ptr, pp), C.cast(in_ptr, pp), C.cast(vad_ptr or None, fp),
+                       C.cast(gains_ptr or None, fp), n_frames)
 
     def process_device(self, d_out: int, d_in: int, d_vad: int, d_gains: int, n_frames: int, stream: int = 0, s16: bool = False):
         """Raw device pointers (ints), asynchronous on `stream` (a hipStream_t handle); s16: the PCM buffers hold int16."""
-        fn = self._L.rnnoise_batch_process_device_s16 if s16 else self._L.rnnoise_batch_process_device
-        if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, n_frames, stream or None):
-            raise RuntimeError("rnnoise_batch_process_device failed")
+        self._call_s16("rnnoise_batch_process_device", s16, d_out, d_in, d_vad or None, d_gains or None, n_frames, stream or None)
 
     def _process(self, name, dtype, pcm, want_gains, out, masked=False, active=None, streams=None):
         """the host process calls: rnnoise_batch_<name> on PCM of `dtype`.  masked: the call takes `active` and leaves absent rows of
@@ -878,32 +873,41 @@ class Batch:
     def process_masked_device(self, d_out: int, d_in: int, d_vad: int, d_gains: int, d_active: int, n_frames: int, stream: int = 0,
                               s16: bool = False):
         """Raw device pointers (ints), asynchronous on `stream`; d_active: [n_frames][N] bytes, 0 = every stream present."""
-        fn = self._L.rnnoise_batch_process_device_masked_s16 if s16 else self._L.rnnoise_batch_process_device_masked
-        if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_active or None, n_frames, stream or None):
-            raise RuntimeError("rnnoise_batch_process_device_masked failed")
+        self._call_s16("rnnoise_batch_process_device_masked", s16, d_out, d_in, d_vad or None, d_gains or None, d_active or None, n_frames,
+                       stream or None)
 
-    def _process_chunks(self, name, dtype, pcm, counts, want_gains, out):
+    def _process_chunks(self, name, dtype, pcm, counts, want_gains, out, streams=None):
+        """the host chunk calls: rnnoise_batch_<name> on PCM of `dtype`, one row per stream; streams: a list call, whose arrays have one
+        row per listed stream"""
+        ip = C.POINTER(C.c_int)
+        if streams is None:
+            R, rows, shape, listed = self.n, [], "chunk PCM is (n_streams, max_count)", ""
+            why = " (a count outside [0, max_count], or a batch with a rate / format table, a PCM layout, channels or a gain link?)"
+        else:
+            idx = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+            R, shape, listed = int(idx.size), "list chunk PCM is (n_rows, max_count)", "listed "
+            rows = [idx.ctypes.data_as(ip), R]
+            why = (" (a stream out of range or listed twice, a count outside [0, max_count], more rows than streams, or a batch"
+                   " with a rate / format table, a PCM layout, channels or a gain link?)")
         pcm = np.asarray(pcm)
-        if pcm.ndim != 2 or pcm.shape[0] != self.n:
-            raise ValueError(f"chunk PCM is (n_streams, max_count); got {pcm.shape} for {self.n} streams")
+        if pcm.ndim != 2 or pcm.shape[0] != R:
+            raise ValueError(f"{shape}; got {pcm.shape} for {R} {listed}streams")
         pcm = np.ascontiguousarray(pcm, dtype)
         max_count = pcm.shape[1]
         counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.int32)
-        if counts.size != self.n:
-            raise ValueError("one count per stream")
+        if counts.size != R:
+            raise ValueError(f"one count per {listed}stream")
         if out is None:
             out = np.zeros_like(pcm)
         elif out.dtype != dtype or out.shape != pcm.shape or not out.flags.c_contiguous:
             raise ValueError("out: a C-contiguous array of the PCM's shape and type")
         F = chunk_frames(self.frame, max_count)
-        vad = np.zeros((F, self.n), np.float32)
-        gains = np.zeros((F, self.n, 32), np.float32) if want_gains else None
-        frames = np.zeros(self.n, np.int32)
+        vad = np.zeros((F, R), np.float32)
+        gains = np.zeros((F, R, 32), np.float32) if want_gains else None
+        frames = np.zeros(R, np.int32)
         pp = C.POINTER(C.c_short if dtype == np.int16 else C.c_float)
-        ip = C.POINTER(C.c_int)
         self._call(f"rnnoise_batch_{name}", out.ctypes.data_as(pp), pcm.ctypes.data_as(pp), counts.ctypes.data_as(ip),
-                   int(max_count), _fp(vad), _fp(gains), frames.ctypes.data_as(ip), exc=ValueError,
-                   why=" (a count outside [0, max_count], or a batch with a rate / format table, a PCM layout, channels or a gain link?)")
+                   int(max_count), *rows, _fp(vad), _fp(gains), frames.ctypes.data_as(ip), exc=ValueError, why=why)
         return out, vad, gains, frames
 
     def process_chunks(self, pcm: np.ndarray, counts, want_gains: bool = True, out: np.ndarray | None = None):
@@ -920,87 +924,46 @@ class Batch:
                               d_frames: int = 0, stream: int = 0, s16: bool = False):
         """Raw device pointers (ints), asynchronous on `stream`: d_in / d_out [N][max_count] float32 (int16 with s16), d_counts [N]
         int32 (clamped into [0, max_count]), d_vad [F][N], d_gains [F][N][32], d_frames [N] int32 or 0."""
-        fn = self._L.rnnoise_batch_process_device_chunks_s16 if s16 else self._L.rnnoise_batch_process_device_chunks
-        if fn(self.h, d_out or None, d_in or None, d_counts or None, int(max_count), d_vad or None, d_gains or None, d_frames or None,
-              stream or None):
-            raise RuntimeError("rnnoise_batch_process_device_chunks failed")
-
-    def _process_chunks_list(self, name, dtype, pcm, counts, streams, want_gains, out):
-        idx = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
-        R = int(idx.size)
-        pcm = np.asarray(pcm)
-        if pcm.ndim != 2 or pcm.shape[0] != R:
-            raise ValueError(f"list chunk PCM is (n_rows, max_count); got {pcm.shape} for {R} listed streams")
-        pcm = np.ascontiguousarray(pcm, dtype)
-        max_count = pcm.shape[1]
-        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.int32)
-        if counts.size != R:
-            raise ValueError("one count per listed stream")
-        if out is None:
-            out = np.zeros_like(pcm)
-        elif out.dtype != dtype or out.shape != pcm.shape or not out.flags.c_contiguous:
-            raise ValueError("out: a C-contiguous array of the PCM's shape and type")
-        F = chunk_frames(self.frame, max_count)
-        vad = np.zeros((F, R), np.float32)
-        gains = np.zeros((F, R, 32), np.float32) if want_gains else None
-        frames = np.zeros(R, np.int32)
-        pp = C.POINTER(C.c_short if dtype == np.int16 else C.c_float)
-        ip = C.POINTER(C.c_int)
-        self._call(f"rnnoise_batch_{name}", out.ctypes.data_as(pp), pcm.ctypes.data_as(pp), counts.ctypes.data_as(ip),
-                   int(max_count), idx.ctypes.data_as(ip), R, _fp(vad), _fp(gains), frames.ctypes.data_as(ip), exc=ValueError,
-                   why=" (a stream out of range or listed twice, a count outside [0, max_count], more rows than streams, or a batch"
-                       " with a rate / format table, a PCM layout, channels or a gain link?)")
-        return out, vad, gains, frames
+        self._call_s16("rnnoise_batch_process_device_chunks", s16, d_out or None, d_in or None, d_counts or None, int(max_count),
+                       d_vad or None, d_gains or None, d_frames or None, stream or None)
 
     def process_chunks_list(self, pcm: np.ndarray, counts, streams, want_gains: bool = True, out: np.ndarray | None = None):
         """process_chunks for the listed streams only: pcm (R, max_count) float32, row i belongs to stream streams[i] and pushes its
         first counts[i] samples -> (out, vad[F,R], gains[F,R,32], frames[R]): rnnoise_batch_process_chunks_list.  Unlisted streams
         are not touched.  ValueError, and nothing changes, on a stream out of range or listed twice or a count out of range."""
-        return self._process_chunks_list("process_chunks_list", np.float32, pcm, counts, streams, want_gains, out)
+        return self._process_chunks("process_chunks_list", np.float32, pcm, counts, want_gains, out, streams)
 
     def process_chunks_list_s16(self, pcm: np.ndarray, counts, streams, want_gains: bool = True, out: np.ndarray | None = None):
         """process_chunks_list on int16 PCM (rnnoise_batch_process_chunks_list_s16)"""
-        return self._process_chunks_list("process_chunks_list_s16", np.int16, pcm, counts, streams, want_gains, out)
+        return self._process_chunks("process_chunks_list_s16", np.int16, pcm, counts, want_gains, out, streams)
 
     def process_chunks_list_device(self, d_out: int, d_in: int, d_counts: int, max_count: int, d_streams: int, n_rows: int,
                                    d_vad: int = 0, d_gains: int = 0, d_frames: int = 0, stream: int = 0, s16: bool = False):
         """Raw device pointers (ints), asynchronous on `stream`: d_in / d_out [R][max_count] float32 (int16 with s16), d_counts [R]
         int32 (clamped into [0, max_count]), d_streams [R] int32 (an entry out of range: an absent row), d_vad [F][R],
         d_gains [F][R][32], d_frames [R] int32 or 0."""
-        fn = self._L.rnnoise_batch_process_device_chunks_list_s16 if s16 else self._L.rnnoise_batch_process_device_chunks_list
-        if fn(self.h, d_out or None, d_in or None, d_counts or None, int(max_count), d_streams or None, int(n_rows), d_vad or None,
-              d_gains or None, d_frames or None, stream or None):
-            raise RuntimeError("rnnoise_batch_process_device_chunks_list failed")
+        self._call_s16("rnnoise_batch_process_device_chunks_list", s16, d_out or None, d_in or None, d_counts or None, int(max_count),
+                       d_streams or None, int(n_rows), d_vad or None, d_gains or None, d_frames or None, stream or None)
 
     def save_chunk_fifos(self, streams=None) -> np.ndarray:
         """the FIFO records of the listed streams (None: the whole batch), (n, CHUNK_REC_FLOATS) float32: pending samples, output FIFO,
         then r, M and the magic word (view as int32) -- rnnoise_batch_save_chunk_fifos.  Synchronous; the batch is unchanged."""
-        idx, n = self._snap_list(streams)
-        rec = np.empty((n, CHUNK_REC_FLOATS), np.float32)
-        if self._L.rnnoise_batch_save_chunk_fifos(self.h, _fp(rec), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
-            raise ValueError("rnnoise_batch_save_chunk_fifos failed (a stream out of range, or too many rows?)")
-        return rec
+        return self._records("rnnoise_batch_save_chunk_fifos", CHUNK_REC_FLOATS, streams)
 
     def load_chunk_fifos(self, rec: np.ndarray, streams=None):
         """row i of rec (n, CHUNK_REC_FLOATS) becomes the FIFOs of stream streams[i]: rnnoise_batch_load_chunk_fifos -- AFTER
         load_streams, which restarts them.  Synchronous.  ValueError, and nothing changes, on an out-of-range or repeated stream or
         a record with another magic word, another frame length or a fill outside [0, M)."""
-        idx, n = self._snap_list(streams)
-        rec = np.ascontiguousarray(rec, np.float32)
-        assert rec.shape == (n, CHUNK_REC_FLOATS), rec.shape
-        if self._L.rnnoise_batch_load_chunk_fifos(self.h, _fp(rec), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
-            raise ValueError("rnnoise_batch_load_chunk_fifos failed (a stream out of range or listed twice, or a bad record?)")
+        self._records("rnnoise_batch_load_chunk_fifos", CHUNK_REC_FLOATS, streams, rec)
 
     def save_chunk_fifos_device(self, d_rec: int, d_streams: int, n: int, stream: int = 0):
         """Raw device pointers (ints), asynchronous on `stream`: d_rec [n][CHUNK_REC_FLOATS] float32, d_streams [n] int32 or 0 with
         n == N.  A row whose entry is out of range gets magic word 0."""
-        if self._L.rnnoise_batch_save_chunk_fifos_device(self.h, d_rec or None, d_streams or None, n, stream or None):
-            raise RuntimeError("rnnoise_batch_save_chunk_fifos_device failed")
+        self._call("rnnoise_batch_save_chunk_fifos_device", d_rec or None, d_streams or None, n, stream or None)
 
     def load_chunk_fifos_device(self, d_rec: int, d_streams: int, n: int, stream: int = 0):
         """the inverse, asynchronous on `stream`: rows that are not records of this frame length and out-of-range entries touch nothing"""
-        if self._L.rnnoise_batch_load_chunk_fifos_device(self.h, d_rec or None, d_streams or None, n, stream or None):
-            raise RuntimeError("rnnoise_batch_load_chunk_fifos_device failed")
+        self._call("rnnoise_batch_load_chunk_fifos_device", d_rec or None, d_streams or None, n, stream or None)
 
     def chunk_fill(self) -> np.ndarray:
         """the pending input samples r_s of every stream, (N,) int32 (rnnoise_batch_chunk_fill; synchronous)"""
@@ -1022,9 +985,8 @@ class Batch:
                             n_frames: int, stream: int = 0, s16: bool = False):
         """Raw device pointers (ints), asynchronous on `stream`: d_streams [n_rows] int32; buffers of n_rows rows per frame;
         d_active [n_frames][n_rows] bytes, 0 = every listed stream present.  Out-of-range entries are absent rows."""
-        fn = self._L.rnnoise_batch_process_device_list_s16 if s16 else self._L.rnnoise_batch_process_device_list
-        if fn(self.h, d_out, d_in, d_vad or None, d_gains or None, d_streams or None, n_rows, d_active or None, n_frames, stream or None):
-            raise RuntimeError("rnnoise_batch_process_device_list failed")
+        self._call_s16("rnnoise_batch_process_device_list", s16, d_out, d_in, d_vad or None, d_gains or None, d_streams or None, n_rows,
+                       d_active or None, n_frames, stream or None)
 
     def reset_streams(self, indices):
         """the listed streams back to rnnoise_init()'s state (synchronous; ValueError on an index out of range)"""
@@ -1048,43 +1010,29 @@ class Batch:
 
     def set_stream_models(self, models):
         """the model slot of every stream: (N,) integers (synchronous; ValueError if an entry names no slot -- nothing changes then)"""
-        m = np.asarray(models).reshape(-1)
-        assert m.size == self.n
-        if m.min(initial=0) < 0 or m.max(initial=0) > 255:
-            raise ValueError("model slot out of range")
-        m = np.ascontiguousarray(m, np.uint8)
-        self._call("rnnoise_batch_set_stream_models", m.ctypes.data_as(C.POINTER(C.c_ubyte)), exc=ValueError, why=" (an entry names no slot)")
+        self._table_set(_MODELS, models)
 
     def set_stream_models_device(self, d_models: int, stream: int = 0):
         """the same from N bytes of device memory, a copy ordered on `stream` (entries naming no slot read as slot 0)"""
-        self._call("rnnoise_batch_set_stream_models_device", d_models or None, stream or None)
+        self._table_set_device(_MODELS, d_models, stream)
 
     def stream_models(self) -> np.ndarray:
         """the model slot of every stream, (N,) uint8 (synchronous)"""
-        m = np.empty(self.n, np.uint8)
-        self._call("rnnoise_batch_stream_models", m.ctypes.data_as(C.POINTER(C.c_ubyte)))
-        return m
+        return self._table_get(_MODELS)
 
     def set_stream_controls(self, ctl):
         """per-stream suppression controls (rnnoise_batch_set_stream_controls): (N, 3) float32 rows {floor, thr, hold} -- floor a
         linear gain floor in [0, 1], thr a VAD gate threshold in [0, 1] (0: no gate), hold whole frames in [0, 65535] -- or None to
         drop the table.  Synchronous; ValueError (and nothing changes) on a non-finite, out-of-range or fractional entry."""
-        if ctl is None:
-            return self._call("rnnoise_batch_set_stream_controls", None)
-        c = np.ascontiguousarray(ctl, np.float32)
-        assert c.shape == (self.n, CTL_FLOATS), c.shape
-        self._call("rnnoise_batch_set_stream_controls", _fp(c), exc=ValueError,
-                   why=" (an entry is non-finite, out of range or has a fractional hold)")
+        self._table_set(_CONTROLS, ctl)
 
     def set_stream_controls_device(self, d_ctl: int, stream: int = 0):
         """the same from N x 3 floats of device memory, a copy ordered on `stream` (the kernel maps NaN to 0, clamps, truncates hold)"""
-        self._call("rnnoise_batch_set_stream_controls_device", d_ctl or None, stream or None)
+        self._table_set_device(_CONTROLS, d_ctl, stream)
 
     def stream_controls(self) -> np.ndarray:
         """the control table, (N, 3) float32 (zeros when there is none; synchronous)"""
-        c = np.empty((self.n, CTL_FLOATS), np.float32)
-        self._call("rnnoise_batch_stream_controls", _fp(c))
-        return c
+        return self._table_get(_CONTROLS)
 
     def export_state(self, stream: int) -> np.ndarray:
         s = np.empty(STATE_FLOATS, np.float32)
@@ -1097,42 +1045,41 @@ class Batch:
         if self._L.rnnoise_batch_import_state(self.h, stream, _fp(state)):
             raise RuntimeError("import_state failed")
 
-    def _snap_list(self, streams):
-        if streams is None:
-            return None, self.n
-        idx = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
-        return idx, int(idx.size)
+    def _records(self, fn, width, streams, rec=None):
+        """save (rec None: a fresh array) or load of the (n, width) float32 records of the listed streams (None: the whole batch),
+        through the host call `fn`"""
+        idx, n = None, self.n
+        if streams is not None:
+            idx = np.ascontiguousarray(np.asarray(streams).reshape(-1), np.int32)
+            n = int(idx.size)
+        if rec is None:
+            rec, why = np.empty((n, width), np.float32), " (a stream out of range, or too many rows?)"
+        else:
+            rec, why = np.ascontiguousarray(rec, np.float32), " (a stream out of range or listed twice, or a bad record?)"
+            assert rec.shape == (n, width), rec.shape
+        self._call(fn, _fp(rec), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n, exc=ValueError, why=why)
+        return rec
 
     def save_streams(self, streams=None) -> np.ndarray:
         """complete snapshots of the listed streams (None: the whole batch, row i = stream i), (n, SNAP_FLOATS) float32:
         rnnoise_batch_save_streams.  Row i's first STATE_FLOATS words are export_state(streams[i]); then the header (view as int32)
         and the resampler history.  Synchronous; the batch is unchanged.  ValueError on an index out of range."""
-        idx, n = self._snap_list(streams)
-        snap = np.empty((n, SNAP_FLOATS), np.float32)
-        if self._L.rnnoise_batch_save_streams(self.h, _fp(snap), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
-            raise ValueError("rnnoise_batch_save_streams failed (a stream out of range, or too many rows?)")
-        return snap
+        return self._records("rnnoise_batch_save_streams", SNAP_FLOATS, streams)
 
     def load_streams(self, snap: np.ndarray, streams=None):
         """row i of snap (n, SNAP_FLOATS) becomes the state of stream streams[i] (None: the whole batch): rnnoise_batch_load_streams.
         Synchronous.  ValueError, and nothing changes, on an out-of-range or repeated stream, a record without the magic word or one
         whose analysis_mem is not the tail of its pitch_buf."""
-        idx, n = self._snap_list(streams)
-        snap = np.ascontiguousarray(snap, np.float32)
-        assert snap.shape == (n, SNAP_FLOATS), snap.shape
-        if self._L.rnnoise_batch_load_streams(self.h, _fp(snap), idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None, n):
-            raise ValueError("rnnoise_batch_load_streams failed (a stream out of range or listed twice, or a bad record?)")
+        self._records("rnnoise_batch_load_streams", SNAP_FLOATS, streams, snap)
 
     def save_streams_device(self, d_snap: int, d_streams: int, n: int, stream: int = 0):
         """Raw device pointers (ints), asynchronous on `stream`: d_snap [n][SNAP_FLOATS] float32 (16-byte aligned), d_streams [n] int32 or
         0 with n == N for the whole batch.  A row whose entry is out of range gets an empty record (magic word 0)."""
-        if self._L.rnnoise_batch_save_streams_device(self.h, d_snap or None, d_streams or None, n, stream or None):
-            raise RuntimeError("rnnoise_batch_save_streams_device failed")
+        self._call("rnnoise_batch_save_streams_device", d_snap or None, d_streams or None, n, stream or None)
 
     def load_streams_device(self, d_snap: int, d_streams: int, n: int, stream: int = 0):
         """the inverse, asynchronous on `stream`: rows without the magic word and out-of-range entries touch nothing"""
-        if self._L.rnnoise_batch_load_streams_device(self.h, d_snap or None, d_streams or None, n, stream or None):
-            raise RuntimeError("rnnoise_batch_load_streams_device failed")
+        self._call("rnnoise_batch_load_streams_device", d_snap or None, d_streams or None, n, stream or None)
 
     def debug_last(self):
         f = np.empty((self.n, NB_FEATURES), np.float32)
@@ -1304,18 +1251,16 @@ class Batch:
         """rnnoise_batch_analyze_device[_s16] on raw device pointers (ints), asynchronous on `stream`; feat_rows: None, Rows or a
         (frame_stride, row_stride) pair"""
         _keep, rows = _rows_arg(feat_rows)
-        fn = self._L.rnnoise_batch_analyze_device_s16 if s16 else self._L.rnnoise_batch_analyze_device
-        if fn(self.h, d_features or None, rows, d_silence or None, d_in or None, n_frames, stream or None):
-            raise RuntimeError("rnnoise_batch_analyze_device failed (frames pending, per-stream frame phase, overlapping rows?)")
+        self._call_s16("rnnoise_batch_analyze_device", s16, d_features or None, rows, d_silence or None, d_in or None, n_frames,
+                       stream or None, why=" (frames pending, per-stream frame phase, overlapping rows?)")
 
     def synthesize_device(self, d_out: int, d_gains: int, d_vad: int, n_frames: int, gain_rows=None, vad_rows=None, stream: int = 0,
                           s16: bool = False):
         """rnnoise_batch_synthesize_device[_s16] on raw device pointers (ints), asynchronous on `stream`"""
         _kg, grows = _rows_arg(gain_rows)
         _kv, vrows = _rows_arg(vad_rows)
-        fn = self._L.rnnoise_batch_synthesize_device_s16 if s16 else self._L.rnnoise_batch_synthesize_device
-        if fn(self.h, d_out or None, d_gains or None, grows, d_vad or None, vrows, n_frames, stream or None):
-            raise RuntimeError("rnnoise_batch_synthesize_device failed (n_frames != split_pending, overlapping rows?)")
+        self._call_s16("rnnoise_batch_synthesize_device", s16, d_out or None, d_gains or None, grows, d_vad or None, vrows, n_frames,
+                       stream or None, why=" (n_frames != split_pending, overlapping rows?)")
 
     def eval_records(self, records, t0: int = 0, n_frames: int | None = None, sums=None, gamma=None, first=None,
                      want_gains: bool = True, want_vad: bool = True, layout: str = "frame"):

@@ -33,6 +33,11 @@ def register_torch_op():
         return
     import torch
 
+    def fake_outs(pcm, F, R, dtype=torch.float32, frames=False):
+        """the outputs of a process op's fake: PCM like pcm, vad (F, R), gains (F, R, 32) and, in the chunk forms, frames (R,)"""
+        res = torch.empty_like(pcm), pcm.new_empty((F, R), dtype=dtype), pcm.new_empty((F, R, capi.NB_BANDS), dtype=dtype)
+        return res + (pcm.new_empty((R,), dtype=torch.int32),) if frames else res
+
     # (explicit schema: this module uses postponed annotations, which infer_schema cannot resolve for a local import)
     @torch.library.custom_op("rnnoise_amd::process", mutates_args=("state",),
                              schema="(Tensor pcm, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)")
@@ -43,8 +48,7 @@ def register_torch_op():
 
     @process.register_fake
     def _(pcm, state, handle):
-        T, N = pcm.shape[0], pcm.shape[1]
-        return torch.empty_like(pcm), pcm.new_empty((T, N)), pcm.new_empty((T, N, capi.NB_BANDS))
+        return fake_outs(pcm, pcm.shape[0], pcm.shape[1], pcm.dtype)
 
     # the masked form (include/rnnoise_amd.h: rnnoise_batch_process_device_masked): active (T, N) bool / uint8, nonzero = the stream
     # has this frame.  Absent rows of the returned PCM are zeros, their vad 0 and gains zeros; absent frames leave a stream's state alone.
@@ -57,8 +61,7 @@ def register_torch_op():
 
     @process_masked.register_fake
     def _(pcm, active, state, handle):
-        T, N = pcm.shape[0], pcm.shape[1]
-        return torch.empty_like(pcm), pcm.new_empty((T, N)), pcm.new_empty((T, N, capi.NB_BANDS))
+        return fake_outs(pcm, pcm.shape[0], pcm.shape[1], pcm.dtype)
 
     # the stream-list form (include/rnnoise_amd.h: rnnoise_batch_process_device_list): pcm (T, R, M), row i of every frame
     # belongs to stream idx[i] (int32 CUDA tensor); active (T, R) or None.  Only the listed streams advance; absent rows of the returned
@@ -72,8 +75,7 @@ def register_torch_op():
 
     @process_list.register_fake
     def _(pcm, idx, active, state, handle):
-        T, R = pcm.shape[0], pcm.shape[1]
-        return torch.empty_like(pcm), pcm.new_empty((T, R)), pcm.new_empty((T, R, capi.NB_BANDS))
+        return fake_outs(pcm, pcm.shape[0], pcm.shape[1], pcm.dtype)
 
     # the stream-contiguous form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_layout): pcm (N, T * (M)) float32 or int16, one
     # contiguous run of samples per stream -- the [B, T] tensor a torch user holds, read and written where it lies, no transpose.
@@ -88,8 +90,7 @@ def register_torch_op():
 
     @process_streams.register_fake
     def _(pcm, active, state, handle):
-        N, T = pcm.shape[0], pcm.shape[1] // _OPS[handle].batch.frame
-        return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
+        return fake_outs(pcm, pcm.shape[1] // _OPS[handle].batch.frame, pcm.shape[0])
 
     # the interleaved form (include/rnnoise_amd.h: rnnoise_batch_set_pcm_channels): pcm (G, T * (M), C) float32 or int16 with
     # G * C the batch's streams -- channel c of group g is stream g * C + c --, read and written where it lies, no de-interleave.
@@ -104,8 +105,7 @@ def register_torch_op():
 
     @process_channels.register_fake
     def _(pcm, active, state, handle):
-        N, T = pcm.shape[0] * pcm.shape[2], pcm.shape[1] // _OPS[handle].batch.frame
-        return torch.empty_like(pcm), pcm.new_empty((T, N), dtype=torch.float32), pcm.new_empty((T, N, capi.NB_BANDS), dtype=torch.float32)
+        return fake_outs(pcm, pcm.shape[1] // _OPS[handle].batch.frame, pcm.shape[0] * pcm.shape[2])
 
     # the chunk form (include/rnnoise_amd.h: rnnoise_batch_process_device_chunks): pcm (N, max_count) float32 or int16, stream s pushes
     # its first counts[s] samples (counts: (N,) int32 CUDA tensor, clamped into [0, max_count]) and gets as many back, one frame late.
@@ -121,9 +121,7 @@ def register_torch_op():
 
     @process_chunks.register_fake
     def _(pcm, counts, state, handle):
-        N, F = pcm.shape[0], capi.chunk_frames(_OPS[handle].batch.frame, pcm.shape[1])
-        return (torch.empty_like(pcm), pcm.new_empty((F, N), dtype=torch.float32),
-                pcm.new_empty((F, N, capi.NB_BANDS), dtype=torch.float32), pcm.new_empty((N,), dtype=torch.int32))
+        return fake_outs(pcm, capi.chunk_frames(_OPS[handle].batch.frame, pcm.shape[1]), pcm.shape[0], frames=True)
 
     # ... and on a stream list (rnnoise_batch_process_device_chunks_list): pcm (R, max_count), counts (R,) int32 and idx (R,) int32 CUDA
     # tensors, row i belonging to stream idx[i]; every result has R rows in idx's order.  The frame counter advances by F.
@@ -131,15 +129,13 @@ def register_torch_op():
                              schema="(Tensor pcm, Tensor counts, Tensor idx, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor, Tensor)")
     def process_chunks_list(pcm, counts, idx, state, handle):
         op = _OPS[handle]
-        res = op._run_chunks_list(pcm, counts, idx)
+        res = op._run_chunks(pcm, counts, idx)
         state.add_(capi.chunk_frames(op.batch.frame, pcm.shape[1]))
         return res
 
     @process_chunks_list.register_fake
     def _(pcm, counts, idx, state, handle):
-        R, F = pcm.shape[0], capi.chunk_frames(_OPS[handle].batch.frame, pcm.shape[1])
-        return (torch.empty_like(pcm), pcm.new_empty((F, R), dtype=torch.float32),
-                pcm.new_empty((F, R, capi.NB_BANDS), dtype=torch.float32), pcm.new_empty((R,), dtype=torch.int32))
+        return fake_outs(pcm, capi.chunk_frames(_OPS[handle].batch.frame, pcm.shape[1]), pcm.shape[0], frames=True)
 
     # the split calls (include/rnnoise_amd.h: rnnoise_batch_analyze_device, rnnoise_batch_synthesize_device): the DSP around a network of
     # the caller's.  analyze: pcm (T, N, M) float32 or int16 -> features (N, T, 65), the trainer's batch-first tensor, and the silence
@@ -312,68 +308,58 @@ class RNNoiseOp:
         # (freeing idx afterwards is safe: torch's allocator hands the block out again only in this stream's order)
         self.batch.reset_streams_device(idx.data_ptr(), int(idx.numel()), torch.cuda.current_stream(self.device).cuda_stream)
 
-    def save_streams(self, idx=None):
-        """complete snapshots of the listed streams (a sequence or a tensor of indices; None: the whole batch) as an (n, SNAP_FLOATS)
-        float32 CUDA tensor, on torch's current stream without a host synchronisation (rnnoise_batch_save_streams_device: a row whose
-        entry is out of range gets an empty record).  The batch is unchanged."""
+    def _records(self, call, width, idx, rec=None):
+        """save (rec None: a fresh tensor) or load of the (n, width) float32 records of the listed streams (a sequence or a tensor of
+        indices; None: the whole batch) through the device call `call`, on torch's current stream"""
         torch = self.torch
         if idx is not None:
             idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
         n = self.n if idx is None else int(idx.numel())
-        snap = torch.empty((n, capi.SNAP_FLOATS), device=self.device, dtype=torch.float32)
-        self.batch.save_streams_device(snap.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
-                                       torch.cuda.current_stream(self.device).cuda_stream)
-        return snap
+        if rec is None:
+            rec = torch.empty((n, width), device=self.device, dtype=torch.float32)
+        else:
+            assert rec.is_cuda and rec.dtype == torch.float32 and tuple(rec.shape) == (n, width)
+            rec = rec.to(self.device).contiguous()
+        # (freeing idx or a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        call(rec.data_ptr(), 0 if idx is None else idx.data_ptr(), n, torch.cuda.current_stream(self.device).cuda_stream)
+        return rec
+
+    def save_streams(self, idx=None):
+        """complete snapshots of the listed streams (a sequence or a tensor of indices; None: the whole batch) as an (n, SNAP_FLOATS)
+        float32 CUDA tensor, on torch's current stream without a host synchronisation (rnnoise_batch_save_streams_device: a row whose
+        entry is out of range gets an empty record).  The batch is unchanged."""
+        return self._records(self.batch.save_streams_device, capi.SNAP_FLOATS, idx)
 
     def load_streams(self, snap, idx=None):
         """row i of snap ((n, SNAP_FLOATS) float32 CUDA tensor) becomes the complete state of stream idx[i] (None: the whole batch), on
         torch's current stream without a host synchronisation (rnnoise_batch_load_streams_device: empty records and entries out of
         range touch nothing).  Model slots and controls are the caller's to set."""
-        torch = self.torch
-        if idx is not None:
-            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
-        n = self.n if idx is None else int(idx.numel())
-        assert snap.is_cuda and snap.dtype == torch.float32 and tuple(snap.shape) == (n, capi.SNAP_FLOATS)
-        snap = snap.to(self.device).contiguous()
-        # (freeing idx or a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
-        self.batch.load_streams_device(snap.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
-                                       torch.cuda.current_stream(self.device).cuda_stream)
+        self._records(self.batch.load_streams_device, capi.SNAP_FLOATS, idx, snap)
 
     def save_chunk_fifos(self, idx=None):
         """the FIFO records of the listed streams (None: the whole batch) as an (n, CHUNK_REC_FLOATS) float32 CUDA tensor, on torch's
         current stream without a host synchronisation (rnnoise_batch_save_chunk_fifos_device): what save_streams leaves behind of a
         stream fed through process_chunks.  The batch is unchanged."""
-        torch = self.torch
-        if idx is not None:
-            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
-        n = self.n if idx is None else int(idx.numel())
-        rec = torch.empty((n, capi.CHUNK_REC_FLOATS), device=self.device, dtype=torch.float32)
-        self.batch.save_chunk_fifos_device(rec.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
-                                           torch.cuda.current_stream(self.device).cuda_stream)
-        return rec
+        return self._records(self.batch.save_chunk_fifos_device, capi.CHUNK_REC_FLOATS, idx)
 
     def load_chunk_fifos(self, rec, idx=None):
         """row i of rec ((n, CHUNK_REC_FLOATS) float32 CUDA tensor) becomes the FIFOs of stream idx[i], on torch's current stream
         (rnnoise_batch_load_chunk_fifos_device: rows that are no records of the batch's frame length and entries out of range touch
         nothing).  Call it AFTER load_streams, which restarts the FIFOs of the streams it loads."""
+        self._records(self.batch.load_chunk_fifos_device, capi.CHUNK_REC_FLOATS, idx, rec)
+
+    def _set_table(self, call, table):
+        """an (N,) uint8 CUDA tensor as a per-stream table, through the device setter `call` on torch's current stream"""
         torch = self.torch
-        if idx is not None:
-            idx = torch.as_tensor(idx).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
-        n = self.n if idx is None else int(idx.numel())
-        assert rec.is_cuda and rec.dtype == torch.float32 and tuple(rec.shape) == (n, capi.CHUNK_REC_FLOATS)
-        rec = rec.to(self.device).contiguous()
-        # (freeing idx or a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
-        self.batch.load_chunk_fifos_device(rec.data_ptr(), 0 if idx is None else idx.data_ptr(), n,
-                                           torch.cuda.current_stream(self.device).cuda_stream)
+        assert table.is_cuda and table.dtype == torch.uint8 and table.numel() == self.n
+        table = table.to(self.device).contiguous()
+        # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
+        call(table.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_stream_models(self, slots):
         """the model slot of every stream: an (N,) uint8 CUDA tensor, copied on torch's current stream without a host synchronisation
         (rnnoise_batch_set_stream_models_device: entries naming no slot read as slot 0).  The frames of later calls run with it."""
-        torch = self.torch
-        assert slots.is_cuda and slots.dtype == torch.uint8 and slots.numel() == self.n
-        slots = slots.to(self.device).contiguous()
-        # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
-        self.batch.set_stream_models_device(slots.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        self._set_table(self.batch.set_stream_models_device, slots)
 
     def set_stream_rates(self, hz):
         """the PCM rate of every stream in Hz (include/rnnoise_amd.h: rnnoise_batch_set_stream_rates): a sequence / array of N values
@@ -387,11 +373,7 @@ class RNNoiseOp:
         rnnoise_amd.g711), copied on torch's current stream without a host synchronisation (rnnoise_batch_set_stream_formats_device: any
         other byte reads as s16).  The op's own calls are float calls and ignore the table; it serves the int16 device calls made on
         `self.batch` with tensors of this process (capi.Batch.process_device_s16 and its masked and list forms)."""
-        torch = self.torch
-        assert formats.is_cuda and formats.dtype == torch.uint8 and formats.numel() == self.n
-        formats = formats.to(self.device).contiguous()
-        # (freeing a temporary copy afterwards is safe: torch's allocator hands the block out again only in this stream's order)
-        self.batch.set_stream_formats_device(formats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        self._set_table(self.batch.set_stream_formats_device, formats)
 
     def set_stream_out_rates(self, hz):
         """the rate every stream's OUTPUT rows are written at in Hz (include/rnnoise_amd.h: rnnoise_batch_set_stream_out_rates): as
@@ -402,10 +384,7 @@ class RNNoiseOp:
     def set_stream_out_formats(self, formats):
         """the PCM format of every stream's OUTPUT rows in the batch's int16 calls: an (N,) uint8 CUDA tensor of codes, as
         set_stream_formats (rnnoise_batch_set_stream_out_formats_device), which then describes the input rows alone"""
-        torch = self.torch
-        assert formats.is_cuda and formats.dtype == torch.uint8 and formats.numel() == self.n
-        formats = formats.to(self.device).contiguous()
-        self.batch.set_stream_out_formats_device(formats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        self._set_table(self.batch.set_stream_out_formats_device, formats)
 
     def set_stream_controls(self, limit_db=None, vad_threshold=0.0, hold_frames=0):
         """per-stream suppression controls (include/rnnoise_amd.h: rnnoise_batch_set_stream_controls): an attenuation limit in dB (a
@@ -432,108 +411,73 @@ class RNNoiseOp:
         if self.batch.pcm_layout != (frame_stride, row_stride):
             self.batch.set_pcm_layout(frame_stride, row_stride)
 
+    def _launch(self, pcm, active, T, frame_stride, row_stride, channels=1):
+        """T frames of every stream from pcm, which lies as the strides say: sets that layout, allocates vad and gains and launches the
+        device call on torch's current stream -- the masked one with `active` (T, N), whose absent rows of out are zeros"""
+        torch = self.torch
+        pcm = pcm.contiguous()  # (a [B, T] or [B, T, C] tensor as torch makes it is: no copy)
+        self._layout(frame_stride, row_stride, channels)
+        s16 = pcm.dtype == torch.int16
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
+        gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        if active is None:
+            out = torch.empty_like(pcm)
+            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream, s16=s16)
+        else:
+            assert active.is_cuda and active.shape == (T, self.n)
+            act = (active != 0).to(torch.uint8).contiguous()
+            out = torch.zeros_like(pcm)
+            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream,
+                                             s16=s16)
+        return out, vad, gains
+
     def _run_channels(self, pcm, active=None):
         torch = self.torch
         M = self.batch.frame
         assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 3
         G, C = pcm.shape[0], pcm.shape[2]
         assert G * C == self.n and 1 <= C <= capi.MAX_CHANNELS and pcm.shape[1] % M == 0 and pcm.shape[1] > 0
-        pcm = pcm.contiguous()  # (a [B, T, C] tensor as torch makes it is: no copy)
         T = pcm.shape[1] // M
-        s16 = pcm.dtype == torch.int16
-        self._layout(M * C, T * M * C, C)
-        stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
-        gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
-        if active is None:
-            out = torch.empty_like(pcm)
-            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream, s16=s16)
-        else:
-            assert active.is_cuda and active.shape == (T, self.n)
-            act = (active != 0).to(torch.uint8).contiguous()
-            out = torch.zeros_like(pcm)
-            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream,
-                                             s16=s16)
-        return out, vad, gains
+        return self._launch(pcm, active, T, M * C, T * M * C, C)
 
     def _run_streams(self, pcm, active=None):
         torch = self.torch
         M = self.batch.frame
         assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2
         assert pcm.shape[0] == self.n and pcm.shape[1] % M == 0 and pcm.shape[1] > 0
-        pcm = pcm.contiguous()  # (a [B, T] tensor as torch makes it is: no copy)
         T = pcm.shape[1] // M
-        s16 = pcm.dtype == torch.int16
-        self._layout(M, T * M)
-        stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
-        gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
-        if active is None:
-            out = torch.empty_like(pcm)
-            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream, s16=s16)
-        else:
-            assert active.is_cuda and active.shape == (T, self.n)
-            act = (active != 0).to(torch.uint8).contiguous()
-            out = torch.zeros_like(pcm)
-            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream,
-                                             s16=s16)
-        return out, vad, gains
+        return self._launch(pcm, active, T, M, T * M)
 
     def _run(self, pcm, active=None):
-        torch = self.torch
-        assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[1:] == (self.n, self.batch.frame)
-        self._layout(0, 0)
-        pcm = pcm.contiguous()
-        T = pcm.shape[0]
-        stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        vad = torch.empty((T, self.n), device=pcm.device, dtype=torch.float32)
-        gains = torch.empty((T, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
-        if active is None:
-            out = torch.empty_like(pcm)
-            self.batch.process_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), T, stream)
-        else:
-            assert active.is_cuda and active.shape == (T, self.n)
-            act = (active != 0).to(torch.uint8).contiguous()
-            out = torch.zeros_like(pcm)
-            self.batch.process_masked_device(out.data_ptr(), pcm.data_ptr(), vad.data_ptr(), gains.data_ptr(), act.data_ptr(), T, stream)
-        return out, vad, gains
+        assert pcm.is_cuda and pcm.dtype == self.torch.float32 and pcm.shape[1:] == (self.n, self.batch.frame)
+        return self._launch(pcm, active, pcm.shape[0], 0, 0)
 
-    def _run_chunks(self, pcm, counts):
+    def _run_chunks(self, pcm, counts, idx=None):
+        """the chunk op, and with idx (R,) its list form, whose R rows belong to the listed streams"""
         torch = self.torch
-        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2 and pcm.shape[0] == self.n
-        assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == self.n
-        self._layout(0, 0)
-        pcm, counts = pcm.contiguous(), counts.contiguous()
-        F = capi.chunk_frames(self.batch.frame, pcm.shape[1])
-        stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        vad = torch.empty((F, self.n), device=pcm.device, dtype=torch.float32)
-        gains = torch.empty((F, self.n, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
-        frames = torch.zeros((self.n,), device=pcm.device, dtype=torch.int32)
-        out = torch.zeros_like(pcm)
-        if pcm.shape[1] == 0:  # (nothing to push: the library's no-op, and an empty tensor has no address to hand it)
-            return out, vad, gains, frames
-        self.batch.process_chunks_device(out.data_ptr(), pcm.data_ptr(), counts.data_ptr(), pcm.shape[1], vad.data_ptr(), gains.data_ptr(),
-                                         frames.data_ptr(), stream, s16=pcm.dtype == torch.int16)
-        return out, vad, gains, frames
-
-    def _run_chunks_list(self, pcm, counts, idx):
-        torch = self.torch
-        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2 and pcm.shape[0] <= self.n
+        assert pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.dim() == 2
         R = pcm.shape[0]
+        assert R == self.n if idx is None else R <= self.n
         assert counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == R
-        assert idx.is_cuda and idx.dtype == torch.int32 and idx.numel() == R
+        assert idx is None or (idx.is_cuda and idx.dtype == torch.int32 and idx.numel() == R)
         self._layout(0, 0)
-        pcm, counts, idx = pcm.contiguous(), counts.contiguous(), idx.contiguous()
+        pcm, counts, idx = pcm.contiguous(), counts.contiguous(), None if idx is None else idx.contiguous()
         F = capi.chunk_frames(self.batch.frame, pcm.shape[1])
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        vad = torch.zeros((F, R), device=pcm.device, dtype=torch.float32)
-        gains = torch.zeros((F, R, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
+        new = torch.empty if idx is None else torch.zeros  # (the list form hands out zeroed vad and gains)
+        vad = new((F, R), device=pcm.device, dtype=torch.float32)
+        gains = new((F, R, capi.NB_BANDS), device=pcm.device, dtype=torch.float32)
         frames = torch.zeros((R,), device=pcm.device, dtype=torch.int32)
         out = torch.zeros_like(pcm)
         if pcm.shape[1] == 0 or R == 0:  # (nothing to push: the library's no-op, and an empty tensor has no address to hand it)
             return out, vad, gains, frames
-        self.batch.process_chunks_list_device(out.data_ptr(), pcm.data_ptr(), counts.data_ptr(), pcm.shape[1], idx.data_ptr(), R,
-                                              vad.data_ptr(), gains.data_ptr(), frames.data_ptr(), stream, s16=pcm.dtype == torch.int16)
+        args = out.data_ptr(), pcm.data_ptr(), counts.data_ptr(), pcm.shape[1]
+        rest = vad.data_ptr(), gains.data_ptr(), frames.data_ptr(), stream
+        if idx is None:
+            self.batch.process_chunks_device(*args, *rest, s16=pcm.dtype == torch.int16)
+        else:
+            self.batch.process_chunks_list_device(*args, idx.data_ptr(), R, *rest, s16=pcm.dtype == torch.int16)
         return out, vad, gains, frames
 
     def _run_list(self, pcm, idx, active=None):

@@ -20,12 +20,16 @@ from rnnoise_amd import capi
 HAVE_GPU = capi.lib().rnnoise_amd_device_count() > 0 if os.path.exists(capi.LIB_PATH) else False
 
 
+def _declarations(header):
+    """(return type, name, parameters) of every RNNOISE_EXPORT prototype of a header, comments stripped"""
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    return [(" ".join(ret.split()), name, " ".join(params.split()))
+            for ret, name, params in re.findall(r"RNNOISE_EXPORT\s+([\w\s\*]+?)\b(rnnoise_\w+)\s*\(([^()]*)\)\s*;", src)]
+
+
 def declared_symbols():
-    names = []
-    for h in ("rnnoise.h", "rnnoise_amd.h"):
-        src = open(os.path.join(ROOT, "include", h)).read()
-        names += re.findall(r"RNNOISE_EXPORT\s+[\w\s\*]+?\b(rnnoise_\w+)\s*\(", src)
-    return names
+    return [name for h in ("rnnoise.h", "rnnoise_amd.h") for _ret, name, _params in _declarations(h)]
 
 
 def test_library_exports_every_declared_symbol():
@@ -48,13 +52,38 @@ def test_product_library_exports_the_api_and_nothing_else():
         nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True).stdout
         syms = {l.split()[-1] for l in nm.splitlines() if l.strip()}
         assert syms == decl, (so, sorted(syms ^ decl))
-    dbg = re.findall(r"RNNOISE_EXPORT\s+[\w\s\*]+?\b(rnnoise_\w+)\s*\(", open(os.path.join(ROOT, "include", "rnnoise_amd_debug.h")).read())
+    dbg = [name for _ret, name, _params in _declarations("rnnoise_amd_debug.h")]
     assert sorted(dbg) == sorted(capi.DEBUG_EXPORTS)
     nm = subprocess.run(["nm", "-D", "--defined-only", capi.INSTR_LIB_PATH], capture_output=True, text=True).stdout
     for n in list(decl) + dbg:
         assert re.search(rf"\bT {n}\b", nm), f"{n} missing from the instrumented library"
     # no tap code in the product kernels: the instrumented image is the bigger one
     assert os.path.getsize(capi.INSTR_LIB_PATH) > os.path.getsize(capi.LIB_PATH)
+
+
+def test_prototype_tables_match_the_headers():
+    """capi.PROTOTYPES / DEBUG_PROTOTYPES against every declaration of the three headers, in their order: as many argtypes as the
+    C prototype has parameters, and the restype of its return type's class -- no library needed"""
+    api = _declarations("rnnoise.h") + _declarations("rnnoise_amd.h")
+    dbg = _declarations("rnnoise_amd_debug.h")
+    assert [d[1] for d in api] == list(capi.PROTOTYPES) == capi.EXPORTS and len(api) == 120
+    assert [d[1] for d in dbg] == list(capi.DEBUG_PROTOTYPES) == capi.DEBUG_EXPORTS and len(dbg) == 6
+    other = 0
+    for table, decls in ((capi.PROTOTYPES, api), (capi.DEBUG_PROTOTYPES, dbg)):
+        for ret, name, params in decls:
+            restype, argtypes = table[name]
+            # (a parameter list with a parenthesis in it would not have matched: commas separate parameters)
+            assert len(argtypes) == (0 if params in ("", "void") else params.count(",") + 1), (name, params, argtypes)
+            if ret == "int":
+                assert restype is C.c_int, name
+            elif ret == "void":
+                assert restype in (C.c_int, None), name  # (the default, or nothing at all)
+            else:
+                want = {"float": C.c_float, "long": C.c_long, "long long": C.c_longlong, "const char *": C.c_char_p}
+                assert ret in want or ret.endswith("*"), (name, ret)
+                assert restype is want.get(ret, C.c_void_p), (name, ret, restype)
+                other += 1
+    assert other == 12
 
 
 def test_frame_geometry_and_state_size():

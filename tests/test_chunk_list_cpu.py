@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT
 from rnnoise_amd import capi
 
@@ -58,10 +59,7 @@ def test_the_record_bodies(exe, lanes, M):
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    src = declared_once(NEW)
     assert re.search(r"#define\s+RNNOISE_AMD_CHUNK_REC_FLOATS\s+964\b", src)
     magic = re.search(r"#define\s+RNNOISE_AMD_CHUNK_MAGIC\s+(0x[0-9a-fA-F]+)", src)
     assert magic and int(magic.group(1), 16) == capi.CHUNK_MAGIC != capi.SNAP_MAGIC
@@ -70,9 +68,7 @@ def test_prototypes_declared_once_each_with_export():
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0"])
 def test_both_product_libraries_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_a_null_batch_returns_minus_one_without_a_gpu():

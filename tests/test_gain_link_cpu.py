@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT, assert_bits_equal, load_blob
 from ctl_oracle import CtlOracle
 from link_oracle import C_NONE, LinkGroup, fold
@@ -19,17 +20,12 @@ NEW = ["rnnoise_batch_set_gain_link", "rnnoise_batch_gain_link"]
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    declared_once(NEW)
 
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0", "librnnoise_amd_instr.so"])
 def test_libraries_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_bindings():

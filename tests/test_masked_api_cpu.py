@@ -1,13 +1,10 @@
 """CPU checks of the masked-call / per-stream reset API (include/rnnoise_amd.h): declared, exported by both product libraries,
 bound by ctypes and by the torch custom op, and argument errors refused without touching a GPU."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
+from abi_contract import declared_once, exported
 from rnnoise_amd import capi
 
 NEW = ["rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_masked_s16", "rnnoise_batch_process_masked",
@@ -15,17 +12,12 @@ NEW = ["rnnoise_batch_process_device_masked", "rnnoise_batch_process_device_mask
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    declared_once(NEW)
 
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0"])
 def test_both_product_libraries_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_ctypes_bindings():
@@ -74,3 +66,25 @@ def test_torch_op_schema_and_fake():
         assert out.shape == (3, 5, 480) and vad.shape == (3, 5) and gains.shape == (3, 5, 32)
     for m in ("process_masked", "reset_streams"):
         assert callable(getattr(torch_op.RNNoiseOp, m)), m
+
+
+# the registered ops as a caller's traces and exported graphs name them: name -> schema
+SCHEMAS = {
+    "process": "(Tensor pcm, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)",
+    "process_masked": "(Tensor pcm, Tensor active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)",
+    "process_list": "(Tensor pcm, Tensor idx, Tensor? active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)",
+    "process_streams": "(Tensor pcm, Tensor? active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)",
+    "process_channels": "(Tensor pcm, Tensor? active, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor)",
+    "process_chunks": "(Tensor pcm, Tensor counts, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor, Tensor)",
+    "process_chunks_list": "(Tensor pcm, Tensor counts, Tensor idx, Tensor(a!) state, int handle) -> (Tensor, Tensor, Tensor, Tensor)",
+    "analyze": "(Tensor pcm, Tensor(a!) state, int handle) -> (Tensor, Tensor)",
+    "synthesize": "(Tensor gains, Tensor vad, Tensor like, Tensor(a!) state, int handle) -> Tensor",
+}
+
+
+def test_torch_op_schemas_are_pinned():
+    torch = pytest.importorskip("torch")
+    from rnnoise_amd import torch_op
+    torch_op.register_torch_op()
+    for name, schema in SCHEMAS.items():
+        assert str(getattr(torch.ops.rnnoise_amd, name).default._schema) == f"rnnoise_amd::{name}{schema}", name

@@ -3,10 +3,10 @@ exported, bound by ctypes, the capi and torch wrappers present, and argument err
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT
 from rnnoise_amd import capi
 
@@ -16,10 +16,7 @@ HEADER = os.path.join(ROOT, "include", "rnnoise_amd.h")
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(HEADER).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    declared_once(NEW)
 
 
 def test_max_models_is_eight():
@@ -31,9 +28,7 @@ def test_max_models_is_eight():
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0"])
 def test_the_product_libraries_export_them(so):
     # (both: the two product libraries export the same declared set -- tests/test_capi_cpu.py holds them to it)
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_ctypes_bindings():

@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT
 from rnnoise_amd import capi
 
@@ -16,18 +17,13 @@ NEW = ["rnnoise_batch_set_pcm_channels", "rnnoise_batch_pcm_channels", "rnnoise_
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    src = declared_once(NEW)
     assert re.search(r"#define\s+RNNOISE_AMD_MAX_CHANNELS\s+8\b", src) and capi.MAX_CHANNELS == 8
 
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0", "librnnoise_amd_instr.so"])
 def test_libraries_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_ctypes_and_torch_bindings():

@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT
 from rnnoise_amd import capi
 
@@ -16,19 +17,13 @@ NEW = ["rnnoise_batch_set_pcm_layout", "rnnoise_batch_pcm_layout", "rnnoise_amd_
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    declared_once(NEW)
 
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0", "librnnoise_amd_instr.so"])
 def test_libraries_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    names = exported(so, NEW)
     if so != "librnnoise_amd_instr.so":  # the product exports the C API and nothing else: no helper of the layout leaks out
-        names = [line.split()[-1] for line in nm.splitlines() if line.strip()]
         assert names and all(x.startswith("rnnoise_") for x in names), [x for x in names if not x.startswith("rnnoise_")][:5]
         assert not [x for x in names if "layout" in x and x not in NEW]
 

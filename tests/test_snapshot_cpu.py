@@ -5,10 +5,10 @@ a GPU; and the two state kernels still the only ones in their source file, with 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT
 from rnnoise_amd import capi
 
@@ -17,18 +17,13 @@ NEW = ["rnnoise_batch_save_streams_device", "rnnoise_batch_load_streams_device",
 
 
 def test_prototypes_declared_once_each_with_export():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    src = declared_once(NEW)
     assert re.search(r"#define\s+RNNOISE_AMD_SNAP_FLOATS\s+RN_SNAP_FLOATS\b", src)
 
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0", "librnnoise_amd_instr.so"])
 def test_the_product_libraries_and_the_instrumented_one_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_ctypes_capi_and_torch_bindings():

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT, assert_bits_equal, golden, load_blob
 from ctl_oracle import C_NONE, CtlOracle
 from oracle.binding import Oracle
@@ -135,10 +136,7 @@ def test_nan_controls_read_as_zero(blob):
 
 # ---- surface ----
 def test_prototypes_declared_once_each_with_export():
-    src = open(HEADER).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    src = declared_once(NEW)
     assert re.search(r"^#define RNNOISE_AMD_CTL_FLOATS 3$", src, re.M)
     assert capi.CTL_FLOATS == 3
     # the drop-in header has no controls
@@ -147,9 +145,7 @@ def test_prototypes_declared_once_each_with_export():
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0"])
 def test_the_product_libraries_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 def test_ctypes_bindings():

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_contract import declared_once, exported
 from conftest import ROOT
 from rnnoise_amd import capi
 
@@ -18,10 +19,7 @@ NEW = ["rnnoise_batch_set_stream_formats", "rnnoise_batch_set_stream_formats_dev
 
 
 def test_prototypes_and_codes_declared_once_each():
-    src = open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
-    for n in NEW:
-        assert len(re.findall(rf"RNNOISE_EXPORT\s+int\s+{n}\s*\(", src)) == 1, n
-        assert n in capi.EXPORTS, n
+    src = declared_once(NEW)
     for name, v in (("LINEAR", 0), ("ULAW", 1), ("ALAW", 2)):
         assert len(re.findall(rf"#define\s+RNNOISE_AMD_PCM_{name}\s+{v}\b", src)) == 1, name
     from rnnoise_amd import g711
@@ -33,9 +31,7 @@ def test_prototypes_and_codes_declared_once_each():
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0", "librnnoise_amd_instr.so"])
 def test_the_product_libraries_and_the_instrumented_one_export_them(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "rnnoise_amd", so)], capture_output=True, text=True).stdout
-    for n in NEW:
-        assert re.search(rf"\bT {n}\b", nm), (so, n)
+    exported(so, NEW)
 
 
 @pytest.mark.parametrize("so", ["librnnoise_amd.so", "librnnoise.so.0"])
