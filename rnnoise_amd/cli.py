@@ -46,6 +46,13 @@ first, as the trainer does it; --pack: the GPU-native RNPK form).  eval-records 
 blobs with the same scoring code, and prints every blob's difference to it and the 32 per-band means of the gain loss of each.
 denoise --checkpoint runs the float network between the split calls, as --torch-net runs a TorchScript file; without --model the DSP's
 batch is built on the blob exported from that checkpoint.
+
+What a blob, a checkpoint or a TorchScript net does to the AUDIO (rnnoise_amd/evaluate.py: evaluate_audio): COUNT
+training sequences are generated on the device as dump-features generates them, denoised, and scored against their clean signals by
+librnnoise_amd_score.so -- a table of SNR, SI-SDR and segmental SNR in dB per model, and every later model's difference to the first:
+
+  python -m rnnoise_amd.cli eval-audio speech.pcm noise.pcm fgnoise.pcm --model a.blob [--model b.blob] [--checkpoint ckpt.pth]
+         [--torch-net net.pt] --count N [--frames T] [--rir-list FILE] [--seed S] [--streams N]
 """
 from __future__ import annotations
 
@@ -285,6 +292,66 @@ def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out:
     return count * seq_frames
 
 
+AUDIO_COLUMNS = (("snr_in", "SNR in"), ("snr_out", "SNR out"), ("snr_gain", "gain"), ("si_sdr_in", "SI-SDR in"),
+                 ("si_sdr_out", "SI-SDR out"), ("si_sdr_gain", "gain"), ("seg_snr_in", "segSNR in"), ("seg_snr_out", "segSNR out"))
+
+
+def audio_table(names, results) -> str:
+    """the table of eval-audio: one row per model with the means over its sequences in dB (audio_score.summary's keys), the
+    sequences scored and left out (zero clean energy); then, for every model after the first, a row of differences to the first"""
+    width = max([len("model")] + [len(n) + 2 for n in names])
+    cell = lambda v: f"{v:>10.3f}"
+    lines = [f"{'model':<{width}} {'seqs':>6} {'left out':>8} " + " ".join(f"{title:>10}" for _key, title in AUDIO_COLUMNS)]
+    for n, r in zip(names, results):
+        lines.append(f"{n:<{width}} {r['sequences']:>6d} {r['excluded']:>8d} " + " ".join(cell(r[k]) for k, _ in AUDIO_COLUMNS))
+    for n, r in zip(names[1:], results[1:]):
+        with np.errstate(invalid="ignore"):  # (inf - inf where both outputs are exact: nan)
+            diff = [np.float64(r[k]) - np.float64(results[0][k]) for k, _ in AUDIO_COLUMNS]
+        lines.append(f"{'d ' + n:<{width}} {'':>6} {'':>8} " + " ".join(cell(v) for v in diff))
+    return "\n".join(lines)
+
+
+def eval_audio_files(speech: str, noise: str, fgnoise: str, models, count: int, frames: int = 2000, checkpoint=None, torch_net=None,
+                     rir_list=None, seed=None, streams: int = 64, device: int = 0, rir_work_mb: int = 256):
+    """eval-audio: `count` sequences of `frames` frames drawn as dump_features draws them (the same generator and seed give the
+    same sequences), through every blob of `models` (paths) and the float networks named -> (names, evaluate.evaluate_audio's
+    results).  Without a blob the DSP runs on the blob the checkpoint exports to."""
+    import torch
+
+    from . import evaluate, train_data
+    dev = torch.device("cuda", device)
+    corpora = [torch.from_numpy(np.fromfile(p, dtype=np.int16)).to(dev) for p in (speech, noise, fgnoise)]
+    rng = np.random.default_rng(seed)
+    draws = train_data.draw(rng, count, [c.numel() for c in corpora], frames)
+    blobs = [open(m, "rb").read() for m in models]
+    names, nets, net_blob = list(models), [], blobs[0] if blobs else None
+    if checkpoint is not None:
+        from . import export, float_net
+        nets.append(float_net.load_checkpoint(checkpoint, device=f"cuda:{device}"))
+        names.append(checkpoint)
+        if net_blob is None:
+            net_blob = export.blob_from_state_dict(export.load_state_dict_file(checkpoint))
+    if torch_net is not None:
+        nets.append(torch.jit.load(torch_net, map_location=f"cuda:{device}").eval())
+        names.append(torch_net)
+    if net_blob is None:
+        raise ValueError("eval-audio: --torch-net needs a --model or a --checkpoint for the DSP's batch")
+    rirs = None
+    if rir_list:
+        with open(rir_list) as f:
+            rir_names = [line.rstrip("\n") for line in f if line.rstrip("\n")]
+        responses = [np.fromfile(name, dtype=np.float32, count=capi.RIR_MAX) for name in rir_names]
+        model = capi.Model(net_blob)
+        loader = capi.Batch(model, 1, device=device)
+        with torch.cuda.device(dev):
+            rirs = (train_data.rir_spectra(loader, responses, dev), train_data.draw_rir(rng, count, len(responses)))
+        loader.close()
+        model.close()
+    res = evaluate.evaluate_audio(corpora, blobs, draws, frames, rirs=rirs, nets=nets, net_blob=net_blob, streams=streams,
+                                  device=device, rir_work_bytes=rir_work_mb << 20)
+    return names, res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -348,7 +415,30 @@ def main(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--max-streams", type=int, default=65536, help="sequences per slab: the batch size")
     p.add_argument("file", help="float32 records of 98 floats, sequence after sequence (dump-features' output)")
+    p = sub.add_parser("eval-audio")
+    p.add_argument("--model", default=None, action="append", help='"DNNw" weight blob; repeat to score several on the same sequences')
+    p.add_argument("--checkpoint", default=None, help="trainer checkpoint (.pth): its float network between the split calls")
+    p.add_argument("--torch-net", default=None, help="TorchScript module [N,T,65] -> ([N,T,32], [N,T,1]) between the split calls")
+    p.add_argument("--count", type=int, required=True, help="sequences to generate and score")
+    p.add_argument("--frames", type=int, default=2000, help="frames per sequence (the trainer: 2000)")
+    p.add_argument("--rir-list", default=None, help="file of RIR file names, one per line (raw float32): the reference's -rir_list")
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--streams", type=int, default=64, help="sequences per round: the batch size (the numbers do not depend on it)")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("speech")
+    p.add_argument("noise")
+    p.add_argument("fgnoise")
     a = ap.parse_args(argv)
+    if a.cmd == "eval-audio":
+        if not a.model and a.checkpoint is None and a.torch_net is None:
+            ap.error("eval-audio: --model, --checkpoint or --torch-net")
+        if a.count < 1 or a.frames < 3:
+            ap.error("eval-audio: --count at least 1, --frames at least 3 (the first two output frames are not scored)")
+        names, res = eval_audio_files(a.speech, a.noise, a.fgnoise, a.model or [], a.count, a.frames, a.checkpoint, a.torch_net,
+                                      a.rir_list, a.seed, a.streams, a.device)
+        print(f"eval-audio: {a.count} sequences of {a.frames} frames, seed {a.seed}, delay 960 samples, first scored frame 2")
+        print(audio_table(names, res))
+        return
     if a.cmd == "export":
         from . import export
         n = export.export_file(a.checkpoint, a.out, a.densities, a.pack)

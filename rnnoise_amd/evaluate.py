@@ -8,6 +8,13 @@ checkpoint.  Nothing is trained here.
 evaluate_checkpoint scores the float checkpoint itself on the same file -- rnnoise_amd.float_net's forward_sequence in torch, its
 outputs scored by rnnoise_batch_score_records_device, the scoring half of the record step -- so that the difference between a blob's
 loss and its checkpoint's is what quantisation and sparsification cost, not what two pieces of loss code differ by.
+
+evaluate_audio measures the AUDIO instead: the sequences the trainer would have seen are generated on the device
+(train_data.mix_rounds), denoised where they lie -- by a blob's batch, or by a float network between the split calls -- and scored
+against the clean signal by librnnoise_amd_score.so (rnnoise_amd/audio_score.py): SNR, SI-SDR and segmental SNR in dB, which see the
+pitch filter, the gain smoothing and the overlap-add that the trainer's loss does not.
+
+  python -m rnnoise_amd.cli eval-audio speech.pcm noise.pcm fgnoise.pcm --model weights_blob.bin [--checkpoint ckpt.pth] --count N
 """
 from __future__ import annotations
 
@@ -153,3 +160,88 @@ def evaluate_checkpoint(path_or_array, checkpoint, sequence_length: int = 2000, 
     batch.close()
     model.close()
     return _means(sums, bands)
+
+
+def evaluate_audio(corpora, models, draws, n_frames: int, rirs=None, nets=(), net_blob=None, streams: int = 64, device: int = 0,
+                   vad: str = "auto", first: int = 2, delay: int = None, rir_work_bytes: int = 256 << 20, tap=None):
+    """Denoises the sequences of `draws` (train_data.draw) and scores the result against their clean signals, on the device.
+    corpora: (speech, noise, fgnoise), 1-D int16 torch tensors on cuda:`device`.  models: blobs (bytes) or capi.Model objects, each
+    run by a batch of `streams` streams; nets: torch modules mapping features (N, T, 65) to (gains (N, T, 32), vad (N, T, 1)) -- a
+    float_net.FloatNet, a TorchScript file's module --, each run by RNNoiseOp.denoise_with on the DSP of net_blob (default: the
+    first model's blob).  All of them see the same planes in one pass over the rounds of train_data.mix_rounds: per round and
+    denoiser the state is reset (rnnoise_batch_reset; a net's reset()), the round's `noisy` plane is denoised, and
+    rnnoise_amd_audio_score_device adds the round's sums with first frame `first` and delay `delay` (audio_score.DELAY) where the
+    three planes lie.  Every sequence starts from the zero state, so its numbers depend neither on `streams` nor on its position.
+    The first model's batch also runs the mixing calls: they touch no denoiser state (train_data.mix_rounds).
+    tap: a function called as tap(first_sequence, k, clean, noisy, outs) after each round with the device tensors, outs one
+    (n_frames, N, 480) plane per denoiser -- valid during the call.
+    -> one dict per denoiser, models first: audio_score.summary's means (snr_in, snr_out, snr_gain, si_sdr_in, si_sdr_out,
+    si_sdr_gain, seg_snr_in, seg_snr_out, sequences, excluded), sums (S, 8), frame_terms (S, n_frames, 8), active (S, n_frames) --
+    vad_target moved to the output frames -- and per_sequence, audio_score.metrics' dict."""
+    import torch
+
+    from . import audio_score, train_data
+    from .torch_op import RNNoiseOp
+    delay = audio_score.DELAY if delay is None else delay
+    if not models and not nets:
+        raise ValueError("nothing to evaluate: no model and no net")
+    S, T = len(draws.mix), n_frames
+    N = max(1, min(streams, S))
+    dev = torch.device("cuda", device)
+    handles = [m if isinstance(m, capi.Model) else capi.Model(m) for m in models]
+    ops = []
+    if nets:
+        dsp = net_blob if net_blob is not None else next((m for m in models if isinstance(m, (bytes, bytearray))), None)
+        if dsp is None:
+            raise ValueError("nets need net_blob, the blob of the DSP's batch")
+        ops = [RNNoiseOp(dsp, N, device=device) for _ in nets]
+    D = len(handles) + len(ops)
+    sums = [np.zeros((S, audio_score.SLOTS), np.float64) for _ in range(D)]
+    terms = [np.zeros((S, T, audio_score.SLOTS), np.float64) for _ in range(D)]
+    active = np.zeros((S, T), np.float32)
+    shift = (delay + audio_score.FRAME // 2) // audio_score.FRAME  # frames by which the output lags the input
+    fs, rs = audio_score.layout_frames(N)
+    with torch.cuda.device(dev):
+        batches = [capi.Batch(m, N, device=device) for m in handles]
+        gen = batches[0] if batches else ops[0].batch
+        st = torch.cuda.current_stream(dev)
+        outs = [torch.empty((T, N, audio_score.FRAME), dtype=torch.float32, device=dev) for _ in handles]
+        d_sums = torch.empty((N, audio_score.SLOTS), dtype=torch.float64, device=dev)
+        d_terms = torch.empty((N, T, audio_score.SLOTS), dtype=torch.float64, device=dev)
+        s0 = 0
+        for k, clean, noisy, vad_target in train_data.mix_rounds(gen, *corpora, draws, T, rirs, vad, rir_work_bytes):
+            planes = []
+            for b, out in zip(batches, outs):
+                st.synchronize()  # (the reset below is not ordered with torch's stream: the round's planes are complete first)
+                b.reset()
+                b.process_device(out.data_ptr(), noisy.data_ptr(), 0, 0, T, st.cuda_stream)
+                planes.append(out)
+            for op, net in zip(ops, nets):
+                st.synchronize()
+                op.reset()
+                if hasattr(net, "reset"):
+                    net.reset()
+                planes.append(op.denoise_with(net, noisy).contiguous())
+            for i, out in enumerate(planes):
+                d_sums.zero_()
+                d_terms.zero_()
+                audio_score.score_device(d_sums.data_ptr(), (clean.data_ptr(), fs, rs), (noisy.data_ptr(), fs, rs),
+                                         (out.data_ptr(), out.stride(0), out.stride(1)), k, 0, T, first, delay,
+                                         d_terms.data_ptr(), T, device, st.cuda_stream)
+                sums[i][s0:s0 + k], terms[i][s0:s0 + k] = d_sums[:k].cpu().numpy(), d_terms[:k].cpu().numpy()  # (waits for the stream)
+            active[s0:s0 + k, shift:] = vad_target[:T - shift, :k].t().cpu().numpy() if shift < T else 0
+            if tap is not None:
+                tap(s0, k, clean, noisy, planes)
+            s0 += k
+        for b in batches:
+            b.close()
+        for op in ops:
+            op.close()
+    for m, h in zip(models, handles):
+        if not isinstance(m, capi.Model):
+            h.close()
+    res = []
+    for i in range(D):
+        per = audio_score.metrics(sums[i], terms[i], active)
+        res.append(dict(**audio_score.summary(per), sums=sums[i], frame_terms=terms[i], active=active, per_sequence=per))
+    return res

@@ -13,6 +13,9 @@ For the same draws the records are bit for bit the reference's.  Its optional RI
 rir_spectra() transforms a list of room impulse responses once, draw_rir() makes the choices of dump_features.c:449-450, and
 generate(..., rirs=(spectra, records)) filters between mix and clip.  draw() and draw_rir() follow the reference's distributions, not
 glibc's rand() stream.
+
+mix_rounds() stops in front of the features call and yields the audio itself -- clean, noisy and the VAD target of every round, on the
+device -- for rnnoise_amd.evaluate.evaluate_audio, which denoises the noisy plane and scores the result against the clean one.
 """
 from __future__ import annotations
 
@@ -148,23 +151,10 @@ def _pad(a, n):
     return a if len(a) == n else np.concatenate([a, np.repeat(a[-1:], n - len(a), 0)])
 
 
-def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20,
-                    vad: str = "auto"):
-    """Yields the records of sequences [r * N, (r + 1) * N) of `draws`, r = 0, 1, ..., each a (sequences, n_frames, 98) float32 array:
-    sequence i runs on stream i % N of `batch` (N streams) in round i // N, and the batch's per-stream analysis state carries from one
-    sequence of a stream to the next, as the reference's two DenoiseStates carry across its loop.  speech, noise, fgnoise: the corpora
-    as 1-D int16 torch tensors on the batch's device.  Everything is enqueued on torch's current stream.  vad: where the Viterbi VAD of the
-    frame energies runs -- "device": in the levels launch, a round then copies nothing back and does not synchronise between its
-    kernels (RuntimeError on a host whose libm the device does not restate, capi.train_vad_device_available()); "host": the energies
-    go to the host, rnnoise_amd_train_vad decodes them on one thread, the bytes go back; "auto" (the default): "device" where
-    available, else "host".  The records are the same to the byte.  When the last round is partial, the streams behind the last sequence run that
-    sequence again (records dropped), so their analysis state advances too: a later call on the same batch starts those streams from
-    a state that no sequence of the file order left.  Reset the batch, or use a sequence count that is a multiple of N, where that
-    matters; one run of the command line is not affected.
-    rirs = (spectra, records): the tensor of rir_spectra() and draw_rir()'s records, one per sequence of `draws`.  The mix then runs
-    without clipping and quantisation, and the RIR call filters the sequences the records name and applies the flags of `draws` to
-    all (dump_features.c:449-465), in a workspace of rir_work_bytes (at least capi.train_rir_work_bytes(1)).  Without rirs nothing
-    changes."""
+def _mix_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs, rir_work_bytes: int, vad: str):
+    """the front of a round, shared by generate_rounds and mix_rounds: levels (+ VAD) -> mix [-> RIR] for sequences [r * N, (r + 1) * N)
+    of `draws`, r = 0, 1, ...  Yields (first, k, clean, noisy, vad_target, noise_free, stream): the round's first sequence, how many
+    of its N streams carry one, the device tensors the calls filled -- reused by the next round -- and the stream they ran on."""
     import torch
     if vad not in ("auto", "device", "host"):
         raise ValueError(f"vad={vad!r}: auto | device | host")
@@ -179,7 +169,6 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
     energy, rms = new((N, n_frames)), new((N, 3))
     clean, noisy = new((n_frames, N, FRAME)), new((n_frames, N, FRAME))
     vad_target, noise_free = new((n_frames, N)), new((N,), torch.int32)
-    rec = new((n_frames, N, REC))
     d_vad = new((N, n_frames), torch.uint8) if on_device else None
     count = len(draws.mix)
     if rirs is not None:
@@ -203,13 +192,55 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
         else:
             batch.train_levels_device(energy.data_ptr(), rms.data_ptr(), ptrs, lens, mix, n_frames, st)
             d_vad = torch.from_numpy(capi.train_vad(energy.cpu().numpy(), _pad(draws.start_pos[rows], N))).to(dev)
-        d_lowpass = torch.from_numpy(_pad(draws.lowpass[rows], N).astype(np.int32)).to(dev)
-        d_band_lp = torch.from_numpy(_pad(draws.band_lp[rows], N).astype(np.int32)).to(dev)
         batch.train_mix_device(clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), noise_free.data_ptr(), ptrs, lens, mix,
                                rms.data_ptr(), d_vad.data_ptr(), n_frames, st)
         if rirs is not None:
             batch.train_rir_device(clean.data_ptr(), noisy.data_ptr(), spectra.data_ptr(), len(spectra), _pad(rir_rec[rows], N),
                                    work.data_ptr(), rir_work_bytes, n_frames, st)
+        yield first, k, clean, noisy, vad_target, noise_free, st
+
+
+def mix_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, vad: str = "auto",
+               rir_work_bytes: int = 256 << 20):
+    """The sequences of `draws` as AUDIO, round by round: what generate_rounds runs in front of its features call -- levels (+ VAD)
+    -> mix -> optional RIR -- and nothing behind it.  Yields (k, clean, noisy, vad_target) per round: clean and noisy
+    (n_frames, N, 480) float32 and vad_target (n_frames, N) float32 tensors on the batch's device, of which streams 0 .. k - 1
+    carry sequences [r * N, r * N + k) of round r (a partial last round repeats its last sequence on the others).  The tensors are
+    the generator's own and valid until the next iteration; the work is enqueued on torch's current stream.  The calls read and
+    write nothing of the batch's per-stream denoiser state (they use its device, its size and its upload buffers), so the same
+    batch may denoise `noisy` in between.  Arguments as in generate_rounds."""
+    for _first, k, clean, noisy, vad_target, _noise_free, _st in _mix_rounds(batch, speech, noise, fgnoise, draws, n_frames, rirs,
+                                                                             rir_work_bytes, vad):
+        yield k, clean, noisy, vad_target
+
+
+def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20,
+                    vad: str = "auto"):
+    """Yields the records of sequences [r * N, (r + 1) * N) of `draws`, r = 0, 1, ..., each a (sequences, n_frames, 98) float32 array:
+    sequence i runs on stream i % N of `batch` (N streams) in round i // N, and the batch's per-stream analysis state carries from one
+    sequence of a stream to the next, as the reference's two DenoiseStates carry across its loop.  speech, noise, fgnoise: the corpora
+    as 1-D int16 torch tensors on the batch's device.  Everything is enqueued on torch's current stream.  vad: where the Viterbi VAD of the
+    frame energies runs -- "device": in the levels launch, a round then copies nothing back and does not synchronise between its
+    kernels (RuntimeError on a host whose libm the device does not restate, capi.train_vad_device_available()); "host": the energies
+    go to the host, rnnoise_amd_train_vad decodes them on one thread, the bytes go back; "auto" (the default): "device" where
+    available, else "host".  The records are the same to the byte.  When the last round is partial, the streams behind the last sequence run that
+    sequence again (records dropped), so their analysis state advances too: a later call on the same batch starts those streams from
+    a state that no sequence of the file order left.  Reset the batch, or use a sequence count that is a multiple of N, where that
+    matters; one run of the command line is not affected.
+    rirs = (spectra, records): the tensor of rir_spectra() and draw_rir()'s records, one per sequence of `draws`.  The mix then runs
+    without clipping and quantisation, and the RIR call filters the sequences the records name and applies the flags of `draws` to
+    all (dump_features.c:449-465), in a workspace of rir_work_bytes (at least capi.train_rir_work_bytes(1)).  Without rirs nothing
+    changes."""
+    import torch
+    rec = None
+    for first, k, clean, noisy, vad_target, noise_free, st in _mix_rounds(batch, speech, noise, fgnoise, draws, n_frames, rirs,
+                                                                          rir_work_bytes, vad):
+        N, dev = batch.n, clean.device
+        if rec is None:
+            rec = torch.empty((n_frames, N, REC), dtype=torch.float32, device=dev)
+        rows = slice(first, first + k)
+        d_lowpass = torch.from_numpy(_pad(draws.lowpass[rows], N).astype(np.int32)).to(dev)
+        d_band_lp = torch.from_numpy(_pad(draws.band_lp[rows], N).astype(np.int32)).to(dev)
         batch.train_features_device(rec.data_ptr(), clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), d_lowpass.data_ptr(),
                                     d_band_lp.data_ptr(), noise_free.data_ptr(), n_frames, st)
         yield rec.permute(1, 0, 2)[:k].contiguous().cpu().numpy()  # sequence-major: the reference's file order
