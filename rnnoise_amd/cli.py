@@ -53,6 +53,15 @@ librnnoise_amd_score.so -- a table of SNR, SI-SDR and segmental SNR in dB per mo
 
   python -m rnnoise_amd.cli eval-audio speech.pcm noise.pcm fgnoise.pcm --model a.blob [--model b.blob] [--checkpoint ckpt.pth]
          [--torch-net net.pt] --count N [--frames T] [--rir-list FILE] [--seed S] [--streams N]
+
+Training (rnnoise_amd/train.py): the loop of the reference's torch/rnnoise/train_rnnoise.py with its options, the loss
+and its gradient computed by librnnoise_amd_train.so in the doubles eval-records prints; one checkpoint per epoch under
+OUT/checkpoints/, in the reference's format, and one line per epoch with the three means:
+
+  python -m rnnoise_amd.cli train records.f32 OUT [--epochs N] [--batch-size B] [--sequence-length T] [--lr R] [--lr-decay D]
+         [--gamma G] [--sparse] [--initial-checkpoint ckpt.pth] [--cond-size C] [--gru-size H] [--suffix S] [--seed S]
+  python -m rnnoise_amd.cli train OUT --online speech.pcm noise.pcm fgnoise.pcm --sequences-per-epoch N [--rir-list FILE] [...]
+--online trains on fresh sequences every epoch, generated on the device as dump-features generates them and never written to a file.
 """
 from __future__ import annotations
 
@@ -292,6 +301,29 @@ def dump_features(model_blob: bytes, speech: str, noise: str, fgnoise: str, out:
     return count * seq_frames
 
 
+def train_arguments(ap, a) -> dict:
+    """the keyword arguments of train.train_files from the parsed `train` command line; argparse errors where they do not fit"""
+    if a.online is not None:
+        if len(a.paths) != 1:
+            ap.error("train --online: one path, the output folder")
+        if a.sequences_per_epoch is None or a.sequences_per_epoch < a.batch_size:
+            ap.error("train --online: --sequences-per-epoch, at least one batch")
+        records, out = None, a.paths[0]
+    else:
+        if len(a.paths) != 2:
+            ap.error("train: RECORDS OUT (or OUT with --online)")
+        if a.sequences_per_epoch is not None or a.rir_list is not None:
+            ap.error("train: --sequences-per-epoch and --rir-list belong to --online")
+        records, out = a.paths
+    if a.epochs < 1 or a.batch_size < 1 or a.sequence_length < 6 or not a.gamma > 0:
+        ap.error("train: --epochs and --batch-size at least 1, --sequence-length at least 6, --gamma above 0")
+    return dict(records=records, out=out, online=tuple(a.online) if a.online is not None else None,
+                sequences_per_epoch=a.sequences_per_epoch, rir_list=a.rir_list, epochs=a.epochs, batch_size=a.batch_size,
+                sequence_length=a.sequence_length, lr=a.lr, lr_decay=a.lr_decay, gamma=a.gamma, sparse=a.sparse,
+                initial_checkpoint=a.initial_checkpoint, cond_size=a.cond_size, gru_size=a.gru_size, suffix=a.suffix, seed=a.seed,
+                device=a.device)
+
+
 AUDIO_COLUMNS = (("snr_in", "SNR in"), ("snr_out", "SNR out"), ("snr_gain", "gain"), ("si_sdr_in", "SI-SDR in"),
                  ("si_sdr_out", "SI-SDR out"), ("si_sdr_gain", "gain"), ("seg_snr_in", "segSNR in"), ("seg_snr_out", "segSNR out"))
 
@@ -428,7 +460,31 @@ def main(argv=None):
     p.add_argument("speech")
     p.add_argument("noise")
     p.add_argument("fgnoise")
+    p = sub.add_parser("train")
+    p.add_argument("--suffix", default="", help="model name suffix of the checkpoint files")
+    p.add_argument("--cond-size", type=int, default=128)
+    p.add_argument("--gru-size", type=int, default=384)
+    p.add_argument("--batch-size", type=int, default=128)
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--epochs", type=int, default=200)
+    p.add_argument("--sequence-length", type=int, default=2000)
+    p.add_argument("--lr-decay", type=float, default=5e-5)
+    p.add_argument("--initial-checkpoint", default=None)
+    p.add_argument("--gamma", type=float, default=0.25, help="perceptual exponent of the gain loss")
+    p.add_argument("--sparse", action="store_true", help="the GRU block sparsifier's schedule after every step")
+    p.add_argument("--seed", type=int, default=None, help="of the shuffle, the initialisation and the online draws")
+    p.add_argument("--online", nargs=3, metavar=("SPEECH", "NOISE", "FGNOISE"), default=None,
+                   help="RAW s16 48 kHz corpora: train on sequences generated on the device instead of a record file")
+    p.add_argument("--sequences-per-epoch", type=int, default=None, help="with --online: sequences generated per epoch")
+    p.add_argument("--rir-list", default=None, help="with --online: file of RIR file names, one per line (raw float32)")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("paths", nargs="+", metavar="PATH", help="RECORDS OUT: a record file and the output folder; with --online: OUT")
     a = ap.parse_args(argv)
+    if a.cmd == "train":
+        kw = train_arguments(ap, a)
+        from . import train
+        train.train_files(**kw)
+        return
     if a.cmd == "eval-audio":
         if not a.model and a.checkpoint is None and a.torch_net is None:
             ap.error("eval-audio: --model, --checkpoint or --torch-net")

@@ -1652,36 +1652,9 @@ rn_analysis_rows_kernel(RnGroupDev g, RnTablesDev tb, RnRows rows) {
 // its row's consecutive floats wherever the rows lie.
 // one scored frame's terms from its four kinds of floats -- gt the record's gain target of band lane & 31, v its VAD target, p the
 // predicted gain of that band, q the predicted VAD -- in the lane roles above: the body of the record step and of the score walk
-struct EvalTerms {
-  double band;     // lanes 0 .. 31: the band's gain term; lanes 32 .. 63: +0
-  double term;     // the butterfly's sum of the 32 gain terms
-  double lg, lg1;  // lane 0: log(.01 + q), log(1.01 - q)
-};
-__device__ __forceinline__ EvalTerms eval_frame_terms(float gt_f, float v_f, float p_f, float q_f, double gamma, int lane) {
-  const double v = (double)v_f;
-  // the f64 library calls are what this launch costs, so each runs once per wave: lane b raises band b's prediction
-  // to gamma while lane 32 + b raises its shaped target, and lanes 0 and 1 take the two logs of the VAD term
-  const double gt = (double)gt_f, p = (double)p_f;
-  double tg = gt < 0.0 ? 0.0 : gt;
-  const double th = tanh(8.0 * tg);
-  tg = tg * (th * th);
-  const double pw = pow(lane < RN_NB_BANDS ? p : tg, gamma);
-  const double d = pw - __shfl_xor(pw, RN_NB_BANDS, WAVE);
-  const double m = gt + 1.0 > 1.0 ? 1.0 : gt + 1.0;
-  EvalTerms k;
-  k.band = lane < RN_NB_BANDS ? ((1.0 + 5.0 * v) * m) * (d * d) : 0.0;
-  k.term = k.band;
-#pragma unroll
-  for (int off = 16; off >= 1; off >>= 1) k.term += __shfl_xor(k.term, off, WAVE);
-  const double q = (double)q_f;
-  k.lg = log(lane == 0 ? .01 + q : 1.01 - q), k.lg1 = __shfl_xor(k.lg, 1, WAVE);
-  return k;
-}
-// lane 0's VAD term of the frame
-__device__ __forceinline__ double eval_vad_term(float v_f, const EvalTerms &k) {
-  const double v = (double)v_f;
-  return fabs(2.0 * v - 1.0) * (-v * k.lg - (1.0 - v) * k.lg1);
-}
+// -- EvalTerms k = eval_frame_terms(gt, v, p, q, gamma, lane) and eval_vad_term(v, k): eval_terms.h, the one definition, which the
+// trainer's loss library (train/train_loss.hip) compiles too
+#include "eval_terms.h"
 
 __device__ __forceinline__ void eval_step_body(const RnGroupDev &g, const RnEvalStep &e) {
   const int s = (int)blockIdx.x, lane = (int)threadIdx.x;

@@ -12,7 +12,8 @@ concatenation [conv2 | gru1 | gru2 | gru3].
       GRUs do not run on them, and their gains and vad are zeros -- what the blob's network leaves on a silent frame.  reset() starts a
       new sequence.  This is the stateful net of RNNoiseOp.denoise_with(net, pcm) and of cli denoise --checkpoint.
 
-Forward only: nothing here trains."""
+The module itself only runs forward; rnnoise_amd.train.fit trains it -- forward_sequence with carried states, torch's autograd through
+these layers, the loss and its gradient from librnnoise_amd_train.so."""
 from __future__ import annotations
 
 import torch

@@ -231,6 +231,18 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
     without clipping and quantisation, and the RIR call filters the sequences the records name and applies the flags of `draws` to
     all (dump_features.c:449-465), in a workspace of rir_work_bytes (at least capi.train_rir_work_bytes(1)).  Without rirs nothing
     changes."""
+    for k, rec in generate_rounds_device(batch, speech, noise, fgnoise, draws, n_frames, rirs, rir_work_bytes, vad):
+        yield rec.permute(1, 0, 2)[:k].contiguous().cpu().numpy()  # sequence-major: the reference's file order
+
+
+def generate_rounds_device(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None,
+                           rir_work_bytes: int = 256 << 20, vad: str = "auto"):
+    """generate_rounds with the records left where the features call wrote them: yields (k, rec) per round, rec the
+    (n_frames, N, 98) float32 tensor on the batch's device -- record t of stream s at rec[t, s]: strides (N * 98, 98) in the words
+    of the score and loss calls -- of which streams 0 .. k - 1 carry sequences [r * N, r * N + k) of round r.  The tensor is the
+    generator's own, reused by the next round and valid until the next iteration; the work is enqueued on torch's current stream and
+    nothing is copied back or waited for (with the VAD on the device).  This is the online data of rnnoise_amd.train.  Arguments,
+    carried state and the partial last round as in generate_rounds, which yields the bytes of these tensors."""
     import torch
     rec = None
     for first, k, clean, noisy, vad_target, noise_free, st in _mix_rounds(batch, speech, noise, fgnoise, draws, n_frames, rirs,
@@ -243,7 +255,7 @@ def generate_rounds(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_f
         d_band_lp = torch.from_numpy(_pad(draws.band_lp[rows], N).astype(np.int32)).to(dev)
         batch.train_features_device(rec.data_ptr(), clean.data_ptr(), noisy.data_ptr(), vad_target.data_ptr(), d_lowpass.data_ptr(),
                                     d_band_lp.data_ptr(), noise_free.data_ptr(), n_frames, st)
-        yield rec.permute(1, 0, 2)[:k].contiguous().cpu().numpy()  # sequence-major: the reference's file order
+        yield k, rec
 
 
 def generate(batch: capi.Batch, speech, noise, fgnoise, draws: Draws, n_frames: int, rirs=None, rir_work_bytes: int = 256 << 20,
