@@ -317,11 +317,14 @@ def train_arguments(ap, a) -> dict:
         records, out = a.paths
     if a.epochs < 1 or a.batch_size < 1 or a.sequence_length < 6 or not a.gamma > 0:
         ap.error("train: --epochs and --batch-size at least 1, --sequence-length at least 6, --gamma above 0")
-    return dict(records=records, out=out, online=tuple(a.online) if a.online is not None else None,
-                sequences_per_epoch=a.sequences_per_epoch, rir_list=a.rir_list, epochs=a.epochs, batch_size=a.batch_size,
-                sequence_length=a.sequence_length, lr=a.lr, lr_decay=a.lr_decay, gamma=a.gamma, sparse=a.sparse,
-                initial_checkpoint=a.initial_checkpoint, cond_size=a.cond_size, gru_size=a.gru_size, suffix=a.suffix, seed=a.seed,
-                device=a.device)
+    kw = dict(records=records, out=out, online=tuple(a.online) if a.online is not None else None,
+              sequences_per_epoch=a.sequences_per_epoch, rir_list=a.rir_list, epochs=a.epochs, batch_size=a.batch_size,
+              sequence_length=a.sequence_length, lr=a.lr, lr_decay=a.lr_decay, gamma=a.gamma, sparse=a.sparse,
+              initial_checkpoint=a.initial_checkpoint, cond_size=a.cond_size, gru_size=a.gru_size, suffix=a.suffix, seed=a.seed,
+              device=a.device)
+    if a.gru != "torch":  # the default run's arguments are what they were before the switch existed
+        kw["gru"] = a.gru
+    return kw
 
 
 AUDIO_COLUMNS = (("snr_in", "SNR in"), ("snr_out", "SNR out"), ("snr_gain", "gain"), ("si_sdr_in", "SI-SDR in"),
@@ -477,6 +480,10 @@ def main(argv=None):
                    help="RAW s16 48 kHz corpora: train on sequences generated on the device instead of a record file")
     p.add_argument("--sequences-per-epoch", type=int, default=None, help="with --online: sequences generated per epoch")
     p.add_argument("--rir-list", default=None, help="with --online: file of RIR file names, one per line (raw float32)")
+    p.add_argument("--gru", choices=("torch", "native"), default="torch",
+                   help="what runs the three GRUs: torch's nn.GRU (default), or native: their recurrences, forward and backward, on "
+                        "this project's own kernels (librnnoise_amd_gru.so: one launch per step, exact float32 matrix instructions); "
+                        "the same parameters and checkpoints either way")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("paths", nargs="+", metavar="PATH", help="RECORDS OUT: a record file and the output folder; with --online: OUT")
     a = ap.parse_args(argv)

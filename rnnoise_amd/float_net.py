@@ -13,19 +13,29 @@ concatenation [conv2 | gru1 | gru2 | gru3].
       new sequence.  This is the stateful net of RNNoiseOp.denoise_with(net, pcm) and of cli denoise --checkpoint.
 
 The module itself only runs forward; rnnoise_amd.train.fit trains it -- forward_sequence with carried states, torch's autograd through
-these layers, the loss and its gradient from librnnoise_amd_train.so."""
+these layers, the loss and its gradient from librnnoise_amd_train.so.  With gru_impl = "native" the three GRUs'
+recurrences, forward and backward, run on librnnoise_amd_gru.so instead of torch's nn.GRU; "torch" is the default."""
 from __future__ import annotations
 
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 FEATURES, BANDS, LOOKAHEAD = 65, 32, 4
 
 
+GRU_IMPLS = ("torch", "native")
+
+
 class FloatNet(nn.Module):
-    def __init__(self, cond_size: int = 128, gru_size: int = 384):
+    def __init__(self, cond_size: int = 128, gru_size: int = 384, gru_impl: str = "torch"):
+        """gru_impl: what runs the three GRUs -- "torch": nn.GRU as it is; "native": the recurrence on librnnoise_amd_gru.so
+        (rnnoise_amd.gru_native.GruSequence) with the nn.GRU modules' own parameters, float32 on the device only.
+        An attribute, not a parameter: it may be set afterwards, and checkpoints do not carry it."""
         super().__init__()
-        self.cond_size, self.gru_size = cond_size, gru_size
+        if gru_impl not in GRU_IMPLS:
+            raise ValueError(f"gru_impl: one of {GRU_IMPLS}, not {gru_impl!r}")
+        self.cond_size, self.gru_size, self.gru_impl = cond_size, gru_size, gru_impl
         self.conv1 = nn.Conv1d(FEATURES, cond_size, kernel_size=3)
         self.conv2 = nn.Conv1d(cond_size, gru_size, kernel_size=3)
         self.gru1 = nn.GRU(gru_size, gru_size, batch_first=True)
@@ -44,11 +54,30 @@ class FloatNet(nn.Module):
 
     def _back(self, c, states):
         """conv2's frames [N, K, gru_size] and three states [1, N, gru_size] -> gains, vad, the states after frame K - 1"""
-        g1, s1 = self.gru1(c, states[0])
-        g2, s2 = self.gru2(g1, states[1])
-        g3, s3 = self.gru3(g2, states[2])
+        if self.gru_impl == "torch":
+            g1, s1 = self.gru1(c, states[0])
+            g2, s2 = self.gru2(g1, states[1])
+            g3, s3 = self.gru3(g2, states[2])
+        elif self.gru_impl == "native":
+            g1, s1 = self._native_gru(self.gru1, c, states[0])
+            g2, s2 = self._native_gru(self.gru2, g1, states[1])
+            g3, s3 = self._native_gru(self.gru3, g2, states[2])
+        else:
+            raise ValueError(f"gru_impl: one of {GRU_IMPLS}, not {self.gru_impl!r}")
         cat = torch.cat([c, g1, g2, g3], dim=-1)
         return torch.sigmoid(self.dense_out(cat)), torch.sigmoid(self.vad_dense(cat)), [s1, s2, s3]
+
+    def _native_gru(self, gru, x, state):
+        """one nn.GRU's layer on the native recurrence: x [N, K, in], state [1, N, H] -> output [N, K, H], state after [1, N, H].
+        The input projection is torch's, one product over all steps; there is no fallback: what the library does not take raises."""
+        from . import gru_native
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise ValueError(f'gru_impl "native" runs float32 tensors on the device, not {x.dtype} on {x.device}: use gru_impl "torch"')
+        if self.gru_size % gru_native.TILE or not gru_native.MIN_HIDDEN <= self.gru_size <= gru_native.MAX_HIDDEN:
+            raise ValueError('gru_impl "native": ' + gru_native.refusal(x.shape[0], x.shape[1], self.gru_size))
+        gi = F.linear(x, gru.weight_ih_l0, gru.bias_ih_l0)
+        y = gru_native.GruSequence.apply(gi, gru.weight_hh_l0, gru.bias_hh_l0, state[0])
+        return y, y[:, -1].unsqueeze(0).contiguous()
 
     def _zero_states(self, n, like):
         return [torch.zeros((1, n, self.gru_size), device=like.device, dtype=like.dtype) for _ in range(3)]

@@ -14,6 +14,8 @@
   python -m rnnoise_amd.cli train out --online speech.pcm noise.pcm fgnoise.pcm --sequences-per-epoch N [...]
 
 The network's forward and backward are torch's (its GRU dominates the step: profiles/train_step.txt); the loss is this project's.
+With gru="native" the GRUs' recurrences run on this project's kernels as well (gru_native); torch's nn.GRU is the
+default.
 """
 from __future__ import annotations
 
@@ -155,12 +157,13 @@ def device_loss(gains, vad, records, gamma):
     return train_loss.TrainerLoss.apply(gains, vad, records, float_net.LOOKAHEAD, float_net.LOOKAHEAD, gamma)
 
 
-def new_network(cond_size: int = 128, gru_size: int = 384, seed=None):
-    """a FloatNet initialised as the reference's RNNoise is: torch's defaults, the recurrent GRU weights orthogonal"""
+def new_network(cond_size: int = 128, gru_size: int = 384, seed=None, gru: str = "torch"):
+    """a FloatNet initialised as the reference's RNNoise is: torch's defaults, the recurrent GRU weights orthogonal; gru: the
+    network's gru_impl (the weights do not depend on it)"""
     import torch
     if seed is not None:
         torch.manual_seed(seed)
-    net = float_net.FloatNet(cond_size=cond_size, gru_size=gru_size)
+    net = float_net.FloatNet(cond_size=cond_size, gru_size=gru_size, gru_impl=gru)
     for gru in (net.gru1, net.gru2, net.gru3):
         torch.nn.init.orthogonal_(gru.weight_hh_l0)
     return net
@@ -172,7 +175,7 @@ def checkpoint_path(out: str, epoch: int, suffix: str = "") -> str:
 
 def fit(data, out: str, epochs: int = 200, lr: float = 1e-3, lr_decay: float = 5e-5, gamma: float = 0.25, sparse=False,
         initial_checkpoint=None, cond_size: int = 128, gru_size: int = 384, suffix: str = "", seed=None, loss=None, device=None,
-        on_step=None, log=print):
+        on_step=None, log=print, gru: str = "torch"):
     """Trains a FloatNet on `data` -- a RecordFile, an OnlineRecords, or anything with __len__ (batches per epoch) and
     batches(rng, device) -- for `epochs` epochs and writes out/checkpoints/rnnoise{suffix}_{epoch}.pth after each.
 
@@ -185,6 +188,8 @@ def fit(data, out: str, epochs: int = 200, lr: float = 1e-3, lr_decay: float = 5
     seed: the shuffle's (and, without initial_checkpoint, the initialisation's).  on_step: called after every step with a dict
     (epoch, step, loss, gain_loss, vad_loss, lr: the rate the step was taken with, states: the detached states carried on,
     sparsified).  log: called with one line per epoch holding the three means (None: silent).
+    gru: "torch" (nn.GRU) or "native": the three GRUs' recurrences, forward and backward, on librnnoise_amd_gru.so (FloatNet's
+    gru_impl; the device only) -- the same parameters and checkpoints either way.
     -> a list with one dict per epoch: epoch, loss, gain_loss, vad_loss (the means over the epoch's batches, as the reference prints
     them), checkpoint (the file)."""
     import torch
@@ -196,7 +201,7 @@ def fit(data, out: str, epochs: int = 200, lr: float = 1e-3, lr_decay: float = 5
         raise ValueError("no batch in an epoch")
     os.makedirs(os.path.join(out, "checkpoints"), exist_ok=True)
     checkpoint = dict(model_args=(), model_kwargs=dict(cond_size=cond_size, gru_size=gru_size))
-    net = new_network(cond_size, gru_size, seed)
+    net = new_network(cond_size, gru_size, seed, gru)
     if initial_checkpoint is not None:
         checkpoint = torch.load(initial_checkpoint, map_location="cpu")
         kw = checkpoint.get("model_kwargs") or {}
@@ -244,9 +249,9 @@ def fit(data, out: str, epochs: int = 200, lr: float = 1e-3, lr_decay: float = 5
 def train_files(records, out: str, online=None, sequences_per_epoch=None, rir_list=None, epochs: int = 200, batch_size: int = 128,
                 sequence_length: int = 2000, lr: float = 1e-3, lr_decay: float = 5e-5, gamma: float = 0.25, sparse: bool = False,
                 initial_checkpoint=None, cond_size: int = 128, gru_size: int = 384, suffix: str = "", seed=None, device: int = 0,
-                log=print):
+                log=print, gru: str = "torch"):
     """cli train: a record file, or with online = (speech, noise, fgnoise) file names the corpora behind OnlineRecords (rir_list: a
-    file of RIR file names, raw float32, one per line) -> fit's history"""
+    file of RIR file names, raw float32, one per line); gru: fit's -> fit's history"""
     import torch
     data = None
     try:
@@ -263,7 +268,7 @@ def train_files(records, out: str, online=None, sequences_per_epoch=None, rir_li
         else:
             data = RecordFile(records, sequence_length, batch_size)
         return fit(data, out, epochs, lr, lr_decay, gamma, sparse, initial_checkpoint, cond_size, gru_size, suffix, seed,
-                   device=f"cuda:{device}", log=log)
+                   device=f"cuda:{device}", log=log, gru=gru)
     finally:
         if isinstance(data, OnlineRecords):
             data.close()

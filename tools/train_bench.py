@@ -12,6 +12,13 @@ Two measurements in one job, device events on torch's stream, median of R rounds
 
 Writes the table to FILE (default profiles/train_step.txt) and prints it.  Without a GPU it fails: a number that was not measured
 is not written.
+
+  python tools/train_bench.py --gru native [--rows N] [--frames T] [--rounds R] [--warmup W] [--out FILE]
+
+measures the native GRUs instead, beside torch's in the same job, the two alternating round by round: the network's
+forward and backward with FloatNet's gru_impl "torch" and "native"; and one layer on fixed inputs -- nn.GRU forward and backward
+against the forward and backward calls of librnnoise_amd_gru.so, with the per-step time of the latter.  FILE defaults to
+profiles/train_step_gru.txt; profiles/train_step.txt is not touched.
 """
 import argparse
 import os
@@ -25,17 +32,116 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def gru_bench(a):
+    """--gru native: the network and one layer's recurrence, torch's nn.GRU and librnnoise_amd_gru.so alternating in one job"""
+    import torch
+    from torch.nn import functional as F
+
+    from rnnoise_amd import gru_native, train
+    dev = torch.device("cuda", 0)
+    N, T, K, H = a.rows, a.frames, a.frames - 4, 384
+    out = a.out or os.path.join(ROOT, "profiles", "train_step_gru.txt")
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def alternate(cases):
+        """{name: fn} -> {name: times in ms}: round after round, every case once per round"""
+        ms = {k: [] for k in cases}
+        for r in range(a.warmup + a.rounds):
+            for k, fn in cases.items():
+                t = once(fn)
+                if r >= a.warmup:
+                    ms[k].append(t)
+        return ms
+
+    fmt = lambda ms: f"{statistics.median(ms):9.3f} ms  ({min(ms):.3f} .. {max(ms):.3f})"
+    lines = [f"# tools/train_bench.py --gru native --rows {N} --frames {T} --rounds {a.rounds} --warmup {a.warmup}; "
+             f"{torch.cuda.get_device_name(0)}; median of {a.rounds} (min .. max), device events, the implementations alternating"]
+
+    # ---- the network: forward, and backward of a fixed linear functional of its outputs ----
+    gen = torch.Generator().manual_seed(1)
+    features = torch.randn(N, T, 65, generator=gen).to(dev)
+    A, B = torch.randn(N, K, 32, generator=gen).to(dev), torch.randn(N, K, 1, generator=gen).to(dev)
+    net = train.new_network(seed=1).to(dev).train()
+    held = {}
+
+    def forward(impl):
+        def fn():
+            net.gru_impl = impl
+            net.zero_grad()
+            g, v = net.forward_sequence(features)
+            held[impl] = (g * A).sum() + (v * B).sum()
+        return fn
+
+    def backward(impl):
+        return lambda: held.pop(impl).backward()
+    ms = alternate({"torch forward": forward("torch"), "torch backward": backward("torch"), "native forward": forward("native"),
+                    "native backward": backward("native")})
+    lines.append(f"network forward and backward, batch {N} x {T} frames, cond_size 128, gru_size {H}:")
+    for k in ms:
+        lines.append(f"  {k:34s} {fmt(ms[k])}")
+
+    # ---- one layer's recurrence on fixed gi ----
+    gru = torch.nn.GRU(H, H, batch_first=True).to(dev)
+    x = torch.randn(N, K, H, generator=gen).to(dev).requires_grad_(True)
+    dy = torch.randn(N, K, H, generator=gen).to(dev)
+    with torch.no_grad():
+        gi = F.linear(x, gru.weight_ih_l0, gru.bias_ih_l0)
+    w, b = gru.weight_hh_l0.detach(), gru.bias_hh_l0.detach()
+    y, dgi = torch.empty(N, K, H, device=dev), torch.empty(N, K, 3 * H, device=dev)
+    kept = {}
+
+    def nn_forward():
+        kept["y"] = gru(x)[0]
+
+    def nn_backward():
+        x.grad = None
+        gru.zero_grad()
+        kept.pop("y").backward(dy)
+
+    def native_forward():
+        kept["saved"] = gru_native.sequence_forward(gi, w, b, None, y=y)[1]
+
+    def native_backward():
+        kept["dgh"] = gru_native.sequence_backward(dy, y, kept["saved"], w, None, None, dgi=dgi)[1]
+    ms = alternate({"nn.GRU forward (whole layer)": nn_forward, "nn.GRU backward (whole layer)": nn_backward,
+                    "native recurrence forward": native_forward, "native recurrence backward": native_backward,
+                    "native dW_hh, db_hh (torch)": lambda: gru_native.weight_grads(kept["dgh"], y, None),
+                    "input projection (F.linear)": lambda: F.linear(x.detach(), gru.weight_ih_l0, gru.bias_ih_l0)})
+    lines.append(f"one layer, {N} rows x {K} steps, hidden {H} (nn.GRU: projection, recurrence and weight gradients; native: the {K} "
+                 "launches of the recurrence alone):")
+    for k in ms:
+        lines.append(f"  {k:34s} {fmt(ms[k])}")
+    for k in ("native recurrence forward", "native recurrence backward"):
+        lines.append(f"  {k + ', per step':34s} {1e3 * statistics.median(ms[k]) / K:9.2f} us")
+    text = "\n".join(lines) + "\n"
+    with open(out, "w") as f:
+        f.write(text)
+    print(text, end="")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=128)
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_step.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--gru", choices=("torch", "native"), default="torch")
     a = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         sys.exit("train_bench: no GPU: nothing measured")
+    if a.gru == "native":
+        return gru_bench(a)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "train_step.txt")
     from rnnoise_amd import synth, train, train_loss
     dev = torch.device("cuda", 0)
     N, T = a.rows, a.frames
