@@ -480,10 +480,11 @@ def main(argv=None):
                    help="RAW s16 48 kHz corpora: train on sequences generated on the device instead of a record file")
     p.add_argument("--sequences-per-epoch", type=int, default=None, help="with --online: sequences generated per epoch")
     p.add_argument("--rir-list", default=None, help="with --online: file of RIR file names, one per line (raw float32)")
-    p.add_argument("--gru", choices=("torch", "native"), default="torch",
+    p.add_argument("--gru", choices=("torch", "native", "stack"), default="torch",
                    help="what runs the three GRUs: torch's nn.GRU (default), or native: their recurrences, forward and backward, on "
-                        "this project's own kernels (librnnoise_amd_gru.so: one launch per step, exact float32 matrix instructions); "
-                        "the same parameters and checkpoints either way")
+                        "this project's own kernels (librnnoise_amd_gru.so: one launch per step, exact float32 matrix instructions), "
+                        "or stack: the three layers as one diagonal launch per step, layers 2 and 3 one step behind each "
+                        "(librnnoise_amd_gru_stack.so); the same parameters and checkpoints either way")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("paths", nargs="+", metavar="PATH", help="RECORDS OUT: a record file and the output folder; with --online: OUT")
     a = ap.parse_args(argv)

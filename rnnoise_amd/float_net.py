@@ -14,7 +14,8 @@ concatenation [conv2 | gru1 | gru2 | gru3].
 
 The module itself only runs forward; rnnoise_amd.train.fit trains it -- forward_sequence with carried states, torch's autograd through
 these layers, the loss and its gradient from librnnoise_amd_train.so.  With gru_impl = "native" the three GRUs'
-recurrences, forward and backward, run on librnnoise_amd_gru.so instead of torch's nn.GRU; "torch" is the default."""
+recurrences, forward and backward, run on librnnoise_amd_gru.so instead of torch's nn.GRU; with "stack" the three
+layers run on librnnoise_amd_gru_stack.so as one diagonal launch a step; "torch" is the default."""
 from __future__ import annotations
 
 import torch
@@ -24,13 +25,15 @@ from torch.nn import functional as F
 FEATURES, BANDS, LOOKAHEAD = 65, 32, 4
 
 
-GRU_IMPLS = ("torch", "native")
+GRU_IMPLS = ("torch", "native", "stack")
 
 
 class FloatNet(nn.Module):
     def __init__(self, cond_size: int = 128, gru_size: int = 384, gru_impl: str = "torch"):
         """gru_impl: what runs the three GRUs -- "torch": nn.GRU as it is; "native": the recurrence on librnnoise_amd_gru.so
-        (rnnoise_amd.gru_native.GruSequence) with the nn.GRU modules' own parameters, float32 on the device only.
+        (rnnoise_amd.gru_native.GruSequence; DESIGN.md 4.33) with the nn.GRU modules' own parameters, float32 on the device only;
+        "stack": the three layers on librnnoise_amd_gru_stack.so, one diagonal launch a step (rnnoise_amd.gru_stack.GruStack; DESIGN.md
+        4.34), likewise.
         An attribute, not a parameter: it may be set afterwards, and checkpoints do not carry it."""
         super().__init__()
         if gru_impl not in GRU_IMPLS:
@@ -62,6 +65,8 @@ class FloatNet(nn.Module):
             g1, s1 = self._native_gru(self.gru1, c, states[0])
             g2, s2 = self._native_gru(self.gru2, g1, states[1])
             g3, s3 = self._native_gru(self.gru3, g2, states[2])
+        elif self.gru_impl == "stack":
+            (g1, g2, g3), (s1, s2, s3) = self._stack_grus(c, states)
         else:
             raise ValueError(f"gru_impl: one of {GRU_IMPLS}, not {self.gru_impl!r}")
         cat = torch.cat([c, g1, g2, g3], dim=-1)
@@ -78,6 +83,20 @@ class FloatNet(nn.Module):
         gi = F.linear(x, gru.weight_ih_l0, gru.bias_ih_l0)
         y = gru_native.GruSequence.apply(gi, gru.weight_hh_l0, gru.bias_hh_l0, state[0])
         return y, y[:, -1].unsqueeze(0).contiguous()
+
+    def _stack_grus(self, x, states):
+        """the three nn.GRU layers on the stack library: x [N, K, in], three states [1, N, H] -> three outputs [N, K, H], three states
+        after [1, N, H].  Layer 1's input projection is torch's, one product over all steps; there is no fallback."""
+        from . import gru_stack
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise ValueError(f'gru_impl "stack" runs float32 tensors on the device, not {x.dtype} on {x.device}: use gru_impl "torch"')
+        if self.gru_size % gru_stack.TILE or not gru_stack.MIN_HIDDEN <= self.gru_size <= gru_stack.MAX_HIDDEN:
+            raise ValueError('gru_impl "stack": ' + gru_stack.refusal(x.shape[0], x.shape[1], self.gru_size))
+        g = (self.gru1, self.gru2, self.gru3)
+        gi0 = F.linear(x, g[0].weight_ih_l0, g[0].bias_ih_l0)
+        ys = gru_stack.GruStack.apply(gi0, g[1].weight_ih_l0, g[1].bias_ih_l0, g[2].weight_ih_l0, g[2].bias_ih_l0,
+                                      *[m.weight_hh_l0 for m in g], *[m.bias_hh_l0 for m in g], *[s[0] for s in states])
+        return ys, [y[:, -1].unsqueeze(0).contiguous() for y in ys]
 
     def _zero_states(self, n, like):
         return [torch.zeros((1, n, self.gru_size), device=like.device, dtype=like.dtype) for _ in range(3)]

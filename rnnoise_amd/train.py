@@ -14,8 +14,8 @@
   python -m rnnoise_amd.cli train out --online speech.pcm noise.pcm fgnoise.pcm --sequences-per-epoch N [...]
 
 The network's forward and backward are torch's (its GRU dominates the step: profiles/train_step.txt); the loss is this project's.
-With gru="native" the GRUs' recurrences run on this project's kernels as well (gru_native); torch's nn.GRU is the
-default.
+With gru="native" the GRUs' recurrences run on this project's kernels as well (gru_native), with gru="stack" the
+three layers as one diagonal launch a step (gru_stack); torch's nn.GRU is the default.
 """
 from __future__ import annotations
 
@@ -188,8 +188,9 @@ def fit(data, out: str, epochs: int = 200, lr: float = 1e-3, lr_decay: float = 5
     seed: the shuffle's (and, without initial_checkpoint, the initialisation's).  on_step: called after every step with a dict
     (epoch, step, loss, gain_loss, vad_loss, lr: the rate the step was taken with, states: the detached states carried on,
     sparsified).  log: called with one line per epoch holding the three means (None: silent).
-    gru: "torch" (nn.GRU) or "native": the three GRUs' recurrences, forward and backward, on librnnoise_amd_gru.so (FloatNet's
-    gru_impl; the device only) -- the same parameters and checkpoints either way.
+    gru: "torch" (nn.GRU), "native": the three GRUs' recurrences, forward and backward, on librnnoise_amd_gru.so, or "stack": the
+    three layers on librnnoise_amd_gru_stack.so (FloatNet's gru_impl; the device only) -- the same parameters and checkpoints either
+    way.
     -> a list with one dict per epoch: epoch, loss, gain_loss, vad_loss (the means over the epoch's batches, as the reference prints
     them), checkpoint (the file)."""
     import torch

@@ -19,6 +19,15 @@ measures the native GRUs instead, beside torch's in the same jo
 forward and backward with FloatNet's gru_impl "torch" and "native"; and one layer on fixed inputs -- nn.GRU forward and backward
 against the forward and backward calls of librnnoise_amd_gru.so, with the per-step time of the latter.  FILE defaults to
 profiles/train_step_gru.txt; profiles/train_step.txt is not touched.
+
+  python tools/train_bench.py --gru stack [--rows N] [--frames T] [--rounds R] [--warmup W] [--out FILE] [--once]
+
+measures the diagonal stack beside the per-layer native path in the same job, the two alternating round by round:
+the network's forward and backward with gru_impl "native" and "stack"; the three recurrences alone on fixed inputs -- the native
+path's three forward and three backward calls with the two projections between them, against the stack's one forward and one backward
+call, with the time per launch over the T + 2 launches; and the torch-side weight gradients of both.  It states whether every stack
+round lies below every native round.  FILE defaults to profiles/train_step_gru_stack.txt.  --once makes one forward and one backward
+call of the stack and exits: the program for a kernel trace.
 """
 import argparse
 import os
@@ -126,6 +135,152 @@ def gru_bench(a):
     print(text, end="")
 
 
+def stack_bench(a):
+    """--gru stack: the network and the three recurrences, librnnoise_amd_gru.so layer by layer and librnnoise_amd_gru_stack.so
+    alternating in one job"""
+    import torch
+    from torch.nn import functional as F
+
+    from rnnoise_amd import gru_native, gru_stack, train
+    dev = torch.device("cuda", 0)
+    N, T, K, H = a.rows, a.frames, a.frames - 4, 384
+    out = a.out or os.path.join(ROOT, "profiles", "train_step_gru_stack.txt")
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def alternate(cases):
+        ms = {k: [] for k in cases}
+        for r in range(a.warmup + a.rounds):
+            for k, fn in cases.items():
+                t = once(fn)
+                if r >= a.warmup:
+                    ms[k].append(t)
+        return ms
+
+    # ---- the three recurrences on fixed inputs ----
+    gen = torch.Generator().manual_seed(1)
+    grus = [torch.nn.GRU(H, H, batch_first=True).to(dev) for _ in range(3)]
+    w_ih, b_ih = [None] + [g.weight_ih_l0.detach() for g in grus[1:]], [None] + [g.bias_ih_l0.detach() for g in grus[1:]]
+    w_hh, b_hh = [g.weight_hh_l0.detach() for g in grus], [g.bias_hh_l0.detach() for g in grus]
+    gi0 = torch.randn(N, K, 3 * H, generator=gen).to(dev)
+    dcat = torch.randn(N, K, 4 * H, generator=gen).to(dev)
+    dy = [dcat[:, :, (l + 1) * H:(l + 2) * H] for l in range(3)]
+    kept = {}
+
+    def stack_forward():
+        kept["ys"], kept["saved"] = gru_stack.stack_forward(gi0, w_ih, b_ih, w_hh, b_hh)
+
+    def stack_backward():
+        kept["dgi"], kept["dgh"], _ = gru_stack.stack_backward(dy, kept["ys"], kept["saved"], w_ih, w_hh)
+
+    if a.once:
+        stack_forward()
+        stack_backward()
+        torch.cuda.synchronize()
+        print(f"one forward and one backward call of librnnoise_amd_gru_stack.so, {N} rows x {K} steps: {K + 2} launches each")
+        return
+
+    def native_forward():
+        gi, kept["nys"], kept["nsaved"] = gi0, [], []
+        for l in range(3):
+            if l:
+                gi = F.linear(kept["nys"][l - 1], w_ih[l], b_ih[l])
+            y, s = gru_native.sequence_forward(gi, w_hh[l], b_hh[l], None)
+            kept["nys"].append(y)
+            kept["nsaved"].append(s)
+
+    def native_backward():
+        kept["ndgh"], kept["ndgi"], dx = [None] * 3, [None] * 3, None
+        for l in (2, 1, 0):
+            d = dy[l] if dx is None else dy[l] + dx
+            kept["ndgi"][l], kept["ndgh"][l], _ = gru_native.sequence_backward(d, kept["nys"][l], kept["nsaved"][l], w_hh[l], None, None)
+            if l:
+                dx = kept["ndgi"][l] @ w_ih[l]
+
+    def stack_weight_grads(per_step):
+        def fn():
+            for l in range(3):
+                gru_native.weight_grads(kept["dgh"][l], kept["ys"][l], None)
+                if l:
+                    gru_stack.input_weight_grads(kept["dgi"][l], kept["ys"][l - 1], per_step=per_step)
+        return fn
+
+    def native_weight_grads():
+        for l in range(3):
+            gru_native.weight_grads(kept["ndgh"][l], kept["nys"][l], None)
+            if l:  # what F.linear's autograd does: one product
+                kept["ndgi"][l].reshape(-1, 3 * H).t() @ kept["nys"][l - 1].reshape(-1, H)
+                kept["ndgi"][l].sum((0, 1))
+
+    fmt = lambda ms: f"{statistics.median(ms):9.3f} ms  ({min(ms):.3f} .. {max(ms):.3f})"
+
+    def verdict(name, native, stack):
+        """the ratio of the medians beside both spreads; "faster" only where every stack round lies below every native round, or the
+        gap of the medians exceeds the larger spread"""
+        mn, mk = statistics.median(native), statistics.median(stack)
+        spread = max(max(native) - min(native), max(stack) - min(stack))
+        if max(stack) < min(native) or mn - mk > spread:
+            word = "stack faster"
+        elif max(native) < min(stack) or mk - mn > spread:
+            word = "stack slower"
+        else:
+            word = "no difference beyond the spread"
+        return (f"  {name}: native / stack = {mn / mk:.3f} (medians {mn:.3f} and {mk:.3f} ms; spread native {max(native) - min(native):.3f}, "
+                f"stack {max(stack) - min(stack):.3f} ms): {word}")
+
+    lines = [f"# tools/train_bench.py --gru stack --rows {N} --frames {T} --rounds {a.rounds} --warmup {a.warmup}; "
+             f"{torch.cuda.get_device_name(0)}; median of {a.rounds} (min .. max), device events, the implementations alternating"]
+    rec = alternate({"native: 3 forward calls + 2 projections": native_forward, "native: 3 backward calls + 2 dx products": native_backward,
+                     "stack: the forward call": stack_forward, "stack: the backward call": stack_backward,
+                     "native: weight gradients (torch)": native_weight_grads,
+                     "stack: weight gradients, dW_ih per step": stack_weight_grads(True),
+                     "stack: weight gradients, dW_ih one product": stack_weight_grads(False)})
+
+    # ---- the network: forward, and backward of a fixed linear functional of its outputs ----
+    features = torch.randn(N, T, 65, generator=gen).to(dev)
+    A, B = torch.randn(N, K, 32, generator=gen).to(dev), torch.randn(N, K, 1, generator=gen).to(dev)
+    net = train.new_network(seed=1).to(dev).train()
+    held = {}
+
+    def forward(impl):
+        def fn():
+            net.gru_impl = impl
+            net.zero_grad()
+            g, v = net.forward_sequence(features)
+            held[impl] = (g * A).sum() + (v * B).sum()
+        return fn
+
+    def backward(impl):
+        return lambda: held.pop(impl).backward()
+    ms = alternate({"native forward": forward("native"), "native backward": backward("native"), "stack forward": forward("stack"),
+                    "stack backward": backward("stack")})
+    lines.append(f"network forward and backward, batch {N} x {T} frames, cond_size 128, gru_size {H}:")
+    for k in ms:
+        lines.append(f"  {k:44s} {fmt(ms[k])}")
+    lines.append(verdict("network forward", ms["native forward"], ms["stack forward"]))
+    lines.append(verdict("network backward", ms["native backward"], ms["stack backward"]))
+    both = lambda impl: [f + b for f, b in zip(ms[impl + " forward"], ms[impl + " backward"])]
+    lines.append(verdict("network forward + backward", both("native"), both("stack")))
+    lines.append(f"the three recurrences alone, {N} rows x {K} steps, hidden {H}, fixed inputs (native: {3 * K} launches each way and the "
+                 f"torch products between the layers; stack: {K + 2} launches each way):")
+    for k in rec:
+        lines.append(f"  {k:44s} {fmt(rec[k])}")
+    for k in ("stack: the forward call", "stack: the backward call"):
+        lines.append(f"  {k + ', per launch':44s} {1e3 * statistics.median(rec[k]) / (K + 2):9.2f} us")
+    lines.append(verdict("recurrences forward", rec["native: 3 forward calls + 2 projections"], rec["stack: the forward call"]))
+    lines.append(verdict("recurrences backward", rec["native: 3 backward calls + 2 dx products"], rec["stack: the backward call"]))
+    text = "\n".join(lines) + "\n"
+    with open(out, "w") as f:
+        f.write(text)
+    print(text, end="")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=128)
@@ -133,13 +288,16 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--gru", choices=("torch", "native"), default="torch")
+    ap.add_argument("--gru", choices=("torch", "native", "stack"), default="torch")
+    ap.add_argument("--once", action="store_true", help="with --gru stack: one forward and one backward call, nothing measured")
     a = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         sys.exit("train_bench: no GPU: nothing measured")
     if a.gru == "native":
         return gru_bench(a)
+    if a.gru == "stack":
+        return stack_bench(a)
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "train_step.txt")
     from rnnoise_amd import synth, train, train_loss
