@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from . import capi
+from . import _sidelib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librnnoise_amd_score.so")
@@ -45,22 +45,8 @@ PROTOTYPES = {
 }
 EXPORTS = list(PROTOTYPES)
 
-_lib = None
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        capi._share_hip_runtime_with_torch()  # (one HIP runtime per process, as for the product library)
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = L
-    return _lib
+    return _sidelib.load(LIB_PATH, PROTOTYPES)
 
 
 def layout_frames(n_rows: int):

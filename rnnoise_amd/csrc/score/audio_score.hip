@@ -28,6 +28,9 @@ static RN_AS_FN void rn_as_exchange(double (&acc)[RN_AS_LANES][RNNOISE_AMD_SCORE
 }
 #endif
 
+#define RN_SIDE_LIB "rnnoise_amd_score"
+#include "../side_host.h"
+
 #define RN_AS_FRAME RNNOISE_AMD_SCORE_FRAME
 #define RN_AS_SLOTS RNNOISE_AMD_SCORE_SLOTS
 #define RN_AS_WAVE 64
@@ -158,7 +161,7 @@ static RN_AS_FN void rn_as_wave(const RnAsArgs &a, int row, int lane0) {
 namespace {
 // last float of a plane that a call over frames [0, T) of n_rows rows may name, or false where that is beyond LONG_MAX
 bool plane_ok(const RNNoiseAudioPlane &p, int n_rows, long long T) {
-  if (!p.p || (reinterpret_cast<size_t>(p.p) & 15)) return false;
+  if (!p.p || !aligned16(p.p)) return false;
   if (p.frame_stride < RN_AS_FRAME || p.row_stride < RN_AS_FRAME || (p.frame_stride & 3) || (p.row_stride & 3)) return false;
   const __int128 end = (__int128)(T > 0 ? T - 1 : 0) * p.frame_stride + (__int128)(n_rows - 1) * p.row_stride + RN_AS_FRAME;
   return end <= (__int128)LONG_MAX;
@@ -210,34 +213,6 @@ extern "C" __global__ __launch_bounds__(RN_AS_WAVES * RN_AS_WAVE) void rn_audio_
 }
 
 namespace {
-#define HIP_OK(expr)                                                                                                        \
-  do {                                                                                                                      \
-    hipError_t e_ = (expr);                                                                                                 \
-    if (e_ != hipSuccess) {                                                                                                 \
-      fprintf(stderr, "[rnnoise_amd_score] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__);      \
-      return -1;                                                                                                            \
-    }                                                                                                                       \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = (prev == device) || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;  // nothing to restore
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-#define ON_DEVICE(dev)                                                                                        \
-  DeviceGuard guard_(dev);                                                                                    \
-  if (!guard_.ok) {                                                                                           \
-    fprintf(stderr, "[rnnoise_amd_score] cannot select HIP device %d (%s:%d)\n", (dev), __FILE__, __LINE__);   \
-    return -1;                                                                                                \
-  }
-
 struct DevBuf {
   void *p = nullptr;
   ~DevBuf() {

@@ -24,6 +24,8 @@
 #define RN_TL_FN __device__ __forceinline__
 #endif
 #include "../eval_terms.h"
+#define RN_SIDE_LIB "rnnoise_amd_train"
+#include "../side_host.h"
 
 #define RN_TL_REC RNNOISE_AMD_TRAIN_RECORD
 #define RN_TL_TARGETS (RN_TL_REC - RN_NB_BANDS - 1)  // the first gain target of a record
@@ -114,18 +116,6 @@ static RN_TL_FN void rn_tl_row_sums(const RnTlArgs &a, int row) {
 }
 
 namespace {
-// whether n_frames x n_rows slots of M floats, slot (f, s) at f * frame_stride + s * row_stride, are disjoint in one of the two
-// orders the product's layouts know, and end within LONG_MAX floats
-bool slots_fit(long frame_stride, long row_stride, int M, int n_rows, long long n_frames) {
-  if (frame_stride <= 0 || row_stride <= 0) return false;
-  if (n_frames <= 0) return true;
-  const __int128 fs = frame_stride, rs = row_stride;
-  if ((n_frames - 1) * fs + (n_rows - 1) * rs + M > (__int128)LONG_MAX) return false;
-  const bool rows_in_frame = rs >= M && fs >= n_rows * rs;
-  const bool frames_in_row = fs >= M && rs >= n_frames * fs;
-  return rows_in_frame || frames_in_row;
-}
-
 bool call_ok(const RNNoiseTrainLoss *c) {
   if (!c || !c->records || !c->gains || !c->vad) return false;
   if (c->n_rows < 1 || c->t0 < 0 || c->n_frames < 0 || c->first < 0) return false;
@@ -133,9 +123,9 @@ bool call_ok(const RNNoiseTrainLoss *c) {
   if (T > INT_MAX) return false;
   if (!(c->gamma > 0.0) || !std::isfinite(c->gamma) || !std::isfinite(c->w_gain) || !std::isfinite(c->w_vad)) return false;
   if ((c->grad_gains == nullptr) != (c->grad_vad == nullptr)) return false;
-  return slots_fit(c->rec_frame_stride, c->rec_row_stride, RN_TL_REC, c->n_rows, T - 1) &&
-         slots_fit(c->gain_frame_stride, c->gain_row_stride, RN_NB_BANDS, c->n_rows, c->n_frames) &&
-         slots_fit(c->vad_frame_stride, c->vad_row_stride, 1, c->n_rows, c->n_frames);
+  return slots_fit(c->rec_frame_stride, c->rec_row_stride, RN_TL_REC, c->n_rows, T - 1, 1) &&
+         slots_fit(c->gain_frame_stride, c->gain_row_stride, RN_NB_BANDS, c->n_rows, c->n_frames, 1) &&
+         slots_fit(c->vad_frame_stride, c->vad_row_stride, 1, c->n_rows, c->n_frames, 1);
 }
 }  // namespace
 
@@ -175,34 +165,6 @@ extern "C" __global__ __launch_bounds__(WAVE) void rn_train_loss_sums_kernel(RnT
 }
 
 namespace {
-#define HIP_OK(expr)                                                                                                        \
-  do {                                                                                                                      \
-    hipError_t e_ = (expr);                                                                                                 \
-    if (e_ != hipSuccess) {                                                                                                 \
-      fprintf(stderr, "[rnnoise_amd_train] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__);      \
-      return -1;                                                                                                            \
-    }                                                                                                                       \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = (prev == device) || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;  // nothing to restore
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-#define ON_DEVICE(dev)                                                                                        \
-  DeviceGuard guard_(dev);                                                                                    \
-  if (!guard_.ok) {                                                                                           \
-    fprintf(stderr, "[rnnoise_amd_train] cannot select HIP device %d (%s:%d)\n", (dev), __FILE__, __LINE__);   \
-    return -1;                                                                                                \
-  }
-
 struct DevBuf {
   void *p = nullptr;
   ~DevBuf() {

@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from . import capi
+from . import _sidelib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librnnoise_amd_gru.so")
@@ -56,22 +56,8 @@ PROTOTYPES = {
 }
 EXPORTS = list(PROTOTYPES)
 
-_lib = None
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        capi._share_hip_runtime_with_torch()  # (one HIP runtime per process, as for the product library)
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = L
-    return _lib
+    return _sidelib.load(LIB_PATH, PROTOTYPES)
 
 
 def make_seq(gi, w_hh, b_hh, y, n_rows, n_frames, hidden, h0=0) -> Seq:
@@ -104,17 +90,26 @@ def check(call) -> bool:
 def workspace(n_rows: int, n_frames: int, hidden: int):
     """(saved_floats, scratch_floats) of a call of these sizes (rnnoise_amd_gru_workspace): T N 4H and 2 N H.  ValueError where the
     library refuses the sizes."""
-    c = Seq()
-    c.n_rows, c.n_frames, c.hidden = int(n_rows), int(n_frames), int(hidden)
-    saved, scratch = C.c_size_t(0), C.c_size_t(0)
-    if lib().rnnoise_amd_gru_workspace(C.byref(c), C.byref(saved), C.byref(scratch)):
-        raise ValueError(refusal(n_rows, n_frames, hidden))
-    return saved.value, scratch.value
+    return _workspace("librnnoise_amd_gru.so", lib().rnnoise_amd_gru_workspace, Seq, n_rows, n_frames, hidden)
 
 
 def refusal(n_rows, n_frames, hidden) -> str:
     """why librnnoise_amd_gru.so does not take these sizes (include/rnnoise_amd_gru.h)"""
-    return (f"librnnoise_amd_gru.so takes a hidden size that is a multiple of {TILE} from {MIN_HIDDEN} to {MAX_HIDDEN}, 1 to {MAX_ROWS} "
+    return _refusal("librnnoise_amd_gru.so", n_rows, n_frames, hidden)
+
+
+def _workspace(library, symbol, struct, n_rows, n_frames, hidden):
+    """the workspace call `symbol` of `library` on a `struct` of these sizes (the gru stack library's too: the limits are the same)"""
+    c = struct()
+    c.n_rows, c.n_frames, c.hidden = int(n_rows), int(n_frames), int(hidden)
+    saved, scratch = C.c_size_t(0), C.c_size_t(0)
+    if symbol(C.byref(c), C.byref(saved), C.byref(scratch)):
+        raise ValueError(_refusal(library, n_rows, n_frames, hidden))
+    return saved.value, scratch.value
+
+
+def _refusal(library, n_rows, n_frames, hidden) -> str:
+    return (f"{library} takes a hidden size that is a multiple of {TILE} from {MIN_HIDDEN} to {MAX_HIDDEN}, 1 to {MAX_ROWS} "
             f"rows and 0 or more steps: not hidden {hidden}, {n_rows} rows, {n_frames} steps")
 
 

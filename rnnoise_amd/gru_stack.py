@@ -20,7 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from . import capi, gru_native
+from . import _sidelib, gru_native
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librnnoise_amd_gru_stack.so")
@@ -64,22 +64,8 @@ PROTOTYPES = {
 }
 EXPORTS = list(PROTOTYPES)
 
-_lib = None
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        capi._share_hip_runtime_with_torch()  # (one HIP runtime per process, as for the product library)
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = L
-    return _lib
+    return _sidelib.load(LIB_PATH, PROTOTYPES)
 
 
 def _ptrs(values):
@@ -128,18 +114,12 @@ def check(call) -> bool:
 def workspace(n_rows: int, n_frames: int, hidden: int):
     """(saved_floats, scratch_floats) of a call of these sizes (rnnoise_amd_gru_stack_workspace): 3 T N 4H and (3 + 2) 2 N H.
     ValueError where the library refuses the sizes."""
-    c = Stack()
-    c.n_rows, c.n_frames, c.hidden = int(n_rows), int(n_frames), int(hidden)
-    saved, scratch = C.c_size_t(0), C.c_size_t(0)
-    if lib().rnnoise_amd_gru_stack_workspace(C.byref(c), C.byref(saved), C.byref(scratch)):
-        raise ValueError(refusal(n_rows, n_frames, hidden))
-    return saved.value, scratch.value
+    return gru_native._workspace("librnnoise_amd_gru_stack.so", lib().rnnoise_amd_gru_stack_workspace, Stack, n_rows, n_frames, hidden)
 
 
 def refusal(n_rows, n_frames, hidden) -> str:
-    """why librnnoise_amd_gru_stack.so does not take these sizes (include/rnnoise_amd_gru_stack.h)"""
-    return (f"librnnoise_amd_gru_stack.so takes a hidden size that is a multiple of {TILE} from {MIN_HIDDEN} to {MAX_HIDDEN}, 1 to "
-            f"{MAX_ROWS} rows and 0 or more steps: not hidden {hidden}, {n_rows} rows, {n_frames} steps")
+    """why librnnoise_amd_gru_stack.so does not take these sizes (include/rnnoise_amd_gru_stack.h: the gru library's limits)"""
+    return gru_native._refusal("librnnoise_amd_gru_stack.so", n_rows, n_frames, hidden)
 
 
 def forward_device(call: Stack, d_saved: int, device: int = 0, stream: int = 0) -> None:

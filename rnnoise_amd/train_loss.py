@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from . import capi
+from . import _sidelib, capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librnnoise_amd_train.so")
@@ -44,22 +44,8 @@ PROTOTYPES = {
 }
 EXPORTS = list(PROTOTYPES)
 
-_lib = None
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        capi._share_hip_runtime_with_torch()  # (one HIP runtime per process, as for the product library)
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = L
-    return _lib
+    return _sidelib.load(LIB_PATH, PROTOTYPES)
 
 
 def make_call(records, gains, vad, n_rows, t0, n_frames, first=4, gamma=.25, w_gain=0.0, w_vad=0.0, grad_gains=0, grad_vad=0) -> Call:

@@ -1,15 +1,21 @@
-// gru_stack_main.cpp -- the host half of rnnoise_amd/csrc/gru_stack/gru_stack.hip as a plain C++ program (TEST INFRASTRUCTURE, built
-// with the address and undefined-behaviour sanitizers by tests/test_gru_stack_cpu.py): the two device calls run with every launch
-// handed to a model of the memory instead of a device.  The model keeps, per float of every buffer, what was last written there
+// gru_stack_main.cpp -- the host halves of rnnoise_amd/csrc/gru_stack/gru_stack.hip and rnnoise_amd/csrc/gru/gru_seq.hip as a plain
+// C++ program (TEST INFRASTRUCTURE, built with the address and undefined-behaviour sanitizers by tests/test_gru_stack_cpu.py): the
+// device calls of both run with every launch handed to a model of the memory instead of a device.  The model keeps, per float of every buffer, what was last written there
 // (which layer, which step, which kind) and in which launch, and checks for every launch of the diagonal schedule that
 //   - the grid and the layers of the launch are those of the header (launch s: layer l at step s - l; backward the mirror image),
 //   - every float a layer's workgroups read holds exactly the value the formulas want (y_l[t-1], y_{l-1}[t], dh of step t + 1,
 //     dx_{l+1}[t], saved[l][t], or an input) and was written by an EARLIER launch,
 //   - no float is written twice in a launch, or read and written in the same launch (the kernel boundary is the only ordering),
 //   - every address lies inside a buffer of the documented size (the work buffers are allocated at exactly the workspace call's),
-// and after a call that everything it promises is written.  Prints "ok <cases>" and exits 0, or the first violation and exits 1.
+// and after a call that everything it promises is written.  The single-layer calls run on the same shapes as a stack of one layer
+// (layer 0): T launches each way of (H/16) x ceil(N/16) workgroups, step t reads the y[t-1] an earlier launch wrote, dh_out is never
+// dh_in, the halves of the scratch alternate and the last step writes dh0.  Prints "ok <cases>" and exits 0, or the first violation
+// and exits 1.
 #define RN_STK_HOST 1
+#define RN_GRU_HOST 1
 #include "gru_stack.hip"
+#undef RN_SIDE_LIB  // (each unit names itself for side_host.h's messages)
+#include "gru_seq.hip"
 
 #include <stdlib.h>
 #include <string.h>
@@ -84,6 +90,9 @@ void want(bool ok, const char *what) {
 const RNNoiseGruStack *g_fwd = nullptr;
 const RNNoiseGruStackGrad *g_bwd = nullptr;
 const float *g_saved = nullptr;
+const RNNoiseGruSeq *g_seq_fwd = nullptr;
+const RNNoiseGruSeqGrad *g_seq_bwd = nullptr;
+const float *g_seq_scratch = nullptr, *g_seq_dh = nullptr;  // the scratch, and what the launch before left as dh
 }  // namespace
 
 static void check_grid(dim3 grid, dim3 block, int layers, int N, int H) {
@@ -189,6 +198,73 @@ static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t, const RnStack
   g_call_launches++, g_launch++;
 }
 
+// the step's y[t-1] (h0 at step 0) of a single layer
+static void reads_prev(const float *prev, long long prev_rs, const float *h0, int t, int N, int H) {
+  if (t == 0) {
+    want(prev == h0, "step 0 reads h0");
+    if (prev)
+      for (int r = 0; r < N; r++) reads(prev + r * prev_rs, H, INPUT, 0, 0, "h0");
+  } else {
+    for (int r = 0; r < N; r++) reads(prev + r * prev_rs, H, Y, 0, t - 1, "y[t-1]");
+  }
+}
+
+static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t, const RnGruStep &a) {
+  const RNNoiseGruSeq &c = *g_seq_fwd;
+  const int t = g_call_launches, T = c.n_frames, N = c.n_rows, H = c.hidden;
+  want(t < T, "more than T launches");
+  want(a.n_rows == N && a.H == H, "the sizes");
+  check_grid(grid, block, 1, N, H);
+  want(a.y == c.y + (long long)t * c.y_frame_stride && a.y_rs == c.y_row_stride, "y is not the step's slot");
+  want(a.w_hh == c.w_hh && a.b_hh == c.b_hh, "the recurrent weights are not the call's");
+  want(a.saved == g_saved + (long long)t * N * 4 * H, "saved is not [t]");
+  for (int r = 0; r < N; r++) {
+    writes(a.y + r * a.y_rs, H, Y, 0, t, "y");
+    writes(a.saved + (long long)r * 4 * H, 4 * H, SAVED, 0, t, "saved");
+  }
+  want(a.gi == c.gi + (long long)t * c.gi_frame_stride && a.in_rs == c.gi_row_stride, "gi is not the step's slot");
+  for (int r = 0; r < N; r++) reads(a.gi + r * a.in_rs, 3 * H, INPUT, 0, 0, "gi");
+  reads_prev(a.prev, a.prev_rs, c.h0, t, N, H);
+  g_call_launches++, g_launch++;
+}
+
+static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t, const RnGruGradStep &a) {
+  const RNNoiseGruSeqGrad &c = *g_seq_bwd;
+  const int s = g_call_launches, T = c.n_frames, N = c.n_rows, H = c.hidden, t = T - 1 - s;
+  want(s < T, "more than T launches");
+  want(a.n_rows == N && a.H == H, "the sizes");
+  check_grid(grid, block, 1, N, H);
+  want(a.dh_out != nullptr && a.dh_out != a.dh_in, "dh_out is never dh_in");
+  if (t == 0)
+    want(a.dh_out == c.dh0, "the last step writes dh0");
+  else
+    want(a.dh_out == g_seq_scratch + (long long)(s & 1) * N * H, "the halves of the scratch alternate");
+  want(a.dgh == c.dgh + (long long)t * N * 3 * H, "dgh is not [t]");
+  want(a.dgi == c.dgi + (long long)t * c.dgi_frame_stride && a.dgi_rs == c.dgi_row_stride, "dgi is not the step's slot");
+  for (int r = 0; r < N; r++) {
+    writes(a.dgi + r * a.dgi_rs, 3 * H, DGI, 0, t, "dgi");
+    writes(a.dgh + (long long)r * 3 * H, 3 * H, DGH, 0, t, "dgh");
+    writes(a.dh_out + (long long)r * H, H, DH, 0, t, "dh");
+  }
+  want(a.w_hh == c.w_hh, "the weights are not the call's");
+  want(a.saved == g_saved + (long long)t * N * 4 * H, "saved is not [t]");
+  want(a.dy == c.dy + (long long)t * c.dy_frame_stride && a.dy_rs == c.dy_row_stride, "dy is not the step's slot");
+  for (int r = 0; r < N; r++) {
+    reads(a.saved + (long long)r * 4 * H, 4 * H, SAVED, 0, t, "saved");
+    reads(a.dy + r * a.dy_rs, H, INPUT, 0, 0, "dy");
+  }
+  want(a.dh_in == g_seq_dh, "dh_in is what the launch before wrote (dhT at the first step)");
+  if (t == T - 1) {
+    if (a.dh_in)
+      for (int r = 0; r < N; r++) reads(a.dh_in + (long long)r * H, H, INPUT, 0, 0, "dhT");
+  } else {
+    for (int r = 0; r < N; r++) reads(a.dh_in + (long long)r * H, H, DH, 0, t + 1, "dh of the step after");
+  }
+  reads_prev(a.prev, a.prev_rs, c.h0, t, N, H);
+  g_seq_dh = a.dh_out;
+  g_call_launches++, g_launch++;
+}
+
 namespace {
 void all_written(const float *p, long fs, long rs, int T, int N, long M, Kind kind, int layer, const char *what) {
   for (int t = 0; t < T; t++)
@@ -268,6 +344,70 @@ int run_case(int N, int T, int H, bool states, bool batch_first) {
   for (Buf *b : own) delete b;
   return 1;
 }
+
+// the single-layer library on the same shapes
+int run_seq_case(int N, int T, int H, bool states, bool batch_first) {
+  g_case = "single layer, N " + std::to_string(N) + " T " + std::to_string(T) + " H " + std::to_string(H) + (states ? ", states" : ", no states") +
+           (batch_first ? ", a slice of a batch-first concatenation" : ", frame-major buffers");
+  g_launch = 0;
+  const long NH = (long)N * H, Tn = T ? T : 1;
+  size_t n_saved = 0, n_scratch = 0;
+  RNNoiseGruSeq f{};
+  f.n_rows = N, f.n_frames = T, f.hidden = H;
+  want(rnnoise_amd_gru_workspace(&f, &n_saved, &n_scratch) == 0, "the workspace call");
+  want(n_saved == (size_t)T * N * 4 * H && n_scratch == (size_t)2 * N * H, "the workspace formulas");
+  std::vector<Buf *> own;
+  auto buf = [&](const char *name, size_t floats, bool input) {
+    own.push_back(new Buf(name, floats ? floats : 4, input));
+    g_bufs.push_back(own.back());
+    return own.back()->mem;
+  };
+  float *saved = buf("saved", n_saved, false), *scratch = buf("scratch", n_scratch, false);
+  f.gi = buf("gi", Tn * NH * 3, true), f.gi_frame_stride = batch_first ? 3 * H : 3 * NH, f.gi_row_stride = batch_first ? (long)Tn * 3 * H : 3 * H;
+  f.w_hh = buf("w_hh", 3L * H * H, true), f.b_hh = buf("b_hh", 3 * H, true);
+  RNNoiseGruSeqGrad g{};
+  g.n_rows = N, g.n_frames = T, g.hidden = H;
+  if (states) f.h0 = buf("h0", NH, true), g.dhT = buf("dhT", NH, true);
+  if (batch_first) {  // slice 1 of a [N][T][4H] concatenation
+    f.y = buf("y (concatenation)", Tn * NH * 4, false) + H, f.y_frame_stride = 4 * H, f.y_row_stride = (long)Tn * 4 * H;
+    g.dy = buf("dy (concatenation)", Tn * NH * 4, true) + H;
+  } else {
+    f.y = buf("y", Tn * NH, false), f.y_frame_stride = NH, f.y_row_stride = H;
+    g.dy = buf("dy", Tn * NH, true);
+  }
+  g.dy_frame_stride = g.y_frame_stride = f.y_frame_stride, g.dy_row_stride = g.y_row_stride = f.y_row_stride;
+  g.y = f.y, g.w_hh = f.w_hh, g.h0 = f.h0;
+  g.dgi = buf("dgi", Tn * NH * 3, false), g.dgi_frame_stride = f.gi_frame_stride, g.dgi_row_stride = f.gi_row_stride;
+  g.dgh = buf("dgh", Tn * NH * 3, false), g.dh0 = buf("dh0", NH, false);
+  want(rnnoise_amd_gru_check(&f) == 0 && rnnoise_amd_gru_grad_check(&g) == 0, "the checks accept the case");
+
+  g_seq_fwd = &f, g_saved = saved, g_call_launches = 0;
+  want(rnnoise_amd_gru_forward_device(1, &f, saved, nullptr) == 0, "the forward call");
+  want(g_call_launches == T, "forward: T launches");
+  want(g_shim_device == 0, "the device is restored");
+  all_written(f.y, f.y_frame_stride, f.y_row_stride, T, N, H, Y, 0, "y");
+  all_written(saved, NH * 4, 4 * H, T, N, 4 * H, SAVED, 0, "saved");
+  g_seq_bwd = &g, g_seq_scratch = scratch, g_seq_dh = g.dhT, g_call_launches = 0;
+  want(rnnoise_amd_gru_backward_device(1, &g, saved, scratch, nullptr) == 0, "the backward call");
+  want(g_call_launches == T, "backward: T launches");
+  all_written(g.dgi, g.dgi_frame_stride, g.dgi_row_stride, T, N, 3 * H, DGI, 0, "dgi");
+  all_written(g.dgh, NH * 3, 3 * H, T, N, 3 * H, DGH, 0, "dgh");
+  if (T) all_written(g.dh0, 0, H, 1, N, H, DH, 0, "dh0");
+  // refused and unreachable: nothing is launched
+  g_call_launches = 0;
+  want(rnnoise_amd_gru_forward_device(2, &f, saved, nullptr) == (T ? -1 : 0), "a device that cannot be selected");
+  RNNoiseGruSeq bad = f;
+  bad.hidden = H + 8;
+  want(rnnoise_amd_gru_forward_device(0, &bad, saved, nullptr) == -1 && g_call_launches == 0, "a refused call launches nothing");
+  if (states) {
+    RNNoiseGruSeqGrad on = g;
+    on.dhT = g.dh0;
+    want(rnnoise_amd_gru_grad_check(&on) == -1, "dh0 on dhT is refused");
+  }
+  g_bufs.clear();
+  for (Buf *b : own) delete b;
+  return 1;
+}
 }  // namespace
 
 int main() {
@@ -276,7 +416,10 @@ int main() {
     for (int N : {1, 17})
       for (int T : {0, 1, 2, 3, 4, 7})
         for (int states = 0; states < 2; states++)
-          for (int batch_first = 0; batch_first < 2; batch_first++) cases += run_case(N, T, H, states != 0, batch_first != 0);
+          for (int batch_first = 0; batch_first < 2; batch_first++) {
+            cases += run_case(N, T, H, states != 0, batch_first != 0);
+            cases += run_seq_case(N, T, H, states != 0, batch_first != 0);
+          }
   printf("ok %d\n", cases);
   return 0;
 }

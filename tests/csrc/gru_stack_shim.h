@@ -1,7 +1,9 @@
-// gru_stack_shim.h -- what the host half of rnnoise_amd/csrc/gru_stack/gru_stack.hip needs to compile as plain C++ with RN_STK_HOST
-// (TEST INFRASTRUCTURE; its own, beside tests/csrc/train_loss_shim.h): the few HIP names the two device calls use, and a launch that
-// hands the kernel's argument block to the test program instead of a device.
+// gru_stack_shim.h -- what the host halves of rnnoise_amd/csrc/gru_stack/gru_stack.hip (RN_STK_HOST) and rnnoise_amd/csrc/gru/gru_seq.hip
+// (RN_GRU_HOST) need to compile as plain C++ (TEST INFRASTRUCTURE; its own, beside tests/csrc/train_loss_shim.h): the few HIP names
+// the device calls and rnnoise_amd/csrc/side_host.h's device guard use, and a launch that hands the kernel's argument block to the
+// test program instead of a device.
 #pragma once
+#define RN_SIDE_HIP_SHIM 1
 
 struct dim3 {
   unsigned x, y, z;
@@ -19,7 +21,11 @@ static inline const char *hipGetErrorString(hipError_t) { return "shim error"; }
 
 struct RnStackStep;
 struct RnStackGradStep;
-// (defined in gru_stack_main.cpp, behind the unit's own text)
+struct RnGruStep;
+struct RnGruGradStep;
+// (defined in gru_stack_main.cpp, behind the units' own text)
 static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t stream, const RnStackStep &a);
 static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t stream, const RnStackGradStep &a);
+static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t stream, const RnGruStep &a);
+static void rn_stk_host_launch(dim3 grid, dim3 block, hipStream_t stream, const RnGruGradStep &a);
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, arg) rn_stk_host_launch((grid), (block), (stream), (arg))

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import train_loss_ref as R
+from gru_cases import _declarations, _fields, _injected_loss, assert_shares_only_the_two_headers
 from rnnoise_amd import capi, float_net, train
 from rnnoise_amd import gru_native as G
 
@@ -62,28 +63,8 @@ def test_reference_formulas_against_nn_gru_in_float64(N, T, H, with_h0, with_dhT
 
 
 # ---- the surface ----
-def _declarations():
-    src = open(HEADER).read()
-    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-    return [(" ".join(ret.split()), name, " ".join(params.split()))
-            for ret, name, params in re.findall(r"RNNOISE_EXPORT\s+([\w\s\*]+?)\b(rnnoise_\w+)\s*\(([^()]*)\)\s*;", src)]
-
-
-def _fields(struct):
-    src = open(HEADER).read()
-    body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", src, re.S)[1]
-    fields = []
-    for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";"):
-        if decl.strip():
-            kind = re.match(r"\s*(const float|float|long|int)\b", decl)[1]
-            for f in decl.strip()[len(kind):].split(","):
-                f = f.strip()
-                fields.append((f.lstrip("*"), C.c_void_p if f.startswith("*") else {"long": C.c_long, "int": C.c_int}[kind]))
-    return fields
-
-
 def test_prototype_table_matches_the_header():
-    decl = _declarations()
+    decl = _declarations(HEADER)
     assert [d[1] for d in decl] == list(G.PROTOTYPES) == G.EXPORTS and len(decl) == 5
     for ret, name, params in decl:
         restype, argtypes = G.PROTOTYPES[name]
@@ -93,8 +74,8 @@ def test_prototype_table_matches_the_header():
     for macro, value in (("TILE", G.TILE), ("MIN_HIDDEN", G.MIN_HIDDEN), ("MAX_HIDDEN", G.MAX_HIDDEN), ("MAX_ROWS", G.MAX_ROWS)):
         assert int(re.search(rf"#define RNNOISE_AMD_GRU_{macro} (\d+)", src)[1]) == value, macro
     assert G.MIN_HIDDEN <= 16 and G.MAX_HIDDEN >= 1024 and G.TILE == 16
-    assert _fields("RNNoiseGruSeq") == list(G.Seq._fields_)
-    assert _fields("RNNoiseGruSeqGrad") == list(G.SeqGrad._fields_)
+    assert _fields(HEADER, "RNNoiseGruSeq") == list(G.Seq._fields_)
+    assert _fields(HEADER, "RNNoiseGruSeqGrad") == list(G.SeqGrad._fields_)
 
 
 def test_library_exports_the_header_and_nothing_else():
@@ -117,12 +98,7 @@ def test_two_kernels_of_its_own_and_nothing_shared():
     assert "librnnoise" not in ldd
     assert "rnnoise_amd_gru" not in open(os.path.join(ROOT, "include", "rnnoise_amd.h")).read()
     assert not [n for n in capi.PROTOTYPES if "amd_gru" in n]
-    mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    for var in ("SRCS", "ISRCS", "FLAGS", "HDRS", "TRAIN_FLAGS", "SCORE_FLAGS"):
-        assert "gru_seq" not in re.search(rf"^{var}\s*:=\s*(.*)$", mk, re.M)[1], var
-    assert "-ffp-contract=off" in re.search(r"^GRU_FLAGS\s*:=\s*(.*)$", mk, re.M)[1]
-    text = open(os.path.join(PKG, "csrc", "gru", "gru_seq.hip")).read()
-    assert not re.findall(r'#include "\.\./', text) and "getenv" not in text
+    assert_shares_only_the_two_headers(PKG, os.path.join("gru", "gru_seq.hip"), "rnnoise_amd_gru.h")
 
 
 # ---- the argument checks ----
@@ -251,10 +227,6 @@ def test_load_checkpoint_leaves_the_default(tmp_path):
     path = str(tmp_path / "ck.pth")
     torch.save(dict(state_dict=net.state_dict(), model_kwargs=dict(cond_size=8, gru_size=16)), path)
     assert float_net.load_checkpoint(path).gru_impl == "torch"
-
-
-def _injected_loss(gains, vad, records, gamma):
-    return R.trainer_loss(gains, vad, records[:, 3:-1, R.FEATURES:R.FEATURES + R.BANDS], records[:, 3:-1, R.REC - 1:], gamma)
 
 
 def test_fit_with_gru_torch_is_fit_without_the_argument(tmp_path):

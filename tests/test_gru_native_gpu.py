@@ -20,16 +20,11 @@ import torch
 
 import train_loss_ref as R
 from conftest import assert_bits_equal
+from gru_cases import DEV, FILL, filled, lay, net_outputs, ratios, slot_mask, u32
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUTPUTS = ("y", "dgi", "dh0", "dW_hh", "db_hh")
-FILL = 0x7A5A5A5A  # the guard word: a float no kernel here computes
-
-
-def u32(t):
-    return t.detach().contiguous().cpu().numpy().view(np.uint32)
 
 
 def problem(N, T, H, with_h0, seed=0):
@@ -69,12 +64,6 @@ def torch_gru32(p):
     return dict(y=y.detach(), dgi=x.grad, dh0=dh0, dW_hh=gru.weight_hh_l0.grad, db_hh=gru.bias_hh_l0.grad)
 
 
-def lay(t, frame_major):
-    """a device copy of a [N, T, W] tensor: contiguous batch-first, or a transposed view of a [T, N, W] one"""
-    t = t.to(DEV)
-    return t.transpose(0, 1).contiguous().transpose(0, 1) if frame_major else t.contiguous()
-
-
 def native32(p, frame_major=False):
     """the two device calls on their own (dhT goes into the backward call as it is), and the wrapper's weight gradients"""
     from rnnoise_amd import gru_native as G
@@ -88,20 +77,6 @@ def native32(p, frame_major=False):
     assert y.data_ptr() == y_buf.data_ptr() and dgi.data_ptr() == dgi_buf.data_ptr()  # written where they lie
     dW, db = G.weight_grads(dgh, y, h0)
     return dict(y=y, dgi=dgi, dh0=dh0, dW_hh=dW, db_hh=db, saved=saved, dgh=dgh)
-
-
-def ratios(native, other, want, names=OUTPUTS):
-    """per output: e_native / max(e_torch, 2^-23 max |X64|)"""
-    out = {}
-    for k in names:
-        if want[k] is None or native[k] is None or other[k] is None:
-            continue
-        w = want[k]
-        e_n = float((native[k].detach().cpu().double() - w).abs().max())
-        e_t = float((other[k].detach().cpu().double() - w).abs().max())
-        assert np.isfinite(e_n) and np.isfinite(e_t), k
-        out[k] = e_n / max(e_t, 2.0 ** -23 * float(w.abs().max()), 1e-300)
-    return out
 
 
 WORST = {}
@@ -119,7 +94,7 @@ def test_parity_with_float64_beside_torch(H, N):
             got, other = native32(p, frame_major), torch_gru32(p)
             if not with_h0:
                 want["dh0"] = None  # torch has none to show; the library's is checked in the cuts below
-            r = ratios(got, other, want)
+            r = ratios(got, other, want, OUTPUTS)
             for k, v in r.items():
                 WORST[k] = max(WORST.get(k, 0.0), v)
                 assert v <= 4.0, (k, v, H, N, T, with_h0, frame_major)
@@ -184,18 +159,6 @@ def test_cuts_give_the_bits_of_one_call():
     assert y0.shape == (N, 0, H)
     _, _, dh_same = G.sequence_backward(dy[:, :0], y[:, :0], torch.zeros(4, device=DEV), w, None, dh)
     assert torch.equal(dh_same, dh)
-
-
-def filled(n):
-    return torch.full((n,), FILL, dtype=torch.int32, device=DEV).view(torch.float32)
-
-
-def slot_mask(total, off, fs, rs, T, N, M):
-    m = np.zeros(total, bool)
-    for t in range(T):
-        for s in range(N):
-            m[off + t * fs + s * rs: off + t * fs + s * rs + M] = True
-    return m
 
 
 @pytest.mark.parametrize("N,T,H", [(17, 3, 48), (5, 2, 16), (16, 4, 48)])
@@ -268,15 +231,6 @@ def test_a_poisoned_row_poisons_only_itself(N, row):
 
 
 # ---- the network ----
-def net_outputs(net, x, A, B):
-    gains, vad = net.forward_sequence(x)
-    net.zero_grad()
-    ((gains * A).sum() + (vad * B).sum()).backward()
-    out = dict(gains=gains.detach(), vad=vad.detach())
-    out.update({f"d {k}": v.grad.detach().clone() for k, v in net.named_parameters()})
-    return out
-
-
 @pytest.mark.parametrize("cond,gru,N,T", [(16, 32, 4, 24), (128, 384, 3, 12)])
 def test_float_net_native_beside_torch(cond, gru, N, T):
     """gains, vad and every parameter gradient of (gains A).sum() + (vad B).sum(): the bound, X64 the float64 CPU net"""

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import train_loss_ref as R
+from gru_cases import _declarations, _fields, _injected_loss, assert_shares_only_the_two_headers
 from rnnoise_amd import capi, float_net, train
 from rnnoise_amd import gru_native
 from rnnoise_amd import gru_stack as S
@@ -73,31 +74,8 @@ def test_reference_formulas_against_three_nn_gru_in_float64(N, T, H, with_states
 
 
 # ---- the surface ----
-def _declarations():
-    src = open(HEADER).read()
-    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-    return [(" ".join(ret.split()), name, " ".join(params.split()))
-            for ret, name, params in re.findall(r"RNNOISE_EXPORT\s+([\w\s\*]+?)\b(rnnoise_\w+)\s*\(([^()]*)\)\s*;", src)]
-
-
-def _fields(struct):
-    """(name, ctypes type) of every field of a struct of the header; name[3] is an array of three"""
-    src = open(HEADER).read()
-    body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", src, re.S)[1]
-    fields = []
-    for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";"):
-        if decl.strip():
-            kind = re.match(r"\s*(const float|float|long|int)\b", decl)[1]
-            for f in decl.strip()[len(kind):].split(","):
-                f = f.strip()
-                base = C.c_void_p if f.startswith("*") else {"long": C.c_long, "int": C.c_int}[kind]
-                name, count = re.match(r"\*?(\w+)(?:\[(\d+)\])?$", f).groups()
-                fields.append((name, base * int(count) if count else base))
-    return fields
-
-
 def test_prototype_table_matches_the_header():
-    decl = _declarations()
+    decl = _declarations(HEADER)
     assert [d[1] for d in decl] == list(S.PROTOTYPES) == S.EXPORTS and len(decl) == 5
     assert S.EXPORTS == ["rnnoise_amd_gru_stack_check", "rnnoise_amd_gru_stack_grad_check", "rnnoise_amd_gru_stack_workspace",
                          "rnnoise_amd_gru_stack_forward_device", "rnnoise_amd_gru_stack_backward_device"]
@@ -114,8 +92,8 @@ def test_prototype_table_matches_the_header():
     assert (S.TILE, S.MIN_HIDDEN, S.MAX_HIDDEN, S.MAX_ROWS) == (gru_native.TILE, gru_native.MIN_HIDDEN, gru_native.MAX_HIDDEN, gru_native.MAX_ROWS)
     same = lambda a, b: [(n, (t._type_, t._length_) if hasattr(t, "_length_") else t) for n, t in a] == \
                         [(n, (t._type_, t._length_) if hasattr(t, "_length_") else t) for n, t in b]
-    assert same(_fields("RNNoiseGruStack"), S.Stack._fields_)
-    assert same(_fields("RNNoiseGruStackGrad"), S.StackGrad._fields_)
+    assert same(_fields(HEADER, "RNNoiseGruStack"), S.Stack._fields_)
+    assert same(_fields(HEADER, "RNNoiseGruStackGrad"), S.StackGrad._fields_)
 
 
 def test_library_exports_the_header_and_nothing_else():
@@ -141,12 +119,9 @@ def test_two_kernels_of_its_own_and_nothing_shared():
         assert "gru_stack" not in open(os.path.join(ROOT, "include", header)).read(), header
     assert not [n for n in list(capi.PROTOTYPES) + list(gru_native.PROTOTYPES) if "gru_stack" in n]
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    for var in ("SRCS", "ISRCS", "FLAGS", "HDRS", "TRAIN_FLAGS", "SCORE_FLAGS", "GRU_FLAGS"):
-        assert "gru_stack" not in re.search(rf"^{var}\s*:=\s*(.*)$", mk, re.M)[1], var
-    assert "-ffp-contract=off" in re.search(r"^GRU_STACK_FLAGS\s*:=\s*(.*)$", mk, re.M)[1]
     assert "build_gru_stack" in re.search(r"^clean:\n\t(.*)$", mk, re.M)[1] and "librnnoise_amd_gru_stack.so" in re.search(r"^all:(.*)$", mk, re.M)[1]
-    text = open(os.path.join(PKG, "csrc", "gru_stack", "gru_stack.hip")).read()
-    assert not re.findall(r'#include "\.\./', text) and "getenv" not in text and "rnnoise_amd_gru.h" not in text
+    assert_shares_only_the_two_headers(PKG, os.path.join("gru_stack", "gru_stack.hip"), "rnnoise_amd_gru_stack.h")
+    assert "rnnoise_amd_gru.h" not in open(os.path.join(PKG, "csrc", "gru_stack", "gru_stack.hip")).read()
 
 
 # ---- the argument checks ----
@@ -298,16 +273,17 @@ def test_workspace_sizes_are_the_documented_formulas():
 
 # ---- the launch schedule on the host, under the sanitizers ----
 def test_launch_schedule_reads_what_an_earlier_launch_wrote(tmp_path):
-    """tests/csrc/gru_stack_main.cpp: the unit's host half as plain C++ with every launch handed to a model of the memory -- which
-    layer runs which step in launch s, what it reads and writes, and that the kernel boundary is ordering enough; with the address
-    and undefined-behaviour sanitizers on the host code"""
+    """tests/csrc/gru_stack_main.cpp: the unit's host half (and the gru library's, as a stack of one layer) as plain C++ with every
+    launch handed to a model of the memory -- which layer runs which step in launch s, what it reads and writes, and that the kernel
+    boundary is ordering enough; with the address and undefined-behaviour sanitizers on the host code"""
     exe = str(tmp_path / "gru_stack_main")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
                     "-Wno-unknown-pragmas", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "csrc"),
-                    "-I", os.path.join(PKG, "csrc", "gru_stack"), os.path.join(ROOT, "tests", "csrc", "gru_stack_main.cpp"), "-o", exe], check=True)
+                    "-I", os.path.join(PKG, "csrc", "gru_stack"), "-I", os.path.join(PKG, "csrc", "gru"),
+                    os.path.join(ROOT, "tests", "csrc", "gru_stack_main.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    assert r.stdout.strip() == "ok 96"
+    assert r.stdout.strip() == "ok 192"  # 96 shapes, the stack and the single layer on each
 
 
 # ---- the switch ----
@@ -338,10 +314,6 @@ def test_load_checkpoint_leaves_the_default(tmp_path):
     path = str(tmp_path / "ck.pth")
     torch.save(dict(state_dict=net.state_dict(), model_kwargs=dict(cond_size=8, gru_size=16)), path)
     assert float_net.load_checkpoint(path).gru_impl == "torch"
-
-
-def _injected_loss(gains, vad, records, gamma):
-    return R.trainer_loss(gains, vad, records[:, 3:-1, R.FEATURES:R.FEATURES + R.BANDS], records[:, 3:-1, R.REC - 1:], gamma)
 
 
 def test_fit_stack_raises_on_the_cpu(tmp_path):

@@ -21,17 +21,12 @@ import torch
 
 import train_loss_ref as R
 from conftest import assert_bits_equal
+from gru_cases import DEV, FILL, filled, lay, net_outputs, ratios, slot_mask, u32
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L3 = range(3)
 OUTPUTS = tuple(f"{k}{l}" for k in ("y", "dh0_", "dW_hh", "db_hh") for l in L3) + ("dgi0", "dW_ih1", "dW_ih2", "db_ih1", "db_ih2")
-FILL = 0x7A5A5A5A  # the guard word: a float no kernel here computes
-
-
-def u32(t):
-    return t.detach().contiguous().cpu().numpy().view(np.uint32)
 
 
 def problem(N, T, H, with_states, seed=0):
@@ -97,12 +92,6 @@ def torch_grus32(p):
     return named([y.detach() for y in ys], out)
 
 
-def lay(t, frame_major):
-    """a device copy of a [N, T, W] tensor: contiguous batch-first, or a transposed view of a [T, N, W] one"""
-    t = t.to(DEV)
-    return t.transpose(0, 1).contiguous().transpose(0, 1) if frame_major else t.contiguous()
-
-
 def stack32(p, frame_major=False):
     """the two device calls on their own (dhT goes into the backward call as it is), and the wrapper's weight gradients.  Batch-first:
     y1 .. y3 are the slices 1 .. 3 of one [N, T, 4H] buffer and dy1 .. dy3 slices of another; frame-major: three buffers each."""
@@ -134,20 +123,6 @@ def stack32(p, frame_major=False):
     return res
 
 
-def ratios(got, other, want, names=OUTPUTS):
-    """per output: e_stack / max(e_torch, 2^-23 max |X64|)"""
-    out = {}
-    for k in names:
-        if want[k] is None or got[k] is None or other[k] is None:
-            continue
-        w = want[k]
-        e_n = float((got[k].detach().cpu().double() - w).abs().max())
-        e_t = float((other[k].detach().cpu().double() - w).abs().max())
-        assert np.isfinite(e_n) and np.isfinite(e_t), k
-        out[k] = e_n / max(e_t, 2.0 ** -23 * float(w.abs().max()), 1e-300)
-    return out
-
-
 WORST = {}
 
 
@@ -162,7 +137,7 @@ def test_parity_with_float64_beside_torch(H, N):
             p = problem(N, T, H, with_states)
             want = reference64(p)
             got, other = stack32(p, frame_major), torch_grus32(p)
-            r = ratios(got, other, want)
+            r = ratios(got, other, want, OUTPUTS)
             assert set(r) == set(OUTPUTS) - (set() if with_states else {"dh0_0", "dh0_1", "dh0_2"})  # (torch shows no dh0 without an h0)
             for k, v in r.items():
                 WORST[k] = max(WORST.get(k, 0.0), v)
@@ -247,16 +222,26 @@ def test_cuts_give_the_bits_of_one_call(cuts):
     assert all(torch.equal(a, b) for a, b in zip(dh_same, dh))
 
 
-def filled(n):
-    return torch.full((n,), FILL, dtype=torch.int32, device=DEV).view(torch.float32)
-
-
-def slot_mask(total, off, fs, rs, T, N, M):
-    m = np.zeros(total, bool)
-    for t in range(T):
-        for s in range(N):
-            m[off + t * fs + s * rs: off + t * fs + s * rs + M] = True
-    return m
+@pytest.mark.parametrize("H", [16, 48, 384])
+def test_one_cell_in_both_libraries(H):
+    """Both libraries compile one cell (rnnoise_amd/csrc/gru_cell.h), so where the stack does what the single layer does the bits are
+    the same: layer 1 forward is a layer that is given its gi, and layer 3 backward is a layer nobody adds a dx to (that it leaves one
+    for the layer below changes none of its own sums).  h0 and dhT given; N 17: a ragged row tile; T 3: the first length with a full
+    diagonal; H 16 and 48 have the remainder loop only, H 384 the blocks of 6, 3 and 2 chunks."""
+    from rnnoise_amd import gru_native as G, gru_stack as S
+    N, T = 17, 3
+    p = problem(N, T, H, True, seed=5)
+    d = convert(p, lambda t: t.to(DEV))
+    ys, saved = S.stack_forward(d["gi0"], d["w_ih"], d["b_ih"], d["w_hh"], d["b_hh"], d["h0"])
+    dgi, dgh, dh0 = S.stack_backward(d["dy"], ys, saved, d["w_ih"], d["w_hh"], d["h0"], d["dhT"])
+    layer = saved.view(-1)[:3 * T * N * 4 * H].view(3, T * N * 4 * H)
+    y1, saved1 = G.sequence_forward(d["gi0"], d["w_hh"][0], d["b_hh"][0], d["h0"][0])
+    assert_bits_equal(u32(ys[0]), u32(y1), "y of layer 1")
+    assert_bits_equal(u32(layer[0]), u32(saved1.view(-1)[:T * N * 4 * H]), "saved of layer 1")
+    dgi3, dgh3, dh03 = G.sequence_backward(d["dy"][2], ys[2], layer[2].contiguous(), d["w_hh"][2], d["h0"][2], d["dhT"][2])
+    assert_bits_equal(u32(dgi[2].transpose(0, 1)), u32(dgi3), "dgi of layer 3")
+    assert_bits_equal(u32(dgh[2]), u32(dgh3), "dgh of layer 3")
+    assert_bits_equal(u32(dh0[2]), u32(dh03), "dh0 of layer 3")
 
 
 @pytest.mark.parametrize("N,T,H", [(17, 3, 48), (5, 2, 16), (16, 4, 48)])
@@ -359,15 +344,6 @@ def test_a_poisoned_row_poisons_only_itself(N, row):
 
 
 # ---- the network ----
-def net_outputs(net, x, A, B):
-    gains, vad = net.forward_sequence(x)
-    net.zero_grad()
-    ((gains * A).sum() + (vad * B).sum()).backward()
-    out = dict(gains=gains.detach(), vad=vad.detach())
-    out.update({f"d {k}": v.grad.detach().clone() for k, v in net.named_parameters()})
-    return out
-
-
 @pytest.mark.parametrize("cond,gru,N,T", [(16, 32, 4, 24), (128, 384, 3, 12)])
 def test_float_net_stack_beside_torch(cond, gru, N, T):
     """gains, vad and every parameter gradient of (gains A).sum() + (vad B).sum(): the bound, X64 the float64 CPU net"""
