@@ -52,7 +52,7 @@ training sequences are generated on the device as dump-features generates them, 
 librnnoise_amd_score.so -- a table of SNR, SI-SDR and segmental SNR in dB per model, and every later model's difference to the first:
 
   python -m rnnoise_amd.cli eval-audio speech.pcm noise.pcm fgnoise.pcm --model a.blob [--model b.blob] [--checkpoint ckpt.pth]
-         [--torch-net net.pt] --count N [--frames T] [--rir-list FILE] [--seed S] [--streams N]
+         [--torch-net net.pt] --count N [--frames T] [--rir-list FILE] [--seed S] [--streams N] [--stoi]
 
 Training (rnnoise_amd/train.py): the loop of the reference's torch/rnnoise/train_rnnoise.py with its options, the loss
 and its gradient computed by librnnoise_amd_train.so in the doubles eval-records prints; one checkpoint per epoch under
@@ -331,26 +331,32 @@ AUDIO_COLUMNS = (("snr_in", "SNR in"), ("snr_out", "SNR out"), ("snr_gain", "gai
                  ("si_sdr_out", "SI-SDR out"), ("si_sdr_gain", "gain"), ("seg_snr_in", "segSNR in"), ("seg_snr_out", "segSNR out"))
 
 
-def audio_table(names, results) -> str:
+STOI_COLUMNS = (("stoi_in", "STOI in"), ("stoi_out", "STOI out"), ("estoi_in", "ESTOI in"), ("estoi_out", "ESTOI out"))
+
+
+def audio_table(names, results, stoi: bool = False) -> str:
     """the table of eval-audio: one row per model with the means over its sequences in dB (audio_score.summary's keys), the
-    sequences scored and left out (zero clean energy); then, for every model after the first, a row of differences to the first"""
+    sequences scored and left out (zero clean energy); then, for every model after the first, a row of differences to the first.
+    stoi: four more columns, the means of STOI and ESTOI (rnnoise_amd.stoi) of the noisy and of the denoised signal"""
     width = max([len("model")] + [len(n) + 2 for n in names])
     cell = lambda v: f"{v:>10.3f}"
-    lines = [f"{'model':<{width}} {'seqs':>6} {'left out':>8} " + " ".join(f"{title:>10}" for _key, title in AUDIO_COLUMNS)]
+    columns = AUDIO_COLUMNS + (STOI_COLUMNS if stoi else ())
+    lines = [f"{'model':<{width}} {'seqs':>6} {'left out':>8} " + " ".join(f"{title:>10}" for _key, title in columns)]
     for n, r in zip(names, results):
-        lines.append(f"{n:<{width}} {r['sequences']:>6d} {r['excluded']:>8d} " + " ".join(cell(r[k]) for k, _ in AUDIO_COLUMNS))
+        lines.append(f"{n:<{width}} {r['sequences']:>6d} {r['excluded']:>8d} " + " ".join(cell(r[k]) for k, _ in columns))
     for n, r in zip(names[1:], results[1:]):
         with np.errstate(invalid="ignore"):  # (inf - inf where both outputs are exact: nan)
-            diff = [np.float64(r[k]) - np.float64(results[0][k]) for k, _ in AUDIO_COLUMNS]
+            diff = [np.float64(r[k]) - np.float64(results[0][k]) for k, _ in columns]
         lines.append(f"{'d ' + n:<{width}} {'':>6} {'':>8} " + " ".join(cell(v) for v in diff))
     return "\n".join(lines)
 
 
 def eval_audio_files(speech: str, noise: str, fgnoise: str, models, count: int, frames: int = 2000, checkpoint=None, torch_net=None,
-                     rir_list=None, seed=None, streams: int = 64, device: int = 0, rir_work_mb: int = 256):
+                     rir_list=None, seed=None, streams: int = 64, device: int = 0, rir_work_mb: int = 256, stoi: bool = False):
     """eval-audio: `count` sequences of `frames` frames drawn as dump_features draws them (the same generator and seed give the
     same sequences), through every blob of `models` (paths) and the float networks named -> (names, evaluate.evaluate_audio's
-    results).  Without a blob the DSP runs on the blob the checkpoint exports to."""
+    results).  Without a blob the DSP runs on the blob the checkpoint exports to.  stoi: every result also has the means of STOI and
+    ESTOI (evaluate.evaluate_audio's stoi)."""
     import torch
 
     from . import evaluate, train_data
@@ -383,7 +389,7 @@ def eval_audio_files(speech: str, noise: str, fgnoise: str, models, count: int, 
         loader.close()
         model.close()
     res = evaluate.evaluate_audio(corpora, blobs, draws, frames, rirs=rirs, nets=nets, net_blob=net_blob, streams=streams,
-                                  device=device, rir_work_bytes=rir_work_mb << 20)
+                                  device=device, rir_work_bytes=rir_work_mb << 20, stoi=stoi)
     return names, res
 
 
@@ -460,6 +466,8 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--streams", type=int, default=64, help="sequences per round: the batch size (the numbers do not depend on it)")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--stoi", action="store_true",
+                   help="also STOI and ESTOI of the noisy and of the denoised signal (librnnoise_amd_stoi.so): four more columns")
     p.add_argument("speech")
     p.add_argument("noise")
     p.add_argument("fgnoise")
@@ -498,10 +506,13 @@ def main(argv=None):
             ap.error("eval-audio: --model, --checkpoint or --torch-net")
         if a.count < 1 or a.frames < 3:
             ap.error("eval-audio: --count at least 1, --frames at least 3 (the first two output frames are not scored)")
+        if a.stoi and a.frames > 8192:
+            ap.error("eval-audio: --stoi takes sequences of at most 8192 frames (RNNOISE_AMD_STOI_MAX_FRAMES)")
         names, res = eval_audio_files(a.speech, a.noise, a.fgnoise, a.model or [], a.count, a.frames, a.checkpoint, a.torch_net,
-                                      a.rir_list, a.seed, a.streams, a.device)
+                                      a.rir_list, a.seed, a.streams, a.device,
+                                      **(dict(stoi=True) if a.stoi else {}))  # (the default run's arguments are what they were before the flag)
         print(f"eval-audio: {a.count} sequences of {a.frames} frames, seed {a.seed}, delay 960 samples, first scored frame 2")
-        print(audio_table(names, res))
+        print(audio_table(names, res, a.stoi))
         return
     if a.cmd == "export":
         from . import export

@@ -1,4 +1,4 @@
-// side_host.h -- what the host halves of the four side libraries (score/, train/, gru/, gru_stack/) have in common: the argument
+// side_host.h -- what the host halves of the side libraries (score/, train/, gru/, gru_stack/, stoi/) have in common: the argument
 // checks on slots and buffers, and the device guard of their *_device calls.  Plain C++; every library still compiles it into its own
 // object.  The device part needs HIP's names, so it is there under hipcc and behind a test shim that supplies them (RN_SIDE_HIP_SHIM:
 // tests/csrc/gru_stack_shim.h); the including unit says who speaks in the messages:

@@ -163,7 +163,7 @@ def evaluate_checkpoint(path_or_array, checkpoint, sequence_length: int = 2000, 
 
 
 def evaluate_audio(corpora, models, draws, n_frames: int, rirs=None, nets=(), net_blob=None, streams: int = 64, device: int = 0,
-                   vad: str = "auto", first: int = 2, delay: int = None, rir_work_bytes: int = 256 << 20, tap=None):
+                   vad: str = "auto", first: int = 2, delay: int = None, rir_work_bytes: int = 256 << 20, tap=None, stoi: bool = False):
     """Denoises the sequences of `draws` (train_data.draw) and scores the result against their clean signals, on the device.
     corpora: (speech, noise, fgnoise), 1-D int16 torch tensors on cuda:`device`.  models: blobs (bytes) or capi.Model objects, each
     run by a batch of `streams` streams; nets: torch modules mapping features (N, T, 65) to (gains (N, T, 32), vad (N, T, 1)) -- a
@@ -177,10 +177,18 @@ def evaluate_audio(corpora, models, draws, n_frames: int, rirs=None, nets=(), ne
     (n_frames, N, 480) plane per denoiser -- valid during the call.
     -> one dict per denoiser, models first: audio_score.summary's means (snr_in, snr_out, snr_gain, si_sdr_in, si_sdr_out,
     si_sdr_gain, seg_snr_in, seg_snr_out, sequences, excluded), sums (S, 8), frame_terms (S, n_frames, 8), active (S, n_frames) --
-    vad_target moved to the output frames -- and per_sequence, audio_score.metrics' dict."""
+    vad_target moved to the output frames -- and per_sequence, audio_score.metrics' dict.
+    stoi: every dict also has stoi_in, stoi_out, estoi_in, estoi_out -- the means of STOI and ESTOI over the sequences that have a
+    segment (rnnoise_amd.stoi, include/rnnoise_amd_stoi.h; same planes, first and delay) --, stoi_results (S, 8) and stoi_per_sequence,
+    stoi.metrics' dict.  The noisy side is computed with the first denoiser and reused for the others.  Without it
+    librnnoise_amd_stoi.so is not loaded."""
     import torch
 
     from . import audio_score, train_data
+    if stoi:
+        from . import stoi as stoi_lib
+        if n_frames > stoi_lib.MAX_FRAMES:  # (before anything is generated or denoised)
+            raise ValueError(f"stoi: sequences of {n_frames} frames; the library takes at most {stoi_lib.MAX_FRAMES}")
     from .torch_op import RNNoiseOp
     delay = audio_score.DELAY if delay is None else delay
     if not models and not nets:
@@ -198,6 +206,7 @@ def evaluate_audio(corpora, models, draws, n_frames: int, rirs=None, nets=(), ne
     D = len(handles) + len(ops)
     sums = [np.zeros((S, audio_score.SLOTS), np.float64) for _ in range(D)]
     terms = [np.zeros((S, T, audio_score.SLOTS), np.float64) for _ in range(D)]
+    stoi_res = [np.zeros((S, 8), np.float64) for _ in range(D)] if stoi else None
     active = np.zeros((S, T), np.float32)
     shift = (delay + audio_score.FRAME // 2) // audio_score.FRAME  # frames by which the output lags the input
     fs, rs = audio_score.layout_frames(N)
@@ -229,6 +238,11 @@ def evaluate_audio(corpora, models, draws, n_frames: int, rirs=None, nets=(), ne
                                          (out.data_ptr(), out.stride(0), out.stride(1)), k, 0, T, first, delay,
                                          d_terms.data_ptr(), T, device, st.cuda_stream)
                 sums[i][s0:s0 + k], terms[i][s0:s0 + k] = d_sums[:k].cpu().numpy(), d_terms[:k].cpu().numpy()  # (waits for the stream)
+                if stoi:
+                    r = stoi_lib.score(clean[:, :k], noisy[:, :k] if i == 0 else None, out[:, :k], T, first, delay, device)
+                    if i > 0:
+                        r[:, :4] = stoi_res[0][s0:s0 + k, :4]
+                    stoi_res[i][s0:s0 + k] = r
             active[s0:s0 + k, shift:] = vad_target[:T - shift, :k].t().cpu().numpy() if shift < T else 0
             if tap is not None:
                 tap(s0, k, clean, noisy, planes)
@@ -244,4 +258,10 @@ def evaluate_audio(corpora, models, draws, n_frames: int, rirs=None, nets=(), ne
     for i in range(D):
         per = audio_score.metrics(sums[i], terms[i], active)
         res.append(dict(**audio_score.summary(per), sums=sums[i], frame_terms=terms[i], active=active, per_sequence=per))
+        if stoi:
+            m = stoi_lib.metrics(stoi_res[i])
+            res[-1].update({k: m["summary"][k] for k in stoi_lib.METRIC_KEYS}, stoi_results=stoi_res[i], stoi_per_sequence=m)
     return res
+
+
+eval_audio = evaluate_audio
