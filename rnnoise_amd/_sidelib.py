@@ -1,5 +1,5 @@
-"""Loading a side library (librnnoise_amd_score.so, _train.so, _gru.so, _gru_stack.so, _stoi.so): each is a library of its own with a
-prototype table of its own in its module; how it is loaded is the same for all five."""
+"""Loading a side library (librnnoise_amd_score.so, _train.so, _gru.so, _gru_stack.so, _stoi.so, _fnet.so): each is a library of its
+own with a prototype table of its own in its module; how it is loaded is the same for all six."""
 from __future__ import annotations
 
 import ctypes as C

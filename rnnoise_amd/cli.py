@@ -41,6 +41,7 @@ From the trainer's checkpoint to the served blob (rnnoise_amd/export.py, float_n
   python -m rnnoise_amd.cli export ckpt.pth out.blob [--densities R,Z,N] [--pack]
   python -m rnnoise_amd.cli eval-records validation.f32 --model out.blob --checkpoint ckpt.pth
   python -m rnnoise_amd.cli denoise --checkpoint ckpt.pth --out-dir out a.raw ...
+  python -m rnnoise_amd.cli denoise --checkpoint ckpt.pth --float-net native --model a.blob --out-dir out a.raw ...
 export writes the "DNNw" blob the reference's exporter and writer make of the checkpoint, byte for byte (--densities: block-sparsified
 first, as the trainer does it; --pack: the GPU-native RNPK form).  eval-records --checkpoint scores the float checkpoint beside the
 blobs with the same scoring code, and prints every blob's difference to it and the 32 per-band means of the gain loss of each.
@@ -100,7 +101,7 @@ def out_info(info: wav.WavInfo, out_rate=None, out_format=None) -> wav.WavInfo:
 def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 100, device: int = 0,
                   vad_csv: bool = False, rate: int = 48000, atten_limit_db=None, vad_gate: float = 0.0, vad_hold: int = 0, rates=None,
                   formats=None, link_channels: bool = False, out_rate=None, out_format=None, torch_net=None, max_store_gb: float = 4.0,
-                  checkpoint=None):
+                  checkpoint=None, float_net: str = "torch"):
     """Streams the files through the batch chunk by chunk: at most `chunk_frames` frames of every file are in host memory
     at a time (two staging buffers, reused), whatever the file lengths.  rate: the files' sample rate (48000, 32000, 24000, 16000 or
     8000: 10 ms frames of 480 * rate // 48000 samples, resampled on the device).  atten_limit_db / vad_gate / vad_hold: the suppression
@@ -120,7 +121,8 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     goes through ONE pair, whole -- a module's state need not survive a call -- and the call is refused (ValueError, before anything
     runs) where the pending frames would need more than max_store_gb GiB of device memory (capi.split_frame_bytes).
     checkpoint: a trainer checkpoint instead: rnnoise_amd.float_net's streaming module on the batch's device goes the same way (reset
-    in front of every group of files); max_store_gb applies.
+    in front of every group of files); max_store_gb applies.  float_net: what runs that checkpoint's network -- "torch": the module;
+    "native": rnnoise_amd.fnet.FloatNetRuntime on librnnoise_amd_fnet.so, any cond_size / gru_size the library takes.
     Returns the frames of every input."""
     os.makedirs(out_dir, exist_ok=True)
     if rates is not None and len(rates) != len(inputs):
@@ -146,6 +148,10 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
     net = None
     if torch_net is not None and checkpoint is not None:
         raise ValueError("--torch-net and --checkpoint both name the network")
+    if float_net not in ("torch", "native"):
+        raise ValueError(f'float_net: "torch" or "native", not {float_net!r}')
+    if float_net == "native" and checkpoint is None:
+        raise ValueError("--float-net native runs a --checkpoint")
     if torch_net is not None or checkpoint is not None:
         for channels, group in groups.items():
             frames, n = max([d["n_frames"] for d in group] + [0]), len(group) * channels
@@ -153,9 +159,12 @@ def denoise_files(model_blob: bytes, inputs, out_dir: str, chunk_frames: int = 1
             if need > max_store_gb * 2 ** 30:
                 raise ValueError(f"--torch-net / --checkpoint: {frames} pending frames of {n} streams need {need / 2 ** 30:.2f} GiB of device memory, "
                                  f"above --max-store-gb {max_store_gb}")
-        if checkpoint is not None:
-            from . import float_net
-            net = float_net.load_checkpoint(checkpoint, device=f"cuda:{device}")
+        if checkpoint is not None and float_net == "native":
+            from . import fnet
+            net = fnet.FloatNetRuntime(checkpoint, device=device)
+        elif checkpoint is not None:
+            from . import float_net as float_net_module
+            net = float_net_module.load_checkpoint(checkpoint, device=f"cuda:{device}")
         else:
             import torch
             net = torch.jit.load(torch_net, map_location=f"cuda:{device}").eval()
@@ -352,11 +361,13 @@ def audio_table(names, results, stoi: bool = False) -> str:
 
 
 def eval_audio_files(speech: str, noise: str, fgnoise: str, models, count: int, frames: int = 2000, checkpoint=None, torch_net=None,
-                     rir_list=None, seed=None, streams: int = 64, device: int = 0, rir_work_mb: int = 256, stoi: bool = False):
+                     rir_list=None, seed=None, streams: int = 64, device: int = 0, rir_work_mb: int = 256, stoi: bool = False,
+                     float_net: str = "torch"):
     """eval-audio: `count` sequences of `frames` frames drawn as dump_features draws them (the same generator and seed give the
     same sequences), through every blob of `models` (paths) and the float networks named -> (names, evaluate.evaluate_audio's
     results).  Without a blob the DSP runs on the blob the checkpoint exports to.  stoi: every result also has the means of STOI and
-    ESTOI (evaluate.evaluate_audio's stoi)."""
+    ESTOI (evaluate.evaluate_audio's stoi).  float_net: "torch" runs the checkpoint's network as the torch module, "native" as
+    rnnoise_amd.fnet.FloatNetRuntime on librnnoise_amd_fnet.so."""
     import torch
 
     from . import evaluate, train_data
@@ -366,9 +377,18 @@ def eval_audio_files(speech: str, noise: str, fgnoise: str, models, count: int, 
     draws = train_data.draw(rng, count, [c.numel() for c in corpora], frames)
     blobs = [open(m, "rb").read() for m in models]
     names, nets, net_blob = list(models), [], blobs[0] if blobs else None
+    if float_net not in ("torch", "native"):
+        raise ValueError(f'float_net: "torch" or "native", not {float_net!r}')
+    if float_net == "native" and checkpoint is None:
+        raise ValueError("--float-net native runs a --checkpoint")
     if checkpoint is not None:
-        from . import export, float_net
-        nets.append(float_net.load_checkpoint(checkpoint, device=f"cuda:{device}"))
+        from . import export
+        if float_net == "native":
+            from . import fnet
+            nets.append(fnet.FloatNetRuntime(checkpoint, device=device))
+        else:
+            from . import float_net as float_net_module
+            nets.append(float_net_module.load_checkpoint(checkpoint, device=f"cuda:{device}"))
         names.append(checkpoint)
         if net_blob is None:
             net_blob = export.blob_from_state_dict(export.load_state_dict_file(checkpoint))
@@ -423,6 +443,9 @@ def main(argv=None):
                    help="trainer checkpoint (.pth): its float network replaces the blob's network (split calls; one pair per file group)")
     p.add_argument("--max-store-gb", type=float, default=4.0,
                    help="--torch-net / --checkpoint: device memory the pending frames may take, in GiB")
+    p.add_argument("--float-net", choices=("torch", "native"), default="torch",
+                   help="what runs --checkpoint's network: the torch module (default), or native: this project's own kernels "
+                        "(librnnoise_amd_fnet.so), any cond_size / gru_size the library takes")
     p.add_argument("inputs", nargs="+")
     p = sub.add_parser("dump-features")
     p.add_argument("--model", required=True, help='"DNNw" weight blob: a batch needs one (the extraction runs no network)')
@@ -460,6 +483,9 @@ def main(argv=None):
     p.add_argument("--model", default=None, action="append", help='"DNNw" weight blob; repeat to score several on the same sequences')
     p.add_argument("--checkpoint", default=None, help="trainer checkpoint (.pth): its float network between the split calls")
     p.add_argument("--torch-net", default=None, help="TorchScript module [N,T,65] -> ([N,T,32], [N,T,1]) between the split calls")
+    p.add_argument("--float-net", choices=("torch", "native"), default="torch",
+                   help="what runs --checkpoint's network: the torch module (default), or native: this project's own kernels "
+                        "(librnnoise_amd_fnet.so), any cond_size / gru_size the library takes")
     p.add_argument("--count", type=int, required=True, help="sequences to generate and score")
     p.add_argument("--frames", type=int, default=2000, help="frames per sequence (the trainer: 2000)")
     p.add_argument("--rir-list", default=None, help="file of RIR file names, one per line (raw float32): the reference's -rir_list")
@@ -506,11 +532,14 @@ def main(argv=None):
             ap.error("eval-audio: --model, --checkpoint or --torch-net")
         if a.count < 1 or a.frames < 3:
             ap.error("eval-audio: --count at least 1, --frames at least 3 (the first two output frames are not scored)")
+        if a.float_net == "native" and a.checkpoint is None:
+            ap.error("eval-audio: --float-net native needs a --checkpoint")
         if a.stoi and a.frames > 8192:
             ap.error("eval-audio: --stoi takes sequences of at most 8192 frames (RNNOISE_AMD_STOI_MAX_FRAMES)")
         names, res = eval_audio_files(a.speech, a.noise, a.fgnoise, a.model or [], a.count, a.frames, a.checkpoint, a.torch_net,
                                       a.rir_list, a.seed, a.streams, a.device,
-                                      **(dict(stoi=True) if a.stoi else {}))  # (the default run's arguments are what they were before the flag)
+                                      **(dict(stoi=True) if a.stoi else {}),  # (the default run's arguments are what they were before the flags)
+                                      **(dict(float_net="native") if a.float_net == "native" else {}))
         print(f"eval-audio: {a.count} sequences of {a.frames} frames, seed {a.seed}, delay 960 samples, first scored frame 2")
         print(audio_table(names, res, a.stoi))
         return
@@ -552,6 +581,8 @@ def main(argv=None):
         return
     if a.model is None and a.checkpoint is None:
         ap.error("denoise: --model or --checkpoint")
+    if a.float_net == "native" and a.checkpoint is None:
+        ap.error("denoise: --float-net native needs a --checkpoint")
     if a.model is None:  # (the DSP's batch needs a blob: the one this checkpoint exports to)
         from . import export
         model_blob = export.blob_from_state_dict(export.load_state_dict_file(a.checkpoint))
@@ -559,7 +590,7 @@ def main(argv=None):
         model_blob = open(a.model, "rb").read()
     n = denoise_files(model_blob, a.inputs, a.out_dir, a.chunk_frames, a.device, a.vad_csv, a.rate,
                       a.atten_limit_db, a.vad_gate, a.vad_hold, a.rates, a.formats, a.link_channels, a.out_rate, a.out_format,
-                      a.torch_net, a.max_store_gb, a.checkpoint)
+                      a.torch_net, a.max_store_gb, a.checkpoint, **(dict(float_net="native") if a.float_net == "native" else {}))
     print(f"denoised {len(a.inputs)} streams, {sum(n)} frames")
 
 
